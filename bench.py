@@ -11,6 +11,11 @@ torch.distributed.run (WORLD_SIZE set) it is one of the ranks.  --gather torch (
 torch.distributed's all_gather_into_tensor (backend "nccl" = RCCL); --gather abi: the C ABI's own pt_comm_gather_frame
 (ncclAllGather + un-permute kernel inside libptrace_hip.so), torch.distributed only carrying the 128-byte id.
 
+A plain run sets up, warms up, times --steps frames, writes the last frame with --dump-outputs DIR (DIR/image.npy: the
+float32 [W*H, 3] framebuffer a caller of pt_ctx_render receives, index (H-1-y)*W + x, or a fixed sample of its pixels for
+frames above 2 Mi pixels; DIR/ray_bounces.npy: its bounce count as float64) and prints the JSON line.  --full adds what
+takes runs of its own: `variants` and `cpu_baseline` below (--no-variants / --no-cpu-baseline leave either out again).
+
 The JSON line also carries
   roofline      the dominant kernel, timed live with HIP events around each of its launches in the timed region,
                 against the 8 TB/s HBM peak.  Scenes without BVH meshes (the default) run a whole pass per launch
@@ -25,9 +30,9 @@ The JSON line also carries
   valu_roofline what does: VALU instruction issue, priced with the per-class cycle costs measured on the box
                 (tools/valu_issue_bench.hip -> profiles/r02_valu_issue_costs.json), the kernel's dynamic instruction count
                 (PMC) and its static class mix (ISA) - profiles/r02_<kernel>_traffic.json;
-  cpu_baseline  the oracle (CPU port of the reference's rayon loop; the Rust reference cannot be built in
+  cpu_baseline  (--full) the oracle (CPU port of the reference's rayon loop; the Rust reference cannot be built in
                 this image) timed on this box's host cores on a bounded sample of the same workload;
-  variants      the same frame through the persistent megakernel backend, through separate generate / intersect /
+  variants      (--full) the same frame through the persistent megakernel backend, through separate generate / intersect /
                 shade kernels (with that intersect kernel's own roofline) and through two concurrent pipelines.
 """
 import argparse
@@ -202,6 +207,27 @@ def mesh_variant(pkg, torch, dev, dev_index, seed, W=1024, H=768, spp=1024, step
     return fig
 
 
+DUMP_MAX_PIXELS = 2 << 20  # 24 MB of float32 RGB (+ 16 MB of float64 indices when sampled): under 64 MB in all
+
+
+def dump_outputs(out_dir, frame, ray_bounces):
+    """The last timed step's result as .npy files: image.npy = the float32 [W*H, 3] framebuffer; a frame of more than
+    DUMP_MAX_PIXELS pixels is written as a fixed sample instead (image_sample.npy, the rows at image_sample_pixels.npy:
+    sorted framebuffer indices drawn with seed 0, so the same for every run of the same size); ray_bounces.npy = the
+    frame's bounce count, float64 (exact below 2**53)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    img = frame.detach().to("cpu").contiguous().numpy().astype(np.float32, copy=False)
+    if img.shape[0] <= DUMP_MAX_PIXELS:
+        np.save(os.path.join(out_dir, "image.npy"), img)
+    else:
+        idx = np.sort(np.random.default_rng(0).choice(img.shape[0], size=DUMP_MAX_PIXELS, replace=False))
+        np.save(os.path.join(out_dir, "image_sample.npy"), img[idx])
+        np.save(os.path.join(out_dir, "image_sample_pixels.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "ray_bounces.npy"), np.array([ray_bounces], dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -216,8 +242,14 @@ def main():
     ap.add_argument("--backend", default="wavefront", choices=["wavefront", "megakernel"])
     ap.add_argument("--pipelines", type=int, default=1,
                     help="concurrent wavefront pipelines per GPU (opt-in; per-kernel roofline is only reported for 1)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-variants", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the variants (other backends, separate kernels, two pipelines, mesh.json) and the CPU "
+                         "baseline; a plain run times the headline workload only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the last step's frame (image.npy, float32 [W*H, 3]; a fixed sample "
+                         "of its pixels above 2 Mi pixels) and its ray bounce count (ray_bounces.npy, float64) to DIR")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--no-variants", action="store_true", help="with --full: leave the variants out")
     ap.add_argument("--separate-kernels", action="store_true",
                     help="the main run with generate / intersect / shade as separate kernels per depth (PT_FLAG_SEPARATE_KERNELS): "
                          "for profiling the stand-alone intersect kernel (tools/pmc_run.sh)")
@@ -228,6 +260,8 @@ def main():
                     help="with one rank: initialise the process group / communicator and run the all-gather anyway "
                          "(checks the RCCL path on a one-GPU box)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # Not under a launcher: start the ranks as children.  This process has not touched the GPU (no torch.cuda call,
@@ -461,7 +495,10 @@ def main():
             out["roofline"]["hbm_counter_gbs"] = out["roofline"]["traffic"] / lt / 1e9
             out["roofline"]["hbm_counter_frac"] = out["roofline"]["hbm_counter_gbs"] / HBM_PEAK_GBS
             out["valu_roofline"] = valu_figures(tr, kernel, out["roofline"]["rays_per_s"], out["roofline"]["profile_matches_binary"])
-    if rank == 0 and world == 1 and not args.no_variants:
+    if rank == 0 and args.dump_outputs:
+        # here, before a --full variant renders into the same buffer (at world size 1 the frame IS `local`)
+        dump_outputs(args.dump_outputs, main_run["image"], out["config"]["ray_bounces_per_frame"])
+    if rank == 0 and world == 1 and args.full and not args.no_variants:
         other = "megakernel" if args.backend == "wavefront" else "wavefront"
         v = timed(other, max(1, min(args.steps, 2)), 1, profile=False)
         same = bool(torch.equal(v["image"], main_run["image"]))
@@ -510,7 +547,7 @@ def main():
             # BASELINE.json's config 4 beside the headline: scenes/mesh.json (meshes/mctri.off, 810 triangles: candidate scan +
             # parked BVH walks, k_pass_cand_bvh) 1024x768 @1024 spp, so that the second kernel form gets a driver-timed number
             out["variants"]["mesh_json"] = mesh_variant(pkg, torch, dev, dev_index, args.seed)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(W, H, args.seed, args.cpu_spp)
     if rank == 0:
         print(json.dumps(out), flush=True)

@@ -1,6 +1,6 @@
 """The formats either side of the path: the product's C++ JSON/OFF loader against an independent Python
-reading of the same files, the committed scene fixtures against the reference's own data files (when the
-reference tree is mounted), and the loader's error behaviour where the reference panics."""
+reading of the same files, the committed scene fixtures against the reference's own data files (stored byte for
+byte under tests/golden/reference/), and the loader's error behaviour where the reference panics."""
 import ctypes as C
 import json
 import os
@@ -12,7 +12,8 @@ import ptlib
 
 L = ptlib.product()
 SCENES = ["single-sphere", "two-spheres", "three-spheres", "cartesian", "cornell", "mesh"]
-REF = "/root/reference"
+# the reference's data files, byte for byte: its scenes/*.json and the mesh they load (meshes/mctri.off)
+REF = os.path.join(ptlib.ROOT, "tests", "golden", "reference")
 
 
 def load_c(path, base=None):
@@ -41,7 +42,6 @@ def test_cpp_loader_equals_python_loader(sid):
     L.pt_scene_free(h)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not mounted (GPU box)")
 @pytest.mark.parametrize("sid", SCENES)
 def test_committed_fixtures_equal_reference_data(sid):
     """scenes/*.json in this repo are compact re-emissions of the reference's data files: every number must
@@ -59,7 +59,6 @@ def test_committed_fixtures_equal_reference_data(sid):
     assert f32ify(ours) == f32ify(theirs)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not mounted (GPU box)")
 def test_committed_mesh_equals_reference_mesh():
     a = ptlib.load_off_py(os.path.join(ptlib.ROOT, "meshes", "mctri.off"), 0.16)
     b = ptlib.load_off_py(os.path.join(REF, "meshes", "mctri.off"), 0.16)
@@ -198,7 +197,6 @@ def test_save_roundtrip(sid, tmp_path):
     L.pt_scene_free(h2)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not mounted (GPU box)")
 @pytest.mark.parametrize("sid", SCENES)
 def test_saved_bytes_equal_the_files_the_reference_wrote(sid, tmp_path):
     """The reference's scenes/*.json ARE outputs of SceneDescriptor::save (serde_json::to_string_pretty): loading
