@@ -246,7 +246,10 @@ int pt_ctx_intersect(pt_ctx *ctx, const float *o, const float *d, uint32_t n, fl
  * conservative filters, per-wave ring, dense exact batches; with PT_FLAG_NO_BVH every triangle per ray; scenes with BVH
  * meshes: scan + parked walks) - where pt_ctx_intersect above goes through the single-ray query kernel.  t[i] = the hit
  * distance (+inf on a miss), id[i] = -1 (miss), the object index of a sphere, or n_objs + the flattened triangle index.
- * For ray-by-ray parity tests of the scan forms (rays that start ON a triangle included). */
+ * For ray-by-ray parity tests of the scan forms (rays that start ON a triangle included).  The same precondition as
+ * pt_ctx_intersect above: bit-for-bit agreement with intersect_scene holds for directions of unit length and origins inside
+ * the bounding box of the scene's objects and camera - the conservative filters and box tests these kernels run first
+ * (pt_host.cpp) rest on error bounds that assume both. */
 int pt_ctx_intersect_streams(pt_ctx *ctx, const float *o, const float *d, uint32_t n, uint32_t flags, float *t, int32_t *id);
 
 /* SceneObjectData::intersect_bounds (mod.rs:282-290) of object `object` for n rays: a sphere is tested itself
