@@ -86,6 +86,9 @@ struct Tuning {
     uint32_t wave_stack = 0;     // PT_WAVE_STACK=n: k_pass_cand's stacks hold n slots (a power of two, 512 <= n < kWaveStackMax)
                                  // instead of kWaveStackMax - the waves then have to hold their primaries back (tests)
     uint32_t mega_items = 0;     // PT_MEGA_ITEMS=n: the megakernel cuts a round into n items per lane the chip holds (0 = default)
+    bool lds_say = false;        // PT_LDS_PAD set: the kernels that stage records in LDS say their layout on stderr (say_layout)
+    size_t lds_pad = 0;          // PT_LDS_PAD=n: k_pass_cand asks for n bytes of LDS it does not use (diagnosis: where does the
+                                 // fifth workgroup of a CU stop fitting?)
     uint32_t debug = 0;
 };
 static Tuning read_tuning() {
@@ -107,6 +110,11 @@ static Tuning read_tuning() {
     t.rays_per_pass = (uint64_t)num("PT_RAYS_PER_PASS", 0);
     t.nodes_lds = num("PT_NODES_LDS", 1) != 0;
     t.glass_defer = num("PT_GLASS_DEFER", 0) != 0;
+    t.lds_say = getenv("PT_LDS_PAD") != nullptr;
+    {
+        const long long pad = num("PT_LDS_PAD", 0);
+        t.lds_pad = pad > 0 ? (size_t)pad : 0u;
+    }
     {
         const long long mi = num("PT_MEGA_ITEMS", 0);
         t.mega_items = mi > 0 && mi <= 4096 ? (uint32_t)mi : 0u;
@@ -127,6 +135,7 @@ struct pt_ctx {
     bool has_scene = false;
     bool profiling = false;
     Tuning tune;
+    std::string lds_said[3];  // the layout line say_layout last wrote for each launcher of this context
     pt_camera cam{};
     DevScene scene{};
     DevBuf<ObjRec> d_objs;
@@ -299,6 +308,16 @@ static uint32_t cand_scan_for(const pt_ctx *c, uint32_t flags) {
     return 1u;
 }
 
+// PT_LDS_PAD set: the layout a kernel that stages records runs with (lds_layout_line, pt_layout.h), on stderr whenever it
+// differs from the last one this context said for that launcher (which: 0 launch_pass, 1 launch_intersect_cand, 2 launch_mega)
+static void say_layout(pt_ctx *c, const LdsLayout &L, int which) {
+    if (!c->tune.lds_say) return;
+    const std::string line = lds_layout_line(L, which);
+    if (line == c->lds_said[which]) return;
+    c->lds_said[which] = line;
+    fprintf(stderr, "%s\n", line.c_str());
+}
+
 double now_ms() {
     using namespace std::chrono;
     return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
@@ -414,6 +433,9 @@ int render_wavefront(pt_ctx *c, const pt_config *cfg, const FrameParams &frame, 
     F.n_streams = K;  // stream b owns pixels b, b+K, ...; accumulators are stream-major (K*m slots per channel)
     c->live_streams = K;
     c->live_m = m;
+    const LdsLayout lay = lds_layout(c->scene, m, c->tune.lds_pad);
+    if (one_kernel && (c->scene.n_bvh_nodes == 0u || c->scene.cand_scan)) say_layout(c, lay, 0);
+    if (!one_kernel && c->scene.n_bvh_nodes == 0u && c->scene.cand_scan) say_layout(c, lay, 1);
     HIP_TRY(hipMemsetAsync(c->acc.p, 0, 3 * (size_t)K * m * sizeof(unsigned long long), st));
     HIP_TRY(hipMemsetAsync(c->blk_rays.p, 0, K * sizeof(unsigned long long), st));
     HIP_TRY(hipMemsetAsync(c->flags.p, 0, sizeof(uint32_t), st));
@@ -508,7 +530,7 @@ int render_wavefront(pt_ctx *c, const pt_config *cfg, const FrameParams &frame, 
             if (c->scene.n_bvh_nodes != 0u && !c->scene.cand_scan)
                 launch_pass_bvh(st, K, c->scene, F, queue_of(c, 0), queue_of(c, 1), cap, s0, s_here, m, c->acc.p,
                                 c->blk_rays.p, c->flags.p);
-            else if (launch_pass(st, K, c->scene, F, queue_of(c, 0), queue_of(c, 1), cap, s0, s_here, m, c->acc.p, c->blk_rays.p,
+            else if (launch_pass(st, K, c->scene, lay, F, queue_of(c, 0), queue_of(c, 1), cap, s0, s_here, m, c->acc.p, c->blk_rays.p,
                                  c->flags.p) != hipSuccess)
                 return PT_ERR_HIP;  // (the message says how much LDS the scene's kernel asked for)
             if (c->profiling) {
@@ -529,11 +551,11 @@ int render_wavefront(pt_ctx *c, const pt_config *cfg, const FrameParams &frame, 
                     return PT_ERR_HIP;
                 }
                 HIP_TRY(hipEventRecord(a, st));
-                launch_intersect(st, K, c->scene, qin, c->hit.p, c->cnt.p + (size_t)d * K, cap, c->blk_rays.p);
+                launch_intersect(st, K, c->scene, lay, qin, c->hit.p, c->cnt.p + (size_t)d * K, cap, c->blk_rays.p);
                 HIP_TRY(hipEventRecord(b, st));
                 ++n_prof;
             } else {
-                launch_intersect(st, K, c->scene, qin, c->hit.p, c->cnt.p + (size_t)d * K, cap, c->blk_rays.p);
+                launch_intersect(st, K, c->scene, lay, qin, c->hit.p, c->cnt.p + (size_t)d * K, cap, c->blk_rays.p);
             }
             launch_shade(st, K, c->scene, F, qin, qout, c->hit.p, c->cnt.p + (size_t)d * K,
                          c->cnt.p + (size_t)(d + 1) * K, cap, c->acc.p, c->flags.p, m, s0);
@@ -611,7 +633,9 @@ int render_mega(pt_ctx *c, const pt_config *cfg, const FrameParams &F, hipStream
     uint32_t n_split = 1;  // lanes per pixel within a round
     // (k_mega_cand hands its items out dynamically: finer ones - 8 per lane the chip holds, cornell 41.3 G bounces/s; 4: 39.1,
     // 16: 40.5, 32: 38.4 - so that a launch's last items are a small part of it; PT_MEGA_ITEMS for A/B runs and tests)
-    const uint64_t item_mult = c->tune.mega_items ? c->tune.mega_items : (mega_uses_cand(c->scene) ? 8u : 4u);
+    const LdsLayout lay = lds_layout(c->scene, 1u, c->tune.lds_pad);
+    say_layout(c, lay, 2);
+    const uint64_t item_mult = c->tune.mega_items ? c->tune.mega_items : (lay.mega_cand ? 8u : 4u);
     const uint64_t want_items = item_mult * lanes;
     while ((uint64_t)npix * n_split < want_items && n_split < round_spp) n_split *= 2;
     if (n_split > round_spp) n_split = round_spp;
@@ -674,9 +698,9 @@ int render_mega(pt_ctx *c, const pt_config *cfg, const FrameParams &F, hipStream
         const uint64_t grid64 = (items + kBlock - 1) / kBlock;
         const uint64_t max_grid = (uint64_t)prop.multiProcessorCount * 8u;
         const uint32_t grid = (uint32_t)(grid64 < max_grid ? grid64 : max_grid);
-        if (mega_uses_cand(c->scene) && (rc = c->q_buf[0].ensure(mega_stack_mem_bytes(grid ? grid : 1u)))) return rc;  // split stacks
+        if (lay.mega_cand && (rc = c->q_buf[0].ensure(mega_stack_mem_bytes(grid ? grid : 1u)))) return rc;  // split stacks
         HIP_TRY(hipMemsetAsync(c->total_rays.p + 7, 0, sizeof(unsigned long long), st));  // k_mega_cand's item counter
-        launch_mega(st, grid ? grid : 1u, c->scene, F, c->acc.p, s0, s0 + s_here, lane_spp, split, c->total_rays.p, c->q_buf[0].p);
+        launch_mega(st, grid ? grid : 1u, c->scene, lay, F, c->acc.p, s0, s0 + s_here, lane_spp, split, c->total_rays.p, c->q_buf[0].p);
         HIP_TRY(hipEventRecord(round_done[r & 1], st));
         c->live_spp_issued = s0 + s_here;
         samples += npix * s_here;
@@ -1357,7 +1381,7 @@ int pt_ctx_intersect_streams(pt_ctx *c, const float *o, const float *d, uint32_t
         S.cand_scan = cand_scan_for(c, flags);
         RayQueue q;
         q.buf = d0.p;
-        launch_intersect(st, K, S, q, dh.p, dc.p, cap, dr.p);
+        launch_intersect(st, K, S, lds_layout(S, 1u, c->tune.lds_pad), q, dh.p, dc.p, cap, dr.p);
         e = hipGetLastError();
     }
     std::vector<float2> hh((size_t)K * cap);

@@ -382,6 +382,25 @@ struct HitRec {
     int32_t id;  // -1 miss; [0,n_objs) sphere object; n_objs + k = flattened triangle k
 };
 
+constexpr uint32_t kLeafListCap = 128u;  // < 64 left over + at most 64 leaves appended by one step
+constexpr uint32_t kWalkQueueHeader = 16;  // bytes in front of a walk queue's entries (WalkQueue)
+#ifndef PT_WALK_FORM
+#define PT_WALK_FORM 2
+#endif
+// the nodes the walker of the candidate forms reads (walk_deferred_keys' `nodes`: global memory, or the workgroup's LDS copy)
+#if PT_WALK_FORM == 2
+typedef BvhNode4 WalkNode;
+PT_HDI uint32_t walk_node_count(const DevScene &S) { return S.n_bvh_nodes4; }
+#else
+typedef BvhNode WalkNode;
+PT_HDI uint32_t walk_node_count(const DevScene &S) { return S.n_bvh_nodes; }
+#endif
+PT_HDI size_t bvh_lds_bytes(const DevScene &S, uint32_t block) {
+    if (S.n_bvh_nodes == 0u) return 0;
+    return ((S.bvh_in_lds & 1u) ? (size_t)S.n_bvh_nodes * sizeof(BvhNode) : 0u) +
+           (size_t)kBvhStack * block * ((S.bvh_in_lds & 2u) ? sizeof(uint16_t) : sizeof(uint32_t));
+}
+
 #if defined(__HIPCC__)
 
 #ifdef PT_PHASE_STATS
@@ -769,7 +788,6 @@ struct LeafLds {
     unsigned long long *keys;  // [64] of this wave
     uint32_t *list;            // [kLeafListCap] of this wave: lane | leaf code << 6 (leaf_first / leaf_count)
 };
-constexpr uint32_t kLeafListCap = 128u;  // < 64 left over + at most 64 leaves appended by one step
 
 template <class NodePtr>
 __device__ __forceinline__ void bvh_closest_postponed(const DevScene &S, NodePtr nodes, StackDyn codec, char *stack,
@@ -910,7 +928,6 @@ struct WalkQueue {
                      // box tests queue up from ent[0], leaves down from ent[cap - 1]
     uint32_t cap;
 };
-constexpr uint32_t kWalkQueueHeader = 16;  // bytes in front of the entries
 
 template <class NodePtr>
 __device__ __forceinline__ void bvh_closest_queue(const DevScene &S, NodePtr nodes, const WalkQueue &Q, unsigned long long *keys,
@@ -1264,10 +1281,7 @@ __device__ __forceinline__ void bvh_closest_queue4(const DevScene &S, NodePtr4 n
 // mesh.json - 14.3 node visits and 5.2 leaves per walk as before, 89 % of the far subtrees still inside their owner's
 // bound when popped: on a thin surface mesh the boxes along a ray overlap, there is little for best-t pruning to prune,
 // and an offline replay of the frame's rays against the same tree says so too: 10.2 / 2.7 with ideal depth-first order
-// against 12.9 / 3.9 with none.)
-#ifndef PT_WALK_FORM
-#define PT_WALK_FORM 2
-#endif
+// against 12.9 / 3.9 with none.)  PT_WALK_FORM and WalkNode are defined above, with the host-side declarations.
 
 
 // LDS carve-up of the kernels that intersect: [BvhNode x n_bvh_nodes][u16 stack: kBvhStack x blockDim] when the
@@ -1278,11 +1292,6 @@ __device__ __forceinline__ void stage_bvh(const DevScene &S, uint4 *lds) {
         for (uint32_t i = threadIdx.x; i < S.n_bvh_nodes * 4u; i += blockDim.x) lds[i] = src[i];
         __syncthreads();
     }
-}
-__host__ __device__ inline size_t bvh_lds_bytes(const DevScene &S, uint32_t block) {
-    if (S.n_bvh_nodes == 0u) return 0;
-    return ((S.bvh_in_lds & 1u) ? (size_t)S.n_bvh_nodes * sizeof(BvhNode) : 0u) +
-           (size_t)kBvhStack * block * ((S.bvh_in_lds & 2u) ? sizeof(uint16_t) : sizeof(uint32_t));
 }
 
 #if defined(__HIPCC__)
@@ -1836,15 +1845,11 @@ __device__ __forceinline__ unsigned long long walk_deferred_keys(const DevScene 
     return key;
 }
 
-// the nodes the walker of the candidate forms reads (walk_deferred_keys' `nodes`: global memory, or the workgroup's LDS copy)
+// where those nodes are in global memory (WalkNode, walk_node_count: above)
 #if PT_WALK_FORM == 2
-typedef BvhNode4 WalkNode;
 __device__ __forceinline__ const WalkNode *walk_nodes(const DevScene &S) { return S.bvh_nodes4; }
-__host__ __device__ inline uint32_t walk_node_count(const DevScene &S) { return S.n_bvh_nodes4; }
 #else
-typedef BvhNode WalkNode;
 __device__ __forceinline__ const WalkNode *walk_nodes(const DevScene &S) { return S.bvh_nodes; }
-__host__ __device__ inline uint32_t walk_node_count(const DevScene &S) { return S.n_bvh_nodes; }
 #endif
 
 // ---------------------------------------------------------------------------------------------

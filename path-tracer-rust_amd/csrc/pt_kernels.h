@@ -4,18 +4,12 @@
 #include <hip/hip_runtime.h>
 
 #include "pt_device.h"
+#include "pt_layout.h"
 
 namespace pt {
 
 constexpr uint32_t kBlockBvh = 256;  // workgroup of the intersect kernel of scenes with a BVH
-// waves per SIMD (= workgroups per compute unit) k_pass_cand is compiled for, without walks (pt_kernels_flat.hip) and with: its
-// __launch_bounds__, launch_pass's LDS budget per workgroup and plan_pass's rounds of resident workgroups follow them
-#ifndef PT_CAND_WAVES
-#define PT_CAND_WAVES 5
-#endif
-#ifndef PT_ISECT_WAVES
-#define PT_ISECT_WAVES 4  // k_intersect_cand (the flat unit's too)
-#endif
+// (PT_CAND_WAVES, PT_ISECT_WAVES, PT_CAND_BVH_WAVES: pt_layout.h)
 #ifndef PT_ISECT_PREFETCH
 #define PT_ISECT_PREFETCH 1  // k_intersect_cand loads the next chunk's rays a trip ahead (0.318 -> 0.324 of the HBM peak, 74 VGPRs: six waves)
 #endif
@@ -24,9 +18,6 @@ constexpr uint32_t kBlockBvh = 256;  // workgroup of the intersect kernel of sce
 #endif
 #ifndef PT_SAMPLE_MAJOR
 #define PT_SAMPLE_MAJOR 1  // k_pass_cand: a trip's 64 primary rays are consecutive samples of one pixel (0: one sample of 64 pixels)
-#endif
-#ifndef PT_CAND_BVH_WAVES
-#define PT_CAND_BVH_WAVES 4
 #endif
 constexpr uint32_t kLevels = 13;    // ray depths 0..11 plus the (always empty) level written by the last shade
 // (kBlock, kMaxStreamPixels, kRayBytes, the wave-stack sizes and queue_bytes: pt_device.h - the pass planner of pt_host.cpp
@@ -41,7 +32,8 @@ struct RayQueue {
 
 
 // one whole pass of a scene without BVH meshes in one launch (see k_pass)
-hipError_t launch_pass(hipStream_t st, uint32_t K, const DevScene &S, const FrameParams &F, const RayQueue &q0,
+// (L = lds_layout(S, m, ..): the kernel, its template instance and its LDS; pt_layout.h)
+hipError_t launch_pass(hipStream_t st, uint32_t K, const DevScene &S, const LdsLayout &L, const FrameParams &F, const RayQueue &q0,
                  const RayQueue &q1, uint32_t cap, uint32_t s0, uint32_t s_here, uint32_t m, unsigned long long *acc,
                  unsigned long long *blk_rays, uint32_t *flags);
 // the same for scenes with BVH meshes (nodes read from global memory: DevScene.bvh_in_lds bit 0 clear)
@@ -50,9 +42,9 @@ void launch_pass_bvh(hipStream_t st, uint32_t K, const DevScene &S, const FrameP
                      unsigned long long *blk_rays, uint32_t *flags);
 void launch_generate(hipStream_t st, uint32_t K, const FrameParams &F, const RayQueue &q, uint32_t *cnt0,
                      uint32_t cap, uint32_t s0, uint32_t s_here, uint32_t m);
-void launch_intersect_cand(hipStream_t st, uint32_t K, const DevScene &S, const RayQueue &q, float2 *hit, const uint32_t *cnt,
+void launch_intersect_cand(hipStream_t st, uint32_t K, const DevScene &S, const LdsLayout &L, const RayQueue &q, float2 *hit, const uint32_t *cnt,
                            uint32_t cap, unsigned long long *blk_rays);  // (pt_kernels_flat.hip)
-void launch_intersect(hipStream_t st, uint32_t K, const DevScene &S, const RayQueue &q, float2 *hit,
+void launch_intersect(hipStream_t st, uint32_t K, const DevScene &S, const LdsLayout &L, const RayQueue &q, float2 *hit,
                       const uint32_t *cnt, uint32_t cap, unsigned long long *blk_rays);
 void launch_shade(hipStream_t st, uint32_t K, const DevScene &S, const FrameParams &F, const RayQueue &qin,
                   const RayQueue &qout, const float2 *hit, const uint32_t *cnt_in, uint32_t *cnt_out, uint32_t cap,
@@ -64,10 +56,9 @@ void launch_resolve(hipStream_t st, const unsigned long long *acc, float *out, u
                     uint32_t n_streams, uint32_t m, bool clamp = true);
 // one round of the megakernel: samples [s_begin, s_end) of every pixel, n_split lanes of lane_spp samples per pixel
 // (total_rays: [0] the ray counter, [1] an overflow flag of k_mega_cand's split stacks, [7] its item counter, which the caller
-// zeroes before every launch; stack_mem: mega_stack_mem_bytes(grid) bytes for the split stacks when mega_uses_cand(S), else unused)
-void launch_mega(hipStream_t st, uint32_t grid, const DevScene &S, const FrameParams &F, unsigned long long *acc,
+// zeroes before every launch; stack_mem: mega_stack_mem_bytes(grid) bytes for the split stacks when L.mega_cand, else unused)
+void launch_mega(hipStream_t st, uint32_t grid, const DevScene &S, const LdsLayout &L, const FrameParams &F, unsigned long long *acc,
                  uint32_t s_begin, uint32_t s_end, uint32_t lane_spp, uint32_t n_split, unsigned long long *total_rays, char *stack_mem);
-bool mega_uses_cand(const DevScene &S);
 size_t mega_stack_mem_bytes(uint32_t grid);
 void launch_query(hipStream_t st, const DevScene &S, const float *o, const float *d, uint32_t n, float *t,
                   int32_t *object_id, int32_t *tri_id, float *x, float *nrm);

@@ -49,31 +49,13 @@ void set_error(const std::string &m);  // pt_api.hip
 // dynamic LDS of the kernels that intersect: staged BVH nodes + per-lane traversal stacks (0 bytes for scenes
 // without a BVH mesh).  No static __shared__ object precedes it in those kernels, so its base is 16-byte aligned.
 extern __shared__ uint4 dyn_lds[];
+// (the LDS layouts of k_pass, k_pass_cand, k_intersect_cand and k_mega_cand, and lds_layout, which picks them per launch: pt_layout.h)
 
-constexpr uint32_t kDeferCap = 128;  // k_pass: deferred glass hits per wave (63 left over + 64 new at most)
-// k_pass LDS: [u64 acc: 3*m][kPassTailWords x u32: counters, camera][u32 pixel index, column, row: 3*m][pad to 16][float4 deferred hits: waves x 3 x kDeferCap]
-// the words between the accumulators and the pixel tables: [0..3] counters, [4..17] the camera for k_pass_cand's primary rays
-constexpr uint32_t kPassTailWords = 20;
-// u64 slots of the accumulator area: 3*m rounded up to even, so that the words behind it start on a 16-byte boundary whatever m
-// is (k_pass_cand reads the camera from there as three float4: with an odd m - small frames have m = 1 - those were
-// 8-byte-aligned ds_read_b128, which only the hardware's unaligned-DS mode forgives)
-__host__ __device__ constexpr uint32_t pass_acc_slots(uint32_t m) { return (3u * m + 1u) & ~1u; }
-__host__ __device__ constexpr size_t pass_lds_defer_offset(uint32_t m) {
-    return ((size_t)pass_acc_slots(m) * sizeof(unsigned long long) + kPassTailWords * 4u + (size_t)3 * m * sizeof(uint32_t) + 15) & ~(size_t)15;
-}
-static_assert(pass_acc_slots(1) == 4u && pass_acc_slots(2) == 6u && (pass_acc_slots(7) * 8u) % 16u == 0u, "tails are 16-byte aligned");
-
-// k_pass_cand LDS: [accumulators, tails, pixel indices as k_pass][per wave: float4 ray_a [128] | u64 key [128] |
-// float2 ray_b [128] | u16 ring [kCandQueueCap]][staged candidate records]
 // Glass deferral (DEFER): the glass hits of a wave wait in the wave's PARKING AREA in global memory - the ray (40 B) and its hit
 // (distance, rank: 8 B), where scenes with BVH meshes park the rays that have to walk - until 64 of them make a dense wave.
 // (Rounds 2-3 kept them in LDS: 18 KB per workgroup for 96 entries per wave, flushed at 32 - half-full batches, and with
 // the levels gone the pushes and flushes cost what the batches saved.)
 constexpr uint32_t kCandDeferFlush = 64;
-__host__ __device__ constexpr size_t pass_lds_cand_offset(uint32_t m, bool /*defer*/) { return pass_lds_defer_offset(m); }
-constexpr size_t kCandWaveBytes = 128u * 16u + 128u * 8u + 128u * 8u + kCandQueueCap * 2u;  // 4480
-__host__ __device__ constexpr size_t pass_lds_cand_bytes() { return (size_t)(kBlock / 64u) * kCandWaveBytes; }
-static_assert(kCandWaveBytes % 16u == 0u, "per-wave areas stay 16-byte aligned");
 
 // a wave-uniform value, said so to the compiler (loop-carried counters of the pass kernels otherwise end up in VGPRs)
 __device__ __forceinline__ uint32_t rfl(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
@@ -231,7 +213,6 @@ __global__ __launch_bounds__(BVH ? kBlockBvh : kBlock, BVH ? 5 : 1) void k_inter
 // it was started, when every candidate of its chunk has been through a batch (the ring is first-in first-out).  The hit
 // record is HitRec's: (t, id) with id = DevScene.rank_id[rank of the key], -1 and t = +inf for a miss - bit for bit what
 // k_intersect<false> writes (test_pass_kernel_equals_separate_kernels).
-__host__ __device__ constexpr size_t intersect_cand_lds_bytes() { return (size_t)(kBlock / 64u) * kCandWaveBytes; }
 
 template <bool STAGED>
 __global__ __launch_bounds__(kBlock, PT_ISECT_WAVES) void k_intersect_cand(DevScene S, RayQueue q, float2 *__restrict__ hit,
@@ -635,31 +616,6 @@ __global__ __launch_bounds__(kBlock, 6) void k_pass(DevScene S, FrameParams F, R
 //   [per wave: walk queue (pass_cand_queue_bytes)][per wave: u64 key x 64][BVH nodes (NLDS: a small tree's nodes, staged)]
 // (the parked rays' keys travel with the rays in the wave's parking area)
 constexpr uint32_t kCandParkCap = kWaveParkCap;  // 63 left over + 64 new at most
-// per wave: the walk queue (header + 8-byte entries: box tests from one end, leaves from the other), which is also where
-// the depth-first stacks (DevScene.bvh_stack entries x 64 lanes x u16, or u32 when a tree has 32 768 nodes or leaves) and
-// the leaf list of the rare second walk live
-// (448 entries.  With sample-major primary rays the walkers of a session are alike and their items crowd the queue together: at
-// 320 entries one wave-walk in fifty dropped pushes - those rays walk again depth-first - at 448 mesh.json gains 1.4 %; 512: the same)
-#ifndef PT_WALK_QUEUE_BYTES
-#define PT_WALK_QUEUE_BYTES 3584
-#endif
-constexpr uint32_t kWalkQueueBytes = PT_WALK_QUEUE_BYTES;
-constexpr uint32_t kWalkQueueBytesStaged = 2048;  // 256 entries: beside the workgroup's copy of the nodes (bvh_in_lds bit 2)
-__host__ __device__ inline size_t pass_cand_queue_bytes(const DevScene &S) {
-    const size_t again = (size_t)S.bvh_stack * 64u * ((S.bvh_in_lds & 2u) ? 2u : 4u) + kLeafListCap * 4u;
-    const size_t q = (S.bvh_in_lds & 4u) ? kWalkQueueBytesStaged : kWalkQueueBytes;
-    return kWalkQueueHeader + (((again > q ? again : q) + 15) & ~(size_t)15);
-}
-__host__ __device__ inline size_t pass_cand_queues_bytes(const DevScene &S) { return (size_t)(kBlock / 64u) * pass_cand_queue_bytes(S); }
-constexpr size_t kCandWalkKeyBytes = 64u * 8u;                         // per wave: the walkers' keys
-// [the waves' walk queues][the waves' walk keys][the workgroup's copy of the BVH nodes, when they fit (bvh_in_lds bit 2)]
-__host__ __device__ inline size_t pass_cand_nodes_offset(const DevScene &S) {
-    return pass_cand_queues_bytes(S) + (size_t)(kBlock / 64u) * kCandWalkKeyBytes;
-}
-__host__ __device__ inline size_t pass_cand_bvh_bytes(const DevScene &S) {
-    return pass_cand_nodes_offset(S) + ((S.bvh_in_lds & 4u) ? (size_t)walk_node_count(S) * sizeof(WalkNode) : 0u);
-}
-static_assert(kCandWalkKeyBytes % 16u == 0u && sizeof(WalkNode) % 16u == 0u, "per-wave areas stay 16-byte aligned");
 
 // (The workgroup's own copy of the nodes in LDS, in front of the stacks, was tried: mesh.json's 141 nodes are 9 KB, which
 // leaves room for three workgroups per CU instead of four - 16.1 against 17.8 G bounces/s.)
@@ -1462,8 +1418,6 @@ __global__ __launch_bounds__(kBlock) void k_mega(DevScene S, FrameParams F, unsi
 // room takes part, started when some lane that needs a ray has none: one round in four to five trips at about half the
 // lanes instead of one in every trip at a ninth.  (pt_ctx_radiance's fixed probe ray needs no maker and no spares.)
 // (two per lane, four where the workgroup's LDS has room for them: 8 / 16 KB)
-__host__ __device__ constexpr size_t mega_spare_bytes(uint32_t depth) { return (size_t)depth * kBlock * sizeof(float4); }
-constexpr size_t kMegaOwnerBytes = kBlock * sizeof(uint32_t);  // the rounds' owner tables
 struct MegaStack {
     float4 *a;  // [4][lanes] origin xyz, direction x
     float4 *b;  // [4][lanes] throughput rgb, meta
@@ -2031,13 +1985,13 @@ void launch_generate(hipStream_t st, uint32_t K, const FrameParams &F, const Ray
     else
         hipLaunchKernelGGL(k_generate<false>, dim3(K), dim3(kBlock), 0, st, F, q, cnt0, cap, s0, s_here, m);
 }
-void launch_intersect(hipStream_t st, uint32_t K, const DevScene &S, const RayQueue &q, float2 *hit,
+void launch_intersect(hipStream_t st, uint32_t K, const DevScene &S, const LdsLayout &L, const RayQueue &q, float2 *hit,
                       const uint32_t *cnt, uint32_t cap, unsigned long long *blk_rays) {
     if (S.n_bvh_nodes != 0u) {
         hipLaunchKernelGGL(k_intersect<true>, dim3(K), dim3(kBlockBvh),
                            bvh_park_offset(S, kBlockBvh) + bvh_park_bytes(kBlockBvh), st, S, q, hit, cnt, cap, blk_rays);
     } else if (S.cand_scan) {  // the candidate scan (PT_CAND_SCAN=0 / PT_FLAG_NO_BVH: the every-triangle scan below)
-        launch_intersect_cand(st, K, S, q, hit, cnt, cap, blk_rays);
+        launch_intersect_cand(st, K, S, L, q, hit, cnt, cap, blk_rays);
     } else {
         hipLaunchKernelGGL(k_intersect<false>, dim3(K), dim3(kBlock), 0, st, S, q, hit, cnt, cap, blk_rays);
     }
@@ -2062,7 +2016,7 @@ void launch_shade(hipStream_t st, uint32_t K, const DevScene &S, const FramePara
                        flags, m);
 }
 #endif  // PT_TU_FLAT
-// k_pass_cand for one pass: the workgroup's LDS (`lds` bytes) is laid out by launch_pass (below); the instances WITHOUT walks
+// k_pass_cand for one pass: the workgroup's LDS (`lds` bytes) is laid out as lds_layout says (pt_layout.h); the instances WITHOUT walks
 // are compiled in a translation unit of their own (pt_kernels_flat.hip: PT_CAND_WAVES waves per SIMD and the instruction
 // scheduling that fits them - the Makefile says which and why), the instances with walks here.
 #define PT_LAUNCH_CAND(ST, DF, BV, NL)                                                                                 \
@@ -2091,27 +2045,16 @@ hipError_t launch_pass_cand_flat(hipStream_t st, uint32_t K, const DevScene &S2,
                                  unsigned long long *blk_rays, uint32_t *flags, size_t lds, bool staged, bool defer);
 #ifdef PT_TU_FLAT
 // the stand-alone intersect step with the candidate scan (PT_FLAG_SEPARATE_KERNELS, scenes without BVH meshes)
-void launch_intersect_cand(hipStream_t st, uint32_t K, const DevScene &S, const RayQueue &q, float2 *hit, const uint32_t *cnt,
-                           uint32_t cap, unsigned long long *blk_rays) {
-    const size_t rec = (size_t)S.n_cand_pairs * sizeof(CandPairRec);
-    if (intersect_cand_lds_bytes() + rec <= 160u * 1024u / PT_ISECT_WAVES)
-        hipLaunchKernelGGL(k_intersect_cand<true>, dim3(K), dim3(kBlock), intersect_cand_lds_bytes() + rec, st, S, q, hit, cnt,
-                           cap, blk_rays);
+void launch_intersect_cand(hipStream_t st, uint32_t K, const DevScene &S, const LdsLayout &L, const RayQueue &q, float2 *hit,
+                           const uint32_t *cnt, uint32_t cap, unsigned long long *blk_rays) {
+    if (L.isect_staged)
+        hipLaunchKernelGGL(k_intersect_cand<true>, dim3(K), dim3(kBlock), L.isect_lds, st, S, q, hit, cnt, cap, blk_rays);
     else
-        hipLaunchKernelGGL(k_intersect_cand<false>, dim3(K), dim3(kBlock), intersect_cand_lds_bytes(), st, S, q, hit, cnt, cap,
-                           blk_rays);
+        hipLaunchKernelGGL(k_intersect_cand<false>, dim3(K), dim3(kBlock), L.isect_lds, st, S, q, hit, cnt, cap, blk_rays);
 }
 hipError_t launch_pass_cand_flat(hipStream_t st, uint32_t K, const DevScene &S2, const FrameParams &F, const RayQueue &q0,
                                  const RayQueue &q1, uint32_t cap, uint32_t s0, uint32_t s_here, uint32_t m, unsigned long long *acc,
                                  unsigned long long *blk_rays, uint32_t *flags, size_t lds, bool staged, bool defer) {
-    // (diagnosis: PT_LDS_PAD=n asks for n bytes of LDS the kernel does not use - where does the fifth workgroup of a CU stop fitting?)
-    static const size_t lds_pad = getenv("PT_LDS_PAD") ? (size_t)atol(getenv("PT_LDS_PAD")) : 0u;
-    static bool said = false;
-    if (getenv("PT_LDS_PAD") && !said) {
-        said = true;
-        fprintf(stderr, "k_pass_cand: %zu bytes of LDS per workgroup (+ %zu of padding), m = %u\n", lds, lds_pad, m);
-    }
-    lds += lds_pad;
     if (staged && defer)
         PT_LAUNCH_CAND(true, true, false, false);
     else if (staged)
@@ -2123,78 +2066,35 @@ hipError_t launch_pass_cand_flat(hipStream_t st, uint32_t K, const DevScene &S2,
     return hipSuccess;
 }
 #else
-hipError_t launch_pass(hipStream_t st, uint32_t K, const DevScene &S, const FrameParams &F, const RayQueue &q0,
+hipError_t launch_pass(hipStream_t st, uint32_t K, const DevScene &S, const LdsLayout &L, const FrameParams &F, const RayQueue &q0,
                        const RayQueue &q1, uint32_t cap, uint32_t s0, uint32_t s_here, uint32_t m, unsigned long long *acc,
                        unsigned long long *blk_rays, uint32_t *flags) {
-    // The deferral buffers are 24 KB per workgroup: worth it while 5-6 workgroups still fit a CU's 160 KB of LDS (the
-    // accumulators of a stream take 28 B per pixel); frames so large that a stream owns hundreds of pixels (4096^2:
-    // 1024) shade every material in place instead.
-    const size_t lds_plain = pass_lds_defer_offset(m);
-    const size_t lds_defer = lds_plain + (size_t)(kBlock / 64u) * 3u * kDeferCap * sizeof(float4);
-    if (S.cand_scan) {
-        // candidate scan: ray slots, keys and ring per wave + the workgroup's copy of the candidate and shading records while
-        // as many workgroups still fit a CU's 160 KiB as the kernel is built to run waves per SIMD (with walks four: 40 KiB each)
-        const bool bvh = S.n_bvh_nodes != 0u;
-        // (measured with PT_LDS_PAD: four workgroups of 40 928 B share a CU, five of 32 144 B do, five of 32 400 B do not)
-        const size_t budget = 160u * 1024u / (bvh ? PT_CAND_BVH_WAVES : PT_CAND_WAVES) - (bvh ? 0u : 512u);
+    // (PT_LDS_PAD=n: k_pass_cand asks for n bytes of LDS it does not use - where does the fifth workgroup of a CU stop fitting?)
+    const size_t lds = L.pass_lds + L.pass_pad;
+    if (L.pass == kPassCand || L.pass == kPassCandBvh) {
         DevScene S2 = S;
-        S2.bvh_in_lds &= ~1u;  // (nodes from global memory: PT_BVH_LDS asks for the staged k_intersect, not for this kernel)
-        const size_t rec_cand = (size_t)S.n_cand_pairs * sizeof(CandPairRec);
-        const size_t rec_surf = (size_t)(S.n_objs + S.n_tris) * sizeof(SurfRec);
-        // glass deferral: not with walks (their queues take its place in LDS; a walked ray is shaded in place anyway)
-        // (Without levels the deferral no longer pays: a chunk mixes rays of every depth and nearly every trip shades some glass
-        // anyway - shading it in place, 46.5 against 46.05 G bounces/s on cornell, builds alternated; PT_GLASS_DEFER=1 brings
-        // the buffers back for that comparison.)
-        const bool defer = !bvh && S.glass_defer_ok;  // (the scene has glass and the context holds parking areas: pt_api.hip)
-        // walks: the nodes of a small tree are staged in LDS beside (smaller) walk queues when they fit with the candidate
-        // records (mesh.json: 171 nodes, 10.9 KB: up to 24 pixels per stream).  Measured: no gain and no loss against the
-        // gathers from L2 (26.74 / 26.72 G bounces/s) - a box-test batch waits for its turn at the SIMD, not for its node -
-        // so streams are not shortened to make room for it
-        bool nodes_lds = false;
-        if (bvh && S.nodes_in_lds_ok) {
-            DevScene S3 = S2;
-            S3.bvh_in_lds |= 4u;
-            nodes_lds = pass_lds_cand_offset(m, false) + pass_lds_cand_bytes() + pass_cand_bvh_bytes(S3) + rec_cand <= budget;
-            if (nodes_lds) S2 = S3;
-        }
-        const size_t walk = bvh ? pass_cand_bvh_bytes(S2) : 0u;
-        const size_t before = pass_lds_cand_offset(m, defer) + pass_lds_cand_bytes() + walk;
-        S2.surf_staged = before + rec_cand + rec_surf <= budget ? 1u : 0u;
-        // (without walks the records are staged whole or not at all; with walks the candidate records alone may be)
-        const bool staged = bvh ? (S2.surf_staged || before + rec_cand <= budget + 8u * 1024u) : S2.surf_staged != 0u;
-        // (walks, table too large: as many leading ranks as still fit - the objects visited first, the room of mesh.json)
-        S2.surf_head = 0u;
-        if (bvh && staged && !S2.surf_staged && before + rec_cand < budget) {
-            const size_t fit = (budget - before - rec_cand) / sizeof(SurfRec);
-            const size_t n_ranks = (size_t)S.n_objs + S.n_tris;
-            S2.surf_head = (uint32_t)(fit < n_ranks ? fit : n_ranks);
-        }
-        size_t lds = before + (staged ? rec_cand + (S2.surf_staged ? rec_surf : (size_t)S2.surf_head * sizeof(SurfRec)) : 0u);
-        if (bvh && getenv("PT_LDS_PAD")) lds += (size_t)atol(getenv("PT_LDS_PAD"));
-        if (!bvh) return launch_pass_cand_flat(st, K, S2, F, q0, q1, cap, s0, s_here, m, acc, blk_rays, flags, lds, staged, defer);
-        static bool said = false;
-        if (getenv("PT_LDS_PAD") && !said) {
-            said = true;
-            fprintf(stderr, "k_pass_cand<BVH>: %zu bytes of LDS per workgroup (+ %ld of padding), m = %u, staged %d nodes_lds %d surf_head %u\n", lds, atol(getenv("PT_LDS_PAD")), m, (int)staged, (int)nodes_lds, S2.surf_head);
-        }
-        if (staged && nodes_lds)
+        S2.bvh_in_lds = L.bvh_in_lds;
+        S2.surf_staged = L.surf_staged;
+        S2.surf_head = L.surf_head;
+        if (L.pass == kPassCand) return launch_pass_cand_flat(st, K, S2, F, q0, q1, cap, s0, s_here, m, acc, blk_rays, flags, lds, L.staged, L.defer);
+        if (L.staged && L.nodes_lds)
             PT_LAUNCH_CAND(true, false, true, true);
-        else if (staged)
+        else if (L.staged)
             PT_LAUNCH_CAND(true, false, true, false);
         else
             PT_LAUNCH_CAND(false, false, true, false);
         return hipSuccess;
     }
-    if (lds_defer <= 32u * 1024u) {
+    if (L.pass == kPassDefer) {
         if (F.probe)
-            hipLaunchKernelGGL((k_pass<true, true>), dim3(K), dim3(kBlock), lds_defer, st, S, F, q0, q1, cap, s0, s_here, m, acc, blk_rays, flags);
+            hipLaunchKernelGGL((k_pass<true, true>), dim3(K), dim3(kBlock), lds, st, S, F, q0, q1, cap, s0, s_here, m, acc, blk_rays, flags);
         else
-            hipLaunchKernelGGL((k_pass<true, false>), dim3(K), dim3(kBlock), lds_defer, st, S, F, q0, q1, cap, s0, s_here, m, acc, blk_rays, flags);
+            hipLaunchKernelGGL((k_pass<true, false>), dim3(K), dim3(kBlock), lds, st, S, F, q0, q1, cap, s0, s_here, m, acc, blk_rays, flags);
     } else {
         if (F.probe)
-            hipLaunchKernelGGL((k_pass<false, true>), dim3(K), dim3(kBlock), lds_plain, st, S, F, q0, q1, cap, s0, s_here, m, acc, blk_rays, flags);
+            hipLaunchKernelGGL((k_pass<false, true>), dim3(K), dim3(kBlock), lds, st, S, F, q0, q1, cap, s0, s_here, m, acc, blk_rays, flags);
         else
-            hipLaunchKernelGGL((k_pass<false, false>), dim3(K), dim3(kBlock), lds_plain, st, S, F, q0, q1, cap, s0, s_here, m, acc, blk_rays, flags);
+            hipLaunchKernelGGL((k_pass<false, false>), dim3(K), dim3(kBlock), lds, st, S, F, q0, q1, cap, s0, s_here, m, acc, blk_rays, flags);
     }
     return hipSuccess;
 }
@@ -2221,21 +2121,13 @@ void launch_resolve(hipStream_t st, const unsigned long long *acc, float *out, u
     hipLaunchKernelGGL(k_resolve, dim3((npix + kBlock - 1) / kBlock), dim3(kBlock), 0, st, acc, out, npix, spp,
                        n_streams, m, clamp ? 1u : 0u);
 }
-void launch_mega(hipStream_t st, uint32_t grid, const DevScene &S, const FrameParams &F, unsigned long long *acc,
+void launch_mega(hipStream_t st, uint32_t grid, const DevScene &S, const LdsLayout &L, const FrameParams &F, unsigned long long *acc,
                  uint32_t s_begin, uint32_t s_end, uint32_t lane_spp, uint32_t n_split, unsigned long long *total_rays, char *stack_mem) {
-    const size_t rec = ((size_t)S.n_cand_pairs * sizeof(CandPairRec) + 15) & ~(size_t)15;
-    DevScene S2 = S;
-    S2.bvh_in_lds &= ~5u;  // (the candidate forms read the nodes from global memory, with full-size walk queues)
-    const size_t walk = S.n_bvh_nodes != 0u ? pass_cand_queues_bytes(S2) + (size_t)(kBlock / 64u) * kCandWalkKeyBytes : 0u;
-    if (mega_uses_cand(S) && stack_mem) {  // the candidate scan, two paths per lane (k_mega_cand)
-        const size_t rec_surf = (size_t)(S.n_objs + S.n_tris) * sizeof(SurfRec);
-        const size_t base = intersect_cand_lds_bytes() + rec + walk;
-        const size_t budget = 40u * 1024u;  // four workgroups per CU
-        const uint32_t depth = base + mega_spare_bytes(4) + kMegaOwnerBytes <= budget ? 4u : 2u;
-        const uint32_t spare_off = (uint32_t)base;
-        const size_t after = base + mega_spare_bytes(depth) + kMegaOwnerBytes;
-        const uint32_t surf_off = after + rec_surf <= budget ? (uint32_t)after : 0u;
-        const size_t lds_c = after + (surf_off ? rec_surf : 0u);
+    if (L.mega_cand) {  // the candidate scan, two paths per lane (k_mega_cand; stack_mem holds its split stacks)
+        DevScene S2 = S;
+        S2.bvh_in_lds &= ~5u;  // (the candidate forms read the nodes from global memory, with full-size walk queues)
+        const size_t lds_c = L.mega_lds;
+        const uint32_t spare_off = L.mega_spare_off, depth = L.mega_depth, surf_off = L.mega_surf_off;
         MegaStack stk;
         stk.lanes = grid * kBlock;
         stk.a = reinterpret_cast<float4 *>(stack_mem);
@@ -2251,7 +2143,7 @@ void launch_mega(hipStream_t st, uint32_t grid, const DevScene &S, const FramePa
             hipLaunchKernelGGL((k_mega_cand<false, false>), dim3(grid), dim3(kBlock), lds_c, st, S2, F, acc, s_begin, s_end, lane_spp, n_split, total_rays, stk, spare_off, depth, surf_off);
         return;
     }
-    const size_t lds = S.n_bvh_nodes != 0u ? bvh_lds_bytes(S, kBlock) : 0u;
+    const size_t lds = L.mega_lds;  // (k_mega: the BVH stacks of scenes with BVH meshes, bvh_lds_bytes)
     if (S.n_bvh_nodes != 0u && F.probe)
         hipLaunchKernelGGL((k_mega<true, true>), dim3(grid), dim3(kBlock), lds, st, S, F, acc, s_begin, s_end, lane_spp, n_split, total_rays);
     else if (S.n_bvh_nodes != 0u)
@@ -2260,14 +2152,6 @@ void launch_mega(hipStream_t st, uint32_t grid, const DevScene &S, const FramePa
         hipLaunchKernelGGL((k_mega<false, true>), dim3(grid), dim3(kBlock), lds, st, S, F, acc, s_begin, s_end, lane_spp, n_split, total_rays);
     else
         hipLaunchKernelGGL((k_mega<false, false>), dim3(grid), dim3(kBlock), lds, st, S, F, acc, s_begin, s_end, lane_spp, n_split, total_rays);
-}
-// does the megakernel run the candidate scan for this scene (and need the split stacks: mega_stack_bytes)?
-bool mega_uses_cand(const DevScene &S) {
-    const size_t rec = ((size_t)S.n_cand_pairs * sizeof(CandPairRec) + 15) & ~(size_t)15;
-    DevScene S2 = S;
-    S2.bvh_in_lds &= ~5u;
-    const size_t walk = S.n_bvh_nodes != 0u ? pass_cand_queues_bytes(S2) + (size_t)(kBlock / 64u) * kCandWalkKeyBytes : 0u;
-    return S.cand_scan && intersect_cand_lds_bytes() + rec + walk + mega_spare_bytes(2) + kMegaOwnerBytes <= 40u * 1024u;
 }
 size_t mega_stack_mem_bytes(uint32_t grid) { return mega_stack_bytes(grid * kBlock); }
 void launch_query(hipStream_t st, const DevScene &S, const float *o, const float *d, uint32_t n, float *t,

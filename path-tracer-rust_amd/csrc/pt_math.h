@@ -22,9 +22,13 @@
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 #define PT_HD __host__ __device__ __forceinline__
+#define PT_HDI __host__ __device__ inline
+#define PT_HDC __host__ __device__ constexpr
 #else
 #include <math.h>
 #define PT_HD static inline
+#define PT_HDI inline
+#define PT_HDC constexpr
 #endif
 
 namespace pt {
