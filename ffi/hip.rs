@@ -126,6 +126,22 @@ extern "C" {
         stats: *mut PtStats,
     ) -> i32;
     pub fn pt_ctx_snapshot(ctx: *mut PtCtx, d_out_rgb: *mut c_void, spp_done: *mut u32) -> i32;
+    // progressive accumulation: the frame up to cfg.spp samples IN TOTAL, from the samples the context holds for it (Stop
+    // keeps them, Continue / "more samples" traces only the rest); checkpoints of the held samples on disk
+    pub fn pt_ctx_accumulate(
+        ctx: *mut PtCtx,
+        cfg: *const PtConfig,
+        d_out_rgb: *mut c_void,
+        hip_stream: *mut c_void,
+        cancel: *const u8,
+        cb: Option<PtProgressFn>,
+        user: *mut c_void,
+        stats: *mut PtStats,
+    ) -> i32;
+    pub fn pt_ctx_accum_info(ctx: *const PtCtx, cfg: *const PtConfig, spp_min: *mut u32, spp_max: *mut u32) -> i32;
+    pub fn pt_ctx_accum_reset(ctx: *mut PtCtx) -> i32;
+    pub fn pt_ctx_accum_save(ctx: *mut PtCtx, path: *const c_char) -> i32;
+    pub fn pt_ctx_accum_load(ctx: *mut PtCtx, path: *const c_char) -> i32;
     pub fn pt_device_malloc(device: i32, bytes: usize, out: *mut *mut c_void) -> i32;
     pub fn pt_device_free(device: i32, p: *mut c_void) -> i32;
     pub fn pt_device_download(device: i32, dst_host: *mut c_void, src_device: *const c_void, bytes: usize) -> i32;

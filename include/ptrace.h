@@ -326,6 +326,50 @@ int pt_render_multi(const pt_config *cfg, uint32_t n_ranks, const pt_camera *cam
  * part in progress at partial spp - spp_done speaks of that part - and the parts not started black.) */
 int pt_ctx_snapshot(pt_ctx *ctx, void *d_out_rgb, uint32_t *spp_done);
 
+/* ---- progressive accumulation across calls: resume, refine, checkpoint -----------------------------------------
+ * The RNG is keyed on (seed; pixel, sample, ...) and radiance is summed in u64 fixed point, whose sum does not depend on the
+ * order of its terms; so a frame rendered to T samples over several calls is pt_ctx_render's frame at T, bit for bit.
+ *
+ * pt_ctx_accumulate renders this frame up to cfg->spp samples per pixel IN TOTAL.  The samples come from an accumulator the
+ * context keeps between calls, so only the samples it does not hold yet are traced.
+ * - Frame key.  The held accumulator belongs to one frame: width, height, the band [idx_begin, idx_end), chunk_pixels /
+ *   chunk_first / chunk_step (as pt_config reads them: all ignored when chunk_step <= 1), seed, and the scene as uploaded.
+ *   backend, flags, rays_per_pass and progress_ms are NOT part of it - they give the same image - so a frame may switch
+ *   backend, scan form (PT_FLAG_NO_BVH, PT_FLAG_SEPARATE_KERNELS) or pass size from one call to the next.
+ * - A call whose key differs from the held one drops the held accumulator and starts from zero; pt_ctx_set_scene drops it too.
+ *   pt_ctx_render neither reads nor disturbs it (the held sums live in a buffer of their own).
+ * - Counts are kept per part, cut as pt_ctx_render cuts a call: one part up to 1.5 Mi pixels, otherwise parts of 2^20 pixels.
+ *   A part whose count is c traces samples [c, cfg->spp) and nothing else; without a cancel every part ends at cfg->spp.  The
+ *   megakernel renders the whole call at once when all counts are equal, otherwise part by part.
+ * - d_out_rgb is laid out as for pt_ctx_render; each pixel is resolved over its own part's count, a pixel with count 0 is black.
+ * - A cancelled call keeps every pass that finished and returns PT_CANCELLED; a later call with the same key continues from there.
+ * - pt_ctx_snapshot from the progress callback shows every pixel at its own count (the parts this call has not reached at
+ *   their earlier samples, not black); its spp_done describes the part in progress.
+ * - PT_ERR_INVALID: cfg->spp below what is held (samples cannot be removed; pt_ctx_accum_reset starts over), PT_FLAG_PIPELINES
+ *   (its accumulators live in child contexts), and whatever pt_ctx_render refuses (cfg->spp > 2^24 among them).
+ * - stats counts only the work this call did; a call with nothing left to trace only resolves and reports zero rays.
+ * - Memory: the held sums take 24 B per pixel of the call (403 MB at 4096^2), on top of and outside the ray-queue budget of
+ *   pt_ctx_set_memory_budget; pt_ctx_accum_reset gives them back. */
+int pt_ctx_accumulate(pt_ctx *ctx, const pt_config *cfg, void *d_out_rgb, void *hip_stream,
+                      const volatile uint8_t *cancel, pt_progress_fn cb, void *user, pt_stats *stats);
+/* Samples per pixel held for cfg's frame (min / max over its parts); 0, 0 if the held accumulator is of another frame or
+ * there is none.  Host only. */
+int pt_ctx_accum_info(const pt_ctx *ctx, const pt_config *cfg, uint32_t *spp_min, uint32_t *spp_max);
+/* Drops the held accumulator and frees its memory. */
+int pt_ctx_accum_reset(pt_ctx *ctx);
+/* Checkpoint of the held accumulator (PT_ERR_INVALID if there is none), written to path + ".tmp" and renamed over `path`.
+ * Little-endian: magic "PTACCUM1"; u32 format version 1; the frame key - u32 width, height, idx_begin, idx_end, chunk_pixels,
+ * chunk_first, chunk_step, u64 seed; u64 scene fingerprint (pt_siphash(1, 3, 0, 0, ...) over u32 n_objs, u32 n_tris, then the
+ * camera, objects and triangles as pt_ctx_set_scene got them); u32 call pixels, u32 part pixels, u32 number of parts; the
+ * per-part counts (u32 each); the sums, 3 planes x call pixels of u64 (32.32 fixed point, pixel order); a trailing u64
+ * pt_siphash(1, 3, 0, 0, ...) of everything before it. */
+int pt_ctx_accum_save(pt_ctx *ctx, const char *path);
+/* Replaces the held accumulator with a checkpoint's; the next pt_ctx_accumulate with its key continues from it.  Needs the
+ * same scene set on ctx.  PT_ERR_IO: missing file or read error; PT_ERR_PARSE: wrong magic or version, bad trailing hash,
+ * truncated file, sizes that do not fit each other; PT_ERR_INVALID: the scene fingerprint is not the context's scene.  On
+ * each of these the held accumulator is left as it was.  No input crashes the loader. */
+int pt_ctx_accum_load(pt_ctx *ctx, const char *path);
+
 /* ---- the one collective of the path: the framebuffer gather over RCCL (xGMI) ---------------------------------
  * One process (or thread) per GPU renders its rows with pt_ctx_render (chunk_first = rank, chunk_step = n_ranks) into
  * device memory; pt_comm_gather_frame then gives EVERY rank the whole frame in device memory: one in-place

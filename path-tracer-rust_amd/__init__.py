@@ -49,6 +49,7 @@ class pt_stats(C.Structure):
 
 
 PT_OK, PT_ERR_INVALID, PT_ERR_NO_DEVICE, PT_ERR_HIP, PT_CANCELLED = 0, -1, -2, -3, -4
+PT_ERR_IO, PT_ERR_PARSE = -6, -7
 BACKEND_WAVEFRONT, BACKEND_MEGAKERNEL = 0, 1
 PT_FLAG_NO_BVH, PT_FLAG_SEPARATE_KERNELS = 1, 2
 BACKENDS = {"wavefront": BACKEND_WAVEFRONT, "megakernel": BACKEND_MEGAKERNEL}
@@ -77,6 +78,11 @@ def lib():
                                    C.POINTER(pt_triangle), C.c_uint32]
     L.pt_ctx_render.argtypes = [C.c_void_p, C.POINTER(pt_config), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.POINTER(pt_stats)]
+    L.pt_ctx_accumulate.argtypes = L.pt_ctx_render.argtypes
+    L.pt_ctx_accum_info.argtypes = [C.c_void_p, C.POINTER(pt_config), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.pt_ctx_accum_reset.argtypes = [C.c_void_p]
+    L.pt_ctx_accum_save.argtypes = [C.c_void_p, C.c_char_p]
+    L.pt_ctx_accum_load.argtypes = [C.c_void_p, C.c_char_p]
     L.pt_ctx_set_profiling.argtypes = [C.c_void_p, C.c_int]
     L.pt_ctx_pass_kernel.argtypes = [C.c_void_p, C.c_uint32]
     L.pt_ctx_pass_kernel.restype = C.c_char_p
@@ -155,20 +161,53 @@ class Context:
     def set_profiling(self, on):
         _check(lib().pt_ctx_set_profiling(self._h, 1 if on else 0))
 
-    def render(self, out_ptr, width, height, spp, seed=1, backend="wavefront", band=None, rays_per_pass=0,
-               stream=None, chunks=None, pipelines=1, separate_kernels=False):
-        """Render band [begin,end) (default whole frame) — or, with chunks=(chunk_pixels, first, step), this rank's
-        interleaved chunks of it — into device memory at out_ptr (owned pixels * 3 floats)."""
+    @staticmethod
+    def _config(width, height, spp, seed=1, backend="wavefront", band=None, rays_per_pass=0, chunks=None, pipelines=1,
+                separate_kernels=False):
         cfg = pt_config(width, height, spp, BACKENDS[backend], seed, 0, 0, rays_per_pass,
                         (((pipelines & 15) << 8) if pipelines > 1 else 0) | (PT_FLAG_SEPARATE_KERNELS if separate_kernels else 0))
         if band is not None:
             cfg.idx_begin, cfg.idx_end = band
         if chunks is not None:
             cfg.chunk_pixels, cfg.chunk_first, cfg.chunk_step = chunks
+        return cfg
+
+    def render(self, out_ptr, width, height, spp, seed=1, backend="wavefront", band=None, rays_per_pass=0,
+               stream=None, chunks=None, pipelines=1, separate_kernels=False):
+        """Render band [begin,end) (default whole frame) — or, with chunks=(chunk_pixels, first, step), this rank's
+        interleaved chunks of it — into device memory at out_ptr (owned pixels * 3 floats)."""
+        cfg = self._config(width, height, spp, seed, backend, band, rays_per_pass, chunks, pipelines, separate_kernels)
         st = pt_stats()
         _check(lib().pt_ctx_render(self._h, C.byref(cfg), C.c_void_p(out_ptr), C.c_void_p(stream or 0), None, None,
                                    None, C.byref(st)))
         return st
+
+    def accumulate(self, out_ptr, width, height, spp, seed=1, backend="wavefront", band=None, rays_per_pass=0,
+                   stream=None, chunks=None, pipelines=1, separate_kernels=False):
+        """The frame of render() with the same arguments, up to `spp` samples per pixel IN TOTAL: the context keeps the
+        samples of earlier calls for this frame and traces only the rest (pt_ctx_accumulate).  Returns this call's pt_stats."""
+        cfg = self._config(width, height, spp, seed, backend, band, rays_per_pass, chunks, pipelines, separate_kernels)
+        st = pt_stats()
+        _check(lib().pt_ctx_accumulate(self._h, C.byref(cfg), C.c_void_p(out_ptr), C.c_void_p(stream or 0), None, None,
+                                       None, C.byref(st)))
+        return st
+
+    def accum_info(self, width, height, seed=1, band=None, chunks=None):
+        """(min, max) samples per pixel held for this frame; (0, 0) if the context holds another frame or none."""
+        cfg = self._config(width, height, 1, seed, band=band, chunks=chunks)
+        lo, hi = C.c_uint32(), C.c_uint32()
+        _check(lib().pt_ctx_accum_info(self._h, C.byref(cfg), C.byref(lo), C.byref(hi)))
+        return lo.value, hi.value
+
+    def accum_reset(self):
+        _check(lib().pt_ctx_accum_reset(self._h))
+
+    def accum_save(self, path):
+        _check(lib().pt_ctx_accum_save(self._h, os.fsencode(path)))
+
+    def accum_load(self, path):
+        """Continue from a checkpoint of accum_save; the scene it was rendered from must be set."""
+        _check(lib().pt_ctx_accum_load(self._h, os.fsencode(path)))
 
     def close(self):
         if self._h:

@@ -1,6 +1,7 @@
 // pt_api.hip — C ABI of the compute path (include/ptrace.h): contexts, scene flattening, the pass loop
 // of the wavefront pipeline, the megakernel launch, single-ray queries.  No CPU fallback exists here:
 // without a HIP device every entry point returns PT_ERR_NO_DEVICE.
+#include <cerrno>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -10,6 +11,7 @@
 #include <vector>
 
 #include "../../include/ptrace.h"
+#include "pt_accum.h"
 #include "pt_host.h"
 #include "pt_kernels.h"
 
@@ -56,6 +58,17 @@ struct DevBuf {
         if (p) (void)hipFree(p);
         p = nullptr;
         n = 0;
+    }
+};
+
+// The frame a pt_ctx_accumulate call renders: what decides the image besides the samples (the scene is the context's).
+// chunk_* as check_cfg reads them: all zero for a whole band.
+struct AccumKey {
+    uint32_t width, height, idx_begin, idx_end, chunk_pixels, chunk_first, chunk_step;
+    uint64_t seed;
+    bool operator==(const AccumKey &o) const {
+        return width == o.width && height == o.height && idx_begin == o.idx_begin && idx_end == o.idx_end &&
+               chunk_pixels == o.chunk_pixels && chunk_first == o.chunk_first && chunk_step == o.chunk_step && seed == o.seed;
     }
 };
 
@@ -193,6 +206,16 @@ struct pt_ctx {
     // forgets them.
     double pass_rate = 0.0, round_rate = 0.0;
     const char *pass_rate_kernel = nullptr;  // the kernel pass_rate was measured on (flags choose other kernels)
+    // pt_ctx_accumulate: the sums of one frame (acc_key) kept between calls, [3] planes of acc_total u64 in the call's pixel
+    // order, and the samples per pixel each part holds (parts of acc_part_px pixels, cut as pt_ctx_render cuts a call).
+    // scene_fp: the checkpoint fingerprint of the scene pt_ctx_set_scene got, which drops the held sums.
+    bool acc_on = false;
+    AccumKey acc_key{};
+    uint32_t acc_total = 0, acc_part_px = 0;
+    std::vector<uint32_t> acc_cnt;
+    DevBuf<unsigned long long> acc_held;
+    uint64_t scene_fp = 0;
+    bool live_accum = false;  // the call in progress is a pt_ctx_accumulate: pt_ctx_snapshot shows the other parts at their counts
 };
 
 namespace {
@@ -318,15 +341,28 @@ static void say_layout(pt_ctx *c, const LdsLayout &L, int which) {
     fprintf(stderr, "%s\n", line.c_str());
 }
 
+// A call of more than 1.5 Mi pixels is rendered in parts of 2^20 pixels (pt_ctx_render says why); pixels per part
+uint32_t part_pixels(uint32_t total, bool wavefront) { return (wavefront && total > (3u << 19)) ? (1u << 20) : total; }
+
+// pt_ctx_accumulate's sums of a part's pixels: [3] planes of `stride` u64 in pixel order, the part's first pixel at p.  A
+// renderer given them starts its accumulators from them (launch_accum_gather) instead of from zero.
+struct HeldSums {
+    const unsigned long long *p;
+    uint32_t stride;
+};
+
 double now_ms() {
     using namespace std::chrono;
     return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
 }
 
+// Samples [s_first, cfg->spp) of every pixel of the part; the accumulators start from `held` (NULL: from zero).
 int render_wavefront(pt_ctx *c, const pt_config *cfg, const FrameParams &frame, hipStream_t st,
-                     const volatile uint8_t *cancel, pt_progress_fn cb, void *user, pt_stats *stats) {
+                     const volatile uint8_t *cancel, pt_progress_fn cb, void *user, pt_stats *stats, uint32_t s_first,
+                     const HeldSums *held) {
     FrameParams F = frame;
     const uint64_t npix = F.npix;
+    const uint32_t spp_left = cfg->spp - s_first;  // samples per pixel this call traces
     // Level-by-level forms (k_pass, k_pass_bvh, the separate kernels): 96 Mi primary rays per pass by default, 36 GB of ray
     // queues (two containers x 4 slots per primary ray x 40 B) of the 288 GB of HBM - fewer, longer launches: cornell 1024x768
     // @4096 spp 32 Mi 35.7, 48 Mi 35.7, 64 Mi 36.2, 96 Mi 36.4 G bounces/s (a launch ends with its slowest streams).
@@ -380,7 +416,7 @@ int render_wavefront(pt_ctx *c, const pt_config *cfg, const FrameParams &frame, 
     for (;;) {
         host::PassPlanIn pin;
         pin.npix = npix;
-        pin.spp = cfg->spp;
+        pin.spp = spp_left;
         pin.want = want;
         pin.want_is_default = !cfg->rays_per_pass;
         pin.stack_form = stack_form;
@@ -436,12 +472,15 @@ int render_wavefront(pt_ctx *c, const pt_config *cfg, const FrameParams &frame, 
     const LdsLayout lay = lds_layout(c->scene, m, c->tune.lds_pad);
     if (one_kernel && (c->scene.n_bvh_nodes == 0u || c->scene.cand_scan)) say_layout(c, lay, 0);
     if (!one_kernel && c->scene.n_bvh_nodes == 0u && c->scene.cand_scan) say_layout(c, lay, 1);
-    HIP_TRY(hipMemsetAsync(c->acc.p, 0, 3 * (size_t)K * m * sizeof(unsigned long long), st));
+    if (held)
+        launch_accum_gather(st, held->p, held->stride, (uint32_t)npix, K, m, c->acc.p);
+    else
+        HIP_TRY(hipMemsetAsync(c->acc.p, 0, 3 * (size_t)K * m * sizeof(unsigned long long), st));
     HIP_TRY(hipMemsetAsync(c->blk_rays.p, 0, K * sizeof(unsigned long long), st));
     HIP_TRY(hipMemsetAsync(c->flags.p, 0, sizeof(uint32_t), st));
     HIP_TRY(hipMemsetAsync(c->cnt.p, 0, (size_t)kLevels * K * sizeof(uint32_t), st));
 
-    const uint32_t n_pass = (cfg->spp + spp_pass - 1) / spp_pass;
+    const uint32_t n_pass = (spp_left + spp_pass - 1) / spp_pass;
     const int n_depth = kMaxDepth;  // rays of depth 0..11 exist
     // PASSES THAT FOLLOW THE SCENE (k_pass_cand at the library's own pass size).  The reference looks at its stop flag every
     // 100 ms (mod.rs:947-958); here the flag is read between passes, so a pass must not take much longer than that WHATEVER a
@@ -460,7 +499,7 @@ int render_wavefront(pt_ctx *c, const pt_config *cfg, const FrameParams &frame, 
     constexpr uint64_t kProbeRays = 1ull << 20, kAdaptiveMinRays = 4ull << 20;
     constexpr double kPassTargetMs = 100.0;
     const bool adaptive = stack_form && !cfg->rays_per_pass && !c->tune.rays_per_pass && n_pass > 0u &&
-                          (uint64_t)npix * cfg->spp > kAdaptiveMinRays;
+                          (uint64_t)npix * spp_left > kAdaptiveMinRays;
     const char *const rate_key = pt_ctx_pass_kernel(c, cfg->flags);
     double rate = (adaptive && c->pass_rate_kernel == rate_key) ? c->pass_rate : 0.0;
     size_t ev_i = 0;
@@ -481,7 +520,7 @@ int render_wavefront(pt_ctx *c, const pt_config *cfg, const FrameParams &frame, 
     // the cancel byte is read at EVERY pass boundary (the reference polls it every 100 ms, mod.rs:947-958).
     const double cb_every_ms = cfg->progress_ms == PT_PROGRESS_EVERY_PASS ? 0.0 : (cfg->progress_ms ? (double)cfg->progress_ms : 500.0);
     double &cb_last_ms = c->cb_last_ms;  // (set when the call began: pt_ctx_render; a call rendered in parts keeps one clock)
-    uint32_t s_next = 0u, s_prev = 0u;  // samples of a pixel issued so far / in the pass before
+    uint32_t s_next = s_first, s_prev = 0u;  // samples of a pixel issued so far / in the pass before
     for (uint32_t p = 0; s_next < cfg->spp; ++p) {
         // keep two passes in flight; k_pass_cand's long passes (0.1 s) one - the cancel flag is looked at when a pass ends, and
         // the few microseconds between two launches are nothing against such a pass
@@ -584,7 +623,7 @@ int render_wavefront(pt_ctx *c, const pt_config *cfg, const FrameParams &frame, 
         stats->intersect_rays = total;
         stats->intersect_launches = one_kernel ? passes_done : passes_done * (uint32_t)n_depth;
         stats->passes = passes_done;
-        stats->samples = npix * (uint64_t)s_next;  // (every pass that was issued has run: the stream is synchronised)
+        stats->samples = npix * (uint64_t)(s_next - s_first);  // (every pass that was issued has run: the stream is synchronised)
         float ms = 0.0f;
         HIP_TRY(hipEventElapsedTime(&ms, ev_begin, ev_end));
         stats->ms_device = ms;
@@ -607,14 +646,19 @@ int render_wavefront(pt_ctx *c, const pt_config *cfg, const FrameParams &frame, 
     return PT_OK;
 }
 
+// Samples [s_first, cfg->spp) of every pixel of the part; the accumulators start from `held` (NULL: from zero).
 int render_mega(pt_ctx *c, const pt_config *cfg, const FrameParams &F, hipStream_t st, const volatile uint8_t *cancel,
-                pt_progress_fn cb, void *user, pt_stats *stats) {
+                pt_progress_fn cb, void *user, pt_stats *stats, uint32_t s_first, const HeldSums *held) {
     const uint64_t npix = F.npix;
+    const uint32_t spp_left = cfg->spp - s_first;  // samples per pixel this call traces
     int rc;
     if ((rc = c->acc.ensure(3 * npix)) || (rc = c->total_rays.ensure(16))) return rc;
     c->live_streams = 1;  // accumulators in pixel order
     c->live_m = (uint32_t)npix;
-    HIP_TRY(hipMemsetAsync(c->acc.p, 0, 3 * npix * sizeof(unsigned long long), st));
+    if (held)
+        launch_accum_gather(st, held->p, held->stride, (uint32_t)npix, 1u, (uint32_t)npix, c->acc.p);
+    else
+        HIP_TRY(hipMemsetAsync(c->acc.p, 0, 3 * npix * sizeof(unsigned long long), st));
     HIP_TRY(hipMemsetAsync(c->total_rays.p, 0, 16 * sizeof(unsigned long long), st));
     // The frame is cut into ROUNDS: one round = every pixel of the call x round_spp consecutive samples, one launch (a
     // lane = one pixel's samples of the round, walked one after the other).  A round is sized to about a tenth of a
@@ -628,7 +672,7 @@ int render_mega(pt_ctx *c, const pt_config *cfg, const FrameParams &F, hipStream
     const uint64_t round_budget = cfg->rays_per_pass ? cfg->rays_per_pass : (256ull << 20);  // primary samples per launch
     uint64_t round_spp64 = round_budget / npix;
     if (round_spp64 == 0) round_spp64 = 1;
-    if (round_spp64 > cfg->spp) round_spp64 = cfg->spp;
+    if (round_spp64 > spp_left) round_spp64 = spp_left;
     const uint32_t round_spp = (uint32_t)round_spp64;
     uint32_t n_split = 1;  // lanes per pixel within a round
     // (k_mega_cand hands its items out dynamically: finer ones - 8 per lane the chip holds, cornell 41.3 G bounces/s; 4: 39.1,
@@ -639,13 +683,13 @@ int render_mega(pt_ctx *c, const pt_config *cfg, const FrameParams &F, hipStream
     const uint64_t want_items = item_mult * lanes;
     while ((uint64_t)npix * n_split < want_items && n_split < round_spp) n_split *= 2;
     if (n_split > round_spp) n_split = round_spp;
-    const uint32_t n_rounds = (cfg->spp + round_spp - 1) / round_spp;
+    const uint32_t n_rounds = (spp_left + round_spp - 1) / round_spp;
     // rounds that follow the scene, as the wavefront's passes do (render_wavefront): a short timed first round, then as many
     // samples per round as the measured rate fits into 100 ms (+ a fifth) (at most 16 x the round before, at most round_spp), the rest
     // of the frame in equal rounds, one launch in flight; the rate stays with the context for the next frame
     constexpr uint64_t kProbeSamples = 1ull << 20, kAdaptiveMinSamples = 4ull << 20;
     constexpr double kRoundTargetMs = 100.0;
-    const bool adaptive = !cfg->rays_per_pass && (uint64_t)npix * cfg->spp > kAdaptiveMinSamples;
+    const bool adaptive = !cfg->rays_per_pass && (uint64_t)npix * spp_left > kAdaptiveMinSamples;
     double rate = adaptive ? c->round_rate : 0.0;
     hipEvent_t ev_begin = get_event(c, 0), ev_end = get_event(c, 1);
     hipEvent_t round_done[2] = {get_event(c, 2), get_event(c, 3)};
@@ -660,7 +704,7 @@ int render_mega(pt_ctx *c, const pt_config *cfg, const FrameParams &F, hipStream
     bool cancelled = false;
     uint32_t rounds_done = 0;
     uint64_t samples = 0;
-    uint32_t s_next = 0u, s_prev = 0u;
+    uint32_t s_next = s_first, s_prev = 0u;
     for (uint32_t r = 0; s_next < cfg->spp; ++r) {
         if (adaptive && r >= 1) {  // one launch in flight: its time sizes the next
             HIP_TRY(hipEventSynchronize(round_done[(r - 1) & 1]));
@@ -748,6 +792,74 @@ int render_mega(pt_ctx *c, const pt_config *cfg, const FrameParams &F, hipStream
     return PT_OK;
 }
 
+// pt_ctx_accumulate's frame key of a checked config (b, e: check_cfg's band)
+AccumKey accum_key(const pt_config *cfg, uint32_t b, uint32_t e) {
+    AccumKey k{};
+    k.width = cfg->width;
+    k.height = cfg->height;
+    k.idx_begin = b;
+    k.idx_end = e;
+    if (cfg->chunk_step > 1u) {
+        k.chunk_pixels = cfg->chunk_pixels;
+        k.chunk_first = cfg->chunk_first;
+        k.chunk_step = cfg->chunk_step;
+    }
+    k.seed = cfg->seed;
+    return k;
+}
+
+void accum_drop(pt_ctx *c) {
+    c->acc_on = false;
+    c->acc_cnt.clear();
+    c->acc_total = c->acc_part_px = 0;
+    c->acc_held.release();
+}
+
+// The checkpoint's scene fingerprint: SipHash-1-3 (zero key) over n_objs, n_tris (u32 each), then the camera, the objects and
+// the triangles as pt_ctx_set_scene got them
+uint64_t scene_fingerprint(const pt_camera *cam, const pt_object *objs, uint32_t n_objs, const pt_triangle *tris, uint32_t n_tris) {
+    std::vector<uint8_t> b(8 + sizeof(pt_camera) + (size_t)n_objs * sizeof(pt_object) + (size_t)n_tris * sizeof(pt_triangle));
+    uint8_t *w = b.data();
+    memcpy(w, &n_objs, 4);
+    memcpy(w + 4, &n_tris, 4);
+    w += 8;
+    memcpy(w, cam, sizeof(pt_camera));
+    w += sizeof(pt_camera);
+    if (n_objs) memcpy(w, objs, (size_t)n_objs * sizeof(pt_object));
+    w += (size_t)n_objs * sizeof(pt_object);
+    if (n_tris) memcpy(w, tris, (size_t)n_tris * sizeof(pt_triangle));
+    return pt_siphash(1, 3, 0, 0, b.data(), b.size());
+}
+
+// resolve part `i` of the held sums into the call's output: over its own count, black at 0
+int accum_resolve_part(pt_ctx *c, uint32_t i, float *out, hipStream_t st) {
+    const uint32_t k0 = i * c->acc_part_px, n = (c->acc_total - k0) < c->acc_part_px ? (c->acc_total - k0) : c->acc_part_px;
+    if (c->acc_cnt[i] != 0u)
+        launch_resolve(st, c->acc_held.p + k0, out + (size_t)k0 * 3, n, c->acc_cnt[i], 1u, c->acc_total);
+    else
+        HIP_TRY(hipMemsetAsync(out + (size_t)k0 * 3, 0, (size_t)n * 3 * sizeof(float), st));
+    return PT_OK;
+}
+
+
+// ---- checkpoint file (pt_ctx_accum_save / _load, ptrace.h): little-endian, the byte order of every target of this library
+constexpr char kCkptMagic[8] = {'P', 'T', 'A', 'C', 'C', 'U', 'M', '1'};
+constexpr uint32_t kCkptVersion = 1u;
+constexpr size_t kCkptHead = 8 + 4 + 7 * 4 + 8 + 8 + 3 * 4;  // magic .. number of parts: 68 bytes
+
+template <class T>
+void put(std::vector<uint8_t> &b, T v) {
+    const size_t at = b.size();
+    b.resize(at + sizeof v);
+    memcpy(b.data() + at, &v, sizeof v);
+}
+template <class T>
+T get(const uint8_t *&r) {
+    T v;
+    memcpy(&v, r, sizeof v);
+    r += sizeof v;
+    return v;
+}
 }  // namespace
 
 extern "C" {
@@ -854,6 +966,7 @@ void pt_ctx_destroy(pt_ctx *c) {
     c->flags.release();
     c->blk_rays.release();
     c->acc.release();
+    c->acc_held.release();
     c->total_rays.release();
     (void)hipStreamDestroy(c->stream);
     delete c;
@@ -872,6 +985,8 @@ int pt_ctx_set_scene(pt_ctx *c, const pt_camera *cam, const pt_object *objs, uin
         return PT_ERR_INVALID;
     }
     HIP_TRY(hipSetDevice(c->device));
+    accum_drop(c);  // (the held sums are of the scene before)
+    c->scene_fp = 0;
     int rc;
     if ((rc = c->d_objs.ensure(fs.objs.size())) || (rc = c->d_opairs.ensure(fs.obj_pairs.size())) || (rc = c->d_tris.ensure(fs.tri_pairs.size())) ||
         (rc = c->d_mats.ensure(fs.mats.size())) || (rc = c->d_tshade.ensure(fs.tri_shade.size())) ||
@@ -982,6 +1097,7 @@ int pt_ctx_set_scene(pt_ctx *c, const pt_camera *cam, const pt_object *objs, uin
     c->has_scene = true;
     c->pass_rate = c->round_rate = 0.0;  // (another scene: the passes' length is measured again)
     c->pass_rate_kernel = nullptr;
+    c->scene_fp = scene_fingerprint(cam, objs, n_objs, tris, n_tris);
     return PT_OK;
 }
 
@@ -1193,8 +1309,7 @@ int pt_ctx_render(pt_ctx *c, const pt_config *cfg, void *d_out_rgb, void *hip_st
     // cancelled call leaves the parts it did not start black (the reference's unrendered pixels are black too,
     // mod.rs:1003-1016) and the part in progress averaged over its accumulated samples.
     const uint32_t total = F.npix;
-    const bool in_parts = cfg->backend == PT_BACKEND_WAVEFRONT && total > (3u << 19);
-    const uint32_t part_px = in_parts ? (1u << 20) : total;
+    const uint32_t part_px = part_pixels(total, cfg->backend == PT_BACKEND_WAVEFRONT);
     const uint32_t n_parts = (total + part_px - 1u) / part_px;
     struct Relay {
         pt_progress_fn cb;
@@ -1234,9 +1349,9 @@ int pt_ctx_render(pt_ctx *c, const pt_config *cfg, void *d_out_rgb, void *hip_st
         pt_progress_fn part_cb = cb ? (n_parts > 1u ? &Relay::fn : cb) : nullptr;
         void *part_user = n_parts > 1u ? (void *)&relay : user;
         if (cfg->backend == PT_BACKEND_WAVEFRONT)
-            rc = render_wavefront(c, cfg, Fp, st, cancel, part_cb, part_user, &ps);
+            rc = render_wavefront(c, cfg, Fp, st, cancel, part_cb, part_user, &ps, 0u, nullptr);
         else
-            rc = render_mega(c, cfg, Fp, st, cancel, part_cb, part_user, &ps);
+            rc = render_mega(c, cfg, Fp, st, cancel, part_cb, part_user, &ps, 0u, nullptr);
         if (rc == PT_OK || rc == PT_CANCELLED) {
             // A cancelled part resolves what was accumulated by the samples per pixel that were accumulated
             // (live_spp_issued, also reported through stats->samples): every pixel at full brightness over fewer
@@ -1271,6 +1386,352 @@ int pt_ctx_render(pt_ctx *c, const pt_config *cfg, void *d_out_rgb, void *hip_st
     c->live_npix = 0;
     c->live_out = nullptr;
     return rc;
+}
+
+int pt_ctx_accumulate(pt_ctx *c, const pt_config *cfg, void *d_out_rgb, void *hip_stream, const volatile uint8_t *cancel,
+                      pt_progress_fn cb, void *user, pt_stats *stats) {
+    if (!c || !d_out_rgb || !cfg) {
+        set_error("NULL argument");
+        return PT_ERR_INVALID;
+    }
+    if (!c->has_scene) {
+        set_error("no scene set");
+        return PT_ERR_INVALID;
+    }
+    uint32_t ib = 0, ie = 0;
+    int rc = check_cfg(cfg, &ib, &ie);
+    if (rc) return rc;
+    if (((cfg->flags >> 8) & 15u) > 1u) {
+        set_error("pt_ctx_accumulate does not take PT_FLAG_PIPELINES: its accumulators live in child contexts");
+        return PT_ERR_INVALID;
+    }
+    const AccumKey key = accum_key(cfg, ib, ie);
+    const uint32_t total = owned_pixels(cfg, ib, ie);
+    if (c->acc_on && c->acc_key == key) {
+        uint32_t held_max = 0;
+        for (uint32_t v : c->acc_cnt) held_max = v > held_max ? v : held_max;
+        if (cfg->spp < held_max) {
+            set_error("cfg->spp (" + std::to_string(cfg->spp) + ") is below the " + std::to_string(held_max) +
+                      " samples per pixel held for this frame: samples cannot be removed (pt_ctx_accum_reset starts over)");
+            return PT_ERR_INVALID;
+        }
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (total == 0u) return PT_OK;  // this rank owns no chunk of the band
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    const uint32_t part_px = part_pixels(total, true);  // counts are kept per part as the wavefront cuts a call, whatever the backend
+    const uint32_t n_parts = (total + part_px - 1u) / part_px;
+    if (!(c->acc_on && c->acc_key == key)) {  // another frame (or none): start from zero
+        accum_drop(c);
+        if ((rc = c->acc_held.ensure(3 * (size_t)total))) return rc;
+        HIP_TRY(hipMemsetAsync(c->acc_held.p, 0, 3 * (size_t)total * sizeof(unsigned long long), st));
+        c->acc_key = key;
+        c->acc_total = total;
+        c->acc_part_px = part_px;
+        c->acc_cnt.assign(n_parts, 0u);
+        c->acc_on = true;
+    }
+    const FrameParams F = make_frame(c, cfg, ib, ie);
+    c->scene.n_bvh_nodes = (cfg->flags & PT_FLAG_NO_BVH) ? 0u : c->n_bvh_nodes;
+    c->scene.planar = (cfg->flags & PT_FLAG_NO_BVH) ? 0u : 1u;
+    c->scene.cand_scan = cand_scan_for(c, cfg->flags);
+    const double t0 = now_ms();
+    // What to render: each part from its own count; the megakernel, which renders a call at once, takes the whole call in one go
+    // when every part holds the same count
+    struct Job {
+        uint32_t k0, n, part_lo, part_hi;  // pixels [k0, k0 + n) = parts [part_lo, part_hi)
+    };
+    std::vector<Job> jobs;
+    bool even = true;
+    for (uint32_t v : c->acc_cnt) even = even && v == c->acc_cnt[0];
+    if (cfg->backend == PT_BACKEND_MEGAKERNEL && even)
+        jobs.push_back({0u, total, 0u, n_parts});
+    else
+        for (uint32_t i = 0; i < n_parts; ++i) jobs.push_back({i * part_px, (total - i * part_px) < part_px ? (total - i * part_px) : part_px, i, i + 1u});
+    struct Relay {  // a job's fractions as fractions of the call (by pixels); its completion is reported by the next job / the end
+        pt_progress_fn cb;
+        void *user;
+        float base, scale;
+        static void fn(void *self, float f) {
+            Relay *r = (Relay *)self;
+            if (f < 1.0f) r->cb(r->user, r->base + r->scale * f);
+        }
+    } relay{cb, user, 0.0f, 1.0f};
+    c->live_out = (float *)d_out_rgb;
+    c->live_total = total;
+    c->live_stream = st;
+    c->live_accum = true;
+    c->cb_last_ms = now_ms();
+    const double cb_every_ms = cfg->progress_ms == PT_PROGRESS_EVERY_PASS ? 0.0 : (cfg->progress_ms ? (double)cfg->progress_ms : 500.0);
+    rc = PT_OK;
+    bool started = false;
+    for (const Job &j : jobs) {
+        const uint32_t s_first = c->acc_cnt[j.part_lo];  // (a job of several parts: all at this count)
+        if (s_first >= cfg->spp) continue;  // nothing left to trace here
+        if (cb && started) {  // a job boundary is a progress point of its own, as a part boundary of pt_ctx_render
+            const double t_now = now_ms();
+            if (t_now - c->cb_last_ms >= cb_every_ms) {
+                c->cb_last_ms = t_now;
+                cb(user, (float)j.k0 / (float)total);
+            }
+        }
+        started = true;
+        FrameParams Fp = F;
+        Fp.k_begin = j.k0;
+        Fp.npix = j.n;
+        c->live_k0 = j.k0;
+        c->live_npix = j.n;
+        c->live_spp_issued = s_first;
+        relay.base = (float)j.k0 / (float)total;
+        relay.scale = (float)j.n / (float)total;
+        const HeldSums held{c->acc_held.p + j.k0, total};
+        pt_stats ps;
+        memset(&ps, 0, sizeof ps);
+        pt_progress_fn job_cb = cb ? &Relay::fn : nullptr;
+        if (cfg->backend == PT_BACKEND_WAVEFRONT)
+            rc = render_wavefront(c, cfg, Fp, st, cancel, job_cb, &relay, &ps, s_first, &held);
+        else
+            rc = render_mega(c, cfg, Fp, st, cancel, job_cb, &relay, &ps, s_first, &held);
+        if (rc == PT_OK || rc == PT_CANCELLED) {
+            // every pass that was issued has run (the renderers synchronise the stream): keep them
+            const uint32_t done = rc == PT_OK ? cfg->spp : c->live_spp_issued;
+            if (done > s_first) {
+                if ((uint64_t)c->live_streams * c->live_m < j.n || (uint64_t)c->live_streams * c->live_m > 0xffffffffull) {
+                    set_error("accumulator layout does not cover the part");
+                    rc = PT_ERR_HIP;
+                } else {
+                    launch_accum_scatter(st, c->acc.p, j.n, c->live_streams, c->live_m, c->acc_held.p + j.k0, total);
+                    hipError_t e = hipGetLastError();
+                    if (e == hipSuccess) e = hipStreamSynchronize(st);
+                    if (e != hipSuccess) {
+                        set_error(std::string("storing the held sums: ") + hipGetErrorString(e));
+                        rc = PT_ERR_HIP;
+                        accum_drop(c);  // (their state is unknown)
+                    } else {
+                        for (uint32_t i = j.part_lo; i < j.part_hi; ++i) c->acc_cnt[i] = done;
+                    }
+                }
+            }
+        }
+        if (stats) {
+            stats->ray_bounces += ps.ray_bounces;
+            stats->samples += ps.samples;
+            stats->intersect_rays += ps.intersect_rays;
+            stats->intersect_launches += ps.intersect_launches;
+            stats->passes += ps.passes;
+            stats->ms_device += ps.ms_device;
+            stats->ms_intersect += ps.ms_intersect;
+        }
+        if (rc != PT_OK) break;
+    }
+    if (rc == PT_OK || rc == PT_CANCELLED) {  // the output: every part over its own count
+        for (uint32_t i = 0; i < n_parts; ++i) {
+            const int r2 = accum_resolve_part(c, i, (float *)d_out_rgb, st);
+            if (r2) {
+                rc = r2;
+                break;
+            }
+        }
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess && (rc == PT_OK || rc == PT_CANCELLED)) {
+            set_error(std::string("resolving the held sums: ") + hipGetErrorString(e));
+            rc = PT_ERR_HIP;
+        }
+    }
+    if (rc == PT_CANCELLED) set_error("cancelled");
+    if (cb && rc == PT_OK) cb(user, 1.0f);
+    if (stats) stats->ms_total = now_ms() - t0;
+    c->scene.n_bvh_nodes = c->n_bvh_nodes;
+    c->scene.planar = 1u;
+    c->scene.cand_scan = cand_scan_for(c, 0u);
+    c->live_npix = 0;
+    c->live_out = nullptr;
+    c->live_accum = false;
+    return rc;
+}
+
+int pt_ctx_accum_info(const pt_ctx *c, const pt_config *cfg, uint32_t *spp_min, uint32_t *spp_max) {
+    if (!c || !cfg || !spp_min || !spp_max) {
+        set_error("NULL argument");
+        return PT_ERR_INVALID;
+    }
+    uint32_t ib = 0, ie = 0;
+    const int rc = check_cfg(cfg, &ib, &ie);
+    if (rc) return rc;
+    *spp_min = *spp_max = 0u;
+    if (!c->acc_on || !(c->acc_key == accum_key(cfg, ib, ie)) || c->acc_cnt.empty()) return PT_OK;
+    uint32_t lo = 0xffffffffu, hi = 0u;
+    for (uint32_t v : c->acc_cnt) {
+        lo = v < lo ? v : lo;
+        hi = v > hi ? v : hi;
+    }
+    *spp_min = lo;
+    *spp_max = hi;
+    return PT_OK;
+}
+
+int pt_ctx_accum_reset(pt_ctx *c) {
+    if (!c) {
+        set_error("ctx is NULL");
+        return PT_ERR_INVALID;
+    }
+    if (c->acc_held.p) HIP_TRY(hipSetDevice(c->device));
+    accum_drop(c);
+    return PT_OK;
+}
+
+int pt_ctx_accum_save(pt_ctx *c, const char *path) {
+    if (!c || !path) {
+        set_error("NULL argument");
+        return PT_ERR_INVALID;
+    }
+    if (!c->acc_on) {
+        set_error("nothing accumulated on this context");
+        return PT_ERR_INVALID;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t n_sums = 3 * (size_t)c->acc_total;
+    std::vector<uint8_t> b;
+    b.reserve(kCkptHead + 4 * c->acc_cnt.size() + 8 * n_sums + 8);
+    b.insert(b.end(), kCkptMagic, kCkptMagic + 8);
+    put<uint32_t>(b, kCkptVersion);
+    const AccumKey &k = c->acc_key;
+    for (uint32_t v : {k.width, k.height, k.idx_begin, k.idx_end, k.chunk_pixels, k.chunk_first, k.chunk_step}) put<uint32_t>(b, v);
+    put<uint64_t>(b, k.seed);
+    put<uint64_t>(b, c->scene_fp);
+    put<uint32_t>(b, c->acc_total);
+    put<uint32_t>(b, c->acc_part_px);
+    put<uint32_t>(b, (uint32_t)c->acc_cnt.size());
+    for (uint32_t v : c->acc_cnt) put<uint32_t>(b, v);
+    const size_t at = b.size();
+    b.resize(at + 8 * n_sums);
+    HIP_TRY(hipMemcpy(b.data() + at, c->acc_held.p, 8 * n_sums, hipMemcpyDeviceToHost));
+    put<uint64_t>(b, pt_siphash(1, 3, 0, 0, b.data(), b.size()));
+    // written next to the target and renamed over it: a process that dies while saving leaves the last checkpoint whole
+    const std::string tmp = std::string(path) + ".tmp";
+    FILE *f = fopen(tmp.c_str(), "wb");
+    if (!f) {
+        set_error(std::string("cannot open ") + tmp + " for writing: " + strerror(errno));
+        return PT_ERR_IO;
+    }
+    const bool ok = fwrite(b.data(), 1, b.size(), f) == b.size();
+    if (fclose(f) != 0 || !ok) {
+        set_error(std::string("cannot write ") + tmp);
+        remove(tmp.c_str());
+        return PT_ERR_IO;
+    }
+    if (rename(tmp.c_str(), path) != 0) {
+        set_error(std::string("cannot rename ") + tmp + " to " + path + ": " + strerror(errno));
+        remove(tmp.c_str());
+        return PT_ERR_IO;
+    }
+    return PT_OK;
+}
+
+int pt_ctx_accum_load(pt_ctx *c, const char *path) {
+    if (!c || !path) {
+        set_error("NULL argument");
+        return PT_ERR_INVALID;
+    }
+    if (!c->has_scene) {
+        set_error("no scene set: a checkpoint is loaded under the scene it was rendered from");
+        return PT_ERR_INVALID;
+    }
+    FILE *f = fopen(path, "rb");
+    if (!f) {
+        set_error(std::string("cannot open ") + path + ": " + strerror(errno));
+        return PT_ERR_IO;
+    }
+    struct Closer {
+        FILE *f;
+        ~Closer() { fclose(f); }
+    } closer{f};
+    if (fseeko(f, 0, SEEK_END) != 0) {
+        set_error(std::string("cannot read ") + path);
+        return PT_ERR_IO;
+    }
+    const off_t fsize = ftello(f);
+    if (fsize < 0 || fseeko(f, 0, SEEK_SET) != 0) {
+        set_error(std::string("cannot read ") + path);
+        return PT_ERR_IO;
+    }
+    auto bad = [&](const std::string &why) {
+        set_error(std::string(path) + " is not a checkpoint of this library: " + why);
+        return PT_ERR_PARSE;
+    };
+    if ((uint64_t)fsize < kCkptHead + 8) return bad("too short");
+    std::vector<uint8_t> b(kCkptHead);
+    if (fread(b.data(), 1, kCkptHead, f) != kCkptHead) {
+        set_error(std::string("cannot read ") + path);
+        return PT_ERR_IO;
+    }
+    const uint8_t *r = b.data();
+    if (memcmp(r, kCkptMagic, 8) != 0) return bad("wrong magic");
+    r += 8;
+    if (get<uint32_t>(r) != kCkptVersion) return bad("unknown format version");
+    AccumKey k{};
+    k.width = get<uint32_t>(r);
+    k.height = get<uint32_t>(r);
+    k.idx_begin = get<uint32_t>(r);
+    k.idx_end = get<uint32_t>(r);
+    k.chunk_pixels = get<uint32_t>(r);
+    k.chunk_first = get<uint32_t>(r);
+    k.chunk_step = get<uint32_t>(r);
+    k.seed = get<uint64_t>(r);
+    const uint64_t fp = get<uint64_t>(r);
+    const uint32_t total = get<uint32_t>(r), part_px = get<uint32_t>(r), n_parts = get<uint32_t>(r);
+    // the key must be one check_cfg accepts and accum_key writes, and the sizes must be the ones it implies
+    pt_config kc{};
+    kc.width = k.width;
+    kc.height = k.height;
+    kc.spp = 1;
+    kc.idx_begin = k.idx_begin;
+    kc.idx_end = k.idx_end;
+    kc.chunk_pixels = k.chunk_pixels;
+    kc.chunk_first = k.chunk_first;
+    kc.chunk_step = k.chunk_step;
+    kc.seed = k.seed;
+    uint32_t ib = 0, ie = 0;
+    if (check_cfg(&kc, &ib, &ie) != PT_OK || !(accum_key(&kc, ib, ie) == k)) return bad("the frame key is not a valid frame");
+    const uint32_t want_total = owned_pixels(&kc, ib, ie);
+    if (total != want_total || want_total == 0u || part_px != part_pixels(total, true) || n_parts != (total + part_px - 1u) / part_px)
+        return bad("sizes that do not fit each other");
+    const uint64_t want_size = kCkptHead + 4ull * n_parts + 24ull * total + 8ull;
+    if ((uint64_t)fsize != want_size) return bad((uint64_t)fsize < want_size ? "truncated" : "trailing bytes");
+    b.resize((size_t)want_size);
+    if (fread(b.data() + kCkptHead, 1, (size_t)want_size - kCkptHead, f) != (size_t)want_size - kCkptHead) {
+        set_error(std::string("cannot read ") + path);
+        return PT_ERR_IO;
+    }
+    uint64_t tag;
+    memcpy(&tag, b.data() + want_size - 8, 8);
+    if (tag != pt_siphash(1, 3, 0, 0, b.data(), (size_t)want_size - 8)) return bad("bad trailing hash");
+    std::vector<uint32_t> cnt(n_parts);
+    memcpy(cnt.data(), b.data() + kCkptHead, 4 * (size_t)n_parts);
+    for (uint32_t v : cnt)
+        if (v > (1u << 24)) return bad("a sample count above 2^24");
+    if (fp != c->scene_fp) {
+        set_error(std::string(path) + " was rendered from another scene than the one set on this context");
+        return PT_ERR_INVALID;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    accum_drop(c);
+    int rc = c->acc_held.ensure(3 * (size_t)total);
+    if (rc) return rc;
+    const hipError_t e = hipMemcpy(c->acc_held.p, b.data() + kCkptHead + 4 * (size_t)n_parts, 24 * (size_t)total, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        set_error(std::string("uploading the checkpoint: ") + hipGetErrorString(e));
+        accum_drop(c);
+        return PT_ERR_HIP;
+    }
+    c->acc_key = k;
+    c->acc_total = total;
+    c->acc_part_px = part_px;
+    c->acc_cnt = cnt;
+    c->acc_on = true;
+    return PT_OK;
 }
 
 int pt_ctx_radiance(pt_ctx *c, const float o[3], const float d[3], uint32_t depth, uint32_t n_samples, uint64_t seed,
@@ -1316,8 +1777,8 @@ int pt_ctx_radiance(pt_ctx *c, const float o[3], const float d[3], uint32_t dept
     pt_stats ps;
     memset(&ps, 0, sizeof ps);
     hipStream_t st = c->stream;
-    int rc = backend == PT_BACKEND_WAVEFRONT ? render_wavefront(c, &cfg, F, st, nullptr, nullptr, nullptr, &ps)
-                                             : render_mega(c, &cfg, F, st, nullptr, nullptr, nullptr, &ps);
+    int rc = backend == PT_BACKEND_WAVEFRONT ? render_wavefront(c, &cfg, F, st, nullptr, nullptr, nullptr, &ps, 0u, nullptr)
+                                             : render_mega(c, &cfg, F, st, nullptr, nullptr, nullptr, &ps, 0u, nullptr);
     c->scene.n_bvh_nodes = c->n_bvh_nodes;
     c->scene.planar = 1u;
     c->scene.cand_scan = cand_scan_for(c, 0u);
@@ -1536,6 +1997,19 @@ int pt_ctx_snapshot(pt_ctx *c, void *d_out_rgb, uint32_t *spp_done) {
     // the parts not started are black.
     float *snap = (float *)d_out_rgb;
     hipStream_t st = c->live_stream;
+    if (c->live_accum) {  // pt_ctx_accumulate: every part outside the one in progress at its own count, from the held sums
+        for (uint32_t i = 0; i < (uint32_t)c->acc_cnt.size(); ++i) {
+            const uint32_t k0 = i * c->acc_part_px;
+            if (k0 >= c->live_k0 && k0 < c->live_k0 + c->live_npix) continue;
+            int rc = accum_resolve_part(c, i, snap, st);
+            if (rc) return rc;
+        }
+        launch_resolve(st, c->acc.p, snap + (size_t)c->live_k0 * 3, c->live_npix, c->live_spp_issued, c->live_streams, c->live_m);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(st));
+        if (spp_done) *spp_done = c->live_spp_issued;
+        return PT_OK;
+    }
     if (c->live_k0 != 0u && c->live_out && c->live_out != snap)
         HIP_TRY(hipMemcpyAsync(snap, c->live_out, (size_t)c->live_k0 * 3 * sizeof(float), hipMemcpyDeviceToDevice, st));
     launch_resolve(st, c->acc.p, snap + (size_t)c->live_k0 * 3, c->live_npix, c->live_spp_issued, c->live_streams, c->live_m);

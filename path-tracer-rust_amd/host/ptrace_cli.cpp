@@ -20,7 +20,10 @@
 static void usage() {
     fprintf(stderr,
             "usage: ptrace <samplesPerPixel> <y-resolution> <scene id|index> [--width W] [--backend wavefront|megakernel]\n"
-            "              [--seed S] [--gpus N] [--root DIR] [--out DIR] [--no-ppm]\n");
+            "              [--seed S] [--gpus N] [--root DIR] [--out DIR] [--no-ppm] [--checkpoint FILE]\n"
+            "  --checkpoint FILE: continue from the samples FILE holds (if it exists), render up to <samplesPerPixel> in all and\n"
+            "                     save them to FILE; one GPU only; the seed defaults to 0 instead of the clock, so that the same\n"
+            "                     command continues the same frame\n");
 }
 
 static std::vector<std::string> scene_ids(const std::string &root) {
@@ -41,6 +44,59 @@ static void progress(void *, float f) {
     fflush(stderr);
 }
 
+constexpr int kCliExit = 1000;  // render_checkpointed: the message is out, exit 1
+
+// --checkpoint: one context on one GPU, the frame accumulated from what FILE holds up to cfg->spp, FILE saved again
+static int render_checkpointed(const pt_config *cfg, pt_scene *sc, const std::string &file, std::vector<float> &img, pt_stats *st) {
+    int dev = 0;
+    if (const char *e = getenv("PT_DEVICE")) dev = atoi(e);
+    uint32_t n_objs = 0, n_tris = 0;
+    const pt_object *objs = pt_scene_objects(sc, &n_objs);
+    const pt_triangle *tris = pt_scene_triangles(sc, &n_tris);
+    pt_ctx *ctx = nullptr;
+    int rc = pt_ctx_create(dev, &ctx);
+    if (!rc) rc = pt_ctx_set_scene(ctx, pt_scene_camera(sc), objs, n_objs, tris, n_tris);
+    if (!rc && access(file.c_str(), F_OK) == 0) {
+        rc = pt_ctx_accum_load(ctx, file.c_str());
+        if (rc) {
+            fprintf(stderr, "cannot resume from %s (%d): %s\n", file.c_str(), rc, pt_last_error());
+            pt_ctx_destroy(ctx);
+            return kCliExit;
+        }
+        uint32_t lo = 0, hi = 0;
+        rc = pt_ctx_accum_info(ctx, cfg, &lo, &hi);
+        if (!rc && hi == 0u) {
+            fprintf(stderr, "checkpoint %s is of another frame (size, seed or scene): not resumed\n", file.c_str());
+            pt_ctx_destroy(ctx);
+            return kCliExit;
+        }
+        if (!rc && hi > cfg->spp) {
+            fprintf(stderr, "checkpoint %s holds %u samples per pixel, more than the %u asked for\n", file.c_str(), hi, cfg->spp);
+            pt_ctx_destroy(ctx);
+            return kCliExit;
+        }
+        if (!rc) {
+            if (lo == hi)
+                printf("Resuming from %u samples per pixel\n", lo);
+            else
+                printf("Resuming from %u samples per pixel (up to %u)\n", lo, hi);
+            fflush(stdout);
+        }
+    }
+    void *d_out = nullptr;
+    const size_t bytes = img.size() * sizeof(float);
+    if (!rc) rc = pt_device_malloc(dev, bytes, &d_out);
+    if (!rc) rc = pt_ctx_accumulate(ctx, cfg, d_out, nullptr, nullptr, progress, nullptr, st);
+    if (!rc) rc = pt_device_download(dev, img.data(), d_out, bytes);
+    if (!rc) {
+        rc = pt_ctx_accum_save(ctx, file.c_str());
+        if (rc) fprintf(stderr, "cannot save checkpoint %s: %s\n", file.c_str(), pt_last_error());
+    }
+    if (d_out) pt_device_free(dev, d_out);
+    if (ctx) pt_ctx_destroy(ctx);
+    return rc;
+}
+
 int main(int argc, char **argv) {
     if (argc < 4) {
         usage();
@@ -51,6 +107,8 @@ int main(int argc, char **argv) {
     std::string scene_arg = argv[3], root = ".", out_dir = "out", backend = "wavefront";
     uint32_t width = res_y * 3 / 2;
     uint64_t seed = (uint64_t)time(nullptr);
+    bool seed_given = false;
+    std::string checkpoint;
     bool write_ppm = true;
     uint32_t gpus = 1;
     for (int i = 4; i < argc; ++i) {
@@ -58,7 +116,17 @@ int main(int argc, char **argv) {
         auto next = [&]() -> const char * { return i + 1 < argc ? argv[++i] : ""; };
         if (a == "--width") width = (uint32_t)strtoul(next(), nullptr, 10);
         else if (a == "--backend") backend = next();
-        else if (a == "--seed") seed = strtoull(next(), nullptr, 10);
+        else if (a == "--seed") {
+            seed = strtoull(next(), nullptr, 10);
+            seed_given = true;
+        }
+        else if (a == "--checkpoint") {
+            checkpoint = next();
+            if (checkpoint.empty()) {
+                usage();
+                return 1;
+            }
+        }
         else if (a == "--gpus") gpus = (uint32_t)strtoul(next(), nullptr, 10);
         else if (a == "--root") root = next();
         else if (a == "--out") out_dir = next();
@@ -72,6 +140,11 @@ int main(int argc, char **argv) {
         usage();
         return 1;
     }
+    if (!checkpoint.empty() && gpus > 1) {
+        fprintf(stderr, "--checkpoint works with one GPU only (--gpus %u)\n", gpus);
+        return 1;
+    }
+    if (!checkpoint.empty() && !seed_given) seed = 0;
     // load_scene_ids (scenes.rs:28-38): a scenes/ directory without any *.json is filled with the built-in scenes
     if (scene_ids(root).empty()) {
         mkdir((root + "/scenes").c_str(), 0777);
@@ -116,8 +189,15 @@ int main(int argc, char **argv) {
     cfg.seed = seed;
     std::vector<float> img((size_t)width * res_y * 3, 0.0f);
     pt_stats st;
-    rc = pt_render_multi(&cfg, gpus ? gpus : 1, pt_scene_camera(sc), objs, n_objs, tris, n_tris, img.data(), nullptr,
-                         progress, nullptr, &st);
+    if (checkpoint.empty())
+        rc = pt_render_multi(&cfg, gpus ? gpus : 1, pt_scene_camera(sc), objs, n_objs, tris, n_tris, img.data(), nullptr,
+                             progress, nullptr, &st);
+    else
+        rc = render_checkpointed(&cfg, sc, checkpoint, img, &st);
+    if (rc == kCliExit) {
+        pt_scene_free(sc);
+        return 1;
+    }
     fprintf(stderr, "\n");
     if (rc) {
         fprintf(stderr, "render failed (%d): %s\n", rc, pt_last_error());
