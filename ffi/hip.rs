@@ -142,6 +142,18 @@ extern "C" {
     pub fn pt_ctx_accum_reset(ctx: *mut PtCtx) -> i32;
     pub fn pt_ctx_accum_save(ctx: *mut PtCtx, path: *const c_char) -> i32;
     pub fn pt_ctx_accum_load(ctx: *mut PtCtx, path: *const c_char) -> i32;
+    // first-hit AOVs of the frame cfg describes (device buffers, any may be null): mean albedo and ray-facing normal over the
+    // first cfg.spp samples, sample 0's depth and object id - a denoiser's guides, a pick map
+    pub fn pt_ctx_render_aov(
+        ctx: *mut PtCtx,
+        cfg: *const PtConfig,
+        d_albedo: *mut f32,
+        d_normal: *mut f32,
+        d_depth: *mut f32,
+        d_object_id: *mut i32,
+        hip_stream: *mut c_void,
+    ) -> i32;
+    pub fn pt_write_pfm(path: *const c_char, data: *const f32, width: u32, height: u32, channels: u32) -> i32;
     pub fn pt_device_malloc(device: i32, bytes: usize, out: *mut *mut c_void) -> i32;
     pub fn pt_device_free(device: i32, p: *mut c_void) -> i32;
     pub fn pt_device_download(device: i32, dst_host: *mut c_void, src_device: *const c_void, bytes: usize) -> i32;

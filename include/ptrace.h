@@ -370,6 +370,30 @@ int pt_ctx_accum_save(pt_ctx *ctx, const char *path);
  * each of these the held accumulator is left as it was.  No input crashes the loader. */
 int pt_ctx_accum_load(pt_ctx *ctx, const char *path);
 
+/* ---- first-hit AOVs: guide buffers for a denoiser, a pick map for a GUI ------------------------------------------
+ * pt_ctx_render_aov covers the pixels pt_ctx_render covers with the same cfg - pt_config_pixels(cfg) of them, in the same
+ * order (the band [idx_begin, idx_end) and the interleaved chunks included); pixel k of the call has framebuffer index p.
+ * For each sample s in [0, cfg->spp) the ray is render_pixel's ray for (seed; p, s) (mod.rs:812-843), bit for bit what
+ * pt_ctx_primary_rays returns and what the frame kernels trace - so these are the first cfg->spp samples of the frame with
+ * that seed, a prefix of a frame rendered at more - and h = intersect_scene(ray) (mod.rs:631-659).  FIRST HIT only: a
+ * mirror or glass surface gives its own colour and normal (following delta chains would draw random numbers).
+ * - albedo[3k+c] = sum over s of (colour[c] of the object hit, 0 on a miss) / spp
+ * - normal[3k+c] = sum over s of (normal_towards_ray[c], 0 on a miss) / spp, not renormalised; normal_towards_ray is the hit
+ *   normal flipped to face the ray, as radiance() computes it (mod.rs:669-673)
+ * - depth[k] = sample 0's hit.distance, +inf on a miss
+ * - object_id[k] = sample 0's object index (pt_ctx_set_scene order), -1 on a miss
+ * Sums are 32.32 fixed point, as the frame accumulator's, so the result does not depend on how samples are spread over the
+ * device: colours to_fixed(v), normal components sign(v) * to_fixed(|v|) summed in two's-complement int64; each mean is
+ * (float)((double)sum * 2^-32) / (float)spp, not clamped.
+ * Device pointers, pt_config_pixels(cfg) * 3 floats (albedo, normal) or * 1 (depth, object_id); any may be NULL and is then
+ * skipped; all four NULL is PT_ERR_INVALID.  PT_FLAG_NO_BVH selects the linear scan (same results); backend, rays_per_pass,
+ * progress_ms, PT_FLAG_SEPARATE_KERNELS and PT_FLAG_PIPELINES are ignored.  PT_ERR_INVALID also for a NULL ctx or cfg, no
+ * scene, spp 0 or above 2^24, and whatever pt_ctx_render refuses about the band or the chunks; PT_ERR_HIP for HIP failures.
+ * `hip_stream` as for pt_ctx_render (NULL = the context's own stream); blocking.  The call changes no other state of the
+ * context: not the frame accumulators, not pt_ctx_accumulate's held sums or counts, not the measured pass rates. */
+int pt_ctx_render_aov(pt_ctx *ctx, const pt_config *cfg, float *d_albedo, float *d_normal, float *d_depth,
+                      int32_t *d_object_id, void *hip_stream);
+
 /* ---- the one collective of the path: the framebuffer gather over RCCL (xGMI) ---------------------------------
  * One process (or thread) per GPU renders its rows with pt_ctx_render (chunk_first = rank, chunk_step = n_ranks) into
  * device memory; pt_comm_gather_frame then gives EVERY rank the whole frame in device memory: one in-place
@@ -437,6 +461,12 @@ float pt_gamma_correction(float x);
 uint32_t pt_to_int_with_gamma_correction(float x);
 int pt_write_ppm(const char *path, const float *rgb, uint32_t width, uint32_t height, uint32_t spp,
                  const char *scene_id, uint64_t seconds);
+/* A whole frame (framebuffer order, width * height * channels floats) as a little-endian PFM: "PF" for 3 channels, "Pf" for 1
+ * (any other count: PT_ERR_INVALID), scale -1.0; PT_ERR_IO when the file cannot be written.  Placed pixel for pixel over
+ * pt_write_ppm's image of the same frame: the PPM lists framebuffer index i as pixel W*H-1-i from the top left, and PFM
+ * stores rows bottom-up, so PFM row q (from the bottom), column c holds framebuffer index q*W + (W-1-c) - each framebuffer
+ * row in turn, its columns reversed. */
+int pt_write_pfm(const char *path, const float *data, uint32_t width, uint32_t height, uint32_t channels);
 
 #ifdef __cplusplus
 }

@@ -83,6 +83,9 @@ def lib():
     L.pt_ctx_accum_reset.argtypes = [C.c_void_p]
     L.pt_ctx_accum_save.argtypes = [C.c_void_p, C.c_char_p]
     L.pt_ctx_accum_load.argtypes = [C.c_void_p, C.c_char_p]
+    L.pt_ctx_render_aov.argtypes = [C.c_void_p, C.POINTER(pt_config), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p]
+    L.pt_write_pfm.argtypes = [C.c_char_p, C.POINTER(C.c_float), C.c_uint32, C.c_uint32, C.c_uint32]
     L.pt_ctx_set_profiling.argtypes = [C.c_void_p, C.c_int]
     L.pt_ctx_pass_kernel.argtypes = [C.c_void_p, C.c_uint32]
     L.pt_ctx_pass_kernel.restype = C.c_char_p
@@ -199,6 +202,19 @@ class Context:
         _check(lib().pt_ctx_accum_info(self._h, C.byref(cfg), C.byref(lo), C.byref(hi)))
         return lo.value, hi.value
 
+    def render_aov(self, width, height, spp, seed=1, band=None, chunks=None, albedo=None, normal=None, depth=None,
+                   object_id=None, no_bvh=False, stream=None):
+        """First-hit AOVs of the frame render() would draw with the same width, height, seed, band and chunks, over its first
+        `spp` samples (pt_ctx_render_aov): device pointers, each optional - albedo / normal: pixels * 3 float32 (the means
+        over the samples), depth: pixels float32 (sample 0's hit distance, +inf on a miss), object_id: pixels int32 (sample
+        0's object, -1 on a miss)."""
+        cfg = self._config(width, height, spp, seed, band=band, chunks=chunks)
+        if no_bvh:
+            cfg.flags |= PT_FLAG_NO_BVH
+        ptr = lambda p: C.c_void_p(p) if p else None  # noqa: E731
+        _check(lib().pt_ctx_render_aov(self._h, C.byref(cfg), ptr(albedo), ptr(normal), ptr(depth), ptr(object_id),
+                                       C.c_void_p(stream or 0)))
+
     def accum_reset(self):
         _check(lib().pt_ctx_accum_reset(self._h))
 
@@ -258,6 +274,21 @@ class Comm:
             self.close()
         except Exception:
             pass
+
+
+def write_pfm(path, array):
+    """A frame as a PFM file (pt_write_pfm): `array` is (height, width, 3) or (height, width) in framebuffer order (row
+    i // width of index i); a 3-channel array gives "PF", a 1-channel one "Pf".  Placed over write_ppm's image pixel for
+    pixel."""
+    import numpy as np
+
+    a = np.ascontiguousarray(array, dtype=np.float32)
+    if a.ndim == 3 and a.shape[2] == 1:
+        a = a[:, :, 0].copy()
+    if a.ndim not in (2, 3):
+        raise ValueError("write_pfm wants a (height, width[, channels]) array, not shape %r" % (a.shape,))
+    channels = a.shape[2] if a.ndim == 3 else 1
+    _check(lib().pt_write_pfm(os.fsencode(path), a.ctypes.data_as(C.POINTER(C.c_float)), a.shape[1], a.shape[0], channels))
 
 
 def build_flags():

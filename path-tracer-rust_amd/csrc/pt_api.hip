@@ -12,6 +12,7 @@
 
 #include "../../include/ptrace.h"
 #include "pt_accum.h"
+#include "pt_aov.h"
 #include "pt_host.h"
 #include "pt_kernels.h"
 
@@ -2172,6 +2173,40 @@ int pt_ctx_primary_rays(pt_ctx *c, uint32_t width, uint32_t height, uint64_t see
         set_error(std::string("primary rays: ") + hipGetErrorString(e));
         return PT_ERR_HIP;
     }
+    return PT_OK;
+}
+
+int pt_ctx_render_aov(pt_ctx *c, const pt_config *cfg, float *d_albedo, float *d_normal, float *d_depth, int32_t *d_object_id,
+                      void *hip_stream) {
+    if (!c || !cfg) {
+        set_error("NULL argument");
+        return PT_ERR_INVALID;
+    }
+    if (!d_albedo && !d_normal && !d_depth && !d_object_id) {
+        set_error("every output is NULL");
+        return PT_ERR_INVALID;
+    }
+    if (!c->has_scene) {
+        set_error("no scene set");
+        return PT_ERR_INVALID;
+    }
+    // the frame's pixels and samples as pt_ctx_render reads them; backend, pass sizes and pipelines do not apply
+    pt_config fc = *cfg;
+    fc.backend = PT_BACKEND_WAVEFRONT;
+    uint32_t ib = 0, ie = 0;
+    int rc = check_cfg(&fc, &ib, &ie);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const FrameParams F = make_frame(c, &fc, ib, ie);
+    if (F.npix == 0u) return PT_OK;  // this rank owns no chunk of the band
+    // a copy of the scene record: the context's own is left as it is (no call in flight sees a change)
+    DevScene S = c->scene;
+    S.n_bvh_nodes = (cfg->flags & PT_FLAG_NO_BVH) ? 0u : c->n_bvh_nodes;
+    S.planar = (cfg->flags & PT_FLAG_NO_BVH) ? 0u : 1u;
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    launch_aov(st, S, F, d_albedo, d_normal, d_depth, d_object_id);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
     return PT_OK;
 }
 

@@ -20,10 +20,13 @@
 static void usage() {
     fprintf(stderr,
             "usage: ptrace <samplesPerPixel> <y-resolution> <scene id|index> [--width W] [--backend wavefront|megakernel]\n"
-            "              [--seed S] [--gpus N] [--root DIR] [--out DIR] [--no-ppm] [--checkpoint FILE]\n"
+            "              [--seed S] [--gpus N] [--root DIR] [--out DIR] [--no-ppm] [--checkpoint FILE] [--aov N]\n"
             "  --checkpoint FILE: continue from the samples FILE holds (if it exists), render up to <samplesPerPixel> in all and\n"
             "                     save them to FILE; one GPU only; the seed defaults to 0 instead of the clock, so that the same\n"
-            "                     command continues the same frame\n");
+            "                     command continues the same frame\n"
+            "  --aov N: after the frame, first-hit AOVs over its first N samples on one GPU, written next to the image as\n"
+            "           PFM files: ...-beauty.pfm (the linear frame), -albedo, -normal, -depth (+inf on a miss) and -id (the\n"
+            "           object index as a float, -1 on a miss)\n");
 }
 
 static std::vector<std::string> scene_ids(const std::string &root) {
@@ -97,6 +100,57 @@ static int render_checkpointed(const pt_config *cfg, pt_scene *sc, const std::st
     return rc;
 }
 
+// --aov: the frame's first-hit AOVs at `spp` samples (pt_ctx_render_aov) on one GPU, and the five PFM files at `stem`
+static int write_aovs(const pt_config *frame, uint32_t spp, pt_scene *sc, const std::vector<float> &img, const std::string &stem) {
+    int dev = 0;
+    if (const char *e = getenv("PT_DEVICE")) dev = atoi(e);
+    uint32_t n_objs = 0, n_tris = 0;
+    const pt_object *objs = pt_scene_objects(sc, &n_objs);
+    const pt_triangle *tris = pt_scene_triangles(sc, &n_tris);
+    pt_config cfg = *frame;
+    cfg.spp = spp;
+    const size_t npix = (size_t)cfg.width * cfg.height;
+    std::vector<float> albedo(npix * 3), normal(npix * 3), depth(npix), id_f(npix);
+    std::vector<int32_t> id(npix);
+    pt_ctx *ctx = nullptr;
+    void *d_buf = nullptr;
+    int rc = pt_ctx_create(dev, &ctx);
+    if (!rc) rc = pt_ctx_set_scene(ctx, pt_scene_camera(sc), objs, n_objs, tris, n_tris);
+    if (!rc) rc = pt_device_malloc(dev, npix * 9 * sizeof(float), &d_buf);
+    if (!rc) {
+        float *d_albedo = (float *)d_buf, *d_normal = d_albedo + npix * 3, *d_depth = d_normal + npix * 3;
+        int32_t *d_id = (int32_t *)(d_depth + npix);
+        rc = pt_ctx_render_aov(ctx, &cfg, d_albedo, d_normal, d_depth, d_id, nullptr);
+        if (!rc) rc = pt_device_download(dev, albedo.data(), d_albedo, npix * 3 * sizeof(float));
+        if (!rc) rc = pt_device_download(dev, normal.data(), d_normal, npix * 3 * sizeof(float));
+        if (!rc) rc = pt_device_download(dev, depth.data(), d_depth, npix * sizeof(float));
+        if (!rc) rc = pt_device_download(dev, id.data(), d_id, npix * sizeof(int32_t));
+    }
+    if (d_buf) pt_device_free(dev, d_buf);
+    if (ctx) pt_ctx_destroy(ctx);
+    if (rc) {
+        fprintf(stderr, "AOVs failed (%d): %s\n", rc, pt_last_error());
+        return rc;
+    }
+    for (size_t i = 0; i < npix; ++i) id_f[i] = (float)id[i];
+    const struct {
+        const char *name;
+        const float *data;
+        uint32_t channels;
+    } files[] = {{"beauty", img.data(), 3}, {"albedo", albedo.data(), 3}, {"normal", normal.data(), 3}, {"depth", depth.data(), 1},
+                 {"id", id_f.data(), 1}};
+    for (const auto &f : files) {
+        const std::string path = stem + f.name + ".pfm";
+        rc = pt_write_pfm(path.c_str(), f.data, cfg.width, cfg.height, f.channels);
+        if (rc) {
+            fprintf(stderr, "cannot write %s: %s\n", path.c_str(), pt_last_error());
+            return rc;
+        }
+        printf("wrote %s\n", path.c_str());
+    }
+    return 0;
+}
+
 int main(int argc, char **argv) {
     if (argc < 4) {
         usage();
@@ -110,7 +164,7 @@ int main(int argc, char **argv) {
     bool seed_given = false;
     std::string checkpoint;
     bool write_ppm = true;
-    uint32_t gpus = 1;
+    uint32_t gpus = 1, aov_spp = 0;
     for (int i = 4; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&]() -> const char * { return i + 1 < argc ? argv[++i] : ""; };
@@ -131,6 +185,13 @@ int main(int argc, char **argv) {
         else if (a == "--root") root = next();
         else if (a == "--out") out_dir = next();
         else if (a == "--no-ppm") write_ppm = false;
+        else if (a == "--aov") {
+            aov_spp = (uint32_t)strtoul(next(), nullptr, 10);
+            if (!aov_spp) {
+                usage();
+                return 1;
+            }
+        }
         else {
             usage();
             return 1;
@@ -208,13 +269,15 @@ int main(int argc, char **argv) {
     printf("{\"ray_bounces\": %llu, \"samples\": %llu, \"ms_total\": %.3f, \"ms_device\": %.3f, \"ray_bounces_per_sec\": %.4g}\n",
            (unsigned long long)st.ray_bounces, (unsigned long long)st.samples, st.ms_total, st.ms_device,
            st.ray_bounces / (st.ms_total * 1e-3));
+    // out/<stamp>-scene-<id>-spp<N>-res<H>- : the image's name without ".ppm" (mod.rs:1035-1041); the AOV files share it
+    char stamp[64];
+    time_t now = time(nullptr);
+    strftime(stamp, sizeof stamp, "%Y-%m-%d_%H:%M:%S", localtime(&now));
+    const std::string stem = out_dir + "/" + stamp + "-scene-" + pt_scene_id(sc) + "-spp" + std::to_string(spp) + "-res" +
+                             std::to_string(res_y) + "-";
+    if (write_ppm || aov_spp) mkdir(out_dir.c_str(), 0755);  // create_dir_all("out"), mod.rs:1032
     if (write_ppm) {
-        mkdir(out_dir.c_str(), 0755);  // create_dir_all("out"), mod.rs:1032
-        char stamp[64];
-        time_t now = time(nullptr);
-        strftime(stamp, sizeof stamp, "%Y-%m-%d_%H:%M:%S", localtime(&now));
-        const std::string path = out_dir + "/" + stamp + "-scene-" + pt_scene_id(sc) + "-spp" + std::to_string(spp) +
-                                 "-res" + std::to_string(res_y) + "-.ppm";  // mod.rs:1035-1041
+        const std::string path = stem + ".ppm";
         rc = pt_write_ppm(path.c_str(), img.data(), width, res_y, spp, pt_scene_id(sc), (uint64_t)(st.ms_total / 1000.0));
         if (rc) {
             fprintf(stderr, "cannot write %s: %s\n", path.c_str(), pt_last_error());
@@ -225,6 +288,10 @@ int main(int argc, char **argv) {
         if (symlink(path.c_str(), "latest.ppm") != 0)
             printf("Could not create symlink to latest image. You can find it at %s\n", path.c_str());
         printf("wrote %s\n", path.c_str());
+    }
+    if (aov_spp && write_aovs(&cfg, aov_spp, sc, img, stem)) {
+        pt_scene_free(sc);
+        return 3;
     }
     pt_scene_free(sc);
     return 0;

@@ -1171,3 +1171,42 @@ int pt_write_ppm(const char *path, const float *rgb, uint32_t width, uint32_t he
 }
 
 }  // extern "C"
+
+// PFM (little-endian, scale -1.0), rows bottom-up.  pt_write_ppm lists framebuffer index i as the (W*H-1-i)-th pixel from the
+// top left, so image row r (from the top) column c is index (H-1-r)*W + (W-1-c); PFM's row q from the bottom is r = H-1-q,
+// i.e. its pixel (q, c) is framebuffer index q*W + (W-1-c): each framebuffer row, columns reversed.
+int pt_write_pfm(const char *path, const float *data, uint32_t width, uint32_t height, uint32_t channels) {
+    if (!path || !data || width == 0 || height == 0) {
+        pt::set_error("NULL argument or an empty image");
+        return PT_ERR_INVALID;
+    }
+    if (channels != 1u && channels != 3u) {
+        pt::set_error("PFM holds 1 or 3 channels");
+        return PT_ERR_INVALID;
+    }
+    FILE *f = fopen(path, "wb");
+    if (!f) {
+        pt::set_error(std::string("cannot create ") + path);
+        return PT_ERR_IO;
+    }
+    std::string buf = std::string(channels == 3u ? "PF" : "Pf") + "\n" + std::to_string(width) + " " + std::to_string(height) + "\n-1.0\n";
+    const size_t head = buf.size();
+    buf.resize(head + (size_t)width * height * channels * 4u);
+    char *w = &buf[head];
+    for (uint32_t q = 0; q < height; ++q)
+        for (uint32_t c = 0; c < width; ++c) {
+            const float *px = data + ((size_t)q * width + (width - 1u - c)) * channels;
+            for (uint32_t ch = 0; ch < channels; ++ch) {
+                uint32_t u;
+                memcpy(&u, px + ch, 4);
+                for (int b = 0; b < 4; ++b) *w++ = (char)((u >> (8 * b)) & 0xffu);
+            }
+        }
+    const size_t wr = fwrite(buf.data(), 1, buf.size(), f);
+    const int cl = fclose(f);
+    if (wr != buf.size() || cl != 0) {
+        pt::set_error(std::string("short write to ") + path);
+        return PT_ERR_IO;
+    }
+    return PT_OK;
+}
