@@ -143,6 +143,19 @@ static Tuning read_tuning() {
     return t;
 }
 
+// The frame call in progress (pt_ctx_render / pt_ctx_accumulate), for pt_ctx_snapshot from the progress callback; the call
+// clears it whenever it returns.  A large call is rendered in parts: pixels [0, k0) of it are final in `out`, [k0, k0 + npix)
+// are the part in progress (spp_issued samples per pixel issued, accumulators of `streams` x `m` slots), the rest has not
+// been started (`total` pixels in all).
+struct LiveFrame {
+    uint32_t npix = 0, spp_issued = 0, streams = 1, m = 0;
+    uint32_t k0 = 0, total = 0;
+    float *out = nullptr;
+    hipStream_t stream = nullptr;
+    bool accum = false;        // a pt_ctx_accumulate: pt_ctx_snapshot shows the other parts at their counts
+    double cb_last_ms = 0.0;   // time of the last progress callback (throttle: pt_config.progress_ms; one clock per call)
+};
+
 struct pt_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -179,19 +192,12 @@ struct pt_ctx {
     DevBuf<float> q_o, q_d, q_t, q_x, q_n;
     DevBuf<int32_t> q_oid, q_tid;
     // wavefront queues
-    uint32_t K = 0, cap = 0;
     DevBuf<char> q_buf[2];  // the two ray-queue containers: K slices of cap * 40 bytes each (RayQueue, pt_kernels.h)
     DevBuf<float2> hit;
     DevBuf<uint32_t> cnt, flags;
     DevBuf<unsigned long long> blk_rays, acc, total_rays;
     std::vector<hipEvent_t> ev_pool;
-    // state of the frame being rendered (for pt_ctx_snapshot from the progress callback)
-    uint32_t live_npix = 0, live_spp_issued = 0, live_streams = 1, live_m = 0;
-    hipStream_t live_stream = nullptr;
-    // a large call is rendered in parts: pixels [0, live_k0) of it are final in live_out, [live_k0, live_k0 + live_npix) are
-    // the part in progress, the rest has not been started (live_total pixels in all)
-    float *live_out = nullptr;
-    uint32_t live_k0 = 0, live_total = 0;
+    LiveFrame live;
     // concurrent pipelines (PT_FLAG_PIPELINES): child contexts that borrow this context's scene tables
     std::vector<pt_ctx *> pipes;
     std::vector<DevBuf<float>> pipe_out;
@@ -201,7 +207,6 @@ struct pt_ctx {
     // what hipMemGetInfo reports free, divided by `mem_share`)
     uint32_t mem_share = 1;
     size_t mem_budget = 0;
-    double cb_last_ms = 0.0;  // time of the last progress callback of the call in progress (throttle: pt_config.progress_ms)
     // Passes sized by TIME (k_pass_cand, megakernel rounds): primary samples per millisecond the last timed pass / round of this
     // scene went through, per backend (0: not measured yet - the next frame starts with a short timed pass).  pt_ctx_set_scene
     // forgets them.
@@ -216,7 +221,6 @@ struct pt_ctx {
     std::vector<uint32_t> acc_cnt;
     DevBuf<unsigned long long> acc_held;
     uint64_t scene_fp = 0;
-    bool live_accum = false;  // the call in progress is a pt_ctx_accumulate: pt_ctx_snapshot shows the other parts at their counts
 };
 
 namespace {
@@ -332,6 +336,46 @@ static uint32_t cand_scan_for(const pt_ctx *c, uint32_t flags) {
     return 1u;
 }
 
+// How a call with these flags runs, decided once per call.  The context's scene record is never changed for a call: the
+// call works on `scene`, a copy with the flags' BVH mode and candidate scan.
+struct FrameForm {
+    DevScene scene;
+    bool one_kernel;     // a wavefront pass is one launch (k_pass*), not generate / intersect / shade
+    bool stack_form;     // ... and that launch is k_pass_cand, whose waves keep their rays on stacks (passes sized by time)
+    bool stack_park;     // ... with container 1 for the waves' parked rays (scenes with walks) or deferred glass hits
+    const char *kernel;  // what pt_ctx_pass_kernel reports (and what pass_rate is keyed on)
+};
+
+FrameForm form_for(const pt_ctx *c, uint32_t flags) {
+    FrameForm f;
+    DevScene &S = f.scene;
+    S = c->scene;
+    // PT_FLAG_NO_BVH: scan meshes triangle by triangle as the reference does (same result, for A/B checks)
+    S.n_bvh_nodes = (flags & PT_FLAG_NO_BVH) ? 0u : c->n_bvh_nodes;
+    S.planar = (flags & PT_FLAG_NO_BVH) ? 0u : 1u;
+    S.cand_scan = cand_scan_for(c, flags);
+    // scenes without BVH meshes run a pass as one launch (k_pass), BVH scenes as k_pass_bvh unless their nodes are staged
+    // in LDS; PT_FLAG_SEPARATE_KERNELS / PT_PASS_KERNEL=0 / PT_PASS_BVH=0 keep the three-kernel form (A/B, profiling)
+    const bool bvh = S.n_bvh_nodes != 0u;
+    const bool bvh_ok = !bvh || (!(S.bvh_in_lds & 1u) && c->tune.pass_bvh);
+    f.one_kernel = bvh_ok && c->tune.pass_kernel && !(flags & PT_FLAG_SEPARATE_KERNELS);
+    f.stack_form = f.one_kernel && S.cand_scan != 0u;
+    f.stack_park = f.stack_form && (bvh || S.glass_defer_ok != 0u);
+    if (!f.one_kernel)
+        f.kernel = (!bvh && S.cand_scan) ? "k_intersect_cand" : "k_intersect";
+    else if (S.cand_scan)
+        f.kernel = bvh ? "k_pass_cand_bvh" : "k_pass_cand";  // (k_pass_cand<.., BVH = true>)
+    else
+        f.kernel = bvh ? "k_pass_bvh" : "k_pass";
+    return f;
+}
+
+// pt_config.progress_ms as milliseconds between two progress callbacks (0 = 500 ms, PT_PROGRESS_EVERY_PASS = every pass
+// boundary)
+double progress_interval_ms(const pt_config *cfg) {
+    return cfg->progress_ms == PT_PROGRESS_EVERY_PASS ? 0.0 : (cfg->progress_ms ? (double)cfg->progress_ms : 500.0);
+}
+
 // PT_LDS_PAD set: the layout a kernel that stages records runs with (lds_layout_line, pt_layout.h), on stderr whenever it
 // differs from the last one this context said for that launcher (which: 0 launch_pass, 1 launch_intersect_cand, 2 launch_mega)
 static void say_layout(pt_ctx *c, const LdsLayout &L, int which) {
@@ -357,10 +401,139 @@ double now_ms() {
     return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
 }
 
+// The progress callback, throttled to pt_config.progress_ms on the call's clock (LiveFrame::cb_last_ms); true when it was made
+bool progress(pt_ctx *c, const pt_config *cfg, pt_progress_fn cb, void *user, float f) {
+    const double t_now = now_ms();
+    if (t_now - c->live.cb_last_ms < progress_interval_ms(cfg)) return false;
+    c->live.cb_last_ms = t_now;
+    cb(user, f);
+    return true;
+}
+
+// The cadence of a renderer's launches (the wavefront's passes, the megakernel's rounds) on events 0..5 of the context's pool.
+// The cancel byte is read at EVERY launch boundary (the reference polls it every 100 ms, mod.rs:947-958) and again after a
+// progress callback; the callback (RenderUpdate, mod.rs:965-982) is throttled to pt_config.progress_ms.  With ONE launch in
+// flight (`one`: asked for, or wherever launches are sized by time) the launch before is waited for before the next is
+// issued - a few microseconds against a launch of 0.1 s - and progress counts the samples issued; otherwise two launches are
+// in flight and progress counts the launches known done.
+//
+// LAUNCHES THAT FOLLOW THE SCENE (`adaptive`).  A launch must not take much longer than 0.1 s WHATEVER a ray of the scene
+// costs - 512 Mi primary rays are 0.1 s on cornell.json, 0.15 s on mesh.json, and a scene of 392 unfiltered candidate records
+// inside an emitting sphere (tests) is fifty times dearer per primary ray.  So the first launch of a scene is TINY (kProbeRays
+// primary rays) and every launch is timed: the next one gets as many samples as the measured rate fits into kTargetMs
+// (host::next_pass_samples: up to a fifth more where that saves a launch, at most sixteen times the launch before - a short
+// launch measures overheads too - never more than `max_spp`, the rest of the frame in equal launches).  The rate is kept with
+// the context (pt_ctx.pass_rate / round_rate), so the following frames of the scene start at full length: the bench frame is
+// six passes of 683 samples, and the first frame of a scene pays three short passes.  Frames of at most kAdaptiveMinRays
+// primary rays are one launch; an explicit rays_per_pass is taken as given.  Launches only batch the samples: the image does
+// not depend on them.
+struct PassPacer {
+    static constexpr uint64_t kProbeRays = 1ull << 20, kAdaptiveMinRays = 4ull << 20;
+    static constexpr double kTargetMs = 100.0;
+    static constexpr int kLaunch = 1;  // next(): issue the launch it sized
+    pt_ctx *c;
+    const pt_config *cfg;
+    hipStream_t st;
+    const volatile uint8_t *cancel;
+    pt_progress_fn cb;
+    void *user;
+    uint64_t npix;
+    uint32_t max_spp, n_pass;  // samples per pixel of a launch at most; launches of max_spp that the frame takes
+    bool adaptive, one;
+    double rate;               // primary samples per millisecond the last timed launch went through (0: not measured)
+    hipEvent_t ev[6] = {};     // frame begun, frame done, launch done [2], launch begun [2]
+    uint32_t p = 0;            // launches issued
+    uint32_t s0 = 0, s_here = 0, s_next, s_prev = 0;  // the launch next() sized: samples [s0, s0 + s_here); issued; in the last
+    bool cancelled = false;
+
+    // samples [s_first, cfg->spp) of npix pixels; `may_adapt`: this renderer's launches may be sized by time, starting
+    // from `known_rate` (0: with a probe)
+    PassPacer(pt_ctx *c_, const pt_config *cfg_, hipStream_t st_, const volatile uint8_t *cancel_, pt_progress_fn cb_, void *user_,
+              uint64_t npix_, uint32_t s_first, uint32_t max_spp_, bool one_in_flight, bool may_adapt, double known_rate)
+        : c(c_), cfg(cfg_), st(st_), cancel(cancel_), cb(cb_), user(user_), npix(npix_), max_spp(max_spp_),
+          n_pass((cfg_->spp - s_first + max_spp_ - 1) / max_spp_),
+          adaptive(may_adapt && !cfg_->rays_per_pass && npix_ * (cfg_->spp - s_first) > kAdaptiveMinRays),
+          one(one_in_flight || adaptive), rate(adaptive ? known_rate : 0.0), s_next(s_first) {}
+
+    hipEvent_t done(uint32_t i) const { return ev[2 + (i & 1u)]; }
+    hipEvent_t begun(uint32_t i) const { return ev[4 + (i & 1u)]; }
+
+    int start() {
+        for (size_t i = 0; i < 6; ++i) ev[i] = get_event(c, i);
+        for (hipEvent_t e : ev)
+            if (!e) {
+                set_error("hipEventCreate failed");
+                return PT_ERR_HIP;
+            }
+        HIP_TRY(hipEventRecord(ev[0], st));
+        return PT_OK;
+    }
+
+    // Before launch p: wait for what must have ended, look at the cancel byte, make the progress callback and size the launch
+    // (s0, s_here).  kLaunch: issue it, then launched(); PT_OK: the frame is complete, or cancelled (`cancelled`).
+    int next() {
+        if (s_next >= cfg->spp) return PT_OK;
+        if (one && p >= 1u) {
+            HIP_TRY(hipEventSynchronize(done(p - 1u)));
+            if (adaptive) {
+                float ms = 0.0f;
+                HIP_TRY(hipEventElapsedTime(&ms, begun(p - 1u), done(p - 1u)));
+                if (ms > 0.0f) rate = (double)npix * s_prev / ms;
+            }
+        }
+        if (p >= 2u) HIP_TRY(hipEventSynchronize(done(p)));
+        cancelled = cancel && *cancel;
+        // (the samples known to be done)
+        if (!cancelled && cb && p >= (one ? 1u : 2u) &&
+            progress(c, cfg, cb, user, one ? (float)s_next / (float)cfg->spp : (float)(p - 1u) / (float)n_pass))
+            cancelled = cancel && *cancel;  // raised from inside the callback
+        if (cancelled) return PT_OK;
+        s0 = s_next;
+        s_here = (cfg->spp - s0) < max_spp ? (cfg->spp - s0) : max_spp;
+        if (adaptive) s_here = host::next_pass_samples(rate, kTargetMs, npix, kProbeRays, s_prev, cfg->spp - s0, max_spp);
+        s_next = s0 + s_here;
+        s_prev = s_here;
+        c->live.spp_issued = s_next;
+        if (adaptive) HIP_TRY(hipEventRecord(begun(p), st));
+        return kLaunch;
+    }
+
+    int launched() {
+        HIP_TRY(hipEventRecord(done(p), st));
+        ++p;
+        return PT_OK;
+    }
+
+    // After the last launch: wait for the frame.  The last launch's rate counts too (a frame of one probe and one long launch
+    // would otherwise only know the probe) when it was long enough to measure.
+    int finish() {
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(ev[1], st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (measured()) {
+            float ms = 0.0f;
+            HIP_TRY(hipEventElapsedTime(&ms, begun(p - 1u), done(p - 1u)));
+            if (ms > 0.0f && (double)npix * s_prev >= 16.0 * (double)kProbeRays) rate = (double)npix * s_prev / ms;
+        }
+        return PT_OK;
+    }
+
+    // `rate` is one to keep with the context
+    bool measured() const { return adaptive && p != 0u; }
+
+    int frame_ms(double &out) const {
+        float ms = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
+        out = ms;
+        return PT_OK;
+    }
+};
+
 // Samples [s_first, cfg->spp) of every pixel of the part; the accumulators start from `held` (NULL: from zero).
-int render_wavefront(pt_ctx *c, const pt_config *cfg, const FrameParams &frame, hipStream_t st,
-                     const volatile uint8_t *cancel, pt_progress_fn cb, void *user, pt_stats *stats, uint32_t s_first,
+int render_wavefront(pt_ctx *c, const FrameForm &form, const pt_config *cfg, const FrameParams &frame, hipStream_t st,
+                     const volatile uint8_t *cancel, pt_progress_fn cb, void *user, pt_stats &stats, uint32_t s_first,
                      const HeldSums *held) {
+    const DevScene &S = form.scene;
     FrameParams F = frame;
     const uint64_t npix = F.npix;
     const uint32_t spp_left = cfg->spp - s_first;  // samples per pixel this call traces
@@ -368,20 +541,15 @@ int render_wavefront(pt_ctx *c, const pt_config *cfg, const FrameParams &frame, 
     // queues (two containers x 4 slots per primary ray x 40 B) of the 288 GB of HBM - fewer, longer launches: cornell 1024x768
     // @4096 spp 32 Mi 35.7, 48 Mi 35.7, 64 Mi 36.2, 96 Mi 36.4 G bounces/s (a launch ends with its slowest streams).
     // k_pass_cand (`stack_form`) keeps a wave's waiting rays on a stack of at most kWaveStackMax slots whatever the pass holds:
-    // its passes are sized by TIME - 512 Mi primary rays, about 0.1 s between two looks at the cancel flag (the reference
-    // polls it every 100 ms, mod.rs:947-958) - and its memory is the streams' (K x 4 waves x stack x 40 B: 4.0 GB for the 24 576
-    // streams of the bench frame's pass; small passes need less: 4 x pow2(primaries per wave) slots per stream).
+    // its passes are sized by TIME (PassPacer) - 512 Mi primary rays at most - and its memory is the streams' (K x 4 waves x
+    // stack x 40 B: 4.0 GB for the 24 576 streams of the bench frame's pass; small passes need less: 4 x pow2(primaries per
+    // wave) slots per stream).
     // The default is what the DEVICE can give: 85 % of the free memory (plus what this context's queues hold already),
     // divided by the contexts that share the device in this call (PT_FLAG_PIPELINES, ranks of pt_render_multi on one GPU),
     // or pt_ctx_set_memory_budget's figure - at 352 B per primary ray for the level-by-level forms (queues + hit records of
     // the three-kernel form), by the streams' stacks for k_pass_cand; and whatever was asked for, a failed allocation halves
     // the pass and tries again: passes only change how the samples are batched, never the image.
-    const bool bvh_ok = c->scene.n_bvh_nodes == 0u || (!(c->scene.bvh_in_lds & 1u) && c->tune.pass_bvh);
-    const bool one_kernel = bvh_ok && c->tune.pass_kernel && !(cfg->flags & PT_FLAG_SEPARATE_KERNELS);
-    const bool needs_hits = !one_kernel;
-    const bool stack_form = one_kernel && c->scene.cand_scan != 0u;
-    // container 1: the waves' parked rays (scenes with walks) or deferred glass hits
-    const bool stack_park = stack_form && (c->scene.n_bvh_nodes != 0u || c->scene.glass_defer_ok != 0u);
+    const bool stack_form = form.stack_form;
     uint64_t want = cfg->rays_per_pass ? cfg->rays_per_pass : c->tune.rays_per_pass;
     size_t stack_budget = 0;  // stack_form, default pass size: what the streams' stacks may take
     if (!want) {
@@ -421,14 +589,14 @@ int render_wavefront(pt_ctx *c, const pt_config *cfg, const FrameParams &frame, 
         pin.want = want;
         pin.want_is_default = !cfg->rays_per_pass;
         pin.stack_form = stack_form;
-        pin.stack_park = stack_park;
-        pin.cand_scan = c->scene.cand_scan != 0u;
-        pin.has_bvh = c->scene.n_bvh_nodes != 0u;
+        pin.stack_park = form.stack_park;
+        pin.cand_scan = S.cand_scan != 0u;
+        pin.has_bvh = S.n_bvh_nodes != 0u;
         pin.streams = c->tune.streams;
         pin.per_stream = c->tune.per_stream;
         pin.wave_stack = c->tune.wave_stack;
         pin.n_cus = c->n_cus;
-        pin.groups_per_cu = !stack_form ? 4u : (c->scene.n_bvh_nodes == 0u ? (uint32_t)PT_CAND_WAVES : (uint32_t)PT_CAND_BVH_WAVES);
+        pin.groups_per_cu = !stack_form ? 4u : (S.n_bvh_nodes == 0u ? (uint32_t)PT_CAND_WAVES : (uint32_t)PT_CAND_BVH_WAVES);
         pin.stack_budget = stack_budget;
         host::PassPlan plan;
         uint64_t want_next = want;
@@ -449,10 +617,8 @@ int render_wavefront(pt_ctx *c, const pt_config *cfg, const FrameParams &frame, 
         int rc = PT_OK;
         rc = c->q_buf[0].ensure(plan.bytes0, true);
         if (!rc && plan.bytes1) rc = c->q_buf[1].ensure(plan.bytes1, true);
-        // scenes without BVH meshes run a pass as one launch (k_pass), BVH scenes as k_pass_bvh unless their nodes are staged
-        // in LDS; PT_FLAG_SEPARATE_KERNELS / PT_PASS_KERNEL=0 / PT_PASS_BVH=0 keep the three-kernel form (A/B, profiling).
-        // Only that form needs the hit records: k_pass keeps hits in registers.
-        if (!rc && needs_hits) rc = c->hit.ensure(slots, true);
+        // only the three-kernel form needs the hit records: k_pass keeps hits in registers
+        if (!rc && !form.one_kernel) rc = c->hit.ensure(slots, true);
         if (!rc) rc = c->cnt.ensure((size_t)kLevels * K, true);
         if (!rc) rc = c->flags.ensure(1, true);
         if (!rc) rc = c->blk_rays.ensure(K, true);
@@ -465,14 +631,12 @@ int render_wavefront(pt_ctx *c, const pt_config *cfg, const FrameParams &frame, 
         if (spp_pass <= 1u) return PT_ERR_HIP;  // (the message names the allocation that failed)
         want = (uint64_t)npix * (spp_pass / 2u ? spp_pass / 2u : 1u);
     }
-    c->K = K;
-    c->cap = cap;
     F.n_streams = K;  // stream b owns pixels b, b+K, ...; accumulators are stream-major (K*m slots per channel)
-    c->live_streams = K;
-    c->live_m = m;
-    const LdsLayout lay = lds_layout(c->scene, m, c->tune.lds_pad);
-    if (one_kernel && (c->scene.n_bvh_nodes == 0u || c->scene.cand_scan)) say_layout(c, lay, 0);
-    if (!one_kernel && c->scene.n_bvh_nodes == 0u && c->scene.cand_scan) say_layout(c, lay, 1);
+    c->live.streams = K;
+    c->live.m = m;
+    const LdsLayout lay = lds_layout(S, m, c->tune.lds_pad);
+    if (form.one_kernel && (S.n_bvh_nodes == 0u || S.cand_scan)) say_layout(c, lay, 0);
+    if (!form.one_kernel && S.n_bvh_nodes == 0u && S.cand_scan) say_layout(c, lay, 1);
     if (held)
         launch_accum_gather(st, held->p, held->stride, (uint32_t)npix, K, m, c->acc.p);
     else
@@ -481,83 +645,17 @@ int render_wavefront(pt_ctx *c, const pt_config *cfg, const FrameParams &frame, 
     HIP_TRY(hipMemsetAsync(c->flags.p, 0, sizeof(uint32_t), st));
     HIP_TRY(hipMemsetAsync(c->cnt.p, 0, (size_t)kLevels * K * sizeof(uint32_t), st));
 
-    const uint32_t n_pass = (spp_left + spp_pass - 1) / spp_pass;
     const int n_depth = kMaxDepth;  // rays of depth 0..11 exist
-    // PASSES THAT FOLLOW THE SCENE (k_pass_cand at the library's own pass size).  The reference looks at its stop flag every
-    // 100 ms (mod.rs:947-958); here the flag is read between passes, so a pass must not take much longer than that WHATEVER a
-    // ray of the scene costs - 512 Mi primary rays are 0.1 s on cornell.json, 0.15 s on mesh.json, and a scene of 392
-    // unfiltered candidate records inside an emitting sphere (tests) is fifty times dearer per primary ray.  Nothing is known
-    // about a scene's cost before its first rays have been traced, so the first pass of a scene is TINY (kProbeRays primary
-    // rays: a fraction of a millisecond on the bench scene) and timed (HIP events around the launch); every pass is timed,
-    // and the next one gets as many samples as the measured rate fits into kPassTargetMs (stretched by up to a fifth where
-    // that saves a pass) - at most sixteen times the pass before (a short pass measures launch overheads too, and its
-    // streams are too short to be efficient: the estimate errs towards short passes), never more than the planned spp_pass
-    // (the stacks, the sample field of the bookkeeping word), the rest of the frame cut into equal passes.  The rate is kept
-    // with the context (pt_ctx.pass_rate), so the following frames of the same scene start at full length: the bench frame
-    // is six passes of 683 samples as before, and the first frame of a scene pays three short passes (a few milliseconds).
-    // Frames of at most kAdaptiveMinRays primary rays are one pass; an explicit rays_per_pass is taken as given.  Passes
-    // only batch the samples: the image does not depend on them.
-    constexpr uint64_t kProbeRays = 1ull << 20, kAdaptiveMinRays = 4ull << 20;
-    constexpr double kPassTargetMs = 100.0;
-    const bool adaptive = stack_form && !cfg->rays_per_pass && !c->tune.rays_per_pass && n_pass > 0u &&
-                          (uint64_t)npix * spp_left > kAdaptiveMinRays;
-    const char *const rate_key = pt_ctx_pass_kernel(c, cfg->flags);
-    double rate = (adaptive && c->pass_rate_kernel == rate_key) ? c->pass_rate : 0.0;
-    size_t ev_i = 0;
-    hipEvent_t ev_begin = get_event(c, ev_i++), ev_end = get_event(c, ev_i++);
-    hipEvent_t pass_done[2] = {get_event(c, ev_i++), get_event(c, ev_i++)};
-    hipEvent_t pass_begin[2] = {get_event(c, ev_i++), get_event(c, ev_i++)};
-    if (!ev_begin || !ev_end || !pass_done[0] || !pass_done[1] || !pass_begin[0] || !pass_begin[1]) {
-        set_error("hipEventCreate failed");
-        return PT_ERR_HIP;
-    }
-    const size_t ev_prof0 = ev_i;
+    // k_pass_cand's long passes: one in flight, and sized by time at the library's own pass size
+    PassPacer pace(c, cfg, st, cancel, cb, user, npix, s_first, spp_pass, stack_form, stack_form && !c->tune.rays_per_pass,
+                   c->pass_rate_kernel == form.kernel ? c->pass_rate : 0.0);
+    int rc = pace.start();
+    if (rc) return rc;
+    const size_t ev_prof0 = 6;  // profiling events follow the pacer's
     size_t n_prof = 0;
-    HIP_TRY(hipEventRecord(ev_begin, st));
-    bool cancelled = false;
-    uint32_t passes_done = 0;
-    // RenderUpdate cadence (mod.rs:965-982): the reference reports every 500 ms.  Passes are much shorter than that, so
-    // the callback is throttled to pt_config.progress_ms (0 = 500 ms, PT_PROGRESS_EVERY_PASS = every pass boundary);
-    // the cancel byte is read at EVERY pass boundary (the reference polls it every 100 ms, mod.rs:947-958).
-    const double cb_every_ms = cfg->progress_ms == PT_PROGRESS_EVERY_PASS ? 0.0 : (cfg->progress_ms ? (double)cfg->progress_ms : 500.0);
-    double &cb_last_ms = c->cb_last_ms;  // (set when the call began: pt_ctx_render; a call rendered in parts keeps one clock)
-    uint32_t s_next = s_first, s_prev = 0u;  // samples of a pixel issued so far / in the pass before
-    for (uint32_t p = 0; s_next < cfg->spp; ++p) {
-        // keep two passes in flight; k_pass_cand's long passes (0.1 s) one - the cancel flag is looked at when a pass ends, and
-        // the few microseconds between two launches are nothing against such a pass
-        if (stack_form && p >= 1) {
-            HIP_TRY(hipEventSynchronize(pass_done[(p - 1) & 1]));
-            if (adaptive) {
-                float ms = 0.0f;
-                HIP_TRY(hipEventElapsedTime(&ms, pass_begin[(p - 1) & 1], pass_done[(p - 1) & 1]));
-                if (ms > 0.0f) rate = (double)npix * s_prev / ms;
-            }
-        }
-        if (p >= 2) HIP_TRY(hipEventSynchronize(pass_done[p & 1]));
-        if (cancel && *cancel) {
-            cancelled = true;
-            break;
-        }
-        if (cb && p >= (stack_form ? 1u : 2u)) {
-            const double t_now = now_ms();
-            if (t_now - cb_last_ms >= cb_every_ms) {
-                cb_last_ms = t_now;
-                // (the samples known to be done)
-                cb(user, stack_form ? (float)s_next / (float)cfg->spp : (float)(p - 1u) / (float)n_pass);
-                if (cancel && *cancel) {  // raised from inside the callback
-                    cancelled = true;
-                    break;
-                }
-            }
-        }
-        const uint32_t s0 = s_next;
-        uint32_t s_here = (cfg->spp - s0) < spp_pass ? (cfg->spp - s0) : spp_pass;
-        if (adaptive) s_here = host::next_pass_samples(rate, kPassTargetMs, npix, kProbeRays, s_prev, cfg->spp - s0, spp_pass);
-        s_next = s0 + s_here;
-        s_prev = s_here;
-        c->live_spp_issued = s0 + s_here;
-        if (adaptive) HIP_TRY(hipEventRecord(pass_begin[p & 1], st));
-        if (one_kernel) {  // the whole pass in one launch (k_pass)
+    while ((rc = pace.next()) == PassPacer::kLaunch) {
+        const uint32_t s0 = pace.s0, s_here = pace.s_here;
+        if (form.one_kernel) {  // the whole pass in one launch (k_pass)
             hipEvent_t a = nullptr, b = nullptr;
             if (c->profiling) {
                 a = get_event(c, ev_prof0 + 2 * n_prof), b = get_event(c, ev_prof0 + 2 * n_prof + 1);
@@ -567,80 +665,67 @@ int render_wavefront(pt_ctx *c, const pt_config *cfg, const FrameParams &frame, 
                 }
                 HIP_TRY(hipEventRecord(a, st));
             }
-            if (c->scene.n_bvh_nodes != 0u && !c->scene.cand_scan)
-                launch_pass_bvh(st, K, c->scene, F, queue_of(c, 0), queue_of(c, 1), cap, s0, s_here, m, c->acc.p,
-                                c->blk_rays.p, c->flags.p);
-            else if (launch_pass(st, K, c->scene, lay, F, queue_of(c, 0), queue_of(c, 1), cap, s0, s_here, m, c->acc.p, c->blk_rays.p,
+            if (S.n_bvh_nodes != 0u && !S.cand_scan)
+                launch_pass_bvh(st, K, S, F, queue_of(c, 0), queue_of(c, 1), cap, s0, s_here, m, c->acc.p, c->blk_rays.p, c->flags.p);
+            else if (launch_pass(st, K, S, lay, F, queue_of(c, 0), queue_of(c, 1), cap, s0, s_here, m, c->acc.p, c->blk_rays.p,
                                  c->flags.p) != hipSuccess)
                 return PT_ERR_HIP;  // (the message says how much LDS the scene's kernel asked for)
             if (c->profiling) {
                 HIP_TRY(hipEventRecord(b, st));
                 ++n_prof;
             }
-            HIP_TRY(hipEventRecord(pass_done[p & 1], st));
-            ++passes_done;
-            continue;
-        }
-        launch_generate(st, K, F, queue_of(c, 0), c->cnt.p, cap, s0, s_here, m);
-        for (int d = 0; d < n_depth; ++d) {
-            const RayQueue qin = queue_of(c, d & 1), qout = queue_of(c, (d + 1) & 1);
-            if (c->profiling) {
-                hipEvent_t a = get_event(c, ev_prof0 + 2 * n_prof), b = get_event(c, ev_prof0 + 2 * n_prof + 1);
-                if (!a || !b) {
-                    set_error("hipEventCreate failed");
-                    return PT_ERR_HIP;
+        } else {
+            launch_generate(st, K, F, queue_of(c, 0), c->cnt.p, cap, s0, s_here, m);
+            for (int d = 0; d < n_depth; ++d) {
+                const RayQueue qin = queue_of(c, d & 1), qout = queue_of(c, (d + 1) & 1);
+                if (c->profiling) {
+                    hipEvent_t a = get_event(c, ev_prof0 + 2 * n_prof), b = get_event(c, ev_prof0 + 2 * n_prof + 1);
+                    if (!a || !b) {
+                        set_error("hipEventCreate failed");
+                        return PT_ERR_HIP;
+                    }
+                    HIP_TRY(hipEventRecord(a, st));
+                    launch_intersect(st, K, S, lay, qin, c->hit.p, c->cnt.p + (size_t)d * K, cap, c->blk_rays.p);
+                    HIP_TRY(hipEventRecord(b, st));
+                    ++n_prof;
+                } else {
+                    launch_intersect(st, K, S, lay, qin, c->hit.p, c->cnt.p + (size_t)d * K, cap, c->blk_rays.p);
                 }
-                HIP_TRY(hipEventRecord(a, st));
-                launch_intersect(st, K, c->scene, lay, qin, c->hit.p, c->cnt.p + (size_t)d * K, cap, c->blk_rays.p);
-                HIP_TRY(hipEventRecord(b, st));
-                ++n_prof;
-            } else {
-                launch_intersect(st, K, c->scene, lay, qin, c->hit.p, c->cnt.p + (size_t)d * K, cap, c->blk_rays.p);
+                launch_shade(st, K, S, F, qin, qout, c->hit.p, c->cnt.p + (size_t)d * K, c->cnt.p + (size_t)(d + 1) * K, cap,
+                             c->acc.p, c->flags.p, m, s0);
             }
-            launch_shade(st, K, c->scene, F, qin, qout, c->hit.p, c->cnt.p + (size_t)d * K,
-                         c->cnt.p + (size_t)(d + 1) * K, cap, c->acc.p, c->flags.p, m, s0);
         }
-        HIP_TRY(hipEventRecord(pass_done[p & 1], st));
-        ++passes_done;
+        if ((rc = pace.launched())) return rc;
     }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ev_end, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (adaptive && passes_done != 0u) {  // the last pass counts too (a frame of one probe and one long pass would otherwise only know the probe)
-        float ms = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&ms, pass_begin[(passes_done - 1u) & 1u], pass_done[(passes_done - 1u) & 1u]));
-        if (ms > 0.0f && (double)npix * s_prev >= 16.0 * (double)kProbeRays) rate = (double)npix * s_prev / ms;
-        c->pass_rate = rate;
-        c->pass_rate_kernel = rate_key;
+    if (rc || (rc = pace.finish())) return rc;
+    if (pace.measured()) {
+        c->pass_rate = pace.rate;
+        c->pass_rate_kernel = form.kernel;
     }
     std::vector<unsigned long long> rays(K);
     HIP_TRY(hipMemcpy(rays.data(), c->blk_rays.p, K * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     uint32_t flags = 0;
     HIP_TRY(hipMemcpy(&flags, c->flags.p, sizeof flags, hipMemcpyDeviceToHost));
-    if (stats) {
-        unsigned long long total = 0;
-        for (auto v : rays) total += v;
-        stats->ray_bounces = total;
-        stats->intersect_rays = total;
-        stats->intersect_launches = one_kernel ? passes_done : passes_done * (uint32_t)n_depth;
-        stats->passes = passes_done;
-        stats->samples = npix * (uint64_t)(s_next - s_first);  // (every pass that was issued has run: the stream is synchronised)
-        float ms = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&ms, ev_begin, ev_end));
-        stats->ms_device = ms;
-        double mi = 0.0;
-        for (size_t i = 0; i < n_prof; ++i) {
-            float e = 0.0f;
-            HIP_TRY(hipEventElapsedTime(&e, c->ev_pool[ev_prof0 + 2 * i], c->ev_pool[ev_prof0 + 2 * i + 1]));
-            mi += e;
-        }
-        stats->ms_intersect = mi;
+    unsigned long long total = 0;
+    for (auto v : rays) total += v;
+    stats.ray_bounces = total;
+    stats.intersect_rays = total;
+    stats.intersect_launches = form.one_kernel ? pace.p : pace.p * (uint32_t)n_depth;
+    stats.passes = pace.p;
+    stats.samples = npix * (uint64_t)(pace.s_next - s_first);  // (every pass that was issued has run: the stream is synchronised)
+    if ((rc = pace.frame_ms(stats.ms_device))) return rc;
+    double mi = 0.0;
+    for (size_t i = 0; i < n_prof; ++i) {
+        float e = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&e, c->ev_pool[ev_prof0 + 2 * i], c->ev_pool[ev_prof0 + 2 * i + 1]));
+        mi += e;
     }
+    stats.ms_intersect = mi;
     if (flags & 3u) {
         set_error((flags & 2u) ? "ray stream slices too small for k_pass_cand's wave stacks" : "ray stream overflow");
         return PT_ERR_OVERFLOW;
     }
-    if (cancelled) {
+    if (pace.cancelled) {
         set_error("cancelled");
         return PT_CANCELLED;
     }
@@ -648,14 +733,16 @@ int render_wavefront(pt_ctx *c, const pt_config *cfg, const FrameParams &frame, 
 }
 
 // Samples [s_first, cfg->spp) of every pixel of the part; the accumulators start from `held` (NULL: from zero).
-int render_mega(pt_ctx *c, const pt_config *cfg, const FrameParams &F, hipStream_t st, const volatile uint8_t *cancel,
-                pt_progress_fn cb, void *user, pt_stats *stats, uint32_t s_first, const HeldSums *held) {
+int render_mega(pt_ctx *c, const FrameForm &form, const pt_config *cfg, const FrameParams &F, hipStream_t st,
+                const volatile uint8_t *cancel, pt_progress_fn cb, void *user, pt_stats &stats, uint32_t s_first,
+                const HeldSums *held) {
+    const DevScene &S = form.scene;
     const uint64_t npix = F.npix;
     const uint32_t spp_left = cfg->spp - s_first;  // samples per pixel this call traces
     int rc;
     if ((rc = c->acc.ensure(3 * npix)) || (rc = c->total_rays.ensure(16))) return rc;
-    c->live_streams = 1;  // accumulators in pixel order
-    c->live_m = (uint32_t)npix;
+    c->live.streams = 1;  // accumulators in pixel order
+    c->live.m = (uint32_t)npix;
     if (held)
         launch_accum_gather(st, held->p, held->stride, (uint32_t)npix, 1u, (uint32_t)npix, c->acc.p);
     else
@@ -678,65 +765,17 @@ int render_mega(pt_ctx *c, const pt_config *cfg, const FrameParams &F, hipStream
     uint32_t n_split = 1;  // lanes per pixel within a round
     // (k_mega_cand hands its items out dynamically: finer ones - 8 per lane the chip holds, cornell 41.3 G bounces/s; 4: 39.1,
     // 16: 40.5, 32: 38.4 - so that a launch's last items are a small part of it; PT_MEGA_ITEMS for A/B runs and tests)
-    const LdsLayout lay = lds_layout(c->scene, 1u, c->tune.lds_pad);
+    const LdsLayout lay = lds_layout(S, 1u, c->tune.lds_pad);
     say_layout(c, lay, 2);
     const uint64_t item_mult = c->tune.mega_items ? c->tune.mega_items : (lay.mega_cand ? 8u : 4u);
     const uint64_t want_items = item_mult * lanes;
     while ((uint64_t)npix * n_split < want_items && n_split < round_spp) n_split *= 2;
     if (n_split > round_spp) n_split = round_spp;
-    const uint32_t n_rounds = (spp_left + round_spp - 1) / round_spp;
-    // rounds that follow the scene, as the wavefront's passes do (render_wavefront): a short timed first round, then as many
-    // samples per round as the measured rate fits into 100 ms (+ a fifth) (at most 16 x the round before, at most round_spp), the rest
-    // of the frame in equal rounds, one launch in flight; the rate stays with the context for the next frame
-    constexpr uint64_t kProbeSamples = 1ull << 20, kAdaptiveMinSamples = 4ull << 20;
-    constexpr double kRoundTargetMs = 100.0;
-    const bool adaptive = !cfg->rays_per_pass && (uint64_t)npix * spp_left > kAdaptiveMinSamples;
-    double rate = adaptive ? c->round_rate : 0.0;
-    hipEvent_t ev_begin = get_event(c, 0), ev_end = get_event(c, 1);
-    hipEvent_t round_done[2] = {get_event(c, 2), get_event(c, 3)};
-    hipEvent_t round_begin[2] = {get_event(c, 4), get_event(c, 5)};
-    if (!ev_begin || !ev_end || !round_done[0] || !round_done[1] || !round_begin[0] || !round_begin[1]) {
-        set_error("hipEventCreate failed");
-        return PT_ERR_HIP;
-    }
-    HIP_TRY(hipEventRecord(ev_begin, st));
-    const double cb_every_ms = cfg->progress_ms == PT_PROGRESS_EVERY_PASS ? 0.0 : (cfg->progress_ms ? (double)cfg->progress_ms : 500.0);
-    double &cb_last_ms = c->cb_last_ms;  // (set when the call began: pt_ctx_render; a call rendered in parts keeps one clock)
-    bool cancelled = false;
-    uint32_t rounds_done = 0;
-    uint64_t samples = 0;
-    uint32_t s_next = s_first, s_prev = 0u;
-    for (uint32_t r = 0; s_next < cfg->spp; ++r) {
-        if (adaptive && r >= 1) {  // one launch in flight: its time sizes the next
-            HIP_TRY(hipEventSynchronize(round_done[(r - 1) & 1]));
-            float ms = 0.0f;
-            HIP_TRY(hipEventElapsedTime(&ms, round_begin[(r - 1) & 1], round_done[(r - 1) & 1]));
-            if (ms > 0.0f) rate = (double)npix * s_prev / ms;
-        }
-        if (r >= 2) HIP_TRY(hipEventSynchronize(round_done[r & 1]));  // two launches in flight
-        if (cancel && *cancel) {
-            cancelled = true;
-            break;
-        }
-        if (cb && r >= (adaptive ? 1u : 2u)) {
-            const double t_now = now_ms();
-            if (t_now - cb_last_ms >= cb_every_ms) {
-                cb_last_ms = t_now;
-                cb(user, adaptive ? (float)s_next / (float)cfg->spp : (float)(r - 1) / (float)n_rounds);
-                if (cancel && *cancel) {
-                    cancelled = true;
-                    break;
-                }
-            }
-        }
-        const uint32_t s0 = s_next;
-        uint32_t s_here = (cfg->spp - s0) < round_spp ? (cfg->spp - s0) : round_spp;
-        if (adaptive) {
-            s_here = host::next_pass_samples(rate, kRoundTargetMs, npix, kProbeSamples, s_prev, cfg->spp - s0, round_spp);
-            HIP_TRY(hipEventRecord(round_begin[r & 1], st));
-        }
-        s_next = s0 + s_here;
-        s_prev = s_here;
+    // rounds that follow the scene, as k_pass_cand's passes do (PassPacer), unless rays_per_pass sizes them
+    PassPacer pace(c, cfg, st, cancel, cb, user, npix, s_first, round_spp, false, true, c->round_rate);
+    if ((rc = pace.start())) return rc;
+    while ((rc = pace.next()) == PassPacer::kLaunch) {
+        const uint32_t s0 = pace.s0, s_here = pace.s_here;
         const uint32_t split = n_split < s_here ? n_split : s_here;
         const uint32_t lane_spp = (s_here + split - 1) / split;
         const uint64_t items = npix * split;
@@ -745,48 +784,33 @@ int render_mega(pt_ctx *c, const pt_config *cfg, const FrameParams &F, hipStream
         const uint32_t grid = (uint32_t)(grid64 < max_grid ? grid64 : max_grid);
         if (lay.mega_cand && (rc = c->q_buf[0].ensure(mega_stack_mem_bytes(grid ? grid : 1u)))) return rc;  // split stacks
         HIP_TRY(hipMemsetAsync(c->total_rays.p + 7, 0, sizeof(unsigned long long), st));  // k_mega_cand's item counter
-        launch_mega(st, grid ? grid : 1u, c->scene, lay, F, c->acc.p, s0, s0 + s_here, lane_spp, split, c->total_rays.p, c->q_buf[0].p);
-        HIP_TRY(hipEventRecord(round_done[r & 1], st));
-        c->live_spp_issued = s0 + s_here;
-        samples += npix * s_here;
-        ++rounds_done;
+        launch_mega(st, grid ? grid : 1u, S, lay, F, c->acc.p, s0, s0 + s_here, lane_spp, split, c->total_rays.p, c->q_buf[0].p);
+        if ((rc = pace.launched())) return rc;
     }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ev_end, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (adaptive && rounds_done != 0u) {
-        float ms = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&ms, round_begin[(rounds_done - 1u) & 1u], round_done[(rounds_done - 1u) & 1u]));
-        if (ms > 0.0f && (double)npix * s_prev >= 16.0 * (double)kProbeSamples) rate = (double)npix * s_prev / ms;
-        c->round_rate = rate;
-    }
-    if (stats) {
-        unsigned long long total2[16] = {0};
-        HIP_TRY(hipMemcpy(total2, c->total_rays.p, sizeof total2, hipMemcpyDeviceToHost));
+    if (rc || (rc = pace.finish())) return rc;
+    if (pace.measured()) c->round_rate = pace.rate;
+    unsigned long long total2[16] = {0};
+    HIP_TRY(hipMemcpy(total2, c->total_rays.p, sizeof total2, hipMemcpyDeviceToHost));
 #ifdef PT_MEGA_STATS
-        fprintf(stderr, "mega stats: trips %llu, started per trip %.2f, finished per trip %.2f, maker iterations %llu (per trip %.3f) at %.1f lanes\n",
-                total2[2], (double)total2[3] / (double)(total2[2] ? total2[2] : 1), (double)total2[4] / (double)(total2[2] ? total2[2] : 1), total2[5],
-                (double)total2[5] / (double)(total2[2] ? total2[2] : 1), (double)total2[6] / (double)(total2[5] ? total2[5] : 1));
-        fprintf(stderr, "mega stats: lanes with an item %.2f, of them dry (no ray to start, samples used up) %.2f, lanes told no more %.2f per trip\n",
-                (double)total2[8] / (double)(total2[2] ? total2[2] : 1), (double)total2[9] / (double)(total2[2] ? total2[2] : 1),
-                (double)total2[10] / (double)(total2[2] ? total2[2] : 1));
+    fprintf(stderr, "mega stats: trips %llu, started per trip %.2f, finished per trip %.2f, maker iterations %llu (per trip %.3f) at %.1f lanes\n",
+            total2[2], (double)total2[3] / (double)(total2[2] ? total2[2] : 1), (double)total2[4] / (double)(total2[2] ? total2[2] : 1), total2[5],
+            (double)total2[5] / (double)(total2[2] ? total2[2] : 1), (double)total2[6] / (double)(total2[5] ? total2[5] : 1));
+    fprintf(stderr, "mega stats: lanes with an item %.2f, of them dry (no ray to start, samples used up) %.2f, lanes told no more %.2f per trip\n",
+            (double)total2[8] / (double)(total2[2] ? total2[2] : 1), (double)total2[9] / (double)(total2[2] ? total2[2] : 1),
+            (double)total2[10] / (double)(total2[2] ? total2[2] : 1));
 #endif
-        const unsigned long long total = total2[0];
-        if (total2[1]) {
-            set_error("megakernel: a lane's split stack overflowed");
-            return PT_ERR_OVERFLOW;
-        }
-        stats->ray_bounces = total;
-        stats->intersect_rays = 0;
-        stats->intersect_launches = 0;
-        stats->passes = rounds_done;
-        stats->samples = samples;
-        float ms = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&ms, ev_begin, ev_end));
-        stats->ms_device = ms;
-        stats->ms_intersect = 0.0;
+    if (total2[1]) {
+        set_error("megakernel: a lane's split stack overflowed");
+        return PT_ERR_OVERFLOW;
     }
-    if (cancelled) {
+    stats.ray_bounces = total2[0];
+    stats.intersect_rays = 0;
+    stats.intersect_launches = 0;
+    stats.passes = pace.p;
+    stats.samples = npix * (uint64_t)(pace.s_next - s_first);
+    if ((rc = pace.frame_ms(stats.ms_device))) return rc;
+    stats.ms_intersect = 0.0;
+    if (pace.cancelled) {
         set_error("cancelled");
         return PT_CANCELLED;
     }
@@ -839,6 +863,154 @@ int accum_resolve_part(pt_ctx *c, uint32_t i, float *out, hipStream_t st) {
         launch_resolve(st, c->acc_held.p + k0, out + (size_t)k0 * 3, n, c->acc_cnt[i], 1u, c->acc_total);
     else
         HIP_TRY(hipMemsetAsync(out + (size_t)k0 * 3, 0, (size_t)n * 3 * sizeof(float), st));
+    return PT_OK;
+}
+
+// One piece of a frame call: pixels [k0, k0 + n) of the call, samples [s_first, cfg->spp) of each, the accumulators starting
+// from `held` (held.p == nullptr: from zero).  Progress inside it is reported as base + scale * f of the call, and its start
+// is a progress point at `base`.  [part_lo, part_hi): the parts of pt_ctx_accumulate's counts it brings to cfg->spp.
+struct Job {
+    uint32_t k0, n, s_first;
+    HeldSums held;
+    float base, scale;
+    uint32_t part_lo, part_hi;
+};
+
+void add_stats(pt_stats *stats, const pt_stats &s) {
+    stats->ray_bounces += s.ray_bounces;
+    stats->samples += s.samples;
+    stats->intersect_rays += s.intersect_rays;
+    stats->intersect_launches += s.intersect_launches;
+    stats->passes += s.passes;
+    stats->ms_device += s.ms_device;
+    stats->ms_intersect += s.ms_intersect;
+}
+
+// pt_ctx_render after a job: its part resolved into the call's output over the samples per pixel it accumulated.  A
+// cancelled part is resolved over the samples that were issued (live.spp_issued, also reported through stats->samples):
+// every pixel at full brightness over fewer samples - the same picture pt_ctx_snapshot gives.  (The reference's partial
+// image has finished pixels at full spp and the rest black; a GPU pass covers every pixel, so "fewer samples everywhere" is
+// its counterpart.)  Nothing accumulated yet: all zero, as the reference's untouched `pixels` vector; so are the parts that
+// were never started.
+int resolve_job(pt_ctx *c, const pt_config *cfg, const Job &j, int rc, hipStream_t st) {
+    float *out_p = c->live.out + (size_t)j.k0 * 3;
+    const uint32_t spp_done = rc == PT_OK ? cfg->spp : c->live.spp_issued;
+    if (spp_done != 0u)
+        launch_resolve(st, c->acc.p, out_p, j.n, spp_done, c->live.streams, c->live.m);
+    else
+        HIP_TRY(hipMemsetAsync(out_p, 0, (size_t)j.n * 3 * sizeof(float), st));
+    if (rc == PT_CANCELLED && j.k0 + j.n < c->live.total)  // the parts that were never started
+        HIP_TRY(hipMemsetAsync(out_p + (size_t)j.n * 3, 0, (size_t)(c->live.total - j.k0 - j.n) * 3 * sizeof(float), st));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    return rc;
+}
+
+// pt_ctx_accumulate after a job: what it traced joins the held sums (every pass that was issued has run: the renderers
+// synchronise the stream), and its parts' counts follow
+int keep_job(pt_ctx *c, const pt_config *cfg, const Job &j, int rc, hipStream_t st) {
+    const uint32_t done = rc == PT_OK ? cfg->spp : c->live.spp_issued;
+    if (done <= j.s_first) return rc;
+    const uint64_t slots = (uint64_t)c->live.streams * c->live.m;
+    if (slots < j.n || slots > 0xffffffffull) {
+        set_error("accumulator layout does not cover the part");
+        return PT_ERR_HIP;
+    }
+    launch_accum_scatter(st, c->acc.p, j.n, c->live.streams, c->live.m, c->acc_held.p + j.k0, j.held.stride);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) {
+        set_error(std::string("storing the held sums: ") + hipGetErrorString(e));
+        accum_drop(c);  // (their state is unknown)
+        return PT_ERR_HIP;
+    }
+    for (uint32_t i = j.part_lo; i < j.part_hi; ++i) c->acc_cnt[i] = done;
+    return rc;
+}
+
+// pt_ctx_accumulate's output at the end of the call: every part over its own count
+int resolve_held(pt_ctx *c, float *out, hipStream_t st, int rc) {
+    for (uint32_t i = 0; i < (uint32_t)c->acc_cnt.size(); ++i) {
+        const int r2 = accum_resolve_part(c, i, out, st);
+        if (r2) {
+            rc = r2;
+            break;
+        }
+    }
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess && (rc == PT_OK || rc == PT_CANCELLED)) {
+        set_error(std::string("resolving the held sums: ") + hipGetErrorString(e));
+        rc = PT_ERR_HIP;
+    }
+    if (rc == PT_CANCELLED) set_error("cancelled");
+    return rc;
+}
+
+// The driver of pt_ctx_render and pt_ctx_accumulate: the call's jobs in order on one form of cfg->flags, into `out` (`total`
+// pixels; F: the call's frame).  After each job its part is resolved into the output (pt_ctx_render) or its sums are kept
+// (pt_ctx_accumulate, which resolves every part at the end).
+int run_frame_call(pt_ctx *c, const pt_config *cfg, const FrameParams &F, const std::vector<Job> &jobs, bool accumulate,
+                   float *out, uint32_t total, hipStream_t st, const volatile uint8_t *cancel, pt_progress_fn cb, void *user,
+                   pt_stats *stats) {
+    const double t0 = now_ms();
+    const FrameForm form = form_for(c, cfg->flags);
+    struct Relay {  // a job's fractions as fractions of the call; its completion is reported by the next job / the end
+        pt_progress_fn cb;
+        void *user;
+        float base, scale;
+        static void fn(void *self, float f) {
+            Relay *r = (Relay *)self;
+            if (f < 1.0f) r->cb(r->user, r->base + r->scale * f);
+        }
+    } relay{cb, user, 0.0f, 1.0f};
+    struct Clear {  // however the call returns, pt_ctx_snapshot finds no frame in progress afterwards
+        pt_ctx *c;
+        ~Clear() { c->live = LiveFrame{}; }
+    } clear{c};
+    c->live.out = out;
+    c->live.total = total;
+    c->live.stream = st;
+    c->live.accum = accumulate;
+    c->live.cb_last_ms = now_ms();
+    int rc = PT_OK;
+    bool started = false;
+    for (const Job &j : jobs) {
+        if (j.s_first >= cfg->spp) continue;  // nothing left to trace here
+        // a job boundary is a progress point of its own (a part of one or two passes makes no callback from inside); a cancel
+        // raised there is seen by the job's first pass, which leaves it and the parts behind it black
+        if (cb && started) progress(c, cfg, cb, user, j.base);
+        started = true;
+        FrameParams Fj = F;
+        Fj.k_begin = j.k0;
+        Fj.npix = j.n;
+        c->live.k0 = j.k0;
+        c->live.npix = j.n;
+        c->live.spp_issued = j.s_first;
+        relay.base = j.base;
+        relay.scale = j.scale;
+        pt_stats js{};
+        rc = (cfg->backend == PT_BACKEND_WAVEFRONT ? render_wavefront : render_mega)(
+            c, form, cfg, Fj, st, cancel, cb ? &Relay::fn : nullptr, &relay, js, j.s_first, j.held.p ? &j.held : nullptr);
+        if (rc == PT_OK || rc == PT_CANCELLED) rc = accumulate ? keep_job(c, cfg, j, rc, st) : resolve_job(c, cfg, j, rc, st);
+        if (stats) add_stats(stats, js);
+        if (rc != PT_OK) break;
+    }
+    if (accumulate && (rc == PT_OK || rc == PT_CANCELLED)) rc = resolve_held(c, out, st, rc);
+    if (cb && rc == PT_OK) cb(user, 1.0f);
+    if (stats) stats->ms_total = now_ms() - t0;
+    return rc;
+}
+
+// The prologue of a frame call: a scene, a valid cfg (its band in *ib, *ie), the context's device current
+int frame_prologue(pt_ctx *c, const pt_config *cfg, uint32_t *ib, uint32_t *ie) {
+    if (!c->has_scene) {
+        set_error("no scene set");
+        return PT_ERR_INVALID;
+    }
+    const int rc = check_cfg(cfg, ib, ie);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
     return PT_OK;
 }
 
@@ -1142,13 +1314,7 @@ int pt_device_download(int device, void *dst_host, const void *src_device, size_
 
 const char *pt_ctx_pass_kernel(const pt_ctx *c, uint32_t flags) {
     if (!c || !c->has_scene) return nullptr;
-    const bool no_bvh = (flags & PT_FLAG_NO_BVH) != 0u;
-    const uint32_t n_nodes = no_bvh ? 0u : c->n_bvh_nodes;
-    const bool bvh_ok = n_nodes == 0u || (!(c->scene.bvh_in_lds & 1u) && c->tune.pass_bvh);
-    const bool one_kernel = bvh_ok && c->tune.pass_kernel && !(flags & PT_FLAG_SEPARATE_KERNELS);
-    if (!one_kernel) return (n_nodes == 0u && cand_scan_for(c, flags)) ? "k_intersect_cand" : "k_intersect";
-    if (cand_scan_for(c, flags)) return n_nodes != 0u ? "k_pass_cand_bvh" : "k_pass_cand";  // (k_pass_cand<.., BVH = true>)
-    return n_nodes != 0u ? "k_pass_bvh" : "k_pass";
+    return form_for(c, flags).kernel;
 }
 
 int pt_bvh_refs_fit(uint64_t n_bvh_nodes, uint64_t n_pair_records) { return host::bvh_refs_fit(n_bvh_nodes, n_pair_records) ? 1 : 0; }
@@ -1268,14 +1434,9 @@ int pt_ctx_render(pt_ctx *c, const pt_config *cfg, void *d_out_rgb, void *hip_st
         set_error("NULL argument");
         return PT_ERR_INVALID;
     }
-    if (!c->has_scene) {
-        set_error("no scene set");
-        return PT_ERR_INVALID;
-    }
     uint32_t ib = 0, ie = 0;
-    int rc = check_cfg(cfg, &ib, &ie);
+    int rc = frame_prologue(c, cfg, &ib, &ie);
     if (rc) return rc;
-    HIP_TRY(hipSetDevice(c->device));
     const uint32_t n_pipes = (cfg->flags >> 8) & 15u;
     if (n_pipes > 1u && cfg->backend == PT_BACKEND_WAVEFRONT) {
         if (n_pipes > 8u) {
@@ -1284,11 +1445,7 @@ int pt_ctx_render(pt_ctx *c, const pt_config *cfg, void *d_out_rgb, void *hip_st
         }
         if (stats) memset(stats, 0, sizeof *stats);
         const double t0p = now_ms();
-        c->scene.n_bvh_nodes = (cfg->flags & PT_FLAG_NO_BVH) ? 0u : c->n_bvh_nodes;
-        c->scene.planar = (cfg->flags & PT_FLAG_NO_BVH) ? 0u : 1u;
         rc = render_pipelined(c, cfg, n_pipes, ib, ie, (float *)d_out_rgb, cancel, cb, user, stats);
-        c->scene.n_bvh_nodes = c->n_bvh_nodes;
-        c->scene.planar = 1u;
         if (cb && rc == PT_OK) cb(user, 1.0f);  // every pipeline has finished and the chunks are in place
         if (stats) stats->ms_total = now_ms() - t0p;
         return rc;
@@ -1297,11 +1454,6 @@ int pt_ctx_render(pt_ctx *c, const pt_config *cfg, void *d_out_rgb, void *hip_st
     const FrameParams F = make_frame(c, cfg, ib, ie);
     if (stats) memset(stats, 0, sizeof *stats);
     if (F.npix == 0u) return PT_OK;  // this rank owns no chunk of the band
-    // PT_FLAG_NO_BVH: scan meshes triangle by triangle as the reference does (same result, for A/B checks)
-    c->scene.n_bvh_nodes = (cfg->flags & PT_FLAG_NO_BVH) ? 0u : c->n_bvh_nodes;
-    c->scene.planar = (cfg->flags & PT_FLAG_NO_BVH) ? 0u : 1u;
-    c->scene.cand_scan = cand_scan_for(c, cfg->flags);
-    const double t0 = now_ms();
     // Parts.  The wavefront kernels are tuned for streams of a few dozen pixels with a couple of thousand rays per pass
     // (accumulators, ray slots and deferral buffers share 40 KB of LDS per workgroup); a call of many millions of pixels
     // (4096^2: BASELINE config 5) would need streams of 1024 pixels or passes of hundreds of GB.  Such a call is
@@ -1312,81 +1464,12 @@ int pt_ctx_render(pt_ctx *c, const pt_config *cfg, void *d_out_rgb, void *hip_st
     const uint32_t total = F.npix;
     const uint32_t part_px = part_pixels(total, cfg->backend == PT_BACKEND_WAVEFRONT);
     const uint32_t n_parts = (total + part_px - 1u) / part_px;
-    struct Relay {
-        pt_progress_fn cb;
-        void *user;
-        float base, scale;
-        static void fn(void *self, float f) {
-            Relay *r = (Relay *)self;
-            if (f < 1.0f) r->cb(r->user, r->base + r->scale * f);  // a part's completion is reported by the next part / the end
-        }
-    } relay{cb, user, 0.0f, 1.0f / (float)n_parts};
-    c->live_out = (float *)d_out_rgb;
-    c->live_total = total;
-    c->live_stream = st;
-    c->cb_last_ms = now_ms();
-    const double cb_every_ms = cfg->progress_ms == PT_PROGRESS_EVERY_PASS ? 0.0 : (cfg->progress_ms ? (double)cfg->progress_ms : 500.0);
-    rc = PT_OK;
-    for (uint32_t part = 0; part < n_parts && rc == PT_OK; ++part) {
-        // a part boundary is a progress point of its own (a part of one or two passes makes no callback from inside); a cancel
-        // raised there is seen by the part's first pass, which leaves it and the parts behind it black
-        if (cb && part > 0u) {
-            const double t_now = now_ms();
-            if (t_now - c->cb_last_ms >= cb_every_ms) {
-                c->cb_last_ms = t_now;
-                cb(user, (float)part / (float)n_parts);
-            }
-        }
-        FrameParams Fp = F;
-        Fp.k_begin = part * part_px;
-        Fp.npix = (total - Fp.k_begin) < part_px ? (total - Fp.k_begin) : part_px;
-        float *out_p = (float *)d_out_rgb + (size_t)Fp.k_begin * 3;
-        c->live_k0 = Fp.k_begin;
-        c->live_npix = Fp.npix;
-        c->live_spp_issued = 0;
-        relay.base = (float)part / (float)n_parts;
-        pt_stats ps;
-        memset(&ps, 0, sizeof ps);
-        pt_progress_fn part_cb = cb ? (n_parts > 1u ? &Relay::fn : cb) : nullptr;
-        void *part_user = n_parts > 1u ? (void *)&relay : user;
-        if (cfg->backend == PT_BACKEND_WAVEFRONT)
-            rc = render_wavefront(c, cfg, Fp, st, cancel, part_cb, part_user, &ps, 0u, nullptr);
-        else
-            rc = render_mega(c, cfg, Fp, st, cancel, part_cb, part_user, &ps, 0u, nullptr);
-        if (rc == PT_OK || rc == PT_CANCELLED) {
-            // A cancelled part resolves what was accumulated by the samples per pixel that were accumulated
-            // (live_spp_issued, also reported through stats->samples): every pixel at full brightness over fewer
-            // samples - the same picture pt_ctx_snapshot gives.  (The reference's partial image has finished pixels at
-            // full spp and the rest black; a GPU pass covers every pixel, so "fewer samples everywhere" is its
-            // counterpart.)  Nothing accumulated yet: all zero, as the reference's untouched `pixels` vector.
-            const uint32_t spp_done = rc == PT_OK ? cfg->spp : c->live_spp_issued;
-            if (spp_done != 0u)
-                launch_resolve(st, c->acc.p, out_p, Fp.npix, spp_done, c->live_streams, c->live_m);
-            else
-                HIP_TRY(hipMemsetAsync(out_p, 0, (size_t)Fp.npix * 3 * sizeof(float), st));
-            if (rc == PT_CANCELLED && Fp.k_begin + Fp.npix < total)  // the parts that were never started
-                HIP_TRY(hipMemsetAsync(out_p + (size_t)Fp.npix * 3, 0, (size_t)(total - Fp.k_begin - Fp.npix) * 3 * sizeof(float), st));
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipStreamSynchronize(st));
-        }
-        if (stats) {
-            stats->ray_bounces += ps.ray_bounces;
-            stats->samples += ps.samples;
-            stats->intersect_rays += ps.intersect_rays;
-            stats->intersect_launches += ps.intersect_launches;
-            stats->passes += ps.passes;
-            stats->ms_device += ps.ms_device;
-            stats->ms_intersect += ps.ms_intersect;
-        }
+    std::vector<Job> jobs;
+    for (uint32_t part = 0; part < n_parts; ++part) {
+        const uint32_t k0 = part * part_px, n = (total - k0) < part_px ? (total - k0) : part_px;
+        jobs.push_back({k0, n, 0u, HeldSums{nullptr, 0u}, (float)part / (float)n_parts, 1.0f / (float)n_parts, 0u, 0u});
     }
-    if (cb && rc == PT_OK) cb(user, 1.0f);
-    if (stats) stats->ms_total = now_ms() - t0;
-    c->scene.n_bvh_nodes = c->n_bvh_nodes;
-    c->scene.planar = 1u;
-    c->scene.cand_scan = cand_scan_for(c, 0u);
-    c->live_npix = 0;
-    c->live_out = nullptr;
-    return rc;
+    return run_frame_call(c, cfg, F, jobs, false, (float *)d_out_rgb, total, st, cancel, cb, user, stats);
 }
 
 int pt_ctx_accumulate(pt_ctx *c, const pt_config *cfg, void *d_out_rgb, void *hip_stream, const volatile uint8_t *cancel,
@@ -1395,12 +1478,8 @@ int pt_ctx_accumulate(pt_ctx *c, const pt_config *cfg, void *d_out_rgb, void *hi
         set_error("NULL argument");
         return PT_ERR_INVALID;
     }
-    if (!c->has_scene) {
-        set_error("no scene set");
-        return PT_ERR_INVALID;
-    }
     uint32_t ib = 0, ie = 0;
-    int rc = check_cfg(cfg, &ib, &ie);
+    int rc = frame_prologue(c, cfg, &ib, &ie);
     if (rc) return rc;
     if (((cfg->flags >> 8) & 15u) > 1u) {
         set_error("pt_ctx_accumulate does not take PT_FLAG_PIPELINES: its accumulators live in child contexts");
@@ -1417,7 +1496,6 @@ int pt_ctx_accumulate(pt_ctx *c, const pt_config *cfg, void *d_out_rgb, void *hi
             return PT_ERR_INVALID;
         }
     }
-    HIP_TRY(hipSetDevice(c->device));
     if (stats) memset(stats, 0, sizeof *stats);
     if (total == 0u) return PT_OK;  // this rank owns no chunk of the band
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
@@ -1433,124 +1511,20 @@ int pt_ctx_accumulate(pt_ctx *c, const pt_config *cfg, void *d_out_rgb, void *hi
         c->acc_cnt.assign(n_parts, 0u);
         c->acc_on = true;
     }
-    const FrameParams F = make_frame(c, cfg, ib, ie);
-    c->scene.n_bvh_nodes = (cfg->flags & PT_FLAG_NO_BVH) ? 0u : c->n_bvh_nodes;
-    c->scene.planar = (cfg->flags & PT_FLAG_NO_BVH) ? 0u : 1u;
-    c->scene.cand_scan = cand_scan_for(c, cfg->flags);
-    const double t0 = now_ms();
     // What to render: each part from its own count; the megakernel, which renders a call at once, takes the whole call in one go
-    // when every part holds the same count
-    struct Job {
-        uint32_t k0, n, part_lo, part_hi;  // pixels [k0, k0 + n) = parts [part_lo, part_hi)
-    };
+    // when every part holds the same count.  Progress by pixels.
     std::vector<Job> jobs;
+    auto job = [&](uint32_t k0, uint32_t n, uint32_t part_lo, uint32_t part_hi) {
+        jobs.push_back({k0, n, c->acc_cnt[part_lo], HeldSums{c->acc_held.p + k0, total}, (float)k0 / (float)total,
+                        (float)n / (float)total, part_lo, part_hi});
+    };
     bool even = true;
     for (uint32_t v : c->acc_cnt) even = even && v == c->acc_cnt[0];
     if (cfg->backend == PT_BACKEND_MEGAKERNEL && even)
-        jobs.push_back({0u, total, 0u, n_parts});
+        job(0u, total, 0u, n_parts);
     else
-        for (uint32_t i = 0; i < n_parts; ++i) jobs.push_back({i * part_px, (total - i * part_px) < part_px ? (total - i * part_px) : part_px, i, i + 1u});
-    struct Relay {  // a job's fractions as fractions of the call (by pixels); its completion is reported by the next job / the end
-        pt_progress_fn cb;
-        void *user;
-        float base, scale;
-        static void fn(void *self, float f) {
-            Relay *r = (Relay *)self;
-            if (f < 1.0f) r->cb(r->user, r->base + r->scale * f);
-        }
-    } relay{cb, user, 0.0f, 1.0f};
-    c->live_out = (float *)d_out_rgb;
-    c->live_total = total;
-    c->live_stream = st;
-    c->live_accum = true;
-    c->cb_last_ms = now_ms();
-    const double cb_every_ms = cfg->progress_ms == PT_PROGRESS_EVERY_PASS ? 0.0 : (cfg->progress_ms ? (double)cfg->progress_ms : 500.0);
-    rc = PT_OK;
-    bool started = false;
-    for (const Job &j : jobs) {
-        const uint32_t s_first = c->acc_cnt[j.part_lo];  // (a job of several parts: all at this count)
-        if (s_first >= cfg->spp) continue;  // nothing left to trace here
-        if (cb && started) {  // a job boundary is a progress point of its own, as a part boundary of pt_ctx_render
-            const double t_now = now_ms();
-            if (t_now - c->cb_last_ms >= cb_every_ms) {
-                c->cb_last_ms = t_now;
-                cb(user, (float)j.k0 / (float)total);
-            }
-        }
-        started = true;
-        FrameParams Fp = F;
-        Fp.k_begin = j.k0;
-        Fp.npix = j.n;
-        c->live_k0 = j.k0;
-        c->live_npix = j.n;
-        c->live_spp_issued = s_first;
-        relay.base = (float)j.k0 / (float)total;
-        relay.scale = (float)j.n / (float)total;
-        const HeldSums held{c->acc_held.p + j.k0, total};
-        pt_stats ps;
-        memset(&ps, 0, sizeof ps);
-        pt_progress_fn job_cb = cb ? &Relay::fn : nullptr;
-        if (cfg->backend == PT_BACKEND_WAVEFRONT)
-            rc = render_wavefront(c, cfg, Fp, st, cancel, job_cb, &relay, &ps, s_first, &held);
-        else
-            rc = render_mega(c, cfg, Fp, st, cancel, job_cb, &relay, &ps, s_first, &held);
-        if (rc == PT_OK || rc == PT_CANCELLED) {
-            // every pass that was issued has run (the renderers synchronise the stream): keep them
-            const uint32_t done = rc == PT_OK ? cfg->spp : c->live_spp_issued;
-            if (done > s_first) {
-                if ((uint64_t)c->live_streams * c->live_m < j.n || (uint64_t)c->live_streams * c->live_m > 0xffffffffull) {
-                    set_error("accumulator layout does not cover the part");
-                    rc = PT_ERR_HIP;
-                } else {
-                    launch_accum_scatter(st, c->acc.p, j.n, c->live_streams, c->live_m, c->acc_held.p + j.k0, total);
-                    hipError_t e = hipGetLastError();
-                    if (e == hipSuccess) e = hipStreamSynchronize(st);
-                    if (e != hipSuccess) {
-                        set_error(std::string("storing the held sums: ") + hipGetErrorString(e));
-                        rc = PT_ERR_HIP;
-                        accum_drop(c);  // (their state is unknown)
-                    } else {
-                        for (uint32_t i = j.part_lo; i < j.part_hi; ++i) c->acc_cnt[i] = done;
-                    }
-                }
-            }
-        }
-        if (stats) {
-            stats->ray_bounces += ps.ray_bounces;
-            stats->samples += ps.samples;
-            stats->intersect_rays += ps.intersect_rays;
-            stats->intersect_launches += ps.intersect_launches;
-            stats->passes += ps.passes;
-            stats->ms_device += ps.ms_device;
-            stats->ms_intersect += ps.ms_intersect;
-        }
-        if (rc != PT_OK) break;
-    }
-    if (rc == PT_OK || rc == PT_CANCELLED) {  // the output: every part over its own count
-        for (uint32_t i = 0; i < n_parts; ++i) {
-            const int r2 = accum_resolve_part(c, i, (float *)d_out_rgb, st);
-            if (r2) {
-                rc = r2;
-                break;
-            }
-        }
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess && (rc == PT_OK || rc == PT_CANCELLED)) {
-            set_error(std::string("resolving the held sums: ") + hipGetErrorString(e));
-            rc = PT_ERR_HIP;
-        }
-    }
-    if (rc == PT_CANCELLED) set_error("cancelled");
-    if (cb && rc == PT_OK) cb(user, 1.0f);
-    if (stats) stats->ms_total = now_ms() - t0;
-    c->scene.n_bvh_nodes = c->n_bvh_nodes;
-    c->scene.planar = 1u;
-    c->scene.cand_scan = cand_scan_for(c, 0u);
-    c->live_npix = 0;
-    c->live_out = nullptr;
-    c->live_accum = false;
-    return rc;
+        for (uint32_t i = 0; i < n_parts; ++i) job(i * part_px, (total - i * part_px) < part_px ? (total - i * part_px) : part_px, i, i + 1u);
+    return run_frame_call(c, cfg, make_frame(c, cfg, ib, ie), jobs, true, (float *)d_out_rgb, total, st, cancel, cb, user, stats);
 }
 
 int pt_ctx_accum_info(const pt_ctx *c, const pt_config *cfg, uint32_t *spp_min, uint32_t *spp_max) {
@@ -1771,22 +1745,15 @@ int pt_ctx_radiance(pt_ctx *c, const float o[3], const float d[3], uint32_t dept
     F.probe_dy = d[1];
     F.probe_dz = d[2];
     if (stats) memset(stats, 0, sizeof *stats);
-    c->scene.n_bvh_nodes = (flags & PT_FLAG_NO_BVH) ? 0u : c->n_bvh_nodes;
-    c->scene.planar = (flags & PT_FLAG_NO_BVH) ? 0u : 1u;
-    c->scene.cand_scan = cand_scan_for(c, flags);
     const double t0 = now_ms();
-    pt_stats ps;
-    memset(&ps, 0, sizeof ps);
+    pt_stats ps{};
     hipStream_t st = c->stream;
-    int rc = backend == PT_BACKEND_WAVEFRONT ? render_wavefront(c, &cfg, F, st, nullptr, nullptr, nullptr, &ps, 0u, nullptr)
-                                             : render_mega(c, &cfg, F, st, nullptr, nullptr, nullptr, &ps, 0u, nullptr);
-    c->scene.n_bvh_nodes = c->n_bvh_nodes;
-    c->scene.planar = 1u;
-    c->scene.cand_scan = cand_scan_for(c, 0u);
+    int rc = (backend == PT_BACKEND_WAVEFRONT ? render_wavefront : render_mega)(c, form_for(c, flags), &cfg, F, st, nullptr, nullptr,
+                                                                              nullptr, ps, 0u, nullptr);
     if (rc != PT_OK) return rc;
     DevBuf<float> d_out;
     if ((rc = d_out.ensure(3))) return rc;
-    launch_resolve(st, c->acc.p, d_out.p, 1u, n_samples, c->live_streams, c->live_m, false);  // the mean, not clamped
+    launch_resolve(st, c->acc.p, d_out.p, 1u, n_samples, c->live.streams, c->live.m, false);  // the mean, not clamped
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e == hipSuccess) e = hipMemcpy(out_rgb, d_out.p, 3 * sizeof(float), hipMemcpyDeviceToHost);
@@ -1837,10 +1804,7 @@ int pt_ctx_intersect_streams(pt_ctx *c, const float *o, const float *d, uint32_t
     if (e == hipSuccess) e = hipMemcpyAsync(dc.p, hc.data(), K * sizeof(uint32_t), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemsetAsync(dr.p, 0, K * sizeof(unsigned long long), st);
     if (e == hipSuccess) {
-        DevScene S = c->scene;
-        S.n_bvh_nodes = (flags & PT_FLAG_NO_BVH) ? 0u : c->n_bvh_nodes;
-        S.planar = (flags & PT_FLAG_NO_BVH) ? 0u : 1u;
-        S.cand_scan = cand_scan_for(c, flags);
+        const DevScene S = form_for(c, flags).scene;
         RayQueue q;
         q.buf = d0.p;
         launch_intersect(st, K, S, lds_layout(S, 1u, c->tune.lds_pad), q, dh.p, dc.p, cap, dr.p);
@@ -1987,39 +1951,35 @@ int pt_ctx_snapshot(pt_ctx *c, void *d_out_rgb, uint32_t *spp_done) {
         set_error("NULL argument");
         return PT_ERR_INVALID;
     }
-    if (c->live_npix == 0 || c->live_spp_issued == 0) {
+    if (c->live.npix == 0 || c->live.spp_issued == 0) {
         set_error("no frame in progress on this context (call from the progress callback of pt_ctx_render; under "
                   "PT_FLAG_PIPELINES the accumulators live in child contexts and no snapshot is offered)");
         return PT_ERR_INVALID;
     }
     HIP_TRY(hipSetDevice(c->device));
-    // stream order: the resolve runs after every pass issued so far, i.e. over live_spp_issued samples per pixel.  A call
+    // stream order: the resolve runs after every pass issued so far, i.e. over live.spp_issued samples per pixel.  A call
     // rendered in parts: the finished parts are copied from the call's own output, the part in progress is resolved,
     // the parts not started are black.
     float *snap = (float *)d_out_rgb;
-    hipStream_t st = c->live_stream;
-    if (c->live_accum) {  // pt_ctx_accumulate: every part outside the one in progress at its own count, from the held sums
+    const LiveFrame &L = c->live;
+    hipStream_t st = L.stream;
+    if (L.accum) {  // pt_ctx_accumulate: every part outside the one in progress at its own count, from the held sums
         for (uint32_t i = 0; i < (uint32_t)c->acc_cnt.size(); ++i) {
             const uint32_t k0 = i * c->acc_part_px;
-            if (k0 >= c->live_k0 && k0 < c->live_k0 + c->live_npix) continue;
+            if (k0 >= L.k0 && k0 < L.k0 + L.npix) continue;
             int rc = accum_resolve_part(c, i, snap, st);
             if (rc) return rc;
         }
-        launch_resolve(st, c->acc.p, snap + (size_t)c->live_k0 * 3, c->live_npix, c->live_spp_issued, c->live_streams, c->live_m);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(st));
-        if (spp_done) *spp_done = c->live_spp_issued;
-        return PT_OK;
+    } else if (L.k0 != 0u && L.out && L.out != snap) {
+        HIP_TRY(hipMemcpyAsync(snap, L.out, (size_t)L.k0 * 3 * sizeof(float), hipMemcpyDeviceToDevice, st));
     }
-    if (c->live_k0 != 0u && c->live_out && c->live_out != snap)
-        HIP_TRY(hipMemcpyAsync(snap, c->live_out, (size_t)c->live_k0 * 3 * sizeof(float), hipMemcpyDeviceToDevice, st));
-    launch_resolve(st, c->acc.p, snap + (size_t)c->live_k0 * 3, c->live_npix, c->live_spp_issued, c->live_streams, c->live_m);
-    const uint32_t done = c->live_k0 + c->live_npix;
-    if (done < c->live_total)
-        HIP_TRY(hipMemsetAsync(snap + (size_t)done * 3, 0, (size_t)(c->live_total - done) * 3 * sizeof(float), st));
+    launch_resolve(st, c->acc.p, snap + (size_t)L.k0 * 3, L.npix, L.spp_issued, L.streams, L.m);
+    const uint32_t done = L.k0 + L.npix;
+    if (!L.accum && done < L.total)
+        HIP_TRY(hipMemsetAsync(snap + (size_t)done * 3, 0, (size_t)(L.total - done) * 3 * sizeof(float), st));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
-    if (spp_done) *spp_done = c->live_spp_issued;
+    if (spp_done) *spp_done = L.spp_issued;
     return PT_OK;
 }
 
@@ -2186,23 +2146,15 @@ int pt_ctx_render_aov(pt_ctx *c, const pt_config *cfg, float *d_albedo, float *d
         set_error("every output is NULL");
         return PT_ERR_INVALID;
     }
-    if (!c->has_scene) {
-        set_error("no scene set");
-        return PT_ERR_INVALID;
-    }
     // the frame's pixels and samples as pt_ctx_render reads them; backend, pass sizes and pipelines do not apply
     pt_config fc = *cfg;
     fc.backend = PT_BACKEND_WAVEFRONT;
     uint32_t ib = 0, ie = 0;
-    int rc = check_cfg(&fc, &ib, &ie);
+    const int rc = frame_prologue(c, &fc, &ib, &ie);
     if (rc) return rc;
-    HIP_TRY(hipSetDevice(c->device));
     const FrameParams F = make_frame(c, &fc, ib, ie);
     if (F.npix == 0u) return PT_OK;  // this rank owns no chunk of the band
-    // a copy of the scene record: the context's own is left as it is (no call in flight sees a change)
-    DevScene S = c->scene;
-    S.n_bvh_nodes = (cfg->flags & PT_FLAG_NO_BVH) ? 0u : c->n_bvh_nodes;
-    S.planar = (cfg->flags & PT_FLAG_NO_BVH) ? 0u : 1u;
+    const DevScene S = form_for(c, cfg->flags).scene;  // (k_aov reads neither the candidate scan nor an LDS layout)
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
     launch_aov(st, S, F, d_albedo, d_normal, d_depth, d_object_id);
     HIP_TRY(hipGetLastError());
