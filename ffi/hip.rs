@@ -77,6 +77,18 @@ pub struct PtStats {
     pub ms_intersect: f64,
 }
 
+// pt_ctx_denoise's parameters; a zero field = the library's default (pt_denoise_defaults)
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct PtDenoiseParams {
+    pub levels: u32,
+    pub sigma_color: f32,
+    pub sigma_normal_pow: f32,
+    pub sigma_depth: f32,
+    pub flags: u32,
+}
+pub const PT_DENOISE_NO_DEMODULATE: u32 = 1;
+
 pub const PT_OK: i32 = 0;
 pub const PT_CANCELLED: i32 = -4;
 
@@ -151,6 +163,21 @@ extern "C" {
         d_normal: *mut f32,
         d_depth: *mut f32,
         d_object_id: *mut i32,
+        hip_stream: *mut c_void,
+    ) -> i32;
+    // edge-avoiding a-trous filter over a whole frame in device memory, guided by pt_ctx_render_aov's buffers (each guide may
+    // be null; d_out may be d_color); params null = defaults
+    pub fn pt_denoise_defaults(out: *mut PtDenoiseParams) -> i32;
+    pub fn pt_ctx_denoise(
+        ctx: *mut PtCtx,
+        width: u32,
+        height: u32,
+        params: *const PtDenoiseParams,
+        d_color: *const f32,
+        d_albedo: *const f32,
+        d_normal: *const f32,
+        d_depth: *const f32,
+        d_out: *mut f32,
         hip_stream: *mut c_void,
     ) -> i32;
     pub fn pt_write_pfm(path: *const c_char, data: *const f32, width: u32, height: u32, channels: u32) -> i32;

@@ -394,6 +394,66 @@ int pt_ctx_accum_load(pt_ctx *ctx, const char *path);
 int pt_ctx_render_aov(pt_ctx *ctx, const pt_config *cfg, float *d_albedo, float *d_normal, float *d_depth,
                       int32_t *d_object_id, void *hip_stream);
 
+/* ---- denoising a frame on the device with the first-hit guides ------------------------------------------------
+ * pt_ctx_denoise runs an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) over a WHOLE frame in device memory,
+ * guided by albedo, normal and depth: the consumer of pt_ctx_render_aov's buffers, for previews at few samples.
+ * - Buffers: device pointers, width * height pixels in framebuffer order - d_color, d_albedo, d_normal, d_out 3 floats per
+ *   pixel, d_depth 1 - the layouts pt_ctx_render / pt_ctx_render_aov write for a cfg without a band and without chunks.  Pixel
+ *   idx has column x = idx % width and row y = idx / width (the filter is symmetric: the framebuffer's flip does not matter).
+ * - d_albedo, d_normal, d_depth may each be NULL (see the arithmetic).  d_out may be d_color (the last level is the only
+ *   writer of d_out, and d_color is read before the first); d_out may not alias a guide.
+ * - `hip_stream` as for pt_ctx_render (NULL = the context's own stream); blocking.  No scene is needed.
+ * - Scratch (48 B per pixel: two colour planes and the packed guides) lives in the context, grows when a frame needs more, is
+ *   reused between calls, and is freed by pt_ctx_destroy.  The call changes no other state of the context: not the frame
+ *   accumulators, not pt_ctx_accumulate's held sums or counts, not the measured pass rates.
+ * - PT_ERR_INVALID, all refused before any device is touched: params->levels > 8, a sigma that is negative or not finite,
+ *   sigma_normal_pow != 0, flag bits other than PT_DENOISE_NO_DEMODULATE, width or height 0, width * height > 2^28, NULL
+ *   d_color or d_out, NULL ctx (checked in this order).  PT_ERR_HIP: a HIP call failed.  (PT_ERR_NO_DEVICE comes from
+ *   pt_ctx_create: without a device there is no context.)
+ * - pt_denoise_defaults fills in the values a zero field (or params == NULL) stands for: levels 5, sigma_color 2,
+ *   sigma_depth 2^-5 (0.03125), flags 0.  They were chosen by the CPU study recorded in profiles/denoise_cpu_study.json.
+ * - PT_DN_LDS_MAXSTEP (environment, read once at pt_ctx_create): levels whose step is at most this value stage their taps in
+ *   LDS, the others read them through the caches.  Same bytes either way.
+ *
+ * THE ARITHMETIC.  Every operation is IEEE binary32 + - * / and sqrt, correctly rounded, never contracted, in the order the
+ * parentheses give.  max(a, b) stands for (a > b ? a : b), pos(v) for (v > 0 ? v : 0) - a NaN gives 0 - and |v| for v with
+ * its sign bit cleared.  +inf = the binary32 infinity.
+ * 1. Prepare, for every pixel p:
+ *    - hit(p) = depth[p] < +inf; without d_depth every pixel is a hit.
+ *    - l = sqrt((nx*nx + ny*ny) + nz*nz) of normal[p]; N(p) = (nx / l, ny / l, nz / l) if l > 0, else (0, 0, 0).
+ *    - per channel c: m_c(p) = albedo[p][c] > 2^-6 ? albedo[p][c] : 1; m_c = 1 without d_albedo or with
+ *      PT_DENOISE_NO_DEMODULATE.  u_0(p)[c] = color[p][c] / m_c(p).
+ * 2. Level i = 0 .. levels-1 with step s = 2^i, for every pixel p = (x, y):
+ *    sum = (0, 0, 0), wsum = 0.  For dy = -2..2 (outer loop), dx = -2..2 (inner loop), q = (x + dx*s, y + dy*s):
+ *    - q outside the frame: the tap is skipped.
+ *    - h = B[|dy|] * B[|dx|] with B = {3/8, 1/4, 1/16} (the products are exact).
+ *    - dx == 0 and dy == 0: w = h.
+ *    - else if hit(p) != hit(q): the tap is skipped (a miss never blends with a hit).
+ *    - else w = ((h * wn) * fall(xz)) * fall(xc), where
+ *        wn = 1 without d_normal or if p and q both miss; else e = pos((N(p).x*N(q).x + N(p).y*N(q).y) + N(p).z*N(q).z),
+ *             squared five times: e = e*e; e = e*e; e = e*e; e = e*e; wn = e*e  (e^32);
+ *        xz = 0 without d_depth or if p and q both miss; else with zp = depth[p], zq = depth[q]:
+ *             xz = |zp - zq| * (1 / (sds_i * max(zp, zq))), sds_i = sigma_depth * (float)s computed on the host in binary32;
+ *        xc = ((dr*dr + dg*dg) + db*db) * rc_i with (dr, dg, db) = u_i(p) - u_i(q), rc_i = 1 / (sc_i * sc_i) and
+ *             sc_i = sigma_color * 2^-i (2^-i exact), both computed on the host in binary32;
+ *        fall(v): t = pos(1 - v * 0.125); t = t*t; t = t*t; fall = t*t  (t^8: exp(-v)'s stand-in, zero from v = 8 on, exact
+ *             operations only, so that the device and a restatement in numpy agree bit for bit).
+ *    - sum[c] = sum[c] + u_i(q)[c] * w for c = 0, 1, 2; wsum = wsum + w.
+ *    u_{i+1}(p)[c] = sum[c] / wsum  (wsum >= 9/64: the centre tap).
+ * 3. Finish: out[p][c] = clamp(u_levels(p)[c] * m_c(p)) with clamp(v) = v < 0 ? 0 : (v > 1 ? 1 : v), as pt_ctx_render clamps. */
+typedef struct pt_denoise_params {
+    uint32_t levels;        /* a-trous levels, step 1, 2, 4, ...; 0 = the default; at most 8 */
+    float sigma_color;      /* 0 = the default */
+    float sigma_normal_pow; /* reserved: must be 0 (the exponent of the normal weight is fixed at 32) */
+    float sigma_depth;      /* 0 = the default */
+    uint32_t flags;         /* PT_DENOISE_NO_DEMODULATE */
+} pt_denoise_params;
+#define PT_DENOISE_NO_DEMODULATE 1u
+int pt_denoise_defaults(pt_denoise_params *out);
+int pt_ctx_denoise(pt_ctx *ctx, uint32_t width, uint32_t height, const pt_denoise_params *params,
+                   const float *d_color, const float *d_albedo, const float *d_normal, const float *d_depth,
+                   float *d_out, void *hip_stream);
+
 /* ---- the one collective of the path: the framebuffer gather over RCCL (xGMI) ---------------------------------
  * One process (or thread) per GPU renders its rows with pt_ctx_render (chunk_first = rank, chunk_step = n_ranks) into
  * device memory; pt_comm_gather_frame then gives EVERY rank the whole frame in device memory: one in-place

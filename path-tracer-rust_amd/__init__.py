@@ -48,6 +48,12 @@ class pt_stats(C.Structure):
                 ("ms_device", C.c_double), ("ms_intersect", C.c_double)]
 
 
+class pt_denoise_params(C.Structure):
+    _fields_ = [("levels", C.c_uint32), ("sigma_color", C.c_float), ("sigma_normal_pow", C.c_float),
+                ("sigma_depth", C.c_float), ("flags", C.c_uint32)]
+
+
+PT_DENOISE_NO_DEMODULATE = 1
 PT_OK, PT_ERR_INVALID, PT_ERR_NO_DEVICE, PT_ERR_HIP, PT_CANCELLED = 0, -1, -2, -3, -4
 PT_ERR_IO, PT_ERR_PARSE = -6, -7
 BACKEND_WAVEFRONT, BACKEND_MEGAKERNEL = 0, 1
@@ -85,6 +91,9 @@ def lib():
     L.pt_ctx_accum_load.argtypes = [C.c_void_p, C.c_char_p]
     L.pt_ctx_render_aov.argtypes = [C.c_void_p, C.POINTER(pt_config), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p]
+    L.pt_denoise_defaults.argtypes = [C.POINTER(pt_denoise_params)]
+    L.pt_ctx_denoise.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(pt_denoise_params), C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pt_write_pfm.argtypes = [C.c_char_p, C.POINTER(C.c_float), C.c_uint32, C.c_uint32, C.c_uint32]
     L.pt_ctx_set_profiling.argtypes = [C.c_void_p, C.c_int]
     L.pt_ctx_pass_kernel.argtypes = [C.c_void_p, C.c_uint32]
@@ -215,6 +224,22 @@ class Context:
         _check(lib().pt_ctx_render_aov(self._h, C.byref(cfg), ptr(albedo), ptr(normal), ptr(depth), ptr(object_id),
                                        C.c_void_p(stream or 0)))
 
+    def denoise(self, width, height, color, out, albedo=None, normal=None, depth=None, stream=None, **params):
+        """Denoise a whole width x height frame in device memory (pt_ctx_denoise): `color` and `out` are device pointers to
+        pixels * 3 float32 (out may be color); the guides albedo / normal (pixels * 3) and depth (pixels) are optional - what
+        render_aov writes for the same frame.  params: levels, sigma_color, sigma_depth (0 or absent = denoise_defaults()),
+        no_demodulate=True for PT_DENOISE_NO_DEMODULATE."""
+        p = pt_denoise_params()
+        p.flags = PT_DENOISE_NO_DEMODULATE if params.pop("no_demodulate", False) else 0
+        for k in ("levels", "sigma_color", "sigma_depth", "sigma_normal_pow"):
+            if k in params:
+                setattr(p, k, params.pop(k))
+        if params:
+            raise TypeError("denoise() got unexpected parameters %r" % sorted(params))
+        ptr = lambda q: C.c_void_p(q) if q else None  # noqa: E731
+        _check(lib().pt_ctx_denoise(self._h, width, height, C.byref(p), ptr(color), ptr(albedo), ptr(normal), ptr(depth),
+                                    ptr(out), C.c_void_p(stream or 0)))
+
     def accum_reset(self):
         _check(lib().pt_ctx_accum_reset(self._h))
 
@@ -289,6 +314,13 @@ def write_pfm(path, array):
         raise ValueError("write_pfm wants a (height, width[, channels]) array, not shape %r" % (a.shape,))
     channels = a.shape[2] if a.ndim == 3 else 1
     _check(lib().pt_write_pfm(os.fsencode(path), a.ctypes.data_as(C.POINTER(C.c_float)), a.shape[1], a.shape[0], channels))
+
+
+def denoise_defaults():
+    """The values pt_ctx_denoise uses for a zero field: {"levels", "sigma_color", "sigma_depth"} (pt_denoise_defaults)."""
+    p = pt_denoise_params()
+    _check(lib().pt_denoise_defaults(C.byref(p)))
+    return {"levels": p.levels, "sigma_color": p.sigma_color, "sigma_depth": p.sigma_depth}
 
 
 def build_flags():

@@ -13,6 +13,7 @@
 #include "../../include/ptrace.h"
 #include "pt_accum.h"
 #include "pt_aov.h"
+#include "pt_denoise.h"
 #include "pt_host.h"
 #include "pt_kernels.h"
 
@@ -103,8 +104,11 @@ struct Tuning {
     bool lds_say = false;        // PT_LDS_PAD set: the kernels that stage records in LDS say their layout on stderr (say_layout)
     size_t lds_pad = 0;          // PT_LDS_PAD=n: k_pass_cand asks for n bytes of LDS it does not use (diagnosis: where does the
                                  // fifth workgroup of a CU stop fitting?)
+    uint32_t dn_lds_maxstep = 0;  // PT_DN_LDS_MAXSTEP=n: pt_ctx_denoise's levels with step <= n stage their taps in LDS, the others
+                                  // load them through the caches (same bytes; 0 = every level direct, 128 = every level LDS)
     uint32_t debug = 0;
 };
+constexpr uint32_t kDnLdsMaxStepDefault = 4;  // measured: LDS wins at steps 1, 2, 4 and loses from 8 on
 static Tuning read_tuning() {
     Tuning t;
     auto num = [](const char *name, long long dflt) {
@@ -136,6 +140,10 @@ static Tuning read_tuning() {
     {
         const long long ws = num("PT_WAVE_STACK", 0);
         if (ws >= 512 && ws < (long long)kWaveStackMax && (ws & (ws - 1)) == 0) t.wave_stack = (uint32_t)ws;
+    }
+    {
+        const long long ms = num("PT_DN_LDS_MAXSTEP", kDnLdsMaxStepDefault);
+        t.dn_lds_maxstep = ms < 0 ? 0u : (ms > 128 ? 128u : (uint32_t)ms);
     }
 #ifdef PT_ALLOW_DEBUG
     t.debug = (uint32_t)num("PT_DEBUG", 0);
@@ -221,6 +229,8 @@ struct pt_ctx {
     std::vector<uint32_t> acc_cnt;
     DevBuf<unsigned long long> acc_held;
     uint64_t scene_fp = 0;
+    // pt_ctx_denoise's scratch, kept between calls: the two colour planes and the packed guides, one float4 per pixel each
+    DevBuf<float4> dn_u[2], dn_guide;
 };
 
 namespace {
@@ -1140,6 +1150,9 @@ void pt_ctx_destroy(pt_ctx *c) {
     c->blk_rays.release();
     c->acc.release();
     c->acc_held.release();
+    c->dn_u[0].release();
+    c->dn_u[1].release();
+    c->dn_guide.release();
     c->total_rays.release();
     (void)hipStreamDestroy(c->stream);
     delete c;
@@ -2157,6 +2170,97 @@ int pt_ctx_render_aov(pt_ctx *c, const pt_config *cfg, float *d_albedo, float *d
     const DevScene S = form_for(c, cfg->flags).scene;  // (k_aov reads neither the candidate scan nor an LDS layout)
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
     launch_aov(st, S, F, d_albedo, d_normal, d_depth, d_object_id);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    return PT_OK;
+}
+
+// the values a zero field of pt_denoise_params stands for: the minimum of the CPU study (profiles/denoise_cpu_study.json)
+static const pt_denoise_params kDenoiseDefaults = {5u, 2.0f, 0.0f, 0.03125f, 0u};
+
+int pt_denoise_defaults(pt_denoise_params *out) {
+    if (!out) {
+        set_error("out is NULL");
+        return PT_ERR_INVALID;
+    }
+    *out = kDenoiseDefaults;
+    return PT_OK;
+}
+
+int pt_ctx_denoise(pt_ctx *c, uint32_t width, uint32_t height, const pt_denoise_params *params, const float *d_color,
+                   const float *d_albedo, const float *d_normal, const float *d_depth, float *d_out, void *hip_stream) {
+    // everything that can be refused is refused here, before the device is touched
+    pt_denoise_params P = kDenoiseDefaults;
+    if (params) {
+        auto bad_sigma = [](float v) { return !(v >= 0.0f) || v == __builtin_inff(); };
+        if (params->levels > 8u) {
+            set_error("pt_denoise_params.levels exceeds 8");
+            return PT_ERR_INVALID;
+        }
+        if (bad_sigma(params->sigma_color) || bad_sigma(params->sigma_depth)) {
+            set_error("pt_denoise_params: a sigma is negative or not finite");
+            return PT_ERR_INVALID;
+        }
+        if (!(params->sigma_normal_pow == 0.0f)) {
+            set_error("pt_denoise_params.sigma_normal_pow is reserved and must be 0");
+            return PT_ERR_INVALID;
+        }
+        if (params->flags & ~PT_DENOISE_NO_DEMODULATE) {
+            set_error("pt_denoise_params.flags: unknown bits");
+            return PT_ERR_INVALID;
+        }
+        if (params->levels) P.levels = params->levels;
+        if (params->sigma_color != 0.0f) P.sigma_color = params->sigma_color;
+        if (params->sigma_depth != 0.0f) P.sigma_depth = params->sigma_depth;
+        P.flags = params->flags;
+    }
+    if (!width || !height) {
+        set_error("width and height must be positive");
+        return PT_ERR_INVALID;
+    }
+    if ((uint64_t)width * height > (1ull << 28)) {
+        set_error("width*height exceeds 2^28");
+        return PT_ERR_INVALID;
+    }
+    if (!d_color || !d_out) {
+        set_error("d_color or d_out is NULL");
+        return PT_ERR_INVALID;
+    }
+    if (!c) {
+        set_error("ctx is NULL");
+        return PT_ERR_INVALID;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t npix = (size_t)width * height;
+    for (int k = 0; k < 2; ++k) {
+        const int rc = c->dn_u[k].ensure(npix);
+        if (rc) return rc;
+    }
+    {
+        const int rc = c->dn_guide.ensure(npix);
+        if (rc) return rc;
+    }
+    DenoiseFrame f{};
+    f.width = width;
+    f.height = height;
+    f.color = d_color;
+    f.albedo = (P.flags & PT_DENOISE_NO_DEMODULATE) ? nullptr : d_albedo;
+    f.normal = d_normal;
+    f.depth = d_depth;
+    f.guide = c->dn_guide.p;
+    f.u[0] = c->dn_u[0].p;
+    f.u[1] = c->dn_u[1].p;
+    f.out = d_out;
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    launch_dn_prepare(st, f);
+    float scale = 1.0f;  // 2^-i
+    for (uint32_t i = 0; i < P.levels; ++i, scale *= 0.5f) {
+        const uint32_t s = 1u << i;
+        const float sc = P.sigma_color * scale;
+        const float rc = 1.0f / (sc * sc);
+        const float sds = P.sigma_depth * (float)s;
+        launch_dn_level(st, f, i, rc, sds, i + 1u == P.levels, s <= c->tune.dn_lds_maxstep);
+    }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
     return PT_OK;

@@ -1,0 +1,28 @@
+// pt_denoise.h — the edge-avoiding a-trous filter behind pt_ctx_denoise (pt_denoise.hip): prepare packs the guides and the
+// demodulated colour, one launch per level ping-pongs the colour plane, the last level multiplies the albedo back and clamps.
+// The arithmetic is the contract in include/ptrace.h, operation for operation.  A translation unit of its own: pt_kernels.s,
+// and so pt_kernel_isa_hash(), describes the pass kernels only.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+namespace pt {
+
+struct DenoiseFrame {
+    uint32_t width, height;
+    const float *color, *albedo, *normal, *depth;  // albedo: NULL also under PT_DENOISE_NO_DEMODULATE
+    float4 *guide;                                 // (N.xyz, depth) per pixel; depth 0 without a depth buffer (every pixel a hit)
+    float4 *u[2];                                  // the colour planes, (r, g, b, unused)
+    float *out;
+};
+
+// u[0] and guide from the caller's buffers
+void launch_dn_prepare(hipStream_t st, const DenoiseFrame &f);
+// level i: u[i & 1] -> u[(i + 1) & 1], or -> f.out (times m, clamped) when `last`.  rc = 1 / sc_i^2, sds = sigma_depth * 2^i
+// (host binary32).  lds: the workgroup stages its taps in LDS (any step: the tile is dense in x up to step 4, a lattice of
+// the step beyond, and always a lattice in y); otherwise every tap is a global load.  Same results.
+void launch_dn_level(hipStream_t st, const DenoiseFrame &f, uint32_t i, float rc, float sds, bool last, bool lds);
+
+}  // namespace pt

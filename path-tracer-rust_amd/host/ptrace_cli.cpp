@@ -21,12 +21,16 @@ static void usage() {
     fprintf(stderr,
             "usage: ptrace <samplesPerPixel> <y-resolution> <scene id|index> [--width W] [--backend wavefront|megakernel]\n"
             "              [--seed S] [--gpus N] [--root DIR] [--out DIR] [--no-ppm] [--checkpoint FILE] [--aov N]\n"
+            "              [--denoise [N]]\n"
             "  --checkpoint FILE: continue from the samples FILE holds (if it exists), render up to <samplesPerPixel> in all and\n"
             "                     save them to FILE; one GPU only; the seed defaults to 0 instead of the clock, so that the same\n"
             "                     command continues the same frame\n"
             "  --aov N: after the frame, first-hit AOVs over its first N samples on one GPU, written next to the image as\n"
             "           PFM files: ...-beauty.pfm (the linear frame), -albedo, -normal, -depth (+inf on a miss) and -id (the\n"
-            "           object index as a float, -1 on a miss)\n");
+            "           object index as a float, -1 on a miss)\n"
+            "  --denoise [N]: after the frame, denoise it on the GPU (pt_ctx_denoise, default parameters) with first-hit guides over\n"
+            "           its first N samples (default 16), written next to the image as ...-denoised.ppm and ...-denoised.pfm; one\n"
+            "           GPU only\n");
 }
 
 static std::vector<std::string> scene_ids(const std::string &root) {
@@ -47,10 +51,19 @@ static void progress(void *, float f) {
     fflush(stderr);
 }
 
-constexpr int kCliExit = 1000;  // render_checkpointed: the message is out, exit 1
+constexpr int kCliExit = 1000;  // render_on_context: the message is out, exit 1
 
-// --checkpoint: one context on one GPU, the frame accumulated from what FILE holds up to cfg->spp, FILE saved again
-static int render_checkpointed(const pt_config *cfg, pt_scene *sc, const std::string &file, std::vector<float> &img, pt_stats *st) {
+// a frame that stays on its GPU after the render (--denoise filters it there)
+struct DeviceFrame {
+    int dev = 0;
+    pt_ctx *ctx = nullptr;
+    void *d_out = nullptr;
+};
+
+// --checkpoint / --denoise: one context on one GPU.  With FILE the frame is accumulated from what FILE holds up to cfg->spp and
+// FILE is saved again; without, it is rendered.  `keep` takes the context and the device frame instead of their being freed.
+static int render_on_context(const pt_config *cfg, pt_scene *sc, const std::string &file, std::vector<float> &img, pt_stats *st,
+                             DeviceFrame *keep) {
     int dev = 0;
     if (const char *e = getenv("PT_DEVICE")) dev = atoi(e);
     uint32_t n_objs = 0, n_tris = 0;
@@ -59,7 +72,7 @@ static int render_checkpointed(const pt_config *cfg, pt_scene *sc, const std::st
     pt_ctx *ctx = nullptr;
     int rc = pt_ctx_create(dev, &ctx);
     if (!rc) rc = pt_ctx_set_scene(ctx, pt_scene_camera(sc), objs, n_objs, tris, n_tris);
-    if (!rc && access(file.c_str(), F_OK) == 0) {
+    if (!rc && !file.empty() && access(file.c_str(), F_OK) == 0) {
         rc = pt_ctx_accum_load(ctx, file.c_str());
         if (rc) {
             fprintf(stderr, "cannot resume from %s (%d): %s\n", file.c_str(), rc, pt_last_error());
@@ -89,14 +102,53 @@ static int render_checkpointed(const pt_config *cfg, pt_scene *sc, const std::st
     void *d_out = nullptr;
     const size_t bytes = img.size() * sizeof(float);
     if (!rc) rc = pt_device_malloc(dev, bytes, &d_out);
-    if (!rc) rc = pt_ctx_accumulate(ctx, cfg, d_out, nullptr, nullptr, progress, nullptr, st);
+    if (!rc)
+        rc = file.empty() ? pt_ctx_render(ctx, cfg, d_out, nullptr, nullptr, progress, nullptr, st)
+                          : pt_ctx_accumulate(ctx, cfg, d_out, nullptr, nullptr, progress, nullptr, st);
     if (!rc) rc = pt_device_download(dev, img.data(), d_out, bytes);
-    if (!rc) {
+    if (!rc && !file.empty()) {
         rc = pt_ctx_accum_save(ctx, file.c_str());
         if (rc) fprintf(stderr, "cannot save checkpoint %s: %s\n", file.c_str(), pt_last_error());
     }
+    if (!rc && keep) {
+        keep->dev = dev;
+        keep->ctx = ctx;
+        keep->d_out = d_out;
+        return rc;
+    }
     if (d_out) pt_device_free(dev, d_out);
     if (ctx) pt_ctx_destroy(ctx);
+    return rc;
+}
+
+// --denoise: first-hit guides over the frame's first `spp` samples, pt_ctx_denoise in place on the device frame, and the two
+// files at `stem`
+static int write_denoised(const pt_config *frame, uint32_t spp, const DeviceFrame &df, const std::string &stem, const char *scene_id) {
+    pt_config cfg = *frame;
+    cfg.spp = spp;
+    const size_t npix = (size_t)cfg.width * cfg.height;
+    std::vector<float> img(npix * 3);
+    void *d_buf = nullptr;
+    int rc = pt_device_malloc(df.dev, npix * 7 * sizeof(float), &d_buf);
+    if (!rc) {
+        float *d_albedo = (float *)d_buf, *d_normal = d_albedo + npix * 3, *d_depth = d_normal + npix * 3;
+        rc = pt_ctx_render_aov(df.ctx, &cfg, d_albedo, d_normal, d_depth, nullptr, nullptr);
+        if (!rc)
+            rc = pt_ctx_denoise(df.ctx, cfg.width, cfg.height, nullptr, (const float *)df.d_out, d_albedo, d_normal, d_depth,
+                                (float *)df.d_out, nullptr);
+        if (!rc) rc = pt_device_download(df.dev, img.data(), df.d_out, npix * 3 * sizeof(float));
+    }
+    if (d_buf) pt_device_free(df.dev, d_buf);
+    if (rc) {
+        fprintf(stderr, "denoising failed (%d): %s\n", rc, pt_last_error());
+        return rc;
+    }
+    const std::string ppm = stem + "denoised.ppm", pfm = stem + "denoised.pfm";
+    rc = pt_write_ppm(ppm.c_str(), img.data(), cfg.width, cfg.height, frame->spp, scene_id, 0);
+    if (!rc) printf("wrote %s\n", ppm.c_str());
+    if (!rc) rc = pt_write_pfm(pfm.c_str(), img.data(), cfg.width, cfg.height, 3);
+    if (!rc) printf("wrote %s\n", pfm.c_str());
+    if (rc) fprintf(stderr, "cannot write the denoised frame: %s\n", pt_last_error());
     return rc;
 }
 
@@ -164,7 +216,7 @@ int main(int argc, char **argv) {
     bool seed_given = false;
     std::string checkpoint;
     bool write_ppm = true;
-    uint32_t gpus = 1, aov_spp = 0;
+    uint32_t gpus = 1, aov_spp = 0, denoise_spp = 0;
     for (int i = 4; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&]() -> const char * { return i + 1 < argc ? argv[++i] : ""; };
@@ -192,6 +244,17 @@ int main(int argc, char **argv) {
                 return 1;
             }
         }
+        else if (a == "--denoise") {
+            denoise_spp = 16;
+            // the count is optional: taken when the next argument is a number
+            if (i + 1 < argc && argv[i + 1][0] != '\0' && strspn(argv[i + 1], "0123456789") == strlen(argv[i + 1])) {
+                denoise_spp = (uint32_t)strtoul(argv[++i], nullptr, 10);
+                if (!denoise_spp) {
+                    usage();
+                    return 1;
+                }
+            }
+        }
         else {
             usage();
             return 1;
@@ -203,6 +266,10 @@ int main(int argc, char **argv) {
     }
     if (!checkpoint.empty() && gpus > 1) {
         fprintf(stderr, "--checkpoint works with one GPU only (--gpus %u)\n", gpus);
+        return 1;
+    }
+    if (denoise_spp && gpus > 1) {
+        fprintf(stderr, "--denoise works with one GPU only (--gpus %u)\n", gpus);
         return 1;
     }
     if (!checkpoint.empty() && !seed_given) seed = 0;
@@ -250,19 +317,25 @@ int main(int argc, char **argv) {
     cfg.seed = seed;
     std::vector<float> img((size_t)width * res_y * 3, 0.0f);
     pt_stats st;
-    if (checkpoint.empty())
+    DeviceFrame df;
+    if (checkpoint.empty() && !denoise_spp)
         rc = pt_render_multi(&cfg, gpus ? gpus : 1, pt_scene_camera(sc), objs, n_objs, tris, n_tris, img.data(), nullptr,
                              progress, nullptr, &st);
     else
-        rc = render_checkpointed(&cfg, sc, checkpoint, img, &st);
-    if (rc == kCliExit) {
+        rc = render_on_context(&cfg, sc, checkpoint, img, &st, denoise_spp ? &df : nullptr);
+    auto release = [&]() {
+        if (df.d_out) pt_device_free(df.dev, df.d_out);
+        if (df.ctx) pt_ctx_destroy(df.ctx);
         pt_scene_free(sc);
+    };
+    if (rc == kCliExit) {
+        release();
         return 1;
     }
     fprintf(stderr, "\n");
     if (rc) {
         fprintf(stderr, "render failed (%d): %s\n", rc, pt_last_error());
-        pt_scene_free(sc);
+        release();
         return 2;
     }
     printf("Rendering complete\n");
@@ -275,13 +348,13 @@ int main(int argc, char **argv) {
     strftime(stamp, sizeof stamp, "%Y-%m-%d_%H:%M:%S", localtime(&now));
     const std::string stem = out_dir + "/" + stamp + "-scene-" + pt_scene_id(sc) + "-spp" + std::to_string(spp) + "-res" +
                              std::to_string(res_y) + "-";
-    if (write_ppm || aov_spp) mkdir(out_dir.c_str(), 0755);  // create_dir_all("out"), mod.rs:1032
+    if (write_ppm || aov_spp || denoise_spp) mkdir(out_dir.c_str(), 0755);  // create_dir_all("out"), mod.rs:1032
     if (write_ppm) {
         const std::string path = stem + ".ppm";
         rc = pt_write_ppm(path.c_str(), img.data(), width, res_y, spp, pt_scene_id(sc), (uint64_t)(st.ms_total / 1000.0));
         if (rc) {
             fprintf(stderr, "cannot write %s: %s\n", path.c_str(), pt_last_error());
-            pt_scene_free(sc);
+            release();
             return 3;
         }
         unlink("latest.ppm");  // mod.rs:1079-1088
@@ -290,9 +363,13 @@ int main(int argc, char **argv) {
         printf("wrote %s\n", path.c_str());
     }
     if (aov_spp && write_aovs(&cfg, aov_spp, sc, img, stem)) {
-        pt_scene_free(sc);
+        release();
         return 3;
     }
-    pt_scene_free(sc);
+    if (denoise_spp && write_denoised(&cfg, denoise_spp, df, stem, pt_scene_id(sc))) {
+        release();
+        return 3;
+    }
+    release();
     return 0;
 }
