@@ -87,6 +87,29 @@ pub struct PtDenoiseParams {
     pub sigma_depth: f32,
     pub flags: u32,
 }
+
+// pt_ctx_accum_noise's frame statistics: the error estimate e(p) from the two halves of a noise-tracked frame's samples
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct PtNoiseStats {
+    pub spp_min: u32,
+    pub spp_max: u32,
+    pub spp_a_min: u32,
+    pub spp_b_min: u32,
+    pub pixels: u64,
+    pub mean_error: f64,
+    pub histogram: [u32; 64],
+}
+
+// pt_ctx_accumulate_until's stopping rule; a zero criterion is not used
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct PtNoiseTarget {
+    pub mean_error: f32,
+    pub quantile: f32,
+    pub quantile_error: f32,
+    pub min_spp: u32,
+}
 pub const PT_DENOISE_NO_DEMODULATE: u32 = 1;
 
 pub const PT_OK: i32 = 0;
@@ -154,6 +177,28 @@ extern "C" {
     pub fn pt_ctx_accum_reset(ctx: *mut PtCtx) -> i32;
     pub fn pt_ctx_accum_save(ctx: *mut PtCtx, path: *const c_char) -> i32;
     pub fn pt_ctx_accum_load(ctx: *mut PtCtx, path: *const c_char) -> i32;
+    // noise tracking: half of every pixel's samples is summed a second time, so that the frame's error can be estimated
+    pub fn pt_ctx_accum_track_noise(ctx: *mut PtCtx, enabled: i32) -> i32;
+    pub fn pt_ctx_accum_noise(
+        ctx: *mut PtCtx,
+        cfg: *const PtConfig,
+        d_error: *mut f32,
+        out: *mut PtNoiseStats,
+        hip_stream: *mut c_void,
+    ) -> i32;
+    // pt_ctx_accumulate until the estimate meets tgt; cfg.spp is the cap
+    pub fn pt_ctx_accumulate_until(
+        ctx: *mut PtCtx,
+        cfg: *const PtConfig,
+        tgt: *const PtNoiseTarget,
+        d_out_rgb: *mut c_void,
+        hip_stream: *mut c_void,
+        cancel: *const u8,
+        cb: Option<PtProgressFn>,
+        user: *mut c_void,
+        stats: *mut PtStats,
+        noise: *mut PtNoiseStats,
+    ) -> i32;
     // first-hit AOVs of the frame cfg describes (device buffers, any may be null): mean albedo and ray-facing normal over the
     // first cfg.spp samples, sample 0's depth and object id - a denoiser's guides, a pick map
     pub fn pt_ctx_render_aov(

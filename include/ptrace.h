@@ -370,6 +370,88 @@ int pt_ctx_accum_save(pt_ctx *ctx, const char *path);
  * each of these the held accumulator is left as it was.  No input crashes the loader. */
 int pt_ctx_accum_load(pt_ctx *ctx, const char *path);
 
+/* ---- how noisy is the held frame: half buffers, a per-pixel estimate, rendering to a target -------------------------
+ * The dual-buffer estimate of Dammertz, Hanika, Keller and Lensch, "A Hierarchical Automatic Stopping Condition for Monte Carlo
+ * Global Illumination" (2010): the samples of every pixel are dealt to two halves A and B, and the difference of the two
+ * half images estimates the error of the whole.  Sums are u64 32.32 fixed point, so sums of disjoint sample sets add and
+ * subtract exactly: the context keeps the sums of A beside the held sums (same layout, 24 B per pixel more), and B is
+ * held - A, never stored.
+ *
+ * pt_ctx_accum_track_noise switches tracking on or off for the frames this context starts AFTER the call (off by default).
+ * PT_ERR_INVALID for a NULL ctx and while an accumulator is held (call pt_ctx_accum_reset first).  With tracking off nothing
+ * changes anywhere.  With tracking on, pt_ctx_accumulate's frame is still pt_ctx_render's frame at cfg->spp, bit for bit -
+ * only the batching of the samples changes - and pt_stats counts the same samples and bounces; `passes` may be larger.
+ * - A part (see pt_ctx_accumulate) holds c samples, nA of them in A, nB = c - nA in B.
+ * - A call that brings the part from c to T traces [c, m) and then [m, T), m = min(T, c + 4 * ceil((T - c) / 8)): the first
+ *   run is rounded up to whole groups of the four sub-pixels (s%2, (s/2)%2).  An empty second run is dropped.
+ * - After a run, the samples it traced (fewer after a cancel) go to the half that holds fewer samples of that part; a tie
+ *   goes to A.  So from zero: 0 -> 4 (A) -> 8 (B); then to 24: 8 -> 16 (A) -> 24 (B).
+ * - The megakernel renders the whole call at once only when c AND nA are equal over all parts.
+ * - WHICH samples A holds depends on the history of calls (and of cancels), not only on T: two hosts that reach T by
+ *   different steps hold different halves, and so slightly different estimates.  What does not depend on history: the held
+ *   sums, the output image, pt_ctx_accum_info.
+ * - pt_ctx_accum_reset, pt_ctx_set_scene and a call with another frame key drop A with the held sums; pt_ctx_render touches
+ *   neither; pt_ctx_snapshot is unchanged.
+ * - Checkpoints.  pt_ctx_accum_save of a tracked frame keeps the magic "PTACCUM1" and writes format version 2: version 1 with
+ *   the per-part nA (u32 each) after the counts and the planes of A (3 x call pixels of u64) after the sums; the trailing hash
+ *   covers everything.  An untracked frame is written as version 1, byte for byte as before.  pt_ctx_accum_load reads both:
+ *   a version-2 file gives a tracked frame whatever the context's switch says; a version-1 file loaded into a context with
+ *   tracking on gives a tracked frame with nA = 0 and A = 0 - everything so far counts as B, the estimate starts with the next
+ *   samples, and the weight w below handles unequal halves.  PT_ERR_PARSE also for a version-2 file with some nA > c. */
+int pt_ctx_accum_track_noise(pt_ctx *ctx, int enabled);
+
+/* THE NOISE ESTIMATE.  Every operation is IEEE binary32 + - * / and sqrt, correctly rounded, never contracted, in the order
+ * the parentheses give, except the conversion of a sum, which is pt_ctx_render's: mean(S, n) = clamp((float)((double)S * 2^-32)
+ * / (float)n) - the u64 to binary64, times 2^-32 (exact), rounded to binary32, divided in binary32 - with clamp(v) = v < 0 ? 0 :
+ * (v > 1 ? 1 : v).  |v| is v with its sign bit cleared.  For pixel p of a part with nA > 0 and nB > 0, H_c / A_c its held / half-A
+ * sums of channel c = r, g, b:
+ *   a_c = mean(A_c, nA),  b_c = mean(H_c - A_c, nB),  m_c = mean(H_c, nA + nB)   (m: the value pt_ctx_accumulate writes)
+ *   e(p) = (((|a_r - b_r| + |a_g - b_g|) + |a_b - b_b|) * w) / sqrt(2^-6 + ((m_r + m_g) + m_b))
+ *   w = sqrt((float)nA * (float)nB) / ((float)nA + (float)nB), computed on the host in binary32 per part: 1/2 for equal halves;
+ *       it makes |a - b| * w an estimate of the deviation of the whole pixel's mean for any split.
+ * So 0 <= e(p) <= 3 * (1/2) / sqrt(2^-6) = 12.
+ * Frame statistics, over the pixels with an estimate, in the same launch:
+ * - sum = the sum of floor(e(p) * 2^28) as unsigned integers (36.28 fixed point in a u64, integer atomics: the order does not
+ *   matter).  A term is below 2^32, pt_ctx_denoise's largest frame has 2^28 pixels and pt_ctx_accumulate's 2^31: the sum stays
+ *   below 2^63.  mean_error = (double)sum * 2^-28 / (double)pixels.
+ * - histogram: k = (the bits of e(p) as a u32) >> 21 - exponent and the top two mantissa bits, four bins per octave from 2^-12 -
+ *   bin = k <= 460 ? 0 : (k >= 523 ? 63 : k - 460).  Bin b holds lo(b) <= e < hi(b), hi(b) = the float with bits (461 + b) << 21
+ *   (hi(0) = 1.25 * 2^-12, hi(62) = 14), lo(b) = hi(b - 1); bin 0 also takes everything below, bin 63 everything from 14 on
+ *   (its upper edge is +inf; it stays empty).  A host reads quantiles from it. */
+typedef struct pt_noise_stats {
+    uint32_t spp_min, spp_max;     /* as pt_ctx_accum_info */
+    uint32_t spp_a_min, spp_b_min; /* smallest nA / nB over the parts */
+    uint64_t pixels;               /* pixels with an estimate (parts with nA > 0 and nB > 0) */
+    double mean_error;             /* mean of e(p) over those pixels */
+    uint32_t histogram[64];        /* e(p) in the fixed bins above */
+} pt_noise_stats;
+/* The estimate of the held frame.  cfg names the frame as for pt_ctx_accum_info (its spp only has to be valid).  d_error: NULL,
+ * or a device pointer of pt_config_pixels(cfg) floats that receives e(p) in the call's pixel order; a pixel of a part without
+ * an estimate gets +inf.  `hip_stream` as for pt_ctx_render; blocking.  PT_ERR_INVALID: a NULL ctx, cfg or out; cfg is not the
+ * held frame; the frame is not tracked; no part has nA > 0 and nB > 0.  Reads 48 B and writes 4 B per pixel; changes no state of
+ * the context. */
+int pt_ctx_accum_noise(pt_ctx *ctx, const pt_config *cfg, float *d_error, pt_noise_stats *out, void *hip_stream);
+
+typedef struct pt_noise_target {
+    float mean_error;     /* stop when stats.mean_error <= this; 0 = not used */
+    float quantile;       /* in (0,1); 0 = not used */
+    float quantile_error; /* stop when the upper edge of the histogram's quantile bin <= this */
+    uint32_t min_spp;     /* 0 = 16 */
+} pt_noise_target;
+/* Renders cfg's frame until it is as clean as `tgt` asks, cfg->spp samples per pixel at most (the cap): a host loop over
+ * pt_ctx_accumulate and pt_ctx_accum_noise.  It accumulates to max(samples held, min_spp), then to twice as many each step,
+ * never beyond the cap; after each step it evaluates the noise, and stops at the first step where every criterion in use holds
+ * (PT_OK), at the cap (PT_OK too: *noise tells which - noise->spp_max, noise->mean_error) or on a cancel (PT_CANCELLED; a later
+ * call continues).  The quantile bin is the first bin at which the cumulative count reaches ceil(quantile * pixels).  A step
+ * after which no part has both halves (a cap below 5) meets no criterion; *noise then has pixels 0 and mean_error +inf.
+ * d_out_rgb holds pt_ctx_render's frame at the sample count reached, bit for bit.  stats (may be NULL) sums the steps.
+ * Progress is the fraction of the cap's samples traced, and 1 at the end.
+ * PT_ERR_INVALID, refused before any device is touched and checked in this order: NULL cfg, tgt, d_out_rgb or noise; a
+ * mean_error, quantile or quantile_error that is negative or not finite; neither criterion in use; a quantile of 1 or more; NULL
+ * ctx; the context is not tracking (or the held frame of cfg is not tracked); cfg->spp below what is held. */
+int pt_ctx_accumulate_until(pt_ctx *ctx, const pt_config *cfg, const pt_noise_target *tgt, void *d_out_rgb, void *hip_stream,
+                            const volatile uint8_t *cancel, pt_progress_fn cb, void *user, pt_stats *stats, pt_noise_stats *noise);
+
 /* ---- first-hit AOVs: guide buffers for a denoiser, a pick map for a GUI ------------------------------------------
  * pt_ctx_render_aov covers the pixels pt_ctx_render covers with the same cfg - pt_config_pixels(cfg) of them, in the same
  * order (the band [idx_begin, idx_end) and the interleaved chunks included); pixel k of the call has framebuffer index p.

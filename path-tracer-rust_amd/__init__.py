@@ -53,6 +53,15 @@ class pt_denoise_params(C.Structure):
                 ("sigma_depth", C.c_float), ("flags", C.c_uint32)]
 
 
+class pt_noise_stats(C.Structure):
+    _fields_ = [("spp_min", C.c_uint32), ("spp_max", C.c_uint32), ("spp_a_min", C.c_uint32), ("spp_b_min", C.c_uint32),
+                ("pixels", C.c_uint64), ("mean_error", C.c_double), ("histogram", C.c_uint32 * 64)]
+
+
+class pt_noise_target(C.Structure):
+    _fields_ = [("mean_error", C.c_float), ("quantile", C.c_float), ("quantile_error", C.c_float), ("min_spp", C.c_uint32)]
+
+
 PT_DENOISE_NO_DEMODULATE = 1
 PT_OK, PT_ERR_INVALID, PT_ERR_NO_DEVICE, PT_ERR_HIP, PT_CANCELLED = 0, -1, -2, -3, -4
 PT_ERR_IO, PT_ERR_PARSE = -6, -7
@@ -89,6 +98,10 @@ def lib():
     L.pt_ctx_accum_reset.argtypes = [C.c_void_p]
     L.pt_ctx_accum_save.argtypes = [C.c_void_p, C.c_char_p]
     L.pt_ctx_accum_load.argtypes = [C.c_void_p, C.c_char_p]
+    L.pt_ctx_accum_track_noise.argtypes = [C.c_void_p, C.c_int]
+    L.pt_ctx_accum_noise.argtypes = [C.c_void_p, C.POINTER(pt_config), C.c_void_p, C.POINTER(pt_noise_stats), C.c_void_p]
+    L.pt_ctx_accumulate_until.argtypes = [C.c_void_p, C.POINTER(pt_config), C.POINTER(pt_noise_target), C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(pt_stats), C.POINTER(pt_noise_stats)]
     L.pt_ctx_render_aov.argtypes = [C.c_void_p, C.POINTER(pt_config), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p]
     L.pt_denoise_defaults.argtypes = [C.POINTER(pt_denoise_params)]
@@ -239,6 +252,31 @@ class Context:
         ptr = lambda q: C.c_void_p(q) if q else None  # noqa: E731
         _check(lib().pt_ctx_denoise(self._h, width, height, C.byref(p), ptr(color), ptr(albedo), ptr(normal), ptr(depth),
                                     ptr(out), C.c_void_p(stream or 0)))
+
+    def accum_track_noise(self, on=True):
+        """Keep half of every pixel's samples in a second accumulator for the frames started from now on
+        (pt_ctx_accum_track_noise), so that accum_noise() / accumulate_until() can estimate the frame's error."""
+        _check(lib().pt_ctx_accum_track_noise(self._h, 1 if on else 0))
+
+    def accum_noise(self, width, height, seed=1, band=None, chunks=None, error=None, stream=None):
+        """The error estimate of the held, noise-tracked frame (pt_ctx_accum_noise): returns pt_noise_stats; `error`, if
+        given, is a device pointer to pixels float32 that receives the per-pixel estimate."""
+        cfg = self._config(width, height, 1, seed, band=band, chunks=chunks)
+        ns = pt_noise_stats()
+        _check(lib().pt_ctx_accum_noise(self._h, C.byref(cfg), C.c_void_p(error) if error else None, C.byref(ns),
+                                        C.c_void_p(stream or 0)))
+        return ns
+
+    def accumulate_until(self, out_ptr, width, height, max_spp, mean_error=0.0, quantile=0.0, quantile_error=0.0, min_spp=0,
+                         seed=1, backend="wavefront", band=None, rays_per_pass=0, stream=None, chunks=None):
+        """accumulate() in doubling steps until the estimated error meets the target or max_spp is reached
+        (pt_ctx_accumulate_until).  Returns (pt_stats summed over the steps, pt_noise_stats of the frame it ended with)."""
+        cfg = self._config(width, height, max_spp, seed, backend, band, rays_per_pass, chunks)
+        tgt = pt_noise_target(mean_error, quantile, quantile_error, min_spp)
+        st, ns = pt_stats(), pt_noise_stats()
+        _check(lib().pt_ctx_accumulate_until(self._h, C.byref(cfg), C.byref(tgt), C.c_void_p(out_ptr), C.c_void_p(stream or 0),
+                                             None, None, None, C.byref(st), C.byref(ns)))
+        return st, ns
 
     def accum_reset(self):
         _check(lib().pt_ctx_accum_reset(self._h))

@@ -18,5 +18,8 @@ void launch_accum_gather(hipStream_t st, const unsigned long long *held, uint32_
 // acc -> held, the npix pixels of the part
 void launch_accum_scatter(hipStream_t st, const unsigned long long *acc, uint32_t npix, uint32_t K, uint32_t m,
                           unsigned long long *held, uint32_t stride);
+// the same, for a job of a noise-tracked frame whose samples go to half A: half_a (laid out as held) += new sum - held sum
+void launch_accum_scatter_half(hipStream_t st, const unsigned long long *acc, uint32_t npix, uint32_t K, uint32_t m,
+                               unsigned long long *held, unsigned long long *half_a, uint32_t stride);
 
 }  // namespace pt

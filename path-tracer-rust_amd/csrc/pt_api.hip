@@ -16,6 +16,7 @@
 #include "pt_denoise.h"
 #include "pt_host.h"
 #include "pt_kernels.h"
+#include "pt_noise.h"
 
 namespace pt {
 
@@ -229,6 +230,13 @@ struct pt_ctx {
     std::vector<uint32_t> acc_cnt;
     DevBuf<unsigned long long> acc_held;
     uint64_t scene_fp = 0;
+    // Noise tracking (pt_ctx_accum_track_noise).  acc_track: the frames this context starts are tracked; acc_tracked: the held
+    // frame is - acc_a then holds the sums of half A of its samples, laid out as acc_held, and acc_na how many samples per
+    // pixel of each part went to it (half B: acc_held - acc_a, acc_cnt - acc_na).  noise_cnt: pt_ctx_accum_noise's counters.
+    bool acc_track = false, acc_tracked = false;
+    std::vector<uint32_t> acc_na;
+    DevBuf<unsigned long long> acc_a;
+    DevBuf<NoiseCounters> noise_cnt;
     // pt_ctx_denoise's scratch, kept between calls: the two colour planes and the packed guides, one float4 per pixel each
     DevBuf<float4> dn_u[2], dn_guide;
 };
@@ -848,6 +856,9 @@ void accum_drop(pt_ctx *c) {
     c->acc_cnt.clear();
     c->acc_total = c->acc_part_px = 0;
     c->acc_held.release();
+    c->acc_tracked = false;
+    c->acc_na.clear();
+    c->acc_a.release();
 }
 
 // The checkpoint's scene fingerprint: SipHash-1-3 (zero key) over n_objs, n_tris (u32 each), then the camera, the objects and
@@ -876,14 +887,17 @@ int accum_resolve_part(pt_ctx *c, uint32_t i, float *out, hipStream_t st) {
     return PT_OK;
 }
 
-// One piece of a frame call: pixels [k0, k0 + n) of the call, samples [s_first, cfg->spp) of each, the accumulators starting
-// from `held` (held.p == nullptr: from zero).  Progress inside it is reported as base + scale * f of the call, and its start
-// is a progress point at `base`.  [part_lo, part_hi): the parts of pt_ctx_accumulate's counts it brings to cfg->spp.
+// One piece of a frame call: pixels [k0, k0 + n) of the call, samples [s_first, s_end) of each (s_end 0: cfg->spp), the
+// accumulators starting from `held` (held.p == nullptr: from zero).  Progress inside it is reported as base + scale * f of the
+// call, and its start is a progress point at `base`.  [part_lo, part_hi): the parts of pt_ctx_accumulate's counts it brings to
+// its last sample.  `boundary`: the fraction reported at its start when that is not `base` (the second job of a part).
 struct Job {
     uint32_t k0, n, s_first;
     HeldSums held;
     float base, scale;
     uint32_t part_lo, part_hi;
+    uint32_t s_end = 0;
+    float boundary = -1.0f;
 };
 
 void add_stats(pt_stats *stats, const pt_stats &s) {
@@ -926,7 +940,13 @@ int keep_job(pt_ctx *c, const pt_config *cfg, const Job &j, int rc, hipStream_t 
         set_error("accumulator layout does not cover the part");
         return PT_ERR_HIP;
     }
-    launch_accum_scatter(st, c->acc.p, j.n, c->live.streams, c->live.m, c->acc_held.p + j.k0, j.held.stride);
+    // A noise-tracked frame deals the samples of a job to the half that holds fewer of them in its part (a tie: to A); the
+    // parts of one job hold the same counts.  Half B is never stored: a job that goes to it only moves the counts.
+    const bool to_a = c->acc_tracked && c->acc_na[j.part_lo] <= c->acc_cnt[j.part_lo] - c->acc_na[j.part_lo];
+    if (to_a)
+        launch_accum_scatter_half(st, c->acc.p, j.n, c->live.streams, c->live.m, c->acc_held.p + j.k0, c->acc_a.p + j.k0, j.held.stride);
+    else
+        launch_accum_scatter(st, c->acc.p, j.n, c->live.streams, c->live.m, c->acc_held.p + j.k0, j.held.stride);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) {
@@ -934,7 +954,10 @@ int keep_job(pt_ctx *c, const pt_config *cfg, const Job &j, int rc, hipStream_t 
         accum_drop(c);  // (their state is unknown)
         return PT_ERR_HIP;
     }
-    for (uint32_t i = j.part_lo; i < j.part_hi; ++i) c->acc_cnt[i] = done;
+    for (uint32_t i = j.part_lo; i < j.part_hi; ++i) {
+        if (to_a) c->acc_na[i] += done - j.s_first;
+        c->acc_cnt[i] = done;
+    }
     return rc;
 }
 
@@ -986,10 +1009,12 @@ int run_frame_call(pt_ctx *c, const pt_config *cfg, const FrameParams &F, const 
     int rc = PT_OK;
     bool started = false;
     for (const Job &j : jobs) {
-        if (j.s_first >= cfg->spp) continue;  // nothing left to trace here
+        pt_config jcfg = *cfg;  // the job's own last sample (a noise-tracked call cuts a part's samples into two jobs)
+        if (j.s_end) jcfg.spp = j.s_end;
+        if (j.s_first >= jcfg.spp) continue;  // nothing left to trace here
         // a job boundary is a progress point of its own (a part of one or two passes makes no callback from inside); a cancel
         // raised there is seen by the job's first pass, which leaves it and the parts behind it black
-        if (cb && started) progress(c, cfg, cb, user, j.base);
+        if (cb && started) progress(c, cfg, cb, user, j.boundary >= 0.0f ? j.boundary : j.base);
         started = true;
         FrameParams Fj = F;
         Fj.k_begin = j.k0;
@@ -1001,8 +1026,8 @@ int run_frame_call(pt_ctx *c, const pt_config *cfg, const FrameParams &F, const 
         relay.scale = j.scale;
         pt_stats js{};
         rc = (cfg->backend == PT_BACKEND_WAVEFRONT ? render_wavefront : render_mega)(
-            c, form, cfg, Fj, st, cancel, cb ? &Relay::fn : nullptr, &relay, js, j.s_first, j.held.p ? &j.held : nullptr);
-        if (rc == PT_OK || rc == PT_CANCELLED) rc = accumulate ? keep_job(c, cfg, j, rc, st) : resolve_job(c, cfg, j, rc, st);
+            c, form, &jcfg, Fj, st, cancel, cb ? &Relay::fn : nullptr, &relay, js, j.s_first, j.held.p ? &j.held : nullptr);
+        if (rc == PT_OK || rc == PT_CANCELLED) rc = accumulate ? keep_job(c, &jcfg, j, rc, st) : resolve_job(c, &jcfg, j, rc, st);
         if (stats) add_stats(stats, js);
         if (rc != PT_OK) break;
     }
@@ -1027,7 +1052,8 @@ int frame_prologue(pt_ctx *c, const pt_config *cfg, uint32_t *ib, uint32_t *ie) 
 
 // ---- checkpoint file (pt_ctx_accum_save / _load, ptrace.h): little-endian, the byte order of every target of this library
 constexpr char kCkptMagic[8] = {'P', 'T', 'A', 'C', 'C', 'U', 'M', '1'};
-constexpr uint32_t kCkptVersion = 1u;
+constexpr uint32_t kCkptVersion = 1u;         // the held sums
+constexpr uint32_t kCkptVersionTracked = 2u;  // ... and half A of a noise-tracked frame: its counts after the counts, its planes after the sums
 constexpr size_t kCkptHead = 8 + 4 + 7 * 4 + 8 + 8 + 3 * 4;  // magic .. number of parts: 68 bytes
 
 template <class T>
@@ -1150,6 +1176,8 @@ void pt_ctx_destroy(pt_ctx *c) {
     c->blk_rays.release();
     c->acc.release();
     c->acc_held.release();
+    c->acc_a.release();
+    c->noise_cnt.release();
     c->dn_u[0].release();
     c->dn_u[1].release();
     c->dn_guide.release();
@@ -1522,17 +1550,41 @@ int pt_ctx_accumulate(pt_ctx *c, const pt_config *cfg, void *d_out_rgb, void *hi
         c->acc_total = total;
         c->acc_part_px = part_px;
         c->acc_cnt.assign(n_parts, 0u);
+        if (c->acc_track) {  // half A starts empty too
+            if ((rc = c->acc_a.ensure(3 * (size_t)total))) {
+                accum_drop(c);
+                return rc;
+            }
+            HIP_TRY(hipMemsetAsync(c->acc_a.p, 0, 3 * (size_t)total * sizeof(unsigned long long), st));
+            c->acc_na.assign(n_parts, 0u);
+            c->acc_tracked = true;
+        }
         c->acc_on = true;
     }
     // What to render: each part from its own count; the megakernel, which renders a call at once, takes the whole call in one go
-    // when every part holds the same count.  Progress by pixels.
+    // when every part holds the same count.  Progress by pixels.  A noise-tracked frame cuts the samples [cnt, spp) of a part
+    // into two jobs at m = cnt + 4 * ceil((spp - cnt) / 8) - the first rounded up to whole groups of the four sub-pixels - so
+    // that both halves of the estimate get samples from every call (keep_job deals them).
     std::vector<Job> jobs;
     auto job = [&](uint32_t k0, uint32_t n, uint32_t part_lo, uint32_t part_hi) {
-        jobs.push_back({k0, n, c->acc_cnt[part_lo], HeldSums{c->acc_held.p + k0, total}, (float)k0 / (float)total,
-                        (float)n / (float)total, part_lo, part_hi});
+        const uint32_t cnt = c->acc_cnt[part_lo];
+        const float base = (float)k0 / (float)total, scale = (float)n / (float)total;
+        const HeldSums held{c->acc_held.p + k0, total};
+        if (c->acc_tracked && cnt < cfg->spp) {
+            const uint64_t m64 = (uint64_t)cnt + 4ull * (((uint64_t)(cfg->spp - cnt) + 7ull) / 8ull);
+            const uint32_t m = m64 < cfg->spp ? (uint32_t)m64 : cfg->spp;
+            // (a renderer reports the samples issued over its job's last sample: the first job's fractions are scaled to the call's)
+            const float f1 = (float)m / (float)cfg->spp;
+            jobs.push_back({k0, n, cnt, held, base, scale * f1, part_lo, part_hi, m});
+            if (m < cfg->spp) jobs.push_back({k0, n, m, held, base, scale, part_lo, part_hi, cfg->spp, base + scale * f1});
+            return;
+        }
+        jobs.push_back({k0, n, cnt, held, base, scale, part_lo, part_hi});
     };
     bool even = true;
     for (uint32_t v : c->acc_cnt) even = even && v == c->acc_cnt[0];
+    if (c->acc_tracked)
+        for (uint32_t v : c->acc_na) even = even && v == c->acc_na[0];
     if (cfg->backend == PT_BACKEND_MEGAKERNEL && even)
         job(0u, total, 0u, n_parts);
     else
@@ -1582,9 +1634,10 @@ int pt_ctx_accum_save(pt_ctx *c, const char *path) {
     HIP_TRY(hipSetDevice(c->device));
     const size_t n_sums = 3 * (size_t)c->acc_total;
     std::vector<uint8_t> b;
-    b.reserve(kCkptHead + 4 * c->acc_cnt.size() + 8 * n_sums + 8);
+    const size_t halves = c->acc_tracked ? 2u : 1u;
+    b.reserve(kCkptHead + halves * (4 * c->acc_cnt.size() + 8 * n_sums) + 8);
     b.insert(b.end(), kCkptMagic, kCkptMagic + 8);
-    put<uint32_t>(b, kCkptVersion);
+    put<uint32_t>(b, c->acc_tracked ? kCkptVersionTracked : kCkptVersion);
     const AccumKey &k = c->acc_key;
     for (uint32_t v : {k.width, k.height, k.idx_begin, k.idx_end, k.chunk_pixels, k.chunk_first, k.chunk_step}) put<uint32_t>(b, v);
     put<uint64_t>(b, k.seed);
@@ -1593,9 +1646,12 @@ int pt_ctx_accum_save(pt_ctx *c, const char *path) {
     put<uint32_t>(b, c->acc_part_px);
     put<uint32_t>(b, (uint32_t)c->acc_cnt.size());
     for (uint32_t v : c->acc_cnt) put<uint32_t>(b, v);
+    if (c->acc_tracked)
+        for (uint32_t v : c->acc_na) put<uint32_t>(b, v);
     const size_t at = b.size();
-    b.resize(at + 8 * n_sums);
+    b.resize(at + halves * 8 * n_sums);
     HIP_TRY(hipMemcpy(b.data() + at, c->acc_held.p, 8 * n_sums, hipMemcpyDeviceToHost));
+    if (c->acc_tracked) HIP_TRY(hipMemcpy(b.data() + at + 8 * n_sums, c->acc_a.p, 8 * n_sums, hipMemcpyDeviceToHost));
     put<uint64_t>(b, pt_siphash(1, 3, 0, 0, b.data(), b.size()));
     // written next to the target and renamed over it: a process that dies while saving leaves the last checkpoint whole
     const std::string tmp = std::string(path) + ".tmp";
@@ -1658,7 +1714,9 @@ int pt_ctx_accum_load(pt_ctx *c, const char *path) {
     const uint8_t *r = b.data();
     if (memcmp(r, kCkptMagic, 8) != 0) return bad("wrong magic");
     r += 8;
-    if (get<uint32_t>(r) != kCkptVersion) return bad("unknown format version");
+    const uint32_t version = get<uint32_t>(r);
+    if (version != kCkptVersion && version != kCkptVersionTracked) return bad("unknown format version");
+    const uint64_t halves = version == kCkptVersionTracked ? 2u : 1u;
     AccumKey k{};
     k.width = get<uint32_t>(r);
     k.height = get<uint32_t>(r);
@@ -1686,7 +1744,7 @@ int pt_ctx_accum_load(pt_ctx *c, const char *path) {
     const uint32_t want_total = owned_pixels(&kc, ib, ie);
     if (total != want_total || want_total == 0u || part_px != part_pixels(total, true) || n_parts != (total + part_px - 1u) / part_px)
         return bad("sizes that do not fit each other");
-    const uint64_t want_size = kCkptHead + 4ull * n_parts + 24ull * total + 8ull;
+    const uint64_t want_size = kCkptHead + halves * (4ull * n_parts + 24ull * total) + 8ull;
     if ((uint64_t)fsize != want_size) return bad((uint64_t)fsize < want_size ? "truncated" : "trailing bytes");
     b.resize((size_t)want_size);
     if (fread(b.data() + kCkptHead, 1, (size_t)want_size - kCkptHead, f) != (size_t)want_size - kCkptHead) {
@@ -1700,6 +1758,15 @@ int pt_ctx_accum_load(pt_ctx *c, const char *path) {
     memcpy(cnt.data(), b.data() + kCkptHead, 4 * (size_t)n_parts);
     for (uint32_t v : cnt)
         if (v > (1u << 24)) return bad("a sample count above 2^24");
+    // a file of a noise-tracked frame brings half A; a plain one loaded into a tracking context starts it empty (all held
+    // samples then count as half B)
+    const bool tracked = halves == 2u || c->acc_track;
+    std::vector<uint32_t> na(tracked ? n_parts : 0u, 0u);
+    if (halves == 2u) {
+        memcpy(na.data(), b.data() + kCkptHead + 4 * (size_t)n_parts, 4 * (size_t)n_parts);
+        for (uint32_t i = 0; i < n_parts; ++i)
+            if (na[i] > cnt[i]) return bad("half A holds more samples than the part");
+    }
     if (fp != c->scene_fp) {
         set_error(std::string(path) + " was rendered from another scene than the one set on this context");
         return PT_ERR_INVALID;
@@ -1707,8 +1774,18 @@ int pt_ctx_accum_load(pt_ctx *c, const char *path) {
     HIP_TRY(hipSetDevice(c->device));
     accum_drop(c);
     int rc = c->acc_held.ensure(3 * (size_t)total);
-    if (rc) return rc;
-    const hipError_t e = hipMemcpy(c->acc_held.p, b.data() + kCkptHead + 4 * (size_t)n_parts, 24 * (size_t)total, hipMemcpyHostToDevice);
+    if (!rc && tracked) rc = c->acc_a.ensure(3 * (size_t)total);
+    if (rc) {
+        accum_drop(c);
+        return rc;
+    }
+    const uint8_t *sums = b.data() + kCkptHead + halves * 4 * (size_t)n_parts;
+    hipError_t e = hipMemcpy(c->acc_held.p, sums, 24 * (size_t)total, hipMemcpyHostToDevice);
+    if (e == hipSuccess && halves == 2u) e = hipMemcpy(c->acc_a.p, sums + 24 * (size_t)total, 24 * (size_t)total, hipMemcpyHostToDevice);
+    if (e == hipSuccess && tracked && halves == 1u) {
+        e = hipMemsetAsync(c->acc_a.p, 0, 24 * (size_t)total, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    }
     if (e != hipSuccess) {
         set_error(std::string("uploading the checkpoint: ") + hipGetErrorString(e));
         accum_drop(c);
@@ -1718,8 +1795,207 @@ int pt_ctx_accum_load(pt_ctx *c, const char *path) {
     c->acc_total = total;
     c->acc_part_px = part_px;
     c->acc_cnt = cnt;
+    c->acc_na = na;
+    c->acc_tracked = tracked;
     c->acc_on = true;
     return PT_OK;
+}
+
+int pt_ctx_accum_track_noise(pt_ctx *c, int enabled) {
+    if (!c) {
+        set_error("ctx is NULL");
+        return PT_ERR_INVALID;
+    }
+    if (c->acc_on) {
+        set_error("an accumulator is held: tracking applies to frames started after the call - call pt_ctx_accum_reset first");
+        return PT_ERR_INVALID;
+    }
+    c->acc_track = enabled != 0;
+    return PT_OK;
+}
+
+// pt_ctx_accum_noise without the argument checks.  kNoiseNone: the frame is held and tracked but no part has samples in both
+// halves yet (*out then holds the counts, pixels 0 and mean_error +inf).
+constexpr int kNoiseNone = 1;
+static int accum_noise(pt_ctx *c, float *d_error, pt_noise_stats *out, hipStream_t st) {
+    memset(out, 0, sizeof *out);
+    const uint32_t n_parts = (uint32_t)c->acc_cnt.size();
+    out->spp_min = out->spp_a_min = out->spp_b_min = 0xffffffffu;
+    bool any = false;
+    for (uint32_t i = 0; i < n_parts; ++i) {
+        const uint32_t cnt = c->acc_cnt[i], na = c->acc_na[i], nb = cnt - na;
+        out->spp_min = cnt < out->spp_min ? cnt : out->spp_min;
+        out->spp_max = cnt > out->spp_max ? cnt : out->spp_max;
+        out->spp_a_min = na < out->spp_a_min ? na : out->spp_a_min;
+        out->spp_b_min = nb < out->spp_b_min ? nb : out->spp_b_min;
+        any = any || (na != 0u && nb != 0u);
+    }
+    if (n_parts == 0u) out->spp_min = out->spp_a_min = out->spp_b_min = 0u;
+    if (!any) {
+        out->mean_error = (double)__builtin_inff();
+        return kNoiseNone;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = c->noise_cnt.ensure(1);
+    if (rc) return rc;
+    HIP_TRY(hipMemsetAsync(c->noise_cnt.p, 0, sizeof(NoiseCounters), st));
+    for (uint32_t i = 0; i < n_parts; ++i) {
+        const uint32_t k0 = i * c->acc_part_px, n = (c->acc_total - k0) < c->acc_part_px ? (c->acc_total - k0) : c->acc_part_px;
+        const uint32_t na = c->acc_na[i], nb = c->acc_cnt[i] - na;
+        if (na != 0u && nb != 0u) {
+            const float fa = (float)na, fb = (float)nb;
+            const float w = __builtin_sqrtf(fa * fb) / (fa + fb);  // binary32, as the header states it
+            launch_noise(st, c->acc_held.p + k0, c->acc_a.p + k0, c->acc_total, n, na, nb, w, d_error ? d_error + k0 : nullptr,
+                         c->noise_cnt.p);
+            out->pixels += n;
+        } else if (d_error) {
+            launch_noise_none(st, d_error + k0, n);
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    NoiseCounters h;
+    HIP_TRY(hipMemcpyAsync(&h, c->noise_cnt.p, sizeof h, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    memcpy(out->histogram, h.hist, sizeof h.hist);
+    out->mean_error = (double)h.sum * (1.0 / 268435456.0) / (double)out->pixels;
+    return PT_OK;
+}
+
+// is cfg's frame the held one (PT_OK), and is it noise-tracked?
+static int held_tracked_frame(const pt_ctx *c, const pt_config *cfg) {
+    uint32_t ib = 0, ie = 0;
+    const int rc = check_cfg(cfg, &ib, &ie);
+    if (rc) return rc;
+    if (!c->acc_on || !(c->acc_key == accum_key(cfg, ib, ie)) || c->acc_cnt.empty()) {
+        set_error("cfg does not name the frame this context holds");
+        return PT_ERR_INVALID;
+    }
+    if (!c->acc_tracked) {
+        set_error("the held frame is not noise-tracked (pt_ctx_accum_track_noise before the frame is started)");
+        return PT_ERR_INVALID;
+    }
+    return PT_OK;
+}
+
+int pt_ctx_accum_noise(pt_ctx *c, const pt_config *cfg, float *d_error, pt_noise_stats *out, void *hip_stream) {
+    if (!c || !cfg || !out) {
+        set_error("NULL argument");
+        return PT_ERR_INVALID;
+    }
+    int rc = held_tracked_frame(c, cfg);
+    if (rc) return rc;
+    rc = accum_noise(c, d_error, out, hip_stream ? (hipStream_t)hip_stream : c->stream);
+    if (rc == kNoiseNone) {
+        set_error("no part of the frame has samples in both halves yet: accumulate more");
+        return PT_ERR_INVALID;
+    }
+    return rc;
+}
+
+// the upper edge of histogram bin `b` of pt_noise_stats (ptrace.h): the float whose bits are (461 + b) << 21; +inf for the last
+static float noise_bin_upper(uint32_t b) {
+    if (b >= kNoiseBins - 1u) return __builtin_inff();
+    const uint32_t bits = (461u + b) << 21;
+    float v;
+    memcpy(&v, &bits, 4);
+    return v;
+}
+
+int pt_ctx_accumulate_until(pt_ctx *c, const pt_config *cfg, const pt_noise_target *tgt, void *d_out_rgb, void *hip_stream,
+                            const volatile uint8_t *cancel, pt_progress_fn cb, void *user, pt_stats *stats, pt_noise_stats *noise) {
+    if (!cfg || !tgt || !d_out_rgb || !noise) {
+        set_error("NULL argument");
+        return PT_ERR_INVALID;
+    }
+    const bool use_mean = tgt->mean_error != 0.0f, use_q = tgt->quantile != 0.0f;
+    auto fin_nonneg = [](float v) { return v >= 0.0f && v < __builtin_inff(); };  // (false for a NaN)
+    if (!fin_nonneg(tgt->mean_error) || !fin_nonneg(tgt->quantile) || !fin_nonneg(tgt->quantile_error)) {
+        set_error("noise target: mean_error, quantile and quantile_error must be finite and not negative");
+        return PT_ERR_INVALID;
+    }
+    if (!use_mean && !use_q) {
+        set_error("noise target: neither mean_error nor quantile is in use");
+        return PT_ERR_INVALID;
+    }
+    if (use_q && !(tgt->quantile < 1.0f)) {
+        set_error("noise target: quantile must lie in (0, 1)");
+        return PT_ERR_INVALID;
+    }
+    if (!c) {
+        set_error("ctx is NULL");
+        return PT_ERR_INVALID;
+    }
+    uint32_t ib = 0, ie = 0;
+    int rc = check_cfg(cfg, &ib, &ie);
+    if (rc) return rc;
+    const bool held = c->acc_on && c->acc_key == accum_key(cfg, ib, ie);
+    if (!(held ? c->acc_tracked : c->acc_track)) {
+        set_error("pt_ctx_accumulate_until needs noise tracking (pt_ctx_accum_track_noise before the frame is started)");
+        return PT_ERR_INVALID;
+    }
+    const double t0 = now_ms();
+    if (stats) memset(stats, 0, sizeof *stats);
+    memset(noise, 0, sizeof *noise);
+    uint32_t have = 0;
+    if (held)
+        for (uint32_t v : c->acc_cnt) have = v > have ? v : have;
+    if (cfg->spp < have) {
+        set_error("cfg->spp, the cap, is below the samples per pixel held for this frame");
+        return PT_ERR_INVALID;
+    }
+    const uint32_t cap = cfg->spp, min_spp = tgt->min_spp ? tgt->min_spp : 16u;
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    struct Relay {  // a step's fractions as fractions of the cap's samples; the end of the call reports 1
+        pt_progress_fn cb;
+        void *user;
+        float base, scale;
+        static void fn(void *self, float f) {
+            Relay *r = (Relay *)self;
+            if (f < 1.0f) r->cb(r->user, r->base + r->scale * f);
+        }
+    } relay{cb, user, 0.0f, 0.0f};
+    uint32_t t = have > min_spp ? have : min_spp;
+    for (;;) {
+        t = t < cap ? t : cap;
+        pt_config step = *cfg;
+        step.spp = t;
+        relay.base = 0.0f;  // (pt_ctx_accumulate's fractions count the samples held as done)
+        relay.scale = (float)t / (float)cap;
+        pt_stats ss{};
+        rc = pt_ctx_accumulate(c, &step, d_out_rgb, hip_stream, cancel, cb ? &Relay::fn : nullptr, &relay, &ss);
+        if (stats) add_stats(stats, ss);
+        if (rc != PT_OK && rc != PT_CANCELLED) break;
+        const int rc_frame = rc;
+        const int rn = accum_noise(c, nullptr, noise, st);
+        if (rn != PT_OK && rn != kNoiseNone) {
+            rc = rn;
+            break;
+        }
+        if (rc_frame == PT_CANCELLED) {
+            set_error("cancelled");
+            break;
+        }
+        bool met = rn == PT_OK;
+        if (met && use_mean) met = noise->mean_error <= (double)tgt->mean_error;
+        if (met && use_q) {
+            // the first bin at which the cumulative count reaches ceil(quantile * pixels)
+            const double need_d = (double)tgt->quantile * (double)noise->pixels;
+            uint64_t need = (uint64_t)need_d;
+            if ((double)need < need_d) ++need;
+            need = need ? need : 1u;
+            uint64_t cum = 0;
+            uint32_t b = 0;
+            for (; b < kNoiseBins; ++b)
+                if ((cum += noise->histogram[b]) >= need) break;
+            met = noise_bin_upper(b) <= tgt->quantile_error;
+        }
+        if (met || t >= cap) break;
+        have = t;
+        t = t > cap / 2u ? cap : t * 2u;
+    }
+    if (cb && rc == PT_OK) cb(user, 1.0f);
+    if (stats) stats->ms_total = now_ms() - t0;
+    return rc;
 }
 
 int pt_ctx_radiance(pt_ctx *c, const float o[3], const float d[3], uint32_t depth, uint32_t n_samples, uint64_t seed,

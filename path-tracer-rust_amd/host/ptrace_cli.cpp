@@ -21,7 +21,7 @@ static void usage() {
     fprintf(stderr,
             "usage: ptrace <samplesPerPixel> <y-resolution> <scene id|index> [--width W] [--backend wavefront|megakernel]\n"
             "              [--seed S] [--gpus N] [--root DIR] [--out DIR] [--no-ppm] [--checkpoint FILE] [--aov N]\n"
-            "              [--denoise [N]]\n"
+            "              [--denoise [N]] [--noise-target X [--noise-map FILE.pfm]]\n"
             "  --checkpoint FILE: continue from the samples FILE holds (if it exists), render up to <samplesPerPixel> in all and\n"
             "                     save them to FILE; one GPU only; the seed defaults to 0 instead of the clock, so that the same\n"
             "                     command continues the same frame\n"
@@ -30,7 +30,11 @@ static void usage() {
             "           object index as a float, -1 on a miss)\n"
             "  --denoise [N]: after the frame, denoise it on the GPU (pt_ctx_denoise, default parameters) with first-hit guides over\n"
             "           its first N samples (default 16), written next to the image as ...-denoised.ppm and ...-denoised.pfm; one\n"
-            "           GPU only\n");
+            "           GPU only\n"
+            "  --noise-target X: <samplesPerPixel> becomes a cap: render until the frame's mean estimated error (pt_ctx_accum_noise)\n"
+            "           is at most X, doubling the samples from 16; prints the samples reached and the error; one GPU only;\n"
+            "           with --checkpoint the file keeps the half buffers too (format version 2)\n"
+            "  --noise-map FILE.pfm: with --noise-target, the per-pixel estimate e(p) of the final frame as a 1-channel PFM\n");
 }
 
 static std::vector<std::string> scene_ids(const std::string &root) {
@@ -60,10 +64,37 @@ struct DeviceFrame {
     void *d_out = nullptr;
 };
 
-// --checkpoint / --denoise: one context on one GPU.  With FILE the frame is accumulated from what FILE holds up to cfg->spp and
-// FILE is saved again; without, it is rendered.  `keep` takes the context and the device frame instead of their being freed.
+// --noise-target: render to a mean error of at most `target` (0: not asked for), cfg->spp at most; *spp_reached = the samples
+// per pixel the frame ended with
+struct NoiseRun {
+    float target = 0.0f;
+    std::string map;  // --noise-map
+    uint32_t spp_reached = 0;
+};
+
+// --noise-map: e(p) of the held frame through pt_write_pfm, one channel
+static int write_noise_map(int dev, pt_ctx *ctx, const pt_config *cfg, const std::string &path) {
+    const size_t npix = (size_t)cfg->width * cfg->height;
+    std::vector<float> err(npix);
+    void *d_err = nullptr;
+    pt_noise_stats ns;
+    int rc = pt_device_malloc(dev, npix * sizeof(float), &d_err);
+    if (!rc) rc = pt_ctx_accum_noise(ctx, cfg, (float *)d_err, &ns, nullptr);
+    if (!rc) rc = pt_device_download(dev, err.data(), d_err, npix * sizeof(float));
+    if (d_err) pt_device_free(dev, d_err);
+    if (!rc) rc = pt_write_pfm(path.c_str(), err.data(), cfg->width, cfg->height, 1);
+    if (rc)
+        fprintf(stderr, "cannot write the noise map %s: %s\n", path.c_str(), pt_last_error());
+    else
+        printf("wrote %s\n", path.c_str());
+    return rc;
+}
+
+// --checkpoint / --denoise / --noise-target: one context on one GPU.  With FILE the frame is accumulated from what FILE holds up
+// to cfg->spp and FILE is saved again; without, it is rendered.  `keep` takes the context and the device frame instead of their
+// being freed.
 static int render_on_context(const pt_config *cfg, pt_scene *sc, const std::string &file, std::vector<float> &img, pt_stats *st,
-                             DeviceFrame *keep) {
+                             DeviceFrame *keep, NoiseRun *noise) {
     int dev = 0;
     if (const char *e = getenv("PT_DEVICE")) dev = atoi(e);
     uint32_t n_objs = 0, n_tris = 0;
@@ -72,6 +103,7 @@ static int render_on_context(const pt_config *cfg, pt_scene *sc, const std::stri
     pt_ctx *ctx = nullptr;
     int rc = pt_ctx_create(dev, &ctx);
     if (!rc) rc = pt_ctx_set_scene(ctx, pt_scene_camera(sc), objs, n_objs, tris, n_tris);
+    if (!rc && noise->target > 0.0f) rc = pt_ctx_accum_track_noise(ctx, 1);
     if (!rc && !file.empty() && access(file.c_str(), F_OK) == 0) {
         rc = pt_ctx_accum_load(ctx, file.c_str());
         if (rc) {
@@ -102,9 +134,24 @@ static int render_on_context(const pt_config *cfg, pt_scene *sc, const std::stri
     void *d_out = nullptr;
     const size_t bytes = img.size() * sizeof(float);
     if (!rc) rc = pt_device_malloc(dev, bytes, &d_out);
-    if (!rc)
+    noise->spp_reached = cfg->spp;
+    if (!rc && noise->target > 0.0f) {
+        pt_noise_target tgt;
+        memset(&tgt, 0, sizeof tgt);
+        tgt.mean_error = noise->target;
+        pt_noise_stats ns;
+        rc = pt_ctx_accumulate_until(ctx, cfg, &tgt, d_out, nullptr, nullptr, progress, nullptr, st, &ns);
+        if (!rc) {
+            noise->spp_reached = ns.spp_max;
+            printf("\nNoise target %g: reached %u samples per pixel, mean error %.6g%s\n", (double)noise->target, ns.spp_max,
+                   ns.mean_error, ns.mean_error <= (double)noise->target ? "" : " (the cap: target not met)");
+            fflush(stdout);
+            if (!noise->map.empty() && write_noise_map(dev, ctx, cfg, noise->map)) rc = kCliExit;
+        }
+    } else if (!rc) {
         rc = file.empty() ? pt_ctx_render(ctx, cfg, d_out, nullptr, nullptr, progress, nullptr, st)
                           : pt_ctx_accumulate(ctx, cfg, d_out, nullptr, nullptr, progress, nullptr, st);
+    }
     if (!rc) rc = pt_device_download(dev, img.data(), d_out, bytes);
     if (!rc && !file.empty()) {
         rc = pt_ctx_accum_save(ctx, file.c_str());
@@ -217,6 +264,7 @@ int main(int argc, char **argv) {
     std::string checkpoint;
     bool write_ppm = true;
     uint32_t gpus = 1, aov_spp = 0, denoise_spp = 0;
+    NoiseRun noise;
     for (int i = 4; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&]() -> const char * { return i + 1 < argc ? argv[++i] : ""; };
@@ -240,6 +288,20 @@ int main(int argc, char **argv) {
         else if (a == "--aov") {
             aov_spp = (uint32_t)strtoul(next(), nullptr, 10);
             if (!aov_spp) {
+                usage();
+                return 1;
+            }
+        }
+        else if (a == "--noise-target") {
+            noise.target = strtof(next(), nullptr);
+            if (!(noise.target > 0.0f)) {
+                usage();
+                return 1;
+            }
+        }
+        else if (a == "--noise-map") {
+            noise.map = next();
+            if (noise.map.empty()) {
                 usage();
                 return 1;
             }
@@ -270,6 +332,14 @@ int main(int argc, char **argv) {
     }
     if (denoise_spp && gpus > 1) {
         fprintf(stderr, "--denoise works with one GPU only (--gpus %u)\n", gpus);
+        return 1;
+    }
+    if (noise.target > 0.0f && gpus > 1) {
+        fprintf(stderr, "--noise-target works with one GPU only (--gpus %u)\n", gpus);
+        return 1;
+    }
+    if (!noise.map.empty() && !(noise.target > 0.0f)) {
+        fprintf(stderr, "--noise-map needs --noise-target\n");
         return 1;
     }
     if (!checkpoint.empty() && !seed_given) seed = 0;
@@ -318,11 +388,13 @@ int main(int argc, char **argv) {
     std::vector<float> img((size_t)width * res_y * 3, 0.0f);
     pt_stats st;
     DeviceFrame df;
-    if (checkpoint.empty() && !denoise_spp)
+    if (checkpoint.empty() && !denoise_spp && !(noise.target > 0.0f))
         rc = pt_render_multi(&cfg, gpus ? gpus : 1, pt_scene_camera(sc), objs, n_objs, tris, n_tris, img.data(), nullptr,
                              progress, nullptr, &st);
     else
-        rc = render_on_context(&cfg, sc, checkpoint, img, &st, denoise_spp ? &df : nullptr);
+        rc = render_on_context(&cfg, sc, checkpoint, img, &st, denoise_spp ? &df : nullptr, &noise);
+    const uint32_t spp_out = noise.target > 0.0f && !rc ? noise.spp_reached : spp;  // the samples the frame holds
+    cfg.spp = spp_out;
     auto release = [&]() {
         if (df.d_out) pt_device_free(df.dev, df.d_out);
         if (df.ctx) pt_ctx_destroy(df.ctx);
@@ -346,12 +418,12 @@ int main(int argc, char **argv) {
     char stamp[64];
     time_t now = time(nullptr);
     strftime(stamp, sizeof stamp, "%Y-%m-%d_%H:%M:%S", localtime(&now));
-    const std::string stem = out_dir + "/" + stamp + "-scene-" + pt_scene_id(sc) + "-spp" + std::to_string(spp) + "-res" +
+    const std::string stem = out_dir + "/" + stamp + "-scene-" + pt_scene_id(sc) + "-spp" + std::to_string(spp_out) + "-res" +
                              std::to_string(res_y) + "-";
     if (write_ppm || aov_spp || denoise_spp) mkdir(out_dir.c_str(), 0755);  // create_dir_all("out"), mod.rs:1032
     if (write_ppm) {
         const std::string path = stem + ".ppm";
-        rc = pt_write_ppm(path.c_str(), img.data(), width, res_y, spp, pt_scene_id(sc), (uint64_t)(st.ms_total / 1000.0));
+        rc = pt_write_ppm(path.c_str(), img.data(), width, res_y, spp_out, pt_scene_id(sc), (uint64_t)(st.ms_total / 1000.0));
         if (rc) {
             fprintf(stderr, "cannot write %s: %s\n", path.c_str(), pt_last_error());
             release();
