@@ -37,10 +37,16 @@ void set_error(const std::string &m) { g_last_error = m; }
 // reports PT_ERR_HIP when even the smallest does not fit)
 constexpr int PT_ERR_NOMEM_INTERNAL = -1000;
 
+// A device allocation and its owner: freed with it (on the device that is current then - pt_ctx_destroy makes it the context's)
 template <class T>
 struct DevBuf {
     T *p = nullptr;
     size_t n = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : p(o.p), n(o.n) { o.p = nullptr, o.n = 0; }
+    ~DevBuf() { release(); }
     size_t bytes() const { return p ? n * sizeof(T) : 0; }
     int ensure(size_t count, bool tell_oom = false) {
         if (count <= n && p) return PT_OK;
@@ -64,20 +70,50 @@ struct DevBuf {
     }
 };
 
-// The frame a pt_ctx_accumulate call renders: what decides the image besides the samples (the scene is the context's).
-// chunk_* as check_cfg reads them: all zero for a whole band.
-struct AccumKey {
-    uint32_t width, height, idx_begin, idx_end, chunk_pixels, chunk_first, chunk_step;
-    uint64_t seed;
-    bool operator==(const AccumKey &o) const {
-        return width == o.width && height == o.height && idx_begin == o.idx_begin && idx_end == o.idx_end &&
-               chunk_pixels == o.chunk_pixels && chunk_first == o.chunk_first && chunk_step == o.chunk_step && seed == o.seed;
+// The frame pt_ctx_accumulate keeps between calls, and its one owner: host::FrameCounts plus the device planes - the sums, [3]
+// planes of `total` u64, and for a noise-tracked frame the sums of half A of its samples in `a`, laid out as `sums` (half B: sums
+// - a).  start() is the only place that gives the counts any entries, after the planes are allocated and filled: a frame is held
+// whole or not at all.
+struct HeldFrame : host::FrameCounts {
+    DevBuf<unsigned long long> sums, a;
+
+    void drop() {
+        static_cast<host::FrameCounts &>(*this) = {};
+        sums.release();
+        a.release();
+    }
+    // Hold the frame f in place of whatever was held.  The planes come from the host bytes from_sums / from_a (a checkpoint's:
+    // they are on the device when this returns) or start at zero on `st` (NULL).  On any failure nothing is held.
+    int start(host::FrameCounts f, const uint8_t *from_sums, const uint8_t *from_a, hipStream_t st) {
+        drop();
+        const size_t bytes = 3 * (size_t)f.total * sizeof(unsigned long long);
+        int rc = sums.ensure(3 * (size_t)f.total);
+        if (!rc && f.tracked()) rc = a.ensure(3 * (size_t)f.total);
+        if (rc) {
+            drop();
+            return rc;
+        }
+        auto fill = [&](unsigned long long *d, const uint8_t *from) {
+            return from ? hipMemcpy(d, from, bytes, hipMemcpyHostToDevice) : hipMemsetAsync(d, 0, bytes, st);
+        };
+        hipError_t e = fill(sums.p, from_sums);
+        if (e == hipSuccess && f.tracked()) e = fill(a.p, from_a);
+        if (e == hipSuccess && from_sums) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) {
+            set_error(std::string(from_sums ? "uploading the checkpoint: " : "clearing the held sums: ") + hipGetErrorString(e));
+            drop();
+            return PT_ERR_HIP;
+        }
+        static_cast<host::FrameCounts &>(*this) = std::move(f);
+        return PT_OK;
     }
 };
 
 }  // namespace pt
 
 using namespace pt;
+using host::check_cfg;
+using host::owned_pixels;
 
 // Tuning switches (A/B runs, profiling).  Read from the environment ONCE, when a context is created, and kept with the
 // context: a frame never sees two different answers.  PT_DEBUG (ablation switches that change the image) exists only in
@@ -221,21 +257,12 @@ struct pt_ctx {
     // forgets them.
     double pass_rate = 0.0, round_rate = 0.0;
     const char *pass_rate_kernel = nullptr;  // the kernel pass_rate was measured on (flags choose other kernels)
-    // pt_ctx_accumulate: the sums of one frame (acc_key) kept between calls, [3] planes of acc_total u64 in the call's pixel
-    // order, and the samples per pixel each part holds (parts of acc_part_px pixels, cut as pt_ctx_render cuts a call).
-    // scene_fp: the checkpoint fingerprint of the scene pt_ctx_set_scene got, which drops the held sums.
-    bool acc_on = false;
-    AccumKey acc_key{};
-    uint32_t acc_total = 0, acc_part_px = 0;
-    std::vector<uint32_t> acc_cnt;
-    DevBuf<unsigned long long> acc_held;
+    // pt_ctx_accumulate: the frame kept between calls.  scene_fp: the checkpoint fingerprint of the scene pt_ctx_set_scene got,
+    // which drops the held frame.  acc_track (pt_ctx_accum_track_noise): the frames this context starts are noise-tracked.
+    // noise_cnt: pt_ctx_accum_noise's counters.
+    HeldFrame held;
     uint64_t scene_fp = 0;
-    // Noise tracking (pt_ctx_accum_track_noise).  acc_track: the frames this context starts are tracked; acc_tracked: the held
-    // frame is - acc_a then holds the sums of half A of its samples, laid out as acc_held, and acc_na how many samples per
-    // pixel of each part went to it (half B: acc_held - acc_a, acc_cnt - acc_na).  noise_cnt: pt_ctx_accum_noise's counters.
-    bool acc_track = false, acc_tracked = false;
-    std::vector<uint32_t> acc_na;
-    DevBuf<unsigned long long> acc_a;
+    bool acc_track = false;
     DevBuf<NoiseCounters> noise_cnt;
     // pt_ctx_denoise's scratch, kept between calls: the two colour planes and the packed guides, one float4 per pixel each
     DevBuf<float4> dn_u[2], dn_guide;
@@ -247,56 +274,6 @@ int device_count_quiet() {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
     return n;
-}
-
-int check_cfg(const pt_config *cfg, uint32_t *idx_begin, uint32_t *idx_end) {
-    if (!cfg) {
-        set_error("cfg is NULL");
-        return PT_ERR_INVALID;
-    }
-    if (cfg->width == 0 || cfg->height == 0 || cfg->spp == 0) {
-        set_error("width, height and spp must be positive");
-        return PT_ERR_INVALID;
-    }
-    const uint64_t npix = (uint64_t)cfg->width * cfg->height;
-    if (npix > 0x7fffffffull) {
-        set_error("width*height exceeds 2^31-1");
-        return PT_ERR_INVALID;
-    }
-    if (cfg->spp > (1u << 24)) {
-        set_error("spp exceeds 2^24");
-        return PT_ERR_INVALID;
-    }
-    uint32_t b = cfg->idx_begin, e = cfg->idx_end;
-    if (b == 0 && e == 0) e = (uint32_t)npix;
-    if (b >= e || e > npix) {
-        set_error("band [idx_begin, idx_end) is empty or outside the frame");
-        return PT_ERR_INVALID;
-    }
-    if (cfg->backend != PT_BACKEND_WAVEFRONT && cfg->backend != PT_BACKEND_MEGAKERNEL) {
-        set_error("unknown backend");
-        return PT_ERR_INVALID;
-    }
-    if (cfg->chunk_step > 1u && (cfg->chunk_pixels == 0u || cfg->chunk_first >= cfg->chunk_step)) {
-        set_error("chunk_pixels must be positive and chunk_first < chunk_step");
-        return PT_ERR_INVALID;
-    }
-    *idx_begin = b;
-    *idx_end = e;
-    return PT_OK;
-}
-
-// pixels of the band [b, e) that fall into chunks first, first+step, ... (all of them when step <= 1)
-uint32_t owned_pixels(const pt_config *cfg, uint32_t b, uint32_t e) {
-    const uint64_t span = e - b;
-    if (cfg->chunk_step <= 1u) return (uint32_t)span;
-    const uint64_t C = cfg->chunk_pixels, n_chunks = (span + C - 1) / C;
-    uint64_t total = 0;
-    for (uint64_t c = cfg->chunk_first; c < n_chunks; c += cfg->chunk_step) {
-        const uint64_t lo = c * C, hi = (lo + C < span) ? lo + C : span;
-        total += hi - lo;
-    }
-    return (uint32_t)total;
 }
 
 FrameParams make_frame(const pt_ctx *ctx, const pt_config *cfg, uint32_t idx_begin, uint32_t idx_end) {
@@ -404,9 +381,6 @@ static void say_layout(pt_ctx *c, const LdsLayout &L, int which) {
     fprintf(stderr, "%s\n", line.c_str());
 }
 
-// A call of more than 1.5 Mi pixels is rendered in parts of 2^20 pixels (pt_ctx_render says why); pixels per part
-uint32_t part_pixels(uint32_t total, bool wavefront) { return (wavefront && total > (3u << 19)) ? (1u << 20) : total; }
-
 // pt_ctx_accumulate's sums of a part's pixels: [3] planes of `stride` u64 in pixel order, the part's first pixel at p.  A
 // renderer given them starts its accumulators from them (launch_accum_gather) instead of from zero.
 struct HeldSums {
@@ -427,6 +401,19 @@ bool progress(pt_ctx *c, const pt_config *cfg, pt_progress_fn cb, void *user, fl
     cb(user, f);
     return true;
 }
+
+// A progress relay: the fractions below 1 of an inner call, passed on as base + scale * f of the outer one.  The inner call's
+// "1.0" is not passed on: the outer call says when IT is complete (the next job, every pipeline or rank finished and the frame
+// assembled).
+struct Relay {
+    pt_progress_fn cb;
+    void *user;
+    float base = 0.0f, scale = 1.0f;
+    static void fn(void *self, float f) {
+        Relay *r = (Relay *)self;
+        if (f < 1.0f) r->cb(r->user, r->base + r->scale * f);
+    }
+};
 
 // The cadence of a renderer's launches (the wavefront's passes, the megakernel's rounds) on events 0..5 of the context's pool.
 // The cancel byte is read at EVERY launch boundary (the reference polls it every 100 ms, mod.rs:947-958) and again after a
@@ -835,32 +822,6 @@ int render_mega(pt_ctx *c, const FrameForm &form, const pt_config *cfg, const Fr
     return PT_OK;
 }
 
-// pt_ctx_accumulate's frame key of a checked config (b, e: check_cfg's band)
-AccumKey accum_key(const pt_config *cfg, uint32_t b, uint32_t e) {
-    AccumKey k{};
-    k.width = cfg->width;
-    k.height = cfg->height;
-    k.idx_begin = b;
-    k.idx_end = e;
-    if (cfg->chunk_step > 1u) {
-        k.chunk_pixels = cfg->chunk_pixels;
-        k.chunk_first = cfg->chunk_first;
-        k.chunk_step = cfg->chunk_step;
-    }
-    k.seed = cfg->seed;
-    return k;
-}
-
-void accum_drop(pt_ctx *c) {
-    c->acc_on = false;
-    c->acc_cnt.clear();
-    c->acc_total = c->acc_part_px = 0;
-    c->acc_held.release();
-    c->acc_tracked = false;
-    c->acc_na.clear();
-    c->acc_a.release();
-}
-
 // The checkpoint's scene fingerprint: SipHash-1-3 (zero key) over n_objs, n_tris (u32 each), then the camera, the objects and
 // the triangles as pt_ctx_set_scene got them
 uint64_t scene_fingerprint(const pt_camera *cam, const pt_object *objs, uint32_t n_objs, const pt_triangle *tris, uint32_t n_tris) {
@@ -878,27 +839,16 @@ uint64_t scene_fingerprint(const pt_camera *cam, const pt_object *objs, uint32_t
 }
 
 // resolve part `i` of the held sums into the call's output: over its own count, black at 0
-int accum_resolve_part(pt_ctx *c, uint32_t i, float *out, hipStream_t st) {
-    const uint32_t k0 = i * c->acc_part_px, n = (c->acc_total - k0) < c->acc_part_px ? (c->acc_total - k0) : c->acc_part_px;
-    if (c->acc_cnt[i] != 0u)
-        launch_resolve(st, c->acc_held.p + k0, out + (size_t)k0 * 3, n, c->acc_cnt[i], 1u, c->acc_total);
+int accum_resolve_part(const HeldFrame &h, uint32_t i, float *out, hipStream_t st) {
+    const host::Part p = h.part(i);
+    if (h.cnt[i] != 0u)
+        launch_resolve(st, h.sums.p + p.k0, out + (size_t)p.k0 * 3, p.n, h.cnt[i], 1u, h.total);
     else
-        HIP_TRY(hipMemsetAsync(out + (size_t)k0 * 3, 0, (size_t)n * 3 * sizeof(float), st));
+        HIP_TRY(hipMemsetAsync(out + (size_t)p.k0 * 3, 0, (size_t)p.n * 3 * sizeof(float), st));
     return PT_OK;
 }
 
-// One piece of a frame call: pixels [k0, k0 + n) of the call, samples [s_first, s_end) of each (s_end 0: cfg->spp), the
-// accumulators starting from `held` (held.p == nullptr: from zero).  Progress inside it is reported as base + scale * f of the
-// call, and its start is a progress point at `base`.  [part_lo, part_hi): the parts of pt_ctx_accumulate's counts it brings to
-// its last sample.  `boundary`: the fraction reported at its start when that is not `base` (the second job of a part).
-struct Job {
-    uint32_t k0, n, s_first;
-    HeldSums held;
-    float base, scale;
-    uint32_t part_lo, part_hi;
-    uint32_t s_end = 0;
-    float boundary = -1.0f;
-};
+using host::Job;  // one piece of a frame call (pt_host.h); pt_ctx_accumulate's start from the held sums of their pixels
 
 void add_stats(pt_stats *stats, const pt_stats &s) {
     stats->ray_bounces += s.ray_bounces;
@@ -908,6 +858,16 @@ void add_stats(pt_stats *stats, const pt_stats &s) {
     stats->passes += s.passes;
     stats->ms_device += s.ms_device;
     stats->ms_intersect += s.ms_intersect;
+}
+
+// the stats of pipelines or ranks that ran side by side: summed, but the device time of the call is the longest of theirs
+void add_stats_concurrent(pt_stats *stats, const std::vector<pt_stats> &each) {
+    double longest = stats->ms_device;
+    for (const pt_stats &s : each) {
+        add_stats(stats, s);
+        longest = s.ms_device > longest ? s.ms_device : longest;
+    }
+    stats->ms_device = longest;
 }
 
 // pt_ctx_render after a job: its part resolved into the call's output over the samples per pixel it accumulated.  A
@@ -942,29 +902,30 @@ int keep_job(pt_ctx *c, const pt_config *cfg, const Job &j, int rc, hipStream_t 
     }
     // A noise-tracked frame deals the samples of a job to the half that holds fewer of them in its part (a tie: to A); the
     // parts of one job hold the same counts.  Half B is never stored: a job that goes to it only moves the counts.
-    const bool to_a = c->acc_tracked && c->acc_na[j.part_lo] <= c->acc_cnt[j.part_lo] - c->acc_na[j.part_lo];
+    HeldFrame &h = c->held;
+    const bool to_a = h.tracked() && host::deal_to_a(h.cnt[j.part_lo], h.na[j.part_lo]);
     if (to_a)
-        launch_accum_scatter_half(st, c->acc.p, j.n, c->live.streams, c->live.m, c->acc_held.p + j.k0, c->acc_a.p + j.k0, j.held.stride);
+        launch_accum_scatter_half(st, c->acc.p, j.n, c->live.streams, c->live.m, h.sums.p + j.k0, h.a.p + j.k0, h.total);
     else
-        launch_accum_scatter(st, c->acc.p, j.n, c->live.streams, c->live.m, c->acc_held.p + j.k0, j.held.stride);
+        launch_accum_scatter(st, c->acc.p, j.n, c->live.streams, c->live.m, h.sums.p + j.k0, h.total);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) {
         set_error(std::string("storing the held sums: ") + hipGetErrorString(e));
-        accum_drop(c);  // (their state is unknown)
+        h.drop();  // (their state is unknown)
         return PT_ERR_HIP;
     }
     for (uint32_t i = j.part_lo; i < j.part_hi; ++i) {
-        if (to_a) c->acc_na[i] += done - j.s_first;
-        c->acc_cnt[i] = done;
+        if (to_a) h.na[i] += done - j.s_first;
+        h.cnt[i] = done;
     }
     return rc;
 }
 
 // pt_ctx_accumulate's output at the end of the call: every part over its own count
 int resolve_held(pt_ctx *c, float *out, hipStream_t st, int rc) {
-    for (uint32_t i = 0; i < (uint32_t)c->acc_cnt.size(); ++i) {
-        const int r2 = accum_resolve_part(c, i, out, st);
+    for (uint32_t i = 0; i < c->held.n_parts(); ++i) {
+        const int r2 = accum_resolve_part(c->held, i, out, st);
         if (r2) {
             rc = r2;
             break;
@@ -988,15 +949,7 @@ int run_frame_call(pt_ctx *c, const pt_config *cfg, const FrameParams &F, const 
                    pt_stats *stats) {
     const double t0 = now_ms();
     const FrameForm form = form_for(c, cfg->flags);
-    struct Relay {  // a job's fractions as fractions of the call; its completion is reported by the next job / the end
-        pt_progress_fn cb;
-        void *user;
-        float base, scale;
-        static void fn(void *self, float f) {
-            Relay *r = (Relay *)self;
-            if (f < 1.0f) r->cb(r->user, r->base + r->scale * f);
-        }
-    } relay{cb, user, 0.0f, 1.0f};
+    Relay relay{cb, user};  // a job's fractions as fractions of the call; its completion is reported by the next job / the end
     struct Clear {  // however the call returns, pt_ctx_snapshot finds no frame in progress afterwards
         pt_ctx *c;
         ~Clear() { c->live = LiveFrame{}; }
@@ -1025,8 +978,10 @@ int run_frame_call(pt_ctx *c, const pt_config *cfg, const FrameParams &F, const 
         relay.base = j.base;
         relay.scale = j.scale;
         pt_stats js{};
+        HeldSums held{nullptr, 0u};  // pt_ctx_accumulate: the job starts from the held sums of its pixels
+        if (accumulate) held = {c->held.sums.p + j.k0, c->held.total};
         rc = (cfg->backend == PT_BACKEND_WAVEFRONT ? render_wavefront : render_mega)(
-            c, form, &jcfg, Fj, st, cancel, cb ? &Relay::fn : nullptr, &relay, js, j.s_first, j.held.p ? &j.held : nullptr);
+            c, form, &jcfg, Fj, st, cancel, cb ? &Relay::fn : nullptr, &relay, js, j.s_first, accumulate ? &held : nullptr);
         if (rc == PT_OK || rc == PT_CANCELLED) rc = accumulate ? keep_job(c, &jcfg, j, rc, st) : resolve_job(c, &jcfg, j, rc, st);
         if (stats) add_stats(stats, js);
         if (rc != PT_OK) break;
@@ -1049,26 +1004,6 @@ int frame_prologue(pt_ctx *c, const pt_config *cfg, uint32_t *ib, uint32_t *ie) 
     return PT_OK;
 }
 
-
-// ---- checkpoint file (pt_ctx_accum_save / _load, ptrace.h): little-endian, the byte order of every target of this library
-constexpr char kCkptMagic[8] = {'P', 'T', 'A', 'C', 'C', 'U', 'M', '1'};
-constexpr uint32_t kCkptVersion = 1u;         // the held sums
-constexpr uint32_t kCkptVersionTracked = 2u;  // ... and half A of a noise-tracked frame: its counts after the counts, its planes after the sums
-constexpr size_t kCkptHead = 8 + 4 + 7 * 4 + 8 + 8 + 3 * 4;  // magic .. number of parts: 68 bytes
-
-template <class T>
-void put(std::vector<uint8_t> &b, T v) {
-    const size_t at = b.size();
-    b.resize(at + sizeof v);
-    memcpy(b.data() + at, &v, sizeof v);
-}
-template <class T>
-T get(const uint8_t *&r) {
-    T v;
-    memcpy(&v, r, sizeof v);
-    r += sizeof v;
-    return v;
-}
 }  // namespace
 
 extern "C" {
@@ -1143,47 +1078,14 @@ void pt_ctx_destroy(pt_ctx *c) {
     if (!c) return;
     for (pt_ctx *p : c->pipes) pt_ctx_destroy(p);  // children own their queues, not the scene tables
     c->pipes.clear();
-    for (auto &b : c->pipe_out) b.release();
     (void)hipSetDevice(c->device);
-    (void)hipStreamSynchronize(c->stream);
+    (void)hipStreamSynchronize(c->stream);  // before anything is freed
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
-    c->d_objs.release();
-    c->d_opairs.release();
-    c->d_tris.release();
-    c->d_mats.release();
-    c->d_tshade.release();
-    c->d_nodes.release();
-    c->d_nodes4.release();
-    c->d_sph.release();
-    c->d_flat.release();
-    c->d_cand.release();
-    c->d_rank_id.release();
-    c->d_tri_rank.release();
-    c->d_bvh_meshes.release();
-    c->d_surf.release();
-    c->d_boxes.release();
-    c->q_o.release();
-    c->q_d.release();
-    c->q_t.release();
-    c->q_x.release();
-    c->q_n.release();
-    c->q_oid.release();
-    c->q_tid.release();
-    for (int w = 0; w < 2; ++w) c->q_buf[w].release();
-    c->hit.release();
-    c->cnt.release();
-    c->flags.release();
-    c->blk_rays.release();
-    c->acc.release();
-    c->acc_held.release();
-    c->acc_a.release();
-    c->noise_cnt.release();
-    c->dn_u[0].release();
-    c->dn_u[1].release();
-    c->dn_guide.release();
-    c->total_rays.release();
-    (void)hipStreamDestroy(c->stream);
+    // every DevBuf of the context frees itself here.  A child (borrowed_scene) holds copies of the parent's device pointers in
+    // `scene`, never the parent's DevBufs: nothing is freed twice.
+    const hipStream_t st = c->stream;
     delete c;
+    (void)hipStreamDestroy(st);
 }
 
 int pt_ctx_set_scene(pt_ctx *c, const pt_camera *cam, const pt_object *objs, uint32_t n_objs,
@@ -1199,7 +1101,7 @@ int pt_ctx_set_scene(pt_ctx *c, const pt_camera *cam, const pt_object *objs, uin
         return PT_ERR_INVALID;
     }
     HIP_TRY(hipSetDevice(c->device));
-    accum_drop(c);  // (the held sums are of the scene before)
+    c->held.drop();  // (the held sums are of the scene before)
     c->scene_fp = 0;
     int rc;
     if ((rc = c->d_objs.ensure(fs.objs.size())) || (rc = c->d_opairs.ensure(fs.obj_pairs.size())) || (rc = c->d_tris.ensure(fs.tri_pairs.size())) ||
@@ -1378,17 +1280,6 @@ int pt_ctx_set_profiling(pt_ctx *c, int enabled) {
     return PT_OK;
 }
 
-// progress relay for pipeline 0 / rank 0 of a call that renders on several contexts: its fractions are passed on, its
-// "1.0" is not - the call is complete when EVERY pipeline has finished and the frame is assembled, and the parent says so
-struct Below1 {
-    pt_progress_fn cb;
-    void *user;
-    static void fn(void *self, float f) {
-        Below1 *r = (Below1 *)self;
-        if (f < 1.0f) r->cb(r->user, f);
-    }
-};
-
 // n concurrent wavefront pipelines over the pixels of one call (PT_FLAG_PIPELINES)
 static int render_pipelined(pt_ctx *c, const pt_config *cfg, uint32_t n, uint32_t ib, uint32_t ie, float *d_out,
                             const volatile uint8_t *cancel, pt_progress_fn cb, void *user, pt_stats *stats) {
@@ -1430,11 +1321,11 @@ static int render_pipelined(pt_ctx *c, const pt_config *cfg, uint32_t n, uint32_
         if (rc) return rc;
     }
     std::vector<std::thread> th;
-    Below1 relay{cb, user};
+    Relay relay{cb, user};  // pipeline 0 / rank 0 reports for the call
     for (uint32_t j = 0; j < n; ++j) {
         if (own[j] == 0u) continue;
         th.emplace_back([&, j]() {
-            rcs[j] = pt_ctx_render(c->pipes[j], &cfgs[j], c->pipe_out[j].p, nullptr, cancel, (j == 0 && cb) ? &Below1::fn : nullptr,
+            rcs[j] = pt_ctx_render(c->pipes[j], &cfgs[j], c->pipe_out[j].p, nullptr, cancel, (j == 0 && cb) ? &Relay::fn : nullptr,
                                    &relay, &sts[j]);
             if (rcs[j] != PT_OK) errs[j] = g_last_error;
         });
@@ -1454,17 +1345,7 @@ static int render_pipelined(pt_ctx *c, const pt_config *cfg, uint32_t n, uint32_
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (stats) {
-        for (uint32_t j = 0; j < n; ++j) {
-            stats->ray_bounces += sts[j].ray_bounces;
-            stats->samples += sts[j].samples;
-            stats->intersect_rays += sts[j].intersect_rays;
-            stats->intersect_launches += sts[j].intersect_launches;
-            stats->passes += sts[j].passes;
-            stats->ms_device = sts[j].ms_device > stats->ms_device ? sts[j].ms_device : stats->ms_device;
-            stats->ms_intersect += sts[j].ms_intersect;
-        }
-    }
+    if (stats) add_stats_concurrent(stats, sts);
     if (worst == PT_CANCELLED) set_error("cancelled");
     return worst;
 }
@@ -1503,12 +1384,12 @@ int pt_ctx_render(pt_ctx *c, const pt_config *cfg, void *d_out_rgb, void *hip_st
     // cancelled call leaves the parts it did not start black (the reference's unrendered pixels are black too,
     // mod.rs:1003-1016) and the part in progress averaged over its accumulated samples.
     const uint32_t total = F.npix;
-    const uint32_t part_px = part_pixels(total, cfg->backend == PT_BACKEND_WAVEFRONT);
-    const uint32_t n_parts = (total + part_px - 1u) / part_px;
+    const uint32_t part_px = host::part_pixels(total, cfg->backend == PT_BACKEND_WAVEFRONT);
+    const uint32_t n_parts = host::part_count(total, part_px);
     std::vector<Job> jobs;
     for (uint32_t part = 0; part < n_parts; ++part) {
-        const uint32_t k0 = part * part_px, n = (total - k0) < part_px ? (total - k0) : part_px;
-        jobs.push_back({k0, n, 0u, HeldSums{nullptr, 0u}, (float)part / (float)n_parts, 1.0f / (float)n_parts, 0u, 0u});
+        const host::Part p = host::part_extent(total, part_px, part);
+        jobs.push_back({p.k0, p.n, 0u, (float)part / (float)n_parts, 1.0f / (float)n_parts, 0u, 0u});
     }
     return run_frame_call(c, cfg, F, jobs, false, (float *)d_out_rgb, total, st, cancel, cb, user, stats);
 }
@@ -1526,69 +1407,24 @@ int pt_ctx_accumulate(pt_ctx *c, const pt_config *cfg, void *d_out_rgb, void *hi
         set_error("pt_ctx_accumulate does not take PT_FLAG_PIPELINES: its accumulators live in child contexts");
         return PT_ERR_INVALID;
     }
-    const AccumKey key = accum_key(cfg, ib, ie);
+    const host::AccumKey key = host::accum_key(cfg, ib, ie);
     const uint32_t total = owned_pixels(cfg, ib, ie);
-    if (c->acc_on && c->acc_key == key) {
-        uint32_t held_max = 0;
-        for (uint32_t v : c->acc_cnt) held_max = v > held_max ? v : held_max;
-        if (cfg->spp < held_max) {
-            set_error("cfg->spp (" + std::to_string(cfg->spp) + ") is below the " + std::to_string(held_max) +
-                      " samples per pixel held for this frame: samples cannot be removed (pt_ctx_accum_reset starts over)");
-            return PT_ERR_INVALID;
-        }
+    HeldFrame &h = c->held;
+    if (h.holds(key) && cfg->spp < h.cnt_max()) {
+        set_error("cfg->spp (" + std::to_string(cfg->spp) + ") is below the " + std::to_string(h.cnt_max()) +
+                  " samples per pixel held for this frame: samples cannot be removed (pt_ctx_accum_reset starts over)");
+        return PT_ERR_INVALID;
     }
     if (stats) memset(stats, 0, sizeof *stats);
     if (total == 0u) return PT_OK;  // this rank owns no chunk of the band
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    const uint32_t part_px = part_pixels(total, true);  // counts are kept per part as the wavefront cuts a call, whatever the backend
-    const uint32_t n_parts = (total + part_px - 1u) / part_px;
-    if (!(c->acc_on && c->acc_key == key)) {  // another frame (or none): start from zero
-        accum_drop(c);
-        if ((rc = c->acc_held.ensure(3 * (size_t)total))) return rc;
-        HIP_TRY(hipMemsetAsync(c->acc_held.p, 0, 3 * (size_t)total * sizeof(unsigned long long), st));
-        c->acc_key = key;
-        c->acc_total = total;
-        c->acc_part_px = part_px;
-        c->acc_cnt.assign(n_parts, 0u);
-        if (c->acc_track) {  // half A starts empty too
-            if ((rc = c->acc_a.ensure(3 * (size_t)total))) {
-                accum_drop(c);
-                return rc;
-            }
-            HIP_TRY(hipMemsetAsync(c->acc_a.p, 0, 3 * (size_t)total * sizeof(unsigned long long), st));
-            c->acc_na.assign(n_parts, 0u);
-            c->acc_tracked = true;
-        }
-        c->acc_on = true;
+    if (!h.holds(key)) {  // another frame (or none): start from zero, half A of a tracked frame too
+        host::FrameCounts f{key, total, host::part_pixels(total, true)};  // counts are kept per part as the wavefront cuts a call, whatever the backend
+        f.cnt.assign(host::part_count(total, f.part_px), 0u);
+        if (c->acc_track) f.na = f.cnt;
+        if ((rc = h.start(std::move(f), nullptr, nullptr, st))) return rc;
     }
-    // What to render: each part from its own count; the megakernel, which renders a call at once, takes the whole call in one go
-    // when every part holds the same count.  Progress by pixels.  A noise-tracked frame cuts the samples [cnt, spp) of a part
-    // into two jobs at m = cnt + 4 * ceil((spp - cnt) / 8) - the first rounded up to whole groups of the four sub-pixels - so
-    // that both halves of the estimate get samples from every call (keep_job deals them).
-    std::vector<Job> jobs;
-    auto job = [&](uint32_t k0, uint32_t n, uint32_t part_lo, uint32_t part_hi) {
-        const uint32_t cnt = c->acc_cnt[part_lo];
-        const float base = (float)k0 / (float)total, scale = (float)n / (float)total;
-        const HeldSums held{c->acc_held.p + k0, total};
-        if (c->acc_tracked && cnt < cfg->spp) {
-            const uint64_t m64 = (uint64_t)cnt + 4ull * (((uint64_t)(cfg->spp - cnt) + 7ull) / 8ull);
-            const uint32_t m = m64 < cfg->spp ? (uint32_t)m64 : cfg->spp;
-            // (a renderer reports the samples issued over its job's last sample: the first job's fractions are scaled to the call's)
-            const float f1 = (float)m / (float)cfg->spp;
-            jobs.push_back({k0, n, cnt, held, base, scale * f1, part_lo, part_hi, m});
-            if (m < cfg->spp) jobs.push_back({k0, n, m, held, base, scale, part_lo, part_hi, cfg->spp, base + scale * f1});
-            return;
-        }
-        jobs.push_back({k0, n, cnt, held, base, scale, part_lo, part_hi});
-    };
-    bool even = true;
-    for (uint32_t v : c->acc_cnt) even = even && v == c->acc_cnt[0];
-    if (c->acc_tracked)
-        for (uint32_t v : c->acc_na) even = even && v == c->acc_na[0];
-    if (cfg->backend == PT_BACKEND_MEGAKERNEL && even)
-        job(0u, total, 0u, n_parts);
-    else
-        for (uint32_t i = 0; i < n_parts; ++i) job(i * part_px, (total - i * part_px) < part_px ? (total - i * part_px) : part_px, i, i + 1u);
+    const std::vector<Job> jobs = host::accum_jobs(h, cfg->spp, cfg->backend == PT_BACKEND_MEGAKERNEL);
     return run_frame_call(c, cfg, make_frame(c, cfg, ib, ie), jobs, true, (float *)d_out_rgb, total, st, cancel, cb, user, stats);
 }
 
@@ -1601,14 +1437,9 @@ int pt_ctx_accum_info(const pt_ctx *c, const pt_config *cfg, uint32_t *spp_min, 
     const int rc = check_cfg(cfg, &ib, &ie);
     if (rc) return rc;
     *spp_min = *spp_max = 0u;
-    if (!c->acc_on || !(c->acc_key == accum_key(cfg, ib, ie)) || c->acc_cnt.empty()) return PT_OK;
-    uint32_t lo = 0xffffffffu, hi = 0u;
-    for (uint32_t v : c->acc_cnt) {
-        lo = v < lo ? v : lo;
-        hi = v > hi ? v : hi;
-    }
-    *spp_min = lo;
-    *spp_max = hi;
+    if (!c->held.holds(host::accum_key(cfg, ib, ie))) return PT_OK;
+    *spp_min = c->held.cnt_min();
+    *spp_max = c->held.cnt_max();
     return PT_OK;
 }
 
@@ -1617,8 +1448,8 @@ int pt_ctx_accum_reset(pt_ctx *c) {
         set_error("ctx is NULL");
         return PT_ERR_INVALID;
     }
-    if (c->acc_held.p) HIP_TRY(hipSetDevice(c->device));
-    accum_drop(c);
+    if (c->held.sums.p) HIP_TRY(hipSetDevice(c->device));
+    c->held.drop();
     return PT_OK;
 }
 
@@ -1627,32 +1458,22 @@ int pt_ctx_accum_save(pt_ctx *c, const char *path) {
         set_error("NULL argument");
         return PT_ERR_INVALID;
     }
-    if (!c->acc_on) {
+    const HeldFrame &h = c->held;
+    if (!h.held()) {
         set_error("nothing accumulated on this context");
         return PT_ERR_INVALID;
     }
     HIP_TRY(hipSetDevice(c->device));
-    const size_t n_sums = 3 * (size_t)c->acc_total;
+    host::Checkpoint ck;
+    static_cast<host::FrameCounts &>(ck) = h;
+    ck.scene_fp = c->scene_fp;
     std::vector<uint8_t> b;
-    const size_t halves = c->acc_tracked ? 2u : 1u;
-    b.reserve(kCkptHead + halves * (4 * c->acc_cnt.size() + 8 * n_sums) + 8);
-    b.insert(b.end(), kCkptMagic, kCkptMagic + 8);
-    put<uint32_t>(b, c->acc_tracked ? kCkptVersionTracked : kCkptVersion);
-    const AccumKey &k = c->acc_key;
-    for (uint32_t v : {k.width, k.height, k.idx_begin, k.idx_end, k.chunk_pixels, k.chunk_first, k.chunk_step}) put<uint32_t>(b, v);
-    put<uint64_t>(b, k.seed);
-    put<uint64_t>(b, c->scene_fp);
-    put<uint32_t>(b, c->acc_total);
-    put<uint32_t>(b, c->acc_part_px);
-    put<uint32_t>(b, (uint32_t)c->acc_cnt.size());
-    for (uint32_t v : c->acc_cnt) put<uint32_t>(b, v);
-    if (c->acc_tracked)
-        for (uint32_t v : c->acc_na) put<uint32_t>(b, v);
-    const size_t at = b.size();
-    b.resize(at + halves * 8 * n_sums);
-    HIP_TRY(hipMemcpy(b.data() + at, c->acc_held.p, 8 * n_sums, hipMemcpyDeviceToHost));
-    if (c->acc_tracked) HIP_TRY(hipMemcpy(b.data() + at + 8 * n_sums, c->acc_a.p, 8 * n_sums, hipMemcpyDeviceToHost));
-    put<uint64_t>(b, pt_siphash(1, 3, 0, 0, b.data(), b.size()));
+    host::ckpt_encode_head(ck, b);
+    const size_t at = b.size(), plane = 3 * (size_t)h.total * sizeof(unsigned long long);
+    b.resize(at + (h.tracked() ? 2u : 1u) * plane);
+    HIP_TRY(hipMemcpy(b.data() + at, h.sums.p, plane, hipMemcpyDeviceToHost));
+    if (h.tracked()) HIP_TRY(hipMemcpy(b.data() + at + plane, h.a.p, plane, hipMemcpyDeviceToHost));
+    host::ckpt_seal(b);
     // written next to the target and renamed over it: a process that dies while saving leaves the last checkpoint whole
     const std::string tmp = std::string(path) + ".tmp";
     FILE *f = fopen(tmp.c_str(), "wb");
@@ -1701,104 +1522,33 @@ int pt_ctx_accum_load(pt_ctx *c, const char *path) {
         set_error(std::string("cannot read ") + path);
         return PT_ERR_IO;
     }
-    auto bad = [&](const std::string &why) {
+    // the decoder asks for the header first, and for the rest only once the file's size is the one the header implies
+    host::Checkpoint ck;
+    std::vector<uint8_t> b;
+    std::string why;
+    int d;
+    while ((d = host::ckpt_decode((uint64_t)fsize, b.data(), b.size(), ck, why)) == host::kCkptMore) {
+        const size_t at = b.size();
+        b.resize(ck.need);
+        if (fread(b.data() + at, 1, ck.need - at, f) != ck.need - at) {
+            set_error(std::string("cannot read ") + path);
+            return PT_ERR_IO;
+        }
+    }
+    if (d != host::kCkptOk) {
         set_error(std::string(path) + " is not a checkpoint of this library: " + why);
         return PT_ERR_PARSE;
-    };
-    if ((uint64_t)fsize < kCkptHead + 8) return bad("too short");
-    std::vector<uint8_t> b(kCkptHead);
-    if (fread(b.data(), 1, kCkptHead, f) != kCkptHead) {
-        set_error(std::string("cannot read ") + path);
-        return PT_ERR_IO;
     }
-    const uint8_t *r = b.data();
-    if (memcmp(r, kCkptMagic, 8) != 0) return bad("wrong magic");
-    r += 8;
-    const uint32_t version = get<uint32_t>(r);
-    if (version != kCkptVersion && version != kCkptVersionTracked) return bad("unknown format version");
-    const uint64_t halves = version == kCkptVersionTracked ? 2u : 1u;
-    AccumKey k{};
-    k.width = get<uint32_t>(r);
-    k.height = get<uint32_t>(r);
-    k.idx_begin = get<uint32_t>(r);
-    k.idx_end = get<uint32_t>(r);
-    k.chunk_pixels = get<uint32_t>(r);
-    k.chunk_first = get<uint32_t>(r);
-    k.chunk_step = get<uint32_t>(r);
-    k.seed = get<uint64_t>(r);
-    const uint64_t fp = get<uint64_t>(r);
-    const uint32_t total = get<uint32_t>(r), part_px = get<uint32_t>(r), n_parts = get<uint32_t>(r);
-    // the key must be one check_cfg accepts and accum_key writes, and the sizes must be the ones it implies
-    pt_config kc{};
-    kc.width = k.width;
-    kc.height = k.height;
-    kc.spp = 1;
-    kc.idx_begin = k.idx_begin;
-    kc.idx_end = k.idx_end;
-    kc.chunk_pixels = k.chunk_pixels;
-    kc.chunk_first = k.chunk_first;
-    kc.chunk_step = k.chunk_step;
-    kc.seed = k.seed;
-    uint32_t ib = 0, ie = 0;
-    if (check_cfg(&kc, &ib, &ie) != PT_OK || !(accum_key(&kc, ib, ie) == k)) return bad("the frame key is not a valid frame");
-    const uint32_t want_total = owned_pixels(&kc, ib, ie);
-    if (total != want_total || want_total == 0u || part_px != part_pixels(total, true) || n_parts != (total + part_px - 1u) / part_px)
-        return bad("sizes that do not fit each other");
-    const uint64_t want_size = kCkptHead + halves * (4ull * n_parts + 24ull * total) + 8ull;
-    if ((uint64_t)fsize != want_size) return bad((uint64_t)fsize < want_size ? "truncated" : "trailing bytes");
-    b.resize((size_t)want_size);
-    if (fread(b.data() + kCkptHead, 1, (size_t)want_size - kCkptHead, f) != (size_t)want_size - kCkptHead) {
-        set_error(std::string("cannot read ") + path);
-        return PT_ERR_IO;
-    }
-    uint64_t tag;
-    memcpy(&tag, b.data() + want_size - 8, 8);
-    if (tag != pt_siphash(1, 3, 0, 0, b.data(), (size_t)want_size - 8)) return bad("bad trailing hash");
-    std::vector<uint32_t> cnt(n_parts);
-    memcpy(cnt.data(), b.data() + kCkptHead, 4 * (size_t)n_parts);
-    for (uint32_t v : cnt)
-        if (v > (1u << 24)) return bad("a sample count above 2^24");
-    // a file of a noise-tracked frame brings half A; a plain one loaded into a tracking context starts it empty (all held
-    // samples then count as half B)
-    const bool tracked = halves == 2u || c->acc_track;
-    std::vector<uint32_t> na(tracked ? n_parts : 0u, 0u);
-    if (halves == 2u) {
-        memcpy(na.data(), b.data() + kCkptHead + 4 * (size_t)n_parts, 4 * (size_t)n_parts);
-        for (uint32_t i = 0; i < n_parts; ++i)
-            if (na[i] > cnt[i]) return bad("half A holds more samples than the part");
-    }
-    if (fp != c->scene_fp) {
+    if (ck.scene_fp != c->scene_fp) {
         set_error(std::string(path) + " was rendered from another scene than the one set on this context");
         return PT_ERR_INVALID;
     }
     HIP_TRY(hipSetDevice(c->device));
-    accum_drop(c);
-    int rc = c->acc_held.ensure(3 * (size_t)total);
-    if (!rc && tracked) rc = c->acc_a.ensure(3 * (size_t)total);
-    if (rc) {
-        accum_drop(c);
-        return rc;
-    }
-    const uint8_t *sums = b.data() + kCkptHead + halves * 4 * (size_t)n_parts;
-    hipError_t e = hipMemcpy(c->acc_held.p, sums, 24 * (size_t)total, hipMemcpyHostToDevice);
-    if (e == hipSuccess && halves == 2u) e = hipMemcpy(c->acc_a.p, sums + 24 * (size_t)total, 24 * (size_t)total, hipMemcpyHostToDevice);
-    if (e == hipSuccess && tracked && halves == 1u) {
-        e = hipMemsetAsync(c->acc_a.p, 0, 24 * (size_t)total, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    }
-    if (e != hipSuccess) {
-        set_error(std::string("uploading the checkpoint: ") + hipGetErrorString(e));
-        accum_drop(c);
-        return PT_ERR_HIP;
-    }
-    c->acc_key = k;
-    c->acc_total = total;
-    c->acc_part_px = part_px;
-    c->acc_cnt = cnt;
-    c->acc_na = na;
-    c->acc_tracked = tracked;
-    c->acc_on = true;
-    return PT_OK;
+    // a file of a noise-tracked frame brings half A; a plain one loaded into a tracking context starts it empty (all held
+    // samples then count as half B)
+    const uint8_t *half_a = ck.tracked() ? b.data() + ck.a_at : nullptr;
+    if (!ck.tracked() && c->acc_track) ck.na.assign(ck.n_parts(), 0u);
+    return c->held.start(std::move(ck), b.data() + ck.sums_at, half_a, c->stream);
 }
 
 int pt_ctx_accum_track_noise(pt_ctx *c, int enabled) {
@@ -1806,7 +1556,7 @@ int pt_ctx_accum_track_noise(pt_ctx *c, int enabled) {
         set_error("ctx is NULL");
         return PT_ERR_INVALID;
     }
-    if (c->acc_on) {
+    if (c->held.held()) {
         set_error("an accumulator is held: tracking applies to frames started after the call - call pt_ctx_accum_reset first");
         return PT_ERR_INVALID;
     }
@@ -1819,11 +1569,12 @@ int pt_ctx_accum_track_noise(pt_ctx *c, int enabled) {
 constexpr int kNoiseNone = 1;
 static int accum_noise(pt_ctx *c, float *d_error, pt_noise_stats *out, hipStream_t st) {
     memset(out, 0, sizeof *out);
-    const uint32_t n_parts = (uint32_t)c->acc_cnt.size();
+    const HeldFrame &fr = c->held;
+    const uint32_t n_parts = fr.n_parts();
     out->spp_min = out->spp_a_min = out->spp_b_min = 0xffffffffu;
     bool any = false;
     for (uint32_t i = 0; i < n_parts; ++i) {
-        const uint32_t cnt = c->acc_cnt[i], na = c->acc_na[i], nb = cnt - na;
+        const uint32_t cnt = fr.cnt[i], na = fr.na[i], nb = cnt - na;
         out->spp_min = cnt < out->spp_min ? cnt : out->spp_min;
         out->spp_max = cnt > out->spp_max ? cnt : out->spp_max;
         out->spp_a_min = na < out->spp_a_min ? na : out->spp_a_min;
@@ -1840,16 +1591,14 @@ static int accum_noise(pt_ctx *c, float *d_error, pt_noise_stats *out, hipStream
     if (rc) return rc;
     HIP_TRY(hipMemsetAsync(c->noise_cnt.p, 0, sizeof(NoiseCounters), st));
     for (uint32_t i = 0; i < n_parts; ++i) {
-        const uint32_t k0 = i * c->acc_part_px, n = (c->acc_total - k0) < c->acc_part_px ? (c->acc_total - k0) : c->acc_part_px;
-        const uint32_t na = c->acc_na[i], nb = c->acc_cnt[i] - na;
+        const host::Part p = fr.part(i);
+        const uint32_t na = fr.na[i], nb = fr.cnt[i] - na;
         if (na != 0u && nb != 0u) {
-            const float fa = (float)na, fb = (float)nb;
-            const float w = __builtin_sqrtf(fa * fb) / (fa + fb);  // binary32, as the header states it
-            launch_noise(st, c->acc_held.p + k0, c->acc_a.p + k0, c->acc_total, n, na, nb, w, d_error ? d_error + k0 : nullptr,
-                         c->noise_cnt.p);
-            out->pixels += n;
+            launch_noise(st, fr.sums.p + p.k0, fr.a.p + p.k0, fr.total, p.n, na, nb, host::noise_part_weight(na, nb),
+                         d_error ? d_error + p.k0 : nullptr, c->noise_cnt.p);
+            out->pixels += p.n;
         } else if (d_error) {
-            launch_noise_none(st, d_error + k0, n);
+            launch_noise_none(st, d_error + p.k0, p.n);
         }
     }
     HIP_TRY(hipGetLastError());
@@ -1866,11 +1615,11 @@ static int held_tracked_frame(const pt_ctx *c, const pt_config *cfg) {
     uint32_t ib = 0, ie = 0;
     const int rc = check_cfg(cfg, &ib, &ie);
     if (rc) return rc;
-    if (!c->acc_on || !(c->acc_key == accum_key(cfg, ib, ie)) || c->acc_cnt.empty()) {
+    if (!c->held.holds(host::accum_key(cfg, ib, ie))) {
         set_error("cfg does not name the frame this context holds");
         return PT_ERR_INVALID;
     }
-    if (!c->acc_tracked) {
+    if (!c->held.tracked()) {
         set_error("the held frame is not noise-tracked (pt_ctx_accum_track_noise before the frame is started)");
         return PT_ERR_INVALID;
     }
@@ -1890,15 +1639,6 @@ int pt_ctx_accum_noise(pt_ctx *c, const pt_config *cfg, float *d_error, pt_noise
         return PT_ERR_INVALID;
     }
     return rc;
-}
-
-// the upper edge of histogram bin `b` of pt_noise_stats (ptrace.h): the float whose bits are (461 + b) << 21; +inf for the last
-static float noise_bin_upper(uint32_t b) {
-    if (b >= kNoiseBins - 1u) return __builtin_inff();
-    const uint32_t bits = (461u + b) << 21;
-    float v;
-    memcpy(&v, &bits, 4);
-    return v;
 }
 
 int pt_ctx_accumulate_until(pt_ctx *c, const pt_config *cfg, const pt_noise_target *tgt, void *d_out_rgb, void *hip_stream,
@@ -1928,39 +1668,28 @@ int pt_ctx_accumulate_until(pt_ctx *c, const pt_config *cfg, const pt_noise_targ
     uint32_t ib = 0, ie = 0;
     int rc = check_cfg(cfg, &ib, &ie);
     if (rc) return rc;
-    const bool held = c->acc_on && c->acc_key == accum_key(cfg, ib, ie);
-    if (!(held ? c->acc_tracked : c->acc_track)) {
+    const bool held = c->held.holds(host::accum_key(cfg, ib, ie));
+    if (!(held ? c->held.tracked() : c->acc_track)) {
         set_error("pt_ctx_accumulate_until needs noise tracking (pt_ctx_accum_track_noise before the frame is started)");
         return PT_ERR_INVALID;
     }
     const double t0 = now_ms();
     if (stats) memset(stats, 0, sizeof *stats);
     memset(noise, 0, sizeof *noise);
-    uint32_t have = 0;
-    if (held)
-        for (uint32_t v : c->acc_cnt) have = v > have ? v : have;
+    uint32_t have = held ? c->held.cnt_max() : 0u;
     if (cfg->spp < have) {
         set_error("cfg->spp, the cap, is below the samples per pixel held for this frame");
         return PT_ERR_INVALID;
     }
     const uint32_t cap = cfg->spp, min_spp = tgt->min_spp ? tgt->min_spp : 16u;
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    struct Relay {  // a step's fractions as fractions of the cap's samples; the end of the call reports 1
-        pt_progress_fn cb;
-        void *user;
-        float base, scale;
-        static void fn(void *self, float f) {
-            Relay *r = (Relay *)self;
-            if (f < 1.0f) r->cb(r->user, r->base + r->scale * f);
-        }
-    } relay{cb, user, 0.0f, 0.0f};
+    Relay relay{cb, user};  // a step's fractions as fractions of the cap's samples; the end of the call reports 1
     uint32_t t = have > min_spp ? have : min_spp;
     for (;;) {
         t = t < cap ? t : cap;
         pt_config step = *cfg;
         step.spp = t;
-        relay.base = 0.0f;  // (pt_ctx_accumulate's fractions count the samples held as done)
-        relay.scale = (float)t / (float)cap;
+        relay.scale = (float)t / (float)cap;  // (base 0: pt_ctx_accumulate's fractions count the samples held as done)
         pt_stats ss{};
         rc = pt_ctx_accumulate(c, &step, d_out_rgb, hip_stream, cancel, cb ? &Relay::fn : nullptr, &relay, &ss);
         if (stats) add_stats(stats, ss);
@@ -1975,21 +1704,7 @@ int pt_ctx_accumulate_until(pt_ctx *c, const pt_config *cfg, const pt_noise_targ
             set_error("cancelled");
             break;
         }
-        bool met = rn == PT_OK;
-        if (met && use_mean) met = noise->mean_error <= (double)tgt->mean_error;
-        if (met && use_q) {
-            // the first bin at which the cumulative count reaches ceil(quantile * pixels)
-            const double need_d = (double)tgt->quantile * (double)noise->pixels;
-            uint64_t need = (uint64_t)need_d;
-            if ((double)need < need_d) ++need;
-            need = need ? need : 1u;
-            uint64_t cum = 0;
-            uint32_t b = 0;
-            for (; b < kNoiseBins; ++b)
-                if ((cum += noise->histogram[b]) >= need) break;
-            met = noise_bin_upper(b) <= tgt->quantile_error;
-        }
-        if (met || t >= cap) break;
+        if ((rn == PT_OK && host::noise_target_met(*noise, *tgt)) || t >= cap) break;
         have = t;
         t = t > cap / 2u ? cap : t * 2u;
     }
@@ -2253,10 +1968,10 @@ int pt_ctx_snapshot(pt_ctx *c, void *d_out_rgb, uint32_t *spp_done) {
     const LiveFrame &L = c->live;
     hipStream_t st = L.stream;
     if (L.accum) {  // pt_ctx_accumulate: every part outside the one in progress at its own count, from the held sums
-        for (uint32_t i = 0; i < (uint32_t)c->acc_cnt.size(); ++i) {
-            const uint32_t k0 = i * c->acc_part_px;
+        for (uint32_t i = 0; i < c->held.n_parts(); ++i) {
+            const uint32_t k0 = c->held.part(i).k0;
             if (k0 >= L.k0 && k0 < L.k0 + L.npix) continue;
-            int rc = accum_resolve_part(c, i, snap, st);
+            int rc = accum_resolve_part(c->held, i, snap, st);
             if (rc) return rc;
         }
     } else if (L.k0 != 0u && L.out && L.out != snap) {
@@ -2630,7 +2345,7 @@ int pt_render_multi(const pt_config *cfg, uint32_t n_ranks, const pt_camera *cam
     std::vector<std::string> errs(n_ranks);
     std::vector<std::thread> th;
     const double t0 = now_ms();
-    Below1 relay{cb, user};
+    Relay relay{cb, user};  // pipeline 0 / rank 0 reports for the call
     for (uint32_t r = 0; r < n_ranks; ++r) {
         cfgs[r].idx_begin = ib;
         cfgs[r].idx_end = ie;
@@ -2645,21 +2360,13 @@ int pt_render_multi(const pt_config *cfg, uint32_t n_ranks, const pt_camera *cam
         const uint32_t on_dev = (n_ranks - dev + (uint32_t)n_dev - 1u) / (uint32_t)n_dev;
         th.emplace_back([&, r, dev, on_dev]() {
             rcs[r] = render_band_to_host((int)dev, &cfgs[r], cam, objs, n_objs, tris, n_tris, out_rgb, cancel,
-                                         (r == 0 && cb) ? &Below1::fn : nullptr, &relay, &sts[r], &errs[r], on_dev);
+                                         (r == 0 && cb) ? &Relay::fn : nullptr, &relay, &sts[r], &errs[r], on_dev);
         });
     }
     for (auto &t : th) t.join();
     if (stats) {
         memset(stats, 0, sizeof *stats);
-        for (uint32_t r = 0; r < n_ranks; ++r) {
-            stats->ray_bounces += sts[r].ray_bounces;
-            stats->samples += sts[r].samples;
-            stats->intersect_rays += sts[r].intersect_rays;
-            stats->intersect_launches += sts[r].intersect_launches;
-            stats->passes += sts[r].passes;
-            stats->ms_device = sts[r].ms_device > stats->ms_device ? sts[r].ms_device : stats->ms_device;
-            stats->ms_intersect += sts[r].ms_intersect;
-        }
+        add_stats_concurrent(stats, sts);
         stats->ms_total = now_ms() - t0;
     }
     for (uint32_t r = 0; r < n_ranks; ++r)

@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <limits>
 
 namespace pt {
@@ -823,6 +824,243 @@ uint32_t next_pass_samples(double rate, double target_ms, uint64_t npix, uint64_
     if (stretch > max_pass) stretch = max_pass;
     const uint32_t n_left = (uint32_t)((left + stretch - 1u) / stretch);
     return (left + n_left - 1u) / n_left;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Frame calls and the held frame of pt_ctx_accumulate
+int check_cfg(const pt_config *cfg, uint32_t *idx_begin, uint32_t *idx_end) {
+    if (!cfg) {
+        set_error("cfg is NULL");
+        return PT_ERR_INVALID;
+    }
+    if (cfg->width == 0 || cfg->height == 0 || cfg->spp == 0) {
+        set_error("width, height and spp must be positive");
+        return PT_ERR_INVALID;
+    }
+    const uint64_t npix = (uint64_t)cfg->width * cfg->height;
+    if (npix > 0x7fffffffull) {
+        set_error("width*height exceeds 2^31-1");
+        return PT_ERR_INVALID;
+    }
+    if (cfg->spp > (1u << 24)) {
+        set_error("spp exceeds 2^24");
+        return PT_ERR_INVALID;
+    }
+    uint32_t b = cfg->idx_begin, e = cfg->idx_end;
+    if (b == 0 && e == 0) e = (uint32_t)npix;
+    if (b >= e || e > npix) {
+        set_error("band [idx_begin, idx_end) is empty or outside the frame");
+        return PT_ERR_INVALID;
+    }
+    if (cfg->backend != PT_BACKEND_WAVEFRONT && cfg->backend != PT_BACKEND_MEGAKERNEL) {
+        set_error("unknown backend");
+        return PT_ERR_INVALID;
+    }
+    if (cfg->chunk_step > 1u && (cfg->chunk_pixels == 0u || cfg->chunk_first >= cfg->chunk_step)) {
+        set_error("chunk_pixels must be positive and chunk_first < chunk_step");
+        return PT_ERR_INVALID;
+    }
+    *idx_begin = b;
+    *idx_end = e;
+    return PT_OK;
+}
+
+uint32_t owned_pixels(const pt_config *cfg, uint32_t b, uint32_t e) {
+    const uint64_t span = e - b;
+    if (cfg->chunk_step <= 1u) return (uint32_t)span;
+    const uint64_t C = cfg->chunk_pixels, n_chunks = (span + C - 1) / C;
+    uint64_t total = 0;
+    for (uint64_t c = cfg->chunk_first; c < n_chunks; c += cfg->chunk_step) {
+        const uint64_t lo = c * C, hi = (lo + C < span) ? lo + C : span;
+        total += hi - lo;
+    }
+    return (uint32_t)total;
+}
+
+uint32_t part_pixels(uint32_t total, bool wavefront) { return (wavefront && total > (3u << 19)) ? (1u << 20) : total; }
+
+AccumKey accum_key(const pt_config *cfg, uint32_t b, uint32_t e) {
+    AccumKey k{};
+    k.width = cfg->width;
+    k.height = cfg->height;
+    k.idx_begin = b;
+    k.idx_end = e;
+    if (cfg->chunk_step > 1u) {
+        k.chunk_pixels = cfg->chunk_pixels;
+        k.chunk_first = cfg->chunk_first;
+        k.chunk_step = cfg->chunk_step;
+    }
+    k.seed = cfg->seed;
+    return k;
+}
+
+std::vector<Job> accum_jobs(const FrameCounts &f, uint32_t spp, bool megakernel) {
+    std::vector<Job> jobs;
+    auto job = [&](Part p, uint32_t part_lo, uint32_t part_hi) {
+        const uint32_t c = f.cnt[part_lo];
+        const float base = (float)p.k0 / (float)f.total, scale = (float)p.n / (float)f.total;
+        if (f.tracked() && c < spp) {
+            const uint64_t m64 = (uint64_t)c + 4ull * (((uint64_t)(spp - c) + 7ull) / 8ull);
+            const uint32_t m = m64 < spp ? (uint32_t)m64 : spp;
+            // (a renderer reports the samples issued over its job's last sample: the first job's fractions are scaled to the call's)
+            const float f1 = (float)m / (float)spp;
+            jobs.push_back({p.k0, p.n, c, base, scale * f1, part_lo, part_hi, m});
+            if (m < spp) jobs.push_back({p.k0, p.n, m, base, scale, part_lo, part_hi, spp, base + scale * f1});
+            return;
+        }
+        jobs.push_back({p.k0, p.n, c, base, scale, part_lo, part_hi});
+    };
+    bool even = true;
+    for (uint32_t v : f.cnt) even = even && v == f.cnt[0];
+    for (uint32_t v : f.na) even = even && v == f.na[0];
+    if (megakernel && even)
+        job({0u, f.total}, 0u, f.n_parts());
+    else
+        for (uint32_t i = 0; i < f.n_parts(); ++i) job(f.part(i), i, i + 1u);
+    return jobs;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The checkpoint file.  Its layout is written down here and nowhere else: magic, u32 version, the key (7 x u32, u64 seed), u64
+// scene fingerprint, u32 total, part_px, number of parts - 68 bytes; the parts' counts; half A's counts (version 2); the held
+// sums; half A's sums (version 2); u64 SipHash-1-3 of everything before it.
+namespace {
+constexpr char kCkptMagic[8] = {'P', 'T', 'A', 'C', 'C', 'U', 'M', '1'};
+constexpr uint32_t kCkptVersion = 1u;         // the held sums
+constexpr uint32_t kCkptVersionTracked = 2u;  // ... and half A of a noise-tracked frame: its counts after the counts, its planes after the sums
+constexpr size_t kCkptHead = 8 + 4 + 7 * 4 + 8 + 8 + 3 * 4;  // magic .. number of parts: 68 bytes
+
+template <class T>
+void put(std::vector<uint8_t> &b, T v) {
+    const size_t at = b.size();
+    b.resize(at + sizeof v);
+    memcpy(b.data() + at, &v, sizeof v);
+}
+template <class T>
+T get(const uint8_t *&r) {
+    T v;
+    memcpy(&v, r, sizeof v);
+    r += sizeof v;
+    return v;
+}
+}  // namespace
+
+void ckpt_encode_head(const Checkpoint &ck, std::vector<uint8_t> &b) {
+    const size_t halves = ck.tracked() ? 2u : 1u;
+    b.reserve(b.size() + kCkptHead + halves * (4 * ck.cnt.size() + 24 * (size_t)ck.total) + 8);
+    b.insert(b.end(), kCkptMagic, kCkptMagic + 8);
+    put<uint32_t>(b, ck.tracked() ? kCkptVersionTracked : kCkptVersion);
+    const AccumKey &k = ck.key;
+    for (uint32_t v : {k.width, k.height, k.idx_begin, k.idx_end, k.chunk_pixels, k.chunk_first, k.chunk_step}) put<uint32_t>(b, v);
+    put<uint64_t>(b, k.seed);
+    put<uint64_t>(b, ck.scene_fp);
+    put<uint32_t>(b, ck.total);
+    put<uint32_t>(b, ck.part_px);
+    put<uint32_t>(b, (uint32_t)ck.cnt.size());
+    for (uint32_t v : ck.cnt) put<uint32_t>(b, v);
+    for (uint32_t v : ck.na) put<uint32_t>(b, v);
+}
+
+void ckpt_seal(std::vector<uint8_t> &b) { put<uint64_t>(b, pt_siphash(1, 3, 0, 0, b.data(), b.size())); }
+
+int ckpt_decode(uint64_t file_size, const uint8_t *b, size_t n, Checkpoint &out, std::string &why) {
+    auto bad = [&](const char *w) {
+        why = w;
+        return kCkptBad;
+    };
+    auto more = [&](size_t need) {
+        out.need = need;
+        return kCkptMore;
+    };
+    if (file_size < kCkptHead + 8) return bad("too short");
+    if (n < kCkptHead) return more(kCkptHead);
+    const uint8_t *r = b;
+    if (memcmp(r, kCkptMagic, 8) != 0) return bad("wrong magic");
+    r += 8;
+    const uint32_t version = get<uint32_t>(r);
+    if (version != kCkptVersion && version != kCkptVersionTracked) return bad("unknown format version");
+    const uint64_t halves = version == kCkptVersionTracked ? 2u : 1u;
+    AccumKey &k = out.key;
+    k.width = get<uint32_t>(r);
+    k.height = get<uint32_t>(r);
+    k.idx_begin = get<uint32_t>(r);
+    k.idx_end = get<uint32_t>(r);
+    k.chunk_pixels = get<uint32_t>(r);
+    k.chunk_first = get<uint32_t>(r);
+    k.chunk_step = get<uint32_t>(r);
+    k.seed = get<uint64_t>(r);
+    out.scene_fp = get<uint64_t>(r);
+    const uint32_t total = out.total = get<uint32_t>(r), part_px = out.part_px = get<uint32_t>(r), n_parts = get<uint32_t>(r);
+    // the key must be one check_cfg accepts and accum_key writes, and the sizes must be the ones it implies
+    pt_config kc{};
+    kc.width = k.width;
+    kc.height = k.height;
+    kc.spp = 1;
+    kc.idx_begin = k.idx_begin;
+    kc.idx_end = k.idx_end;
+    kc.chunk_pixels = k.chunk_pixels;
+    kc.chunk_first = k.chunk_first;
+    kc.chunk_step = k.chunk_step;
+    kc.seed = k.seed;
+    uint32_t ib = 0, ie = 0;
+    if (check_cfg(&kc, &ib, &ie) != PT_OK || !(accum_key(&kc, ib, ie) == k)) return bad("the frame key is not a valid frame");
+    const uint32_t want_total = owned_pixels(&kc, ib, ie);
+    if (total != want_total || want_total == 0u || part_px != part_pixels(total, true) || n_parts != part_count(total, part_px))
+        return bad("sizes that do not fit each other");
+    // (nothing behind the header is looked at before the file's size is the one the header implies)
+    const uint64_t want_size = kCkptHead + halves * (4ull * n_parts + 24ull * total) + 8ull;
+    if (file_size != want_size) return bad(file_size < want_size ? "truncated" : "trailing bytes");
+    if (n < want_size) return more((size_t)want_size);
+    uint64_t tag;
+    memcpy(&tag, b + want_size - 8, 8);
+    if (tag != pt_siphash(1, 3, 0, 0, b, (size_t)want_size - 8)) return bad("bad trailing hash");
+    out.cnt.resize(n_parts);
+    memcpy(out.cnt.data(), b + kCkptHead, 4 * (size_t)n_parts);
+    for (uint32_t v : out.cnt)
+        if (v > (1u << 24)) return bad("a sample count above 2^24");
+    out.na.assign(halves == 2u ? n_parts : 0u, 0u);
+    if (halves == 2u) {
+        memcpy(out.na.data(), b + kCkptHead + 4 * (size_t)n_parts, 4 * (size_t)n_parts);
+        for (uint32_t i = 0; i < n_parts; ++i)
+            if (out.na[i] > out.cnt[i]) return bad("half A holds more samples than the part");
+    }
+    out.sums_at = kCkptHead + halves * 4 * (size_t)n_parts;
+    out.a_at = out.sums_at + 24 * (size_t)total;
+    return kCkptOk;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The noise estimate
+float noise_part_weight(uint32_t na, uint32_t nb) {
+    const float fa = (float)na, fb = (float)nb;
+    return __builtin_sqrtf(fa * fb) / (fa + fb);
+}
+
+static constexpr uint32_t kNoiseBinCount = sizeof(pt_noise_stats::histogram) / sizeof(uint32_t);
+
+float noise_bin_upper(uint32_t b) {
+    if (b >= kNoiseBinCount - 1u) return std::numeric_limits<float>::infinity();
+    const uint32_t bits = (461u + b) << 21;
+    float v;
+    memcpy(&v, &bits, 4);
+    return v;
+}
+
+uint32_t noise_quantile_bin(const pt_noise_stats &s, float quantile) {
+    const double need_d = (double)quantile * (double)s.pixels;
+    uint64_t need = (uint64_t)need_d;
+    if ((double)need < need_d) ++need;
+    need = need ? need : 1u;
+    uint64_t cum = 0;
+    uint32_t b = 0;
+    for (; b < kNoiseBinCount; ++b)
+        if ((cum += s.histogram[b]) >= need) break;
+    return b;
+}
+
+bool noise_target_met(const pt_noise_stats &s, const pt_noise_target &t) {
+    if (t.mean_error != 0.0f && !(s.mean_error <= (double)t.mean_error)) return false;
+    return t.quantile == 0.0f || noise_bin_upper(noise_quantile_bin(s, t.quantile)) <= t.quantile_error;
 }
 
 }  // namespace host

@@ -1,6 +1,7 @@
 // pt_host.h — host-side setup arithmetic of the path (camera basis, Mesh::new bounds, scene flattening).
 #pragma once
 
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -86,6 +87,101 @@ uint32_t next_pass_samples(double rate, double target_ms, uint64_t npix, uint64_
                            uint32_t max_pass);
 bool flatten_scene(const pt_camera &cam, const pt_object *objs, uint32_t n_objs, const pt_triangle *tris,
                    uint32_t n_tris, FlatScene &out, std::string &err);
+
+// ---- the arithmetic of a frame call and of the frame pt_ctx_accumulate holds (pt_api.hip): pure, tested on the CPU -----------
+// a valid cfg's band in [*idx_begin, *idx_end); PT_ERR_INVALID + message otherwise
+int check_cfg(const pt_config *cfg, uint32_t *idx_begin, uint32_t *idx_end);
+// pixels of the band [b, e) that fall into chunks first, first+step, ... (all of them when step <= 1)
+uint32_t owned_pixels(const pt_config *cfg, uint32_t b, uint32_t e);
+// A call of more than 1.5 Mi pixels is rendered in parts of 2^20 pixels (pt_ctx_render says why); pixels per part
+uint32_t part_pixels(uint32_t total, bool wavefront);
+// part i of `total` pixels cut into parts of part_px: pixels [k0, k0 + n)
+struct Part {
+    uint32_t k0, n;
+};
+inline uint32_t part_count(uint32_t total, uint32_t part_px) { return (total + part_px - 1u) / part_px; }
+inline Part part_extent(uint32_t total, uint32_t part_px, uint32_t i) {
+    const uint32_t k0 = i * part_px;
+    return {k0, (total - k0) < part_px ? (total - k0) : part_px};
+}
+
+// The frame a pt_ctx_accumulate call renders: what decides the image besides the samples (the scene is the context's).
+// chunk_* as check_cfg reads them: all zero for a whole band.
+struct AccumKey {
+    uint32_t width, height, idx_begin, idx_end, chunk_pixels, chunk_first, chunk_step;
+    uint64_t seed;
+    bool operator==(const AccumKey &o) const {
+        return width == o.width && height == o.height && idx_begin == o.idx_begin && idx_end == o.idx_end &&
+               chunk_pixels == o.chunk_pixels && chunk_first == o.chunk_first && chunk_step == o.chunk_step && seed == o.seed;
+    }
+};
+// pt_ctx_accumulate's frame key of a checked config (b, e: check_cfg's band)
+AccumKey accum_key(const pt_config *cfg, uint32_t b, uint32_t e);
+
+// The host's side of the frame pt_ctx_accumulate holds between calls (pt_api.hip: HeldFrame adds the device planes) and of a
+// checkpoint of it: `total` pixels of the frame `key` in the call's pixel order, and the samples per pixel each part holds (parts
+// of part_px pixels, cut as pt_ctx_render cuts a call).  na: how many of them went to half A of a noise-tracked frame
+// (pt_ctx_accum_track_noise; half B: cnt - na).  Whether a frame is held, and whether it is tracked, IS whether cnt / na have
+// entries - there are no flags that could disagree with them.
+struct FrameCounts {
+    AccumKey key{};
+    uint32_t total = 0, part_px = 0;
+    std::vector<uint32_t> cnt, na;
+    bool held() const { return !cnt.empty(); }
+    bool tracked() const { return !na.empty(); }
+    bool holds(const AccumKey &k) const { return held() && key == k; }
+    uint32_t n_parts() const { return (uint32_t)cnt.size(); }
+    Part part(uint32_t i) const { return part_extent(total, part_px, i); }
+    uint32_t cnt_min() const { return held() ? *std::min_element(cnt.begin(), cnt.end()) : 0u; }
+    uint32_t cnt_max() const { return held() ? *std::max_element(cnt.begin(), cnt.end()) : 0u; }
+};
+
+// One piece of a frame call: pixels [k0, k0 + n) of the call, samples [s_first, s_end) of each (s_end 0: cfg->spp).  Progress
+// inside it is reported as base + scale * f of the call, and its start is a progress point at `base`.  [part_lo, part_hi): the
+// parts of pt_ctx_accumulate's counts it brings to its last sample.  `boundary`: the fraction reported at its start when that is
+// not `base` (the second job of a part).
+struct Job {
+    uint32_t k0, n, s_first;
+    float base, scale;
+    uint32_t part_lo, part_hi;
+    uint32_t s_end = 0;
+    float boundary = -1.0f;
+};
+// What a pt_ctx_accumulate to `spp` samples renders on the held frame f: each part from its own count; the megakernel, which renders a call at once, takes the whole
+// call in one go when every part holds the same counts.  Progress by pixels.  A noise-tracked frame cuts the samples [cnt, spp)
+// of a part into two jobs at m = cnt + 4 * ceil((spp - cnt) / 8) - the first rounded up to whole groups of the four sub-pixels -
+// so that both halves of the estimate get samples from every call (deal_to_a deals them).
+std::vector<Job> accum_jobs(const FrameCounts &f, uint32_t spp, bool megakernel);
+// A noise-tracked frame deals the samples of a job to the half that holds fewer of them in its part (a tie: to A); cnt, na: the
+// part's counts before the job
+inline bool deal_to_a(uint32_t cnt, uint32_t na) { return na <= cnt - na; }
+
+// ---- checkpoint file (pt_ctx_accum_save / _load, ptrace.h): little-endian, the byte order of every target of this library.
+// What a file says besides its planes: the frame (tracked: version 2, which brings half A; plain: version 1), the fingerprint
+// of its scene, and where its planes of 24 * total bytes lie - the held sums at sums_at, half A's at a_at.
+struct Checkpoint : FrameCounts {
+    uint64_t scene_fp = 0;
+    size_t sums_at = 0, a_at = 0;
+    size_t need = 0;  // kCkptMore: the leading bytes of the file ckpt_decode asks for
+};
+// the file up to its planes (header, counts, half A's counts) appended to b; the planes follow (the held sums, then half A's),
+// then ckpt_seal's hash of everything before it
+void ckpt_encode_head(const Checkpoint &ck, std::vector<uint8_t> &b);
+void ckpt_seal(std::vector<uint8_t> &b);
+enum { kCkptOk = 0, kCkptBad = 1, kCkptMore = 2 };
+// A file of file_size bytes whose first n are at b.  kCkptMore: nothing wrong so far, call again with the first out.need bytes
+// (the header first; the whole file only once its size is the one the header implies); kCkptBad: `why` says what is wrong.
+int ckpt_decode(uint64_t file_size, const uint8_t *b, size_t n, Checkpoint &out, std::string &why);
+
+// ---- the noise estimate's host arithmetic (pt_ctx_accum_noise, pt_ctx_accumulate_until)
+// a part's weight sqrt(nA * nB) / (nA + nB), in binary32 as the header states it
+float noise_part_weight(uint32_t na, uint32_t nb);
+// the upper edge of histogram bin `b` of pt_noise_stats (ptrace.h): the float whose bits are (461 + b) << 21; +inf for the last
+float noise_bin_upper(uint32_t b);
+// the first bin at which the cumulative count reaches ceil(quantile * pixels) (the bin count when none does)
+uint32_t noise_quantile_bin(const pt_noise_stats &s, float quantile);
+// is an estimate within the target: its criteria in use (non-zero mean_error, non-zero quantile), all of them
+bool noise_target_met(const pt_noise_stats &s, const pt_noise_target &t);
 
 }  // namespace host
 }  // namespace pt

@@ -433,3 +433,314 @@ def test_pass_length_follows_the_measured_rate(tmp_path):
     subprocess.check_call(["g++", "-O1", "-std=c++17", "-I", os.path.join(ptlib.PKG, "csrc"), "-I", os.path.join(ptlib.ROOT, "include"),
                            str(src), "-o", exe, "-L", ptlib.PKG, "-lptrace_hip", "-Wl,-rpath," + ptlib.PKG])
     assert subprocess.check_output([exe]).decode().strip() == "OK"
+
+
+def _host_tool(tmp_path, name, source):
+    """a small g++ program over csrc/pt_host.h, linked against the library"""
+    src = tmp_path / (name + ".cpp")
+    src.write_text(source)
+    exe = str(tmp_path / name)
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-I", os.path.join(ptlib.PKG, "csrc"), "-I", os.path.join(ptlib.ROOT, "include"),
+                           str(src), "-o", exe, "-L", ptlib.PKG, "-lptrace_hip", "-Wl,-rpath," + ptlib.PKG])
+    return lambda *args: subprocess.check_output([exe] + [str(a) for a in args]).decode()
+
+
+CKPT_SRC = r"""
+#include <cstdio>
+#include <cstdlib>
+#include <string>
+#include <vector>
+#include "ptrace.h"
+#include "pt_host.h"
+using namespace pt;
+// argv: FILE [N]: decode the file from its first N bytes (default: all of them).  Prints MORE <need> / BAD <reason> / OK and the
+// fields, then whether encoding the decoded fields, the planes at their offsets and the seal gives the file's bytes again.
+int main(int argc, char **argv) {
+    FILE *f = fopen(argv[1], "rb");
+    if (!f) return 2;
+    std::vector<uint8_t> b;
+    uint8_t buf[1 << 16];
+    for (size_t n; (n = fread(buf, 1, sizeof buf, f)) != 0;) b.insert(b.end(), buf, buf + n);
+    fclose(f);
+    const size_t n = argc > 2 ? strtoull(argv[2], 0, 10) : b.size();
+    host::Checkpoint ck;
+    std::string why;
+    const int d = host::ckpt_decode(b.size(), b.data(), n, ck, why);
+    if (d == host::kCkptMore) { printf("MORE %zu\n", ck.need); return 0; }
+    if (d == host::kCkptBad) { printf("BAD %s\n", why.c_str()); return 0; }
+    const host::AccumKey &k = ck.key;
+    printf("OK key %u %u %u %u %u %u %u %llu fp %llu total %u part_px %u tracked %d sums_at %zu a_at %zu cnt", k.width, k.height, k.idx_begin,
+           k.idx_end, k.chunk_pixels, k.chunk_first, k.chunk_step, (unsigned long long)k.seed, (unsigned long long)ck.scene_fp, ck.total,
+           ck.part_px, (int)ck.tracked(), ck.sums_at, ck.a_at);
+    for (uint32_t v : ck.cnt) printf(" %u", v);
+    printf(" na");
+    for (uint32_t v : ck.na) printf(" %u", v);
+    std::vector<uint8_t> again;
+    host::ckpt_encode_head(ck, again);
+    const size_t plane = 24 * (size_t)ck.total;
+    again.insert(again.end(), b.begin() + ck.sums_at, b.begin() + ck.sums_at + plane);
+    if (ck.tracked()) again.insert(again.end(), b.begin() + ck.a_at, b.begin() + ck.a_at + plane);
+    host::ckpt_seal(again);
+    printf(" %s\n", again == b ? "SAME" : "DIFF");
+    return 0;
+}
+"""
+
+
+def _checkpoint(L, key, fp, total, part_px, counts, n_a, sums, a, version=None, seal=True):
+    """a checkpoint file from the layout include/ptrace.h documents; key: (width, height, idx_begin, idx_end, chunk_pixels,
+    chunk_first, chunk_step, seed); n_a / a: None for version 1"""
+    import struct
+    b = b"PTACCUM1" + struct.pack("<I", version or (1 if n_a is None else 2)) + struct.pack("<7IQ", *key) + struct.pack("<Q", fp)
+    b += struct.pack("<3I", total, part_px, len(counts)) + struct.pack("<%dI" % len(counts), *counts)
+    if n_a is not None:
+        b += struct.pack("<%dI" % len(n_a), *n_a)
+    b += sums + (a if a is not None else b"")
+    return b + struct.pack("<Q", L.pt_siphash(1, 3, 0, 0, b, len(b))) if seal else b
+
+
+def test_checkpoint_codec(tmp_path):
+    """host::ckpt_encode_head / ckpt_seal / ckpt_decode against files built here from the documented layout: a plain and a
+    noise-tracked checkpoint (a chunked band; a frame of two parts) decode to their fields and encode to the same bytes again;
+    the header alone is asked for first, the rest only when the size fits; every damaged file is refused with the loader's
+    reason, in the loader's order."""
+    import numpy as np
+    L = ptlib.product()
+    tool = _host_tool(tmp_path, "ckpt", CKPT_SRC)
+
+    def run(data, *n):
+        p = tmp_path / "c.ptacc"
+        p.write_bytes(data)
+        return tool(p, *n).strip()
+
+    planes = lambda total, salt: (np.arange(3 * total, dtype="<u8") * np.uint64(0x9e3779b97f4a7c15) + np.uint64(salt)).tobytes()
+    # version 1: a whole 8x4 frame, one part
+    key1 = (8, 4, 0, 32, 0, 0, 0, 0xfedcba9876543210)
+    v1 = _checkpoint(L, key1, 0x1122334455667788, 32, 32, [12], None, planes(32, 1), None)
+    assert len(v1) == 68 + 4 + 24 * 32 + 8
+    assert run(v1) == "OK key 8 4 0 32 0 0 0 %d fp %d total 32 part_px 32 tracked 0 sums_at 72 a_at %d cnt 12 na SAME" % (
+        key1[7], 0x1122334455667788, 72 + 768)
+    # version 2: chunks 1, 3, 5 of four pixels of the band [4, 28) of that frame: 12 pixels
+    key2 = (8, 4, 4, 28, 4, 1, 2, 7)
+    v2 = _checkpoint(L, key2, 5, 12, 12, [12], [8], planes(12, 2), planes(12, 3))
+    assert run(v2) == "OK key 8 4 4 28 4 1 2 7 fp 5 total 12 part_px 12 tracked 1 sums_at 76 a_at %d cnt 12 na 8 SAME" % (76 + 288)
+    # version 2, a frame of two parts (more than 1.5 Mi pixels: parts of 2^20) at unequal counts
+    total = 1600 * 1000
+    big = _checkpoint(L, (1600, 1000, 0, total, 0, 0, 0, 1), 9, total, 1 << 20, [4, 2], [2, 2], planes(total, 4), planes(total, 5))
+    assert run(big) == "OK key 1600 1000 0 %d 0 0 0 1 fp 9 total %d part_px 1048576 tracked 1 sums_at 84 a_at %d cnt 4 2 na 2 2 SAME" % (
+        total, total, 84 + 24 * total)
+    del big
+    # the loader's two reads: the header, then the whole file - and nothing behind the header when the size does not fit it
+    assert run(v2, 0) == "MORE 68" and run(v2, 68) == "MORE %d" % len(v2) and run(v2, 67) == "MORE 68"
+    assert run(v2[:-10], 68) == "BAD truncated" and run(v2 + b"\0" * 4, 68) == "BAD trailing bytes"
+
+    def resealed(data, at, fmt, value):
+        import struct
+        b = data[:at] + struct.pack(fmt, value) + data[at + struct.calcsize(fmt):-8]
+        return b + struct.pack("<Q", L.pt_siphash(1, 3, 0, 0, b, len(b)))
+
+    flipped = bytearray(v1)
+    flipped[200] ^= 0x10
+    for data, why in ((v1[:-10], "truncated"), (bytes(flipped), "bad trailing hash"), (b"PTACCUM2" + v1[8:], "wrong magic"),
+                      (v1[:40], "too short"), (b"", "too short"), (v1[:75], "too short"),
+                      (resealed(v1, 8, "<I", 3), "unknown format version"), (resealed(v2, 8, "<I", 0), "unknown format version"),
+                      (v1 + b"\0", "trailing bytes"), (v2 + v2[-8:], "trailing bytes"),
+                      (resealed(v1, 68, "<I", (1 << 24) + 1), "a sample count above 2^24"),
+                      (resealed(v2, 72, "<I", 13), "half A holds more samples than the part"),
+                      (resealed(v1, 12, "<I", 0), "the frame key is not a valid frame"),           # width 0
+                      (resealed(v1, 28, "<I", 5), "the frame key is not a valid frame"),           # chunk_pixels without chunk_step
+                      (resealed(v2, 36, "<I", 3), "sizes that do not fit each other"),             # another chunk_step: 8 pixels
+                      (resealed(v1, 60, "<I", 16), "sizes that do not fit each other"),            # part_px
+                      (resealed(v1, 64, "<I", 2), "sizes that do not fit each other")):            # number of parts
+        assert run(data) == "BAD " + why, why
+    assert run(resealed(v1, 68, "<I", 1 << 24)).startswith("OK ") and run(resealed(v2, 72, "<I", 12)).startswith("OK ")
+    # the order of the checks: a wrong magic in a truncated file of an unknown version is a wrong magic, and so on down the list
+    bad_all = resealed(b"PTACCUM2" + v2[8:], 8, "<I", 9)[:-20]
+    assert run(bad_all) == "BAD wrong magic" and run(b"PTACCUM1" + bad_all[8:]) == "BAD unknown format version"
+    assert run(resealed(v2, 72, "<I", 13)[:-20]) == "BAD truncated"
+    bad_hash_and_count = bytearray(resealed(v1, 68, "<I", 1 << 25))
+    bad_hash_and_count[-1] ^= 1
+    assert run(bytes(bad_hash_and_count)) == "BAD bad trailing hash"
+
+
+SCHED_SRC = r"""
+#include <cstdio>
+#include <cstdlib>
+#include <vector>
+#include "ptrace.h"
+#include "pt_host.h"
+using namespace pt;
+// argv: spp megakernel total n_parts cnt.. [na..]: the jobs of one pt_ctx_accumulate call that is not cancelled, in order, with the
+// half each goes to, the counts following as keep_job moves them (pt_api.hip); then the counts at the end
+int main(int argc, char **argv) {
+    const uint32_t spp = (uint32_t)atoi(argv[1]);
+    const bool mega = atoi(argv[2]) != 0;
+    host::FrameCounts f;
+    f.total = (uint32_t)atoi(argv[3]);
+    f.part_px = host::part_pixels(f.total, true);
+    const int n_parts = atoi(argv[4]);
+    if ((uint32_t)n_parts != host::part_count(f.total, f.part_px)) return 2;
+    for (int i = 0; i < n_parts; ++i) f.cnt.push_back((uint32_t)atoi(argv[5 + i]));
+    for (int i = 5 + n_parts; i < argc; ++i) f.na.push_back((uint32_t)atoi(argv[i]));
+    for (const host::Job &j : host::accum_jobs(f, spp, mega)) {
+        const uint32_t end = j.s_end ? j.s_end : spp;
+        if (j.s_first >= end) continue;  // run_frame_call: nothing left to trace here
+        const bool to_a = f.tracked() && host::deal_to_a(f.cnt[j.part_lo], f.na[j.part_lo]);
+        printf("job %u %u %u %u %d %u %u %.9g %.9g %.9g\n", j.k0, j.n, j.s_first, end, (int)to_a, j.part_lo, j.part_hi, j.base, j.scale,
+               j.boundary);
+        for (uint32_t i = j.part_lo; i < j.part_hi; ++i) {
+            if (to_a) f.na[i] += end - j.s_first;
+            f.cnt[i] = end;
+        }
+    }
+    printf("cnt");
+    for (uint32_t v : f.cnt) printf(" %u", v);
+    printf(" na");
+    for (uint32_t v : f.na) printf(" %u", v);
+    printf("\n");
+    return 0;
+}
+"""
+
+
+def test_accumulate_schedule_is_the_deal(tmp_path):
+    """host::accum_jobs and host::deal_to_a - what pt_ctx_accumulate renders and which half keep_job gives it to - against
+    deal(), the header's rule as tests/test_gpu_noise.py restates it: the issue's sequence 0 -> 8 -> 24 -> 64, a part already at
+    the target, an untracked frame, parts of 2^20 pixels, and the megakernel's whole-call job only when every part is even."""
+    import numpy as np
+    from test_gpu_noise import deal
+    tool = _host_tool(tmp_path, "sched", SCHED_SRC)
+    f32 = np.float32
+
+    def call(spp, mega, total, cnt, na=None):
+        lines = tool(spp, int(mega), total, len(cnt), *(list(cnt) + list(na or []))).strip().split("\n")
+        jobs = [ln.split()[1:] for ln in lines[:-1]]
+        end = lines[-1].split()
+        return ([tuple(int(v) for v in j[:7]) + tuple(float(f32(v)) for v in j[7:]) for j in jobs],
+                [int(v) for v in end[1:end.index("na")]], [int(v) for v in end[end.index("na") + 1:]])
+
+    def expect(spp, total, pieces, cnt, na):
+        """pieces: (k0, n, part_lo, part_hi) in order -> the jobs deal() gives them, with their progress fractions"""
+        jobs = []
+        for k0, n, lo, hi in pieces:
+            runs, _ = deal(cnt[lo], na[lo], spp) if na else ([(cnt[lo], spp, False)] if cnt[lo] < spp else [], 0)
+            base, scale = f32(k0) / f32(total), f32(n) / f32(total)
+            f1 = f32(runs[0][1]) / f32(spp) if runs else None
+            for r, (s0, s1, to_a) in enumerate(runs):
+                first = r == 0 and bool(na)  # the first of a tracked part's two jobs: its fractions are scaled to the call's
+                jobs.append((k0, n, s0, s1, int(to_a), lo, hi, float(base), float(scale * f1 if first else scale),
+                             float(base + scale * f1) if r == 1 else -1.0))
+        return jobs
+
+    # the issue's sequence on one part of 96x64, wavefront and megakernel alike
+    total = 96 * 64
+    for mega in (False, True):
+        cnt, na, runs = [0], [0], []
+        for t in (8, 24, 64):
+            jobs, cnt2, na2 = call(t, mega, total, cnt, na)
+            assert jobs == expect(t, total, [(0, total, 0, 1)], cnt, na)
+            assert (cnt2, na2) == ([t], [deal(cnt[0], na[0], t)[1]])
+            runs += [(j[2], j[3], bool(j[4])) for j in jobs]
+            cnt, na = cnt2, na2
+        assert runs == [(0, 4, True), (4, 8, False), (8, 16, True), (16, 24, False), (24, 44, True), (44, 64, False)] and na == [32]
+    # a part already at the target: nothing to render, the counts stay
+    assert call(64, False, total, [64], [32]) == ([], [64], [32])
+    assert call(64, False, total, [64]) == ([], [64], [])
+    # a step of one sample is one job (m = spp); a plain frame is one job per part whatever the step
+    assert call(9, False, total, [8], [4]) == ([(0, total, 8, 9, 1, 0, 1, 0.0, 1.0, -1.0)], [9], [5])
+    assert call(64, False, total, [5]) == ([(0, total, 5, 64, 0, 0, 1, 0.0, 1.0, -1.0)], [64], [])
+    # two parts (2^20 pixels and the rest): the wavefront goes part by part; the megakernel takes the call at once while every
+    # part holds the same counts, and goes part by part when they do not - each part dealt by its own counts
+    total, p0 = 1600 * 1000, 1 << 20
+    parts = [(0, p0, 0, 1), (p0, total - p0, 1, 2)]
+    for mega, cnt, na, pieces in ((False, [8, 8], [4, 4], parts), (True, [8, 8], [4, 4], [(0, total, 0, 2)]),
+                                  (True, [16, 8], [8, 4], parts), (True, [8, 8], [8, 4], parts), (True, [24, 0], [12, 0], parts),
+                                  (True, [8, 8], None, [(0, total, 0, 2)]), (True, [8, 2], None, parts), (False, [8, 8], None, parts)):
+        jobs, cnt2, na2 = call(24, mega, total, cnt, na)
+        assert jobs == expect(24, total, pieces, cnt, na), (mega, cnt, na)
+        assert cnt2 == [24, 24] and na2 == ([deal(c, a, 24)[1] for c, a in zip(cnt, na)] if na else [])
+
+
+NOISE_SRC = r"""
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include "ptrace.h"
+#include "pt_host.h"
+using namespace pt;
+// argv: pixels stats.mean_error target.mean_error target.quantile target.quantile_error [bin count]..: the quantile bin, the bits of
+// its upper edge, whether the target is met
+int main(int argc, char **argv) {
+    if (argv[1][0] == 'w') {  // w nA nB ..: the bits of a part's weight, pair by pair
+        for (int i = 2; i + 1 < argc; i += 2) {
+            const float w = host::noise_part_weight((uint32_t)atoi(argv[i]), (uint32_t)atoi(argv[i + 1]));
+            uint32_t bits;
+            memcpy(&bits, &w, 4);
+            printf("%u\n", bits);
+        }
+        return 0;
+    }
+    pt_noise_stats s{};
+    s.pixels = strtoull(argv[1], 0, 10);
+    s.mean_error = atof(argv[2]);
+    pt_noise_target t{};
+    t.mean_error = (float)atof(argv[3]);
+    t.quantile = (float)atof(argv[4]);
+    t.quantile_error = (float)atof(argv[5]);
+    for (int i = 6; i + 1 < argc; i += 2) s.histogram[atoi(argv[i])] = (uint32_t)atoi(argv[i + 1]);
+    const uint32_t b = host::noise_quantile_bin(s, t.quantile);
+    const float up = host::noise_bin_upper(b);
+    uint32_t bits;
+    memcpy(&bits, &up, 4);
+    printf("%u %u %d\n", b, bits, (int)host::noise_target_met(s, t));
+    return 0;
+}
+"""
+
+
+def test_noise_target_decision(tmp_path):
+    """host::noise_quantile_bin / noise_bin_upper / noise_target_met / noise_part_weight - pt_ctx_accumulate_until's decision
+    and pt_ctx_accum_noise's weights - on hand-made histograms, against tests/noise_ref.py's restatement of the header."""
+    import numpy as np
+    import noise_ref
+    tool = _host_tool(tmp_path, "noise", NOISE_SRC)
+    bits = lambda v: int(np.array([v], dtype=np.float32).view(np.uint32)[0])
+
+    def ask(pixels, hist, mean=0.0, t_mean=0.0, q=0.0, q_err=0.0):
+        flat = [v for kv in sorted(hist.items()) for v in kv]
+        b, up, met = (int(v) for v in tool(pixels, repr(mean), repr(t_mean), repr(q), repr(q_err), *flat).split())
+        if q:
+            full = np.zeros(64, dtype=np.uint32)
+            for k, v in hist.items():
+                full[k] = v
+            assert b == noise_ref.quantile_bin(full, pixels, q) and up == bits(noise_ref.bin_upper(b))
+        return b, bool(met)
+
+    edge = noise_ref.bin_upper  # bin b holds errors below edge(b)
+    # `need` exactly on a bin's cumulative count, and one above it
+    assert ask(100, {3: 10, 7: 40, 20: 50}, q=0.5, q_err=edge(7)) == (7, True)
+    assert ask(100, {3: 10, 7: 39, 20: 51}, q=0.5, q_err=edge(7)) == (20, False)
+    assert ask(100, {3: 10, 7: 39, 20: 51}, q=0.5, q_err=edge(20)) == (20, True)
+    assert ask(100, {3: 10, 7: 40, 20: 50}, q=0.5, q_err=float(np.nextafter(np.float32(edge(7)), np.float32(0)))) == (7, False)
+    # the ceiling is of the DOUBLE product of the binary32 quantile: 0.4f * 100 is a little more than 40
+    assert ask(100, {3: 10, 7: 30, 20: 60}, q=0.4, q_err=1.0) == (20, True)
+    # quantile * pixels below 1 (and at 0 pixels) asks for one pixel
+    assert ask(100, {5: 1, 9: 99}, q=0.001, q_err=edge(5)) == (5, True)
+    assert ask(3, {9: 3}, q=1e-30, q_err=edge(9)) == (9, True)
+    assert ask(0, {}, q=0.5, q_err=3e38) == (64, False)  # no bin reaches it: past the last bin, whose edge is +inf
+    # the last bin's upper edge is +inf: no finite quantile_error is met there
+    assert ask(10, {63: 10}, q=0.9, q_err=3e38) == (63, False) and noise_ref.bin_upper(63) == float("inf")
+    assert ask(10, {62: 10}, q=0.9, q_err=3e38) == (62, True)
+    # mean only, quantile only, both
+    h = {3: 10, 7: 40, 20: 50}
+    assert ask(100, h, mean=0.01, t_mean=0.02)[1] and not ask(100, h, mean=0.03, t_mean=0.02)[1]
+    assert ask(100, h, mean=float(np.float32(0.02)), t_mean=0.02)[1]  # (<=, against the double of the binary32 target)
+    assert not ask(100, h, mean=float("nan"), t_mean=0.02)[1]
+    assert ask(100, h, mean=9.0, q=0.5, q_err=edge(7))[1]  # the mean is not in use
+    assert ask(100, h, mean=0.01, t_mean=0.02, q=0.5, q_err=edge(7))[1]
+    assert not ask(100, h, mean=0.03, t_mean=0.02, q=0.5, q_err=edge(7))[1]
+    assert not ask(100, h, mean=0.01, t_mean=0.02, q=0.5, q_err=edge(6))[1]
+    # a part's weight, every operation in binary32 (rounding a double result once gives other bits for (1, 5), (1, 6), ...)
+    pairs = [(a, b) for a in range(1, 33) for b in range(1, 33)] + [(20, 44), (3, 16777213), (1, 16777215), (8388608, 8388608)]
+    got = [int(v) for v in tool("w", *[n for p in pairs for n in p]).split()]
+    assert got == [bits(noise_ref.weight(a, b)) for a, b in pairs]
