@@ -110,6 +110,29 @@ pub struct PtNoiseTarget {
     pub quantile_error: f32,
     pub min_spp: u32,
 }
+
+// pt_ctx_render_adaptive: a tile (4, 8, 16 or 32 pixels square; 0 = 8) takes no more samples once the mean of its error
+// estimate is at most tile_error; min_spp is the first level (0 = 16)
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct PtAdaptiveParams {
+    pub tile_error: f32,
+    pub tile: u32,
+    pub min_spp: u32,
+}
+
+// what an adaptive frame did: the levels run, the tiles that closed at each, the samples traced
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct PtAdaptiveStats {
+    pub tiles: u32,
+    pub tiles_open: u32,
+    pub levels: u32,
+    pub level_spp: [u32; 32],
+    pub tiles_closed: [u32; 32],
+    pub samples: u64,
+    pub mean_error: f64,
+}
 pub const PT_DENOISE_NO_DEMODULATE: u32 = 1;
 
 pub const PT_OK: i32 = 0;
@@ -198,6 +221,22 @@ extern "C" {
         user: *mut c_void,
         stats: *mut PtStats,
         noise: *mut PtNoiseStats,
+    ) -> i32;
+    // the frame with every tile rendered to its own noise target; cfg.spp is the cap; d_spp (the count per pixel: a GUI's
+    // heat map) and d_error may be null
+    pub fn pt_ctx_render_adaptive(
+        ctx: *mut PtCtx,
+        cfg: *const PtConfig,
+        params: *const PtAdaptiveParams,
+        d_out_rgb: *mut c_void,
+        d_spp: *mut u32,
+        d_error: *mut f32,
+        hip_stream: *mut c_void,
+        cancel: *const u8,
+        cb: Option<PtProgressFn>,
+        user: *mut c_void,
+        stats: *mut PtStats,
+        astats: *mut PtAdaptiveStats,
     ) -> i32;
     // first-hit AOVs of the frame cfg describes (device buffers, any may be null): mean albedo and ray-facing normal over the
     // first cfg.spp samples, sample 0's depth and object id - a denoiser's guides, a pick map

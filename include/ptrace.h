@@ -452,6 +452,63 @@ typedef struct pt_noise_target {
 int pt_ctx_accumulate_until(pt_ctx *ctx, const pt_config *cfg, const pt_noise_target *tgt, void *d_out_rgb, void *hip_stream,
                             const volatile uint8_t *cancel, pt_progress_fn cb, void *user, pt_stats *stats, pt_noise_stats *noise);
 
+/* ---- adaptive sampling: every tile rendered to its own noise target -------------------------------------------------
+ * pt_ctx_accumulate_until doubles the samples of the whole frame until the frame is clean; pt_ctx_render_adaptive does it tile by
+ * tile (the step the paper above is about): a tile whose mean estimate meets the target takes no more samples, the others go on.
+ * Because the RNG is keyed on (seed; pixel, sample) and radiance is summed in u64 fixed point, a pixel that ends with n samples is
+ * pt_ctx_render's pixel at spp = n, bit for bit, whatever its neighbours hold.
+ * - Frame.  cfg as for pt_ctx_render; cfg->spp is the CAP.  The band consists of whole image rows: idx_begin and idx_end are
+ *   multiples of width (0, 0 = the whole frame).  A tile covers `tile` columns by `tile` rows of the band, counted from the band's
+ *   first row and column 0: the pixel with call index k lies in tile row (k / width) / tile and tile column (k % width) / tile.
+ *   Tiles at the right and bottom edges are partial.
+ * - Levels.  n_0 = min_spp rounded up to a multiple of 8, n_(j+1) = min(2 * n_j, cap); a cap below n_0 is the only level.  Every
+ *   open tile holds the same count.  The level that takes the open tiles from c to T traces [c, m) into half A and [m, T) into half
+ *   B, m = min(T, c + 4 * ceil((T - c) / 8)): the rule of a tracked pt_ctx_accumulate call, so an open tile's halves after level j
+ *   are those a tracked frame holds after pt_ctx_accumulate calls at n_0, ..., n_j (nA = the sum of the m - c, nB = T - nA).
+ * - Decision.  After a level every pixel p of an open tile gets e(p) exactly as THE NOISE ESTIMATE defines it (the tiles' nA, nB,
+ *   w on the host).  E = the sum over the tile's pixels of floor(e(p) * 2^28) as unsigned integers in a u64; the tile CLOSES iff
+ *   E <= q * (pixels of the tile inside the frame), q = (uint64) floor((double) tile_error * 2^28) computed on the host.  A
+ *   closed tile is never reopened.  The call ends when no tile is open or the cap is reached.  A level at which nB is 0 (a cap
+ *   below 5) closes nothing and evaluates nothing.
+ * - d_out_rgb (pt_config_pixels(cfg) * 3 floats, device): every pixel resolved over its own tile's count - pt_ctx_render's
+ *   pixel at that count, bit for bit; a count of 0 (a cancel before the first level ended) gives black.
+ * - d_spp (may be NULL; pt_config_pixels(cfg) u32, device): the count of every pixel, in the call's pixel order.
+ * - d_error (may be NULL; pt_config_pixels(cfg) floats, device): e(p) of the tile's last evaluation, +inf where none was made.
+ * - Cancel.  *cancel is read between levels (and after the progress callback made there); inside a level the tile pass runs in
+ *   the time-sized rounds of the megakernel (pt_ctx_render), one level being the unit that is kept: PT_CANCELLED leaves every
+ *   tile at the last count it completed, and the outputs are filled accordingly.
+ * - Progress: the samples traced so far (partial tiles counted whole) over pixels * cap, between levels; 1.0 at the end.
+ * - stats (may be NULL): samples = the sum of the counts = astats->samples; ray_bounces exact; passes = the tile pass's launches.
+ * - astats.  level_spp[j] = n_j and tiles_closed[j] for the `levels` levels run; tiles_open = tiles still open at the end (at the
+ *   cap, or at the cancel); mean_error = (double)(the sum of the tiles' last E) * 2^-28 / (double)pixels, +inf unless every tile
+ *   has been evaluated.
+ * - State.  Scratch lives in the context - the held sums and half A's (48 B per pixel of the call), a count and an E per tile,
+ *   two open-tile lists, and the compact accumulator of the open tiles (24 B per pixel of an open tile) - grows on demand, is
+ *   reused between calls and freed by pt_ctx_destroy.  Every call starts from zero.  It changes no other state of the context:
+ *   not pt_ctx_accumulate's held frame or counts, not the measured pass rates pt_ctx_render uses (its rounds keep a rate of their own).
+ * - PT_ERR_INVALID, refused before any device is touched, checked in this order: NULL cfg, params, d_out_rgb or astats; a
+ *   tile_error that is negative or not finite; a tile other than 0, 4, 8, 16, 32; NULL ctx; no scene; a band that is not whole
+ *   rows; chunk_step > 1 or PT_FLAG_PIPELINES; whatever pt_ctx_render refuses; tiles that hold 2^32 pixels or more.
+ * - backend is ignored: the call has one pass kernel, the megakernel's source compiled for the open-tile list (an item is a
+ *   slot of the list, a pixel of the tile, a part of the level's samples).  PT_FLAG_NO_BVH selects the linear scan. */
+typedef struct pt_adaptive_params {
+    float tile_error;   /* a tile is finished when the mean of e(p) over its pixels <= this; finite, >= 0 */
+    uint32_t tile;      /* tile edge in pixels: 4, 8, 16 or 32; 0 = 8 */
+    uint32_t min_spp;   /* first level; 0 = 16; rounded up to a multiple of 8 */
+} pt_adaptive_params;
+typedef struct pt_adaptive_stats {
+    uint32_t tiles, tiles_open;   /* tiles of the call; tiles that reached the cap (or the cancel) unfinished */
+    uint32_t levels;              /* levels run */
+    uint32_t level_spp[32];       /* samples per pixel a tile holds after level j */
+    uint32_t tiles_closed[32];    /* tiles that finished at level j */
+    uint64_t samples;             /* primary samples traced = sum over pixels of their count */
+    double mean_error;            /* mean of e(p) over all pixels, each at its tile's last evaluation */
+} pt_adaptive_stats;
+int pt_ctx_render_adaptive(pt_ctx *ctx, const pt_config *cfg, const pt_adaptive_params *params,
+                           void *d_out_rgb, uint32_t *d_spp, float *d_error, void *hip_stream,
+                           const volatile uint8_t *cancel, pt_progress_fn cb, void *user,
+                           pt_stats *stats, pt_adaptive_stats *astats);
+
 /* ---- first-hit AOVs: guide buffers for a denoiser, a pick map for a GUI ------------------------------------------
  * pt_ctx_render_aov covers the pixels pt_ctx_render covers with the same cfg - pt_config_pixels(cfg) of them, in the same
  * order (the band [idx_begin, idx_end) and the interleaved chunks included); pixel k of the call has framebuffer index p.

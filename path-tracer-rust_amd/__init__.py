@@ -62,6 +62,15 @@ class pt_noise_target(C.Structure):
     _fields_ = [("mean_error", C.c_float), ("quantile", C.c_float), ("quantile_error", C.c_float), ("min_spp", C.c_uint32)]
 
 
+class pt_adaptive_params(C.Structure):
+    _fields_ = [("tile_error", C.c_float), ("tile", C.c_uint32), ("min_spp", C.c_uint32)]
+
+
+class pt_adaptive_stats(C.Structure):
+    _fields_ = [("tiles", C.c_uint32), ("tiles_open", C.c_uint32), ("levels", C.c_uint32), ("level_spp", C.c_uint32 * 32),
+                ("tiles_closed", C.c_uint32 * 32), ("samples", C.c_uint64), ("mean_error", C.c_double)]
+
+
 PT_DENOISE_NO_DEMODULATE = 1
 PT_OK, PT_ERR_INVALID, PT_ERR_NO_DEVICE, PT_ERR_HIP, PT_CANCELLED = 0, -1, -2, -3, -4
 PT_ERR_IO, PT_ERR_PARSE = -6, -7
@@ -102,6 +111,9 @@ def lib():
     L.pt_ctx_accum_noise.argtypes = [C.c_void_p, C.POINTER(pt_config), C.c_void_p, C.POINTER(pt_noise_stats), C.c_void_p]
     L.pt_ctx_accumulate_until.argtypes = [C.c_void_p, C.POINTER(pt_config), C.POINTER(pt_noise_target), C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(pt_stats), C.POINTER(pt_noise_stats)]
+    L.pt_ctx_render_adaptive.argtypes = [C.c_void_p, C.POINTER(pt_config), C.POINTER(pt_adaptive_params), C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(pt_stats),
+                                         C.POINTER(pt_adaptive_stats)]
     L.pt_ctx_render_aov.argtypes = [C.c_void_p, C.POINTER(pt_config), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p]
     L.pt_denoise_defaults.argtypes = [C.POINTER(pt_denoise_params)]
@@ -277,6 +289,21 @@ class Context:
         _check(lib().pt_ctx_accumulate_until(self._h, C.byref(cfg), C.byref(tgt), C.c_void_p(out_ptr), C.c_void_p(stream or 0),
                                              None, None, None, C.byref(st), C.byref(ns)))
         return st, ns
+
+    def render_adaptive(self, out_ptr, width, height, max_spp, tile_error, tile=0, min_spp=0, seed=1, band=None, spp_map=None,
+                        error=None, no_bvh=False, rays_per_pass=0, stream=None):
+        """The frame with every tile rendered until the mean of its error estimate meets tile_error, max_spp samples per
+        pixel at most (pt_ctx_render_adaptive).  `spp_map` (pixels uint32: the samples each pixel got) and `error` (pixels
+        float32: the estimate) are optional device pointers.  Returns (pt_stats, pt_adaptive_stats)."""
+        cfg = self._config(width, height, max_spp, seed, "megakernel", band, rays_per_pass)
+        if no_bvh:
+            cfg.flags |= PT_FLAG_NO_BVH
+        par = pt_adaptive_params(tile_error, tile, min_spp)
+        st, ast = pt_stats(), pt_adaptive_stats()
+        ptr = lambda p: C.c_void_p(p) if p else None  # noqa: E731
+        _check(lib().pt_ctx_render_adaptive(self._h, C.byref(cfg), C.byref(par), C.c_void_p(out_ptr), ptr(spp_map), ptr(error),
+                                            C.c_void_p(stream or 0), None, None, None, C.byref(st), C.byref(ast)))
+        return st, ast
 
     def accum_reset(self):
         _check(lib().pt_ctx_accum_reset(self._h))

@@ -17,6 +17,7 @@
 #include "pt_host.h"
 #include "pt_kernels.h"
 #include "pt_noise.h"
+#include "pt_tile.h"
 
 namespace pt {
 
@@ -266,6 +267,14 @@ struct pt_ctx {
     DevBuf<NoiseCounters> noise_cnt;
     // pt_ctx_denoise's scratch, kept between calls: the two colour planes and the packed guides, one float4 per pixel each
     DevBuf<float4> dn_u[2], dn_guide;
+    // pt_ctx_render_adaptive's scratch, kept between calls (every call starts it from zero): the held sums and half A's ([3]
+    // planes of the call's pixels each), the compact accumulator of the open tiles, per tile the count and the last E, the two
+    // open-tile lists (this level's, the next one's), the level's counters (u64 [0]: the sum of E at the end; u32 [2], [3]: the
+    // next list's length, the tiles closed), and the rate its own rounds measured (pt_ctx_set_scene forgets it)
+    DevBuf<unsigned long long> ad_held, ad_a, ad_acc, ad_err, ad_cnt, ad_rays;
+    DevBuf<uint32_t> ad_spp, ad_open[2];
+    DevBuf<char> ad_stack;
+    double ad_rate = 0.0;
 };
 
 namespace {
@@ -1211,7 +1220,7 @@ int pt_ctx_set_scene(pt_ctx *c, const pt_camera *cam, const pt_object *objs, uin
             host::mesh_bounding_box(tris + objs[i].tri_offset, objs[i].tri_count, &c->h_boxes[(size_t)12 * i]);
     c->boxes_dirty = true;
     c->has_scene = true;
-    c->pass_rate = c->round_rate = 0.0;  // (another scene: the passes' length is measured again)
+    c->pass_rate = c->round_rate = c->ad_rate = 0.0;  // (another scene: the passes' length is measured again)
     c->pass_rate_kernel = nullptr;
     c->scene_fp = scene_fingerprint(cam, objs, n_objs, tris, n_tris);
     return PT_OK;
@@ -1711,6 +1720,230 @@ int pt_ctx_accumulate_until(pt_ctx *c, const pt_config *cfg, const pt_noise_targ
     if (cb && rc == PT_OK) cb(user, 1.0f);
     if (stats) stats->ms_total = now_ms() - t0;
     return rc;
+}
+
+// One run of a level of pt_ctx_render_adaptive: samples [s_first, s_end) of every open tile into the compact accumulator (zeroed
+// here), in render_mega's time-sized rounds.  The cancel byte is the level loop's business, not the rounds'.
+static int tile_run(pt_ctx *c, const DevScene &S, const LdsLayout &lay, const pt_config *cfg, TileParams F, uint32_t n_open,
+                    uint32_t s_first, uint32_t s_end, hipStream_t st, uint32_t n_cus, pt_stats &stats) {
+    const uint64_t entries = (uint64_t)n_open << (2u * F.tile_shift);
+    F.npix = (uint32_t)entries;
+    int rc;
+    if ((rc = c->ad_acc.ensure(3 * entries))) return rc;
+    HIP_TRY(hipMemsetAsync(c->ad_acc.p, 0, 3 * entries * sizeof(unsigned long long), st));
+    pt_config run = *cfg;
+    run.spp = s_end;
+    const uint32_t spp_left = s_end - s_first;
+    const uint64_t lanes = (uint64_t)n_cus * 2048u;
+    const uint64_t round_budget = cfg->rays_per_pass ? cfg->rays_per_pass : (256ull << 20);  // (as render_mega)
+    uint64_t round_spp64 = round_budget / entries;
+    if (round_spp64 == 0) round_spp64 = 1;
+    if (round_spp64 > spp_left) round_spp64 = spp_left;
+    const uint32_t round_spp = (uint32_t)round_spp64;
+    uint32_t n_split = 1;
+    const uint64_t want_items = (lay.mega_cand ? 8u : 4u) * lanes;
+    while (entries * n_split < want_items && n_split < round_spp) n_split *= 2;
+    if (n_split > round_spp) n_split = round_spp;
+    PassPacer pace(c, &run, st, nullptr, nullptr, nullptr, entries, s_first, round_spp, false, true, c->ad_rate);
+    if ((rc = pace.start())) return rc;
+    while ((rc = pace.next()) == PassPacer::kLaunch) {
+        const uint32_t s0 = pace.s0, s_here = pace.s_here;
+        const uint32_t split = n_split < s_here ? n_split : s_here;
+        const uint32_t lane_spp = (s_here + split - 1) / split;
+        const uint64_t grid64 = (entries * split + kBlock - 1) / kBlock, max_grid = (uint64_t)n_cus * 8u;
+        const uint32_t grid = (uint32_t)(grid64 < max_grid ? grid64 : max_grid);
+        if (lay.mega_cand && (rc = c->ad_stack.ensure(mega_stack_mem_bytes(grid ? grid : 1u)))) return rc;
+        HIP_TRY(hipMemsetAsync(c->ad_rays.p + 7, 0, sizeof(unsigned long long), st));  // the item counter
+        launch_tile_pass(st, grid ? grid : 1u, S, lay, F, c->ad_acc.p, s0, s0 + s_here, lane_spp, split, c->ad_rays.p, c->ad_stack.p);
+        if ((rc = pace.launched())) return rc;
+    }
+    if (rc || (rc = pace.finish())) return rc;
+    if (pace.measured()) c->ad_rate = pace.rate;
+    stats.passes += pace.p;
+    return PT_OK;
+}
+
+int pt_ctx_render_adaptive(pt_ctx *c, const pt_config *cfg, const pt_adaptive_params *params, void *d_out_rgb, uint32_t *d_spp,
+                           float *d_error, void *hip_stream, const volatile uint8_t *cancel, pt_progress_fn cb, void *user,
+                           pt_stats *stats, pt_adaptive_stats *astats) {
+    if (!cfg || !params || !d_out_rgb || !astats) {
+        set_error("NULL argument");
+        return PT_ERR_INVALID;
+    }
+    if (!(params->tile_error >= 0.0f && params->tile_error < __builtin_inff())) {  // (false for a NaN)
+        set_error("adaptive: tile_error must be finite and not negative");
+        return PT_ERR_INVALID;
+    }
+    const uint32_t tile = params->tile ? params->tile : 8u;
+    if (tile != 4u && tile != 8u && tile != 16u && tile != 32u) {
+        set_error("adaptive: tile must be 4, 8, 16 or 32 (0 = 8)");
+        return PT_ERR_INVALID;
+    }
+    if (!c) {
+        set_error("ctx is NULL");
+        return PT_ERR_INVALID;
+    }
+    if (!c->has_scene) {
+        set_error("no scene set");
+        return PT_ERR_INVALID;
+    }
+    if (cfg->width != 0u && (cfg->idx_begin % cfg->width != 0u || cfg->idx_end % cfg->width != 0u)) {
+        set_error("adaptive: the band must consist of whole image rows");
+        return PT_ERR_INVALID;
+    }
+    if (cfg->chunk_step > 1u || ((cfg->flags >> 8) & 15u) != 0u) {
+        set_error("adaptive: chunk_step > 1 and PT_FLAG_PIPELINES are not supported");
+        return PT_ERR_INVALID;
+    }
+    uint32_t ib = 0, ie = 0;
+    int rc = check_cfg(cfg, &ib, &ie);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const double t0 = now_ms();
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    if (stats) memset(stats, 0, sizeof *stats);
+    memset(astats, 0, sizeof *astats);
+    pt_stats ps{};
+    const FrameForm form = form_for(c, cfg->flags);
+    const DevScene &S = form.scene;
+    const LdsLayout lay = lds_layout(S, 1u, c->tune.lds_pad);
+    TileParams F{};
+    static_cast<FrameParams &>(F) = make_frame(c, cfg, ib, ie);
+    F.chunk_step = 0u;
+    const uint32_t npix = ie - ib;
+    TileGrid G{};
+    G.width = cfg->width;
+    G.rows = npix / cfg->width;
+    G.tile_shift = tile == 4u ? 2u : (tile == 8u ? 3u : (tile == 16u ? 4u : 5u));
+    G.tiles_x = (G.width + tile - 1u) / tile;
+    G.tiles = G.tiles_x * ((G.rows + tile - 1u) / tile);
+    if ((uint64_t)G.tiles * tile * tile >= (1ull << 32)) {  // (the compact accumulator is indexed with 32 bits)
+        set_error("adaptive: the band's tiles hold 2^32 pixels or more");
+        return PT_ERR_INVALID;
+    }
+    F.tile_shift = G.tile_shift;
+    F.tiles_x = G.tiles_x;
+    F.rows = G.rows;
+    if ((rc = c->ad_held.ensure(3 * (size_t)npix)) || (rc = c->ad_a.ensure(3 * (size_t)npix)) || (rc = c->ad_err.ensure(G.tiles)) ||
+        (rc = c->ad_spp.ensure(G.tiles)) || (rc = c->ad_open[0].ensure(G.tiles)) || (rc = c->ad_open[1].ensure(G.tiles)) ||
+        (rc = c->ad_cnt.ensure(2)) || (rc = c->ad_rays.ensure(16)))
+        return rc;
+    G.spp = c->ad_spp.p;
+    G.err = c->ad_err.p;
+    hipEvent_t ev0 = get_event(c, 6), ev1 = get_event(c, 7);  // (0..5 are the rounds' pacer's)
+    if (!ev0 || !ev1) {
+        set_error("hipEventCreate failed");
+        return PT_ERR_HIP;
+    }
+    HIP_TRY(hipEventRecord(ev0, st));
+    HIP_TRY(hipMemsetAsync(c->ad_held.p, 0, 3 * (size_t)npix * sizeof(unsigned long long), st));
+    HIP_TRY(hipMemsetAsync(c->ad_a.p, 0, 3 * (size_t)npix * sizeof(unsigned long long), st));
+    HIP_TRY(hipMemsetAsync(c->ad_err.p, 0xff, (size_t)G.tiles * sizeof(unsigned long long), st));  // kTileNoError
+    HIP_TRY(hipMemsetAsync(c->ad_spp.p, 0, (size_t)G.tiles * sizeof(uint32_t), st));
+    HIP_TRY(hipMemsetAsync(c->ad_rays.p, 0, 16 * sizeof(unsigned long long), st));
+    launch_tile_begin(st, d_error, npix, c->ad_open[0].p, G.tiles);
+    struct Clear {  // (the rounds' pacer notes its samples in the live frame: pt_ctx_snapshot finds none afterwards)
+        pt_ctx *c;
+        ~Clear() { c->live = LiveFrame{}; }
+    } clear{c};
+    c->live.cb_last_ms = now_ms();
+    hipDeviceProp_t prop;
+    HIP_TRY(hipGetDeviceProperties(&prop, c->device));
+    const uint32_t cap = cfg->spp;
+    const unsigned long long q = (unsigned long long)__builtin_floor((double)params->tile_error * 268435456.0);
+    uint32_t level = (params->min_spp ? params->min_spp : 16u);
+    level = level > 0xfffffff8u ? cap : (level + 7u) / 8u * 8u;
+    if (level > cap) level = cap;
+    uint32_t have = 0, n_a = 0, n_open = G.tiles, which = 0;
+    uint64_t samples = 0;
+    bool cancelled = false;
+    astats->tiles = G.tiles;
+    for (uint32_t j = 0; n_open != 0u && have < cap && j < 32u; ++j) {
+        cancelled = cancel && *cancel;
+        if (!cancelled && cb && j != 0u && progress(c, cfg, cb, user, (float)((double)samples / ((double)npix * cap))))
+            cancelled = cancel && *cancel;  // raised from inside the callback
+        if (cancelled) break;
+        // [have, m) to half A, [m, level) to half B: the rule of a tracked pt_ctx_accumulate call (ptrace.h)
+        const uint32_t m_a = have + 4u * ((level - have + 7u) / 8u), m = m_a < level ? m_a : level;
+        F.open = c->ad_open[which].p;
+        n_a += m - have;
+        const uint32_t n_b = level - n_a;
+        TileLevel V{};
+        V.open = F.open;
+        V.n_open = n_open;
+        V.spp = level;
+        V.q = q;
+        V.next = c->ad_open[which ^ 1u].p;
+        V.counters = reinterpret_cast<uint32_t *>(c->ad_cnt.p + 1);
+        V.fa = (float)n_a;
+        V.fb = (float)n_b;
+        V.fn = (float)level;
+        V.w = n_b != 0u ? host::noise_part_weight(n_a, n_b) : 0.0f;
+        HIP_TRY(hipMemsetAsync(c->ad_cnt.p + 1, 0, sizeof(unsigned long long), st));
+        for (uint32_t run = 0; run < (m < level ? 2u : 1u); ++run) {
+            const uint32_t r0 = run ? m : have, r1 = run ? level : m;
+            if ((rc = tile_run(c, S, lay, cfg, F, n_open, r0, r1, st, (uint32_t)prop.multiProcessorCount, ps))) return rc;
+            V.acc = c->ad_acc.p;
+            V.to_a = run == 0u ? 1u : 0u;
+            V.evaluate = r1 == level ? 1u : 0u;
+            V.estimate = V.evaluate && n_b != 0u ? 1u : 0u;
+            launch_tile_level(st, G, V, c->ad_held.p, c->ad_a.p, d_error);
+        }
+        HIP_TRY(hipGetLastError());
+        uint32_t back[2] = {0u, 0u};  // the next list's length, the tiles closed: all that comes back per level
+        HIP_TRY(hipMemcpyAsync(back, c->ad_cnt.p + 1, sizeof back, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        // (partial tiles counted whole: this only feeds the progress fraction; the exact total comes from the counts at the end)
+        samples += (uint64_t)n_open * tile * tile * (level - have);
+        if (samples > (uint64_t)npix * cap) samples = (uint64_t)npix * cap;
+        astats->level_spp[j] = level;
+        astats->tiles_closed[j] = back[1];
+        astats->levels = j + 1u;
+        n_open = back[0];
+        which ^= 1u;
+        have = level;
+        level = level > cap / 2u ? cap : level * 2u;
+    }
+    astats->tiles_open = n_open;
+    // the outputs: every pixel over its tile's count, the counts, the sum of E over the tiles
+    HIP_TRY(hipMemsetAsync(c->ad_cnt.p, 0, sizeof(unsigned long long), st));
+    launch_tile_resolve(st, G, c->ad_held.p, (float *)d_out_rgb, d_spp, c->ad_cnt.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ev1, st));
+    unsigned long long err_sum = 0, rays[16] = {0};
+    std::vector<uint32_t> tile_spp(G.tiles);
+    std::vector<unsigned long long> tile_err(G.tiles);
+    HIP_TRY(hipMemcpyAsync(&err_sum, c->ad_cnt.p, sizeof err_sum, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(rays, c->ad_rays.p, sizeof rays, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(tile_spp.data(), c->ad_spp.p, (size_t)G.tiles * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(tile_err.data(), c->ad_err.p, (size_t)G.tiles * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (rays[1]) {
+        set_error("tile pass: a lane's split stack overflowed");
+        return PT_ERR_OVERFLOW;
+    }
+    uint64_t total = 0, est_pixels = 0;
+    for (uint32_t t = 0; t < G.tiles; ++t) {
+        const uint32_t tx = t % G.tiles_x, ty = t / G.tiles_x;
+        const uint32_t w = G.width - tx * tile < tile ? G.width - tx * tile : tile, h = G.rows - ty * tile < tile ? G.rows - ty * tile : tile;
+        total += (uint64_t)w * h * tile_spp[t];
+        if (tile_err[t] != kTileNoError) est_pixels += (uint64_t)w * h;
+    }
+    astats->samples = total;
+    astats->mean_error = est_pixels == (uint64_t)npix ? (double)err_sum * (1.0 / 268435456.0) / (double)npix : (double)__builtin_inff();
+    ps.samples = total;
+    ps.ray_bounces = rays[0];
+    float ms_dev = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&ms_dev, ev0, ev1));
+    ps.ms_device = ms_dev;
+    ps.ms_total = now_ms() - t0;
+    if (stats) *stats = ps;
+    if (cancelled) {
+        set_error("cancelled");
+        return PT_CANCELLED;
+    }
+    if (cb) cb(user, 1.0f);
+    return PT_OK;
 }
 
 int pt_ctx_radiance(pt_ctx *c, const float o[3], const float d[3], uint32_t depth, uint32_t n_samples, uint64_t seed,

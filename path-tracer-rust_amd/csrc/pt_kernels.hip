@@ -9,6 +9,9 @@
 // TWO TRANSLATION UNITS.  This file is compiled twice: as it is (every kernel but the instances of k_pass_cand WITHOUT walks and
 // k_intersect_cand), and through pt_kernels_flat.hip with PT_TU_FLAT defined (those instances alone, five waves per SIMD): the
 // two want different instruction scheduling from the back end, and -mllvm options are per compile (Makefile: MLLVM, MLLVM_FLAT).
+// A THIRD UNIT, pt_kernels_tile.hip (PT_TU_TILE), holds the megakernel's two bodies alone, compiled for TileParams (pt_tile.h) under
+// the names k_tile_mega / k_tile_mega_cand: the tile pass of pt_ctx_render_adaptive.  The text the other two units compile is
+// what it was - the params type of the megakernels is spelled MegaParams, a typedef of FrameParams there.
 // the level-by-level forms (PT_CAND_SCAN=0 / PT_FLAG_NO_BVH / PT_CAND_BVH=0), scenes without BVH meshes:
 //   k_pass                             the whole pass in one launch: per workgroup (= ray stream) the primary rays
 //                                      (render_pixel, mod.rs:812-843), then level by level closest hit
@@ -41,8 +44,22 @@
 #include <string>
 
 #include "pt_kernels.h"
+#ifdef PT_TU_TILE
+#include "pt_tile.h"
+#endif
 
 namespace pt {
+
+#ifdef PT_TU_TILE
+typedef TileParams MegaParams;
+#define k_mega k_tile_mega
+#define k_mega_cand k_tile_mega_cand
+#else
+typedef FrameParams MegaParams;
+#endif
+#if defined(PT_TU_FLAT) || defined(PT_TU_TILE)
+#define PT_TU_PART 1  // a unit that holds a part of this file
+#endif
 
 void set_error(const std::string &m);  // pt_api.hip
 
@@ -99,7 +116,7 @@ __device__ __forceinline__ void load_ray_slice(const StreamSlice &q, uint32_t i,
     word = __float_as_uint(tp.w);
 }
 
-#ifndef PT_TU_FLAT  // (the translation unit of k_pass_cand without walks - pt_kernels_flat.hip - holds nothing else)
+#ifndef PT_TU_PART  // (the units that hold a part of this file - pt_kernels_flat.hip, pt_kernels_tile.hip - do not hold this)
 // ------------------------------------------------------------------------------------------------
 template <bool PROBE>
 __global__ __launch_bounds__(kBlock) void k_generate(FrameParams F, RayQueue q, uint32_t *__restrict__ cnt0,
@@ -203,7 +220,7 @@ __global__ __launch_bounds__(BVH ? kBlockBvh : kBlock, BVH ? 5 : 1) void k_inter
     if (tid == 0) blk_rays[b] += n;
 }
 
-#endif  // PT_TU_FLAT (k_intersect_cand below is the flat unit's too)
+#endif  // PT_TU_PART (k_intersect_cand below is the flat unit's too)
 // ------------------------------------------------------------------------------------------------
 // The stand-alone intersect step with the CANDIDATE SCAN of k_pass_cand (pt_device.h: "Candidate scan"; scenes without BVH
 // meshes): intersect_scene (mod.rs:631-659) for every ray of a stream, as its own kernel - 24 B of ray in, 8 B of hit
@@ -313,7 +330,7 @@ __device__ __forceinline__ void add_radiance_lds(unsigned long long *lds_acc, ui
     if (bl) atomicAdd(&lds_acc[2u * m + slot], (unsigned long long)bl);
 }
 
-#ifndef PT_TU_FLAT
+#ifndef PT_TU_PART
 __global__ __launch_bounds__(kBlock) void k_shade(DevScene S, ShadeParams F, RayQueue qin, RayQueue qout,
                                                   const float2 *__restrict__ hit,
                                                   const uint32_t *__restrict__ cnt_in,
@@ -598,7 +615,7 @@ __global__ __launch_bounds__(kBlock, 6) void k_pass(DevScene S, FrameParams F, R
     }
 }
 
-#endif  // PT_TU_FLAT
+#endif  // PT_TU_PART
 // ------------------------------------------------------------------------------------------------
 // k_pass with the candidate scan (pt_device.h: "Candidate scan") and WITHOUT LEVELS: a ray is FINISHED one chunk after it was
 // started, and the rays that wait for their next bounce live on a stack of the wave (see "THE WAVE'S RAY STACK" in the body).
@@ -1079,7 +1096,7 @@ __global__ __launch_bounds__(kBlock, BVH ? PT_CAND_BVH_WAVES : PT_CAND_WAVES) vo
 #endif
 }
 
-#ifndef PT_TU_FLAT
+#ifndef PT_TU_PART
 // ------------------------------------------------------------------------------------------------
 // k_pass for scenes with a BVH: the same one-launch-per-pass walk of a stream, with the BVH walks of k_intersect<true>:
 // the scan skips them (gates exact, first step of the walk taken from SGPRs), a ray that needs one is parked per wave
@@ -1298,6 +1315,8 @@ __global__ __launch_bounds__(kBlock) void k_scatter_chunks(const float *__restri
     dst[at * 3 + 2] = src[(size_t)p * 3 + 2];
 }
 
+#endif  // PT_TU_PART
+#ifndef PT_TU_FLAT  // (the megakernel: this unit's, and pt_kernels_tile.hip's for its own params type)
 // ------------------------------------------------------------------------------------------------
 // Persistent megakernel: one lane = one (pixel, sample chunk); the lane walks its samples one after the
 // other and each loop trip advances every live path of the wave by one bounce, so the intersect and
@@ -1308,7 +1327,7 @@ __global__ __launch_bounds__(kBlock) void k_scatter_chunks(const float *__restri
 // (Scenes whose candidate records fit LDS run k_mega_cand below instead: the candidate scan, two paths per lane.  This form -
 // every object and triangle per lane - remains for PT_CAND_SCAN=0 / PT_FLAG_NO_BVH and for scenes with too many records.)
 template <bool BVH, bool PROBE>
-__global__ __launch_bounds__(kBlock) void k_mega(DevScene S, FrameParams F, unsigned long long *__restrict__ acc,
+__global__ __launch_bounds__(kBlock) void k_mega(DevScene S, MegaParams F, unsigned long long *__restrict__ acc,
                                                  uint32_t s_begin, uint32_t s_end, uint32_t lane_spp, uint32_t n_split,
                                                  unsigned long long *__restrict__ total_rays) {
     const uint64_t items = (uint64_t)F.npix * n_split;
@@ -1316,7 +1335,11 @@ __global__ __launch_bounds__(kBlock) void k_mega(DevScene S, FrameParams F, unsi
     if (BVH) stage_bvh(S, dyn_lds);
     for (uint64_t first = (uint64_t)blockIdx.x * kBlock; first < items; first += (uint64_t)gridDim.x * kBlock) {
         const uint64_t item = first + threadIdx.x;
+#ifdef PT_TU_TILE  // (an item of a partial tile may name no pixel: such a lane is idle)
+        const bool lane_valid = item < items && global_pixel(F, (uint32_t)(item % F.npix)) != kNoPixel;
+#else
         const bool lane_valid = item < items;
+#endif
         const uint32_t pl = lane_valid ? (uint32_t)(item % F.npix) : 0u;
         const uint32_t part = lane_valid ? (uint32_t)(item / F.npix) : 0u;
         uint32_t s = s_begin + part * lane_spp;
@@ -1432,7 +1455,7 @@ constexpr uint32_t kMegaItemChunk = 32;
 __host__ __device__ inline size_t mega_stack_bytes(uint32_t lanes) { return (size_t)lanes * kMegaStackEntries * 40u; }
 
 template <bool BVH, bool PROBE>
-__global__ __launch_bounds__(kBlock, BVH ? 4 : PT_MEGA_WAVES) void k_mega_cand(DevScene S, FrameParams F, unsigned long long *__restrict__ acc,
+__global__ __launch_bounds__(kBlock, BVH ? 4 : PT_MEGA_WAVES) void k_mega_cand(DevScene S, MegaParams F, unsigned long long *__restrict__ acc,
                                                          uint32_t s_begin, uint32_t s_end, uint32_t lane_spp, uint32_t n_split,
                                                          unsigned long long *__restrict__ total_rays, MegaStack stk, uint32_t spare_off,
                                                          uint32_t n_spare_max, uint32_t surf_off) {
@@ -1549,6 +1572,9 @@ __global__ __launch_bounds__(kBlock, BVH ? 4 : PT_MEGA_WAVES) void k_mega_cand(D
                         s_stop = s_lim < s_end ? s_lim : s_end;
                         if (s > s_stop) s = s_stop;
                         gpix = global_pixel(F, pl);
+#ifdef PT_TU_TILE  // (an item of a partial tile may name no pixel: the lane takes it and traces nothing)
+                        if (gpix == kNoPixel) s_stop = s;
+#endif
                         have_item = true;
                     } else {
                         no_more = true;
@@ -1749,6 +1775,8 @@ __global__ __launch_bounds__(kBlock, BVH ? 4 : PT_MEGA_WAVES) void k_mega_cand(D
     if ((threadIdx.x & 63u) == 0u && rays) atomicAdd(total_rays, rays);
 }
 
+#endif  // PT_TU_FLAT
+#ifndef PT_TU_PART
 // ------------------------------------------------------------------------------------------------
 // single-ray queries (picking / click-debug callers of intersect_scene)
 __global__ __launch_bounds__(kBlock) void k_query(DevScene S, const float *__restrict__ o,
@@ -2015,7 +2043,7 @@ void launch_shade(hipStream_t st, uint32_t K, const DevScene &S, const FramePara
     hipLaunchKernelGGL(k_shade, dim3(K), dim3(kBlock), lds, st, S, P, qin, qout, hit, cnt_in, cnt_out, cap, acc,
                        flags, m);
 }
-#endif  // PT_TU_FLAT
+#endif  // PT_TU_PART
 // k_pass_cand for one pass: the workgroup's LDS (`lds` bytes) is laid out as lds_layout says (pt_layout.h); the instances WITHOUT walks
 // are compiled in a translation unit of their own (pt_kernels_flat.hip: PT_CAND_WAVES waves per SIMD and the instruction
 // scheduling that fits them - the Makefile says which and why), the instances with walks here.
@@ -2065,7 +2093,7 @@ hipError_t launch_pass_cand_flat(hipStream_t st, uint32_t K, const DevScene &S2,
         PT_LAUNCH_CAND(false, false, false, false);
     return hipSuccess;
 }
-#else
+#elif !defined(PT_TU_TILE)
 hipError_t launch_pass(hipStream_t st, uint32_t K, const DevScene &S, const LdsLayout &L, const FrameParams &F, const RayQueue &q0,
                        const RayQueue &q1, uint32_t cap, uint32_t s0, uint32_t s_here, uint32_t m, unsigned long long *acc,
                        unsigned long long *blk_rays, uint32_t *flags) {
@@ -2101,7 +2129,7 @@ hipError_t launch_pass(hipStream_t st, uint32_t K, const DevScene &S, const LdsL
 #endif  // PT_TU_FLAT
 #undef PT_LAUNCH_CAND
 #undef PT_LAUNCH_CAND2
-#ifndef PT_TU_FLAT
+#ifndef PT_TU_PART
 void launch_pass_bvh(hipStream_t st, uint32_t K, const DevScene &S, const FrameParams &F, const RayQueue &q0,
                      const RayQueue &q1, uint32_t cap, uint32_t s0, uint32_t s_here, uint32_t m, unsigned long long *acc,
                      unsigned long long *blk_rays, uint32_t *flags) {
@@ -2177,5 +2205,29 @@ void launch_numerics(hipStream_t st, const float *in, uint32_t n, float *out_sin
                        out_rcp, out_philox);
 }
 
-#endif  // PT_TU_FLAT
+#endif  // PT_TU_PART
+#ifdef PT_TU_TILE
+// one round of the tile pass: launch_mega's choice of form and its arguments, for the open tiles' items (pt_tile.h)
+void launch_tile_pass(hipStream_t st, uint32_t grid, const DevScene &S, const LdsLayout &L, const TileParams &F, unsigned long long *acc,
+                      uint32_t s_begin, uint32_t s_end, uint32_t lane_spp, uint32_t n_split, unsigned long long *total_rays, char *stack_mem) {
+    if (L.mega_cand) {
+        DevScene S2 = S;
+        S2.bvh_in_lds &= ~5u;  // (as launch_mega)
+        MegaStack stk;
+        stk.lanes = grid * kBlock;
+        stk.a = reinterpret_cast<float4 *>(stack_mem);
+        stk.b = stk.a + (size_t)kMegaStackEntries * stk.lanes;
+        stk.c = reinterpret_cast<float2 *>(stk.b + (size_t)kMegaStackEntries * stk.lanes);
+        if (S.n_bvh_nodes != 0u)
+            hipLaunchKernelGGL((k_mega_cand<true, false>), dim3(grid), dim3(kBlock), L.mega_lds, st, S2, F, acc, s_begin, s_end, lane_spp, n_split, total_rays, stk, L.mega_spare_off, L.mega_depth, L.mega_surf_off);
+        else
+            hipLaunchKernelGGL((k_mega_cand<false, false>), dim3(grid), dim3(kBlock), L.mega_lds, st, S2, F, acc, s_begin, s_end, lane_spp, n_split, total_rays, stk, L.mega_spare_off, L.mega_depth, L.mega_surf_off);
+        return;
+    }
+    if (S.n_bvh_nodes != 0u)
+        hipLaunchKernelGGL((k_mega<true, false>), dim3(grid), dim3(kBlock), L.mega_lds, st, S, F, acc, s_begin, s_end, lane_spp, n_split, total_rays);
+    else
+        hipLaunchKernelGGL((k_mega<false, false>), dim3(grid), dim3(kBlock), L.mega_lds, st, S, F, acc, s_begin, s_end, lane_spp, n_split, total_rays);
+}
+#endif  // PT_TU_TILE
 }  // namespace pt

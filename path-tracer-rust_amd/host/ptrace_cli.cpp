@@ -22,6 +22,7 @@ static void usage() {
             "usage: ptrace <samplesPerPixel> <y-resolution> <scene id|index> [--width W] [--backend wavefront|megakernel]\n"
             "              [--seed S] [--gpus N] [--root DIR] [--out DIR] [--no-ppm] [--checkpoint FILE] [--aov N]\n"
             "              [--denoise [N]] [--noise-target X [--noise-map FILE.pfm]]\n"
+            "              [--adaptive X [--tile N] [--spp-map FILE.pfm]]\n"
             "  --checkpoint FILE: continue from the samples FILE holds (if it exists), render up to <samplesPerPixel> in all and\n"
             "                     save them to FILE; one GPU only; the seed defaults to 0 instead of the clock, so that the same\n"
             "                     command continues the same frame\n"
@@ -34,7 +35,11 @@ static void usage() {
             "  --noise-target X: <samplesPerPixel> becomes a cap: render until the frame's mean estimated error (pt_ctx_accum_noise)\n"
             "           is at most X, doubling the samples from 16; prints the samples reached and the error; one GPU only;\n"
             "           with --checkpoint the file keeps the half buffers too (format version 2)\n"
-            "  --noise-map FILE.pfm: with --noise-target, the per-pixel estimate e(p) of the final frame as a 1-channel PFM\n");
+            "  --noise-map FILE.pfm: with --noise-target, the per-pixel estimate e(p) of the final frame as a 1-channel PFM\n"
+            "  --adaptive X: <samplesPerPixel> becomes a cap: every tile (--tile N: 4, 8, 16 or 32 pixels square, default 8) is\n"
+            "           rendered until its mean estimated error is at most X (pt_ctx_render_adaptive); one GPU; not with\n"
+            "           --checkpoint or --noise-target\n"
+            "  --spp-map FILE.pfm: with --adaptive, the samples every pixel got as a 1-channel PFM\n");
 }
 
 static std::vector<std::string> scene_ids(const std::string &root) {
@@ -87,6 +92,59 @@ static int write_noise_map(int dev, pt_ctx *ctx, const pt_config *cfg, const std
         fprintf(stderr, "cannot write the noise map %s: %s\n", path.c_str(), pt_last_error());
     else
         printf("wrote %s\n", path.c_str());
+    return rc;
+}
+
+// --adaptive: every tile to a mean error of at most `target` (negative: not asked for), cfg->spp at most
+struct AdaptiveRun {
+    float target = -1.0f;
+    uint32_t tile = 0;
+    std::string map;  // --spp-map
+};
+
+// --adaptive on one context on one GPU: the frame into img, the counts through pt_write_pfm (one channel)
+static int render_adaptive(const pt_config *cfg, pt_scene *sc, const AdaptiveRun &run, std::vector<float> &img, pt_stats *st) {
+    int dev = 0;
+    if (const char *e = getenv("PT_DEVICE")) dev = atoi(e);
+    uint32_t n_objs = 0, n_tris = 0;
+    const pt_object *objs = pt_scene_objects(sc, &n_objs);
+    const pt_triangle *tris = pt_scene_triangles(sc, &n_tris);
+    const size_t npix = (size_t)cfg->width * cfg->height;
+    pt_ctx *ctx = nullptr;
+    void *d_out = nullptr, *d_spp = nullptr;
+    pt_adaptive_params par;
+    memset(&par, 0, sizeof par);
+    par.tile_error = run.target;
+    par.tile = run.tile;
+    pt_adaptive_stats as;
+    int rc = pt_ctx_create(dev, &ctx);
+    if (!rc) rc = pt_ctx_set_scene(ctx, pt_scene_camera(sc), objs, n_objs, tris, n_tris);
+    if (!rc) rc = pt_device_malloc(dev, npix * 3 * sizeof(float), &d_out);
+    if (!rc && !run.map.empty()) rc = pt_device_malloc(dev, npix * sizeof(uint32_t), &d_spp);
+    if (!rc) rc = pt_ctx_render_adaptive(ctx, cfg, &par, d_out, (uint32_t *)d_spp, nullptr, nullptr, nullptr, progress, nullptr, st, &as);
+    if (!rc) rc = pt_device_download(dev, img.data(), d_out, npix * 3 * sizeof(float));
+    if (!rc) {
+        printf("\nAdaptive, tile error %g: %u of %u tiles finished in %u levels, %.1f samples per pixel on average (cap %u), mean error %.6g\n",
+               (double)run.target, as.tiles - as.tiles_open, as.tiles, as.levels, (double)as.samples / (double)npix, cfg->spp,
+               as.mean_error);
+        fflush(stdout);
+    }
+    if (!rc && d_spp) {
+        std::vector<uint32_t> cnt(npix);
+        std::vector<float> f(npix);
+        rc = pt_device_download(dev, cnt.data(), d_spp, npix * sizeof(uint32_t));
+        for (size_t i = 0; i < npix; ++i) f[i] = (float)cnt[i];
+        if (!rc) rc = pt_write_pfm(run.map.c_str(), f.data(), cfg->width, cfg->height, 1);
+        if (rc) {
+            fprintf(stderr, "cannot write the sample-count map %s: %s\n", run.map.c_str(), pt_last_error());
+            rc = kCliExit;
+        } else {
+            printf("wrote %s\n", run.map.c_str());
+        }
+    }
+    if (d_spp) pt_device_free(dev, d_spp);
+    if (d_out) pt_device_free(dev, d_out);
+    if (ctx) pt_ctx_destroy(ctx);
     return rc;
 }
 
@@ -265,6 +323,7 @@ int main(int argc, char **argv) {
     bool write_ppm = true;
     uint32_t gpus = 1, aov_spp = 0, denoise_spp = 0;
     NoiseRun noise;
+    AdaptiveRun adaptive;
     for (int i = 4; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&]() -> const char * { return i + 1 < argc ? argv[++i] : ""; };
@@ -306,6 +365,23 @@ int main(int argc, char **argv) {
                 return 1;
             }
         }
+        else if (a == "--adaptive") {
+            const char *v = next();
+            char *end = nullptr;
+            adaptive.target = strtof(v, &end);
+            if (end == v || !(adaptive.target >= 0.0f)) {
+                usage();
+                return 1;
+            }
+        }
+        else if (a == "--tile") adaptive.tile = (uint32_t)strtoul(next(), nullptr, 10);
+        else if (a == "--spp-map") {
+            adaptive.map = next();
+            if (adaptive.map.empty()) {
+                usage();
+                return 1;
+            }
+        }
         else if (a == "--denoise") {
             denoise_spp = 16;
             // the count is optional: taken when the next argument is a number
@@ -340,6 +416,19 @@ int main(int argc, char **argv) {
     }
     if (!noise.map.empty() && !(noise.target > 0.0f)) {
         fprintf(stderr, "--noise-map needs --noise-target\n");
+        return 1;
+    }
+    const bool is_adaptive = adaptive.target >= 0.0f;
+    if (is_adaptive && (!checkpoint.empty() || noise.target > 0.0f)) {
+        fprintf(stderr, "--adaptive cannot be combined with --checkpoint or --noise-target\n");
+        return 1;
+    }
+    if (is_adaptive && (gpus > 1 || denoise_spp)) {
+        fprintf(stderr, "--adaptive works with one GPU only and not with --denoise\n");
+        return 1;
+    }
+    if ((!adaptive.map.empty() || adaptive.tile) && !is_adaptive) {
+        fprintf(stderr, "--tile and --spp-map need --adaptive\n");
         return 1;
     }
     if (!checkpoint.empty() && !seed_given) seed = 0;
@@ -388,7 +477,9 @@ int main(int argc, char **argv) {
     std::vector<float> img((size_t)width * res_y * 3, 0.0f);
     pt_stats st;
     DeviceFrame df;
-    if (checkpoint.empty() && !denoise_spp && !(noise.target > 0.0f))
+    if (is_adaptive)
+        rc = render_adaptive(&cfg, sc, adaptive, img, &st);
+    else if (checkpoint.empty() && !denoise_spp && !(noise.target > 0.0f))
         rc = pt_render_multi(&cfg, gpus ? gpus : 1, pt_scene_camera(sc), objs, n_objs, tris, n_tris, img.data(), nullptr,
                              progress, nullptr, &st);
     else
