@@ -77,6 +77,16 @@ pub struct PtStats {
     pub ms_intersect: f64,
 }
 
+// pt_ctx_denoise_var's parameters; a zero field = the library's default (pt_denoise_var_defaults)
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct PtDenoiseVarParams {
+    pub levels: u32,
+    pub sigma_var: f32,
+    pub sigma_depth: f32,
+    pub flags: u32,
+}
+
 // pt_ctx_denoise's parameters; a zero field = the library's default (pt_denoise_defaults)
 #[repr(C)]
 #[derive(Clone, Copy, Default, Debug)]
@@ -258,6 +268,22 @@ extern "C" {
         height: u32,
         params: *const PtDenoiseParams,
         d_color: *const f32,
+        d_albedo: *const f32,
+        d_normal: *const f32,
+        d_depth: *const f32,
+        d_out: *mut f32,
+        hip_stream: *mut c_void,
+    ) -> i32;
+    // the same filter with its colour weight taken from the frame's noise estimate (pt_ctx_accum_noise's or
+    // pt_ctx_render_adaptive's d_error, one f32 per pixel) in place of one sigma_color; params null = defaults
+    pub fn pt_denoise_var_defaults(out: *mut PtDenoiseVarParams) -> i32;
+    pub fn pt_ctx_denoise_var(
+        ctx: *mut PtCtx,
+        width: u32,
+        height: u32,
+        params: *const PtDenoiseVarParams,
+        d_color: *const f32,
+        d_error: *const f32,
         d_albedo: *const f32,
         d_normal: *const f32,
         d_depth: *const f32,

@@ -593,6 +593,56 @@ int pt_ctx_denoise(pt_ctx *ctx, uint32_t width, uint32_t height, const pt_denois
                    const float *d_color, const float *d_albedo, const float *d_normal, const float *d_depth,
                    float *d_out, void *hip_stream);
 
+/* ---- denoising what the frame's own noise estimate says is noise -----------------------------------------------
+ * pt_ctx_denoise_var is pt_ctx_denoise with the fixed sigma_color replaced by a per-pixel variance taken from the frame's
+ * noise estimate e(p): where the two half buffers agree the filter leaves the colour alone (a converged frame comes back
+ * nearly untouched, detail on one surface survives), where they differ it smooths as far as they differ.  The variance is
+ * prefiltered 3x3 and carried from level to level with the squares of the weights used (as SVGF does, Schied et al. 2017).
+ * - Buffers, the aliasing rule (d_out may be d_color), `hip_stream`, blocking, the scratch and its ownership (the same 48 B per
+ *   pixel, shared with pt_ctx_denoise), "no scene is needed" and "changes no other state of the context" are pt_ctx_denoise's.
+ * - d_error: width * height floats in framebuffer order - the map pt_ctx_accum_noise writes for a cfg without a band and
+ *   without chunks, or pt_ctx_render_adaptive's d_error.  +inf marks "no estimate".  It may not alias d_out.
+ * - PT_ERR_INVALID, all refused before any device is touched, checked in this order: params->levels > 8, a sigma that is
+ *   negative or not finite, flag bits other than PT_DENOISE_NO_DEMODULATE, width or height 0, width * height > 2^28, NULL
+ *   d_color, NULL d_error (pt_ctx_denoise is the filter without an estimate), NULL d_out, NULL ctx.  PT_ERR_HIP: a HIP call
+ *   failed.
+ * - pt_denoise_var_defaults fills in the values a zero field (or params == NULL) stands for: levels 5, sigma_var 1,
+ *   sigma_depth 2^-3 (0.125), flags 0.  They were chosen by the CPU study recorded in profiles/denoise_var_cpu_study.json.
+ * - PT_DN_LDS_MAXSTEP selects the form of each level as for pt_ctx_denoise.  Same bytes either way.
+ *
+ * THE ARITHMETIC.  The rules are pt_ctx_denoise's: binary32 + - * / and sqrt, correctly rounded, never contracted, in the
+ * order the parentheses give.  pos, fall, B, hit, N, m_c, wn, xz, sds_i, the order of the taps and the finish are those of
+ * pt_ctx_denoise's contract above, word for word.  Only these things differ:
+ * 1. Prepare, in addition, for every pixel p:
+ *    - ev = error[p] < 12 ? pos(error[p]) : 12  (NaN and +inf give 12, the largest value an estimate can take).
+ *    - d = ev * sqrt(2^-6 + ((color[p][0] + color[p][1]) + color[p][2])): e(p)'s normalisation undone, the weighted L1 half
+ *      difference in colour units.
+ *    - t_c = d / m_c(p) for c = 0, 1, 2; Vraw(p) = (t_0*t_0 + t_1*t_1) + t_2*t_2.
+ * 2. Prefilter, for every pixel p = (x, y): sum = 0, gsum = 0.  For dy = -1..1 (outer loop), dx = -1..1 (inner loop),
+ *    q = (x + dx, y + dy) inside the frame: g = G[|dy|] * G[|dx|] with G = {1/2, 1/4}; sum = sum + Vraw(q) * g;
+ *    gsum = gsum + g.  V_0(p) = sum / gsum.  No guide weights are applied here.
+ * 3. Level i = 0 .. levels-1 with step s = 2^i, for every pixel p:
+ *    - r = 1 / ((kv * V_i(p)) + 2^-20), kv = sigma_var * sigma_var computed on the host in binary32.
+ *    - the colour term of a tap that is not the centre is xc = ((dr*dr + dg*dg) + db*db) * r: constant over the levels, there
+ *      is no 2^-i.  w is as in pt_ctx_denoise.
+ *    - vs = 0 beside sum and wsum.  Every tap that is taken adds vs = vs + V_i(q) * (w * w); the centre adds
+ *      V_i(p) * (h * h); a skipped tap adds nothing.
+ *    - u_{i+1}(p) as in pt_ctx_denoise.  V_{i+1}(p) = vs / (wsum * wsum).
+ * 4. Finish as in pt_ctx_denoise.
+ * 5. Range: for colours in [0, 1] everything stays finite: Vraw <= 3 * (12 * sqrt(3 + 2^-6) * 64)^2.  For colours that are not
+ *    finite the result is unspecified.  The constant 2^-20 and the factor-free Vraw (no 1/3, no 1/n) are deliberate:
+ *    sigma_var absorbs the scale. */
+typedef struct pt_denoise_var_params {
+    uint32_t levels;     /* a-trous levels, step 1, 2, 4, ...; 0 = the default; at most 8 */
+    float sigma_var;     /* 0 = the default; finite, >= 0 */
+    float sigma_depth;   /* 0 = the default; finite, >= 0 */
+    uint32_t flags;      /* PT_DENOISE_NO_DEMODULATE */
+} pt_denoise_var_params;
+int pt_denoise_var_defaults(pt_denoise_var_params *out);
+int pt_ctx_denoise_var(pt_ctx *ctx, uint32_t width, uint32_t height, const pt_denoise_var_params *params,
+                       const float *d_color, const float *d_error, const float *d_albedo, const float *d_normal,
+                       const float *d_depth, float *d_out, void *hip_stream);
+
 /* ---- the one collective of the path: the framebuffer gather over RCCL (xGMI) ---------------------------------
  * One process (or thread) per GPU renders its rows with pt_ctx_render (chunk_first = rank, chunk_step = n_ranks) into
  * device memory; pt_comm_gather_frame then gives EVERY rank the whole frame in device memory: one in-place

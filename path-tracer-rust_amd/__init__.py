@@ -53,6 +53,10 @@ class pt_denoise_params(C.Structure):
                 ("sigma_depth", C.c_float), ("flags", C.c_uint32)]
 
 
+class pt_denoise_var_params(C.Structure):
+    _fields_ = [("levels", C.c_uint32), ("sigma_var", C.c_float), ("sigma_depth", C.c_float), ("flags", C.c_uint32)]
+
+
 class pt_noise_stats(C.Structure):
     _fields_ = [("spp_min", C.c_uint32), ("spp_max", C.c_uint32), ("spp_a_min", C.c_uint32), ("spp_b_min", C.c_uint32),
                 ("pixels", C.c_uint64), ("mean_error", C.c_double), ("histogram", C.c_uint32 * 64)]
@@ -119,6 +123,9 @@ def lib():
     L.pt_denoise_defaults.argtypes = [C.POINTER(pt_denoise_params)]
     L.pt_ctx_denoise.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(pt_denoise_params), C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.pt_denoise_var_defaults.argtypes = [C.POINTER(pt_denoise_var_params)]
+    L.pt_ctx_denoise_var.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(pt_denoise_var_params), C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pt_write_pfm.argtypes = [C.c_char_p, C.POINTER(C.c_float), C.c_uint32, C.c_uint32, C.c_uint32]
     L.pt_ctx_set_profiling.argtypes = [C.c_void_p, C.c_int]
     L.pt_ctx_pass_kernel.argtypes = [C.c_void_p, C.c_uint32]
@@ -265,6 +272,16 @@ class Context:
         _check(lib().pt_ctx_denoise(self._h, width, height, C.byref(p), ptr(color), ptr(albedo), ptr(normal), ptr(depth),
                                     ptr(out), C.c_void_p(stream or 0)))
 
+    def denoise_var(self, width, height, color, error, out, albedo=None, normal=None, depth=None, levels=0, sigma_var=0.0,
+                    sigma_depth=0.0, no_demodulate=False, stream=None):
+        """Denoise a whole width x height frame in device memory as far as its own noise estimate says it needs
+        (pt_ctx_denoise_var): as denoise(), with `error` a device pointer to pixels float32 - what accum_noise(error=...) or
+        render_adaptive(error=...) wrote for the same frame.  levels, sigma_var, sigma_depth: 0 = denoise_var_defaults()."""
+        p = pt_denoise_var_params(levels, sigma_var, sigma_depth, PT_DENOISE_NO_DEMODULATE if no_demodulate else 0)
+        ptr = lambda q: C.c_void_p(q) if q else None  # noqa: E731
+        _check(lib().pt_ctx_denoise_var(self._h, width, height, C.byref(p), ptr(color), ptr(error), ptr(albedo), ptr(normal),
+                                        ptr(depth), ptr(out), C.c_void_p(stream or 0)))
+
     def accum_track_noise(self, on=True):
         """Keep half of every pixel's samples in a second accumulator for the frames started from now on
         (pt_ctx_accum_track_noise), so that accum_noise() / accumulate_until() can estimate the frame's error."""
@@ -386,6 +403,13 @@ def denoise_defaults():
     p = pt_denoise_params()
     _check(lib().pt_denoise_defaults(C.byref(p)))
     return {"levels": p.levels, "sigma_color": p.sigma_color, "sigma_depth": p.sigma_depth}
+
+
+def denoise_var_defaults():
+    """The values pt_ctx_denoise_var uses for a zero field: {"levels", "sigma_var", "sigma_depth"} (pt_denoise_var_defaults)."""
+    p = pt_denoise_var_params()
+    _check(lib().pt_denoise_var_defaults(C.byref(p)))
+    return {"levels": p.levels, "sigma_var": p.sigma_var, "sigma_depth": p.sigma_depth}
 
 
 def build_flags():

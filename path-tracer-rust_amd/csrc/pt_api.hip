@@ -2399,6 +2399,48 @@ int pt_ctx_render_aov(pt_ctx *c, const pt_config *cfg, float *d_albedo, float *d
     return PT_OK;
 }
 
+// pt_ctx_denoise (d_error NULL, sigma = sigma_color) and pt_ctx_denoise_var (sigma = sigma_var) once their arguments are checked
+static int run_denoise(pt_ctx *c, uint32_t width, uint32_t height, uint32_t levels, float sigma, float sigma_depth,
+                       uint32_t flags, const float *d_color, const float *d_error, const float *d_albedo, const float *d_normal,
+                       const float *d_depth, float *d_out, void *hip_stream) {
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t npix = (size_t)width * height;
+    for (int k = 0; k < 2; ++k) {
+        const int rc = c->dn_u[k].ensure(npix);
+        if (rc) return rc;
+    }
+    {
+        const int rc = c->dn_guide.ensure(npix);
+        if (rc) return rc;
+    }
+    DenoiseFrame f{};
+    f.width = width;
+    f.height = height;
+    f.color = d_color;
+    f.albedo = (flags & PT_DENOISE_NO_DEMODULATE) ? nullptr : d_albedo;
+    f.normal = d_normal;
+    f.depth = d_depth;
+    f.error = d_error;
+    f.guide = c->dn_guide.p;
+    f.u[0] = c->dn_u[0].p;
+    f.u[1] = c->dn_u[1].p;
+    f.out = d_out;
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    launch_dn_prepare(st, f);
+    const float kv = sigma * sigma;
+    float scale = 1.0f;  // 2^-i
+    for (uint32_t i = 0; i < levels; ++i, scale *= 0.5f) {
+        const uint32_t s = 1u << i;
+        const float sc = sigma * scale;
+        const float rc = d_error ? kv : 1.0f / (sc * sc);  // with an error map the colour scale is per pixel, from kv
+        const float sds = sigma_depth * (float)s;
+        launch_dn_level(st, f, i, rc, sds, i + 1u == levels, s <= c->tune.dn_lds_maxstep);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    return PT_OK;
+}
+
 // the values a zero field of pt_denoise_params stands for: the minimum of the CPU study (profiles/denoise_cpu_study.json)
 static const pt_denoise_params kDenoiseDefaults = {5u, 2.0f, 0.0f, 0.03125f, 0u};
 
@@ -2454,40 +2496,72 @@ int pt_ctx_denoise(pt_ctx *c, uint32_t width, uint32_t height, const pt_denoise_
         set_error("ctx is NULL");
         return PT_ERR_INVALID;
     }
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t npix = (size_t)width * height;
-    for (int k = 0; k < 2; ++k) {
-        const int rc = c->dn_u[k].ensure(npix);
-        if (rc) return rc;
+    return run_denoise(c, width, height, P.levels, P.sigma_color, P.sigma_depth, P.flags, d_color, nullptr, d_albedo, d_normal,
+                       d_depth, d_out, hip_stream);
+}
+
+// the values a zero field of pt_denoise_var_params stands for: the minimum of the CPU study (profiles/denoise_var_cpu_study.json)
+static const pt_denoise_var_params kDenoiseVarDefaults = {5u, 1.0f, 0.125f, 0u};
+
+int pt_denoise_var_defaults(pt_denoise_var_params *out) {
+    if (!out) {
+        set_error("out is NULL");
+        return PT_ERR_INVALID;
     }
-    {
-        const int rc = c->dn_guide.ensure(npix);
-        if (rc) return rc;
-    }
-    DenoiseFrame f{};
-    f.width = width;
-    f.height = height;
-    f.color = d_color;
-    f.albedo = (P.flags & PT_DENOISE_NO_DEMODULATE) ? nullptr : d_albedo;
-    f.normal = d_normal;
-    f.depth = d_depth;
-    f.guide = c->dn_guide.p;
-    f.u[0] = c->dn_u[0].p;
-    f.u[1] = c->dn_u[1].p;
-    f.out = d_out;
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    launch_dn_prepare(st, f);
-    float scale = 1.0f;  // 2^-i
-    for (uint32_t i = 0; i < P.levels; ++i, scale *= 0.5f) {
-        const uint32_t s = 1u << i;
-        const float sc = P.sigma_color * scale;
-        const float rc = 1.0f / (sc * sc);
-        const float sds = P.sigma_depth * (float)s;
-        launch_dn_level(st, f, i, rc, sds, i + 1u == P.levels, s <= c->tune.dn_lds_maxstep);
-    }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(st));
+    *out = kDenoiseVarDefaults;
     return PT_OK;
+}
+
+int pt_ctx_denoise_var(pt_ctx *c, uint32_t width, uint32_t height, const pt_denoise_var_params *params, const float *d_color,
+                       const float *d_error, const float *d_albedo, const float *d_normal, const float *d_depth, float *d_out,
+                       void *hip_stream) {
+    // everything that can be refused is refused here, before the device is touched
+    pt_denoise_var_params P = kDenoiseVarDefaults;
+    if (params) {
+        auto bad_sigma = [](float v) { return !(v >= 0.0f) || v == __builtin_inff(); };
+        if (params->levels > 8u) {
+            set_error("pt_denoise_var_params.levels exceeds 8");
+            return PT_ERR_INVALID;
+        }
+        if (bad_sigma(params->sigma_var) || bad_sigma(params->sigma_depth)) {
+            set_error("pt_denoise_var_params: a sigma is negative or not finite");
+            return PT_ERR_INVALID;
+        }
+        if (params->flags & ~PT_DENOISE_NO_DEMODULATE) {
+            set_error("pt_denoise_var_params.flags: unknown bits");
+            return PT_ERR_INVALID;
+        }
+        if (params->levels) P.levels = params->levels;
+        if (params->sigma_var != 0.0f) P.sigma_var = params->sigma_var;
+        if (params->sigma_depth != 0.0f) P.sigma_depth = params->sigma_depth;
+        P.flags = params->flags;
+    }
+    if (!width || !height) {
+        set_error("width and height must be positive");
+        return PT_ERR_INVALID;
+    }
+    if ((uint64_t)width * height > (1ull << 28)) {
+        set_error("width*height exceeds 2^28");
+        return PT_ERR_INVALID;
+    }
+    if (!d_color) {
+        set_error("d_color is NULL");
+        return PT_ERR_INVALID;
+    }
+    if (!d_error) {
+        set_error("d_error is NULL: pt_ctx_denoise is the filter without a noise estimate");
+        return PT_ERR_INVALID;
+    }
+    if (!d_out) {
+        set_error("d_out is NULL");
+        return PT_ERR_INVALID;
+    }
+    if (!c) {
+        set_error("ctx is NULL");
+        return PT_ERR_INVALID;
+    }
+    return run_denoise(c, width, height, P.levels, P.sigma_var, P.sigma_depth, P.flags, d_color, d_error, d_albedo, d_normal,
+                       d_depth, d_out, hip_stream);
 }
 
 // one band on one device into the host framebuffer

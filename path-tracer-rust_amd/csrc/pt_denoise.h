@@ -13,16 +13,19 @@ namespace pt {
 struct DenoiseFrame {
     uint32_t width, height;
     const float *color, *albedo, *normal, *depth;  // albedo: NULL also under PT_DENOISE_NO_DEMODULATE
+    const float *error;                            // pt_ctx_denoise_var's noise estimate per pixel; NULL selects pt_ctx_denoise
     float4 *guide;                                 // (N.xyz, depth) per pixel; depth 0 without a depth buffer (every pixel a hit)
-    float4 *u[2];                                  // the colour planes, (r, g, b, unused)
+    float4 *u[2];                                  // the colour planes, (r, g, b, V); V is 0 and unread without `error`
     float *out;
 };
 
-// u[0] and guide from the caller's buffers
+// u[0] and guide from the caller's buffers; with `error` also V_0 into u[0].w (Vraw through u[1].w, then one 3x3 launch)
 void launch_dn_prepare(hipStream_t st, const DenoiseFrame &f);
 // level i: u[i & 1] -> u[(i + 1) & 1], or -> f.out (times m, clamped) when `last`.  rc = 1 / sc_i^2, sds = sigma_depth * 2^i
 // (host binary32).  lds: the workgroup stages its taps in LDS (any step: the tile is dense in x up to step 4, a lattice of
 // the step beyond, and always a lattice in y); otherwise every tap is a global load.  Same results.
+// With `error`, rc is kv = sigma_var^2 and each pixel scales its colour term by 1 / (kv * V(p) + 2^-20); V goes on to the
+// next plane as sum(V(q) w^2) / wsum^2.
 void launch_dn_level(hipStream_t st, const DenoiseFrame &f, uint32_t i, float rc, float sds, bool last, bool lds);
 
 }  // namespace pt

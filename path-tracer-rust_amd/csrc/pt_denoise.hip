@@ -11,6 +11,11 @@
 //           pixels are a lattice of the taps: in y always rows y0 + j*s (12 rows hold all five dy), in x dense up to step 4
 //           (32 + 4s columns) and columns x0 + j*s beyond (36 columns), where a dense halo would not fit any tile.
 // No atomics, no scratch memory, no host round trip between the levels; the last level folds the finish in (times m, clamp).
+//
+// pt_ctx_denoise_var (VAR = true below) is the same filter whose colour weight follows a per-pixel variance V in place of one
+// sigma_color.  V rides in the .w lane of the colour plane, so a tap is still two 16-byte loads and the LDS tile does not
+// grow: prepare derives Vraw from the frame's error map into u[1].w, k_dn_prefilter smooths it 3x3 into u[0].w, and every
+// level carries V on with the squares of the weights it used.  The VAR = false instantiations are pt_ctx_denoise's, unchanged.
 #include "pt_denoise.h"
 
 namespace pt {
@@ -32,9 +37,11 @@ __device__ __forceinline__ float dn_clamp(float v) { return v < 0.0f ? 0.0f : (v
 
 struct DnSum {
     float r, g, b, w;
+    float v;  // VAR only: the sum of V(q) * w^2
 };
 
-// one tap q of pixel p that lies inside the frame and is not the centre
+// one tap q of pixel p that lies inside the frame and is not the centre; rc: 1 / sc_i^2, or with VAR the pixel's own r
+template <bool VAR>
 __device__ __forceinline__ void dn_tap(DnSum &a, float h, const float4 gp, const float4 up, const float4 gq, const float4 uq,
                                        bool has_n, bool has_z, float rc, float sds) {
     const bool hp = gp.w < __builtin_inff(), hq = gq.w < __builtin_inff();
@@ -61,10 +68,12 @@ __device__ __forceinline__ void dn_tap(DnSum &a, float h, const float4 gp, const
     a.g = a.g + uq.y * w;
     a.b = a.b + uq.z * w;
     a.w = a.w + w;
+    if (VAR) a.v = a.v + uq.w * (w * w);
 }
 
 __device__ __forceinline__ float dn_b(int d) { return d == 0 ? 0.375f : ((d == 1 || d == -1) ? 0.25f : 0.0625f); }
 
+template <bool VAR>
 __global__ __launch_bounds__(kDnBlock) void k_dn_prepare(DenoiseFrame f, uint32_t npix) {
     const uint32_t p = blockIdx.x * kDnBlock + threadIdx.x;
     if (p >= npix) return;
@@ -88,11 +97,43 @@ __global__ __launch_bounds__(kDnBlock) void k_dn_prepare(DenoiseFrame f, uint32_
         m2 = a2 > 0.015625f ? a2 : 1.0f;
     }
     f.guide[p] = g;
-    f.u[0][p] = make_float4(f.color[p3] / m0, f.color[p3 + 1] / m1, f.color[p3 + 2] / m2, 0.0f);
+    const float c0 = f.color[p3], c1 = f.color[p3 + 1], c2 = f.color[p3 + 2];
+    f.u[0][p] = make_float4(c0 / m0, c1 / m1, c2 / m2, 0.0f);
+    if (VAR) {
+        // the error map's normalisation undone: the weighted L1 half difference in colour units, then demodulated
+        const float e = f.error[p];
+        const float ev = e < 12.0f ? dn_pos(e) : 12.0f;
+        const float d = ev * __builtin_sqrtf(0.015625f + ((c0 + c1) + c2));
+        const float t0 = d / m0, t1 = d / m1, t2 = d / m2;
+        f.u[1][p].w = (t0 * t0 + t1 * t1) + t2 * t2;
+    }
+}
+
+// V_0 = Vraw under a 3x3 binomial, renormalised at the frame's edge; no guide weights.  u[1].w -> u[0].w
+__global__ __launch_bounds__(kDnBlock) void k_dn_prefilter(DenoiseFrame f) {
+    const int W = (int)f.width, H = (int)f.height;
+    const uint32_t gx = (f.width + kDnTx - 1u) / kDnTx;
+    const int x = (int)((blockIdx.x % gx) * kDnTx + threadIdx.x % kDnTx);
+    const int y = (int)((blockIdx.x / gx) * kDnTy + threadIdx.x / kDnTx);
+    if (x >= W || y >= H) return;
+    float sum = 0.0f, wsum = 0.0f;
+#pragma unroll
+    for (int dy = -1; dy <= 1; ++dy) {
+#pragma unroll
+        for (int dx = -1; dx <= 1; ++dx) {
+            const int qx = x + dx, qy = y + dy;
+            if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
+            const float g = (dy == 0 ? 0.5f : 0.25f) * (dx == 0 ? 0.5f : 0.25f);
+            sum = sum + f.u[1][(size_t)qy * (size_t)W + (size_t)qx].w * g;
+            wsum = wsum + g;
+        }
+    }
+    f.u[0][(size_t)y * (size_t)W + (size_t)x].w = sum / wsum;
 }
 
 // gx: workgroups along x (gridDim.x = gx * workgroups along y: a one-dimensional grid has no 65535 limit)
-template <bool LDS, bool LAST>
+// VAR: rc is kv = sigma_var^2, and the colour term's scale is the pixel's own 1 / (kv * V(p) + 2^-20)
+template <bool LDS, bool LAST, bool VAR>
 __global__ __launch_bounds__(kDnBlock) void k_dn_level(DenoiseFrame f, const float4 *__restrict__ uin, float4 *__restrict__ uout,
                                                        uint32_t s, uint32_t gx, float rc, float sds) {
     __shared__ float4 sg[LDS ? kDnLw * kDnLh : 1];
@@ -137,7 +178,8 @@ __global__ __launch_bounds__(kDnBlock) void k_dn_level(DenoiseFrame f, const flo
     const int lp = (2 + ty) * lw + lc;
     const float4 gp = LDS ? sg[lp] : f.guide[p];
     const float4 up = LDS ? su[lp] : uin[p];
-    DnSum a = {0.0f, 0.0f, 0.0f, 0.0f};
+    DnSum a = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    if (VAR) rc = 1.0f / ((rc * up.w) + 0x1p-20f);
 #pragma unroll
     for (int dy = -2; dy <= 2; ++dy) {
 #pragma unroll
@@ -148,6 +190,7 @@ __global__ __launch_bounds__(kDnBlock) void k_dn_level(DenoiseFrame f, const flo
                 a.g = a.g + up.y * h;
                 a.b = a.b + up.z * h;
                 a.w = a.w + h;
+                if (VAR) a.v = a.v + up.w * (h * h);
                 continue;
             }
             const long long qx = (long long)x + (long long)dx * S, qy = (long long)y + (long long)dy * S;
@@ -162,7 +205,7 @@ __global__ __launch_bounds__(kDnBlock) void k_dn_level(DenoiseFrame f, const flo
                 gq = f.guide[q];
                 uq = uin[q];
             }
-            dn_tap(a, h, gp, up, gq, uq, has_n, has_z, rc, sds);
+            dn_tap<VAR>(a, h, gp, up, gq, uq, has_n, has_z, rc, sds);
         }
     }
     const float r = a.r / a.w, g = a.g / a.w, b = a.b / a.w;
@@ -179,7 +222,7 @@ __global__ __launch_bounds__(kDnBlock) void k_dn_level(DenoiseFrame f, const flo
         f.out[p3 + 1] = dn_clamp(g * m1);
         f.out[p3 + 2] = dn_clamp(b * m2);
     } else {
-        uout[p] = make_float4(r, g, b, 0.0f);
+        uout[p] = make_float4(r, g, b, VAR ? a.v / (a.w * a.w) : 0.0f);
     }
 }
 
@@ -189,10 +232,19 @@ uint32_t ceil_div(uint32_t a, uint32_t b) { return (a + b - 1u) / b; }
 
 void launch_dn_prepare(hipStream_t st, const DenoiseFrame &f) {
     const uint32_t npix = f.width * f.height;
-    hipLaunchKernelGGL(k_dn_prepare, dim3(ceil_div(npix, kDnBlock)), dim3(kDnBlock), 0, st, f, npix);
+    const dim3 grid(ceil_div(npix, kDnBlock)), block(kDnBlock);
+    if (f.error) {
+        hipLaunchKernelGGL(k_dn_prepare<true>, grid, block, 0, st, f, npix);
+        hipLaunchKernelGGL(k_dn_prefilter, dim3(ceil_div(f.width, kDnTx) * ceil_div(f.height, kDnTy)), block, 0, st, f);
+    } else {
+        hipLaunchKernelGGL(k_dn_prepare<false>, grid, block, 0, st, f, npix);
+    }
 }
 
-void launch_dn_level(hipStream_t st, const DenoiseFrame &f, uint32_t i, float rc, float sds, bool last, bool lds) {
+namespace {
+
+template <bool VAR>
+void launch_level(hipStream_t st, const DenoiseFrame &f, uint32_t i, float rc, float sds, bool last, bool lds) {
     const uint32_t s = 1u << i;
     const float4 *uin = f.u[i & 1u];
     float4 *uout = f.u[(i + 1u) & 1u];
@@ -210,15 +262,24 @@ void launch_dn_level(hipStream_t st, const DenoiseFrame &f, uint32_t i, float rc
     const dim3 grid(gx * gy), block(kDnBlock);
     if (lds) {
         if (last)
-            hipLaunchKernelGGL((k_dn_level<true, true>), grid, block, 0, st, f, uin, uout, s, gx, rc, sds);
+            hipLaunchKernelGGL((k_dn_level<true, true, VAR>), grid, block, 0, st, f, uin, uout, s, gx, rc, sds);
         else
-            hipLaunchKernelGGL((k_dn_level<true, false>), grid, block, 0, st, f, uin, uout, s, gx, rc, sds);
+            hipLaunchKernelGGL((k_dn_level<true, false, VAR>), grid, block, 0, st, f, uin, uout, s, gx, rc, sds);
     } else {
         if (last)
-            hipLaunchKernelGGL((k_dn_level<false, true>), grid, block, 0, st, f, uin, uout, s, gx, rc, sds);
+            hipLaunchKernelGGL((k_dn_level<false, true, VAR>), grid, block, 0, st, f, uin, uout, s, gx, rc, sds);
         else
-            hipLaunchKernelGGL((k_dn_level<false, false>), grid, block, 0, st, f, uin, uout, s, gx, rc, sds);
+            hipLaunchKernelGGL((k_dn_level<false, false, VAR>), grid, block, 0, st, f, uin, uout, s, gx, rc, sds);
     }
+}
+
+}  // namespace
+
+void launch_dn_level(hipStream_t st, const DenoiseFrame &f, uint32_t i, float rc, float sds, bool last, bool lds) {
+    if (f.error)
+        launch_level<true>(st, f, i, rc, sds, last, lds);
+    else
+        launch_level<false>(st, f, i, rc, sds, last, lds);
 }
 
 }  // namespace pt

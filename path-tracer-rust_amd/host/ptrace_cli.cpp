@@ -22,7 +22,7 @@ static void usage() {
             "usage: ptrace <samplesPerPixel> <y-resolution> <scene id|index> [--width W] [--backend wavefront|megakernel]\n"
             "              [--seed S] [--gpus N] [--root DIR] [--out DIR] [--no-ppm] [--checkpoint FILE] [--aov N]\n"
             "              [--denoise [N]] [--noise-target X [--noise-map FILE.pfm]]\n"
-            "              [--adaptive X [--tile N] [--spp-map FILE.pfm]]\n"
+            "              [--adaptive X [--tile N] [--spp-map FILE.pfm] [--error-map FILE.pfm]] [--denoise-var [N]]\n"
             "  --checkpoint FILE: continue from the samples FILE holds (if it exists), render up to <samplesPerPixel> in all and\n"
             "                     save them to FILE; one GPU only; the seed defaults to 0 instead of the clock, so that the same\n"
             "                     command continues the same frame\n"
@@ -39,7 +39,11 @@ static void usage() {
             "  --adaptive X: <samplesPerPixel> becomes a cap: every tile (--tile N: 4, 8, 16 or 32 pixels square, default 8) is\n"
             "           rendered until its mean estimated error is at most X (pt_ctx_render_adaptive); one GPU; not with\n"
             "           --checkpoint or --noise-target\n"
-            "  --spp-map FILE.pfm: with --adaptive, the samples every pixel got as a 1-channel PFM\n");
+            "  --spp-map FILE.pfm: with --adaptive, the samples every pixel got as a 1-channel PFM\n"
+            "  --error-map FILE.pfm: with --adaptive, the estimate e(p) every pixel ended with (+inf: none) as a 1-channel PFM\n"
+            "  --denoise-var [N]: with --noise-target or --adaptive: after the frame, denoise it on the GPU as far as its own noise\n"
+            "           estimate says (pt_ctx_denoise_var, default parameters), guides and files as for --denoise; one GPU only;\n"
+            "           not with --denoise\n");
 }
 
 static std::vector<std::string> scene_ids(const std::string &root) {
@@ -62,11 +66,13 @@ static void progress(void *, float f) {
 
 constexpr int kCliExit = 1000;  // render_on_context: the message is out, exit 1
 
-// a frame that stays on its GPU after the render (--denoise filters it there)
+// a frame that stays on its GPU after the render (--denoise and --denoise-var filter it there)
 struct DeviceFrame {
     int dev = 0;
     pt_ctx *ctx = nullptr;
     void *d_out = nullptr;
+    bool want_error = false;  // --denoise-var: keep the frame's estimate e(p) too
+    void *d_error = nullptr;
 };
 
 // --noise-target: render to a mean error of at most `target` (0: not asked for), cfg->spp at most; *spp_reached = the samples
@@ -99,11 +105,14 @@ static int write_noise_map(int dev, pt_ctx *ctx, const pt_config *cfg, const std
 struct AdaptiveRun {
     float target = -1.0f;
     uint32_t tile = 0;
-    std::string map;  // --spp-map
+    std::string map;        // --spp-map
+    std::string error_map;  // --error-map
 };
 
-// --adaptive on one context on one GPU: the frame into img, the counts through pt_write_pfm (one channel)
-static int render_adaptive(const pt_config *cfg, pt_scene *sc, const AdaptiveRun &run, std::vector<float> &img, pt_stats *st) {
+// --adaptive on one context on one GPU: the frame into img, the counts and the estimate through pt_write_pfm (one channel).
+// `keep` takes the context, the device frame and its estimate instead of their being freed.
+static int render_adaptive(const pt_config *cfg, pt_scene *sc, const AdaptiveRun &run, std::vector<float> &img, pt_stats *st,
+                           DeviceFrame *keep) {
     int dev = 0;
     if (const char *e = getenv("PT_DEVICE")) dev = atoi(e);
     uint32_t n_objs = 0, n_tris = 0;
@@ -111,7 +120,7 @@ static int render_adaptive(const pt_config *cfg, pt_scene *sc, const AdaptiveRun
     const pt_triangle *tris = pt_scene_triangles(sc, &n_tris);
     const size_t npix = (size_t)cfg->width * cfg->height;
     pt_ctx *ctx = nullptr;
-    void *d_out = nullptr, *d_spp = nullptr;
+    void *d_out = nullptr, *d_spp = nullptr, *d_err = nullptr;
     pt_adaptive_params par;
     memset(&par, 0, sizeof par);
     par.tile_error = run.target;
@@ -121,7 +130,10 @@ static int render_adaptive(const pt_config *cfg, pt_scene *sc, const AdaptiveRun
     if (!rc) rc = pt_ctx_set_scene(ctx, pt_scene_camera(sc), objs, n_objs, tris, n_tris);
     if (!rc) rc = pt_device_malloc(dev, npix * 3 * sizeof(float), &d_out);
     if (!rc && !run.map.empty()) rc = pt_device_malloc(dev, npix * sizeof(uint32_t), &d_spp);
-    if (!rc) rc = pt_ctx_render_adaptive(ctx, cfg, &par, d_out, (uint32_t *)d_spp, nullptr, nullptr, nullptr, progress, nullptr, st, &as);
+    if (!rc && (keep || !run.error_map.empty())) rc = pt_device_malloc(dev, npix * sizeof(float), &d_err);
+    if (!rc)
+        rc = pt_ctx_render_adaptive(ctx, cfg, &par, d_out, (uint32_t *)d_spp, (float *)d_err, nullptr, nullptr, progress, nullptr, st,
+                                    &as);
     if (!rc) rc = pt_device_download(dev, img.data(), d_out, npix * 3 * sizeof(float));
     if (!rc) {
         printf("\nAdaptive, tile error %g: %u of %u tiles finished in %u levels, %.1f samples per pixel on average (cap %u), mean error %.6g\n",
@@ -142,7 +154,26 @@ static int render_adaptive(const pt_config *cfg, pt_scene *sc, const AdaptiveRun
             printf("wrote %s\n", run.map.c_str());
         }
     }
+    if (!rc && !run.error_map.empty()) {
+        std::vector<float> err(npix);
+        rc = pt_device_download(dev, err.data(), d_err, npix * sizeof(float));
+        if (!rc) rc = pt_write_pfm(run.error_map.c_str(), err.data(), cfg->width, cfg->height, 1);
+        if (rc) {
+            fprintf(stderr, "cannot write the error map %s: %s\n", run.error_map.c_str(), pt_last_error());
+            rc = kCliExit;
+        } else {
+            printf("wrote %s\n", run.error_map.c_str());
+        }
+    }
     if (d_spp) pt_device_free(dev, d_spp);
+    if (!rc && keep) {
+        keep->dev = dev;
+        keep->ctx = ctx;
+        keep->d_out = d_out;
+        keep->d_error = d_err;
+        return rc;
+    }
+    if (d_err) pt_device_free(dev, d_err);
     if (d_out) pt_device_free(dev, d_out);
     if (ctx) pt_ctx_destroy(ctx);
     return rc;
@@ -215,19 +246,27 @@ static int render_on_context(const pt_config *cfg, pt_scene *sc, const std::stri
         rc = pt_ctx_accum_save(ctx, file.c_str());
         if (rc) fprintf(stderr, "cannot save checkpoint %s: %s\n", file.c_str(), pt_last_error());
     }
+    void *d_err = nullptr;
+    if (!rc && keep && keep->want_error) {  // the held frame's e(p), where --noise-map's comes from
+        pt_noise_stats ns;
+        rc = pt_device_malloc(dev, (img.size() / 3) * sizeof(float), &d_err);
+        if (!rc) rc = pt_ctx_accum_noise(ctx, cfg, (float *)d_err, &ns, nullptr);
+    }
     if (!rc && keep) {
         keep->dev = dev;
         keep->ctx = ctx;
         keep->d_out = d_out;
+        keep->d_error = d_err;
         return rc;
     }
+    if (d_err) pt_device_free(dev, d_err);
     if (d_out) pt_device_free(dev, d_out);
     if (ctx) pt_ctx_destroy(ctx);
     return rc;
 }
 
-// --denoise: first-hit guides over the frame's first `spp` samples, pt_ctx_denoise in place on the device frame, and the two
-// files at `stem`
+// --denoise / --denoise-var: first-hit guides over the frame's first `spp` samples, pt_ctx_denoise - or, with the frame's
+// estimate, pt_ctx_denoise_var - in place on the device frame, and the two files at `stem`
 static int write_denoised(const pt_config *frame, uint32_t spp, const DeviceFrame &df, const std::string &stem, const char *scene_id) {
     pt_config cfg = *frame;
     cfg.spp = spp;
@@ -238,7 +277,10 @@ static int write_denoised(const pt_config *frame, uint32_t spp, const DeviceFram
     if (!rc) {
         float *d_albedo = (float *)d_buf, *d_normal = d_albedo + npix * 3, *d_depth = d_normal + npix * 3;
         rc = pt_ctx_render_aov(df.ctx, &cfg, d_albedo, d_normal, d_depth, nullptr, nullptr);
-        if (!rc)
+        if (!rc && df.d_error)
+            rc = pt_ctx_denoise_var(df.ctx, cfg.width, cfg.height, nullptr, (const float *)df.d_out, (const float *)df.d_error,
+                                    d_albedo, d_normal, d_depth, (float *)df.d_out, nullptr);
+        else if (!rc)
             rc = pt_ctx_denoise(df.ctx, cfg.width, cfg.height, nullptr, (const float *)df.d_out, d_albedo, d_normal, d_depth,
                                 (float *)df.d_out, nullptr);
         if (!rc) rc = pt_device_download(df.dev, img.data(), df.d_out, npix * 3 * sizeof(float));
@@ -321,7 +363,7 @@ int main(int argc, char **argv) {
     bool seed_given = false;
     std::string checkpoint;
     bool write_ppm = true;
-    uint32_t gpus = 1, aov_spp = 0, denoise_spp = 0;
+    uint32_t gpus = 1, aov_spp = 0, denoise_spp = 0, denoise_var_spp = 0;
     NoiseRun noise;
     AdaptiveRun adaptive;
     for (int i = 4; i < argc; ++i) {
@@ -382,6 +424,23 @@ int main(int argc, char **argv) {
                 return 1;
             }
         }
+        else if (a == "--error-map") {
+            adaptive.error_map = next();
+            if (adaptive.error_map.empty()) {
+                usage();
+                return 1;
+            }
+        }
+        else if (a == "--denoise-var") {
+            denoise_var_spp = 16;
+            if (i + 1 < argc && argv[i + 1][0] != '\0' && strspn(argv[i + 1], "0123456789") == strlen(argv[i + 1])) {
+                denoise_var_spp = (uint32_t)strtoul(argv[++i], nullptr, 10);
+                if (!denoise_var_spp) {
+                    fprintf(stderr, "--denoise-var needs a positive number of guide samples\n");
+                    return 1;
+                }
+            }
+        }
         else if (a == "--denoise") {
             denoise_spp = 16;
             // the count is optional: taken when the next argument is a number
@@ -431,6 +490,18 @@ int main(int argc, char **argv) {
         fprintf(stderr, "--tile and --spp-map need --adaptive\n");
         return 1;
     }
+    if (!adaptive.error_map.empty() && !is_adaptive) {
+        fprintf(stderr, "--error-map needs --adaptive\n");
+        return 1;
+    }
+    if (denoise_var_spp && denoise_spp) {
+        fprintf(stderr, "--denoise-var cannot be combined with --denoise\n");
+        return 1;
+    }
+    if (denoise_var_spp && !is_adaptive && !(noise.target > 0.0f)) {
+        fprintf(stderr, "--denoise-var needs a frame with a noise estimate: --noise-target or --adaptive\n");
+        return 1;
+    }
     if (!checkpoint.empty() && !seed_given) seed = 0;
     // load_scene_ids (scenes.rs:28-38): a scenes/ directory without any *.json is filled with the built-in scenes
     if (scene_ids(root).empty()) {
@@ -477,16 +548,18 @@ int main(int argc, char **argv) {
     std::vector<float> img((size_t)width * res_y * 3, 0.0f);
     pt_stats st;
     DeviceFrame df;
+    df.want_error = denoise_var_spp != 0;
     if (is_adaptive)
-        rc = render_adaptive(&cfg, sc, adaptive, img, &st);
+        rc = render_adaptive(&cfg, sc, adaptive, img, &st, denoise_var_spp ? &df : nullptr);
     else if (checkpoint.empty() && !denoise_spp && !(noise.target > 0.0f))
         rc = pt_render_multi(&cfg, gpus ? gpus : 1, pt_scene_camera(sc), objs, n_objs, tris, n_tris, img.data(), nullptr,
                              progress, nullptr, &st);
     else
-        rc = render_on_context(&cfg, sc, checkpoint, img, &st, denoise_spp ? &df : nullptr, &noise);
+        rc = render_on_context(&cfg, sc, checkpoint, img, &st, denoise_spp || denoise_var_spp ? &df : nullptr, &noise);
     const uint32_t spp_out = noise.target > 0.0f && !rc ? noise.spp_reached : spp;  // the samples the frame holds
     cfg.spp = spp_out;
     auto release = [&]() {
+        if (df.d_error) pt_device_free(df.dev, df.d_error);
         if (df.d_out) pt_device_free(df.dev, df.d_out);
         if (df.ctx) pt_ctx_destroy(df.ctx);
         pt_scene_free(sc);
@@ -511,7 +584,7 @@ int main(int argc, char **argv) {
     strftime(stamp, sizeof stamp, "%Y-%m-%d_%H:%M:%S", localtime(&now));
     const std::string stem = out_dir + "/" + stamp + "-scene-" + pt_scene_id(sc) + "-spp" + std::to_string(spp_out) + "-res" +
                              std::to_string(res_y) + "-";
-    if (write_ppm || aov_spp || denoise_spp) mkdir(out_dir.c_str(), 0755);  // create_dir_all("out"), mod.rs:1032
+    if (write_ppm || aov_spp || denoise_spp || denoise_var_spp) mkdir(out_dir.c_str(), 0755);  // create_dir_all("out"), mod.rs:1032
     if (write_ppm) {
         const std::string path = stem + ".ppm";
         rc = pt_write_ppm(path.c_str(), img.data(), width, res_y, spp_out, pt_scene_id(sc), (uint64_t)(st.ms_total / 1000.0));
@@ -529,7 +602,8 @@ int main(int argc, char **argv) {
         release();
         return 3;
     }
-    if (denoise_spp && write_denoised(&cfg, denoise_spp, df, stem, pt_scene_id(sc))) {
+    if ((denoise_spp || denoise_var_spp) &&
+        write_denoised(&cfg, denoise_spp ? denoise_spp : denoise_var_spp, df, stem, pt_scene_id(sc))) {
         release();
         return 3;
     }

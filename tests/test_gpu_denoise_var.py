@@ -1,0 +1,524 @@
+"""pt_ctx_denoise_var on the GPU against tests/denoise_var_ref.py, the numpy binary32 restatement of the contract in
+include/ptrace.h.  Every comparison with the restatement is of bytes.  The frames are the device's own: a noise-tracked
+pt_ctx_accumulate frame at 16 samples, its pt_ctx_accum_noise map and pt_ctx_render_aov guides at 4, downloaded and handed to
+the restatement; or pt_ctx_render_adaptive's frame and d_error.  Quality is measured on the device's frames with the bounds of
+tests/test_denoise_var_abi.py (the CPU study, profiles/denoise_var_cpu_study.json).
+No device was available when this file was written: it has been collected and its helpers exercised, not run on a GPU; the
+quality test prints its four ratios for DESIGN.md section 4, which has none yet."""
+import ctypes as C
+import hashlib
+import importlib
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import denoise_ref
+import denoise_var_ref as ref
+import ptlib
+from denoise_ref import PtDenoiseParams
+from denoise_var_ref import F32, NO_DEMODULATE, PtDenoiseVarParams
+from ptlib import PtConfig, PtStats
+from test_adaptive_abi import PtAdaptiveParams, PtAdaptiveStats, bind as bind_adaptive
+from test_gpu_aov import cfg_of, pfm_to_framebuffer, read_pfm, scene
+from test_noise_abi import PtNoiseStats, bind as bind_noise
+
+pytestmark = pytest.mark.gpu
+
+PT_ERR_INVALID = -1
+SEED = 8
+SIZES = ((64, 40), (67, 41), (5, 3), (1, 1), (300, 7))
+NON_DEFAULT = (0.6, 0.4)  # (sigma_var, sigma_depth)
+STUDY = json.load(open(os.path.join(ptlib.ROOT, "profiles", "denoise_var_cpu_study.json")))
+BUFS = (("color", 3), ("error", 1), ("albedo", 3), ("normal", 3), ("depth", 1), ("out", 3))
+
+
+def _bind(L):
+    ref.bind(L)
+    denoise_ref.bind(L)
+    bind_adaptive(bind_noise(L))
+    L.pt_ctx_render_aov.argtypes = [C.c_void_p, C.POINTER(PtConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p]
+    L.pt_ctx_accumulate.argtypes = [C.c_void_p, C.POINTER(PtConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.POINTER(PtStats)]
+    L.pt_ctx_accum_info.argtypes = [C.c_void_p, C.POINTER(PtConfig), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.pt_ctx_accum_reset.argtypes = [C.c_void_p]
+    L.pt_last_error.restype = C.c_char_p
+    return L
+
+
+def hip_runtime():
+    """the HIP runtime the product is bound to: the copy already mapped into this process that is not torch's"""
+    paths = {line.split()[-1] for line in open("/proc/self/maps") if "/libamdhip64.so" in line}
+    own = sorted(p for p in paths if "/torch/" not in p)
+    assert own, "libptrace_hip.so has not mapped a HIP runtime: %r" % sorted(paths)
+    hip = C.CDLL(own[0])
+    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    return hip
+
+
+class Frame:
+    """One noise-tracking context and the device buffers of one frame size: color, error, albedo, normal, depth, out."""
+
+    def __init__(self, L, sc, npix_max):
+        self.L = L
+        self.ctx = C.c_void_p()
+        assert L.pt_ctx_create(0, C.byref(self.ctx)) == 0, L.pt_last_error()
+        assert L.pt_ctx_set_scene(self.ctx, C.byref(sc.cam), sc.objs, sc.n_objs, sc.tris, sc.n_tris) == 0, L.pt_last_error()
+        assert L.pt_ctx_accum_track_noise(self.ctx, 1) == 0, L.pt_last_error()
+        self.bufs = {}
+        for name, k in BUFS:
+            p = C.c_void_p()
+            assert L.pt_device_malloc(0, npix_max * k * 4, C.byref(p)) == 0, L.pt_last_error()
+            self.bufs[name] = p
+
+    def get(self, name, npix):
+        k = dict(BUFS)[name]
+        host = np.zeros(npix * k, dtype=F32)
+        assert self.L.pt_device_download(0, host.ctypes.data_as(C.c_void_p), self.bufs[name], host.nbytes) == 0
+        return host.reshape(npix, 3) if k == 3 else host
+
+    def put(self, name, host):
+        host = np.ascontiguousarray(host, dtype=F32)
+        assert hip_runtime().hipMemcpy(self.bufs[name], host.ctypes.data_as(C.c_void_p), host.nbytes, 1) == 0  # host to device
+
+    def accumulate(self, w, h, spp, seed=SEED):
+        st = PtStats()
+        assert self.L.pt_ctx_accumulate(self.ctx, C.byref(cfg_of(w, h, spp, seed=seed)), self.bufs["color"], None, None, None,
+                                        None, C.byref(st)) == 0, self.L.pt_last_error()
+
+    def noise(self, w, h, spp, seed=SEED):
+        ns = PtNoiseStats()
+        assert self.L.pt_ctx_accum_noise(self.ctx, C.byref(cfg_of(w, h, spp, seed=seed)), self.bufs["error"], C.byref(ns),
+                                         None) == 0, self.L.pt_last_error()
+
+    def guides(self, w, h, guide_spp, seed=SEED):
+        b = self.bufs
+        assert self.L.pt_ctx_render_aov(self.ctx, C.byref(cfg_of(w, h, guide_spp, seed=seed)), b["albedo"], b["normal"],
+                                        b["depth"], None, None) == 0, self.L.pt_last_error()
+
+    def host(self, w, h):
+        """(color, error, albedo, normal, depth) as they are on the device"""
+        return tuple(self.get(n, w * h) for n in ("color", "error", "albedo", "normal", "depth"))
+
+    def render(self, w, h, spp=16, guide_spp=4, seed=SEED):
+        """a fresh tracked frame, its noise map and its guides; returns them on the host"""
+        assert self.L.pt_ctx_accum_reset(self.ctx) == 0
+        self.accumulate(w, h, spp, seed)
+        self.noise(w, h, spp, seed)
+        self.guides(w, h, guide_spp, seed)
+        return self.host(w, h)
+
+    def denoise_var(self, w, h, levels=0, sigma_var=0.0, sigma_depth=0.0, flags=0, guides=(1, 1, 1), out="out", stream=None,
+                    params=True):
+        b = self.bufs
+        p = PtDenoiseVarParams(levels, sigma_var, sigma_depth, flags)
+        g = [b[n] if on else None for n, on in zip(("albedo", "normal", "depth"), guides)]
+        rc = self.L.pt_ctx_denoise_var(self.ctx, w, h, C.byref(p) if params else None, b["color"], b["error"], g[0], g[1], g[2],
+                                       b[out], stream)
+        assert rc == 0, (rc, self.L.pt_last_error())
+        return self.get(out, w * h)
+
+    def denoise(self, w, h, levels=0):
+        b = self.bufs
+        p = PtDenoiseParams(levels, 0.0, 0.0, 0.0, 0)
+        rc = self.L.pt_ctx_denoise(self.ctx, w, h, C.byref(p), b["color"], b["albedo"], b["normal"], b["depth"], b["out"], None)
+        assert rc == 0, (rc, self.L.pt_last_error())
+        return self.get("out", w * h)
+
+    def close(self):
+        for p in self.bufs.values():
+            self.L.pt_device_free(0, p)
+        self.L.pt_ctx_destroy(self.ctx)
+
+
+def reference(L, host, w, h, levels=0, sigma_var=0.0, sigma_depth=0.0, flags=0, guides=(1, 1, 1)):
+    d_levels, d_sv, d_sd = ref.defaults(L)
+    color, error, albedo, normal, depth = host
+    return ref.denoise_var(color, error, w, h, albedo if guides[0] else None, normal if guides[1] else None,
+                           depth if guides[2] else None, levels or d_levels, sigma_var or d_sv, sigma_depth or d_sd, flags)
+
+
+def reference_fixed(L, host, w, h, levels=0):
+    d_levels, d_sc, d_sd = denoise_ref.defaults(L)
+    color, _, albedo, normal, depth = host
+    return denoise_ref.denoise(color, w, h, albedo, normal, depth, levels or d_levels, d_sc, d_sd)
+
+
+def assert_bytes(got, want, what):
+    got, want = np.ascontiguousarray(got, dtype=F32), np.ascontiguousarray(want, dtype=F32).reshape(got.shape)
+    if got.tobytes() != want.tobytes():
+        bad = np.argwhere(got.view(np.uint32) != want.view(np.uint32))
+        raise AssertionError("%s: %d of %d words differ, first at %s: %r vs %r" % (
+            what, len(bad), got.size, bad[0], got[tuple(bad[0])], want[tuple(bad[0])]))
+
+
+@pytest.fixture(scope="module")
+def L():
+    L = _bind(ptlib.product())
+    assert L.pt_device_count() >= 1, "no HIP device visible: the product has no CPU fallback"
+    return L
+
+
+# ------------------------------------------------------------------------------------------------ bit for bit
+@pytest.mark.parametrize("sid", ["cornell", "three-spheres", "mesh", "mesh-hdodec"])
+def test_bit_equal_to_the_rebuild(L, sid):
+    fr = Frame(L, scene(sid), 64 * 41 + 300 * 7)
+    try:
+        for w, h in SIZES:
+            host = fr.render(w, h)
+            assert np.isfinite(host[1]).all()  # 8 + 8 samples: every pixel has an estimate
+            for levels in (1, 2, 5, 8):
+                assert_bytes(fr.denoise_var(w, h, levels), reference(L, host, w, h, levels),
+                             "%s %dx%d levels %d" % (sid, w, h, levels))
+                sv, sd = NON_DEFAULT
+                assert_bytes(fr.denoise_var(w, h, levels, sv, sd), reference(L, host, w, h, levels, sv, sd),
+                             "%s %dx%d levels %d sigmas %r" % (sid, w, h, levels, NON_DEFAULT))
+            # params == NULL and all-zero params are the defaults
+            want = reference(L, host, w, h)
+            assert_bytes(fr.denoise_var(w, h, params=False), want, "NULL params")
+            assert_bytes(fr.denoise_var(w, h), want, "zero params")
+    finally:
+        fr.close()
+
+
+@pytest.mark.parametrize("sid", ["cornell", "mesh"])
+def test_null_guides_and_no_demodulate(L, sid):
+    w, h = 67, 41
+    fr = Frame(L, scene(sid), w * h)
+    try:
+        host = fr.render(w, h)
+        seen = {}
+        for a in (0, 1):
+            for n in (0, 1):
+                for d in (0, 1):
+                    for flags in (0, NO_DEMODULATE):
+                        got = fr.denoise_var(w, h, 3, 0.0, 0.0, flags, (a, n, d))
+                        assert_bytes(got, reference(L, host, w, h, 3, 0.0, 0.0, flags, (a, n, d)),
+                                     "guides %d%d%d flags %d" % (a, n, d, flags))
+                        seen[(a, n, d, flags)] = got.tobytes()
+        # NO_DEMODULATE is a NULL albedo, and the guides matter
+        assert seen[(1, 1, 1, NO_DEMODULATE)] == seen[(0, 1, 1, 0)]
+        assert len({seen[(a, n, d, 0)] for a in (0, 1) for n in (0, 1) for d in (0, 1)}) == 8
+    finally:
+        fr.close()
+
+
+def test_special_error_values(L):
+    """A host-made map over the device's: 0, a denormal, 2^-12, just below 12, 12, 13, +inf, NaN, -1 and -0.0, spread over the
+    frame so that every value meets every kind of neighbour."""
+    w, h = 67, 41
+    values = np.array([0.0, 1e-40, 2.0 ** -12, 11.999, 12.0, 13.0, np.inf, np.nan, -1.0, -0.0], dtype=F32)
+    fr = Frame(L, scene("cornell"), w * h)
+    try:
+        color, error, albedo, normal, depth = fr.render(w, h)
+        rng = np.random.default_rng(3)
+        k = rng.integers(0, len(values) + 3, w * h)  # three in thirteen pixels keep the device's own estimate
+        made = np.where(k < len(values), values[np.minimum(k, len(values) - 1)], error).astype(F32)
+        made[: len(values)] = values  # each at least once, side by side
+        fr.put("error", made)
+        assert fr.get("error", w * h).tobytes() == made.tobytes()
+        host = (color, made, albedo, normal, depth)
+        for levels in (1, 5):
+            assert_bytes(fr.denoise_var(w, h, levels), reference(L, host, w, h, levels), "special values, levels %d" % levels)
+    finally:
+        fr.close()
+
+
+def test_an_adaptive_frame_as_input(L):
+    """pt_ctx_render_adaptive's d_out and d_error go straight in (96x64, tile 8, target 0.08, cap 256: the shape
+    tests/test_gpu_adaptive.py uses); a cap-4 frame's d_error is all +inf ("no estimate") and is filtered as e = 12."""
+    w, h = 96, 64
+    fr = Frame(L, scene("cornell"), w * h)
+    try:
+        fr.guides(w, h, 4)
+        for cap, all_inf in ((256, False), (4, True)):
+            par, st, ast = PtAdaptiveParams(0.08, 8, 0), PtStats(), PtAdaptiveStats()
+            cfg = cfg_of(w, h, cap, backend=1)
+            assert L.pt_ctx_render_adaptive(fr.ctx, C.byref(cfg), C.byref(par), fr.bufs["color"], None, fr.bufs["error"], None,
+                                            None, None, None, C.byref(st), C.byref(ast)) == 0, L.pt_last_error()
+            host = fr.host(w, h)
+            assert np.isinf(host[1]).all() == all_inf
+            if not all_inf:
+                assert len(np.unique(host[1][np.isfinite(host[1])])) > 100  # a real map
+            assert_bytes(fr.denoise_var(w, h), reference(L, host, w, h), "adaptive frame, cap %d" % cap)
+        # all +inf is all 12
+        fr.put("error", np.full(w * h, 12.0, F32))
+        assert_bytes(fr.denoise_var(w, h), reference(L, host, w, h), "e = 12 against e = +inf")
+    finally:
+        fr.close()
+
+
+def test_large_frame_on_picked_pixels(L):
+    w, h = 2100, 1000
+    npix = w * h
+    fr = Frame(L, scene("cornell"), npix)
+    try:
+        host = fr.render(w, h, 8, 4)
+        got = fr.denoise_var(w, h)
+    finally:
+        fr.close()
+    want = reference(L, host, w, h)
+    rng = np.random.default_rng(11)
+    special = [0, w - 1, npix - w, npix - 1, w // 2, npix - w // 2, (h // 2) * w, (h // 2) * w + w - 1]
+    special += [y * w + x for y in (0, 1, 2, h - 3, h - 2, h - 1) for x in (0, 1, 2, 31, 32, w - 3, w - 2, w - 1)]
+    special += [y * w + x for y in (7, 8, 15, 16, 17, 500) for x in (0, 1, 2, 15, 16, 33, w - 1)]
+    pick = np.unique(np.concatenate([np.array(special), rng.choice(npix, 4096 - len(special), replace=False)]))
+    assert_bytes(got[pick], want[pick], "2100x1000 picked")
+
+
+# ------------------------------------------------------------------------------------------------ the two forms
+CHILD_FRAMES = ((67, 41), (300, 200), (5, 3))
+
+
+def child_main():
+    """python tests/test_gpu_denoise_var.py --child: sha256 of pt_ctx_denoise_var's output for every frame of CHILD_FRAMES and
+    every level count, in the form PT_DN_LDS_MAXSTEP selects, as one JSON line"""
+    L = _bind(ptlib.product())
+    out = {}
+    fr = Frame(L, scene("mesh"), max(w * h for w, h in CHILD_FRAMES))
+    try:
+        for w, h in CHILD_FRAMES:
+            fr.render(w, h)
+            for levels in range(1, 9):
+                out["%dx%d/%d" % (w, h, levels)] = hashlib.sha256(fr.denoise_var(w, h, levels).tobytes()).hexdigest()
+    finally:
+        fr.close()
+    print("HASHES " + json.dumps(out))
+
+
+def test_both_forms_give_the_same_bytes(L):
+    res = {}
+    for maxstep in ("0", "128"):
+        env = dict(os.environ, PT_DN_LDS_MAXSTEP=maxstep)
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"], env=env, capture_output=True, text=True,
+                           timeout=600)
+        assert r.returncode == 0, r.stdout + r.stderr
+        line = [l for l in r.stdout.splitlines() if l.startswith("HASHES ")][0]
+        res[maxstep] = json.loads(line[len("HASHES "):])
+    assert len(res["0"]) == len(CHILD_FRAMES) * 8
+    assert res["0"] == res["128"], [k for k in res["0"] if res["0"][k] != res["128"][k]]
+    # and they are the restatement's bytes (this process runs the default mix of forms)
+    fr = Frame(L, scene("mesh"), 300 * 200)
+    try:
+        for w, h in CHILD_FRAMES:
+            host = fr.render(w, h)
+            for levels in (3, 8):
+                want = reference(L, host, w, h, levels)
+                assert hashlib.sha256(want.tobytes()).hexdigest() == res["0"]["%dx%d/%d" % (w, h, levels)], (w, h, levels)
+                assert_bytes(fr.denoise_var(w, h, levels), want, "default forms %dx%d levels %d" % (w, h, levels))
+    finally:
+        fr.close()
+
+
+# ------------------------------------------------------------------------------------------------ calling conventions
+def test_in_place_stream_repeat_growth_and_the_other_filter(L):
+    fr = Frame(L, scene("cornell"), 128 * 80)
+    try:
+        w, h = 64, 40
+        host = fr.render(w, h)
+        first = fr.denoise_var(w, h)
+        assert_bytes(first, reference(L, host, w, h), "out of place")
+        assert_bytes(fr.denoise_var(w, h), first, "second call")  # scratch reuse leaks nothing
+        # interleaved with pt_ctx_denoise on the same context and scratch, in both orders: each gives its own bytes
+        fixed = reference_fixed(L, host, w, h)
+        assert first.tobytes() != fixed.tobytes()
+        assert_bytes(fr.denoise(w, h), fixed, "pt_ctx_denoise after pt_ctx_denoise_var")
+        assert_bytes(fr.denoise_var(w, h), first, "pt_ctx_denoise_var after pt_ctx_denoise")
+        assert_bytes(fr.denoise(w, h, 8), reference_fixed(L, host, w, h, 8), "pt_ctx_denoise, 8 levels, after")
+        assert_bytes(fr.denoise_var(w, h, 2), reference(L, host, w, h, 2), "pt_ctx_denoise_var, 2 levels, after")
+        # a larger frame after a smaller one (scratch grows), then the smaller again
+        W2, H2 = 128, 80
+        host2 = fr.render(W2, H2)
+        assert_bytes(fr.denoise_var(W2, H2), reference(L, host2, W2, H2), "larger frame")
+        fr.render(w, h)
+        assert_bytes(fr.denoise_var(w, h), first, "smaller frame after the larger")
+        # a caller's stream
+        hip = hip_runtime()
+        stream = C.c_void_p()
+        assert hip.hipStreamCreate(C.byref(stream)) == 0
+        try:
+            assert_bytes(fr.denoise_var(w, h, stream=stream), first, "caller's stream")
+        finally:
+            hip.hipStreamDestroy(stream)
+        # in place: d_out == d_color (last: it overwrites the frame)
+        assert_bytes(fr.denoise_var(w, h, out="color"), first, "in place")
+    finally:
+        fr.close()
+
+
+def test_runtime_errors_with_a_context(L):
+    fr = Frame(L, scene("three-spheres"), 16)
+    try:
+        b = fr.bufs
+        call = lambda *a: L.pt_ctx_denoise_var(fr.ctx, *a)  # noqa: E731
+        bad = PtDenoiseVarParams(9, 0, 0, 0)
+        assert call(4, 4, C.byref(bad), b["color"], b["error"], None, None, None, b["out"], None) == PT_ERR_INVALID
+        assert call(4, 4, None, None, b["error"], None, None, None, b["out"], None) == PT_ERR_INVALID
+        assert call(4, 4, None, b["color"], None, None, None, None, b["out"], None) == PT_ERR_INVALID
+        assert b"d_error" in L.pt_last_error()
+        assert call(4, 4, None, b["color"], b["error"], None, None, None, None, None) == PT_ERR_INVALID
+        assert call(0, 4, None, b["color"], b["error"], None, None, None, b["out"], None) == PT_ERR_INVALID
+    finally:
+        fr.close()
+    # no scene is needed
+    ctx = C.c_void_p()
+    assert L.pt_ctx_create(0, C.byref(ctx)) == 0
+    p, e = C.c_void_p(), C.c_void_p()
+    assert L.pt_device_malloc(0, 16 * 12, C.byref(p)) == 0 and L.pt_device_malloc(0, 16 * 4, C.byref(e)) == 0
+    try:
+        assert L.pt_ctx_denoise_var(ctx, 4, 4, None, p, e, None, None, None, p, None) == 0, L.pt_last_error()
+    finally:
+        L.pt_device_free(0, p)
+        L.pt_device_free(0, e)
+        L.pt_ctx_destroy(ctx)
+
+
+def test_no_disturbance_of_accumulation(L):
+    """accumulate to 16, denoise, accumulate to 32: the frame is pt_ctx_render's at 32 and the noise map is the one a context
+    gives that never denoised."""
+    w, h = 64, 40
+    npix = w * h
+
+    def run(with_denoise):
+        fr = Frame(L, scene("cornell"), npix)
+        try:
+            fr.accumulate(w, h, 16)
+            fr.noise(w, h, 16)
+            fr.guides(w, h, 4)
+            lo, hi = C.c_uint32(), C.c_uint32()
+            if with_denoise:
+                fr.denoise_var(w, h)
+                assert L.pt_ctx_accum_info(fr.ctx, C.byref(cfg_of(w, h, 1)), C.byref(lo), C.byref(hi)) == 0
+                assert (lo.value, hi.value) == (16, 16)
+            fr.accumulate(w, h, 32)
+            fr.noise(w, h, 32)
+            got, err = fr.get("color", npix), fr.get("error", npix)
+            st = PtStats()
+            assert L.pt_ctx_render(fr.ctx, C.byref(cfg_of(w, h, 32)), fr.bufs["out"], None, None, None, None, C.byref(st)) == 0
+            return got, err, fr.get("out", npix)
+        finally:
+            fr.close()
+
+    got, err, want = run(True)
+    assert got.tobytes() == want.tobytes()
+    got0, err0, _ = run(False)
+    assert got.tobytes() == got0.tobytes() and err.tobytes() == err0.tobytes()
+
+
+# ------------------------------------------------------------------------------------------------ quality
+def rmse(a, b):
+    return float(np.sqrt(np.mean((a.astype(np.float64) - b.astype(np.float64)) ** 2)))
+
+
+@pytest.mark.parametrize("sid", ["cornell", "mesh"])
+def test_quality_on_the_devices_own_frames(L, sid):
+    """96x64, the tracked frame at 16 and at 256 samples with guides at 16, against pt_ctx_render at 4096 samples: in each cell
+    ratio = rmse(denoised, converged) / rmse(noisy, converged) is at most 1.15 x the CPU study's ratio, and at 256 samples it is
+    below 1 and below pt_ctx_denoise's on the same frame.  (The device's halves are sample ranges of one seed, the study's two
+    seeds: DESIGN.md records that the estimate behaves the same.)"""
+    w, h = 96, 64
+    npix = w * h
+    fr = Frame(L, scene(sid), npix)
+    try:
+        st = PtStats()
+        assert L.pt_ctx_render(fr.ctx, C.byref(cfg_of(w, h, 4096)), fr.bufs["out"], None, None, None, None, C.byref(st)) == 0
+        conv = fr.get("out", npix)
+        fr.guides(w, h, 16)
+        cells = {}
+        for n in (16, 256):
+            fr.accumulate(w, h, n)  # 16, then on to 256
+            fr.noise(w, h, n)
+            noisy = fr.get("color", npix)
+            cells[n] = (rmse(noisy, conv), rmse(fr.denoise_var(w, h), conv), rmse(fr.denoise(w, h), conv))
+    finally:
+        fr.close()
+    for n, (e_noisy, e_var, e_fixed) in cells.items():
+        bound = 1.15 * STUDY["chosen"]["ratio"]["%s_%d" % (sid, n)]
+        print("%s n %d: rmse noisy %.5f, guided ratio %.4f (bound %.4f), pt_ctx_denoise ratio %.4f"
+              % (sid, n, e_noisy, e_var / e_noisy, bound, e_fixed / e_noisy))
+    for n, (e_noisy, e_var, e_fixed) in cells.items():
+        bound = 1.15 * STUDY["chosen"]["ratio"]["%s_%d" % (sid, n)]
+        assert e_var <= bound * e_noisy, (sid, n, e_var / e_noisy, bound)
+        if n == 256:
+            assert e_var < e_noisy, (sid, e_var / e_noisy)
+            assert e_var < e_fixed, (sid, e_var / e_noisy, e_fixed / e_noisy)
+
+
+# ------------------------------------------------------------------------------------------------ above the ABI
+def test_python_context_denoise_var(L):
+    pkg = importlib.import_module("path-tracer-rust_amd")
+    w, h = 67, 41
+    ctx = pkg.Context(0)
+    fr = Frame(L, scene("mesh"), w * h)
+    try:
+        host = fr.render(w, h)
+        b = {k: v.value for k, v in fr.bufs.items()}
+        ctx.denoise_var(w, h, b["color"], b["error"], b["out"], albedo=b["albedo"], normal=b["normal"], depth=b["depth"])
+        assert_bytes(fr.get("out", w * h), reference(L, host, w, h), "python defaults")
+        ctx.denoise_var(w, h, b["color"], b["error"], b["out"], normal=b["normal"], levels=2, sigma_var=0.6, no_demodulate=True)
+        assert_bytes(fr.get("out", w * h), reference(L, host, w, h, 2, 0.6, 0.0, NO_DEMODULATE, (0, 1, 0)), "python params")
+        with pytest.raises(pkg.PtraceError):
+            ctx.denoise_var(w, h, b["color"], b["error"], b["out"], levels=9)
+        with pytest.raises(pkg.PtraceError):
+            ctx.denoise_var(w, h, b["color"], None, b["out"])
+    finally:
+        fr.close()
+        ctx.close()
+
+
+@pytest.mark.parametrize("source", ["noise-target", "adaptive"])
+def test_cli_writes_the_denoised_files(L, tmp_path, source):
+    cli = os.path.join(ptlib.PKG, "ptrace")
+    out = tmp_path / "out"
+    emap = tmp_path / "e.pfm"
+    args = ["--noise-target", "0.2", "--noise-map", str(emap)] if source == "noise-target" else \
+        ["--adaptive", "0.2", "--error-map", str(emap)]
+    r = subprocess.run([cli, "64", "24", "mesh", "--root", ptlib.ROOT, "--seed", "3", "--out", str(out), "--aov", "4"] + args +
+                       ["--denoise-var", "4"], cwd=str(tmp_path), capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    files = sorted(os.listdir(out))
+    stem = [f for f in files if f.endswith("-.ppm")][0][:-len(".ppm")]
+    assert stem + "denoised.ppm" in files and stem + "denoised.pfm" in files, files
+    w, h = 36, 24
+    load = lambda n: pfm_to_framebuffer(read_pfm(out / (stem + n + ".pfm")))  # noqa: E731
+    beauty, albedo, normal, depth = load("beauty"), load("albedo"), load("normal"), load("depth")[:, 0]
+    error = pfm_to_framebuffer(read_pfm(emap))[:, 0]
+    den = read_pfm(out / (stem + "denoised.pfm"))
+    assert den.shape == (h, w, 3)
+    want = ref.denoise_var(beauty, error, w, h, albedo, normal, depth, *ref.defaults(L))
+    assert_bytes(pfm_to_framebuffer(den), want, "cli " + source)
+    O = ptlib.oracle()
+    vals = np.array(open(out / (stem + "denoised.ppm")).read().split("255\n", 1)[1].split(), dtype=np.int64).reshape(h, w, 3)
+    mapped = np.vectorize(lambda v: O.pto_to_int_with_gamma_correction(float(v)))(den[::-1])
+    assert (mapped == vals).all()
+
+
+def test_cli_usage_errors():
+    cli = os.path.join(ptlib.PKG, "ptrace")
+
+    def run(*args):
+        return subprocess.run([cli, "6", "24", "mesh", "--root", ptlib.ROOT, "--no-ppm"] + list(args), capture_output=True,
+                              text=True, timeout=60)
+
+    for args in (["--denoise-var"],                                                   # no estimate to take
+                 ["--denoise-var", "4", "--checkpoint", "c.ckpt"],
+                 ["--noise-target", "0.2", "--denoise-var", "--denoise"],             # one filter or the other
+                 ["--adaptive", "0.2", "--denoise-var", "0"],                         # N = 0
+                 ["--noise-target", "0.2", "--denoise-var", "--gpus", "2"]):          # one GPU only
+        r = run(*args)
+        assert r.returncode == 1, (args, r.stdout + r.stderr)
+        assert ("--denoise-var" in r.stderr) or ("one GPU" in r.stderr), (args, r.stderr)
+    r = run("--error-map", "e.pfm")
+    assert r.returncode == 1 and "--error-map" in r.stderr
+    # what was refused before still is
+    r = run("--adaptive", "0.2", "--denoise")
+    assert r.returncode == 1 and "--denoise" in r.stderr
+
+
+if __name__ == "__main__":
+    if sys.argv[1:] == ["--child"]:
+        child_main()
