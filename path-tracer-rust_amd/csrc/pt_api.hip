@@ -227,7 +227,7 @@ struct pt_ctx {
     DevBuf<SurfRec> d_surf;
     bool cand_ok = false;
     uint32_t n_bvh_nodes = 0;
-    uint32_t n_cus = 0;  // compute units of the device (stream-count rounding)
+    uint32_t n_cus = 0;  // compute units of the device (pt_ctx_create: never 0 afterwards)
     // Mesh.bounding_box of every object (12 object-local triangles each; Mesh::new's unless pt_ctx_set_mesh_bounds gave
     // the stored ones) and their device form (6 pair records per object), for intersect_bounds / orbit-point queries
     std::vector<pt_triangle> h_boxes;
@@ -410,6 +410,15 @@ bool progress(pt_ctx *c, const pt_config *cfg, pt_progress_fn cb, void *user, fl
     cb(user, f);
     return true;
 }
+
+// The frame call in progress owns pt_ctx.live: its clock starts here, and however the call returns, pt_ctx_snapshot finds no frame
+// in progress afterwards
+struct LiveScope {
+    pt_ctx *c;
+    explicit LiveScope(pt_ctx *c_) : c(c_) { c->live.cb_last_ms = now_ms(); }
+    LiveScope(const LiveScope &) = delete;
+    ~LiveScope() { c->live = LiveFrame{}; }
+};
 
 // A progress relay: the fractions below 1 of an inner call, passed on as base + scale * f of the outer one.  The inner call's
 // "1.0" is not passed on: the outer call says when IT is complete (the next job, every pipeline or rank finished and the frame
@@ -746,13 +755,47 @@ int render_wavefront(pt_ctx *c, const FrameForm &form, const pt_config *cfg, con
     return PT_OK;
 }
 
+// Samples [s_first, cfg->spp) of `entries` items in ROUNDS (host::plan_rounds), for the kernels that hand (item, sample range)
+// pieces out from a counter: the megakernel (an item is a pixel of the part) and the tile pass (an entry of the compact
+// accumulator).  A round is one launch, sized to about a tenth of a second - it follows the scene as k_pass_cand's passes do
+// (PassPacer, from `rate`, which is brought up to date) unless cfg->rays_per_pass sizes it - so cancel and cb (either may be NULL)
+// are served between launches (the reference polls cancel every 100 ms, mod.rs:947-958) and every item holds the same number of
+// samples at every boundary: what pt_ctx_snapshot and a cancelled frame resolve.  Before each launch counters[7], the kernels'
+// item counter, is zeroed and the split stacks (mega_cand) cover the grid; launch(grid, s0, s_end, lane_spp, split) issues it.
+struct Rounds {
+    uint32_t launches = 0, s_issued = 0;  // launches issued; samples [s_first, s_issued) of every item have run
+    bool cancelled = false;
+    double ms_device = 0.0;  // first to last launch
+};
+template <class Launch>
+int run_rounds(pt_ctx *c, const pt_config *cfg, hipStream_t st, const volatile uint8_t *cancel, pt_progress_fn cb, void *user,
+               uint64_t entries, uint32_t s_first, bool mega_cand, uint32_t item_mult, unsigned long long *counters, DevBuf<char> &stacks,
+               double &rate, Launch launch, Rounds &out) {
+    const host::RoundPlan plan = host::plan_rounds(entries, cfg->spp - s_first, cfg->rays_per_pass, item_mult, c->n_cus);
+    PassPacer pace(c, cfg, st, cancel, cb, user, entries, s_first, plan.round_spp, false, true, rate);
+    int rc = pace.start();
+    if (rc) return rc;
+    while ((rc = pace.next()) == PassPacer::kLaunch) {
+        const host::RoundLaunch l = host::round_launch(entries, plan.n_split, pace.s_here, c->n_cus);
+        if (mega_cand && (rc = stacks.ensure(mega_stack_mem_bytes(l.grid)))) return rc;
+        HIP_TRY(hipMemsetAsync(counters + 7, 0, sizeof(unsigned long long), st));
+        launch(l.grid, pace.s0, pace.s0 + pace.s_here, l.lane_spp, l.split);
+        if ((rc = pace.launched())) return rc;
+    }
+    if (rc || (rc = pace.finish())) return rc;
+    if (pace.measured()) rate = pace.rate;
+    out.launches = pace.p;
+    out.s_issued = pace.s_next;
+    out.cancelled = pace.cancelled;
+    return pace.frame_ms(out.ms_device);
+}
+
 // Samples [s_first, cfg->spp) of every pixel of the part; the accumulators start from `held` (NULL: from zero).
 int render_mega(pt_ctx *c, const FrameForm &form, const pt_config *cfg, const FrameParams &F, hipStream_t st,
                 const volatile uint8_t *cancel, pt_progress_fn cb, void *user, pt_stats &stats, uint32_t s_first,
                 const HeldSums *held) {
     const DevScene &S = form.scene;
     const uint64_t npix = F.npix;
-    const uint32_t spp_left = cfg->spp - s_first;  // samples per pixel this call traces
     int rc;
     if ((rc = c->acc.ensure(3 * npix)) || (rc = c->total_rays.ensure(16))) return rc;
     c->live.streams = 1;  // accumulators in pixel order
@@ -762,47 +805,18 @@ int render_mega(pt_ctx *c, const FrameForm &form, const pt_config *cfg, const Fr
     else
         HIP_TRY(hipMemsetAsync(c->acc.p, 0, 3 * npix * sizeof(unsigned long long), st));
     HIP_TRY(hipMemsetAsync(c->total_rays.p, 0, 16 * sizeof(unsigned long long), st));
-    // The frame is cut into ROUNDS: one round = every pixel of the call x round_spp consecutive samples, one launch (a
-    // lane = one pixel's samples of the round, walked one after the other).  A round is sized to about a tenth of a
-    // second of work, so the cancel byte and the progress callback are served between launches (the reference polls
-    // cancel every 100 ms, mod.rs:947-958) and every pixel holds the same number of samples at every boundary - which is
-    // what pt_ctx_snapshot and a cancelled frame resolve.  Small frames get several lanes per pixel inside a round
-    // (n_split) so that a launch still fills the chip.
-    hipDeviceProp_t prop;
-    HIP_TRY(hipGetDeviceProperties(&prop, c->device));
-    const uint64_t lanes = (uint64_t)prop.multiProcessorCount * 2048u;
-    const uint64_t round_budget = cfg->rays_per_pass ? cfg->rays_per_pass : (256ull << 20);  // primary samples per launch
-    uint64_t round_spp64 = round_budget / npix;
-    if (round_spp64 == 0) round_spp64 = 1;
-    if (round_spp64 > spp_left) round_spp64 = spp_left;
-    const uint32_t round_spp = (uint32_t)round_spp64;
-    uint32_t n_split = 1;  // lanes per pixel within a round
-    // (k_mega_cand hands its items out dynamically: finer ones - 8 per lane the chip holds, cornell 41.3 G bounces/s; 4: 39.1,
-    // 16: 40.5, 32: 38.4 - so that a launch's last items are a small part of it; PT_MEGA_ITEMS for A/B runs and tests)
     const LdsLayout lay = lds_layout(S, 1u, c->tune.lds_pad);
     say_layout(c, lay, 2);
-    const uint64_t item_mult = c->tune.mega_items ? c->tune.mega_items : (lay.mega_cand ? 8u : 4u);
-    const uint64_t want_items = item_mult * lanes;
-    while ((uint64_t)npix * n_split < want_items && n_split < round_spp) n_split *= 2;
-    if (n_split > round_spp) n_split = round_spp;
-    // rounds that follow the scene, as k_pass_cand's passes do (PassPacer), unless rays_per_pass sizes them
-    PassPacer pace(c, cfg, st, cancel, cb, user, npix, s_first, round_spp, false, true, c->round_rate);
-    if ((rc = pace.start())) return rc;
-    while ((rc = pace.next()) == PassPacer::kLaunch) {
-        const uint32_t s0 = pace.s0, s_here = pace.s_here;
-        const uint32_t split = n_split < s_here ? n_split : s_here;
-        const uint32_t lane_spp = (s_here + split - 1) / split;
-        const uint64_t items = npix * split;
-        const uint64_t grid64 = (items + kBlock - 1) / kBlock;
-        const uint64_t max_grid = (uint64_t)prop.multiProcessorCount * 8u;
-        const uint32_t grid = (uint32_t)(grid64 < max_grid ? grid64 : max_grid);
-        if (lay.mega_cand && (rc = c->q_buf[0].ensure(mega_stack_mem_bytes(grid ? grid : 1u)))) return rc;  // split stacks
-        HIP_TRY(hipMemsetAsync(c->total_rays.p + 7, 0, sizeof(unsigned long long), st));  // k_mega_cand's item counter
-        launch_mega(st, grid ? grid : 1u, S, lay, F, c->acc.p, s0, s0 + s_here, lane_spp, split, c->total_rays.p, c->q_buf[0].p);
-        if ((rc = pace.launched())) return rc;
-    }
-    if (rc || (rc = pace.finish())) return rc;
-    if (pace.measured()) c->round_rate = pace.rate;
+    // (PT_MEGA_ITEMS for A/B runs and tests)
+    const uint32_t item_mult = c->tune.mega_items ? c->tune.mega_items : (lay.mega_cand ? 8u : 4u);
+    Rounds r;
+    rc = run_rounds(
+        c, cfg, st, cancel, cb, user, npix, s_first, lay.mega_cand, item_mult, c->total_rays.p, c->q_buf[0], c->round_rate,
+        [&](uint32_t grid, uint32_t s0, uint32_t s_end, uint32_t lane_spp, uint32_t split) {
+            launch_mega(st, grid, S, lay, F, c->acc.p, s0, s_end, lane_spp, split, c->total_rays.p, c->q_buf[0].p);
+        },
+        r);
+    if (rc) return rc;
     unsigned long long total2[16] = {0};
     HIP_TRY(hipMemcpy(total2, c->total_rays.p, sizeof total2, hipMemcpyDeviceToHost));
 #ifdef PT_MEGA_STATS
@@ -820,11 +834,11 @@ int render_mega(pt_ctx *c, const FrameForm &form, const pt_config *cfg, const Fr
     stats.ray_bounces = total2[0];
     stats.intersect_rays = 0;
     stats.intersect_launches = 0;
-    stats.passes = pace.p;
-    stats.samples = npix * (uint64_t)(pace.s_next - s_first);
-    if ((rc = pace.frame_ms(stats.ms_device))) return rc;
+    stats.passes = r.launches;
+    stats.samples = npix * (uint64_t)(r.s_issued - s_first);
+    stats.ms_device = r.ms_device;
     stats.ms_intersect = 0.0;
-    if (pace.cancelled) {
+    if (r.cancelled) {
         set_error("cancelled");
         return PT_CANCELLED;
     }
@@ -959,15 +973,11 @@ int run_frame_call(pt_ctx *c, const pt_config *cfg, const FrameParams &F, const 
     const double t0 = now_ms();
     const FrameForm form = form_for(c, cfg->flags);
     Relay relay{cb, user};  // a job's fractions as fractions of the call; its completion is reported by the next job / the end
-    struct Clear {  // however the call returns, pt_ctx_snapshot finds no frame in progress afterwards
-        pt_ctx *c;
-        ~Clear() { c->live = LiveFrame{}; }
-    } clear{c};
+    LiveScope live(c);
     c->live.out = out;
     c->live.total = total;
     c->live.stream = st;
     c->live.accum = accumulate;
-    c->live.cb_last_ms = now_ms();
     int rc = PT_OK;
     bool started = false;
     for (const Job &j : jobs) {
@@ -1010,6 +1020,163 @@ int frame_prologue(pt_ctx *c, const pt_config *cfg, uint32_t *ib, uint32_t *ie) 
     const int rc = check_cfg(cfg, ib, ie);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device));
+    return PT_OK;
+}
+
+// One run of a level of pt_ctx_render_adaptive: samples [s_first, s_end) of every open tile into the compact accumulator (zeroed
+// here), in the megakernel's rounds at a rate of their own.  The cancel byte is the level loop's business, not the rounds'.
+int tile_run(pt_ctx *c, const DevScene &S, const LdsLayout &lay, const pt_config *cfg, TileParams F, uint32_t n_open, uint32_t s_first,
+             uint32_t s_end, hipStream_t st, pt_stats &stats) {
+    const uint64_t entries = (uint64_t)n_open << (2u * F.tile_shift);
+    F.npix = (uint32_t)entries;
+    int rc = c->ad_acc.ensure(3 * entries);
+    if (rc) return rc;
+    HIP_TRY(hipMemsetAsync(c->ad_acc.p, 0, 3 * entries * sizeof(unsigned long long), st));
+    pt_config run = *cfg;
+    run.spp = s_end;
+    Rounds r;
+    rc = run_rounds(
+        c, &run, st, nullptr, nullptr, nullptr, entries, s_first, lay.mega_cand, lay.mega_cand ? 8u : 4u, c->ad_rays.p, c->ad_stack, c->ad_rate,
+        [&](uint32_t grid, uint32_t s0, uint32_t s1, uint32_t lane_spp, uint32_t split) {
+            launch_tile_pass(st, grid, S, lay, F, c->ad_acc.p, s0, s1, lane_spp, split, c->ad_rays.p, c->ad_stack.p);
+        },
+        r);
+    stats.passes += r.launches;
+    return rc;
+}
+
+// pt_ctx_render_adaptive after its refusals about the arguments: the band [ib, ie) of a checked cfg in tiles of 1 << tile_shift,
+// level by level (host::adaptive_first_level, host::next_target; a level's two runs: host::tracked_split), then the outputs
+int render_adaptive(pt_ctx *c, const pt_config *cfg, uint32_t ib, uint32_t ie, uint32_t tile_shift, const pt_adaptive_params *params,
+                    float *d_out_rgb, uint32_t *d_spp, float *d_error, hipStream_t st, const volatile uint8_t *cancel, pt_progress_fn cb,
+                    void *user, pt_stats *stats, pt_adaptive_stats *astats) {
+    const double t0 = now_ms();
+    if (stats) memset(stats, 0, sizeof *stats);
+    memset(astats, 0, sizeof *astats);
+    pt_stats ps{};
+    const FrameForm form = form_for(c, cfg->flags);
+    const DevScene &S = form.scene;
+    const LdsLayout lay = lds_layout(S, 1u, c->tune.lds_pad);
+    const uint32_t npix = ie - ib;
+    TileGrid G{};
+    G.width = cfg->width;
+    G.rows = npix / cfg->width;
+    host::TileGeometry geo;
+    int rc = host::tile_geometry(G.width, G.rows, tile_shift, geo);
+    if (rc) return rc;
+    G.tile_shift = geo.tile_shift;
+    G.tiles_x = geo.tiles_x;
+    G.tiles = geo.tiles;
+    TileParams F{};
+    static_cast<FrameParams &>(F) = make_frame(c, cfg, ib, ie);
+    F.chunk_step = 0u;
+    F.tile_shift = G.tile_shift;
+    F.tiles_x = G.tiles_x;
+    F.rows = G.rows;
+    if ((rc = c->ad_held.ensure(3 * (size_t)npix)) || (rc = c->ad_a.ensure(3 * (size_t)npix)) || (rc = c->ad_err.ensure(G.tiles)) ||
+        (rc = c->ad_spp.ensure(G.tiles)) || (rc = c->ad_open[0].ensure(G.tiles)) || (rc = c->ad_open[1].ensure(G.tiles)) ||
+        (rc = c->ad_cnt.ensure(2)) || (rc = c->ad_rays.ensure(16)))
+        return rc;
+    G.spp = c->ad_spp.p;
+    G.err = c->ad_err.p;
+    hipEvent_t ev0 = get_event(c, 6), ev1 = get_event(c, 7);  // (0..5 are the rounds' pacer's)
+    if (!ev0 || !ev1) {
+        set_error("hipEventCreate failed");
+        return PT_ERR_HIP;
+    }
+    HIP_TRY(hipEventRecord(ev0, st));
+    HIP_TRY(hipMemsetAsync(c->ad_held.p, 0, 3 * (size_t)npix * sizeof(unsigned long long), st));
+    HIP_TRY(hipMemsetAsync(c->ad_a.p, 0, 3 * (size_t)npix * sizeof(unsigned long long), st));
+    HIP_TRY(hipMemsetAsync(c->ad_err.p, 0xff, (size_t)G.tiles * sizeof(unsigned long long), st));  // kTileNoError
+    HIP_TRY(hipMemsetAsync(c->ad_spp.p, 0, (size_t)G.tiles * sizeof(uint32_t), st));
+    HIP_TRY(hipMemsetAsync(c->ad_rays.p, 0, 16 * sizeof(unsigned long long), st));
+    launch_tile_begin(st, d_error, npix, c->ad_open[0].p, G.tiles);
+    LiveScope live(c);  // (the rounds' pacer notes its samples in the live frame)
+    const uint32_t cap = cfg->spp;
+    const unsigned long long q = (unsigned long long)__builtin_floor((double)params->tile_error * 268435456.0);
+    uint32_t level = host::adaptive_first_level(params->min_spp, cap);
+    uint32_t have = 0, n_a = 0, n_open = G.tiles, which = 0;
+    uint64_t samples = 0;
+    bool cancelled = false;
+    astats->tiles = G.tiles;
+    for (uint32_t j = 0; n_open != 0u && have < cap && j < 32u; ++j) {
+        cancelled = cancel && *cancel;
+        if (!cancelled && cb && j != 0u && progress(c, cfg, cb, user, (float)((double)samples / ((double)npix * cap))))
+            cancelled = cancel && *cancel;  // raised from inside the callback
+        if (cancelled) break;
+        const uint32_t m = host::tracked_split(have, level);  // [have, m) to half A, [m, level) to half B
+        F.open = c->ad_open[which].p;
+        n_a += m - have;
+        const uint32_t n_b = level - n_a;
+        TileLevel V{};
+        V.open = F.open;
+        V.n_open = n_open;
+        V.spp = level;
+        V.q = q;
+        V.next = c->ad_open[which ^ 1u].p;
+        V.counters = reinterpret_cast<uint32_t *>(c->ad_cnt.p + 1);
+        V.fa = (float)n_a;
+        V.fb = (float)n_b;
+        V.fn = (float)level;
+        V.w = n_b != 0u ? host::noise_part_weight(n_a, n_b) : 0.0f;
+        HIP_TRY(hipMemsetAsync(c->ad_cnt.p + 1, 0, sizeof(unsigned long long), st));
+        for (uint32_t run = 0; run < (m < level ? 2u : 1u); ++run) {
+            const uint32_t r0 = run ? m : have, r1 = run ? level : m;
+            if ((rc = tile_run(c, S, lay, cfg, F, n_open, r0, r1, st, ps))) return rc;
+            V.acc = c->ad_acc.p;
+            V.to_a = run == 0u ? 1u : 0u;
+            V.evaluate = r1 == level ? 1u : 0u;
+            V.estimate = V.evaluate && n_b != 0u ? 1u : 0u;
+            launch_tile_level(st, G, V, c->ad_held.p, c->ad_a.p, d_error);
+        }
+        HIP_TRY(hipGetLastError());
+        uint32_t back[2] = {0u, 0u};  // the next list's length, the tiles closed: all that comes back per level
+        HIP_TRY(hipMemcpyAsync(back, c->ad_cnt.p + 1, sizeof back, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        // (partial tiles counted whole: this only feeds the progress fraction; the exact total comes from the counts at the end)
+        samples += ((uint64_t)n_open << (2u * G.tile_shift)) * (level - have);
+        if (samples > (uint64_t)npix * cap) samples = (uint64_t)npix * cap;
+        astats->level_spp[j] = level;
+        astats->tiles_closed[j] = back[1];
+        astats->levels = j + 1u;
+        n_open = back[0];
+        which ^= 1u;
+        have = level;
+        level = host::next_target(level, cap);
+    }
+    astats->tiles_open = n_open;
+    // the outputs: every pixel over its tile's count, the counts, the sum of E over the tiles
+    HIP_TRY(hipMemsetAsync(c->ad_cnt.p, 0, sizeof(unsigned long long), st));
+    launch_tile_resolve(st, G, c->ad_held.p, d_out_rgb, d_spp, c->ad_cnt.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ev1, st));
+    unsigned long long err_sum = 0, rays[16] = {0};
+    std::vector<uint32_t> tile_spp(G.tiles);
+    std::vector<unsigned long long> tile_err(G.tiles);
+    HIP_TRY(hipMemcpyAsync(&err_sum, c->ad_cnt.p, sizeof err_sum, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(rays, c->ad_rays.p, sizeof rays, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(tile_spp.data(), c->ad_spp.p, (size_t)G.tiles * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(tile_err.data(), c->ad_err.p, (size_t)G.tiles * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (rays[1]) {
+        set_error("tile pass: a lane's split stack overflowed");
+        return PT_ERR_OVERFLOW;
+    }
+    const host::TileTotals tot = host::tile_totals(G.width, G.rows, geo, tile_spp.data(), tile_err.data(), err_sum);
+    astats->samples = tot.samples;
+    astats->mean_error = tot.mean_error;
+    ps.samples = tot.samples;
+    ps.ray_bounces = rays[0];
+    float ms_dev = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&ms_dev, ev0, ev1));
+    ps.ms_device = ms_dev;
+    ps.ms_total = now_ms() - t0;
+    if (stats) *stats = ps;
+    if (cancelled) {
+        set_error("cancelled");
+        return PT_CANCELLED;
+    }
+    if (cb) cb(user, 1.0f);
     return PT_OK;
 }
 
@@ -1066,13 +1233,16 @@ int pt_ctx_create(int device, pt_ctx **out) {
         return PT_ERR_INVALID;
     }
     HIP_TRY(hipSetDevice(device));
+    int cus = 0;  // (every launch of the megakernel and the tile pass is sized by it: never 0)
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+    if (cus <= 0) {
+        set_error("the device reports no compute units");
+        return PT_ERR_HIP;
+    }
     pt_ctx *c = new pt_ctx();
     c->device = device;
     c->tune = read_tuning();
-    {
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) c->n_cus = (uint32_t)cus;
-    }
+    c->n_cus = (uint32_t)cus;
     hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
     if (e != hipSuccess) {
         set_error(std::string("hipStreamCreate: ") + hipGetErrorString(e));
@@ -1652,50 +1822,23 @@ int pt_ctx_accum_noise(pt_ctx *c, const pt_config *cfg, float *d_error, pt_noise
 
 int pt_ctx_accumulate_until(pt_ctx *c, const pt_config *cfg, const pt_noise_target *tgt, void *d_out_rgb, void *hip_stream,
                             const volatile uint8_t *cancel, pt_progress_fn cb, void *user, pt_stats *stats, pt_noise_stats *noise) {
-    if (!cfg || !tgt || !d_out_rgb || !noise) {
-        set_error("NULL argument");
-        return PT_ERR_INVALID;
-    }
-    const bool use_mean = tgt->mean_error != 0.0f, use_q = tgt->quantile != 0.0f;
-    auto fin_nonneg = [](float v) { return v >= 0.0f && v < __builtin_inff(); };  // (false for a NaN)
-    if (!fin_nonneg(tgt->mean_error) || !fin_nonneg(tgt->quantile) || !fin_nonneg(tgt->quantile_error)) {
-        set_error("noise target: mean_error, quantile and quantile_error must be finite and not negative");
-        return PT_ERR_INVALID;
-    }
-    if (!use_mean && !use_q) {
-        set_error("noise target: neither mean_error nor quantile is in use");
-        return PT_ERR_INVALID;
-    }
-    if (use_q && !(tgt->quantile < 1.0f)) {
-        set_error("noise target: quantile must lie in (0, 1)");
-        return PT_ERR_INVALID;
-    }
-    if (!c) {
-        set_error("ctx is NULL");
-        return PT_ERR_INVALID;
-    }
-    uint32_t ib = 0, ie = 0;
-    int rc = check_cfg(cfg, &ib, &ie);
+    if (!cfg || !tgt || !d_out_rgb || !noise) return refuse("NULL argument");
+    int rc = host::check_noise_target(*tgt);
     if (rc) return rc;
+    if (!c) return refuse("ctx is NULL");
+    uint32_t ib = 0, ie = 0;
+    if ((rc = check_cfg(cfg, &ib, &ie))) return rc;
     const bool held = c->held.holds(host::accum_key(cfg, ib, ie));
-    if (!(held ? c->held.tracked() : c->acc_track)) {
-        set_error("pt_ctx_accumulate_until needs noise tracking (pt_ctx_accum_track_noise before the frame is started)");
-        return PT_ERR_INVALID;
-    }
+    if (!(held ? c->held.tracked() : c->acc_track))
+        return refuse("pt_ctx_accumulate_until needs noise tracking (pt_ctx_accum_track_noise before the frame is started)");
     const double t0 = now_ms();
     if (stats) memset(stats, 0, sizeof *stats);
     memset(noise, 0, sizeof *noise);
-    uint32_t have = held ? c->held.cnt_max() : 0u;
-    if (cfg->spp < have) {
-        set_error("cfg->spp, the cap, is below the samples per pixel held for this frame");
-        return PT_ERR_INVALID;
-    }
-    const uint32_t cap = cfg->spp, min_spp = tgt->min_spp ? tgt->min_spp : 16u;
+    const uint32_t have = held ? c->held.cnt_max() : 0u, cap = cfg->spp;
+    if (cap < have) return refuse("cfg->spp, the cap, is below the samples per pixel held for this frame");
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
     Relay relay{cb, user};  // a step's fractions as fractions of the cap's samples; the end of the call reports 1
-    uint32_t t = have > min_spp ? have : min_spp;
-    for (;;) {
-        t = t < cap ? t : cap;
+    for (uint32_t t = host::until_first_target(have, tgt->min_spp, cap);; t = host::next_target(t, cap)) {
         pt_config step = *cfg;
         step.spp = t;
         relay.scale = (float)t / (float)cap;  // (base 0: pt_ctx_accumulate's fractions count the samples held as done)
@@ -1714,236 +1857,25 @@ int pt_ctx_accumulate_until(pt_ctx *c, const pt_config *cfg, const pt_noise_targ
             break;
         }
         if ((rn == PT_OK && host::noise_target_met(*noise, *tgt)) || t >= cap) break;
-        have = t;
-        t = t > cap / 2u ? cap : t * 2u;
     }
     if (cb && rc == PT_OK) cb(user, 1.0f);
     if (stats) stats->ms_total = now_ms() - t0;
     return rc;
 }
 
-// One run of a level of pt_ctx_render_adaptive: samples [s_first, s_end) of every open tile into the compact accumulator (zeroed
-// here), in render_mega's time-sized rounds.  The cancel byte is the level loop's business, not the rounds'.
-static int tile_run(pt_ctx *c, const DevScene &S, const LdsLayout &lay, const pt_config *cfg, TileParams F, uint32_t n_open,
-                    uint32_t s_first, uint32_t s_end, hipStream_t st, uint32_t n_cus, pt_stats &stats) {
-    const uint64_t entries = (uint64_t)n_open << (2u * F.tile_shift);
-    F.npix = (uint32_t)entries;
-    int rc;
-    if ((rc = c->ad_acc.ensure(3 * entries))) return rc;
-    HIP_TRY(hipMemsetAsync(c->ad_acc.p, 0, 3 * entries * sizeof(unsigned long long), st));
-    pt_config run = *cfg;
-    run.spp = s_end;
-    const uint32_t spp_left = s_end - s_first;
-    const uint64_t lanes = (uint64_t)n_cus * 2048u;
-    const uint64_t round_budget = cfg->rays_per_pass ? cfg->rays_per_pass : (256ull << 20);  // (as render_mega)
-    uint64_t round_spp64 = round_budget / entries;
-    if (round_spp64 == 0) round_spp64 = 1;
-    if (round_spp64 > spp_left) round_spp64 = spp_left;
-    const uint32_t round_spp = (uint32_t)round_spp64;
-    uint32_t n_split = 1;
-    const uint64_t want_items = (lay.mega_cand ? 8u : 4u) * lanes;
-    while (entries * n_split < want_items && n_split < round_spp) n_split *= 2;
-    if (n_split > round_spp) n_split = round_spp;
-    PassPacer pace(c, &run, st, nullptr, nullptr, nullptr, entries, s_first, round_spp, false, true, c->ad_rate);
-    if ((rc = pace.start())) return rc;
-    while ((rc = pace.next()) == PassPacer::kLaunch) {
-        const uint32_t s0 = pace.s0, s_here = pace.s_here;
-        const uint32_t split = n_split < s_here ? n_split : s_here;
-        const uint32_t lane_spp = (s_here + split - 1) / split;
-        const uint64_t grid64 = (entries * split + kBlock - 1) / kBlock, max_grid = (uint64_t)n_cus * 8u;
-        const uint32_t grid = (uint32_t)(grid64 < max_grid ? grid64 : max_grid);
-        if (lay.mega_cand && (rc = c->ad_stack.ensure(mega_stack_mem_bytes(grid ? grid : 1u)))) return rc;
-        HIP_TRY(hipMemsetAsync(c->ad_rays.p + 7, 0, sizeof(unsigned long long), st));  // the item counter
-        launch_tile_pass(st, grid ? grid : 1u, S, lay, F, c->ad_acc.p, s0, s0 + s_here, lane_spp, split, c->ad_rays.p, c->ad_stack.p);
-        if ((rc = pace.launched())) return rc;
-    }
-    if (rc || (rc = pace.finish())) return rc;
-    if (pace.measured()) c->ad_rate = pace.rate;
-    stats.passes += pace.p;
-    return PT_OK;
-}
-
 int pt_ctx_render_adaptive(pt_ctx *c, const pt_config *cfg, const pt_adaptive_params *params, void *d_out_rgb, uint32_t *d_spp,
                            float *d_error, void *hip_stream, const volatile uint8_t *cancel, pt_progress_fn cb, void *user,
                            pt_stats *stats, pt_adaptive_stats *astats) {
-    if (!cfg || !params || !d_out_rgb || !astats) {
-        set_error("NULL argument");
-        return PT_ERR_INVALID;
-    }
-    if (!(params->tile_error >= 0.0f && params->tile_error < __builtin_inff())) {  // (false for a NaN)
-        set_error("adaptive: tile_error must be finite and not negative");
-        return PT_ERR_INVALID;
-    }
-    const uint32_t tile = params->tile ? params->tile : 8u;
-    if (tile != 4u && tile != 8u && tile != 16u && tile != 32u) {
-        set_error("adaptive: tile must be 4, 8, 16 or 32 (0 = 8)");
-        return PT_ERR_INVALID;
-    }
-    if (!c) {
-        set_error("ctx is NULL");
-        return PT_ERR_INVALID;
-    }
-    if (!c->has_scene) {
-        set_error("no scene set");
-        return PT_ERR_INVALID;
-    }
-    if (cfg->width != 0u && (cfg->idx_begin % cfg->width != 0u || cfg->idx_end % cfg->width != 0u)) {
-        set_error("adaptive: the band must consist of whole image rows");
-        return PT_ERR_INVALID;
-    }
-    if (cfg->chunk_step > 1u || ((cfg->flags >> 8) & 15u) != 0u) {
-        set_error("adaptive: chunk_step > 1 and PT_FLAG_PIPELINES are not supported");
-        return PT_ERR_INVALID;
-    }
-    uint32_t ib = 0, ie = 0;
-    int rc = check_cfg(cfg, &ib, &ie);
+    if (!cfg || !params || !d_out_rgb || !astats) return refuse("NULL argument");
+    uint32_t tile_shift = 0, ib = 0, ie = 0;
+    int rc = host::check_adaptive_params(*params, &tile_shift);
     if (rc) return rc;
+    if (!c) return refuse("ctx is NULL");
+    if (!c->has_scene) return refuse("no scene set");
+    if ((rc = host::check_adaptive_cfg(*cfg)) || (rc = check_cfg(cfg, &ib, &ie))) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    const double t0 = now_ms();
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    if (stats) memset(stats, 0, sizeof *stats);
-    memset(astats, 0, sizeof *astats);
-    pt_stats ps{};
-    const FrameForm form = form_for(c, cfg->flags);
-    const DevScene &S = form.scene;
-    const LdsLayout lay = lds_layout(S, 1u, c->tune.lds_pad);
-    TileParams F{};
-    static_cast<FrameParams &>(F) = make_frame(c, cfg, ib, ie);
-    F.chunk_step = 0u;
-    const uint32_t npix = ie - ib;
-    TileGrid G{};
-    G.width = cfg->width;
-    G.rows = npix / cfg->width;
-    G.tile_shift = tile == 4u ? 2u : (tile == 8u ? 3u : (tile == 16u ? 4u : 5u));
-    G.tiles_x = (G.width + tile - 1u) / tile;
-    G.tiles = G.tiles_x * ((G.rows + tile - 1u) / tile);
-    if ((uint64_t)G.tiles * tile * tile >= (1ull << 32)) {  // (the compact accumulator is indexed with 32 bits)
-        set_error("adaptive: the band's tiles hold 2^32 pixels or more");
-        return PT_ERR_INVALID;
-    }
-    F.tile_shift = G.tile_shift;
-    F.tiles_x = G.tiles_x;
-    F.rows = G.rows;
-    if ((rc = c->ad_held.ensure(3 * (size_t)npix)) || (rc = c->ad_a.ensure(3 * (size_t)npix)) || (rc = c->ad_err.ensure(G.tiles)) ||
-        (rc = c->ad_spp.ensure(G.tiles)) || (rc = c->ad_open[0].ensure(G.tiles)) || (rc = c->ad_open[1].ensure(G.tiles)) ||
-        (rc = c->ad_cnt.ensure(2)) || (rc = c->ad_rays.ensure(16)))
-        return rc;
-    G.spp = c->ad_spp.p;
-    G.err = c->ad_err.p;
-    hipEvent_t ev0 = get_event(c, 6), ev1 = get_event(c, 7);  // (0..5 are the rounds' pacer's)
-    if (!ev0 || !ev1) {
-        set_error("hipEventCreate failed");
-        return PT_ERR_HIP;
-    }
-    HIP_TRY(hipEventRecord(ev0, st));
-    HIP_TRY(hipMemsetAsync(c->ad_held.p, 0, 3 * (size_t)npix * sizeof(unsigned long long), st));
-    HIP_TRY(hipMemsetAsync(c->ad_a.p, 0, 3 * (size_t)npix * sizeof(unsigned long long), st));
-    HIP_TRY(hipMemsetAsync(c->ad_err.p, 0xff, (size_t)G.tiles * sizeof(unsigned long long), st));  // kTileNoError
-    HIP_TRY(hipMemsetAsync(c->ad_spp.p, 0, (size_t)G.tiles * sizeof(uint32_t), st));
-    HIP_TRY(hipMemsetAsync(c->ad_rays.p, 0, 16 * sizeof(unsigned long long), st));
-    launch_tile_begin(st, d_error, npix, c->ad_open[0].p, G.tiles);
-    struct Clear {  // (the rounds' pacer notes its samples in the live frame: pt_ctx_snapshot finds none afterwards)
-        pt_ctx *c;
-        ~Clear() { c->live = LiveFrame{}; }
-    } clear{c};
-    c->live.cb_last_ms = now_ms();
-    hipDeviceProp_t prop;
-    HIP_TRY(hipGetDeviceProperties(&prop, c->device));
-    const uint32_t cap = cfg->spp;
-    const unsigned long long q = (unsigned long long)__builtin_floor((double)params->tile_error * 268435456.0);
-    uint32_t level = (params->min_spp ? params->min_spp : 16u);
-    level = level > 0xfffffff8u ? cap : (level + 7u) / 8u * 8u;
-    if (level > cap) level = cap;
-    uint32_t have = 0, n_a = 0, n_open = G.tiles, which = 0;
-    uint64_t samples = 0;
-    bool cancelled = false;
-    astats->tiles = G.tiles;
-    for (uint32_t j = 0; n_open != 0u && have < cap && j < 32u; ++j) {
-        cancelled = cancel && *cancel;
-        if (!cancelled && cb && j != 0u && progress(c, cfg, cb, user, (float)((double)samples / ((double)npix * cap))))
-            cancelled = cancel && *cancel;  // raised from inside the callback
-        if (cancelled) break;
-        // [have, m) to half A, [m, level) to half B: the rule of a tracked pt_ctx_accumulate call (ptrace.h)
-        const uint32_t m_a = have + 4u * ((level - have + 7u) / 8u), m = m_a < level ? m_a : level;
-        F.open = c->ad_open[which].p;
-        n_a += m - have;
-        const uint32_t n_b = level - n_a;
-        TileLevel V{};
-        V.open = F.open;
-        V.n_open = n_open;
-        V.spp = level;
-        V.q = q;
-        V.next = c->ad_open[which ^ 1u].p;
-        V.counters = reinterpret_cast<uint32_t *>(c->ad_cnt.p + 1);
-        V.fa = (float)n_a;
-        V.fb = (float)n_b;
-        V.fn = (float)level;
-        V.w = n_b != 0u ? host::noise_part_weight(n_a, n_b) : 0.0f;
-        HIP_TRY(hipMemsetAsync(c->ad_cnt.p + 1, 0, sizeof(unsigned long long), st));
-        for (uint32_t run = 0; run < (m < level ? 2u : 1u); ++run) {
-            const uint32_t r0 = run ? m : have, r1 = run ? level : m;
-            if ((rc = tile_run(c, S, lay, cfg, F, n_open, r0, r1, st, (uint32_t)prop.multiProcessorCount, ps))) return rc;
-            V.acc = c->ad_acc.p;
-            V.to_a = run == 0u ? 1u : 0u;
-            V.evaluate = r1 == level ? 1u : 0u;
-            V.estimate = V.evaluate && n_b != 0u ? 1u : 0u;
-            launch_tile_level(st, G, V, c->ad_held.p, c->ad_a.p, d_error);
-        }
-        HIP_TRY(hipGetLastError());
-        uint32_t back[2] = {0u, 0u};  // the next list's length, the tiles closed: all that comes back per level
-        HIP_TRY(hipMemcpyAsync(back, c->ad_cnt.p + 1, sizeof back, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        // (partial tiles counted whole: this only feeds the progress fraction; the exact total comes from the counts at the end)
-        samples += (uint64_t)n_open * tile * tile * (level - have);
-        if (samples > (uint64_t)npix * cap) samples = (uint64_t)npix * cap;
-        astats->level_spp[j] = level;
-        astats->tiles_closed[j] = back[1];
-        astats->levels = j + 1u;
-        n_open = back[0];
-        which ^= 1u;
-        have = level;
-        level = level > cap / 2u ? cap : level * 2u;
-    }
-    astats->tiles_open = n_open;
-    // the outputs: every pixel over its tile's count, the counts, the sum of E over the tiles
-    HIP_TRY(hipMemsetAsync(c->ad_cnt.p, 0, sizeof(unsigned long long), st));
-    launch_tile_resolve(st, G, c->ad_held.p, (float *)d_out_rgb, d_spp, c->ad_cnt.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ev1, st));
-    unsigned long long err_sum = 0, rays[16] = {0};
-    std::vector<uint32_t> tile_spp(G.tiles);
-    std::vector<unsigned long long> tile_err(G.tiles);
-    HIP_TRY(hipMemcpyAsync(&err_sum, c->ad_cnt.p, sizeof err_sum, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(rays, c->ad_rays.p, sizeof rays, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(tile_spp.data(), c->ad_spp.p, (size_t)G.tiles * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(tile_err.data(), c->ad_err.p, (size_t)G.tiles * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (rays[1]) {
-        set_error("tile pass: a lane's split stack overflowed");
-        return PT_ERR_OVERFLOW;
-    }
-    uint64_t total = 0, est_pixels = 0;
-    for (uint32_t t = 0; t < G.tiles; ++t) {
-        const uint32_t tx = t % G.tiles_x, ty = t / G.tiles_x;
-        const uint32_t w = G.width - tx * tile < tile ? G.width - tx * tile : tile, h = G.rows - ty * tile < tile ? G.rows - ty * tile : tile;
-        total += (uint64_t)w * h * tile_spp[t];
-        if (tile_err[t] != kTileNoError) est_pixels += (uint64_t)w * h;
-    }
-    astats->samples = total;
-    astats->mean_error = est_pixels == (uint64_t)npix ? (double)err_sum * (1.0 / 268435456.0) / (double)npix : (double)__builtin_inff();
-    ps.samples = total;
-    ps.ray_bounces = rays[0];
-    float ms_dev = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&ms_dev, ev0, ev1));
-    ps.ms_device = ms_dev;
-    ps.ms_total = now_ms() - t0;
-    if (stats) *stats = ps;
-    if (cancelled) {
-        set_error("cancelled");
-        return PT_CANCELLED;
-    }
-    if (cb) cb(user, 1.0f);
-    return PT_OK;
+    return render_adaptive(c, cfg, ib, ie, tile_shift, params, (float *)d_out_rgb, d_spp, d_error,
+                           hip_stream ? (hipStream_t)hip_stream : c->stream, cancel, cb, user, stats, astats);
 }
 
 int pt_ctx_radiance(pt_ctx *c, const float o[3], const float d[3], uint32_t depth, uint32_t n_samples, uint64_t seed,
@@ -2458,44 +2390,20 @@ int pt_ctx_denoise(pt_ctx *c, uint32_t width, uint32_t height, const pt_denoise_
     // everything that can be refused is refused here, before the device is touched
     pt_denoise_params P = kDenoiseDefaults;
     if (params) {
-        auto bad_sigma = [](float v) { return !(v >= 0.0f) || v == __builtin_inff(); };
-        if (params->levels > 8u) {
-            set_error("pt_denoise_params.levels exceeds 8");
-            return PT_ERR_INVALID;
-        }
-        if (bad_sigma(params->sigma_color) || bad_sigma(params->sigma_depth)) {
-            set_error("pt_denoise_params: a sigma is negative or not finite");
-            return PT_ERR_INVALID;
-        }
-        if (!(params->sigma_normal_pow == 0.0f)) {
-            set_error("pt_denoise_params.sigma_normal_pow is reserved and must be 0");
-            return PT_ERR_INVALID;
-        }
-        if (params->flags & ~PT_DENOISE_NO_DEMODULATE) {
-            set_error("pt_denoise_params.flags: unknown bits");
-            return PT_ERR_INVALID;
-        }
+        if (params->levels > 8u) return refuse("pt_denoise_params.levels exceeds 8");
+        if (!host::finite_nonneg(params->sigma_color) || !host::finite_nonneg(params->sigma_depth))
+            return refuse("pt_denoise_params: a sigma is negative or not finite");
+        if (!(params->sigma_normal_pow == 0.0f)) return refuse("pt_denoise_params.sigma_normal_pow is reserved and must be 0");
+        if (params->flags & ~PT_DENOISE_NO_DEMODULATE) return refuse("pt_denoise_params.flags: unknown bits");
         if (params->levels) P.levels = params->levels;
         if (params->sigma_color != 0.0f) P.sigma_color = params->sigma_color;
         if (params->sigma_depth != 0.0f) P.sigma_depth = params->sigma_depth;
         P.flags = params->flags;
     }
-    if (!width || !height) {
-        set_error("width and height must be positive");
-        return PT_ERR_INVALID;
-    }
-    if ((uint64_t)width * height > (1ull << 28)) {
-        set_error("width*height exceeds 2^28");
-        return PT_ERR_INVALID;
-    }
-    if (!d_color || !d_out) {
-        set_error("d_color or d_out is NULL");
-        return PT_ERR_INVALID;
-    }
-    if (!c) {
-        set_error("ctx is NULL");
-        return PT_ERR_INVALID;
-    }
+    if (!width || !height) return refuse("width and height must be positive");
+    if ((uint64_t)width * height > (1ull << 28)) return refuse("width*height exceeds 2^28");
+    if (!d_color || !d_out) return refuse("d_color or d_out is NULL");
+    if (!c) return refuse("ctx is NULL");
     return run_denoise(c, width, height, P.levels, P.sigma_color, P.sigma_depth, P.flags, d_color, nullptr, d_albedo, d_normal,
                        d_depth, d_out, hip_stream);
 }
@@ -2518,48 +2426,21 @@ int pt_ctx_denoise_var(pt_ctx *c, uint32_t width, uint32_t height, const pt_deno
     // everything that can be refused is refused here, before the device is touched
     pt_denoise_var_params P = kDenoiseVarDefaults;
     if (params) {
-        auto bad_sigma = [](float v) { return !(v >= 0.0f) || v == __builtin_inff(); };
-        if (params->levels > 8u) {
-            set_error("pt_denoise_var_params.levels exceeds 8");
-            return PT_ERR_INVALID;
-        }
-        if (bad_sigma(params->sigma_var) || bad_sigma(params->sigma_depth)) {
-            set_error("pt_denoise_var_params: a sigma is negative or not finite");
-            return PT_ERR_INVALID;
-        }
-        if (params->flags & ~PT_DENOISE_NO_DEMODULATE) {
-            set_error("pt_denoise_var_params.flags: unknown bits");
-            return PT_ERR_INVALID;
-        }
+        if (params->levels > 8u) return refuse("pt_denoise_var_params.levels exceeds 8");
+        if (!host::finite_nonneg(params->sigma_var) || !host::finite_nonneg(params->sigma_depth))
+            return refuse("pt_denoise_var_params: a sigma is negative or not finite");
+        if (params->flags & ~PT_DENOISE_NO_DEMODULATE) return refuse("pt_denoise_var_params.flags: unknown bits");
         if (params->levels) P.levels = params->levels;
         if (params->sigma_var != 0.0f) P.sigma_var = params->sigma_var;
         if (params->sigma_depth != 0.0f) P.sigma_depth = params->sigma_depth;
         P.flags = params->flags;
     }
-    if (!width || !height) {
-        set_error("width and height must be positive");
-        return PT_ERR_INVALID;
-    }
-    if ((uint64_t)width * height > (1ull << 28)) {
-        set_error("width*height exceeds 2^28");
-        return PT_ERR_INVALID;
-    }
-    if (!d_color) {
-        set_error("d_color is NULL");
-        return PT_ERR_INVALID;
-    }
-    if (!d_error) {
-        set_error("d_error is NULL: pt_ctx_denoise is the filter without a noise estimate");
-        return PT_ERR_INVALID;
-    }
-    if (!d_out) {
-        set_error("d_out is NULL");
-        return PT_ERR_INVALID;
-    }
-    if (!c) {
-        set_error("ctx is NULL");
-        return PT_ERR_INVALID;
-    }
+    if (!width || !height) return refuse("width and height must be positive");
+    if ((uint64_t)width * height > (1ull << 28)) return refuse("width*height exceeds 2^28");
+    if (!d_color) return refuse("d_color is NULL");
+    if (!d_error) return refuse("d_error is NULL: pt_ctx_denoise is the filter without a noise estimate");
+    if (!d_out) return refuse("d_out is NULL");
+    if (!c) return refuse("ctx is NULL");
     return run_denoise(c, width, height, P.levels, P.sigma_var, P.sigma_depth, P.flags, d_color, d_error, d_albedo, d_normal,
                        d_depth, d_out, hip_stream);
 }

@@ -2091,4 +2091,7 @@ __device__ __forceinline__ uint64_t to_fixed(float v) {
 
 #endif  // __HIPCC__
 
+// pt_ctx_render_adaptive's per-tile E (pt_tile.h: TileGrid::err) before the tile's first evaluation; the host's totals read it too
+constexpr unsigned long long kTileNoError = ~0ull;
+
 }  // namespace pt

@@ -826,40 +826,44 @@ uint32_t next_pass_samples(double rate, double target_ms, uint64_t npix, uint64_
     return (left + n_left - 1u) / n_left;
 }
 
+RoundPlan plan_rounds(uint64_t entries, uint32_t spp_left, uint64_t rays_per_pass, uint32_t item_mult, uint32_t n_cus) {
+    const uint64_t round_budget = rays_per_pass ? rays_per_pass : (256ull << 20);  // primary samples per launch
+    uint64_t round_spp = round_budget / entries;
+    if (round_spp == 0) round_spp = 1;
+    if (round_spp > spp_left) round_spp = spp_left;
+    RoundPlan p{(uint32_t)round_spp, 1u};
+    // (k_mega_cand hands its items out dynamically: finer ones - 8 per lane the chip holds, cornell 41.3 G bounces/s; 4: 39.1,
+    // 16: 40.5, 32: 38.4 - so that a launch's last items are a small part of it)
+    const uint64_t want_items = (uint64_t)item_mult * n_cus * 2048u;
+    while (entries * p.n_split < want_items && p.n_split < p.round_spp) p.n_split *= 2;
+    if (p.n_split > p.round_spp) p.n_split = p.round_spp;
+    return p;
+}
+
+RoundLaunch round_launch(uint64_t entries, uint32_t n_split, uint32_t s_here, uint32_t n_cus) {
+    RoundLaunch l;
+    l.split = n_split < s_here ? n_split : s_here;
+    l.lane_spp = (s_here + l.split - 1) / l.split;
+    const uint64_t grid = (entries * l.split + kBlock - 1) / kBlock, max_grid = (uint64_t)n_cus * 8u;
+    l.grid = (uint32_t)(grid < max_grid ? grid : max_grid);
+    if (l.grid == 0u) l.grid = 1u;
+    return l;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Frame calls and the held frame of pt_ctx_accumulate
 int check_cfg(const pt_config *cfg, uint32_t *idx_begin, uint32_t *idx_end) {
-    if (!cfg) {
-        set_error("cfg is NULL");
-        return PT_ERR_INVALID;
-    }
-    if (cfg->width == 0 || cfg->height == 0 || cfg->spp == 0) {
-        set_error("width, height and spp must be positive");
-        return PT_ERR_INVALID;
-    }
+    if (!cfg) return refuse("cfg is NULL");
+    if (cfg->width == 0 || cfg->height == 0 || cfg->spp == 0) return refuse("width, height and spp must be positive");
     const uint64_t npix = (uint64_t)cfg->width * cfg->height;
-    if (npix > 0x7fffffffull) {
-        set_error("width*height exceeds 2^31-1");
-        return PT_ERR_INVALID;
-    }
-    if (cfg->spp > (1u << 24)) {
-        set_error("spp exceeds 2^24");
-        return PT_ERR_INVALID;
-    }
+    if (npix > 0x7fffffffull) return refuse("width*height exceeds 2^31-1");
+    if (cfg->spp > (1u << 24)) return refuse("spp exceeds 2^24");
     uint32_t b = cfg->idx_begin, e = cfg->idx_end;
     if (b == 0 && e == 0) e = (uint32_t)npix;
-    if (b >= e || e > npix) {
-        set_error("band [idx_begin, idx_end) is empty or outside the frame");
-        return PT_ERR_INVALID;
-    }
-    if (cfg->backend != PT_BACKEND_WAVEFRONT && cfg->backend != PT_BACKEND_MEGAKERNEL) {
-        set_error("unknown backend");
-        return PT_ERR_INVALID;
-    }
-    if (cfg->chunk_step > 1u && (cfg->chunk_pixels == 0u || cfg->chunk_first >= cfg->chunk_step)) {
-        set_error("chunk_pixels must be positive and chunk_first < chunk_step");
-        return PT_ERR_INVALID;
-    }
+    if (b >= e || e > npix) return refuse("band [idx_begin, idx_end) is empty or outside the frame");
+    if (cfg->backend != PT_BACKEND_WAVEFRONT && cfg->backend != PT_BACKEND_MEGAKERNEL) return refuse("unknown backend");
+    if (cfg->chunk_step > 1u && (cfg->chunk_pixels == 0u || cfg->chunk_first >= cfg->chunk_step))
+        return refuse("chunk_pixels must be positive and chunk_first < chunk_step");
     *idx_begin = b;
     *idx_end = e;
     return PT_OK;
@@ -900,8 +904,7 @@ std::vector<Job> accum_jobs(const FrameCounts &f, uint32_t spp, bool megakernel)
         const uint32_t c = f.cnt[part_lo];
         const float base = (float)p.k0 / (float)f.total, scale = (float)p.n / (float)f.total;
         if (f.tracked() && c < spp) {
-            const uint64_t m64 = (uint64_t)c + 4ull * (((uint64_t)(spp - c) + 7ull) / 8ull);
-            const uint32_t m = m64 < spp ? (uint32_t)m64 : spp;
+            const uint32_t m = tracked_split(c, spp);
             // (a renderer reports the samples issued over its job's last sample: the first job's fractions are scaled to the call's)
             const float f1 = (float)m / (float)spp;
             jobs.push_back({p.k0, p.n, c, base, scale * f1, part_lo, part_hi, m});
@@ -1061,6 +1064,55 @@ uint32_t noise_quantile_bin(const pt_noise_stats &s, float quantile) {
 bool noise_target_met(const pt_noise_stats &s, const pt_noise_target &t) {
     if (t.mean_error != 0.0f && !(s.mean_error <= (double)t.mean_error)) return false;
     return t.quantile == 0.0f || noise_bin_upper(noise_quantile_bin(s, t.quantile)) <= t.quantile_error;
+}
+
+int check_noise_target(const pt_noise_target &t) {
+    if (!finite_nonneg(t.mean_error) || !finite_nonneg(t.quantile) || !finite_nonneg(t.quantile_error))
+        return refuse("noise target: mean_error, quantile and quantile_error must be finite and not negative");
+    if (t.mean_error == 0.0f && t.quantile == 0.0f) return refuse("noise target: neither mean_error nor quantile is in use");
+    if (!(t.quantile < 1.0f)) return refuse("noise target: quantile must lie in (0, 1)");
+    return PT_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Adaptive sampling
+int check_adaptive_params(const pt_adaptive_params &p, uint32_t *tile_shift) {
+    if (!finite_nonneg(p.tile_error)) return refuse("adaptive: tile_error must be finite and not negative");
+    const uint32_t tile = p.tile ? p.tile : 8u;
+    if (tile != 4u && tile != 8u && tile != 16u && tile != 32u) return refuse("adaptive: tile must be 4, 8, 16 or 32 (0 = 8)");
+    *tile_shift = tile == 4u ? 2u : (tile == 8u ? 3u : (tile == 16u ? 4u : 5u));
+    return PT_OK;
+}
+
+int check_adaptive_cfg(const pt_config &cfg) {
+    if (cfg.width != 0u && (cfg.idx_begin % cfg.width != 0u || cfg.idx_end % cfg.width != 0u))
+        return refuse("adaptive: the band must consist of whole image rows");
+    if (cfg.chunk_step > 1u || ((cfg.flags >> 8) & 15u) != 0u)
+        return refuse("adaptive: chunk_step > 1 and PT_FLAG_PIPELINES are not supported");
+    return PT_OK;
+}
+
+int tile_geometry(uint32_t width, uint32_t rows, uint32_t tile_shift, TileGeometry &out) {
+    const uint64_t tile = 1ull << tile_shift;
+    const uint64_t tiles_x = (width + tile - 1u) / tile, tiles = tiles_x * ((rows + tile - 1u) / tile);
+    if (tiles * tile * tile >= (1ull << 32)) return refuse("adaptive: the band's tiles hold 2^32 pixels or more");
+    out = {tile_shift, (uint32_t)tiles_x, (uint32_t)tiles};
+    return PT_OK;
+}
+
+TileTotals tile_totals(uint32_t width, uint32_t rows, const TileGeometry &g, const uint32_t *tile_spp, const unsigned long long *tile_err,
+                       unsigned long long err_sum) {
+    const uint32_t tile = 1u << g.tile_shift;
+    TileTotals t{};
+    for (uint32_t i = 0; i < g.tiles; ++i) {
+        const uint32_t x0 = i % g.tiles_x * tile, y0 = i / g.tiles_x * tile;
+        const uint64_t pixels = (uint64_t)std::min(width - x0, tile) * std::min(rows - y0, tile);
+        t.samples += pixels * tile_spp[i];
+        if (tile_err[i] != kTileNoError) t.est_pixels += pixels;
+    }
+    const uint64_t npix = (uint64_t)width * rows;
+    t.mean_error = t.est_pixels == npix ? (double)err_sum * (1.0 / 268435456.0) / (double)npix : std::numeric_limits<double>::infinity();
+    return t;
 }
 
 }  // namespace host

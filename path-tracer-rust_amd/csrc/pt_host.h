@@ -11,6 +11,11 @@
 namespace pt {
 
 void set_error(const std::string &m);
+// a refusal of the caller's arguments: the message is set, the code is the one to return
+inline int refuse(const char *why) {
+    set_error(why);
+    return PT_ERR_INVALID;
+}
 
 namespace host {
 
@@ -85,6 +90,19 @@ int plan_pass(const PassPlanIn &in, PassPlan &out, uint64_t *want_next);
 // rather than one pass more.
 uint32_t next_pass_samples(double rate, double target_ms, uint64_t npix, uint64_t probe, uint32_t s_prev, uint32_t left,
                            uint32_t max_pass);
+// How the megakernel and the tile pass cut the samples of `entries` items (a part's pixels; the compact accumulator's entries) into
+// ROUNDS (run_rounds, pt_api.hip).  A round is every item x round_spp consecutive samples in one launch: rays_per_pass primary
+// samples (0: 256 Mi), at least one per item, at most spp_left.  Few items get n_split lanes each - doubled until there are
+// item_mult items per lane of the 2048 a compute unit holds, at most round_spp - so that a launch still fills the chip.
+struct RoundPlan {
+    uint32_t round_spp, n_split;
+};
+RoundPlan plan_rounds(uint64_t entries, uint32_t spp_left, uint64_t rays_per_pass, uint32_t item_mult, uint32_t n_cus);
+// A launch of s_here (> 0) samples: `split` lanes of lane_spp samples per item, on at most 8 workgroups per compute unit
+struct RoundLaunch {
+    uint32_t split, lane_spp, grid;
+};
+RoundLaunch round_launch(uint64_t entries, uint32_t n_split, uint32_t s_here, uint32_t n_cus);
 bool flatten_scene(const pt_camera &cam, const pt_object *objs, uint32_t n_objs, const pt_triangle *tris,
                    uint32_t n_tris, FlatScene &out, std::string &err);
 
@@ -182,6 +200,47 @@ float noise_bin_upper(uint32_t b);
 uint32_t noise_quantile_bin(const pt_noise_stats &s, float quantile);
 // is an estimate within the target: its criteria in use (non-zero mean_error, non-zero quantile), all of them
 bool noise_target_met(const pt_noise_stats &s, const pt_noise_target &t);
+// what the entry points ask of a tolerance or a sigma (false for a NaN)
+inline bool finite_nonneg(float v) { return v >= 0.0f && v < __builtin_inff(); }
+// pt_ctx_accumulate_until's refusals about its target, in the header's order: PT_ERR_INVALID + message
+int check_noise_target(const pt_noise_target &t);
+
+// ---- the sample schedules of the calls that render to a noise target (ptrace.h states them)
+// samples [c, T) of a tracked part or an open tile: half A's up to m = min(T, c + 4 * ceil((T - c) / 8)), half B's from there
+inline uint32_t tracked_split(uint32_t c, uint32_t T) {
+    const uint64_t m = (uint64_t)c + 4ull * (((uint64_t)(T - c) + 7ull) / 8ull);
+    return m < T ? (uint32_t)m : T;
+}
+// the count after t: twice as many, never beyond the cap
+inline uint32_t next_target(uint32_t t, uint32_t cap) { return t > cap / 2u ? cap : t * 2u; }
+// The first count, min_spp 0 = 16.  pt_ctx_accumulate_until: that or what is held, whichever is more.  pt_ctx_render_adaptive:
+// rounded up to a multiple of 8, so that the first level fills both halves evenly.
+inline uint32_t until_first_target(uint32_t held, uint32_t min_spp, uint32_t cap) {
+    return std::min(cap, std::max(held, min_spp ? min_spp : 16u));
+}
+inline uint32_t adaptive_first_level(uint32_t min_spp, uint32_t cap) {
+    const uint32_t n = min_spp ? min_spp : 16u;
+    return n > 0xfffffff8u ? cap : std::min(cap, (n + 7u) / 8u * 8u);
+}
+
+// ---- pt_ctx_render_adaptive: its refusals in the header's order (PT_ERR_INVALID + message), its tiles, its totals
+// tile_error, then the tile edge (0 = 8), whose log2 goes to *tile_shift
+int check_adaptive_params(const pt_adaptive_params &p, uint32_t *tile_shift);
+// the band of whole image rows, then chunk_step and PT_FLAG_PIPELINES
+int check_adaptive_cfg(const pt_config &cfg);
+// TileGrid's geometry (pt_tile.h) for a band of `rows` rows; refused: tiles that hold 2^32 entries or more (32-bit indices)
+struct TileGeometry {
+    uint32_t tile_shift, tiles_x, tiles;
+};
+int tile_geometry(uint32_t width, uint32_t rows, uint32_t tile_shift, TileGeometry &out);
+// From the tiles' counts, their last E (kTileNoError: none) and the device's sum of the E: the samples traced, the pixels that
+// have an estimate - a partial tile counts the pixels it has inside the band - and the mean error, +inf unless every pixel has one
+struct TileTotals {
+    uint64_t samples, est_pixels;
+    double mean_error;
+};
+TileTotals tile_totals(uint32_t width, uint32_t rows, const TileGeometry &g, const uint32_t *tile_spp, const unsigned long long *tile_err,
+                       unsigned long long err_sum);
 
 }  // namespace host
 }  // namespace pt

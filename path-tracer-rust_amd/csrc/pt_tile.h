@@ -50,9 +50,8 @@ struct TileGrid {
     uint32_t width, rows;  // the band: whole rows
     uint32_t tile_shift, tiles_x, tiles;
     uint32_t *spp;            // samples every pixel of the tile holds
-    unsigned long long *err;  // E of the tile's last evaluation; kTileNoError before the first
+    unsigned long long *err;  // E of the tile's last evaluation; kTileNoError (pt_device.h) before the first
 };
-constexpr unsigned long long kTileNoError = ~0ull;
 
 // What a run of a level does with the compact accumulator once its samples are traced.
 struct TileLevel {

@@ -254,3 +254,21 @@ def test_isolation_from_the_held_frame_and_between_calls(L, scenes):
             assert (x["st"].samples, x["st"].ray_bounces, x["ast"].mean_error) == (a["st"].samples, a["st"].ray_bounces, a["ast"].mean_error)
     finally:
         d.close()
+
+
+def test_the_tile_pass_rounds_are_counted(L, scenes):
+    """Rounds only batch the samples, so no image shows how many there were: pt_stats.passes does.  32 x 32 in tiles of 8, one
+    level of 16 samples (min_spp = cap = 16; tile_error 0 leaves every tile open), rays_per_pass = 4096: the level's runs are [0, 8)
+    and [8, 16), each over 16 tiles x 64 = 1024 entries in rounds of 4096 / 1024 = 4 samples - two launches per run, four in all."""
+    w = h = 32
+    d = ADev(L, scenes["cornell"], w * h)
+    try:
+        r = d.adaptive(cfg_of(16, w=w, h=h, rays_per_pass=4096), 0.0, min_spp=16)
+        whole = d.adaptive(cfg_of(16, w=w, h=h), 0.0, min_spp=16)
+    finally:
+        d.close()
+    assert r["ast"].levels == 1 and r["ast"].level_spp[0] == 16
+    assert r["st"].passes == 4 and whole["st"].passes == 2
+    assert r["st"].samples == r["ast"].samples == w * h * 16 and (r["spp"] == 16).all()
+    assert r["st"].ray_bounces == whole["st"].ray_bounces
+    assert np.array_equal(r["img"].view(np.uint32), whole["img"].view(np.uint32))

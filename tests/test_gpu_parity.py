@@ -241,6 +241,18 @@ def test_many_passes_and_odd_sizes(gpu):
     assert np.array_equal(got1, got)  # the image does not depend on the pass size (integer accumulation)
 
 
+def test_megakernel_rounds_are_counted(gpu):
+    """The megakernel's rounds only batch the samples, so no image shows how many there were: pt_stats.passes does.  32 x 32 at
+    8 samples with rays_per_pass = 2048: a round is 2048 / 1024 = 2 samples of every pixel, four launches."""
+    sc = ptlib.load_scene_py(ptlib.scene_path("cornell"))
+    w, h, spp = 32, 32, 8
+    got, st = gpu_render(gpu, sc, w, h, spp, 9, ptlib.BACKEND_MEGAKERNEL, rays_per_pass=2048)
+    whole, st0 = gpu_render(gpu, sc, w, h, spp, 9, ptlib.BACKEND_MEGAKERNEL)
+    assert st.passes == 4 and st0.passes == 1
+    assert st.samples == st0.samples == w * h * spp and st.ray_bounces == st0.ray_bounces
+    assert np.array_equal(got.view(np.uint32), whole.view(np.uint32))
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("sid", ["cornell", "mesh"])
 def test_primary_ray_order_of_the_pass_kernel(gpu, sid):

@@ -744,3 +744,151 @@ def test_noise_target_decision(tmp_path):
     pairs = [(a, b) for a in range(1, 33) for b in range(1, 33)] + [(20, 44), (3, 16777213), (1, 16777215), (8388608, 8388608)]
     got = [int(v) for v in tool("w", *[n for p in pairs for n in p]).split()]
     assert got == [bits(noise_ref.weight(a, b)) for a, b in pairs]
+
+
+SCHEDULE_SRC = r"""
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+#include "ptrace.h"
+#include "pt_host.h"
+using namespace pt;
+static uint64_t num(const char *s) { return strtoull(s, 0, 0); }
+// argv[1] names the function, the rest are its arguments in order; prints its results (a refusal: REFUSED and the message)
+int main(int argc, char **argv) {
+    const char *f = argv[1];
+    auto arg = [&](int i) { return num(argv[1 + i]); };
+    if (!strcmp(f, "rounds")) {  // entries spp_left rays_per_pass item_mult n_cus s_here..: the plan, then each launch
+        const host::RoundPlan p = host::plan_rounds(arg(1), (uint32_t)arg(2), arg(3), (uint32_t)arg(4), (uint32_t)arg(5));
+        printf("%u %u", p.round_spp, p.n_split);
+        for (int i = 6; 1 + i < argc; ++i) {
+            const host::RoundLaunch l = host::round_launch(arg(1), p.n_split, (uint32_t)arg(i), (uint32_t)arg(5));
+            printf(" %u %u %u", l.split, l.lane_spp, l.grid);
+        }
+        printf("\n");
+    } else if (!strcmp(f, "launch")) {  // entries n_split s_here n_cus
+        const host::RoundLaunch l = host::round_launch(arg(1), (uint32_t)arg(2), (uint32_t)arg(3), (uint32_t)arg(4));
+        printf("%u %u %u\n", l.split, l.lane_spp, l.grid);
+    } else if (!strcmp(f, "split")) {  // c T
+        printf("%u\n", host::tracked_split((uint32_t)arg(1), (uint32_t)arg(2)));
+    } else if (!strcmp(f, "adaptive") || !strcmp(f, "until")) {  // [held] min_spp cap: the counts up to the cap
+        const bool ad = f[0] == 'a';
+        const uint32_t cap = (uint32_t)arg(ad ? 2 : 3);
+        uint32_t t = ad ? host::adaptive_first_level((uint32_t)arg(1), cap) : host::until_first_target((uint32_t)arg(1), (uint32_t)arg(2), cap);
+        for (int i = 0; i < 40; ++i, t = host::next_target(t, cap)) {
+            printf("%u ", t);
+            if (t >= cap) break;
+        }
+        printf("\n");
+    } else if (!strcmp(f, "params")) {  // tile_error tile
+        pt_adaptive_params p{(float)atof(argv[2]), (uint32_t)arg(2), 0u};
+        uint32_t shift = 99;
+        if (host::check_adaptive_params(p, &shift)) printf("REFUSED %s\n", pt_last_error());
+        else printf("%u\n", shift);
+    } else if (!strcmp(f, "cfg")) {  // width idx_begin idx_end chunk_step flags
+        pt_config c{};
+        c.width = (uint32_t)arg(1), c.idx_begin = (uint32_t)arg(2), c.idx_end = (uint32_t)arg(3), c.chunk_step = (uint32_t)arg(4), c.flags = (uint32_t)arg(5);
+        if (host::check_adaptive_cfg(c)) printf("REFUSED %s\n", pt_last_error());
+        else printf("OK\n");
+    } else if (!strcmp(f, "target")) {  // mean_error quantile quantile_error
+        pt_noise_target t{(float)atof(argv[2]), (float)atof(argv[3]), (float)atof(argv[4]), 0u};
+        if (host::check_noise_target(t)) printf("REFUSED %s\n", pt_last_error());
+        else printf("OK\n");
+    } else if (!strcmp(f, "tiles")) {  // width rows tile_shift [err_sum (spp err)..]: err "-" = no error yet
+        host::TileGeometry g{};
+        if (host::tile_geometry((uint32_t)arg(1), (uint32_t)arg(2), (uint32_t)arg(3), g)) { printf("REFUSED %s\n", pt_last_error()); return 0; }
+        printf("%u %u %u", g.tile_shift, g.tiles_x, g.tiles);
+        if (argc > 5) {
+            std::vector<uint32_t> spp;
+            std::vector<unsigned long long> err;
+            for (int i = 5; 1 + i + 1 < argc; i += 2) {
+                spp.push_back((uint32_t)arg(i));
+                err.push_back(argv[1 + i + 1][0] == '-' ? kTileNoError : arg(i + 1));
+            }
+            if (spp.size() != g.tiles) return 2;
+            const host::TileTotals t = host::tile_totals((uint32_t)arg(1), (uint32_t)arg(2), g, spp.data(), err.data(), arg(4));
+            printf(" %llu %llu %.17g", (unsigned long long)t.samples, (unsigned long long)t.est_pixels, t.mean_error);
+        }
+        printf("\n");
+    } else {
+        return 2;
+    }
+    return 0;
+}
+"""
+
+
+def test_rounds_schedules_and_tiles(tmp_path):
+    """The host arithmetic of the megakernel's and the tile pass's rounds (host::plan_rounds / round_launch), the sample schedules
+    of the calls that render to a noise target (tracked_split, next_target and the two first counts), and pt_ctx_render_adaptive's
+    refusals, tile geometry and totals - on values worked by hand from their definitions."""
+    tool = _host_tool(tmp_path, "schedule", SCHEDULE_SRC)
+    ask = lambda *a: tool(*a).strip()
+    nums = lambda *a: [int(v) for v in ask(*a).split()]
+    # the bench frame on 256 CUs: 256 Mi / 786432 = 341 samples per round; 8 x 256 x 2048 items are wanted, 786432 x 8 reaches
+    # them; a round of 341 is 8 lanes of ceil(341 / 8) = 43 samples per pixel, on the 8 x 256 workgroups the grid is capped at
+    assert nums("rounds", 1024 * 768, 4096, 0, 8, 256, 341) == [341, 8, 8, 43, 2048]
+    # three open tiles of 8 x 8 with 8 samples left: split eightfold (4 x 256 x 2048 items is out of reach: n_split <= round_spp),
+    # 192 x 8 = 1536 items in 6 workgroups of 256
+    assert nums("rounds", 192, 8, 0, 4, 256, 8) == [8, 8, 8, 1, 6]
+    assert nums("rounds", 1024, 100, 4096, 8, 256)[0] == 4                # an explicit budget: 4096 / 1024
+    assert nums("rounds", 5000, 100, 4096, 8, 256)[:2] == [1, 1]          # more entries than the budget: one sample, no split
+    assert nums("rounds", 1024, 3, 0, 8, 256)[:2] == [3, 3]               # clipped to what is left; n_split to round_spp
+    assert nums("rounds", 1 << 25, 64, 0, 8, 256) == [8, 1]               # enough items without a split
+    assert nums("launch", 192, 8, 3, 256) == [3, 1, 3]                    # fewer samples than lanes: one lane per sample
+    assert nums("launch", 192, 8, 5, 256) == [5, 1, 4]
+    assert nums("launch", 1024, 4, 7, 256) == [4, 2, 16]
+    assert nums("launch", 0, 1, 1, 256) == [1, 1, 1]                      # never an empty grid
+    assert nums("launch", 1 << 31, 8, 8, 256) == [8, 1, 2048]             # (64-bit item counts)
+    # m = min(T, c + 4 * ceil((T - c) / 8))
+    for c, t, m in ((0, 16, 8), (16, 32, 24), (64, 100, 84), (0, 10, 8), (0, 3, 3), (0, 4, 4), (0, 5, 4), (7, 7, 7), (0, 0, 0),
+                    (0, 1 << 24, 1 << 23), (0, 0xffffffff, 0x80000000), (0xfffffff0, 0xffffffff, 0xfffffff8)):
+        assert nums("split", c, t) == [m], (c, t)
+    # accum_jobs cuts a tracked part at exactly this value
+    sched = _host_tool(tmp_path, "sched", SCHED_SRC)
+    for c, na, t in ((0, 0, 16), (16, 8, 32), (64, 32, 100), (0, 0, 10), (0, 0, 3)):
+        jobs = [ln.split() for ln in sched(t, 0, 96 * 64, 1, c, na).strip().split("\n")[:-1]]
+        m = nums("split", c, t)[0]
+        assert [(int(j[3]), int(j[4])) for j in jobs] == ([(c, m), (m, t)] if m < t else [(c, t)]), (c, t)
+    # the levels of the adaptive call (min_spp, cap) and the targets of pt_ctx_accumulate_until (held, min_spp, cap)
+    assert nums("adaptive", 0, 100) == [16, 32, 64, 100]
+    assert nums("adaptive", 5, 100)[0] == 8 and nums("adaptive", 16, 10) == [10] and nums("adaptive", 17, 1000)[0] == 24
+    assert nums("adaptive", 0xfffffffa, 1 << 24) == [1 << 24] and nums("adaptive", 0xfffffff8, 1 << 24) == [1 << 24]
+    assert nums("adaptive", 0, 0xffffffff)[-3:] == [1 << 30, 1 << 31, 0xffffffff]  # (no wrap in the doubling)
+    assert nums("until", 20, 0, 100) == [20, 40, 80, 100] and nums("until", 0, 24, 30) == [24, 30]
+    assert nums("until", 0, 0, 100) == [16, 32, 64, 100] and nums("until", 0, 5, 100)[0] == 5  # (not rounded to 8s)
+    assert nums("until", 20, 64, 100) == [64, 100] and nums("until", 0, 64, 10) == [10] and nums("until", 100, 0, 100) == [100]
+    # tiles: 20 x 12 in tiles of 8 is 3 x 2, the right column 4 wide, the bottom row 4 high
+    assert nums("tiles", 20, 12, 3) == [3, 3, 6]
+    assert [nums("params", "0.5", t) for t in (4, 8, 16, 32, 0)] == [[2], [3], [4], [5], [3]]
+    for t in (1, 2, 7, 12, 64, 0xffffffff):
+        assert "tile must be 4, 8, 16 or 32" in ask("params", "0.5", t)
+    for v in ("-0.5", "inf", "nan"):
+        assert "tile_error must be finite and not negative" in ask("params", v, 7)  # before the tile
+    assert nums("params", "0", 8) == [3]
+    # 2^32 entries or more, from the arithmetic alone (nothing is allocated): a band one pixel wide has tile^2 entries for every
+    # `tile` pixels; a wide frame of 2^31 pixels stays far below
+    assert nums("tiles", 65536, 32767, 5) == [5, 2048, 2048 * 1024]
+    assert nums("tiles", 1, (1 << 30) - 4, 2)[2] == (1 << 28) - 1 and "2^32 pixels or more" in ask("tiles", 1, (1 << 30) - 3, 2)
+    assert nums("tiles", 1, (1 << 27) - 32, 5)[2] == (1 << 22) - 1 and "2^32 pixels or more" in ask("tiles", 1, (1 << 27) - 31, 5)
+    assert "2^32 pixels or more" in ask("tiles", 1, 0x7fffffff, 5)
+    # the band and the chunks, in this order
+    assert ask("cfg", 96, 0, 0, 0, 0) == "OK" and ask("cfg", 96, 96 * 20, 96 * 46, 1, 1) == "OK"
+    assert "whole image rows" in ask("cfg", 96, 10, 900, 2, 0) and "whole image rows" in ask("cfg", 96, 0, 961, 0, 0)
+    assert "chunk_step" in ask("cfg", 96, 0, 0, 2, 0) and "PT_FLAG_PIPELINES" in ask("cfg", 96, 0, 0, 0, 2 << 8)
+    # the noise target, in the header's order
+    assert ask("target", "0.1", "0", "0") == "OK" and ask("target", "0", "0.5", "0.2") == "OK"
+    for bad in (("-1", "2", "0"), ("0", "nan", "0"), ("0", "0", "inf")):
+        assert "finite and not negative" in ask("target", *bad)
+    assert "neither" in ask("target", "0", "0", "0.5") and "(0, 1)" in ask("target", "0.1", "1", "0")
+    # totals: the counts weigh 64, 64, 32 / 32, 32, 16 pixels; one tile without an error leaves the mean at +inf
+    spp = [16, 32, 64, 16, 32, 64]
+    some = [v for pair in zip(spp, [5, 0, "-", 7, 9, 11]) for v in pair]
+    out = ask("tiles", 20, 12, 3, 1000, *some).split()
+    assert int(out[3]) == 16 * 64 + 32 * 64 + 64 * 32 + 16 * 32 + 32 * 32 + 64 * 16 and int(out[4]) == 240 - 32 and out[5] == "inf"
+    every = [v for pair in zip(spp, [5, 0, 1 << 40, 7, 9, 11]) for v in pair]
+    out = ask("tiles", 20, 12, 3, (1 << 40) + 32, *every).split()
+    assert int(out[4]) == 240 and float(out[5]) == ((1 << 40) + 32) * 2.0 ** -28 / 240
+    out = ask("tiles", 20, 12, 3, 0, *[v for s in spp for v in (0, "-")]).split()
+    assert (int(out[3]), int(out[4]), out[5]) == (0, 0, "inf")
