@@ -143,6 +143,19 @@ pub struct PtAdaptiveStats {
     pub samples: u64,
     pub mean_error: f64,
 }
+
+// the adaptive frame a context holds, re-decided under a target and a cap (pt_ctx_adaptive_info)
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct PtAdaptiveInfo {
+    pub tiles: u32,
+    pub tiles_open: u32,
+    pub tiles_at_cap: u32,
+    pub spp_min: u32,
+    pub spp_max: u32,
+    pub samples: u64,
+    pub mean_error: f64,
+}
 pub const PT_DENOISE_NO_DEMODULATE: u32 = 1;
 
 pub const PT_OK: i32 = 0;
@@ -248,6 +261,40 @@ extern "C" {
         stats: *mut PtStats,
         astats: *mut PtAdaptiveStats,
     ) -> i32;
+    // pt_ctx_render_adaptive on the adaptive frame the context keeps: Stop keeps it, the same call continues it, a smaller
+    // tile_error refines it, a higher cap extends it; checkpoints of it on disk
+    pub fn pt_ctx_accumulate_adaptive(
+        ctx: *mut PtCtx,
+        cfg: *const PtConfig,
+        params: *const PtAdaptiveParams,
+        d_out_rgb: *mut c_void,
+        d_spp: *mut u32,
+        d_error: *mut f32,
+        hip_stream: *mut c_void,
+        cancel: *const u8,
+        cb: Option<PtProgressFn>,
+        user: *mut c_void,
+        stats: *mut PtStats,
+        astats: *mut PtAdaptiveStats,
+    ) -> i32;
+    pub fn pt_ctx_adaptive_info(
+        ctx: *mut PtCtx,
+        cfg: *const PtConfig,
+        params: *const PtAdaptiveParams,
+        out: *mut PtAdaptiveInfo,
+    ) -> i32;
+    // the preview between steps: allowed from pt_ctx_accumulate_adaptive's progress callback
+    pub fn pt_ctx_adaptive_resolve(
+        ctx: *mut PtCtx,
+        cfg: *const PtConfig,
+        d_out_rgb: *mut c_void,
+        d_spp: *mut u32,
+        d_error: *mut f32,
+        hip_stream: *mut c_void,
+    ) -> i32;
+    pub fn pt_ctx_adaptive_reset(ctx: *mut PtCtx) -> i32;
+    pub fn pt_ctx_adaptive_save(ctx: *mut PtCtx, path: *const c_char) -> i32;
+    pub fn pt_ctx_adaptive_load(ctx: *mut PtCtx, path: *const c_char) -> i32;
     // first-hit AOVs of the frame cfg describes (device buffers, any may be null): mean albedo and ray-facing normal over the
     // first cfg.spp samples, sample 0's depth and object id - a denoiser's guides, a pick map
     pub fn pt_ctx_render_aov(

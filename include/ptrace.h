@@ -482,10 +482,12 @@ int pt_ctx_accumulate_until(pt_ctx *ctx, const pt_config *cfg, const pt_noise_ta
  * - astats.  level_spp[j] = n_j and tiles_closed[j] for the `levels` levels run; tiles_open = tiles still open at the end (at the
  *   cap, or at the cancel); mean_error = (double)(the sum of the tiles' last E) * 2^-28 / (double)pixels, +inf unless every tile
  *   has been evaluated.
- * - State.  Scratch lives in the context - the held sums and half A's (48 B per pixel of the call), a count and an E per tile,
- *   two open-tile lists, and the compact accumulator of the open tiles (24 B per pixel of an open tile) - grows on demand, is
- *   reused between calls and freed by pt_ctx_destroy.  Every call starts from zero.  It changes no other state of the context:
- *   not pt_ctx_accumulate's held frame or counts, not the measured pass rates pt_ctx_render uses (its rounds keep a rate of their own).
+ * - State.  The call is pt_ctx_adaptive_reset followed by pt_ctx_accumulate_adaptive (below): it starts from zero, replaces a
+ *   held adaptive frame, and its own frame is held afterwards - pt_ctx_accumulate_adaptive continues it.  The held sums and half
+ *   A's (48 B per pixel of the call), a count, nA and an E per tile, the open-tile list and the compact accumulator of a step's
+ *   tiles (24 B per pixel of an open tile) live in the context, grow on demand and are reused between calls.  It changes no other
+ *   state of the context: not pt_ctx_accumulate's held frame or counts, not the measured pass rates pt_ctx_render uses (its
+ *   rounds keep a rate of their own).
  * - PT_ERR_INVALID, refused before any device is touched, checked in this order: NULL cfg, params, d_out_rgb or astats; a
  *   tile_error that is negative or not finite; a tile other than 0, 4, 8, 16, 32; NULL ctx; no scene; a band that is not whole
  *   rows; chunk_step > 1 or PT_FLAG_PIPELINES; whatever pt_ctx_render refuses; tiles that hold 2^32 pixels or more.
@@ -508,6 +510,75 @@ int pt_ctx_render_adaptive(pt_ctx *ctx, const pt_config *cfg, const pt_adaptive_
                            void *d_out_rgb, uint32_t *d_spp, float *d_error, void *hip_stream,
                            const volatile uint8_t *cancel, pt_progress_fn cb, void *user,
                            pt_stats *stats, pt_adaptive_stats *astats);
+
+/* ---- the adaptive frame held across calls: continue, refine, checkpoint -------------------------------------------
+ * pt_ctx_accumulate_adaptive is pt_ctx_render_adaptive on a frame the context KEEPS: a cancelled frame is continued, a smaller
+ * tile_error refines it, a higher cap extends it, and only the samples that are not held yet are traced.  Arguments, outputs
+ * and refusals (in that order) are pt_ctx_render_adaptive's.
+ * - Held adaptive frame and its key.  The context keeps one adaptive frame between calls.  Its key is pt_ctx_accumulate's frame
+ *   key - width, height, the band, seed, and the scene as uploaded - plus the tile edge and n_0 = min_spp (0 = 16) rounded up to a
+ *   multiple of 8, before any cap.  tile_error, the cap (cfg->spp), backend, flags, rays_per_pass and progress_ms are NOT part of
+ *   it.  A call with another key, pt_ctx_set_scene and pt_ctx_adaptive_reset drop the frame; pt_ctx_render_adaptive replaces it.
+ *   It is independent of pt_ctx_accumulate's held frame, in both directions.
+ * - Per-tile state.  A tile holds a count c, nA of its samples in half A (nB = c - nA), and its last E or none.  The ladder is
+ *   n_0, 2 n_0, 4 n_0, ...; a tile's next count after c is T = min(cap, the smallest ladder value > c) - min(cap, n_0) for c = 0.
+ * - A call, 1: re-decide.  Every tile that has an E is closed iff E <= q * (its pixels inside the frame), q from THIS call's
+ *   tile_error; a tile without an E is open.  So a smaller tile_error reopens tiles, and a larger one closes tiles without
+ *   tracing anything.  A tile with c >= cap takes no samples; if it is not closed it counts in tiles_open (and in
+ *   pt_adaptive_info.tiles_at_cap).  A cap below a tile's count is no error: samples are never removed.
+ * - A call, 2: steps.  While some open tile has c < cap: the open tiles with the smallest c, among those the ones with the
+ *   smallest nA, are a CLASS.  Every tile of the class is traced from c to T in two runs, [c, m) and [m, T), m = min(T, c + 4 *
+ *   ceil((T - c) / 8)); an empty second run is dropped.  After each run its samples go to the half that holds fewer samples of
+ *   the tile, a tie to A (pt_ctx_accumulate's rule for tracked frames).  After the last run every tile of the class is evaluated
+ *   exactly as pt_ctx_render_adaptive evaluates a level - e(p), E, the decision; with nB = 0 nothing is evaluated.  From zero
+ *   this is pt_ctx_render_adaptive's level sequence, halves and decisions; the two only differ after a cap that was not on the
+ *   ladder.
+ * - Cancel and progress.  *cancel is read between steps (and after the progress callback made there).  A step is kept whole or
+ *   not at all: PT_CANCELLED leaves the frame held at the steps that completed, and the same call made again continues it.
+ *   Progress: the samples held (the steps' partial tiles counted whole) over pixels * cap, between steps; 1.0 at the end.
+ * - Outputs, over the held state: every pixel resolved over its tile's count (pt_ctx_render's pixel at that count, bit for
+ *   bit), d_spp the counts, d_error e(p) of the tile's last evaluation - recomputed from the held sums, half A's, the count and
+ *   nA, which are those of that evaluation - and +inf where the tile has no E.
+ * - stats counts only this call's work: samples = the samples it added, ray_bounces and passes its own; a call with nothing to
+ *   trace reports zero rays and still fills the outputs.  astats: level_spp[j] = the T of this call's step j and tiles_closed[j]
+ *   the tiles its evaluation closed (steps beyond 32 run but are not recorded; `levels` saturates at 32); tiles, tiles_open,
+ *   samples and mean_error describe the held frame after the call.
+ * - Equality with a from-scratch render.  If tile_error never increased from call to call, and every earlier cap is a ladder
+ *   value or equals the last call's cap, the held frame after the last call is the frame pt_ctx_render_adaptive gives from
+ *   scratch with the last call's tile_error and cap: d_out_rgb, d_spp, d_error, samples and mean_error, bit for bit.  Otherwise
+ *   every pixel is still pt_ctx_render's pixel at its own count; only which tiles hold which count may differ.
+ * - Memory: 48 B per pixel of the call and 16 B per tile, outside the ray-queue budget; pt_ctx_adaptive_reset gives them back. */
+int pt_ctx_accumulate_adaptive(pt_ctx *ctx, const pt_config *cfg, const pt_adaptive_params *params,
+                               void *d_out_rgb, uint32_t *d_spp, float *d_error, void *hip_stream,
+                               const volatile uint8_t *cancel, pt_progress_fn cb, void *user,
+                               pt_stats *stats, pt_adaptive_stats *astats);
+typedef struct pt_adaptive_info {
+    uint32_t tiles, tiles_open, tiles_at_cap; /* tiles held; not closed under params->tile_error; of those, at cfg->spp or beyond */
+    uint32_t spp_min, spp_max;                /* smallest / largest count over the tiles */
+    uint64_t samples;                         /* sum over pixels of their count */
+    double mean_error;                        /* as pt_adaptive_stats.mean_error */
+} pt_adaptive_info;
+/* The held adaptive frame of cfg / params, re-decided under params->tile_error and cfg->spp, without changing it.  All zeros
+ * (PT_OK) if the key is not the held one.  Refusals as pt_ctx_render_adaptive's about cfg, params and ctx; blocking. */
+int pt_ctx_adaptive_info(pt_ctx *ctx, const pt_config *cfg, const pt_adaptive_params *params, pt_adaptive_info *out);
+/* Writes the three outputs (d_spp, d_error: may be NULL) from the held adaptive frame, as pt_ctx_accumulate_adaptive does at
+ * its end.  Allowed from the progress callback of pt_ctx_accumulate_adaptive, in stream order after the steps issued: the
+ * preview between steps (pt_ctx_snapshot does not know adaptive frames).  PT_ERR_INVALID if cfg's frame (width, height, band,
+ * seed) is not the held one.  Blocking. */
+int pt_ctx_adaptive_resolve(pt_ctx *ctx, const pt_config *cfg, void *d_out_rgb, uint32_t *d_spp, float *d_error, void *hip_stream);
+/* Drops the held adaptive frame and frees its memory. */
+int pt_ctx_adaptive_reset(pt_ctx *ctx);
+/* Checkpoint of the held adaptive frame (PT_ERR_INVALID if there is none), written to path + ".tmp" and renamed over `path`.
+ * Little-endian: magic "PTADAPT1"; u32 format version 1; the frame key as PTACCUM1 writes it (chunk fields 0), then u32 tile
+ * edge and u32 n_0; the u64 scene fingerprint; u32 call pixels; u32 tiles; per tile u32 count, u32 nA, u64 E (all ones = none);
+ * the held sums, then half A's, 3 planes x call pixels of u64 each; a trailing u64 pt_siphash(1, 3, 0, 0, ...) of everything
+ * before it. */
+int pt_ctx_adaptive_save(pt_ctx *ctx, const char *path);
+/* Replaces the held adaptive frame with a checkpoint's; the next pt_ctx_accumulate_adaptive with its key continues from it.
+ * Error codes as pt_ctx_accum_load's; PT_ERR_PARSE also for nA > count, a count above 2^24, an E of a tile one of whose halves
+ * is empty, and sizes that do not fit the tile geometry.  On each of these the held frame is left as it was.  No input crashes
+ * the loader. */
+int pt_ctx_adaptive_load(pt_ctx *ctx, const char *path);
 
 /* ---- first-hit AOVs: guide buffers for a denoiser, a pick map for a GUI ------------------------------------------
  * pt_ctx_render_aov covers the pixels pt_ctx_render covers with the same cfg - pt_config_pixels(cfg) of them, in the same

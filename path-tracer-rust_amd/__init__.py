@@ -75,6 +75,11 @@ class pt_adaptive_stats(C.Structure):
                 ("tiles_closed", C.c_uint32 * 32), ("samples", C.c_uint64), ("mean_error", C.c_double)]
 
 
+class pt_adaptive_info(C.Structure):
+    _fields_ = [("tiles", C.c_uint32), ("tiles_open", C.c_uint32), ("tiles_at_cap", C.c_uint32), ("spp_min", C.c_uint32),
+                ("spp_max", C.c_uint32), ("samples", C.c_uint64), ("mean_error", C.c_double)]
+
+
 PT_DENOISE_NO_DEMODULATE = 1
 PT_OK, PT_ERR_INVALID, PT_ERR_NO_DEVICE, PT_ERR_HIP, PT_CANCELLED = 0, -1, -2, -3, -4
 PT_ERR_IO, PT_ERR_PARSE = -6, -7
@@ -118,6 +123,12 @@ def lib():
     L.pt_ctx_render_adaptive.argtypes = [C.c_void_p, C.POINTER(pt_config), C.POINTER(pt_adaptive_params), C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(pt_stats),
                                          C.POINTER(pt_adaptive_stats)]
+    L.pt_ctx_accumulate_adaptive.argtypes = L.pt_ctx_render_adaptive.argtypes
+    L.pt_ctx_adaptive_info.argtypes = [C.c_void_p, C.POINTER(pt_config), C.POINTER(pt_adaptive_params), C.POINTER(pt_adaptive_info)]
+    L.pt_ctx_adaptive_resolve.argtypes = [C.c_void_p, C.POINTER(pt_config), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.pt_ctx_adaptive_reset.argtypes = [C.c_void_p]
+    L.pt_ctx_adaptive_save.argtypes = [C.c_void_p, C.c_char_p]
+    L.pt_ctx_adaptive_load.argtypes = [C.c_void_p, C.c_char_p]
     L.pt_ctx_render_aov.argtypes = [C.c_void_p, C.POINTER(pt_config), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p]
     L.pt_denoise_defaults.argtypes = [C.POINTER(pt_denoise_params)]
@@ -321,6 +332,46 @@ class Context:
         _check(lib().pt_ctx_render_adaptive(self._h, C.byref(cfg), C.byref(par), C.c_void_p(out_ptr), ptr(spp_map), ptr(error),
                                             C.c_void_p(stream or 0), None, None, None, C.byref(st), C.byref(ast)))
         return st, ast
+
+    def accumulate_adaptive(self, out_ptr, width, height, max_spp, tile_error, tile=0, min_spp=0, seed=1, band=None,
+                            spp_map=None, error=None, no_bvh=False, rays_per_pass=0, stream=None):
+        """render_adaptive() on the adaptive frame the context keeps between calls (pt_ctx_accumulate_adaptive): a cancelled
+        frame is continued, a smaller tile_error refines it, a higher max_spp extends it; only the samples not held yet are
+        traced.  Returns (this call's pt_stats, pt_adaptive_stats)."""
+        cfg = self._config(width, height, max_spp, seed, "megakernel", band, rays_per_pass)
+        if no_bvh:
+            cfg.flags |= PT_FLAG_NO_BVH
+        par = pt_adaptive_params(tile_error, tile, min_spp)
+        st, ast = pt_stats(), pt_adaptive_stats()
+        ptr = lambda p: C.c_void_p(p) if p else None  # noqa: E731
+        _check(lib().pt_ctx_accumulate_adaptive(self._h, C.byref(cfg), C.byref(par), C.c_void_p(out_ptr), ptr(spp_map),
+                                                ptr(error), C.c_void_p(stream or 0), None, None, None, C.byref(st), C.byref(ast)))
+        return st, ast
+
+    def adaptive_info(self, width, height, max_spp, tile_error, tile=0, min_spp=0, seed=1, band=None):
+        """The held adaptive frame re-decided under tile_error and max_spp (pt_ctx_adaptive_info): pt_adaptive_info, all zeros
+        if the context holds another adaptive frame or none."""
+        cfg = self._config(width, height, max_spp, seed, "megakernel", band)
+        par, out = pt_adaptive_params(tile_error, tile, min_spp), pt_adaptive_info()
+        _check(lib().pt_ctx_adaptive_info(self._h, C.byref(cfg), C.byref(par), C.byref(out)))
+        return out
+
+    def adaptive_resolve(self, out_ptr, width, height, seed=1, band=None, spp_map=None, error=None, stream=None):
+        """Write the image, and optionally the count and error maps, of the held adaptive frame (pt_ctx_adaptive_resolve)."""
+        cfg = self._config(width, height, 1, seed, "megakernel", band)
+        ptr = lambda p: C.c_void_p(p) if p else None  # noqa: E731
+        _check(lib().pt_ctx_adaptive_resolve(self._h, C.byref(cfg), C.c_void_p(out_ptr), ptr(spp_map), ptr(error),
+                                             C.c_void_p(stream or 0)))
+
+    def adaptive_reset(self):
+        _check(lib().pt_ctx_adaptive_reset(self._h))
+
+    def adaptive_save(self, path):
+        _check(lib().pt_ctx_adaptive_save(self._h, os.fsencode(path)))
+
+    def adaptive_load(self, path):
+        """Continue from a checkpoint of adaptive_save; the scene it was rendered from must be set."""
+        _check(lib().pt_ctx_adaptive_load(self._h, os.fsencode(path)))
 
     def accum_reset(self):
         _check(lib().pt_ctx_accum_reset(self._h))

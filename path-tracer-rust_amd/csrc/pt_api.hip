@@ -110,6 +110,70 @@ struct HeldFrame : host::FrameCounts {
     }
 };
 
+// The adaptive frame a context keeps between calls (pt_ctx_accumulate_adaptive), and its one owner: host::AdaptiveFrame plus the
+// device side - the held sums and half A's ([3] planes of `total` u64 each) and the tiles' table (per tile the count, nA and the
+// last E).  start() is the only place that makes a frame held, after everything is allocated and filled: a frame is held whole or
+// not at all.  forget() stops holding it and keeps the memory for the next frame (pt_ctx_render_adaptive renders frame after
+// frame); drop() gives the memory back.
+struct HeldAdaptive : host::AdaptiveFrame {
+    DevBuf<unsigned long long> sums, a, err;
+    DevBuf<uint32_t> cnt, na;
+    host::TileGeometry geo{};
+
+    void forget() { static_cast<host::AdaptiveFrame &>(*this) = {}; }
+    void drop() {
+        forget();
+        sums.release();
+        a.release();
+        err.release();
+        cnt.release();
+        na.release();
+    }
+    // Hold the frame f (tiles as g cuts it) in place of whatever was held.  The state comes from a checkpoint - the table and the
+    // host bytes from_sums / from_a, on the device when this returns - or starts at zero on `st` (table NULL).  On any failure
+    // nothing is held.
+    int start(const host::AdaptiveFrame &f, const host::TileGeometry &g, const host::TileTable *table, const uint8_t *from_sums,
+              const uint8_t *from_a, hipStream_t st) {
+        forget();
+        const size_t planes = 3 * (size_t)f.total, bytes = planes * sizeof(unsigned long long);
+        int rc;
+        if ((rc = sums.ensure(planes)) || (rc = a.ensure(planes)) || (rc = err.ensure(f.tiles)) || (rc = cnt.ensure(f.tiles)) ||
+            (rc = na.ensure(f.tiles)))
+            return rc;
+        hipError_t e;
+        if (table) {
+            if ((e = hipMemcpy(sums.p, from_sums, bytes, hipMemcpyHostToDevice)) == hipSuccess &&
+                (e = hipMemcpy(a.p, from_a, bytes, hipMemcpyHostToDevice)) == hipSuccess &&
+                (e = hipMemcpy(err.p, table->err.data(), (size_t)f.tiles * sizeof(unsigned long long), hipMemcpyHostToDevice)) == hipSuccess &&
+                (e = hipMemcpy(cnt.p, table->cnt.data(), (size_t)f.tiles * sizeof(uint32_t), hipMemcpyHostToDevice)) == hipSuccess)
+                e = hipMemcpy(na.p, table->na.data(), (size_t)f.tiles * sizeof(uint32_t), hipMemcpyHostToDevice);
+        } else {
+            if ((e = hipMemsetAsync(sums.p, 0, bytes, st)) == hipSuccess && (e = hipMemsetAsync(a.p, 0, bytes, st)) == hipSuccess &&
+                (e = hipMemsetAsync(err.p, 0xff, (size_t)f.tiles * sizeof(unsigned long long), st)) == hipSuccess &&  // kTileNoError
+                (e = hipMemsetAsync(cnt.p, 0, (size_t)f.tiles * sizeof(uint32_t), st)) == hipSuccess)
+                e = hipMemsetAsync(na.p, 0, (size_t)f.tiles * sizeof(uint32_t), st);
+        }
+        if (e != hipSuccess) {
+            set_error(std::string(table ? "uploading the checkpoint: " : "clearing the held adaptive frame: ") + hipGetErrorString(e));
+            return PT_ERR_HIP;
+        }
+        static_cast<host::AdaptiveFrame &>(*this) = f;
+        geo = g;
+        return PT_OK;
+    }
+    // the tiles' table as the device holds it (the host waits for `st`)
+    int download(host::TileTable &t, hipStream_t st) const {
+        t.cnt.resize(tiles);
+        t.na.resize(tiles);
+        t.err.resize(tiles);
+        HIP_TRY(hipMemcpyAsync(t.cnt.data(), cnt.p, (size_t)tiles * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(t.na.data(), na.p, (size_t)tiles * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(t.err.data(), err.p, (size_t)tiles * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return PT_OK;
+    }
+};
+
 }  // namespace pt
 
 using namespace pt;
@@ -267,12 +331,13 @@ struct pt_ctx {
     DevBuf<NoiseCounters> noise_cnt;
     // pt_ctx_denoise's scratch, kept between calls: the two colour planes and the packed guides, one float4 per pixel each
     DevBuf<float4> dn_u[2], dn_guide;
-    // pt_ctx_render_adaptive's scratch, kept between calls (every call starts it from zero): the held sums and half A's ([3]
-    // planes of the call's pixels each), the compact accumulator of the open tiles, per tile the count and the last E, the two
-    // open-tile lists (this level's, the next one's), the level's counters (u64 [0]: the sum of E at the end; u32 [2], [3]: the
-    // next list's length, the tiles closed), and the rate its own rounds measured (pt_ctx_set_scene forgets it)
-    DevBuf<unsigned long long> ad_held, ad_a, ad_acc, ad_err, ad_cnt, ad_rays;
-    DevBuf<uint32_t> ad_spp, ad_open[2];
+    // The adaptive calls: the frame kept between calls (pt_ctx_set_scene drops it), and their scratch, kept too and grown on
+    // demand: the compact accumulator of a step's tiles, the step's open-tile list, the counters (u64 [0]: the sum of E at the
+    // end; u32 [2], [3]: the tiles a step left open / closed; u32 [4]: the list's length; u32 [5..7]: k_tile_select's counts),
+    // the tile pass's ray counters, and the rate its own rounds measured (pt_ctx_set_scene forgets it)
+    HeldAdaptive adaptive;
+    DevBuf<unsigned long long> ad_acc, ad_cnt, ad_rays;
+    DevBuf<uint32_t> ad_open;
     DevBuf<char> ad_stack;
     double ad_rate = 0.0;
 };
@@ -1023,8 +1088,8 @@ int frame_prologue(pt_ctx *c, const pt_config *cfg, uint32_t *ib, uint32_t *ie) 
     return PT_OK;
 }
 
-// One run of a level of pt_ctx_render_adaptive: samples [s_first, s_end) of every open tile into the compact accumulator (zeroed
-// here), in the megakernel's rounds at a rate of their own.  The cancel byte is the level loop's business, not the rounds'.
+// One run of a step of pt_ctx_accumulate_adaptive: samples [s_first, s_end) of every open tile into the compact accumulator (zeroed
+// here), in the megakernel's rounds at a rate of their own.  The cancel byte is the step loop's business, not the rounds'.
 int tile_run(pt_ctx *c, const DevScene &S, const LdsLayout &lay, const pt_config *cfg, TileParams F, uint32_t n_open, uint32_t s_first,
              uint32_t s_end, hipStream_t st, pt_stats &stats) {
     const uint64_t entries = (uint64_t)n_open << (2u * F.tile_shift);
@@ -1045,11 +1110,33 @@ int tile_run(pt_ctx *c, const DevScene &S, const LdsLayout &lay, const pt_config
     return rc;
 }
 
-// pt_ctx_render_adaptive after its refusals about the arguments: the band [ib, ie) of a checked cfg in tiles of 1 << tile_shift,
-// level by level (host::adaptive_first_level, host::next_target; a level's two runs: host::tracked_split), then the outputs
-int render_adaptive(pt_ctx *c, const pt_config *cfg, uint32_t ib, uint32_t ie, uint32_t tile_shift, const pt_adaptive_params *params,
-                    float *d_out_rgb, uint32_t *d_spp, float *d_error, hipStream_t st, const volatile uint8_t *cancel, pt_progress_fn cb,
-                    void *user, pt_stats *stats, pt_adaptive_stats *astats) {
+// the key of the held adaptive frame a checked call names (b, e: check_cfg's band)
+host::AdaptiveKey adaptive_key(const pt_config *cfg, uint32_t b, uint32_t e, uint32_t tile_shift, uint32_t min_spp) {
+    return {host::accum_key(cfg, b, e), 1u << tile_shift, host::adaptive_n0(min_spp)};
+}
+
+TileGrid tile_grid(const HeldAdaptive &h) {
+    TileGrid G{};
+    G.width = h.key.frame.width;
+    G.rows = h.total / G.width;
+    G.tile_shift = h.geo.tile_shift;
+    G.tiles_x = h.geo.tiles_x;
+    G.tiles = h.geo.tiles;
+    G.spp = h.cnt.p;
+    G.na = h.na.p;
+    G.err = h.err.p;
+    return G;
+}
+
+unsigned long long tile_threshold(float tile_error) { return (unsigned long long)__builtin_floor((double)tile_error * 268435456.0); }
+
+// pt_ctx_accumulate_adaptive after its refusals about the arguments: the band [ib, ie) of a checked cfg in tiles of 1 <<
+// tile_shift.  The held frame of this key (or a new one, from zero) is re-decided under this call's target and cap and taken on
+// step by step - host::AdaptiveSchedule says which class is next, k_tile_select finds its tiles, a step's two runs are
+// host::tracked_split's - then the outputs are written from what is held.
+int accumulate_adaptive(pt_ctx *c, const pt_config *cfg, uint32_t ib, uint32_t ie, uint32_t tile_shift, const pt_adaptive_params *params,
+                        float *d_out_rgb, uint32_t *d_spp, float *d_error, hipStream_t st, const volatile uint8_t *cancel,
+                        pt_progress_fn cb, void *user, pt_stats *stats, pt_adaptive_stats *astats) {
     const double t0 = now_ms();
     if (stats) memset(stats, 0, sizeof *stats);
     memset(astats, 0, sizeof *astats);
@@ -1058,114 +1145,136 @@ int render_adaptive(pt_ctx *c, const pt_config *cfg, uint32_t ib, uint32_t ie, u
     const DevScene &S = form.scene;
     const LdsLayout lay = lds_layout(S, 1u, c->tune.lds_pad);
     const uint32_t npix = ie - ib;
-    TileGrid G{};
-    G.width = cfg->width;
-    G.rows = npix / cfg->width;
     host::TileGeometry geo;
-    int rc = host::tile_geometry(G.width, G.rows, tile_shift, geo);
+    int rc = host::tile_geometry(cfg->width, npix / cfg->width, tile_shift, geo);
     if (rc) return rc;
-    G.tile_shift = geo.tile_shift;
-    G.tiles_x = geo.tiles_x;
-    G.tiles = geo.tiles;
+    HeldAdaptive &h = c->adaptive;
+    const host::AdaptiveKey key = adaptive_key(cfg, ib, ie, tile_shift, params->min_spp);
+    host::TileTable tab;  // the tiles' state at the start of the call: all the scheduler ever learns about single tiles
+    if (h.holds(key)) {
+        if ((rc = h.download(tab, st))) return rc;
+    } else {  // another frame (or none): from zero
+        host::AdaptiveFrame f;
+        f.key = key;
+        f.total = npix;
+        f.tiles = geo.tiles;
+        if ((rc = h.start(f, geo, nullptr, nullptr, nullptr, st))) return rc;
+        tab.cnt.assign(geo.tiles, 0u);
+        tab.na.assign(geo.tiles, 0u);
+        tab.err.assign(geo.tiles, kTileNoError);
+    }
+    const TileGrid G = tile_grid(h);
     TileParams F{};
     static_cast<FrameParams &>(F) = make_frame(c, cfg, ib, ie);
     F.chunk_step = 0u;
     F.tile_shift = G.tile_shift;
     F.tiles_x = G.tiles_x;
     F.rows = G.rows;
-    if ((rc = c->ad_held.ensure(3 * (size_t)npix)) || (rc = c->ad_a.ensure(3 * (size_t)npix)) || (rc = c->ad_err.ensure(G.tiles)) ||
-        (rc = c->ad_spp.ensure(G.tiles)) || (rc = c->ad_open[0].ensure(G.tiles)) || (rc = c->ad_open[1].ensure(G.tiles)) ||
-        (rc = c->ad_cnt.ensure(2)) || (rc = c->ad_rays.ensure(16)))
-        return rc;
-    G.spp = c->ad_spp.p;
-    G.err = c->ad_err.p;
+    if (c->ad_open.n < G.tiles) {  // (a slot of the list names a tile whatever a launch reads of it)
+        if ((rc = c->ad_open.ensure(G.tiles))) return rc;
+        HIP_TRY(hipMemsetAsync(c->ad_open.p, 0, (size_t)G.tiles * sizeof(uint32_t), st));
+    }
+    if ((rc = c->ad_cnt.ensure(4)) || (rc = c->ad_rays.ensure(16))) return rc;
+    F.open = c->ad_open.p;
+    uint32_t *const words = reinterpret_cast<uint32_t *>(c->ad_cnt.p);
     hipEvent_t ev0 = get_event(c, 6), ev1 = get_event(c, 7);  // (0..5 are the rounds' pacer's)
     if (!ev0 || !ev1) {
         set_error("hipEventCreate failed");
         return PT_ERR_HIP;
     }
     HIP_TRY(hipEventRecord(ev0, st));
-    HIP_TRY(hipMemsetAsync(c->ad_held.p, 0, 3 * (size_t)npix * sizeof(unsigned long long), st));
-    HIP_TRY(hipMemsetAsync(c->ad_a.p, 0, 3 * (size_t)npix * sizeof(unsigned long long), st));
-    HIP_TRY(hipMemsetAsync(c->ad_err.p, 0xff, (size_t)G.tiles * sizeof(unsigned long long), st));  // kTileNoError
-    HIP_TRY(hipMemsetAsync(c->ad_spp.p, 0, (size_t)G.tiles * sizeof(uint32_t), st));
     HIP_TRY(hipMemsetAsync(c->ad_rays.p, 0, 16 * sizeof(unsigned long long), st));
-    launch_tile_begin(st, d_error, npix, c->ad_open[0].p, G.tiles);
     LiveScope live(c);  // (the rounds' pacer notes its samples in the live frame)
     const uint32_t cap = cfg->spp;
-    const unsigned long long q = (unsigned long long)__builtin_floor((double)params->tile_error * 268435456.0);
-    uint32_t level = host::adaptive_first_level(params->min_spp, cap);
-    uint32_t have = 0, n_a = 0, n_open = G.tiles, which = 0;
-    uint64_t samples = 0;
+    const unsigned long long q = tile_threshold(params->tile_error);
+    host::AdaptiveSchedule sched(tab, G.width, G.rows, geo, q, cap, key.n0);
+    uint64_t held_before = 0;
+    for (uint32_t i = 0; i < geo.tiles; ++i) held_before += host::tile_pixels(G.width, G.rows, geo, i) * tab.cnt[i];
+    uint64_t samples = std::min<uint64_t>(held_before, (uint64_t)npix * cap);
     bool cancelled = false;
     astats->tiles = G.tiles;
-    for (uint32_t j = 0; n_open != 0u && have < cap && j < 32u; ++j) {
+    host::AdaptiveStep s;
+    // an error inside a step leaves sums without their counts: the frame is not held any more
+    auto broken = [&](int code) {
+        h.forget();
+        return code;
+    };
+    for (uint32_t j = 0; sched.next(s); ++j) {
         cancelled = cancel && *cancel;
         if (!cancelled && cb && j != 0u && progress(c, cfg, cb, user, (float)((double)samples / ((double)npix * cap))))
             cancelled = cancel && *cancel;  // raised from inside the callback
         if (cancelled) break;
-        const uint32_t m = host::tracked_split(have, level);  // [have, m) to half A, [m, level) to half B
-        F.open = c->ad_open[which].p;
-        n_a += m - have;
-        const uint32_t n_b = level - n_a;
+        HIP_TRY(hipMemsetAsync(c->ad_cnt.p + 1, 0, 3 * sizeof(unsigned long long), st));
+        TileSelect sel{};
+        sel.q = q;
+        sel.cap = cap;
+        sel.c = s.c;
+        sel.na = s.na;
+        sel.list = c->ad_open.p;
+        sel.list_len = words + 4;
+        sel.out = words + 5;
+        launch_tile_select(st, G, sel);
+        const uint32_t n_b = s.T - s.na_end;
         TileLevel V{};
         V.open = F.open;
-        V.n_open = n_open;
-        V.spp = level;
+        V.n_open = s.n;
+        V.spp = s.T;
+        V.na = s.na_end;
         V.q = q;
-        V.next = c->ad_open[which ^ 1u].p;
-        V.counters = reinterpret_cast<uint32_t *>(c->ad_cnt.p + 1);
-        V.fa = (float)n_a;
+        V.counters = words + 2;
+        V.fa = (float)s.na_end;
         V.fb = (float)n_b;
-        V.fn = (float)level;
-        V.w = n_b != 0u ? host::noise_part_weight(n_a, n_b) : 0.0f;
-        HIP_TRY(hipMemsetAsync(c->ad_cnt.p + 1, 0, sizeof(unsigned long long), st));
-        for (uint32_t run = 0; run < (m < level ? 2u : 1u); ++run) {
-            const uint32_t r0 = run ? m : have, r1 = run ? level : m;
-            if ((rc = tile_run(c, S, lay, cfg, F, n_open, r0, r1, st, ps))) return rc;
+        V.fn = (float)s.T;
+        V.w = n_b != 0u ? host::noise_part_weight(s.na_end, n_b) : 0.0f;
+        for (uint32_t run = 0; run < s.runs(); ++run) {
+            const uint32_t r0 = run ? s.m : s.c, r1 = run ? s.T : s.m;
+            if ((rc = tile_run(c, S, lay, cfg, F, s.n, r0, r1, st, ps))) return broken(rc);
             V.acc = c->ad_acc.p;
-            V.to_a = run == 0u ? 1u : 0u;
-            V.evaluate = r1 == level ? 1u : 0u;
+            V.to_a = s.to_a[run] ? 1u : 0u;
+            V.evaluate = r1 == s.T ? 1u : 0u;
             V.estimate = V.evaluate && n_b != 0u ? 1u : 0u;
-            launch_tile_level(st, G, V, c->ad_held.p, c->ad_a.p, d_error);
+            launch_tile_level(st, G, V, h.sums.p, h.a.p);
         }
-        HIP_TRY(hipGetLastError());
-        uint32_t back[2] = {0u, 0u};  // the next list's length, the tiles closed: all that comes back per level
-        HIP_TRY(hipMemcpyAsync(back, c->ad_cnt.p + 1, sizeof back, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
+        uint32_t back[2] = {0u, 0u};  // the tiles the step left open, the tiles it closed: all that comes back per step
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(back, words + 2, sizeof back, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) {
+            set_error(std::string("a step of the adaptive frame: ") + hipGetErrorString(e));
+            return broken(PT_ERR_HIP);
+        }
+        if (back[0] + back[1] != s.n) {
+            set_error("the adaptive frame's tiles and the host's count of them disagree");
+            return broken(PT_ERR_HIP);
+        }
         // (partial tiles counted whole: this only feeds the progress fraction; the exact total comes from the counts at the end)
-        samples += ((uint64_t)n_open << (2u * G.tile_shift)) * (level - have);
+        samples += ((uint64_t)s.n << (2u * G.tile_shift)) * (s.T - s.c);
         if (samples > (uint64_t)npix * cap) samples = (uint64_t)npix * cap;
-        astats->level_spp[j] = level;
-        astats->tiles_closed[j] = back[1];
-        astats->levels = j + 1u;
-        n_open = back[0];
-        which ^= 1u;
-        have = level;
-        level = host::next_target(level, cap);
+        if (j < 32u) {
+            astats->level_spp[j] = s.T;
+            astats->tiles_closed[j] = back[1];
+            astats->levels = j + 1u;
+        }
+        sched.done(s, back[0], back[1]);
     }
-    astats->tiles_open = n_open;
-    // the outputs: every pixel over its tile's count, the counts, the sum of E over the tiles
+    astats->tiles_open = sched.tiles_open();
+    // the outputs: every pixel over its tile's count, the counts, the error map, the sum of E over the tiles
     HIP_TRY(hipMemsetAsync(c->ad_cnt.p, 0, sizeof(unsigned long long), st));
-    launch_tile_resolve(st, G, c->ad_held.p, d_out_rgb, d_spp, c->ad_cnt.p);
+    launch_tile_resolve(st, G, h.sums.p, h.a.p, d_out_rgb, d_spp, d_error, c->ad_cnt.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(ev1, st));
     unsigned long long err_sum = 0, rays[16] = {0};
-    std::vector<uint32_t> tile_spp(G.tiles);
-    std::vector<unsigned long long> tile_err(G.tiles);
     HIP_TRY(hipMemcpyAsync(&err_sum, c->ad_cnt.p, sizeof err_sum, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(rays, c->ad_rays.p, sizeof rays, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(tile_spp.data(), c->ad_spp.p, (size_t)G.tiles * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(tile_err.data(), c->ad_err.p, (size_t)G.tiles * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    if ((rc = h.download(tab, st))) return rc;
     if (rays[1]) {
         set_error("tile pass: a lane's split stack overflowed");
-        return PT_ERR_OVERFLOW;
+        return broken(PT_ERR_OVERFLOW);
     }
-    const host::TileTotals tot = host::tile_totals(G.width, G.rows, geo, tile_spp.data(), tile_err.data(), err_sum);
+    const host::TileTotals tot = host::tile_totals(G.width, G.rows, geo, tab.cnt.data(), tab.err.data(), err_sum);
     astats->samples = tot.samples;
     astats->mean_error = tot.mean_error;
-    ps.samples = tot.samples;
+    ps.samples = tot.samples - held_before;
     ps.ray_bounces = rays[0];
     float ms_dev = 0.0f;
     HIP_TRY(hipEventElapsedTime(&ms_dev, ev0, ev1));
@@ -1177,6 +1286,77 @@ int render_adaptive(pt_ctx *c, const pt_config *cfg, uint32_t ib, uint32_t ie, u
         return PT_CANCELLED;
     }
     if (cb) cb(user, 1.0f);
+    return PT_OK;
+}
+
+// the refusals of the adaptive calls that name a frame by cfg and params, in the header's order, up to the band: no device is touched
+int adaptive_prologue(pt_ctx *c, const pt_config *cfg, const pt_adaptive_params *params, uint32_t *tile_shift, uint32_t *ib, uint32_t *ie) {
+    int rc = host::check_adaptive_params(*params, tile_shift);
+    if (rc) return rc;
+    if (!c) return refuse("ctx is NULL");
+    if (!c->has_scene) return refuse("no scene set");
+    if ((rc = host::check_adaptive_cfg(*cfg)) || (rc = check_cfg(cfg, ib, ie))) return rc;
+    return PT_OK;
+}
+
+// a file written next to its target and renamed over it: a process that dies while saving leaves the last checkpoint whole
+int write_renamed(const std::vector<uint8_t> &b, const char *path) {
+    const std::string tmp = std::string(path) + ".tmp";
+    FILE *f = fopen(tmp.c_str(), "wb");
+    if (!f) {
+        set_error(std::string("cannot open ") + tmp + " for writing: " + strerror(errno));
+        return PT_ERR_IO;
+    }
+    const bool ok = fwrite(b.data(), 1, b.size(), f) == b.size();
+    if (fclose(f) != 0 || !ok) {
+        set_error(std::string("cannot write ") + tmp);
+        remove(tmp.c_str());
+        return PT_ERR_IO;
+    }
+    if (rename(tmp.c_str(), path) != 0) {
+        set_error(std::string("cannot rename ") + tmp + " to " + path + ": " + strerror(errno));
+        remove(tmp.c_str());
+        return PT_ERR_IO;
+    }
+    return PT_OK;
+}
+
+// A checkpoint file read as its decoder asks for it - the header first, the rest only once the file's size is the one the header
+// implies - into b and ck.  decode: host::ckpt_decode or host::adckpt_decode.
+template <class Ckpt, class Decode>
+int read_checkpoint(const char *path, Decode decode, Ckpt &ck, std::vector<uint8_t> &b) {
+    FILE *f = fopen(path, "rb");
+    if (!f) {
+        set_error(std::string("cannot open ") + path + ": " + strerror(errno));
+        return PT_ERR_IO;
+    }
+    struct Closer {
+        FILE *f;
+        ~Closer() { fclose(f); }
+    } closer{f};
+    if (fseeko(f, 0, SEEK_END) != 0) {
+        set_error(std::string("cannot read ") + path);
+        return PT_ERR_IO;
+    }
+    const off_t fsize = ftello(f);
+    if (fsize < 0 || fseeko(f, 0, SEEK_SET) != 0) {
+        set_error(std::string("cannot read ") + path);
+        return PT_ERR_IO;
+    }
+    std::string why;
+    int d;
+    while ((d = decode((uint64_t)fsize, b.data(), b.size(), ck, why)) == host::kCkptMore) {
+        const size_t at = b.size();
+        b.resize(ck.need);
+        if (fread(b.data() + at, 1, ck.need - at, f) != ck.need - at) {
+            set_error(std::string("cannot read ") + path);
+            return PT_ERR_IO;
+        }
+    }
+    if (d != host::kCkptOk) {
+        set_error(std::string(path) + " is not a checkpoint of this library: " + why);
+        return PT_ERR_PARSE;
+    }
     return PT_OK;
 }
 
@@ -1281,6 +1461,7 @@ int pt_ctx_set_scene(pt_ctx *c, const pt_camera *cam, const pt_object *objs, uin
     }
     HIP_TRY(hipSetDevice(c->device));
     c->held.drop();  // (the held sums are of the scene before)
+    c->adaptive.drop();
     c->scene_fp = 0;
     int rc;
     if ((rc = c->d_objs.ensure(fs.objs.size())) || (rc = c->d_opairs.ensure(fs.obj_pairs.size())) || (rc = c->d_tris.ensure(fs.tri_pairs.size())) ||
@@ -1653,25 +1834,7 @@ int pt_ctx_accum_save(pt_ctx *c, const char *path) {
     HIP_TRY(hipMemcpy(b.data() + at, h.sums.p, plane, hipMemcpyDeviceToHost));
     if (h.tracked()) HIP_TRY(hipMemcpy(b.data() + at + plane, h.a.p, plane, hipMemcpyDeviceToHost));
     host::ckpt_seal(b);
-    // written next to the target and renamed over it: a process that dies while saving leaves the last checkpoint whole
-    const std::string tmp = std::string(path) + ".tmp";
-    FILE *f = fopen(tmp.c_str(), "wb");
-    if (!f) {
-        set_error(std::string("cannot open ") + tmp + " for writing: " + strerror(errno));
-        return PT_ERR_IO;
-    }
-    const bool ok = fwrite(b.data(), 1, b.size(), f) == b.size();
-    if (fclose(f) != 0 || !ok) {
-        set_error(std::string("cannot write ") + tmp);
-        remove(tmp.c_str());
-        return PT_ERR_IO;
-    }
-    if (rename(tmp.c_str(), path) != 0) {
-        set_error(std::string("cannot rename ") + tmp + " to " + path + ": " + strerror(errno));
-        remove(tmp.c_str());
-        return PT_ERR_IO;
-    }
-    return PT_OK;
+    return write_renamed(b, path);
 }
 
 int pt_ctx_accum_load(pt_ctx *c, const char *path) {
@@ -1683,41 +1846,10 @@ int pt_ctx_accum_load(pt_ctx *c, const char *path) {
         set_error("no scene set: a checkpoint is loaded under the scene it was rendered from");
         return PT_ERR_INVALID;
     }
-    FILE *f = fopen(path, "rb");
-    if (!f) {
-        set_error(std::string("cannot open ") + path + ": " + strerror(errno));
-        return PT_ERR_IO;
-    }
-    struct Closer {
-        FILE *f;
-        ~Closer() { fclose(f); }
-    } closer{f};
-    if (fseeko(f, 0, SEEK_END) != 0) {
-        set_error(std::string("cannot read ") + path);
-        return PT_ERR_IO;
-    }
-    const off_t fsize = ftello(f);
-    if (fsize < 0 || fseeko(f, 0, SEEK_SET) != 0) {
-        set_error(std::string("cannot read ") + path);
-        return PT_ERR_IO;
-    }
-    // the decoder asks for the header first, and for the rest only once the file's size is the one the header implies
     host::Checkpoint ck;
     std::vector<uint8_t> b;
-    std::string why;
-    int d;
-    while ((d = host::ckpt_decode((uint64_t)fsize, b.data(), b.size(), ck, why)) == host::kCkptMore) {
-        const size_t at = b.size();
-        b.resize(ck.need);
-        if (fread(b.data() + at, 1, ck.need - at, f) != ck.need - at) {
-            set_error(std::string("cannot read ") + path);
-            return PT_ERR_IO;
-        }
-    }
-    if (d != host::kCkptOk) {
-        set_error(std::string(path) + " is not a checkpoint of this library: " + why);
-        return PT_ERR_PARSE;
-    }
+    const int rc = read_checkpoint(path, host::ckpt_decode, ck, b);
+    if (rc) return rc;
     if (ck.scene_fp != c->scene_fp) {
         set_error(std::string(path) + " was rendered from another scene than the one set on this context");
         return PT_ERR_INVALID;
@@ -1863,19 +1995,122 @@ int pt_ctx_accumulate_until(pt_ctx *c, const pt_config *cfg, const pt_noise_targ
     return rc;
 }
 
+int pt_ctx_accumulate_adaptive(pt_ctx *c, const pt_config *cfg, const pt_adaptive_params *params, void *d_out_rgb, uint32_t *d_spp,
+                               float *d_error, void *hip_stream, const volatile uint8_t *cancel, pt_progress_fn cb, void *user,
+                               pt_stats *stats, pt_adaptive_stats *astats) {
+    if (!cfg || !params || !d_out_rgb || !astats) return refuse("NULL argument");
+    uint32_t tile_shift = 0, ib = 0, ie = 0;
+    const int rc = adaptive_prologue(c, cfg, params, &tile_shift, &ib, &ie);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    return accumulate_adaptive(c, cfg, ib, ie, tile_shift, params, (float *)d_out_rgb, d_spp, d_error,
+                               hip_stream ? (hipStream_t)hip_stream : c->stream, cancel, cb, user, stats, astats);
+}
+
 int pt_ctx_render_adaptive(pt_ctx *c, const pt_config *cfg, const pt_adaptive_params *params, void *d_out_rgb, uint32_t *d_spp,
                            float *d_error, void *hip_stream, const volatile uint8_t *cancel, pt_progress_fn cb, void *user,
                            pt_stats *stats, pt_adaptive_stats *astats) {
-    if (!cfg || !params || !d_out_rgb || !astats) return refuse("NULL argument");
+    if (c) c->adaptive.forget();  // pt_ctx_adaptive_reset, its memory kept for this frame: the call starts from zero
+    return pt_ctx_accumulate_adaptive(c, cfg, params, d_out_rgb, d_spp, d_error, hip_stream, cancel, cb, user, stats, astats);
+}
+
+int pt_ctx_adaptive_info(pt_ctx *c, const pt_config *cfg, const pt_adaptive_params *params, pt_adaptive_info *out) {
+    if (!cfg || !params || !out) return refuse("NULL argument");
     uint32_t tile_shift = 0, ib = 0, ie = 0;
-    int rc = host::check_adaptive_params(*params, &tile_shift);
+    int rc = adaptive_prologue(c, cfg, params, &tile_shift, &ib, &ie);
     if (rc) return rc;
-    if (!c) return refuse("ctx is NULL");
-    if (!c->has_scene) return refuse("no scene set");
-    if ((rc = host::check_adaptive_cfg(*cfg)) || (rc = check_cfg(cfg, &ib, &ie))) return rc;
+    memset(out, 0, sizeof *out);
+    const HeldAdaptive &h = c->adaptive;
+    if (!h.holds(adaptive_key(cfg, ib, ie, tile_shift, params->min_spp))) return PT_OK;
     HIP_TRY(hipSetDevice(c->device));
-    return render_adaptive(c, cfg, ib, ie, tile_shift, params, (float *)d_out_rgb, d_spp, d_error,
-                           hip_stream ? (hipStream_t)hip_stream : c->stream, cancel, cb, user, stats, astats);
+    // the re-decision is the device's scan, the one a call's steps start with; the counts and the E come down with it
+    if ((rc = c->ad_cnt.ensure(4))) return rc;
+    uint32_t *const words = reinterpret_cast<uint32_t *>(c->ad_cnt.p);
+    HIP_TRY(hipMemsetAsync(c->ad_cnt.p + 2, 0, 2 * sizeof(unsigned long long), c->stream));
+    const TileGrid G = tile_grid(h);
+    TileSelect sel{};
+    sel.q = tile_threshold(params->tile_error);
+    sel.cap = cfg->spp;
+    sel.out = words + 5;
+    launch_tile_select(c->stream, G, sel);
+    HIP_TRY(hipGetLastError());
+    uint32_t counts[3] = {0u, 0u, 0u};
+    HIP_TRY(hipMemcpyAsync(counts, words + 5, sizeof counts, hipMemcpyDeviceToHost, c->stream));
+    host::TileTable tab;
+    if ((rc = h.download(tab, c->stream))) return rc;
+    out->tiles = h.tiles;
+    out->tiles_open = counts[0];
+    out->tiles_at_cap = counts[1];
+    out->spp_min = *std::min_element(tab.cnt.begin(), tab.cnt.end());
+    out->spp_max = *std::max_element(tab.cnt.begin(), tab.cnt.end());
+    unsigned long long err_sum = 0;
+    for (unsigned long long E : tab.err)
+        if (E != kTileNoError) err_sum += E;
+    const host::TileTotals tot = host::tile_totals(G.width, G.rows, h.geo, tab.cnt.data(), tab.err.data(), err_sum);
+    out->samples = tot.samples;
+    out->mean_error = tot.mean_error;
+    return PT_OK;
+}
+
+int pt_ctx_adaptive_resolve(pt_ctx *c, const pt_config *cfg, void *d_out_rgb, uint32_t *d_spp, float *d_error, void *hip_stream) {
+    if (!c || !cfg || !d_out_rgb) return refuse("NULL argument");
+    uint32_t ib = 0, ie = 0;
+    int rc;
+    if ((rc = host::check_adaptive_cfg(*cfg)) || (rc = check_cfg(cfg, &ib, &ie))) return rc;
+    const HeldAdaptive &h = c->adaptive;
+    if (!h.held() || !(h.key.frame == host::accum_key(cfg, ib, ie))) return refuse("cfg does not name the adaptive frame this context holds");
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    launch_tile_resolve(st, tile_grid(h), h.sums.p, h.a.p, (float *)d_out_rgb, d_spp, d_error, nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    return PT_OK;
+}
+
+int pt_ctx_adaptive_reset(pt_ctx *c) {
+    if (!c) return refuse("ctx is NULL");
+    if (c->adaptive.sums.p) HIP_TRY(hipSetDevice(c->device));
+    c->adaptive.drop();
+    return PT_OK;
+}
+
+int pt_ctx_adaptive_save(pt_ctx *c, const char *path) {
+    if (!c || !path) return refuse("NULL argument");
+    const HeldAdaptive &h = c->adaptive;
+    if (!h.held()) return refuse("no adaptive frame is held on this context");
+    HIP_TRY(hipSetDevice(c->device));
+    host::AdaptiveCheckpoint ck;
+    static_cast<host::AdaptiveFrame &>(ck) = h;
+    ck.scene_fp = c->scene_fp;
+    int rc = h.download(ck.table, c->stream);
+    if (rc) return rc;
+    std::vector<uint8_t> b;
+    host::adckpt_encode_head(ck, b);
+    const size_t at = b.size(), plane = 3 * (size_t)h.total * sizeof(unsigned long long);
+    b.resize(at + 2u * plane);
+    HIP_TRY(hipMemcpy(b.data() + at, h.sums.p, plane, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(b.data() + at + plane, h.a.p, plane, hipMemcpyDeviceToHost));
+    host::ckpt_seal(b);
+    return write_renamed(b, path);
+}
+
+int pt_ctx_adaptive_load(pt_ctx *c, const char *path) {
+    if (!c || !path) return refuse("NULL argument");
+    if (!c->has_scene) return refuse("no scene set: a checkpoint is loaded under the scene it was rendered from");
+    host::AdaptiveCheckpoint ck;
+    std::vector<uint8_t> b;
+    int rc = read_checkpoint(path, host::adckpt_decode, ck, b);
+    if (rc) return rc;
+    if (ck.scene_fp != c->scene_fp) {
+        set_error(std::string(path) + " was rendered from another scene than the one set on this context");
+        return PT_ERR_INVALID;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    host::TileGeometry geo;
+    uint32_t tile_shift = 0;
+    while ((1u << tile_shift) < ck.key.tile) ++tile_shift;
+    if ((rc = host::tile_geometry(ck.key.frame.width, ck.total / ck.key.frame.width, tile_shift, geo))) return rc;
+    return c->adaptive.start(ck, geo, &ck.table, b.data() + ck.sums_at, b.data() + ck.a_at, c->stream);
 }
 
 int pt_ctx_radiance(pt_ctx *c, const float o[3], const float d[3], uint32_t depth, uint32_t n_samples, uint64_t seed,

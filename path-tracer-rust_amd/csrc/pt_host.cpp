@@ -1115,5 +1115,155 @@ TileTotals tile_totals(uint32_t width, uint32_t rows, const TileGeometry &g, con
     return t;
 }
 
+// ---------------------------------------------------------------------------------------------
+// The held adaptive frame: which class is next, what is held, the checkpoint
+AdaptiveSchedule::AdaptiveSchedule(const TileTable &t, uint32_t width, uint32_t rows, const TileGeometry &g, unsigned long long q,
+                                   uint32_t cap, uint32_t n0)
+    : cap_(cap), n0_(n0) {
+    std::vector<uint64_t> keys;
+    for (uint32_t i = 0; i < g.tiles; ++i)
+        if (!tile_closed(t.err[i], q, tile_pixels(width, rows, g, i))) keys.push_back((uint64_t)t.cnt[i] << 32 | t.na[i]);
+    std::sort(keys.begin(), keys.end());
+    for (uint64_t k : keys) {
+        if (classes_.empty() || classes_.back().first != k) classes_.push_back({k, 0u});
+        ++classes_.back().second;
+    }
+    open_ = (uint32_t)keys.size();
+}
+
+bool AdaptiveSchedule::next(AdaptiveStep &s) const {
+    if (classes_.empty() || (uint32_t)(classes_.front().first >> 32) >= cap_) return false;  // (ascending: no class is below the cap)
+    s.c = (uint32_t)(classes_.front().first >> 32);
+    s.na = (uint32_t)classes_.front().first;
+    s.n = classes_.front().second;
+    s.T = adaptive_next_count(s.c, n0_, cap_);
+    s.m = tracked_split(s.c, s.T);
+    s.to_a[0] = deal_to_a(s.c, s.na);
+    s.na_end = s.na + (s.to_a[0] ? s.m - s.c : 0u);
+    s.to_a[1] = s.m < s.T && deal_to_a(s.m, s.na_end);
+    if (s.to_a[1]) s.na_end += s.T - s.m;
+    return true;
+}
+
+void AdaptiveSchedule::done(const AdaptiveStep &s, uint32_t still_open, uint32_t closed) {
+    classes_.erase(classes_.begin());
+    open_ -= closed;
+    if (still_open == 0u) return;
+    const uint64_t k = (uint64_t)s.T << 32 | s.na_end;
+    auto at = std::lower_bound(classes_.begin(), classes_.end(), std::make_pair(k, 0u));
+    if (at != classes_.end() && at->first == k)
+        at->second += still_open;
+    else
+        classes_.insert(at, {k, still_open});
+}
+
+uint32_t AdaptiveSchedule::tiles_at_cap() const {
+    uint32_t n = 0;
+    for (const auto &c : classes_)
+        if ((uint32_t)(c.first >> 32) >= cap_) n += c.second;
+    return n;
+}
+
+// The adaptive checkpoint's layout: magic, u32 version, the key as PTACCUM1 writes it (7 x u32, u64 seed), u32 tile edge, u32 n_0,
+// u64 scene fingerprint, u32 call pixels, u32 tiles - 72 bytes; per tile u32 count, u32 nA, u64 E; the held sums; half A's sums;
+// u64 SipHash-1-3 of everything before it.
+namespace {
+constexpr char kAdCkptMagic[8] = {'P', 'T', 'A', 'D', 'A', 'P', 'T', '1'};
+constexpr uint32_t kAdCkptVersion = 1u;
+constexpr size_t kAdCkptHead = 8 + 4 + 7 * 4 + 8 + 2 * 4 + 8 + 2 * 4;  // 72 bytes
+}  // namespace
+
+void adckpt_encode_head(const AdaptiveCheckpoint &ck, std::vector<uint8_t> &b) {
+    b.reserve(b.size() + kAdCkptHead + 16 * (size_t)ck.tiles + 48 * (size_t)ck.total + 8);
+    b.insert(b.end(), kAdCkptMagic, kAdCkptMagic + 8);
+    put<uint32_t>(b, kAdCkptVersion);
+    const AccumKey &k = ck.key.frame;
+    for (uint32_t v : {k.width, k.height, k.idx_begin, k.idx_end, k.chunk_pixels, k.chunk_first, k.chunk_step}) put<uint32_t>(b, v);
+    put<uint64_t>(b, k.seed);
+    put<uint32_t>(b, ck.key.tile);
+    put<uint32_t>(b, ck.key.n0);
+    put<uint64_t>(b, ck.scene_fp);
+    put<uint32_t>(b, ck.total);
+    put<uint32_t>(b, ck.tiles);
+    for (uint32_t i = 0; i < ck.tiles; ++i) {
+        put<uint32_t>(b, ck.table.cnt[i]);
+        put<uint32_t>(b, ck.table.na[i]);
+        put<uint64_t>(b, ck.table.err[i]);
+    }
+}
+
+int adckpt_decode(uint64_t file_size, const uint8_t *b, size_t n, AdaptiveCheckpoint &out, std::string &why) {
+    auto bad = [&](const char *w) {
+        why = w;
+        return kCkptBad;
+    };
+    auto more = [&](size_t need) {
+        out.need = need;
+        return kCkptMore;
+    };
+    if (file_size < kAdCkptHead + 8) return bad("too short");
+    if (n < kAdCkptHead) return more(kAdCkptHead);
+    const uint8_t *r = b;
+    if (memcmp(r, kAdCkptMagic, 8) != 0) return bad("wrong magic");
+    r += 8;
+    if (get<uint32_t>(r) != kAdCkptVersion) return bad("unknown format version");
+    AccumKey &k = out.key.frame;
+    k.width = get<uint32_t>(r);
+    k.height = get<uint32_t>(r);
+    k.idx_begin = get<uint32_t>(r);
+    k.idx_end = get<uint32_t>(r);
+    k.chunk_pixels = get<uint32_t>(r);
+    k.chunk_first = get<uint32_t>(r);
+    k.chunk_step = get<uint32_t>(r);
+    k.seed = get<uint64_t>(r);
+    const uint32_t tile = out.key.tile = get<uint32_t>(r), n0 = out.key.n0 = get<uint32_t>(r);
+    out.scene_fp = get<uint64_t>(r);
+    const uint32_t total = out.total = get<uint32_t>(r), tiles = out.tiles = get<uint32_t>(r);
+    // the key must be one the call accepts and writes, and the sizes must be the ones it implies
+    pt_config kc{};
+    kc.width = k.width;
+    kc.height = k.height;
+    kc.spp = 1;
+    kc.idx_begin = k.idx_begin;
+    kc.idx_end = k.idx_end;
+    kc.chunk_pixels = k.chunk_pixels;
+    kc.chunk_first = k.chunk_first;
+    kc.chunk_step = k.chunk_step;
+    kc.seed = k.seed;
+    pt_adaptive_params kp{};
+    kp.tile = tile;
+    uint32_t ib = 0, ie = 0, tile_shift = 0;
+    if (check_cfg(&kc, &ib, &ie) != PT_OK || !(accum_key(&kc, ib, ie) == k) || check_adaptive_cfg(kc) != PT_OK)
+        return bad("the frame key is not a valid frame");
+    if (tile == 0u || check_adaptive_params(kp, &tile_shift) != PT_OK || n0 == 0u || n0 % 8u != 0u || n0 > 0xfffffff8u)
+        return bad("the tile edge or n_0 is not one the call writes");
+    TileGeometry g{};
+    if (total != ie - ib || tile_geometry(k.width, total / k.width, tile_shift, g) != PT_OK || tiles != g.tiles || tiles == 0u)
+        return bad("sizes that do not fit each other");
+    // (nothing behind the header is looked at before the file's size is the one the header implies)
+    const uint64_t want_size = kAdCkptHead + 16ull * tiles + 48ull * total + 8ull;
+    if (file_size != want_size) return bad(file_size < want_size ? "truncated" : "trailing bytes");
+    if (n < want_size) return more((size_t)want_size);
+    uint64_t tag;
+    memcpy(&tag, b + want_size - 8, 8);
+    if (tag != pt_siphash(1, 3, 0, 0, b, (size_t)want_size - 8)) return bad("bad trailing hash");
+    TileTable &t = out.table;
+    t.cnt.resize(tiles);
+    t.na.resize(tiles);
+    t.err.resize(tiles);
+    r = b + kAdCkptHead;
+    for (uint32_t i = 0; i < tiles; ++i) {
+        t.cnt[i] = get<uint32_t>(r);
+        t.na[i] = get<uint32_t>(r);
+        t.err[i] = get<uint64_t>(r);
+        if (t.cnt[i] > (1u << 24)) return bad("a sample count above 2^24");
+        if (t.na[i] > t.cnt[i]) return bad("half A holds more samples than the tile");
+        if (t.err[i] != kTileNoError && (t.na[i] == 0u || t.na[i] == t.cnt[i])) return bad("an E of a tile with an empty half");
+    }
+    out.sums_at = kAdCkptHead + 16 * (size_t)tiles;
+    out.a_at = out.sums_at + 24 * (size_t)total;
+    return kCkptOk;
+}
+
 }  // namespace host
 }  // namespace pt

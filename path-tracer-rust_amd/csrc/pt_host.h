@@ -242,5 +242,81 @@ struct TileTotals {
 TileTotals tile_totals(uint32_t width, uint32_t rows, const TileGeometry &g, const uint32_t *tile_spp, const unsigned long long *tile_err,
                        unsigned long long err_sum);
 
+// ---- the adaptive frame a context holds between calls (pt_ctx_accumulate_adaptive, ptrace.h): pure, tested on the CPU
+// n_0 of the key: min_spp (0 = 16) rounded up to a multiple of 8, BEFORE any cap (never above 0xfffffff8: every count is below)
+inline uint32_t adaptive_n0(uint32_t min_spp) {
+    const uint64_t n = min_spp ? min_spp : 16u;
+    return (uint32_t)std::min<uint64_t>((n + 7u) / 8u * 8u, 0xfffffff8ull);
+}
+// the count after c on the ladder n_0, 2 n_0, 4 n_0, ..: min(cap, the smallest ladder value > c)
+inline uint32_t adaptive_next_count(uint32_t c, uint32_t n0, uint32_t cap) {
+    uint64_t t = n0;
+    while (t <= c) t *= 2u;
+    return (uint32_t)std::min<uint64_t>(t, cap);
+}
+// The key of the held adaptive frame: pt_ctx_accumulate's, the tile edge and n_0
+struct AdaptiveKey {
+    AccumKey frame{};
+    uint32_t tile = 0, n0 = 0;
+    bool operator==(const AdaptiveKey &o) const { return frame == o.frame && tile == o.tile && n0 == o.n0; }
+};
+// The host's side of the held adaptive frame (pt_api.hip: HeldAdaptive adds the device planes and the tiles' device table) and
+// of a checkpoint of it: `total` pixels of the frame `key` in `tiles` tiles.  A frame is held iff tiles != 0.
+struct AdaptiveFrame {
+    AdaptiveKey key{};
+    uint32_t total = 0, tiles = 0;
+    bool held() const { return tiles != 0u; }
+    bool holds(const AdaptiveKey &k) const { return held() && key == k; }
+};
+// The per-tile state: the count, the samples of it in half A, the last E (kTileNoError: none)
+struct TileTable {
+    std::vector<uint32_t> cnt, na;
+    std::vector<unsigned long long> err;
+};
+// is a tile with this E closed under q (its `pixels` inside the frame)?  A tile without an E is open.
+inline bool tile_closed(unsigned long long E, unsigned long long q, uint64_t pixels) { return E != kTileNoError && E <= q * pixels; }
+// pixels of tile i inside a band of `rows` rows
+inline uint64_t tile_pixels(uint32_t width, uint32_t rows, const TileGeometry &g, uint32_t i) {
+    const uint32_t tile = 1u << g.tile_shift, x0 = i % g.tiles_x * tile, y0 = i / g.tiles_x * tile;
+    return (uint64_t)std::min(width - x0, tile) * std::min(rows - y0, tile);
+}
+
+// One step of a pt_ctx_accumulate_adaptive call: the class - the n open tiles that hold c samples, na of them in half A - goes
+// to T samples in the runs [c, m) and [m, T) (the second one empty when m == T); to_a[r]: run r goes to half A (the half that
+// holds fewer samples of the tile, a tie to A); na_end: half A's samples afterwards.
+struct AdaptiveStep {
+    uint32_t c, na, n, T, m, na_end;
+    bool to_a[2];
+    uint32_t runs() const { return m < T ? 2u : 1u; }
+};
+// WHICH CLASS IS NEXT.  Built from the tiles' table once, re-decided under q and the cap: how many tiles every class (c, nA)
+// holds open - never which ones (the device finds them: k_tile_select).  next(): the open tiles with the smallest c below the
+// cap, among those the smallest nA; false when no open tile is below the cap.  done(): the step's two words - the tiles it left
+// open and the tiles it closed - move the class to (T, na_end).
+class AdaptiveSchedule {
+   public:
+    AdaptiveSchedule(const TileTable &t, uint32_t width, uint32_t rows, const TileGeometry &g, unsigned long long q, uint32_t cap, uint32_t n0);
+    bool next(AdaptiveStep &s) const;
+    void done(const AdaptiveStep &s, uint32_t still_open, uint32_t closed);
+    uint32_t tiles_open() const { return open_; }
+    uint32_t tiles_at_cap() const;  // open tiles that take no samples: c >= cap
+
+   private:
+    std::vector<std::pair<uint64_t, uint32_t>> classes_;  // (c << 32 | nA, open tiles), ascending, none empty
+    uint32_t cap_, n0_, open_ = 0;
+};
+
+// ---- checkpoint of the held adaptive frame (pt_ctx_adaptive_save / _load, ptrace.h): as the held accumulate frame's
+struct AdaptiveCheckpoint : AdaptiveFrame {
+    TileTable table;
+    uint64_t scene_fp = 0;
+    size_t sums_at = 0, a_at = 0;  // the planes of 24 * total bytes each
+    size_t need = 0;               // kCkptMore: the leading bytes adckpt_decode asks for
+};
+// the file up to its planes appended to b; the planes follow (the held sums, then half A's), then ckpt_seal's hash
+void adckpt_encode_head(const AdaptiveCheckpoint &ck, std::vector<uint8_t> &b);
+// as ckpt_decode; kCkptBad also for nA > count, a count above 2^24, an E where a half is empty, sizes that do not fit the tiles
+int adckpt_decode(uint64_t file_size, const uint8_t *b, size_t n, AdaptiveCheckpoint &out, std::string &why);
+
 }  // namespace host
 }  // namespace pt

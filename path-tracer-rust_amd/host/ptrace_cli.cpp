@@ -22,7 +22,8 @@ static void usage() {
             "usage: ptrace <samplesPerPixel> <y-resolution> <scene id|index> [--width W] [--backend wavefront|megakernel]\n"
             "              [--seed S] [--gpus N] [--root DIR] [--out DIR] [--no-ppm] [--checkpoint FILE] [--aov N]\n"
             "              [--denoise [N]] [--noise-target X [--noise-map FILE.pfm]]\n"
-            "              [--adaptive X [--tile N] [--spp-map FILE.pfm] [--error-map FILE.pfm]] [--denoise-var [N]]\n"
+            "              [--adaptive X [--tile N] [--spp-map FILE.pfm] [--error-map FILE.pfm] [--adaptive-checkpoint FILE]]\n"
+            "              [--denoise-var [N]]\n"
             "  --checkpoint FILE: continue from the samples FILE holds (if it exists), render up to <samplesPerPixel> in all and\n"
             "                     save them to FILE; one GPU only; the seed defaults to 0 instead of the clock, so that the same\n"
             "                     command continues the same frame\n"
@@ -39,6 +40,9 @@ static void usage() {
             "  --adaptive X: <samplesPerPixel> becomes a cap: every tile (--tile N: 4, 8, 16 or 32 pixels square, default 8) is\n"
             "           rendered until its mean estimated error is at most X (pt_ctx_render_adaptive); one GPU; not with\n"
             "           --checkpoint or --noise-target\n"
+            "  --adaptive-checkpoint FILE: with --adaptive, continue the adaptive frame FILE holds (if it exists) to this X and\n"
+            "           this cap - only tiles still above X take samples - and save FILE again (pt_ctx_accumulate_adaptive);\n"
+            "           the seed defaults to 0 then\n"
             "  --spp-map FILE.pfm: with --adaptive, the samples every pixel got as a 1-channel PFM\n"
             "  --error-map FILE.pfm: with --adaptive, the estimate e(p) every pixel ended with (+inf: none) as a 1-channel PFM\n"
             "  --denoise-var [N]: with --noise-target or --adaptive: after the frame, denoise it on the GPU as far as its own noise\n"
@@ -107,6 +111,7 @@ struct AdaptiveRun {
     uint32_t tile = 0;
     std::string map;        // --spp-map
     std::string error_map;  // --error-map
+    std::string file;       // --adaptive-checkpoint
 };
 
 // --adaptive on one context on one GPU: the frame into img, the counts and the estimate through pt_write_pfm (one channel).
@@ -131,9 +136,31 @@ static int render_adaptive(const pt_config *cfg, pt_scene *sc, const AdaptiveRun
     if (!rc) rc = pt_device_malloc(dev, npix * 3 * sizeof(float), &d_out);
     if (!rc && !run.map.empty()) rc = pt_device_malloc(dev, npix * sizeof(uint32_t), &d_spp);
     if (!rc && (keep || !run.error_map.empty())) rc = pt_device_malloc(dev, npix * sizeof(float), &d_err);
+    if (!rc && !run.file.empty() && access(run.file.c_str(), F_OK) == 0) {
+        rc = pt_ctx_adaptive_load(ctx, run.file.c_str());
+        pt_adaptive_info held;
+        if (!rc) rc = pt_ctx_adaptive_info(ctx, cfg, &par, &held);
+        if (rc) {
+            fprintf(stderr, "cannot resume from %s (%d): %s\n", run.file.c_str(), rc, pt_last_error());
+            pt_ctx_destroy(ctx);
+            return kCliExit;
+        }
+        if (held.tiles == 0u) {
+            fprintf(stderr, "checkpoint %s is of another frame (size, seed, tile or scene): not resumed\n", run.file.c_str());
+            pt_ctx_destroy(ctx);
+            return kCliExit;
+        }
+        printf("Resuming from %.1f samples per pixel on average, %u of %u tiles open\n", (double)held.samples / (double)npix,
+               held.tiles_open, held.tiles);
+        fflush(stdout);
+    }
     if (!rc)
-        rc = pt_ctx_render_adaptive(ctx, cfg, &par, d_out, (uint32_t *)d_spp, (float *)d_err, nullptr, nullptr, progress, nullptr, st,
-                                    &as);
+        rc = pt_ctx_accumulate_adaptive(ctx, cfg, &par, d_out, (uint32_t *)d_spp, (float *)d_err, nullptr, nullptr, progress, nullptr,
+                                        st, &as);
+    if (!rc && !run.file.empty()) {
+        rc = pt_ctx_adaptive_save(ctx, run.file.c_str());
+        if (rc) fprintf(stderr, "cannot save checkpoint %s: %s\n", run.file.c_str(), pt_last_error());
+    }
     if (!rc) rc = pt_device_download(dev, img.data(), d_out, npix * 3 * sizeof(float));
     if (!rc) {
         printf("\nAdaptive, tile error %g: %u of %u tiles finished in %u levels, %.1f samples per pixel on average (cap %u), mean error %.6g\n",
@@ -416,6 +443,13 @@ int main(int argc, char **argv) {
                 return 1;
             }
         }
+        else if (a == "--adaptive-checkpoint") {
+            adaptive.file = next();
+            if (adaptive.file.empty()) {
+                usage();
+                return 1;
+            }
+        }
         else if (a == "--tile") adaptive.tile = (uint32_t)strtoul(next(), nullptr, 10);
         else if (a == "--spp-map") {
             adaptive.map = next();
@@ -494,6 +528,10 @@ int main(int argc, char **argv) {
         fprintf(stderr, "--error-map needs --adaptive\n");
         return 1;
     }
+    if (!adaptive.file.empty() && !is_adaptive) {
+        fprintf(stderr, "--adaptive-checkpoint needs --adaptive\n");
+        return 1;
+    }
     if (denoise_var_spp && denoise_spp) {
         fprintf(stderr, "--denoise-var cannot be combined with --denoise\n");
         return 1;
@@ -502,7 +540,7 @@ int main(int argc, char **argv) {
         fprintf(stderr, "--denoise-var needs a frame with a noise estimate: --noise-target or --adaptive\n");
         return 1;
     }
-    if (!checkpoint.empty() && !seed_given) seed = 0;
+    if ((!checkpoint.empty() || !adaptive.file.empty()) && !seed_given) seed = 0;
     // load_scene_ids (scenes.rs:28-38): a scenes/ directory without any *.json is filled with the built-in scenes
     if (scene_ids(root).empty()) {
         mkdir((root + "/scenes").c_str(), 0777);
