@@ -87,6 +87,17 @@ pub struct PtDenoiseVarParams {
     pub flags: u32,
 }
 
+// pt_ctx_present's parameters; all zero = the frame's own size, exposure 1, RGBA8, display order
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct PtPresentParams {
+    pub out_width: u32,
+    pub out_height: u32,
+    pub exposure: f32,
+    pub format: u32,
+    pub flags: u32,
+}
+
 // pt_ctx_denoise's parameters; a zero field = the library's default (pt_denoise_defaults)
 #[repr(C)]
 #[derive(Clone, Copy, Default, Debug)]
@@ -157,6 +168,9 @@ pub struct PtAdaptiveInfo {
     pub mean_error: f64,
 }
 pub const PT_DENOISE_NO_DEMODULATE: u32 = 1;
+pub const PT_PRESENT_RGBA8: u32 = 0;
+pub const PT_PRESENT_RGB8: u32 = 1;
+pub const PT_PRESENT_FRAMEBUFFER_ORDER: u32 = 1;
 
 pub const PT_OK: i32 = 0;
 pub const PT_CANCELLED: i32 = -4;
@@ -337,6 +351,17 @@ extern "C" {
         d_out: *mut f32,
         hip_stream: *mut c_void,
     ) -> i32;
+    // a float frame in device memory as gamma-corrected 8-bit pixels at the size asked for, in the canvas's order (the
+    // reference's gamma_correction per pixel and redraw, src/views/render_tab.rs:278-296, done once on the device)
+    pub fn pt_ctx_present(
+        ctx: *mut PtCtx,
+        width: u32,
+        height: u32,
+        params: *const PtPresentParams,
+        d_rgb: *const f32,
+        d_out: *mut u8,
+        hip_stream: *mut c_void,
+    ) -> i32;
     pub fn pt_write_pfm(path: *const c_char, data: *const f32, width: u32, height: u32, channels: u32) -> i32;
     pub fn pt_device_malloc(device: i32, bytes: usize, out: *mut *mut c_void) -> i32;
     pub fn pt_device_free(device: i32, p: *mut c_void) -> i32;
@@ -404,13 +429,47 @@ fn last_error() -> String {
     unsafe { CStr::from_ptr(pt_last_error()) }.to_string_lossy().into_owned()
 }
 
-/// what the progress callback needs: the counter and the pixel buffer the reference's 500 ms thread reads (:960-976)
+/// The window a preview is shown in: its size in pixels and the bytes the canvas draws, width * height * 4 (r, g, b, 255),
+/// row-major from the top left - gamma-corrected and in the canvas's order already (pt_ctx_present).  The GUI uploads them
+/// as a texture as they are; it neither walks the frame backwards nor calls gamma_correction (render_tab.rs:278-296).
+pub struct PreviewWindow {
+    pub width: u32,
+    pub height: u32,
+    pub rgba: Mutex<Vec<u8>>,
+}
+
+/// what the progress callback needs: the counter and the pixel buffer the reference's 500 ms thread reads (:960-976), and,
+/// for a host that shows a window, the window and its device buffer
 struct Preview<'a> {
     ctx: *mut PtCtx,
     d_snap: *mut c_void,
+    d_rgba: *mut u8,
+    frame: (u32, u32),
+    window: Option<&'a PreviewWindow>,
     pixels: &'a Mutex<Vec<Vec3>>,
     processed_pixel_count: &'a AtomicUsize,
     grid_size: usize,
+}
+
+/// d_rgb (the frame, in device memory) at the window's size into the window's bytes: one device call, 4 B per window pixel
+/// downloaded
+fn present_to_window(ctx: *mut PtCtx, frame: (u32, u32), d_rgb: *const c_void, d_rgba: *mut u8, win: &PreviewWindow) -> i32 {
+    let pp = PtPresentParams {
+        out_width: win.width,
+        out_height: win.height,
+        ..Default::default() // exposure 1, RGBA8, the canvas's order
+    };
+    let rc = unsafe { pt_ctx_present(ctx, frame.0, frame.1, &pp, d_rgb as *const f32, d_rgba, std::ptr::null_mut()) };
+    if rc != PT_OK {
+        return rc;
+    }
+    let n = win.width as usize * win.height as usize * 4;
+    let mut local = vec![0u8; n];
+    let rc = unsafe { pt_device_download(0, local.as_mut_ptr() as *mut c_void, d_rgba as *const c_void, n) };
+    if rc == PT_OK {
+        *win.rgba.lock().unwrap() = local;
+    }
+    rc
 }
 
 /// Called by the library between passes, at most every 500 ms (pt_config.progress_ms = 0: the reference's RenderUpdate
@@ -418,7 +477,8 @@ struct Preview<'a> {
 /// puts the picture accumulated so far into `pixels`, so that the RenderUpdate that thread sends next (:969-972) carries a
 /// partial image: pt_ctx_snapshot resolves the accumulators into device memory (every pixel over the samples it has so far
 /// - the reference's partial image is a random subset of finished pixels, this one is the whole frame at partial spp),
-/// one download, one copy under the mutex (held for a memcpy, as render_pixel_to_vec holds it for one store, :1013-1014).
+/// With a window, pt_ctx_present then fits the snapshot to the window on the device and 4 B per WINDOW pixel come down;
+/// without one, the floats do: one download, one copy under the mutex (held for a memcpy, as render_pixel_to_vec holds it for one store, :1013-1014).
 extern "C" fn on_progress(user: *mut c_void, fraction: f32) {
     let p = unsafe { &*(user as *const Preview) };
     p.processed_pixel_count
@@ -429,6 +489,11 @@ extern "C" fn on_progress(user: *mut c_void, fraction: f32) {
     let mut spp_done: u32 = 0;
     if unsafe { pt_ctx_snapshot(p.ctx, p.d_snap, &mut spp_done) } != PT_OK {
         return; // nothing accumulated yet
+    }
+    if let Some(win) = p.window {
+        // same stream as the snapshot (the context's own): in stream order after it
+        let _ = present_to_window(p.ctx, p.frame, p.d_snap as *const c_void, p.d_rgba, win);
+        return;
     }
     let mut local = vec![Vec3::default(); p.grid_size];
     let bytes = p.grid_size * 3 * std::mem::size_of::<f32>();
@@ -447,6 +512,7 @@ pub fn render_pixels_hip(
     cancel: &AtomicBool,
     processed_pixel_count: &AtomicUsize,
     seed: u64,
+    window: Option<&PreviewWindow>,
 ) -> Result<PtStats, String> {
     let (cam, objs, tris) = flatten(&cfg.scene);
     let grid_size = cfg.resolution.width * cfg.resolution.height;
@@ -460,6 +526,7 @@ pub fn render_pixels_hip(
     };
     let mut ctx: *mut PtCtx = std::ptr::null_mut();
     let (mut d_out, mut d_snap): (*mut c_void, *mut c_void) = (std::ptr::null_mut(), std::ptr::null_mut());
+    let mut d_rgba: *mut c_void = std::ptr::null_mut();
     let mut st = PtStats::default();
     let rc = unsafe {
         let mut rc = pt_ctx_create(0, &mut ctx);
@@ -472,10 +539,16 @@ pub fn render_pixels_hip(
         if rc == PT_OK {
             rc = pt_device_malloc(0, bytes, &mut d_snap);
         }
+        if let (true, Some(win)) = (rc == PT_OK, window) {
+            rc = pt_device_malloc(0, win.width as usize * win.height as usize * 4, &mut d_rgba);
+        }
         if rc == PT_OK {
             let preview = Preview {
                 ctx,
                 d_snap,
+                d_rgba: d_rgba as *mut u8,
+                frame: (c.width, c.height),
+                window,
                 pixels,
                 processed_pixel_count,
                 grid_size,
@@ -501,11 +574,19 @@ pub fn render_pixels_hip(
             } else {
                 rc = rc2;
             }
+            // ... and the window shows it
+            if let (true, Some(win)) = (rc2 == PT_OK, window) {
+                let rc3 = present_to_window(ctx, (c.width, c.height), d_out, d_rgba as *mut u8, win);
+                if rc3 != PT_OK {
+                    rc = rc3;
+                }
+            }
         }
         rc
     };
     let msg = if rc == PT_OK || rc == PT_CANCELLED { String::new() } else { last_error() };
     unsafe {
+        pt_device_free(0, d_rgba);
         pt_device_free(0, d_snap);
         pt_device_free(0, d_out);
         pt_ctx_destroy(ctx);
@@ -523,7 +604,7 @@ pub fn render_pixels_hip(
 //     let render_pixel_to_vec = ...;                       // unchanged (CPU path)
 //     if hip::pt_device_count() > 0 && !MOCK_RANDOM {
 //         let seed = rand::random::<u64>();                // the reference is OS-seeded too (:53)
-//         match hip::render_pixels_hip(&render_config, &pixels, &stop_render, &processed_pixel_count, seed) {
+//         match hip::render_pixels_hip(&render_config, &pixels, &stop_render, &processed_pixel_count, seed, None) {
 //             Ok(stats) => println!("GPU: {} ray bounces in {:.1} ms", stats.ray_bounces, stats.ms_total),
 //             Err(msg) => panic!("libptrace_hip: {msg}"),  // the reference unwraps its own errors (:1032,1042)
 //         }

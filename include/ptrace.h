@@ -714,6 +714,69 @@ int pt_ctx_denoise_var(pt_ctx *ctx, uint32_t width, uint32_t height, const pt_de
                        const float *d_color, const float *d_error, const float *d_albedo, const float *d_normal,
                        const float *d_depth, float *d_out, void *hip_stream);
 
+/* ---- presenting a frame: fit to a window, gamma, 8 bits ----------------------------------------------------------
+ * pt_ctx_present turns a linear float frame in device memory into what a window or an image file holds: gamma-corrected 8-bit
+ * pixels at the size asked for, in display order.  The host downloads 4 B per window pixel instead of 12 B per frame pixel and
+ * never calls powf.
+ * - Buffers: device pointers.  d_rgb is width * height * 3 floats in framebuffer order - what pt_ctx_render,
+ *   pt_ctx_accumulate*, pt_ctx_snapshot, pt_ctx_adaptive_resolve and the denoisers write for a whole frame (a cfg without a band
+ *   and without chunks).  d_out is out_width * out_height * 4 (PT_PRESENT_RGBA8: r, g, b, 255) or * 3 (PT_PRESENT_RGB8) bytes,
+ *   row-major from the top-left display pixel; for RGBA8 it is 4-byte aligned, as every device allocation is.  d_out may not
+ *   alias d_rgb.
+ * - `hip_stream` as for pt_ctx_render (NULL = the context's own stream); blocking.  No scene is needed.
+ * - The call may be made from a progress callback, in stream order after pt_ctx_snapshot or pt_ctx_adaptive_resolve on the same
+ *   stream.  It changes no other state of the context: not the frame accumulators, not the held frames, not the denoisers'
+ *   scratch, not the measured pass rates.
+ * - Scratch lives in the context, grows on demand, is reused between calls and is freed by pt_ctx_destroy; it is outside the
+ *   ray-queue budget (pt_ctx_set_memory_budget): the 1 KB table, uploaded by the first call, and - only when the size changes -
+ *   an intermediate of width * out_height * 24 B (the source rows an output row covers, summed per column and channel).  It
+ *   shares nothing with the denoisers.
+ * - PT_ERR_INVALID, all refused before any device is touched, checked in this order: an exposure that is negative, not finite
+ *   or NaN; an unknown format; flag bits other than PT_PRESENT_FRAMEBUFFER_ORDER; width or height 0; exactly one of out_width,
+ *   out_height 0; width * height or out_width * out_height above 2^28; NULL d_rgb; NULL d_out; NULL ctx.  PT_ERR_HIP: a HIP
+ *   call failed (an intermediate that does not fit the device among them).
+ *
+ * THE ARITHMETIC.  All operations are IEEE binary32, correctly rounded, never contracted, except where integers or binary64
+ * are named.  W, H = width, height; OW, OH = the output size (out_width, out_height, or W, H when both are 0).
+ * 1. Display image.  Without PT_PRESENT_FRAMEBUFFER_ORDER D(x, y) = frame[W*H-1-(y*W+x)]: the order pt_write_ppm lists and the
+ *    reference's canvas draws.  With the flag D(x, y) = frame[y*W+x].
+ * 2. Per source value v: v' = v * exposure (one multiply; exposure 0 stands for 1); c(v') = v' > 0 ? (v' > 1 ? 1 : v') : 0.
+ *    NaN and -0 give +0, +inf gives 1.
+ * 3. Same size (OW == W and OH == H): m = c(v').  No fixed point: this path reproduces pt_write_ppm's numbers exactly.
+ * 4. Otherwise, the area average in integers.  q = (uint64) floor(c(v') * 2^32) (the product is exact; q <= 2^32).  Output cell
+ *    X covers [X*W, (X+1)*W) on an axis where source pixel x covers [x*OW, (x+1)*OW); wx(X, x) is the integer length of their
+ *    overlap, wy(Y, y) likewise with H and OH, so sum_x wx = W and sum_y wy = H.  S = sum_y sum_x wy * wx * q in u64: below 2^60
+ *    (at most W * H * 2^32), independent of the order of summation.  m = (float)((double)S / ((double)(W*H) * 4294967296.0)):
+ *    the u64 -> binary64 conversion rounds to nearest even, the divisor is exact, one binary64 division, one rounding to
+ *    binary32.  The same rule serves shrinking, enlarging and an axis whose size does not change.
+ * 5. Eight bits: a table, not powf, is the contract on the device.  T[k], k = 1..255, is the bit pattern of the smallest
+ *    binary32 x in [0, 1] with pt_to_int_with_gamma_correction(x) >= k, found on the host by bisection over bit patterns
+ *    (non-negative floats order as their bits) with the host's own powf, once per process (thread-safe); T[0] = 0.  byte(m) =
+ *    the number of k in 1..255 with bits(m) >= T[k].  It equals pt_to_int_with_gamma_correction(m) for every m iff that
+ *    function does not decrease on [0, 1] - which holds for the libm this was checked against over all 1 065 353 217 bit
+ *    patterns (tests/test_present_abi.py samples them).  The table's values belong to the host's libm: read them with
+ *    pt_present_thresholds, never hard-code them.
+ * pt_present_thresholds returns T.  pt_present_quantize_host applies steps 2 and 5 to n values on the host: the host
+ * instantiation of the source the kernels compile (csrc/pt_present.h), to them what pt_host_sincos is to the device's sincos.
+ * PT_ERR_INVALID for an exposure pt_ctx_present refuses and for a NULL pointer.  pt_write_ppm8 writes width * height * 3 bytes as
+ * a binary PPM ("P6\n<width> <height>\n255\n" and the bytes); PT_ERR_INVALID for a NULL argument or an empty image, PT_ERR_IO
+ * when the file cannot be written.  None of the three needs a device. */
+#define PT_PRESENT_RGBA8 0u   /* r, g, b, 255 */
+#define PT_PRESENT_RGB8  1u
+#define PT_PRESENT_FRAMEBUFFER_ORDER 1u  /* flags: do not turn the frame into display order */
+typedef struct pt_present_params {
+    uint32_t out_width, out_height; /* 0, 0 = the frame's own size; one of them 0 alone: PT_ERR_INVALID */
+    float exposure;                 /* 0 = 1; finite, > 0 otherwise */
+    uint32_t format;                /* PT_PRESENT_* */
+    uint32_t flags;
+} pt_present_params;
+int pt_ctx_present(pt_ctx *ctx, uint32_t width, uint32_t height, const pt_present_params *params /* NULL = all zero */,
+                   const float *d_rgb, uint8_t *d_out, void *hip_stream);
+/* host only, no device needed */
+int pt_present_thresholds(uint32_t out[256]);
+int pt_present_quantize_host(const float *in, size_t n, float exposure, uint8_t *out);
+int pt_write_ppm8(const char *path, const uint8_t *rgb8, uint32_t width, uint32_t height); /* binary P6, maxval 255 */
+
 /* ---- the one collective of the path: the framebuffer gather over RCCL (xGMI) ---------------------------------
  * One process (or thread) per GPU renders its rows with pt_ctx_render (chunk_first = rank, chunk_step = n_ranks) into
  * device memory; pt_comm_gather_frame then gives EVERY rank the whole frame in device memory: one in-place

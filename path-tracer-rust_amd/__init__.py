@@ -57,6 +57,11 @@ class pt_denoise_var_params(C.Structure):
     _fields_ = [("levels", C.c_uint32), ("sigma_var", C.c_float), ("sigma_depth", C.c_float), ("flags", C.c_uint32)]
 
 
+class pt_present_params(C.Structure):
+    _fields_ = [("out_width", C.c_uint32), ("out_height", C.c_uint32), ("exposure", C.c_float), ("format", C.c_uint32),
+                ("flags", C.c_uint32)]
+
+
 class pt_noise_stats(C.Structure):
     _fields_ = [("spp_min", C.c_uint32), ("spp_max", C.c_uint32), ("spp_a_min", C.c_uint32), ("spp_b_min", C.c_uint32),
                 ("pixels", C.c_uint64), ("mean_error", C.c_double), ("histogram", C.c_uint32 * 64)]
@@ -81,6 +86,8 @@ class pt_adaptive_info(C.Structure):
 
 
 PT_DENOISE_NO_DEMODULATE = 1
+PT_PRESENT_RGBA8, PT_PRESENT_RGB8 = 0, 1
+PT_PRESENT_FRAMEBUFFER_ORDER = 1
 PT_OK, PT_ERR_INVALID, PT_ERR_NO_DEVICE, PT_ERR_HIP, PT_CANCELLED = 0, -1, -2, -3, -4
 PT_ERR_IO, PT_ERR_PARSE = -6, -7
 BACKEND_WAVEFRONT, BACKEND_MEGAKERNEL = 0, 1
@@ -137,6 +144,11 @@ def lib():
     L.pt_denoise_var_defaults.argtypes = [C.POINTER(pt_denoise_var_params)]
     L.pt_ctx_denoise_var.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(pt_denoise_var_params), C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.pt_ctx_present.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(pt_present_params), C.c_void_p, C.c_void_p,
+                                 C.c_void_p]
+    L.pt_present_thresholds.argtypes = [C.POINTER(C.c_uint32)]
+    L.pt_present_quantize_host.argtypes = [C.POINTER(C.c_float), C.c_size_t, C.c_float, C.POINTER(C.c_uint8)]
+    L.pt_write_ppm8.argtypes = [C.c_char_p, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32]
     L.pt_write_pfm.argtypes = [C.c_char_p, C.POINTER(C.c_float), C.c_uint32, C.c_uint32, C.c_uint32]
     L.pt_ctx_set_profiling.argtypes = [C.c_void_p, C.c_int]
     L.pt_ctx_pass_kernel.argtypes = [C.c_void_p, C.c_uint32]
@@ -293,6 +305,17 @@ class Context:
         _check(lib().pt_ctx_denoise_var(self._h, width, height, C.byref(p), ptr(color), ptr(error), ptr(albedo), ptr(normal),
                                         ptr(depth), ptr(out), C.c_void_p(stream or 0)))
 
+    def present(self, width, height, rgb, out, out_size=None, exposure=0.0, rgb8=False, framebuffer_order=False, stream=None):
+        """A whole width x height float frame in device memory as gamma-corrected 8-bit pixels (pt_ctx_present): `rgb` is a
+        device pointer to pixels * 3 float32, `out` one to out pixels * 4 bytes (r, g, b, 255) or * 3 with rgb8=True, row-major
+        from the top-left display pixel.  out_size=(w, h) fits the frame to that size by area averaging; exposure 0 = 1;
+        framebuffer_order=True keeps the frame's own order instead of the display's."""
+        ow, oh = out_size if out_size else (0, 0)
+        p = pt_present_params(ow, oh, exposure, PT_PRESENT_RGB8 if rgb8 else PT_PRESENT_RGBA8,
+                              PT_PRESENT_FRAMEBUFFER_ORDER if framebuffer_order else 0)
+        ptr = lambda q: C.c_void_p(q) if q else None  # noqa: E731
+        _check(lib().pt_ctx_present(self._h, width, height, C.byref(p), ptr(rgb), ptr(out), C.c_void_p(stream or 0)))
+
     def accum_track_noise(self, on=True):
         """Keep half of every pixel's samples in a second accumulator for the frames started from now on
         (pt_ctx_accum_track_noise), so that accum_noise() / accumulate_until() can estimate the frame's error."""
@@ -447,6 +470,35 @@ def write_pfm(path, array):
         raise ValueError("write_pfm wants a (height, width[, channels]) array, not shape %r" % (a.shape,))
     channels = a.shape[2] if a.ndim == 3 else 1
     _check(lib().pt_write_pfm(os.fsencode(path), a.ctypes.data_as(C.POINTER(C.c_float)), a.shape[1], a.shape[0], channels))
+
+
+def write_ppm8(path, array):
+    """8-bit pixels as a binary PPM (pt_write_ppm8): `array` is (height, width, 3) uint8 from the top-left pixel - what
+    Context.present(rgb8=True) wrote, downloaded."""
+    import numpy as np
+
+    a = np.ascontiguousarray(array, dtype=np.uint8)
+    if a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError("write_ppm8 wants a (height, width, 3) array, not shape %r" % (a.shape,))
+    _check(lib().pt_write_ppm8(os.fsencode(path), a.ctypes.data_as(C.POINTER(C.c_uint8)), a.shape[1], a.shape[0]))
+
+
+def present_thresholds():
+    """pt_ctx_present's table (pt_present_thresholds): 256 bit patterns, T[k] the smallest float that maps to at least k."""
+    t = (C.c_uint32 * 256)()
+    _check(lib().pt_present_thresholds(t))
+    return list(t)
+
+
+def present_quantize_host(values, exposure=0.0):
+    """pt_ctx_present's per-value mapping on the host (pt_present_quantize_host): float32 values to bytes, same shape."""
+    import numpy as np
+
+    a = np.ascontiguousarray(values, dtype=np.float32)
+    out = np.zeros(a.shape, dtype=np.uint8)
+    _check(lib().pt_present_quantize_host(a.ctypes.data_as(C.POINTER(C.c_float)), a.size, exposure,
+                                          out.ctypes.data_as(C.POINTER(C.c_uint8))))
+    return out
 
 
 def denoise_defaults():

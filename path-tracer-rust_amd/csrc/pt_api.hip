@@ -17,6 +17,7 @@
 #include "pt_host.h"
 #include "pt_kernels.h"
 #include "pt_noise.h"
+#include "pt_present.h"
 #include "pt_tile.h"
 
 namespace pt {
@@ -331,6 +332,10 @@ struct pt_ctx {
     DevBuf<NoiseCounters> noise_cnt;
     // pt_ctx_denoise's scratch, kept between calls: the two colour planes and the packed guides, one float4 per pixel each
     DevBuf<float4> dn_u[2], dn_guide;
+    // pt_ctx_present's scratch, its own (outside the ray-queue budget): the threshold table, uploaded by the first call, and the
+    // resampling form's intermediate, [3] planes of width * out_height u64, grown on demand
+    DevBuf<uint32_t> pr_table;
+    DevBuf<unsigned long long> pr_mid;
     // The adaptive calls: the frame kept between calls (pt_ctx_set_scene drops it), and their scratch, kept too and grown on
     // demand: the compact accumulator of a step's tiles, the step's open-tile list, the counters (u64 [0]: the sum of E at the
     // end; u32 [2], [3]: the tiles a step left open / closed; u32 [4]: the list's length; u32 [5..7]: k_tile_select's counts),
@@ -2678,6 +2683,57 @@ int pt_ctx_denoise_var(pt_ctx *c, uint32_t width, uint32_t height, const pt_deno
     if (!c) return refuse("ctx is NULL");
     return run_denoise(c, width, height, P.levels, P.sigma_var, P.sigma_depth, P.flags, d_color, d_error, d_albedo, d_normal,
                        d_depth, d_out, hip_stream);
+}
+
+int pt_ctx_present(pt_ctx *c, uint32_t width, uint32_t height, const pt_present_params *params, const float *d_rgb, uint8_t *d_out,
+                   void *hip_stream) {
+    // everything that can be refused is refused here, before the device is touched
+    pt_present_params P{};
+    if (params) P = *params;
+    if (!host::finite_nonneg(P.exposure)) return refuse("pt_present_params.exposure is negative or not finite");
+    if (P.format != PT_PRESENT_RGBA8 && P.format != PT_PRESENT_RGB8) return refuse("pt_present_params.format: unknown format");
+    if (P.flags & ~PT_PRESENT_FRAMEBUFFER_ORDER) return refuse("pt_present_params.flags: unknown bits");
+    if (!width || !height) return refuse("width and height must be positive");
+    if ((P.out_width == 0u) != (P.out_height == 0u)) return refuse("pt_present_params: one of out_width, out_height is 0 alone");
+    const uint32_t ow = P.out_width ? P.out_width : width, oh = P.out_height ? P.out_height : height;
+    if ((uint64_t)width * height > (1ull << 28) || (uint64_t)ow * oh > (1ull << 28))
+        return refuse("width*height or out_width*out_height exceeds 2^28");
+    if (!d_rgb) return refuse("d_rgb is NULL");
+    if (!d_out) return refuse("d_out is NULL");
+    if (!c) return refuse("ctx is NULL");
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    if (!c->pr_table.p) {
+        const int rc = c->pr_table.ensure(256);
+        if (rc) return rc;
+        // (the table lives as long as the process: the copy may read it whenever it runs)
+        const hipError_t e = hipMemcpyAsync(c->pr_table.p, present_table(), 256 * sizeof(uint32_t), hipMemcpyHostToDevice, st);
+        if (e != hipSuccess) {
+            c->pr_table.release();
+            set_error(std::string("uploading the present table: ") + hipGetErrorString(e));
+            return PT_ERR_HIP;
+        }
+    }
+    PresentFrame f{};
+    f.rgb = d_rgb;
+    f.out = d_out;
+    f.width = width;
+    f.height = height;
+    f.out_width = ow;
+    f.out_height = oh;
+    f.bpp = P.format == PT_PRESENT_RGBA8 ? 4u : 3u;
+    f.flip = !(P.flags & PT_PRESENT_FRAMEBUFFER_ORDER);
+    f.exposure = P.exposure == 0.0f ? 1.0f : P.exposure;
+    f.table = c->pr_table.p;
+    if (ow != width || oh != height) {
+        const int rc = c->pr_mid.ensure(3 * (size_t)width * oh);
+        if (rc) return rc;
+        f.mid = c->pr_mid.p;
+    }
+    launch_present(st, f);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    return PT_OK;
 }
 
 // one band on one device into the host framebuffer

@@ -8,6 +8,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -23,7 +24,7 @@ static void usage() {
             "              [--seed S] [--gpus N] [--root DIR] [--out DIR] [--no-ppm] [--checkpoint FILE] [--aov N]\n"
             "              [--denoise [N]] [--noise-target X [--noise-map FILE.pfm]]\n"
             "              [--adaptive X [--tile N] [--spp-map FILE.pfm] [--error-map FILE.pfm] [--adaptive-checkpoint FILE]]\n"
-            "              [--denoise-var [N]]\n"
+            "              [--denoise-var [N]] [--preview FILE.ppm [--preview-size WxH] [--exposure E]]\n"
             "  --checkpoint FILE: continue from the samples FILE holds (if it exists), render up to <samplesPerPixel> in all and\n"
             "                     save them to FILE; one GPU only; the seed defaults to 0 instead of the clock, so that the same\n"
             "                     command continues the same frame\n"
@@ -47,7 +48,11 @@ static void usage() {
             "  --error-map FILE.pfm: with --adaptive, the estimate e(p) every pixel ended with (+inf: none) as a 1-channel PFM\n"
             "  --denoise-var [N]: with --noise-target or --adaptive: after the frame, denoise it on the GPU as far as its own noise\n"
             "           estimate says (pt_ctx_denoise_var, default parameters), guides and files as for --denoise; one GPU only;\n"
-            "           not with --denoise\n");
+            "           not with --denoise\n"
+            "  --preview FILE.ppm: after the frame (after --denoise / --denoise-var: of the denoised frame), turn it into 8-bit display\n"
+            "           pixels on the GPU (pt_ctx_present, RGB8) and write them as a binary PPM; --preview-size WxH fits the frame to\n"
+            "           that size by area averaging (default: the frame's own), --exposure E scales it first (default 1); one GPU\n"
+            "           only\n");
 }
 
 static std::vector<std::string> scene_ids(const std::string &root) {
@@ -326,6 +331,30 @@ static int write_denoised(const pt_config *frame, uint32_t spp, const DeviceFram
     return rc;
 }
 
+// --preview: the device frame as 8-bit display pixels (pt_ctx_present, RGB8) at ow x oh (0, 0: the frame's size), and the P6 file
+static int write_preview(const pt_config *frame, const DeviceFrame &df, const std::string &path, uint32_t ow, uint32_t oh,
+                         float exposure) {
+    pt_present_params pp;
+    memset(&pp, 0, sizeof pp);
+    pp.out_width = ow;
+    pp.out_height = oh;
+    pp.exposure = exposure;
+    pp.format = PT_PRESENT_RGB8;
+    if (!ow) ow = frame->width, oh = frame->height;
+    std::vector<uint8_t> px((size_t)ow * oh * 3);
+    void *d_px = nullptr;
+    int rc = pt_device_malloc(df.dev, px.size(), &d_px);
+    if (!rc) rc = pt_ctx_present(df.ctx, frame->width, frame->height, &pp, (const float *)df.d_out, (uint8_t *)d_px, nullptr);
+    if (!rc) rc = pt_device_download(df.dev, px.data(), d_px, px.size());
+    if (d_px) pt_device_free(df.dev, d_px);
+    if (!rc) rc = pt_write_ppm8(path.c_str(), px.data(), ow, oh);
+    if (rc)
+        fprintf(stderr, "cannot write the preview %s (%d): %s\n", path.c_str(), rc, pt_last_error());
+    else
+        printf("wrote %s\n", path.c_str());
+    return rc;
+}
+
 // --aov: the frame's first-hit AOVs at `spp` samples (pt_ctx_render_aov) on one GPU, and the five PFM files at `stem`
 static int write_aovs(const pt_config *frame, uint32_t spp, pt_scene *sc, const std::vector<float> &img, const std::string &stem) {
     int dev = 0;
@@ -393,6 +422,9 @@ int main(int argc, char **argv) {
     uint32_t gpus = 1, aov_spp = 0, denoise_spp = 0, denoise_var_spp = 0;
     NoiseRun noise;
     AdaptiveRun adaptive;
+    std::string preview;
+    uint32_t preview_w = 0, preview_h = 0;
+    float exposure = 0.0f;
     for (int i = 4; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&]() -> const char * { return i + 1 < argc ? argv[++i] : ""; };
@@ -413,6 +445,29 @@ int main(int argc, char **argv) {
         else if (a == "--root") root = next();
         else if (a == "--out") out_dir = next();
         else if (a == "--no-ppm") write_ppm = false;
+        else if (a == "--preview") {
+            preview = next();
+            if (preview.empty()) {
+                usage();
+                return 1;
+            }
+        }
+        else if (a == "--preview-size") {
+            char x = 0, rest = 0;
+            if (sscanf(next(), "%u%c%u%c", &preview_w, &x, &preview_h, &rest) != 3 || x != 'x' || !preview_w || !preview_h) {
+                fprintf(stderr, "--preview-size needs WxH, both positive\n");
+                return 1;
+            }
+        }
+        else if (a == "--exposure") {
+            char *e = nullptr;
+            const char *v = next();
+            exposure = strtof(v, &e);
+            if (e == v || *e || !(exposure > 0.0f) || !(exposure < INFINITY)) {
+                fprintf(stderr, "--exposure needs a positive finite number\n");
+                return 1;
+            }
+        }
         else if (a == "--aov") {
             aov_spp = (uint32_t)strtoul(next(), nullptr, 10);
             if (!aov_spp) {
@@ -532,6 +587,14 @@ int main(int argc, char **argv) {
         fprintf(stderr, "--adaptive-checkpoint needs --adaptive\n");
         return 1;
     }
+    if (!preview.empty() && gpus > 1) {
+        fprintf(stderr, "--preview works with one GPU only (--gpus %u)\n", gpus);
+        return 1;
+    }
+    if (preview.empty() && (preview_w || exposure != 0.0f)) {
+        fprintf(stderr, "--preview-size and --exposure go with --preview FILE.ppm\n");
+        return 1;
+    }
     if (denoise_var_spp && denoise_spp) {
         fprintf(stderr, "--denoise-var cannot be combined with --denoise\n");
         return 1;
@@ -587,13 +650,14 @@ int main(int argc, char **argv) {
     pt_stats st;
     DeviceFrame df;
     df.want_error = denoise_var_spp != 0;
+    const bool keep_frame = denoise_spp || denoise_var_spp || !preview.empty();  // the frame stays on its GPU for what follows
     if (is_adaptive)
-        rc = render_adaptive(&cfg, sc, adaptive, img, &st, denoise_var_spp ? &df : nullptr);
-    else if (checkpoint.empty() && !denoise_spp && !(noise.target > 0.0f))
+        rc = render_adaptive(&cfg, sc, adaptive, img, &st, keep_frame ? &df : nullptr);
+    else if (checkpoint.empty() && !keep_frame && !(noise.target > 0.0f))
         rc = pt_render_multi(&cfg, gpus ? gpus : 1, pt_scene_camera(sc), objs, n_objs, tris, n_tris, img.data(), nullptr,
                              progress, nullptr, &st);
     else
-        rc = render_on_context(&cfg, sc, checkpoint, img, &st, denoise_spp || denoise_var_spp ? &df : nullptr, &noise);
+        rc = render_on_context(&cfg, sc, checkpoint, img, &st, keep_frame ? &df : nullptr, &noise);
     const uint32_t spp_out = noise.target > 0.0f && !rc ? noise.spp_reached : spp;  // the samples the frame holds
     cfg.spp = spp_out;
     auto release = [&]() {
@@ -642,6 +706,10 @@ int main(int argc, char **argv) {
     }
     if ((denoise_spp || denoise_var_spp) &&
         write_denoised(&cfg, denoise_spp ? denoise_spp : denoise_var_spp, df, stem, pt_scene_id(sc))) {
+        release();
+        return 3;
+    }
+    if (!preview.empty() && write_preview(&cfg, df, preview, preview_w, preview_h, exposure)) {
         release();
         return 3;
     }

@@ -22,6 +22,7 @@
 
 #include "../../include/ptrace.h"
 #include "../csrc/pt_host.h"
+#include "../csrc/pt_present.h"
 
 namespace {
 
@@ -1164,6 +1165,83 @@ int pt_write_ppm(const char *path, const float *rgb, uint32_t width, uint32_t he
     const size_t wr = fwrite(buf.data(), 1, buf.size(), f);
     const int cl = fclose(f);
     if (wr != buf.size() || cl != 0) {
+        pt::set_error(std::string("short write to ") + path);
+        return PT_ERR_IO;
+    }
+    return PT_OK;
+}
+
+}  // extern "C"
+
+// pt_ctx_present's table: T[k], k = 1..255, the bit pattern of the smallest binary32 x in [0, 1] with
+// pt_to_int_with_gamma_correction(x) >= k; T[0] = 0.  Non-negative floats order as their bits, so the search bisects bit
+// patterns: the function is below k at `lo` and at least k at `hi` throughout.  Built once per process.
+namespace pt {
+const uint32_t *present_table() {
+    static const struct Table {
+        uint32_t T[256];
+        Table() {
+            T[0] = 0u;
+            for (uint32_t k = 1; k < 256u; ++k) {
+                uint32_t lo = 0u, hi = 0x3f800000u;  // 0 maps to 0, 1 to 255
+                while (hi - lo > 1u) {
+                    const uint32_t mid = lo + (hi - lo) / 2u;
+                    float x;
+                    memcpy(&x, &mid, 4);
+                    if (pt_to_int_with_gamma_correction(x) >= k)
+                        hi = mid;
+                    else
+                        lo = mid;
+                }
+                T[k] = hi;
+            }
+        }
+    } table;  // (a function-local static: initialised once, thread-safe)
+    return table.T;
+}
+}  // namespace pt
+
+extern "C" {
+
+int pt_present_thresholds(uint32_t out[256]) {
+    if (!out) {
+        pt::set_error("out is NULL");
+        return PT_ERR_INVALID;
+    }
+    memcpy(out, pt::present_table(), 256 * sizeof(uint32_t));
+    return PT_OK;
+}
+
+int pt_present_quantize_host(const float *in, size_t n, float exposure, uint8_t *out) {
+    if (!pt::host::finite_nonneg(exposure)) {
+        pt::set_error("exposure is negative or not finite");
+        return PT_ERR_INVALID;
+    }
+    if (n && (!in || !out)) {
+        pt::set_error("NULL argument");
+        return PT_ERR_INVALID;
+    }
+    const float e = exposure == 0.0f ? 1.0f : exposure;
+    const uint32_t *T = pt::present_table();
+    for (size_t i = 0; i < n; ++i) out[i] = (uint8_t)pt::present_byte(T, pt::present_bits(pt::present_clamp(in[i], e)));
+    return PT_OK;
+}
+
+int pt_write_ppm8(const char *path, const uint8_t *rgb8, uint32_t width, uint32_t height) {
+    if (!path || !rgb8 || width == 0 || height == 0) {
+        pt::set_error("NULL argument or an empty image");
+        return PT_ERR_INVALID;
+    }
+    FILE *f = fopen(path, "wb");
+    if (!f) {
+        pt::set_error(std::string("cannot create ") + path);
+        return PT_ERR_IO;
+    }
+    const std::string head = "P6\n" + std::to_string(width) + " " + std::to_string(height) + "\n255\n";
+    const size_t n = (size_t)width * height * 3u;
+    const size_t wr = fwrite(head.data(), 1, head.size(), f) + fwrite(rgb8, 1, n, f);
+    const int cl = fclose(f);
+    if (wr != head.size() + n || cl != 0) {
         pt::set_error(std::string("short write to ") + path);
         return PT_ERR_IO;
     }

@@ -1,0 +1,121 @@
+"""pt_ctx_present restated: the contract of include/ptrace.h ("THE ARITHMETIC" of pt_ctx_present) with Python integers for S and
+numpy.float32 / float64 for the conversions.  The table is an argument (pt_present_thresholds gives the library's).  Also the
+ctypes prototypes of the four entry points, which the tests of pt_ctx_present bind for themselves."""
+import ctypes as C
+
+import numpy as np
+
+F32 = np.float32
+RGBA8, RGB8 = 0, 1
+FRAMEBUFFER_ORDER = 1
+ONE_BITS = 0x3F800000
+
+
+class PtPresentParams(C.Structure):
+    _fields_ = [("out_width", C.c_uint32), ("out_height", C.c_uint32), ("exposure", C.c_float), ("format", C.c_uint32),
+                ("flags", C.c_uint32)]
+
+
+def bind(L):
+    L.pt_ctx_present.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(PtPresentParams), C.c_void_p, C.c_void_p,
+                                 C.c_void_p]
+    L.pt_present_thresholds.argtypes = [C.POINTER(C.c_uint32)]
+    L.pt_present_quantize_host.argtypes = [C.c_void_p, C.c_size_t, C.c_float, C.c_void_p]
+    L.pt_write_ppm8.argtypes = [C.c_char_p, C.c_void_p, C.c_uint32, C.c_uint32]
+    L.pt_last_error.restype = C.c_char_p
+    return L
+
+
+def thresholds(L):
+    t = (C.c_uint32 * 256)()
+    assert L.pt_present_thresholds(t) == 0
+    return np.array(t, dtype=np.uint32)
+
+
+def quantize_host(L, values, exposure=0.0):
+    a = np.ascontiguousarray(values, dtype=F32)
+    out = np.zeros(a.shape, dtype=np.uint8)
+    assert L.pt_present_quantize_host(a.ctypes.data_as(C.c_void_p), a.size, exposure, out.ctypes.data_as(C.c_void_p)) == 0
+    return out
+
+
+def bits_to_f32(bits):
+    return np.asarray(bits, dtype=np.uint32).view(F32)
+
+
+# ------------------------------------------------------------------------------------------------------ the arithmetic
+def clamp(v, exposure):
+    """step 2: v' = v * exposure in binary32; c(v') = v' > 0 ? (v' > 1 ? 1 : v') : 0 (NaN and -0 give +0, +inf gives 1)"""
+    with np.errstate(over="ignore", invalid="ignore"):
+        e = np.asarray(v, dtype=F32) * F32(exposure if exposure != 0.0 else 1.0)
+        return np.where(e > 0, np.where(e > 1, F32(1), e), F32(0)).astype(F32)
+
+
+def byte(table, m):
+    """step 5: the number of k in 1..255 with bits(m) >= T[k]"""
+    b = np.ascontiguousarray(m, dtype=F32).view(np.uint32)
+    return (b[..., None] >= np.asarray(table, dtype=np.uint32)[1:]).sum(axis=-1).astype(np.uint8)
+
+
+def weights(n, on):
+    """w[X][x]: the integer overlap of output cell X, [X*n, (X+1)*n), with source pixel x, [x*on, (x+1)*on); on rows, n columns"""
+    w = [[0] * n for _ in range(on)]
+    for X in range(on):
+        lo, hi = X * n, (X + 1) * n
+        for x in range(lo // on, -(-hi // on)):
+            w[X][x] = min(hi, (x + 1) * on) - max(lo, x * on)
+    return w
+
+
+def display(frame, w, h, flags=0):
+    """step 1: D[y][x] of a (w*h, 3) frame"""
+    f = np.asarray(frame, dtype=F32).reshape(w * h, 3)
+    return (f if flags & FRAMEBUFFER_ORDER else f[::-1]).reshape(h, w, 3)
+
+
+def mean(frame, w, h, ow, oh, exposure=0.0, flags=0):
+    """steps 1-4: m per output pixel and channel, (oh, ow, 3) binary32"""
+    c = clamp(display(frame, w, h, flags), exposure)
+    if (ow, oh) == (w, h):
+        return c
+    q = np.floor(c.astype(np.float64) * 4294967296.0).astype(np.uint64)  # exact: c has 24 bits, the factor is a power of two
+    ql = [[[int(v) for v in px] for px in row] for row in q.tolist()]
+    wx, wy = weights(w, ow), weights(h, oh)
+    div = np.float64(w * h) * np.float64(4294967296.0)
+    out = np.zeros((oh, ow, 3), dtype=F32)
+    for Y in range(oh):
+        ys = [(y, wy[Y][y]) for y in range(h) if wy[Y][y]]
+        for X in range(ow):
+            xs = [(x, wx[X][x]) for x in range(w) if wx[X][x]]
+            for ch in range(3):
+                S = sum(a * b * ql[y][x][ch] for y, a in ys for x, b in xs)
+                assert S < 1 << 60
+                out[Y, X, ch] = F32(np.float64(S) / div)  # int -> binary64 rounds to nearest even; one division; one rounding
+    return out
+
+
+def present(table, frame, w, h, ow=0, oh=0, exposure=0.0, fmt=RGBA8, flags=0):
+    """the bytes pt_ctx_present writes: (oh, ow, 4 or 3) uint8"""
+    ow, oh = (ow, oh) if ow or oh else (w, h)
+    b = byte(table, mean(frame, w, h, ow, oh, exposure, flags))
+    if fmt == RGBA8:
+        b = np.concatenate([b, np.full((oh, ow, 1), 255, dtype=np.uint8)], axis=2)
+    return b
+
+
+def read_p3(path):
+    """the numbers of pt_write_ppm's file: (h, w, 3) uint8"""
+    lines = [ln for ln in open(path).read().split("\n") if not ln.startswith("#")]
+    tok = " ".join(lines).split()
+    assert tok[0] == "P3" and tok[3] == "255"
+    w, h = int(tok[1]), int(tok[2])
+    return np.array(tok[4:], dtype=np.int64).astype(np.uint8).reshape(h, w, 3)
+
+
+def read_p6(path):
+    data = open(path, "rb").read()
+    magic, dims, maxval, body = data.split(b"\n", 3)
+    assert magic == b"P6" and maxval == b"255"
+    w, h = (int(v) for v in dims.split())
+    assert len(body) == w * h * 3
+    return np.frombuffer(body, dtype=np.uint8).reshape(h, w, 3)
