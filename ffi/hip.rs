@@ -98,6 +98,17 @@ pub struct PtPresentParams {
     pub flags: u32,
 }
 
+// pt_ctx_reproject's parameters; a zero field = the library's default (pt_reproject_defaults)
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct PtReprojectParams {
+    pub weight: u32,
+    pub max_history: f32,
+    pub depth_tol: f32,
+    pub normal_min: f32,
+    pub flags: u32,
+}
+
 // pt_ctx_denoise's parameters; a zero field = the library's default (pt_denoise_defaults)
 #[repr(C)]
 #[derive(Clone, Copy, Default, Debug)]
@@ -362,6 +373,40 @@ extern "C" {
         d_out: *mut u8,
         hip_stream: *mut c_void,
     ) -> i32;
+    // last frame's colour carried into this frame's pixels through the depth and object-id guides, blended by history length:
+    // what lets the viewport tab (src/views/viewport_tab.rs) keep its samples while the camera orbits
+    pub fn pt_reproject_defaults(out: *mut PtReprojectParams) -> i32;
+    pub fn pt_ctx_reproject(
+        ctx: *mut PtCtx,
+        width: u32,
+        height: u32,
+        params: *const PtReprojectParams,
+        cam: *const PtCamera,
+        d_color: *const f32,
+        d_depth: *const f32,
+        d_object_id: *const i32,
+        d_normal: *const f32,
+        hist_cam: *const PtCamera,
+        d_hist_color: *const f32,
+        d_hist_len: *const f32,
+        d_hist_depth: *const f32,
+        d_hist_object_id: *const i32,
+        d_hist_normal: *const f32,
+        d_out_color: *mut f32,
+        d_out_len: *mut f32,
+        hip_stream: *mut c_void,
+    ) -> i32;
+    pub fn pt_reproject_project_host(
+        cam: *const PtCamera,
+        hist_cam: *const PtCamera,
+        width: u32,
+        height: u32,
+        idx: u32,
+        depth: f32,
+        px: *mut f32,
+        pr: *mut f32,
+        zexp: *mut f32,
+    ) -> i32;
     pub fn pt_write_pfm(path: *const c_char, data: *const f32, width: u32, height: u32, channels: u32) -> i32;
     pub fn pt_device_malloc(device: i32, bytes: usize, out: *mut *mut c_void) -> i32;
     pub fn pt_device_free(device: i32, p: *mut c_void) -> i32;
@@ -427,6 +472,51 @@ pub fn flatten(scene: &SceneData) -> (PtCamera, Vec<PtObject>, Vec<PtTriangle>) 
 
 fn last_error() -> String {
     unsafe { CStr::from_ptr(pt_last_error()) }.to_string_lossy().into_owned()
+}
+
+/// One side of a viewport's temporal history, all in device memory: a colour frame with its history length and the first-hit
+/// guides it was rendered with (pt_ctx_render, pt_ctx_render_aov), and the camera it was seen from.
+pub struct ReprojectFrame {
+    pub cam: PtCamera,
+    pub d_color: *mut f32,
+    pub d_len: *mut f32,
+    pub d_depth: *mut f32,
+    pub d_object_id: *mut i32,
+    pub d_normal: *mut f32,
+}
+
+/// `cur` holds the frame just rendered (colour, guides, camera); its colour and length become the blend with `hist`
+/// (pt_ctx_reproject, in place: d_out_color = d_color), and the two swap roles: on return `hist` is the new history and `cur`
+/// the set of buffers the next frame renders into.  Pointers change hands; nothing is copied.  `have_history`: false for the
+/// first frame after a scene change.  `weight`: the samples per pixel `cur` was rendered with.
+pub fn reproject_and_swap(
+    ctx: *mut PtCtx,
+    frame: (u32, u32),
+    weight: u32,
+    cur: &mut ReprojectFrame,
+    hist: &mut ReprojectFrame,
+    have_history: bool,
+) -> i32 {
+    let pp = PtReprojectParams { weight, ..Default::default() };
+    let null = std::ptr::null::<f32>();
+    let rc = unsafe {
+        if have_history {
+            pt_ctx_reproject(
+                ctx, frame.0, frame.1, &pp, &cur.cam, cur.d_color, cur.d_depth, cur.d_object_id, cur.d_normal, &hist.cam,
+                hist.d_color, hist.d_len, hist.d_depth, hist.d_object_id, hist.d_normal, cur.d_color, cur.d_len,
+                std::ptr::null_mut(),
+            )
+        } else {
+            pt_ctx_reproject(
+                ctx, frame.0, frame.1, &pp, &cur.cam, cur.d_color, cur.d_depth, cur.d_object_id, cur.d_normal,
+                std::ptr::null(), null, null, null, std::ptr::null(), null, cur.d_color, cur.d_len, std::ptr::null_mut(),
+            )
+        }
+    };
+    if rc == PT_OK {
+        std::mem::swap(cur, hist);
+    }
+    rc
 }
 
 /// The window a preview is shown in: its size in pixels and the bytes the canvas draws, width * height * 4 (r, g, b, 255),

@@ -777,6 +777,81 @@ int pt_present_thresholds(uint32_t out[256]);
 int pt_present_quantize_host(const float *in, size_t n, float exposure, uint8_t *out);
 int pt_write_ppm8(const char *path, const uint8_t *rgb8, uint32_t width, uint32_t height); /* binary P6, maxval 255 */
 
+/* ---- reprojecting a preview frame's history across a camera move ---------------------------------------------------
+ * pt_ctx_reproject carries last frame's colour into this frame's pixels through the depth and object-id guides and blends it
+ * with this frame's colour by the history length: the temporal half of SVGF (Schied et al. 2017), whose spatial half the
+ * denoisers are.  A pure image-space call on device buffers, for a viewport whose camera moves between frames of few samples.
+ * - Buffers: device pointers, whole frames of width * height pixels in framebuffer order - d_color, d_normal, d_hist_color,
+ *   d_hist_normal, d_out_color 3 floats per pixel; d_depth, d_hist_depth, d_hist_len, d_out_len 1 float; d_object_id,
+ *   d_hist_object_id 1 int32 - the layouts pt_ctx_render / pt_ctx_render_aov write for a cfg without a band and without chunks.
+ *   d_normal and d_hist_normal may each be NULL: the normal test runs only when both are given.
+ * - History: after a call the host's history is the set (d_out_color, d_out_len, this call's d_depth, d_object_id, d_normal,
+ *   cam).  The host swaps pointers; nothing is copied.  d_out_len is the history length in samples per pixel.
+ * - First frame: d_hist_color, d_hist_len, d_hist_depth and d_hist_object_id are all NULL or none is.  When all are NULL
+ *   hist_cam and d_hist_normal are not read, and the outputs are the colour and (float)weight everywhere.
+ * - Aliasing: d_out_color may be d_color (a pixel reads its own colour before it writes).  No output may alias a history buffer
+ *   or a guide: the kernel gathers neighbours.
+ * - `hip_stream` as for pt_ctx_render (NULL = the context's own stream); blocking.  No scene is needed.  No scratch is taken.
+ *   The call changes no state of the context: not the frame accumulators, not the held frames, not the denoisers' or
+ *   pt_ctx_present's scratch, not the measured pass rates.
+ * - PT_ERR_INVALID, all refused before any device is touched, checked in this order: a max_history or depth_tol that is
+ *   negative or not finite; normal_min outside [-1, 1] or NaN; flags != 0; width or height 0; width * height above 2^28; NULL
+ *   cam, d_color, d_depth, d_object_id, d_out_color or d_out_len; a partial set of history pointers; a full set of history
+ *   pointers with NULL hist_cam; NULL ctx.  PT_ERR_HIP: a HIP call failed.  params == NULL stands for all zero.
+ * - pt_reproject_defaults fills in the values a zero field stands for: weight 1, max_history 64, depth_tol 2^-3 (0.125),
+ *   normal_min 0.9, flags 0.  They were chosen by the CPU study recorded in profiles/reproject_cpu_study.json.
+ *
+ * THE ARITHMETIC.  Every operation is IEEE binary32 + - * / and sqrt, correctly rounded, never contracted, in the order the
+ * parentheses give - pt_ctx_denoise's rules.  dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z; max(a, b) = a > b ? a : b; |v| is v
+ * with its sign bit cleared; N(.) is pt_ctx_denoise's normalised normal, word for word.  (L, su, sv) and (L', su', sv') are
+ * pt_camera_basis of cam and hist_cam, computed on the host in binary32; C is cam's position; C', D', f' are hist_cam's
+ * position, direction (as stored) and focal length; W, H = width, height; wt = (float)weight (weight 0 stands for 1).
+ * For pixel idx: x = idx % W, r = idx / W, y = H-1-r (render_pixel's row, mod.rs:805-806).
+ * 1. No history.  If there is no history, or object_id[idx] < 0, or step 3 rejects, or step 4 ends with bsum > 0 false (every
+ *    tap skipped, or taken with b = 0): out[c] = color[idx][c], len_out = wt.
+ * 2. Same camera: all nine floats of cam and hist_cam are bitwise equal.  One tap, q = idx, with b = 1 and zexp = depth[idx];
+ *    go to step 4.  A still camera is then an exact running mean.
+ * 3. Projection.  sx = ((float)x + 0.5) / (float)W - 0.5; sy = ((float)y + 0.5) / (float)H - 0.5.
+ *    S = (C + su*sx) + sv*sy per component; g = L - S; P = L + (g * (1 / sqrt(dot(g, g)))) * depth[idx]: the point the pixel
+ *    centre's ray reaches at that distance, the direction made as render_pixel makes it.  The depth is sample 0's distance
+ *    along a JITTERED ray while P uses the pixel centre: a sub-pixel error, which depth_tol and the bilinear taps are there for.
+ *    v = P - L'; a = dot(v, D'); reject unless a > 0.  t = a / (f' * dot(D', D')); w = D'*f' - v / t per component (the sensor
+ *    point minus C').  sx' = dot(w, su') / dot(su', su'); sy' = dot(w, sv') / dot(sv', sv').
+ *    px = (sx' + 0.5) * (float)W - 0.5; py = (sy' + 0.5) * (float)H - 0.5; pr = (float)(H-1) - py.
+ *    Reject unless px > -1 && px < W && pr > -1 && pr < H (a NaN rejects).
+ *    x0 = floor(px), fx = px - (float)x0; r0 = floor(pr), fr = pr - (float)r0.  zexp = sqrt(dot(v, v)).
+ *    The taps are q = (x0+i, r0+j), j = 0, 1 in the outer loop and i = 0, 1 in the inner loop, with
+ *    b = (i ? fx : 1 - fx) * (j ? fr : 1 - fr).
+ * 4. Tap test.  sum = (0, 0, 0), nsum = 0, bsum = 0.  A tap is skipped when q is outside the frame; when hist_len[q] > 0 does
+ *    not hold; when hist_object_id[q] != object_id[idx]; when |zexp - hist_depth[q]| <= depth_tol * max(zexp, hist_depth[q])
+ *    does not hold; when both normals are given and dot(N(idx), N'(q)) >= normal_min does not hold.  A tap that is taken adds
+ *    sum[c] = sum[c] + hist_color[q][c] * b; nsum = nsum + hist_len[q] * b; bsum = bsum + b.
+ * 5. Blend, if bsum > 0: h[c] = sum[c] / bsum; n = nsum / bsum; n' = n + wt; if n' > max_history, n' = max_history; if n' < wt,
+ *    n' = wt; out[c] = h[c] + (color[idx][c] - h[c]) * (wt / n'); len_out = n'.
+ * pt_reproject_project_host is the host instantiation of the projection the kernel compiles (csrc/pt_reproject.h): step 3 for
+ * pixel idx at `depth`, from pt_camera_basis to zexp.  PT_OK and the three values; 1 for "no position" (step 3 rejected the
+ * point; nothing is written); PT_ERR_INVALID for a NULL pointer, an empty frame, one above 2^28 pixels, or idx outside it.  It
+ * needs no device. */
+typedef struct pt_reproject_params {
+    uint32_t weight;      /* samples per pixel the current frame holds; 0 = 1 */
+    float max_history;    /* cap of the history length, in samples; 0 = the default; finite, >= 0 */
+    float depth_tol;      /* relative depth tolerance; 0 = the default; finite, >= 0 */
+    float normal_min;     /* smallest cosine between the two normals; 0 = the default; in [-1, 1] */
+    uint32_t flags;       /* none defined: must be 0 */
+} pt_reproject_params;
+int pt_reproject_defaults(pt_reproject_params *out);
+int pt_ctx_reproject(pt_ctx *ctx, uint32_t width, uint32_t height, const pt_reproject_params *params,
+                     const pt_camera *cam, const float *d_color, const float *d_depth,
+                     const int32_t *d_object_id, const float *d_normal /* may be NULL */,
+                     const pt_camera *hist_cam, const float *d_hist_color, const float *d_hist_len,
+                     const float *d_hist_depth, const int32_t *d_hist_object_id,
+                     const float *d_hist_normal /* may be NULL */,
+                     float *d_out_color, float *d_out_len, void *hip_stream);
+/* host only, no device: the host instantiation of the projection the kernel compiles */
+int pt_reproject_project_host(const pt_camera *cam, const pt_camera *hist_cam, uint32_t width,
+                              uint32_t height, uint32_t idx, float depth,
+                              float *px, float *pr, float *zexp);
+
 /* ---- the one collective of the path: the framebuffer gather over RCCL (xGMI) ---------------------------------
  * One process (or thread) per GPU renders its rows with pt_ctx_render (chunk_first = rank, chunk_step = n_ranks) into
  * device memory; pt_comm_gather_frame then gives EVERY rank the whole frame in device memory: one in-place

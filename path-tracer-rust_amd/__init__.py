@@ -62,6 +62,11 @@ class pt_present_params(C.Structure):
                 ("flags", C.c_uint32)]
 
 
+class pt_reproject_params(C.Structure):
+    _fields_ = [("weight", C.c_uint32), ("max_history", C.c_float), ("depth_tol", C.c_float), ("normal_min", C.c_float),
+                ("flags", C.c_uint32)]
+
+
 class pt_noise_stats(C.Structure):
     _fields_ = [("spp_min", C.c_uint32), ("spp_max", C.c_uint32), ("spp_a_min", C.c_uint32), ("spp_b_min", C.c_uint32),
                 ("pixels", C.c_uint64), ("mean_error", C.c_double), ("histogram", C.c_uint32 * 64)]
@@ -149,6 +154,11 @@ def lib():
     L.pt_present_thresholds.argtypes = [C.POINTER(C.c_uint32)]
     L.pt_present_quantize_host.argtypes = [C.POINTER(C.c_float), C.c_size_t, C.c_float, C.POINTER(C.c_uint8)]
     L.pt_write_ppm8.argtypes = [C.c_char_p, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32]
+    L.pt_reproject_defaults.argtypes = [C.POINTER(pt_reproject_params)]
+    L.pt_ctx_reproject.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(pt_reproject_params), C.POINTER(pt_camera)] + \
+        [C.c_void_p] * 4 + [C.POINTER(pt_camera)] + [C.c_void_p] * 8
+    L.pt_reproject_project_host.argtypes = [C.POINTER(pt_camera), C.POINTER(pt_camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_float] + \
+        [C.POINTER(C.c_float)] * 3
     L.pt_write_pfm.argtypes = [C.c_char_p, C.POINTER(C.c_float), C.c_uint32, C.c_uint32, C.c_uint32]
     L.pt_ctx_set_profiling.argtypes = [C.c_void_p, C.c_int]
     L.pt_ctx_pass_kernel.argtypes = [C.c_void_p, C.c_uint32]
@@ -315,6 +325,23 @@ class Context:
                               PT_PRESENT_FRAMEBUFFER_ORDER if framebuffer_order else 0)
         ptr = lambda q: C.c_void_p(q) if q else None  # noqa: E731
         _check(lib().pt_ctx_present(self._h, width, height, C.byref(p), ptr(rgb), ptr(out), C.c_void_p(stream or 0)))
+
+    def reproject(self, width, height, cam, color, depth, object_id, out_color, out_len, normal=None, history=None, weight=1,
+                  max_history=0.0, depth_tol=0.0, normal_min=0.0, stream=None):
+        """Carry a preview frame's history across a camera move and blend it with this frame (pt_ctx_reproject).  Device pointers
+        to whole width x height frames: color, normal, out_color pixels * 3 float32; depth, out_len pixels float32; object_id
+        pixels int32 - what render() and render_aov() write.  `cam`: this frame's camera (a pt_camera, a pointer to one, or a dict
+        of its fields).  `history`: None for the first frame, else a dict with "cam", "color", "len", "depth", "object_id" and
+        optionally "normal" - after the call the next frame's history is dict(cam=cam, color=out_color, len=out_len, depth=depth,
+        object_id=object_id, normal=normal): pointers are swapped, nothing is copied.  weight: the samples per pixel `color`
+        holds; max_history, depth_tol, normal_min: 0 = reproject_defaults().  out_color may be color."""
+        p = pt_reproject_params(weight, max_history, depth_tol, normal_min, 0)
+        ptr = lambda q: C.c_void_p(q) if q else None  # noqa: E731
+        h = history or {}
+        _check(lib().pt_ctx_reproject(self._h, width, height, C.byref(p), _camera(cam), ptr(color), ptr(depth), ptr(object_id),
+                                      ptr(normal), _camera(h["cam"]) if history else None, ptr(h.get("color")), ptr(h.get("len")),
+                                      ptr(h.get("depth")), ptr(h.get("object_id")), ptr(h.get("normal")), ptr(out_color),
+                                      ptr(out_len), C.c_void_p(stream or 0)))
 
     def accum_track_noise(self, on=True):
         """Keep half of every pixel's samples in a second accumulator for the frames started from now on
@@ -499,6 +526,34 @@ def present_quantize_host(values, exposure=0.0):
     _check(lib().pt_present_quantize_host(a.ctypes.data_as(C.POINTER(C.c_float)), a.size, exposure,
                                           out.ctypes.data_as(C.POINTER(C.c_uint8))))
     return out
+
+
+def _camera(cam):
+    """a pt_camera, a pointer to one, or a dict of its fields, as an argument for POINTER(pt_camera)"""
+    if isinstance(cam, dict):
+        return C.pointer(pt_camera(f3(*cam["position"]), f3(*cam["direction"]), cam["focal_length"], cam["sensor_width"],
+                                   cam["aspect_ratio"]))
+    return C.pointer(cam) if isinstance(cam, pt_camera) else cam
+
+
+def reproject_defaults():
+    """The values pt_ctx_reproject uses for a zero field: {"weight", "max_history", "depth_tol", "normal_min"}
+    (pt_reproject_defaults)."""
+    p = pt_reproject_params()
+    _check(lib().pt_reproject_defaults(C.byref(p)))
+    return {"weight": p.weight, "max_history": p.max_history, "depth_tol": p.depth_tol, "normal_min": p.normal_min}
+
+
+def reproject_project_host(cam, hist_cam, width, height, idx, depth):
+    """Where the point pixel `idx` of `cam` sees at `depth` lies in hist_cam's frame (pt_reproject_project_host, the host
+    instantiation of the kernel's projection): (px, pr, zexp) - column, row and expected history depth - or None when the point
+    has no position there (behind the lens, outside the frame)."""
+    out = [C.c_float() for _ in range(3)]
+    rc = lib().pt_reproject_project_host(_camera(cam), _camera(hist_cam), width, height, idx, depth, *[C.byref(o) for o in out])
+    if rc == 1:
+        return None
+    _check(rc)
+    return tuple(o.value for o in out)
 
 
 def denoise_defaults():

@@ -18,6 +18,7 @@
 #include "pt_kernels.h"
 #include "pt_noise.h"
 #include "pt_present.h"
+#include "pt_reproject.h"
 #include "pt_tile.h"
 
 namespace pt {
@@ -2731,6 +2732,33 @@ int pt_ctx_present(pt_ctx *c, uint32_t width, uint32_t height, const pt_present_
         f.mid = c->pr_mid.p;
     }
     launch_present(st, f);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    return PT_OK;
+}
+
+int pt_reproject_defaults(pt_reproject_params *out) {
+    if (!out) {
+        set_error("out is NULL");
+        return PT_ERR_INVALID;
+    }
+    *out = pt_reproject_params{1u, kReprojectMaxHistory, kReprojectDepthTol, kReprojectNormalMin, 0u};
+    return PT_OK;
+}
+
+int pt_ctx_reproject(pt_ctx *c, uint32_t width, uint32_t height, const pt_reproject_params *params, const pt_camera *cam,
+                     const float *d_color, const float *d_depth, const int32_t *d_object_id, const float *d_normal,
+                     const pt_camera *hist_cam, const float *d_hist_color, const float *d_hist_len, const float *d_hist_depth,
+                     const int32_t *d_hist_object_id, const float *d_hist_normal, float *d_out_color, float *d_out_len,
+                     void *hip_stream) {
+    // everything that can be refused is refused here, before the device is touched
+    ReprojectFrame f;
+    const int rc = host::check_reproject(c, width, height, params, cam, d_color, d_depth, d_object_id, d_normal, hist_cam, d_hist_color,
+                                         d_hist_len, d_hist_depth, d_hist_object_id, d_hist_normal, d_out_color, d_out_len, f);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    launch_reproject(st, f);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
     return PT_OK;

@@ -2,6 +2,7 @@
 // values produced here must be the f32 values the reference computes (per frame for the camera, per ray
 // for the triangle edges — see pt_device.h).
 #include "pt_host.h"
+#include "pt_reproject.h"
 
 #include <algorithm>
 #include <cmath>
@@ -1263,6 +1264,71 @@ int adckpt_decode(uint64_t file_size, const uint8_t *b, size_t n, AdaptiveCheckp
     out.sums_at = kAdCkptHead + 16 * (size_t)tiles;
     out.a_at = out.sums_at + 24 * (size_t)total;
     return kCkptOk;
+}
+
+
+// ---- pt_ctx_reproject (ptrace.h, pt_reproject.h)
+void reproject_view(const pt_camera &cam, const pt_camera *hist_cam, ReprojectView &out) {
+    out = ReprojectView{};
+    float lens[3], su[3], sv[3];
+    camera_basis(cam, lens, su, sv);
+    out.C = ld(cam.position);
+    out.L = ld(lens);
+    out.su = ld(su);
+    out.sv = ld(sv);
+    if (!hist_cam) return;
+    camera_basis(*hist_cam, lens, su, sv);
+    out.hL = ld(lens);
+    out.hD = ld(hist_cam->direction);
+    out.hDf = out.hD * hist_cam->focal_length;
+    out.hsu = ld(su);
+    out.hsv = ld(sv);
+    out.hfdd = hist_cam->focal_length * dot(out.hD, out.hD);
+    out.hsuu = dot(out.hsu, out.hsu);
+    out.hsvv = dot(out.hsv, out.hsv);
+    out.same = memcmp(&cam, hist_cam, sizeof(pt_camera)) == 0 ? 1u : 0u;  // nine floats, no padding
+}
+
+int check_reproject(const void *ctx, uint32_t width, uint32_t height, const pt_reproject_params *params, const pt_camera *cam,
+                    const float *d_color, const float *d_depth, const int32_t *d_object_id, const float *d_normal,
+                    const pt_camera *hist_cam, const float *d_hist_color, const float *d_hist_len, const float *d_hist_depth,
+                    const int32_t *d_hist_object_id, const float *d_hist_normal, float *d_out_color, float *d_out_len,
+                    ReprojectFrame &f) {
+    pt_reproject_params P{};
+    if (params) P = *params;
+    if (!finite_nonneg(P.max_history) || !finite_nonneg(P.depth_tol))
+        return refuse("pt_reproject_params: max_history or depth_tol is negative or not finite");
+    if (!(P.normal_min >= -1.0f && P.normal_min <= 1.0f)) return refuse("pt_reproject_params.normal_min is outside [-1, 1]");
+    if (P.flags) return refuse("pt_reproject_params.flags: none is defined");
+    if (!width || !height) return refuse("width and height must be positive");
+    if ((uint64_t)width * height > (1ull << 28)) return refuse("width*height exceeds 2^28");
+    if (!cam || !d_color || !d_depth || !d_object_id || !d_out_color || !d_out_len)
+        return refuse("cam, d_color, d_depth, d_object_id, d_out_color or d_out_len is NULL");
+    const int n_hist = (d_hist_color != nullptr) + (d_hist_len != nullptr) + (d_hist_depth != nullptr) + (d_hist_object_id != nullptr);
+    if (n_hist != 0 && n_hist != 4)
+        return refuse("history: d_hist_color, d_hist_len, d_hist_depth and d_hist_object_id are all NULL or none is");
+    if (n_hist && !hist_cam) return refuse("hist_cam is NULL with a history");
+    if (!ctx) return refuse("ctx is NULL");
+    f = ReprojectFrame{};
+    f.width = width;
+    f.height = height;
+    f.color = d_color;
+    f.depth = d_depth;
+    f.normal = d_normal;
+    f.object_id = d_object_id;
+    f.hist_color = d_hist_color;
+    f.hist_len = d_hist_len;
+    f.hist_depth = d_hist_depth;
+    f.hist_normal = n_hist ? d_hist_normal : nullptr;
+    f.hist_object_id = d_hist_object_id;
+    f.out_color = d_out_color;
+    f.out_len = d_out_len;
+    f.wt = (float)(P.weight ? P.weight : 1u);
+    f.max_history = P.max_history != 0.0f ? P.max_history : kReprojectMaxHistory;
+    f.depth_tol = P.depth_tol != 0.0f ? P.depth_tol : kReprojectDepthTol;
+    f.normal_min = P.normal_min != 0.0f ? P.normal_min : kReprojectNormalMin;
+    reproject_view(*cam, n_hist ? hist_cam : nullptr, f.view);
+    return PT_OK;
 }
 
 }  // namespace host

@@ -1,0 +1,219 @@
+// pt_reproject.h — pt_ctx_reproject (pt_reproject.hip): last frame's colour carried into this frame's pixels through the depth
+// and object-id guides, and blended with this frame's colour by the history length (the temporal half of SVGF, Schied et al.
+// 2017).  The arithmetic is the contract in include/ptrace.h ("THE ARITHMETIC" of pt_ctx_reproject), operation for operation.
+// Steps 3 to 5 - and the pixel that strings them together - are stated once, below, for host and device:
+// pt_reproject_project_host (host/scene_io.cpp) is the host instantiation of the projection the kernel compiles, as
+// pt_present_quantize_host is of pt_present.h.  A translation unit of its own: pt_kernels.s, and so pt_kernel_isa_hash(),
+// describes the pass kernels only.
+#pragma once
+
+#include "../../include/ptrace.h"
+#include "pt_math.h"
+
+namespace pt {
+
+// the values a zero field of pt_reproject_params stands for: what the CPU study picked (profiles/reproject_cpu_study.json)
+constexpr float kReprojectMaxHistory = 64.0f, kReprojectDepthTol = 0.125f, kReprojectNormalMin = 0.9f;
+
+// What step 3 needs of the two cameras, computed on the host in binary32 (host::reproject_view, pt_host.cpp): pt_camera_basis of
+// both, and the history camera's constants - each the one binary32 operation sequence the contract names, so a pixel that
+// computed them itself would hold the same bits.
+struct ReprojectView {
+    vec3 C, L, su, sv;           // cam: position, lens centre, sensor axes
+    vec3 hL, hD, hDf, hsu, hsv;  // hist_cam: lens centre L', direction D' as stored, D' * f', sensor axes
+    float hfdd, hsuu, hsvv;      // f' * dot(D', D'), dot(su', su'), dot(sv', sv')
+    uint32_t same;               // step 2: all nine floats of the two cameras are bitwise equal
+};
+
+// The call's whole frames.  Host pointers on the host, device pointers on the device.
+struct ReprojectFrame {
+    uint32_t width, height;
+    const float *color, *depth, *normal;  // normal may be NULL
+    const int32_t *object_id;
+    const float *hist_color, *hist_len, *hist_depth, *hist_normal;  // hist_color NULL: no history; hist_normal may be NULL
+    const int32_t *hist_object_id;
+    float *out_color, *out_len;
+    float wt, max_history, depth_tol, normal_min;  // defaults filled in; wt = (float)weight
+    ReprojectView view;
+};
+
+struct ReprojectPos {
+    float px, pr, zexp;
+};
+
+// step 3 up to the reject test: where the point pixel idx sees at `depth` lies in the history frame.  false: no position.
+PT_HD bool reproject_project(const ReprojectView &V, uint32_t W, uint32_t H, uint32_t idx, float depth, ReprojectPos &o) {
+    const uint32_t x = idx % W, r = idx / W, y = H - 1u - r;
+    const float fw = (float)W, fh = (float)H;
+    const float sx = ((float)x + 0.5f) / fw - 0.5f;
+    const float sy = ((float)y + 0.5f) / fh - 0.5f;
+    const vec3 S = (V.C + V.su * sx) + V.sv * sy;
+    const vec3 g = V.L - S;
+    const vec3 P = V.L + (g * (1.0f / __builtin_sqrtf(dot(g, g)))) * depth;
+    const vec3 v = P - V.hL;
+    const float a = dot(v, V.hD);
+    if (!(a > 0.0f)) return false;
+    const float t = a / V.hfdd;
+    const vec3 w = V.hDf - v / t;
+    const float sxh = dot(w, V.hsu) / V.hsuu;
+    const float syh = dot(w, V.hsv) / V.hsvv;
+    o.px = (sxh + 0.5f) * fw - 0.5f;
+    const float py = (syh + 0.5f) * fh - 0.5f;
+    o.pr = (float)(H - 1u) - py;
+    if (!(o.px > -1.0f && o.px < fw && o.pr > -1.0f && o.pr < fh)) return false;  // a NaN rejects
+    o.zexp = __builtin_sqrtf(dot(v, v));
+    return true;
+}
+
+// N(.): pt_ctx_denoise's normalised normal
+PT_HD vec3 reproject_normal(const float *n) {
+    const float nx = n[0], ny = n[1], nz = n[2];
+    const float l = __builtin_sqrtf((nx * nx + ny * ny) + nz * nz);
+    return l > 0.0f ? mk(nx / l, ny / l, nz / l) : mk(0.0f, 0.0f, 0.0f);
+}
+
+// step 4 without the normals: is history pixel q (length, id, depth) the surface pixel idx sees?
+PT_HD bool reproject_tap_ok(float hist_len, int32_t hist_id, int32_t id, float zexp, float hist_depth, float depth_tol) {
+    if (!(hist_len > 0.0f) || hist_id != id) return false;
+    const float zm = zexp > hist_depth ? zexp : hist_depth;
+    return __builtin_fabsf(zexp - hist_depth) <= depth_tol * zm;
+}
+
+// One tap of step 4: history pixel q (clamped into the frame, so that it can be read before anything is known about it), its
+// bilinear weight b, and whether the tap lies inside the frame at all.
+struct ReprojectTap {
+    uint32_t q;
+    float b;
+    bool inside;
+};
+
+// Steps 4 and 5 over NT taps (1: the same camera; 4: the bilinear footprint, in the contract's order).  Written for the
+// memory system: everything the taps may need - guides, normals, colours - is read before the first tap is tested, so a lane has
+// all of its history reads in flight at once instead of up to three dependent round trips per tap, one tap after the other.  A
+// tap that fails its test has been read for nothing - its neighbours want the same lines - and adds nothing: the sums are the
+// contract's, in its order.  false: bsum > 0 does not hold (step 1).
+template <int NT>
+PT_HD bool reproject_gather(const ReprojectFrame &f, const ReprojectTap (&tap)[NT], float zexp, int32_t id, bool normals, vec3 N,
+                            const float col[3], float out[3], float *len_out) {
+    float hlen[NT], hdepth[NT];
+    int32_t hid[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        hlen[t] = f.hist_len[tap[t].q];
+        hid[t] = f.hist_object_id[tap[t].q];
+        hdepth[t] = f.hist_depth[tap[t].q];
+    }
+    float hc[NT][3], hn[NT][3];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        const size_t q3 = (size_t)tap[t].q * 3u;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            hc[t][c] = f.hist_color[q3 + c];
+            hn[t][c] = normals ? f.hist_normal[q3 + c] : 0.0f;
+        }
+    }
+    float s[3] = {0.0f, 0.0f, 0.0f}, nsum = 0.0f, bsum = 0.0f;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        bool take = tap[t].inside && reproject_tap_ok(hlen[t], hid[t], id, zexp, hdepth[t], f.depth_tol);
+        if (normals) take = take && dot(N, reproject_normal(hn[t])) >= f.normal_min;
+        const float b = tap[t].b;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) s[c] = take ? s[c] + hc[t][c] * b : s[c];
+        nsum = take ? nsum + hlen[t] * b : nsum;
+        bsum = take ? bsum + b : bsum;
+    }
+    if (!(bsum > 0.0f)) return false;
+    float n = nsum / bsum + f.wt;
+    if (n > f.max_history) n = f.max_history;
+    if (n < f.wt) n = f.wt;
+    const float k = f.wt / n;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float h = s[c] / bsum;
+        out[c] = h + (col[c] - h) * k;
+    }
+    *len_out = n;
+    return true;
+}
+
+// a value of the pixel's own planes: read once by one lane, so the device keeps it out of the L1 the taps live in
+PT_HD float reproject_own(const float *p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_nontemporal_load(p);
+#else
+    return *p;
+#endif
+}
+PT_HD int32_t reproject_own(const int32_t *p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_nontemporal_load(p);
+#else
+    return *p;
+#endif
+}
+
+// steps 1 to 5 for pixel idx (< width * height): the colour and the length it ends with.  The pixel's own colour is read before
+// anything is returned, so the caller may store into color[idx].
+PT_HD void reproject_pixel(const ReprojectFrame &f, uint32_t idx, float out[3], float *len_out) {
+    const size_t i3 = (size_t)idx * 3u;
+    float col[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) out[c] = col[c] = reproject_own(f.color + i3 + c);
+    *len_out = f.wt;
+    if (!f.hist_color) return;
+    const int32_t id = reproject_own(f.object_id + idx);
+    if (id < 0) return;
+    const float depth = reproject_own(f.depth + idx);
+    const bool normals = f.normal && f.hist_normal;
+    vec3 N = mk(0.0f, 0.0f, 0.0f);
+    if (normals) {
+        const float n[3] = {reproject_own(f.normal + i3), reproject_own(f.normal + i3 + 1), reproject_own(f.normal + i3 + 2)};
+        N = reproject_normal(n);
+    }
+    if (f.view.same) {
+        const ReprojectTap tap[1] = {{idx, 1.0f, true}};
+        reproject_gather<1>(f, tap, depth, id, normals, N, col, out, len_out);
+        return;
+    }
+    ReprojectPos p;
+    if (!reproject_project(f.view, f.width, f.height, idx, depth, p)) return;
+    const float flx = __builtin_floorf(p.px), flr = __builtin_floorf(p.pr);
+    const int32_t x0 = (int32_t)flx, r0 = (int32_t)flr;  // in [-1, width - 1] and [-1, height - 1]
+    const float fx = p.px - flx, fr = p.pr - flr;
+    const int32_t xmax = (int32_t)f.width - 1, rmax = (int32_t)f.height - 1;
+    ReprojectTap tap[4];
+#pragma unroll
+    for (int32_t j = 0; j < 2; ++j) {
+#pragma unroll
+        for (int32_t i = 0; i < 2; ++i) {
+            const int32_t qx = x0 + i, qr = r0 + j;
+            ReprojectTap &t = tap[j * 2 + i];
+            t.inside = qx >= 0 && qr >= 0 && qx <= xmax && qr <= rmax;
+            const int32_t cx = qx < 0 ? 0 : (qx > xmax ? xmax : qx), cr = qr < 0 ? 0 : (qr > rmax ? rmax : qr);
+            t.q = (uint32_t)cr * f.width + (uint32_t)cx;
+            t.b = (i ? fx : 1.0f - fx) * (j ? fr : 1.0f - fr);
+        }
+    }
+    reproject_gather<4>(f, tap, p.zexp, id, normals, N, col, out, len_out);
+}
+
+namespace host {
+// the view of a camera pair; hist_cam NULL: the first frame, nothing of the history is set
+void reproject_view(const pt_camera &cam, const pt_camera *hist_cam, ReprojectView &out);
+// pt_ctx_reproject's refusals in the header's order (PT_ERR_INVALID + message); PT_OK: `f` holds the call with the defaults
+// filled in.  No device is touched.
+int check_reproject(const void *ctx, uint32_t width, uint32_t height, const pt_reproject_params *params, const pt_camera *cam,
+                    const float *d_color, const float *d_depth, const int32_t *d_object_id, const float *d_normal,
+                    const pt_camera *hist_cam, const float *d_hist_color, const float *d_hist_len, const float *d_hist_depth,
+                    const int32_t *d_hist_object_id, const float *d_hist_normal, float *d_out_color, float *d_out_len,
+                    ReprojectFrame &f);
+}  // namespace host
+
+#if defined(__HIPCC__)
+// one lane per pixel
+void launch_reproject(hipStream_t st, const ReprojectFrame &f);
+#endif
+
+}  // namespace pt

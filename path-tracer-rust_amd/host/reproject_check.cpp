@@ -1,0 +1,209 @@
+// reproject_check — pt_ctx_reproject's host side under a sanitizer, as a program of its own (make reproject-check builds it with
+// -fsanitize=address,undefined and runs it; no device, no Python).  It drives pt_reproject_project_host and the refusals over
+// edge inputs, and runs the pixel the kernel compiles (csrc/pt_reproject.h: reproject_pixel) over host frames allocated to their
+// exact size, so that the sanitizer bounds every tap of the gather: a failed check or a sanitizer report ends it with a non-zero
+// status.
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/ptrace.h"
+#include "../csrc/pt_reproject.h"
+
+namespace pt {
+static std::string g_error;
+void set_error(const std::string &m) { g_error = m; }
+}  // namespace pt
+extern "C" const char *pt_last_error(void) { return pt::g_error.c_str(); }
+
+#define CHECK(cond)                                                      \
+    do {                                                                 \
+        if (!(cond)) {                                                   \
+            fprintf(stderr, "%s:%d: %s failed\n", __FILE__, __LINE__, #cond); \
+            return 1;                                                    \
+        }                                                                \
+    } while (0)
+
+static pt_camera camera(float px, float py, float pz, float dx, float dy, float dz) {
+    const float l = sqrtf(dx * dx + dy * dy + dz * dz);
+    pt_camera c = {{px, py, pz}, {dx, dy, dz}, 0.035f, 0.036f, 1.5f};
+    if (l > 0.0f)
+        for (float &v : c.direction) v /= l;
+    return c;
+}
+
+static uint32_t lcg(uint32_t &s) { return s = s * 1664525u + 1013904223u; }
+static float unit(uint32_t &s) { return (float)(lcg(s) >> 8) * (1.0f / 16777216.0f); }
+
+struct Frames {
+    std::vector<float> color, depth, normal, hcolor, hlen, hdepth, hnormal, out, len;
+    std::vector<int32_t> id, hid;
+};
+
+// random frames in the style of the GPU test: depths on a few planes and +inf, ids -1..2, normals with zero vectors, lengths
+// with zeros
+static Frames make_frames(uint32_t n, uint32_t seed) {
+    Frames f;
+    uint32_t s = seed;
+    const float planes[] = {2.0f, 6.0f, 6.25f, 9.0f, INFINITY};
+    auto fill = [&](std::vector<float> &v, size_t k) {
+        v.resize(k);
+        for (float &x : v) x = unit(s);
+    };
+    fill(f.color, 3 * (size_t)n);
+    fill(f.hcolor, 3 * (size_t)n);
+    fill(f.normal, 3 * (size_t)n);
+    fill(f.hnormal, 3 * (size_t)n);
+    for (size_t i = 0; i < 3 * (size_t)n; ++i) {
+        f.normal[i] -= 0.5f;
+        f.hnormal[i] = lcg(s) % 8u ? f.normal[i] : 0.0f;
+    }
+    f.depth.resize(n), f.hdepth.resize(n), f.hlen.resize(n), f.id.resize(n), f.hid.resize(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        f.depth[i] = planes[lcg(s) % 5u];
+        f.hdepth[i] = lcg(s) % 4u ? f.depth[i] : planes[lcg(s) % 5u];
+        f.id[i] = (int32_t)(lcg(s) % 4u) - 1;
+        f.hid[i] = lcg(s) % 4u ? f.id[i] : (int32_t)(lcg(s) % 4u) - 1;
+        f.hlen[i] = (float)(lcg(s) % 5u) * 4.0f;
+    }
+    f.out.assign(3 * (size_t)n, -1.0f);
+    f.len.assign(n, -1.0f);
+    return f;
+}
+
+int main() {
+    const pt_camera cam = camera(0.0f, -0.2f, 7.8f, 0.0f, -0.06f, -1.0f);
+    const pt_camera near_cam = camera(0.3f, -0.2f, 7.7f, -0.04f, -0.06f, -1.0f);
+    const pt_camera back = camera(0.0f, -0.2f, 7.8f, 0.0f, 0.06f, 1.0f);
+    const pt_camera aside = camera(4.0f, -0.2f, 3.0f, -1.0f, -0.06f, -0.2f);  // part of the frame behind its lens, part outside
+    const pt_camera down = camera(0.5f, 6.0f, -0.25f, 0.0f, -1.0f, 0.0f);
+    const pt_camera zero = camera(0.0f, -0.2f, 7.8f, 0.0f, 0.0f, 0.0f);
+    float px = -7.0f, pr = -7.0f, z = -7.0f;
+
+    // ---- pt_reproject_project_host
+    CHECK(pt_reproject_project_host(nullptr, &cam, 4, 4, 0, 1.0f, &px, &pr, &z) == PT_ERR_INVALID);
+    CHECK(pt_reproject_project_host(&cam, nullptr, 4, 4, 0, 1.0f, &px, &pr, &z) == PT_ERR_INVALID);
+    CHECK(pt_reproject_project_host(&cam, &cam, 4, 4, 0, 1.0f, nullptr, &pr, &z) == PT_ERR_INVALID);
+    CHECK(pt_reproject_project_host(&cam, &cam, 4, 4, 0, 1.0f, &px, nullptr, &z) == PT_ERR_INVALID);
+    CHECK(pt_reproject_project_host(&cam, &cam, 4, 4, 0, 1.0f, &px, &pr, nullptr) == PT_ERR_INVALID);
+    CHECK(pt_reproject_project_host(&cam, &cam, 0, 4, 0, 1.0f, &px, &pr, &z) == PT_ERR_INVALID);
+    CHECK(pt_reproject_project_host(&cam, &cam, 4, 0, 0, 1.0f, &px, &pr, &z) == PT_ERR_INVALID);
+    CHECK(pt_reproject_project_host(&cam, &cam, 4, 4, 16, 1.0f, &px, &pr, &z) == PT_ERR_INVALID);
+    CHECK(pt_reproject_project_host(&cam, &cam, 1u << 15, 1u << 15, 0, 1.0f, &px, &pr, &z) == PT_ERR_INVALID);
+    CHECK(px == -7.0f && pr == -7.0f && z == -7.0f);
+    const uint32_t sizes[][2] = {{1, 1}, {7, 5}, {450, 300}, {1024, 768}, {1u << 14, 1u << 14}};
+    for (const auto &s : sizes) {
+        const uint32_t w = s[0], h = s[1], last = w * h - 1u;
+        for (uint32_t idx : {0u, w - 1u, last - (w - 1u), last, (h / 2u) * w + w / 2u}) {
+            // a point behind the history lens, a zero direction on either side, depths that are not distances
+            CHECK(pt_reproject_project_host(&cam, &back, w, h, idx, 4.0f, &px, &pr, &z) == 1);
+            CHECK(pt_reproject_project_host(&cam, &zero, w, h, idx, 4.0f, &px, &pr, &z) == 1);
+            CHECK(pt_reproject_project_host(&zero, &cam, w, h, idx, 4.0f, &px, &pr, &z) == 1);
+            CHECK(pt_reproject_project_host(&cam, &near_cam, w, h, idx, NAN, &px, &pr, &z) == 1);
+            CHECK(pt_reproject_project_host(&cam, &near_cam, w, h, idx, INFINITY, &px, &pr, &z) == 1);
+            CHECK(pt_reproject_project_host(&cam, &near_cam, w, h, idx, -INFINITY, &px, &pr, &z) == 1);
+            CHECK(px == -7.0f && pr == -7.0f && z == -7.0f);  // "no position" writes nothing
+            for (float depth : {0.125f, 1.0f, 8.0f, 64.0f, 0.0f, -1.0f, 1e-30f, 3e38f}) {
+                for (const pt_camera *hc : {&cam, &near_cam, &aside, &down}) {
+                    float x = -7.0f, r = -7.0f, d = -7.0f;
+                    const int rc = pt_reproject_project_host(&cam, hc, w, h, idx, depth, &x, &r, &d);
+                    CHECK(rc == PT_OK || rc == 1);
+                    if (rc == PT_OK) CHECK(x > -1.0f && x < (float)w && r > -1.0f && r < (float)h && d >= 0.0f);
+                }
+            }
+            // the same camera sees the pixel where it is
+            CHECK(pt_reproject_project_host(&cam, &cam, w, h, idx, 8.0f, &px, &pr, &z) == PT_OK);
+            CHECK(fabsf(px - (float)(idx % w)) < 0.25f && fabsf(pr - (float)(idx / w)) < 0.25f && fabsf(z - 8.0f) < 1e-4f);
+            px = pr = z = -7.0f;
+        }
+    }
+
+    // ---- the refusals, in the header's order: each call breaks one rule and every rule after it
+    {
+        float buf[4];
+        int32_t ibuf[4];
+        const float *F = buf;
+        const int32_t *I = ibuf;
+        pt::ReprojectFrame f;
+        const void *ctx = buf;  // never dereferenced
+        auto check = [&](const pt_reproject_params *p, uint32_t w, uint32_t h, const pt_camera *c, const float *col, const float *hc,
+                         const float *hl, const pt_camera *hcam, float *out, const void *cx) {
+            return pt::host::check_reproject(cx, w, h, p, c, col, col ? F : nullptr, col ? I : nullptr, nullptr, hcam, hc, hl, hc,
+                                             hc ? I : nullptr, nullptr, out, out, f);
+        };
+        auto refused = [&](int rc, const char *word) { return rc == PT_ERR_INVALID && pt::g_error.find(word) != std::string::npos; };
+        const pt_reproject_params bad_mh = {0, -1.0f, NAN, 2.0f, 1}, bad_dt = {0, 1.0f, INFINITY, 2.0f, 1}, bad_nm = {0, 1.0f, 1.0f, NAN, 1},
+                                  bad_nm2 = {0, 1.0f, 1.0f, -1.5f, 1}, bad_flags = {0, 1.0f, 1.0f, -1.0f, 1}, fine = {3, 8.0f, 0.1f, 1.0f, 0};
+        CHECK(refused(check(&bad_mh, 0, 0, nullptr, nullptr, F, nullptr, nullptr, nullptr, nullptr), "max_history or depth_tol"));
+        CHECK(refused(check(&bad_dt, 0, 0, nullptr, nullptr, F, nullptr, nullptr, nullptr, nullptr), "max_history or depth_tol"));
+        CHECK(refused(check(&bad_nm, 0, 0, nullptr, nullptr, F, nullptr, nullptr, nullptr, nullptr), "normal_min"));
+        CHECK(refused(check(&bad_nm2, 0, 0, nullptr, nullptr, F, nullptr, nullptr, nullptr, nullptr), "normal_min"));
+        CHECK(refused(check(&bad_flags, 0, 0, nullptr, nullptr, F, nullptr, nullptr, nullptr, nullptr), "flags"));
+        CHECK(refused(check(&fine, 0, 3, nullptr, nullptr, F, nullptr, nullptr, nullptr, nullptr), "width and height"));
+        CHECK(refused(check(&fine, 1u << 15, 1u << 15, nullptr, nullptr, F, nullptr, nullptr, nullptr, nullptr), "2^28"));
+        CHECK(refused(check(nullptr, 2, 2, nullptr, F, F, nullptr, nullptr, buf, nullptr), "is NULL"));
+        CHECK(refused(check(nullptr, 2, 2, &cam, nullptr, F, nullptr, nullptr, buf, nullptr), "is NULL"));
+        CHECK(refused(check(nullptr, 2, 2, &cam, F, F, nullptr, nullptr, nullptr, nullptr), "is NULL"));
+        CHECK(refused(check(nullptr, 2, 2, &cam, F, F, nullptr, nullptr, buf, nullptr), "history"));
+        CHECK(refused(check(nullptr, 2, 2, &cam, F, nullptr, F, nullptr, buf, nullptr), "history"));
+        CHECK(refused(check(nullptr, 2, 2, &cam, F, F, F, nullptr, buf, nullptr), "hist_cam"));
+        CHECK(refused(check(nullptr, 2, 2, &cam, F, F, F, &cam, buf, nullptr), "ctx"));
+        CHECK(refused(check(nullptr, 2, 2, &cam, F, nullptr, nullptr, nullptr, buf, nullptr), "ctx"));
+        // accepted: the defaults are filled in, the first frame carries no history
+        pt_reproject_params d;
+        CHECK(check(nullptr, 2, 2, &cam, F, F, F, &near_cam, buf, ctx) == PT_OK);
+        CHECK(f.wt == 1.0f && f.max_history == pt::kReprojectMaxHistory && f.depth_tol == pt::kReprojectDepthTol &&
+              f.normal_min == pt::kReprojectNormalMin && f.view.same == 0u && f.hist_color == F);
+        CHECK(check(&fine, 2, 2, &cam, F, F, F, &cam, buf, ctx) == PT_OK);
+        CHECK(f.wt == 3.0f && f.max_history == 8.0f && f.depth_tol == 0.1f && f.normal_min == 1.0f && f.view.same == 1u);
+        CHECK(check(&fine, 2, 2, &cam, F, nullptr, nullptr, nullptr, buf, ctx) == PT_OK && f.hist_color == nullptr);
+        (void)d;
+    }
+
+    // ---- the pixel over host frames of exactly width * height: every tap inside them, or the sanitizer says so
+    size_t pixels = 0, blended = 0;
+    const uint32_t frames[][2] = {{1, 1}, {2, 1}, {1, 2}, {7, 5}, {257, 3}, {33, 25}};
+    for (const auto &s : frames) {
+        const uint32_t w = s[0], h = s[1], n = w * h;
+        for (const pt_camera *hc : {&cam, &near_cam, &aside, &back, &zero}) {
+            for (int with_normals = 0; with_normals < 2; ++with_normals) {
+                Frames fr = make_frames(n, w * 131u + h);
+                const pt_reproject_params p = {4, 64.0f, 0.05f, 0.5f, 0};
+                pt::ReprojectFrame f;
+                CHECK(pt::host::check_reproject(&fr, w, h, &p, &cam, fr.color.data(), fr.depth.data(), fr.id.data(),
+                                                with_normals ? fr.normal.data() : nullptr, hc, fr.hcolor.data(), fr.hlen.data(),
+                                                fr.hdepth.data(), fr.hid.data(), with_normals ? fr.hnormal.data() : nullptr,
+                                                fr.out.data(), fr.len.data(), f) == PT_OK);
+                for (uint32_t i = 0; i < n; ++i) {
+                    pt::reproject_pixel(f, i, &fr.out[3 * (size_t)i], &fr.len[i]);
+                    CHECK(fr.len[i] >= 4.0f && fr.len[i] <= 64.0f);
+                    for (int c = 0; c < 3; ++c) CHECK(fr.out[3 * (size_t)i + c] >= -1e-6f && fr.out[3 * (size_t)i + c] <= 1.0f + 1e-6f);
+                    if (fr.len[i] > 4.0f) {
+                        CHECK(fr.id[i] >= 0);
+                        ++blended;
+                    } else {
+                        for (int c = 0; c < 3; ++c) CHECK(fr.out[3 * (size_t)i + c] == fr.color[3 * (size_t)i + c]);
+                    }
+                    ++pixels;
+                }
+                if (hc == &back || hc == &zero)
+                    for (uint32_t i = 0; i < n; ++i) CHECK(fr.len[i] == 4.0f);
+            }
+        }
+        // the first frame, and in place
+        Frames fr = make_frames(n, 7u);
+        pt::ReprojectFrame f;
+        CHECK(pt::host::check_reproject(&fr, w, h, nullptr, &cam, fr.color.data(), fr.depth.data(), fr.id.data(), nullptr, nullptr, nullptr,
+                                        nullptr, nullptr, nullptr, nullptr, fr.color.data(), fr.len.data(), f) == PT_OK);
+        const std::vector<float> before = fr.color;
+        for (uint32_t i = 0; i < n; ++i) pt::reproject_pixel(f, i, &fr.color[3 * (size_t)i], &fr.len[i]);
+        CHECK(fr.color == before);
+        for (uint32_t i = 0; i < n; ++i) CHECK(fr.len[i] == 1.0f);
+    }
+    CHECK(blended > pixels / 50);
+    printf("reproject_check: ok (%zu pixels, %zu blended)\n", pixels, blended);
+    return 0;
+}

@@ -23,6 +23,7 @@
 #include "../../include/ptrace.h"
 #include "../csrc/pt_host.h"
 #include "../csrc/pt_present.h"
+#include "../csrc/pt_reproject.h"
 
 namespace {
 
@@ -1224,6 +1225,26 @@ int pt_present_quantize_host(const float *in, size_t n, float exposure, uint8_t 
     const float e = exposure == 0.0f ? 1.0f : exposure;
     const uint32_t *T = pt::present_table();
     for (size_t i = 0; i < n; ++i) out[i] = (uint8_t)pt::present_byte(T, pt::present_bits(pt::present_clamp(in[i], e)));
+    return PT_OK;
+}
+
+int pt_reproject_project_host(const pt_camera *cam, const pt_camera *hist_cam, uint32_t width, uint32_t height, uint32_t idx,
+                              float depth, float *px, float *pr, float *zexp) {
+    if (!cam || !hist_cam || !px || !pr || !zexp) {
+        pt::set_error("NULL argument");
+        return PT_ERR_INVALID;
+    }
+    if (width == 0 || height == 0 || (uint64_t)width * height > (1ull << 28) || idx >= (uint64_t)width * height) {
+        pt::set_error("an empty frame, one above 2^28 pixels, or idx outside it");
+        return PT_ERR_INVALID;
+    }
+    pt::ReprojectView v;
+    pt::host::reproject_view(*cam, hist_cam, v);
+    pt::ReprojectPos p;
+    if (!pt::reproject_project(v, width, height, idx, depth, p)) return 1;  // no position
+    *px = p.px;
+    *pr = p.pr;
+    *zexp = p.zexp;
     return PT_OK;
 }
 

@@ -1,0 +1,346 @@
+"""pt_ctx_reproject on the GPU against tests/reproject_ref.py, the restatement of the contract in include/ptrace.h in numpy
+binary32.  Every comparison is of bytes, for equality.  The frames are the smallest that reach every path: one pixel, odd sizes,
+a frame of three long rows (257 x 3: two workgroups with a one-lane tail, taps that leave the frame above and below), and 33 x 25
+(four workgroups of 256 with a tail).  The cameras: identical (step 2's single tap), translated by less than a pixel to a few
+pixels, rotated onto orthogonals()' other `up` vector (the history frame is turned), and one that puts part of the frame behind
+the history lens and part outside the history frame."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import kats_camera as kc
+import ptlib
+import reproject_ref as ref
+from ptlib import PtConfig, PtStats
+from reproject_ref import F32, I32, PtReprojectParams
+
+pytestmark = pytest.mark.gpu
+
+GUARD = 64  # floats behind each output
+FRAMES = ((1, 1), (7, 5), (257, 3), (33, 25))
+MAXPIX = 96 * 64
+CUR = kc.CORNELL_CAM
+CAMERAS = {
+    "identical": (CUR, dict(CUR)),
+    "translated": (CUR, dict(CUR, position=(0.05, -0.18000005, 7.8))),
+    "other-up": (dict(kc.TILT_CAM, direction=(0.35355338, -0.8660254, 0.35355338)), kc.TILT_CAM),
+    "partly-behind": (CUR, dict(CUR, position=(3.0, -0.2, 3.0), direction=(-0.9578263, 0.0, -0.2873479))),
+}
+PARAMS = dict(weight=4, max_history=64.0, depth_tol=0.05, normal_min=0.5)
+
+
+def hip_runtime():
+    """the HIP runtime the product is bound to: the copy already mapped into this process that is not torch's"""
+    paths = {line.split()[-1] for line in open("/proc/self/maps") if "/libamdhip64.so" in line}
+    own = sorted(p for p in paths if "/torch/" not in p)
+    assert own, "libptrace_hip.so has not mapped a HIP runtime: %r" % sorted(paths)
+    hip = C.CDLL(own[0])
+    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    hip.hipStreamCreate.argtypes = [C.POINTER(C.c_void_p)]
+    hip.hipStreamDestroy.argtypes = [C.c_void_p]
+    return hip
+
+
+NAMES = ("color", "depth", "oid", "normal", "hcolor", "hlen", "hdepth", "hoid", "hnormal", "out", "len")
+FLOATS = dict(color=3, depth=1, oid=1, normal=3, hcolor=3, hlen=1, hdepth=1, hoid=1, hnormal=3, out=3, len=1)
+
+
+class Dev:
+    """one context and the eleven planes of a call, the two outputs with guard floats behind whatever a call writes"""
+
+    def __init__(self, L, max_pix=MAXPIX):
+        self.L = L
+        self.ctx = C.c_void_p()
+        assert L.pt_ctx_create(0, C.byref(self.ctx)) == 0, L.pt_last_error()
+        self.hip = hip_runtime()
+        self.p = {}
+        for name in NAMES:
+            self.p[name] = C.c_void_p()
+            assert L.pt_device_malloc(0, (max_pix * FLOATS[name] + GUARD) * 4, C.byref(self.p[name])) == 0, L.pt_last_error()
+
+    def upload(self, name, host):
+        host = np.ascontiguousarray(host)
+        assert self.hip.hipMemcpy(self.p[name], host.ctypes.data_as(C.c_void_p), host.nbytes, 1) == 0  # host to device
+
+    def download(self, name, count, dtype=F32):
+        host = np.zeros(count, dtype=dtype)
+        assert self.L.pt_device_download(0, host.ctypes.data_as(C.c_void_p), self.p[name], host.nbytes) == 0
+        return host
+
+    def put(self, cur, hist=None):
+        for name, key in (("color", "color"), ("depth", "depth"), ("oid", "oid"), ("normal", "normal")):
+            self.upload(name, cur[key])
+        if hist is not None:
+            for name, key in (("hcolor", "color"), ("hlen", "len"), ("hdepth", "depth"), ("hoid", "oid"), ("hnormal", "normal")):
+                self.upload(name, hist[key])
+
+    def reproject(self, w, h, cam, hist_cam=None, normal=True, hist_normal=True, history=True, in_place=False, stream=None,
+                  params=PARAMS, default_params=False):
+        """the two outputs of one call, (w*h, 3) and (w*h,); the guards behind them are checked on the way"""
+        n = w * h
+        out = "color" if in_place else "out"
+        if not in_place:
+            self.upload("out", np.full(n * 3 + GUARD, -3.0, dtype=F32))
+        else:  # the guard of the colour plane, behind the frame
+            tail = np.full(GUARD, -3.0, dtype=F32)
+            assert self.hip.hipMemcpy(C.c_void_p(self.p["color"].value + n * 12), tail.ctypes.data_as(C.c_void_p), tail.nbytes, 1) == 0
+        self.upload("len", np.full(n + GUARD, -3.0, dtype=F32))
+        p = PtReprojectParams(params["weight"], params["max_history"], params["depth_tol"], params["normal_min"], 0)
+        a = ref.pt_camera(cam)
+        b = ref.pt_camera(hist_cam) if hist_cam is not None else None
+        P = self.p
+        hist = [P["hcolor"], P["hlen"], P["hdepth"], P["hoid"]] if history else [None] * 4
+        rc = self.L.pt_ctx_reproject(self.ctx, w, h, None if default_params else C.byref(p), C.byref(a), P["color"], P["depth"],
+                                     P["oid"], P["normal"] if normal else None, C.byref(b) if b is not None else None, *hist,
+                                     P["hnormal"] if hist_normal else None, P[out], P["len"], stream)
+        assert rc == 0, (rc, self.L.pt_last_error())
+        got = self.download(out, n * 3 + GUARD)
+        ln = self.download("len", n + GUARD)
+        assert (got[n * 3:] == -3.0).all() and (ln[n:] == -3.0).all(), "floats behind an output were written"
+        return got[:n * 3].reshape(n, 3), ln[:n]
+
+    def close(self):
+        for p in self.p.values():
+            self.L.pt_device_free(0, p)
+        self.L.pt_ctx_destroy(self.ctx)
+
+
+@pytest.fixture(scope="module")
+def L():
+    L = ref.bind(ptlib.product())
+    assert L.pt_device_count() >= 1
+    L.pt_ctx_render_aov.argtypes = [C.c_void_p, C.POINTER(PtConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    return L
+
+
+@pytest.fixture(scope="module")
+def dev(L):
+    d = Dev(L)
+    yield d
+    d.close()
+
+
+# ------------------------------------------------------------------------------------------------------ the inputs
+def synthetic(w, h):
+    """(cur, hist): random colours in [0, 1]; depths on a few planes, in blocks so that neighbours mostly share one, and +inf;
+    ids in {-1, 0, 1, 2}; normals around one direction, a tenth of them zero; history lengths 0, 4, .. 16; the history's guides
+    are the frame's own with a part disturbed.  Pixel 0 always has a history that passes (the one-pixel frame blends)."""
+    rng = np.random.default_rng(w * 100 + h)
+    n = w * h
+    planes = np.array([2.0, 6.0, 6.25, 9.0, np.inf], dtype=F32)
+    block = (np.arange(n) % w) // 3 + (np.arange(n) // w) // 2
+    depth = np.where(rng.random(n) < 0.1, planes[rng.integers(0, 5, n)], planes[block % 4]).astype(F32)
+    oid = np.where(rng.random(n) < 0.15, rng.integers(-1, 3, n), block % 3).astype(I32)
+    normal = (np.array([0.2, 0.3, 1.0], dtype=F32) + (rng.random((n, 3)).astype(F32) - F32(0.5)) * F32(0.6)).astype(F32)
+    normal[rng.random(n) < 0.1] = 0
+    depth[0], oid[0], normal[0] = 6.0, 1, (0.0, 0.0, 1.0)
+    cur = dict(color=rng.random((n, 3)).astype(F32), depth=depth, oid=oid, normal=normal)
+    hnormal = normal.copy()
+    flip = rng.random(n) < 0.1
+    hnormal[flip] = -hnormal[flip]
+    hist = dict(color=rng.random((n, 3)).astype(F32), len=(rng.integers(0, 5, n) * 4).astype(F32),
+                depth=np.where(rng.random(n) < 0.15, depth * F32(1.2), depth).astype(F32),
+                oid=np.where(rng.random(n) < 0.1, rng.integers(-1, 3, n), oid).astype(I32), normal=hnormal)
+    hist["len"][0], hist["depth"][0], hist["oid"][0], hist["normal"][0] = 8.0, 6.0, 1, (0.0, 0.0, 1.0)
+    return cur, hist
+
+
+def want(w, h, cam, cur, hist_cam=None, hist=None, normal=True, hist_normal=True, params=PARAMS):
+    kw = {}
+    if hist is not None:
+        kw = dict(hist_cam=hist_cam, hist_color=hist["color"], hist_len=hist["len"], hist_depth=hist["depth"],
+                  hist_object_id=hist["oid"], hist_normal=hist["normal"] if hist_normal else None)
+    return ref.reproject(w, h, cam, cur["color"], cur["depth"], cur["oid"], cur["normal"] if normal else None, **kw, **params)
+
+
+def same_bytes(got, exp, what):
+    for name, a, b in (("colour", got[0], exp[0]), ("length", got[1], exp[1])):
+        if a.tobytes() != b.tobytes():
+            bad = np.argwhere(a.view(np.uint32) != b.view(np.uint32))
+            raise AssertionError("%s %s: %d of %d words differ, first at %s: %r vs %r" % (
+                what, name, len(bad), a.size, bad[0], a[tuple(bad[0])], b[tuple(bad[0])]))
+
+
+# --------------------------------------------------------------------------------------------------- synthetic frames
+@pytest.mark.parametrize("size", FRAMES, ids=["%dx%d" % s for s in FRAMES])
+@pytest.mark.parametrize("camera", list(CAMERAS))
+def test_is_the_restatement(dev, size, camera):
+    w, h = size
+    cam, hist_cam = CAMERAS[camera]
+    cur, hist = synthetic(w, h)
+    dev.put(cur, hist)
+    exp = want(w, h, cam, cur, hist_cam, hist)
+    same_bytes(dev.reproject(w, h, cam, hist_cam), exp, camera)
+    # the inputs reach what they are there for: some pixels blend, and under the last camera some have no position
+    blended = exp[1] > PARAMS["weight"]
+    if camera != "partly-behind" or w * h > 35:
+        assert blended.any(), camera
+    if w * h > 35:
+        assert not blended.all()
+    if camera == "partly-behind" and w * h > 35:
+        ok = ref.project(cam, hist_cam, w, h, np.arange(w * h), np.full(w * h, 6.0, dtype=F32))[0]
+        assert 0.1 < ok.mean() < 0.9
+
+
+@pytest.mark.parametrize("camera", ["identical", "translated"])
+def test_optional_normals(dev, camera):
+    w, h = 33, 25
+    cam, hist_cam = CAMERAS[camera]
+    cur, hist = synthetic(w, h)
+    dev.put(cur, hist)
+    both = dev.reproject(w, h, cam, hist_cam)
+    results = []
+    for normal, hist_normal in ((False, False), (False, True), (True, False)):
+        got = dev.reproject(w, h, cam, hist_cam, normal=normal, hist_normal=hist_normal)
+        same_bytes(got, want(w, h, cam, cur, hist_cam, hist, normal=normal, hist_normal=hist_normal), (camera, normal, hist_normal))
+        results.append(got)
+    # the normal test runs only when both are given: the three forms agree, and differ from the call with both
+    assert all(r[0].tobytes() == results[0][0].tobytes() and r[1].tobytes() == results[0][1].tobytes() for r in results)
+    assert both[1].tobytes() != results[0][1].tobytes()
+
+
+def test_first_frame_form(L, dev):
+    w, h = 33, 25
+    cur, hist = synthetic(w, h)
+    dev.put(cur, hist)
+    for params in (PARAMS, dict(PARAMS, weight=0)):
+        got = dev.reproject(w, h, CUR, None, history=False, hist_normal=False, params=params)
+        assert got[0].tobytes() == cur["color"].tobytes() and (got[1] == (params["weight"] or 1)).all()
+    # hist_cam and a lone history normal are not read
+    got = dev.reproject(w, h, CUR, None, history=False, hist_normal=True)
+    assert got[0].tobytes() == cur["color"].tobytes() and (got[1] == 4).all()
+    # a partial set is refused on the device's side too
+    a = ref.pt_camera(CUR)
+    P = dev.p
+    rc = L.pt_ctx_reproject(dev.ctx, w, h, None, C.byref(a), P["color"], P["depth"], P["oid"], None, C.byref(a), P["hcolor"], None,
+                            P["hdepth"], P["hoid"], None, P["out"], P["len"], None)
+    assert rc == -1 and "history" in L.pt_last_error().decode()
+
+
+def test_defaults_stand_for_zero(L, dev):
+    w, h = 33, 25
+    cam, hist_cam = CAMERAS["translated"]
+    cur, hist = synthetic(w, h)
+    dev.put(cur, hist)
+    d = ref.defaults(L)
+    exp = want(w, h, cam, cur, hist_cam, hist, params=d)
+    same_bytes(dev.reproject(w, h, cam, hist_cam, default_params=True), exp, "NULL params")
+    same_bytes(dev.reproject(w, h, cam, hist_cam, params=dict(weight=0, max_history=0.0, depth_tol=0.0, normal_min=0.0)), exp, "zeros")
+
+
+@pytest.mark.parametrize("camera", ["identical", "translated"])
+def test_in_place_and_on_a_stream(dev, camera):
+    w, h = 33, 25
+    cam, hist_cam = CAMERAS[camera]
+    cur, hist = synthetic(w, h)
+    dev.put(cur, hist)
+    exp = want(w, h, cam, cur, hist_cam, hist)
+    st = C.c_void_p()
+    assert dev.hip.hipStreamCreate(C.byref(st)) == 0
+    try:
+        same_bytes(dev.reproject(w, h, cam, hist_cam, stream=st), exp, "stream")
+        same_bytes(dev.reproject(w, h, cam, hist_cam), exp, "again")
+        same_bytes(dev.reproject(w, h, cam, hist_cam, in_place=True, stream=st), exp, "in place")  # d_out_color == d_color
+    finally:
+        assert dev.hip.hipStreamDestroy(st) == 0
+
+
+def test_still_camera_accumulates_a_running_mean(dev):
+    """three calls with one camera, the outputs swapped in as the history: lengths 4, 8, 12 and the mean of the three colours"""
+    w, h = 7, 5
+    n = w * h
+    rng = np.random.default_rng(9)
+    guides = dict(depth=np.full(n, 6.0, dtype=F32), oid=np.ones(n, dtype=I32), normal=np.tile(np.array([0, 0, 1], dtype=F32), (n, 1)))
+    colors = [rng.random((n, 3)).astype(F32) for _ in range(3)]
+    hist = None
+    for k, c in enumerate(colors):
+        cur = dict(guides, color=c)
+        dev.put(cur, hist)
+        got = dev.reproject(w, h, CUR, CUR, history=hist is not None, hist_normal=hist is not None)
+        same_bytes(got, want(w, h, CUR, cur, CUR, hist), k)
+        hist = dict(guides, color=got[0], len=got[1])
+    assert (hist["len"] == 12).all()
+    assert np.abs(hist["color"] - np.mean(colors, axis=0)).max() < 1e-6
+
+
+# ---------------------------------------------------------------------------------------------------- no state touched
+def render(L, ctx, d_out, w, h, spp, seed):
+    cfg = PtConfig(w, h, spp, 0, seed, 0, 0, 0, 0)
+    st = PtStats()
+    assert L.pt_ctx_render(ctx, C.byref(cfg), d_out, None, None, None, None, C.byref(st)) == 0, L.pt_last_error()
+
+
+def test_leaves_the_context_alone(L):
+    sc = ptlib.load_scene_py(ptlib.scene_path("cornell"))
+    w, h = 33, 25
+    d = Dev(L, w * h)
+    try:
+        assert L.pt_ctx_set_scene(d.ctx, C.byref(sc.cam), sc.objs, sc.n_objs, sc.tris, sc.n_tris) == 0, L.pt_last_error()
+        render(L, d.ctx, d.p["hcolor"], w, h, 4, 3)
+        before = d.download("hcolor", w * h * 3)
+        cur, hist = synthetic(w, h)
+        d.put(cur, hist)
+        cam, hist_cam = CAMERAS["translated"]
+        same_bytes(d.reproject(w, h, cam, hist_cam), want(w, h, cam, cur, hist_cam, hist), "with a scene")
+        for name, key in (("color", "color"), ("depth", "depth"), ("normal", "normal"), ("hcolor", "color"), ("hlen", "len")):
+            src = cur if not name.startswith("h") else hist
+            assert d.download(name, src[key].size).tobytes() == src[key].tobytes(), name  # the inputs are read only
+        render(L, d.ctx, d.p["hcolor"], w, h, 4, 3)
+        assert d.download("hcolor", w * h * 3).tobytes() == before.tobytes()
+    finally:
+        d.close()
+
+
+# --------------------------------------------------------------------------------------------------------- end to end
+def test_end_to_end_on_cornell(L):
+    """Frame A with the scene's camera, frame B one step of the study's orbit on (reproject_ref.ORBIT_DEGREES), each at the study's
+    samples per pixel with its first-hit guides; the history starts at A and is reprojected onto B.
+    (a) the outputs are the restatement's on the downloaded inputs, bit for bit;
+    (b) at least 3/4 of B's hit pixels end with len_out > wt;
+    (c) over those pixels the mean absolute error against B's truth (4096 samples on the device) is below that of B's own colour.
+    The study (profiles/reproject_cpu_study.json, "end_to_end") shows (b) and (c) on oracle inputs, for the whole frame: share
+    0.983, errors 0.0822 with history against 0.1280 without."""
+    w, h = ref.ORBIT_SIZE
+    spp = ref.ORBIT_SPP
+    n = w * h
+    sc = ptlib.load_scene_py(ptlib.scene_path("cornell"))
+    cam_a = ref.cam_dict(sc.cam)
+    cam_b = ref.orbit(cam_a, ref.ORBIT_DEGREES)
+    d = Dev(L, n)
+    d_truth = C.c_void_p()
+    assert L.pt_device_malloc(0, n * 12, C.byref(d_truth)) == 0
+    try:
+        frames = {}
+        for name, cam, seed in (("a", cam_a, 11), ("b", cam_b, 12)):
+            c = ref.pt_camera(cam)
+            assert L.pt_ctx_set_scene(d.ctx, C.byref(c), sc.objs, sc.n_objs, sc.tris, sc.n_tris) == 0, L.pt_last_error()
+            render(L, d.ctx, d.p["color"], w, h, spp, seed)
+            cfg = PtConfig(w, h, spp, 0, seed, 0, 0, 0, 0)
+            assert L.pt_ctx_render_aov(d.ctx, C.byref(cfg), None, d.p["normal"], d.p["depth"], d.p["oid"], None) == 0, L.pt_last_error()
+            frames[name] = dict(color=d.download("color", n * 3).reshape(n, 3), depth=d.download("depth", n),
+                                oid=d.download("oid", n, I32), normal=d.download("normal", n * 3).reshape(n, 3))
+            if name == "a":  # the history starts here: the first-frame form, in place
+                first = d.reproject(w, h, cam, None, history=False, hist_normal=False, in_place=True, params=dict(PARAMS, weight=spp))
+                assert first[0].tobytes() == frames["a"]["color"].tobytes() and (first[1] == spp).all()
+                frames["a"]["len"] = first[1]
+            else:
+                render(L, d.ctx, d_truth, w, h, 4096, 1012)
+        truth = np.zeros((n, 3), dtype=F32)
+        assert L.pt_device_download(0, truth.ctypes.data_as(C.c_void_p), d_truth, truth.nbytes) == 0
+        a, b = frames["a"], frames["b"]
+        d.put(b, a)
+        params = dict(ref.defaults(L), weight=spp)
+        got = d.reproject(w, h, cam_b, cam_a, params=params)
+        same_bytes(got, want(w, h, cam_b, b, cam_a, a, params=params), "cornell")                          # (a)
+        hit = b["oid"] >= 0
+        found = hit & (got[1] > spp)
+        share = found.sum() / hit.sum()
+        with_history = np.abs(got[0][found].astype(np.float64) - truth[found]).mean()
+        without = np.abs(b["color"][found].astype(np.float64) - truth[found]).mean()
+        print("share %.4f, error with history %.5f, without %.5f, over %d pixels" % (share, with_history, without, found.sum()))
+        assert share >= 0.75, share                                                                       # (b)
+        assert with_history < without, (with_history, without)                                            # (c)
+    finally:
+        L.pt_device_free(0, d_truth)
+        d.close()
