@@ -109,6 +109,19 @@ pub struct PtReprojectParams {
     pub flags: u32,
 }
 
+// pt_ctx_reproject_var's parameters; a zero field = the library's default (pt_reproject_var_defaults)
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct PtReprojectVarParams {
+    pub weight: u32,
+    pub max_history: f32,
+    pub depth_tol: f32,
+    pub normal_min: f32,
+    pub min_frames: u32,
+    pub radius: u32,
+    pub flags: u32,
+}
+
 // pt_ctx_denoise's parameters; a zero field = the library's default (pt_denoise_defaults)
 #[repr(C)]
 #[derive(Clone, Copy, Default, Debug)]
@@ -396,6 +409,32 @@ extern "C" {
         d_out_len: *mut f32,
         hip_stream: *mut c_void,
     ) -> i32;
+    // the same with the temporal moments of (r + g) + b carried along and a per-pixel error map out of them, in the units
+    // pt_ctx_denoise_var reads: the viewport's loop is reproject_var -> denoise_var -> present
+    pub fn pt_reproject_var_defaults(out: *mut PtReprojectVarParams) -> i32;
+    pub fn pt_ctx_reproject_var(
+        ctx: *mut PtCtx,
+        width: u32,
+        height: u32,
+        params: *const PtReprojectVarParams,
+        cam: *const PtCamera,
+        d_color: *const f32,
+        d_depth: *const f32,
+        d_object_id: *const i32,
+        d_normal: *const f32,
+        hist_cam: *const PtCamera,
+        d_hist_color: *const f32,
+        d_hist_len: *const f32,
+        d_hist_moments: *const f32,
+        d_hist_depth: *const f32,
+        d_hist_object_id: *const i32,
+        d_hist_normal: *const f32,
+        d_out_color: *mut f32,
+        d_out_len: *mut f32,
+        d_out_moments: *mut f32,
+        d_error: *mut f32,
+        hip_stream: *mut c_void,
+    ) -> i32;
     pub fn pt_reproject_project_host(
         cam: *const PtCamera,
         hist_cam: *const PtCamera,
@@ -475,11 +514,13 @@ fn last_error() -> String {
 }
 
 /// One side of a viewport's temporal history, all in device memory: a colour frame with its history length and the first-hit
-/// guides it was rendered with (pt_ctx_render, pt_ctx_render_aov), and the camera it was seen from.
+/// guides it was rendered with (pt_ctx_render, pt_ctx_render_aov), and the camera it was seen from.  d_moments: the temporal
+/// moments, 2 floats per pixel, which reproject_var_and_swap carries (reproject_and_swap does not read it: it may be null there).
 pub struct ReprojectFrame {
     pub cam: PtCamera,
     pub d_color: *mut f32,
     pub d_len: *mut f32,
+    pub d_moments: *mut f32,
     pub d_depth: *mut f32,
     pub d_object_id: *mut i32,
     pub d_normal: *mut f32,
@@ -510,6 +551,42 @@ pub fn reproject_and_swap(
             pt_ctx_reproject(
                 ctx, frame.0, frame.1, &pp, &cur.cam, cur.d_color, cur.d_depth, cur.d_object_id, cur.d_normal,
                 std::ptr::null(), null, null, null, std::ptr::null(), null, cur.d_color, cur.d_len, std::ptr::null_mut(),
+            )
+        }
+    };
+    if rc == PT_OK {
+        std::mem::swap(cur, hist);
+    }
+    rc
+}
+
+/// reproject_and_swap with the moments carried along and the frame's noise map out of them (pt_ctx_reproject_var): `cur`'s colour
+/// is blended in place, its d_len and d_moments are written, and `d_error` - width * height floats, no part of either side -
+/// receives the estimate pt_ctx_denoise_var reads.  Then the two sides swap roles as there: pointers change hands, nothing is
+/// copied.
+pub fn reproject_var_and_swap(
+    ctx: *mut PtCtx,
+    frame: (u32, u32),
+    weight: u32,
+    cur: &mut ReprojectFrame,
+    hist: &mut ReprojectFrame,
+    d_error: *mut f32,
+    have_history: bool,
+) -> i32 {
+    let pp = PtReprojectVarParams { weight, ..Default::default() };
+    let null = std::ptr::null::<f32>();
+    let rc = unsafe {
+        if have_history {
+            pt_ctx_reproject_var(
+                ctx, frame.0, frame.1, &pp, &cur.cam, cur.d_color, cur.d_depth, cur.d_object_id, cur.d_normal, &hist.cam,
+                hist.d_color, hist.d_len, hist.d_moments, hist.d_depth, hist.d_object_id, hist.d_normal, cur.d_color, cur.d_len,
+                cur.d_moments, d_error, std::ptr::null_mut(),
+            )
+        } else {
+            pt_ctx_reproject_var(
+                ctx, frame.0, frame.1, &pp, &cur.cam, cur.d_color, cur.d_depth, cur.d_object_id, cur.d_normal,
+                std::ptr::null(), null, null, null, null, std::ptr::null(), null, cur.d_color, cur.d_len, cur.d_moments,
+                d_error, std::ptr::null_mut(),
             )
         }
     };

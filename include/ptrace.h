@@ -852,6 +852,70 @@ int pt_reproject_project_host(const pt_camera *cam, const pt_camera *hist_cam, u
                               uint32_t height, uint32_t idx, float depth,
                               float *px, float *pr, float *zexp);
 
+/* ---- reprojection with temporal moments and a noise map per frame -----------------------------------------------
+ * pt_ctx_reproject_var is pt_ctx_reproject plus the rest of SVGF's temporal pass: the first and second moment of s = (r + g) + b
+ * are carried through the same reprojection as the colour and turned into a per-pixel variance; where the history is too short
+ * to trust (the first frame, disocclusions) a spatial estimate over a window of the current frame stands in.  The result is an
+ * error map in the units of THE NOISE ESTIMATE's e(p), which pt_ctx_denoise_var reads as it is: a viewport's loop is
+ * pt_ctx_reproject_var -> pt_ctx_denoise_var -> pt_ctx_present.  pt_ctx_reproject itself is unchanged, and everything it states
+ * about buffers, `hip_stream`, blocking, "no scene is needed" and the first-frame form carries over.  The differences:
+ * - Moments planes: d_hist_moments and d_out_moments hold 2 floats per pixel, (m1, m2), in framebuffer order, 8-byte aligned.
+ *   d_hist_moments belongs to the history set: all five history pointers (d_hist_color, d_hist_len, d_hist_moments,
+ *   d_hist_depth, d_hist_object_id) are NULL, or none is.  After a call the host's history is the set (d_out_color, d_out_len,
+ *   d_out_moments, this call's d_depth, d_object_id, d_normal, cam).
+ * - Error map: d_error is 1 float per pixel, e below, in the units of THE NOISE ESTIMATE's e(p); it can be handed to
+ *   pt_ctx_denoise_var as it is.  +inf means "no estimate".
+ * - Aliasing: d_out_color may be d_color, as for pt_ctx_reproject.  d_out_moments and d_error may alias no input and no other
+ *   output.
+ * - Scratch: the in-place rule makes the call take a scratch plane of 4 B per pixel in the context - this frame's s values,
+ *   written before any colour is overwritten.  It grows on demand, is reused between calls and is freed by pt_ctx_destroy; it
+ *   lies outside the ray-queue budget and is shared with nothing.  The call changes no other state of the context.
+ * - PT_ERR_INVALID, all refused before any device is touched, checked in this order: a max_history or depth_tol that is
+ *   negative or not finite; normal_min outside [-1, 1] or NaN; radius above 3; flags != 0; width or height 0; width * height
+ *   above 2^28; NULL cam, d_color, d_depth, d_object_id, d_out_color, d_out_len, d_out_moments or d_error; a partial set of the
+ *   five history pointers; a full set of history pointers with NULL hist_cam; NULL ctx.  PT_ERR_HIP: a HIP call failed.
+ *   params == NULL stands for all zero.
+ * - pt_reproject_var_defaults fills in the values a zero field stands for: weight 1, max_history 64, depth_tol 2^-3 (0.125),
+ *   normal_min 0.9 (pt_reproject_defaults' three), min_frames 2, radius 3, flags 0.  min_frames and radius were chosen by the
+ *   CPU study recorded in profiles/reproject_var_cpu_study.json.
+ *
+ * THE ARITHMETIC, under pt_ctx_reproject's rules: binary32, correctly rounded, never contracted, in the order the parentheses
+ * give; max(a, b) = a > b ? a : b; pos(v) = v > 0 ? v : 0 (a NaN gives 0); wt, W as there.
+ * Colour and length.  d_out_color and d_out_len are pt_ctx_reproject's, bit for bit: its steps 1-5 with the same taps taken
+ *    and the same b.
+ * Moments.  s = (color[idx][0] + color[idx][1]) + color[idx][2], of the input colour; q2 = s*s.  Where pt_ctx_reproject's step 1
+ *    applies to the pixel: m1 = s, m2 = q2.  Otherwise, over the taps that were taken and in their order:
+ *    a1 = a1 + hist_m[q][0]*b; a2 = a2 + hist_m[q][1]*b; then h1 = a1/bsum; h2 = a2/bsum; k = wt/n';
+ *    m1 = h1 + (s - h1)*k; m2 = h2 + (q2 - h2)*k: the colour's blend applied to the pair (s, s*s).
+ * Temporal variance.  vt = pos(m2 - m1*m1); k = wt / len_out; long = len_out >= (float)min_frames * wt, the product formed on
+ *    the host in binary32.
+ * Spatial estimate, for pixels that are not long.  The pixel sits at column x and row r = idx / W; R = radius.  Loop dy = -R..R
+ *    outside, dx = -R..R inside, over q = (x+dx, r+dy) inside the frame (a q outside it is skipped, not clamped).  The centre is
+ *    always taken.  Another q is taken iff object_id[q] == object_id[idx] and either object_id[idx] < 0 or
+ *    |depth[idx] - depth[q]| <= depth_tol * max(depth[idx], depth[q]).  A taken q adds S1 = S1 + s_q; S2 = S2 + s_q*s_q;
+ *    cnt = cnt + 1, where s_q comes from the INPUT colour at q and cnt is an integer.  mean = S1/(float)cnt;
+ *    vs = pos(S2/(float)cnt - mean*mean); v = max(vs, vt).  With cnt < 2 there is no estimate: e = +inf.
+ * Long pixels.  v = vt.
+ * Error.  e = sqrt(v*k) / sqrt(2^-6 + ((out[0] + out[1]) + out[2])), over the blended colour; if !(e < 12), e = 12. */
+typedef struct pt_reproject_var_params {
+    uint32_t weight;      /* as pt_reproject_params */
+    float max_history;    /* as pt_reproject_params */
+    float depth_tol;      /* as pt_reproject_params; also the spatial window's depth test */
+    float normal_min;     /* as pt_reproject_params */
+    uint32_t min_frames;  /* a history shorter than min_frames * weight samples takes the spatial estimate; 0 = the default */
+    uint32_t radius;      /* spatial window (2*radius+1)^2; 0 = the default; at most 3 */
+    uint32_t flags;       /* none defined: must be 0 */
+} pt_reproject_var_params;
+int pt_reproject_var_defaults(pt_reproject_var_params *out);
+int pt_ctx_reproject_var(pt_ctx *ctx, uint32_t width, uint32_t height, const pt_reproject_var_params *params,
+                         const pt_camera *cam, const float *d_color, const float *d_depth,
+                         const int32_t *d_object_id, const float *d_normal /* may be NULL */,
+                         const pt_camera *hist_cam, const float *d_hist_color, const float *d_hist_len,
+                         const float *d_hist_moments, const float *d_hist_depth,
+                         const int32_t *d_hist_object_id, const float *d_hist_normal /* may be NULL */,
+                         float *d_out_color, float *d_out_len, float *d_out_moments, float *d_error,
+                         void *hip_stream);
+
 /* ---- the one collective of the path: the framebuffer gather over RCCL (xGMI) ---------------------------------
  * One process (or thread) per GPU renders its rows with pt_ctx_render (chunk_first = rank, chunk_step = n_ranks) into
  * device memory; pt_comm_gather_frame then gives EVERY rank the whole frame in device memory: one in-place

@@ -67,6 +67,11 @@ class pt_reproject_params(C.Structure):
                 ("flags", C.c_uint32)]
 
 
+class pt_reproject_var_params(C.Structure):
+    _fields_ = [("weight", C.c_uint32), ("max_history", C.c_float), ("depth_tol", C.c_float), ("normal_min", C.c_float),
+                ("min_frames", C.c_uint32), ("radius", C.c_uint32), ("flags", C.c_uint32)]
+
+
 class pt_noise_stats(C.Structure):
     _fields_ = [("spp_min", C.c_uint32), ("spp_max", C.c_uint32), ("spp_a_min", C.c_uint32), ("spp_b_min", C.c_uint32),
                 ("pixels", C.c_uint64), ("mean_error", C.c_double), ("histogram", C.c_uint32 * 64)]
@@ -157,6 +162,9 @@ def lib():
     L.pt_reproject_defaults.argtypes = [C.POINTER(pt_reproject_params)]
     L.pt_ctx_reproject.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(pt_reproject_params), C.POINTER(pt_camera)] + \
         [C.c_void_p] * 4 + [C.POINTER(pt_camera)] + [C.c_void_p] * 8
+    L.pt_reproject_var_defaults.argtypes = [C.POINTER(pt_reproject_var_params)]
+    L.pt_ctx_reproject_var.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(pt_reproject_var_params), C.POINTER(pt_camera)] + \
+        [C.c_void_p] * 4 + [C.POINTER(pt_camera)] + [C.c_void_p] * 11
     L.pt_reproject_project_host.argtypes = [C.POINTER(pt_camera), C.POINTER(pt_camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_float] + \
         [C.POINTER(C.c_float)] * 3
     L.pt_write_pfm.argtypes = [C.c_char_p, C.POINTER(C.c_float), C.c_uint32, C.c_uint32, C.c_uint32]
@@ -342,6 +350,22 @@ class Context:
                                       ptr(normal), _camera(h["cam"]) if history else None, ptr(h.get("color")), ptr(h.get("len")),
                                       ptr(h.get("depth")), ptr(h.get("object_id")), ptr(h.get("normal")), ptr(out_color),
                                       ptr(out_len), C.c_void_p(stream or 0)))
+
+    def reproject_var(self, width, height, cam, color, depth, object_id, out_color, out_len, out_moments, error, normal=None,
+                      history=None, weight=1, max_history=0.0, depth_tol=0.0, normal_min=0.0, min_frames=0, radius=0, stream=None):
+        """reproject() with the temporal moments of (r + g) + b carried along and a noise map per frame out of them
+        (pt_ctx_reproject_var).  As reproject(), and: out_moments pixels * 2 float32, error pixels float32 - the estimate
+        denoise_var() reads, +inf where there is none; `history` also holds "moments" - after the call the next frame's history
+        is dict(cam=cam, color=out_color, len=out_len, moments=out_moments, depth=depth, object_id=object_id, normal=normal).
+        min_frames, radius: 0 = reproject_var_defaults().  out_color may be color; out_moments and error alias nothing."""
+        p = pt_reproject_var_params(weight, max_history, depth_tol, normal_min, min_frames, radius, 0)
+        ptr = lambda q: C.c_void_p(q) if q else None  # noqa: E731
+        h = history or {}
+        _check(lib().pt_ctx_reproject_var(self._h, width, height, C.byref(p), _camera(cam), ptr(color), ptr(depth), ptr(object_id),
+                                          ptr(normal), _camera(h["cam"]) if history else None, ptr(h.get("color")),
+                                          ptr(h.get("len")), ptr(h.get("moments")), ptr(h.get("depth")), ptr(h.get("object_id")),
+                                          ptr(h.get("normal")), ptr(out_color), ptr(out_len), ptr(out_moments), ptr(error),
+                                          C.c_void_p(stream or 0)))
 
     def accum_track_noise(self, on=True):
         """Keep half of every pixel's samples in a second accumulator for the frames started from now on
@@ -542,6 +566,15 @@ def reproject_defaults():
     p = pt_reproject_params()
     _check(lib().pt_reproject_defaults(C.byref(p)))
     return {"weight": p.weight, "max_history": p.max_history, "depth_tol": p.depth_tol, "normal_min": p.normal_min}
+
+
+def reproject_var_defaults():
+    """The values pt_ctx_reproject_var uses for a zero field: reproject_defaults()' four and {"min_frames", "radius"}
+    (pt_reproject_var_defaults)."""
+    p = pt_reproject_var_params()
+    _check(lib().pt_reproject_var_defaults(C.byref(p)))
+    return {"weight": p.weight, "max_history": p.max_history, "depth_tol": p.depth_tol, "normal_min": p.normal_min,
+            "min_frames": p.min_frames, "radius": p.radius}
 
 
 def reproject_project_host(cam, hist_cam, width, height, idx, depth):

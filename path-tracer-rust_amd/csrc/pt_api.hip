@@ -337,6 +337,8 @@ struct pt_ctx {
     // resampling form's intermediate, [3] planes of width * out_height u64, grown on demand
     DevBuf<uint32_t> pr_table;
     DevBuf<unsigned long long> pr_mid;
+    // pt_ctx_reproject_var's scratch, its own too: the frame's s values, one float per pixel, grown on demand
+    DevBuf<float> rv_s;
     // The adaptive calls: the frame kept between calls (pt_ctx_set_scene drops it), and their scratch, kept too and grown on
     // demand: the compact accumulator of a step's tiles, the step's open-tile list, the counters (u64 [0]: the sum of E at the
     // end; u32 [2], [3]: the tiles a step left open / closed; u32 [4]: the list's length; u32 [5..7]: k_tile_select's counts),
@@ -2759,6 +2761,38 @@ int pt_ctx_reproject(pt_ctx *c, uint32_t width, uint32_t height, const pt_reproj
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
     launch_reproject(st, f);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    return PT_OK;
+}
+
+int pt_reproject_var_defaults(pt_reproject_var_params *out) {
+    if (!out) {
+        set_error("out is NULL");
+        return PT_ERR_INVALID;
+    }
+    *out = pt_reproject_var_params{1u, kReprojectMaxHistory, kReprojectDepthTol, kReprojectNormalMin, kReprojectVarMinFrames,
+                                   kReprojectVarRadius, 0u};
+    return PT_OK;
+}
+
+int pt_ctx_reproject_var(pt_ctx *c, uint32_t width, uint32_t height, const pt_reproject_var_params *params, const pt_camera *cam,
+                         const float *d_color, const float *d_depth, const int32_t *d_object_id, const float *d_normal,
+                         const pt_camera *hist_cam, const float *d_hist_color, const float *d_hist_len, const float *d_hist_moments,
+                         const float *d_hist_depth, const int32_t *d_hist_object_id, const float *d_hist_normal, float *d_out_color,
+                         float *d_out_len, float *d_out_moments, float *d_error, void *hip_stream) {
+    // everything that can be refused is refused here, before the device is touched
+    ReprojectVarFrame v;
+    const int rc = host::check_reproject_var(c, width, height, params, cam, d_color, d_depth, d_object_id, d_normal, hist_cam,
+                                             d_hist_color, d_hist_len, d_hist_moments, d_hist_depth, d_hist_object_id, d_hist_normal,
+                                             d_out_color, d_out_len, d_out_moments, d_error, v);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    const int rs = c->rv_s.ensure((size_t)width * height);
+    if (rs) return rs;
+    v.s_plane = c->rv_s.p;
+    launch_reproject_var(st, v);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
     return PT_OK;

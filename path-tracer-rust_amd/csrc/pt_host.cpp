@@ -1331,5 +1331,41 @@ int check_reproject(const void *ctx, uint32_t width, uint32_t height, const pt_r
     return PT_OK;
 }
 
+int check_reproject_var(const void *ctx, uint32_t width, uint32_t height, const pt_reproject_var_params *params, const pt_camera *cam,
+                        const float *d_color, const float *d_depth, const int32_t *d_object_id, const float *d_normal,
+                        const pt_camera *hist_cam, const float *d_hist_color, const float *d_hist_len, const float *d_hist_moments,
+                        const float *d_hist_depth, const int32_t *d_hist_object_id, const float *d_hist_normal, float *d_out_color,
+                        float *d_out_len, float *d_out_moments, float *d_error, ReprojectVarFrame &v) {
+    pt_reproject_var_params P{};
+    if (params) P = *params;
+    if (!finite_nonneg(P.max_history) || !finite_nonneg(P.depth_tol))
+        return refuse("pt_reproject_var_params: max_history or depth_tol is negative or not finite");
+    if (!(P.normal_min >= -1.0f && P.normal_min <= 1.0f)) return refuse("pt_reproject_var_params.normal_min is outside [-1, 1]");
+    if (P.radius > kReprojectVarMaxRadius) return refuse("pt_reproject_var_params.radius exceeds 3");
+    if (P.flags) return refuse("pt_reproject_var_params.flags: none is defined");
+    if (!width || !height) return refuse("width and height must be positive");
+    if ((uint64_t)width * height > (1ull << 28)) return refuse("width*height exceeds 2^28");
+    if (!cam || !d_color || !d_depth || !d_object_id || !d_out_color || !d_out_len || !d_out_moments || !d_error)
+        return refuse("cam, d_color, d_depth, d_object_id, d_out_color, d_out_len, d_out_moments or d_error is NULL");
+    const int n_hist = (d_hist_color != nullptr) + (d_hist_len != nullptr) + (d_hist_moments != nullptr) + (d_hist_depth != nullptr) +
+                       (d_hist_object_id != nullptr);
+    if (n_hist != 0 && n_hist != 5)
+        return refuse("history: d_hist_color, d_hist_len, d_hist_moments, d_hist_depth and d_hist_object_id are all NULL or none is");
+    if (n_hist && !hist_cam) return refuse("hist_cam is NULL with a history");
+    if (!ctx) return refuse("ctx is NULL");
+    // what is left is pt_ctx_reproject's call, which has passed every one of its own checks above
+    const pt_reproject_params Q = {P.weight, P.max_history, P.depth_tol, P.normal_min, 0u};
+    v = ReprojectVarFrame{};
+    const int rc = check_reproject(ctx, width, height, &Q, cam, d_color, d_depth, d_object_id, d_normal, hist_cam, d_hist_color,
+                                   d_hist_len, d_hist_depth, d_hist_object_id, d_hist_normal, d_out_color, d_out_len, v.f);
+    if (rc) return rc;
+    v.hist_moments = reinterpret_cast<const ReprojectMom *>(d_hist_moments);
+    v.out_moments = reinterpret_cast<ReprojectMom *>(d_out_moments);
+    v.error = d_error;
+    v.long_len = (float)(P.min_frames ? P.min_frames : kReprojectVarMinFrames) * v.f.wt;
+    v.radius = P.radius ? P.radius : kReprojectVarRadius;
+    return PT_OK;
+}
+
 }  // namespace host
 }  // namespace pt

@@ -37,6 +37,28 @@ struct ReprojectFrame {
     ReprojectView view;
 };
 
+// pt_ctx_reproject_var: the values a zero min_frames / radius stands for - what its CPU study picked
+// (profiles/reproject_var_cpu_study.json) - the marker kernel A leaves in d_error for a pixel whose history is short (an
+// estimate is never negative), and kernel B's tile (pt_denoise.hip's shape)
+constexpr uint32_t kReprojectVarMinFrames = 2u, kReprojectVarRadius = 3u, kReprojectVarMaxRadius = 3u;
+constexpr float kReprojectVarShort = -1.0f;
+constexpr uint32_t kReprojectVarTileW = 32u, kReprojectVarTileH = 8u;
+
+// a pixel's temporal moments (m1, m2) of s = (r + g) + b: one 8-byte load or store
+struct alignas(8) ReprojectMom {
+    float m1, m2;
+};
+
+// pt_ctx_reproject_var's call: pt_ctx_reproject's, the moments planes, the error map and the context's plane of s values
+struct ReprojectVarFrame {
+    ReprojectFrame f;
+    const ReprojectMom *hist_moments;  // NULL with f.hist_color
+    ReprojectMom *out_moments;
+    float *error, *s_plane;
+    float long_len;   // (float)min_frames * wt: a history of at least this many samples is long
+    uint32_t radius;  // the spatial window is (2 * radius + 1)^2
+};
+
 struct ReprojectPos {
     float px, pr, zexp;
 };
@@ -92,9 +114,13 @@ struct ReprojectTap {
 // all of its history reads in flight at once instead of up to three dependent round trips per tap, one tap after the other.  A
 // tap that fails its test has been read for nothing - its neighbours want the same lines - and adds nothing: the sums are the
 // contract's, in its order.  false: bsum > 0 does not hold (step 1).
-template <int NT>
+// MOM (pt_ctx_reproject_var): the taps' moments ride along - read with the rest, summed with the same b over the same taps, and
+// blended with the same k as the colour; `mom` holds (s, s*s) on entry and (m1, m2) on return.  Without MOM nothing of it is
+// compiled.
+template <int NT, bool MOM = false>
 PT_HD bool reproject_gather(const ReprojectFrame &f, const ReprojectTap (&tap)[NT], float zexp, int32_t id, bool normals, vec3 N,
-                            const float col[3], float out[3], float *len_out) {
+                            const float col[3], float out[3], float *len_out, const ReprojectMom *hist_moments = nullptr,
+                            ReprojectMom *mom = nullptr) {
     float hlen[NT], hdepth[NT];
     int32_t hid[NT];
 #pragma unroll
@@ -113,7 +139,12 @@ PT_HD bool reproject_gather(const ReprojectFrame &f, const ReprojectTap (&tap)[N
             hn[t][c] = normals ? f.hist_normal[q3 + c] : 0.0f;
         }
     }
-    float s[3] = {0.0f, 0.0f, 0.0f}, nsum = 0.0f, bsum = 0.0f;
+    ReprojectMom hm[NT];
+    if constexpr (MOM) {
+#pragma unroll
+        for (int t = 0; t < NT; ++t) hm[t] = hist_moments[tap[t].q];
+    }
+    float s[3] = {0.0f, 0.0f, 0.0f}, nsum = 0.0f, bsum = 0.0f, a1 = 0.0f, a2 = 0.0f;
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
         bool take = tap[t].inside && reproject_tap_ok(hlen[t], hid[t], id, zexp, hdepth[t], f.depth_tol);
@@ -121,6 +152,10 @@ PT_HD bool reproject_gather(const ReprojectFrame &f, const ReprojectTap (&tap)[N
         const float b = tap[t].b;
 #pragma unroll
         for (int c = 0; c < 3; ++c) s[c] = take ? s[c] + hc[t][c] * b : s[c];
+        if constexpr (MOM) {
+            a1 = take ? a1 + hm[t].m1 * b : a1;
+            a2 = take ? a2 + hm[t].m2 * b : a2;
+        }
         nsum = take ? nsum + hlen[t] * b : nsum;
         bsum = take ? bsum + b : bsum;
     }
@@ -133,6 +168,11 @@ PT_HD bool reproject_gather(const ReprojectFrame &f, const ReprojectTap (&tap)[N
     for (int c = 0; c < 3; ++c) {
         const float h = s[c] / bsum;
         out[c] = h + (col[c] - h) * k;
+    }
+    if constexpr (MOM) {
+        const float h1 = a1 / bsum, h2 = a2 / bsum;
+        mom->m1 = h1 + (mom->m1 - h1) * k;
+        mom->m2 = h2 + (mom->m2 - h2) * k;
     }
     *len_out = n;
     return true;
@@ -155,13 +195,22 @@ PT_HD int32_t reproject_own(const int32_t *p) {
 }
 
 // steps 1 to 5 for pixel idx (< width * height): the colour and the length it ends with.  The pixel's own colour is read before
-// anything is returned, so the caller may store into color[idx].
-PT_HD void reproject_pixel(const ReprojectFrame &f, uint32_t idx, float out[3], float *len_out) {
+// anything is returned, so the caller may store into color[idx].  MOM: pt_ctx_reproject_var's moments too - *s_out is the
+// pixel's s = (r + g) + b of the input colour, *mom its (m1, m2).
+template <bool MOM>
+PT_HD void reproject_pixel_t(const ReprojectFrame &f, uint32_t idx, float out[3], float *len_out, const ReprojectMom *hist_moments,
+                             ReprojectMom *mom, float *s_out) {
     const size_t i3 = (size_t)idx * 3u;
     float col[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) out[c] = col[c] = reproject_own(f.color + i3 + c);
     *len_out = f.wt;
+    if constexpr (MOM) {
+        const float s = (col[0] + col[1]) + col[2];
+        *s_out = s;
+        mom->m1 = s;
+        mom->m2 = s * s;
+    }
     if (!f.hist_color) return;
     const int32_t id = reproject_own(f.object_id + idx);
     if (id < 0) return;
@@ -174,7 +223,7 @@ PT_HD void reproject_pixel(const ReprojectFrame &f, uint32_t idx, float out[3], 
     }
     if (f.view.same) {
         const ReprojectTap tap[1] = {{idx, 1.0f, true}};
-        reproject_gather<1>(f, tap, depth, id, normals, N, col, out, len_out);
+        reproject_gather<1, MOM>(f, tap, depth, id, normals, N, col, out, len_out, hist_moments, mom);
         return;
     }
     ReprojectPos p;
@@ -196,7 +245,87 @@ PT_HD void reproject_pixel(const ReprojectFrame &f, uint32_t idx, float out[3], 
             t.b = (i ? fx : 1.0f - fx) * (j ? fr : 1.0f - fr);
         }
     }
-    reproject_gather<4>(f, tap, p.zexp, id, normals, N, col, out, len_out);
+    reproject_gather<4, MOM>(f, tap, p.zexp, id, normals, N, col, out, len_out, hist_moments, mom);
+}
+PT_HD void reproject_pixel(const ReprojectFrame &f, uint32_t idx, float out[3], float *len_out) {
+    reproject_pixel_t<false>(f, idx, out, len_out, nullptr, nullptr, nullptr);
+}
+
+// ---- pt_ctx_reproject_var: the variance and the error map ("THE ARITHMETIC" of pt_ctx_reproject_var in include/ptrace.h)
+PT_HD float reproject_pos(float v) { return v > 0.0f ? v : 0.0f; }
+// vt = pos(m2 - m1*m1)
+PT_HD float reproject_var_temporal(const ReprojectMom &m) { return reproject_pos(m.m2 - m.m1 * m.m1); }
+// e = sqrt(v*k) / sqrt(2^-6 + ((out[0] + out[1]) + out[2])), at most 12 (a NaN gives 12)
+PT_HD float reproject_var_error(float v, float k, const float out[3]) {
+    const float e = __builtin_sqrtf(v * k) / __builtin_sqrtf(0.015625f + ((out[0] + out[1]) + out[2]));
+    return e < 12.0f ? e : 12.0f;
+}
+
+// Kernel A's pixel: pt_ctx_reproject's colour and length, the moments, the s plane, and d_error - final where the history is
+// long, kReprojectVarShort where the spatial estimate has to stand in.  Everything the pixel reads of planes it may share with
+// an output (its own colour) is read before the first store.
+PT_HD void reproject_var_pixel(const ReprojectVarFrame &v, uint32_t idx) {
+    float out[3], len, s;
+    ReprojectMom mom;
+    reproject_pixel_t<true>(v.f, idx, out, &len, v.hist_moments, &mom, &s);
+    float *o = v.f.out_color + (size_t)idx * 3u;
+    o[0] = out[0];
+    o[1] = out[1];
+    o[2] = out[2];
+    v.f.out_len[idx] = len;
+    v.out_moments[idx] = mom;
+    v.s_plane[idx] = s;
+    v.error[idx] = len >= v.long_len ? reproject_var_error(reproject_var_temporal(mom), v.f.wt / len, out) : kReprojectVarShort;
+}
+
+// The spatial estimate of the pixel at column x, row r: the window of s values around it, in the contract's tap order (dy outside,
+// dx inside; taps outside the frame skipped, the centre always taken).  src(qx, qr, s, id, depth) reads a pixel of the frame:
+// global planes on the host, the staged tile on the device.  false: fewer than two taps, no estimate.
+template <class Src>
+PT_HD bool reproject_var_spatial(const Src &src, int32_t W, int32_t H, int32_t R, float depth_tol, int32_t x, int32_t r, float *vs) {
+    float s0, z0;
+    int32_t id0;
+    src(x, r, s0, id0, z0);
+    float S1 = 0.0f, S2 = 0.0f;
+    uint32_t cnt = 0;
+    for (int32_t dy = -R; dy <= R; ++dy) {
+        const int32_t qr = r + dy;
+        if (qr < 0 || qr >= H) continue;
+        for (int32_t dx = -R; dx <= R; ++dx) {
+            const int32_t qx = x + dx;
+            if (qx < 0 || qx >= W) continue;
+            float sq, zq;
+            int32_t idq;
+            src(qx, qr, sq, idq, zq);
+            bool take = idq == id0;
+            if (id0 >= 0) {
+                const float zm = z0 > zq ? z0 : zq;
+                take = take && __builtin_fabsf(z0 - zq) <= depth_tol * zm;
+            }
+            take = take || (dx == 0 && dy == 0);
+            S1 = take ? S1 + sq : S1;
+            S2 = take ? S2 + sq * sq : S2;
+            cnt += take ? 1u : 0u;
+        }
+    }
+    if (cnt < 2u) return false;
+    const float fc = (float)cnt, mean = S1 / fc;
+    *vs = reproject_pos(S2 / fc - mean * mean);
+    return true;
+}
+
+// Kernel B's pixel, for one kernel A marked short: e from max(vs, vt), or +inf without a spatial estimate.  It reads the pixel's
+// own outputs of kernel A and writes d_error[idx] alone.
+template <class Src>
+PT_HD float reproject_var_short_pixel(const ReprojectVarFrame &v, const Src &src, uint32_t idx) {
+    const int32_t W = (int32_t)v.f.width, H = (int32_t)v.f.height;
+    float vs;
+    if (!reproject_var_spatial(src, W, H, (int32_t)v.radius, v.f.depth_tol, (int32_t)(idx % v.f.width), (int32_t)(idx / v.f.width), &vs))
+        return __builtin_inff();
+    const float vt = reproject_var_temporal(v.out_moments[idx]);
+    const float *o = v.f.out_color + (size_t)idx * 3u;
+    const float out[3] = {o[0], o[1], o[2]};
+    return reproject_var_error(vs > vt ? vs : vt, v.f.wt / v.f.out_len[idx], out);
 }
 
 namespace host {
@@ -209,11 +338,20 @@ int check_reproject(const void *ctx, uint32_t width, uint32_t height, const pt_r
                     const pt_camera *hist_cam, const float *d_hist_color, const float *d_hist_len, const float *d_hist_depth,
                     const int32_t *d_hist_object_id, const float *d_hist_normal, float *d_out_color, float *d_out_len,
                     ReprojectFrame &f);
+// pt_ctx_reproject_var's refusals in the header's order; PT_OK: `v` holds the call with the defaults filled in, but for
+// v.s_plane, which the caller owns.  No device is touched.
+int check_reproject_var(const void *ctx, uint32_t width, uint32_t height, const pt_reproject_var_params *params, const pt_camera *cam,
+                        const float *d_color, const float *d_depth, const int32_t *d_object_id, const float *d_normal,
+                        const pt_camera *hist_cam, const float *d_hist_color, const float *d_hist_len, const float *d_hist_moments,
+                        const float *d_hist_depth, const int32_t *d_hist_object_id, const float *d_hist_normal, float *d_out_color,
+                        float *d_out_len, float *d_out_moments, float *d_error, ReprojectVarFrame &v);
 }  // namespace host
 
 #if defined(__HIPCC__)
 // one lane per pixel
 void launch_reproject(hipStream_t st, const ReprojectFrame &f);
+// kernel A, one lane per pixel, then kernel B, one workgroup per tile of 32 x 8
+void launch_reproject_var(hipStream_t st, const ReprojectVarFrame &v);
 #endif
 
 }  // namespace pt

@@ -30,7 +30,76 @@ __global__ __launch_bounds__(kReprojectBlock) void k_reproject(const ReprojectFr
     f.out_len[idx] = len;
 }
 
+// ---- pt_ctx_reproject_var.  Two launches, because which pixels are short is known only after the projection and the gather,
+// and because d_out_color may be d_color: the window reads its neighbours' s values, so the s plane has to be complete before any
+// colour is overwritten.
+//
+// Kernel A is k_reproject with the moments riding along (reproject_gather<NT, true>): 112 B per pixel at most - 32 read of this
+// frame, 36 + 8 of the history, 16 + 8 + 4 + 4 written.
+__global__ __launch_bounds__(kReprojectBlock) void k_reproject_var(const ReprojectVarFrame v, uint32_t npix) {
+    const uint32_t idx = blockIdx.x * kReprojectBlock + threadIdx.x;
+    if (idx >= npix) return;
+    reproject_var_pixel(v, idx);
+}
+
+// Kernel B: the spatial estimate of the pixels kernel A marked.  One workgroup per tile of 32 x 8, one lane per pixel.  In steady
+// state a few percent of the pixels are short, so a workgroup reads its tile's markers (4 B per pixel, one line per row) and
+// returns when none is set.  Otherwise it stages s, object id and depth of tile + halo in LDS once - three planes of
+// 38 x 14 words, 6384 B: the halo of the largest radius, whatever R is - and the marked lanes run the window from there:
+// up to 49 taps of three words each from LDS instead of from L1.  Entries outside the frame are staged as zeros and never
+// read: the window skips them by their coordinates.
+constexpr uint32_t kRvTileW = kReprojectVarTileW, kRvTileH = kReprojectVarTileH, kRvMaxR = kReprojectVarMaxRadius;
+constexpr uint32_t kRvStageW = kRvTileW + 2u * kRvMaxR, kRvStageH = kRvTileH + 2u * kRvMaxR;
+
+struct RvTile {
+    const float *s, *z;
+    const int32_t *id;
+    int32_t x0, r0, pitch;  // the frame position of entry (0, 0), and the entries per staged row
+    __device__ void operator()(int32_t qx, int32_t qr, float &so, int32_t &ido, float &zo) const {
+        const int32_t e = (qr - r0) * pitch + (qx - x0);
+        so = s[e];
+        ido = id[e];
+        zo = z[e];
+    }
+};
+
+__global__ __launch_bounds__(kRvTileW *kRvTileH) void k_reproject_var_spatial(const ReprojectVarFrame v, uint32_t tiles_x) {
+    __shared__ float sh_s[kRvStageW * kRvStageH], sh_z[kRvStageW * kRvStageH];
+    __shared__ int32_t sh_id[kRvStageW * kRvStageH];
+    const int32_t W = (int32_t)v.f.width, H = (int32_t)v.f.height;
+    const int32_t tx = (int32_t)(threadIdx.x % kRvTileW), ty = (int32_t)(threadIdx.x / kRvTileW);
+    const int32_t bx = (int32_t)((blockIdx.x % tiles_x) * kRvTileW), br = (int32_t)((blockIdx.x / tiles_x) * kRvTileH);
+    const int32_t x = bx + tx, r = br + ty;
+    const bool in_frame = x < W && r < H;
+    const uint32_t idx = in_frame ? (uint32_t)r * v.f.width + (uint32_t)x : 0u;
+    const bool marked = in_frame && v.error[idx] == kReprojectVarShort;
+    if (!__syncthreads_or(marked)) return;
+    // (always the halo of the largest radius: a pitch known at compile time, so that e % pitch and e / pitch are multiplies)
+    constexpr int32_t pitch = (int32_t)kRvStageW, rows = (int32_t)kRvStageH;
+    const int32_t x0 = bx - (int32_t)kRvMaxR, r0 = br - (int32_t)kRvMaxR;
+    for (int32_t e = (int32_t)threadIdx.x; e < pitch * rows; e += (int32_t)(kRvTileW * kRvTileH)) {
+        const int32_t qx = x0 + e % pitch, qr = r0 + e / pitch;
+        const bool in = qx >= 0 && qx < W && qr >= 0 && qr < H;
+        const uint32_t q = in ? (uint32_t)qr * v.f.width + (uint32_t)qx : 0u;
+        sh_s[e] = in ? v.s_plane[q] : 0.0f;
+        sh_id[e] = in ? v.f.object_id[q] : 0;
+        sh_z[e] = in ? v.f.depth[q] : 0.0f;
+    }
+    __syncthreads();
+    if (!marked) return;
+    const RvTile tile = {sh_s, sh_z, sh_id, x0, r0, pitch};
+    v.error[idx] = reproject_var_short_pixel(v, tile, idx);
+}
+
 }  // namespace
+
+void launch_reproject_var(hipStream_t st, const ReprojectVarFrame &v) {
+    const uint32_t npix = v.f.width * v.f.height;  // at most 2^28
+    hipLaunchKernelGGL(k_reproject_var, dim3((npix + kReprojectBlock - 1u) / kReprojectBlock), dim3(kReprojectBlock), 0, st, v, npix);
+    // a grid of one dimension: a frame of one column and 2^28 rows is 2^25 tiles down, more than a grid's y takes
+    const uint32_t tiles_x = (v.f.width + kRvTileW - 1u) / kRvTileW, tiles_y = (v.f.height + kRvTileH - 1u) / kRvTileH;
+    hipLaunchKernelGGL(k_reproject_var_spatial, dim3(tiles_x * tiles_y), dim3(kRvTileW * kRvTileH), 0, st, v, tiles_x);
+}
 
 void launch_reproject(hipStream_t st, const ReprojectFrame &f) {
     const uint32_t npix = f.width * f.height;  // at most 2^28: 2^20 workgroups

@@ -1,0 +1,229 @@
+// reproject_var_check — pt_ctx_reproject_var's host side under a sanitizer, as a program of its own (make reproject-var-check
+// builds it with -fsanitize=address,undefined and runs it; no device, no Python).  It drives the refusals in the header's order,
+// and runs the whole pixel the kernels compile (csrc/pt_reproject.h: reproject_var_pixel - projection and gather with moments -
+// then reproject_var_short_pixel - the spatial window) over host frames allocated to their exact size, so that the sanitizer
+// bounds every tap and every window read: a failed check or a sanitizer report ends it with a non-zero status.
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/ptrace.h"
+#include "../csrc/pt_reproject.h"
+
+namespace pt {
+static std::string g_error;
+void set_error(const std::string &m) { g_error = m; }
+}  // namespace pt
+extern "C" const char *pt_last_error(void) { return pt::g_error.c_str(); }
+
+#define CHECK(cond)                                                      \
+    do {                                                                 \
+        if (!(cond)) {                                                   \
+            fprintf(stderr, "%s:%d: %s failed\n", __FILE__, __LINE__, #cond); \
+            return 1;                                                    \
+        }                                                                \
+    } while (0)
+
+static pt_camera camera(float px, float py, float pz, float dx, float dy, float dz) {
+    const float l = sqrtf(dx * dx + dy * dy + dz * dz);
+    pt_camera c = {{px, py, pz}, {dx, dy, dz}, 0.035f, 0.036f, 1.5f};
+    if (l > 0.0f)
+        for (float &v : c.direction) v /= l;
+    return c;
+}
+
+static uint32_t lcg(uint32_t &s) { return s = s * 1664525u + 1013904223u; }
+static float unit(uint32_t &s) { return (float)(lcg(s) >> 8) * (1.0f / 16777216.0f); }
+
+struct Frames {
+    std::vector<float> color, depth, normal, hcolor, hlen, hmom, hdepth, hnormal, out, len, mom, err, splane;
+    std::vector<int32_t> id, hid;
+};
+
+// random frames in the style of the GPU test: depths on a few planes and +inf, ids -1..2, normals with zero vectors, lengths
+// with zeros and in blocks (so that some stretches are all long and some all short), moments of a colour sum in [0, 3]
+static Frames make_frames(uint32_t n, uint32_t seed) {
+    Frames f;
+    uint32_t s = seed;
+    const float planes[] = {2.0f, 6.0f, 6.25f, 9.0f, INFINITY};
+    auto fill = [&](std::vector<float> &v, size_t k) {
+        v.resize(k);
+        for (float &x : v) x = unit(s);
+    };
+    fill(f.color, 3 * (size_t)n);
+    fill(f.hcolor, 3 * (size_t)n);
+    fill(f.normal, 3 * (size_t)n);
+    fill(f.hnormal, 3 * (size_t)n);
+    for (size_t i = 0; i < 3 * (size_t)n; ++i) {
+        f.normal[i] -= 0.5f;
+        f.hnormal[i] = lcg(s) % 8u ? f.normal[i] : 0.0f;
+    }
+    f.depth.resize(n), f.hdepth.resize(n), f.hlen.resize(n), f.id.resize(n), f.hid.resize(n), f.hmom.resize(2 * (size_t)n);
+    for (uint32_t i = 0; i < n; ++i) {
+        f.depth[i] = planes[(i / 5u) % 4u == 3u ? lcg(s) % 5u : (i / 5u) % 4u];
+        f.hdepth[i] = lcg(s) % 4u ? f.depth[i] : planes[lcg(s) % 5u];
+        f.id[i] = lcg(s) % 6u ? (int32_t)((i / 7u) % 3u) : (int32_t)(lcg(s) % 4u) - 1;
+        f.hid[i] = lcg(s) % 4u ? f.id[i] : (int32_t)(lcg(s) % 4u) - 1;
+        f.hlen[i] = (i / 40u) % 3u == 0u ? 32.0f : (float)(lcg(s) % 5u) * 4.0f;
+        const float m1 = 3.0f * unit(s);
+        f.hmom[2 * (size_t)i] = m1;
+        f.hmom[2 * (size_t)i + 1] = m1 * m1 + unit(s);
+    }
+    f.out.assign(3 * (size_t)n, -1.0f);
+    f.len.assign(n, -1.0f);
+    f.mom.assign(2 * (size_t)n, -1.0f);
+    f.err.assign(n, -2.0f);
+    f.splane.assign(n, -1.0f);
+    return f;
+}
+
+// the frame as kernel B's window sees it: global planes, every read inside them or the sanitizer says so
+struct HostSrc {
+    const float *s, *z;
+    const int32_t *id;
+    int32_t W;
+    void operator()(int32_t qx, int32_t qr, float &so, int32_t &ido, float &zo) const {
+        const size_t q = (size_t)qr * (size_t)W + (size_t)qx;
+        so = s[q];
+        ido = id[q];
+        zo = z[q];
+    }
+};
+
+// both kernels' work over the whole frame, in their order: every pixel of A before any of B.  Returns the number of short pixels.
+static size_t run(const pt::ReprojectVarFrame &v) {
+    const uint32_t n = v.f.width * v.f.height;
+    for (uint32_t i = 0; i < n; ++i) pt::reproject_var_pixel(v, i);
+    const HostSrc src = {v.s_plane, v.f.depth, v.f.object_id, (int32_t)v.f.width};
+    size_t shorts = 0;
+    for (uint32_t i = 0; i < n; ++i)
+        if (v.error[i] == pt::kReprojectVarShort) {
+            v.error[i] = pt::reproject_var_short_pixel(v, src, i);
+            ++shorts;
+        }
+    return shorts;
+}
+
+int main() {
+    const pt_camera cam = camera(0.0f, -0.2f, 7.8f, 0.0f, -0.06f, -1.0f);
+    const pt_camera near_cam = camera(0.3f, -0.2f, 7.7f, -0.04f, -0.06f, -1.0f);
+    const pt_camera back = camera(0.0f, -0.2f, 7.8f, 0.0f, 0.06f, 1.0f);
+    const pt_camera aside = camera(4.0f, -0.2f, 3.0f, -1.0f, -0.06f, -0.2f);  // part of the frame behind its lens, part outside
+    const pt_camera zero = camera(0.0f, -0.2f, 7.8f, 0.0f, 0.0f, 0.0f);
+
+    // ---- the refusals, in the header's order: each call breaks one rule and every rule after it
+    {
+        float buf[4];
+        int32_t ibuf[4];
+        const float *F = buf;
+        const int32_t *I = ibuf;
+        pt::ReprojectVarFrame v;
+        const void *ctx = buf;  // never dereferenced
+        // col: the frame's own planes; hc / hl / hm: history colour (with depth and id) / length / moments; out: colour and
+        // length; om / er: moments and error
+        auto check = [&](const pt_reproject_var_params *p, uint32_t w, uint32_t h, const pt_camera *c, const float *col, const float *hc,
+                         const float *hl, const float *hm, const pt_camera *hcam, float *out, float *om, float *er, const void *cx) {
+            return pt::host::check_reproject_var(cx, w, h, p, c, col, col ? F : nullptr, col ? I : nullptr, nullptr, hcam, hc, hl, hm,
+                                                 hc, hc ? I : nullptr, nullptr, out, out, om, er, v);
+        };
+        auto refused = [&](int rc, const char *word) { return rc == PT_ERR_INVALID && pt::g_error.find(word) != std::string::npos; };
+        const pt_reproject_var_params bad_mh = {0, -1.0f, NAN, 2.0f, 0, 4, 1}, bad_dt = {0, 1.0f, INFINITY, 2.0f, 0, 4, 1},
+                                      bad_nm = {0, 1.0f, 1.0f, NAN, 0, 4, 1}, bad_nm2 = {0, 1.0f, 1.0f, -1.5f, 0, 4, 1},
+                                      bad_r = {0, 1.0f, 1.0f, -1.0f, 0, 4, 1}, bad_flags = {0, 1.0f, 1.0f, -1.0f, 9, 3, 1},
+                                      fine = {3, 8.0f, 0.1f, 1.0f, 2, 1, 0};
+        float *N = nullptr;
+        CHECK(refused(check(&bad_mh, 0, 0, nullptr, nullptr, F, nullptr, nullptr, nullptr, N, N, N, nullptr), "max_history or depth_tol"));
+        CHECK(refused(check(&bad_dt, 0, 0, nullptr, nullptr, F, nullptr, nullptr, nullptr, N, N, N, nullptr), "max_history or depth_tol"));
+        CHECK(refused(check(&bad_nm, 0, 0, nullptr, nullptr, F, nullptr, nullptr, nullptr, N, N, N, nullptr), "normal_min"));
+        CHECK(refused(check(&bad_nm2, 0, 0, nullptr, nullptr, F, nullptr, nullptr, nullptr, N, N, N, nullptr), "normal_min"));
+        CHECK(refused(check(&bad_r, 0, 0, nullptr, nullptr, F, nullptr, nullptr, nullptr, N, N, N, nullptr), "radius"));
+        CHECK(refused(check(&bad_flags, 0, 0, nullptr, nullptr, F, nullptr, nullptr, nullptr, N, N, N, nullptr), "flags"));
+        CHECK(refused(check(&fine, 0, 3, nullptr, nullptr, F, nullptr, nullptr, nullptr, N, N, N, nullptr), "width and height"));
+        CHECK(refused(check(&fine, 1u << 15, 1u << 15, nullptr, nullptr, F, nullptr, nullptr, nullptr, N, N, N, nullptr), "2^28"));
+        CHECK(refused(check(nullptr, 2, 2, nullptr, F, F, nullptr, nullptr, nullptr, buf, buf, buf, nullptr), "is NULL"));
+        CHECK(refused(check(nullptr, 2, 2, &cam, nullptr, F, nullptr, nullptr, nullptr, buf, buf, buf, nullptr), "is NULL"));
+        CHECK(refused(check(nullptr, 2, 2, &cam, F, F, nullptr, nullptr, nullptr, N, buf, buf, nullptr), "is NULL"));
+        CHECK(refused(check(nullptr, 2, 2, &cam, F, F, nullptr, nullptr, nullptr, buf, N, buf, nullptr), "is NULL"));
+        CHECK(refused(check(nullptr, 2, 2, &cam, F, F, nullptr, nullptr, nullptr, buf, buf, N, nullptr), "is NULL"));
+        CHECK(refused(check(nullptr, 2, 2, &cam, F, F, nullptr, nullptr, nullptr, buf, buf, buf, nullptr), "history"));
+        CHECK(refused(check(nullptr, 2, 2, &cam, F, nullptr, F, nullptr, nullptr, buf, buf, buf, nullptr), "history"));
+        CHECK(refused(check(nullptr, 2, 2, &cam, F, nullptr, nullptr, F, nullptr, buf, buf, buf, nullptr), "history"));
+        CHECK(refused(check(nullptr, 2, 2, &cam, F, F, F, nullptr, nullptr, buf, buf, buf, nullptr), "history"));  // no moments
+        CHECK(refused(check(nullptr, 2, 2, &cam, F, F, F, F, nullptr, buf, buf, buf, nullptr), "hist_cam"));
+        CHECK(refused(check(nullptr, 2, 2, &cam, F, F, F, F, &cam, buf, buf, buf, nullptr), "ctx"));
+        CHECK(refused(check(nullptr, 2, 2, &cam, F, nullptr, nullptr, nullptr, nullptr, buf, buf, buf, nullptr), "ctx"));
+        // accepted: the defaults are filled in, the first frame carries no history
+        CHECK(check(nullptr, 2, 2, &cam, F, F, F, F, &near_cam, buf, buf, buf, ctx) == PT_OK);
+        CHECK(v.f.wt == 1.0f && v.f.max_history == pt::kReprojectMaxHistory && v.f.depth_tol == pt::kReprojectDepthTol &&
+              v.f.normal_min == pt::kReprojectNormalMin && v.f.view.same == 0u && v.f.hist_color == F);
+        CHECK(v.radius == pt::kReprojectVarRadius && v.long_len == (float)pt::kReprojectVarMinFrames && v.s_plane == nullptr);
+        CHECK((const void *)v.hist_moments == (const void *)F && (void *)v.out_moments == (void *)buf && v.error == buf);
+        CHECK(check(&fine, 2, 2, &cam, F, F, F, F, &cam, buf, buf, buf, ctx) == PT_OK);
+        CHECK(v.f.wt == 3.0f && v.f.max_history == 8.0f && v.f.depth_tol == 0.1f && v.f.normal_min == 1.0f && v.f.view.same == 1u);
+        CHECK(v.radius == 1u && v.long_len == 6.0f);
+        CHECK(check(&fine, 2, 2, &cam, F, nullptr, nullptr, nullptr, nullptr, buf, buf, buf, ctx) == PT_OK && v.f.hist_color == nullptr &&
+              v.hist_moments == nullptr);
+    }
+
+    // ---- the whole pixel over host frames of exactly width * height: every tap and every window read inside them
+    size_t pixels = 0, blended = 0, shorts = 0, none = 0;
+    const uint32_t frames[][2] = {{1, 1}, {7, 5}, {257, 3}, {33, 25}};
+    for (const auto &s : frames) {
+        const uint32_t w = s[0], h = s[1], n = w * h;
+        for (const pt_camera *hc : {&cam, &near_cam, &aside, &back, &zero}) {
+            for (uint32_t radius = 1; radius <= 3; ++radius) {
+                for (int with_normals = 0; with_normals < 2; ++with_normals) {
+                    Frames fr = make_frames(n, w * 131u + h);
+                    const pt_reproject_var_params p = {4, 64.0f, 0.05f, 0.5f, with_normals ? 4u : 1u, radius, 0};
+                    pt::ReprojectVarFrame v;
+                    CHECK(pt::host::check_reproject_var(&fr, w, h, &p, &cam, fr.color.data(), fr.depth.data(), fr.id.data(),
+                                                        with_normals ? fr.normal.data() : nullptr, hc, fr.hcolor.data(), fr.hlen.data(),
+                                                        fr.hmom.data(), fr.hdepth.data(), fr.hid.data(),
+                                                        with_normals ? fr.hnormal.data() : nullptr, fr.out.data(), fr.len.data(),
+                                                        fr.mom.data(), fr.err.data(), v) == PT_OK);
+                    v.s_plane = fr.splane.data();
+                    shorts += run(v);
+                    for (uint32_t i = 0; i < n; ++i) {
+                        const float sum = (fr.color[3 * (size_t)i] + fr.color[3 * (size_t)i + 1]) + fr.color[3 * (size_t)i + 2];
+                        CHECK(fr.splane[i] == sum);
+                        CHECK(fr.len[i] >= 4.0f && fr.len[i] <= 64.0f);
+                        CHECK(fr.mom[2 * (size_t)i] >= 0.0f && fr.mom[2 * (size_t)i] <= 3.0f + 1e-5f && fr.mom[2 * (size_t)i + 1] >= 0.0f);
+                        CHECK((fr.err[i] >= 0.0f && fr.err[i] <= 12.0f) || (std::isinf(fr.err[i]) && fr.err[i] > 0.0f));
+                        if (std::isinf(fr.err[i])) ++none;
+                        if (fr.len[i] > 4.0f) {
+                            CHECK(fr.id[i] >= 0);
+                            ++blended;
+                        } else {
+                            CHECK(fr.mom[2 * (size_t)i] == sum && fr.mom[2 * (size_t)i + 1] == sum * sum);
+                            if (with_normals) CHECK(n == 1 ? std::isinf(fr.err[i]) : true);  // short, and a window of one pixel
+                        }
+                        ++pixels;
+                    }
+                    if (hc == &back || hc == &zero)
+                        for (uint32_t i = 0; i < n; ++i) CHECK(fr.len[i] == 4.0f);
+                }
+            }
+        }
+        // the first frame, in place: every pixel short, the colour unchanged, the moments (s, s*s)
+        Frames fr = make_frames(n, 7u);
+        pt::ReprojectVarFrame v;
+        CHECK(pt::host::check_reproject_var(&fr, w, h, nullptr, &cam, fr.color.data(), fr.depth.data(), fr.id.data(), nullptr, nullptr,
+                                            nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, fr.color.data(), fr.len.data(),
+                                            fr.mom.data(), fr.err.data(), v) == PT_OK);
+        v.s_plane = fr.splane.data();
+        const std::vector<float> before = fr.color;
+        CHECK(run(v) == n);
+        CHECK(fr.color == before);
+        for (uint32_t i = 0; i < n; ++i) {
+            CHECK(fr.len[i] == 1.0f && fr.mom[2 * (size_t)i] == fr.splane[i]);
+            CHECK(fr.err[i] >= 0.0f);
+        }
+        if (n == 1) CHECK(std::isinf(fr.err[0]));
+    }
+    CHECK(blended > pixels / 50 && shorts > pixels / 50 && shorts < pixels && none > 0);
+    printf("reproject_var_check: ok (%zu pixels, %zu blended, %zu short, %zu without an estimate)\n", pixels, blended, shorts, none);
+    return 0;
+}

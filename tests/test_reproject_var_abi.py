@@ -1,0 +1,417 @@
+"""pt_ctx_reproject_var at the ABI and its contract, without a device.
+
+- The header declares pt_reproject_var_params (28 bytes) and the two functions and states the contract; the library exports
+  them; PT_ABI_VERSION is still 5; the Rust shim and the Python binding mirror them.
+- Every refusal, in the header's order, with a NULL context (the last thing checked): none needs a device.
+- The defaults are the header's text and the CPU study's choice.
+- Properties of the restatement (tests/reproject_var_ref.py): the temporal variance of a still camera, the spatial estimate
+  against numpy's variance, what removes a window tap, "no estimate".
+- make reproject-var-check: the stand-alone host program under AddressSanitizer and UBSan exits 0.
+The GPU side is tests/test_gpu_reproject_var.py."""
+import ctypes as C
+import importlib
+import json
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import kats_camera as kc
+import ptlib
+import reproject_ref as ref
+import reproject_var_ref as rv
+from reproject_ref import F32, I32
+from reproject_var_ref import PtReprojectVarParams
+
+ROOT = ptlib.ROOT
+PT_ERR_INVALID = -1
+CAM = kc.CORNELL_CAM
+REL = 1e-5  # the binary32 rounding of a handful of operations
+
+
+def _header(strip=True):
+    text = open(os.path.join(ROOT, "include", "ptrace.h")).read()
+    return re.sub(r"/\*.*?\*/", "", text, flags=re.S) if strip else text
+
+
+def _doc():
+    text = _header(strip=False)
+    at = text.index("pt_ctx_reproject_var is pt_ctx_reproject plus")
+    return " ".join(text[at:text.index("typedef struct pt_reproject_var_params", at)].replace("*", " ").split())
+
+
+@pytest.fixture(scope="module")
+def L():
+    return rv.bind(ptlib.product())
+
+
+# ---------------------------------------------------------------------------------------------------------- the ABI
+NAMES = ["ctx", "width", "height", "params", "cam", "d_color", "d_depth", "d_object_id", "d_normal", "hist_cam", "d_hist_color",
+         "d_hist_len", "d_hist_moments", "d_hist_depth", "d_hist_object_id", "d_hist_normal", "d_out_color", "d_out_len",
+         "d_out_moments", "d_error", "hip_stream"]
+FIELDS = [("uint32_t", "weight"), ("float", "max_history"), ("float", "depth_tol"), ("float", "normal_min"), ("uint32_t", "min_frames"),
+          ("uint32_t", "radius"), ("uint32_t", "flags")]
+
+
+def test_header_declares_them():
+    h = _header()
+    body = re.search(r"typedef struct pt_reproject_var_params \{(.*?)\} pt_reproject_var_params;", h, flags=re.S).group(1)
+    fields = [(t, n.strip()) for t, names in re.findall(r"\b(uint32_t|float)\s+([\w\s,]+);", body) for n in names.split(",")]
+    assert fields == FIELDS
+    assert [n for n, _ in PtReprojectVarParams._fields_] == [n for _, n in fields]
+    assert C.sizeof(PtReprojectVarParams) == 28
+    m = re.search(r"\bint pt_ctx_reproject_var\((.*?)\);", h, flags=re.S)
+    params = [q.strip() for q in m.group(1).split(",")]
+    assert "".join("p" if "*" in q else "i" for q in params) == "pii" + "p" * 18
+    assert [q.split()[-1].lstrip("*") for q in params] == NAMES
+    assert re.search(r"\bint pt_reproject_var_defaults\(\s*pt_reproject_var_params \*\w+\);", h)
+    assert re.search(r"#define PT_ABI_VERSION 5\b", h)  # symbols were added, nothing changed
+
+
+def test_header_states_the_contract():
+    def norm(t):
+        return " ".join(t.replace("*", " ").split())
+
+    doc = _doc()
+    for phrase in ("THE ARITHMETIC", "pt_ctx_reproject's, bit for bit", "s = (color[idx][0] + color[idx][1]) + color[idx][2]",
+                   "q2 = s*s", "m1 = s, m2 = q2", "a1 = a1 + hist_m[q][0]*b", "a2 = a2 + hist_m[q][1]*b", "h1 = a1/bsum", "k = wt/n'",
+                   "m1 = h1 + (s - h1)*k", "m2 = h2 + (q2 - h2)*k", "vt = pos(m2 - m1*m1)", "k = wt / len_out",
+                   "long = len_out >= (float)min_frames * wt", "on the host in binary32", "dy = -R..R outside, dx = -R..R inside",
+                   "skipped, not clamped", "The centre is always taken", "object_id[q] == object_id[idx]", "object_id[idx] < 0",
+                   "|depth[idx] - depth[q]| <= depth_tol * max(depth[idx], depth[q])", "S1 = S1 + s_q", "S2 = S2 + s_q*s_q",
+                   "cnt = cnt + 1", "INPUT colour", "mean = S1/(float)cnt", "vs = pos(S2/(float)cnt - mean*mean)", "v = max(vs, vt)",
+                   "cnt < 2", "e = +inf", "v = vt", "e = sqrt(v*k) / sqrt(2^-6 + ((out[0] + out[1]) + out[2]))", "if !(e < 12), e = 12",
+                   "2 floats per pixel", "all five history pointers", "d_out_color may be d_color",
+                   "d_out_moments and d_error may alias no input and no other output", "4 B per pixel", "freed by pt_ctx_destroy",
+                   "outside the ray-queue budget", "changes no other state of the context", "+inf means \"no estimate\"",
+                   "THE NOISE ESTIMATE", "checked in this order", "params == NULL stands for all zero",
+                   "profiles/reproject_var_cpu_study.json"):
+        assert norm(phrase) in doc, phrase
+    order = ["max_history or depth_tol that is negative", "normal_min outside", "radius above 3", "flags != 0", "width or height 0",
+             "above 2^28", "NULL cam, d_color", "partial set of the five history", "with NULL hist_cam", "NULL ctx"]
+    where = [doc.index(p) for p in order]
+    assert where == sorted(where)
+    # pt_ctx_reproject's own section is as it was
+    text = _header(strip=False)
+    assert "No scratch is taken" in text[text.index("pt_ctx_reproject carries"):text.index("typedef struct pt_reproject_params")]
+
+
+def test_library_exports_them_and_the_abi_version_stays(L):
+    out = subprocess.check_output(["nm", "-D", "--defined-only", ptlib.PRODUCT_SO], text=True)
+    exported = {line.split()[-1] for line in out.splitlines() if line.strip()}
+    assert {"pt_ctx_reproject_var", "pt_reproject_var_defaults", "pt_ctx_reproject", "pt_reproject_defaults"} <= exported
+    assert L.pt_abi_version() == 5
+
+
+def test_defaults_are_what_the_header_and_the_study_say(L):
+    d = rv.defaults(L)
+    assert {k: d[k] for k in ("weight", "max_history", "depth_tol", "normal_min")} == ref.defaults(L)
+    assert 1 <= d["min_frames"] and 1 <= d["radius"] <= 3
+    m = re.search(r"weight 1, max_history (\S+), depth_tol 2\^-(\d+) \((\S+)\), normal_min (\S+) \(pt_reproject_defaults' three\), "
+                  r"min_frames (\d+), radius (\d+), flags 0", _doc())
+    assert (float(m.group(1)), 2.0 ** -int(m.group(2)), float(m.group(3)), float(F32(m.group(4)))) == (
+        d["max_history"], d["depth_tol"], d["depth_tol"], d["normal_min"])
+    assert (int(m.group(5)), int(m.group(6))) == (d["min_frames"], d["radius"])
+    study = json.load(open(os.path.join(ROOT, "profiles", "reproject_var_cpu_study.json")))
+    assert (study["chosen"]["min_frames"], study["chosen"]["radius"]) == (d["min_frames"], d["radius"])
+    best = min((g for g in study["grid"] if g["no_estimate"] == 0), key=lambda g: g["mean_ratio"])
+    assert {k: best[k] for k in ("min_frames", "radius", "sigma_var")} == study["chosen"]
+    # the sigma_var the study chose is the one INTEGRATION.md names for the loop
+    text = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    assert re.search(r"sigma_var\s*=\s*%g\b" % study["chosen"]["sigma_var"], text)
+    assert L.pt_reproject_var_defaults(None) == PT_ERR_INVALID
+
+
+def test_rust_shim_mirrors_them():
+    rust = re.sub(r"//[^\n]*", "", open(os.path.join(ROOT, "ffi", "hip.rs")).read())
+    body = re.search(r"#\[repr\(C\)\]\s*#\[derive\([^)]*\)\]\s*pub struct PtReprojectVarParams \{(.*?)\n\}", rust, flags=re.S).group(1)
+    assert re.findall(r"pub (\w+): (\w+),", body) == [(n, "u32" if t == "uint32_t" else "f32") for t, n in FIELDS]
+    ext = re.search(r'extern "C" \{(.*?)\n\}', rust, flags=re.S).group(1)
+    m = re.search(r"pub fn pt_ctx_reproject_var\((.*?)\)\s*->\s*i32;", ext, flags=re.S)
+    params = [(q.split(":", 1)[0].strip(), q.split(":", 1)[1].strip()) for q in m.group(1).split(",") if ":" in q]
+    assert [n for n, _ in params] == NAMES
+    assert [t for _, t in params] == ["*mut PtCtx", "u32", "u32", "*const PtReprojectVarParams", "*const PtCamera", "*const f32",
+                                      "*const f32", "*const i32", "*const f32", "*const PtCamera", "*const f32", "*const f32",
+                                      "*const f32", "*const f32", "*const i32", "*const f32", "*mut f32", "*mut f32", "*mut f32",
+                                      "*mut f32", "*mut c_void"]
+    assert re.search(r"pub fn pt_reproject_var_defaults\(out: \*mut PtReprojectVarParams\) -> i32;", ext)
+    frame = re.search(r"pub struct ReprojectFrame \{(.*?)\n\}", rust, flags=re.S).group(1)
+    assert "pub d_moments: *mut f32" in frame
+    # the variant shows the pointer swap: the outputs and this frame's guides become the history, nothing is copied
+    helper = rust[rust.index("pub fn reproject_var_and_swap("):]
+    helper = helper[:helper.index("\n}\n")]
+    assert "pt_ctx_reproject_var(" in helper and "std::mem::swap(" in helper and "pt_device_download" not in helper
+    assert "hist.d_moments" in helper and "cur.d_moments" in helper and "d_error" in helper
+
+
+def test_python_binding_offers_them():
+    pkg = importlib.import_module("path-tracer-rust_amd")
+    assert list(pkg.pt_reproject_var_params._fields_) == list(PtReprojectVarParams._fields_)
+    assert C.sizeof(pkg.pt_reproject_var_params) == 28
+    assert callable(pkg.Context.reproject_var)
+    d = pkg.reproject_var_defaults()
+    assert set(d) == {"weight", "max_history", "depth_tol", "normal_min", "min_frames", "radius"} and d["weight"] == 1
+    assert {k: d[k] for k in pkg.reproject_defaults()} == pkg.reproject_defaults()
+    assert "moments" in pkg.Context.reproject_var.__doc__
+    assert len(pkg.lib().pt_ctx_reproject_var.argtypes) == len(NAMES)
+
+
+# -------------------------------------------------------------------------------------------------------- refusals
+def test_refusals_in_order_without_a_device(L):
+    """Each call breaks one rule and every rule checked AFTER it: the message names the first.  The context is NULL throughout."""
+    p = [C.c_void_p(0x1000 * (i + 1)) for i in range(16)]  # never dereferenced: every call is refused before a device is touched
+    cam = ref.pt_camera(CAM)
+    BIG = 1 << 15  # BIG * BIG = 2^30 > 2^28
+    P = PtReprojectVarParams
+
+    def call(w, h, prm, cam_, cur, hist_cam, hist, outs):
+        """cur: (color, depth, id, normal); hist: (color, len, moments, depth, id, normal); outs: (color, len, moments, error)"""
+        rc = L.pt_ctx_reproject_var(None, w, h, C.byref(prm) if prm is not None else None, C.byref(cam_) if cam_ is not None else None,
+                                    *cur, C.byref(hist_cam) if hist_cam is not None else None, *hist, *outs, None)
+        return rc, L.pt_last_error().decode()
+
+    none4, none6 = (None,) * 4, (None,) * 6
+    cur = (p[0], p[1], p[2], p[3])
+    hist = (p[4], p[5], p[6], p[7], p[8], p[9])
+    outs = (p[10], p[11], p[12], p[13])
+    part = (p[4], None, None, None, None, None)  # a partial history: broken in every call before the history's own turn
+    nan, inf = float("nan"), float("inf")
+    cases = [
+        (call(0, 0, P(0, -1.0, 0, 2.0, 0, 4, 6), None, none4, None, none6, none4), "max_history or depth_tol"),
+        (call(0, 0, P(0, inf, 0, 2.0, 0, 4, 6), None, none4, None, none6, none4), "max_history or depth_tol"),
+        (call(0, 0, P(0, nan, 0, 2.0, 0, 4, 6), None, none4, None, none6, none4), "max_history or depth_tol"),
+        (call(0, 0, P(0, 8.0, -0.5, 2.0, 0, 4, 6), None, none4, None, none6, none4), "max_history or depth_tol"),
+        (call(0, 0, P(0, 8.0, nan, 2.0, 0, 4, 6), None, none4, None, none6, none4), "max_history or depth_tol"),
+        (call(0, 0, P(0, 8.0, 0.1, 1.5, 0, 4, 6), None, none4, None, none6, none4), "normal_min"),
+        (call(0, 0, P(0, 8.0, 0.1, -1.5, 0, 4, 6), None, none4, None, none6, none4), "normal_min"),
+        (call(0, 0, P(0, 8.0, 0.1, nan, 0, 4, 6), None, none4, None, none6, none4), "normal_min"),
+        (call(0, 0, P(0, 8.0, 0.1, -1.0, 0, 4, 6), None, none4, None, none6, none4), "radius"),
+        (call(0, 0, P(0, 8.0, 0.1, 1.0, 0, 0xFFFFFFFF, 6), None, none4, None, none6, none4), "radius"),
+        (call(0, 0, P(0, 8.0, 0.1, -1.0, 99, 3, 6), None, none4, None, none6, none4), "flags"),
+        (call(0, 5, P(0, 8.0, 0.1, 1.0, 99, 3, 0), None, none4, None, none6, none4), "width and height"),
+        (call(5, 0, None, None, none4, None, none6, none4), "width and height"),
+        (call(BIG, BIG, None, None, none4, None, none6, none4), "2^28"),
+        (call(4, 4, None, None, cur, None, part, outs), "is NULL"),
+        (call(4, 4, None, cam, (None,) + cur[1:], None, part, outs), "is NULL"),
+        (call(4, 4, None, cam, (p[0], None, p[2], p[3]), None, part, outs), "is NULL"),
+        (call(4, 4, None, cam, (p[0], p[1], None, p[3]), None, part, outs), "is NULL"),
+        (call(4, 4, None, cam, cur, None, part, (None,) + outs[1:]), "is NULL"),
+        (call(4, 4, None, cam, cur, None, part, (p[10], None, p[12], p[13])), "is NULL"),
+        (call(4, 4, None, cam, cur, None, part, (p[10], p[11], None, p[13])), "is NULL"),
+        (call(4, 4, None, cam, cur, None, part, (p[10], p[11], p[12], None)), "is NULL"),
+        (call(4, 4, None, cam, cur, None, part, outs), "history"),
+        (call(4, 4, None, cam, cur, None, (None, p[5], p[6], p[7], p[8], None), outs), "history"),
+        (call(4, 4, None, cam, cur, None, (p[4], None, p[6], p[7], p[8], p[9]), outs), "history"),
+        (call(4, 4, None, cam, cur, None, (p[4], p[5], None, p[7], p[8], p[9]), outs), "history"),  # pt_ctx_reproject's full set
+        (call(4, 4, None, cam, cur, None, (p[4], p[5], p[6], None, p[8], p[9]), outs), "history"),
+        (call(4, 4, None, cam, cur, None, (p[4], p[5], p[6], p[7], None, p[9]), outs), "history"),
+        (call(4, 4, None, cam, cur, None, (None, None, p[6], None, None, None), outs), "history"),  # the moments alone
+        (call(4, 4, None, cam, cur, None, hist, outs), "hist_cam"),
+        (call(4, 4, None, cam, cur, cam, hist, outs), "ctx"),
+        (call(4, 4, P(3, 8.0, 0.1, -1.0, 7, 3, 0), cam, (p[0], p[1], p[2], None), cam, hist[:5] + (None,), outs), "ctx"),
+        (call(4, 4, None, cam, cur, None, none6, outs), "ctx"),                  # the first frame: hist_cam is not asked for
+        (call(4, 4, None, cam, cur, None, (None,) * 5 + (p[9],), outs), "ctx"),  # ... and a lone history normal is not a history
+        (call(1 << 14, 1 << 14, None, cam, cur, cam, hist, outs), "ctx"),        # 2^28 pixels exactly are allowed
+    ]
+    for i, ((rc, msg), word) in enumerate(cases):
+        assert rc == PT_ERR_INVALID and word in msg, (i, rc, msg, word)
+
+
+# -------------------------------------------------------------------------------------- properties of the restatement
+def _guides(n, oid=1, depth=6.0):
+    return dict(depth=np.full(n, depth, dtype=F32), object_id=np.full(n, oid, dtype=I32),
+                normal=np.tile(np.array([0.0, 0.0, 1.0], dtype=F32), (n, 1)))
+
+
+def _still(w, h, colors, wt, min_frames, radius=2):
+    """the outputs and parts of each call of a still camera with unchanging guides fed `colors` in turn"""
+    g = _guides(w * h)
+    hist = None
+    rows = []
+    for c in colors:
+        kw = {} if hist is None else dict(hist_cam=CAM, hist_color=hist[0], hist_len=hist[1], hist_moments=hist[2],
+                                          hist_depth=g["depth"], hist_object_id=g["object_id"], hist_normal=g["normal"])
+        hist = rv.reproject_var(w, h, CAM, c, g["depth"], g["object_id"], g["normal"], weight=wt, min_frames=min_frames, radius=radius,
+                                parts=True, **kw)
+        rows.append(hist)
+    return rows
+
+
+def test_ref_first_frame_moments_are_s_and_s_squared():
+    rng = np.random.default_rng(1)
+    c = rng.random((35, 3)).astype(F32)
+    g = _guides(35)
+    out, ln, mom, e = rv.reproject_var(7, 5, CAM, c, g["depth"], g["object_id"], weight=4)
+    s = (c[:, 0] + c[:, 1]) + c[:, 2]
+    assert out.tobytes() == c.tobytes() and (ln == 4).all()
+    assert mom.tobytes() == np.stack([s, s * s], axis=1).tobytes()
+    assert np.isfinite(e).all() and (e > 0).all() and (e <= 12).all()
+
+
+def test_ref_still_camera_same_colour_has_no_variance():
+    """the same colour every frame: m1 = s and m2 = s*s exactly, so vt = 0 in every frame, and e = 0 once the history is long;
+    while it is short the spatial estimate stands in and e > 0"""
+    w, h, wt, mf = 7, 5, 2, 3
+    rng = np.random.default_rng(2)
+    c = rng.random((w * h, 3)).astype(F32)
+    for k, (out, ln, mom, e, parts) in enumerate(_still(w, h, [c] * 5, wt, mf), 1):
+        assert (ln == k * wt).all() and (parts["vt"] == 0).all(), k
+        assert parts["long"].all() == (k >= mf)
+        if k >= mf:
+            assert (e == 0).all(), k
+        else:
+            assert (e > 0).all() and not parts["long"].any(), k
+
+
+def test_ref_still_camera_two_colours_give_the_running_means_variance():
+    """two colours alternately: after k frames m1 and m2 are the plain means of s and s*s over the k frames (the running-mean
+    weights wt / (j * wt)), so vt is their variance - computed here in binary64 from the colours - and, once long,
+    e = sqrt(vt / k) / sqrt(2^-6 + sum(out)).  Within 1e-5 relative: the colours are far apart (s near 0.3 and near 2.5), so the
+    subtraction m2 - m1*m1 cancels less than two bits."""
+    w, h, wt, mf = 7, 5, 4, 2
+    rng = np.random.default_rng(3)
+    a = (rng.random((w * h, 3)) * 0.2).astype(F32)
+    b = (rng.random((w * h, 3)) * 0.3 + 0.7).astype(F32)
+    colors = [a if k % 2 == 0 else b for k in range(7)]
+    s64 = [c.astype(np.float64).sum(axis=1) for c in colors]
+    for k, (out, ln, mom, e, parts) in enumerate(_still(w, h, colors, wt, mf), 1):
+        assert (ln == k * wt).all()
+        m1 = np.mean(s64[:k], axis=0)
+        var = np.mean([s * s for s in s64[:k]], axis=0) - m1 * m1
+        if k == 1:
+            assert (parts["vt"] == 0).all()
+            continue
+        assert np.abs(parts["vt"] / var - 1).max() <= REL, (k, np.abs(parts["vt"] / var - 1).max())
+        assert parts["long"].all()
+        mean_out = np.mean([c.astype(np.float64) for c in colors[:k]], axis=0).sum(axis=1)
+        want = np.sqrt(var / k) / np.sqrt(2.0 ** -6 + mean_out)
+        assert np.abs(e / want - 1).max() <= REL, (k, np.abs(e / want - 1).max())
+
+
+@pytest.mark.parametrize("radius", [1, 2, 3])
+def test_ref_first_frame_spatial_estimate_is_the_windows_variance(radius):
+    """one id, one depth, the first frame: vs is numpy's variance (binary64) of s over the window clipped to the frame, and
+    e = sqrt(vs) / sqrt(2^-6 + s).  The colours are near 0 or near 1 per channel, so s spreads over [0, 3] and S2/cnt - mean^2
+    cancels about two bits of at most 49 accumulated roundings."""
+    w, h = 9, 8
+    n = w * h
+    rng = np.random.default_rng(10 + radius)
+    c = (rng.integers(0, 2, (n, 3)) * 0.9 + rng.random((n, 3)) * 0.1).astype(F32)
+    g = _guides(n)
+    out, ln, mom, e, parts = rv.reproject_var(w, h, CAM, c, g["depth"], g["object_id"], g["normal"], weight=1, min_frames=2,
+                                              radius=radius, parts=True)
+    s = c.astype(np.float64).sum(axis=1).reshape(h, w)
+    want = np.zeros((h, w))
+    cnt = np.zeros((h, w), dtype=np.int64)
+    for r in range(h):
+        for x in range(w):
+            win = s[max(0, r - radius):r + radius + 1, max(0, x - radius):x + radius + 1]
+            want[r, x], cnt[r, x] = np.var(win), win.size
+    assert (parts["cnt"].reshape(h, w) == cnt).all()
+    assert cnt.min() == (radius + 1) ** 2 and cnt.max() == min(2 * radius + 1, w) * min(2 * radius + 1, h)
+    rel = np.abs(parts["vs"].reshape(h, w) / want - 1).max()
+    assert rel <= REL, rel
+    assert not parts["long"].any() and (parts["vt"] == 0).all()
+    want_e = np.sqrt(want) / np.sqrt(2.0 ** -6 + s)
+    assert np.abs(e.reshape(h, w) / want_e - 1).max() <= REL
+
+
+def test_ref_what_removes_a_window_tap():
+    """each of another id, a depth beyond the tolerance and the frame's edge removes a tap - the count of every pixel that had it
+    in its window drops by one - and nothing else does; equal negative ids are taken whatever the depths"""
+    w, h, R = 9, 7, 2
+    n = w * h
+    rng = np.random.default_rng(4)
+    c = rng.random((n, 3)).astype(F32)
+    s = rv.s_of(c)
+    g = _guides(n)
+    full = (2 * R + 1) ** 2
+    _, cnt = rv.spatial(w, h, s, g["object_id"], g["depth"], R, 0.05)
+    cnt = cnt.reshape(h, w)
+    xs, rs = np.arange(w), np.arange(h)
+    inside = np.outer(np.minimum(rs, R) + np.minimum(h - 1 - rs, R) + 1, np.minimum(xs, R) + np.minimum(w - 1 - xs, R) + 1)
+    assert (cnt == inside).all() and cnt[h // 2, w // 2] == full and cnt[0, 0] == (R + 1) ** 2  # the edge removes taps
+    q = (h // 2, w // 2)
+    near = np.zeros((h, w), bool)
+    near[q[0] - R:q[0] + R + 1, q[1] - R:q[1] + R + 1] = True
+    near[q] = False
+    for key, value in (("object_id", 2), ("object_id", -1), ("depth", 6.0 * 1.06), ("depth", 6.0 / 1.06), ("depth", np.nan)):
+        broken = dict(g, **{key: g[key].copy()})
+        broken[key][q[0] * w + q[1]] = value
+        vs, got = rv.spatial(w, h, s, broken["object_id"], broken["depth"], R, 0.05)
+        got = got.reshape(h, w)
+        assert (got[near] == cnt[near] - 1).all() and (got[~near & (np.arange(n).reshape(h, w) != q[0] * w + q[1])] ==
+                                                        cnt[~near & (np.arange(n).reshape(h, w) != q[0] * w + q[1])]).all(), (key, value)
+        assert got[q] == 1, (key, value)  # the centre is always taken, and alone here
+    # within the tolerance nothing is removed
+    fine = g["depth"].copy()
+    fine[q[0] * w + q[1]] = 6.0 * 1.04
+    assert (rv.spatial(w, h, s, g["object_id"], fine, R, 0.05)[1].reshape(h, w) == cnt).all()
+    # a frame of misses: equal negative ids are taken without a depth test
+    miss = np.full(n, -1, dtype=I32)
+    depths = np.where(rng.random(n) < 0.5, np.inf, rng.random(n) * 9).astype(F32)
+    assert (rv.spatial(w, h, s, miss, depths, R, 0.05)[1].reshape(h, w) == cnt).all()
+    # the sums are of the taken taps only: the variance of a pixel whose neighbours are all removed is that of one value, 0
+    alone = g["object_id"].copy()
+    alone[q[0] * w + q[1]] = 7
+    vs, got = rv.spatial(w, h, s, alone, g["depth"], R, 0.05)
+    assert got[q[0] * w + q[1]] == 1 and vs[q[0] * w + q[1]] == 0
+
+
+def test_ref_fewer_than_two_taps_is_no_estimate():
+    g = _guides(1)
+    c = np.array([[0.2, 0.3, 0.4]], dtype=F32)
+    assert rv.reproject_var(1, 1, CAM, c, g["depth"], g["object_id"], weight=1, min_frames=2)[3][0] == np.inf
+    assert rv.reproject_var(1, 1, CAM, c, g["depth"], g["object_id"], weight=1, min_frames=1)[3][0] == 0  # long: vt = 0
+    # a pixel alone with its id in a larger frame: +inf while short, its neighbours finite
+    w, h = 7, 5
+    rng = np.random.default_rng(5)
+    c = rng.random((w * h, 3)).astype(F32)
+    g = _guides(w * h)
+    g["object_id"][17] = 5
+    e = rv.reproject_var(w, h, CAM, c, g["depth"], g["object_id"], weight=1, min_frames=2, radius=3)[3]
+    assert e[17] == np.inf and np.isfinite(np.delete(e, 17)).all()
+    # and the filter reads +inf as its largest value: denoise_var's contract (ev = 12 for +inf) - nothing to do here
+
+
+def test_ref_error_is_capped_at_12():
+    """a pixel that is almost black with a window of bright neighbours: sqrt(v*k) / sqrt(2^-6 + s) would exceed 12"""
+    w, h = 5, 5
+    c = np.zeros((w * h, 3), dtype=F32)
+    c[::2] = 2.0
+    c[12] = 0.0
+    g = _guides(w * h)
+    e = rv.reproject_var(w, h, CAM, c, g["depth"], g["object_id"], weight=1, min_frames=2, radius=2)[3]
+    assert e[12] == 12 and (e <= 12).all()
+
+
+# ------------------------------------------------------------------------------------- the documents and the profiles
+def test_documents_quote_the_timing_profile():
+    """profiles/reproject_var_timing.json is committed, holds both sizes with the three measurements and a verdict against the
+    steady-state budget, and README, DESIGN and INTEGRATION quote it: the steady-state ratio to two decimals with its HIT or
+    MISSES in README and DESIGN, the file's name in all three, and no template token left anywhere"""
+    prof = json.load(open(os.path.join(ROOT, "profiles", "reproject_var_timing.json")))
+    docs = {name: " ".join(open(os.path.join(ROOT, name)).read().split()) for name in ("README.md", "DESIGN.md", "INTEGRATION.md")}
+    assert set(prof["cases"]) == {"1024x768", "4096x4096"}
+    for name, text in docs.items():
+        assert "TIMING_" not in text and "profiles/reproject_var_timing.json" in text, name
+    for size, case in prof["cases"].items():
+        for key in ("reproject", "steady", "first_frame"):
+            assert case[key]["ms_median"] > 0
+        assert case["steady"]["share_long"] == 1.0 and case["first_frame"]["share_short"] == 1.0
+        assert case["budget"] == ("HIT" if case["steady_over_reproject"] <= 1.5 else "MISSES")
+        quote = "%.2f" % case["steady_over_reproject"]
+        for name in ("README.md", "DESIGN.md"):
+            assert re.search(r"%s\b.{0,40}?%s" % (re.escape(quote), case["budget"]), docs[name]), (name, size, quote, case["budget"])
+        assert "%.2f" % case["first_frame_over_reproject"] in docs["DESIGN.md"], size
+
+
+# ------------------------------------------------------------------------------------------- the stand-alone program
+def test_make_reproject_var_check(tmp_path):
+    """the host side - refusals, projection, gather with moments, spatial window - over buffers of the exact size under
+    AddressSanitizer and UBSan, as a program of its own: no device, nothing loaded into this process"""
+    r = subprocess.run(["make", "-C", ptlib.PKG, "reproject-var-check", "B=%s" % tmp_path], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    assert "reproject_var_check: ok" in r.stdout
