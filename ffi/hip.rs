@@ -122,6 +122,15 @@ pub struct PtReprojectVarParams {
     pub flags: u32,
 }
 
+// pt_ctx_upsample's parameters; a zero field = the library's default (pt_upsample_defaults)
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct PtUpsampleParams {
+    pub depth_tol: f32,
+    pub normal_min: f32,
+    pub flags: u32,
+}
+
 // pt_ctx_denoise's parameters; a zero field = the library's default (pt_denoise_defaults)
 #[repr(C)]
 #[derive(Clone, Copy, Default, Debug)]
@@ -446,6 +455,30 @@ extern "C" {
         pr: *mut f32,
         zexp: *mut f32,
     ) -> i32;
+    // a colour frame traced at lo_width x lo_height filled in at width x height through the first-hit guides of both sizes: the
+    // viewport traces a quarter of the paths while the camera moves ("pixel size" 2)
+    pub fn pt_upsample_defaults(out: *mut PtUpsampleParams) -> i32;
+    pub fn pt_ctx_upsample(
+        ctx: *mut PtCtx,
+        width: u32,
+        height: u32,
+        lo_width: u32,
+        lo_height: u32,
+        params: *const PtUpsampleParams,
+        d_lo_color: *const f32,
+        d_lo_depth: *const f32,
+        d_lo_object_id: *const i32,
+        d_lo_normal: *const f32,
+        d_lo_albedo: *const f32,
+        d_depth: *const f32,
+        d_object_id: *const i32,
+        d_normal: *const f32,
+        d_albedo: *const f32,
+        d_out_color: *mut f32,
+        d_out_weight: *mut f32,
+        hip_stream: *mut c_void,
+    ) -> i32;
+    pub fn pt_upsample_tap_host(size: u32, lo_size: u32, coord: u32, first: *mut i32, frac: *mut f32) -> i32;
     pub fn pt_write_pfm(path: *const c_char, data: *const f32, width: u32, height: u32, channels: u32) -> i32;
     pub fn pt_device_malloc(device: i32, bytes: usize, out: *mut *mut c_void) -> i32;
     pub fn pt_device_free(device: i32, p: *mut c_void) -> i32;
@@ -594,6 +627,31 @@ pub fn reproject_var_and_swap(
         std::mem::swap(cur, hist);
     }
     rc
+}
+
+/// The first-hit guides of one frame in device memory (pt_ctx_render_aov), and for the low-resolution side the colour traced
+/// at that size (pt_ctx_render); d_color is not read on the full-resolution side.  d_normal and d_albedo may be null.
+pub struct UpsampleGuides {
+    pub width: u32,
+    pub height: u32,
+    pub d_color: *const f32,
+    pub d_depth: *const f32,
+    pub d_object_id: *const i32,
+    pub d_normal: *const f32,
+    pub d_albedo: *const f32,
+}
+
+/// `lo` traced at a fraction of the resolution, filled in at `full`'s size through the guides of both (pt_ctx_upsample, the
+/// library's defaults): `d_out_color` - full.width * full.height * 3 floats, no part of either side - is the frame that goes
+/// on to reproject_var_and_swap with `weight` = the samples per pixel `lo` was traced with.
+pub fn upsample_into(ctx: *mut PtCtx, lo: &UpsampleGuides, full: &UpsampleGuides, d_out_color: *mut f32) -> i32 {
+    unsafe {
+        pt_ctx_upsample(
+            ctx, full.width, full.height, lo.width, lo.height, std::ptr::null(), lo.d_color, lo.d_depth, lo.d_object_id,
+            lo.d_normal, lo.d_albedo, full.d_depth, full.d_object_id, full.d_normal, full.d_albedo, d_out_color,
+            std::ptr::null_mut(), std::ptr::null_mut(),
+        )
+    }
 }
 
 /// The window a preview is shown in: its size in pixels and the bytes the canvas draws, width * height * 4 (r, g, b, 255),

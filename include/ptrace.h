@@ -916,6 +916,74 @@ int pt_ctx_reproject_var(pt_ctx *ctx, uint32_t width, uint32_t height, const pt_
                          float *d_out_color, float *d_out_len, float *d_out_moments, float *d_error,
                          void *hip_stream);
 
+/* ---- tracing at low resolution and filling the frame in through the guides ---------------------------------------------
+ * pt_ctx_upsample fills a frame of width x height pixels from a colour frame traced at lo_width x lo_height: a joint bilateral
+ * upsampler (Kopf et al. 2007) over the first-hit guides of BOTH sizes.  The paths, about nine intersections per sample, are
+ * traced at a fraction of the resolution; the guides, one intersection per sample, at full resolution, so edges stay where they
+ * are.  Its tap tests are pt_ctx_reproject's: object id, relative depth, normal cosine.  A pure image-space call on device
+ * buffers; a viewport's loop is pt_ctx_render + pt_ctx_render_aov at the low size, pt_ctx_render_aov at the full size,
+ * pt_ctx_upsample, then pt_ctx_reproject_var -> pt_ctx_denoise_var -> pt_ctx_present as before.
+ * - Buffers: device pointers to whole frames in framebuffer order - what pt_ctx_render / pt_ctx_render_aov write for a cfg
+ *   without a band and without chunks.  The d_lo_ planes hold lo_width * lo_height pixels, rendered with the SAME camera and
+ *   scene at that size (the sensor does not depend on the pixel counts: both frames see the same picture); the others hold
+ *   width * height pixels.  Colour, normal and albedo 3 floats per pixel; depth and weight 1 float; object id 1 int32.  Any
+ *   sizes may be combined: smaller, equal or larger on either axis.
+ * - Optional guides: the normal test runs only when both normals are given; demodulation runs only when both albedos are given.
+ * - d_out_weight (may be NULL) receives the sum of the bilinear weights of the taps that passed the tests: 0 where none did
+ *   and the fallback was used - "how sure" the pixel is.
+ * - Aliasing: no output may alias any input or the other output.
+ * - `hip_stream` as for pt_ctx_render (NULL = the context's own stream); blocking.  No scene is needed.  No scratch is taken.
+ *   The call changes no state of the context.
+ * - PT_ERR_INVALID, all refused before any device is touched, checked in this order: a depth_tol that is negative or not
+ *   finite; normal_min outside [-1, 1] or NaN; flags != 0; one of the four sizes 0; one of the four sizes above 2^14 (16384:
+ *   with that bound the integers of step 1 fit 32 bits and frac never reaches 1); NULL d_lo_color, d_lo_depth, d_lo_object_id,
+ *   d_depth, d_object_id or d_out_color; NULL ctx.  PT_ERR_HIP: a HIP call failed.  params == NULL stands for all zero.
+ * - pt_upsample_defaults fills in the values a zero field stands for: depth_tol 2^-2 (0.25), normal_min 0.95, flags 0.  They
+ *   were chosen by the CPU study recorded in profiles/upsample_cpu_study.json.
+ *
+ * THE ARITHMETIC.  The rules are pt_ctx_denoise's: every operation is IEEE binary32 + - * /, correctly rounded and never
+ * contracted, in the order the parentheses give.  max(a, b) = a > b ? a : b; |v| is v with its sign bit cleared;
+ * clamp(v) = v < 0 ? 0 : (v > 1 ? 1 : v); dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z; N(.) is pt_ctx_denoise's normalised
+ * normal, word for word; m_c(.) is pt_ctx_denoise's demodulation factor, albedo[c] > 2^-6 ? albedo[c] : 1 - and 1 for every
+ * channel unless BOTH albedo planes are given.  W, H are the frame's size and w, h the low-resolution size.  For frame pixel
+ * idx: x = idx % W, r = idx / W.
+ * 1. Tap position, in unsigned 32-bit integers.  ax = (2x + 1) * w + W; x0 = (int)(ax / (2W)) - 1; ex = ax % (2W);
+ *    fx = (float)ex / (float)(2W).  Likewise ar = (2r + 1) * h + H, which gives r0, er and fr = (float)er / (float)(2H).  The
+ *    centre of frame pixel x lies at x0 + fx on the axis whose integers are the low-resolution pixel centres.  It follows that
+ *    -1 <= x0 <= w-1 and 0 <= fx < 1; equal sizes give x0 = x, fx = 0; wherever one tap of an axis is outside the
+ *    low-resolution frame, the other one's weight is > 0.
+ * 2. Taps.  q = (x0 + i, r0 + j), with j = 0, 1 in the outer loop and i = 0, 1 in the inner loop;
+ *    b = (i ? fx : 1 - fx) * (j ? fr : 1 - fr); u_q[c] = lo_color[q][c] / m_c^lo(q).
+ * 3. Tested pass.  sum = (0, 0, 0), bsum = 0.  A tap is skipped when q is outside the low-resolution frame; when
+ *    lo_object_id[q] != object_id[idx]; when object_id[idx] >= 0 and
+ *    |depth[idx] - lo_depth[q]| <= depth_tol * max(depth[idx], lo_depth[q]) does not hold; when object_id[idx] >= 0, both
+ *    normals are given and dot(N(idx), N_lo(q)) >= normal_min does not hold.  A miss (id < 0) is held to the id test alone: its
+ *    depth is +inf.  A tap that is taken adds sum[c] = sum[c] + u_q[c] * b; bsum = bsum + b.  A taken tap with b = 0 adds zeros.
+ * 4. If bsum > 0: weight = bsum.  Otherwise the fallback: the same loop again, with only the taps outside the low-resolution
+ *    frame skipped; weight = 0.  By step 1 its bsum is > 0.
+ * 5. out[c] = clamp((sum[c] / bsum) * m_c(idx)).
+ * Colours are expected finite; for others the result is unspecified.  With equal sizes and the low-resolution guides equal to
+ * the frame's, the output is clamp(color): the colour itself for a rendered frame, bit for bit (without the albedo planes; with
+ * them (c / m) * m may differ from c in the last bit).
+ * pt_upsample_tap_host is the host instantiation of the tap position the kernel compiles (csrc/pt_upsample.h): step 1 for one
+ * coordinate of one axis, *first = x0 and *frac = fx.  PT_ERR_INVALID for a NULL pointer, a size that is 0 or above 2^14, or
+ * coord >= size.  It needs no device. */
+typedef struct pt_upsample_params {
+    float depth_tol;    /* relative depth tolerance of a tap; 0 = the default; finite, >= 0 */
+    float normal_min;   /* smallest cosine between the two normals; 0 = the default; in [-1, 1] */
+    uint32_t flags;     /* none defined: must be 0 */
+} pt_upsample_params;
+int pt_upsample_defaults(pt_upsample_params *out);
+int pt_ctx_upsample(pt_ctx *ctx, uint32_t width, uint32_t height, uint32_t lo_width, uint32_t lo_height,
+                    const pt_upsample_params *params /* NULL = all zero */,
+                    const float *d_lo_color, const float *d_lo_depth, const int32_t *d_lo_object_id,
+                    const float *d_lo_normal /* may be NULL */, const float *d_lo_albedo /* may be NULL */,
+                    const float *d_depth, const int32_t *d_object_id,
+                    const float *d_normal /* may be NULL */, const float *d_albedo /* may be NULL */,
+                    float *d_out_color, float *d_out_weight /* may be NULL */, void *hip_stream);
+/* host only, no device: the host instantiation of the tap position the kernel compiles */
+int pt_upsample_tap_host(uint32_t size, uint32_t lo_size, uint32_t coord, int32_t *first, float *frac);
+
 /* ---- the one collective of the path: the framebuffer gather over RCCL (xGMI) ---------------------------------
  * One process (or thread) per GPU renders its rows with pt_ctx_render (chunk_first = rank, chunk_step = n_ranks) into
  * device memory; pt_comm_gather_frame then gives EVERY rank the whole frame in device memory: one in-place

@@ -72,6 +72,10 @@ class pt_reproject_var_params(C.Structure):
                 ("min_frames", C.c_uint32), ("radius", C.c_uint32), ("flags", C.c_uint32)]
 
 
+class pt_upsample_params(C.Structure):
+    _fields_ = [("depth_tol", C.c_float), ("normal_min", C.c_float), ("flags", C.c_uint32)]
+
+
 class pt_noise_stats(C.Structure):
     _fields_ = [("spp_min", C.c_uint32), ("spp_max", C.c_uint32), ("spp_a_min", C.c_uint32), ("spp_b_min", C.c_uint32),
                 ("pixels", C.c_uint64), ("mean_error", C.c_double), ("histogram", C.c_uint32 * 64)]
@@ -167,6 +171,9 @@ def lib():
         [C.c_void_p] * 4 + [C.POINTER(pt_camera)] + [C.c_void_p] * 11
     L.pt_reproject_project_host.argtypes = [C.POINTER(pt_camera), C.POINTER(pt_camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_float] + \
         [C.POINTER(C.c_float)] * 3
+    L.pt_upsample_defaults.argtypes = [C.POINTER(pt_upsample_params)]
+    L.pt_ctx_upsample.argtypes = [C.c_void_p] + [C.c_uint32] * 4 + [C.POINTER(pt_upsample_params)] + [C.c_void_p] * 12
+    L.pt_upsample_tap_host.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_float)]
     L.pt_write_pfm.argtypes = [C.c_char_p, C.POINTER(C.c_float), C.c_uint32, C.c_uint32, C.c_uint32]
     L.pt_ctx_set_profiling.argtypes = [C.c_void_p, C.c_int]
     L.pt_ctx_pass_kernel.argtypes = [C.c_void_p, C.c_uint32]
@@ -366,6 +373,20 @@ class Context:
                                           ptr(h.get("len")), ptr(h.get("moments")), ptr(h.get("depth")), ptr(h.get("object_id")),
                                           ptr(h.get("normal")), ptr(out_color), ptr(out_len), ptr(out_moments), ptr(error),
                                           C.c_void_p(stream or 0)))
+
+    def upsample(self, width, height, lo_width, lo_height, lo, depth, object_id, out_color, normal=None, albedo=None,
+                 out_weight=None, depth_tol=0.0, normal_min=0.0, stream=None):
+        """Fill a width x height frame from a colour frame traced at lo_width x lo_height, through the first-hit guides of both
+        sizes (pt_ctx_upsample).  Device pointers to whole frames: `lo` is a dict with "color", "depth", "object_id" and
+        optionally "normal", "albedo" - what render() and render_aov() write at the low size with the same camera and scene;
+        depth, object_id, normal, albedo: render_aov()'s at the full size; out_color pixels * 3 float32; out_weight, if given,
+        pixels float32 - the bilinear weight of the taps that passed, 0 where none did.  The normal test needs both normals,
+        demodulation both albedos.  depth_tol, normal_min: 0 = upsample_defaults().  No output may alias an input."""
+        p = pt_upsample_params(depth_tol, normal_min, 0)
+        ptr = lambda q: C.c_void_p(q) if q else None  # noqa: E731
+        _check(lib().pt_ctx_upsample(self._h, width, height, lo_width, lo_height, C.byref(p), ptr(lo["color"]), ptr(lo["depth"]),
+                                     ptr(lo["object_id"]), ptr(lo.get("normal")), ptr(lo.get("albedo")), ptr(depth), ptr(object_id),
+                                     ptr(normal), ptr(albedo), ptr(out_color), ptr(out_weight), C.c_void_p(stream or 0)))
 
     def accum_track_noise(self, on=True):
         """Keep half of every pixel's samples in a second accumulator for the frames started from now on
@@ -575,6 +596,22 @@ def reproject_var_defaults():
     _check(lib().pt_reproject_var_defaults(C.byref(p)))
     return {"weight": p.weight, "max_history": p.max_history, "depth_tol": p.depth_tol, "normal_min": p.normal_min,
             "min_frames": p.min_frames, "radius": p.radius}
+
+
+def upsample_defaults():
+    """The values pt_ctx_upsample uses for a zero field: {"depth_tol", "normal_min"} (pt_upsample_defaults)."""
+    p = pt_upsample_params()
+    _check(lib().pt_upsample_defaults(C.byref(p)))
+    return {"depth_tol": p.depth_tol, "normal_min": p.normal_min}
+
+
+def upsample_tap_host(size, lo_size, coord):
+    """Where the centre of pixel `coord` of an axis of `size` pixels lies among the centres of an axis of `lo_size` pixels
+    (pt_upsample_tap_host, the host instantiation of the tap position the kernel compiles): (first, frac) - the taps are first
+    and first + 1, with weights 1 - frac and frac."""
+    first, frac = C.c_int32(), C.c_float()
+    _check(lib().pt_upsample_tap_host(size, lo_size, coord, C.byref(first), C.byref(frac)))
+    return first.value, frac.value
 
 
 def reproject_project_host(cam, hist_cam, width, height, idx, depth):

@@ -19,6 +19,7 @@
 #include "pt_noise.h"
 #include "pt_present.h"
 #include "pt_reproject.h"
+#include "pt_upsample.h"
 #include "pt_tile.h"
 
 namespace pt {
@@ -2793,6 +2794,32 @@ int pt_ctx_reproject_var(pt_ctx *c, uint32_t width, uint32_t height, const pt_re
     if (rs) return rs;
     v.s_plane = c->rv_s.p;
     launch_reproject_var(st, v);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    return PT_OK;
+}
+
+int pt_upsample_defaults(pt_upsample_params *out) {
+    if (!out) {
+        set_error("out is NULL");
+        return PT_ERR_INVALID;
+    }
+    *out = pt_upsample_params{kUpsampleDepthTol, kUpsampleNormalMin, 0u};
+    return PT_OK;
+}
+
+int pt_ctx_upsample(pt_ctx *c, uint32_t width, uint32_t height, uint32_t lo_width, uint32_t lo_height, const pt_upsample_params *params,
+                    const float *d_lo_color, const float *d_lo_depth, const int32_t *d_lo_object_id, const float *d_lo_normal,
+                    const float *d_lo_albedo, const float *d_depth, const int32_t *d_object_id, const float *d_normal,
+                    const float *d_albedo, float *d_out_color, float *d_out_weight, void *hip_stream) {
+    // everything that can be refused is refused here, before the device is touched
+    UpsampleFrame f;
+    const int rc = host::check_upsample(c, width, height, lo_width, lo_height, params, d_lo_color, d_lo_depth, d_lo_object_id, d_lo_normal,
+                                        d_lo_albedo, d_depth, d_object_id, d_normal, d_albedo, d_out_color, d_out_weight, f);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    launch_upsample(st, f);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
     return PT_OK;

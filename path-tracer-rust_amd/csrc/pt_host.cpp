@@ -3,6 +3,7 @@
 // for the triangle edges — see pt_device.h).
 #include "pt_host.h"
 #include "pt_reproject.h"
+#include "pt_upsample.h"
 
 #include <algorithm>
 #include <cmath>
@@ -1364,6 +1365,44 @@ int check_reproject_var(const void *ctx, uint32_t width, uint32_t height, const 
     v.error = d_error;
     v.long_len = (float)(P.min_frames ? P.min_frames : kReprojectVarMinFrames) * v.f.wt;
     v.radius = P.radius ? P.radius : kReprojectVarRadius;
+    return PT_OK;
+}
+
+// ---- pt_ctx_upsample (ptrace.h, pt_upsample.h)
+int check_upsample(const void *ctx, uint32_t width, uint32_t height, uint32_t lo_width, uint32_t lo_height,
+                   const pt_upsample_params *params, const float *d_lo_color, const float *d_lo_depth, const int32_t *d_lo_object_id,
+                   const float *d_lo_normal, const float *d_lo_albedo, const float *d_depth, const int32_t *d_object_id,
+                   const float *d_normal, const float *d_albedo, float *d_out_color, float *d_out_weight, UpsampleFrame &f) {
+    pt_upsample_params P{};
+    if (params) P = *params;
+    if (!finite_nonneg(P.depth_tol)) return refuse("pt_upsample_params.depth_tol is negative or not finite");
+    if (!(P.normal_min >= -1.0f && P.normal_min <= 1.0f)) return refuse("pt_upsample_params.normal_min is outside [-1, 1]");
+    if (P.flags) return refuse("pt_upsample_params.flags: none is defined");
+    if (!width || !height || !lo_width || !lo_height) return refuse("width, height, lo_width and lo_height must be positive");
+    if (width > kUpsampleMaxSize || height > kUpsampleMaxSize || lo_width > kUpsampleMaxSize || lo_height > kUpsampleMaxSize)
+        return refuse("width, height, lo_width or lo_height exceeds 2^14");
+    if (!d_lo_color || !d_lo_depth || !d_lo_object_id || !d_depth || !d_object_id || !d_out_color)
+        return refuse("d_lo_color, d_lo_depth, d_lo_object_id, d_depth, d_object_id or d_out_color is NULL");
+    if (!ctx) return refuse("ctx is NULL");
+    f = UpsampleFrame{};
+    f.width = width;
+    f.height = height;
+    f.lo_width = lo_width;
+    f.lo_height = lo_height;
+    f.lo_color = d_lo_color;
+    f.lo_depth = d_lo_depth;
+    f.lo_object_id = d_lo_object_id;
+    f.depth = d_depth;
+    f.object_id = d_object_id;
+    if (d_lo_normal && d_normal) f.lo_normal = d_lo_normal, f.normal = d_normal;  // a test of both or of neither
+    if (d_lo_albedo && d_albedo) f.lo_albedo = d_lo_albedo, f.albedo = d_albedo;
+    f.out_color = d_out_color;
+    f.out_weight = d_out_weight;
+    f.depth_tol = P.depth_tol != 0.0f ? P.depth_tol : kUpsampleDepthTol;
+    f.normal_min = P.normal_min != 0.0f ? P.normal_min : kUpsampleNormalMin;
+    f.div_w = upsample_div_make(width);
+    f.div_2w = upsample_div_make(2u * width);
+    f.div_2h = upsample_div_make(2u * height);
     return PT_OK;
 }
 

@@ -24,7 +24,7 @@ static void usage() {
             "              [--seed S] [--gpus N] [--root DIR] [--out DIR] [--no-ppm] [--checkpoint FILE] [--aov N]\n"
             "              [--denoise [N]] [--noise-target X [--noise-map FILE.pfm]]\n"
             "              [--adaptive X [--tile N] [--spp-map FILE.pfm] [--error-map FILE.pfm] [--adaptive-checkpoint FILE]]\n"
-            "              [--denoise-var [N]] [--preview FILE.ppm [--preview-size WxH] [--exposure E]]\n"
+            "              [--denoise-var [N]] [--preview FILE.ppm [--preview-size WxH] [--exposure E]] [--trace-scale K]\n"
             "  --checkpoint FILE: continue from the samples FILE holds (if it exists), render up to <samplesPerPixel> in all and\n"
             "                     save them to FILE; one GPU only; the seed defaults to 0 instead of the clock, so that the same\n"
             "                     command continues the same frame\n"
@@ -52,7 +52,11 @@ static void usage() {
             "  --preview FILE.ppm: after the frame (after --denoise / --denoise-var: of the denoised frame), turn it into 8-bit display\n"
             "           pixels on the GPU (pt_ctx_present, RGB8) and write them as a binary PPM; --preview-size WxH fits the frame to\n"
             "           that size by area averaging (default: the frame's own), --exposure E scales it first (default 1); one GPU\n"
-            "           only\n");
+            "           only\n"
+            "  --trace-scale K: K = 2..8: trace the paths at ceil(W/K) x ceil(H/K), the first-hit guides at both sizes, and fill the\n"
+            "           frame in through the guides with albedo and normals (pt_ctx_upsample, default parameters); the image written\n"
+            "           is the full-size frame; combines with --denoise and --preview; one GPU only; not with --checkpoint,\n"
+            "           --noise-target or --adaptive\n");
 }
 
 static std::vector<std::string> scene_ids(const std::string &root) {
@@ -297,6 +301,56 @@ static int render_on_context(const pt_config *cfg, pt_scene *sc, const std::stri
     return rc;
 }
 
+// --trace-scale K: one context on one GPU.  The paths at ceil(W/K) x ceil(H/K), the first-hit guides over the frame's samples at
+// both sizes, then pt_ctx_upsample with albedo and normals at its defaults: the full-size frame into img.  `keep` takes the
+// context and the device frame instead of their being freed.
+static int render_scaled(const pt_config *cfg, pt_scene *sc, uint32_t scale, std::vector<float> &img, pt_stats *st, DeviceFrame *keep) {
+    int dev = 0;
+    if (const char *e = getenv("PT_DEVICE")) dev = atoi(e);
+    uint32_t n_objs = 0, n_tris = 0;
+    const pt_object *objs = pt_scene_objects(sc, &n_objs);
+    const pt_triangle *tris = pt_scene_triangles(sc, &n_tris);
+    pt_config lo = *cfg;
+    lo.width = (cfg->width + scale - 1u) / scale;
+    lo.height = (cfg->height + scale - 1u) / scale;
+    const size_t npix = (size_t)cfg->width * cfg->height, nlo = (size_t)lo.width * lo.height;
+    pt_ctx *ctx = nullptr;
+    void *d_out = nullptr, *d_lo = nullptr, *d_full = nullptr;
+    int rc = pt_ctx_create(dev, &ctx);
+    if (!rc) rc = pt_ctx_set_scene(ctx, pt_scene_camera(sc), objs, n_objs, tris, n_tris);
+    if (!rc) rc = pt_device_malloc(dev, npix * 3 * sizeof(float), &d_out);
+    if (!rc) rc = pt_device_malloc(dev, nlo * 11 * sizeof(float), &d_lo);      // colour, albedo, normal, depth, id
+    if (!rc) rc = pt_device_malloc(dev, npix * 8 * sizeof(float), &d_full);  // albedo, normal, depth, id
+    if (!rc) {
+        float *lo_color = (float *)d_lo, *lo_albedo = lo_color + nlo * 3, *lo_normal = lo_albedo + nlo * 3, *lo_depth = lo_normal + nlo * 3;
+        int32_t *lo_id = (int32_t *)(lo_depth + nlo);
+        float *albedo = (float *)d_full, *normal = albedo + npix * 3, *depth = normal + npix * 3;
+        int32_t *id = (int32_t *)(depth + npix);
+        rc = pt_ctx_render(ctx, &lo, lo_color, nullptr, nullptr, progress, nullptr, st);
+        if (!rc) rc = pt_ctx_render_aov(ctx, &lo, lo_albedo, lo_normal, lo_depth, lo_id, nullptr);
+        if (!rc) rc = pt_ctx_render_aov(ctx, cfg, albedo, normal, depth, id, nullptr);
+        if (!rc)
+            rc = pt_ctx_upsample(ctx, cfg->width, cfg->height, lo.width, lo.height, nullptr, lo_color, lo_depth, lo_id, lo_normal, lo_albedo,
+                                 depth, id, normal, albedo, (float *)d_out, nullptr, nullptr);
+    }
+    if (!rc) rc = pt_device_download(dev, img.data(), d_out, npix * 3 * sizeof(float));
+    if (!rc) {
+        printf("\nTraced at %ux%u (--trace-scale %u), filled in to %ux%u\n", lo.width, lo.height, scale, cfg->width, cfg->height);
+        fflush(stdout);
+    }
+    if (d_lo) pt_device_free(dev, d_lo);
+    if (d_full) pt_device_free(dev, d_full);
+    if (!rc && keep) {
+        keep->dev = dev;
+        keep->ctx = ctx;
+        keep->d_out = d_out;
+        return rc;
+    }
+    if (d_out) pt_device_free(dev, d_out);
+    if (ctx) pt_ctx_destroy(ctx);
+    return rc;
+}
+
 // --denoise / --denoise-var: first-hit guides over the frame's first `spp` samples, pt_ctx_denoise - or, with the frame's
 // estimate, pt_ctx_denoise_var - in place on the device frame, and the two files at `stem`
 static int write_denoised(const pt_config *frame, uint32_t spp, const DeviceFrame &df, const std::string &stem, const char *scene_id) {
@@ -419,7 +473,7 @@ int main(int argc, char **argv) {
     bool seed_given = false;
     std::string checkpoint;
     bool write_ppm = true;
-    uint32_t gpus = 1, aov_spp = 0, denoise_spp = 0, denoise_var_spp = 0;
+    uint32_t gpus = 1, aov_spp = 0, denoise_spp = 0, denoise_var_spp = 0, trace_scale = 0;
     NoiseRun noise;
     AdaptiveRun adaptive;
     std::string preview;
@@ -520,6 +574,14 @@ int main(int argc, char **argv) {
                 return 1;
             }
         }
+        else if (a == "--trace-scale") {
+            const char *v = next();
+            trace_scale = strspn(v, "0123456789") == strlen(v) ? (uint32_t)strtoul(v, nullptr, 10) : 0u;
+            if (trace_scale < 2u || trace_scale > 8u) {
+                fprintf(stderr, "--trace-scale needs K = 2..8\n");
+                return 1;
+            }
+        }
         else if (a == "--denoise-var") {
             denoise_var_spp = 16;
             if (i + 1 < argc && argv[i + 1][0] != '\0' && strspn(argv[i + 1], "0123456789") == strlen(argv[i + 1])) {
@@ -603,6 +665,10 @@ int main(int argc, char **argv) {
         fprintf(stderr, "--denoise-var needs a frame with a noise estimate: --noise-target or --adaptive\n");
         return 1;
     }
+    if (trace_scale && (gpus > 1 || !checkpoint.empty() || noise.target > 0.0f || is_adaptive)) {
+        fprintf(stderr, "--trace-scale works with one GPU only and not with --checkpoint, --noise-target or --adaptive\n");
+        return 1;
+    }
     if ((!checkpoint.empty() || !adaptive.file.empty()) && !seed_given) seed = 0;
     // load_scene_ids (scenes.rs:28-38): a scenes/ directory without any *.json is filled with the built-in scenes
     if (scene_ids(root).empty()) {
@@ -651,7 +717,9 @@ int main(int argc, char **argv) {
     DeviceFrame df;
     df.want_error = denoise_var_spp != 0;
     const bool keep_frame = denoise_spp || denoise_var_spp || !preview.empty();  // the frame stays on its GPU for what follows
-    if (is_adaptive)
+    if (trace_scale)
+        rc = render_scaled(&cfg, sc, trace_scale, img, &st, keep_frame ? &df : nullptr);
+    else if (is_adaptive)
         rc = render_adaptive(&cfg, sc, adaptive, img, &st, keep_frame ? &df : nullptr);
     else if (checkpoint.empty() && !keep_frame && !(noise.target > 0.0f))
         rc = pt_render_multi(&cfg, gpus ? gpus : 1, pt_scene_camera(sc), objs, n_objs, tris, n_tris, img.data(), nullptr,

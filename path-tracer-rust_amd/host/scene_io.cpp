@@ -24,6 +24,7 @@
 #include "../csrc/pt_host.h"
 #include "../csrc/pt_present.h"
 #include "../csrc/pt_reproject.h"
+#include "../csrc/pt_upsample.h"
 
 namespace {
 
@@ -1245,6 +1246,19 @@ int pt_reproject_project_host(const pt_camera *cam, const pt_camera *hist_cam, u
     *px = p.px;
     *pr = p.pr;
     *zexp = p.zexp;
+    return PT_OK;
+}
+
+int pt_upsample_tap_host(uint32_t size, uint32_t lo_size, uint32_t coord, int32_t *first, float *frac) {
+    if (!first || !frac) {
+        pt::set_error("NULL argument");
+        return PT_ERR_INVALID;
+    }
+    if (size == 0 || lo_size == 0 || size > pt::kUpsampleMaxSize || lo_size > pt::kUpsampleMaxSize || coord >= size) {
+        pt::set_error("a size that is 0 or above 2^14, or coord outside the axis");
+        return PT_ERR_INVALID;
+    }
+    pt::upsample_tap(size, lo_size, pt::upsample_div_make(2u * size), coord, *first, *frac);
     return PT_OK;
 }
 
