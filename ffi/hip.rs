@@ -243,6 +243,19 @@ extern "C" {
         tris: *const PtTriangle,
         n_tris: u32,
     ) -> i32;
+    // the camera of the scene moved without building the scene again (a viewport's call per frame); `rebuilt` may be null
+    pub fn pt_ctx_set_camera(ctx: *mut PtCtx, cam: *const PtCamera, rebuilt: *mut i32) -> i32;
+    pub fn pt_ctx_camera_reach(ctx: *const PtCtx, lo: *mut f32, hi: *mut f32) -> i32;
+    pub fn pt_ctx_reserve_camera_reach(ctx: *mut PtCtx, lo: *const f32, hi: *const f32, rebuilt: *mut i32) -> i32;
+    pub fn pt_scene_reach(
+        cam: *const PtCamera,
+        objs: *const PtObject,
+        n_objs: u32,
+        tris: *const PtTriangle,
+        n_tris: u32,
+        lo: *mut f32,
+        hi: *mut f32,
+    ) -> i32;
     pub fn pt_ctx_render(
         ctx: *mut PtCtx,
         cfg: *const PtConfig,
@@ -563,6 +576,19 @@ pub struct ReprojectFrame {
 /// (pt_ctx_reproject, in place: d_out_color = d_color), and the two swap roles: on return `hist` is the new history and `cur`
 /// the set of buffers the next frame renders into.  Pointers change hands; nothing is copied.  `have_history`: false for the
 /// first frame after a scene change.  `weight`: the samples per pixel `cur` was rendered with.
+///
+/// One turn of a viewport: the scene is set once (pt_ctx_set_scene), the camera moves per frame (pt_ctx_set_camera):
+/// ```ignore
+/// let mut rebuilt = 0i32;
+/// cur.cam = camera_from_the_gui();
+/// unsafe {
+///     pt_ctx_set_camera(ctx, &cur.cam, &mut rebuilt);   // rebuilt != 0: the lens centre left the scene's reach (rare)
+///     pt_ctx_render(ctx, &cfg, cur.d_color as *mut c_void, null_mut(), null(), None, null_mut(), &mut stats);
+///     pt_ctx_render_aov(ctx, &cfg, d_albedo, cur.d_normal, cur.d_depth, cur.d_object_id, null_mut());
+/// }
+/// reproject_and_swap(ctx, (cfg.width, cfg.height), cfg.spp, &mut cur, &mut hist, have_history);
+/// have_history = true;
+/// ```
 pub fn reproject_and_swap(
     ctx: *mut PtCtx,
     frame: (u32, u32),
@@ -838,4 +864,4 @@ pub fn render_pixels_hip(
 // RenderUpdate { progress, image } (:969-972) then carries the growing picture every 500 ms exactly as with the CPU path:
 // the progress thread is untouched, it finds `pixels` refreshed by on_progress.  A host that renders many frames of one
 // scene (the GUI re-renders on every camera move) keeps the PtCtx and the two device buffers instead of creating them per
-// frame: pt_ctx_set_scene only when the scene changed.
+// frame: pt_ctx_set_scene only when the scene changed, pt_ctx_set_camera when only the camera moved.

@@ -169,6 +169,43 @@ void pt_ctx_destroy(pt_ctx *ctx);
 int pt_ctx_set_scene(pt_ctx *ctx, const pt_camera *cam, const pt_object *objs, uint32_t n_objs,
                      const pt_triangle *tris, uint32_t n_tris);
 
+/* Move the camera of the scene pt_ctx_set_scene gave, without building the scene again: what a viewport calls per frame.
+ * REACH.  The device tables of a scene (BVH box paddings, bounding-sphere shortcuts, filter pads) rest on error bounds derived
+ * from ONE box B = [lo, hi]: the box that bounds every ray origin - the objects and the lens centre (pt_camera_basis).  Nothing
+ * else of the camera enters them, so they hold unchanged for every camera whose lens centre lies inside B.  pt_ctx_set_scene sets
+ * B to the objects' box grown by its camera's lens centre (pt_scene_reach computes that box on the host, without a device);
+ * pt_ctx_camera_reach returns the box in force.
+ * SAME CAMERA: *cam bitwise equal to the context's (nine floats): nothing changes, both held frames stay, *rebuilt = 0.
+ * FAST PATH (*rebuilt = 0): lo[a] <= lens[a] <= hi[a] on all three axes.  The context takes the camera, drops the frame
+ * pt_ctx_accumulate holds and the held adaptive frame (their key includes the camera, as under pt_ctx_set_scene) and marks the
+ * checkpoint fingerprint stale.  Nothing else: no flattening, no HIP call (but the release of a held frame's planes), no device
+ * memory touched; the measured pass and round rates, the boxes of pt_ctx_set_mesh_bounds and the scratch of the denoisers,
+ * pt_ctx_present and pt_ctx_reproject_var are kept.
+ * SLOW PATH (*rebuilt = 1): the lens centre is outside B.  B grows geometrically, in binary32, per axis: lens[a] < lo[a] gives
+ * lo[a] = lens[a] - (lo[a] - lens[a]); lens[a] > hi[a] gives hi[a] = lens[a] + (lens[a] - hi[a]); a bound that is not violated
+ * stays.  The scene is flattened again for the new box from the context's host copies of the objects and triangles (it keeps
+ * the triangles: 36 B each) and uploaded as pt_ctx_set_scene uploads it, then the camera is taken as on the fast path.  The
+ * overshoot doubles: a dolly outwards costs O(log distance) rebuilds, an orbit is back on the fast path after a few.  The boxes of
+ * pt_ctx_set_mesh_bounds and the measured rates survive.  If flattening fails the context is left as it was.
+ * EQUIVALENCE.  After pt_ctx_set_camera(cam1), on either path, every entry point returns what it returns after
+ * pt_ctx_set_scene(cam1, the same objects and triangles), bit for bit: frames, AOVs, queries, pt_stats.ray_bounces.  The device
+ * tables may differ in their paddings; the results may not (the tables only ever decide what is tested exactly, never a result).
+ * pt_ctx_accum_save / pt_ctx_adaptive_save write the fingerprint pt_ctx_set_scene(cam1, ...) would have given - computed at the
+ * first save or load after a camera change, never by this call - so checkpoints interchange.
+ * PT_ERR_INVALID, in this order, nothing changed: ctx NULL; cam NULL; no scene; a lens centre that is not finite.  rebuilt may
+ * be NULL.  Like pt_ctx_set_scene, not to be called from a progress callback. */
+int pt_ctx_set_camera(pt_ctx *ctx, const pt_camera *cam, int *rebuilt);
+/* the box B in force (see pt_ctx_set_camera); PT_ERR_INVALID without a scene */
+int pt_ctx_camera_reach(const pt_ctx *ctx, float lo[3], float hi[3]);
+/* Pay pt_ctx_set_camera's rebuild once, up front: if [lo, hi] is not inside B, B becomes the union of the two and the scene is
+ * rebuilt for it (*rebuilt = 1); otherwise nothing happens (*rebuilt = 0).  The camera does not change and the held frames stay.
+ * PT_ERR_INVALID for lo[a] > hi[a], a bound that is not finite, or no scene. */
+int pt_ctx_reserve_camera_reach(pt_ctx *ctx, const float lo[3], const float hi[3], int *rebuilt);
+/* The box pt_ctx_set_scene would derive its bounds for: min / max in binary32 over the lens centre, every sphere's centre -/+
+ * |radius| and every mesh vertex + the object's position.  Host only, no device. */
+int pt_scene_reach(const pt_camera *cam, const pt_object *objs, uint32_t n_objs, const pt_triangle *tris, uint32_t n_tris,
+                   float lo[3], float hi[3]);
+
 /* Number of pixels a call with this config renders (the band, or this rank's chunks of it); 0 on a bad config. */
 uint32_t pt_config_pixels(const pt_config *cfg);
 

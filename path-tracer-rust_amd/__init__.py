@@ -130,6 +130,11 @@ def lib():
     L.pt_ctx_destroy.restype = None
     L.pt_ctx_set_scene.argtypes = [C.c_void_p, C.POINTER(pt_camera), C.POINTER(pt_object), C.c_uint32,
                                    C.POINTER(pt_triangle), C.c_uint32]
+    L.pt_ctx_set_camera.argtypes = [C.c_void_p, C.POINTER(pt_camera), C.POINTER(C.c_int)]
+    L.pt_ctx_camera_reach.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.pt_ctx_reserve_camera_reach.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int)]
+    L.pt_scene_reach.argtypes = [C.POINTER(pt_camera), C.POINTER(pt_object), C.c_uint32, C.POINTER(pt_triangle), C.c_uint32,
+                                 C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.pt_ctx_render.argtypes = [C.c_void_p, C.POINTER(pt_config), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.POINTER(pt_stats)]
     L.pt_ctx_accumulate.argtypes = L.pt_ctx_render.argtypes
@@ -244,6 +249,26 @@ class Context:
     def set_scene(self, scene):
         _check(lib().pt_ctx_set_scene(self._h, scene.camera, scene.objects, scene.n_objects, scene.triangles,
                                       scene.n_triangles))
+
+    def set_camera(self, cam):
+        """Move the camera of the scene set_scene gave (pt_ctx_set_camera): a pt_camera, a pointer to one or a dict of its fields.
+        Returns whether the scene had to be rebuilt (the lens centre left camera_reach()); False on the fast path."""
+        rebuilt = C.c_int(0)
+        _check(lib().pt_ctx_set_camera(self._h, _camera(cam), C.byref(rebuilt)))
+        return bool(rebuilt.value)
+
+    def camera_reach(self):
+        """The box (lo, hi), three floats each, of lens centres the scene's tables hold for (pt_ctx_camera_reach)."""
+        lo, hi = f3(), f3()
+        _check(lib().pt_ctx_camera_reach(self._h, lo, hi))
+        return tuple(lo), tuple(hi)
+
+    def reserve_camera_reach(self, lo, hi):
+        """Grow camera_reach() to hold the box [lo, hi] now, rebuilding the scene once if it does not
+        (pt_ctx_reserve_camera_reach).  Returns whether it rebuilt."""
+        rebuilt = C.c_int(0)
+        _check(lib().pt_ctx_reserve_camera_reach(self._h, f3(*lo), f3(*hi), C.byref(rebuilt)))
+        return bool(rebuilt.value)
 
     def pass_kernel(self, separate_kernels=False):
         """Name of the kernel a wavefront pass of this scene launches (see pt_ctx_pass_kernel)."""
@@ -579,6 +604,15 @@ def _camera(cam):
         return C.pointer(pt_camera(f3(*cam["position"]), f3(*cam["direction"]), cam["focal_length"], cam["sensor_width"],
                                    cam["aspect_ratio"]))
     return C.pointer(cam) if isinstance(cam, pt_camera) else cam
+
+
+def scene_reach(scene, cam=None):
+    """The box (lo, hi) Context.set_scene(scene) derives its bounds for - with `cam`, for that camera in place of the scene's own
+    (pt_scene_reach: host only, no device)."""
+    lo, hi = f3(), f3()
+    _check(lib().pt_scene_reach(scene.camera if cam is None else _camera(cam), scene.objects, scene.n_objects, scene.triangles,
+                                scene.n_triangles, lo, hi))
+    return tuple(lo), tuple(hi)
 
 
 def reproject_defaults():

@@ -299,6 +299,10 @@ struct pt_ctx {
     // the stored ones) and their device form (6 pair records per object), for intersect_bounds / orbit-point queries
     std::vector<pt_triangle> h_boxes;
     std::vector<pt_object> h_objs;
+    // the triangles as pt_ctx_set_scene got them (36 B each) and the box its bounds were derived for: what pt_ctx_set_camera
+    // rebuilds the tables from when the lens centre leaves the box, and what the lazy fingerprint hashes
+    std::vector<pt_triangle> h_tris;
+    host::Reach reach{};
     DevBuf<TriPairRec> d_boxes;
     bool boxes_dirty = true;
     // scratch of the single-ray query entry points (kept across calls: a picking caller sends one ray per click)
@@ -328,8 +332,10 @@ struct pt_ctx {
     // pt_ctx_accumulate: the frame kept between calls.  scene_fp: the checkpoint fingerprint of the scene pt_ctx_set_scene got,
     // which drops the held frame.  acc_track (pt_ctx_accum_track_noise): the frames this context starts are noise-tracked.
     // noise_cnt: pt_ctx_accum_noise's counters.
+    // fp_stale: the camera changed since scene_fp was computed (pt_ctx_set_camera) - read it through scene_fp_of().
     HeldFrame held;
     uint64_t scene_fp = 0;
+    bool fp_stale = false;
     bool acc_track = false;
     DevBuf<NoiseCounters> noise_cnt;
     // pt_ctx_denoise's scratch, kept between calls: the two colour planes and the packed guides, one float4 per pixel each
@@ -935,6 +941,16 @@ uint64_t scene_fingerprint(const pt_camera *cam, const pt_object *objs, uint32_t
     return pt_siphash(1, 3, 0, 0, b.data(), b.size());
 }
 
+// The fingerprint pt_ctx_set_scene would give for the context's camera and scene: pt_ctx_set_camera only marks it stale, the first
+// checkpoint call afterwards hashes the kept host copies
+uint64_t scene_fp_of(pt_ctx *c) {
+    if (c->fp_stale) {
+        c->scene_fp = scene_fingerprint(&c->cam, c->h_objs.data(), (uint32_t)c->h_objs.size(), c->h_tris.data(), (uint32_t)c->h_tris.size());
+        c->fp_stale = false;
+    }
+    return c->scene_fp;
+}
+
 // resolve part `i` of the held sums into the call's output: over its own count, black at 0
 int accum_resolve_part(const HeldFrame &h, uint32_t i, float *out, hipStream_t st) {
     const host::Part p = h.part(i);
@@ -1456,22 +1472,9 @@ void pt_ctx_destroy(pt_ctx *c) {
     (void)hipStreamDestroy(st);
 }
 
-int pt_ctx_set_scene(pt_ctx *c, const pt_camera *cam, const pt_object *objs, uint32_t n_objs,
-                     const pt_triangle *tris, uint32_t n_tris) {
-    if (!c || !cam || (!objs && n_objs) || (!tris && n_tris)) {
-        set_error("NULL argument");
-        return PT_ERR_INVALID;
-    }
-    host::FlatScene fs;
-    std::string err;
-    if (!host::flatten_scene(*cam, objs, n_objs, tris, n_tris, fs, err)) {
-        set_error(err);
-        return PT_ERR_INVALID;
-    }
-    HIP_TRY(hipSetDevice(c->device));
-    c->held.drop();  // (the held sums are of the scene before)
-    c->adaptive.drop();
-    c->scene_fp = 0;
+// The device form of a flattened scene: the tables uploaded and c->scene pointed at them (pt_ctx_set_scene; the rebuilds of
+// pt_ctx_set_camera and pt_ctx_reserve_camera_reach).  Nothing of the context's host state changes here.
+static int upload_flat(pt_ctx *c, const host::FlatScene &fs, const pt_object *objs, uint32_t n_objs, uint32_t n_tris) {
     int rc;
     if ((rc = c->d_objs.ensure(fs.objs.size())) || (rc = c->d_opairs.ensure(fs.obj_pairs.size())) || (rc = c->d_tris.ensure(fs.tri_pairs.size())) ||
         (rc = c->d_mats.ensure(fs.mats.size())) || (rc = c->d_tshade.ensure(fs.tri_shade.size())) ||
@@ -1572,8 +1575,33 @@ int pt_ctx_set_scene(pt_ctx *c, const pt_camera *cam, const pt_object *objs, uin
     c->scene.tri_shade = c->d_tshade.p;
     c->scene.n_objs = n_objs;
     c->scene.n_tris = n_tris;
+    return PT_OK;
+}
+
+int pt_ctx_set_scene(pt_ctx *c, const pt_camera *cam, const pt_object *objs, uint32_t n_objs,
+                     const pt_triangle *tris, uint32_t n_tris) {
+    if (!c || !cam || (!objs && n_objs) || (!tris && n_tris)) {
+        set_error("NULL argument");
+        return PT_ERR_INVALID;
+    }
+    host::FlatScene fs;
+    host::Reach reach;
+    std::string err;
+    if (!host::flatten_scene(*cam, objs, n_objs, tris, n_tris, fs, err, nullptr, &reach)) {
+        set_error(err);
+        return PT_ERR_INVALID;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    c->held.drop();  // (the held sums are of the scene before)
+    c->adaptive.drop();
+    c->scene_fp = 0;
+    c->fp_stale = false;
+    int rc = upload_flat(c, fs, objs, n_objs, n_tris);
+    if (rc) return rc;
     c->cam = *cam;
+    c->reach = reach;
     c->h_objs.assign(objs, objs + n_objs);
+    c->h_tris.assign(tris, tris + n_tris);
     c->h_boxes.assign((size_t)12 * n_objs, pt_triangle{});
     for (uint32_t i = 0; i < n_objs; ++i)
         if (objs[i].kind == PT_MESH && objs[i].tri_count != 0u)
@@ -1583,6 +1611,89 @@ int pt_ctx_set_scene(pt_ctx *c, const pt_camera *cam, const pt_object *objs, uin
     c->pass_rate = c->round_rate = c->ad_rate = 0.0;  // (another scene: the passes' length is measured again)
     c->pass_rate_kernel = nullptr;
     c->scene_fp = scene_fingerprint(cam, objs, n_objs, tris, n_tris);
+    return PT_OK;
+}
+
+// the tables rebuilt for the origin box B from the kept host copies (the camera is the context's unless `cam` brings another);
+// on a failure of flatten_scene the context is as it was
+static int rebuild_for_reach(pt_ctx *c, const pt_camera &cam, const host::Reach &B) {
+    host::FlatScene fs;
+    host::Reach used;
+    std::string err;
+    const uint32_t n_objs = (uint32_t)c->h_objs.size(), n_tris = (uint32_t)c->h_tris.size();
+    if (!host::flatten_scene(cam, c->h_objs.data(), n_objs, c->h_tris.data(), n_tris, fs, err, &B, &used)) {
+        set_error(err);
+        return PT_ERR_INVALID;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    const int rc = upload_flat(c, fs, c->h_objs.data(), n_objs, n_tris);
+    if (rc) return rc;
+    c->reach = used;
+    return PT_OK;
+}
+
+int pt_ctx_set_camera(pt_ctx *c, const pt_camera *cam, int *rebuilt) {
+    if (!c) return refuse("ctx is NULL");
+    if (!cam) return refuse("cam is NULL");
+    if (!c->has_scene) return refuse("no scene set: pt_ctx_set_camera moves the camera of the scene pt_ctx_set_scene gave");
+    float lens[3], su[3], sv[3];
+    host::camera_basis(*cam, lens, su, sv);
+    if (!std::isfinite(lens[0]) || !std::isfinite(lens[1]) || !std::isfinite(lens[2])) return refuse("the camera's lens centre is not finite");
+    if (rebuilt) *rebuilt = 0;
+    if (memcmp(cam, &c->cam, sizeof(pt_camera)) == 0) return PT_OK;  // nine floats, no padding
+    if (!c->reach.holds(lens)) {
+        host::Reach B = c->reach;
+        host::grow_reach(B, lens);
+        const int rc = rebuild_for_reach(c, *cam, B);
+        if (rc) return rc;
+        if (rebuilt) *rebuilt = 1;
+    }
+    c->cam = *cam;
+    // the held frames' key includes the camera (an empty one frees nothing: no HIP call then)
+    c->held.drop();
+    c->adaptive.drop();
+    c->fp_stale = true;
+    return PT_OK;
+}
+
+int pt_ctx_camera_reach(const pt_ctx *c, float lo[3], float hi[3]) {
+    if (!c || !lo || !hi) return refuse("NULL argument");
+    if (!c->has_scene) return refuse("no scene set");
+    memcpy(lo, c->reach.lo, sizeof c->reach.lo);
+    memcpy(hi, c->reach.hi, sizeof c->reach.hi);
+    return PT_OK;
+}
+
+int pt_ctx_reserve_camera_reach(pt_ctx *c, const float lo[3], const float hi[3], int *rebuilt) {
+    if (!c || !lo || !hi) return refuse("NULL argument");
+    if (!c->has_scene) return refuse("no scene set");
+    host::Reach want;
+    for (int a = 0; a < 3; ++a) {
+        if (!std::isfinite(lo[a]) || !std::isfinite(hi[a])) return refuse("a bound of the box is not finite");
+        if (lo[a] > hi[a]) return refuse("lo > hi on an axis of the box");
+        want.lo[a] = lo[a];
+        want.hi[a] = hi[a];
+    }
+    if (rebuilt) *rebuilt = 0;
+    if (c->reach.holds(want)) return PT_OK;
+    host::Reach B = c->reach;
+    for (int a = 0; a < 3; ++a) {
+        B.lo[a] = std::fmin(B.lo[a], want.lo[a]);
+        B.hi[a] = std::fmax(B.hi[a], want.hi[a]);
+    }
+    const int rc = rebuild_for_reach(c, c->cam, B);
+    if (rc) return rc;
+    if (rebuilt) *rebuilt = 1;
+    return PT_OK;
+}
+
+int pt_scene_reach(const pt_camera *cam, const pt_object *objs, uint32_t n_objs, const pt_triangle *tris, uint32_t n_tris, float lo[3],
+                   float hi[3]) {
+    if (!cam || (!objs && n_objs) || (!tris && n_tris) || !lo || !hi) return refuse("NULL argument");
+    host::Reach r;
+    host::scene_reach(*cam, objs, n_objs, tris, n_tris, r);
+    memcpy(lo, r.lo, sizeof r.lo);
+    memcpy(hi, r.hi, sizeof r.hi);
     return PT_OK;
 }
 
@@ -1835,7 +1946,7 @@ int pt_ctx_accum_save(pt_ctx *c, const char *path) {
     HIP_TRY(hipSetDevice(c->device));
     host::Checkpoint ck;
     static_cast<host::FrameCounts &>(ck) = h;
-    ck.scene_fp = c->scene_fp;
+    ck.scene_fp = scene_fp_of(c);
     std::vector<uint8_t> b;
     host::ckpt_encode_head(ck, b);
     const size_t at = b.size(), plane = 3 * (size_t)h.total * sizeof(unsigned long long);
@@ -1859,7 +1970,7 @@ int pt_ctx_accum_load(pt_ctx *c, const char *path) {
     std::vector<uint8_t> b;
     const int rc = read_checkpoint(path, host::ckpt_decode, ck, b);
     if (rc) return rc;
-    if (ck.scene_fp != c->scene_fp) {
+    if (ck.scene_fp != scene_fp_of(c)) {
         set_error(std::string(path) + " was rendered from another scene than the one set on this context");
         return PT_ERR_INVALID;
     }
@@ -2090,7 +2201,7 @@ int pt_ctx_adaptive_save(pt_ctx *c, const char *path) {
     HIP_TRY(hipSetDevice(c->device));
     host::AdaptiveCheckpoint ck;
     static_cast<host::AdaptiveFrame &>(ck) = h;
-    ck.scene_fp = c->scene_fp;
+    ck.scene_fp = scene_fp_of(c);
     int rc = h.download(ck.table, c->stream);
     if (rc) return rc;
     std::vector<uint8_t> b;
@@ -2110,7 +2221,7 @@ int pt_ctx_adaptive_load(pt_ctx *c, const char *path) {
     std::vector<uint8_t> b;
     int rc = read_checkpoint(path, host::adckpt_decode, ck, b);
     if (rc) return rc;
-    if (ck.scene_fp != c->scene_fp) {
+    if (ck.scene_fp != scene_fp_of(c)) {
         set_error(std::string(path) + " was rendered from another scene than the one set on this context");
         return PT_ERR_INVALID;
     }

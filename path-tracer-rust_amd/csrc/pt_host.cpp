@@ -268,8 +268,46 @@ bool bvh_refs_fit(uint64_t n_nodes, uint64_t n_pair_records) {
     return n_nodes < (1ull << 26) && (n_pair_records << kBvhLeafBits) < (1ull << 26);
 }
 
+void scene_reach(const pt_camera &cam, const pt_object *objs, uint32_t n_objs, const pt_triangle *tris, uint32_t n_tris, Reach &out) {
+    const float finf = std::numeric_limits<float>::infinity();
+    vec3 slo = mk(finf, finf, finf), shi = mk(-finf, -finf, -finf);
+    float lens[3], su[3], sv[3];
+    camera_basis(cam, lens, su, sv);
+    BvhBuilder::grow(slo, shi, ld(lens), ld(lens));
+    for (uint32_t i = 0; i < n_objs; ++i) {
+        const vec3 pos = ld(objs[i].position);
+        if (objs[i].kind == PT_SPHERE) {
+            const float r = f_abs(objs[i].radius);
+            BvhBuilder::grow(slo, shi, pos - mk(r, r, r), pos + mk(r, r, r));
+        } else if (objs[i].kind == PT_MESH && (uint64_t)objs[i].tri_offset + objs[i].tri_count <= n_tris) {
+            for (uint32_t k = objs[i].tri_offset; k < objs[i].tri_offset + objs[i].tri_count; ++k) {
+                BvhBuilder::grow(slo, shi, ld(tris[k].a) + pos, ld(tris[k].a) + pos);
+                BvhBuilder::grow(slo, shi, ld(tris[k].b) + pos, ld(tris[k].b) + pos);
+                BvhBuilder::grow(slo, shi, ld(tris[k].c) + pos, ld(tris[k].c) + pos);
+            }
+        }
+    }
+    st(out.lo, slo);
+    st(out.hi, shi);
+}
+
+bool grow_reach(Reach &B, const float lens[3]) {
+    bool grew = false;
+    for (int a = 0; a < 3; ++a) {
+        if (lens[a] < B.lo[a]) {
+            B.lo[a] = lens[a] - (B.lo[a] - lens[a]);
+            grew = true;
+        }
+        if (lens[a] > B.hi[a]) {
+            B.hi[a] = lens[a] + (lens[a] - B.hi[a]);
+            grew = true;
+        }
+    }
+    return grew;
+}
+
 bool flatten_scene(const pt_camera &cam, const pt_object *objs, uint32_t n_objs, const pt_triangle *tris,
-                   uint32_t n_tris, FlatScene &out, std::string &err) {
+                   uint32_t n_tris, FlatScene &out, std::string &err, const Reach *origin_box, Reach *used) {
     if (n_objs >= (1u << 30) || n_tris >= (1u << 30)) {
         err = "scene too large";
         return false;
@@ -279,26 +317,16 @@ bool flatten_scene(const pt_camera &cam, const pt_object *objs, uint32_t n_objs,
     out.tri_pairs.clear();
     out.bvh_nodes.clear();
     out.tri_shade.assign(n_tris, TriShade{});
-    // R: bound on |ray origin - any vertex|: ray origins are the lens centre or points on objects
+    // R: bound on |ray origin - any vertex|: ray origins are the lens centre or points on objects - or, with an origin box,
+    // the lens centre of any camera inside it
     const float finf = std::numeric_limits<float>::infinity();
-    vec3 slo = mk(finf, finf, finf), shi = mk(-finf, -finf, -finf);
-    {
-        float lens[3], su[3], sv[3];
-        camera_basis(cam, lens, su, sv);
-        BvhBuilder::grow(slo, shi, ld(lens), ld(lens));
-        for (uint32_t i = 0; i < n_objs; ++i) {
-            const vec3 pos = ld(objs[i].position);
-            if (objs[i].kind == PT_SPHERE) {
-                const float r = f_abs(objs[i].radius);
-                BvhBuilder::grow(slo, shi, pos - mk(r, r, r), pos + mk(r, r, r));
-            } else if (objs[i].kind == PT_MESH && (uint64_t)objs[i].tri_offset + objs[i].tri_count <= n_tris) {
-                for (uint32_t k = objs[i].tri_offset; k < objs[i].tri_offset + objs[i].tri_count; ++k) {
-                    BvhBuilder::grow(slo, shi, ld(tris[k].a) + pos, ld(tris[k].a) + pos);
-                    BvhBuilder::grow(slo, shi, ld(tris[k].b) + pos, ld(tris[k].b) + pos);
-                    BvhBuilder::grow(slo, shi, ld(tris[k].c) + pos, ld(tris[k].c) + pos);
-                }
-            }
-        }
+    Reach reach;
+    scene_reach(cam, objs, n_objs, tris, n_tris, reach);
+    vec3 slo = ld(reach.lo), shi = ld(reach.hi);
+    if (origin_box) BvhBuilder::grow(slo, shi, ld(origin_box->lo), ld(origin_box->hi));
+    if (used) {
+        st(used->lo, slo);
+        st(used->hi, shi);
     }
     const float scene_R = n_objs ? length(shi - slo) : 0.0f;
     std::vector<uint8_t> claimed(n_tris, 0);

@@ -103,8 +103,25 @@ struct RoundLaunch {
     uint32_t split, lane_spp, grid;
 };
 RoundLaunch round_launch(uint64_t entries, uint32_t n_split, uint32_t s_here, uint32_t n_cus);
+// The box that bounds every ray origin of a scene: the lens centre and the objects (spheres by their extent, meshes by their
+// translated vertices).  scene_R, the box paddings, admit, rr_in and the filters' pads are conservative bounds derived from it
+// and from nothing else of the camera: they hold for every camera whose lens centre lies inside (pt_ctx_set_camera).
+struct Reach {
+    float lo[3], hi[3];
+    bool holds(const float p[3]) const {  // false for a NaN
+        return lo[0] <= p[0] && p[0] <= hi[0] && lo[1] <= p[1] && p[1] <= hi[1] && lo[2] <= p[2] && p[2] <= hi[2];
+    }
+    bool holds(const Reach &b) const { return holds(b.lo) && holds(b.hi); }
+};
+// the box flatten_scene derives a scene's bounds for when it is given none
+void scene_reach(const pt_camera &cam, const pt_object *objs, uint32_t n_objs, const pt_triangle *tris, uint32_t n_tris, Reach &out);
+// pt_ctx_set_camera's growth rule, in binary32: a bound the lens centre violates moves beyond it by the overshoot once more
+// (lo = lens - (lo - lens), hi = lens + (lens - hi)), the others stay.  True when B changed (the lens centre was outside).
+bool grow_reach(Reach &B, const float lens[3]);
+// `origin_box` (optional): the bounds are derived for scene_reach's box united with it - what the call computes without one
+// when the box lies inside scene_reach's
 bool flatten_scene(const pt_camera &cam, const pt_object *objs, uint32_t n_objs, const pt_triangle *tris,
-                   uint32_t n_tris, FlatScene &out, std::string &err);
+                   uint32_t n_tris, FlatScene &out, std::string &err, const Reach *origin_box = nullptr, Reach *used = nullptr);
 
 // ---- the arithmetic of a frame call and of the frame pt_ctx_accumulate holds (pt_api.hip): pure, tested on the CPU -----------
 // a valid cfg's band in [*idx_begin, *idx_end); PT_ERR_INVALID + message otherwise

@@ -8,6 +8,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -25,6 +26,7 @@ static void usage() {
             "              [--denoise [N]] [--noise-target X [--noise-map FILE.pfm]]\n"
             "              [--adaptive X [--tile N] [--spp-map FILE.pfm] [--error-map FILE.pfm] [--adaptive-checkpoint FILE]]\n"
             "              [--denoise-var [N]] [--preview FILE.ppm [--preview-size WxH] [--exposure E]] [--trace-scale K]\n"
+            "              [--orbit N [--orbit-step DEG]]\n"
             "  --checkpoint FILE: continue from the samples FILE holds (if it exists), render up to <samplesPerPixel> in all and\n"
             "                     save them to FILE; one GPU only; the seed defaults to 0 instead of the clock, so that the same\n"
             "                     command continues the same frame\n"
@@ -56,7 +58,14 @@ static void usage() {
             "  --trace-scale K: K = 2..8: trace the paths at ceil(W/K) x ceil(H/K), the first-hit guides at both sizes, and fill the\n"
             "           frame in through the guides with albedo and normals (pt_ctx_upsample, default parameters); the image written\n"
             "           is the full-size frame; combines with --denoise and --preview; one GPU only; not with --checkpoint,\n"
-            "           --noise-target or --adaptive\n");
+            "           --noise-target or --adaptive\n"
+            "  --orbit N: with --preview FILE.ppm: N frames of a viewport whose camera turns about the vertical axis through the\n"
+            "           origin, frame k by k * DEG degrees (--orbit-step DEG, default 2) from the scene's own camera: per frame\n"
+            "           pt_ctx_set_camera, pt_ctx_render at <samplesPerPixel>, the first-hit guides, pt_ctx_reproject_var against\n"
+            "           frame k-1, pt_ctx_denoise_var (sigma_var 2) and pt_ctx_present; the frames go to FILE-000.ppm, FILE-001.ppm,\n"
+            "           ..., one line per frame to stderr (the camera update's milliseconds, whether it rebuilt the scene, the\n"
+            "           frame's total); one GPU only; not with --trace-scale, --adaptive, --noise-target, --checkpoint, --denoise or\n"
+            "           --denoise-var\n");
 }
 
 static std::vector<std::string> scene_ids(const std::string &root) {
@@ -460,6 +469,113 @@ static int write_aovs(const pt_config *frame, uint32_t spp, pt_scene *sc, const 
     return 0;
 }
 
+// --orbit: the scene's camera turned by `degrees` about the vertical axis through the origin - binary64 arithmetic, rounded to
+// binary32 once (always from camera 0, never from the frame before)
+static pt_camera orbit_camera(const pt_camera &cam, double degrees) {
+    const double a = degrees * (M_PI / 180.0), c = cos(a), s = sin(a);
+    pt_camera o = cam;
+    const float *in[2] = {cam.position, cam.direction};
+    float *out[2] = {o.position, o.direction};
+    for (int i = 0; i < 2; ++i) {
+        const double x = in[i][0], z = in[i][2];
+        out[i][0] = (float)(c * x + s * z);
+        out[i][2] = (float)(-s * x + c * z);
+    }
+    return o;
+}
+
+// one side of the orbit loop's history: device planes of one frame
+struct OrbitSide {
+    float *color, *len, *moments, *depth, *normal;
+    int32_t *id;
+};
+
+// --orbit N: the viewport loop of INTEGRATION.md on one context on one GPU, the camera moved with pt_ctx_set_camera
+static int render_orbit(const pt_config *cfg, pt_scene *sc, uint32_t frames, double step, const std::string &preview, uint32_t ow,
+                        uint32_t oh, float exposure) {
+    using clk = std::chrono::steady_clock;
+    auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    int dev = 0;
+    if (const char *e = getenv("PT_DEVICE")) dev = atoi(e);
+    uint32_t n_objs = 0, n_tris = 0;
+    const pt_object *objs = pt_scene_objects(sc, &n_objs);
+    const pt_triangle *tris = pt_scene_triangles(sc, &n_tris);
+    const pt_camera cam0 = *pt_scene_camera(sc);
+    const uint32_t w = cfg->width, h = cfg->height;
+    const size_t npix = (size_t)w * h;
+    pt_present_params pp;
+    memset(&pp, 0, sizeof pp);
+    pp.out_width = ow;
+    pp.out_height = oh;
+    pp.exposure = exposure;
+    pp.format = PT_PRESENT_RGB8;
+    if (!ow) ow = w, oh = h;
+    std::vector<uint8_t> px((size_t)ow * oh * 3);
+    const std::string stem = preview.size() > 4 && preview.substr(preview.size() - 4) == ".ppm" ? preview.substr(0, preview.size() - 4) : preview;
+    pt_ctx *ctx = nullptr;
+    // two sides of 11 floats per pixel, then albedo (3), the error (1) and the frame shown (3)
+    void *d_buf = nullptr, *d_px = nullptr;
+    int rc = pt_ctx_create(dev, &ctx);
+    if (!rc) rc = pt_ctx_set_scene(ctx, &cam0, objs, n_objs, tris, n_tris);
+    if (!rc) rc = pt_device_malloc(dev, npix * 29 * sizeof(float), &d_buf);
+    if (!rc) rc = pt_device_malloc(dev, px.size(), &d_px);
+    OrbitSide side[2];
+    float *d_albedo = nullptr, *d_error = nullptr, *d_shown = nullptr;
+    if (!rc) {
+        float *f = (float *)d_buf;
+        for (OrbitSide &s : side) {
+            s.color = f, s.len = f + npix * 3, s.moments = f + npix * 4, s.depth = f + npix * 6, s.normal = f + npix * 7;
+            s.id = (int32_t *)(f + npix * 10);
+            f += npix * 11;
+        }
+        d_albedo = f, d_error = f + npix * 3, d_shown = f + npix * 4;
+    }
+    OrbitSide *cur = &side[0], *hist = &side[1];
+    pt_camera hist_cam = cam0;
+    for (uint32_t k = 0; k < frames && !rc; ++k) {
+        const pt_camera cam = orbit_camera(cam0, (double)k * step);
+        const bool hh = k != 0u;
+        int rebuilt = 0;
+        pt_stats st;
+        const clk::time_point t0 = clk::now();
+        rc = pt_ctx_set_camera(ctx, &cam, &rebuilt);
+        const clk::time_point t1 = clk::now();
+        if (!rc) rc = pt_ctx_render(ctx, cfg, cur->color, nullptr, nullptr, nullptr, nullptr, &st);
+        if (!rc) rc = pt_ctx_render_aov(ctx, cfg, d_albedo, cur->normal, cur->depth, cur->id, nullptr);
+        pt_reproject_var_params rp;
+        memset(&rp, 0, sizeof rp);
+        rp.weight = cfg->spp;
+        if (!rc)
+            rc = pt_ctx_reproject_var(ctx, w, h, &rp, &cam, cur->color, cur->depth, cur->id, cur->normal, hh ? &hist_cam : nullptr,
+                                      hh ? hist->color : nullptr, hh ? hist->len : nullptr, hh ? hist->moments : nullptr,
+                                      hh ? hist->depth : nullptr, hh ? hist->id : nullptr, hh ? hist->normal : nullptr, cur->color,
+                                      cur->len, cur->moments, d_error, nullptr);
+        pt_denoise_var_params dp;
+        memset(&dp, 0, sizeof dp);
+        dp.sigma_var = 2.0f;
+        if (!rc) rc = pt_ctx_denoise_var(ctx, w, h, &dp, cur->color, d_error, d_albedo, cur->normal, cur->depth, d_shown, nullptr);
+        if (!rc) rc = pt_ctx_present(ctx, w, h, &pp, d_shown, (uint8_t *)d_px, nullptr);
+        if (!rc) rc = pt_device_download(dev, px.data(), d_px, px.size());
+        const clk::time_point t2 = clk::now();
+        if (rc) break;
+        std::swap(cur, hist);
+        hist_cam = cam;
+        char name[32];
+        snprintf(name, sizeof name, "-%03u.ppm", k);
+        const std::string path = stem + name;
+        rc = pt_write_ppm8(path.c_str(), px.data(), ow, oh);
+        if (rc) break;
+        fprintf(stderr, "frame %u: pt_ctx_set_camera %.3f ms (%s), frame %.3f ms\n", k, ms(t0, t1), rebuilt ? "rebuilt" : "not rebuilt",
+                ms(t0, t2));
+        printf("wrote %s\n", path.c_str());
+    }
+    if (rc) fprintf(stderr, "--orbit failed (%d): %s\n", rc, pt_last_error());
+    if (d_px) pt_device_free(dev, d_px);
+    if (d_buf) pt_device_free(dev, d_buf);
+    if (ctx) pt_ctx_destroy(ctx);
+    return rc;
+}
+
 int main(int argc, char **argv) {
     if (argc < 4) {
         usage();
@@ -479,6 +595,9 @@ int main(int argc, char **argv) {
     std::string preview;
     uint32_t preview_w = 0, preview_h = 0;
     float exposure = 0.0f;
+    uint32_t orbit_frames = 0;
+    double orbit_step = 2.0;
+    bool orbit_step_given = false;
     for (int i = 4; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&]() -> const char * { return i + 1 < argc ? argv[++i] : ""; };
@@ -582,6 +701,24 @@ int main(int argc, char **argv) {
                 return 1;
             }
         }
+        else if (a == "--orbit") {
+            const char *v = next();
+            orbit_frames = *v && strspn(v, "0123456789") == strlen(v) ? (uint32_t)strtoul(v, nullptr, 10) : 0u;
+            if (!orbit_frames || orbit_frames > 1000u) {
+                fprintf(stderr, "--orbit needs N = 1..1000 frames\n");
+                return 1;
+            }
+        }
+        else if (a == "--orbit-step") {
+            char *e = nullptr;
+            const char *v = next();
+            orbit_step = strtod(v, &e);
+            orbit_step_given = true;
+            if (e == v || *e || !std::isfinite(orbit_step)) {
+                fprintf(stderr, "--orbit-step needs a finite number of degrees\n");
+                return 1;
+            }
+        }
         else if (a == "--denoise-var") {
             denoise_var_spp = 16;
             if (i + 1 < argc && argv[i + 1][0] != '\0' && strspn(argv[i + 1], "0123456789") == strlen(argv[i + 1])) {
@@ -610,6 +747,20 @@ int main(int argc, char **argv) {
     }
     if (!spp || !res_y || !width) {
         usage();
+        return 1;
+    }
+    if (orbit_step_given && !orbit_frames) {
+        fprintf(stderr, "--orbit-step goes with --orbit N\n");
+        return 1;
+    }
+    if (orbit_frames && preview.empty()) {
+        fprintf(stderr, "--orbit needs --preview FILE.ppm: the frames are written as FILE-000.ppm, FILE-001.ppm, ...\n");
+        return 1;
+    }
+    if (orbit_frames && (gpus > 1 || trace_scale || adaptive.target >= 0.0f || noise.target > 0.0f || !checkpoint.empty() || denoise_spp || denoise_var_spp ||
+                         aov_spp)) {
+        fprintf(stderr, "--orbit works with one GPU only and not with --trace-scale, --adaptive, --noise-target, --checkpoint, --denoise, "
+                        "--denoise-var or --aov\n");
         return 1;
     }
     if (!checkpoint.empty() && gpus > 1) {
@@ -712,6 +863,11 @@ int main(int argc, char **argv) {
     cfg.spp = spp;
     cfg.backend = backend == "megakernel" ? PT_BACKEND_MEGAKERNEL : PT_BACKEND_WAVEFRONT;
     cfg.seed = seed;
+    if (orbit_frames) {
+        rc = render_orbit(&cfg, sc, orbit_frames, orbit_step, preview, preview_w, preview_h, exposure);
+        pt_scene_free(sc);
+        return rc ? 2 : 0;
+    }
     std::vector<float> img((size_t)width * res_y * 3, 0.0f);
     pt_stats st;
     DeviceFrame df;
