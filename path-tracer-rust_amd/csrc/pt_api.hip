@@ -1385,6 +1385,28 @@ int read_checkpoint(const char *path, Decode decode, Ckpt &ck, std::vector<uint8
     return PT_OK;
 }
 
+// An image pass once its arguments are checked (host::check_*: everything that can be refused is refused there, before the device is
+// touched): the context's device is made current, the pass runs on the caller's stream or the context's - launch(st) grows what
+// scratch it needs and issues the kernels; its error is the call's - and the call waits for it.
+template <class Launch>
+int run_image_pass(pt_ctx *c, void *hip_stream, Launch launch) {
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    const int rc = launch(st);
+    if (rc) return rc;
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    return PT_OK;
+}
+
+// pt_*_defaults: the values a zero field of a pass's parameters stands for
+template <class Params>
+int give_defaults(Params *out, const Params &defaults) {
+    if (!out) return refuse("out is NULL");
+    *out = defaults;
+    return PT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2662,14 +2684,8 @@ int pt_ctx_primary_rays(pt_ctx *c, uint32_t width, uint32_t height, uint64_t see
 
 int pt_ctx_render_aov(pt_ctx *c, const pt_config *cfg, float *d_albedo, float *d_normal, float *d_depth, int32_t *d_object_id,
                       void *hip_stream) {
-    if (!c || !cfg) {
-        set_error("NULL argument");
-        return PT_ERR_INVALID;
-    }
-    if (!d_albedo && !d_normal && !d_depth && !d_object_id) {
-        set_error("every output is NULL");
-        return PT_ERR_INVALID;
-    }
+    if (!c || !cfg) return refuse("NULL argument");
+    if (!d_albedo && !d_normal && !d_depth && !d_object_id) return refuse("every output is NULL");
     // the frame's pixels and samples as pt_ctx_render reads them; backend, pass sizes and pipelines do not apply
     pt_config fc = *cfg;
     fc.backend = PT_BACKEND_WAVEFRONT;
@@ -2679,185 +2695,78 @@ int pt_ctx_render_aov(pt_ctx *c, const pt_config *cfg, float *d_albedo, float *d
     const FrameParams F = make_frame(c, &fc, ib, ie);
     if (F.npix == 0u) return PT_OK;  // this rank owns no chunk of the band
     const DevScene S = form_for(c, cfg->flags).scene;  // (k_aov reads neither the candidate scan nor an LDS layout)
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    launch_aov(st, S, F, d_albedo, d_normal, d_depth, d_object_id);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(st));
-    return PT_OK;
+    return run_image_pass(c, hip_stream, [&](hipStream_t st) {
+        launch_aov(st, S, F, d_albedo, d_normal, d_depth, d_object_id);
+        return PT_OK;
+    });
 }
 
-// pt_ctx_denoise (d_error NULL, sigma = sigma_color) and pt_ctx_denoise_var (sigma = sigma_var) once their arguments are checked
-static int run_denoise(pt_ctx *c, uint32_t width, uint32_t height, uint32_t levels, float sigma, float sigma_depth,
-                       uint32_t flags, const float *d_color, const float *d_error, const float *d_albedo, const float *d_normal,
-                       const float *d_depth, float *d_out, void *hip_stream) {
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t npix = (size_t)width * height;
-    for (int k = 0; k < 2; ++k) {
-        const int rc = c->dn_u[k].ensure(npix);
-        if (rc) return rc;
-    }
-    {
-        const int rc = c->dn_guide.ensure(npix);
-        if (rc) return rc;
-    }
-    DenoiseFrame f{};
-    f.width = width;
-    f.height = height;
-    f.color = d_color;
-    f.albedo = (flags & PT_DENOISE_NO_DEMODULATE) ? nullptr : d_albedo;
-    f.normal = d_normal;
-    f.depth = d_depth;
-    f.error = d_error;
-    f.guide = c->dn_guide.p;
-    f.u[0] = c->dn_u[0].p;
-    f.u[1] = c->dn_u[1].p;
-    f.out = d_out;
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    launch_dn_prepare(st, f);
-    const float kv = sigma * sigma;
-    float scale = 1.0f;  // 2^-i
-    for (uint32_t i = 0; i < levels; ++i, scale *= 0.5f) {
-        const uint32_t s = 1u << i;
-        const float sc = sigma * scale;
-        const float rc = d_error ? kv : 1.0f / (sc * sc);  // with an error map the colour scale is per pixel, from kv
-        const float sds = sigma_depth * (float)s;
-        launch_dn_level(st, f, i, rc, sds, i + 1u == levels, s <= c->tune.dn_lds_maxstep);
-    }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(st));
-    return PT_OK;
+// pt_ctx_denoise and pt_ctx_denoise_var once host::check_denoise* has passed: the scratch, prepare, the levels of the schedule
+static int run_denoise(pt_ctx *c, DenoiseCall &call, void *hip_stream) {
+    return run_image_pass(c, hip_stream, [&](hipStream_t st) {
+        DenoiseFrame &f = call.f;
+        const size_t npix = (size_t)f.width * f.height;
+        int rc;
+        if ((rc = c->dn_u[0].ensure(npix)) || (rc = c->dn_u[1].ensure(npix)) || (rc = c->dn_guide.ensure(npix))) return rc;
+        f.guide = c->dn_guide.p;
+        f.u[0] = c->dn_u[0].p;
+        f.u[1] = c->dn_u[1].p;
+        launch_dn_prepare(st, f);
+        for (uint32_t i = 0; i < call.levels; ++i)
+            launch_dn_level(st, f, i, call.rc[i], call.sds[i], i + 1u == call.levels, (1u << i) <= c->tune.dn_lds_maxstep);
+        return PT_OK;
+    });
 }
 
-// the values a zero field of pt_denoise_params stands for: the minimum of the CPU study (profiles/denoise_cpu_study.json)
-static const pt_denoise_params kDenoiseDefaults = {5u, 2.0f, 0.0f, 0.03125f, 0u};
-
-int pt_denoise_defaults(pt_denoise_params *out) {
-    if (!out) {
-        set_error("out is NULL");
-        return PT_ERR_INVALID;
-    }
-    *out = kDenoiseDefaults;
-    return PT_OK;
-}
+int pt_denoise_defaults(pt_denoise_params *out) { return give_defaults(out, kDenoiseDefaults); }
 
 int pt_ctx_denoise(pt_ctx *c, uint32_t width, uint32_t height, const pt_denoise_params *params, const float *d_color,
                    const float *d_albedo, const float *d_normal, const float *d_depth, float *d_out, void *hip_stream) {
-    // everything that can be refused is refused here, before the device is touched
-    pt_denoise_params P = kDenoiseDefaults;
-    if (params) {
-        if (params->levels > 8u) return refuse("pt_denoise_params.levels exceeds 8");
-        if (!host::finite_nonneg(params->sigma_color) || !host::finite_nonneg(params->sigma_depth))
-            return refuse("pt_denoise_params: a sigma is negative or not finite");
-        if (!(params->sigma_normal_pow == 0.0f)) return refuse("pt_denoise_params.sigma_normal_pow is reserved and must be 0");
-        if (params->flags & ~PT_DENOISE_NO_DEMODULATE) return refuse("pt_denoise_params.flags: unknown bits");
-        if (params->levels) P.levels = params->levels;
-        if (params->sigma_color != 0.0f) P.sigma_color = params->sigma_color;
-        if (params->sigma_depth != 0.0f) P.sigma_depth = params->sigma_depth;
-        P.flags = params->flags;
-    }
-    if (!width || !height) return refuse("width and height must be positive");
-    if ((uint64_t)width * height > (1ull << 28)) return refuse("width*height exceeds 2^28");
-    if (!d_color || !d_out) return refuse("d_color or d_out is NULL");
-    if (!c) return refuse("ctx is NULL");
-    return run_denoise(c, width, height, P.levels, P.sigma_color, P.sigma_depth, P.flags, d_color, nullptr, d_albedo, d_normal,
-                       d_depth, d_out, hip_stream);
+    DenoiseCall call;
+    const int rc = host::check_denoise(c, width, height, params, d_color, d_albedo, d_normal, d_depth, d_out, call);
+    return rc ? rc : run_denoise(c, call, hip_stream);
 }
 
-// the values a zero field of pt_denoise_var_params stands for: the minimum of the CPU study (profiles/denoise_var_cpu_study.json)
-static const pt_denoise_var_params kDenoiseVarDefaults = {5u, 1.0f, 0.125f, 0u};
-
-int pt_denoise_var_defaults(pt_denoise_var_params *out) {
-    if (!out) {
-        set_error("out is NULL");
-        return PT_ERR_INVALID;
-    }
-    *out = kDenoiseVarDefaults;
-    return PT_OK;
-}
+int pt_denoise_var_defaults(pt_denoise_var_params *out) { return give_defaults(out, kDenoiseVarDefaults); }
 
 int pt_ctx_denoise_var(pt_ctx *c, uint32_t width, uint32_t height, const pt_denoise_var_params *params, const float *d_color,
                        const float *d_error, const float *d_albedo, const float *d_normal, const float *d_depth, float *d_out,
                        void *hip_stream) {
-    // everything that can be refused is refused here, before the device is touched
-    pt_denoise_var_params P = kDenoiseVarDefaults;
-    if (params) {
-        if (params->levels > 8u) return refuse("pt_denoise_var_params.levels exceeds 8");
-        if (!host::finite_nonneg(params->sigma_var) || !host::finite_nonneg(params->sigma_depth))
-            return refuse("pt_denoise_var_params: a sigma is negative or not finite");
-        if (params->flags & ~PT_DENOISE_NO_DEMODULATE) return refuse("pt_denoise_var_params.flags: unknown bits");
-        if (params->levels) P.levels = params->levels;
-        if (params->sigma_var != 0.0f) P.sigma_var = params->sigma_var;
-        if (params->sigma_depth != 0.0f) P.sigma_depth = params->sigma_depth;
-        P.flags = params->flags;
-    }
-    if (!width || !height) return refuse("width and height must be positive");
-    if ((uint64_t)width * height > (1ull << 28)) return refuse("width*height exceeds 2^28");
-    if (!d_color) return refuse("d_color is NULL");
-    if (!d_error) return refuse("d_error is NULL: pt_ctx_denoise is the filter without a noise estimate");
-    if (!d_out) return refuse("d_out is NULL");
-    if (!c) return refuse("ctx is NULL");
-    return run_denoise(c, width, height, P.levels, P.sigma_var, P.sigma_depth, P.flags, d_color, d_error, d_albedo, d_normal,
-                       d_depth, d_out, hip_stream);
+    DenoiseCall call;
+    const int rc = host::check_denoise_var(c, width, height, params, d_color, d_error, d_albedo, d_normal, d_depth, d_out, call);
+    return rc ? rc : run_denoise(c, call, hip_stream);
 }
 
 int pt_ctx_present(pt_ctx *c, uint32_t width, uint32_t height, const pt_present_params *params, const float *d_rgb, uint8_t *d_out,
                    void *hip_stream) {
-    // everything that can be refused is refused here, before the device is touched
-    pt_present_params P{};
-    if (params) P = *params;
-    if (!host::finite_nonneg(P.exposure)) return refuse("pt_present_params.exposure is negative or not finite");
-    if (P.format != PT_PRESENT_RGBA8 && P.format != PT_PRESENT_RGB8) return refuse("pt_present_params.format: unknown format");
-    if (P.flags & ~PT_PRESENT_FRAMEBUFFER_ORDER) return refuse("pt_present_params.flags: unknown bits");
-    if (!width || !height) return refuse("width and height must be positive");
-    if ((P.out_width == 0u) != (P.out_height == 0u)) return refuse("pt_present_params: one of out_width, out_height is 0 alone");
-    const uint32_t ow = P.out_width ? P.out_width : width, oh = P.out_height ? P.out_height : height;
-    if ((uint64_t)width * height > (1ull << 28) || (uint64_t)ow * oh > (1ull << 28))
-        return refuse("width*height or out_width*out_height exceeds 2^28");
-    if (!d_rgb) return refuse("d_rgb is NULL");
-    if (!d_out) return refuse("d_out is NULL");
-    if (!c) return refuse("ctx is NULL");
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    if (!c->pr_table.p) {
-        const int rc = c->pr_table.ensure(256);
-        if (rc) return rc;
-        // (the table lives as long as the process: the copy may read it whenever it runs)
-        const hipError_t e = hipMemcpyAsync(c->pr_table.p, present_table(), 256 * sizeof(uint32_t), hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) {
-            c->pr_table.release();
-            set_error(std::string("uploading the present table: ") + hipGetErrorString(e));
-            return PT_ERR_HIP;
+    PresentFrame f;
+    const int rc = host::check_present(c, width, height, params, d_rgb, d_out, f);
+    if (rc) return rc;
+    return run_image_pass(c, hip_stream, [&](hipStream_t st) {
+        if (!c->pr_table.p) {
+            const int rt = c->pr_table.ensure(256);
+            if (rt) return rt;
+            // (the table lives as long as the process: the copy may read it whenever it runs)
+            const hipError_t e = hipMemcpyAsync(c->pr_table.p, present_table(), 256 * sizeof(uint32_t), hipMemcpyHostToDevice, st);
+            if (e != hipSuccess) {
+                c->pr_table.release();
+                set_error(std::string("uploading the present table: ") + hipGetErrorString(e));
+                return PT_ERR_HIP;
+            }
         }
-    }
-    PresentFrame f{};
-    f.rgb = d_rgb;
-    f.out = d_out;
-    f.width = width;
-    f.height = height;
-    f.out_width = ow;
-    f.out_height = oh;
-    f.bpp = P.format == PT_PRESENT_RGBA8 ? 4u : 3u;
-    f.flip = !(P.flags & PT_PRESENT_FRAMEBUFFER_ORDER);
-    f.exposure = P.exposure == 0.0f ? 1.0f : P.exposure;
-    f.table = c->pr_table.p;
-    if (ow != width || oh != height) {
-        const int rc = c->pr_mid.ensure(3 * (size_t)width * oh);
-        if (rc) return rc;
-        f.mid = c->pr_mid.p;
-    }
-    launch_present(st, f);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(st));
-    return PT_OK;
+        f.table = c->pr_table.p;
+        if (f.resamples()) {
+            const int rm = c->pr_mid.ensure(3 * (size_t)f.width * f.out_height);
+            if (rm) return rm;
+            f.mid = c->pr_mid.p;
+        }
+        launch_present(st, f);
+        return PT_OK;
+    });
 }
 
 int pt_reproject_defaults(pt_reproject_params *out) {
-    if (!out) {
-        set_error("out is NULL");
-        return PT_ERR_INVALID;
-    }
-    *out = pt_reproject_params{1u, kReprojectMaxHistory, kReprojectDepthTol, kReprojectNormalMin, 0u};
-    return PT_OK;
+    return give_defaults(out, pt_reproject_params{1u, kReprojectMaxHistory, kReprojectDepthTol, kReprojectNormalMin, 0u});
 }
 
 int pt_ctx_reproject(pt_ctx *c, uint32_t width, uint32_t height, const pt_reproject_params *params, const pt_camera *cam,
@@ -2865,27 +2774,19 @@ int pt_ctx_reproject(pt_ctx *c, uint32_t width, uint32_t height, const pt_reproj
                      const pt_camera *hist_cam, const float *d_hist_color, const float *d_hist_len, const float *d_hist_depth,
                      const int32_t *d_hist_object_id, const float *d_hist_normal, float *d_out_color, float *d_out_len,
                      void *hip_stream) {
-    // everything that can be refused is refused here, before the device is touched
     ReprojectFrame f;
     const int rc = host::check_reproject(c, width, height, params, cam, d_color, d_depth, d_object_id, d_normal, hist_cam, d_hist_color,
                                          d_hist_len, d_hist_depth, d_hist_object_id, d_hist_normal, d_out_color, d_out_len, f);
     if (rc) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    launch_reproject(st, f);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(st));
-    return PT_OK;
+    return run_image_pass(c, hip_stream, [&](hipStream_t st) {
+        launch_reproject(st, f);
+        return PT_OK;
+    });
 }
 
 int pt_reproject_var_defaults(pt_reproject_var_params *out) {
-    if (!out) {
-        set_error("out is NULL");
-        return PT_ERR_INVALID;
-    }
-    *out = pt_reproject_var_params{1u, kReprojectMaxHistory, kReprojectDepthTol, kReprojectNormalMin, kReprojectVarMinFrames,
-                                   kReprojectVarRadius, 0u};
-    return PT_OK;
+    return give_defaults(out, pt_reproject_var_params{1u, kReprojectMaxHistory, kReprojectDepthTol, kReprojectNormalMin,
+                                                      kReprojectVarMinFrames, kReprojectVarRadius, 0u});
 }
 
 int pt_ctx_reproject_var(pt_ctx *c, uint32_t width, uint32_t height, const pt_reproject_var_params *params, const pt_camera *cam,
@@ -2893,47 +2794,36 @@ int pt_ctx_reproject_var(pt_ctx *c, uint32_t width, uint32_t height, const pt_re
                          const pt_camera *hist_cam, const float *d_hist_color, const float *d_hist_len, const float *d_hist_moments,
                          const float *d_hist_depth, const int32_t *d_hist_object_id, const float *d_hist_normal, float *d_out_color,
                          float *d_out_len, float *d_out_moments, float *d_error, void *hip_stream) {
-    // everything that can be refused is refused here, before the device is touched
     ReprojectVarFrame v;
     const int rc = host::check_reproject_var(c, width, height, params, cam, d_color, d_depth, d_object_id, d_normal, hist_cam,
                                              d_hist_color, d_hist_len, d_hist_moments, d_hist_depth, d_hist_object_id, d_hist_normal,
                                              d_out_color, d_out_len, d_out_moments, d_error, v);
     if (rc) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    const int rs = c->rv_s.ensure((size_t)width * height);
-    if (rs) return rs;
-    v.s_plane = c->rv_s.p;
-    launch_reproject_var(st, v);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(st));
-    return PT_OK;
+    return run_image_pass(c, hip_stream, [&](hipStream_t st) {
+        const int rs = c->rv_s.ensure((size_t)width * height);
+        if (rs) return rs;
+        v.s_plane = c->rv_s.p;
+        launch_reproject_var(st, v);
+        return PT_OK;
+    });
 }
 
 int pt_upsample_defaults(pt_upsample_params *out) {
-    if (!out) {
-        set_error("out is NULL");
-        return PT_ERR_INVALID;
-    }
-    *out = pt_upsample_params{kUpsampleDepthTol, kUpsampleNormalMin, 0u};
-    return PT_OK;
+    return give_defaults(out, pt_upsample_params{kUpsampleDepthTol, kUpsampleNormalMin, 0u});
 }
 
 int pt_ctx_upsample(pt_ctx *c, uint32_t width, uint32_t height, uint32_t lo_width, uint32_t lo_height, const pt_upsample_params *params,
                     const float *d_lo_color, const float *d_lo_depth, const int32_t *d_lo_object_id, const float *d_lo_normal,
                     const float *d_lo_albedo, const float *d_depth, const int32_t *d_object_id, const float *d_normal,
                     const float *d_albedo, float *d_out_color, float *d_out_weight, void *hip_stream) {
-    // everything that can be refused is refused here, before the device is touched
     UpsampleFrame f;
     const int rc = host::check_upsample(c, width, height, lo_width, lo_height, params, d_lo_color, d_lo_depth, d_lo_object_id, d_lo_normal,
                                         d_lo_albedo, d_depth, d_object_id, d_normal, d_albedo, d_out_color, d_out_weight, f);
     if (rc) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    launch_upsample(st, f);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(st));
-    return PT_OK;
+    return run_image_pass(c, hip_stream, [&](hipStream_t st) {
+        launch_upsample(st, f);
+        return PT_OK;
+    });
 }
 
 // one band on one device into the host framebuffer

@@ -8,7 +8,15 @@
 
 #include <cstdint>
 
+#include "../../include/ptrace.h"
+
 namespace pt {
+
+// the values a zero field of pt_denoise_params / pt_denoise_var_params stands for: the minima of the CPU studies
+// (profiles/denoise_cpu_study.json, profiles/denoise_var_cpu_study.json)
+constexpr pt_denoise_params kDenoiseDefaults = {5u, 2.0f, 0.0f, 0.03125f, 0u};
+constexpr pt_denoise_var_params kDenoiseVarDefaults = {5u, 1.0f, 0.125f, 0u};
+constexpr uint32_t kDenoiseMaxLevels = 8u;
 
 struct DenoiseFrame {
     uint32_t width, height;
@@ -27,5 +35,24 @@ void launch_dn_prepare(hipStream_t st, const DenoiseFrame &f);
 // With `error`, rc is kv = sigma_var^2 and each pixel scales its colour term by 1 / (kv * V(p) + 2^-20); V goes on to the
 // next plane as sum(V(q) w^2) / wsum^2.
 void launch_dn_level(hipStream_t st, const DenoiseFrame &f, uint32_t i, float rc, float sds, bool last, bool lds);
+
+// A checked call of either filter: the frame, and per level i < levels the rc and sds launch_dn_level receives - host binary32,
+// sc_i = sigma * 2^-i with 2^-i as the running product of 0.5f, rc = 1 / (sc_i * sc_i) or, with an error map, kv = sigma * sigma
+// at every level; sds = sigma_depth * (float)(1 << i).
+struct DenoiseCall {
+    DenoiseFrame f;
+    uint32_t levels;
+    float rc[kDenoiseMaxLevels], sds[kDenoiseMaxLevels];
+};
+
+namespace host {
+// pt_ctx_denoise's and pt_ctx_denoise_var's refusals in the header's order (PT_ERR_INVALID + message); PT_OK: `call` holds the
+// call with the defaults filled in, but for f.guide and f.u[], which the caller owns.  No device is touched.
+int check_denoise(const void *ctx, uint32_t width, uint32_t height, const pt_denoise_params *params, const float *d_color,
+                  const float *d_albedo, const float *d_normal, const float *d_depth, float *d_out, DenoiseCall &call);
+int check_denoise_var(const void *ctx, uint32_t width, uint32_t height, const pt_denoise_var_params *params, const float *d_color,
+                      const float *d_error, const float *d_albedo, const float *d_normal, const float *d_depth, float *d_out,
+                      DenoiseCall &call);
+}  // namespace host
 
 }  // namespace pt

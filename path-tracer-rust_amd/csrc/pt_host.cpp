@@ -2,6 +2,8 @@
 // values produced here must be the f32 values the reference computes (per frame for the camera, per ray
 // for the triangle edges — see pt_device.h).
 #include "pt_host.h"
+#include "pt_denoise.h"
+#include "pt_present.h"
 #include "pt_reproject.h"
 #include "pt_upsample.h"
 
@@ -1295,6 +1297,104 @@ int adckpt_decode(uint64_t file_size, const uint8_t *b, size_t n, AdaptiveCheckp
     return kCkptOk;
 }
 
+// ---- pt_ctx_denoise, pt_ctx_denoise_var (ptrace.h, pt_denoise.h)
+// What the two filters share once their parameters are read: the frame's size, the planes (`var`: pt_ctx_denoise_var's, with its
+// error map), the context, then the frame and the levels' schedule - sigma is sigma_color or sigma_var.
+static int denoise_tail(const void *ctx, uint32_t width, uint32_t height, uint32_t levels, float sigma, float sigma_depth,
+                        uint32_t flags, bool var, const float *d_color, const float *d_error, const float *d_albedo, const float *d_normal,
+                        const float *d_depth, float *d_out, DenoiseCall &call) {
+    if (!width || !height) return refuse("width and height must be positive");
+    if ((uint64_t)width * height > (1ull << 28)) return refuse("width*height exceeds 2^28");
+    if (!var && (!d_color || !d_out)) return refuse("d_color or d_out is NULL");
+    if (!d_color) return refuse("d_color is NULL");
+    if (var && !d_error) return refuse("d_error is NULL: pt_ctx_denoise is the filter without a noise estimate");
+    if (!d_out) return refuse("d_out is NULL");
+    if (!ctx) return refuse("ctx is NULL");
+    call = DenoiseCall{};
+    DenoiseFrame &f = call.f;
+    f.width = width;
+    f.height = height;
+    f.color = d_color;
+    f.albedo = (flags & PT_DENOISE_NO_DEMODULATE) ? nullptr : d_albedo;
+    f.normal = d_normal;
+    f.depth = d_depth;
+    f.error = d_error;
+    f.out = d_out;
+    call.levels = levels;
+    const float kv = sigma * sigma;
+    float scale = 1.0f;  // 2^-i
+    for (uint32_t i = 0; i < levels; ++i, scale *= 0.5f) {
+        const float sc = sigma * scale;
+        call.rc[i] = d_error ? kv : 1.0f / (sc * sc);  // with an error map the colour scale is per pixel, from kv
+        call.sds[i] = sigma_depth * (float)(1u << i);
+    }
+    return PT_OK;
+}
+
+int check_denoise(const void *ctx, uint32_t width, uint32_t height, const pt_denoise_params *params, const float *d_color,
+                  const float *d_albedo, const float *d_normal, const float *d_depth, float *d_out, DenoiseCall &call) {
+    pt_denoise_params P = kDenoiseDefaults;
+    if (params) {
+        if (params->levels > kDenoiseMaxLevels) return refuse("pt_denoise_params.levels exceeds 8");
+        if (!finite_nonneg(params->sigma_color) || !finite_nonneg(params->sigma_depth))
+            return refuse("pt_denoise_params: a sigma is negative or not finite");
+        if (!(params->sigma_normal_pow == 0.0f)) return refuse("pt_denoise_params.sigma_normal_pow is reserved and must be 0");
+        if (params->flags & ~PT_DENOISE_NO_DEMODULATE) return refuse("pt_denoise_params.flags: unknown bits");
+        if (params->levels) P.levels = params->levels;
+        if (params->sigma_color != 0.0f) P.sigma_color = params->sigma_color;
+        if (params->sigma_depth != 0.0f) P.sigma_depth = params->sigma_depth;
+        P.flags = params->flags;
+    }
+    return denoise_tail(ctx, width, height, P.levels, P.sigma_color, P.sigma_depth, P.flags, false, d_color, nullptr, d_albedo, d_normal,
+                        d_depth, d_out, call);
+}
+
+int check_denoise_var(const void *ctx, uint32_t width, uint32_t height, const pt_denoise_var_params *params, const float *d_color,
+                      const float *d_error, const float *d_albedo, const float *d_normal, const float *d_depth, float *d_out,
+                      DenoiseCall &call) {
+    pt_denoise_var_params P = kDenoiseVarDefaults;
+    if (params) {
+        if (params->levels > kDenoiseMaxLevels) return refuse("pt_denoise_var_params.levels exceeds 8");
+        if (!finite_nonneg(params->sigma_var) || !finite_nonneg(params->sigma_depth))
+            return refuse("pt_denoise_var_params: a sigma is negative or not finite");
+        if (params->flags & ~PT_DENOISE_NO_DEMODULATE) return refuse("pt_denoise_var_params.flags: unknown bits");
+        if (params->levels) P.levels = params->levels;
+        if (params->sigma_var != 0.0f) P.sigma_var = params->sigma_var;
+        if (params->sigma_depth != 0.0f) P.sigma_depth = params->sigma_depth;
+        P.flags = params->flags;
+    }
+    return denoise_tail(ctx, width, height, P.levels, P.sigma_var, P.sigma_depth, P.flags, true, d_color, d_error, d_albedo, d_normal,
+                        d_depth, d_out, call);
+}
+
+// ---- pt_ctx_present (ptrace.h, pt_present.h)
+int check_present(const void *ctx, uint32_t width, uint32_t height, const pt_present_params *params, const float *d_rgb, uint8_t *d_out,
+                  PresentFrame &f) {
+    pt_present_params P{};
+    if (params) P = *params;
+    if (!finite_nonneg(P.exposure)) return refuse("pt_present_params.exposure is negative or not finite");
+    if (P.format != PT_PRESENT_RGBA8 && P.format != PT_PRESENT_RGB8) return refuse("pt_present_params.format: unknown format");
+    if (P.flags & ~PT_PRESENT_FRAMEBUFFER_ORDER) return refuse("pt_present_params.flags: unknown bits");
+    if (!width || !height) return refuse("width and height must be positive");
+    if ((P.out_width == 0u) != (P.out_height == 0u)) return refuse("pt_present_params: one of out_width, out_height is 0 alone");
+    const uint32_t ow = P.out_width ? P.out_width : width, oh = P.out_height ? P.out_height : height;
+    if ((uint64_t)width * height > (1ull << 28) || (uint64_t)ow * oh > (1ull << 28))
+        return refuse("width*height or out_width*out_height exceeds 2^28");
+    if (!d_rgb) return refuse("d_rgb is NULL");
+    if (!d_out) return refuse("d_out is NULL");
+    if (!ctx) return refuse("ctx is NULL");
+    f = PresentFrame{};
+    f.rgb = d_rgb;
+    f.out = d_out;
+    f.width = width;
+    f.height = height;
+    f.out_width = ow;
+    f.out_height = oh;
+    f.bpp = P.format == PT_PRESENT_RGBA8 ? 4u : 3u;
+    f.flip = !(P.flags & PT_PRESENT_FRAMEBUFFER_ORDER);
+    f.exposure = P.exposure == 0.0f ? 1.0f : P.exposure;
+    return PT_OK;
+}
 
 // ---- pt_ctx_reproject (ptrace.h, pt_reproject.h)
 void reproject_view(const pt_camera &cam, const pt_camera *hist_cam, ReprojectView &out) {

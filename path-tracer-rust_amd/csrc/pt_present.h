@@ -5,6 +5,7 @@
 // of sincos_f32.  A translation unit of its own: pt_kernels.s, and so pt_kernel_isa_hash(), describes the pass kernels only.
 #pragma once
 
+#include "../../include/ptrace.h"
 #include "pt_math.h"
 
 namespace pt {
@@ -58,7 +59,6 @@ PT_HD float present_mean(uint64_t S, double divisor) { return (float)((double)S 
 // The table T[0..255] of step 5 (host/scene_io.cpp): built once per process with the host's powf, thread-safe.
 const uint32_t *present_table();
 
-#if defined(__HIPCC__)
 struct PresentFrame {
     const float *rgb;     // width * height * 3 floats, framebuffer order
     uint8_t *out;         // out_width * out_height * bpp bytes
@@ -68,7 +68,17 @@ struct PresentFrame {
     float exposure;
     const uint32_t *table;          // T on the device, 256 entries
     unsigned long long *mid;        // the resampling form's intermediate: [3] planes of width * out_height u64 (NULL: same size)
+    bool resamples() const { return out_width != width || out_height != height; }  // the call needs `mid`
 };
+
+namespace host {
+// pt_ctx_present's refusals in the header's order (PT_ERR_INVALID + message); PT_OK: `f` holds the call with the defaults filled
+// in, but for f.table and f.mid, which the caller owns.  No device is touched.
+int check_present(const void *ctx, uint32_t width, uint32_t height, const pt_present_params *params, const float *d_rgb, uint8_t *d_out,
+                  PresentFrame &f);
+}  // namespace host
+
+#if defined(__HIPCC__)
 // out_width == width and out_height == height: one streaming kernel.  Otherwise two passes, rows first.
 void launch_present(hipStream_t st, const PresentFrame &f);
 #endif

@@ -3,33 +3,12 @@
 // scenes, the growth rule over a scripted walk, and the same walk with the rebuilds it asks for on mesh.json with its mesh
 // replaced by a generated one of 20 000 triangles: a failed check or a sanitizer report ends it with a non-zero status.
 // argv[1]: the directory that holds meshes/ (the built-in "mesh" scene loads its OFF file from there).
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
-
-#include "../../include/ptrace.h"
+#include "check_common.h"
 #include "../csrc/pt_host.h"
-
-namespace pt {
-static std::string g_error;
-void set_error(const std::string &m) { g_error = m; }
-}  // namespace pt
-extern "C" const char *pt_last_error(void) { return pt::g_error.c_str(); }
 
 using namespace pt;
 using host::FlatScene;
 using host::Reach;
-
-#define CHECK(cond)                                                      \
-    do {                                                                 \
-        if (!(cond)) {                                                   \
-            fprintf(stderr, "%s:%d: %s failed\n", __FILE__, __LINE__, #cond); \
-            return 1;                                                    \
-        }                                                                \
-    } while (0)
 
 static bool same_bits(const float *a, const float *b, size_t n) { return memcmp(a, b, n * sizeof(float)) == 0; }
 

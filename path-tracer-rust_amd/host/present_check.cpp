@@ -1,30 +1,9 @@
 // present_check — pt_ctx_present's host side under a sanitizer, as a program of its own (make present-check builds it with
-// -fsanitize=address,undefined and runs it; no device, no Python).  It drives the table builder, pt_present_quantize_host,
+// -fsanitize=address,undefined and runs it; no device, no Python).  It drives the refusals, the table builder, pt_present_quantize_host,
 // pt_write_ppm8 and the footprint arithmetic the kernels share with the host (csrc/pt_present.h), and checks each against its
 // definition: a failed check or a sanitizer report ends it with a non-zero status.
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
-
-#include "../../include/ptrace.h"
+#include "check_common.h"
 #include "../csrc/pt_present.h"
-
-namespace pt {
-static std::string g_error;
-void set_error(const std::string &m) { g_error = m; }
-}  // namespace pt
-extern "C" const char *pt_last_error(void) { return pt::g_error.c_str(); }
-
-#define CHECK(cond)                                                      \
-    do {                                                                 \
-        if (!(cond)) {                                                   \
-            fprintf(stderr, "%s:%d: %s failed\n", __FILE__, __LINE__, #cond); \
-            return 1;                                                    \
-        }                                                                \
-    } while (0)
 
 static float from_bits(uint32_t u) {
     float f;
@@ -91,6 +70,40 @@ int main(int argc, char **argv) {
         const float m = pt::present_mean(fx * 35u, 35.0 * 4294967296.0);
         CHECK(m == (float)((double)fx / 4294967296.0));
         if (c >= 0x1p-8f) CHECK(m == c);
+    }
+    // the refusals, in the header's order: each call breaks one rule and every rule after it; then what an accepted call fills in
+    {
+        float rgb[1];
+        uint8_t out[1];
+        const uint32_t BIG = 1u << 15;  // BIG * BIG = 2^30 > 2^28
+        pt::PresentFrame f;
+        auto check = [&](uint32_t w, uint32_t h, const pt_present_params *p, const float *d_rgb, uint8_t *d_out, const void *cx = nullptr) {
+            return pt::host::check_present(cx, w, h, p, d_rgb, d_out, f);
+        };
+        using P = pt_present_params;
+        const P neg = {3, 0, -1.0f, 7, 6}, inf = {3, 0, INFINITY, 7, 6}, nan = {3, 0, NAN, 7, 6}, fmt = {3, 0, 1.0f, 2, 6},
+                flags = {3, 0, 1.0f, 1, 2}, w_alone = {3, 0, 1.0f, 1, 1}, w_alone0 = {3, 0, 0.0f, 0, 0}, w_only = {3, 0, 1.0f, 0, 0},
+                h_only = {0, 3, 1.0f, 0, 0}, small = {2, 2, 1.0f, 0, 0}, big_out = {BIG, BIG, 1.0f, 0, 0}, fine = {2, 2, 2.0f, 1, 1};
+        for (const P *p : {&neg, &inf, &nan}) CHECK(refused(check(0, 0, p, nullptr, nullptr), "exposure"));
+        CHECK(refused(check(0, 0, &fmt, nullptr, nullptr), "format"));
+        CHECK(refused(check(0, 0, &flags, nullptr, nullptr), "flags"));
+        CHECK(refused(check(0, 5, &w_alone, nullptr, nullptr), "width and height"));
+        CHECK(refused(check(5, 0, &w_alone0, nullptr, nullptr), "width and height"));
+        CHECK(refused(check(BIG, BIG, &w_only, nullptr, nullptr), "0 alone"));
+        CHECK(refused(check(BIG, BIG, &h_only, nullptr, nullptr), "0 alone"));
+        CHECK(refused(check(BIG, BIG, &small, nullptr, nullptr), "2^28"));
+        CHECK(refused(check(BIG, BIG, nullptr, nullptr, nullptr), "2^28"));
+        CHECK(refused(check(4, 4, &big_out, nullptr, nullptr), "2^28"));
+        CHECK(refused(check(4, 4, &small, nullptr, nullptr), "d_rgb"));
+        CHECK(refused(check(4, 4, nullptr, rgb, nullptr), "d_out"));
+        CHECK(refused(check(4, 4, &fine, rgb, out), "ctx"));
+        CHECK(refused(check(1u << 14, 1u << 14, nullptr, rgb, out), "ctx"));  // 2^28 pixels exactly are allowed
+        const void *ctx = rgb;  // never dereferenced
+        CHECK(check(1u << 14, 1u << 14, nullptr, rgb, out, ctx) == PT_OK);
+        CHECK(f.rgb == rgb && f.out == out && f.width == 1u << 14 && f.out_width == 1u << 14 && f.out_height == 1u << 14 && f.bpp == 4u &&
+              f.flip && f.exposure == 1.0f && !f.table && !f.mid && !f.resamples());
+        CHECK(check(4, 4, &fine, rgb, out, ctx) == PT_OK);
+        CHECK(f.out_width == 2u && f.out_height == 2u && f.bpp == 3u && !f.flip && f.exposure == 2.0f && f.resamples());
     }
     // the file
     const std::string path = std::string(argc > 1 ? argv[1] : "/tmp") + "/present_check.ppm";

@@ -3,76 +3,8 @@
 // edge inputs, and runs the pixel the kernel compiles (csrc/pt_reproject.h: reproject_pixel) over host frames allocated to their
 // exact size, so that the sanitizer bounds every tap of the gather: a failed check or a sanitizer report ends it with a non-zero
 // status.
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
-
-#include "../../include/ptrace.h"
+#include "check_common.h"
 #include "../csrc/pt_reproject.h"
-
-namespace pt {
-static std::string g_error;
-void set_error(const std::string &m) { g_error = m; }
-}  // namespace pt
-extern "C" const char *pt_last_error(void) { return pt::g_error.c_str(); }
-
-#define CHECK(cond)                                                      \
-    do {                                                                 \
-        if (!(cond)) {                                                   \
-            fprintf(stderr, "%s:%d: %s failed\n", __FILE__, __LINE__, #cond); \
-            return 1;                                                    \
-        }                                                                \
-    } while (0)
-
-static pt_camera camera(float px, float py, float pz, float dx, float dy, float dz) {
-    const float l = sqrtf(dx * dx + dy * dy + dz * dz);
-    pt_camera c = {{px, py, pz}, {dx, dy, dz}, 0.035f, 0.036f, 1.5f};
-    if (l > 0.0f)
-        for (float &v : c.direction) v /= l;
-    return c;
-}
-
-static uint32_t lcg(uint32_t &s) { return s = s * 1664525u + 1013904223u; }
-static float unit(uint32_t &s) { return (float)(lcg(s) >> 8) * (1.0f / 16777216.0f); }
-
-struct Frames {
-    std::vector<float> color, depth, normal, hcolor, hlen, hdepth, hnormal, out, len;
-    std::vector<int32_t> id, hid;
-};
-
-// random frames in the style of the GPU test: depths on a few planes and +inf, ids -1..2, normals with zero vectors, lengths
-// with zeros
-static Frames make_frames(uint32_t n, uint32_t seed) {
-    Frames f;
-    uint32_t s = seed;
-    const float planes[] = {2.0f, 6.0f, 6.25f, 9.0f, INFINITY};
-    auto fill = [&](std::vector<float> &v, size_t k) {
-        v.resize(k);
-        for (float &x : v) x = unit(s);
-    };
-    fill(f.color, 3 * (size_t)n);
-    fill(f.hcolor, 3 * (size_t)n);
-    fill(f.normal, 3 * (size_t)n);
-    fill(f.hnormal, 3 * (size_t)n);
-    for (size_t i = 0; i < 3 * (size_t)n; ++i) {
-        f.normal[i] -= 0.5f;
-        f.hnormal[i] = lcg(s) % 8u ? f.normal[i] : 0.0f;
-    }
-    f.depth.resize(n), f.hdepth.resize(n), f.hlen.resize(n), f.id.resize(n), f.hid.resize(n);
-    for (uint32_t i = 0; i < n; ++i) {
-        f.depth[i] = planes[lcg(s) % 5u];
-        f.hdepth[i] = lcg(s) % 4u ? f.depth[i] : planes[lcg(s) % 5u];
-        f.id[i] = (int32_t)(lcg(s) % 4u) - 1;
-        f.hid[i] = lcg(s) % 4u ? f.id[i] : (int32_t)(lcg(s) % 4u) - 1;
-        f.hlen[i] = (float)(lcg(s) % 5u) * 4.0f;
-    }
-    f.out.assign(3 * (size_t)n, -1.0f);
-    f.len.assign(n, -1.0f);
-    return f;
-}
 
 int main() {
     const pt_camera cam = camera(0.0f, -0.2f, 7.8f, 0.0f, -0.06f, -1.0f);
@@ -134,7 +66,6 @@ int main() {
             return pt::host::check_reproject(cx, w, h, p, c, col, col ? F : nullptr, col ? I : nullptr, nullptr, hcam, hc, hl, hc,
                                              hc ? I : nullptr, nullptr, out, out, f);
         };
-        auto refused = [&](int rc, const char *word) { return rc == PT_ERR_INVALID && pt::g_error.find(word) != std::string::npos; };
         const pt_reproject_params bad_mh = {0, -1.0f, NAN, 2.0f, 1}, bad_dt = {0, 1.0f, INFINITY, 2.0f, 1}, bad_nm = {0, 1.0f, 1.0f, NAN, 1},
                                   bad_nm2 = {0, 1.0f, 1.0f, -1.5f, 1}, bad_flags = {0, 1.0f, 1.0f, -1.0f, 1}, fine = {3, 8.0f, 0.1f, 1.0f, 0};
         CHECK(refused(check(&bad_mh, 0, 0, nullptr, nullptr, F, nullptr, nullptr, nullptr, nullptr), "max_history or depth_tol"));
@@ -153,14 +84,12 @@ int main() {
         CHECK(refused(check(nullptr, 2, 2, &cam, F, F, F, &cam, buf, nullptr), "ctx"));
         CHECK(refused(check(nullptr, 2, 2, &cam, F, nullptr, nullptr, nullptr, buf, nullptr), "ctx"));
         // accepted: the defaults are filled in, the first frame carries no history
-        pt_reproject_params d;
         CHECK(check(nullptr, 2, 2, &cam, F, F, F, &near_cam, buf, ctx) == PT_OK);
         CHECK(f.wt == 1.0f && f.max_history == pt::kReprojectMaxHistory && f.depth_tol == pt::kReprojectDepthTol &&
               f.normal_min == pt::kReprojectNormalMin && f.view.same == 0u && f.hist_color == F);
         CHECK(check(&fine, 2, 2, &cam, F, F, F, &cam, buf, ctx) == PT_OK);
         CHECK(f.wt == 3.0f && f.max_history == 8.0f && f.depth_tol == 0.1f && f.normal_min == 1.0f && f.view.same == 1u);
         CHECK(check(&fine, 2, 2, &cam, F, nullptr, nullptr, nullptr, buf, ctx) == PT_OK && f.hist_color == nullptr);
-        (void)d;
     }
 
     // ---- the pixel over host frames of exactly width * height: every tap inside them, or the sanitizer says so
@@ -170,7 +99,7 @@ int main() {
         const uint32_t w = s[0], h = s[1], n = w * h;
         for (const pt_camera *hc : {&cam, &near_cam, &aside, &back, &zero}) {
             for (int with_normals = 0; with_normals < 2; ++with_normals) {
-                Frames fr = make_frames(n, w * 131u + h);
+                Frames fr = make_frames(n, w * 131u + h, false);
                 const pt_reproject_params p = {4, 64.0f, 0.05f, 0.5f, 0};
                 pt::ReprojectFrame f;
                 CHECK(pt::host::check_reproject(&fr, w, h, &p, &cam, fr.color.data(), fr.depth.data(), fr.id.data(),
@@ -194,7 +123,7 @@ int main() {
             }
         }
         // the first frame, and in place
-        Frames fr = make_frames(n, 7u);
+        Frames fr = make_frames(n, 7u, false);
         pt::ReprojectFrame f;
         CHECK(pt::host::check_reproject(&fr, w, h, nullptr, &cam, fr.color.data(), fr.depth.data(), fr.id.data(), nullptr, nullptr, nullptr,
                                         nullptr, nullptr, nullptr, nullptr, fr.color.data(), fr.len.data(), f) == PT_OK);

@@ -3,82 +3,8 @@
 // and runs the whole pixel the kernels compile (csrc/pt_reproject.h: reproject_var_pixel - projection and gather with moments -
 // then reproject_var_short_pixel - the spatial window) over host frames allocated to their exact size, so that the sanitizer
 // bounds every tap and every window read: a failed check or a sanitizer report ends it with a non-zero status.
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
-
-#include "../../include/ptrace.h"
+#include "check_common.h"
 #include "../csrc/pt_reproject.h"
-
-namespace pt {
-static std::string g_error;
-void set_error(const std::string &m) { g_error = m; }
-}  // namespace pt
-extern "C" const char *pt_last_error(void) { return pt::g_error.c_str(); }
-
-#define CHECK(cond)                                                      \
-    do {                                                                 \
-        if (!(cond)) {                                                   \
-            fprintf(stderr, "%s:%d: %s failed\n", __FILE__, __LINE__, #cond); \
-            return 1;                                                    \
-        }                                                                \
-    } while (0)
-
-static pt_camera camera(float px, float py, float pz, float dx, float dy, float dz) {
-    const float l = sqrtf(dx * dx + dy * dy + dz * dz);
-    pt_camera c = {{px, py, pz}, {dx, dy, dz}, 0.035f, 0.036f, 1.5f};
-    if (l > 0.0f)
-        for (float &v : c.direction) v /= l;
-    return c;
-}
-
-static uint32_t lcg(uint32_t &s) { return s = s * 1664525u + 1013904223u; }
-static float unit(uint32_t &s) { return (float)(lcg(s) >> 8) * (1.0f / 16777216.0f); }
-
-struct Frames {
-    std::vector<float> color, depth, normal, hcolor, hlen, hmom, hdepth, hnormal, out, len, mom, err, splane;
-    std::vector<int32_t> id, hid;
-};
-
-// random frames in the style of the GPU test: depths on a few planes and +inf, ids -1..2, normals with zero vectors, lengths
-// with zeros and in blocks (so that some stretches are all long and some all short), moments of a colour sum in [0, 3]
-static Frames make_frames(uint32_t n, uint32_t seed) {
-    Frames f;
-    uint32_t s = seed;
-    const float planes[] = {2.0f, 6.0f, 6.25f, 9.0f, INFINITY};
-    auto fill = [&](std::vector<float> &v, size_t k) {
-        v.resize(k);
-        for (float &x : v) x = unit(s);
-    };
-    fill(f.color, 3 * (size_t)n);
-    fill(f.hcolor, 3 * (size_t)n);
-    fill(f.normal, 3 * (size_t)n);
-    fill(f.hnormal, 3 * (size_t)n);
-    for (size_t i = 0; i < 3 * (size_t)n; ++i) {
-        f.normal[i] -= 0.5f;
-        f.hnormal[i] = lcg(s) % 8u ? f.normal[i] : 0.0f;
-    }
-    f.depth.resize(n), f.hdepth.resize(n), f.hlen.resize(n), f.id.resize(n), f.hid.resize(n), f.hmom.resize(2 * (size_t)n);
-    for (uint32_t i = 0; i < n; ++i) {
-        f.depth[i] = planes[(i / 5u) % 4u == 3u ? lcg(s) % 5u : (i / 5u) % 4u];
-        f.hdepth[i] = lcg(s) % 4u ? f.depth[i] : planes[lcg(s) % 5u];
-        f.id[i] = lcg(s) % 6u ? (int32_t)((i / 7u) % 3u) : (int32_t)(lcg(s) % 4u) - 1;
-        f.hid[i] = lcg(s) % 4u ? f.id[i] : (int32_t)(lcg(s) % 4u) - 1;
-        f.hlen[i] = (i / 40u) % 3u == 0u ? 32.0f : (float)(lcg(s) % 5u) * 4.0f;
-        const float m1 = 3.0f * unit(s);
-        f.hmom[2 * (size_t)i] = m1;
-        f.hmom[2 * (size_t)i + 1] = m1 * m1 + unit(s);
-    }
-    f.out.assign(3 * (size_t)n, -1.0f);
-    f.len.assign(n, -1.0f);
-    f.mom.assign(2 * (size_t)n, -1.0f);
-    f.err.assign(n, -2.0f);
-    f.splane.assign(n, -1.0f);
-    return f;
-}
 
 // the frame as kernel B's window sees it: global planes, every read inside them or the sanitizer says so
 struct HostSrc {
@@ -129,7 +55,6 @@ int main() {
             return pt::host::check_reproject_var(cx, w, h, p, c, col, col ? F : nullptr, col ? I : nullptr, nullptr, hcam, hc, hl, hm,
                                                  hc, hc ? I : nullptr, nullptr, out, out, om, er, v);
         };
-        auto refused = [&](int rc, const char *word) { return rc == PT_ERR_INVALID && pt::g_error.find(word) != std::string::npos; };
         const pt_reproject_var_params bad_mh = {0, -1.0f, NAN, 2.0f, 0, 4, 1}, bad_dt = {0, 1.0f, INFINITY, 2.0f, 0, 4, 1},
                                       bad_nm = {0, 1.0f, 1.0f, NAN, 0, 4, 1}, bad_nm2 = {0, 1.0f, 1.0f, -1.5f, 0, 4, 1},
                                       bad_r = {0, 1.0f, 1.0f, -1.0f, 0, 4, 1}, bad_flags = {0, 1.0f, 1.0f, -1.0f, 9, 3, 1},
@@ -176,7 +101,7 @@ int main() {
         for (const pt_camera *hc : {&cam, &near_cam, &aside, &back, &zero}) {
             for (uint32_t radius = 1; radius <= 3; ++radius) {
                 for (int with_normals = 0; with_normals < 2; ++with_normals) {
-                    Frames fr = make_frames(n, w * 131u + h);
+                    Frames fr = make_frames(n, w * 131u + h, true);
                     const pt_reproject_var_params p = {4, 64.0f, 0.05f, 0.5f, with_normals ? 4u : 1u, radius, 0};
                     pt::ReprojectVarFrame v;
                     CHECK(pt::host::check_reproject_var(&fr, w, h, &p, &cam, fr.color.data(), fr.depth.data(), fr.id.data(),
@@ -208,7 +133,7 @@ int main() {
             }
         }
         // the first frame, in place: every pixel short, the colour unchanged, the moments (s, s*s)
-        Frames fr = make_frames(n, 7u);
+        Frames fr = make_frames(n, 7u, true);
         pt::ReprojectVarFrame v;
         CHECK(pt::host::check_reproject_var(&fr, w, h, nullptr, &cam, fr.color.data(), fr.depth.data(), fr.id.data(), nullptr, nullptr,
                                             nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, fr.color.data(), fr.len.data(),

@@ -3,32 +3,8 @@
 // against / and %, the multiply-and-shift divisions of csrc/pt_upsample.h against /, and runs the pixel the kernel compiles
 // (upsample_pixel) over host frames allocated to their exact size - the sizes of tests/test_gpu_upsample.py - so that the
 // sanitizer bounds every tap: a failed check or a sanitizer report ends it with a non-zero status.
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
-
-#include "../../include/ptrace.h"
+#include "check_common.h"
 #include "../csrc/pt_upsample.h"
-
-namespace pt {
-static std::string g_error;
-void set_error(const std::string &m) { g_error = m; }
-}  // namespace pt
-extern "C" const char *pt_last_error(void) { return pt::g_error.c_str(); }
-
-#define CHECK(cond)                                                      \
-    do {                                                                 \
-        if (!(cond)) {                                                   \
-            fprintf(stderr, "%s:%d: %s failed\n", __FILE__, __LINE__, #cond); \
-            return 1;                                                    \
-        }                                                                \
-    } while (0)
-
-static uint32_t lcg(uint32_t &s) { return s = s * 1664525u + 1013904223u; }
-static float unit(uint32_t &s) { return (float)(lcg(s) >> 8) * (1.0f / 16777216.0f); }
 
 struct Guides {
     std::vector<float> color, depth, normal, albedo;
@@ -131,7 +107,6 @@ int main() {
                          const float *own, const int32_t *id, float *out, const void *cx) {
             return pt::host::check_upsample(cx, W, H, w, h, p, lo, lo, loid, nullptr, nullptr, own, id, nullptr, nullptr, out, nullptr, f);
         };
-        auto refused = [&](int rc, const char *word) { return rc == PT_ERR_INVALID && pt::g_error.find(word) != std::string::npos; };
         const pt_upsample_params bad_dt = {-1.0f, 2.0f, 1}, bad_dt2 = {NAN, 2.0f, 1}, bad_dt3 = {INFINITY, 2.0f, 1}, bad_nm = {0.5f, NAN, 1},
                                  bad_nm2 = {0.5f, -1.5f, 1}, bad_flags = {0.5f, -1.0f, 1}, fine = {0.25f, 1.0f, 0};
         CHECK(refused(check(&bad_dt, 0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr), "depth_tol"));

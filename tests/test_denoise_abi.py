@@ -9,6 +9,8 @@
   than R times the noisy frame's distance.  R = 1.15 x the ratio tools/denoise_cpu_study.py measured at the chosen defaults
   (profiles/denoise_cpu_study.json: cornell 0.381820, mesh 0.316506); the frames are deterministic, the 15 % is room for a later
   deliberate change of a constant.
+- `make denoise-check` - both filters' refusals, the limits they accept and the levels' schedule against this restatement's
+  formula bit for bit, host only under AddressSanitizer and UBSan - builds and passes.
 The GPU side is tests/test_gpu_denoise.py."""
 import ctypes as C
 import importlib
@@ -138,6 +140,14 @@ def test_invalid_arguments_are_refused_without_a_device():
         rc, msg = call(**kw)
         assert rc == PT_ERR_INVALID, (kw, rc)
         assert word in msg, (kw, msg)
+
+
+# ---------------------------------------------------------------------------------------------------------- make denoise-check
+def test_denoise_check_builds_and_passes(tmp_path):
+    r = subprocess.run(["make", "-C", ptlib.PKG, "denoise-check", "B=" + str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    assert "denoise_check: ok" in r.stdout
+    assert "-fsanitize=address,undefined" in r.stdout and "--cuda-host-only" in r.stdout
 
 
 # ------------------------------------------------------------------------------------------- known answers on the rebuild
