@@ -131,6 +131,15 @@ pub struct PtUpsampleParams {
     pub flags: u32,
 }
 
+// pt_ctx_select_pixels' thresholds: taken literally, no defaults
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct PtSelectParams {
+    pub weight_max: f32,
+    pub len_max: f32,
+    pub flags: u32,
+}
+
 // pt_ctx_denoise's parameters; a zero field = the library's default (pt_denoise_defaults)
 #[repr(C)]
 #[derive(Clone, Copy, Default, Debug)]
@@ -492,6 +501,29 @@ extern "C" {
         hip_stream: *mut c_void,
     ) -> i32;
     pub fn pt_upsample_tap_host(size: u32, lo_size: u32, coord: u32, first: *mut i32, frac: *mut f32) -> i32;
+    // the pixels a pass could not serve (upsample weight 0, no history) as a byte mask, and those pixels of a frame traced again
+    // and written into it: each one pt_ctx_render's pixel, bit for bit
+    pub fn pt_ctx_select_pixels(
+        ctx: *mut PtCtx,
+        width: u32,
+        height: u32,
+        params: *const PtSelectParams,
+        d_weight: *const f32,
+        d_len: *const f32,
+        d_mask: *mut u8,
+        n_selected: *mut u32,
+        hip_stream: *mut c_void,
+    ) -> i32;
+    pub fn pt_ctx_render_masked(
+        ctx: *mut PtCtx,
+        cfg: *const PtConfig,
+        d_mask: *const u8,
+        d_rgb: *mut c_void,
+        hip_stream: *mut c_void,
+        cancel: *const u8,
+        stats: *mut PtStats,
+        n_pixels: *mut u32,
+    ) -> i32;
     pub fn pt_write_pfm(path: *const c_char, data: *const f32, width: u32, height: u32, channels: u32) -> i32;
     pub fn pt_device_malloc(device: i32, bytes: usize, out: *mut *mut c_void) -> i32;
     pub fn pt_device_free(device: i32, p: *mut c_void) -> i32;
@@ -676,6 +708,25 @@ pub fn upsample_into(ctx: *mut PtCtx, lo: &UpsampleGuides, full: &UpsampleGuides
             ctx, full.width, full.height, lo.width, lo.height, std::ptr::null(), lo.d_color, lo.d_depth, lo.d_object_id,
             lo.d_normal, lo.d_albedo, full.d_depth, full.d_object_id, full.d_normal, full.d_albedo, d_out_color,
             std::ptr::null_mut(), std::ptr::null_mut(),
+        )
+    }
+}
+
+/// The fallback pixels of an upsampled frame traced again at full size: `d_weight` is the plane pt_ctx_upsample wrote beside
+/// `d_color` (upsample_into passes none: a host that retraces calls pt_ctx_upsample with one), `d_mask` full-size scratch of one
+/// byte per pixel, `cfg` the full-size frame at the LOW-RESOLUTION samples per pixel, so that reproject_var_and_swap's uniform
+/// `weight` stays true for every pixel.  Returns the library's code; `retraced` is the number of pixels replaced.
+pub fn retrace_fallback(ctx: *mut PtCtx, cfg: &PtConfig, d_weight: *const f32, d_mask: *mut u8, d_color: *mut f32, retraced: &mut u32) -> i32 {
+    let sel = PtSelectParams { weight_max: 0.0, len_max: 0.0, flags: 0 };
+    unsafe {
+        let rc = pt_ctx_select_pixels(
+            ctx, cfg.width, cfg.height, &sel, d_weight, std::ptr::null(), d_mask, std::ptr::null_mut(), std::ptr::null_mut(),
+        );
+        if rc != PT_OK {
+            return rc;
+        }
+        pt_ctx_render_masked(
+            ctx, cfg, d_mask, d_color as *mut c_void, std::ptr::null_mut(), std::ptr::null(), std::ptr::null_mut(), retraced,
         )
     }
 }

@@ -1021,6 +1021,60 @@ int pt_ctx_upsample(pt_ctx *ctx, uint32_t width, uint32_t height, uint32_t lo_wi
 /* host only, no device: the host instantiation of the tap position the kernel compiles */
 int pt_upsample_tap_host(uint32_t size, uint32_t lo_size, uint32_t coord, int32_t *first, float *frac);
 
+/* ---- retracing chosen pixels of a frame ---------------------------------------------------------------------------------
+ * Two passes of the viewport loop say which pixels they could not serve: pt_ctx_upsample writes d_out_weight = 0 where no tap
+ * passed and the pixel took the bilinear fallback, pt_ctx_reproject* write d_out_len = weight where a pixel found no history.
+ * pt_ctx_select_pixels turns such planes into a byte mask and counts it; pt_ctx_render_masked traces the masked pixels of a
+ * frame and writes them into it, each one pt_ctx_render's pixel bit for bit.  The loop with both:
+ *   pt_ctx_upsample(..., d_up, d_weight) -> pt_ctx_select_pixels(weight_max = 0, d_weight) -> pt_ctx_render_masked(cfg at the
+ *   LOW-RESOLUTION spp, d_mask, d_up) -> pt_ctx_reproject_var -> ...
+ *
+ * pt_ctx_select_pixels: an image pass on device buffers.
+ * - The planes are whole frames of width * height floats in framebuffer order; either may be NULL, not both.  d_mask receives
+ *   width * height bytes.  No output may alias an input.
+ * - THE PREDICATE, in IEEE binary32 comparisons:
+ *     mask[p] = ((d_weight && !(weight[p] > weight_max)) || (d_len && !(len[p] > len_max))) ? 1 : 0.
+ *   A NaN in a plane selects the pixel (no comparison with a NaN holds).  The thresholds are taken literally: there are no
+ *   defaults; a threshold of +inf selects every pixel, one of -inf only the pixels that hold -inf or a NaN.
+ * - *n_selected (host memory, may be NULL) is the number of ones, counted with integer atomics in the same launch: exact,
+ *   whatever the order.
+ * - `hip_stream` as for pt_ctx_render (NULL = the context's own stream); blocking.  No scene is needed.  The call changes no
+ *   state of the context beyond a scratch word for the count.
+ * - PT_ERR_INVALID, all refused before any device is touched, checked in this order: a NaN threshold; flags != 0; width or
+ *   height 0; width * height > 2^28; both planes NULL; NULL d_mask; NULL params; NULL ctx.  PT_ERR_HIP: a HIP call failed.
+ *
+ * pt_ctx_render_masked: a frame call.
+ * - d_mask: pt_config_pixels(cfg) bytes in the call's pixel order (byte k is pixel idx_begin + k of the frame); nonzero means
+ *   selected, whatever the value.  d_rgb: the call's frame, pt_config_pixels(cfg) * 3 floats in pt_ctx_render's layout, input
+ *   and output.
+ * - Every selected pixel k gets d_rgb[3k + c] = what pt_ctx_render with the same cfg writes there: samples [0, cfg->spp), the
+ *   same fixed-point sums, the same mean and clamp, bit for bit.  No other float of d_rgb is written.  *n_pixels (host memory,
+ *   may be NULL) is the number of selected pixels.
+ * - The band and the flags follow pt_ctx_render_adaptive: the band is whole image rows, chunk_step <= 1, `backend` is ignored
+ *   (but must be a valid one), PT_FLAG_NO_BVH selects the linear scan (same bytes), PT_FLAG_PIPELINES is refused; cfg->spp as
+ *   pt_ctx_render bounds it.
+ * - An empty mask: PT_OK, *n_pixels = 0, zero stats; nothing is traced or written.
+ * - `cancel` is read before the trace and between its rounds (sized as the megakernel's: about a tenth of a second).  On
+ *   PT_CANCELLED d_rgb is untouched: the call is kept whole or not at all.  There is no progress callback.
+ * - stats (may be NULL): samples = *n_pixels * spp, ray_bounces exact, passes = the trace's launches.
+ * - State: the list of selected pixels (4 B each) and the compact accumulator (24 B each) are scratch of the context, grown on
+ *   demand and freed by pt_ctx_destroy; the rounds keep a measured rate of their own, which pt_ctx_set_scene forgets.  Nothing
+ *   else changes: not the frame pt_ctx_accumulate holds, not the adaptive frame, not the other calls' rates.
+ * - PT_ERR_INVALID, all refused before any device is touched, checked in this order: NULL cfg, d_mask or d_rgb; NULL ctx; no
+ *   scene; a band that is not whole rows; chunk_step > 1 or PT_FLAG_PIPELINES; whatever pt_ctx_render refuses of a cfg.
+ *   PT_ERR_HIP: a HIP call failed.  PT_ERR_OVERFLOW as for the megakernel. */
+typedef struct pt_select_params {
+    float weight_max;   /* taken literally, no default; not NaN */
+    float len_max;      /* taken literally, no default; not NaN */
+    uint32_t flags;     /* none defined: must be 0 */
+} pt_select_params;
+int pt_ctx_select_pixels(pt_ctx *ctx, uint32_t width, uint32_t height, const pt_select_params *params,
+                         const float *d_weight /* may be NULL */, const float *d_len /* may be NULL */,
+                         uint8_t *d_mask, uint32_t *n_selected /* host, may be NULL */, void *hip_stream);
+int pt_ctx_render_masked(pt_ctx *ctx, const pt_config *cfg, const uint8_t *d_mask, void *d_rgb,
+                         void *hip_stream, const volatile uint8_t *cancel, pt_stats *stats,
+                         uint32_t *n_pixels /* host, may be NULL */);
+
 /* ---- the one collective of the path: the framebuffer gather over RCCL (xGMI) ---------------------------------
  * One process (or thread) per GPU renders its rows with pt_ctx_render (chunk_first = rank, chunk_step = n_ranks) into
  * device memory; pt_comm_gather_frame then gives EVERY rank the whole frame in device memory: one in-place

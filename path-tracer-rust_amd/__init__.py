@@ -76,6 +76,10 @@ class pt_upsample_params(C.Structure):
     _fields_ = [("depth_tol", C.c_float), ("normal_min", C.c_float), ("flags", C.c_uint32)]
 
 
+class pt_select_params(C.Structure):
+    _fields_ = [("weight_max", C.c_float), ("len_max", C.c_float), ("flags", C.c_uint32)]
+
+
 class pt_noise_stats(C.Structure):
     _fields_ = [("spp_min", C.c_uint32), ("spp_max", C.c_uint32), ("spp_a_min", C.c_uint32), ("spp_b_min", C.c_uint32),
                 ("pixels", C.c_uint64), ("mean_error", C.c_double), ("histogram", C.c_uint32 * 64)]
@@ -179,6 +183,10 @@ def lib():
     L.pt_upsample_defaults.argtypes = [C.POINTER(pt_upsample_params)]
     L.pt_ctx_upsample.argtypes = [C.c_void_p] + [C.c_uint32] * 4 + [C.POINTER(pt_upsample_params)] + [C.c_void_p] * 12
     L.pt_upsample_tap_host.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_float)]
+    L.pt_ctx_select_pixels.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(pt_select_params), C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p]
+    L.pt_ctx_render_masked.argtypes = [C.c_void_p, C.POINTER(pt_config), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.POINTER(pt_stats), C.POINTER(C.c_uint32)]
     L.pt_write_pfm.argtypes = [C.c_char_p, C.POINTER(C.c_float), C.c_uint32, C.c_uint32, C.c_uint32]
     L.pt_ctx_set_profiling.argtypes = [C.c_void_p, C.c_int]
     L.pt_ctx_pass_kernel.argtypes = [C.c_void_p, C.c_uint32]
@@ -412,6 +420,31 @@ class Context:
         _check(lib().pt_ctx_upsample(self._h, width, height, lo_width, lo_height, C.byref(p), ptr(lo["color"]), ptr(lo["depth"]),
                                      ptr(lo["object_id"]), ptr(lo.get("normal")), ptr(lo.get("albedo")), ptr(depth), ptr(object_id),
                                      ptr(normal), ptr(albedo), ptr(out_color), ptr(out_weight), C.c_void_p(stream or 0)))
+
+    def select_pixels(self, width, height, mask, weight=None, len=None, weight_max=0.0, len_max=0.0, stream=None):
+        """Turn the loop's planes into a byte mask (pt_ctx_select_pixels): mask[p] = 1 where weight[p] <= weight_max or
+        len[p] <= len_max or either holds a NaN, else 0.  Device pointers to whole frames: `weight` is upsample()'s out_weight,
+        `len` is reproject()'s out_len (pixels float32 each, at least one given); `mask` pixels bytes.  The thresholds are taken
+        literally.  Returns the number of selected pixels."""
+        p = pt_select_params(weight_max, len_max, 0)
+        ptr = lambda q: C.c_void_p(q) if q else None  # noqa: E731
+        n = C.c_uint32(0)
+        _check(lib().pt_ctx_select_pixels(self._h, width, height, C.byref(p), ptr(weight), ptr(len), ptr(mask), C.byref(n),
+                                          C.c_void_p(stream or 0)))
+        return n.value
+
+    def render_masked(self, mask, rgb, width, height, spp, seed=1, band=None, no_bvh=False, rays_per_pass=0, stream=None):
+        """Trace the pixels of the frame whose mask byte is not zero and write them into `rgb` (pt_ctx_render_masked): each gets
+        what render() with the same arguments writes there, bit for bit; no other float of `rgb` is written.  `mask`: the
+        band's pixels bytes, `rgb`: the band's pixels * 3 float32, device pointers; the band is whole rows.  Returns
+        (pt_stats, the number of pixels traced)."""
+        cfg = self._config(width, height, spp, seed, "megakernel", band, rays_per_pass)
+        if no_bvh:
+            cfg.flags |= PT_FLAG_NO_BVH
+        st, n = pt_stats(), C.c_uint32(0)
+        _check(lib().pt_ctx_render_masked(self._h, C.byref(cfg), C.c_void_p(mask), C.c_void_p(rgb), C.c_void_p(stream or 0), None,
+                                          C.byref(st), C.byref(n)))
+        return st, n.value
 
     def accum_track_noise(self, on=True):
         """Keep half of every pixel's samples in a second accumulator for the frames started from now on

@@ -16,6 +16,7 @@
 #include "pt_denoise.h"
 #include "pt_host.h"
 #include "pt_kernels.h"
+#include "pt_masked.h"
 #include "pt_noise.h"
 #include "pt_present.h"
 #include "pt_reproject.h"
@@ -355,6 +356,13 @@ struct pt_ctx {
     DevBuf<uint32_t> ad_open;
     DevBuf<char> ad_stack;
     double ad_rate = 0.0;
+    // pt_ctx_select_pixels and pt_ctx_render_masked.  Their own: two counter words ([0]: the select pass's count, [1]: the list's
+    // length), the list of a call's selected pixels (4 B each, grown on demand: NOT ad_open, whose slots must name tiles of the
+    // held adaptive frame whatever a launch reads of them) and the rate the call's rounds measured (pt_ctx_set_scene forgets
+    // it).  The compact accumulator, the ray counters and the split stacks are the adaptive calls' per-step scratch - ad_acc,
+    // ad_rays, ad_stack - which hold nothing between calls.
+    DevBuf<uint32_t> mk_cnt, mk_list;
+    double mk_rate = 0.0;
 };
 
 namespace {
@@ -1630,7 +1638,7 @@ int pt_ctx_set_scene(pt_ctx *c, const pt_camera *cam, const pt_object *objs, uin
             host::mesh_bounding_box(tris + objs[i].tri_offset, objs[i].tri_count, &c->h_boxes[(size_t)12 * i]);
     c->boxes_dirty = true;
     c->has_scene = true;
-    c->pass_rate = c->round_rate = c->ad_rate = 0.0;  // (another scene: the passes' length is measured again)
+    c->pass_rate = c->round_rate = c->ad_rate = c->mk_rate = 0.0;  // (another scene: the passes' length is measured again)
     c->pass_rate_kernel = nullptr;
     c->scene_fp = scene_fingerprint(cam, objs, n_objs, tris, n_tris);
     return PT_OK;
@@ -2824,6 +2832,119 @@ int pt_ctx_upsample(pt_ctx *c, uint32_t width, uint32_t height, uint32_t lo_widt
         launch_upsample(st, f);
         return PT_OK;
     });
+}
+
+int pt_ctx_select_pixels(pt_ctx *c, uint32_t width, uint32_t height, const pt_select_params *params, const float *d_weight,
+                         const float *d_len, uint8_t *d_mask, uint32_t *n_selected, void *hip_stream) {
+    SelectFrame f;
+    int rc = host::check_select_pixels(c, width, height, params, d_weight, d_len, d_mask, f);
+    if (rc) return rc;
+    uint32_t ones = 0u;
+    rc = run_image_pass(c, hip_stream, [&](hipStream_t st) {
+        const int r2 = c->mk_cnt.ensure(2);
+        if (r2) return r2;
+        f.count = c->mk_cnt.p;
+        HIP_TRY(hipMemsetAsync(f.count, 0, sizeof(uint32_t), st));
+        launch_select(st, f);
+        if (n_selected) HIP_TRY(hipMemcpyAsync(&ones, f.count, sizeof ones, hipMemcpyDeviceToHost, st));
+        return PT_OK;
+    });
+    if (rc == PT_OK && n_selected) *n_selected = ones;
+    return rc;
+}
+
+// The mask of a checked call compacted into c->mk_list on `st`; *n: the selected pixels.  The list's length is known only after
+// the pass, so a list that turns out too short (the kernel counts every selected pixel and writes the slots it has) is grown to
+// the length and the pass runs again: one synchronisation per call once the list has its size.
+static int masked_list(pt_ctx *c, const uint8_t *d_mask, uint32_t npix, hipStream_t st, uint32_t *n) {
+    int rc;
+    if ((rc = c->mk_cnt.ensure(2))) return rc;
+    if (!c->mk_list.p && (rc = c->mk_list.ensure(std::min<uint32_t>(npix, 1024u)))) return rc;
+    for (;;) {
+        uint32_t *const len = c->mk_cnt.p + 1;
+        const uint32_t cap = (uint32_t)std::min<size_t>(c->mk_list.n, 0xffffffffu);
+        HIP_TRY(hipMemsetAsync(len, 0, sizeof(uint32_t), st));
+        launch_masked_compact(st, d_mask, npix, c->mk_list.p, cap, len);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(n, len, sizeof *n, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (*n <= cap) return PT_OK;
+        if ((rc = c->mk_list.ensure(std::min<uint64_t>(npix, (uint64_t)*n + *n / 4u)))) return rc;
+    }
+}
+
+int pt_ctx_render_masked(pt_ctx *c, const pt_config *cfg, const uint8_t *d_mask, void *d_rgb, void *hip_stream,
+                         const volatile uint8_t *cancel, pt_stats *stats, uint32_t *n_pixels) {
+    if (!cfg || !d_mask || !d_rgb) return refuse("NULL argument");
+    if (!c) return refuse("ctx is NULL");
+    if (!c->has_scene) return refuse("no scene set");
+    uint32_t ib = 0, ie = 0;
+    int rc;
+    if ((rc = host::check_masked_cfg(*cfg)) || (rc = check_cfg(cfg, &ib, &ie))) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    const double t0 = now_ms();
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (n_pixels) *n_pixels = 0u;
+    uint32_t n = 0u;
+    if ((rc = masked_list(c, d_mask, ie - ib, st, &n))) return rc;
+    if (n_pixels) *n_pixels = n;
+    if (n == 0u) {  // (nothing to trace, and a grid of zero is an error)
+        if (stats) stats->ms_total = now_ms() - t0;
+        return PT_OK;
+    }
+    if (cancel && *cancel) {  // (before anything is traced; between the rounds their pacer reads it)
+        if (stats) stats->ms_total = now_ms() - t0;
+        set_error("cancelled");
+        return PT_CANCELLED;
+    }
+    // the trace: the tile pass over a grid of 1 x 1 tiles, entry k of the compact accumulator being pixel ib + list[k]
+    const FrameForm form = form_for(c, cfg->flags);
+    const DevScene &S = form.scene;
+    const LdsLayout lay = lds_layout(S, 1u, c->tune.lds_pad);
+    TileParams F{};
+    static_cast<FrameParams &>(F) = make_frame(c, cfg, ib, ie);
+    F.chunk_step = 0u;
+    F.npix = n;
+    F.open = c->mk_list.p;
+    F.tile_shift = 0u;
+    F.tiles_x = cfg->width;
+    F.rows = (ie - ib) / cfg->width;
+    if ((rc = c->ad_acc.ensure(3 * (size_t)n)) || (rc = c->ad_rays.ensure(16))) return rc;
+    HIP_TRY(hipMemsetAsync(c->ad_acc.p, 0, 3 * (size_t)n * sizeof(unsigned long long), st));
+    HIP_TRY(hipMemsetAsync(c->ad_rays.p, 0, 16 * sizeof(unsigned long long), st));
+    LiveScope live(c);  // (the rounds' pacer notes its samples in the live frame)
+    Rounds r;
+    rc = run_rounds(
+        c, cfg, st, cancel, nullptr, nullptr, n, 0u, lay.mega_cand, lay.mega_cand ? 8u : 4u, c->ad_rays.p, c->ad_stack, c->mk_rate,
+        [&](uint32_t grid, uint32_t s0, uint32_t s1, uint32_t lane_spp, uint32_t split) {
+            launch_tile_pass(st, grid, S, lay, F, c->ad_acc.p, s0, s1, lane_spp, split, c->ad_rays.p, c->ad_stack.p);
+        },
+        r);
+    if (rc) return rc;
+    // (the rounds have ended: run_rounds waits for the stream)
+    unsigned long long rays[16] = {0};
+    HIP_TRY(hipMemcpy(rays, c->ad_rays.p, sizeof rays, hipMemcpyDeviceToHost));
+    if (rays[1]) {
+        set_error("masked trace: a lane's split stack overflowed");
+        return PT_ERR_OVERFLOW;
+    }
+    if (stats) {
+        stats->ray_bounces = rays[0];
+        stats->samples = (uint64_t)n * r.s_issued;
+        stats->passes = r.launches;
+        stats->ms_device = r.ms_device;
+    }
+    if (r.cancelled) {  // the frame is kept whole: nothing was written
+        if (stats) stats->ms_total = now_ms() - t0;
+        set_error("cancelled");
+        return PT_CANCELLED;
+    }
+    launch_masked_scatter(st, c->mk_list.p, n, c->ad_acc.p, cfg->spp, (float *)d_rgb);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    if (stats) stats->ms_total = now_ms() - t0;
+    return PT_OK;
 }
 
 // one band on one device into the host framebuffer

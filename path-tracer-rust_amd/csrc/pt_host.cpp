@@ -3,6 +3,7 @@
 // for the triangle edges — see pt_device.h).
 #include "pt_host.h"
 #include "pt_denoise.h"
+#include "pt_masked.h"
 #include "pt_present.h"
 #include "pt_reproject.h"
 #include "pt_upsample.h"
@@ -1531,6 +1532,37 @@ int check_upsample(const void *ctx, uint32_t width, uint32_t height, uint32_t lo
     f.div_w = upsample_div_make(width);
     f.div_2w = upsample_div_make(2u * width);
     f.div_2h = upsample_div_make(2u * height);
+    return PT_OK;
+}
+
+// ---- pt_ctx_select_pixels, pt_ctx_render_masked (ptrace.h, pt_masked.h)
+int check_select_pixels(const void *ctx, uint32_t width, uint32_t height, const pt_select_params *params, const float *d_weight,
+                        const float *d_len, uint8_t *d_mask, SelectFrame &f) {
+    pt_select_params P{};
+    if (params) P = *params;
+    if (P.weight_max != P.weight_max || P.len_max != P.len_max) return refuse("pt_select_params: weight_max or len_max is NaN");
+    if (P.flags) return refuse("pt_select_params.flags: none is defined");
+    if (!width || !height) return refuse("width and height must be positive");
+    if ((uint64_t)width * height > (1ull << 28)) return refuse("width*height exceeds 2^28");
+    if (!d_weight && !d_len) return refuse("d_weight and d_len are both NULL");
+    if (!d_mask) return refuse("d_mask is NULL");
+    if (!params) return refuse("params is NULL");
+    if (!ctx) return refuse("ctx is NULL");
+    f = SelectFrame{};
+    f.npix = width * height;
+    f.weight = d_weight;
+    f.len = d_len;
+    f.mask = d_mask;
+    f.weight_max = P.weight_max;
+    f.len_max = P.len_max;
+    return PT_OK;
+}
+
+int check_masked_cfg(const pt_config &cfg) {
+    if (cfg.width != 0u && (cfg.idx_begin % cfg.width != 0u || cfg.idx_end % cfg.width != 0u))
+        return refuse("masked: the band must consist of whole image rows");
+    if (cfg.chunk_step > 1u || ((cfg.flags >> 8) & 15u) != 0u)
+        return refuse("masked: chunk_step > 1 and PT_FLAG_PIPELINES are not supported");
     return PT_OK;
 }
 

@@ -25,7 +25,8 @@ static void usage() {
             "              [--seed S] [--gpus N] [--root DIR] [--out DIR] [--no-ppm] [--checkpoint FILE] [--aov N]\n"
             "              [--denoise [N]] [--noise-target X [--noise-map FILE.pfm]]\n"
             "              [--adaptive X [--tile N] [--spp-map FILE.pfm] [--error-map FILE.pfm] [--adaptive-checkpoint FILE]]\n"
-            "              [--denoise-var [N]] [--preview FILE.ppm [--preview-size WxH] [--exposure E]] [--trace-scale K]\n"
+            "              [--denoise-var [N]] [--preview FILE.ppm [--preview-size WxH] [--exposure E]]\n"
+            "              [--trace-scale K [--retrace]]\n"
             "              [--orbit N [--orbit-step DEG]]\n"
             "  --checkpoint FILE: continue from the samples FILE holds (if it exists), render up to <samplesPerPixel> in all and\n"
             "                     save them to FILE; one GPU only; the seed defaults to 0 instead of the clock, so that the same\n"
@@ -59,6 +60,9 @@ static void usage() {
             "           frame in through the guides with albedo and normals (pt_ctx_upsample, default parameters); the image written\n"
             "           is the full-size frame; combines with --denoise and --preview; one GPU only; not with --checkpoint,\n"
             "           --noise-target or --adaptive\n"
+            "  --retrace: with --trace-scale: the pixels for which no low-resolution tap passed the tests (pt_ctx_upsample's weight 0:\n"
+            "           they took the bilinear fallback across an edge) are selected (pt_ctx_select_pixels) and traced at full size\n"
+            "           with <samplesPerPixel> samples into the filled-in frame (pt_ctx_render_masked); prints their number\n"
             "  --orbit N: with --preview FILE.ppm: N frames of a viewport whose camera turns about the vertical axis through the\n"
             "           origin, frame k by k * DEG degrees (--orbit-step DEG, default 2) from the scene's own camera: per frame\n"
             "           pt_ctx_set_camera, pt_ctx_render at <samplesPerPixel>, the first-hit guides, pt_ctx_reproject_var against\n"
@@ -311,9 +315,11 @@ static int render_on_context(const pt_config *cfg, pt_scene *sc, const std::stri
 }
 
 // --trace-scale K: one context on one GPU.  The paths at ceil(W/K) x ceil(H/K), the first-hit guides over the frame's samples at
-// both sizes, then pt_ctx_upsample with albedo and normals at its defaults: the full-size frame into img.  `keep` takes the
-// context and the device frame instead of their being freed.
-static int render_scaled(const pt_config *cfg, pt_scene *sc, uint32_t scale, std::vector<float> &img, pt_stats *st, DeviceFrame *keep) {
+// both sizes, then pt_ctx_upsample with albedo and normals at its defaults: the full-size frame into img.  `retrace`: the pixels
+// the upsampler could not serve (weight 0) are then traced at full size, with the low-resolution frame's samples per pixel, into
+// that frame.  `keep` takes the context and the device frame instead of their being freed.
+static int render_scaled(const pt_config *cfg, pt_scene *sc, uint32_t scale, bool retrace, std::vector<float> &img, pt_stats *st,
+                         DeviceFrame *keep) {
     int dev = 0;
     if (const char *e = getenv("PT_DEVICE")) dev = atoi(e);
     uint32_t n_objs = 0, n_tris = 0;
@@ -324,12 +330,14 @@ static int render_scaled(const pt_config *cfg, pt_scene *sc, uint32_t scale, std
     lo.height = (cfg->height + scale - 1u) / scale;
     const size_t npix = (size_t)cfg->width * cfg->height, nlo = (size_t)lo.width * lo.height;
     pt_ctx *ctx = nullptr;
-    void *d_out = nullptr, *d_lo = nullptr, *d_full = nullptr;
+    void *d_out = nullptr, *d_lo = nullptr, *d_full = nullptr, *d_sel = nullptr;  // d_sel: the weight plane, then the mask
+    uint32_t retraced = 0;
     int rc = pt_ctx_create(dev, &ctx);
     if (!rc) rc = pt_ctx_set_scene(ctx, pt_scene_camera(sc), objs, n_objs, tris, n_tris);
     if (!rc) rc = pt_device_malloc(dev, npix * 3 * sizeof(float), &d_out);
     if (!rc) rc = pt_device_malloc(dev, nlo * 11 * sizeof(float), &d_lo);      // colour, albedo, normal, depth, id
     if (!rc) rc = pt_device_malloc(dev, npix * 8 * sizeof(float), &d_full);  // albedo, normal, depth, id
+    if (!rc && retrace) rc = pt_device_malloc(dev, npix * (sizeof(float) + 1), &d_sel);
     if (!rc) {
         float *lo_color = (float *)d_lo, *lo_albedo = lo_color + nlo * 3, *lo_normal = lo_albedo + nlo * 3, *lo_depth = lo_normal + nlo * 3;
         int32_t *lo_id = (int32_t *)(lo_depth + nlo);
@@ -340,15 +348,23 @@ static int render_scaled(const pt_config *cfg, pt_scene *sc, uint32_t scale, std
         if (!rc) rc = pt_ctx_render_aov(ctx, cfg, albedo, normal, depth, id, nullptr);
         if (!rc)
             rc = pt_ctx_upsample(ctx, cfg->width, cfg->height, lo.width, lo.height, nullptr, lo_color, lo_depth, lo_id, lo_normal, lo_albedo,
-                                 depth, id, normal, albedo, (float *)d_out, nullptr, nullptr);
+                                 depth, id, normal, albedo, (float *)d_out, (float *)d_sel, nullptr);
+        if (!rc && retrace) {
+            const pt_select_params sel = {0.0f, 0.0f, 0u};
+            uint8_t *mask = (uint8_t *)((float *)d_sel + npix);
+            rc = pt_ctx_select_pixels(ctx, cfg->width, cfg->height, &sel, (const float *)d_sel, nullptr, mask, nullptr, nullptr);
+            if (!rc) rc = pt_ctx_render_masked(ctx, cfg, mask, d_out, nullptr, nullptr, nullptr, &retraced);
+        }
     }
     if (!rc) rc = pt_device_download(dev, img.data(), d_out, npix * 3 * sizeof(float));
     if (!rc) {
         printf("\nTraced at %ux%u (--trace-scale %u), filled in to %ux%u\n", lo.width, lo.height, scale, cfg->width, cfg->height);
+        if (retrace) printf("Retraced %u of %zu pixels\n", retraced, npix);
         fflush(stdout);
     }
     if (d_lo) pt_device_free(dev, d_lo);
     if (d_full) pt_device_free(dev, d_full);
+    if (d_sel) pt_device_free(dev, d_sel);
     if (!rc && keep) {
         keep->dev = dev;
         keep->ctx = ctx;
@@ -590,6 +606,7 @@ int main(int argc, char **argv) {
     std::string checkpoint;
     bool write_ppm = true;
     uint32_t gpus = 1, aov_spp = 0, denoise_spp = 0, denoise_var_spp = 0, trace_scale = 0;
+    bool retrace = false;
     NoiseRun noise;
     AdaptiveRun adaptive;
     std::string preview;
@@ -701,6 +718,8 @@ int main(int argc, char **argv) {
                 return 1;
             }
         }
+        else if (a == "--retrace")
+            retrace = true;
         else if (a == "--orbit") {
             const char *v = next();
             orbit_frames = *v && strspn(v, "0123456789") == strlen(v) ? (uint32_t)strtoul(v, nullptr, 10) : 0u;
@@ -820,6 +839,10 @@ int main(int argc, char **argv) {
         fprintf(stderr, "--trace-scale works with one GPU only and not with --checkpoint, --noise-target or --adaptive\n");
         return 1;
     }
+    if (retrace && !trace_scale) {
+        fprintf(stderr, "--retrace needs --trace-scale\n");
+        return 1;
+    }
     if ((!checkpoint.empty() || !adaptive.file.empty()) && !seed_given) seed = 0;
     // load_scene_ids (scenes.rs:28-38): a scenes/ directory without any *.json is filled with the built-in scenes
     if (scene_ids(root).empty()) {
@@ -874,7 +897,7 @@ int main(int argc, char **argv) {
     df.want_error = denoise_var_spp != 0;
     const bool keep_frame = denoise_spp || denoise_var_spp || !preview.empty();  // the frame stays on its GPU for what follows
     if (trace_scale)
-        rc = render_scaled(&cfg, sc, trace_scale, img, &st, keep_frame ? &df : nullptr);
+        rc = render_scaled(&cfg, sc, trace_scale, retrace, img, &st, keep_frame ? &df : nullptr);
     else if (is_adaptive)
         rc = render_adaptive(&cfg, sc, adaptive, img, &st, keep_frame ? &df : nullptr);
     else if (checkpoint.empty() && !keep_frame && !(noise.target > 0.0f))
