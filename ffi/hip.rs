@@ -140,6 +140,55 @@ pub struct PtSelectParams {
     pub flags: u32,
 }
 
+// pt_ctx_scatter (a parity probe: one radiance() invocation on the device): an item, a given surface, what the step decided
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct PtScatterItem {
+    pub o: [f32; 3],
+    pub d: [f32; 3],
+    pub thr: [f32; 3],
+    pub pixel: u32,
+    pub sample: u32,
+    pub depth: u32,
+    pub branch: u32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct PtScatterSurface {
+    pub x: [f32; 3],
+    pub n: [f32; 3],
+    pub color: [f32; 3],
+    pub emission: [f32; 3],
+    pub reflect: u32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct PtScatterOut {
+    pub hit: i32,
+    pub n_rays: u32,
+    pub emits: u32,
+    pub deferred: u32,
+    pub x: [f32; 3],
+    pub contrib: [f32; 3],
+    pub d0: [f32; 3],
+    pub thr0: [f32; 3],
+    pub d1: [f32; 3],
+    pub thr1: [f32; 3],
+    pub depth0: u32,
+    pub branch0: u32,
+    pub depth1: u32,
+    pub branch1: u32,
+}
+
+pub const PT_SCATTER_GIVEN: u32 = 0;
+pub const PT_SCATTER_BY_ID: u32 = 1;
+pub const PT_SCATTER_BY_RANK: u32 = 2;
+pub const PT_SCATTER_DEFER_REFRACT: u32 = 0x10;
+pub const PT_SCATTER_REFRACT_ONLY: u32 = 0x20;
+pub const PT_SCATTER_NOT_SHADED: i32 = -2;
+
 // pt_ctx_denoise's parameters; a zero field = the library's default (pt_denoise_defaults)
 #[repr(C)]
 #[derive(Clone, Copy, Default, Debug)]
@@ -523,6 +572,16 @@ extern "C" {
         cancel: *const u8,
         stats: *mut PtStats,
         n_pixels: *mut u32,
+    ) -> i32;
+    // host arrays of n; `surfaces` is read by PT_SCATTER_GIVEN alone
+    pub fn pt_ctx_scatter(
+        ctx: *mut PtCtx,
+        seed: u64,
+        form: u32,
+        items: *const PtScatterItem,
+        surfaces: *const PtScatterSurface,
+        n: u32,
+        out: *mut PtScatterOut,
     ) -> i32;
     pub fn pt_write_pfm(path: *const c_char, data: *const f32, width: u32, height: u32, channels: u32) -> i32;
     pub fn pt_device_malloc(device: i32, bytes: usize, out: *mut *mut c_void) -> i32;

@@ -335,6 +335,67 @@ int pt_ctx_sincos_sweep(pt_ctx *ctx, uint64_t out[2]);
 int pt_ctx_primary_rays(pt_ctx *ctx, uint32_t width, uint32_t height, uint64_t seed, const uint32_t *pixel,
                         const uint32_t *sample, uint32_t n, uint32_t form, float *o, float *d);
 
+/* Diagnostics: ONE radiance() invocation after its intersect_scene call (mod.rs:665-789) - the roulette verdict, the diffuse
+ * basis and direction, the mirror direction, tdir, Re / Tr / P, the split, the children's depth and branch - ON THE DEVICE,
+ * through the functions the frame kernels call (shade_surface, fetch_surface, fetch_surface_rank: called, not copied), for n
+ * items.  An item is the ray, the throughput above it and its RNG key: the draws are words 0 (roulette), 1 (diffuse r1 / the
+ * refract choice) and 2 (diffuse r2) of the block (seed; pixel, sample, tag (branch << 8) | (depth + 1)).  `form` says where
+ * the surface comes from and which instantiation of the shading step runs:
+ *   PT_SCATTER_GIVEN      surfaces[i] is the surface (hit point, normal, colour, emission, reflect type); max(colour) and its
+ *                         reciprocal are filled in on the host by the routine that fills them for a scene's materials.  No scene
+ *                         is needed; out[i].hit = 0.
+ *   PT_SCATTER_BY_ID      the closest hit of pt_ctx_intersect's kernel function, then the surface by hit id (what k_shade, k_pass and
+ *                         k_mega do).  `surfaces` is not read.
+ *   PT_SCATTER_BY_RANK    the same hit mapped to its visiting rank, then the surface from the rank's record (what k_pass_cand and
+ *                         k_mega_cand do).  A workgroup stages the leading ranks of the table in LDS exactly when k_pass_cand
+ *                         would for this scene (the whole table does not fit beside the walk queues), so ranks below that head
+ *                         come from LDS and the others from global memory.  Refused for a scene without candidate tables.
+ *   | PT_SCATTER_DEFER_REFRACT   kShadeDeferRefract: a Refract surface comes back `deferred` with no rays and nothing else
+ *                         defined; every other surface as without the flag.
+ *   | PT_SCATTER_REFRACT_ONLY    kShadeRefractOnly.  The frame kernels only hand it Refract surfaces: with PT_SCATTER_GIVEN an item
+ *                         whose surface is not Refract is refused; with the other two sources such an item comes back with hit
+ *                         = PT_SCATTER_NOT_SHADED and nothing else defined.
+ * out[i]: hit = -1 for a miss (nothing else defined), else the hit id (object index of a sphere, n_objs + flattened triangle
+ * index); x; contrib = thr * emission and emits (some channel of the emission != 0); n_rays (0: the roulette or MAX_DEPTH ended the
+ * path) continuation rays from x with directions d0, d1 and throughputs thr0, thr1 (d1, thr1: the transmitted ray of a split;
+ * with fewer rays the unused ones hold what ShadeOut holds) and the depth and branch of each child.  Throughput goes DOWN
+ * the path: thr0 = fl(fl(thr * colour') * factor) per channel, colour' the colour after the roulette's rescale.
+ * This proves the functions, not each kernel's use of them: that stays with the bounce counts and the frame tests.
+ * tests/kats_scatter.py is the independent restatement; the oracle's pto_dump_paths gives its paths with their keys.
+ * PT_ERR_INVALID, all refused before any device is touched, checked in this order: NULL items or out; n == 0; unknown form
+ * bits (or both mode flags, or source 3); PT_SCATTER_GIVEN without surfaces; an item with sample >= 2^24, depth > 11 or
+ * branch outside 1..7; PT_SCATTER_GIVEN: a reflect type above 2, or PT_SCATTER_REFRACT_ONLY with a surface that is not Refract;
+ * NULL ctx.  Then PT_ERR_NO_DEVICE without a device; then PT_ERR_INVALID for the other two sources without a scene, or
+ * PT_SCATTER_BY_RANK on a scene without candidate tables.  Host arrays of n. */
+#define PT_SCATTER_GIVEN 0u
+#define PT_SCATTER_BY_ID 1u
+#define PT_SCATTER_BY_RANK 2u
+#define PT_SCATTER_DEFER_REFRACT 0x10u
+#define PT_SCATTER_REFRACT_ONLY 0x20u
+#define PT_SCATTER_NOT_SHADED (-2)
+typedef struct pt_scatter_item {
+    float o[3], d[3];   /* the ray of this radiance() call */
+    float thr[3];       /* product of the weights above it ((1, 1, 1) for a primary ray) */
+    uint32_t pixel;     /* framebuffer index: the RNG counter's first word */
+    uint32_t sample;    /* < 2^24 */
+    uint32_t depth;     /* the `depth` argument: 0..11 */
+    uint32_t branch;    /* 1..7 (1: no split above) */
+} pt_scatter_item;
+typedef struct pt_scatter_surface {
+    float x[3], n[3];   /* hit.intersection, hit.normal */
+    float color[3], emission[3];
+    uint32_t reflect;   /* PT_DIFFUSE / PT_SPECULAR / PT_REFRACT */
+} pt_scatter_surface;
+typedef struct pt_scatter_out {
+    int32_t hit;
+    uint32_t n_rays, emits, deferred;
+    float x[3], contrib[3];
+    float d0[3], thr0[3], d1[3], thr1[3];
+    uint32_t depth0, branch0, depth1, branch1;
+} pt_scatter_out;
+int pt_ctx_scatter(pt_ctx *ctx, uint64_t seed, uint32_t form, const pt_scatter_item *items,
+                   const pt_scatter_surface *surfaces /* PT_SCATTER_GIVEN only */, uint32_t n, pt_scatter_out *out);
+
 /* The host instantiation of the shared numerics header's sincos (the same source the kernels compile). */
 void pt_host_sincos(float y, float *s, float *c);
 

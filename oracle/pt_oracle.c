@@ -416,6 +416,8 @@ typedef struct {
     /* optional ray dump (every intersect_scene call): o(3) d(3) per ray */
     float *dump;
     uint64_t dump_cap, dump_n;
+    /* pto_dump_paths: with a dump, (pixel, sample, depth, branch) of every dumped ray - the arguments radiance() carries */
+    uint32_t *dump_keys;
     /* MOCK_RANDOM mode (mod.rs:31-51): when non-NULL every rand01() call takes the next entry of the reference's
      * cyclic 9-value table, in the reference's own call order, instead of a Philox word */
     uint64_t *mock_index;
@@ -433,6 +435,10 @@ static inline float mock_rand01(uint64_t *index) { return MOCK_RANDOMS[(*index)+
 static v3 radiance(rctx *c, v3 ro, v3 rd, int depth, uint32_t branch) {
     if (c->cnt) c->cnt->ray_bounces++;
     if (c->dump && c->dump_n < c->dump_cap) {
+        if (c->dump_keys) {
+            uint32_t *k = c->dump_keys + 4 * c->dump_n;
+            k[0] = c->pixel, k[1] = c->sample, k[2] = (uint32_t)depth, k[3] = branch;
+        }
         float *p = c->dump + 6 * c->dump_n++;
         vst(p, ro);
         vst(p + 3, rd);
@@ -519,7 +525,7 @@ static v3 radiance(rctx *c, v3 ro, v3 rd, int depth, uint32_t branch) {
 /* test_radiance's loop (test.rs:146-183): `n` samples of one fixed ray, sample i keyed (pixel, i) */
 void pto_radiance_mean(const pto_scene *s, const float o[3], const float d[3], uint64_t seed, uint32_t pixel,
                        uint32_t n, float out[3], pto_counters *cnt) {
-    rctx c = {s, seed, pixel, 0, cnt, NULL, 0, 0, NULL};
+    rctx c = {s, seed, pixel, 0, cnt, NULL, 0, 0, NULL, NULL};
     v3 acc = V(0, 0, 0);
     for (uint32_t i = 0; i < n; i++) {
         c.sample = i;
@@ -532,7 +538,7 @@ void pto_radiance_mean(const pto_scene *s, const float o[3], const float d[3], u
  * mod.rs:677 (new_depth > 5) and mod.rs:760 (new_depth > 2) */
 void pto_radiance_mean_at(const pto_scene *s, const float o[3], const float d[3], uint32_t depth, uint64_t seed,
                           uint32_t pixel, uint32_t n, float out[3], pto_counters *cnt) {
-    rctx c = {s, seed, pixel, 0, cnt, NULL, 0, 0, NULL};
+    rctx c = {s, seed, pixel, 0, cnt, NULL, 0, 0, NULL, NULL};
     v3 acc = V(0, 0, 0);
     for (uint32_t i = 0; i < n; i++) {
         c.sample = i;
@@ -585,7 +591,7 @@ static void primary_ray(const cam_basis *cb, uint32_t width, uint32_t height, ui
 
 static v3 render_pixel(const pto_scene *s, const cam_basis *cb, const pto_config *cfg, uint32_t pixel_index,
                        pto_counters *cnt, uint64_t *mock_index) {
-    rctx c = {s, cfg->seed, pixel_index, 0, cnt, NULL, 0, 0, mock_index};
+    rctx c = {s, cfg->seed, pixel_index, 0, cnt, NULL, 0, 0, NULL, mock_index};
     v3 radiance_v = V(0, 0, 0);
     for (uint32_t smp = 0; smp < cfg->spp; smp++) {
         v3 ro, rd;
@@ -618,7 +624,26 @@ void pto_render_pixel(const pto_scene *s, const pto_config *cfg, uint32_t pixel_
 uint64_t pto_dump_rays(const pto_scene *s, const pto_config *cfg, uint32_t idx_begin, uint32_t idx_end,
                        float *rays_od, uint64_t cap) {
     cam_basis cb = make_basis(&s->camera);
-    rctx c = {s, cfg->seed, 0, 0, NULL, rays_od, cap, 0, NULL};
+    rctx c = {s, cfg->seed, 0, 0, NULL, rays_od, cap, 0, NULL, NULL};
+    for (uint32_t idx = idx_begin; idx < idx_end; idx++) {
+        c.pixel = idx;
+        for (uint32_t smp = 0; smp < cfg->spp; smp++) {
+            v3 ro, rd;
+            primary_ray(&cb, cfg->width, cfg->height, idx, smp, cfg->seed, NULL, &ro, &rd);
+            c.sample = smp;
+            (void)radiance(&c, ro, rd, 0, 1u);
+        }
+    }
+    return c.dump_n;
+}
+
+/* pto_dump_rays with the key of every dumped ray: keys[4 * i ..] = (pixel, sample, depth, branch) of ray i, depth and branch
+ * being the arguments of that radiance() call.  The children of a ray are the dumped rays with its pixel and sample, depth + 1
+ * and branch b (one child), or 2b and 2b + 1 (the reflected and the transmitted ray of a split). */
+uint64_t pto_dump_paths(const pto_scene *s, const pto_config *cfg, uint32_t idx_begin, uint32_t idx_end, float *rays_od,
+                        uint32_t *keys, uint64_t cap) {
+    cam_basis cb = make_basis(&s->camera);
+    rctx c = {s, cfg->seed, 0, 0, NULL, rays_od, cap, 0, keys, NULL};
     for (uint32_t idx = idx_begin; idx < idx_end; idx++) {
         c.pixel = idx;
         for (uint32_t smp = 0; smp < cfg->spp; smp++) {

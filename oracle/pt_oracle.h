@@ -64,6 +64,9 @@ void pto_render_pixel(const pto_scene *s, const pto_config *cfg, uint32_t pixel_
                       pto_counters *cnt);
 uint64_t pto_dump_rays(const pto_scene *s, const pto_config *cfg, uint32_t idx_begin, uint32_t idx_end,
                        float *rays_od, uint64_t cap);
+/* the same with keys[4 * i ..] = (pixel, sample, depth, branch) of dumped ray i: the arguments of its radiance() call */
+uint64_t pto_dump_paths(const pto_scene *s, const pto_config *cfg, uint32_t idx_begin, uint32_t idx_end, float *rays_od,
+                        uint32_t *keys, uint64_t cap);
 int pto_render(const pto_scene *s, const pto_config *cfg, uint32_t idx_begin, uint32_t idx_end, float *out_rgb,
                int threads, pto_counters *cnt_out, double *seconds);
 /* render() with MOCK_RANDOM = true (mod.rs:31-51, 1017-1018): sequential pixels, one global cyclic 9-value table */

@@ -80,6 +80,28 @@ class pt_select_params(C.Structure):
     _fields_ = [("weight_max", C.c_float), ("len_max", C.c_float), ("flags", C.c_uint32)]
 
 
+class pt_scatter_item(C.Structure):
+    _fields_ = [("o", C.c_float * 3), ("d", C.c_float * 3), ("thr", C.c_float * 3), ("pixel", C.c_uint32), ("sample", C.c_uint32),
+                ("depth", C.c_uint32), ("branch", C.c_uint32)]
+
+
+class pt_scatter_surface(C.Structure):
+    _fields_ = [("x", C.c_float * 3), ("n", C.c_float * 3), ("color", C.c_float * 3), ("emission", C.c_float * 3),
+                ("reflect", C.c_uint32)]
+
+
+class pt_scatter_out(C.Structure):
+    _fields_ = [("hit", C.c_int32), ("n_rays", C.c_uint32), ("emits", C.c_uint32), ("deferred", C.c_uint32),
+                ("x", C.c_float * 3), ("contrib", C.c_float * 3), ("d0", C.c_float * 3), ("thr0", C.c_float * 3),
+                ("d1", C.c_float * 3), ("thr1", C.c_float * 3), ("depth0", C.c_uint32), ("branch0", C.c_uint32),
+                ("depth1", C.c_uint32), ("branch1", C.c_uint32)]
+
+
+PT_SCATTER_GIVEN, PT_SCATTER_BY_ID, PT_SCATTER_BY_RANK = 0, 1, 2
+PT_SCATTER_DEFER_REFRACT, PT_SCATTER_REFRACT_ONLY = 0x10, 0x20
+PT_SCATTER_NOT_SHADED = -2
+
+
 class pt_noise_stats(C.Structure):
     _fields_ = [("spp_min", C.c_uint32), ("spp_max", C.c_uint32), ("spp_a_min", C.c_uint32), ("spp_b_min", C.c_uint32),
                 ("pixels", C.c_uint64), ("mean_error", C.c_double), ("histogram", C.c_uint32 * 64)]
@@ -187,6 +209,8 @@ def lib():
                                        C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p]
     L.pt_ctx_render_masked.argtypes = [C.c_void_p, C.POINTER(pt_config), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.POINTER(pt_stats), C.POINTER(C.c_uint32)]
+    L.pt_ctx_scatter.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(pt_scatter_item), C.POINTER(pt_scatter_surface),
+                                 C.c_uint32, C.POINTER(pt_scatter_out)]
     L.pt_write_pfm.argtypes = [C.c_char_p, C.POINTER(C.c_float), C.c_uint32, C.c_uint32, C.c_uint32]
     L.pt_ctx_set_profiling.argtypes = [C.c_void_p, C.c_int]
     L.pt_ctx_pass_kernel.argtypes = [C.c_void_p, C.c_uint32]
@@ -432,6 +456,15 @@ class Context:
         _check(lib().pt_ctx_select_pixels(self._h, width, height, C.byref(p), ptr(weight), ptr(len), ptr(mask), C.byref(n),
                                           C.c_void_p(stream or 0)))
         return n.value
+
+    def scatter(self, items, seed=1, form=PT_SCATTER_BY_ID, surfaces=None):
+        """One radiance() invocation per item on the device, through the functions the frame kernels call (pt_ctx_scatter, a
+        parity probe).  `items`: a ctypes array of pt_scatter_item; `surfaces`: one of pt_scatter_surface with PT_SCATTER_GIVEN.
+        `form`: PT_SCATTER_GIVEN / _BY_ID / _BY_RANK, optionally | PT_SCATTER_DEFER_REFRACT or PT_SCATTER_REFRACT_ONLY.  Returns a
+        ctypes array of pt_scatter_out."""
+        out = (pt_scatter_out * len(items))()
+        _check(lib().pt_ctx_scatter(self._h, seed, form, items, surfaces, len(items), out))
+        return out
 
     def render_masked(self, mask, rgb, width, height, spp, seed=1, band=None, no_bvh=False, rays_per_pass=0, stream=None):
         """Trace the pixels of the frame whose mask byte is not zero and write them into `rgb` (pt_ctx_render_masked): each gets

@@ -19,6 +19,7 @@
 #include "pt_masked.h"
 #include "pt_noise.h"
 #include "pt_present.h"
+#include "pt_probe.h"
 #include "pt_reproject.h"
 #include "pt_upsample.h"
 #include "pt_tile.h"
@@ -2685,6 +2686,55 @@ int pt_ctx_primary_rays(pt_ctx *c, uint32_t width, uint32_t height, uint64_t see
     d_d.release();
     if (e != hipSuccess) {
         set_error(std::string("primary rays: ") + hipGetErrorString(e));
+        return PT_ERR_HIP;
+    }
+    return PT_OK;
+}
+
+int pt_ctx_scatter(pt_ctx *c, uint64_t seed, uint32_t form, const pt_scatter_item *items, const pt_scatter_surface *surfaces,
+                   uint32_t n, pt_scatter_out *out) {
+    std::vector<ScatterSurf> given;
+    int rc = host::check_scatter(c, form, items, surfaces, n, out, given);
+    if (rc) return rc;
+    if (device_count_quiet() <= 0) {
+        set_error("no HIP device: libptrace_hip has no CPU fallback");
+        return PT_ERR_NO_DEVICE;
+    }
+    const uint32_t src = form & kScatterSourceMask;
+    if (src != PT_SCATTER_GIVEN && !c->has_scene) return refuse("no scene set");
+    if (src == PT_SCATTER_BY_RANK && !c->cand_ok) return refuse("PT_SCATTER_BY_RANK: the scene has no candidate tables");
+    HIP_TRY(hipSetDevice(c->device));
+    ScatterCall call{};
+    call.n = n;
+    call.form = form;
+    call.seed_lo = (uint32_t)seed;
+    call.seed_hi = (uint32_t)(seed >> 32);
+    if (src == PT_SCATTER_BY_RANK) {
+        // the head k_pass_cand would stage for this scene (pt_layout.h; one-pixel streams), while it fits the probe's workgroup
+        const DevScene F = form_for(c, 0u).scene;
+        const size_t room = scatter_head_room(c->scene) / sizeof(SurfRec);
+        call.head = (uint32_t)std::min<size_t>(lds_layout(F, 1u, c->tune.lds_pad).surf_head, room);
+    }
+    DevBuf<pt_scatter_item> d_items;
+    DevBuf<ScatterSurf> d_surf;
+    DevBuf<pt_scatter_out> d_out;
+    if ((rc = d_items.ensure(n)) || (rc = d_out.ensure(n)) || (!given.empty() && (rc = d_surf.ensure(n)))) return rc;
+    hipStream_t st = c->stream;
+    hipError_t e = hipMemcpyAsync(d_items.p, items, (size_t)n * sizeof(pt_scatter_item), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && !given.empty())
+        e = hipMemcpyAsync(d_surf.p, given.data(), (size_t)n * sizeof(ScatterSurf), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+        call.items = d_items.p;
+        call.surf = d_surf.p;
+        call.out = d_out.p;
+        launch_scatter(st, c->scene, call);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out.p, (size_t)n * sizeof(pt_scatter_out), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    else (void)hipStreamSynchronize(st);  // (the host arrays of the copies issued so far stay the caller's until they have run)
+    if (e != hipSuccess) {
+        set_error(std::string("scatter: ") + hipGetErrorString(e));
         return PT_ERR_HIP;
     }
     return PT_OK;

@@ -5,6 +5,7 @@
 #include "pt_denoise.h"
 #include "pt_masked.h"
 #include "pt_present.h"
+#include "pt_probe.h"
 #include "pt_reproject.h"
 #include "pt_upsample.h"
 
@@ -479,11 +480,10 @@ bool flatten_scene(const pt_camera &cam, const pt_object *objs, uint32_t n_objs,
         m.cr = o.color[0];
         m.cg = o.color[1];
         m.cb = o.color[2];
-        m.max_refl = f_max(o.color[0], f_max(o.color[1], o.color[2]));  // mod.rs:668
         m.er = o.emission[0];
         m.eg = o.emission[1];
         m.eb = o.emission[2];
-        m.inv_max_refl = 1.0f / m.max_refl;  // mod.rs:679
+        material_reflectance(o.color, m.max_refl, m.inv_max_refl);
         m.px = position.x;
         m.py = position.y;
         m.pz = position.z;
@@ -1563,6 +1563,46 @@ int check_masked_cfg(const pt_config &cfg) {
         return refuse("masked: the band must consist of whole image rows");
     if (cfg.chunk_step > 1u || ((cfg.flags >> 8) & 15u) != 0u)
         return refuse("masked: chunk_step > 1 and PT_FLAG_PIPELINES are not supported");
+    return PT_OK;
+}
+
+// ---- pt_ctx_scatter (ptrace.h, pt_probe.h)
+void material_reflectance(const float color[3], float &max_refl, float &inv_max_refl) {
+    max_refl = f_max(color[0], f_max(color[1], color[2]));  // mod.rs:668
+    inv_max_refl = 1.0f / max_refl;                         // mod.rs:679
+}
+
+int check_scatter(const void *ctx, uint32_t form, const pt_scatter_item *items, const pt_scatter_surface *surfaces, uint32_t n,
+                  const pt_scatter_out *out, std::vector<ScatterSurf> &given) {
+    if (!items || !out) return refuse("items or out is NULL");
+    if (n == 0u) return refuse("n is 0");
+    const uint32_t src = form & kScatterSourceMask, mode = form & kScatterModeMask;
+    if ((form & ~(kScatterSourceMask | kScatterModeMask)) || src == 3u || mode == kScatterModeMask)
+        return refuse("form: unknown bits, source 3 or both mode flags");
+    if (src == PT_SCATTER_GIVEN && !surfaces) return refuse("surfaces is NULL with PT_SCATTER_GIVEN");
+    for (uint32_t i = 0; i < n; ++i)
+        if (items[i].sample >= (1u << 24) || items[i].depth > 11u || items[i].branch < 1u || items[i].branch > 7u)
+            return refuse("an item's sample >= 2^24, depth > 11 or branch outside 1..7");
+    if (src == PT_SCATTER_GIVEN)
+        for (uint32_t i = 0; i < n; ++i) {
+            if (surfaces[i].reflect > PT_REFRACT) return refuse("a surface's reflect type is unknown");
+            if (mode == PT_SCATTER_REFRACT_ONLY && surfaces[i].reflect != PT_REFRACT)
+                return refuse("PT_SCATTER_REFRACT_ONLY with a surface that is not Refract");
+        }
+    if (!ctx) return refuse("ctx is NULL");
+    given.clear();
+    if (src != PT_SCATTER_GIVEN) return PT_OK;
+    given.resize(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        const pt_scatter_surface &s = surfaces[i];
+        ScatterSurf &g = given[i];
+        memcpy(g.x, s.x, sizeof g.x);
+        memcpy(g.n, s.n, sizeof g.n);
+        memcpy(g.color, s.color, sizeof g.color);
+        memcpy(g.emission, s.emission, sizeof g.emission);
+        material_reflectance(s.color, g.max_refl, g.inv_max_refl);
+        g.reflect = s.reflect;
+    }
     return PT_OK;
 }
 

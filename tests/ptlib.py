@@ -122,6 +122,8 @@ def oracle():
     L.pto_dump_rays.argtypes = [C.POINTER(PtoScene), C.POINTER(PtoConfig), C.c_uint32, C.c_uint32, fp,
                                 C.c_uint64]
     L.pto_dump_rays.restype = C.c_uint64
+    L.pto_dump_paths.argtypes = [C.POINTER(PtoScene), C.POINTER(PtoConfig), C.c_uint32, C.c_uint32, fp, u32p, C.c_uint64]
+    L.pto_dump_paths.restype = C.c_uint64
     L.pto_render.argtypes = [C.POINTER(PtoScene), C.POINTER(PtoConfig), C.c_uint32, C.c_uint32, fp, C.c_int,
                              C.POINTER(PtoCounters), C.POINTER(C.c_double)]
     L.pto_render.restype = C.c_int

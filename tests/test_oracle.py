@@ -499,3 +499,83 @@ def test_mock_random_frames_against_committed_ppm(sid, res_y, spp):
     L.pto_format_ppm(_np_f(img), width, res_y, spp, sid.encode(), 0, buf, n)
     want = open(os.path.join(ptlib.ROOT, "tests", "golden", "mock_%s_%d_%d.ppm" % (sid, res_y, spp)), "rb").read()
     assert buf.raw[:n] == want
+
+
+# ---- one radiance() invocation, ray by ray: the oracle's paths (pto_dump_paths) against tests/kats_scatter.py -------------------
+import kats_camera
+import kats_scatter
+import scatter_walk
+
+
+def test_dump_paths_is_dump_rays_with_keys():
+    """pto_dump_paths writes pto_dump_rays' rays in its order, and for each the arguments of its radiance() call: every path
+    starts at (depth 0, branch 1), a key names one ray, every other ray is the child of exactly one ray."""
+    W = scatter_walk.walk("cornell", 16, 12, 8)
+    L = ptlib.oracle()
+    rays = np.zeros((W.n + 8, 6), np.float32)
+    cfg = ptlib.PtoConfig(W.width, W.height, W.spp, 0, scatter_walk.SEED)
+    ps = W.scene.pto()
+    assert L.pto_dump_rays(C.byref(ps), C.byref(cfg), 0, W.width * W.height, _np_f(rays), len(rays)) == W.n
+    assert rays[:W.n, :3].tobytes() == W.o.tobytes() and rays[:W.n, 3:].tobytes() == W.d.tobytes()
+    roots = [i for i in range(W.n) if W.keys[i][2] == 0]
+    assert len(roots) == W.width * W.height * W.spp and all(W.keys[i][3] == 1 for i in roots)
+    claimed = sorted(k for kids in W.children for k in kids)
+    assert claimed == sorted(set(range(W.n)) - set(roots))
+    assert (W.keys[:, 2] <= 11).all() and (W.keys[:, 3] >= 1).all() and (W.keys[:, 3] <= 7).all()
+
+
+# what the oracle shows of each kind at these sizes (scatter_walk.kinds: from the oracle alone); cornell shows every kind
+WALK_KINDS = {
+    "cornell": dict(diffuse_child=10490, mirror_child=265, split_pair=195, chosen_reflection=161, chosen_transmission=390,
+                    roulette_death=704, roulette_survival=4070, stop_at_12=407, miss=620),
+    "three-spheres": dict(diffuse_child=89, mirror_child=0, split_pair=0, chosen_reflection=0, chosen_transmission=0,
+                          roulette_death=0, roulette_survival=0, stop_at_12=0, miss=1536),
+    "mesh": dict(diffuse_child=2534, mirror_child=0, split_pair=0, chosen_reflection=0, chosen_transmission=0,
+                 roulette_death=130, roulette_survival=866, stop_at_12=92, miss=162),
+}
+
+
+def test_the_walked_frames_show_every_kind():
+    total = dict.fromkeys(scatter_walk.KINDS, 0)
+    for frame in scatter_walk.FRAMES:
+        got = scatter_walk.kinds(scatter_walk.walk(*frame))
+        assert got == WALK_KINDS[frame[0]], frame
+        for k, v in got.items():
+            total[k] += v
+    assert all(v > 0 for v in total.values()), total
+
+
+@pytest.mark.parametrize("frame", scatter_walk.FRAMES, ids=[f[0] for f in scatter_walk.FRAMES])
+def test_oracle_paths_against_the_independent_restatement(frame):
+    """Every dumped ray that hits goes, with its pto_intersect_batch hit, through kats_scatter.scatter: exactly the dumped
+    children must come back - the same count, origin (the hit point) and direction bit for bit, depth and branch as the keys
+    say.  A miss has no children; every primary ray is kats_camera's.  No ray is left out: each is a primary ray or is claimed
+    as a child exactly once."""
+    W = scatter_walk.walk(*frame)
+    sc = W.scene
+    cam = dict(position=tuple(sc.cam.position), direction=tuple(sc.cam.direction), focal_length=sc.cam.focal_length,
+               sensor_width=sc.cam.sensor_width, aspect_ratio=sc.cam.aspect_ratio)
+    compared = np.zeros(W.n, bool)
+    for i in range(W.n):
+        p, s, depth, branch = (int(v) for v in W.keys[i])
+        if depth == 0:
+            u1, u2 = kats_camera.camera_draws(scatter_walk.SEED, p, s)
+            o, d = kats_camera.primary_ray(cam, W.width, W.height, p, s, u1, u2)
+            assert o.tobytes() == W.o[i].tobytes() and d.tobytes() == W.d[i].tobytes(), (i, p, s)
+            assert not compared[i]
+            compared[i] = True
+        if W.oid[i] < 0:
+            assert W.children[i] == [], i
+            continue
+        obj = sc.objs[int(W.oid[i])]
+        got = kats_scatter.scatter(W.d[i], W.nrm[i], tuple(obj.color), tuple(obj.emission), obj.reflect_type, depth, branch,
+                                   kats_scatter.draws(scatter_walk.SEED, p, s, depth, branch))
+        kids = W.children[i]
+        assert len(got["children"]) == len(kids), (i, got["kind"], len(kids))
+        for (cd, _, cdepth, cbranch), k in zip(got["children"], kids):
+            assert W.x[i].tobytes() == W.o[k].tobytes(), (i, k, got["kind"])
+            assert cd.tobytes() == W.d[k].tobytes(), (i, k, got["kind"], cd, W.d[k])
+            assert (cdepth, cbranch) == (int(W.keys[k][2]), int(W.keys[k][3])), (i, k)
+            assert not compared[k]
+            compared[k] = True
+    assert compared.all()
