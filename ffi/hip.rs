@@ -258,6 +258,22 @@ pub struct PtAdaptiveInfo {
     pub samples: u64,
     pub mean_error: f64,
 }
+/// pt_ctx_table_hashes: the index of each device table in its output (PT_TABLE_* of ptrace.h)
+pub const PT_TABLE_OBJS: usize = 0;
+pub const PT_TABLE_OBJ_PAIRS: usize = 1;
+pub const PT_TABLE_TRI_PAIRS: usize = 2;
+pub const PT_TABLE_MATS: usize = 3;
+pub const PT_TABLE_TRI_SHADE: usize = 4;
+pub const PT_TABLE_BVH_NODES: usize = 5;
+pub const PT_TABLE_BVH_NODES4: usize = 6;
+pub const PT_TABLE_SPH_PAIRS: usize = 7;
+pub const PT_TABLE_FLAT_PAIRS: usize = 8;
+pub const PT_TABLE_CAND_PAIRS: usize = 9;
+pub const PT_TABLE_RANK_ID: usize = 10;
+pub const PT_TABLE_SURF: usize = 11;
+pub const PT_TABLE_TRI_RANK: usize = 12;
+pub const PT_TABLE_BVH_MESHES: usize = 13;
+pub const PT_TABLE_COUNT: usize = 14;
 pub const PT_DENOISE_NO_DEMODULATE: u32 = 1;
 pub const PT_PRESENT_RGBA8: u32 = 0;
 pub const PT_PRESENT_RGB8: u32 = 1;
@@ -305,6 +321,8 @@ extern "C" {
     pub fn pt_ctx_set_camera(ctx: *mut PtCtx, cam: *const PtCamera, rebuilt: *mut i32) -> i32;
     pub fn pt_ctx_camera_reach(ctx: *const PtCtx, lo: *mut f32, hi: *mut f32) -> i32;
     pub fn pt_ctx_reserve_camera_reach(ctx: *mut PtCtx, lo: *const f32, hi: *const f32, rebuilt: *mut i32) -> i32;
+    pub fn pt_ctx_set_object(ctx: *mut PtCtx, index: u32, obj: *const PtObject, rebuilt: *mut i32) -> i32;
+    pub fn pt_ctx_table_hashes(ctx: *mut PtCtx, out: *mut u64) -> i32;
     pub fn pt_scene_reach(
         cam: *const PtCamera,
         objs: *const PtObject,
@@ -667,6 +685,15 @@ pub struct ReprojectFrame {
 /// (pt_ctx_reproject, in place: d_out_color = d_color), and the two swap roles: on return `hist` is the new history and `cur`
 /// the set of buffers the next frame renders into.  Pointers change hands; nothing is copied.  `have_history`: false for the
 /// first frame after a scene change.  `weight`: the samples per pixel `cur` was rendered with.
+///
+/// Dragging an object (the GUI's selection): pick once, then per mouse move replace the object and render - no pt_ctx_set_scene:
+/// ```ignore
+/// let mut obj = objects[picked];                        // the host's copy of the object pt_ctx_orbit_point named
+/// obj.position = dragged_position();
+/// let mut rebuilt = 0i32;
+/// unsafe { pt_ctx_set_object(ctx, picked as u32, &obj, &mut rebuilt) };   // rebuilt != 0: it left the scene's reach (rare)
+/// have_history = false;                                 // a frame in which an object moved passes no history on
+/// ```
 ///
 /// One turn of a viewport: the scene is set once (pt_ctx_set_scene), the camera moves per frame (pt_ctx_set_camera):
 /// ```ignore

@@ -206,6 +206,63 @@ int pt_ctx_reserve_camera_reach(pt_ctx *ctx, const float lo[3], const float hi[3
 int pt_scene_reach(const pt_camera *cam, const pt_object *objs, uint32_t n_objs, const pt_triangle *tris, uint32_t n_tris,
                    float lo[3], float hi[3]);
 
+/* Replace object `index` of the scene pt_ctx_set_scene gave, without building the scene again: what a host calls per mouse move
+ * while the user drags a sphere, nudges a mesh or changes a colour.  The triangle array is not touched.
+ * REACH.  As under pt_ctx_set_camera: the device tables depend on the scene only through the box B (pt_ctx_camera_reach) that
+ * bounds every ray origin, and otherwise each record on its own object.  So while an edited object stays inside B, only that
+ * object's records change.  The object's bounds, in binary32: a sphere's centre -/+ |radius|; a mesh's object-local vertex box,
+ * cached at pt_ctx_set_scene, plus position (addition is monotone, so this is what pt_scene_reach computes vertex by vertex).
+ * SAME: *obj bitwise equal to the context's copy (nineteen words): nothing changes, both held frames stay, *rebuilt = 0.
+ * MATERIAL path (*rebuilt = 0): only color, emission or reflect_type differ.  The object's material record, the surface records
+ * at its ranks and the glass deferral, as pt_ctx_set_scene derives it, are updated; no geometry table is touched.
+ * MOVE path, in reach (*rebuilt = 0): position, radius, bs_center or bs_radius differ (the material may too) and
+ * lo[a] <= bounds.lo[a], bounds.hi[a] <= hi[a] on all three axes.  Only this object's records are rewritten, at their offsets in
+ * the device tables.  A mesh with a BVH (16 triangles or more) keeps its tree and is REFIT ON THE DEVICE: the first such edit of
+ * a mesh uploads its object-local triangles (36 B each) and a plan of its tree; from then on no triangle crosses to the device -
+ * one lane per leaf recomputes the pair records, normals and padded boxes, one launch per height of the tree unites the boxes
+ * bottom-up, one gathers the four-wide nodes.  Every edit recomputes from the object-local triangles: a sequence of moves does
+ * not drift.  Smaller meshes and spheres are recomputed on the host by the code pt_ctx_set_scene runs.
+ * OUT OF REACH (*rebuilt = 1): B grows per axis by pt_ctx_set_camera's rule applied to the violated bounds:
+ * bounds.lo[a] < lo[a] gives lo[a] = bounds.lo[a] - (lo[a] - bounds.lo[a]); bounds.hi[a] > hi[a] gives
+ * hi[a] = bounds.hi[a] + (bounds.hi[a] - hi[a]); the overshoot doubles.  The scene is flattened again for the new box from the
+ * context's host copies and uploaded, exactly as on pt_ctx_set_camera's slow path.  If flattening fails the context is left as it was.
+ * AFTERWARDS, on every path but SAME: the context's copy of the object is *obj; the frame pt_ctx_accumulate holds and the held
+ * adaptive frame are dropped; the checkpoint fingerprint is marked stale (the next save or load computes the one
+ * pt_ctx_set_scene would have given); the boxes of pt_ctx_set_mesh_bounds are marked dirty, because they take the object's
+ * position.  The measured pass and round rates and the image passes' scratch are kept.  The call returns when the tables are final.
+ * EQUIVALENCE.  After the call, on any path, every entry point returns what it returns after pt_ctx_set_scene(the context's
+ * camera, the edited objects, the same triangles), bit for bit: frames on both backends and every scan form, AOVs,
+ * pt_ctx_intersect*, pt_ctx_intersect_bounds, pt_ctx_orbit_point, pt_ctx_scatter, pt_stats.ray_bounces, checkpoints.  The tables
+ * may differ in their paddings and, for a mesh with a BVH, in the tree's topology (a refit keeps the tree a build would choose
+ * anew); the results may not.
+ * PT_ERR_INVALID, in this order, nothing changed, before any device is touched: ctx NULL; obj NULL; no scene; index >= n_objs;
+ * kind, tri_offset or tri_count differ from the object's (topology edits go through pt_ctx_set_scene);
+ * reflect_type > PT_REFRACT; a position, radius, bs_center or bs_radius that is not finite.  rebuilt may be NULL.  One object per
+ * call.  Like pt_ctx_set_scene, not to be called from a progress callback. */
+int pt_ctx_set_object(pt_ctx *ctx, uint32_t index, const pt_object *obj, int *rebuilt);
+
+/* Diagnostics: pt_siphash(1, 3, 0, 0, ...) over each device table of the scene, downloaded - what the tests compare a refit's
+ * tables by.  On a scene whose arithmetic is exact (coordinates and moves that are multiples of 1/8, far below 2^20) an edited
+ * context holds, under the same box B, the tables a fresh pt_ctx_set_scene builds, to the bit.  PT_ERR_INVALID without a scene. */
+enum {
+    PT_TABLE_OBJS = 0,
+    PT_TABLE_OBJ_PAIRS,
+    PT_TABLE_TRI_PAIRS,
+    PT_TABLE_MATS,
+    PT_TABLE_TRI_SHADE,
+    PT_TABLE_BVH_NODES,
+    PT_TABLE_BVH_NODES4,
+    PT_TABLE_SPH_PAIRS,
+    PT_TABLE_FLAT_PAIRS,
+    PT_TABLE_CAND_PAIRS,
+    PT_TABLE_RANK_ID,
+    PT_TABLE_SURF,
+    PT_TABLE_TRI_RANK,
+    PT_TABLE_BVH_MESHES,
+    PT_TABLE_COUNT
+};
+int pt_ctx_table_hashes(pt_ctx *ctx, uint64_t out[PT_TABLE_COUNT]);
+
 /* Number of pixels a call with this config renders (the band, or this rank's chunks of it); 0 on a bad config. */
 uint32_t pt_config_pixels(const pt_config *cfg);
 

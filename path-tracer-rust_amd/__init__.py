@@ -125,6 +125,9 @@ class pt_adaptive_info(C.Structure):
                 ("spp_max", C.c_uint32), ("samples", C.c_uint64), ("mean_error", C.c_double)]
 
 
+# the device tables of a scene, by their PT_TABLE_* index (pt_ctx_table_hashes)
+TABLE_NAMES = ("objs", "obj_pairs", "tri_pairs", "mats", "tri_shade", "bvh_nodes", "bvh_nodes4", "sph_pairs", "flat_pairs", "cand_pairs",
+               "rank_id", "surf", "tri_rank", "bvh_meshes")
 PT_DENOISE_NO_DEMODULATE = 1
 PT_PRESENT_RGBA8, PT_PRESENT_RGB8 = 0, 1
 PT_PRESENT_FRAMEBUFFER_ORDER = 1
@@ -159,6 +162,8 @@ def lib():
     L.pt_ctx_set_camera.argtypes = [C.c_void_p, C.POINTER(pt_camera), C.POINTER(C.c_int)]
     L.pt_ctx_camera_reach.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.pt_ctx_reserve_camera_reach.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int)]
+    L.pt_ctx_set_object.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(pt_object), C.POINTER(C.c_int)]
+    L.pt_ctx_table_hashes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     L.pt_scene_reach.argtypes = [C.POINTER(pt_camera), C.POINTER(pt_object), C.c_uint32, C.POINTER(pt_triangle), C.c_uint32,
                                  C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.pt_ctx_render.argtypes = [C.c_void_p, C.POINTER(pt_config), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -301,6 +306,20 @@ class Context:
         rebuilt = C.c_int(0)
         _check(lib().pt_ctx_reserve_camera_reach(self._h, f3(*lo), f3(*hi), C.byref(rebuilt)))
         return bool(rebuilt.value)
+
+    def set_object(self, index, obj):
+        """Replace object `index` of the scene set_scene gave (pt_ctx_set_object): a pt_object with the kind and triangle range of
+        the one it replaces.  A move inside camera_reach() rewrites that object's records only - a mesh with a BVH is refit on
+        the device.  Returns whether the scene had to be rebuilt (the object left camera_reach()); False otherwise."""
+        rebuilt = C.c_int(0)
+        _check(lib().pt_ctx_set_object(self._h, index, C.byref(obj), C.byref(rebuilt)))
+        return bool(rebuilt.value)
+
+    def table_hashes(self):
+        """Diagnostics (pt_ctx_table_hashes): {table name: hash of the device table, downloaded}, in TABLE_NAMES' order."""
+        out = (C.c_uint64 * len(TABLE_NAMES))()
+        _check(lib().pt_ctx_table_hashes(self._h, out))
+        return dict(zip(TABLE_NAMES, out))
 
     def pass_kernel(self, separate_kernels=False):
         """Name of the kernel a wavefront pass of this scene launches (see pt_ctx_pass_kernel)."""

@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <string>
 #include <thread>
 #include <vector>
@@ -20,6 +21,7 @@
 #include "pt_noise.h"
 #include "pt_present.h"
 #include "pt_probe.h"
+#include "pt_refit.h"
 #include "pt_reproject.h"
 #include "pt_upsample.h"
 #include "pt_tile.h"
@@ -305,6 +307,24 @@ struct pt_ctx {
     // rebuilds the tables from when the lens centre leaves the box, and what the lazy fingerprint hashes
     std::vector<pt_triangle> h_tris;
     host::Reach reach{};
+    // pt_ctx_set_object.  fs: the tables as flatten_scene made them for `reach`, kept on the host without the three that hold
+    // nothing an edit reads (rank_id, surf, tri_rank) - an in-reach edit rewrites one object's records in it and uploads those.
+    // Of a mesh with a BVH it keeps the TOPOLOGY (ids, child references, wide_src): the floats of its pair records, shading
+    // records and boxes go stale with the first refit, which rewrites the device's.  h_local: every mesh's object-local vertex
+    // box.  refit: the device plans of the meshes moved since the last full build (upload_flat drops them).  table_count: the
+    // records each device table holds (pt_ctx_table_hashes).
+    host::FlatScene fs;
+    std::vector<host::Reach> h_local;
+    struct DevRefit {
+        DevBuf<pt_triangle> local;
+        DevBuf<RefitLeaf> leaves;
+        DevBuf<RefitNode> nodes;
+        DevBuf<RefitWide> wide;
+        std::vector<uint32_t> level_begin;
+        uint32_t n_leaves = 0, n_wide = 0;
+    };
+    std::map<uint32_t, DevRefit> refit;
+    size_t table_count[PT_TABLE_COUNT] = {};
     DevBuf<TriPairRec> d_boxes;
     bool boxes_dirty = true;
     // scratch of the single-ray query entry points (kept across calls: a picking caller sends one ray per click)
@@ -1503,6 +1523,21 @@ void pt_ctx_destroy(pt_ctx *c) {
     (void)hipStreamDestroy(st);
 }
 
+// glass deferral only where there is glass to defer
+static void set_glass_defer(pt_ctx *c, const pt_object *objs, uint32_t n_objs) {
+    bool has_glass = false;
+    for (uint32_t i = 0; i < n_objs; ++i) has_glass = has_glass || objs[i].reflect_type == PT_REFRACT;
+    c->scene.glass_defer_ok = (c->tune.glass_defer && has_glass) ? 1u : 0u;
+}
+
+// the host keeps the tables it uploaded, for pt_ctx_set_object (pt_ctx.fs says what of them)
+static void keep_flat(pt_ctx *c, host::FlatScene &fs) {
+    std::vector<uint32_t>().swap(fs.rank_id);
+    std::vector<SurfRec>().swap(fs.surf);
+    std::vector<uint32_t>().swap(fs.tri_rank);
+    c->fs = std::move(fs);
+}
+
 // The device form of a flattened scene: the tables uploaded and c->scene pointed at them (pt_ctx_set_scene; the rebuilds of
 // pt_ctx_set_camera and pt_ctx_reserve_camera_reach).  Nothing of the context's host state changes here.
 static int upload_flat(pt_ctx *c, const host::FlatScene &fs, const pt_object *objs, uint32_t n_objs, uint32_t n_tris) {
@@ -1516,6 +1551,13 @@ static int upload_flat(pt_ctx *c, const host::FlatScene &fs, const pt_object *ob
         (rc = c->d_tri_rank.ensure(fs.tri_rank.size())) || (rc = c->d_bvh_meshes.ensure(fs.bvh_meshes.size())))
         return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
+    c->refit.clear();  // (the plans name records of the tables before)
+    {
+        const size_t counts[PT_TABLE_COUNT] = {fs.objs.size(),      fs.obj_pairs.size(), fs.tri_pairs.size(),  fs.mats.size(),    fs.tri_shade.size(),
+                                               fs.bvh_nodes.size(), fs.bvh_nodes4.size(), fs.sph_pairs.size(), fs.flat_pairs.size(), fs.cand_pairs.size(),
+                                               fs.rank_id.size(),   fs.surf.size(),      fs.tri_rank.size(),   fs.bvh_meshes.size()};
+        memcpy(c->table_count, counts, sizeof counts);
+    }
     if (!fs.objs.empty())
         HIP_TRY(hipMemcpy(c->d_objs.p, fs.objs.data(), fs.objs.size() * sizeof(ObjRec), hipMemcpyHostToDevice));
     if (!fs.obj_pairs.empty())
@@ -1561,11 +1603,7 @@ static int upload_flat(pt_ctx *c, const host::FlatScene &fs, const pt_object *ob
     c->scene.n_other_pairs = fs.n_other_pairs;
     c->scene.n_flat_exact = fs.n_flat_exact;
     c->scene.nodes_in_lds_ok = c->tune.nodes_lds ? 1u : 0u;
-    {  // glass deferral only where there is glass to defer
-        bool has_glass = false;
-        for (uint32_t i = 0; i < n_objs; ++i) has_glass = has_glass || objs[i].reflect_type == PT_REFRACT;
-        c->scene.glass_defer_ok = (c->tune.glass_defer && has_glass) ? 1u : 0u;
-    }
+    set_glass_defer(c, objs, n_objs);
     c->cand_ok = fs.cand_ok;
     c->scene.cand_staged = 0u;
     c->scene.surf_staged = 0u;
@@ -1629,14 +1667,18 @@ int pt_ctx_set_scene(pt_ctx *c, const pt_camera *cam, const pt_object *objs, uin
     c->fp_stale = false;
     int rc = upload_flat(c, fs, objs, n_objs, n_tris);
     if (rc) return rc;
+    keep_flat(c, fs);
     c->cam = *cam;
     c->reach = reach;
     c->h_objs.assign(objs, objs + n_objs);
     c->h_tris.assign(tris, tris + n_tris);
     c->h_boxes.assign((size_t)12 * n_objs, pt_triangle{});
+    c->h_local.assign(n_objs, host::Reach{});
     for (uint32_t i = 0; i < n_objs; ++i)
-        if (objs[i].kind == PT_MESH && objs[i].tri_count != 0u)
+        if (objs[i].kind == PT_MESH && objs[i].tri_count != 0u) {
             host::mesh_bounding_box(tris + objs[i].tri_offset, objs[i].tri_count, &c->h_boxes[(size_t)12 * i]);
+            host::local_vertex_box(tris + objs[i].tri_offset, objs[i].tri_count, c->h_local[i]);
+        }
     c->boxes_dirty = true;
     c->has_scene = true;
     c->pass_rate = c->round_rate = c->ad_rate = c->mk_rate = 0.0;  // (another scene: the passes' length is measured again)
@@ -1659,6 +1701,7 @@ static int rebuild_for_reach(pt_ctx *c, const pt_camera &cam, const host::Reach 
     HIP_TRY(hipSetDevice(c->device));
     const int rc = upload_flat(c, fs, c->h_objs.data(), n_objs, n_tris);
     if (rc) return rc;
+    keep_flat(c, fs);
     c->reach = used;
     return PT_OK;
 }
@@ -1684,6 +1727,184 @@ int pt_ctx_set_camera(pt_ctx *c, const pt_camera *cam, int *rebuilt) {
     c->held.drop();
     c->adaptive.drop();
     c->fp_stale = true;
+    return PT_OK;
+}
+
+// ---- pt_ctx_set_object ---------------------------------------------------------------------------------------------------
+// the refit plan of mesh `index` on the device: built from the tree in c->fs and uploaded, with the mesh's object-local
+// triangles, by the first MOVE edit of the mesh; kept until the next full build
+static int refit_plan_for(pt_ctx *c, uint32_t index, pt_ctx::DevRefit **out) {
+    auto it = c->refit.find(index);
+    if (it != c->refit.end()) {
+        *out = &it->second;
+        return PT_OK;
+    }
+    host::RefitPlan plan;
+    if (!host::build_refit_plan(c->fs, index, plan)) {
+        set_error("internal: refit plan asked for an object without a BVH");
+        return PT_ERR_INVALID;
+    }
+    pt_ctx::DevRefit &d = c->refit[index];
+    const pt_object &o = c->h_objs[index];
+    int rc;
+    if ((rc = d.local.ensure(o.tri_count)) || (rc = d.leaves.ensure(plan.leaves.size())) || (rc = d.nodes.ensure(plan.nodes.size())) ||
+        (rc = d.wide.ensure(plan.wide.size()))) {
+        c->refit.erase(index);
+        return rc;
+    }
+    hipError_t e = hipMemcpy(d.local.p, c->h_tris.data() + o.tri_offset, (size_t)o.tri_count * sizeof(pt_triangle), hipMemcpyHostToDevice);
+    if (e == hipSuccess && !plan.leaves.empty())
+        e = hipMemcpy(d.leaves.p, plan.leaves.data(), plan.leaves.size() * sizeof(RefitLeaf), hipMemcpyHostToDevice);
+    if (e == hipSuccess && !plan.nodes.empty())
+        e = hipMemcpy(d.nodes.p, plan.nodes.data(), plan.nodes.size() * sizeof(RefitNode), hipMemcpyHostToDevice);
+    if (e == hipSuccess && !plan.wide.empty())
+        e = hipMemcpy(d.wide.p, plan.wide.data(), plan.wide.size() * sizeof(RefitWide), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        c->refit.erase(index);
+        set_error(std::string("hipMemcpy of a refit plan: ") + hipGetErrorString(e));
+        return PT_ERR_HIP;
+    }
+    d.level_begin = plan.level_begin;
+    d.n_leaves = (uint32_t)plan.leaves.size();
+    d.n_wide = (uint32_t)plan.wide.size();
+    *out = &d;
+    return PT_OK;
+}
+
+// an in-reach edit: the records edit_object rewrote in c->fs go to their offsets in the device tables; a mesh with a BVH is
+// refit by the kernels.  c->h_objs[index] is the edited object already.
+static int upload_object_edit(pt_ctx *c, uint32_t index, bool moved, bool material, const host::ObjectEdit &e) {
+    const host::FlatScene &fs = c->fs;
+    const pt_object &o = c->h_objs[index];
+    const uint32_t n_objs = (uint32_t)c->h_objs.size();
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpy(c->d_objs.p + index, &fs.objs[index], sizeof(ObjRec), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->d_mats.p + index, &fs.mats[index], sizeof(MatRec), hipMemcpyHostToDevice));
+    if (moved) {
+        HIP_TRY(hipMemcpy(c->d_opairs.p + e.obj_pair, &fs.obj_pairs[e.obj_pair], sizeof(ObjPairRec), hipMemcpyHostToDevice));
+        if (e.on_device) {
+            HIP_TRY(hipMemcpy(c->d_bvh_meshes.p + e.bvh_mesh, &fs.bvh_meshes[e.bvh_mesh], sizeof(BvhMeshRec), hipMemcpyHostToDevice));
+        } else {
+            // the candidate scan's tables whole (a few records per sphere and listed mesh): a translation can, through rounding,
+            // change which records are flat, their order and their count
+            int rc;
+            if ((rc = c->d_sph.ensure(fs.sph_pairs.size())) || (rc = c->d_flat.ensure(fs.flat_pairs.size())) ||
+                (rc = c->d_cand.ensure(fs.cand_pairs.size())))
+                return rc;
+            if (!fs.sph_pairs.empty())
+                HIP_TRY(hipMemcpy(c->d_sph.p, fs.sph_pairs.data(), fs.sph_pairs.size() * sizeof(SphPairRec), hipMemcpyHostToDevice));
+            if (!fs.flat_pairs.empty())
+                HIP_TRY(hipMemcpy(c->d_flat.p, fs.flat_pairs.data(), fs.flat_pairs.size() * sizeof(FlatPairRec), hipMemcpyHostToDevice));
+            if (!fs.cand_pairs.empty())
+                HIP_TRY(hipMemcpy(c->d_cand.p, fs.cand_pairs.data(), fs.cand_pairs.size() * sizeof(CandPairRec), hipMemcpyHostToDevice));
+            c->scene.sph_pairs = c->d_sph.p;
+            c->scene.flat_pairs = c->d_flat.p;
+            c->scene.cand_pairs = c->d_cand.p;
+            c->scene.n_sph_pairs = (uint32_t)fs.sph_pairs.size();
+            c->scene.n_flat_pairs = (uint32_t)fs.flat_pairs.size();
+            c->scene.n_cand_pairs = (uint32_t)fs.cand_pairs.size();
+            c->scene.n_other_pairs = fs.n_other_pairs;
+            c->scene.n_flat_exact = fs.n_flat_exact;
+            c->cand_ok = fs.cand_ok;
+            c->scene.cand_scan = cand_scan_for(c, 0u);
+            c->table_count[PT_TABLE_SPH_PAIRS] = fs.sph_pairs.size();
+            c->table_count[PT_TABLE_FLAT_PAIRS] = fs.flat_pairs.size();
+            c->table_count[PT_TABLE_CAND_PAIRS] = fs.cand_pairs.size();
+            if (o.kind == PT_MESH && o.tri_count != 0u) {
+                const ObjRec &r = fs.objs[index];
+                HIP_TRY(hipMemcpy(c->d_tris.p + r.pair_begin, &fs.tri_pairs[r.pair_begin], (size_t)r.pair_count * sizeof(TriPairRec),
+                                  hipMemcpyHostToDevice));
+                HIP_TRY(hipMemcpy(c->d_tshade.p + o.tri_offset, &fs.tri_shade[o.tri_offset], (size_t)o.tri_count * sizeof(TriShade),
+                                  hipMemcpyHostToDevice));
+            }
+        }
+    }
+    if (!e.surf.empty())
+        HIP_TRY(hipMemcpy(c->d_surf.p + e.rank, e.surf.data(), e.surf.size() * sizeof(SurfRec), hipMemcpyHostToDevice));
+    if (!e.tail.empty())
+        HIP_TRY(hipMemcpy(c->d_surf.p + e.tail_at, e.tail.data(), e.tail.size() * sizeof(SurfRec), hipMemcpyHostToDevice));
+    if (e.on_device) {
+        if (moved) {
+            pt_ctx::DevRefit *d = nullptr;
+            const int rc = refit_plan_for(c, index, &d);
+            if (rc) return rc;
+            RefitTables T{};
+            T.tri_pairs = c->d_tris.p, T.tri_shade = c->d_tshade.p, T.surf = c->d_surf.p;
+            T.nodes = c->d_nodes.p, T.nodes4 = c->d_nodes4.p, T.tri_rank = c->d_tri_rank.p;
+            T.local = d->local.p, T.tri_offset = o.tri_offset;
+            T.px = o.position[0], T.py = o.position[1], T.pz = o.position[2];
+            T.scene_R = e.scene_R;
+            launch_refit_leaves(c->stream, T, d->leaves.p, d->n_leaves);
+            for (size_t h = 0; h + 1 < d->level_begin.size(); ++h)
+                launch_refit_nodes(c->stream, c->d_nodes.p, d->nodes.p + d->level_begin[h], d->level_begin[h + 1] - d->level_begin[h]);
+            launch_refit_wide(c->stream, c->d_nodes4.p, c->d_nodes.p, d->wide.p, d->n_wide);
+        }
+        if (material) launch_refit_materials(c->stream, c->d_surf.p + e.rank, o.tri_count, fs.mats[index]);
+        HIP_TRY(hipGetLastError());
+    }
+    set_glass_defer(c, c->h_objs.data(), n_objs);
+    // a frame may render on a stream of the caller's: the tables are final when the call returns
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return PT_OK;
+}
+
+int pt_ctx_set_object(pt_ctx *c, uint32_t index, const pt_object *obj, int *rebuilt) {
+    {
+        const int rc = host::check_object_edit(c != nullptr, obj, c && c->has_scene, c ? c->h_objs.data() : nullptr,
+                                               c ? (uint32_t)c->h_objs.size() : 0u, index);
+        if (rc) return rc;
+    }
+    if (rebuilt) *rebuilt = 0;
+    const pt_object before = c->h_objs[index];
+    if (memcmp(obj, &before, sizeof(pt_object)) == 0) return PT_OK;  // nineteen words, no padding
+    const bool moved = !host::same_geometry(*obj, before);
+    const bool material = memcmp(obj->color, before.color, sizeof before.color) != 0 ||
+                          memcmp(obj->emission, before.emission, sizeof before.emission) != 0 || obj->reflect_type != before.reflect_type;
+    const uint32_t n_objs = (uint32_t)c->h_objs.size();
+    HIP_TRY(hipSetDevice(c->device));
+    host::Reach box;
+    host::object_bounds(*obj, c->h_local[index], box);
+    const bool has_bounds = obj->kind == PT_SPHERE || obj->tri_count != 0u;
+    if (moved && has_bounds && !c->reach.holds(box)) {
+        host::Reach B = c->reach;
+        host::grow_reach_box(B, box);
+        c->h_objs[index] = *obj;
+        const int rc = rebuild_for_reach(c, c->cam, B);
+        if (rc) {
+            c->h_objs[index] = before;
+            return rc;
+        }
+        if (rebuilt) *rebuilt = 1;
+    } else {
+        c->h_objs[index] = *obj;
+        host::ObjectEdit e;
+        host::edit_object(c->fs, c->reach, c->h_objs.data(), n_objs, c->h_tris.data(), index, moved, e);
+        const int rc = upload_object_edit(c, index, moved, material, e);
+        if (rc) return rc;  // (a HIP failure: the tables are in no known state, as after a failed pt_ctx_set_scene)
+    }
+    c->held.drop();
+    c->adaptive.drop();
+    c->fp_stale = true;
+    c->boxes_dirty = true;  // (the boxes of pt_ctx_set_mesh_bounds take the object's position)
+    return PT_OK;
+}
+
+int pt_ctx_table_hashes(pt_ctx *c, uint64_t out[PT_TABLE_COUNT]) {
+    if (!c || !out) return refuse("NULL argument");
+    if (!c->has_scene) return refuse("no scene set");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const void *src[PT_TABLE_COUNT] = {c->d_objs.p,  c->d_opairs.p, c->d_tris.p, c->d_mats.p,    c->d_tshade.p, c->d_nodes.p,    c->d_nodes4.p,
+                                       c->d_sph.p,   c->d_flat.p,   c->d_cand.p, c->d_rank_id.p, c->d_surf.p,   c->d_tri_rank.p, c->d_bvh_meshes.p};
+    const size_t width[PT_TABLE_COUNT] = {sizeof(ObjRec),     sizeof(ObjPairRec),  sizeof(TriPairRec),  sizeof(MatRec),   sizeof(TriShade),
+                                          sizeof(BvhNode),    sizeof(BvhNode4),    sizeof(SphPairRec),  sizeof(FlatPairRec), sizeof(CandPairRec),
+                                          sizeof(uint32_t),   sizeof(SurfRec),     sizeof(uint32_t),    sizeof(BvhMeshRec)};
+    std::vector<uint8_t> h;
+    for (int t = 0; t < PT_TABLE_COUNT; ++t) {
+        h.resize(c->table_count[t] * width[t]);
+        if (!h.empty()) HIP_TRY(hipMemcpy(h.data(), src[t], h.size(), hipMemcpyDeviceToHost));
+        out[t] = pt_siphash(1, 3, 0, 0, h.data(), h.size());
+    }
     return PT_OK;
 }
 

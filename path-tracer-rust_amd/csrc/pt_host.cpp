@@ -6,6 +6,7 @@
 #include "pt_masked.h"
 #include "pt_present.h"
 #include "pt_probe.h"
+#include "pt_refit.h"
 #include "pt_reproject.h"
 #include "pt_upsample.h"
 
@@ -222,15 +223,18 @@ struct BvhBuilder {
 // The binary tree below `ref` four children wide (BvhNode4): a node's children are its two children, and while there is
 // room the inner child with the largest box is replaced by ITS two children - boxes and leaf references are the binary
 // tree's.  Returns the reference in the wide tree (a leaf reference stays what it is).
-int32_t widen(const std::vector<BvhNode> &bin, int32_t ref, std::vector<BvhNode4> &wide) {
+// src (FlatScene.wide_src) gets, per child slot, the binary (node, half) the box was taken from: 2 * node + half, kRefitNone for none.
+int32_t widen(const std::vector<BvhNode> &bin, int32_t ref, std::vector<BvhNode4> &wide, std::vector<uint32_t> &src) {
     if (ref < 0) return ref;
     struct Kid {
         int32_t ref;
+        uint32_t src;
         float lo[3], hi[3];
     };
     auto kid_of = [&](const BvhNode &n, int h) {
         Kid k;
         k.ref = n.c[h];
+        k.src = 2u * (uint32_t)(&n - bin.data()) + (uint32_t)h;
         k.lo[0] = n.lox[h], k.lo[1] = n.loy[h], k.lo[2] = n.loz[h];
         k.hi[0] = n.hix[h], k.hi[1] = n.hiy[h], k.hi[2] = n.hiz[h];
         return k;
@@ -251,9 +255,11 @@ int32_t widen(const std::vector<BvhNode> &bin, int32_t ref, std::vector<BvhNode4
     }
     const size_t at = wide.size();
     wide.push_back(BvhNode4{});
+    src.resize(4u * wide.size(), kRefitNone);
+    for (size_t j = 0; j < kids.size(); ++j) src[4u * at + j] = kids[j].src;
     const float nan = std::numeric_limits<float>::quiet_NaN();
     int32_t refs[4];
-    for (size_t j = 0; j < 4u; ++j) refs[j] = j < kids.size() ? widen(bin, kids[j].ref, wide) : 0;
+    for (size_t j = 0; j < 4u; ++j) refs[j] = j < kids.size() ? widen(bin, kids[j].ref, wide, src) : 0;
     BvhNode4 &w = wide[at];
     for (size_t j = 0; j < 4u; ++j) {
         const bool has = j < kids.size();
@@ -310,185 +316,102 @@ bool grow_reach(Reach &B, const float lens[3]) {
     return grew;
 }
 
-bool flatten_scene(const pt_camera &cam, const pt_object *objs, uint32_t n_objs, const pt_triangle *tris,
-                   uint32_t n_tris, FlatScene &out, std::string &err, const Reach *origin_box, Reach *used) {
-    if (n_objs >= (1u << 30) || n_tris >= (1u << 30)) {
-        err = "scene too large";
-        return false;
+// ---- flatten_scene's per-object steps, which edit_object runs again for the one object that changed -------------------------
+// everything of an object's record but its triangle ranges and its tree: the (bounding) sphere and rr_in, from the object and
+// the box [slo, shi] that bounds every ray origin.  A sphere's record is complete afterwards.
+static void object_head(const pt_object &o, vec3 slo, vec3 shi, ObjRec &r) {
+    const vec3 position = ld(o.position);
+    r.kind = o.kind;
+    if (o.kind == PT_SPHERE) {
+        r.cx = position.x;
+        r.cy = position.y;
+        r.cz = position.z;
+        r.rr = o.radius * o.radius;  // radius.powi(2), mod.rs:416
+        r.rr_in = -1.0f;
+        r.tri_begin = 0;
+        r.tri_count = 0;
+        r.pair_begin = 0;
+        r.pair_count = 0;
+        r.bvh_root = kNoBvh;
+        return;
     }
-    out.objs.assign(n_objs, ObjRec{});
-    out.mats.assign(n_objs, MatRec{});
-    out.tri_pairs.clear();
-    out.bvh_nodes.clear();
-    out.tri_shade.assign(n_tris, TriShade{});
-    // R: bound on |ray origin - any vertex|: ray origins are the lens centre or points on objects - or, with an origin box,
-    // the lens centre of any camera inside it
+    const vec3 gate = ld(o.bs_center) + position;  // mod.rs:268
+    r.cx = gate.x;
+    r.cy = gate.y;
+    r.cz = gate.z;
+    r.rr = o.bs_radius * o.bs_radius;
+    // rr_in: see intersect_scene_dev.  A point of the ray, ahead of the origin, within (1 - eta) r of the
+    // centre with eta = 1e-3: the chord through it is >= 0.09 r long, so the exact discriminant is
+    // >= 2e-3 r^2 and the far root lies >= 1e-3 r ahead of the origin.  With every origin within 4 r of the
+    // centre (origins lie in the scene's bounding box) the f32 discriminant is off by <= 4 e (16+16+1) r^2
+    // ~ 8e-6 r^2, its root by <= 9e-5 r, so the computed far root is >= 9e-4 r >= 1e-4 for r >= 0.2: the
+    // gate passes.  The factor 0.998 and the absolute term cover the device's own o + d*t and distance.
+    const float rad = f_abs(o.bs_radius);
+    float far2 = 0.0f;  // squared distance from the centre to the farthest corner of the scene's box
+    for (int k = 0; k < 8; ++k) {
+        const vec3 corner = mk((k & 1) ? shi.x : slo.x, (k & 2) ? shi.y : slo.y, (k & 4) ? shi.z : slo.z);
+        far2 = f_max(far2, dot(corner - gate, corner - gate));
+    }
+    const bool offer = std::isfinite(rad) && rad >= 0.2f && far2 <= 16.0f * rad * rad;
+    r.rr_in = offer ? r.rr * 0.998f - 1e-4f * (1.0f + rad) : -1.0f;
+    r.bvh_root = kNoBvh;
+}
+
+static void object_material(const pt_object &o, MatRec &m) {
+    m.cr = o.color[0];
+    m.cg = o.color[1];
+    m.cb = o.color[2];
+    m.er = o.emission[0];
+    m.eg = o.emission[1];
+    m.eb = o.emission[2];
+    material_reflectance(o.color, m.max_refl, m.inv_max_refl);
+    m.px = o.position[0];
+    m.py = o.position[1];
+    m.pz = o.position[2];
+    m.reflect = o.reflect_type;
+}
+
+// a mesh's triangles in world space (pt_refit.h: world_triangle), in list order; their shading records
+static void mesh_triangles(uint32_t i, const pt_object &o, const pt_triangle *tris, float scene_R, std::vector<TriShade> &tri_shade,
+                           std::vector<BuildTri> &bt) {
+    const vec3 position = ld(o.position);
+    bt.clear();
+    bt.reserve(o.tri_count);
+    for (uint32_t k = o.tri_offset; k < o.tri_offset + o.tri_count; ++k) {
+        const WorldTri w = world_triangle(tris[k], position, scene_R);
+        TriShade &s = tri_shade[k];
+        s.nx = w.nrm.x;
+        s.ny = w.nrm.y;
+        s.nz = w.nrm.z;
+        s.owner = i;
+        BuildTri q;
+        q.a = w.a, q.e1 = w.e1, q.e2 = w.e2, q.id = k;
+        q.lo = w.lo, q.hi = w.hi, q.mid = w.mid;
+        bt.push_back(q);
+    }
+}
+
+// a mesh without a BVH: its triangles in list order, two per record, into dst[0, (n + 1) / 2)
+static void list_pairs(const std::vector<BuildTri> &bt, TriPairRec *dst) {
+    for (size_t k = 0; k < bt.size(); k += 2) {
+        TriPairRec rec{};
+        rec.id[0] = rec.id[1] = kNoTri;
+        for (size_t hf = 0; hf < 2 && k + hf < bt.size(); ++hf) {
+            const BuildTri &q = bt[k + hf];
+            rec.ax[hf] = q.a.x, rec.ay[hf] = q.a.y, rec.az[hf] = q.a.z;
+            rec.e1x[hf] = q.e1.x, rec.e1y[hf] = q.e1.y, rec.e1z[hf] = q.e1.z;
+            rec.e2x[hf] = q.e2.x, rec.e2y[hf] = q.e2.y, rec.e2z[hf] = q.e2.z;
+            rec.id[hf] = q.id;
+        }
+        dst[k / 2] = rec;
+    }
+}
+
+// The tables that hold a few records per object (never one per triangle of a mesh with a BVH): obj_pairs, sph_pairs, and the
+// candidate scan's flat_pairs and cand_pairs - from out.objs and the pair records of the meshes WITHOUT a BVH.  flatten_scene
+// runs it once; edit_object runs it again after it rewrote one object's records.
+static void derive_small(const pt_object *objs, uint32_t n_objs, float scene_R, FlatScene &out) {
     const float finf = std::numeric_limits<float>::infinity();
-    Reach reach;
-    scene_reach(cam, objs, n_objs, tris, n_tris, reach);
-    vec3 slo = ld(reach.lo), shi = ld(reach.hi);
-    if (origin_box) BvhBuilder::grow(slo, shi, ld(origin_box->lo), ld(origin_box->hi));
-    if (used) {
-        st(used->lo, slo);
-        st(used->hi, shi);
-    }
-    const float scene_R = n_objs ? length(shi - slo) : 0.0f;
-    std::vector<uint8_t> claimed(n_tris, 0);
-    bool have_bvh = false;
-    out.bvh_pair_base = 0;
-    out.bvh_stack = 0;
-    out.bvh_pair_span = 0;
-    for (uint32_t i = 0; i < n_objs; ++i) {
-        const pt_object &o = objs[i];
-        if (o.kind != PT_SPHERE && o.kind != PT_MESH) {
-            err = "object " + std::to_string(i) + ": unknown kind";
-            return false;
-        }
-        if (o.reflect_type > PT_REFRACT) {
-            err = "object " + std::to_string(i) + ": unknown reflect_type";
-            return false;
-        }
-        const vec3 position = ld(o.position);
-        ObjRec &r = out.objs[i];
-        MatRec &m = out.mats[i];
-        r.kind = o.kind;
-        if (o.kind == PT_SPHERE) {
-            r.cx = position.x;
-            r.cy = position.y;
-            r.cz = position.z;
-            r.rr = o.radius * o.radius;  // radius.powi(2), mod.rs:416
-            r.rr_in = -1.0f;
-            r.tri_begin = 0;
-            r.tri_count = 0;
-            r.pair_begin = 0;
-            r.pair_count = 0;
-            r.bvh_root = kNoBvh;
-        } else {
-            if ((uint64_t)o.tri_offset + o.tri_count > n_tris) {
-                err = "object " + std::to_string(i) + ": triangle range outside the triangle array";
-                return false;
-            }
-            const vec3 gate = ld(o.bs_center) + position;  // mod.rs:268
-            r.cx = gate.x;
-            r.cy = gate.y;
-            r.cz = gate.z;
-            r.rr = o.bs_radius * o.bs_radius;
-            {
-                // rr_in: see intersect_scene_dev.  A point of the ray, ahead of the origin, within (1 - eta) r of the
-                // centre with eta = 1e-3: the chord through it is >= 0.09 r long, so the exact discriminant is
-                // >= 2e-3 r^2 and the far root lies >= 1e-3 r ahead of the origin.  With every origin within 4 r of the
-                // centre (origins lie in the scene's bounding box) the f32 discriminant is off by <= 4 e (16+16+1) r^2
-                // ~ 8e-6 r^2, its root by <= 9e-5 r, so the computed far root is >= 9e-4 r >= 1e-4 for r >= 0.2: the
-                // gate passes.  The factor 0.998 and the absolute term cover the device's own o + d*t and distance.
-                const float rad = f_abs(o.bs_radius);
-                float far2 = 0.0f;  // squared distance from the centre to the farthest corner of the scene's box
-                for (int k = 0; k < 8; ++k) {
-                    const vec3 corner = mk((k & 1) ? shi.x : slo.x, (k & 2) ? shi.y : slo.y, (k & 4) ? shi.z : slo.z);
-                    far2 = f_max(far2, dot(corner - gate, corner - gate));
-                }
-                const bool offer = std::isfinite(rad) && rad >= 0.2f && far2 <= 16.0f * rad * rad;
-                r.rr_in = offer ? r.rr * 0.998f - 1e-4f * (1.0f + rad) : -1.0f;
-            }
-            r.tri_begin = o.tri_offset;
-            r.tri_count = o.tri_count;
-            r.pair_begin = (uint32_t)out.tri_pairs.size();
-            r.bvh_root = kNoBvh;
-            std::vector<BuildTri> bt;
-            bt.reserve(o.tri_count);
-            for (uint32_t k = o.tri_offset; k < o.tri_offset + o.tri_count; ++k) {
-                if (claimed[k]) {
-                    err = "triangle " + std::to_string(k) + " belongs to two objects";
-                    return false;
-                }
-                claimed[k] = 1;
-                const vec3 a = ld(tris[k].a) + position;  // Triangle::transformed, mod.rs:546-552
-                const vec3 b = ld(tris[k].b) + position;
-                const vec3 c = ld(tris[k].c) + position;
-                const vec3 e1 = b - a, e2 = c - a;  // mod.rs:560-561
-                const vec3 nrm = normalize(cross(e1, e2));  // mod.rs:605
-                TriShade &s = out.tri_shade[k];
-                s.nx = nrm.x;
-                s.ny = nrm.y;
-                s.nz = nrm.z;
-                s.owner = i;
-                BuildTri q;
-                q.a = a, q.e1 = e1, q.e2 = e2, q.id = k;
-                q.lo = mk(std::fmin(a.x, std::fmin(b.x, c.x)), std::fmin(a.y, std::fmin(b.y, c.y)),
-                          std::fmin(a.z, std::fmin(b.z, c.z)));
-                q.hi = mk(std::fmax(a.x, std::fmax(b.x, c.x)), std::fmax(a.y, std::fmax(b.y, c.y)),
-                          std::fmax(a.z, std::fmax(b.z, c.z)));
-                q.mid = (q.lo + q.hi) * 0.5f;
-                {
-                    // Padding = bound on how far from the exact triangle a hit accepted by the f32 Moller-Trumbore
-                    // arithmetic can lie.  With |det| >= 1e-4 (mod.rs:571), |tvec| <= R (scene diagonal), this
-                    // triangle's edges <= L and unit roundoff e = 2^-24, forward error analysis of mod.rs:560-589
-                    // gives |du|,|dv| <= e L (7L + 8R) / 1e-4 (the hit point moves by that times L) and
-                    // |dt| <= e L^2 (7 t + 8R) / 1e-4 with t <= R; 16 e L^2 (R+L) / 1e-4 covers each of the three,
-                    // so three times that (the 16 already holds a factor 2 of slack), plus the slab test's own roundoff.
-                    const float L = std::fmax(length(e1), std::fmax(length(e2), length(c - b)));
-                    const float e = 5.9604645e-8f;
-                    const float pad = 3.0f * (16.0f * e * L * L * (scene_R + L) / 1e-4f) + 16.0f * e * (scene_R + L) + 1e-6f;
-                    q.lo = q.lo - mk(pad, pad, pad);
-                    q.hi = q.hi + mk(pad, pad, pad);
-                }
-                bt.push_back(q);
-            }
-            if (o.tri_count >= kBvhMinTris) {
-                const size_t pairs_mark = out.tri_pairs.size(), nodes_mark = out.bvh_nodes.size();
-                const std::vector<BuildTri> keep = bt;
-                for (int attempt = 0; attempt < 2; ++attempt) {
-                    BvhBuilder bb{out, bt};
-                    bb.use_sah = attempt == 0;
-                    vec3 blo, bhi;
-                    r.bvh_root = bb.build(0, bt.size(), blo, bhi, 0);
-                    if (bb.depth_max + 2 < kBvhStack) {
-                        out.bvh_stack = std::max(out.bvh_stack, (uint32_t)bb.depth_max + 2u);
-                        break;
-                    }
-                    if (attempt == 1) {
-                        err = "object " + std::to_string(i) + ": BVH deeper than the traversal stack";
-                        return false;
-                    }
-                    out.tri_pairs.resize(pairs_mark);  // SAH tree too deep for the stack: rebuild balanced
-                    out.bvh_nodes.resize(nodes_mark);
-                    bt = keep;
-                }
-                if (!have_bvh) out.bvh_pair_base = (uint32_t)pairs_mark;
-                have_bvh = true;
-                out.bvh_pair_span = (uint32_t)out.tri_pairs.size() - out.bvh_pair_base;
-                if (!bvh_refs_fit(out.bvh_nodes.size(), out.tri_pairs.size())) {
-                    err = "mesh too large for the BVH walkers: node indices and leaf codes are packed into 26 bits of a queue entry "
-                          "(2^26 nodes, 2^25 pair records with leaves of two records)";
-                    return false;
-                }
-            } else {
-                for (size_t k = 0; k < bt.size(); k += 2) {  // list order, two triangles per record
-                    TriPairRec rec{};
-                    rec.id[0] = rec.id[1] = kNoTri;
-                    for (size_t hf = 0; hf < 2 && k + hf < bt.size(); ++hf) {
-                        const BuildTri &q = bt[k + hf];
-                        rec.ax[hf] = q.a.x, rec.ay[hf] = q.a.y, rec.az[hf] = q.a.z;
-                        rec.e1x[hf] = q.e1.x, rec.e1y[hf] = q.e1.y, rec.e1z[hf] = q.e1.z;
-                        rec.e2x[hf] = q.e2.x, rec.e2y[hf] = q.e2.y, rec.e2z[hf] = q.e2.z;
-                        rec.id[hf] = q.id;
-                    }
-                    out.tri_pairs.push_back(rec);
-                }
-            }
-            r.pair_count = (uint32_t)out.tri_pairs.size() - r.pair_begin;
-        }
-        m.cr = o.color[0];
-        m.cg = o.color[1];
-        m.cb = o.color[2];
-        m.er = o.emission[0];
-        m.eg = o.emission[1];
-        m.eb = o.emission[2];
-        material_reflectance(o.color, m.max_refl, m.inv_max_refl);
-        m.px = position.x;
-        m.py = position.y;
-        m.pz = position.z;
-        m.reflect = o.reflect_type;
-    }
     // pairs in visiting order (mod.rs:637: highest index first)
     out.obj_pairs.assign((n_objs + 1u) / 2u, ObjPairRec{});
     for (uint32_t v = 0; v < 2u * (uint32_t)out.obj_pairs.size(); ++v) {
@@ -532,44 +455,16 @@ bool flatten_scene(const pt_camera &cam, const pt_object *objs, uint32_t n_objs,
             pr.admit[hf] = 0u;
         }
     }
-    // ---- tables of the candidate scan (intersect_cand) -----------------------------------------------------------
-    // ranks: the reference's visiting sequence - objects from the last to the first (mod.rs:637), a mesh's triangles in
-    // list order (mod.rs:558)
-    std::vector<uint32_t> tri_rank(n_tris ? n_tris : 1u, 0u);
-    out.rank_id.assign((size_t)n_objs + n_tris + 1u, 0u);
+    // ranks of the objects: the reference's visiting sequence - objects from the last to the first (mod.rs:637), a mesh's
+    // triangles in list order (mod.rs:558): triangle k of object i has rank obj_rank[i] + k
     std::vector<uint32_t> obj_rank(n_objs, 0u);
     {
         uint32_t next = 0;
         for (uint32_t v = 0; v < n_objs; ++v) {
             const uint32_t i = n_objs - 1u - v;
             obj_rank[i] = next;
-            if (objs[i].kind == PT_SPHERE) {
-                out.rank_id[next++] = i;
-            } else {
-                for (uint32_t k = 0; k < objs[i].tri_count; ++k) {
-                    tri_rank[objs[i].tri_offset + k] = next;
-                    out.rank_id[next++] = n_objs + objs[i].tri_offset + k;
-                }
-            }
+            next += objs[i].kind == PT_SPHERE ? 1u : objs[i].tri_count;
         }
-    }
-    // shading records by rank
-    out.surf.assign(out.rank_id.size(), SurfRec{});
-    for (size_t rk = 0; rk + 1 < out.rank_id.size(); ++rk) {
-        const uint32_t id = out.rank_id[rk];
-        SurfRec &sr = out.surf[rk];
-        uint32_t owner = id;
-        if (id >= n_objs) {
-            const TriShade &ts = out.tri_shade[id - n_objs];
-            sr.vx = ts.nx, sr.vy = ts.ny, sr.vz = ts.nz;
-            owner = ts.owner;
-            sr.kind = 0x100u;
-        }
-        const MatRec &mm = out.mats[owner];
-        if (id < n_objs) sr.vx = mm.px, sr.vy = mm.py, sr.vz = mm.pz;
-        sr.kind |= mm.reflect & 3u;
-        sr.cr = mm.cr, sr.cg = mm.cg, sr.cb = mm.cb, sr.max_refl = mm.max_refl;
-        sr.er = mm.er, sr.eg = mm.eg, sr.eb = mm.eb, sr.inv_max_refl = mm.inv_max_refl;
     }
     out.sph_pairs.clear();
     out.flat_pairs.clear();
@@ -583,7 +478,7 @@ bool flatten_scene(const pt_camera &cam, const pt_object *objs, uint32_t n_objs,
             c.ax[hf] = tp.ax[hf], c.ay[hf] = tp.ay[hf], c.az[hf] = tp.az[hf];
             c.e1x[hf] = tp.e1x[hf], c.e1y[hf] = tp.e1y[hf], c.e1z[hf] = tp.e1z[hf];
             c.e2x[hf] = tp.e2x[hf], c.e2y[hf] = tp.e2y[hf], c.e2z[hf] = tp.e2z[hf];
-            c.id[hf] = tp.id[hf] == kNoTri ? kNoTri : tri_rank[tp.id[hf]];
+            c.id[hf] = tp.id[hf] == kNoTri ? kNoTri : obj_rank[i] + (tp.id[hf] - objs[i].tri_offset);
         }
         c.gx = out.objs[i].cx, c.gy = out.objs[i].cy, c.gz = out.objs[i].cz;
         c.grr = out.objs[i].rr;
@@ -695,6 +590,136 @@ bool flatten_scene(const pt_camera &cam, const pt_object *objs, uint32_t n_objs,
         out.cand_pairs.insert(out.cand_pairs.end(), filtered.begin(), filtered.end());
         out.cand_ok = out.cand_pairs.size() <= kCandMaxPairs;
     }
+}
+
+bool flatten_scene(const pt_camera &cam, const pt_object *objs, uint32_t n_objs, const pt_triangle *tris,
+                   uint32_t n_tris, FlatScene &out, std::string &err, const Reach *origin_box, Reach *used) {
+    if (n_objs >= (1u << 30) || n_tris >= (1u << 30)) {
+        err = "scene too large";
+        return false;
+    }
+    out.objs.assign(n_objs, ObjRec{});
+    out.mats.assign(n_objs, MatRec{});
+    out.tri_pairs.clear();
+    out.bvh_nodes.clear();
+    out.bvh_nodes4.clear();
+    out.wide_src.clear();
+    out.tri_shade.assign(n_tris, TriShade{});
+    // R: bound on |ray origin - any vertex|: ray origins are the lens centre or points on objects - or, with an origin box,
+    // the lens centre of any camera inside it
+    Reach reach;
+    scene_reach(cam, objs, n_objs, tris, n_tris, reach);
+    vec3 slo = ld(reach.lo), shi = ld(reach.hi);
+    if (origin_box) BvhBuilder::grow(slo, shi, ld(origin_box->lo), ld(origin_box->hi));
+    if (used) {
+        st(used->lo, slo);
+        st(used->hi, shi);
+    }
+    const float scene_R = n_objs ? length(shi - slo) : 0.0f;
+    std::vector<uint8_t> claimed(n_tris, 0);
+    bool have_bvh = false;
+    out.bvh_pair_base = 0;
+    out.bvh_stack = 0;
+    out.bvh_pair_span = 0;
+    for (uint32_t i = 0; i < n_objs; ++i) {
+        const pt_object &o = objs[i];
+        if (o.kind != PT_SPHERE && o.kind != PT_MESH) {
+            err = "object " + std::to_string(i) + ": unknown kind";
+            return false;
+        }
+        if (o.reflect_type > PT_REFRACT) {
+            err = "object " + std::to_string(i) + ": unknown reflect_type";
+            return false;
+        }
+        ObjRec &r = out.objs[i];
+        object_head(o, slo, shi, r);
+        if (o.kind == PT_MESH) {
+            if ((uint64_t)o.tri_offset + o.tri_count > n_tris) {
+                err = "object " + std::to_string(i) + ": triangle range outside the triangle array";
+                return false;
+            }
+            r.tri_begin = o.tri_offset;
+            r.tri_count = o.tri_count;
+            r.pair_begin = (uint32_t)out.tri_pairs.size();
+            for (uint32_t k = o.tri_offset; k < o.tri_offset + o.tri_count; ++k) {
+                if (claimed[k]) {
+                    err = "triangle " + std::to_string(k) + " belongs to two objects";
+                    return false;
+                }
+                claimed[k] = 1;
+            }
+            std::vector<BuildTri> bt;
+            mesh_triangles(i, o, tris, scene_R, out.tri_shade, bt);
+            if (o.tri_count >= kBvhMinTris) {
+                const size_t pairs_mark = out.tri_pairs.size(), nodes_mark = out.bvh_nodes.size();
+                const std::vector<BuildTri> keep = bt;
+                for (int attempt = 0; attempt < 2; ++attempt) {
+                    BvhBuilder bb{out, bt};
+                    bb.use_sah = attempt == 0;
+                    vec3 blo, bhi;
+                    r.bvh_root = bb.build(0, bt.size(), blo, bhi, 0);
+                    if (bb.depth_max + 2 < kBvhStack) {
+                        out.bvh_stack = std::max(out.bvh_stack, (uint32_t)bb.depth_max + 2u);
+                        break;
+                    }
+                    if (attempt == 1) {
+                        err = "object " + std::to_string(i) + ": BVH deeper than the traversal stack";
+                        return false;
+                    }
+                    out.tri_pairs.resize(pairs_mark);  // SAH tree too deep for the stack: rebuild balanced
+                    out.bvh_nodes.resize(nodes_mark);
+                    bt = keep;
+                }
+                if (!have_bvh) out.bvh_pair_base = (uint32_t)pairs_mark;
+                have_bvh = true;
+                out.bvh_pair_span = (uint32_t)out.tri_pairs.size() - out.bvh_pair_base;
+                if (!bvh_refs_fit(out.bvh_nodes.size(), out.tri_pairs.size())) {
+                    err = "mesh too large for the BVH walkers: node indices and leaf codes are packed into 26 bits of a queue entry "
+                          "(2^26 nodes, 2^25 pair records with leaves of two records)";
+                    return false;
+                }
+            } else {
+                out.tri_pairs.resize(out.tri_pairs.size() + (bt.size() + 1u) / 2u);
+                list_pairs(bt, out.tri_pairs.data() + r.pair_begin);
+            }
+            r.pair_count = (uint32_t)out.tri_pairs.size() - r.pair_begin;
+        }
+        object_material(o, out.mats[i]);
+    }
+    derive_small(objs, n_objs, scene_R, out);
+    // ranks: the reference's visiting sequence - objects from the last to the first (mod.rs:637), a mesh's triangles in
+    // list order (mod.rs:558)
+    std::vector<uint32_t> tri_rank(n_tris ? n_tris : 1u, 0u);
+    out.rank_id.assign((size_t)n_objs + n_tris + 1u, 0u);
+    {
+        uint32_t next = 0;
+        for (uint32_t v = 0; v < n_objs; ++v) {
+            const uint32_t i = n_objs - 1u - v;
+            if (objs[i].kind == PT_SPHERE) {
+                out.rank_id[next++] = i;
+            } else {
+                for (uint32_t k = 0; k < objs[i].tri_count; ++k) {
+                    tri_rank[objs[i].tri_offset + k] = next;
+                    out.rank_id[next++] = n_objs + objs[i].tri_offset + k;
+                }
+            }
+        }
+    }
+    // shading records by rank
+    out.surf.assign(out.rank_id.size(), SurfRec{});
+    for (size_t rk = 0; rk + 1 < out.rank_id.size(); ++rk) {
+        const uint32_t id = out.rank_id[rk];
+        SurfRec &sr = out.surf[rk];
+        uint32_t owner = id;
+        if (id >= n_objs) {
+            const TriShade &ts = out.tri_shade[id - n_objs];
+            sr.vx = ts.nx, sr.vy = ts.ny, sr.vz = ts.nz;
+            owner = ts.owner;
+        }
+        const MatRec &mm = out.mats[owner];
+        if (id < n_objs) sr.vx = mm.px, sr.vy = mm.py, sr.vz = mm.pz;
+        surf_material(sr, mm, id >= n_objs);
+    }
     out.tri_rank = tri_rank;
     out.bvh_meshes.clear();
     for (uint32_t v = 0; v < n_objs; ++v) {
@@ -703,10 +728,190 @@ bool flatten_scene(const pt_camera &cam, const pt_object *objs, uint32_t n_objs,
         BvhMeshRec bm{};
         bm.cx = r.cx, bm.cy = r.cy, bm.cz = r.cz, bm.rr = r.rr;
         bm.root = r.bvh_root;
-        bm.root4 = widen(out.bvh_nodes, r.bvh_root, out.bvh_nodes4);
+        bm.root4 = widen(out.bvh_nodes, r.bvh_root, out.bvh_nodes4, out.wide_src);
         out.bvh_meshes.push_back(bm);
     }
     return true;
+}
+
+// ---------------------------------------------------------------------------------------------
+// pt_ctx_set_object: the host side of an edit in place
+int check_object_edit(bool has_ctx, const pt_object *obj, bool has_scene, const pt_object *objs, uint32_t n_objs, uint32_t index) {
+    if (!has_ctx) return refuse("ctx is NULL");
+    if (!obj) return refuse("obj is NULL");
+    if (!has_scene) return refuse("no scene set: pt_ctx_set_object edits an object of the scene pt_ctx_set_scene gave");
+    if (index >= n_objs) return refuse("index is not an object of the scene");
+    const pt_object &have = objs[index];
+    if (obj->kind != have.kind || obj->tri_offset != have.tri_offset || obj->tri_count != have.tri_count)
+        return refuse("kind, tri_offset or tri_count differ from the object's: topology edits go through pt_ctx_set_scene");
+    if (obj->reflect_type > PT_REFRACT) return refuse("unknown reflect_type");
+    const float geo[] = {obj->position[0], obj->position[1], obj->position[2], obj->radius,
+                         obj->bs_center[0], obj->bs_center[1], obj->bs_center[2], obj->bs_radius};
+    for (float v : geo)
+        if (!std::isfinite(v)) return refuse("a position, radius, bs_center or bs_radius that is not finite");
+    return PT_OK;
+}
+
+bool same_geometry(const pt_object &a, const pt_object &b) {
+    return memcmp(a.position, b.position, sizeof a.position) == 0 && memcmp(&a.radius, &b.radius, sizeof a.radius) == 0 &&
+           memcmp(a.bs_center, b.bs_center, sizeof a.bs_center) == 0 && memcmp(&a.bs_radius, &b.bs_radius, sizeof a.bs_radius) == 0;
+}
+
+void local_vertex_box(const pt_triangle *tris, uint32_t n, Reach &out) {
+    const float finf = std::numeric_limits<float>::infinity();
+    vec3 lo = mk(finf, finf, finf), hi = mk(-finf, -finf, -finf);
+    for (uint32_t k = 0; k < n; ++k) {
+        BvhBuilder::grow(lo, hi, ld(tris[k].a), ld(tris[k].a));
+        BvhBuilder::grow(lo, hi, ld(tris[k].b), ld(tris[k].b));
+        BvhBuilder::grow(lo, hi, ld(tris[k].c), ld(tris[k].c));
+    }
+    st(out.lo, lo);
+    st(out.hi, hi);
+}
+
+void object_bounds(const pt_object &o, const Reach &local, Reach &out) {
+    const vec3 pos = ld(o.position);
+    if (o.kind == PT_SPHERE) {
+        const float r = f_abs(o.radius);
+        st(out.lo, pos - mk(r, r, r));
+        st(out.hi, pos + mk(r, r, r));
+    } else {  // rounding is monotone: min over (v + pos) is (min over v) + pos
+        st(out.lo, ld(local.lo) + pos);
+        st(out.hi, ld(local.hi) + pos);
+    }
+}
+
+bool grow_reach_box(Reach &B, const Reach &box) {
+    bool grew = false;
+    for (int a = 0; a < 3; ++a) {
+        if (box.lo[a] < B.lo[a]) {
+            B.lo[a] = box.lo[a] - (B.lo[a] - box.lo[a]);
+            grew = true;
+        }
+        if (box.hi[a] > B.hi[a]) {
+            B.hi[a] = box.hi[a] + (box.hi[a] - B.hi[a]);
+            grew = true;
+        }
+    }
+    return grew;
+}
+
+uint32_t object_rank(const pt_object *objs, uint32_t n_objs, uint32_t index) {
+    uint32_t next = 0;
+    for (uint32_t i = n_objs; i-- > index + 1u;) next += objs[i].kind == PT_SPHERE ? 1u : objs[i].tri_count;
+    return next;
+}
+
+void edit_object(FlatScene &fs, const Reach &B, const pt_object *objs, uint32_t n_objs, const pt_triangle *tris, uint32_t index,
+                 bool moved, ObjectEdit &e) {
+    const pt_object &o = objs[index];
+    const vec3 slo = ld(B.lo), shi = ld(B.hi);
+    const float scene_R = n_objs ? length(shi - slo) : 0.0f;
+    ObjRec &r = fs.objs[index];
+    e.rank = object_rank(objs, n_objs, index);
+    e.scene_R = scene_R;
+    e.on_device = o.kind == PT_MESH && r.bvh_root != kNoBvh;
+    e.obj_pair = (n_objs - 1u - index) / 2u;
+    e.bvh_mesh = kRefitNone;
+    if (e.on_device) {
+        e.bvh_mesh = 0;
+        for (uint32_t i = n_objs; i-- > index + 1u;) e.bvh_mesh += fs.objs[i].kind == kKindMesh && fs.objs[i].bvh_root != kNoBvh ? 1u : 0u;
+    }
+    object_material(o, fs.mats[index]);
+    if (moved) {
+        const ObjRec ranges = r;  // object_head writes the sphere's and clears the tree: the triangle ranges and the tree stay
+        object_head(o, slo, shi, r);
+        if (o.kind == PT_MESH) {
+            r.tri_begin = ranges.tri_begin, r.tri_count = ranges.tri_count;
+            r.pair_begin = ranges.pair_begin, r.pair_count = ranges.pair_count;
+            r.bvh_root = ranges.bvh_root;
+            if (!e.on_device) {
+                std::vector<BuildTri> bt;
+                mesh_triangles(index, o, tris, scene_R, fs.tri_shade, bt);
+                list_pairs(bt, fs.tri_pairs.data() + r.pair_begin);
+            }
+        }
+        derive_small(objs, n_objs, scene_R, fs);  // the small tables again, whole (bvh_meshes is not among them: the roots stay)
+        if (e.on_device) {
+            BvhMeshRec &bm = fs.bvh_meshes[e.bvh_mesh];
+            bm.cx = r.cx, bm.cy = r.cy, bm.cz = r.cz, bm.rr = r.rr;
+        }
+    }
+    // the surface records at the object's ranks: a sphere's one, a listed mesh's few; a mesh with a BVH gets its on the device
+    e.surf.clear();
+    e.tail.clear();
+    if (index == 0u) {
+        // flatten_scene fills the slots of surf past the last rank - one per mesh: rank_id has n_objs + n_tris entries, the
+        // ranks are the spheres and the triangles - from rank_id's zeros: as a sphere's record of object 0.  No kernel reads them.
+        uint32_t ranks = 0;
+        for (uint32_t i = 0; i < n_objs; ++i) ranks += objs[i].kind == PT_SPHERE ? 1u : objs[i].tri_count;
+        SurfRec sr{};
+        sr.vx = fs.mats[0].px, sr.vy = fs.mats[0].py, sr.vz = fs.mats[0].pz;
+        surf_material(sr, fs.mats[0], false);
+        e.tail_at = ranks;
+        e.tail.assign((size_t)n_objs + fs.tri_shade.size() - ranks, sr);
+    }
+    if (o.kind == PT_SPHERE) {
+        SurfRec sr{};
+        sr.vx = fs.mats[index].px, sr.vy = fs.mats[index].py, sr.vz = fs.mats[index].pz;
+        surf_material(sr, fs.mats[index], false);
+        e.surf.push_back(sr);
+    } else if (!e.on_device) {
+        for (uint32_t k = o.tri_offset; k < o.tri_offset + o.tri_count; ++k) {
+            SurfRec sr{};
+            sr.vx = fs.tri_shade[k].nx, sr.vy = fs.tri_shade[k].ny, sr.vz = fs.tri_shade[k].nz;
+            surf_material(sr, fs.mats[index], true);
+            e.surf.push_back(sr);
+        }
+    }
+}
+
+bool build_refit_plan(const FlatScene &fs, uint32_t index, RefitPlan &p) {
+    p = RefitPlan{};
+    const ObjRec &r = fs.objs[index];
+    if (r.kind != kKindMesh || r.bvh_root == kNoBvh) return false;
+    std::vector<std::vector<RefitNode>> by_height;
+    uint32_t node_lo = kRefitNone, node_hi = 0;
+    // height above the leaves of the subtree at `ref`, which is child `slot` of `parent` (the recursion is as deep as the tree: < kBvhStack)
+    struct Walk {
+        const FlatScene &fs;
+        RefitPlan &p;
+        std::vector<std::vector<RefitNode>> &by_height;
+        uint32_t &node_lo, &node_hi;
+        uint32_t go(int32_t ref, uint32_t parent, uint32_t slot) {
+            if (ref < 0) {
+                const uint32_t code = (uint32_t)~ref;
+                p.leaves.push_back(RefitLeaf{leaf_first(code), leaf_count(code), parent, slot});
+                return 0u;
+            }
+            const BvhNode &n = fs.bvh_nodes[(size_t)ref];
+            node_lo = std::min(node_lo, (uint32_t)ref);
+            node_hi = std::max(node_hi, (uint32_t)ref + 1u);
+            const uint32_t h = 1u + std::max(go(n.c[0], (uint32_t)ref, 0u), go(n.c[1], (uint32_t)ref, 1u));
+            if (parent != kRefitNone) {
+                if (by_height.size() < h) by_height.resize(h);
+                by_height[h - 1u].push_back(RefitNode{(uint32_t)ref, parent, slot});
+            }
+            return h;
+        }
+    } walk{fs, p, by_height, node_lo, node_hi};
+    walk.go(r.bvh_root, kRefitNone, 0u);
+    for (const std::vector<RefitNode> &level : by_height) {
+        p.level_begin.push_back((uint32_t)p.nodes.size());
+        p.nodes.insert(p.nodes.end(), level.begin(), level.end());
+    }
+    p.level_begin.push_back((uint32_t)p.nodes.size());
+    for (size_t d = 0; d < fs.wide_src.size(); ++d) {
+        const uint32_t src = fs.wide_src[d];
+        if (src != kRefitNone && (src >> 1) >= node_lo && (src >> 1) < node_hi) p.wide.push_back(RefitWide{(uint32_t)d, src});
+    }
+    return true;
+}
+
+void run_refit_plan(const RefitPlan &p, const RefitTables &T) {
+    for (const RefitLeaf &lf : p.leaves) refit_leaf(T, lf);
+    for (const RefitNode &n : p.nodes) refit_node(T.nodes, n);  // (by height, ascending: children before parents)
+    for (const RefitWide &w : p.wide) refit_wide(T.nodes4, T.nodes, w);
 }
 
 // ---------------------------------------------------------------------------------------------

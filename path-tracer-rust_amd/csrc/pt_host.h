@@ -7,6 +7,7 @@
 
 #include "../../include/ptrace.h"
 #include "pt_device.h"
+#include "pt_refit.h"
 
 namespace pt {
 
@@ -34,6 +35,8 @@ struct FlatScene {
     std::vector<SurfRec> surf;  // by rank
     std::vector<uint32_t> tri_rank;  // rank of triangle k (the inverse of rank_id over the triangles)
     std::vector<BvhMeshRec> bvh_meshes;  // the meshes that have a BVH, in visiting order (last object first)
+    std::vector<uint32_t> wide_src;  // host only: per child slot of bvh_nodes4, the binary 2 * node + half its box was copied from
+                                     // (kRefitNone: an absent child) - what a refit's gather reads (build_refit_plan)
     uint32_t n_other_pairs = 0;
     uint32_t n_flat_exact = 0;  // flat_pairs [0, n_flat_exact) have sign_exact set (they come first)
     bool cand_ok = false;  // the scene can use the candidate scan (the records of its meshes without a BVH are numbered in
@@ -122,6 +125,51 @@ bool grow_reach(Reach &B, const float lens[3]);
 // when the box lies inside scene_reach's
 bool flatten_scene(const pt_camera &cam, const pt_object *objs, uint32_t n_objs, const pt_triangle *tris,
                    uint32_t n_tris, FlatScene &out, std::string &err, const Reach *origin_box = nullptr, Reach *used = nullptr);
+
+// ---- pt_ctx_set_object (ptrace.h): the host side of an edit in place.  Pure, tested on the CPU (host/object_check.cpp).
+// the call's refusals in the header's order: PT_ERR_INVALID + message.  objs, n_objs: the context's copy (read only past `no scene`)
+int check_object_edit(bool has_ctx, const pt_object *obj, bool has_scene, const pt_object *objs, uint32_t n_objs, uint32_t index);
+// do two objects agree, bit for bit, in position, radius, bs_center and bs_radius (a MATERIAL edit when they do)
+bool same_geometry(const pt_object &a, const pt_object &b);
+// min / max in binary32 over the object-local vertices of a mesh (+inf / -inf for none): cached per object at pt_ctx_set_scene
+void local_vertex_box(const pt_triangle *tris, uint32_t n, Reach &out);
+// An object's bounds as scene_reach takes them: a sphere's centre -/+ |radius|; a mesh's local vertex box + position, which is
+// what min / max over its translated vertices gives, since x -> x + p is monotone in binary32
+void object_bounds(const pt_object &o, const Reach &local, Reach &out);
+// grow_reach's rule applied to the bounds of B that an object's box violates; true when B changed
+bool grow_reach_box(Reach &B, const Reach &box);
+// the visiting rank of object `index` (a sphere's own; a mesh's first triangle's)
+uint32_t object_rank(const pt_object *objs, uint32_t n_objs, uint32_t index);
+// What an in-reach edit of object `index` changed in fs besides objs[index] and mats[index], for the uploader
+struct ObjectEdit {
+    bool on_device = false;  // a mesh with a BVH: its pair records, shading records, surface records and boxes are the refit's
+    uint32_t rank = 0;       // the object's first rank
+    uint32_t obj_pair = 0;   // its record of obj_pairs
+    uint32_t bvh_mesh = kRefitNone;  // its record of bvh_meshes
+    float scene_R = 0.0f;    // the diagonal of B, as flatten_scene takes it (the refit's pads)
+    std::vector<SurfRec> surf;  // the surface records at [rank, rank + size) (none for a mesh with a BVH)
+    uint32_t tail_at = 0;       // object 0 only: the unused slots of surf past the last rank, [tail_at, tail_at + size), which
+    std::vector<SurfRec> tail;  // flatten_scene fills from object 0 (so that an edited table equals a built one to the bit)
+};
+// fs - flatten_scene's tables under the origin box B for these objects but for objs[index], which the caller changed (kind and
+// triangle range as before; its bounds inside B) - brought to what the scene now is, without building a tree: objs[index] and
+// mats[index]; `moved`: also a listed mesh's pair and shading records, and obj_pairs, sph_pairs, flat_pairs, cand_pairs and their
+// counts whole, by the code flatten_scene runs (derive_small).  NOT touched: tri_pairs, tri_shade, bvh_nodes, bvh_nodes4 of a
+// mesh with a BVH (their floats go stale in fs: the refit rewrites the device's; fs keeps the topology), rank_id, surf, tri_rank.
+void edit_object(FlatScene &fs, const Reach &B, const pt_object *objs, uint32_t n_objs, const pt_triangle *tris, uint32_t index,
+                 bool moved, ObjectEdit &e);
+// The refit plan of mesh `index` (pt_refit.h), from the tree in fs: the leaves; the inner nodes but the root, grouped by height
+// above the leaves, ascending (level_begin[h] .. level_begin[h + 1]: height h + 1); the child slots of its four-wide nodes.
+// false: the object has no BVH.
+struct RefitPlan {
+    std::vector<RefitLeaf> leaves;
+    std::vector<RefitNode> nodes;
+    std::vector<uint32_t> level_begin;
+    std::vector<RefitWide> wide;
+};
+bool build_refit_plan(const FlatScene &fs, uint32_t index, RefitPlan &p);
+// the plan's steps in order on host tables, through the functions the kernels call (host/object_check.cpp)
+void run_refit_plan(const RefitPlan &p, const RefitTables &T);
 
 // ---- the arithmetic of a frame call and of the frame pt_ctx_accumulate holds (pt_api.hip): pure, tested on the CPU -----------
 // a valid cfg's band in [*idx_begin, *idx_end); PT_ERR_INVALID + message otherwise

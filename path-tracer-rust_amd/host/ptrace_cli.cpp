@@ -27,7 +27,7 @@ static void usage() {
             "              [--adaptive X [--tile N] [--spp-map FILE.pfm] [--error-map FILE.pfm] [--adaptive-checkpoint FILE]]\n"
             "              [--denoise-var [N]] [--preview FILE.ppm [--preview-size WxH] [--exposure E]]\n"
             "              [--trace-scale K [--retrace]]\n"
-            "              [--orbit N [--orbit-step DEG]]\n"
+            "              [--orbit N [--orbit-step DEG] [--move I:DX,DY,DZ]]\n"
             "  --checkpoint FILE: continue from the samples FILE holds (if it exists), render up to <samplesPerPixel> in all and\n"
             "                     save them to FILE; one GPU only; the seed defaults to 0 instead of the clock, so that the same\n"
             "                     command continues the same frame\n"
@@ -69,7 +69,10 @@ static void usage() {
             "           frame k-1, pt_ctx_denoise_var (sigma_var 2) and pt_ctx_present; the frames go to FILE-000.ppm, FILE-001.ppm,\n"
             "           ..., one line per frame to stderr (the camera update's milliseconds, whether it rebuilt the scene, the\n"
             "           frame's total); one GPU only; not with --trace-scale, --adaptive, --noise-target, --checkpoint, --denoise or\n"
-            "           --denoise-var\n");
+            "           --denoise-var\n"
+            "  --move I:DX,DY,DZ: with --orbit: in frame k object I stands at its position + k * (DX, DY, DZ), in binary32, set\n"
+            "           through pt_ctx_set_object - no pt_ctx_set_scene per frame; a frame in which the object moved passes no\n"
+            "           history to the reprojection; the frame's stderr line adds what the edit took and whether it rebuilt\n");
 }
 
 static std::vector<std::string> scene_ids(const std::string &root) {
@@ -507,8 +510,14 @@ struct OrbitSide {
 };
 
 // --orbit N: the viewport loop of INTEGRATION.md on one context on one GPU, the camera moved with pt_ctx_set_camera
+// --move I:DX,DY,DZ: object `index` stands at its position + k * d in frame k (index < 0: nothing moves)
+struct OrbitMove {
+    long index = -1;
+    float d[3] = {0.0f, 0.0f, 0.0f};
+};
+
 static int render_orbit(const pt_config *cfg, pt_scene *sc, uint32_t frames, double step, const std::string &preview, uint32_t ow,
-                        uint32_t oh, float exposure) {
+                        uint32_t oh, float exposure, const OrbitMove &mv) {
     using clk = std::chrono::steady_clock;
     auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
     int dev = 0;
@@ -550,12 +559,20 @@ static int render_orbit(const pt_config *cfg, pt_scene *sc, uint32_t frames, dou
     pt_camera hist_cam = cam0;
     for (uint32_t k = 0; k < frames && !rc; ++k) {
         const pt_camera cam = orbit_camera(cam0, (double)k * step);
-        const bool hh = k != 0u;
-        int rebuilt = 0;
+        // a frame in which an object moved passes no history on: the reprojection follows the camera, not the objects
+        const bool moves = mv.index >= 0 && k != 0u && (mv.d[0] != 0.0f || mv.d[1] != 0.0f || mv.d[2] != 0.0f);
+        const bool hh = k != 0u && !moves;
+        int rebuilt = 0, edit_rebuilt = 0;
         pt_stats st;
         const clk::time_point t0 = clk::now();
         rc = pt_ctx_set_camera(ctx, &cam, &rebuilt);
         const clk::time_point t1 = clk::now();
+        if (!rc && mv.index >= 0) {
+            pt_object o = objs[mv.index];
+            for (int a = 0; a < 3; ++a) o.position[a] = objs[mv.index].position[a] + (float)k * mv.d[a];
+            rc = pt_ctx_set_object(ctx, (uint32_t)mv.index, &o, &edit_rebuilt);
+        }
+        const clk::time_point t1b = clk::now();
         if (!rc) rc = pt_ctx_render(ctx, cfg, cur->color, nullptr, nullptr, nullptr, nullptr, &st);
         if (!rc) rc = pt_ctx_render_aov(ctx, cfg, d_albedo, cur->normal, cur->depth, cur->id, nullptr);
         pt_reproject_var_params rp;
@@ -581,8 +598,12 @@ static int render_orbit(const pt_config *cfg, pt_scene *sc, uint32_t frames, dou
         const std::string path = stem + name;
         rc = pt_write_ppm8(path.c_str(), px.data(), ow, oh);
         if (rc) break;
-        fprintf(stderr, "frame %u: pt_ctx_set_camera %.3f ms (%s), frame %.3f ms\n", k, ms(t0, t1), rebuilt ? "rebuilt" : "not rebuilt",
-                ms(t0, t2));
+        if (mv.index >= 0)
+            fprintf(stderr, "frame %u: pt_ctx_set_camera %.3f ms (%s), pt_ctx_set_object %.3f ms (%s), frame %.3f ms\n", k, ms(t0, t1),
+                    rebuilt ? "rebuilt" : "not rebuilt", ms(t1, t1b), edit_rebuilt ? "rebuilt" : "not rebuilt", ms(t0, t2));
+        else
+            fprintf(stderr, "frame %u: pt_ctx_set_camera %.3f ms (%s), frame %.3f ms\n", k, ms(t0, t1), rebuilt ? "rebuilt" : "not rebuilt",
+                    ms(t0, t2));
         printf("wrote %s\n", path.c_str());
     }
     if (rc) fprintf(stderr, "--orbit failed (%d): %s\n", rc, pt_last_error());
@@ -615,6 +636,7 @@ int main(int argc, char **argv) {
     uint32_t orbit_frames = 0;
     double orbit_step = 2.0;
     bool orbit_step_given = false;
+    OrbitMove orbit_move;
     for (int i = 4; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&]() -> const char * { return i + 1 < argc ? argv[++i] : ""; };
@@ -728,6 +750,16 @@ int main(int argc, char **argv) {
                 return 1;
             }
         }
+        else if (a == "--move") {
+            const char *v = next();
+            char colon = 0, rest = 0;
+            if (sscanf(v, "%ld%c%f,%f,%f%c", &orbit_move.index, &colon, &orbit_move.d[0], &orbit_move.d[1], &orbit_move.d[2], &rest) != 5 ||
+                colon != ':' || orbit_move.index < 0 || !std::isfinite(orbit_move.d[0]) || !std::isfinite(orbit_move.d[1]) ||
+                !std::isfinite(orbit_move.d[2])) {
+                fprintf(stderr, "--move needs I:DX,DY,DZ, an object index and three finite numbers\n");
+                return 1;
+            }
+        }
         else if (a == "--orbit-step") {
             char *e = nullptr;
             const char *v = next();
@@ -770,6 +802,10 @@ int main(int argc, char **argv) {
     }
     if (orbit_step_given && !orbit_frames) {
         fprintf(stderr, "--orbit-step goes with --orbit N\n");
+        return 1;
+    }
+    if (orbit_move.index >= 0 && !orbit_frames) {
+        fprintf(stderr, "--move goes with --orbit N\n");
         return 1;
     }
     if (orbit_frames && preview.empty()) {
@@ -887,7 +923,12 @@ int main(int argc, char **argv) {
     cfg.backend = backend == "megakernel" ? PT_BACKEND_MEGAKERNEL : PT_BACKEND_WAVEFRONT;
     cfg.seed = seed;
     if (orbit_frames) {
-        rc = render_orbit(&cfg, sc, orbit_frames, orbit_step, preview, preview_w, preview_h, exposure);
+        if (orbit_move.index >= (long)n_objs) {
+            fprintf(stderr, "--move: object %ld is not one of the scene's %u\n", orbit_move.index, n_objs);
+            pt_scene_free(sc);
+            return 1;
+        }
+        rc = render_orbit(&cfg, sc, orbit_frames, orbit_step, preview, preview_w, preview_h, exposure, orbit_move);
         pt_scene_free(sc);
         return rc ? 2 : 0;
     }

@@ -1,0 +1,119 @@
+"""pt_ctx_set_object's contract where no device is needed:
+
+- The header declares pt_ctx_set_object and pt_ctx_table_hashes, names every table, and states the contract in the style of
+  pt_ctx_set_camera's; the library exports both; PT_ABI_VERSION is still 5; the Rust shim and the Python binding mirror them.
+- The refusals that come before a context exists - ctx NULL, whatever else is wrong - set pt_last_error and write nothing.  The
+  rest of the order (obj NULL; no scene; index; topology; reflect_type; not finite) needs a context: host/object_check.cpp runs it
+  on the host through the function the call uses, tests/test_gpu_set_object.py on a device.
+- pt_refit.hip is a unit of the library and pt_refit.h the one statement of the per-triangle arithmetic: flatten_scene and the
+  kernels both go through world_triangle.
+- `make object-check` - the refusals in order, the reach test at its edges, the growth rule, edit_object's tables and the refit
+  plan run on the host against flatten_scene of the edited scene, host only under AddressSanitizer and UBSan - builds and passes."""
+import ctypes as C
+import importlib
+import os
+import re
+import subprocess
+
+import ptlib
+from ptlib import PtObject
+
+ROOT = ptlib.ROOT
+PT_ERR_INVALID = -1
+NEW = ("pt_ctx_set_object", "pt_ctx_table_hashes")
+TABLES = ("OBJS", "OBJ_PAIRS", "TRI_PAIRS", "MATS", "TRI_SHADE", "BVH_NODES", "BVH_NODES4", "SPH_PAIRS", "FLAT_PAIRS", "CAND_PAIRS",
+          "RANK_ID", "SURF", "TRI_RANK", "BVH_MESHES")
+norm = lambda s: re.sub(r"\s+", " ", s)
+
+
+def header():
+    return open(os.path.join(ROOT, "include", "ptrace.h")).read()
+
+
+def test_header_declares_them_and_states_the_contract():
+    h = header()
+    code = norm(re.sub(r"/\*.*?\*/", "", h, flags=re.S))
+    for decl in ("int pt_ctx_set_object(pt_ctx *ctx, uint32_t index, const pt_object *obj, int *rebuilt);",
+                 "int pt_ctx_table_hashes(pt_ctx *ctx, uint64_t out[PT_TABLE_COUNT]);"):
+        assert decl in code, decl
+    enum = re.search(r"enum \{([^}]*PT_TABLE_COUNT[^}]*)\}", code).group(1)
+    names = [n.strip().split(" ")[0] for n in enum.split(",")]
+    assert names == ["PT_TABLE_" + t for t in TABLES] + ["PT_TABLE_COUNT"], names
+    assert "PT_TABLE_OBJS = 0" in enum
+    assert "#define PT_ABI_VERSION 5" in h
+    doc = norm(re.sub(r"\n \*", "\n", h[h.index("Replace object `index`"):h.index("int pt_ctx_set_object(")]))
+    for phrase in ("bitwise equal", "SAME", "MATERIAL path", "MOVE path", "OUT OF REACH", "*rebuilt = 0", "*rebuilt = 1", "in binary32",
+                   "centre -/+ |radius|", "object-local vertex box", "monotone", "REFIT ON THE DEVICE", "36 B each", "does not drift",
+                   "lo[a] = bounds.lo[a] - (lo[a] - bounds.lo[a])", "hi[a] = bounds.hi[a] + (bounds.hi[a] - hi[a])",
+                   "the context is left as it was", "fingerprint", "pt_ctx_set_mesh_bounds", "bit for bit", "pt_ctx_scatter",
+                   "ctx NULL; obj NULL; no scene; index >= n_objs", "topology edits go through pt_ctx_set_scene",
+                   "reflect_type > PT_REFRACT", "that is not finite", "rebuilt may be NULL", "progress callback", "One object per call"):
+        assert norm(phrase) in doc, phrase
+
+
+def test_library_exports_them_and_the_abi_version_stays():
+    L = ptlib.product()
+    out = subprocess.check_output(["nm", "-D", "--defined-only", ptlib.PRODUCT_SO], text=True)
+    exported = {line.split()[-1] for line in out.splitlines() if line.strip()}
+    assert set(NEW) <= exported
+    assert L.pt_abi_version() == 5
+
+
+def test_rust_shim_and_python_binding_mirror_them():
+    full = open(os.path.join(ROOT, "ffi", "hip.rs")).read()
+    rust = re.sub(r"//[^\n]*", "", full)
+    ext = re.search(r'extern "C" \{(.*?)\n\}', rust, flags=re.S).group(1)
+    ext = norm(ext).replace(", )", ")").replace("( ", "(")
+    for decl in ("pub fn pt_ctx_set_object(ctx: *mut PtCtx, index: u32, obj: *const PtObject, rebuilt: *mut i32) -> i32;",
+                 "pub fn pt_ctx_table_hashes(ctx: *mut PtCtx, out: *mut u64) -> i32;"):
+        assert decl in ext, decl
+    for i, t in enumerate(TABLES + ("COUNT",)):
+        assert "pub const PT_TABLE_%s: usize = %d;" % (t, i) in rust, t
+    assert "pt_ctx_set_object(ctx, picked as u32, &obj, &mut rebuilt)" in full  # the drag loop's example
+    pkg = importlib.import_module("path-tracer-rust_amd")
+    assert callable(pkg.Context.set_object) and callable(pkg.Context.table_hashes)
+    assert pkg.TABLE_NAMES == tuple(t.lower() for t in TABLES)
+    lib = pkg.lib()
+    assert lib.pt_ctx_set_object.argtypes[2]._type_ is pkg.pt_object and len(lib.pt_ctx_table_hashes.argtypes) == 2
+
+
+def test_refusals_without_a_device():
+    L = ptlib.product()
+    L.pt_ctx_set_object.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(PtObject), C.POINTER(C.c_int)]
+    L.pt_ctx_table_hashes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    obj = PtObject()
+    obj.kind, obj.reflect_type, obj.radius = 9, 9, float("nan")  # everything after the context is wrong too: ctx comes first
+    rebuilt = C.c_int(-7)
+    for args in ((None, 0, None), (None, 0, C.byref(obj)), (None, 0xffffffff, C.byref(obj))):
+        assert L.pt_ctx_set_object(*args, C.byref(rebuilt)) == PT_ERR_INVALID
+        assert b"ctx is NULL" in L.pt_last_error()
+    assert L.pt_ctx_set_object(None, 0, C.byref(obj), None) == PT_ERR_INVALID
+    assert rebuilt.value == -7
+    out = (C.c_uint64 * 14)(*([5] * 14))
+    assert L.pt_ctx_table_hashes(None, out) == PT_ERR_INVALID and b"NULL" in L.pt_last_error()
+    assert list(out) == [5] * 14
+
+
+def test_one_statement_of_the_triangle_arithmetic_and_a_unit_of_its_own():
+    pkg = ptlib.PKG
+    mk = open(os.path.join(pkg, "Makefile")).read()
+    units = re.search(r"^UNITS\s*=(.*)$", mk, flags=re.M).group(1).split()
+    assert "pt_refit" in units and "pt_refit" not in re.search(r"^TUNED\s*=(.*)$", mk, flags=re.M).group(1).split()
+    assert "object" in re.search(r"^CHECKS\s*=(.*)$", mk, flags=re.M).group(1).split()
+    host = open(os.path.join(pkg, "csrc", "pt_host.cpp")).read()
+    refit_h = open(os.path.join(pkg, "csrc", "pt_refit.h")).read()
+    kernels = open(os.path.join(pkg, "csrc", "pt_refit.hip")).read()
+    assert "PT_HD WorldTri world_triangle(" in refit_h and "world_triangle(" in host
+    assert "normalize(cross(e1, e2))" not in host  # flatten_scene no longer states the arithmetic itself
+    for step in ("refit_leaf(", "refit_node(", "refit_wide(", "surf_material("):
+        assert "PT_HD void " + step in refit_h and step in kernels, step
+    # the frame kernels' unit does not see the refit: pt_kernels.s, and so pt_kernel_isa_hash(), is theirs alone
+    assert "pt_refit" not in open(os.path.join(pkg, "csrc", "pt_kernels.hip")).read()
+    assert "pt_refit" not in open(os.path.join(pkg, "csrc", "pt_device.h")).read()
+
+
+def test_object_check_builds_and_passes(tmp_path):
+    r = subprocess.run(["make", "-C", ptlib.PKG, "object-check", "B=" + str(tmp_path)], capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    assert "object_check: OK" in r.stdout
+    assert "-fsanitize=address,undefined" in r.stdout and "--cuda-host-only" in r.stdout
