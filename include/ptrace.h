@@ -419,6 +419,9 @@ int pt_ctx_primary_rays(pt_ctx *ctx, uint32_t width, uint32_t height, uint64_t s
  * the path: thr0 = fl(fl(thr * colour') * factor) per channel, colour' the colour after the roulette's rescale.
  * This proves the functions, not each kernel's use of them: that stays with the bounce counts and the frame tests.
  * tests/kats_scatter.py is the independent restatement; the oracle's pto_dump_paths gives its paths with their keys.
+ * Bit-for-bit agreement with it holds for directions and (PT_SCATTER_GIVEN) normals of unit length to within rounding, which
+ * is all the frame kernels ever hand the step: its square roots of the diffuse basis, the diffuse direction and tdir skip the
+ * range test of the general routine on the strength of that (csrc/pt_device.h states each bound).
  * PT_ERR_INVALID, all refused before any device is touched, checked in this order: NULL items or out; n == 0; unknown form
  * bits (or both mode flags, or source 3); PT_SCATTER_GIVEN without surfaces; an item with sample >= 2^24, depth > 11 or
  * branch outside 1..7; PT_SCATTER_GIVEN: a reflect type above 2, or PT_SCATTER_REFRACT_ONLY with a surface that is not Refract;

@@ -289,6 +289,26 @@ struct PhaseLds {
 #define PT_WSTAT(S, i, v) do { } while (0)
 #endif
 
+#if defined(PT_RANGE_STATS) && defined(__HIPCC__)
+// Diagnostic build only (make range, tools/range_stats.py; never in the shipped library): per call site of f_sqrt_ranged /
+// normalize_ranged, the arguments evaluated and those OUTSIDE [2^-96, largest float] - where the site's bound would not
+// hold and f_sqrt would have taken the compiler's full path.  One table per translation unit (pt_kernels.hip reads its own).
+enum : uint32_t { kRsOneMinusR2 = 0, kRsBasis, kRsDiffuseDir, kRsTdir, kRsCount };
+static __device__ unsigned long long g_range_stats[kRsCount][2];  // [site]{evaluated, outside}
+__device__ __forceinline__ void range_note(uint32_t site, float x) {
+    const uint32_t u = __float_as_uint(x);
+    const bool outside = (u >> 31) != 0u || (u - 0x0f800000u) >= 0x70000000u;  // f_sqrt's test, and no negative argument
+    const uint64_t all = __builtin_amdgcn_ballot_w64(true), bad = __builtin_amdgcn_ballot_w64(outside);
+    if ((threadIdx.x & 63u) == (uint32_t)__builtin_ctzll(all)) {
+        atomicAdd(&g_range_stats[site][0], (unsigned long long)__builtin_popcountll(all));
+        if (bad != 0ull) atomicAdd(&g_range_stats[site][1], (unsigned long long)__builtin_popcountll(bad));
+    }
+}
+#define PT_RANGE_NOTE(site, x) ::pt::range_note(site, x)
+#else
+#define PT_RANGE_NOTE(site, x) do { } while (0)
+#endif
+
 // per-frame constants
 struct FrameParams {
     uint32_t width, height, spp;
@@ -1584,11 +1604,14 @@ __device__ __forceinline__ unsigned long long cand_spheres(const DevScene &S, ve
 #pragma unroll
         for (int hf = 0; hf < 2; ++hf) {
             if (__builtin_amdgcn_ballot_w64(!(det[hf] < 0.0f)) == 0ull) continue;  // no lane of the wave hits this one
-            const float sq = f_sqrt(det[hf]);  // NaN when det < 0: both comparisons below are then false
+            const float sq = f_sqrt(det[hf]);  // NaN when det < 0 (or NaN): both comparisons below are then false
             const float t0 = b[hf] - sq, t1 = b[hf] + sq;
             const bool near_ok = t0 >= 1e-4f, far_ok = t1 >= 1e-4f;
             const float t = near_ok ? t0 : t1;
-            if (!(det[hf] < 0.0f) && (near_ok || far_ok) && t < best_t) {
+            // mod.rs:419-426 accepts when !(det < 0) && (near_ok || far_ok).  far_ok alone says the same: sq >= 0 and rounding
+            // is monotone, so t1 = fl(b + sq) >= fl(b - sq) = t0 and near_ok implies far_ok; and with det < 0 or NaN, sq and t1
+            // are NaN and far_ok is false.  (The compiler may not drop either term under IEEE rules: a v_cmp per sphere.)
+            if (far_ok && t < best_t) {
                 best_t = t;
                 best_rank = sp.rank[hf];
             }
@@ -1949,7 +1972,8 @@ __device__ __forceinline__ void shade_surface(const Params &F, const PathRay &in
     PT_PHASE(kPhRng);
     const vec3 d = in.d;
     const vec3 n = sf.n;
-    const vec3 nl = dot(n, d) < 0.0f ? n : n * -1.0f;  // normal_towards_ray
+    const float dn = dot(n, d);
+    const vec3 nl = dn < 0.0f ? n : n * -1.0f;  // normal_towards_ray
     const uint32_t sample = meta_sample(in.meta), depth = meta_depth(in.meta), branch = meta_branch(in.meta);
     const uint32_t new_depth = depth + 1u;
     const u32x4 rnd = draw_block(((uint64_t)F.seed_hi << 32) | F.seed_lo, in.pix, sample, (branch << 8) | new_depth);
@@ -1982,26 +2006,51 @@ __device__ __forceinline__ void shade_surface(const Params &F, const PathRay &in
         PT_PHASE(kPhDiffuse);
         const float r1 = (2.0f * 3.141592653589793f) * unit_f32(rnd.b);
         const float r2 = unit_f32(rnd.c);
-        const float r2s = f_sqrt(r2);
+        const float r2s = f_sqrt(r2);  // (r2 can be 0: the full form)
         const vec3 w = nl;
-        const vec3 uu = normalize(cross(f_abs(w.x) > 0.1f ? mk(0.0f, 1.0f, 0.0f) : mk(1.0f, 0.0f, 0.0f), w));
+        // The three below are f_sqrt's fast path without its range test (pt_math.h: f_sqrt_ranged).  They rest on w being a
+        // unit vector to within rounding - a hit's normal: a triangle's, normalised on the host from a cross product whose
+        // length passed |det| >= 1e-4, or a sphere's, normalised by fetch_surface*; |w|^2 in [0.5, 2] is all they need.
+        // (A NaN normal gives NaN directions with either form.)
+        const vec3 cr = cross(f_abs(w.x) > 0.1f ? mk(0.0f, 1.0f, 0.0f) : mk(1.0f, 0.0f, 0.0f), w);
+        // |cr|^2 in [0.01, 2]: (w.z, 0, -w.x) with w.x^2 > 0.01, or (0, -w.z, w.y) with w.y^2 + w.z^2 = |w|^2 - w.x^2 >= 0.5 - 0.0101
+        PT_RANGE_NOTE(kRsBasis, dot(cr, cr));
+        const vec3 uu = normalize_ranged(cr);
         const vec3 vv = cross(w, uu);
         float sn, cs;
         sincos_f32(r1, &sn, &cs);
-        d0 = normalize(uu * cs * r2s + vv * sn * r2s + w * f_sqrt(1.0f - r2));
+        // 1 - r2 in [2^-24, 1]: r2 = k * 2^-24 with k < 2^24, and the subtraction is exact
+        PT_RANGE_NOTE(kRsOneMinusR2, 1.0f - r2);
+        const vec3 dd = uu * cs * r2s + vv * sn * r2s + w * f_sqrt_ranged(1.0f - r2);
+        // |dd|^2 in [0.49, 2.1]: uu (unit), vv (|vv| = |w|), w are orthogonal to within rounding, so |dd|^2 = r2 (cs^2 + sn^2 |w|^2)
+        // + (1 - r2) |w|^2 to within rounding, between min(1, |w|^2) and max(1, |w|^2) - 1 for a unit w
+        PT_RANGE_NOTE(kRsDiffuseDir, dot(dd, dd));
+        d0 = normalize_ranged(dd);
     } else {
         PT_PHASE(kPhSpecular);
-        const vec3 refl = d - n * 2.0f * dot(n, d);  // mod.rs:722-723 / 733-734
+        const vec3 refl = d - n * 2.0f * dn;  // mod.rs:722-723 / 733-734
         d0 = refl;
         if (MODE == kShadeRefractOnly || sf.reflect == kRefract) {  // mod.rs:729-788
             PT_PHASE(kPhGlass);
-            const bool into = dot(n, nl) > 0.0f;
+            // mod.rs:736 takes normal.dot(normal_towards_ray) > 0 and mod.rs:740 direction.dot(normal_towards_ray): both follow
+            // from dn without a second and third dot product (11 instructions, two of them compares).  nl is n exactly when
+            // dn < 0, and n . n > 0 for a unit n, n . (-n) < 0 (a zero n gives false either way; NaN too).  The products of a
+            // dot commute and negating nl negates every product and both sums exactly, so d . nl is dn or -dn bit for bit - but
+            // for the sign of a sum that cancels to zero (x + -x is +0 either way), which nothing below keeps: ddn is squared,
+            // added to sqrt(cos2t) = sqrt(5/9) (a zero ddn from outside; from inside it is total internal reflection), and
+            // subtracted from 1.
+            const bool into = dn < 0.0f;
             const float nc = 1.0f, nt = 1.5f;
             const float nnt = into ? nc / nt : nt / nc;
-            const float ddn = dot(d, nl);
+            const float ddn = into ? dn : -dn;
             const float cos2t = 1.0f - (nnt * nnt) * (1.0f - ddn * ddn);
             if (!(cos2t < 0.0f)) {  // otherwise total internal reflection: the reflected ray alone
-                const vec3 tdir = normalize(d * nnt - n * ((into ? 1.0f : -1.0f) * (ddn * nnt + f_sqrt(cos2t))));
+                // (cos2t can be 0 or tiny at the edge of total internal reflection: the full form)
+                const vec3 tv = d * nnt - n * ((into ? 1.0f : -1.0f) * (ddn * nnt + f_sqrt(cos2t)));
+                // |tv|^2 in [0.9, 1.1] for unit d and n (a ray's direction is normalised where it is made, a probe's by
+                // contract): tv = nnt (d - ddn nl) - sqrt(cos2t) nl, tangential part nnt^2 (1 - ddn^2) = 1 - cos2t, normal part cos2t
+                PT_RANGE_NOTE(kRsTdir, dot(tv, tv));
+                const vec3 tdir = normalize_ranged(tv);
                 const float a = nt - nc, bb = nt + nc;
                 const float r0 = a * a / (bb * bb);
                 const float c = 1.0f - (into ? -ddn : dot(tdir, n));

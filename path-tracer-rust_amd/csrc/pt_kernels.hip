@@ -2231,3 +2231,22 @@ void launch_tile_pass(hipStream_t st, uint32_t grid, const DevScene &S, const Ld
 }
 #endif  // PT_TU_TILE
 }  // namespace pt
+
+#ifdef PT_RANGE_STATS
+// instrumented builds only (tools/range_stats.py): read and clear this unit's table of pt_device.h's range_note
+#if defined(PT_TU_FLAT)
+#define PT_RANGE_READER pt_debug_range_stats_flat
+#elif defined(PT_TU_TILE)
+#define PT_RANGE_READER pt_debug_range_stats_tile
+#else
+#define PT_RANGE_READER pt_debug_range_stats_main
+#endif
+extern "C" int PT_RANGE_READER(unsigned long long *out, uint32_t cap) {
+    static const unsigned long long zero[pt::kRsCount][2] = {};
+    if (!out || cap < pt::kRsCount * 2u) return -1;
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(pt::g_range_stats), sizeof zero) != hipSuccess) return -1;
+    if (hipMemcpyToSymbol(HIP_SYMBOL(pt::g_range_stats), zero, sizeof zero) != hipSuccess) return -1;
+    return (int)pt::kRsCount;
+}
+#endif

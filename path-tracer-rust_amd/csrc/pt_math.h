@@ -3,7 +3,8 @@
 // Every function here is a strict per-operation IEEE-754 binary32 (or binary64 inside sin/cos)
 // evaluation in the order the reference evaluates it; the translation units that include this
 // header are built with -ffp-contract=off -fno-fast-math so neither hipcc nor the host compiler
-// fuses or reassociates anything (rustc/LLVM never does for the reference either).
+// fuses or reassociates anything (rustc/LLVM never does for the reference either).  The one exception is written out, not
+// left to a compiler: sincos_f32's binary64 interior uses explicit fma, its binary32 results counted equal on every argument.
 //
 // Reference semantics restated (citations relative to /root/reference):
 //   glam 0.30.8 scalar Vec3 (Cargo.lock:1508)  dot, cross, length, normalize = v*(1/len)
@@ -78,6 +79,15 @@ __device__ __forceinline__ float f_sqrt(float x) {
     const float d = __builtin_fmaf(-s, s, x);
     return __builtin_fmaf(d, h, s);
 }
+// f_sqrt's fast path alone, for a call site that can BOUND its argument inside [2^-96, largest float] (the bound stands in a
+// comment at the site): the range test (v_and, v_add_u32, v_cmp, s_cbranch) and the site's private copy of the IEEE expansion
+// go.  Same five instructions, so the same bits as f_sqrt on that domain.  Outside it the result is unspecified.
+__device__ __forceinline__ float f_sqrt_ranged(float x) {
+    const float r = __builtin_amdgcn_rsqf(x);
+    const float s = x * r, h = 0.5f * r;
+    const float d = __builtin_fmaf(-s, s, x);
+    return __builtin_fmaf(d, h, s);
+}
 __device__ __forceinline__ float f_rcp(float d) {
     const float r0 = __builtin_amdgcn_rcpf(d);
     const float e0 = __builtin_fmaf(-d, r0, 1.0f);
@@ -85,11 +95,14 @@ __device__ __forceinline__ float f_rcp(float d) {
 }
 #else
 PT_HD float f_sqrt(float x) { return __builtin_sqrtf(x); }
+PT_HD float f_sqrt_ranged(float x) { return __builtin_sqrtf(x); }
 PT_HD float f_rcp(float d) { return 1.0f / d; }
 #endif
 PT_HD float f_max(float a, float b) { return __builtin_fmaxf(a, b); }
 PT_HD float length(vec3 a) { return f_sqrt(dot(a, a)); }
 PT_HD vec3 normalize(vec3 a) { return a * f_rcp(length(a)); }
+// normalize for a vector whose squared length the call site bounds inside [2^-96, largest float] (see f_sqrt_ranged)
+PT_HD vec3 normalize_ranged(vec3 a) { return a * f_rcp(f_sqrt_ranged(dot(a, a))); }
 
 // ---- rand 0.8.5: 24 high bits of a u32 -> [0,1)
 PT_HD float unit_f32(uint32_t u) { return (float)(u >> 8) * (1.0f / 16777216.0f); }
@@ -159,22 +172,31 @@ PT_HD uint32_t top12(float f) {
     memcpy(&u, &f, sizeof u);
     return (u >> 20) & 0x7ffu;
 }
+// The two polynomials of the first quadrant, every a + b * c as ONE fused operation (five and six binary64 operations).
+// glibc rounds each product and each sum; the fused form rounds once per pair.  The binary64 results differ in their last
+// bits, the binary32 values they round to do not: see sincos_f32.
 PT_HD float sin_poly(double x, double x2) {
     const double x3 = x * x2;
-    const double s1 = kS2 + x2 * kS3;
+    const double s1 = __builtin_fma(x2, kS3, kS2);
     const double x7 = x3 * x2;
-    const double s = x + x3 * kS1;
-    return (float)(s + x7 * s1);
+    const double s = __builtin_fma(x3, kS1, x);
+    return (float)__builtin_fma(x7, s1, s);
 }
-// `flip` selects the negated cosine table (quadrants 2 and 3)
-PT_HD float cos_poly(double x2, bool flip) {
-    const double g = flip ? -1.0 : 1.0;
+PT_HD float cos_poly(double x2) {
     const double x4 = x2 * x2;
-    const double c2 = g * kC3 + x2 * (g * kC4);
-    const double c1 = g * kC1 + x2 * (g * kC2);
+    const double c2 = __builtin_fma(x2, kC4, kC3);
+    const double c1 = __builtin_fma(x2, kC2, kC1);
     const double x6 = x4 * x2;
-    const double c = g * kC0 + x2 * c1;
-    return (float)(c + x6 * c2);
+    const double c = __builtin_fma(x2, c1, kC0);
+    return (float)__builtin_fma(x6, c2, c);
+}
+// v with its sign bit flipped where bit 1 of k is set
+PT_HD float flip_sign(float v, int k) {
+    uint32_t u;
+    memcpy(&u, &v, sizeof u);
+    u ^= ((uint32_t)k & 2u) << 30;
+    memcpy(&v, &u, sizeof v);
+    return v;
 }
 }  // namespace sc
 
@@ -184,19 +206,32 @@ PT_HD float cos_poly(double x2, bool flip) {
 // y < 2^-12 the polynomials round back to y and 1.0f.  So one branch-free path gives bit-identical results
 // (checked against the two-shortcut restatement in the oracle, and through it against the platform libm, on all
 // 2^24 reachable arguments: tests/test_abi.py) and the wave never runs two copies of the polynomials.
+//
+// FUSED, SIGN-OUTSIDE FORM: 14 binary64 operations (r, the reduction, x2, five for the sine, six for the cosine) where the
+// operation-by-operation form ran 26 under -ffp-contract=off.  Two things went, both written out here rather than left to
+// the compiler (-ffp-contract=off stays):
+//   - glibc flips the sign of a quadrant by negating x and the cosine table (five multiplications by +-1.0 and a select to
+//     build the factor).  Round-to-nearest is odd-symmetric, so negating every input of a polynomial negates every
+//     intermediate and the result exactly: the sign is applied to the two binary32 results instead, one integer xor each.
+//     The sine's sign is bit 1 of n and the cosine's bit 1 of n + 1, whichever polynomial the quadrant's parity picked.
+//   - every a + b * c of the reduction x - n * hpi and of the polynomials is one __builtin_fma (v_fma_f64; fma() on the
+//     host: the same operation on both sides).  The binary64 values differ from the unfused ones by parts in 2^53, far below
+//     the half-ulp of the binary32 result - not a proof that no argument lands across a rounding boundary, which is why it
+//     was counted: host/sincos_check.cpp (make sincos-check) compares this function with an in-file restatement of the
+//     unfused form on all 2^24 arguments, sine and cosine: 0 mismatches of 2 x 2^24.  tests/test_abi.py (against the oracle
+//     and libm) and pt_ctx_sincos_sweep (device against host) pin the result as before.
 PT_HD void sincos_f32(float y, float *s_out, float *c_out) {
     double x = (double)y;
     const double r = x * sc::kHpiInv;
     const int n = ((int32_t)r + 0x800000) >> 24;
-    x = x - (double)n * sc::kHpi;
-    const int q = n & 3;
-    const double sgn = (q == 1 || q == 2) ? -1.0 : 1.0;
-    const float sp = sc::sin_poly(x * sgn, x * x);
-    const float cp = sc::cos_poly(x * x, (n & 2) != 0);
+    x = __builtin_fma(-(double)n, sc::kHpi, x);
+    const double x2 = x * x;
+    const float sp = sc::sin_poly(x, x2);
+    const float cp = sc::cos_poly(x2);
     // sinf uses polynomial index n, cosf uses n^1: even -> sine polynomial, odd -> cosine polynomial
     const bool even = (n & 1) == 0;
-    *s_out = even ? sp : cp;
-    *c_out = even ? cp : sp;
+    *s_out = sc::flip_sign(even ? sp : cp, n);
+    *c_out = sc::flip_sign(even ? cp : sp, n + 1);
 }
 
 // tent filter of render_pixel (mod.rs:820-830)
