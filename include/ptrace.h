@@ -87,8 +87,8 @@ typedef struct pt_object {
     uint32_t kind;
     float position[3];
     float radius; /* PT_SPHERE only */
-    float color[3];
-    float emission[3]; /* the reference spells it `emmission` */
+    float color[3];    /* every component finite and >= 0 (-0.0f counts as 0): see pt_ctx_set_scene */
+    float emission[3]; /* the same; the reference spells it `emmission` */
     uint32_t reflect_type;
     uint32_t tri_offset;
     uint32_t tri_count;
@@ -166,6 +166,11 @@ int pt_mesh_bounding_sphere(const pt_triangle *tris, uint32_t n_tris, float cent
 /* One context = one GPU, one stream, device copies of one scene and the ray queues. */
 int pt_ctx_create(int device, pt_ctx **out);
 void pt_ctx_destroy(pt_ctx *ctx);
+/* PT_ERR_INVALID, the context left as it was, pt_last_error naming the object and the field: an unknown kind or reflect_type, a
+ * triangle range outside the array or shared by two objects, BVHs beyond pt_bvh_refs_fit, and a component of color or emission
+ * that is negative or not finite (NaN included).  The last because radiance is summed in unsigned fixed point (see "progressive
+ * accumulation" below): a contribution is a product of these components, and the conversion is defined for finite values >= 0
+ * only.  pt_render and pt_render_multi refuse the same scenes, pt_ctx_set_object the same materials. */
 int pt_ctx_set_scene(pt_ctx *ctx, const pt_camera *cam, const pt_object *objs, uint32_t n_objs,
                      const pt_triangle *tris, uint32_t n_tris);
 
@@ -237,7 +242,8 @@ int pt_scene_reach(const pt_camera *cam, const pt_object *objs, uint32_t n_objs,
  * anew); the results may not.
  * PT_ERR_INVALID, in this order, nothing changed, before any device is touched: ctx NULL; obj NULL; no scene; index >= n_objs;
  * kind, tri_offset or tri_count differ from the object's (topology edits go through pt_ctx_set_scene);
- * reflect_type > PT_REFRACT; a position, radius, bs_center or bs_radius that is not finite.  rebuilt may be NULL.  One object per
+ * reflect_type > PT_REFRACT; a position, radius, bs_center or bs_radius that is not finite; a component of color or emission
+ * that is negative or not finite (as pt_ctx_set_scene refuses it).  rebuilt may be NULL.  One object per
  * call.  Like pt_ctx_set_scene, not to be called from a progress callback. */
 int pt_ctx_set_object(pt_ctx *ctx, uint32_t index, const pt_object *obj, int *rebuilt);
 
@@ -460,7 +466,8 @@ int pt_ctx_scatter(pt_ctx *ctx, uint64_t seed, uint32_t form, const pt_scatter_i
 void pt_host_sincos(float y, float *s, float *c);
 
 /* The drop-in for mod.rs:1017-1024: host buffers in, host framebuffer out (whole W*H*3 floats,
- * only the band is written).  Uses device 0 (or PT_DEVICE env).  Blocking. */
+ * only the band is written).  Uses device 0 (or PT_DEVICE env).  Blocking.  PT_ERR_INVALID for a scene pt_ctx_set_scene
+ * refuses, a negative or non-finite colour or emission component among them. */
 int pt_render(const pt_config *cfg, const pt_camera *cam, const pt_object *objs, uint32_t n_objs,
               const pt_triangle *tris, uint32_t n_tris, float *out_rgb,
               const volatile uint8_t *cancel, pt_progress_fn cb, void *user, pt_stats *stats);
@@ -487,6 +494,12 @@ int pt_ctx_snapshot(pt_ctx *ctx, void *d_out_rgb, uint32_t *spp_done);
 /* ---- progressive accumulation across calls: resume, refine, checkpoint -----------------------------------------
  * The RNG is keyed on (seed; pixel, sample, ...) and radiance is summed in u64 fixed point, whose sum does not depend on the
  * order of its terms; so a frame rendered to T samples over several calls is pt_ctx_render's frame at T, bit for bit.
+ * THE SUMS.  A pixel channel is one u64 in 32.32 fixed point.  A contribution v (finite, >= 0: pt_ctx_set_scene keeps the others
+ * out) adds c = min(v, 4294967040) as trunc(c) * 2^32 + trunc((c - trunc(c)) * 2^32), every step in binary32 and exact but the
+ * truncations: one contribution SATURATES at 4294967040 = 2^32 - 256, the largest binary32 below 2^32.  The sum over all the
+ * samples a pixel holds WRAPS at 2^32 radiance units and nothing detects it: mean x samples must stay below 4.29e9 - an emission
+ * of 256 seen directly at 2^24 samples per pixel is the first frame that does not fit.  A frame is the sums resolved:
+ * (float)((double)sum * 2^-32) / (float)samples, clamped to [0, 1] (pt_ctx_radiance: not clamped).
  *
  * pt_ctx_accumulate renders this frame up to cfg->spp samples per pixel IN TOTAL.  The samples come from an accumulator the
  * context keeps between calls, so only the samples it does not hold yet are traced.

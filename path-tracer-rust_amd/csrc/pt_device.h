@@ -2129,9 +2129,12 @@ __device__ __forceinline__ PathRay primary_ray_at(const FrameParams &F, uint32_t
 
 // Radiance is summed per pixel in unsigned 32.32 fixed point: integer adds commute, so the image does
 // not depend on the order in which paths finish (any queue order, any number of GPUs), and the sum is
-// exact to 2^-32 per contribution.  v is finite and >= 0 (throughput and emission are non-negative).
+// exact to 2^-32 per contribution.  v is finite and >= 0: throughput and emission are products of colour and emission
+// components, and the door (host::bad_material: pt_ctx_set_scene, pt_render, pt_ctx_set_object) refuses a component that is
+// negative or not finite.  What the code would do with the others: a NaN fails the comparison, takes the second arm and
+// saturates like a large value; a negative v reaches the float -> uint32_t conversion, which C++ leaves undefined.
 __device__ __forceinline__ uint64_t to_fixed(float v) {
-    const float c = v < 4294967040.0f ? v : 4294967040.0f;  // saturate; NaN falls through to cvt -> 0
+    const float c = v < 4294967040.0f ? v : 4294967040.0f;  // saturate: one contribution holds at most 2^32 - 256
     const uint32_t hi = (uint32_t)c;                         // truncation, exact
     const float frac = c - (float)hi;                        // exact
     const uint32_t lo = (uint32_t)(frac * 4294967296.0f);    // exact scaling, truncation

@@ -592,6 +592,14 @@ static void derive_small(const pt_object *objs, uint32_t n_objs, float scene_R, 
     }
 }
 
+const char *bad_material(const pt_object &o) {
+    for (float v : o.color)
+        if (!finite_nonneg(v)) return "color";
+    for (float v : o.emission)
+        if (!finite_nonneg(v)) return "emission";
+    return nullptr;
+}
+
 bool flatten_scene(const pt_camera &cam, const pt_object *objs, uint32_t n_objs, const pt_triangle *tris,
                    uint32_t n_tris, FlatScene &out, std::string &err, const Reach *origin_box, Reach *used) {
     if (n_objs >= (1u << 30) || n_tris >= (1u << 30)) {
@@ -629,6 +637,10 @@ bool flatten_scene(const pt_camera &cam, const pt_object *objs, uint32_t n_objs,
         }
         if (o.reflect_type > PT_REFRACT) {
             err = "object " + std::to_string(i) + ": unknown reflect_type";
+            return false;
+        }
+        if (const char *field = bad_material(o)) {
+            err = "object " + std::to_string(i) + ": a component of " + field + " is negative or not finite";
             return false;
         }
         ObjRec &r = out.objs[i];
@@ -749,6 +761,8 @@ int check_object_edit(bool has_ctx, const pt_object *obj, bool has_scene, const 
                          obj->bs_center[0], obj->bs_center[1], obj->bs_center[2], obj->bs_radius};
     for (float v : geo)
         if (!std::isfinite(v)) return refuse("a position, radius, bs_center or bs_radius that is not finite");
+    if (const char *field = bad_material(*obj))
+        return refuse((std::string("a component of ") + field + " is negative or not finite").c_str());
     return PT_OK;
 }
 

@@ -121,6 +121,10 @@ void scene_reach(const pt_camera &cam, const pt_object *objs, uint32_t n_objs, c
 // pt_ctx_set_camera's growth rule, in binary32: a bound the lens centre violates moves beyond it by the overshoot once more
 // (lo = lens - (lo - lens), hi = lens + (lens - hi)), the others stay.  True when B changed (the lens centre was outside).
 bool grow_reach(Reach &B, const float lens[3]);
+// The material at the door (pt_ctx_set_scene, pt_render, pt_ctx_set_object): "color" or "emission" when a component of it is
+// negative or not finite (a NaN among them; -0.0f passes), nullptr when both are fine.  The kernels' to_fixed (pt_device.h) is
+// only defined for finite v >= 0, and throughput and contributions are products of these components.
+const char *bad_material(const pt_object &o);
 // `origin_box` (optional): the bounds are derived for scene_reach's box united with it - what the call computes without one
 // when the box lies inside scene_reach's
 bool flatten_scene(const pt_camera &cam, const pt_object *objs, uint32_t n_objs, const pt_triangle *tris,

@@ -240,6 +240,21 @@ int main(int argc, char **argv) {
             CHECK(refused(host::check_object_edit(true, &bad, true, objs, 2, 1), "not finite"));
             *f = keep;
         }
+        // the material, last: a component of color or emission that is negative or not finite, the message naming the field
+        for (int k = 0; k < 6; ++k) {
+            float *f = k < 3 ? &bad.color[k] : &bad.emission[k - 3];
+            const float keep = *f;
+            for (float v : {-1.0f, -1e-45f, NAN, INFINITY, -INFINITY}) {
+                *f = v;
+                CHECK(refused(host::check_object_edit(true, &bad, true, objs, 2, 1), k < 3 ? "of color is negative or not finite"
+                                                                                           : "of emission is negative or not finite"));
+            }
+            for (float v : {-0.0f, 0.0f, 1e-45f, 3e38f}) {
+                *f = v;
+                CHECK(host::check_object_edit(true, &bad, true, objs, 2, 1) == PT_OK);
+            }
+            *f = keep;
+        }
         CHECK(host::check_object_edit(true, &bad, true, objs, 2, 1) == PT_OK);
     }
     // ---- 2. the reach test at its edges and the growth rule

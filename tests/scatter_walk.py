@@ -1,7 +1,8 @@
 """The oracle's paths with their keys (pto_dump_paths) for the frames the scatter tests walk, computed once per process: every
 ray of every path, its (pixel, sample, depth, branch), its pto_intersect_batch hit, and its children - the dumped rays with the
 same pixel and sample, depth + 1 and branch b (one child) or 2b and 2b + 1 (a split).  tests/test_oracle.py holds the oracle to
-tests/kats_scatter.py on them, tests/test_gpu_scatter.py holds the device (pt_ctx_scatter) to the oracle."""
+tests/kats_scatter.py on them, tests/test_gpu_scatter.py holds the device (pt_ctx_scatter) to the oracle.  A walk is of SEED
+unless another is asked for (tests/frame_sums.py walks one frame at a seed above 2^32); W.seed says which."""
 import ctypes as C
 import functools
 
@@ -19,8 +20,8 @@ class Walk:
     pass
 
 
-def walk(sid, width, height, spp):
-    return walk_scene(_scene(sid), width, height, spp)
+def walk(sid, width, height, spp, seed=SEED):
+    return walk_scene(_scene(sid), width, height, spp, seed)
 
 
 @functools.lru_cache(maxsize=None)
@@ -29,17 +30,17 @@ def _scene(sid):
 
 
 @functools.lru_cache(maxsize=None)
-def walk_scene(sc, width, height, spp):
+def walk_scene(sc, width, height, spp, seed=SEED):
     L = ptlib.oracle()
     cap = width * height * spp * 64  # a path holds at most 4 branches of 12 rays
     rays = np.zeros((cap, 6), np.float32)
     keys = np.zeros((cap, 4), np.uint32)
-    cfg = ptlib.PtoConfig(width, height, spp, 0, SEED)
+    cfg = ptlib.PtoConfig(width, height, spp, 0, seed)
     ps = sc.pto()
     n = L.pto_dump_paths(C.byref(ps), C.byref(cfg), 0, width * height, ptlib._np_f(rays), keys.ctypes.data_as(ptlib.u32p), cap)
     assert 0 < n < cap
     W = Walk()
-    W.scene, W.n, W.width, W.height, W.spp = sc, int(n), width, height, spp
+    W.scene, W.n, W.width, W.height, W.spp, W.seed = sc, int(n), width, height, spp, seed
     W.o, W.d, W.keys = rays[:n, :3].copy(), rays[:n, 3:].copy(), keys[:n].copy()
     W.t, W.oid, W.tid, W.x, W.nrm = ptlib.oracle_intersect(sc, W.o, W.d)
     W.index = {tuple(int(v) for v in k): i for i, k in enumerate(W.keys)}

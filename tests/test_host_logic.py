@@ -300,6 +300,73 @@ def test_flat_filter_sign_rule_needs_well_shaped_triangles(tmp_path):
     assert subprocess.check_output([exe, "1"]).decode().split() == ["OK", "axis", "2", "sign_exact", "0"]
 
 
+DOOR_SRC = r"""
+#include <cmath>
+#include <cstdio>
+#include <string>
+#include <vector>
+#include "ptrace.h"
+#include "pt_host.h"
+using namespace pt;
+// a sphere and a two-triangle mesh; each colour and emission component of each object in turn set to a value the door must
+// refuse (the message names the object and the field) or must let through
+int main() {
+    pt_camera cam = {{0, 0, 5}, {0, 0, -1}, 0.035f, 0.036f, 1.5f};
+    std::vector<pt_triangle> tris = {{{0, 0, 1}, {1, 0, 1}, {0, 1, 1}}, {{1, 0, 1}, {1, 1, 1}, {0, 1, 1}}};
+    pt_object objs[2] = {};
+    objs[0].kind = PT_SPHERE, objs[0].radius = 1.0f, objs[0].position[2] = -3.0f;
+    objs[1].kind = PT_MESH, objs[1].tri_count = 2, objs[1].bs_radius = 100.0f;
+    for (pt_object &o : objs) o.color[0] = 0.75f, o.color[1] = 0.5f, o.color[2] = 0.25f, o.emission[1] = 12.0f;
+    host::FlatScene fs;
+    std::string err;
+    if (!host::flatten_scene(cam, objs, 2, tris.data(), 2, fs, err)) { printf("FAIL clean scene: %s\n", err.c_str()); return 1; }
+    const float bad[] = {-1.0f, -1e-45f, NAN, INFINITY, -INFINITY}, fine[] = {-0.0f, 0.0f, 1e-45f, 4294967296.0f, 3e38f};
+    int refusals = 0;
+    for (int i = 0; i < 2; ++i)
+        for (int k = 0; k < 6; ++k) {
+            float *f = k < 3 ? &objs[i].color[k] : &objs[i].emission[k - 3];
+            const float keep = *f;
+            const std::string want = "object " + std::to_string(i) + ": a component of " + (k < 3 ? "color" : "emission") +
+                                     " is negative or not finite";
+            for (float v : bad) {
+                *f = v;
+                err.clear();
+                if (host::flatten_scene(cam, objs, 2, tris.data(), 2, fs, err) || err != want) {
+                    printf("FAIL object %d field %d value %g: `%s`\n", i, k, v, err.c_str());
+                    return 1;
+                }
+                if (host::bad_material(objs[i]) == nullptr) { printf("FAIL bad_material %d %d %g\n", i, k, v); return 1; }
+                ++refusals;
+            }
+            for (float v : fine) {
+                *f = v;
+                if (!host::flatten_scene(cam, objs, 2, tris.data(), 2, fs, err)) { printf("FAIL refused %g: %s\n", v, err.c_str()); return 1; }
+            }
+            *f = keep;
+        }
+    printf("OK %d\n", refusals);
+    return 0;
+}
+"""
+
+
+def test_the_door_refuses_negative_and_non_finite_materials(tmp_path):
+    """flatten_scene - what pt_ctx_set_scene, and through it pt_render and pt_render_multi, build a scene with - refuses a colour
+    or emission component that is negative, NaN or infinite, naming the object and the field, and lets -0.0f, denormals and
+    large finite values through: to_fixed (csrc/pt_device.h) is defined for finite values >= 0 only.  pt_ctx_set_object's
+    refusals (check_object_edit) are in host/object_check.cpp."""
+    import re
+    src = tmp_path / "door.cpp"
+    src.write_text(DOOR_SRC)
+    exe = str(tmp_path / "door")
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-I", os.path.join(ptlib.PKG, "csrc"), "-I", os.path.join(ptlib.ROOT, "include"),
+                           str(src), "-o", exe, "-L", ptlib.PKG, "-lptrace_hip", "-Wl,-rpath," + ptlib.PKG])
+    assert subprocess.check_output([exe]).decode().split() == ["OK", "60"]
+    h = open(os.path.join(ptlib.ROOT, "include", "ptrace.h")).read()
+    assert "a component of color or emission that is negative or not finite" in re.sub(r"\s*\n \* ", " ", h)
+    assert "SATURATES at 4294967040" in h and "WRAPS at 2^32 radiance units" in h
+
+
 PLAN_SRC = r"""
 #include <cstdio>
 #include <cstdlib>
