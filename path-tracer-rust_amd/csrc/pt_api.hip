@@ -1602,6 +1602,7 @@ static int upload_flat(pt_ctx *c, const host::FlatScene &fs, const pt_object *ob
     c->scene.n_cand_pairs = (uint32_t)fs.cand_pairs.size();
     c->scene.n_other_pairs = fs.n_other_pairs;
     c->scene.n_flat_exact = fs.n_flat_exact;
+    for (int k = 0; k < 3; ++k) c->scene.n_flat_exact_axis[k] = fs.n_flat_exact_axis[k];
     c->scene.nodes_in_lds_ok = c->tune.nodes_lds ? 1u : 0u;
     set_glass_defer(c, objs, n_objs);
     c->cand_ok = fs.cand_ok;
@@ -1805,6 +1806,7 @@ static int upload_object_edit(pt_ctx *c, uint32_t index, bool moved, bool materi
             c->scene.n_cand_pairs = (uint32_t)fs.cand_pairs.size();
             c->scene.n_other_pairs = fs.n_other_pairs;
             c->scene.n_flat_exact = fs.n_flat_exact;
+            for (int k = 0; k < 3; ++k) c->scene.n_flat_exact_axis[k] = fs.n_flat_exact_axis[k];
             c->cand_ok = fs.cand_ok;
             c->scene.cand_scan = cand_scan_for(c, 0u);
             c->table_count[PT_TABLE_SPH_PAIRS] = fs.sph_pairs.size();

@@ -19,6 +19,8 @@
 
 #include "pt_math.h"
 
+#include <type_traits>
+
 namespace pt {
 
 constexpr uint32_t kKindSphere = 0u, kKindMesh = 1u;
@@ -234,6 +236,7 @@ struct DevScene {
     uint32_t n_sph_pairs, n_flat_pairs, n_cand_pairs;
     uint32_t n_other_pairs;         // cand_pairs [0, n_other_pairs) have no filter: candidates for every ray
     uint32_t n_flat_exact;          // flat_pairs [0, n_flat_exact) have sign_exact set
+    uint32_t n_flat_exact_axis[3];  // ... of which so many lie on the x, y, z axis, in that order in the table
     uint32_t glass_defer_ok;        // k_pass_cand may defer glass hits to dense batches (PT_GLASS_DEFER=1; default: shaded in place)
     uint32_t nodes_in_lds_ok;       // k_pass_cand with walks may stage the BVH nodes in LDS when they fit (PT_NODES_LDS=0: never)
     uint32_t cand_scan;             // 1: k_pass uses the candidate scan
@@ -487,6 +490,61 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ f32x2 splat2(float v) {
     f32x2 r = {v, v};
     return r;
+}
+// A ray in registers AS IT IS STORED - on a wave's stack (load_ray_slice / store_ray) and in a chunk's LDS slot (CandLds::ray_a,
+// ray_b): the 16-byte row (o.x, o.y, o.z, d.x) and the 8-byte row (d.y, d.z).  A row that is loaded as four (two) consecutive
+// registers and written to LDS as such needs no move in between, and a packed operand "component c in both halves" is a shuffle of the
+// NATURAL PAIR that holds c - (o.x, o.y), (o.z, d.x), (d.y, d.z) - which instruction selection folds into the op_sel / op_sel_hi
+// bits of the v_pk_* instruction: no second register per component (splat2 of a scalar costs a v_mov and a VGPR each).
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+struct RayRows {
+    f32x2 p0, p1;  // the 16-byte row: (o.x, o.y), (o.z, d.x)
+    f32x2 p2;      // the 8-byte row: (d.y, d.z)
+};
+enum : int { kRayOx = 0, kRayOy, kRayOz, kRayDx, kRayDy, kRayDz };  // component numbers of ray_get / ray_rep
+__device__ __forceinline__ RayRows ray_rows(vec3 o, vec3 d) {
+    RayRows r;
+    r.p0 = f32x2{o.x, o.y};
+    r.p1 = f32x2{o.z, d.x};
+    r.p2 = f32x2{d.y, d.z};
+    return r;
+}
+template <int C>
+__device__ __forceinline__ float ray_get(const RayRows &r) {
+    static_assert(C >= 0 && C < 6, "o.x, o.y, o.z, d.x, d.y, d.z");
+    if constexpr (C < 2)
+        return r.p0[C];
+    else if constexpr (C < 4)
+        return r.p1[C - 2];
+    else
+        return r.p2[C - 4];
+}
+// The shuffles only fold when they are selected in the basic block of the instruction that uses them.  Written once in front
+// of a loop over scene records - or hoisted there by the compiler, they are loop invariant - they become six splat pairs again
+// (so does a row held as ONE four-vector: its halves are shuffles of their own).  So a loop's body starts with pin_rows(): an empty
+// asm that hands each pair back in the registers it came in (no instruction), behind which the compiler cannot tell that the pair
+// is the same in every iteration.  (The empty asm on the SPLAT, tried first, forces it into registers of its own instead: more
+// moves than without it.)
+__device__ __forceinline__ void pin_pair(f32x2 &p) { asm volatile("" : "+v"(p)); }
+__device__ __forceinline__ void pin_rows(RayRows &r) {
+    pin_pair(r.p0);
+    pin_pair(r.p1);
+    pin_pair(r.p2);
+}
+// half H of pair p in both halves
+template <int H>
+__device__ __forceinline__ f32x2 rep2(f32x2 p) {
+    return __builtin_shufflevector(p, p, H, H);
+}
+template <int C>
+__device__ __forceinline__ f32x2 ray_rep(const RayRows &r) {
+    static_assert(C >= 0 && C < 6, "o.x, o.y, o.z, d.x, d.y, d.z");
+    if constexpr (C < 2)
+        return rep2<C>(r.p0);
+    else if constexpr (C < 4)
+        return rep2<C - 2>(r.p1);
+    else
+        return rep2<C - 4>(r.p2);
 }
 // Load of a scene-table record whose index is the same for the whole wave.  The scene tables are written once by
 // pt_ctx_set_scene and never by a kernel, so the load goes through the constant address space: the backend then
@@ -1554,18 +1612,24 @@ struct CandRing {
 // with (A_a - o_a) * sign(d_a) <= 0 (an underflow to zero only rejects more).  For such records the filter keeps a ray only
 // if (plane - origin) * sign(d_a) > 0: about two thirds of the self-candidates go (the origin is on the inner side of the plane,
 // or exactly on it).
+// The ray comes as its rows (RayRows), the reciprocals of its direction and the bound as the pairs (inv.x, inv.y), (inv.z, bound):
+// every packed operand below is a half of one of those five pairs, picked by op_sel.
 template <int AXIS, bool EXACT>
-__device__ __forceinline__ void filter_flat(const FlatPairRec &f, vec3 o, vec3 d, vec3 inv, float bound, uint64_t valid_m,
+__device__ __forceinline__ void filter_flat(const FlatPairRec &f, const RayRows &ray, f32x2 inv_xy, f32x2 inv_zb, uint64_t valid_m,
                                             uint64_t graze, uint64_t *m0, uint64_t *m1) {
-    const float oa = AXIS == 0 ? o.x : (AXIS == 1 ? o.y : o.z), ob = AXIS == 0 ? o.y : (AXIS == 1 ? o.z : o.x),
-                oc = AXIS == 0 ? o.z : (AXIS == 1 ? o.x : o.y);
-    const float db = AXIS == 0 ? d.y : (AXIS == 1 ? d.z : d.x), dc = AXIS == 0 ? d.z : (AXIS == 1 ? d.x : d.y);
-    const float ia = AXIS == 0 ? inv.x : (AXIS == 1 ? inv.y : inv.z);
-    const f32x2 tv = ld2(f.pc) - splat2(oa);  // -(tvec_a) of mod.rs:577: exact sign, zero iff the origin is on the plane
-    const f32x2 t2 = tv * splat2(ia);         // distance to the plane (approximate reciprocal)
-    const f32x2 yb = __builtin_elementwise_fma(splat2(db), t2, splat2(ob)) - ld2(f.cb);
-    const f32x2 zc = __builtin_elementwise_fma(splat2(dc), t2, splat2(oc)) - ld2(f.cc);
-    const f32x2 lim = splat2(bound) + ld2(f.tpad);
+    constexpr int A = AXIS, B = (AXIS + 1) % 3, C = (AXIS + 2) % 3;
+    const f32x2 oa = ray_rep<kRayOx + A>(ray), ob = ray_rep<kRayOx + B>(ray), oc = ray_rep<kRayOx + C>(ray);
+    const f32x2 db = ray_rep<kRayDx + B>(ray), dc = ray_rep<kRayDx + C>(ray);
+    f32x2 ia;
+    if constexpr (A < 2)
+        ia = rep2<A>(inv_xy);
+    else
+        ia = rep2<0>(inv_zb);
+    const f32x2 tv = ld2(f.pc) - oa;  // -(tvec_a) of mod.rs:577: exact sign, zero iff the origin is on the plane
+    const f32x2 t2 = tv * ia;         // distance to the plane (approximate reciprocal)
+    const f32x2 yb = __builtin_elementwise_fma(db, t2, ob) - ld2(f.cb);
+    const f32x2 zc = __builtin_elementwise_fma(dc, t2, oc) - ld2(f.cc);
+    const f32x2 lim = rep2<1>(inv_zb) + ld2(f.tpad);
     uint64_t in[2];
     if (EXACT) {  // (records with FlatPairRec.sign_exact: a loop of their own, cand_filter_and_drain)
 #pragma unroll
@@ -1590,14 +1654,16 @@ __device__ __forceinline__ void filter_flat(const FlatPairRec &f, vec3 o, vec3 d
 }
 
 // intersect_sphere against the scene's spheres (mod.rs:412-427), two per record, in visiting order (strict '<' keeps
-// the first): the ray's first key
-__device__ __forceinline__ unsigned long long cand_spheres(const DevScene &S, vec3 o, vec3 d, float *best_out) {
+// the first): the ray's first key.  (`r` comes back as it went in: it is pinned - pin_pair - in place, in the caller's own registers,
+// where a copy to pin costs three moves in front of the loop.)
+__device__ __forceinline__ unsigned long long cand_spheres(const DevScene &S, RayRows &r, float *best_out) {
     float best_t = __builtin_inff();
     uint32_t best_rank = 0xffffffffu;
-    const f32x2 ox2 = splat2(o.x), oy2 = splat2(o.y), oz2 = splat2(o.z);
-    const f32x2 dx2 = splat2(d.x), dy2 = splat2(d.y), dz2 = splat2(d.z);
     for (uint32_t p = 0; p < S.n_sph_pairs; ++p) {
         const SphPairRec sp = ld_uniform(S.sph_pairs + p);
+        pin_rows(r);
+        const f32x2 ox2 = ray_rep<kRayOx>(r), oy2 = ray_rep<kRayOy>(r), oz2 = ray_rep<kRayOz>(r);
+        const f32x2 dx2 = ray_rep<kRayDx>(r), dy2 = ray_rep<kRayDy>(r), dz2 = ray_rep<kRayDz>(r);
         const f32x2 opx = ld2(sp.cx) - ox2, opy = ld2(sp.cy) - oy2, opz = ld2(sp.cz) - oz2;
         const f32x2 b = (opx * dx2 + opy * dy2) + opz * dz2;
         const f32x2 det = (b * b - ((opx * opx + opy * opy) + opz * opz)) + ld2(sp.rr);
@@ -1619,6 +1685,11 @@ __device__ __forceinline__ unsigned long long cand_spheres(const DevScene &S, ve
     }
     *best_out = best_t;
     return ((unsigned long long)__float_as_uint(best_t) << 32) | best_rank;
+}
+// (for a caller that holds the ray as two vec3 and starts no chunk: the shuffles of the rows built here are plain splats again)
+__device__ __forceinline__ unsigned long long cand_spheres(const DevScene &S, vec3 o, vec3 d, float *best_out) {
+    RayRows r = ray_rows(o, d);
+    return cand_spheres(S, r, best_out);
 }
 // (Round 4 tried to run the tail - square root, two roots, the 1e-4 tests - once per trip instead of once per sphere: a lane
 // NOTES the sphere whose discriminant is non-negative (b, det, rank) and the tail runs after the last record, and in between
@@ -1673,9 +1744,11 @@ __device__ __forceinline__ void cand_batch(const DevScene &S, const CandLds &L, 
 
 // Filters of the current chunk's ray (o, d; `valid` lanes) -> ring; full batches are run as they fill up.  `par` is the
 // chunk's parity (its slots).
+// The chunk's lanes come as the MASK valid_m (the caller's `lane < cnt` is one compare into an SGPR pair; a bool parameter is turned
+// into a VGPR 0 / 1 and back), the ray as its rows.
 template <bool STAGED>
 __device__ __forceinline__ void cand_filter_and_drain(const DevScene &S, const CandLds &L, CandRing &R, uint32_t lane,
-                                                      uint32_t par, bool valid, vec3 o, vec3 d, float bound) {
+                                                      uint32_t par, uint64_t valid_m, const RayRows &ray, float bound) {
     // both halves of a filter record in one step: entries of half 0 first, then half 1.  (Collecting the filters' verdicts as
     // bits per lane and writing the set bits to the ring one per lane at a time - fewer ballot / prefix rounds when every
     // lane has one or two candidates - was tried: the rounds follow the lane with the most candidates; cornell 36.8
@@ -1709,38 +1782,49 @@ __device__ __forceinline__ void cand_filter_and_drain(const DevScene &S, const C
 #endif
     };
     PT_PHASE(kPhFilter);
-    const vec3 inv = mk(__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y), __builtin_amdgcn_rcpf(d.z));
+    const float dx = ray_get<kRayDx>(ray), dy = ray_get<kRayDy>(ray), dz = ray_get<kRayDz>(ray);
+    // the reciprocals of the direction and the bound as two pairs (filter_flat)
+    f32x2 inv_xy = {__builtin_amdgcn_rcpf(dx), __builtin_amdgcn_rcpf(dy)};
+    f32x2 inv_zb = {__builtin_amdgcn_rcpf(dz), bound};
+    RayRows r = ray;
     // (Noting a lane's first two candidate records in registers while the filters run and pushing twice at the end of the
     // loop instead of twice per record - a third candidate pushed on the spot - was built and measured: some lane of a wave
     // nearly always grazes a plane (|d_a| < 1/64 makes it a candidate of both halves of that axis' record), so the "rare"
     // third-candidate push runs in most trips on top of the two at the end: cornell 36.3 against 39.6 G bounces/s.)
-    const uint64_t valid_m = __builtin_amdgcn_ballot_w64(valid);
     // rays that graze the planes of an axis (|d_a| < kGrazing, or NaN): not judged by the filters of that axis
-    const uint64_t gz_x = __builtin_amdgcn_ballot_w64(!(f_abs(d.x) >= kGrazing)), gz_y = __builtin_amdgcn_ballot_w64(!(f_abs(d.y) >= kGrazing)),
-                   gz_z = __builtin_amdgcn_ballot_w64(!(f_abs(d.z) >= kGrazing));
+    const uint64_t gz_x = __builtin_amdgcn_ballot_w64(!(f_abs(dx) >= kGrazing)), gz_y = __builtin_amdgcn_ballot_w64(!(f_abs(dy) >= kGrazing)),
+                   gz_z = __builtin_amdgcn_ballot_w64(!(f_abs(dz) >= kGrazing));
     // (Issuing the next record's scalar load before this record's arithmetic - a second sixteen-register tuple - was measured in
     // round 4: 44.3 against 47.2 G bounces/s; the kernel is short of scalar registers, not of time to wait for them.)
-    for (uint32_t p = 0; p < S.n_flat_exact; ++p) {  // the records with the exact sign rule (the host puts them first)
+    // ONE LOOP PER AXIS for the records with the exact sign rule (every wall of a room): flatten_scene lays the table out as exact x, y,
+    // z, then the others (DevScene.n_flat_exact_axis), so their `axis` is not looked at - three scalar compares and branches per
+    // record that sat between the record's s_waitcnt and its first VALU instruction.  The loop's operands are pinned in its body:
+    // see pin_pair.
+    uint32_t p = 0;
+    auto run_axis = [&](auto axis, uint32_t n, uint64_t graze) {
+        for (const uint32_t end = p + n; p < end; ++p) {
+            const FlatPairRec f = ld_uniform(S.flat_pairs + p);
+            pin_rows(r), pin_pair(inv_xy), pin_pair(inv_zb);
+            uint64_t m0, m1;
+            filter_flat<decltype(axis)::value, true>(f, r, inv_xy, inv_zb, valid_m, graze, &m0, &m1);
+            push2(m0, f.pair[0], m1, f.pair[1]);
+            drain();
+        }
+    };
+    run_axis(std::integral_constant<int, 0>(), S.n_flat_exact_axis[0], gz_x);
+    run_axis(std::integral_constant<int, 1>(), S.n_flat_exact_axis[1], gz_y);
+    run_axis(std::integral_constant<int, 2>(), S.n_flat_exact_axis[2], gz_z);
+    // the other filter records (slivers: rare) share one loop - every loop here holds a copy of the batch, 320 VALU instructions
+    for (; p < S.n_flat_pairs; ++p) {
         const FlatPairRec f = ld_uniform(S.flat_pairs + p);
+        pin_rows(r), pin_pair(inv_xy), pin_pair(inv_zb);
         uint64_t m0, m1;
         if (f.axis == 0u)
-            filter_flat<0, true>(f, o, d, inv, bound, valid_m, gz_x, &m0, &m1);
+            filter_flat<0, false>(f, r, inv_xy, inv_zb, valid_m, gz_x, &m0, &m1);
         else if (f.axis == 1u)
-            filter_flat<1, true>(f, o, d, inv, bound, valid_m, gz_y, &m0, &m1);
+            filter_flat<1, false>(f, r, inv_xy, inv_zb, valid_m, gz_y, &m0, &m1);
         else
-            filter_flat<2, true>(f, o, d, inv, bound, valid_m, gz_z, &m0, &m1);
-        push2(m0, f.pair[0], m1, f.pair[1]);
-        drain();
-    }
-    for (uint32_t p = S.n_flat_exact; p < S.n_flat_pairs; ++p) {
-        const FlatPairRec f = ld_uniform(S.flat_pairs + p);
-        uint64_t m0, m1;
-        if (f.axis == 0u)
-            filter_flat<0, false>(f, o, d, inv, bound, valid_m, gz_x, &m0, &m1);
-        else if (f.axis == 1u)
-            filter_flat<1, false>(f, o, d, inv, bound, valid_m, gz_y, &m0, &m1);
-        else
-            filter_flat<2, false>(f, o, d, inv, bound, valid_m, gz_z, &m0, &m1);
+            filter_flat<2, false>(f, r, inv_xy, inv_zb, valid_m, gz_z, &m0, &m1);
         push2(m0, f.pair[0], m1, f.pair[1]);
         drain();
     }
@@ -1748,6 +1832,12 @@ __device__ __forceinline__ void cand_filter_and_drain(const DevScene &S, const C
         push2(valid_m, q, 0ull, 0u);
         drain();
     }
+}
+// (for a caller that holds the ray as two vec3 and its lanes as a bool)
+template <bool STAGED>
+__device__ __forceinline__ void cand_filter_and_drain(const DevScene &S, const CandLds &L, CandRing &R, uint32_t lane,
+                                                      uint32_t par, bool valid, vec3 o, vec3 d, float bound) {
+    cand_filter_and_drain<STAGED>(S, L, R, lane, par, (uint64_t)__builtin_amdgcn_ballot_w64(valid), ray_rows(o, d), bound);
 }
 
 // The BVH walks of a ray whose other objects are done (best_t / best_id hold their winner): every mesh with a BVH, in

@@ -583,6 +583,10 @@ static void derive_small(const pt_object *objs, uint32_t n_objs, float scene_R, 
         out.n_flat_exact = (uint32_t)(std::stable_partition(out.flat_pairs.begin(), out.flat_pairs.end(),
                                                             [](const FlatPairRec &f) { return f.sign_exact != 0u; }) -
                                       out.flat_pairs.begin());
+        // by_axis went in x, y, z and the partition is stable: the exact records are sorted by axis, and the kernels run one loop
+        // per axis over them without looking at a record's `axis` (cand_filter_and_drain)
+        for (uint32_t &n : out.n_flat_exact_axis) n = 0u;
+        for (uint32_t k = 0; k < out.n_flat_exact; ++k) ++out.n_flat_exact_axis[out.flat_pairs[k].axis];
         out.n_other_pairs = (uint32_t)out.cand_pairs.size();
         for (FlatPairRec &f : out.flat_pairs)
             for (int hf = 0; hf < 2; ++hf)

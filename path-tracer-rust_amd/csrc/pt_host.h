@@ -39,6 +39,8 @@ struct FlatScene {
                                      // (kRefitNone: an absent child) - what a refit's gather reads (build_refit_plan)
     uint32_t n_other_pairs = 0;
     uint32_t n_flat_exact = 0;  // flat_pairs [0, n_flat_exact) have sign_exact set (they come first)
+    uint32_t n_flat_exact_axis[3] = {0, 0, 0};  // ... of which so many lie on the x, y, z axis, in that order in the table (the
+                                                // kernels run one loop per axis over them)
     bool cand_ok = false;  // the scene can use the candidate scan (the records of its meshes without a BVH are numbered in
                            // 9 bits; meshes with a BVH are walked: k_pass_cand<.., BVH>)
     uint32_t bvh_stack = 0;      // traversal-stack entries the deepest tree needs (<= kBvhStack)

@@ -115,6 +115,15 @@ __device__ __forceinline__ void load_ray_slice(const StreamSlice &q, uint32_t i,
     thr = mk(tp.x, tp.y, tp.z);
     word = __float_as_uint(tp.w);
 }
+// the same as the rows it is stored in (RayRows; tp = throughput xyz and the bookkeeping word's bits): the registers the three loads
+// fill are the ones the chunk's LDS slot is written from and the packed tests read their operands from
+__device__ __forceinline__ void load_ray_slice(const StreamSlice &q, uint32_t i, RayRows &ray, f32x4 &tp) {
+    const f32x2 *a = reinterpret_cast<const f32x2 *>(q.base + i * 16u);
+    ray.p0 = a[0];
+    ray.p1 = a[1];
+    tp = *reinterpret_cast<const f32x4 *>(q.base + (i * 16u + q.off_tp));
+    ray.p2 = *reinterpret_cast<const f32x2 *>(q.base + (i * 8u + q.off_od1));
+}
 
 #ifndef PT_TU_PART  // (the units that hold a part of this file - pt_kernels_flat.hip, pt_kernels_tile.hip - do not hold this)
 // ------------------------------------------------------------------------------------------------
@@ -923,10 +932,14 @@ __global__ __launch_bounds__(kBlock, BVH ? PT_CAND_BVH_WAVES : PT_CAND_WAVES) vo
         const uint32_t pend_entries = ring.count;  // candidate entries of the chunk to finish that are still queued (< 64)
         bool ran_batch = false;
         if (src != 0u) {
-            PathRay in;
-            in.o = in.d = in.thr = mk(0.0f, 0.0f, 0.0f);
+            RayRows ray;
             if (src == 2u) {  // render_pixel's rays for (pixel, sample) = (g % mb, s0 + g / mb), g = this wave's next 64 indices
                 PT_PHASE(kPhPrimary);
+                // (a lane past a partial chunk of primaries holds zeros: its pixel and sample indices are past the stream's, so there
+                // is no lane's ray to repeat as below without a clamp of both and a second set of table reads - one trip in nine
+                // starts primaries, and only a stream's last one is partial)
+                PathRay in;
+                in.o = in.d = in.thr = mk(0.0f, 0.0f, 0.0f);
                 if (cur_valid) {
                     const uint32_t pj = gen_pj, sj = gen_sj;
                     FrameParams Fl;  // (the fields primary_ray_at reads)
@@ -957,24 +970,34 @@ __global__ __launch_bounds__(kBlock, BVH ? PT_CAND_BVH_WAVES : PT_CAND_WAVES) vo
                 }
 #endif
                 gen_left = rfl(gen_left - cnt);
+                ray = ray_rows(in.o, in.d);
+                cur_thr = in.thr;
             } else {
                 PT_PHASE(kPhLoad);
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // (the wave's own stores, read back by other lanes)
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
                 top = rfl(top - cnt);
-                if (cur_valid) load_ray_slice(qs, top + lane, in.o, in.d, in.thr, word);
+                // NO ZERO-FILL AND NO MASKED LOAD: a lane past the chunk (cnt < 64: a wave's last trips) loads the chunk's last ray
+                // again.  It can never reach a result: its key is kKeyMiss (below), valid_m masks it out of every filter, so no
+                // candidate entry names its slot, and prev_valid keeps it from shading and appending in the next trip.  What it
+                // does take part in are the wave-wide ballots of cand_spheres - and there it votes as the lane it repeats does:
+                // no sphere tail runs that would not run anyway, and no value enters the wave that a valid lane does not hold (no
+                // f_sqrt slow path of its own either).
+                f32x4 tp;
+                load_ray_slice(qs, top + (lane < cnt - 1u ? lane : cnt - 1u), ray, tp);
+                cur_thr = mk(tp[0], tp[1], tp[2]);
+                word = __float_as_uint(tp[3]);
             }
             total += cnt;
-            cur_thr = in.thr;
             const uint32_t slot = (par << 6) | lane;
-            cand.ray_a[slot] = make_float4(in.o.x, in.o.y, in.o.z, in.d.x);
-            cand.ray_b[slot] = make_float2(in.d.y, in.d.z);
+            cand.ray_a[slot] = make_float4(ray.p0[0], ray.p0[1], ray.p1[0], ray.p1[1]);
+            cand.ray_b[slot] = make_float2(ray.p2[0], ray.p2[1]);
             float bound;
             PT_PHASE(kPhSpheres);
-            const unsigned long long key0 = cand_spheres(S, in.o, in.d, &bound);
+            const unsigned long long key0 = cand_spheres(S, ray, &bound);
             cand.keys[slot] = cur_valid ? key0 : kKeyMiss;
             const uint32_t before = ring.head;
-            cand_filter_and_drain<STAGED>(S, cand, ring, lane, par, cur_valid, in.o, in.d, bound);
+            cand_filter_and_drain<STAGED>(S, cand, ring, lane, par, __builtin_amdgcn_uicmp(lane, cnt, 36 /* ult */), ray, bound);
             ran_batch = ring.head != before;
         }
         if (pending) {

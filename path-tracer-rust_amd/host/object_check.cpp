@@ -5,6 +5,8 @@
 // normals equal and every box conservative on inexact moves; two meshes with a BVH, of which only the moved one changes.  A
 // failed check or a sanitizer report ends it with a non-zero status.
 // argv[1]: the directory that holds meshes/ (the built-in "mesh" scene loads its OFF file from there).
+#include <algorithm>
+
 #include "check_common.h"
 #include "../csrc/pt_host.h"
 
@@ -112,7 +114,8 @@ static bool same_tables(const FlatScene &a, const FlatScene &b) {
              {"surf", same_table(a.surf, b.surf)},
              {"tri_rank", same_table(a.tri_rank, b.tri_rank)},
              {"bvh_meshes", same_table(a.bvh_meshes, b.bvh_meshes)},
-             {"the counts", a.n_other_pairs == b.n_other_pairs && a.n_flat_exact == b.n_flat_exact && a.cand_ok == b.cand_ok}};
+             {"the counts", a.n_other_pairs == b.n_other_pairs && a.n_flat_exact == b.n_flat_exact &&
+                  std::equal(a.n_flat_exact_axis, a.n_flat_exact_axis + 3, b.n_flat_exact_axis) && a.cand_ok == b.cand_ok}};
     for (const auto &x : t)
         if (!x.same) {
             fprintf(stderr, "same_tables: %s differ\n", x.name);
@@ -125,7 +128,8 @@ static bool same_tables(const FlatScene &a, const FlatScene &b) {
 static bool same_small_tables(const FlatScene &a, const FlatScene &b) {
     return same_table(a.mats, b.mats) && same_table(a.tri_shade, b.tri_shade) && same_table(a.sph_pairs, b.sph_pairs) &&
            same_table(a.flat_pairs, b.flat_pairs) && same_table(a.cand_pairs, b.cand_pairs) && same_table(a.surf, b.surf) &&
-           a.n_other_pairs == b.n_other_pairs && a.n_flat_exact == b.n_flat_exact && a.cand_ok == b.cand_ok;
+           a.n_other_pairs == b.n_other_pairs && a.n_flat_exact == b.n_flat_exact &&
+           std::equal(a.n_flat_exact_axis, a.n_flat_exact_axis + 3, b.n_flat_exact_axis) && a.cand_ok == b.cand_ok;
 }
 
 // the (bounding) spheres of the objects and of the meshes that have a BVH, and the shortcut radii: no tree enters them
