@@ -7,7 +7,7 @@
 //                                      global memory, pops 64 or starts 64 primary rays (consecutive samples of one pixel,
 //                                      the stream's chunks of 64 dealt to the four waves in turn); BVH meshes: walks parked per wave
 // TWO TRANSLATION UNITS.  This file is compiled twice: as it is (every kernel but the instances of k_pass_cand WITHOUT walks and
-// k_intersect_cand), and through pt_kernels_flat.hip with PT_TU_FLAT defined (those instances alone, five waves per SIMD): the
+// k_intersect_cand), and through pt_kernels_flat.hip with PT_TU_FLAT defined (those instances alone, six waves per SIMD): the
 // two want different instruction scheduling from the back end, and -mllvm options are per compile (Makefile: MLLVM, MLLVM_FLAT).
 // A THIRD UNIT, pt_kernels_tile.hip (PT_TU_TILE), holds the megakernel's two bodies alone, compiled for TileParams (pt_tile.h) under
 // the names k_tile_mega / k_tile_mega_cand: the tile pass of pt_ctx_render_adaptive.  The text the other two units compile is
@@ -122,6 +122,13 @@ __device__ __forceinline__ void load_ray_slice(const StreamSlice &q, uint32_t i,
     ray.p0 = a[0];
     ray.p1 = a[1];
     tp = *reinterpret_cast<const f32x4 *>(q.base + (i * 16u + q.off_tp));
+    ray.p2 = *reinterpret_cast<const f32x2 *>(q.base + (i * 8u + q.off_od1));
+}
+// origin and direction alone: k_pass_cand without walks fetches throughput and word later, straight into the ray's row in LDS
+__device__ __forceinline__ void load_ray_slice(const StreamSlice &q, uint32_t i, RayRows &ray) {
+    const f32x2 *a = reinterpret_cast<const f32x2 *>(q.base + i * 16u);
+    ray.p0 = a[0];
+    ray.p1 = a[1];
     ray.p2 = *reinterpret_cast<const f32x2 *>(q.base + (i * 8u + q.off_od1));
 }
 
@@ -669,7 +676,7 @@ __global__ __launch_bounds__(kBlock, BVH ? PT_CAND_BVH_WAVES : PT_CAND_WAVES) vo
         float *cw = reinterpret_cast<float *>(s_tail_p + 4);
         cw[0] = F.lens_x, cw[1] = F.lens_y, cw[2] = F.lens_z, cw[3] = F.cam_px, cw[4] = F.cam_py, cw[5] = F.cam_pz;
         cw[6] = F.su_x, cw[7] = F.su_y, cw[8] = F.su_z, cw[9] = F.sv_x, cw[10] = F.sv_y, cw[11] = F.sv_z;
-        s_tail_p[16] = F.width, s_tail_p[17] = F.height;
+        s_tail_p[2] = F.width, s_tail_p[3] = F.height;  // (words 2 and 3 are counters of k_pass only)
     }
     // per stream pixel: framebuffer index (the RNG counter), and its column and row from the bottom (render_pixel's x, y,
     // mod.rs:805-806): two divisions here instead of two per primary ray
@@ -723,7 +730,7 @@ __global__ __launch_bounds__(kBlock, BVH ? PT_CAND_BVH_WAVES : PT_CAND_WAVES) vo
         cand.keys = reinterpret_cast<unsigned long long *>(wbase + 128u * 16u);
         cand.ray_b = reinterpret_cast<float2 *>(wbase + 128u * 24u);
         cand.queue = reinterpret_cast<uint16_t *>(wbase + 128u * 32u);
-        char *sbase = cbase + pass_lds_cand_bytes() + (BVH ? pass_cand_bvh_bytes(S) : 0u);
+        char *sbase = cbase + pass_lds_cand_bytes() + pass_lds_wait_bytes(BVH) + (BVH ? pass_cand_bvh_bytes(S) : 0u);
         cand.staged = reinterpret_cast<const CandPairRec *>(sbase);
         cand.surf = S.surf;
         if (STAGED) {  // the workgroup's own copies of the candidate records and (while they fit) of the shading records
@@ -899,7 +906,36 @@ __global__ __launch_bounds__(kBlock, BVH ? PT_CAND_BVH_WAVES : PT_CAND_WAVES) vo
     PT_PHASE(kPhOther);
     uint32_t par = 0u;                      // the slots (LDS) of the chunk started in this trip
     bool pending = false;                   // wave-uniform: the chunk started in the trip before waits to be finished
-    vec3 prev_thr = mk(0.0f, 0.0f, 0.0f);   // what the ray started in the trip before still needs from registers
+    // THE WAITING RAY'S ROW.  A ray's throughput and bookkeeping word are not needed while it is started - only when it is
+    // FINISHED one trip later - and as four registers they rode through the spheres, the filter loops and the exact batches of
+    // two trips.  Without walks they wait in LDS instead: row `tid` of the area behind the per-wave areas (pt_layout.h) belongs
+    // to this lane alone, so the LDS operations of the wave, which are performed in order, need no fence.  ONE row per lane and
+    // no parity: a trip first reads the row of the ray it is about to finish (prev_thr, prev_word: live from here to the append
+    // only) and then writes the row of the ray it has started - which is why a popped ray's throughput row is not loaded with
+    // its origin and direction at the pop but HERE, straight from the stack into the row: the slots the pop has left are still
+    // intact (this trip's append, which may push over them, comes after, and the vector memory operations of a wave are performed
+    // in order).  A trip that starts nothing writes nothing and is followed by one that finishes nothing; a lane past a partial
+    // chunk writes whatever it loads and prev_valid keeps it from shading.  With walks (four waves per SIMD, the LDS spoken for)
+    // the four values stay in registers, carried from trip to trip as before.
+    float4 *const wait_row = reinterpret_cast<float4 *>(reinterpret_cast<char *>(dyn_lds) + pass_lds_wait_offset(m)) + tid;
+    auto gen_advance = [&]() {  // the lane's next primary ray: 256 further on
+#if PT_SAMPLE_MAJOR
+        gen_sj += step_r;
+        gen_pj += step_q;
+        if (gen_sj >= s_here) {
+            gen_sj -= s_here;
+            gen_pj += 1u;
+        }
+#else
+        gen_pj += step_r;
+        gen_sj += step_q;
+        if (gen_pj >= mb) {
+            gen_pj -= mb;
+            gen_sj += 1u;
+        }
+#endif
+    };
+    vec3 prev_thr = mk(0.0f, 0.0f, 0.0f);   // what the ray started in the trip before still needs
     uint32_t prev_word = 0;
     bool prev_valid = false;
     for (;;) {  // one trip: start a chunk of up to 64 rays (filters, candidates), finish the chunk started in the trip before
@@ -948,30 +984,16 @@ __global__ __launch_bounds__(kBlock, BVH ? PT_CAND_BVH_WAVES : PT_CAND_WAVES) vo
                                      c2 = *reinterpret_cast<const float4 *>(s_tail_p + 12);
                         Fl.lens_x = c0.x, Fl.lens_y = c0.y, Fl.lens_z = c0.z, Fl.cam_px = c0.w, Fl.cam_py = c1.x, Fl.cam_pz = c1.y;
                         Fl.su_x = c1.z, Fl.su_y = c1.w, Fl.su_z = c2.x, Fl.sv_x = c2.y, Fl.sv_y = c2.z, Fl.sv_z = c2.w;
-                        Fl.width = s_tail_p[16], Fl.height = s_tail_p[17];
+                        Fl.width = s_tail_p[2], Fl.height = s_tail_p[3];
                         Fl.seed_lo = P.seed_lo, Fl.seed_hi = P.seed_hi;
                     }
                     in = PROBE ? primary_ray<PROBE>(F, lds_pix[pj], s0 + sj) : primary_ray_at(Fl, lds_pix[pj], lds_px[pj], lds_py[pj], s0 + sj);
-                    word = pack_word(pj, sj, PROBE ? F.depth0 : 0u, 1u);
+                    if constexpr (BVH) word = pack_word(pj, sj, PROBE ? F.depth0 : 0u, 1u);
                 }
-#if PT_SAMPLE_MAJOR
-                gen_sj += step_r;
-                gen_pj += step_q;
-                if (gen_sj >= s_here) {
-                    gen_sj -= s_here;
-                    gen_pj += 1u;
-                }
-#else
-                gen_pj += step_r;
-                gen_sj += step_q;
-                if (gen_pj >= mb) {
-                    gen_pj -= mb;
-                    gen_sj += 1u;
-                }
-#endif
+                if constexpr (BVH) gen_advance();  // (without walks: where the row is written, below)
                 gen_left = rfl(gen_left - cnt);
                 ray = ray_rows(in.o, in.d);
-                cur_thr = in.thr;
+                if constexpr (BVH) cur_thr = in.thr;
             } else {
                 PT_PHASE(kPhLoad);
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // (the wave's own stores, read back by other lanes)
@@ -983,10 +1005,14 @@ __global__ __launch_bounds__(kBlock, BVH ? PT_CAND_BVH_WAVES : PT_CAND_WAVES) vo
                 // does take part in are the wave-wide ballots of cand_spheres - and there it votes as the lane it repeats does:
                 // no sphere tail runs that would not run anyway, and no value enters the wave that a valid lane does not hold (no
                 // f_sqrt slow path of its own either).
-                f32x4 tp;
-                load_ray_slice(qs, top + (lane < cnt - 1u ? lane : cnt - 1u), ray, tp);
-                cur_thr = mk(tp[0], tp[1], tp[2]);
-                word = __float_as_uint(tp[3]);
+                if constexpr (BVH) {
+                    f32x4 tp;
+                    load_ray_slice(qs, top + (lane < cnt - 1u ? lane : cnt - 1u), ray, tp);
+                    cur_thr = mk(tp[0], tp[1], tp[2]);
+                    word = __float_as_uint(tp[3]);
+                } else {
+                    load_ray_slice(qs, top + (lane < cnt - 1u ? lane : cnt - 1u), ray);
+                }
             }
             total += cnt;
             const uint32_t slot = (par << 6) | lane;
@@ -1005,6 +1031,19 @@ __global__ __launch_bounds__(kBlock, BVH ? PT_CAND_BVH_WAVES : PT_CAND_WAVES) vo
             // the chunk started in the trip before: its candidates were the oldest entries of the ring; if no full batch ran in
             // this trip (few candidates, or nothing was started) run what is queued now
             if (pend_entries != 0u && !ran_batch) cand_batch<STAGED>(S, cand, ring, lane, ring.count);
+        }
+        if constexpr (!BVH) {  // the row: out with the ray to finish, in with the one started (see "THE WAITING RAY'S ROW")
+            const float4 w = *wait_row;  // (no chunk pending: whatever is there, and nothing reads it)
+            prev_thr = mk(w.x, w.y, w.z);
+            prev_word = __float_as_uint(w.w);
+            if (src == 1u) {  // `top` is still what the pop left
+                *wait_row = ld_tp(qs, top + (lane < cnt - 1u ? lane : cnt - 1u));
+            } else if (src == 2u) {  // (a lane past a partial chunk: indices past the stream's, never used)
+                *wait_row = make_float4(1.0f, 1.0f, 1.0f, __uint_as_float(pack_word(gen_pj, gen_sj, PROBE ? F.depth0 : 0u, 1u)));
+                gen_advance();
+            }
+        }
+        if (pending) {
             PT_PHASE(kPhFinish);
             ShadeOut so;
             so.n_rays = 0;
@@ -1096,8 +1135,10 @@ __global__ __launch_bounds__(kBlock, BVH ? PT_CAND_BVH_WAVES : PT_CAND_WAVES) vo
             shade_deferred(n_defer + lane, lane < c);
         }
         PT_PHASE(kPhOther);
-        prev_thr = cur_thr;
-        prev_word = word;
+        if constexpr (BVH) {
+            prev_thr = cur_thr;
+            prev_word = word;
+        }
         prev_valid = cur_valid;
         pending = src != 0u;
         par = rfl(par ^ 1u);

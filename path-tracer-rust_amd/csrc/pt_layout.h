@@ -15,7 +15,7 @@ namespace pt {
 // waves per SIMD (= workgroups per compute unit) k_pass_cand is compiled for, without walks (pt_kernels_flat.hip) and with: its
 // __launch_bounds__, lds_layout's LDS budget per workgroup and plan_pass's rounds of resident workgroups follow them
 #ifndef PT_CAND_WAVES
-#define PT_CAND_WAVES 5
+#define PT_CAND_WAVES 6
 #endif
 #ifndef PT_ISECT_WAVES
 #define PT_ISECT_WAVES 4  // k_intersect_cand (the flat unit's too)
@@ -26,8 +26,10 @@ namespace pt {
 
 constexpr uint32_t kDeferCap = 128;  // k_pass: deferred glass hits per wave (63 left over + 64 new at most)
 // k_pass LDS: [u64 acc: 3*m][kPassTailWords x u32: counters, camera][u32 pixel index, column, row: 3*m][pad to 16][float4 deferred hits: waves x 3 x kDeferCap]
-// the words between the accumulators and the pixel tables: [0..3] counters, [4..17] the camera for k_pass_cand's primary rays
-constexpr uint32_t kPassTailWords = 20;
+// the words between the accumulators and the pixel tables: [0..3] counters (k_pass_cand: [0..1] the ray count, [2..3] the frame's
+// width and height), [4..15] the camera for k_pass_cand's primary rays.  (Twenty words until k_pass_cand went to six waves per
+// SIMD: the sixteen bytes are what keeps cornell.json's records staged up to 64 pixels per stream - lds_layout's budget.)
+constexpr uint32_t kPassTailWords = 16;
 // u64 slots of the accumulator area: 3*m rounded up to even, so that the words behind it start on a 16-byte boundary whatever m
 // is (k_pass_cand reads the camera from there as three float4: with an odd m - small frames have m = 1 - those were
 // 8-byte-aligned ds_read_b128, which only the hardware's unaligned-DS mode forgives)
@@ -38,11 +40,21 @@ PT_HDC size_t pass_lds_defer_offset(uint32_t m) {
 static_assert(pass_acc_slots(1) == 4u && pass_acc_slots(2) == 6u && (pass_acc_slots(7) * 8u) % 16u == 0u, "tails are 16-byte aligned");
 
 // k_pass_cand LDS: [accumulators, tails, pixel indices as k_pass][per wave: float4 ray_a [128] | u64 key [128] |
-// float2 ray_b [128] | u16 ring [kCandQueueCap]][BVH: walk queues, keys, nodes (below)][staged candidate records][staged surf]
+// float2 ray_b [128] | u16 ring [kCandQueueCap]][without walks: the waiting rays' rows (below)][BVH: walk queues, keys, nodes
+// (below)][staged candidate records][staged surf]
 PT_HDC size_t pass_lds_cand_offset(uint32_t m, bool /*defer*/) { return pass_lds_defer_offset(m); }
 constexpr size_t kCandWaveBytes = 128u * 16u + 128u * 8u + 128u * 8u + kCandQueueCap * 2u;  // 4480
 PT_HDC size_t pass_lds_cand_bytes() { return (size_t)(kBlock / 64u) * kCandWaveBytes; }
 static_assert(kCandWaveBytes % 16u == 0u, "per-wave areas stay 16-byte aligned");
+
+// k_pass_cand WITHOUT walks only, behind the per-wave areas: THE WAITING RAYS' ROWS, one float4 (throughput xyz, bookkeeping word)
+// per lane of the workgroup - what a ray started in one trip needs again when it is finished in the next, kept out of the
+// registers in between.  One row per lane, no parity: a trip reads the row of the ray it finishes and only then writes the row
+// of the ray it has started (k_pass_cand: "THE WAITING RAY'S ROW").  A term of its own, not part of kCandWaveBytes, which
+// k_intersect_cand and k_mega_cand share; the instances with walks keep the four values in registers and have no such area.
+PT_HDC size_t pass_lds_wait_bytes(bool bvh) { return bvh ? 0u : (size_t)kBlock * 16u; }
+PT_HDC size_t pass_lds_wait_offset(uint32_t m) { return pass_lds_cand_offset(m, false) + pass_lds_cand_bytes(); }
+static_assert((pass_lds_wait_offset(1) % 16u) == 0u && (pass_lds_wait_offset(7) % 16u) == 0u, "rows are read and written as b128");
 
 // k_intersect_cand LDS: [per wave as k_pass_cand][staged candidate records (STAGED)]
 PT_HDC size_t intersect_cand_lds_bytes() { return (size_t)(kBlock / 64u) * kCandWaveBytes; }
@@ -113,6 +125,15 @@ struct LdsLayout {
     size_t mega_lds;
 };
 
+// k_pass_cand's LDS budget per workgroup: what still lets a CU's 160 KiB hold as many workgroups as the kernel is built to run
+// waves per SIMD.  Measured with PT_LDS_PAD (a frame loses a twentieth to a tenth when one workgroup fewer fits): with walks
+// four workgroups of 40 928 B share a CU; without, at five waves, five of 32 144 B did and five of 32 400 B did not; at six,
+// six of 26 880 B do (58.1 - 58.7 G bounces/s on cornell.json) and six of 26 944 B do not (55.5 - 55.8) - 21 units of 1 280 B, 426 B short
+// of a sixth of the 160 KiB.  At any other PT_CAND_WAVES (an A/B build): the five-wave rule.
+PT_HDC size_t pass_cand_lds_budget(bool bvh) {
+    return bvh ? 160u * 1024u / PT_CAND_BVH_WAVES : (PT_CAND_WAVES == 6 ? 26880u : 160u * 1024u / PT_CAND_WAVES - 512u);
+}
+
 inline LdsLayout lds_layout(const DevScene &S, uint32_t m, size_t lds_pad) {
     LdsLayout L{};
     L.m = m;
@@ -123,8 +144,7 @@ inline LdsLayout lds_layout(const DevScene &S, uint32_t m, size_t lds_pad) {
     if (S.cand_scan) {
         // candidate scan: ray slots, keys and ring per wave + the workgroup's copy of the candidate and shading records while
         // as many workgroups still fit a CU's 160 KiB as the kernel is built to run waves per SIMD (with walks four: 40 KiB each)
-        // (measured with PT_LDS_PAD: four workgroups of 40 928 B share a CU, five of 32 144 B do, five of 32 400 B do not)
-        const size_t budget = 160u * 1024u / (bvh ? PT_CAND_BVH_WAVES : PT_CAND_WAVES) - (bvh ? 0u : 512u);
+        const size_t budget = pass_cand_lds_budget(bvh);
         DevScene S2 = S;
         S2.bvh_in_lds &= ~1u;  // (nodes from global memory: PT_BVH_LDS asks for the staged k_intersect, not for this kernel)
         // glass deferral: not with walks (their queues take its place in LDS; a walked ray is shaded in place anyway)
@@ -143,7 +163,7 @@ inline LdsLayout lds_layout(const DevScene &S, uint32_t m, size_t lds_pad) {
             if (L.nodes_lds) S2 = S3;
         }
         const size_t walk = bvh ? pass_cand_bvh_bytes(S2) : 0u;
-        const size_t before = pass_lds_cand_offset(m, L.defer) + pass_lds_cand_bytes() + walk;
+        const size_t before = pass_lds_cand_offset(m, L.defer) + pass_lds_cand_bytes() + pass_lds_wait_bytes(bvh) + walk;
         L.surf_staged = before + rec_cand + rec_surf <= budget ? 1u : 0u;
         // (without walks the records are staged whole or not at all; with walks the candidate records alone may be)
         L.staged = bvh ? (L.surf_staged || before + rec_cand <= budget + 8u * 1024u) : L.surf_staged != 0u;
