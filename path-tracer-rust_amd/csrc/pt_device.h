@@ -181,10 +181,12 @@ struct alignas(16) MatRec {
 // its centre; then the object's material as in MatRec.
 struct alignas(16) SurfRec {
     float vx, vy, vz;  // triangle: va_vb.cross(va_vc).normalize() (mod.rs:605); sphere: position (mod.rs:431)
-    uint32_t kind;     // bits 0-1: reflect type, bit 8: triangle
+    uint32_t kind;     // bits 0-1: reflect type, bit 8: triangle, bit 9: some emission component is not zero (kSurfEmits)
     float cr, cg, cb, max_refl;
     float er, eg, eb, inv_max_refl;
 };
+
+constexpr uint32_t kSurfTriangle = 0x100u, kSurfEmits = 0x200u;  // SurfRec.kind (surf_material writes every record)
 
 // per-triangle shading record, gathered per lane in shade
 struct alignas(16) TriShade {
@@ -1977,8 +1979,12 @@ struct ShadeOut {
     int n_rays;          // 0, 1 or 2 continuation rays, all starting at x
     vec3 x;              // hit point
     vec3 d0, thr0;       // first continuation (on a refract split: the reflected ray, branch 2b)
-    vec3 d1, thr1;       // second continuation (refract split only: the transmitted ray, branch 2b+1)
+    // second continuation (refract split only: the transmitted ray, branch 2b+1).  d1, thr1 and meta1 are WRITTEN ONLY WHERE
+    // n_rays BECOMES 2: read them under n_rays == 2 alone.  (As defaults for a ray that almost never exists they were seven
+    // values kept alive, by copies, through the specular/glass body of nearly every trip.)
+    vec3 d1, thr1;
     uint32_t meta0, meta1;
+    vec3 thr;            // throughput below the hit, before a glass weight (what pt_ctx_scatter reports as thr1 without a second ray)
     vec3 contrib;        // throughput * emission of the hit object (zero when it does not emit)
     bool emits;
     bool deferred;       // kShadeDeferRefract only: the hit is on glass and was not shaded
@@ -1996,7 +2002,10 @@ struct Surface {
     vec3 color, emission;
     float max_refl, inv_max_refl;
     uint32_t reflect;
+    bool emits;  // some emission component is not zero
 };
+
+__device__ __forceinline__ bool emission_nonzero(vec3 e) { return (e.x != 0.0f) || (e.y != 0.0f) || (e.z != 0.0f); }
 
 __device__ __forceinline__ Surface fetch_surface(const DevScene &S, vec3 o, vec3 d, HitRec h) {
     Surface s;
@@ -2016,6 +2025,7 @@ __device__ __forceinline__ Surface fetch_surface(const DevScene &S, vec3 o, vec3
     s.max_refl = m.max_refl;
     s.inv_max_refl = m.inv_max_refl;
     s.reflect = m.reflect;
+    s.emits = emission_nonzero(s.emission);
     return s;
 }
 
@@ -2030,12 +2040,13 @@ __device__ __forceinline__ Surface fetch_surface_rank(const SurfRec *surf, vec3 
         r = surf[rank];
     Surface s;
     s.x = o + d * t;  // mod.rs:430 / mod.rs:604
-    s.n = (r.kind & 0x100u) ? mk(r.vx, r.vy, r.vz) : normalize(s.x - mk(r.vx, r.vy, r.vz));
+    s.n = (r.kind & kSurfTriangle) ? mk(r.vx, r.vy, r.vz) : normalize(s.x - mk(r.vx, r.vy, r.vz));
     s.color = mk(r.cr, r.cg, r.cb);
     s.emission = mk(r.er, r.eg, r.eb);
     s.max_refl = r.max_refl;
     s.inv_max_refl = r.inv_max_refl;
     s.reflect = r.kind & 3u;
+    s.emits = (r.kind & kSurfEmits) != 0u;  // the record's bit is emission_nonzero of its emission, taken once on the host
     return s;
 }
 
@@ -2068,10 +2079,10 @@ __device__ __forceinline__ void shade_surface(const Params &F, const PathRay &in
     const uint32_t new_depth = depth + 1u;
     const u32x4 rnd = draw_block(((uint64_t)F.seed_hi << 32) | F.seed_lo, in.pix, sample, (branch << 8) | new_depth);
 
-    out.emits = (sf.emission.x != 0.0f) || (sf.emission.y != 0.0f) || (sf.emission.z != 0.0f);
+    out.emits = sf.emits;
     out.contrib = in.thr * sf.emission;
     out.x = sf.x;
-    out.meta0 = out.meta1 = pack_meta(sample, new_depth, branch);
+    out.meta0 = pack_meta(sample, new_depth, branch);
 
     // Russian roulette, mod.rs:677-683 (the draw is taken first: `rand01() < max_reflection && ...`)
     vec3 color = sf.color;
@@ -2086,7 +2097,8 @@ __device__ __forceinline__ void shade_surface(const Params &F, const PathRay &in
     PT_PHASE(kPhRng);
     const vec3 thr = in.thr * color;
     int n_rays = alive ? 1 : 0;
-    vec3 d0 = d, thr0 = thr, d1 = d, thr1 = thr;
+    out.thr = thr;
+    vec3 d0, thr0 = thr;  // (d0: the diffuse direction or the mirror's, below)
 
     PT_PHASE_PIN(rnd.a);
     PT_PHASE_PIN(rnd.b);
@@ -2131,7 +2143,11 @@ __device__ __forceinline__ void shade_surface(const Params &F, const PathRay &in
             // subtracted from 1.
             const bool into = dn < 0.0f;
             const float nc = 1.0f, nt = 1.5f;
-            const float nnt = into ? nc / nt : nt / nc;
+            float nnt = into ? nc / nt : nt / nc;
+            // One select, and nnt * nnt a multiplication at run time: left to itself the compiler folds the square into a second
+            // select between two more literals (two moves and a select where one v_mul_f32 does).  The product it would fold is
+            // this very one - the correctly rounded binary32 product of the same two values.
+            asm volatile("" : "+v"(nnt));
             const float ddn = into ? dn : -dn;
             const float cos2t = 1.0f - (nnt * nnt) * (1.0f - ddn * ddn);
             if (!(cos2t < 0.0f)) {  // otherwise total internal reflection: the reflected ray alone
@@ -2156,8 +2172,8 @@ __device__ __forceinline__ void shade_surface(const Params &F, const PathRay &in
                     thr0 = thr * ((pick_refl ? re : tr) / (pick_refl ? p : 1.0f - p));
                 } else {  // mod.rs:775-786: both subtrees
                     thr0 = thr * re;
-                    d1 = tdir;
-                    thr1 = thr * tr;
+                    out.d1 = tdir;
+                    out.thr1 = thr * tr;
                     out.meta0 = pack_meta(sample, new_depth, 2u * branch);
                     out.meta1 = pack_meta(sample, new_depth, 2u * branch + 1u);
                     n_rays = alive ? 2 : 0;
@@ -2171,8 +2187,6 @@ __device__ __forceinline__ void shade_surface(const Params &F, const PathRay &in
     PT_PHASE(kPhFinish);
     out.d0 = d0;
     out.thr0 = thr0;
-    out.d1 = d1;
-    out.thr1 = thr1;
     out.n_rays = n_rays;
 }
 

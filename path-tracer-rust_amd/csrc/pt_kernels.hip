@@ -339,11 +339,14 @@ __global__ __launch_bounds__(kBlock, PT_ISECT_WAVES) void k_intersect_cand(DevSc
 
 // ------------------------------------------------------------------------------------------------
 // radiance of the stream's own pixels, summed in LDS (u64 32.32 fixed point, [3][m])
+// SKIP_ZERO = false: no test for a zero sum around each add - adding zero changes nothing, and on k_pass_cand's in-place path
+// each test was a 64-bit compare and an EXEC round trip for the few lanes of a trip that hit an emitter
+template <bool SKIP_ZERO = true>
 __device__ __forceinline__ void add_radiance_lds(unsigned long long *lds_acc, uint32_t m, uint32_t slot, vec3 v) {
     const uint64_t r = to_fixed(v.x), g = to_fixed(v.y), bl = to_fixed(v.z);
-    if (r) atomicAdd(&lds_acc[slot], (unsigned long long)r);
-    if (g) atomicAdd(&lds_acc[m + slot], (unsigned long long)g);
-    if (bl) atomicAdd(&lds_acc[2u * m + slot], (unsigned long long)bl);
+    if (!SKIP_ZERO || r) atomicAdd(&lds_acc[slot], (unsigned long long)r);
+    if (!SKIP_ZERO || g) atomicAdd(&lds_acc[m + slot], (unsigned long long)g);
+    if (!SKIP_ZERO || bl) atomicAdd(&lds_acc[2u * m + slot], (unsigned long long)bl);
 }
 
 #ifndef PT_TU_PART
@@ -1091,7 +1094,7 @@ __global__ __launch_bounds__(kBlock, BVH ? PT_CAND_BVH_WAVES : PT_CAND_WAVES) vo
                     // conversions and LDS atomics - was measured once the glass deferral had left its LDS free: +0.45 %, not kept.)
                     if (so.emits) {
                         PT_PHASE(kPhEmitAdd);
-                        add_radiance_lds(lds_acc, m, word_pix(prev_word), so.contrib);
+                        add_radiance_lds<false>(lds_acc, m, word_pix(prev_word), so.contrib);
                     }
                 }
             }
@@ -1446,6 +1449,9 @@ __global__ __launch_bounds__(kBlock) void k_mega(DevScene S, MegaParams F, unsig
                     active = false;
                 } else {
                     ShadeOut so;
+                    // (The second ray starts out as the lane's own: values already in registers.  Left unwritten, as shade_surface leaves
+                    // them without a split, the child's hand-over below is threaded into the glass body - eight VGPRs more.)
+                    so.d1 = cur.d, so.thr1 = cur.thr, so.meta1 = cur.meta;
                     shade_hit(S, F, cur, h, so);
                     if (so.emits) {
                         ar += to_fixed(so.contrib.x);
@@ -1794,6 +1800,9 @@ __global__ __launch_bounds__(kBlock, BVH ? 4 : PT_MEGA_WAVES) void k_mega_cand(D
                         pr.meta = prev_meta;
                         const Surface sf = fetch_surface_rank(cand.surf, pr.o, pr.d, __uint_as_float((uint32_t)(key >> 32)), rank);
                         ShadeOut so;
+                        // (as in k_mega: without initial values the child's stores move into the glass body, <1,0> then needs 127
+                        // VGPRs and 20 B of scratch against 123 and none)
+                        so.d1 = pr.d, so.thr1 = pr.thr, so.meta1 = pr.meta;
                         shade_surface<kShadeAll>(P, pr, sf, so);
                         if (so.emits) {
                             ar += to_fixed(so.contrib.x);

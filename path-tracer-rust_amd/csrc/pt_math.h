@@ -117,6 +117,9 @@ struct u32x4 {
     uint32_t a, b, c, d;
 };
 constexpr int kPhiloxRounds = 7;
+#ifndef PT_PHILOX_BITOP3
+#define PT_PHILOX_BITOP3 1  // device builds: the round keys enter through v_bitop3_b32 (below); 0: two v_xor_b32, for A/B
+#endif
 
 template <int ROUNDS>
 PT_HD u32x4 philox4x32(u32x4 ctr, uint32_t k0, uint32_t k1) {
@@ -127,9 +130,17 @@ PT_HD u32x4 philox4x32(u32x4 ctr, uint32_t k0, uint32_t k1) {
         const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0;
         const uint32_t hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
         u32x4 nx;
+#if defined(__HIP_DEVICE_COMPILE__) && PT_PHILOX_BITOP3
+        // hi ^ ctr ^ key as ONE three-input logic op (truth table 0x96: the parity of the three bits).  With the round key in a
+        // scalar register the compiler writes v_xor_b32 (VGPR, VGPR), two cycles, then v_xor_b32 (SGPR, VGPR), four; the
+        // three-input form with the same sources is one instruction of the four-cycle class (profiles/r04_bitop3_issue_cost.json).
+        nx.a = __builtin_amdgcn_bitop3_b32(hi1, ctr.b, k0, 0x96);
+        nx.c = __builtin_amdgcn_bitop3_b32(hi0, ctr.d, k1, 0x96);
+#else
         nx.a = hi1 ^ ctr.b ^ k0;
-        nx.b = lo1;
         nx.c = hi0 ^ ctr.d ^ k1;
+#endif
+        nx.b = lo1;
         nx.d = lo0;
         ctr = nx;
         k0 += 0x9E3779B9u;

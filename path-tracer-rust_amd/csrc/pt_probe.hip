@@ -65,6 +65,7 @@ __global__ __launch_bounds__(kBlock) void k_scatter(DevScene S, ScatterCall c) {
             sf.max_refl = g.max_refl;
             sf.inv_max_refl = g.inv_max_refl;
             sf.reflect = g.reflect;
+            sf.emits = emission_nonzero(sf.emission);
         } else {
             const HitRec h = intersect_scene_dev<true>(S, in.o, in.d, probe_lds);
             o.hit = h.id;
@@ -88,6 +89,13 @@ __global__ __launch_bounds__(kBlock) void k_scatter(DevScene S, ScatterCall c) {
         if (have) {
             ShadeOut so;
             shade_surface<MODE>(P, in, sf, so);
+            // shade_surface writes the second ray only where it makes one.  The record is filled as it was when the step kept
+            // defaults for it: the incoming direction, the throughput below the hit and the first ray's bookkeeping.
+            if (!so.deferred && so.n_rays != 2) {
+                so.d1 = in.d;
+                so.thr1 = so.thr;
+                so.meta1 = so.meta0;
+            }
             o.deferred = so.deferred ? 1u : 0u;
             o.n_rays = (uint32_t)so.n_rays;
             o.emits = so.emits ? 1u : 0u;

@@ -153,7 +153,7 @@ PT_HD void refit_wide(BvhNode4 *nodes4, const BvhNode *nodes, const RefitWide &w
 
 // the material half of a surface record (flatten_scene fills every record through this; STEP 4 runs it per rank of a large mesh)
 PT_HD void surf_material(SurfRec &sr, const MatRec &mm, bool triangle) {
-    sr.kind = (triangle ? 0x100u : 0u) | (mm.reflect & 3u);
+    sr.kind = (triangle ? kSurfTriangle : 0u) | (mm.reflect & 3u) | ((mm.er != 0.0f || mm.eg != 0.0f || mm.eb != 0.0f) ? kSurfEmits : 0u);
     sr.cr = mm.cr, sr.cg = mm.cg, sr.cb = mm.cb, sr.max_refl = mm.max_refl;
     sr.er = mm.er, sr.eg = mm.eg, sr.eb = mm.eb, sr.inv_max_refl = mm.inv_max_refl;
 }

@@ -15,11 +15,13 @@
 //
 // build: hipcc -O2 --offload-arch=gfx950 -o valu_issue_bench tools/valu_issue_bench.hip
 // run  : ./valu_issue_bench > gpurun_out/valu_issue_costs.json
+//        ./valu_issue_bench ITERS NAME[,NAME...]: only the named entries (a new opcode needs no run of the whole table)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -188,6 +190,12 @@ typedef float f2 __attribute__((ext_vector_type(2)));
 #define OP_mix_fma_pkfma(a, b) "v_fma_f32 v" #a ", %0, %1, %2\n v_pk_fma_f32 v[" #a ":" #b "], %5, %6, %5\n"
 #define OP_mix_mul_cmp(a, b) "v_mul_f32 v" #a ", %0, %1\n v_cmp_lt_f32 vcc, %0, %1\n"
 #define OP_mix_cmp_cndmask(a, b) "v_cmp_lt_f32 vcc, %0, %1\n v_cndmask_b32 v" #a ", %0, %1, vcc\n"
+// the Philox round-key step hi ^ ctr ^ key, key in a scalar register: as the compiler writes it (two instructions per slot,
+// the second consuming the first) and as one three-input logic op (truth table 0x96)
+#define OP_xor_b32_sgpr(a, b) "v_xor_b32 v" #a ", %8, %1\n"
+#define OP_bitop3_b32(a, b) "v_bitop3_b32 v" #a ", %0, %1, %2 bitop3:0x96\n"
+#define OP_bitop3_b32_sgpr(a, b) "v_bitop3_b32 v" #a ", %0, %1, %8 bitop3:0x96\n"
+#define OP_pair_xor_xor_sgpr(a, b) "v_xor_b32 v" #a ", %0, %1\n v_xor_b32 v" #a ", %8, v" #a "\n"
 // dependent chains (latency): each instruction consumes the previous result
 #define OP_dep_fma_f32(a, b) "v_fma_f32 v10, v10, %1, %2\n"
 #define OP_dep_pk_fma_f32(a, b) "v_pk_fma_f32 v[10:11], v[10:11], %6, %5\n"
@@ -214,7 +222,8 @@ typedef float f2 __attribute__((ext_vector_type(2)));
     X(pair_mad64A, 2) X(pair_f64A, 2) X(pair_BA_raw2, 4) X(pair_AA_fma, 2) X(pair_cmpA, 2) X(pair_cmpsA, 2)                \
     X(pair_rcpA, 2) X(trip_rcpAA, 3) X(pair_B_salu, 2) X(trip_BA_salu, 3) X(trip_B_salu_A, 3)                              \
     X(mix_fma_salu, 2) X(mix_fma_pkfma, 2) X(mix_mul_cmp, 2) X(mix_cmp_cndmask, 2) X(dep_fma_f32, 1)                    \
-    X(dep_pk_fma_f32, 1) X(dep_mul_f32, 1)
+    X(dep_pk_fma_f32, 1) X(dep_mul_f32, 1)                                                                                 \
+    X(xor_b32_sgpr, 1) X(bitop3_b32, 1) X(bitop3_b32_sgpr, 1) X(pair_xor_xor_sgpr, 2)
 
 #define DEFINE(NAME, PER) KERNEL(NAME, R64(OP_##NAME))
 LIST(DEFINE)
@@ -246,9 +255,20 @@ int main(int argc, char **argv) {
            prop.name, prop.gcnArchName, cus, iters);
     printf("  \"unit\": \"shader cycles (s_memtime) per wave-instruction per SIMD; every CU busy; median over waves\",\n");
     printf("  \"costs\": {\n");
-    const int n_entries = (int)(sizeof(g_list) / sizeof(g_list[0]));
+    std::vector<Entry> picked;
+    for (const Entry &en : g_list) {
+        bool want = argc <= 2;
+        for (const char *p = argc > 2 ? argv[2] : nullptr; p && !want;) {  // comma-separated names
+            const char *q = strchr(p, ',');
+            const size_t len = q ? (size_t)(q - p) : strlen(p);
+            want = strlen(en.name) == len && strncmp(en.name, p, len) == 0;
+            p = q ? q + 1 : nullptr;
+        }
+        if (want) picked.push_back(en);
+    }
+    const int n_entries = (int)picked.size();
     for (int e = 0; e < n_entries; ++e) {
-        const Entry &en = g_list[e];
+        const Entry &en = picked[e];
         printf("    \"%s\": {", en.name);
         for (size_t si = 0; si < sizeof(shapes) / sizeof(shapes[0]); ++si) {
             const Shape &sh = shapes[si];
