@@ -202,6 +202,9 @@ struct Tuning {
     uint32_t leaf_quorum = 12; // PT_LEAF_QUORUM: lanes on a leaf that send a walking wave to the triangle code
     uint64_t streams = 0;      // PT_STREAMS: ray streams per pass (0 = derived from the frame)
     uint32_t per_stream = 0;   // PT_PER_STREAM: primary rays per stream and pass that k_pass_cand's stream count aims at (0 = default)
+    int64_t taper_cut = -1;    // PT_TAPER_CUT=n: k_pass_cand's launches run their last n streams in pieces (host::plan_taper; 0 = off,
+                               // unset = the default of render_wavefront)
+    uint32_t taper_pieces = 0; // PT_TAPER_PIECES=c: ... c pieces each, a power of two (unset = the default)
     uint64_t rays_per_pass = 0;  // PT_RAYS_PER_PASS: the default of pt_config.rays_per_pass (probes; 0 = the library's)
     bool glass_defer = false;    // PT_GLASS_DEFER=1: k_pass_cand collects glass hits per wave and shades them 64 at a time (A/B: it
                                  // paid with levels, it does not without)
@@ -217,6 +220,15 @@ struct Tuning {
                                   // load them through the caches (same bytes; 0 = every level direct, 128 = every level LDS)
     uint32_t debug = 0;
 };
+// The taper's defaults (render_wavefront; measured: DESIGN.md section 4, profiles/r04_taper_sweep.txt): streams cut in HALF rounds of
+// resident workgroups (0: no taper), pieces per cut stream, and the primaries per stream and pass asked for with it (0: plan_pass's)
+// - without walks and with.  cornell 1024x768 @4096, one session, 448.0 ms without: one round in 4 pieces 438.1 ms at 24 Ki primaries
+// per stream, 439.0 at 32 Ki, 439.8 at 20 Ki; half a round in 8 pieces 436.8 - but in another session (449.9 without) half a round
+// 440.4 and a third of a round 446.9: too close to where the cut stops paying, so a whole round it is.  mesh.json @1024, 194.6 ms
+// without: half a round in 4 pieces at its own stream length 191.6, a whole round 192.4, 8 pieces 194.6; longer streams (32 Ki) gain
+// nothing there (192.0) and lose 3 % with a cut of half a round.
+constexpr uint32_t kTaperCutHalfRounds = 2, kTaperPieces = 4, kTaperPerStream = 24576;
+constexpr uint32_t kTaperCutHalfRoundsBvh = 1, kTaperPiecesBvh = 4, kTaperPerStreamBvh = 0;
 constexpr uint32_t kDnLdsMaxStepDefault = 4;  // measured: LDS wins at steps 1, 2, 4 and loses from 8 on
 static Tuning read_tuning() {
     Tuning t;
@@ -234,6 +246,11 @@ static Tuning read_tuning() {
     const long long st = num("PT_STREAMS", 0);
     t.streams = st > 0 ? (uint64_t)st : 0;
     t.per_stream = (uint32_t)num("PT_PER_STREAM", 0);
+    {
+        const long long tc = num("PT_TAPER_CUT", -1), tp = num("PT_TAPER_PIECES", 0);
+        t.taper_cut = tc < 0 ? -1 : (tc > 0xffffffffll ? 0xffffffffll : tc);
+        t.taper_pieces = tp > 0 ? (uint32_t)(tp > 64 ? 64 : tp) : 0u;
+    }
     t.rays_per_pass = (uint64_t)num("PT_RAYS_PER_PASS", 0);
     t.nodes_lds = num("PT_NODES_LDS", 1) != 0;
     t.glass_defer = num("PT_GLASS_DEFER", 0) != 0;
@@ -714,6 +731,18 @@ int render_wavefront(pt_ctx *c, const FrameForm &form, const pt_config *cfg, con
         if (want < npix) want = npix;
     }
     uint32_t spp_pass = 0, m = 0, K = 0, cap = 0;
+    // k_pass_cand's TAPER (host::plan_taper; the kernel: "THE TAPER"): the launch's last streams in pieces, and - only then - longer
+    // streams.  The knobs by hand (PT_TAPER_CUT, PT_TAPER_PIECES, PT_PER_STREAM) are taken as given; the defaults are kTaper* (above read_tuning).
+    // Never for the PROBE instances, whose frames are a handful of rays.
+    const uint64_t resident =
+        (uint64_t)c->n_cus * (!stack_form ? 4u : (S.n_bvh_nodes == 0u ? (uint32_t)PT_CAND_WAVES : (uint32_t)PT_CAND_BVH_WAVES));
+    const bool walks = S.n_bvh_nodes != 0u;
+    const bool taper_forced = c->tune.taper_cut >= 0;
+    const uint64_t cut_dflt = (uint64_t)(walks ? kTaperCutHalfRoundsBvh : kTaperCutHalfRounds) * resident / 2u;
+    const uint32_t taper_cut = (uint32_t)std::min<uint64_t>(taper_forced ? (uint64_t)c->tune.taper_cut : cut_dflt, 0xffffffffu);
+    const uint32_t taper_pieces = c->tune.taper_pieces ? c->tune.taper_pieces : (walks ? kTaperPiecesBvh : kTaperPieces);
+    bool try_taper = stack_form && form.one_kernel && !F.probe && taper_cut != 0u && taper_pieces >= 2u;
+    host::Taper taper;
     for (;;) {
         host::PassPlanIn pin;
         pin.npix = npix;
@@ -741,14 +770,39 @@ int render_wavefront(pt_ctx *c, const FrameForm &form, const pt_config *cfg, con
             set_error("rays per pass too large");
             return PT_ERR_INVALID;
         }
+        taper = host::Taper{};
+        if (try_taper) {
+            host::TaperIn tin;
+            tin.n_cut = taper_cut;
+            tin.pieces = taper_pieces;
+            tin.pass_samples = plan.spp_pass;
+            tin.resident = resident;
+            tin.budget = stack_budget;
+            tin.stack_park = form.stack_park;
+            tin.probe = F.probe != 0u;
+            tin.forced = taper_forced;
+            // longer streams with the default taper - if the plan is otherwise the same pass and the records stay staged
+            host::PassPlan plan_t = plan;
+            const uint32_t long_stream = walks ? kTaperPerStreamBvh : kTaperPerStream;
+            if (!taper_forced && !pin.per_stream && !pin.streams && long_stream != 0u) {
+                host::PassPlanIn pin_t = pin;
+                pin_t.per_stream = long_stream;
+                uint64_t unused = want;
+                if (host::plan_pass(pin_t, plan_t, &unused) != host::kPlanOk || plan_t.spp_pass != plan.spp_pass ||
+                    lds_layout(S, plan_t.m, c->tune.lds_pad).staged != lds_layout(S, plan.m, c->tune.lds_pad).staged)
+                    plan_t = plan;
+            }
+            taper = host::plan_taper(plan_t, tin);
+            if (taper.on()) plan = plan_t;
+        }
         spp_pass = plan.spp_pass;
         m = plan.m;
         K = plan.K;
         cap = plan.cap;
         const size_t slots = (size_t)K * cap;
         int rc = PT_OK;
-        rc = c->q_buf[0].ensure(plan.bytes0, true);
-        if (!rc && plan.bytes1) rc = c->q_buf[1].ensure(plan.bytes1, true);
+        rc = c->q_buf[0].ensure(plan.bytes0 + taper.extra0, true);
+        if (!rc && plan.bytes1) rc = c->q_buf[1].ensure(plan.bytes1 + taper.extra1, true);
         // only the three-kernel form needs the hit records: k_pass keeps hits in registers
         if (!rc && !form.one_kernel) rc = c->hit.ensure(slots, true);
         if (!rc) rc = c->cnt.ensure((size_t)kLevels * K, true);
@@ -760,6 +814,10 @@ int render_wavefront(pt_ctx *c, const FrameForm &form, const pt_config *cfg, con
         // out of device memory: give back what this attempt took and try passes of half the size
         for (int w = 0; w < 2; ++w) c->q_buf[w].release();
         c->hit.release();
+        if (taper.on()) {  // the taper goes before a pass is halved
+            try_taper = false;
+            continue;
+        }
         if (spp_pass <= 1u) return PT_ERR_HIP;  // (the message names the allocation that failed)
         want = (uint64_t)npix * (spp_pass / 2u ? spp_pass / 2u : 1u);
     }
@@ -787,6 +845,8 @@ int render_wavefront(pt_ctx *c, const FrameForm &form, const pt_config *cfg, con
     size_t n_prof = 0;
     while ((rc = pace.next()) == PassPacer::kLaunch) {
         const uint32_t s0 = pace.s0, s_here = pace.s_here;
+        // (a launch of fewer samples than pieces - the pacer's first, short ones - runs whole streams: the slices are there either way)
+        const bool taper_now = taper.on() && (taper_forced || s_here >= taper.pieces);
         if (form.one_kernel) {  // the whole pass in one launch (k_pass)
             hipEvent_t a = nullptr, b = nullptr;
             if (c->profiling) {
@@ -800,7 +860,7 @@ int render_wavefront(pt_ctx *c, const FrameForm &form, const pt_config *cfg, con
             if (S.n_bvh_nodes != 0u && !S.cand_scan)
                 launch_pass_bvh(st, K, S, F, queue_of(c, 0), queue_of(c, 1), cap, s0, s_here, m, c->acc.p, c->blk_rays.p, c->flags.p);
             else if (launch_pass(st, K, S, lay, F, queue_of(c, 0), queue_of(c, 1), cap, s0, s_here, m, c->acc.p, c->blk_rays.p,
-                                 c->flags.p) != hipSuccess)
+                                 c->flags.p, taper_now ? taper.n_cut : 0u, taper_now ? taper.lg_pieces : 0u) != hipSuccess)
                 return PT_ERR_HIP;  // (the message says how much LDS the scene's kernel asked for)
             if (c->profiling) {
                 HIP_TRY(hipEventRecord(b, st));
@@ -1620,6 +1680,12 @@ static int upload_flat(pt_ctx *c, const host::FlatScene &fs, const pt_object *ob
     if (!c->scene.phase_stats) {  // instrumented builds only: never freed
         HIP_TRY(hipMalloc((void **)&c->scene.phase_stats, (kPhCount * 3 + 2) * sizeof(unsigned long long)));
         HIP_TRY(hipMemset(c->scene.phase_stats, 0, (kPhCount * 3 + 2) * sizeof(unsigned long long)));
+    }
+#endif
+#ifdef PT_TAIL_STATS
+    if (!c->scene.tail_stats) {  // instrumented builds only: never freed
+        HIP_TRY(hipMalloc((void **)&c->scene.tail_stats, 2 * (size_t)kTailStatsCap * sizeof(unsigned long long)));
+        HIP_TRY(hipMemset(c->scene.tail_stats, 0, 2 * (size_t)kTailStatsCap * sizeof(unsigned long long)));
     }
 #endif
     c->n_bvh_nodes = (uint32_t)fs.bvh_nodes.size();
@@ -3360,6 +3426,18 @@ int pt_debug_phase_stats(pt_ctx *c, unsigned long long *out, uint32_t cap) {
     (void)hipMemcpy(out, c->scene.phase_stats, (kPhCount * 3 + 2) * sizeof(unsigned long long), hipMemcpyDeviceToHost);
     (void)hipMemset(c->scene.phase_stats, 0, (kPhCount * 3 + 2) * sizeof(unsigned long long));
     return (int)kPhCount;
+}
+#endif
+
+#ifdef PT_TAIL_STATS
+// instrumented builds only (tools/tail_probe.py): read and clear the begin / end stamps of the first n workgroups of the launches
+// since the last call (a later launch writes over an earlier one: the probe renders one pass); returns the table's capacity
+int pt_debug_tail_stats(pt_ctx *c, unsigned long long *out, uint32_t n) {
+    if (!c || !c->scene.tail_stats || n > kTailStatsCap) return PT_ERR_INVALID;
+    (void)hipDeviceSynchronize();
+    (void)hipMemcpy(out, c->scene.tail_stats, 2 * (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+    (void)hipMemset(c->scene.tail_stats, 0, 2 * (size_t)kTailStatsCap * sizeof(unsigned long long));
+    return (int)kTailStatsCap;
 }
 #endif
 

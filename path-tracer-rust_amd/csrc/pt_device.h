@@ -252,7 +252,14 @@ struct DevScene {
 #ifdef PT_PHASE_STATS
     unsigned long long *phase_stats;  // [kPhCount][3] + [2] (wave lifetimes: s_memtime, s_memrealtime) of a -DPT_PHASE_STATS build
 #endif
+#ifdef PT_TAIL_STATS
+    unsigned long long *tail_stats;   // [kTailStatsCap][2]: begin and end of every workgroup of k_pass_cand's last launch in
+                                      // s_memrealtime ticks (100 MHz), of a -DPT_TAIL_STATS build (tools/tail_probe.py)
+#endif
 };
+#ifdef PT_TAIL_STATS
+constexpr uint32_t kTailStatsCap = 1u << 18;  // workgroups of a launch the table holds (the bench frame's launch: 32 768)
+#endif
 #ifdef PT_PHASE_STATS
 // Diagnostic build only (tools/phase_budget.py -> profiles/r03_*_phase_budget.json; never in the shipped library): the
 // wave's lifetime inside k_pass_cand split by PHASE.  PT_PHASE(id) stamps s_memtime (shader cycles) and books the cycles

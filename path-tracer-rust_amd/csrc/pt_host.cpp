@@ -1069,6 +1069,24 @@ int plan_pass(const PassPlanIn &in, PassPlan &out, uint64_t *want_next) {
     return kPlanOk;
 }
 
+Taper plan_taper(const PassPlan &plan, const TaperIn &in) {
+    Taper off;
+    if (in.n_cut == 0u || in.pieces < 2u || in.probe || plan.K == 0u) return off;
+    Taper t;
+    t.n_cut = in.n_cut < plan.K ? in.n_cut : plan.K;
+    while (t.lg_pieces < 6u && (2u << t.lg_pieces) <= in.pieces) ++t.lg_pieces;
+    t.pieces = 1u << t.lg_pieces;
+    if (!in.forced && in.pass_samples < t.pieces) return off;
+    if (!in.forced && in.resident != 0u && plan.K < (uint64_t)kTaperMinRounds * in.resident) return off;
+    const uint64_t more = (uint64_t)t.n_cut * (t.pieces - 1u);
+    t.extra0 = queue_bytes(more, plan.cap);
+    t.extra1 = in.stack_park ? (size_t)more * 4u * kWaveParkBytes : 0u;
+    if (in.budget && plan.bytes0 + plan.bytes1 + t.extra0 + t.extra1 > in.budget) return off;
+    // (slot indices are 32-bit over the whole container, as in plan_pass)
+    if ((uint64_t)plan.cap * (plan.K + more) > 0xffffffffull / 2) return off;
+    return t;
+}
+
 uint32_t next_pass_samples(double rate, double target_ms, uint64_t npix, uint64_t probe, uint32_t s_prev, uint32_t left,
                            uint32_t max_pass) {
     if (npix == 0u) npix = 1u;

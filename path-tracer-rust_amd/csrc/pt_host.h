@@ -87,6 +87,40 @@ struct PassPlan {
 enum { kPlanOk = 0, kPlanRetry = 1, kPlanTooLarge = 2 };
 // kPlanRetry: the plan does not fit (the stacks' budget, or 32-bit slot indices) - try again with in.want = *want_next
 int plan_pass(const PassPlanIn &in, PassPlan &out, uint64_t *want_next);
+// THE TAPER of a k_pass_cand launch: its last n_cut streams run as `pieces` workgroups each - (stream, a contiguous share of the
+// pass's samples) instead of (stream, whole pass) - dispatched behind the whole-pass workgroups of the streams before them, so
+// that what a launch ends on are short workgroups while the bulk of it runs long streams (a workgroup's fill and drain are paid
+// once whatever it traces).  Workgroup n_whole + j is piece j % pieces of stream n_whole + j / pieces; the pieces of a stream may
+// run at the same time, so every WORKGROUP has stack (and parking) slices of its own: extra0 / extra1 bytes behind
+// plan.bytes0 / bytes1.  plan_pass is not asked again: the taper never changes a plan, it is dropped where it does not fit.
+struct TaperIn {
+    uint32_t n_cut = 0;         // streams to cut (PT_TAPER_CUT or the default; more than K: all of them)
+    uint32_t pieces = 0;        // pieces per cut stream (PT_TAPER_PIECES or the default; rounded down to a power of two, <= 64)
+    uint32_t pass_samples = 0;  // samples of a pixel in the shortest pass the plan will be launched with
+    uint64_t resident = 0;      // workgroups the chip holds at a time (0: unknown - no rule about rounds)
+    size_t budget = 0;          // bytes the containers may take, extra slices included (0: unbounded)
+    bool stack_park = false;    // the second container holds the waves' parking areas (PassPlanIn.stack_park)
+    bool probe = false;         // a PROBE instance (pt_ctx_scatter's frames): never tapered
+    bool forced = false;        // the knobs were set by hand: neither the rule about rounds nor the one about samples applies
+                                // (tests: tiny frames, pieces without a sample - such a workgroup returns at once)
+};
+struct Taper {
+    uint32_t n_cut = 0, pieces = 1, lg_pieces = 0;  // off: 0, 1, 0
+    size_t extra0 = 0, extra1 = 0;
+    bool on() const { return n_cut != 0u; }
+    uint32_t grid(uint32_t K) const { return K - n_cut + n_cut * pieces; }
+};
+constexpr uint32_t kTaperMinRounds = 4;  // launches of fewer rounds of resident workgroups are the small-frame rule's (plan_pass)
+// Off (n_cut = 0) when: in.n_cut or in.pieces < 2 is 0; in.probe; the launch has fewer than kTaperMinRounds rounds of resident
+// workgroups, or the pass has fewer samples than pieces (neither when in.forced); plan.bytes0 + bytes1 + the extra slices exceed
+// in.budget; or the slices no longer fit 32-bit slot indices.
+Taper plan_taper(const PassPlan &plan, const TaperIn &in);
+// the samples [*s0, *s0 + *n) of piece `piece` of a pass of s_here samples (what k_pass_cand derives in its prologue)
+inline void taper_piece(uint32_t s_here, uint32_t lg_pieces, uint32_t piece, uint32_t *s0, uint32_t *n) {
+    const uint32_t share = s_here >> lg_pieces, longer = s_here & ((1u << lg_pieces) - 1u);
+    *s0 = piece * share + (piece < longer ? piece : longer);
+    *n = share + (piece < longer ? 1u : 0u);
+}
 // Samples of a pixel in the next pass (wavefront) / round (megakernel) of a frame whose passes follow the scene (pt_api.hip:
 // render_wavefront, render_mega).  `rate`: primary samples per millisecond the last timed pass went through (0: nothing
 // measured yet - the pass is `probe` samples in all); `s_prev`: samples per pixel of the pass before (0: none); `left`: samples

@@ -35,7 +35,9 @@ struct RayQueue {
 // (L = lds_layout(S, m, ..): the kernel, its template instance and its LDS; pt_layout.h)
 hipError_t launch_pass(hipStream_t st, uint32_t K, const DevScene &S, const LdsLayout &L, const FrameParams &F, const RayQueue &q0,
                  const RayQueue &q1, uint32_t cap, uint32_t s0, uint32_t s_here, uint32_t m, unsigned long long *acc,
-                 unsigned long long *blk_rays, uint32_t *flags);
+                 unsigned long long *blk_rays, uint32_t *flags, uint32_t n_cut = 0, uint32_t lg_pieces = 0);
+// (n_cut, lg_pieces: k_pass_cand's taper - the launch's last n_cut streams run as 2^lg_pieces workgroups each, host::plan_taper;
+// the containers then hold K + n_cut * (2^lg_pieces - 1) slices.  The other pass kernels take neither.)
 // the same for scenes with BVH meshes (nodes read from global memory: DevScene.bvh_in_lds bit 0 clear)
 void launch_pass_bvh(hipStream_t st, uint32_t K, const DevScene &S, const FrameParams &F, const RayQueue &q0,
                      const RayQueue &q1, uint32_t cap, uint32_t s0, uint32_t s_here, uint32_t m, unsigned long long *acc,

@@ -657,18 +657,37 @@ constexpr uint32_t kCandParkCap = kWaveParkCap;  // 63 left over + 64 new at mos
 // leaves room for three workgroups per CU instead of four - 16.1 against 17.8 G bounces/s.)
 template <bool STAGED, bool DEFER, bool BVH, bool PROBE, bool NLDS = false>
 __global__ __launch_bounds__(kBlock, BVH ? PT_CAND_BVH_WAVES : PT_CAND_WAVES) void k_pass_cand(DevScene S, FrameParams F, RayQueue q0, RayQueue q1, uint32_t cap,
-                                                         uint32_t s0, uint32_t s_here, uint32_t m,
+                                                         uint32_t s0, uint32_t s_here, uint32_t m, uint32_t n_whole, uint32_t lg_pieces,
                                                          unsigned long long *__restrict__ acc,
                                                          unsigned long long *__restrict__ blk_rays,
                                                          uint32_t *__restrict__ flags) {
     unsigned long long *lds_acc = reinterpret_cast<unsigned long long *>(dyn_lds);
     uint32_t *s_tail_p = reinterpret_cast<uint32_t *>(lds_acc + pass_acc_slots(m));
-    const uint32_t b = blockIdx.x, tid = threadIdx.x, lane = tid & 63u;
+    // THE TAPER (host::plan_taper).  Workgroups [0, n_whole) trace the whole pass of streams 0 .. n_whole - 1.  The launch's last
+    // streams are cut into 2^lg_pieces PIECES each, dispatched after every whole stream: workgroup n_whole + j traces piece
+    // j % 2^lg_pieces of stream n_whole + j / 2^lg_pieces - a contiguous share of the pass's samples, the shares differing by one
+    // at most, the leading pieces the longer ones.  What a launch ends on are then its shortest workgroups.  A piece is a workgroup
+    // like any other from here on: `b` is its stream (pixels, accumulator slots), s0 and s_here its samples, and `slice` -
+    // blockIdx.x - its stacks and parking areas, because the pieces of a stream may run side by side (which is also why the
+    // flush at the end adds atomically).  That the pieces start last is for speed alone; nothing depends on any order.
+    const uint32_t slice = blockIdx.x, tid = threadIdx.x, lane = tid & 63u;
+    uint32_t b = slice;
+    if (slice >= n_whole) {  // (scalar; never taken with the taper off: n_whole is the grid)
+        const uint32_t j = slice - n_whole, piece = j & ((1u << lg_pieces) - 1u);
+        const uint32_t share = s_here >> lg_pieces, longer = s_here & ((1u << lg_pieces) - 1u);
+        b = n_whole + (j >> lg_pieces);
+        s0 += piece * share + (piece < longer ? piece : longer);
+        s_here = share + (piece < longer ? 1u : 0u);
+        if (s_here == 0u) return;  // (a pass of fewer samples than pieces)
+    }
     const uint32_t mb = stream_pixel_count(F.npix, F.n_streams, b);  // <= m
     if (mb == 0u) return;
 #ifdef PT_PHASE_STATS
     unsigned long long ph_t0, ph_r0;
     phase_begin(&ph_t0, &ph_r0);
+#endif
+#ifdef PT_TAIL_STATS
+    const unsigned long long tail_t0 = __builtin_amdgcn_s_memrealtime();
 #endif
     for (uint32_t k = tid; k < 3u * m; k += kBlock) lds_acc[k] = 0ull;
     if (tid == 0) s_tail_p[0] = s_tail_p[1] = 0u;  // (here: the workgroup's ray count, u64)
@@ -811,12 +830,12 @@ __global__ __launch_bounds__(kBlock, BVH ? PT_CAND_BVH_WAVES : PT_CAND_WAVES) vo
     const uint32_t room = cap_w < kWaveStackMax ? cap_w : kWaveStackMax;
     const bool room_for_all = 4u * quarter + 3u <= room;  // everything this wave will ever trace fits: nothing to watch
     StreamSlice qs;
-    qs.base = q0.buf + (size_t)(b * 4u + wv) * cap_w * kRayBytes;
+    qs.base = q0.buf + (size_t)(slice * 4u + wv) * cap_w * kRayBytes;
     qs.off_tp = room * 16u;
     qs.off_od1 = room * 32u;
     StreamSlice qpark{};  // BVH: the parked rays of the wave (container 1); DEFER: its glass hits
     if (BVH || DEFER) {
-        qpark.base = q1.buf + (size_t)(b * 4u + wv) * kWaveParkBytes;
+        qpark.base = q1.buf + (size_t)(slice * 4u + wv) * kWaveParkBytes;
         qpark.off_tp = kCandParkCap * 16u;
         qpark.off_od1 = kCandParkCap * 32u;
         p_key = reinterpret_cast<unsigned long long *>(qpark.base + kCandParkCap * kRayBytes);  // (the keys follow the rays)
@@ -1151,15 +1170,22 @@ __global__ __launch_bounds__(kBlock, BVH ? PT_CAND_BVH_WAVES : PT_CAND_WAVES) vo
     PT_PHASE(kPhBarrier);
     __syncthreads();  // every wave of the workgroup is done: the accumulators are complete
     PT_PHASE(kPhOther);
-    if (tid == 0) blk_rays[b] += *reinterpret_cast<unsigned long long *>(s_tail_p);
+    // (atomic adds: the pieces of a stream share its slots - see THE TAPER; sums of integers, whatever their order)
+    if (tid == 0) atomicAdd(&blk_rays[b], *reinterpret_cast<unsigned long long *>(s_tail_p));
     const size_t plane = (size_t)F.n_streams * m;
     for (uint32_t k = tid; k < 3u * mb; k += kBlock) {
         const uint32_t c = k / mb, p = k - c * mb;
         const unsigned long long v = lds_acc[c * m + p];
-        if (v) acc[(size_t)c * plane + (size_t)b * m + p] += v;
+        if (v) atomicAdd(&acc[(size_t)c * plane + (size_t)b * m + p], v);
     }
 #ifdef PT_PHASE_STATS
     phase_end(S.phase_stats, ph_t0, ph_r0);
+#endif
+#ifdef PT_TAIL_STATS
+    if (tid == 0 && slice < kTailStatsCap) {
+        S.tail_stats[2u * slice] = tail_t0;
+        S.tail_stats[2u * slice + 1u] = __builtin_amdgcn_s_memrealtime();
+    }
 #endif
 }
 
@@ -2139,11 +2165,12 @@ void launch_shade(hipStream_t st, uint32_t K, const DevScene &S, const FramePara
                 return ea;                                                                                             \
             }                                                                                                          \
         }                                                                                                              \
-        hipLaunchKernelGGL((k_pass_cand<ST, DF, BV, PR, NL>), dim3(K), dim3(kBlock), lds, st, S2, F, q0, q1, cap, s0, s_here, m, acc, blk_rays, flags); \
+        hipLaunchKernelGGL((k_pass_cand<ST, DF, BV, PR, NL>), dim3(K - n_cut + (n_cut << lg_pieces)), dim3(kBlock), lds, st, S2, F, q0, q1, cap, s0, s_here, m, K - n_cut, lg_pieces, acc, blk_rays, flags); \
     } while (0)
 hipError_t launch_pass_cand_flat(hipStream_t st, uint32_t K, const DevScene &S2, const FrameParams &F, const RayQueue &q0,
-                                 const RayQueue &q1, uint32_t cap, uint32_t s0, uint32_t s_here, uint32_t m, unsigned long long *acc,
-                                 unsigned long long *blk_rays, uint32_t *flags, size_t lds, bool staged, bool defer);
+                                 const RayQueue &q1, uint32_t cap, uint32_t s0, uint32_t s_here, uint32_t m, uint32_t n_cut,
+                                 uint32_t lg_pieces, unsigned long long *acc, unsigned long long *blk_rays, uint32_t *flags, size_t lds,
+                                 bool staged, bool defer);
 #ifdef PT_TU_FLAT
 // the stand-alone intersect step with the candidate scan (PT_FLAG_SEPARATE_KERNELS, scenes without BVH meshes)
 void launch_intersect_cand(hipStream_t st, uint32_t K, const DevScene &S, const LdsLayout &L, const RayQueue &q, float2 *hit,
@@ -2154,8 +2181,9 @@ void launch_intersect_cand(hipStream_t st, uint32_t K, const DevScene &S, const 
         hipLaunchKernelGGL(k_intersect_cand<false>, dim3(K), dim3(kBlock), L.isect_lds, st, S, q, hit, cnt, cap, blk_rays);
 }
 hipError_t launch_pass_cand_flat(hipStream_t st, uint32_t K, const DevScene &S2, const FrameParams &F, const RayQueue &q0,
-                                 const RayQueue &q1, uint32_t cap, uint32_t s0, uint32_t s_here, uint32_t m, unsigned long long *acc,
-                                 unsigned long long *blk_rays, uint32_t *flags, size_t lds, bool staged, bool defer) {
+                                 const RayQueue &q1, uint32_t cap, uint32_t s0, uint32_t s_here, uint32_t m, uint32_t n_cut,
+                                 uint32_t lg_pieces, unsigned long long *acc, unsigned long long *blk_rays, uint32_t *flags, size_t lds,
+                                 bool staged, bool defer) {
     if (staged && defer)
         PT_LAUNCH_CAND(true, true, false, false);
     else if (staged)
@@ -2169,7 +2197,7 @@ hipError_t launch_pass_cand_flat(hipStream_t st, uint32_t K, const DevScene &S2,
 #elif !defined(PT_TU_TILE)
 hipError_t launch_pass(hipStream_t st, uint32_t K, const DevScene &S, const LdsLayout &L, const FrameParams &F, const RayQueue &q0,
                        const RayQueue &q1, uint32_t cap, uint32_t s0, uint32_t s_here, uint32_t m, unsigned long long *acc,
-                       unsigned long long *blk_rays, uint32_t *flags) {
+                       unsigned long long *blk_rays, uint32_t *flags, uint32_t n_cut, uint32_t lg_pieces) {
     // (PT_LDS_PAD=n: k_pass_cand asks for n bytes of LDS it does not use - where does the fifth workgroup of a CU stop fitting?)
     const size_t lds = L.pass_lds + L.pass_pad;
     if (L.pass == kPassCand || L.pass == kPassCandBvh) {
@@ -2177,7 +2205,7 @@ hipError_t launch_pass(hipStream_t st, uint32_t K, const DevScene &S, const LdsL
         S2.bvh_in_lds = L.bvh_in_lds;
         S2.surf_staged = L.surf_staged;
         S2.surf_head = L.surf_head;
-        if (L.pass == kPassCand) return launch_pass_cand_flat(st, K, S2, F, q0, q1, cap, s0, s_here, m, acc, blk_rays, flags, lds, L.staged, L.defer);
+        if (L.pass == kPassCand) return launch_pass_cand_flat(st, K, S2, F, q0, q1, cap, s0, s_here, m, n_cut, lg_pieces, acc, blk_rays, flags, lds, L.staged, L.defer);
         if (L.staged && L.nodes_lds)
             PT_LAUNCH_CAND(true, false, true, true);
         else if (L.staged)
