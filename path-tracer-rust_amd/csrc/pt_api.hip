@@ -76,6 +76,37 @@ struct DevBuf {
         p = nullptr;
         n = 0;
     }
+    // `count` records from the host to [at, at + count) of the buffer (none: no copy); `what` names it in a failure's message
+    int copy_in(size_t at, const T *src, size_t count, const char *what) {
+        const hipError_t e = count ? hipMemcpy(p + at, src, count * sizeof(T), hipMemcpyHostToDevice) : hipSuccess;
+        if (e != hipSuccess) set_error(std::string("hipMemcpy to ") + what + ": " + hipGetErrorString(e));
+        return e == hipSuccess ? PT_OK : PT_ERR_HIP;
+    }
+    // the buffer made large enough for the records and filled with them
+    int upload(const T *src, size_t count, const char *what) {
+        const int rc = ensure(count);
+        return rc ? rc : copy_in(0, src, count, what);
+    }
+    int upload(const std::vector<T> &v, const char *what) { return upload(v.data(), v.size(), what); }
+};
+
+// A table of the scene on the device (host::PT_SCENE_TABLES): the buffer, and the records it holds now - what
+// pt_ctx_table_hashes hashes and DevScene's n_* report.  buf.n is the CAPACITY, which never shrinks; a table that an edit made
+// shorter keeps its allocation.  The count outlives the host's copy (keep_flat drops three tables there).
+template <class T>
+struct DevTable {
+    DevBuf<T> buf;
+    size_t count = 0;
+    int upload(const std::vector<T> &v, const char *name) {  // the table whole
+        const int rc = buf.upload(v, name);
+        count = rc ? 0 : v.size();
+        return rc;
+    }
+    int upload_range(size_t at, const T *src, size_t n, const char *name) {  // its records [at, at + n)
+        if (at <= count && n <= count - at) return buf.copy_in(at, src, n, name);
+        set_error(std::string("internal: a range past the end of the device table ") + name);
+        return PT_ERR_INVALID;
+    }
 };
 
 // The frame pt_ctx_accumulate keeps between calls, and its one owner: host::FrameCounts plus the device planes - the sums, [3]
@@ -299,20 +330,11 @@ struct pt_ctx {
     std::string lds_said[3];  // the layout line say_layout last wrote for each launcher of this context
     pt_camera cam{};
     DevScene scene{};
-    DevBuf<ObjRec> d_objs;
-    DevBuf<ObjPairRec> d_opairs;
-    DevBuf<TriPairRec> d_tris;
-    DevBuf<MatRec> d_mats;
-    DevBuf<TriShade> d_tshade;
-    DevBuf<BvhNode> d_nodes;
-    DevBuf<BvhNode4> d_nodes4;
-    DevBuf<SphPairRec> d_sph;
-    DevBuf<FlatPairRec> d_flat;
-    DevBuf<CandPairRec> d_cand;
-    DevBuf<uint32_t> d_rank_id;
-    DevBuf<uint32_t> d_tri_rank;
-    DevBuf<BvhMeshRec> d_bvh_meshes;
-    DevBuf<SurfRec> d_surf;
+    struct SceneTables {  // one DevTable per table of the list, under the list's name
+#define PT_X(ID, T, name) DevTable<T> name;
+        PT_SCENE_TABLES(PT_X)
+#undef PT_X
+    } tab;
     bool cand_ok = false;
     uint32_t n_bvh_nodes = 0;
     uint32_t n_cus = 0;  // compute units of the device (pt_ctx_create: never 0 afterwards)
@@ -328,8 +350,7 @@ struct pt_ctx {
     // nothing an edit reads (rank_id, surf, tri_rank) - an in-reach edit rewrites one object's records in it and uploads those.
     // Of a mesh with a BVH it keeps the TOPOLOGY (ids, child references, wide_src): the floats of its pair records, shading
     // records and boxes go stale with the first refit, which rewrites the device's.  h_local: every mesh's object-local vertex
-    // box.  refit: the device plans of the meshes moved since the last full build (upload_flat drops them).  table_count: the
-    // records each device table holds (pt_ctx_table_hashes).
+    // box.  refit: the device plans of the meshes moved since the last full build (upload_flat drops them).
     host::FlatScene fs;
     std::vector<host::Reach> h_local;
     struct DevRefit {
@@ -341,7 +362,6 @@ struct pt_ctx {
         uint32_t n_leaves = 0, n_wide = 0;
     };
     std::map<uint32_t, DevRefit> refit;
-    size_t table_count[PT_TABLE_COUNT] = {};
     DevBuf<TriPairRec> d_boxes;
     bool boxes_dirty = true;
     // scratch of the single-ray query entry points (kept across calls: a picking caller sends one ray per click)
@@ -1598,99 +1618,58 @@ static void keep_flat(pt_ctx *c, host::FlatScene &fs) {
     c->fs = std::move(fs);
 }
 
-// The device form of a flattened scene: the tables uploaded and c->scene pointed at them (pt_ctx_set_scene; the rebuilds of
-// pt_ctx_set_camera and pt_ctx_reserve_camera_reach).  Nothing of the context's host state changes here.
-static int upload_flat(pt_ctx *c, const host::FlatScene &fs, const pt_object *objs, uint32_t n_objs, uint32_t n_tris) {
-    int rc;
-    if ((rc = c->d_objs.ensure(fs.objs.size())) || (rc = c->d_opairs.ensure(fs.obj_pairs.size())) || (rc = c->d_tris.ensure(fs.tri_pairs.size())) ||
-        (rc = c->d_mats.ensure(fs.mats.size())) || (rc = c->d_tshade.ensure(fs.tri_shade.size())) ||
-        (rc = c->d_nodes.ensure(fs.bvh_nodes.size())) || (rc = c->d_nodes4.ensure(fs.bvh_nodes4.size())) ||
-        (rc = c->d_sph.ensure(fs.sph_pairs.size())) ||
-        (rc = c->d_flat.ensure(fs.flat_pairs.size())) || (rc = c->d_cand.ensure(fs.cand_pairs.size())) ||
-        (rc = c->d_rank_id.ensure(fs.rank_id.size())) || (rc = c->d_surf.ensure(fs.surf.size())) ||
-        (rc = c->d_tri_rank.ensure(fs.tri_rank.size())) || (rc = c->d_bvh_meshes.ensure(fs.bvh_meshes.size())))
-        return rc;
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    c->refit.clear();  // (the plans name records of the tables before)
-    {
-        const size_t counts[PT_TABLE_COUNT] = {fs.objs.size(),      fs.obj_pairs.size(), fs.tri_pairs.size(),  fs.mats.size(),    fs.tri_shade.size(),
-                                               fs.bvh_nodes.size(), fs.bvh_nodes4.size(), fs.sph_pairs.size(), fs.flat_pairs.size(), fs.cand_pairs.size(),
-                                               fs.rank_id.size(),   fs.surf.size(),      fs.tri_rank.size(),   fs.bvh_meshes.size()};
-        memcpy(c->table_count, counts, sizeof counts);
-    }
-    if (!fs.objs.empty())
-        HIP_TRY(hipMemcpy(c->d_objs.p, fs.objs.data(), fs.objs.size() * sizeof(ObjRec), hipMemcpyHostToDevice));
-    if (!fs.obj_pairs.empty())
-        HIP_TRY(hipMemcpy(c->d_opairs.p, fs.obj_pairs.data(), fs.obj_pairs.size() * sizeof(ObjPairRec),
-                          hipMemcpyHostToDevice));
-    if (!fs.tri_pairs.empty())
-        HIP_TRY(hipMemcpy(c->d_tris.p, fs.tri_pairs.data(), fs.tri_pairs.size() * sizeof(TriPairRec),
-                          hipMemcpyHostToDevice));
-    if (!fs.mats.empty())
-        HIP_TRY(hipMemcpy(c->d_mats.p, fs.mats.data(), fs.mats.size() * sizeof(MatRec), hipMemcpyHostToDevice));
-    if (!fs.tri_shade.empty())
-        HIP_TRY(hipMemcpy(c->d_tshade.p, fs.tri_shade.data(), fs.tri_shade.size() * sizeof(TriShade),
-                          hipMemcpyHostToDevice));
-    if (!fs.bvh_nodes.empty())
-        HIP_TRY(hipMemcpy(c->d_nodes.p, fs.bvh_nodes.data(), fs.bvh_nodes.size() * sizeof(BvhNode),
-                          hipMemcpyHostToDevice));
-    if (!fs.bvh_nodes4.empty())
-        HIP_TRY(hipMemcpy(c->d_nodes4.p, fs.bvh_nodes4.data(), fs.bvh_nodes4.size() * sizeof(BvhNode4), hipMemcpyHostToDevice));
-    c->scene.bvh_nodes4 = c->d_nodes4.p;
-    c->scene.n_bvh_nodes4 = (uint32_t)fs.bvh_nodes4.size();
-    if (!fs.sph_pairs.empty())
-        HIP_TRY(hipMemcpy(c->d_sph.p, fs.sph_pairs.data(), fs.sph_pairs.size() * sizeof(SphPairRec), hipMemcpyHostToDevice));
-    if (!fs.flat_pairs.empty())
-        HIP_TRY(hipMemcpy(c->d_flat.p, fs.flat_pairs.data(), fs.flat_pairs.size() * sizeof(FlatPairRec), hipMemcpyHostToDevice));
-    if (!fs.cand_pairs.empty())
-        HIP_TRY(hipMemcpy(c->d_cand.p, fs.cand_pairs.data(), fs.cand_pairs.size() * sizeof(CandPairRec), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(c->d_rank_id.p, fs.rank_id.data(), fs.rank_id.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    c->scene.sph_pairs = c->d_sph.p;
-    c->scene.flat_pairs = c->d_flat.p;
-    c->scene.cand_pairs = c->d_cand.p;
-    HIP_TRY(hipMemcpy(c->d_surf.p, fs.surf.data(), fs.surf.size() * sizeof(SurfRec), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(c->d_tri_rank.p, fs.tri_rank.data(), fs.tri_rank.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    c->scene.rank_id = c->d_rank_id.p;
-    c->scene.tri_rank = c->d_tri_rank.p;
-    if (!fs.bvh_meshes.empty())
-        HIP_TRY(hipMemcpy(c->d_bvh_meshes.p, fs.bvh_meshes.data(), fs.bvh_meshes.size() * sizeof(BvhMeshRec), hipMemcpyHostToDevice));
-    c->scene.bvh_meshes = c->d_bvh_meshes.p;
-    c->scene.n_bvh_meshes = (uint32_t)fs.bvh_meshes.size();
-    c->scene.surf = c->d_surf.p;
-    c->scene.n_sph_pairs = (uint32_t)fs.sph_pairs.size();
-    c->scene.n_flat_pairs = (uint32_t)fs.flat_pairs.size();
-    c->scene.n_cand_pairs = (uint32_t)fs.cand_pairs.size();
+// c->scene pointed at the device tables: every pointer, and every n_* that is a table's length
+static void bind_tables(pt_ctx *c) {
+#define PT_X(ID, T, name) c->scene.name = c->tab.name.buf.p;
+    PT_SCENE_TABLES(PT_X)
+#undef PT_X
+    c->scene.n_bvh_nodes = c->n_bvh_nodes = (uint32_t)c->tab.bvh_nodes.count;
+    c->scene.n_bvh_nodes4 = (uint32_t)c->tab.bvh_nodes4.count;
+    c->scene.n_bvh_meshes = (uint32_t)c->tab.bvh_meshes.count;
+    c->scene.n_sph_pairs = (uint32_t)c->tab.sph_pairs.count;
+    c->scene.n_flat_pairs = (uint32_t)c->tab.flat_pairs.count;
+    c->scene.n_cand_pairs = (uint32_t)c->tab.cand_pairs.count;
+}
+
+// the candidate scan's counts, and whether the scene uses it: cand_scan_for reads c->n_bvh_nodes (bind_tables) and
+// scene.bvh_in_lds (upload_flat), which are set by now
+static void bind_cand_counts(pt_ctx *c, const host::FlatScene &fs) {
     c->scene.n_other_pairs = fs.n_other_pairs;
     c->scene.n_flat_exact = fs.n_flat_exact;
     for (int k = 0; k < 3; ++k) c->scene.n_flat_exact_axis[k] = fs.n_flat_exact_axis[k];
-    c->scene.nodes_in_lds_ok = c->tune.nodes_lds ? 1u : 0u;
-    set_glass_defer(c, objs, n_objs);
     c->cand_ok = fs.cand_ok;
-    c->scene.cand_staged = 0u;
-    c->scene.surf_staged = 0u;
-    c->scene.surf_head = 0u;
+    c->scene.cand_scan = cand_scan_for(c, 0u);
+}
+
+// instrumented builds only (PT_WALK_STATS, PT_PHASE_STATS, PT_TAIL_STATS): a zeroed table of n counters, made with the
+// context's first scene and never freed
+static int ensure_stats(unsigned long long **p, size_t n) {
+    if (*p) return PT_OK;
+    HIP_TRY(hipMalloc((void **)p, n * sizeof(unsigned long long)));
+    HIP_TRY(hipMemset(*p, 0, n * sizeof(unsigned long long)));
+    return PT_OK;
+}
+
+// The device form of a flattened scene: the tables uploaded and c->scene pointed at them (pt_ctx_set_scene; the rebuilds of
+// pt_ctx_set_camera and pt_ctx_reserve_camera_reach).  Nothing of the context's host state changes here.  Every allocation
+// comes before the stream is waited for, every copy after.
+static int upload_flat(pt_ctx *c, const host::FlatScene &fs, const pt_object *objs, uint32_t n_objs, uint32_t n_tris) {
+    int rc;
+#define PT_X(ID, T, name) if ((rc = c->tab.name.buf.ensure(fs.name.size()))) return rc;
+    PT_SCENE_TABLES(PT_X)
+#undef PT_X
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->refit.clear();  // (the plans name records of the tables before)
+#define PT_X(ID, T, name) if ((rc = c->tab.name.upload(fs.name, #name))) return rc;
+    PT_SCENE_TABLES(PT_X)
+#undef PT_X
+    bind_tables(c);
+    c->scene.n_objs = n_objs;
+    c->scene.n_tris = n_tris;
+    // what the tuning and the trees' shape decide
+    c->scene.leaf_quorum = c->tune.leaf_quorum;  // mesh.json: 65 (all) 11.7, 32 12.5, 16 12.8, 8 12.8, 1 11.0 G bounces/s
     c->scene.walk_queue_cap = c->tune.walk_queue_cap;
-#ifdef PT_WALK_STATS
-    if (!c->scene.stats) {
-        HIP_TRY(hipMalloc((void **)&c->scene.stats, 16 * sizeof(unsigned long long)));  // instrumented builds only: never freed
-        HIP_TRY(hipMemset(c->scene.stats, 0, 16 * sizeof(unsigned long long)));
-    }
-#endif
-#ifdef PT_PHASE_STATS
-    if (!c->scene.phase_stats) {  // instrumented builds only: never freed
-        HIP_TRY(hipMalloc((void **)&c->scene.phase_stats, (kPhCount * 3 + 2) * sizeof(unsigned long long)));
-        HIP_TRY(hipMemset(c->scene.phase_stats, 0, (kPhCount * 3 + 2) * sizeof(unsigned long long)));
-    }
-#endif
-#ifdef PT_TAIL_STATS
-    if (!c->scene.tail_stats) {  // instrumented builds only: never freed
-        HIP_TRY(hipMalloc((void **)&c->scene.tail_stats, 2 * (size_t)kTailStatsCap * sizeof(unsigned long long)));
-        HIP_TRY(hipMemset(c->scene.tail_stats, 0, 2 * (size_t)kTailStatsCap * sizeof(unsigned long long)));
-    }
-#endif
-    c->n_bvh_nodes = (uint32_t)fs.bvh_nodes.size();
-    c->scene.bvh_nodes = c->d_nodes.p;
-    c->scene.n_bvh_nodes = c->n_bvh_nodes;
+    c->scene.nodes_in_lds_ok = c->tune.nodes_lds ? 1u : 0u;
     c->scene.planar = 1u;
     {
         // bit 1: node and leaf references fit 16 bits (u16 traversal stacks); bit 0: nodes staged in LDS by every
@@ -1700,17 +1679,22 @@ static int upload_flat(pt_ctx *c, const host::FlatScene &fs, const pt_object *ob
         const bool stage = ref16 && c->n_bvh_nodes <= kBvhMaxLdsNodes && c->tune.bvh_lds;
         c->scene.bvh_in_lds = (ref16 ? 2u : 0u) | (stage ? 1u : 0u);
     }
-    c->scene.cand_scan = cand_scan_for(c, 0u);
     c->scene.bvh_pair_base = fs.bvh_pair_base;
     c->scene.bvh_stack = fs.bvh_stack;
-    c->scene.leaf_quorum = c->tune.leaf_quorum;  // mesh.json: 65 (all) 11.7, 32 12.5, 16 12.8, 8 12.8, 1 11.0 G bounces/s
-    c->scene.objs = c->d_objs.p;
-    c->scene.obj_pairs = c->d_opairs.p;
-    c->scene.tri_pairs = c->d_tris.p;
-    c->scene.mats = c->d_mats.p;
-    c->scene.tri_shade = c->d_tshade.p;
-    c->scene.n_objs = n_objs;
-    c->scene.n_tris = n_tris;
+    c->scene.cand_staged = 0u;
+    c->scene.surf_staged = 0u;
+    c->scene.surf_head = 0u;
+    set_glass_defer(c, objs, n_objs);
+    bind_cand_counts(c, fs);
+#ifdef PT_WALK_STATS
+    if ((rc = ensure_stats(&c->scene.stats, 16))) return rc;
+#endif
+#ifdef PT_PHASE_STATS
+    if ((rc = ensure_stats(&c->scene.phase_stats, kPhCount * 3 + 2))) return rc;
+#endif
+#ifdef PT_TAIL_STATS
+    if ((rc = ensure_stats(&c->scene.tail_stats, 2 * (size_t)kTailStatsCap))) return rc;
+#endif
     return PT_OK;
 }
 
@@ -1814,22 +1798,11 @@ static int refit_plan_for(pt_ctx *c, uint32_t index, pt_ctx::DevRefit **out) {
     pt_ctx::DevRefit &d = c->refit[index];
     const pt_object &o = c->h_objs[index];
     int rc;
-    if ((rc = d.local.ensure(o.tri_count)) || (rc = d.leaves.ensure(plan.leaves.size())) || (rc = d.nodes.ensure(plan.nodes.size())) ||
-        (rc = d.wide.ensure(plan.wide.size()))) {
+    if ((rc = d.local.upload(c->h_tris.data() + o.tri_offset, o.tri_count, "a refit plan's triangles")) ||
+        (rc = d.leaves.upload(plan.leaves, "a refit plan's leaves")) || (rc = d.nodes.upload(plan.nodes, "a refit plan's nodes")) ||
+        (rc = d.wide.upload(plan.wide, "a refit plan's wide slots"))) {
         c->refit.erase(index);
         return rc;
-    }
-    hipError_t e = hipMemcpy(d.local.p, c->h_tris.data() + o.tri_offset, (size_t)o.tri_count * sizeof(pt_triangle), hipMemcpyHostToDevice);
-    if (e == hipSuccess && !plan.leaves.empty())
-        e = hipMemcpy(d.leaves.p, plan.leaves.data(), plan.leaves.size() * sizeof(RefitLeaf), hipMemcpyHostToDevice);
-    if (e == hipSuccess && !plan.nodes.empty())
-        e = hipMemcpy(d.nodes.p, plan.nodes.data(), plan.nodes.size() * sizeof(RefitNode), hipMemcpyHostToDevice);
-    if (e == hipSuccess && !plan.wide.empty())
-        e = hipMemcpy(d.wide.p, plan.wide.data(), plan.wide.size() * sizeof(RefitWide), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        c->refit.erase(index);
-        set_error(std::string("hipMemcpy of a refit plan: ") + hipGetErrorString(e));
-        return PT_ERR_HIP;
     }
     d.level_begin = plan.level_begin;
     d.n_leaves = (uint32_t)plan.leaves.size();
@@ -1844,70 +1817,50 @@ static int upload_object_edit(pt_ctx *c, uint32_t index, bool moved, bool materi
     const host::FlatScene &fs = c->fs;
     const pt_object &o = c->h_objs[index];
     const uint32_t n_objs = (uint32_t)c->h_objs.size();
+    pt_ctx::SceneTables &t = c->tab;
+    int rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipMemcpy(c->d_objs.p + index, &fs.objs[index], sizeof(ObjRec), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(c->d_mats.p + index, &fs.mats[index], sizeof(MatRec), hipMemcpyHostToDevice));
+    if ((rc = t.objs.upload_range(index, &fs.objs[index], 1, "objs")) || (rc = t.mats.upload_range(index, &fs.mats[index], 1, "mats")))
+        return rc;
     if (moved) {
-        HIP_TRY(hipMemcpy(c->d_opairs.p + e.obj_pair, &fs.obj_pairs[e.obj_pair], sizeof(ObjPairRec), hipMemcpyHostToDevice));
+        if ((rc = t.obj_pairs.upload_range(e.obj_pair, &fs.obj_pairs[e.obj_pair], 1, "obj_pairs"))) return rc;
         if (e.on_device) {
-            HIP_TRY(hipMemcpy(c->d_bvh_meshes.p + e.bvh_mesh, &fs.bvh_meshes[e.bvh_mesh], sizeof(BvhMeshRec), hipMemcpyHostToDevice));
+            if ((rc = t.bvh_meshes.upload_range(e.bvh_mesh, &fs.bvh_meshes[e.bvh_mesh], 1, "bvh_meshes"))) return rc;
         } else {
             // the candidate scan's tables whole (a few records per sphere and listed mesh): a translation can, through rounding,
             // change which records are flat, their order and their count
-            int rc;
-            if ((rc = c->d_sph.ensure(fs.sph_pairs.size())) || (rc = c->d_flat.ensure(fs.flat_pairs.size())) ||
-                (rc = c->d_cand.ensure(fs.cand_pairs.size())))
+            if ((rc = t.sph_pairs.upload(fs.sph_pairs, "sph_pairs")) || (rc = t.flat_pairs.upload(fs.flat_pairs, "flat_pairs")) ||
+                (rc = t.cand_pairs.upload(fs.cand_pairs, "cand_pairs")))
                 return rc;
-            if (!fs.sph_pairs.empty())
-                HIP_TRY(hipMemcpy(c->d_sph.p, fs.sph_pairs.data(), fs.sph_pairs.size() * sizeof(SphPairRec), hipMemcpyHostToDevice));
-            if (!fs.flat_pairs.empty())
-                HIP_TRY(hipMemcpy(c->d_flat.p, fs.flat_pairs.data(), fs.flat_pairs.size() * sizeof(FlatPairRec), hipMemcpyHostToDevice));
-            if (!fs.cand_pairs.empty())
-                HIP_TRY(hipMemcpy(c->d_cand.p, fs.cand_pairs.data(), fs.cand_pairs.size() * sizeof(CandPairRec), hipMemcpyHostToDevice));
-            c->scene.sph_pairs = c->d_sph.p;
-            c->scene.flat_pairs = c->d_flat.p;
-            c->scene.cand_pairs = c->d_cand.p;
-            c->scene.n_sph_pairs = (uint32_t)fs.sph_pairs.size();
-            c->scene.n_flat_pairs = (uint32_t)fs.flat_pairs.size();
-            c->scene.n_cand_pairs = (uint32_t)fs.cand_pairs.size();
-            c->scene.n_other_pairs = fs.n_other_pairs;
-            c->scene.n_flat_exact = fs.n_flat_exact;
-            for (int k = 0; k < 3; ++k) c->scene.n_flat_exact_axis[k] = fs.n_flat_exact_axis[k];
-            c->cand_ok = fs.cand_ok;
-            c->scene.cand_scan = cand_scan_for(c, 0u);
-            c->table_count[PT_TABLE_SPH_PAIRS] = fs.sph_pairs.size();
-            c->table_count[PT_TABLE_FLAT_PAIRS] = fs.flat_pairs.size();
-            c->table_count[PT_TABLE_CAND_PAIRS] = fs.cand_pairs.size();
+            bind_tables(c);
+            bind_cand_counts(c, fs);
             if (o.kind == PT_MESH && o.tri_count != 0u) {
                 const ObjRec &r = fs.objs[index];
-                HIP_TRY(hipMemcpy(c->d_tris.p + r.pair_begin, &fs.tri_pairs[r.pair_begin], (size_t)r.pair_count * sizeof(TriPairRec),
-                                  hipMemcpyHostToDevice));
-                HIP_TRY(hipMemcpy(c->d_tshade.p + o.tri_offset, &fs.tri_shade[o.tri_offset], (size_t)o.tri_count * sizeof(TriShade),
-                                  hipMemcpyHostToDevice));
+                if ((rc = t.tri_pairs.upload_range(r.pair_begin, fs.tri_pairs.data() + r.pair_begin, r.pair_count, "tri_pairs")) ||
+                    (rc = t.tri_shade.upload_range(o.tri_offset, fs.tri_shade.data() + o.tri_offset, o.tri_count, "tri_shade")))
+                    return rc;
             }
         }
     }
-    if (!e.surf.empty())
-        HIP_TRY(hipMemcpy(c->d_surf.p + e.rank, e.surf.data(), e.surf.size() * sizeof(SurfRec), hipMemcpyHostToDevice));
-    if (!e.tail.empty())
-        HIP_TRY(hipMemcpy(c->d_surf.p + e.tail_at, e.tail.data(), e.tail.size() * sizeof(SurfRec), hipMemcpyHostToDevice));
+    if ((rc = t.surf.upload_range(e.rank, e.surf.data(), e.surf.size(), "surf")) ||
+        (rc = t.surf.upload_range(e.tail_at, e.tail.data(), e.tail.size(), "surf")))
+        return rc;
     if (e.on_device) {
         if (moved) {
             pt_ctx::DevRefit *d = nullptr;
-            const int rc = refit_plan_for(c, index, &d);
-            if (rc) return rc;
+            if ((rc = refit_plan_for(c, index, &d))) return rc;
             RefitTables T{};
-            T.tri_pairs = c->d_tris.p, T.tri_shade = c->d_tshade.p, T.surf = c->d_surf.p;
-            T.nodes = c->d_nodes.p, T.nodes4 = c->d_nodes4.p, T.tri_rank = c->d_tri_rank.p;
+            T.tri_pairs = t.tri_pairs.buf.p, T.tri_shade = t.tri_shade.buf.p, T.surf = t.surf.buf.p;
+            T.nodes = t.bvh_nodes.buf.p, T.nodes4 = t.bvh_nodes4.buf.p, T.tri_rank = t.tri_rank.buf.p;
             T.local = d->local.p, T.tri_offset = o.tri_offset;
             T.px = o.position[0], T.py = o.position[1], T.pz = o.position[2];
             T.scene_R = e.scene_R;
             launch_refit_leaves(c->stream, T, d->leaves.p, d->n_leaves);
             for (size_t h = 0; h + 1 < d->level_begin.size(); ++h)
-                launch_refit_nodes(c->stream, c->d_nodes.p, d->nodes.p + d->level_begin[h], d->level_begin[h + 1] - d->level_begin[h]);
-            launch_refit_wide(c->stream, c->d_nodes4.p, c->d_nodes.p, d->wide.p, d->n_wide);
+                launch_refit_nodes(c->stream, T.nodes, d->nodes.p + d->level_begin[h], d->level_begin[h + 1] - d->level_begin[h]);
+            launch_refit_wide(c->stream, T.nodes4, T.nodes, d->wide.p, d->n_wide);
         }
-        if (material) launch_refit_materials(c->stream, c->d_surf.p + e.rank, o.tri_count, fs.mats[index]);
+        if (material) launch_refit_materials(c->stream, t.surf.buf.p + e.rank, o.tri_count, fs.mats[index]);
         HIP_TRY(hipGetLastError());
     }
     set_glass_defer(c, c->h_objs.data(), n_objs);
@@ -1962,17 +1915,13 @@ int pt_ctx_table_hashes(pt_ctx *c, uint64_t out[PT_TABLE_COUNT]) {
     if (!c->has_scene) return refuse("no scene set");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    const void *src[PT_TABLE_COUNT] = {c->d_objs.p,  c->d_opairs.p, c->d_tris.p, c->d_mats.p,    c->d_tshade.p, c->d_nodes.p,    c->d_nodes4.p,
-                                       c->d_sph.p,   c->d_flat.p,   c->d_cand.p, c->d_rank_id.p, c->d_surf.p,   c->d_tri_rank.p, c->d_bvh_meshes.p};
-    const size_t width[PT_TABLE_COUNT] = {sizeof(ObjRec),     sizeof(ObjPairRec),  sizeof(TriPairRec),  sizeof(MatRec),   sizeof(TriShade),
-                                          sizeof(BvhNode),    sizeof(BvhNode4),    sizeof(SphPairRec),  sizeof(FlatPairRec), sizeof(CandPairRec),
-                                          sizeof(uint32_t),   sizeof(SurfRec),     sizeof(uint32_t),    sizeof(BvhMeshRec)};
     std::vector<uint8_t> h;
-    for (int t = 0; t < PT_TABLE_COUNT; ++t) {
-        h.resize(c->table_count[t] * width[t]);
-        if (!h.empty()) HIP_TRY(hipMemcpy(h.data(), src[t], h.size(), hipMemcpyDeviceToHost));
-        out[t] = pt_siphash(1, 3, 0, 0, h.data(), h.size());
-    }
+#define PT_X(ID, T, name)                                                                                 \
+    h.resize(c->tab.name.count * sizeof(T));                                                              \
+    if (!h.empty()) HIP_TRY(hipMemcpy(h.data(), c->tab.name.buf.p, h.size(), hipMemcpyDeviceToHost));     \
+    out[PT_TABLE_##ID] = pt_siphash(1, 3, 0, 0, h.data(), h.size());
+    PT_SCENE_TABLES(PT_X)
+#undef PT_X
     return PT_OK;
 }
 
@@ -2710,10 +2659,9 @@ static int upload_boxes(pt_ctx *c) {
     std::vector<TriPairRec> recs(6 * (n_objs ? n_objs : 1), TriPairRec{});
     for (size_t i = 0; i < n_objs; ++i)
         if (c->h_objs[i].kind == PT_MESH) host::box_pair_records(&c->h_boxes[12 * i], c->h_objs[i].position, &recs[6 * i]);
-    int rc = c->d_boxes.ensure(recs.size());
-    if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipMemcpy(c->d_boxes.p, recs.data(), recs.size() * sizeof(TriPairRec), hipMemcpyHostToDevice));
+    const int rc = c->d_boxes.upload(recs, "the bounding boxes");
+    if (rc) return rc;
     c->boxes_dirty = false;
     return PT_OK;
 }

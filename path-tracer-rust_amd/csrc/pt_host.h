@@ -48,6 +48,35 @@ struct FlatScene {
     uint32_t bvh_pair_span = 0;  // leaves lie in [bvh_pair_base, bvh_pair_base + bvh_pair_span)
 };
 
+// THE SCENE'S DEVICE TABLES, written down once: X(PT_TABLE_* suffix, record type, name).  The name is the FlatScene member's, the
+// DevScene pointer's and the device table's in pt_ctx (pt_api.hip: SceneTables).  What uploads, binds, hashes or compares every
+// table expands this list: pt_api.hip, host/object_check.cpp.
+#define PT_SCENE_TABLES(X)                 \
+    X(OBJS, ObjRec, objs)                  \
+    X(OBJ_PAIRS, ObjPairRec, obj_pairs)    \
+    X(TRI_PAIRS, TriPairRec, tri_pairs)    \
+    X(MATS, MatRec, mats)                  \
+    X(TRI_SHADE, TriShade, tri_shade)      \
+    X(BVH_NODES, BvhNode, bvh_nodes)       \
+    X(BVH_NODES4, BvhNode4, bvh_nodes4)    \
+    X(SPH_PAIRS, SphPairRec, sph_pairs)    \
+    X(FLAT_PAIRS, FlatPairRec, flat_pairs) \
+    X(CAND_PAIRS, CandPairRec, cand_pairs) \
+    X(RANK_ID, uint32_t, rank_id)          \
+    X(SURF, SurfRec, surf)                 \
+    X(TRI_RANK, uint32_t, tri_rank)        \
+    X(BVH_MESHES, BvhMeshRec, bvh_meshes)
+#define PT_X(ID, T, name) PT_TABLE_##ID,
+constexpr int kSceneTableIds[] = {PT_SCENE_TABLES(PT_X)};
+#undef PT_X
+constexpr bool scene_tables_in_enum_order() {
+    for (int i = 0; i < PT_TABLE_COUNT; ++i)
+        if (kSceneTableIds[i] != i) return false;
+    return true;
+}
+static_assert(sizeof kSceneTableIds / sizeof kSceneTableIds[0] == PT_TABLE_COUNT && scene_tables_in_enum_order(),
+              "PT_SCENE_TABLES lists the tables of ptrace.h's PT_TABLE_* enum, every one, in its order");
+
 // CameraData::{lens_center, orthogonals} — src/render/mod.rs:211-232
 void camera_basis(const pt_camera &cam, float lens_center[3], float su[3], float sv[3]);
 // Mesh::new bounding sphere — src/render/mod.rs:450-499

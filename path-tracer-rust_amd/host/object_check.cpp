@@ -97,31 +97,16 @@ static bool flatten(const Scene &sc, FlatScene &fs, const Reach *B, Reach *used)
 
 // every table and count; the first one that differs is named on stderr
 static bool same_tables(const FlatScene &a, const FlatScene &b) {
-    const struct {
-        const char *name;
-        bool same;
-    } t[] = {{"objs", same_table(a.objs, b.objs)},
-             {"obj_pairs", same_table(a.obj_pairs, b.obj_pairs)},
-             {"tri_pairs", same_table(a.tri_pairs, b.tri_pairs)},
-             {"mats", same_table(a.mats, b.mats)},
-             {"tri_shade", same_table(a.tri_shade, b.tri_shade)},
-             {"bvh_nodes", same_table(a.bvh_nodes, b.bvh_nodes)},
-             {"bvh_nodes4", same_table(a.bvh_nodes4, b.bvh_nodes4)},
-             {"sph_pairs", same_table(a.sph_pairs, b.sph_pairs)},
-             {"flat_pairs", same_table(a.flat_pairs, b.flat_pairs)},
-             {"cand_pairs", same_table(a.cand_pairs, b.cand_pairs)},
-             {"rank_id", same_table(a.rank_id, b.rank_id)},
-             {"surf", same_table(a.surf, b.surf)},
-             {"tri_rank", same_table(a.tri_rank, b.tri_rank)},
-             {"bvh_meshes", same_table(a.bvh_meshes, b.bvh_meshes)},
-             {"the counts", a.n_other_pairs == b.n_other_pairs && a.n_flat_exact == b.n_flat_exact &&
-                  std::equal(a.n_flat_exact_axis, a.n_flat_exact_axis + 3, b.n_flat_exact_axis) && a.cand_ok == b.cand_ok}};
-    for (const auto &x : t)
-        if (!x.same) {
-            fprintf(stderr, "same_tables: %s differ\n", x.name);
-            return false;
-        }
-    return true;
+    const char *differ = nullptr;
+#define PT_X(ID, T, name) \
+    if (!differ && !same_table(a.name, b.name)) differ = #name;
+    PT_SCENE_TABLES(PT_X)
+#undef PT_X
+    if (!differ && !(a.n_other_pairs == b.n_other_pairs && a.n_flat_exact == b.n_flat_exact &&
+                     std::equal(a.n_flat_exact_axis, a.n_flat_exact_axis + 3, b.n_flat_exact_axis) && a.cand_ok == b.cand_ok))
+        differ = "the counts";
+    if (differ) fprintf(stderr, "same_tables: %s differ\n", differ);
+    return !differ;
 }
 
 // the tables that hold no tree: equal whatever the trees are
