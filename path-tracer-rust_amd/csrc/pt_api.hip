@@ -234,7 +234,7 @@ struct Tuning {
     uint64_t streams = 0;      // PT_STREAMS: ray streams per pass (0 = derived from the frame)
     uint32_t per_stream = 0;   // PT_PER_STREAM: primary rays per stream and pass that k_pass_cand's stream count aims at (0 = default)
     int64_t taper_cut = -1;    // PT_TAPER_CUT=n: k_pass_cand's launches run their last n streams in pieces (host::plan_taper; 0 = off,
-                               // unset = the default of render_wavefront)
+                               // unset = the default, host::kTaper*)
     uint32_t taper_pieces = 0; // PT_TAPER_PIECES=c: ... c pieces each, a power of two (unset = the default)
     uint64_t rays_per_pass = 0;  // PT_RAYS_PER_PASS: the default of pt_config.rays_per_pass (probes; 0 = the library's)
     bool glass_defer = false;    // PT_GLASS_DEFER=1: k_pass_cand collects glass hits per wave and shades them 64 at a time (A/B: it
@@ -251,15 +251,6 @@ struct Tuning {
                                   // load them through the caches (same bytes; 0 = every level direct, 128 = every level LDS)
     uint32_t debug = 0;
 };
-// The taper's defaults (render_wavefront; measured: DESIGN.md section 4, profiles/r04_taper_sweep.txt): streams cut in HALF rounds of
-// resident workgroups (0: no taper), pieces per cut stream, and the primaries per stream and pass asked for with it (0: plan_pass's)
-// - without walks and with.  cornell 1024x768 @4096, one session, 448.0 ms without: one round in 4 pieces 438.1 ms at 24 Ki primaries
-// per stream, 439.0 at 32 Ki, 439.8 at 20 Ki; half a round in 8 pieces 436.8 - but in another session (449.9 without) half a round
-// 440.4 and a third of a round 446.9: too close to where the cut stops paying, so a whole round it is.  mesh.json @1024, 194.6 ms
-// without: half a round in 4 pieces at its own stream length 191.6, a whole round 192.4, 8 pieces 194.6; longer streams (32 Ki) gain
-// nothing there (192.0) and lose 3 % with a cut of half a round.
-constexpr uint32_t kTaperCutHalfRounds = 2, kTaperPieces = 4, kTaperPerStream = 24576;
-constexpr uint32_t kTaperCutHalfRoundsBvh = 1, kTaperPiecesBvh = 4, kTaperPerStreamBvh = 0;
 constexpr uint32_t kDnLdsMaxStepDefault = 4;  // measured: LDS wins at steps 1, 2, 4 and loses from 8 on
 static Tuning read_tuning() {
     Tuning t;
@@ -698,6 +689,20 @@ struct PassPacer {
     }
 };
 
+// The device buffers of a wavefront frame planned as `plan`.  PT_ERR_NOMEM_INTERNAL: out of device memory.
+static int ensure_pass_buffers(pt_ctx *c, const FrameForm &form, const host::FramePlan &plan) {
+    const host::PassPlan &p = plan.pass;
+    int rc = c->q_buf[0].ensure(p.bytes0 + plan.taper.extra0, true);
+    if (!rc && p.bytes1) rc = c->q_buf[1].ensure(p.bytes1 + plan.taper.extra1, true);
+    // only the three-kernel form needs the hit records: k_pass keeps hits in registers
+    if (!rc && !form.one_kernel) rc = c->hit.ensure((size_t)p.K * p.cap, true);
+    if (!rc) rc = c->cnt.ensure((size_t)kLevels * p.K, true);
+    if (!rc) rc = c->flags.ensure(1, true);
+    if (!rc) rc = c->blk_rays.ensure(p.K, true);
+    if (!rc) rc = c->acc.ensure(3 * (size_t)p.K * p.m, true);
+    return rc;
+}
+
 // Samples [s_first, cfg->spp) of every pixel of the part; the accumulators start from `held` (NULL: from zero).
 int render_wavefront(pt_ctx *c, const FrameForm &form, const pt_config *cfg, const FrameParams &frame, hipStream_t st,
                      const volatile uint8_t *cancel, pt_progress_fn cb, void *user, pt_stats &stats, uint32_t s_first,
@@ -705,142 +710,52 @@ int render_wavefront(pt_ctx *c, const FrameForm &form, const pt_config *cfg, con
     const DevScene &S = form.scene;
     FrameParams F = frame;
     const uint64_t npix = F.npix;
-    const uint32_t spp_left = cfg->spp - s_first;  // samples per pixel this call traces
-    // Level-by-level forms (k_pass, k_pass_bvh, the separate kernels): 96 Mi primary rays per pass by default, 36 GB of ray
-    // queues (two containers x 4 slots per primary ray x 40 B) of the 288 GB of HBM - fewer, longer launches: cornell 1024x768
-    // @4096 spp 32 Mi 35.7, 48 Mi 35.7, 64 Mi 36.2, 96 Mi 36.4 G bounces/s (a launch ends with its slowest streams).
-    // k_pass_cand (`stack_form`) keeps a wave's waiting rays on a stack of at most kWaveStackMax slots whatever the pass holds:
-    // its passes are sized by TIME (PassPacer) - 512 Mi primary rays at most - and its memory is the streams' (K x 4 waves x
-    // stack x 40 B: 4.0 GB for the 24 576 streams of the bench frame's pass; small passes need less: 4 x pow2(primaries per
-    // wave) slots per stream).
-    // The default is what the DEVICE can give: 85 % of the free memory (plus what this context's queues hold already),
-    // divided by the contexts that share the device in this call (PT_FLAG_PIPELINES, ranks of pt_render_multi on one GPU),
-    // or pt_ctx_set_memory_budget's figure - at 352 B per primary ray for the level-by-level forms (queues + hit records of
-    // the three-kernel form), by the streams' stacks for k_pass_cand; and whatever was asked for, a failed allocation halves
-    // the pass and tries again: passes only change how the samples are batched, never the image.
-    const bool stack_form = form.stack_form;
-    uint64_t want = cfg->rays_per_pass ? cfg->rays_per_pass : c->tune.rays_per_pass;
-    size_t stack_budget = 0;  // stack_form, default pass size: what the streams' stacks may take
-    if (!want) {
-        const uint64_t dflt = stack_form ? (512u << 20) : (96u << 20);
-        want = dflt;
-        size_t held = c->hit.bytes();
-        for (int w = 0; w < 2; ++w) held += c->q_buf[w].bytes();
-        size_t avail = c->mem_budget;
-        if (!avail) {
-            size_t mem_free = 0, mem_total = 0;
-            if (hipMemGetInfo(&mem_free, &mem_total) == hipSuccess) avail = (size_t)((double)(mem_free + held) * 0.85) / (c->mem_share ? c->mem_share : 1u);
-        }
-        if (avail && !stack_form) {
-            const uint64_t fit = avail / 352u;
-            if (fit < want) want = fit;
-        }
-        if (stack_form) stack_budget = avail;
-        if (c->mem_share > 1u && want > dflt / c->mem_share) want = dflt / c->mem_share;  // (co-resident contexts also share the chip)
-        if (want < npix) want = npix;  // one sample per pixel and pass at least
-    } else if (c->mem_budget) {
-        // an explicit pass size under an explicit budget (pt_ctx_set_memory_budget): the budget wins - the pass is cut to what
-        // it allows (level-by-level forms: 352 B per primary ray; k_pass_cand: its streams' stacks, plan_pass retries with
-        // smaller passes).  Without a budget an explicit size is taken as given and only a failed allocation halves it.
-        if (!stack_form) {
-            const uint64_t fit = c->mem_budget / 352u;
-            if (fit < want) want = fit;
-        } else {
-            stack_budget = c->mem_budget;
-        }
-        if (want < npix) want = npix;
+    // THE FRAME'S PLAN - passes, streams, slices, k_pass_cand's taper - is host arithmetic (pt_host.h: first_request, plan_frame,
+    // shrink_request).  A default pass is cut to what the DEVICE can give: the free memory plus what this context's queues hold
+    // already, shared among the contexts of this call (PT_FLAG_PIPELINES, ranks of pt_render_multi on one GPU).
+    host::FramePlanIn pin;
+    pin.pass.npix = npix;
+    pin.pass.spp = cfg->spp - s_first;  // samples per pixel this call traces
+    pin.pass.stack_form = form.stack_form;
+    pin.pass.stack_park = form.stack_park;
+    pin.pass.cand_scan = S.cand_scan != 0u;
+    pin.pass.has_bvh = S.n_bvh_nodes != 0u;
+    pin.pass.streams = c->tune.streams;
+    pin.pass.per_stream = c->tune.per_stream;
+    pin.pass.wave_stack = c->tune.wave_stack;
+    pin.pass.n_cus = c->n_cus;
+    pin.rays_per_pass = cfg->rays_per_pass;
+    pin.rays_per_pass_tuned = c->tune.rays_per_pass;
+    pin.mem_budget = c->mem_budget;
+    pin.mem_share = c->mem_share;
+    pin.probe = F.probe != 0u;
+    pin.taper_cut = c->tune.taper_cut;
+    pin.taper_pieces = c->tune.taper_pieces;
+    pin.scene = S;
+    pin.lds_pad = c->tune.lds_pad;
+    if (!pin.rays_per_pass && !pin.rays_per_pass_tuned && !pin.mem_budget) {
+        size_t mem_free = 0, mem_total = 0;
+        if (hipMemGetInfo(&mem_free, &mem_total) == hipSuccess)
+            pin.mem_avail = mem_free + c->hit.bytes() + c->q_buf[0].bytes() + c->q_buf[1].bytes();
     }
-    uint32_t spp_pass = 0, m = 0, K = 0, cap = 0;
-    // k_pass_cand's TAPER (host::plan_taper; the kernel: "THE TAPER"): the launch's last streams in pieces, and - only then - longer
-    // streams.  The knobs by hand (PT_TAPER_CUT, PT_TAPER_PIECES, PT_PER_STREAM) are taken as given; the defaults are kTaper* (above read_tuning).
-    // Never for the PROBE instances, whose frames are a handful of rays.
-    const uint64_t resident =
-        (uint64_t)c->n_cus * (!stack_form ? 4u : (S.n_bvh_nodes == 0u ? (uint32_t)PT_CAND_WAVES : (uint32_t)PT_CAND_BVH_WAVES));
-    const bool walks = S.n_bvh_nodes != 0u;
-    const bool taper_forced = c->tune.taper_cut >= 0;
-    const uint64_t cut_dflt = (uint64_t)(walks ? kTaperCutHalfRoundsBvh : kTaperCutHalfRounds) * resident / 2u;
-    const uint32_t taper_cut = (uint32_t)std::min<uint64_t>(taper_forced ? (uint64_t)c->tune.taper_cut : cut_dflt, 0xffffffffu);
-    const uint32_t taper_pieces = c->tune.taper_pieces ? c->tune.taper_pieces : (walks ? kTaperPiecesBvh : kTaperPieces);
-    bool try_taper = stack_form && form.one_kernel && !F.probe && taper_cut != 0u && taper_pieces >= 2u;
-    host::Taper taper;
+    host::FrameRequest req = host::first_request(pin);
+    host::FramePlan plan;
     for (;;) {
-        host::PassPlanIn pin;
-        pin.npix = npix;
-        pin.spp = spp_left;
-        pin.want = want;
-        pin.want_is_default = !cfg->rays_per_pass;
-        pin.stack_form = stack_form;
-        pin.stack_park = form.stack_park;
-        pin.cand_scan = S.cand_scan != 0u;
-        pin.has_bvh = S.n_bvh_nodes != 0u;
-        pin.streams = c->tune.streams;
-        pin.per_stream = c->tune.per_stream;
-        pin.wave_stack = c->tune.wave_stack;
-        pin.n_cus = c->n_cus;
-        pin.groups_per_cu = !stack_form ? 4u : (S.n_bvh_nodes == 0u ? (uint32_t)PT_CAND_WAVES : (uint32_t)PT_CAND_BVH_WAVES);
-        pin.stack_budget = stack_budget;
-        host::PassPlan plan;
-        uint64_t want_next = want;
-        const int pr = host::plan_pass(pin, plan, &want_next);  // (the arithmetic and its measurements: pt_host.cpp)
-        if (pr == host::kPlanRetry) {
-            want = want_next;
-            continue;
-        }
-        if (pr != host::kPlanOk) {
+        if (host::plan_frame(pin, req, plan) != host::kPlanOk) {
             set_error("rays per pass too large");
             return PT_ERR_INVALID;
         }
-        taper = host::Taper{};
-        if (try_taper) {
-            host::TaperIn tin;
-            tin.n_cut = taper_cut;
-            tin.pieces = taper_pieces;
-            tin.pass_samples = plan.spp_pass;
-            tin.resident = resident;
-            tin.budget = stack_budget;
-            tin.stack_park = form.stack_park;
-            tin.probe = F.probe != 0u;
-            tin.forced = taper_forced;
-            // longer streams with the default taper - if the plan is otherwise the same pass and the records stay staged
-            host::PassPlan plan_t = plan;
-            const uint32_t long_stream = walks ? kTaperPerStreamBvh : kTaperPerStream;
-            if (!taper_forced && !pin.per_stream && !pin.streams && long_stream != 0u) {
-                host::PassPlanIn pin_t = pin;
-                pin_t.per_stream = long_stream;
-                uint64_t unused = want;
-                if (host::plan_pass(pin_t, plan_t, &unused) != host::kPlanOk || plan_t.spp_pass != plan.spp_pass ||
-                    lds_layout(S, plan_t.m, c->tune.lds_pad).staged != lds_layout(S, plan.m, c->tune.lds_pad).staged)
-                    plan_t = plan;
-            }
-            taper = host::plan_taper(plan_t, tin);
-            if (taper.on()) plan = plan_t;
-        }
-        spp_pass = plan.spp_pass;
-        m = plan.m;
-        K = plan.K;
-        cap = plan.cap;
-        const size_t slots = (size_t)K * cap;
-        int rc = PT_OK;
-        rc = c->q_buf[0].ensure(plan.bytes0 + taper.extra0, true);
-        if (!rc && plan.bytes1) rc = c->q_buf[1].ensure(plan.bytes1 + taper.extra1, true);
-        // only the three-kernel form needs the hit records: k_pass keeps hits in registers
-        if (!rc && !form.one_kernel) rc = c->hit.ensure(slots, true);
-        if (!rc) rc = c->cnt.ensure((size_t)kLevels * K, true);
-        if (!rc) rc = c->flags.ensure(1, true);
-        if (!rc) rc = c->blk_rays.ensure(K, true);
-        if (!rc) rc = c->acc.ensure(3 * (size_t)K * m, true);
+        const int rc = ensure_pass_buffers(c, form, plan);
         if (!rc) break;
         if (rc != PT_ERR_NOMEM_INTERNAL) return rc;
-        // out of device memory: give back what this attempt took and try passes of half the size
+        // out of device memory: give back what this attempt took and ask for less
         for (int w = 0; w < 2; ++w) c->q_buf[w].release();
         c->hit.release();
-        if (taper.on()) {  // the taper goes before a pass is halved
-            try_taper = false;
-            continue;
-        }
-        if (spp_pass <= 1u) return PT_ERR_HIP;  // (the message names the allocation that failed)
-        want = (uint64_t)npix * (spp_pass / 2u ? spp_pass / 2u : 1u);
+        if (!host::shrink_request(pin, plan, req)) return PT_ERR_HIP;  // (the message names the allocation that failed)
     }
+    const bool stack_form = form.stack_form, taper_forced = c->tune.taper_cut >= 0;
+    const uint32_t spp_pass = plan.pass.spp_pass, m = plan.pass.m, K = plan.pass.K, cap = plan.pass.cap;
+    const host::Taper &taper = plan.taper;
     F.n_streams = K;  // stream b owns pixels b, b+K, ...; accumulators are stream-major (K*m slots per channel)
     c->live.streams = K;
     c->live.m = m;

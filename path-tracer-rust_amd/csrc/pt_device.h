@@ -393,6 +393,9 @@ constexpr uint32_t kWaveStackMax = 1024;  // slots of a wave's ray stack (k_pass
                                           // ever wait is bounded by phi (k_pass_cand); with 1024 slots a wave that is about to
                                           // start primaries (fewer than 64 rays waiting, fewer than 64 parked) is never held back
 PT_HD size_t queue_bytes(size_t K, uint32_t cap) { return K * (size_t)cap * kRayBytes; }
+// level-by-level forms: device bytes per primary ray of a pass - two containers x 4 slots x kRayBytes and, for the three-kernel
+// form, 4 hit records of 8 B: what a memory budget is divided by (host::first_request)
+constexpr uint32_t kLevelBytesPerPrimary = 2u * 4u * kRayBytes + 4u * 8u;  // 352
 PT_HD uint32_t pack_word(uint32_t pix_in_stream, uint32_t sample_in_pass, uint32_t depth, uint32_t branch) {
     return (pix_in_stream & 1023u) | ((sample_in_pass & 32767u) << 10) | ((depth & 15u) << 25) | (branch << 29);
 }

@@ -3,6 +3,7 @@
 // for the triangle edges — see pt_device.h).
 #include "pt_host.h"
 #include "pt_denoise.h"
+#include "pt_layout.h"
 #include "pt_masked.h"
 #include "pt_present.h"
 #include "pt_probe.h"
@@ -933,8 +934,8 @@ void run_refit_plan(const RefitPlan &p, const RefitTables &T) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// Passes and streams of a wavefront frame (see render_wavefront for how the plan is used, and for the retry on a failed
-// allocation).
+// Passes and streams of a wavefront frame (plan_frame, below, follows the retries and adds the taper; shrink_request is the
+// step after a failed allocation).
 int plan_pass(const PassPlanIn &in, PassPlan &out, uint64_t *want_next) {
     const uint64_t npix = in.npix;
     uint32_t spp_pass = (uint32_t)std::min<uint64_t>(in.want / (npix ? npix : 1u), 0xffffffffull);
@@ -1085,6 +1086,91 @@ Taper plan_taper(const PassPlan &plan, const TaperIn &in) {
     // (slot indices are 32-bit over the whole container, as in plan_pass)
     if ((uint64_t)plan.cap * (plan.K + more) > 0xffffffffull / 2) return off;
     return t;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The plan of a wavefront frame (pt_host.h).  The staging question is asked of lds_layout itself: pt_layout.h is host-only.
+uint32_t pass_groups_per_cu(bool stack_form, bool has_bvh) {
+    return !stack_form ? 4u : (has_bvh ? (uint32_t)PT_CAND_BVH_WAVES : (uint32_t)PT_CAND_WAVES);
+}
+
+// Level-by-level forms (k_pass, k_pass_bvh, the separate kernels): 96 Mi primary rays per pass by default, 36 GB of ray
+// queues of the 288 GB of HBM - fewer, longer launches: cornell 1024x768 @4096 spp 32 Mi 35.7, 48 Mi 35.7, 64 Mi 36.2, 96 Mi
+// 36.4 G bounces/s (a launch ends with its slowest streams).  k_pass_cand (`stack_form`) keeps a wave's waiting rays on a stack
+// of at most kWaveStackMax slots whatever the pass holds: its passes are sized by TIME (pt_api.hip: PassPacer) - 512 Mi primary
+// rays at most - and its memory is the streams' (K x 4 waves x stack x 40 B: 4.0 GB for the 24 576 streams of the bench frame's
+// pass).  Passes only change how the samples are batched, never the image.
+FrameRequest first_request(const FramePlanIn &in) {
+    FrameRequest r;
+    r.want = in.rays_per_pass ? in.rays_per_pass : in.rays_per_pass_tuned;
+    const bool given = r.want != 0u, stack_form = in.pass.stack_form;
+    const uint64_t dflt = stack_form ? (512u << 20) : (96u << 20);
+    // bytes the pass may take (0: unbounded); an explicit size without an explicit budget is taken as given
+    size_t avail = in.mem_budget;
+    if (!given) {
+        r.want = dflt;
+        if (!avail) avail = (size_t)((double)in.mem_avail * 0.85) / (in.mem_share ? in.mem_share : 1u);
+    }
+    if (stack_form)
+        r.stack_budget = avail;  // (plan_pass retries with smaller passes until the streams' stacks fit)
+    else if (avail)
+        r.want = std::min<uint64_t>(r.want, avail / kLevelBytesPerPrimary);
+    if (!given && in.mem_share > 1u) r.want = std::min(r.want, dflt / in.mem_share);  // (co-resident contexts also share the chip)
+    if (!given || in.mem_budget) r.want = std::max(r.want, in.pass.npix);  // one sample per pixel and pass at least
+    r.try_taper = stack_form;  // (k_pass_cand's alone; plan_taper has the rules, knobs by hand and PROBE instances among them)
+    return r;
+}
+
+int plan_frame(const FramePlanIn &in, const FrameRequest &req, FramePlan &out) {
+    PassPlanIn pin = in.pass;
+    pin.want = req.want;
+    pin.want_is_default = !in.rays_per_pass;
+    pin.groups_per_cu = pass_groups_per_cu(pin.stack_form, pin.has_bvh);
+    pin.stack_budget = req.stack_budget;
+    out = FramePlan{};
+    int pr;
+    uint64_t want_next = pin.want;
+    while ((pr = plan_pass(pin, out.pass, &want_next)) == kPlanRetry) {  // (every retry asks for less: it ends)
+        pin.want = want_next;
+        ++out.retries;
+    }
+    if (pr != kPlanOk || !req.try_taper) return pr;
+    // the taper's knobs by hand (PT_TAPER_CUT, PT_TAPER_PIECES, PT_PER_STREAM) are taken as given; the defaults are kTaper*
+    const bool walks = pin.has_bvh;
+    TaperIn tin;
+    tin.forced = in.taper_cut >= 0;
+    tin.resident = (uint64_t)pin.n_cus * pin.groups_per_cu;
+    const uint64_t cut_dflt = (uint64_t)(walks ? kTaperCutHalfRoundsBvh : kTaperCutHalfRounds) * tin.resident / 2u;
+    tin.n_cut = (uint32_t)std::min<uint64_t>(tin.forced ? (uint64_t)in.taper_cut : cut_dflt, 0xffffffffu);
+    tin.pieces = in.taper_pieces ? in.taper_pieces : (walks ? kTaperPiecesBvh : kTaperPieces);
+    tin.pass_samples = out.pass.spp_pass;
+    tin.budget = req.stack_budget;
+    tin.stack_park = pin.stack_park;
+    tin.probe = in.probe;
+    // longer streams with the default taper - if the plan is otherwise the same pass and the records stay staged
+    PassPlan plan_t = out.pass;
+    const uint32_t long_stream = walks ? kTaperPerStreamBvh : kTaperPerStream;
+    if (!tin.forced && !pin.per_stream && !pin.streams && long_stream != 0u) {
+        PassPlanIn pin_t = pin;
+        pin_t.per_stream = long_stream;
+        uint64_t unused = pin.want;
+        if (plan_pass(pin_t, plan_t, &unused) != kPlanOk || plan_t.spp_pass != out.pass.spp_pass ||
+            lds_layout(in.scene, plan_t.m, in.lds_pad).staged != lds_layout(in.scene, out.pass.m, in.lds_pad).staged)
+            plan_t = out.pass;
+    }
+    out.taper = plan_taper(plan_t, tin);
+    if (out.taper.on()) out.pass = plan_t;
+    return kPlanOk;
+}
+
+bool shrink_request(const FramePlanIn &in, const FramePlan &plan, FrameRequest &req) {
+    if (plan.taper.on()) {  // the taper goes before a pass is halved
+        req.try_taper = false;
+        return true;
+    }
+    if (plan.pass.spp_pass <= 1u) return false;
+    req.want = in.pass.npix * std::max(1u, plan.pass.spp_pass / 2u);
+    return true;
 }
 
 uint32_t next_pass_samples(double rate, double target_ms, uint64_t npix, uint64_t probe, uint32_t s_prev, uint32_t left,

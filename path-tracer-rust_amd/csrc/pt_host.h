@@ -90,7 +90,7 @@ void box_pair_records(const pt_triangle box[12], const float position[3], TriPai
 // `cam` only widens the distance bound that sizes the BVH box padding (ray origins include the lens centre)
 bool bvh_refs_fit(uint64_t n_nodes, uint64_t n_pair_records);
 
-// How a wavefront frame is cut into passes and streams (render_wavefront, pt_api.hip): pure arithmetic, tested on the CPU.
+// How a wavefront frame is cut into passes and streams (one attempt of plan_frame, below): pure arithmetic, tested on the CPU.
 struct PassPlanIn {
     uint64_t npix = 0;          // pixels of the call (or of its part)
     uint32_t spp = 0;           // samples per pixel of the frame
@@ -150,6 +150,54 @@ inline void taper_piece(uint32_t s_here, uint32_t lg_pieces, uint32_t piece, uin
     *s0 = piece * share + (piece < longer ? piece : longer);
     *n = share + (piece < longer ? 1u : 0u);
 }
+// The taper's defaults (measured: DESIGN.md section 4, profiles/r04_taper_sweep.txt): streams cut in HALF rounds of resident
+// workgroups (0: no taper), pieces per cut stream, and the primaries per stream and pass asked for with it (0: plan_pass's) -
+// without walks and with.  cornell 1024x768 @4096, one session, 448.0 ms without: one round in 4 pieces 438.1 ms at 24 Ki primaries
+// per stream, 439.0 at 32 Ki, 439.8 at 20 Ki; half a round in 8 pieces 436.8 - but in another session (449.9 without) half a round
+// 440.4 and a third of a round 446.9: too close to where the cut stops paying, so a whole round it is.  mesh.json @1024, 194.6 ms
+// without: half a round in 4 pieces at its own stream length 191.6, a whole round 192.4, 8 pieces 194.6; longer streams (32 Ki) gain
+// nothing there (192.0) and lose 3 % with a cut of half a round.
+constexpr uint32_t kTaperCutHalfRounds = 2, kTaperPieces = 4, kTaperPerStream = 24576;
+constexpr uint32_t kTaperCutHalfRoundsBvh = 1, kTaperPiecesBvh = 4, kTaperPerStreamBvh = 0;
+
+// THE PLAN OF A WAVEFRONT FRAME: what render_wavefront (pt_api.hip) decides before it allocates, nothing of HIP.  first_request,
+// then plan_frame; when the allocation fails shrink_request and plan_frame again.  tests/golden/frame_plans_parent.json records
+// what they give (tests/test_frame_plan.py).
+struct FramePlanIn {
+    // the caller's: npix, spp (the samples still to trace), the form, cand_scan, has_bvh, streams, per_stream, wave_stack, n_cus;
+    // the planner's: want, want_is_default, groups_per_cu, stack_budget
+    PassPlanIn pass;
+    uint64_t rays_per_pass = 0, rays_per_pass_tuned = 0;  // pt_config's (0: the library chooses); PT_RAYS_PER_PASS, its default
+    size_t mem_budget = 0;      // pt_ctx_set_memory_budget (0: none)
+    size_t mem_avail = 0;       // bytes free on the device + what the context's queues hold already (0: unknown)
+    uint32_t mem_share = 1;     // contexts that share the device in this call
+    bool probe = false;         // a PROBE instance
+    int64_t taper_cut = -1;     // PT_TAPER_CUT (< 0: the default)
+    uint32_t taper_pieces = 0;  // PT_TAPER_PIECES (0: the default)
+    DevScene scene{};           // the frame's scene record, for lds_layout (which reads its counts and flags, no table)
+    size_t lds_pad = 0;         // PT_LDS_PAD
+};
+struct FrameRequest {  // what one attempt asks for: the ladder's state
+    uint64_t want = 0;        // primary rays per pass
+    size_t stack_budget = 0;  // k_pass_cand: bytes the streams' stacks and the taper's slices may take (0: unbounded)
+    bool try_taper = false;
+};
+struct FramePlan {
+    PassPlan pass;
+    Taper taper;
+    int retries = 0;  // kPlanRetry answers of plan_pass that were followed
+};
+// workgroups of the pass kernel a compute unit holds at a time: k_pass_cand's waves per SIMD (pt_layout.h), else four
+uint32_t pass_groups_per_cu(bool stack_form, bool has_bvh);
+// The first request: the default pass, cut to what the device can give (85 % of mem_avail / mem_share, or mem_budget) and to a
+// mem_share-th of itself; an explicit size as given, but an explicit budget beats it; one sample per pixel at least.
+FrameRequest first_request(const FramePlanIn &in);
+// One attempt: plan_pass with its retries followed and, where req.try_taper, plan_taper - with the default taper on longer
+// streams (kTaperPerStream*) if the pass's samples and the records' staging (lds_layout) stay as they are.  kPlanOk or kPlanTooLarge.
+int plan_frame(const FramePlanIn &in, const FrameRequest &req, FramePlan &out);
+// After the allocation of `plan` failed: the same without its taper, else passes of half the samples; false: nothing smaller
+bool shrink_request(const FramePlanIn &in, const FramePlan &plan, FrameRequest &req);
+
 // Samples of a pixel in the next pass (wavefront) / round (megakernel) of a frame whose passes follow the scene (pt_api.hip:
 // render_wavefront, render_mega).  `rate`: primary samples per millisecond the last timed pass went through (0: nothing
 // measured yet - the pass is `probe` samples in all); `s_prev`: samples per pixel of the pass before (0: none); `left`: samples

@@ -374,7 +374,8 @@ PLAN_SRC = r"""
 #include "pt_host.h"
 using namespace pt;
 // argv: npix spp want default(0/1) stack_form stack_park cand_scan has_bvh streams per_stream wave_stack n_cus budget groups_per_cu
-// prints the plan after following plan_pass's retries the way render_wavefront does: OK spp_pass m K cap bytes0 bytes1 retries
+// prints OK spp_pass m K cap bytes0 bytes1 retries.  groups_per_cu by hand: plan_pass itself, once (RETRY: it asks for a smaller pass);
+// groups_per_cu 0: the library's, through host::plan_frame, which follows plan_pass's retries (no taper)
 int main(int argc, char **argv) {
     if (argc != 15) return 2;
     host::PassPlanIn in;
@@ -392,25 +393,31 @@ int main(int argc, char **argv) {
     in.n_cus = (uint32_t)strtoul(argv[12], 0, 10);
     in.stack_budget = (size_t)strtoull(argv[13], 0, 10);
     in.groups_per_cu = (uint32_t)strtoul(argv[14], 0, 10);
-    host::PassPlan p;
-    int retries = 0;
-    for (;;) {
+    host::FramePlan f;
+    int rc;
+    if (in.groups_per_cu) {
         uint64_t next = in.want;
-        const int rc = host::plan_pass(in, p, &next);
-        if (rc == host::kPlanOk) break;
-        if (rc == host::kPlanTooLarge) { printf("TOOLARGE\n"); return 0; }
-        if (next >= in.want || ++retries > 64) { printf("STUCK\n"); return 1; }
-        in.want = next;
+        rc = host::plan_pass(in, f.pass, &next);
+    } else {
+        host::FramePlanIn fin;
+        fin.pass = in;
+        fin.rays_per_pass = in.want_is_default ? 0u : in.want;
+        host::FrameRequest req;
+        req.want = in.want;
+        req.stack_budget = in.stack_budget;
+        rc = host::plan_frame(fin, req, f);
     }
-    printf("OK %u %u %u %u %zu %zu %d\n", p.spp_pass, p.m, p.K, p.cap, p.bytes0, p.bytes1, retries);
+    if (rc == host::kPlanTooLarge) { printf("TOOLARGE\n"); return 0; }
+    if (rc == host::kPlanRetry) { printf("RETRY\n"); return 0; }
+    printf("OK %u %u %u %u %zu %zu %d\n", f.pass.spp_pass, f.pass.m, f.pass.K, f.pass.cap, f.pass.bytes0, f.pass.bytes1, f.retries);
     return 0;
 }
 """
 
 
 def test_pass_plan(tmp_path):
-    """host::plan_pass - how render_wavefront cuts a frame into passes and streams - on the CPU: the bench frame (six passes of
-    683 samples, stacks of 1024 slots per wave, nothing in the second container), mesh.json (parking areas), a frame of few
+    """host::plan_pass - how a wavefront frame is cut into passes and streams; host::plan_frame follows its retries - on the CPU:
+    the bench frame (six passes of 683 samples, stacks of 1024 slots per wave, nothing in the second container), mesh.json (parking areas), a frame of few
     samples (at most 64 pixels per stream), the memory budget (passes halved until the stacks fit), small stacks on request,
     tiny passes (smaller stacks), the level-by-level forms (slices of 4 slots per primary ray, two containers), and a pass
     that 32-bit slot indices cannot hold."""
@@ -420,8 +427,11 @@ def test_pass_plan(tmp_path):
     subprocess.check_call(["g++", "-O1", "-std=c++17", "-I", os.path.join(ptlib.PKG, "csrc"), "-I", os.path.join(ptlib.ROOT, "include"),
                            str(src), "-o", exe, "-L", ptlib.PKG, "-lptrace_hip", "-Wl,-rpath," + ptlib.PKG])
 
-    def plan(npix, spp, want, default=1, stack=1, park=0, cand=1, bvh=0, streams=0, per_stream=0, wave_stack=0, n_cus=256, budget=0, groups=None):
-        groups = groups or (4 if bvh or not stack else 5)  # workgroups a CU holds: k_pass_cand without walks runs five waves per SIMD
+    def plan(npix, spp, want, default=1, stack=1, park=0, cand=1, bvh=0, streams=0, per_stream=0, wave_stack=0, n_cus=256, budget=0, groups=None,
+             follow=False):
+        # workgroups a CU holds, by hand: five for k_pass_cand without walks (its waves per SIMD when these figures were pinned).
+        # follow: through host::plan_frame, which derives them and follows plan_pass's retries
+        groups = 0 if follow else groups or (4 if bvh or not stack else 5)
         out = subprocess.check_output([exe] + [str(v) for v in (npix, spp, want, default, stack, park, cand, bvh, streams, per_stream,
                                                                 wave_stack, n_cus, budget, groups)]).decode().split()
         if out[0] != "OK":
@@ -446,7 +456,7 @@ def test_pass_plan(tmp_path):
     assert spp_pass == 512 and m == -(-npix // -(-npix * 512 // 22528)) and cap == 4096
     spp_pass, m, K, cap, _ = plan(npix, 128, 512 << 20)  # few samples: one pass, short streams of at most 64 (+ nudge) pixels
     assert spp_pass == 128 and m <= 72 and K >= 10922
-    spp_pass, m, K, cap, retries = plan(128 * 96, 64, 512 << 20, budget=8 << 20)  # the budget test of the GPU suite
+    spp_pass, m, K, cap, retries = plan(128 * 96, 64, 512 << 20, budget=8 << 20, follow=True)  # the budget test of the GPU suite
     assert spp_pass == 1 and retries == 6 and cap == 512
     spp_pass, m, K, cap, _ = plan(npix, 4096, 512 << 20, wave_stack=512)
     assert cap == 2048
@@ -455,7 +465,7 @@ def test_pass_plan(tmp_path):
     spp_pass, m, K, cap, _ = plan(npix, 4096, 96 << 20, stack=0)  # level by level: 128 samples per pass, 4 slots per primary
     assert spp_pass == 128 and cap >= 4 * m * 128
     assert plan(1 << 20, 32767, 1 << 31, default=0, stack=0) == "TOOLARGE"
-    spp_pass, m, K, cap, retries = plan(1 << 20, 32767, 1 << 31, default=1, stack=0)  # the same as a default: halved until it fits
+    spp_pass, m, K, cap, retries = plan(1 << 20, 32767, 1 << 31, default=1, stack=0, follow=True)  # the same as a default: halved until it fits
     assert retries >= 1 and K * cap <= 0x7fffffff
 
 

@@ -34,15 +34,22 @@ static host::PassPlan plan_of(uint32_t K, uint32_t cap, bool park) {
     return p;
 }
 
-static int follow(host::PassPlanIn in, host::PassPlan &p) {  // plan_pass with its retries, as render_wavefront follows them
-    int retries = 0;
-    for (;;) {
-        uint64_t next = in.want;
-        const int rc = host::plan_pass(in, p, &next);
-        if (rc == host::kPlanOk) return retries;
-        if (rc != host::kPlanRetry || next >= in.want || ++retries > 64) return -1;
-        in.want = next;
-    }
+static int once(const host::PassPlanIn &in, host::PassPlan &p) {  // plan_pass itself (groups_per_cu by hand): its answer
+    uint64_t next = in.want;
+    return host::plan_pass(in, p, &next);
+}
+
+static int follow(const host::PassPlanIn &in, host::PassPlan &p) {  // its retries followed by the library (host::plan_frame, no taper): how many
+    host::FramePlanIn fin;
+    fin.pass = in;  // (groups_per_cu is plan_frame's to set)
+    fin.rays_per_pass = in.want_is_default ? 0u : in.want;
+    host::FrameRequest req;
+    req.want = in.want;
+    req.stack_budget = in.stack_budget;
+    host::FramePlan f;
+    if (host::plan_frame(fin, req, f) != host::kPlanOk) return -1;
+    p = f.pass;
+    return f.retries;
 }
 
 int main() {
@@ -157,7 +164,7 @@ int main() {
         host::PassPlanIn in;
         in.npix = 1024u * 768u, in.spp = 4096, in.want = 512u << 20, in.stack_form = true, in.cand_scan = true, in.n_cus = 256, in.groups_per_cu = 5;
         host::PassPlan p, before;
-        CHECK(follow(in, p) == 0);
+        CHECK(once(in, p) == host::kPlanOk);
         CHECK(p.spp_pass == 683u && p.m == 22u && p.K == 35747u && p.cap == 4096u && p.bytes0 == (size_t)35747 * 4096u * 40u && p.bytes1 == 0u);
         before = p;
         host::TaperIn tin;
@@ -165,12 +172,12 @@ int main() {
         CHECK(host::plan_taper(p, tin).on());
         CHECK(memcmp(&before, &p, sizeof p) == 0);
         host::PassPlan again;
-        CHECK(follow(in, again) == 0 && again.m == 22u && again.K == 35747u && again.bytes0 == before.bytes0);
+        CHECK(once(in, again) == host::kPlanOk && again.m == 22u && again.K == 35747u && again.bytes0 == before.bytes0);
         in.groups_per_cu = 4;
-        CHECK(follow(in, p) == 0 && p.m == 24u && p.K == 32768u);
+        CHECK(once(in, p) == host::kPlanOk && p.m == 24u && p.K == 32768u);
         // the budget frame: passes halved six times; a taper that breaks the budget is dropped, the pass is not halved again
         host::PassPlanIn bin;
-        bin.npix = 128u * 96u, bin.spp = 64, bin.want = 512u << 20, bin.stack_form = true, bin.cand_scan = true, bin.n_cus = 256, bin.groups_per_cu = 5;
+        bin.npix = 128u * 96u, bin.spp = 64, bin.want = 512u << 20, bin.stack_form = true, bin.cand_scan = true, bin.n_cus = 256;
         bin.stack_budget = 8u << 20;
         CHECK(follow(bin, p) == 6 && p.spp_pass == 1u && p.cap == 512u);
         before = p;

@@ -1,8 +1,8 @@
 """k_pass_cand's rows of waiting rays (csrc/pt_layout.h: pass_lds_wait_bytes) and its budget at six workgroups per CU, on the CPU:
 what lds_layout decides is asked of the header itself through tests/lds_layouts.py's helper, never restated.
 
-- cornell.json's candidate and shading records stay staged at 1 pixel per stream, at the bench pass's stream length (plan_pass
-  for 1024x768 @4096 on 256 CUs) and at 64, the most plan_pass gives a frame of few samples;
+- cornell.json's candidate and shading records stay staged at 1 pixel per stream, at the bench pass's stream length (host::plan_frame
+  for 1024x768 @4096 on 256 CUs, before the taper) and at 64, the most plan_pass gives a frame of few samples;
 - what a launch asks for never exceeds the header's own budget expression (pass_cand_lds_budget);
 - the ladder of tests/lds_layouts.py - its knob ranges were chosen when the budget was a fifth of a CU's LDS - still brackets
   every cliff;
@@ -25,18 +25,17 @@ BUDGET_SRC = r"""
 using namespace pt;
 // the budget per workgroup without and with walks, the waves per SIMD, the bytes of the rows, and the bench pass's stream length
 int main() {
-    host::PassPlanIn in;
-    in.npix = 1024u * 768u;
-    in.spp = 4096;
-    in.want = 512ull << 20;
-    in.want_is_default = true;
-    in.stack_form = true;
-    in.cand_scan = true;
-    in.n_cus = 256;
-    in.groups_per_cu = PT_CAND_WAVES;
-    host::PassPlan p;
-    uint64_t next = 0;
-    if (host::plan_pass(in, p, &next) != host::kPlanOk) return 1;
+    host::FramePlanIn in;
+    in.pass.npix = 1024u * 768u;
+    in.pass.spp = 4096;
+    in.pass.stack_form = true;
+    in.pass.cand_scan = true;
+    in.pass.n_cus = 256;
+    host::FrameRequest req;
+    req.want = 512ull << 20;
+    host::FramePlan f;
+    if (host::plan_frame(in, req, f) != host::kPlanOk || f.retries != 0) return 1;
+    const host::PassPlan &p = f.pass;
     printf("%zu %zu %d %zu %zu %u %u\n", pass_cand_lds_budget(false), pass_cand_lds_budget(true), (int)PT_CAND_WAVES,
            pass_lds_wait_bytes(false), pass_lds_wait_bytes(true), p.m, p.K);
     return 0;
