@@ -200,6 +200,14 @@ pub struct PtDenoiseParams {
     pub flags: u32,
 }
 
+// pt_ctx_render_aov_ex's parameters: flags PT_AOV_THROUGH_DELTA or 0; max_chain 0 = 8, at most PT_AOV_MAX_CHAIN, needs the flag
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct PtAovParams {
+    pub flags: u32,
+    pub max_chain: u32,
+}
+
 // pt_ctx_accum_noise's frame statistics: the error estimate e(p) from the two halves of a noise-tracked frame's samples
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
@@ -275,6 +283,8 @@ pub const PT_TABLE_TRI_RANK: usize = 12;
 pub const PT_TABLE_BVH_MESHES: usize = 13;
 pub const PT_TABLE_COUNT: usize = 14;
 pub const PT_DENOISE_NO_DEMODULATE: u32 = 1;
+pub const PT_AOV_THROUGH_DELTA: u32 = 1;
+pub const PT_AOV_MAX_CHAIN: u32 = 16;
 pub const PT_PRESENT_RGBA8: u32 = 0;
 pub const PT_PRESENT_RGB8: u32 = 1;
 pub const PT_PRESENT_FRAMEBUFFER_ORDER: u32 = 1;
@@ -440,6 +450,20 @@ extern "C" {
         d_normal: *mut f32,
         d_depth: *mut f32,
         d_object_id: *mut i32,
+        hip_stream: *mut c_void,
+    ) -> i32;
+    // the same with parameters (null = the plain call) and sample 0's chain length per pixel: with PT_AOV_THROUGH_DELTA the
+    // guides are those of the first surface behind the mirrors and the glass - for the filters, not for a pick map
+    pub fn pt_aov_defaults(out: *mut PtAovParams) -> i32;
+    pub fn pt_ctx_render_aov_ex(
+        ctx: *mut PtCtx,
+        cfg: *const PtConfig,
+        params: *const PtAovParams,
+        d_albedo: *mut f32,
+        d_normal: *mut f32,
+        d_depth: *mut f32,
+        d_object_id: *mut i32,
+        d_chain: *mut u32,
         hip_stream: *mut c_void,
     ) -> i32;
     // edge-avoiding a-trous filter over a whole frame in device memory, guided by pt_ctx_render_aov's buffers (each guide may

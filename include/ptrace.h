@@ -757,7 +757,7 @@ int pt_ctx_adaptive_load(pt_ctx *ctx, const char *path);
  * For each sample s in [0, cfg->spp) the ray is render_pixel's ray for (seed; p, s) (mod.rs:812-843), bit for bit what
  * pt_ctx_primary_rays returns and what the frame kernels trace - so these are the first cfg->spp samples of the frame with
  * that seed, a prefix of a frame rendered at more - and h = intersect_scene(ray) (mod.rs:631-659).  FIRST HIT only: a
- * mirror or glass surface gives its own colour and normal (following delta chains would draw random numbers).
+ * mirror or glass surface gives its own colour and normal (pt_ctx_render_aov_ex, below, can follow the deterministic chain).
  * - albedo[3k+c] = sum over s of (colour[c] of the object hit, 0 on a miss) / spp
  * - normal[3k+c] = sum over s of (normal_towards_ray[c], 0 on a miss) / spp, not renormalised; normal_towards_ray is the hit
  *   normal flipped to face the ray, as radiance() computes it (mod.rs:669-673)
@@ -774,6 +774,45 @@ int pt_ctx_adaptive_load(pt_ctx *ctx, const char *path);
  * context: not the frame accumulators, not pt_ctx_accumulate's held sums or counts, not the measured pass rates. */
 int pt_ctx_render_aov(pt_ctx *ctx, const pt_config *cfg, float *d_albedo, float *d_normal, float *d_depth,
                       int32_t *d_object_id, void *hip_stream);
+
+/* ---- AOVs through mirror and glass surfaces: the guides of what a delta surface shows -----------------------------------
+ * pt_ctx_render_aov_ex is pt_ctx_render_aov with parameters and a fifth output.  With params NULL or all zero it runs the
+ * plain call - the same kernel, the same bits in the four buffers - and writes 0 to every word of d_chain.
+ * With PT_AOV_THROUGH_DELTA a sample does not stop on a PT_SPECULAR or PT_REFRACT object: it follows the deterministic chain
+ * to the first surface that is neither, and the guides describe THAT surface - the reflected wall, the refracted floor.  The
+ * chain draws no random number, so it is stated bit for bit.  For sample s of pixel p (framebuffer index, as above) the first
+ * ray is render_pixel's ray for (seed; p, s); thr = (1, 1, 1), L = +0, j = 0; then repeat h = intersect_scene(ray):
+ * - a miss, at any stage: the sample adds 0 to albedo and normal; sample 0 gives depth +inf, object_id -1, chain j.
+ * - a hit: L = L + h.distance (one binary32 addition per hit, in chain order).  If the object is PT_DIFFUSE or j == max_chain
+ *   the hit is TERMINAL: the sample adds thr * colour to albedo (per channel one binary32 product) and normal_towards_ray of
+ *   this hit against the current ray's direction (mod.rs:669-673) to normal; sample 0 gives depth L, object_id this object's
+ *   index, chain j.  Otherwise thr = thr * colour, j = j + 1, and the next ray starts at hit.intersection with direction
+ *   d - n*2*dot(n,d) on PT_SPECULAR (mod.rs:722-723, not renormalised) and on PT_REFRACT that same direction when cos2t < 0
+ *   and tdir of mod.rs:746-749 otherwise - the values radiance() gives its recursive calls, what pt_ctx_scatter reports as
+ *   d0 (mirror, total internal reflection) and d1 (a split's transmitted ray).  No roulette, no Fresnel weight, no draw: on
+ *   glass the chain follows the transmitted ray wherever one exists.
+ * Sums and their means are pt_ctx_render_aov's 32.32 fixed-point rules, so a frame that sees no delta surface gets the plain
+ * call's bits (thr = 1 and L = +0 change nothing: 1 * c == c, 0 + t == t).  depth is the UNFOLDED path length to the terminal
+ * surface, not a distance from the lens along the primary ray; object_id is the reflected or refracted object's, so a GUI's
+ * pick map should keep using the plain call.  What pt_ctx_reproject* makes of an unfolded depth under a camera move has not
+ * been studied.
+ * - max_chain: the most delta steps a sample takes, 1..PT_AOV_MAX_CHAIN; 0 = 8.  A sample still on a delta surface after
+ *   max_chain steps ends there with that surface's colour (times thr) and normal.
+ * - d_chain: pt_config_pixels(cfg) uint32, sample 0's j; may be NULL, as each of the four others.
+ * PT_ERR_INVALID before any device is touched, checked in this order: flag bits other than PT_AOV_THROUGH_DELTA; max_chain
+ * above PT_AOV_MAX_CHAIN; max_chain != 0 without the flag; all five outputs NULL; then whatever pt_ctx_render_aov refuses.
+ * Everything else - pixels covered, ignored cfg fields, PT_FLAG_NO_BVH, the stream, blocking, no other state of the context
+ * changed - as pt_ctx_render_aov.  pt_aov_defaults writes the parameters of a through-delta call with every default written
+ * out, {PT_AOV_THROUGH_DELTA, 8}; PT_ERR_INVALID for a NULL out. */
+#define PT_AOV_THROUGH_DELTA 1u
+#define PT_AOV_MAX_CHAIN 16u
+typedef struct pt_aov_params {
+    uint32_t flags;     /* PT_AOV_THROUGH_DELTA or 0 */
+    uint32_t max_chain; /* 0 = 8; needs the flag */
+} pt_aov_params;
+int pt_aov_defaults(pt_aov_params *out);
+int pt_ctx_render_aov_ex(pt_ctx *ctx, const pt_config *cfg, const pt_aov_params *params, float *d_albedo, float *d_normal,
+                         float *d_depth, int32_t *d_object_id, uint32_t *d_chain, void *hip_stream);
 
 /* ---- denoising a frame on the device with the first-hit guides ------------------------------------------------
  * pt_ctx_denoise runs an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) over a WHOLE frame in device memory,

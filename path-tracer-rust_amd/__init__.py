@@ -53,6 +53,10 @@ class pt_denoise_params(C.Structure):
                 ("sigma_depth", C.c_float), ("flags", C.c_uint32)]
 
 
+class pt_aov_params(C.Structure):
+    _fields_ = [("flags", C.c_uint32), ("max_chain", C.c_uint32)]
+
+
 class pt_denoise_var_params(C.Structure):
     _fields_ = [("levels", C.c_uint32), ("sigma_var", C.c_float), ("sigma_depth", C.c_float), ("flags", C.c_uint32)]
 
@@ -129,6 +133,7 @@ class pt_adaptive_info(C.Structure):
 TABLE_NAMES = ("objs", "obj_pairs", "tri_pairs", "mats", "tri_shade", "bvh_nodes", "bvh_nodes4", "sph_pairs", "flat_pairs", "cand_pairs",
                "rank_id", "surf", "tri_rank", "bvh_meshes")
 PT_DENOISE_NO_DEMODULATE = 1
+PT_AOV_THROUGH_DELTA, PT_AOV_MAX_CHAIN = 1, 16
 PT_PRESENT_RGBA8, PT_PRESENT_RGB8 = 0, 1
 PT_PRESENT_FRAMEBUFFER_ORDER = 1
 PT_OK, PT_ERR_INVALID, PT_ERR_NO_DEVICE, PT_ERR_HIP, PT_CANCELLED = 0, -1, -2, -3, -4
@@ -188,6 +193,9 @@ def lib():
     L.pt_ctx_adaptive_load.argtypes = [C.c_void_p, C.c_char_p]
     L.pt_ctx_render_aov.argtypes = [C.c_void_p, C.POINTER(pt_config), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p]
+    L.pt_aov_defaults.argtypes = [C.POINTER(pt_aov_params)]
+    L.pt_ctx_render_aov_ex.argtypes = [C.c_void_p, C.POINTER(pt_config), C.POINTER(pt_aov_params), C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pt_denoise_defaults.argtypes = [C.POINTER(pt_denoise_params)]
     L.pt_ctx_denoise.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(pt_denoise_params), C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -368,17 +376,26 @@ class Context:
         return lo.value, hi.value
 
     def render_aov(self, width, height, spp, seed=1, band=None, chunks=None, albedo=None, normal=None, depth=None,
-                   object_id=None, no_bvh=False, stream=None):
+                   object_id=None, no_bvh=False, stream=None, through_delta=False, max_chain=0, chain=None):
         """First-hit AOVs of the frame render() would draw with the same width, height, seed, band and chunks, over its first
         `spp` samples (pt_ctx_render_aov): device pointers, each optional - albedo / normal: pixels * 3 float32 (the means
         over the samples), depth: pixels float32 (sample 0's hit distance, +inf on a miss), object_id: pixels int32 (sample
-        0's object, -1 on a miss)."""
+        0's object, -1 on a miss).
+        through_delta=True (pt_ctx_render_aov_ex with PT_AOV_THROUGH_DELTA): a sample that hits a mirror or glass surface
+        follows the deterministic chain, at most max_chain steps (0 = 8, at most PT_AOV_MAX_CHAIN), and the guides describe
+        the surface that ends it; depth is then the path's whole length.  chain: pixels uint32, sample 0's number of delta
+        steps (zeros without through_delta).  Without through_delta, max_chain and chain this is the plain call."""
         cfg = self._config(width, height, spp, seed, band=band, chunks=chunks)
         if no_bvh:
             cfg.flags |= PT_FLAG_NO_BVH
         ptr = lambda p: C.c_void_p(p) if p else None  # noqa: E731
-        _check(lib().pt_ctx_render_aov(self._h, C.byref(cfg), ptr(albedo), ptr(normal), ptr(depth), ptr(object_id),
-                                       C.c_void_p(stream or 0)))
+        if not through_delta and not max_chain and not chain:
+            _check(lib().pt_ctx_render_aov(self._h, C.byref(cfg), ptr(albedo), ptr(normal), ptr(depth), ptr(object_id),
+                                           C.c_void_p(stream or 0)))
+            return
+        params = pt_aov_params(PT_AOV_THROUGH_DELTA if through_delta else 0, max_chain)
+        _check(lib().pt_ctx_render_aov_ex(self._h, C.byref(cfg), C.byref(params), ptr(albedo), ptr(normal), ptr(depth),
+                                          ptr(object_id), ptr(chain), C.c_void_p(stream or 0)))
 
     def denoise(self, width, height, color, out, albedo=None, normal=None, depth=None, stream=None, **params):
         """Denoise a whole width x height frame in device memory (pt_ctx_denoise): `color` and `out` are device pointers to
@@ -750,6 +767,14 @@ def denoise_defaults():
     p = pt_denoise_params()
     _check(lib().pt_denoise_defaults(C.byref(p)))
     return {"levels": p.levels, "sigma_color": p.sigma_color, "sigma_depth": p.sigma_depth}
+
+
+def aov_defaults():
+    """The parameters of a through-delta render_aov with every default written out: {"through_delta", "max_chain"}
+    (pt_aov_defaults)."""
+    p = pt_aov_params()
+    _check(lib().pt_aov_defaults(C.byref(p)))
+    return {"through_delta": bool(p.flags & PT_AOV_THROUGH_DELTA), "max_chain": p.max_chain}
 
 
 def denoise_var_defaults():

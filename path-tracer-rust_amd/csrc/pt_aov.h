@@ -16,4 +16,9 @@ namespace pt {
 void launch_aov(hipStream_t st, const DevScene &S, const FrameParams &F, float *albedo, float *normal, float *depth,
                 int32_t *object_id);
 
+// The same through mirror and glass surfaces (pt_ctx_render_aov_ex with PT_AOV_THROUGH_DELTA): the guides of the surface that
+// ends each sample's deterministic chain, at most max_chain (1..PT_AOV_MAX_CHAIN) delta steps; chain[k] = sample 0's steps.
+void launch_aov_chain(hipStream_t st, const DevScene &S, const FrameParams &F, uint32_t max_chain, float *albedo, float *normal,
+                      float *depth, int32_t *object_id, uint32_t *chain);
+
 }  // namespace pt

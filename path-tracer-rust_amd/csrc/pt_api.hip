@@ -2911,6 +2911,42 @@ int pt_ctx_render_aov(pt_ctx *c, const pt_config *cfg, float *d_albedo, float *d
     });
 }
 
+// pt_aov_params with every default written out: a through-delta call of kAovDefaultChain steps (a plain call has no parameters
+// to default; {0, 8} would be a set the call itself refuses)
+static constexpr uint32_t kAovDefaultChain = 8u;
+int pt_aov_defaults(pt_aov_params *out) { return give_defaults(out, pt_aov_params{PT_AOV_THROUGH_DELTA, kAovDefaultChain}); }
+
+int pt_ctx_render_aov_ex(pt_ctx *c, const pt_config *cfg, const pt_aov_params *params, float *d_albedo, float *d_normal,
+                         float *d_depth, int32_t *d_object_id, uint32_t *d_chain, void *hip_stream) {
+    const pt_aov_params P = params ? *params : pt_aov_params{0u, 0u};
+    if (P.flags & ~PT_AOV_THROUGH_DELTA) return refuse("pt_aov_params.flags: unknown bits");
+    if (P.max_chain > PT_AOV_MAX_CHAIN) return refuse("pt_aov_params.max_chain exceeds PT_AOV_MAX_CHAIN");
+    if (P.max_chain != 0u && !(P.flags & PT_AOV_THROUGH_DELTA))
+        return refuse("pt_aov_params.max_chain without PT_AOV_THROUGH_DELTA");
+    if (!d_albedo && !d_normal && !d_depth && !d_object_id && !d_chain) return refuse("every output is NULL");
+    if (!cfg || !c) return refuse("NULL argument");
+    // from here on pt_ctx_render_aov's own steps
+    pt_config fc = *cfg;
+    fc.backend = PT_BACKEND_WAVEFRONT;
+    uint32_t ib = 0, ie = 0;
+    const int rc = frame_prologue(c, &fc, &ib, &ie);
+    if (rc) return rc;
+    const FrameParams F = make_frame(c, &fc, ib, ie);
+    if (F.npix == 0u) return PT_OK;
+    const DevScene S = form_for(c, cfg->flags).scene;
+    return run_image_pass(c, hip_stream, [&](hipStream_t st) {
+        if (P.flags & PT_AOV_THROUGH_DELTA) {
+            launch_aov_chain(st, S, F, P.max_chain ? P.max_chain : kAovDefaultChain, d_albedo, d_normal, d_depth, d_object_id,
+                             d_chain);
+            return PT_OK;
+        }
+        // the plain call's kernel; no chain was followed
+        if (d_albedo || d_normal || d_depth || d_object_id) launch_aov(st, S, F, d_albedo, d_normal, d_depth, d_object_id);
+        if (d_chain) HIP_TRY(hipMemsetAsync(d_chain, 0, (size_t)F.npix * sizeof(uint32_t), st));
+        return PT_OK;
+    });
+}
+
 // pt_ctx_denoise and pt_ctx_denoise_var once host::check_denoise* has passed: the scratch, prepare, the levels of the schedule
 static int run_denoise(pt_ctx *c, DenoiseCall &call, void *hip_stream) {
     return run_image_pass(c, hip_stream, [&](hipStream_t st) {

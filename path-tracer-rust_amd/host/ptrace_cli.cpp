@@ -19,10 +19,22 @@
 
 #include "../../include/ptrace.h"
 
+// --aov-chain [K]: the guides every pass of this program reads come from pt_ctx_render_aov_ex with PT_AOV_THROUGH_DELTA
+static bool g_aov_chain = false;
+static pt_aov_params g_aov = {0u, 0u};
+
+// the guides of one frame: the plain call, byte for byte what it always wrote - or, with --aov-chain, the chain call
+static int render_guides(pt_ctx *ctx, const pt_config *cfg, float *d_albedo, float *d_normal, float *d_depth, int32_t *d_id,
+                         uint32_t *d_chain = nullptr) {
+    if (!g_aov_chain) return pt_ctx_render_aov(ctx, cfg, d_albedo, d_normal, d_depth, d_id, nullptr);
+    return pt_ctx_render_aov_ex(ctx, cfg, &g_aov, d_albedo, d_normal, d_depth, d_id, d_chain, nullptr);
+}
+
 static void usage() {
     fprintf(stderr,
             "usage: ptrace <samplesPerPixel> <y-resolution> <scene id|index> [--width W] [--backend wavefront|megakernel]\n"
             "              [--seed S] [--gpus N] [--root DIR] [--out DIR] [--no-ppm] [--checkpoint FILE] [--aov N]\n"
+            "              [--aov-chain [K]]\n"
             "              [--denoise [N]] [--noise-target X [--noise-map FILE.pfm]]\n"
             "              [--adaptive X [--tile N] [--spp-map FILE.pfm] [--error-map FILE.pfm] [--adaptive-checkpoint FILE]]\n"
             "              [--denoise-var [N]] [--preview FILE.ppm [--preview-size WxH] [--exposure E]]\n"
@@ -34,6 +46,10 @@ static void usage() {
             "  --aov N: after the frame, first-hit AOVs over its first N samples on one GPU, written next to the image as\n"
             "           PFM files: ...-beauty.pfm (the linear frame), -albedo, -normal, -depth (+inf on a miss) and -id (the\n"
             "           object index as a float, -1 on a miss)\n"
+            "  --aov-chain [K]: guides THROUGH mirror and glass surfaces (pt_ctx_render_aov_ex, PT_AOV_THROUGH_DELTA, at most K = 1..16\n"
+            "           steps, default 8): --aov then also writes ...-chain.pfm (sample 0's number of steps), its -depth is the\n"
+            "           path's whole length and its -id the reflected object's; --denoise, --denoise-var, --trace-scale and --orbit\n"
+            "           take their guides from that call\n"
             "  --denoise [N]: after the frame, denoise it on the GPU (pt_ctx_denoise, default parameters) with first-hit guides over\n"
             "           its first N samples (default 16), written next to the image as ...-denoised.ppm and ...-denoised.pfm; one\n"
             "           GPU only\n"
@@ -347,8 +363,8 @@ static int render_scaled(const pt_config *cfg, pt_scene *sc, uint32_t scale, boo
         float *albedo = (float *)d_full, *normal = albedo + npix * 3, *depth = normal + npix * 3;
         int32_t *id = (int32_t *)(depth + npix);
         rc = pt_ctx_render(ctx, &lo, lo_color, nullptr, nullptr, progress, nullptr, st);
-        if (!rc) rc = pt_ctx_render_aov(ctx, &lo, lo_albedo, lo_normal, lo_depth, lo_id, nullptr);
-        if (!rc) rc = pt_ctx_render_aov(ctx, cfg, albedo, normal, depth, id, nullptr);
+        if (!rc) rc = render_guides(ctx, &lo, lo_albedo, lo_normal, lo_depth, lo_id);
+        if (!rc) rc = render_guides(ctx, cfg, albedo, normal, depth, id);
         if (!rc)
             rc = pt_ctx_upsample(ctx, cfg->width, cfg->height, lo.width, lo.height, nullptr, lo_color, lo_depth, lo_id, lo_normal, lo_albedo,
                                  depth, id, normal, albedo, (float *)d_out, (float *)d_sel, nullptr);
@@ -390,7 +406,7 @@ static int write_denoised(const pt_config *frame, uint32_t spp, const DeviceFram
     int rc = pt_device_malloc(df.dev, npix * 7 * sizeof(float), &d_buf);
     if (!rc) {
         float *d_albedo = (float *)d_buf, *d_normal = d_albedo + npix * 3, *d_depth = d_normal + npix * 3;
-        rc = pt_ctx_render_aov(df.ctx, &cfg, d_albedo, d_normal, d_depth, nullptr, nullptr);
+        rc = render_guides(df.ctx, &cfg, d_albedo, d_normal, d_depth, nullptr);
         if (!rc && df.d_error)
             rc = pt_ctx_denoise_var(df.ctx, cfg.width, cfg.height, nullptr, (const float *)df.d_out, (const float *)df.d_error,
                                     d_albedo, d_normal, d_depth, (float *)df.d_out, nullptr);
@@ -437,7 +453,8 @@ static int write_preview(const pt_config *frame, const DeviceFrame &df, const st
     return rc;
 }
 
-// --aov: the frame's first-hit AOVs at `spp` samples (pt_ctx_render_aov) on one GPU, and the five PFM files at `stem`
+// --aov: the frame's first-hit AOVs at `spp` samples (pt_ctx_render_aov) on one GPU, and the five PFM files at `stem`; with
+// --aov-chain the chain call's, and a sixth file, the chain plane as floats
 static int write_aovs(const pt_config *frame, uint32_t spp, pt_scene *sc, const std::vector<float> &img, const std::string &stem) {
     int dev = 0;
     if (const char *e = getenv("PT_DEVICE")) dev = atoi(e);
@@ -449,15 +466,19 @@ static int write_aovs(const pt_config *frame, uint32_t spp, pt_scene *sc, const 
     const size_t npix = (size_t)cfg.width * cfg.height;
     std::vector<float> albedo(npix * 3), normal(npix * 3), depth(npix), id_f(npix);
     std::vector<int32_t> id(npix);
+    std::vector<uint32_t> chain(g_aov_chain ? npix : 0);
+    std::vector<float> chain_f(chain.size());
     pt_ctx *ctx = nullptr;
     void *d_buf = nullptr;
     int rc = pt_ctx_create(dev, &ctx);
     if (!rc) rc = pt_ctx_set_scene(ctx, pt_scene_camera(sc), objs, n_objs, tris, n_tris);
-    if (!rc) rc = pt_device_malloc(dev, npix * 9 * sizeof(float), &d_buf);
+    if (!rc) rc = pt_device_malloc(dev, npix * (g_aov_chain ? 10 : 9) * sizeof(float), &d_buf);
     if (!rc) {
         float *d_albedo = (float *)d_buf, *d_normal = d_albedo + npix * 3, *d_depth = d_normal + npix * 3;
         int32_t *d_id = (int32_t *)(d_depth + npix);
-        rc = pt_ctx_render_aov(ctx, &cfg, d_albedo, d_normal, d_depth, d_id, nullptr);
+        uint32_t *d_chain = g_aov_chain ? (uint32_t *)(d_id + npix) : nullptr;
+        rc = render_guides(ctx, &cfg, d_albedo, d_normal, d_depth, d_id, d_chain);
+        if (!rc && d_chain) rc = pt_device_download(dev, chain.data(), d_chain, npix * sizeof(uint32_t));
         if (!rc) rc = pt_device_download(dev, albedo.data(), d_albedo, npix * 3 * sizeof(float));
         if (!rc) rc = pt_device_download(dev, normal.data(), d_normal, npix * 3 * sizeof(float));
         if (!rc) rc = pt_device_download(dev, depth.data(), d_depth, npix * sizeof(float));
@@ -475,8 +496,10 @@ static int write_aovs(const pt_config *frame, uint32_t spp, pt_scene *sc, const 
         const float *data;
         uint32_t channels;
     } files[] = {{"beauty", img.data(), 3}, {"albedo", albedo.data(), 3}, {"normal", normal.data(), 3}, {"depth", depth.data(), 1},
-                 {"id", id_f.data(), 1}};
+                 {"id", id_f.data(), 1}, {"chain", chain_f.data(), 1}};
+    for (size_t i = 0; i < chain.size(); ++i) chain_f[i] = (float)chain[i];
     for (const auto &f : files) {
+        if (!g_aov_chain && !strcmp(f.name, "chain")) continue;
         const std::string path = stem + f.name + ".pfm";
         rc = pt_write_pfm(path.c_str(), f.data, cfg.width, cfg.height, f.channels);
         if (rc) {
@@ -574,7 +597,7 @@ static int render_orbit(const pt_config *cfg, pt_scene *sc, uint32_t frames, dou
         }
         const clk::time_point t1b = clk::now();
         if (!rc) rc = pt_ctx_render(ctx, cfg, cur->color, nullptr, nullptr, nullptr, nullptr, &st);
-        if (!rc) rc = pt_ctx_render_aov(ctx, cfg, d_albedo, cur->normal, cur->depth, cur->id, nullptr);
+        if (!rc) rc = render_guides(ctx, cfg, d_albedo, cur->normal, cur->depth, cur->id);
         pt_reproject_var_params rp;
         memset(&rp, 0, sizeof rp);
         rp.weight = cfg->spp;
@@ -685,6 +708,19 @@ int main(int argc, char **argv) {
             if (!aov_spp) {
                 usage();
                 return 1;
+            }
+        }
+        else if (a == "--aov-chain") {
+            g_aov_chain = true;
+            g_aov.flags = PT_AOV_THROUGH_DELTA;
+            if (i + 1 < argc && strncmp(argv[i + 1], "--", 2) != 0) {  // the optional K
+                const char *v = argv[++i];
+                const unsigned long k = *v && strspn(v, "0123456789") == strlen(v) && strlen(v) < 4 ? strtoul(v, nullptr, 10) : 0ul;
+                if (k < 1ul || k > PT_AOV_MAX_CHAIN) {
+                    fprintf(stderr, "--aov-chain takes K = 1..%u steps (or none: 8)\n", PT_AOV_MAX_CHAIN);
+                    return 1;
+                }
+                g_aov.max_chain = (uint32_t)k;
             }
         }
         else if (a == "--noise-target") {
@@ -798,6 +834,10 @@ int main(int argc, char **argv) {
     }
     if (!spp || !res_y || !width) {
         usage();
+        return 1;
+    }
+    if (g_aov_chain && !(aov_spp || denoise_spp || denoise_var_spp || trace_scale || orbit_frames)) {
+        fprintf(stderr, "--aov-chain goes with --aov, --denoise, --denoise-var, --trace-scale or --orbit: nothing else reads guides\n");
         return 1;
     }
     if (orbit_step_given && !orbit_frames) {

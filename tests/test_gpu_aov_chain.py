@@ -1,0 +1,401 @@
+"""AOVs through mirror and glass surfaces on the GPU (pt_ctx_render_aov_ex, PT_AOV_THROUGH_DELTA) against tests/aov_chain_ref.py:
+the oracle's rays and hits, kats_scatter's child directions, numpy binary32 and integer sums.  All five planes - albedo, normal,
+depth, object id, chain - are compared bit for bit.  Before a scene is used, the restatement's own statistics (never device
+output) must show that it exercises what it is there for."""
+import ctypes as C
+import importlib
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import aov_chain_ref as R
+import ptlib
+from ptlib import PtConfig, PtStats
+from test_gpu_aov import (F32, H, NO_BVH, PT_ERR_INVALID, SEED, W, call_pixels, cfg_of, oracle_rays, pfm_to_framebuffer, read_pfm,
+                          scene)
+
+pytestmark = pytest.mark.gpu
+
+THROUGH_DELTA, MAX_CHAIN = 1, 16
+NAMES = ("albedo", "normal", "depth", "object_id", "chain")
+
+
+class PtAovParams(C.Structure):
+    _fields_ = [("flags", C.c_uint32), ("max_chain", C.c_uint32)]
+
+
+def _bind(L):
+    L.pt_ctx_render_aov.argtypes = [C.c_void_p, C.POINTER(PtConfig)] + [C.c_void_p] * 5
+    L.pt_ctx_render_aov_ex.argtypes = [C.c_void_p, C.POINTER(PtConfig), C.POINTER(PtAovParams)] + [C.c_void_p] * 6
+    L.pt_ctx_accumulate.argtypes = [C.c_void_p, C.POINTER(PtConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.POINTER(PtStats)]
+    L.pt_ctx_accum_info.argtypes = [C.c_void_p, C.POINTER(PtConfig), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    return L
+
+
+@pytest.fixture(scope="module")
+def L():
+    return _bind(ptlib.product())
+
+
+# ------------------------------------------------------------------------------------------------------- scenes and records
+_made = {}
+
+
+def chain_scene(name):
+    if name not in _made:
+        if name in ("cornell", "three-spheres", "mesh"):
+            _made[name] = scene(name)
+        elif name == "cornell-all-mirror":  # every object that does not emit becomes a mirror: long chains, the cap, misses
+            _made[name] = R.with_reflect(scene("cornell"), lambda i, o: 1 if not any(o.emission) else None, name)
+        elif name == "mesh-glass":  # object 0, the 810-triangle BVH mesh, becomes glass: transmissions and total internal reflection
+            assert scene("mesh").objs[0].tri_count == 810
+            _made[name] = R.with_reflect(scene("mesh"), lambda i, o: 2 if i == 0 else None, name)
+        elif name == "three-spheres-delta":  # mirror, glass, mirror in front of nothing: chains that leave the scene
+            _made[name] = R.with_reflect(scene("three-spheres"), lambda i, o: (1, 2, 1)[i], name)
+        else:
+            raise KeyError(name)
+    return _made[name]
+
+
+_records = {}
+
+
+def record(name, spp, band=None):
+    """the chains of the frame's (or the band's) pixels at `spp` samples, walked once to PT_AOV_MAX_CHAIN steps"""
+    key = (name, spp, band)
+    if key not in _records:
+        sc = chain_scene(name)
+        pixels = call_pixels(W, H, band)
+        _records[key] = R.chain_record(sc, W, H, SEED, pixels, spp, oracle_rays(sc, W, H, SEED, pixels, spp))
+    return _records[key]
+
+
+# ------------------------------------------------------------------------------------------------------- the device
+class Dev:
+    def __init__(self, L, sc, npix_max=W * H):
+        self.L = L
+        self.ctx = C.c_void_p()
+        assert L.pt_ctx_create(0, C.byref(self.ctx)) == 0, L.pt_last_error()
+        if sc is not None:
+            assert L.pt_ctx_set_scene(self.ctx, C.byref(sc.cam), sc.objs, sc.n_objs, sc.tris, sc.n_tris) == 0, L.pt_last_error()
+        self.bufs = []
+        for nbytes in (npix_max * 12, npix_max * 12, npix_max * 4, npix_max * 4, npix_max * 4):
+            p = C.c_void_p()
+            assert L.pt_device_malloc(0, nbytes, C.byref(p)) == 0
+            self.bufs.append(p)
+
+    def call(self, cfg, params, which=(1, 1, 1, 1, 1)):
+        ptrs = [b if on else None for b, on in zip(self.bufs, which)]
+        return self.L.pt_ctx_render_aov_ex(self.ctx, C.byref(cfg), C.byref(params) if params is not None else None, *ptrs, None)
+
+    def plain(self, cfg):
+        assert self.L.pt_ctx_render_aov(self.ctx, C.byref(cfg), *self.bufs[:4], None) == 0, self.L.pt_last_error()
+        return self.download(self.L.pt_config_pixels(C.byref(cfg)))[:4]
+
+    def download(self, npix):
+        out = []
+        for p, (k, dt) in zip(self.bufs, ((3, F32), (3, F32), (1, F32), (1, np.int32), (1, np.uint32))):
+            host = np.zeros(npix * k, dtype=dt)
+            assert self.L.pt_device_download(0, host.ctypes.data_as(C.c_void_p), p, host.nbytes) == 0
+            out.append(host.reshape(npix, 3) if k == 3 else host)
+        return out
+
+    def aov(self, cfg, max_chain=0, flags=THROUGH_DELTA, which=(1, 1, 1, 1, 1)):
+        assert self.call(cfg, PtAovParams(flags, max_chain), which) == 0, self.L.pt_last_error()
+        return self.download(self.L.pt_config_pixels(C.byref(cfg)))
+
+    def close(self):
+        for p in self.bufs:
+            self.L.pt_device_free(0, p)
+        self.L.pt_ctx_destroy(self.ctx)
+
+
+def assert_bits(got, want, what):
+    for name, a, b in zip(NAMES, got, want):
+        a = np.ascontiguousarray(a)
+        b = np.ascontiguousarray(b, dtype=a.dtype).reshape(a.shape)
+        if a.tobytes() != b.tobytes():
+            bad = np.argwhere(a.view(np.uint32) != b.view(np.uint32))
+            raise AssertionError("%s %s: %d of %d words differ, first at %s: %r vs %r" % (
+                what, name, len(bad), a.size, bad[0], a[tuple(bad[0])], b[tuple(bad[0])]))
+
+
+# ------------------------------------------------------------------------------------------------------- tests
+def test_cornell_bit_equal_to_the_restatement(L):
+    rec = record("cornell", 100)
+    st = R.stats(rec)
+    print("cornell:", st)
+    # the headline scene: about 8 % of the pixels see a mirror or glass first, every chain ends on a diffuse surface
+    assert st["delta_pixels"] >= 0.05 * st["pixels"] and st["on_surface_after_delta"] == st["delta_pixels"]
+    assert st["mirror_steps"] > 0 and st["transmissions"] > 0
+    dev = Dev(L, chain_scene("cornell"))
+    try:
+        for spp in (1, 3, 64, 100):
+            got = dev.aov(cfg_of(W, H, spp))
+            assert_bits(got, R.planes(rec, spp), "cornell spp %d" % spp)
+        plain = dev.plain(cfg_of(W, H, 100))
+        assert plain[0].tobytes() != got[0].tobytes() and plain[2].tobytes() != got[2].tobytes()  # the guides do differ
+    finally:
+        dev.close()
+
+
+def _preconditions(name, st):
+    if name == "cornell-all-mirror":
+        assert st["at_cap"] >= 0.01 * st["pixels"], st
+        assert st["miss_after_delta"] > 0 and st["lengths"] == list(range(9)), st
+    elif name == "mesh-glass":
+        assert st["tir_steps"] >= 10 and st["transmissions"] > 0, st
+    elif name == "three-spheres-delta":
+        assert st["miss_after_delta"] >= 50, st
+
+
+@pytest.mark.parametrize("name", ["cornell-all-mirror", "mesh-glass", "three-spheres-delta"])
+def test_delta_scenes_bit_equal_to_the_restatement(L, name):
+    rec = record(name, 3)
+    st = R.stats(rec)  # sample 0, max_chain 8
+    print(name, st)
+    _preconditions(name, st)
+    band = (1200, 1328)  # two rows through the middle of the frame, at more than 64 samples: lanes loop, waves diverge
+    dev = Dev(L, chain_scene(name))
+    try:
+        for spp in (1, 3):
+            assert_bits(dev.aov(cfg_of(W, H, spp)), R.planes(rec, spp), "%s spp %d" % (name, spp))
+        assert_bits(dev.aov(cfg_of(W, H, 70, band=band)), R.planes(record(name, 70, band)), "%s spp 70, a band" % name)
+    finally:
+        dev.close()
+
+
+@pytest.mark.parametrize("cap", [1, 2, 8, 16])
+def test_caps_on_the_all_mirror_scene(L, cap):
+    name = "cornell-all-mirror"
+    rec = record(name, 3)
+    st = R.stats(rec, cap)
+    print(name, "cap", cap, st)
+    assert st["at_cap"] > 0 and st["max_length"] == cap, st  # the cap binds
+    dev = Dev(L, chain_scene(name))
+    try:
+        for spp in (1, 3):
+            got = dev.aov(cfg_of(W, H, spp), max_chain=cap)
+            assert_bits(got, R.planes(rec, spp, cap), "cap %d spp %d" % (cap, spp))
+        if cap == 8:  # max_chain 0 is 8
+            assert_bits(dev.aov(cfg_of(W, H, 3), max_chain=0), got, "max_chain 0")
+    finally:
+        dev.close()
+
+
+def test_flags_zero_is_the_plain_call(L):
+    dev = Dev(L, chain_scene("cornell"))
+    try:
+        for spp in (3, 64):
+            cfg = cfg_of(W, H, spp)
+            dev.aov(cfg)  # other contents in every plane, the chain plane included
+            want = dev.plain(cfg)
+            dev.aov(cfg_of(W, H, 1, seed=5))
+            for params in (None, PtAovParams(0, 0)):
+                assert dev.call(cfg, params) == 0, L.pt_last_error()
+                got = dev.download(W * H)
+                assert_bits(got, want + [np.zeros(W * H, np.uint32)], "flags 0, spp %d" % spp)
+                dev.aov(cfg_of(W, H, 1, seed=5))
+    finally:
+        dev.close()
+
+
+def test_a_scene_without_delta_surfaces_gives_the_plain_bits(L):
+    sc = chain_scene("three-spheres")
+    assert all(sc.objs[i].reflect_type == 0 for i in range(sc.n_objs))
+    dev = Dev(L, sc)
+    try:
+        for spp in (1, 5, 70):
+            cfg = cfg_of(W, H, spp)
+            want = dev.plain(cfg)
+            assert_bits(dev.aov(cfg), want + [np.zeros(W * H, np.uint32)], "no delta surface, spp %d" % spp)
+    finally:
+        dev.close()
+
+
+def test_linear_scan_gives_the_same_bits(L):
+    dev = Dev(L, chain_scene("mesh-glass"))
+    try:
+        for spp in (3, 64):
+            assert_bits(dev.aov(cfg_of(W, H, spp, flags=NO_BVH)), dev.aov(cfg_of(W, H, spp)), "NO_BVH spp %d" % spp)
+    finally:
+        dev.close()
+
+
+def test_bands_and_chunks_match_the_whole_frame(L):
+    dev = Dev(L, chain_scene("mesh-glass"))
+    spp = 5
+    try:
+        whole = dev.aov(cfg_of(W, H, spp))
+        parts = [dev.aov(cfg_of(W, H, spp, band=b)) for b in ((0, 1000), (1000, 1001), (1001, W * H))]
+        assert_bits([np.concatenate([p[i] for p in parts]) for i in range(5)], whole, "bands")
+        for band, chunks in ((None, (100, 1, 3)), ((500, 2300), (64, 2, 4)), (None, (7, 0, 2))):
+            idx = call_pixels(W, H, band, chunks)
+            cfg = cfg_of(W, H, spp, band=band, chunks=chunks)
+            assert L.pt_config_pixels(C.byref(cfg)) == len(idx)
+            assert_bits(dev.aov(cfg), [a[idx] for a in whole], "chunks %r %r" % (band, chunks))
+    finally:
+        dev.close()
+
+
+def test_each_output_may_be_null(L):
+    dev = Dev(L, chain_scene("cornell"))
+    try:
+        full = dev.aov(cfg_of(W, H, 4))
+        other = dev.aov(cfg_of(W, H, 2, seed=99))
+        for k in range(5):
+            which = tuple(int(i == k) for i in range(5))
+            dev.aov(cfg_of(W, H, 2, seed=99))
+            got = dev.aov(cfg_of(W, H, 4), which=which)
+            for i in range(5):
+                want = full[i] if i == k else other[i]
+                assert got[i].tobytes() == want.tobytes(), (k, i)
+        # flags 0 with the chain plane alone: zeros, the others untouched
+        dev.aov(cfg_of(W, H, 2, seed=99))
+        got = dev.aov(cfg_of(W, H, 4), flags=0, which=(0, 0, 0, 0, 1))
+        assert not got[4].any() and all(got[i].tobytes() == other[i].tobytes() for i in range(4))
+    finally:
+        dev.close()
+
+
+def test_errors(L):
+    dev = Dev(L, chain_scene("three-spheres-delta"))
+    try:
+        cfg = cfg_of(W, H, 4)
+        on = PtAovParams(THROUGH_DELTA, 0)
+        for bad in (PtAovParams(2, 0), PtAovParams(THROUGH_DELTA | 0x80000000, 0), PtAovParams(THROUGH_DELTA, MAX_CHAIN + 1),
+                    PtAovParams(0, 1), PtAovParams(0, MAX_CHAIN)):
+            assert dev.call(cfg, bad) == PT_ERR_INVALID, (bad.flags, bad.max_chain)
+        assert dev.call(cfg, on, which=(0, 0, 0, 0, 0)) == PT_ERR_INVALID
+        assert dev.call(cfg, None, which=(0, 0, 0, 0, 0)) == PT_ERR_INVALID
+        assert L.pt_ctx_render_aov_ex(None, C.byref(cfg), C.byref(on), *dev.bufs, None) == PT_ERR_INVALID
+        assert L.pt_ctx_render_aov_ex(dev.ctx, None, C.byref(on), *dev.bufs, None) == PT_ERR_INVALID
+        for bad in (cfg_of(W, H, 0), cfg_of(W, H, (1 << 24) + 1), cfg_of(W, H, 4, band=(10, 10)), cfg_of(W, H, 4, band=(0, W * H + 1)),
+                    cfg_of(W, H, 4, chunks=(0, 0, 2)), cfg_of(W, H, 4, chunks=(8, 3, 3)), cfg_of(0, H, 4)):
+            assert dev.call(bad, on) == PT_ERR_INVALID
+        assert dev.call(cfg, PtAovParams(THROUGH_DELTA, MAX_CHAIN)) == 0, L.pt_last_error()
+    finally:
+        dev.close()
+    bare = Dev(L, None, 16)
+    try:
+        assert bare.call(cfg_of(4, 4, 1), PtAovParams(THROUGH_DELTA, 0)) == PT_ERR_INVALID  # no scene
+    finally:
+        bare.close()
+
+
+def test_no_disturbance_of_accumulation(L):
+    dev = Dev(L, chain_scene("cornell"))
+    out = C.c_void_p()
+    assert L.pt_device_malloc(0, W * H * 12, C.byref(out)) == 0
+    try:
+        def frame(fn, spp):
+            st = PtStats()
+            assert fn(dev.ctx, C.byref(cfg_of(W, H, spp)), out, None, None, None, None, C.byref(st)) == 0, L.pt_last_error()
+            host = np.zeros((W * H, 3), F32)
+            assert L.pt_device_download(0, host.ctypes.data_as(C.c_void_p), out, host.nbytes) == 0
+            return host
+
+        def info():
+            lo, hi = C.c_uint32(), C.c_uint32()
+            assert L.pt_ctx_accum_info(dev.ctx, C.byref(cfg_of(W, H, 1)), C.byref(lo), C.byref(hi)) == 0
+            return lo.value, hi.value
+
+        frame(L.pt_ctx_accumulate, 8)
+        assert info() == (8, 8)
+        dev.aov(cfg_of(W, H, 16))
+        dev.aov(cfg_of(W, H, 3, band=(100, 900)), max_chain=2)
+        assert info() == (8, 8)
+        got = frame(L.pt_ctx_accumulate, 16)
+        assert got.tobytes() == frame(L.pt_ctx_render, 16).tobytes()
+    finally:
+        L.pt_device_free(0, out)
+        dev.close()
+
+
+def test_python_context_render_aov_through_delta(L):
+    pkg = importlib.import_module("path-tracer-rust_amd")
+    s = pkg.Scene(ptlib.scene_path("cornell"))
+    ctx = pkg.Context(0)
+    dev = Dev(L, chain_scene("cornell"))
+    try:
+        ctx.set_scene(s)
+        want = dev.aov(cfg_of(W, H, 6, chunks=(32, 1, 2)), max_chain=1)
+        dev.aov(cfg_of(W, H, 1, seed=3))  # other contents
+        p = [b.value for b in dev.bufs]
+        ctx.render_aov(W, H, 6, seed=SEED, chunks=(32, 1, 2), albedo=p[0], normal=p[1], depth=p[2], object_id=p[3], chain=p[4],
+                       through_delta=True, max_chain=1)
+        assert_bits(dev.download(len(want[2])), want, "python")
+        assert want[4].max() == 1
+        with pytest.raises(pkg.PtraceError):
+            ctx.render_aov(W, H, 6, depth=p[2], max_chain=3)  # max_chain without through_delta
+    finally:
+        dev.close()
+        ctx.close()
+        s.close()
+
+
+def test_cli_denoises_with_the_chain_guides(L, tmp_path):
+    """--denoise N --aov-chain: the frame itself is the one without --aov-chain; the denoised frame is pt_ctx_denoise's with the
+    chain call's guides at N samples, byte for byte"""
+    pkg = importlib.import_module("path-tracer-rust_amd")
+    cli = os.path.join(ptlib.PKG, "ptrace")
+    w, h, spp, seed, guide_spp = 36, 24, 6, 3, 4
+
+    def run(name, *more):
+        out = tmp_path / name
+        r = subprocess.run([cli, str(spp), str(h), "cornell", "--root", ptlib.ROOT, "--seed", str(seed), "--out", str(out), "--denoise",
+                            str(guide_spp)] + list(more), cwd=str(tmp_path), capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stdout + r.stderr
+        files = {f.split("-res%d-" % h)[1]: open(out / f, "rb").read() for f in os.listdir(out)}
+        assert set(files) == {".ppm", "denoised.ppm", "denoised.pfm"}, sorted(files)
+        return files, [f for f in os.listdir(out) if f.endswith("-denoised.pfm")][0]
+
+    plain, _ = run("plain")
+    chained, name = run("chain", "--aov-chain")
+    strip = lambda ppm: [ln for ln in ppm.split(b"\n") if not ln.startswith(b"#")]  # noqa: E731
+    assert strip(plain[".ppm"]) == strip(chained[".ppm"])
+    assert plain["denoised.pfm"] != chained["denoised.pfm"]
+    s = pkg.Scene(ptlib.scene_path("cornell"))
+    ctx = pkg.Context(0)
+    dev = Dev(L, None, w * h)
+    color = C.c_void_p()
+    assert L.pt_device_malloc(0, w * h * 12, C.byref(color)) == 0
+    try:
+        ctx.set_scene(s)
+        p = [b.value for b in dev.bufs]
+        ctx.render(color.value, w, h, spp, seed=seed)
+        ctx.render_aov(w, h, guide_spp, seed=seed, albedo=p[0], normal=p[1], depth=p[2], through_delta=True)
+        ctx.denoise(w, h, color.value, color.value, albedo=p[0], normal=p[1], depth=p[2])
+        want = np.zeros((w * h, 3), F32)
+        assert L.pt_device_download(0, want.ctypes.data_as(C.c_void_p), color, want.nbytes) == 0
+    finally:
+        L.pt_device_free(0, color)
+        dev.close()
+        ctx.close()
+        s.close()
+    got = pfm_to_framebuffer(read_pfm(tmp_path / "chain" / name))
+    assert got.tobytes() == want.tobytes()
+
+
+def test_cli_writes_the_chain_plane(L, tmp_path):
+    cli = os.path.join(ptlib.PKG, "ptrace")
+    out = tmp_path / "out"
+    r = subprocess.run([cli, "6", "24", "cornell", "--root", ptlib.ROOT, "--seed", "3", "--out", str(out), "--aov", "4",
+                        "--aov-chain", "3"], cwd=str(tmp_path), capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    files = sorted(os.listdir(out))
+    stem = [f for f in files if f.endswith(".ppm")][0][:-len(".ppm")]
+    w, h = 36, 24
+    dev = Dev(L, chain_scene("cornell"), w * h)
+    try:
+        want = dev.aov(cfg_of(w, h, 4, seed=3), max_chain=3)
+    finally:
+        dev.close()
+    got = [pfm_to_framebuffer(read_pfm(out / (stem + n + ".pfm"))) for n in ("albedo", "normal", "depth", "id", "chain")]
+    assert got[0].tobytes() == want[0].tobytes() and got[1].tobytes() == want[1].tobytes()
+    assert got[2][:, 0].tobytes() == want[2].tobytes()
+    assert (got[3][:, 0] == want[3].astype(F32)).all()
+    assert (got[4][:, 0] == want[4].astype(F32)).all() and want[4].max() >= 1

@@ -1,0 +1,156 @@
+#!/usr/bin/env python3
+"""What pt_ctx_render_aov_ex with PT_AOV_THROUGH_DELTA costs against pt_ctx_render_aov: for DESIGN.md section 4.  One process on
+one GPU, both calls in the same run, alternating.
+
+Per scene (cornell, mesh) and spp (8, 1) at 1024x768, with all four guide buffers (and the chain plane for the chain call):
+after a warm-up of both calls, ROUNDS rounds of [a window of N plain calls, a window of N chain calls], each window between two
+HIP events on a caller's stream, N chosen so that a window is at least WINDOW_MS.  Both calls block, so a window holds the
+host's turn-around per call too - the same for both.  Reported per call: the median over the rounds, the extremes, and
+chain_over_plain = the median of the per-round ratios.
+
+mesh.json has no mirror or glass surface: the chain call does the plain call's intersections plus one reflect-type test per hit,
+and its planes must be the plain call's bit for bit (checked here at the timed size).  Its budget is the plain call's time times
+BUDGET; the margin is for the chain loop's registers.  cornell has no budget: the chain call traces more rays there.  What bounds
+it is recorded with it - the mean of the chain plane (sample 0's extra rays per pixel) and the mean over waves of a wave's
+maximum (a wave loops until its longest chain ends; lanes are consecutive samples of one pixel at spp 8 and 8 pixels per wave,
+64 consecutive pixels per wave at spp 1, so the chain plane's maximum over those pixels stands for the wave's).
+
+    python tools/aov_chain_timing.py [out.json]
+"""
+import ctypes as C
+import json
+import os
+import statistics
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import ptlib  # noqa: E402
+from ptlib import PtConfig  # noqa: E402
+
+W, H = 1024, 768
+SPPS = (8, 1)
+SCENES = ("mesh", "cornell")
+BUDGET = 1.10
+BUDGETED = ("mesh",)
+WINDOW_MS = 250.0
+ROUNDS = 5
+THROUGH_DELTA = 1
+
+
+class PtAovParams(C.Structure):
+    _fields_ = [("flags", C.c_uint32), ("max_chain", C.c_uint32)]
+
+
+def hip_runtime():
+    for line in open("/proc/self/maps"):
+        path = line.split()[-1]
+        if "/libamdhip64.so" in path and "/torch/" not in path:
+            return C.CDLL(path)
+    raise RuntimeError("no HIP runtime mapped")
+
+
+def main():
+    L = ptlib.product()
+    L.pt_kernel_isa_hash.restype = C.c_char_p
+    L.pt_ctx_render_aov.argtypes = [C.c_void_p, C.POINTER(PtConfig)] + [C.c_void_p] * 5
+    L.pt_ctx_render_aov_ex.argtypes = [C.c_void_p, C.POINTER(PtConfig), C.POINTER(PtAovParams)] + [C.c_void_p] * 6
+    assert L.pt_device_count() >= 1, "aov_chain_timing needs a GPU: there is nothing to time without one"
+    hip = hip_runtime()
+    hip.hipEventElapsedTime.argtypes = [C.POINTER(C.c_float), C.c_void_p, C.c_void_p]
+    hip.hipEventRecord.argtypes = [C.c_void_p, C.c_void_p]
+    hip.hipEventSynchronize.argtypes = [C.c_void_p]
+    ctx = C.c_void_p()
+    assert L.pt_ctx_create(0, C.byref(ctx)) == 0, L.pt_last_error()
+    stream, e0, e1 = C.c_void_p(), C.c_void_p(), C.c_void_p()
+    assert hip.hipStreamCreate(C.byref(stream)) == 0
+    assert hip.hipEventCreate(C.byref(e0)) == 0 and hip.hipEventCreate(C.byref(e1)) == 0
+    n = W * H
+    sizes = (n * 12, n * 12, n * 4, n * 4, n * 4)
+    bufs = {}
+    for side in ("plain", "chain"):
+        bufs[side] = []
+        for nbytes in sizes:
+            p = C.c_void_p()
+            assert L.pt_device_malloc(0, nbytes, C.byref(p)) == 0, L.pt_last_error()
+            bufs[side].append(p)
+
+    def download(side):
+        out = []
+        for p, nbytes in zip(bufs[side], sizes):
+            host = np.zeros(nbytes // 4, dtype=np.uint32)
+            assert L.pt_device_download(0, host.ctypes.data_as(C.c_void_p), p, nbytes) == 0
+            out.append(host)
+        return out
+
+    def timed(fn, calls):
+        assert hip.hipEventRecord(e0, stream) == 0
+        for _ in range(calls):
+            fn()
+        assert hip.hipEventRecord(e1, stream) == 0
+        assert hip.hipEventSynchronize(e1) == 0
+        ms = C.c_float()
+        assert hip.hipEventElapsedTime(C.byref(ms), e0, e1) == 0
+        return ms.value / calls
+
+    doc = {"command": "python tools/aov_chain_timing.py", "isa_hash": L.pt_kernel_isa_hash().decode(), "size": [W, H],
+           "method": "%d rounds of [N plain calls, N chain calls], each window between two HIP events on one stream (window >= %.0f ms), "
+                     "after a warm-up of both; ms per call; chain_over_plain = median of the per-round ratios" % (ROUNDS, WINDOW_MS),
+           "budget_rule": "scenes without a delta surface (%s): chain <= %.2f x plain" % (", ".join(BUDGETED), BUDGET),
+           "max_chain": 8, "cases": {}}
+    on = PtAovParams(THROUGH_DELTA, 0)
+    for sid in SCENES:
+        sc = ptlib.load_scene_py(ptlib.scene_path(sid))
+        assert L.pt_ctx_set_scene(ctx, C.byref(sc.cam), sc.objs, sc.n_objs, sc.tris, sc.n_tris) == 0, L.pt_last_error()
+        for spp in SPPS:
+            cfg = PtConfig(W, H, spp, 0, 7, 0, 0, 0, 0)
+
+            def plain():
+                assert L.pt_ctx_render_aov(ctx, C.byref(cfg), *bufs["plain"][:4], stream) == 0, L.pt_last_error()
+
+            def chain():
+                assert L.pt_ctx_render_aov_ex(ctx, C.byref(cfg), C.byref(on), *bufs["chain"], stream) == 0, L.pt_last_error()
+
+            timed(plain, 10)
+            timed(chain, 10)
+            calls = max(10, int(WINDOW_MS / max(timed(chain, 20), timed(plain, 20))) + 1)
+            rounds = [(timed(plain, calls), timed(chain, calls)) for _ in range(ROUNDS)]
+            a, b = download("plain"), download("chain")
+            plane = b[4]
+            group = 64 // min(spp, 64)  # pixels per wave
+            per_wave = plane[:n - n % group].reshape(-1, group).max(axis=1)
+            res = {"calls_per_window": calls,
+                   "plain_ms": {"median": statistics.median(r[0] for r in rounds), "min": min(r[0] for r in rounds),
+                                "max": max(r[0] for r in rounds)},
+                   "chain_ms": {"median": statistics.median(r[1] for r in rounds), "min": min(r[1] for r in rounds),
+                                "max": max(r[1] for r in rounds)},
+                   "chain_over_plain": statistics.median(r[1] / r[0] for r in rounds),
+                   "ratio_min": min(r[1] / r[0] for r in rounds), "ratio_max": max(r[1] / r[0] for r in rounds),
+                   "chain_plane_mean": float(plane.mean()), "chain_plane_max": int(plane.max()),
+                   "chain_plane_mean_of_wave_max": float(per_wave.mean()),
+                   "same_bits_as_plain": bool(all(x.tobytes() == y.tobytes() for x, y in zip(a[:4], b[:4])))}
+            if sid in BUDGETED:
+                assert res["same_bits_as_plain"] and res["chain_plane_max"] == 0, "a scene without delta surfaces must give the plain bits"
+                res["budget"] = BUDGET
+                res["verdict"] = "HIT" if res["chain_over_plain"] <= BUDGET else "MISS"
+            key = "%s %dx%d @ %d spp" % (sid, W, H, spp)
+            doc["cases"][key] = res
+            print(key, json.dumps(res), flush=True)
+    for side in bufs.values():
+        for p in side:
+            L.pt_device_free(0, p)
+    hip.hipEventDestroy(e0)
+    hip.hipEventDestroy(e1)
+    hip.hipStreamDestroy(stream)
+    L.pt_ctx_destroy(ctx)
+    path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "aov_chain_timing.json")
+    with open(path, "w") as f:
+        json.dump(doc, f, indent=1)
+        f.write("\n")
+    print("->", path)
+
+
+if __name__ == "__main__":
+    main()
