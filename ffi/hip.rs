@@ -122,6 +122,15 @@ pub struct PtReprojectVarParams {
     pub flags: u32,
 }
 
+// one record of pt_ctx_reproject_moved's per-object motion table: the surface point now at P was at P * scale + offset in the
+// history frame; (0, 0, 0, 1) bit for bit = did not move, scale 0 = no usable history (pt_object_motion_between makes one)
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct PtObjectMotion {
+    pub offset: [f32; 3],
+    pub scale: f32,
+}
+
 // pt_ctx_upsample's parameters; a zero field = the library's default (pt_upsample_defaults)
 #[repr(C)]
 #[derive(Clone, Copy, Default, Debug)]
@@ -556,6 +565,68 @@ extern "C" {
         d_out_moments: *mut f32,
         d_error: *mut f32,
         hip_stream: *mut c_void,
+    ) -> i32;
+    // the two calls with a per-object motion table (a HOST array, copied by the call): history carried on objects that
+    // pt_ctx_set_object moved; motion null, n_motion 0 or all records IDENTITY = the plain calls
+    pub fn pt_object_motion_between(now: *const PtObject, before: *const PtObject, out: *mut PtObjectMotion) -> i32;
+    pub fn pt_ctx_reproject_moved(
+        ctx: *mut PtCtx,
+        width: u32,
+        height: u32,
+        params: *const PtReprojectParams,
+        cam: *const PtCamera,
+        d_color: *const f32,
+        d_depth: *const f32,
+        d_object_id: *const i32,
+        d_normal: *const f32,
+        hist_cam: *const PtCamera,
+        d_hist_color: *const f32,
+        d_hist_len: *const f32,
+        d_hist_depth: *const f32,
+        d_hist_object_id: *const i32,
+        d_hist_normal: *const f32,
+        d_out_color: *mut f32,
+        d_out_len: *mut f32,
+        motion: *const PtObjectMotion,
+        n_motion: u32,
+        hip_stream: *mut c_void,
+    ) -> i32;
+    pub fn pt_ctx_reproject_var_moved(
+        ctx: *mut PtCtx,
+        width: u32,
+        height: u32,
+        params: *const PtReprojectVarParams,
+        cam: *const PtCamera,
+        d_color: *const f32,
+        d_depth: *const f32,
+        d_object_id: *const i32,
+        d_normal: *const f32,
+        hist_cam: *const PtCamera,
+        d_hist_color: *const f32,
+        d_hist_len: *const f32,
+        d_hist_moments: *const f32,
+        d_hist_depth: *const f32,
+        d_hist_object_id: *const i32,
+        d_hist_normal: *const f32,
+        d_out_color: *mut f32,
+        d_out_len: *mut f32,
+        d_out_moments: *mut f32,
+        d_error: *mut f32,
+        motion: *const PtObjectMotion,
+        n_motion: u32,
+        hip_stream: *mut c_void,
+    ) -> i32;
+    pub fn pt_reproject_project_moved_host(
+        cam: *const PtCamera,
+        hist_cam: *const PtCamera,
+        width: u32,
+        height: u32,
+        idx: u32,
+        depth: f32,
+        rec: *const PtObjectMotion,
+        px: *mut f32,
+        pr: *mut f32,
+        zexp: *mut f32,
     ) -> i32;
     pub fn pt_reproject_project_host(
         cam: *const PtCamera,

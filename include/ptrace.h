@@ -1126,6 +1126,79 @@ int pt_ctx_reproject_var(pt_ctx *ctx, uint32_t width, uint32_t height, const pt_
                          float *d_out_color, float *d_out_len, float *d_out_moments, float *d_error,
                          void *hip_stream);
 
+/* ---- reprojecting history through object edits: per-object motion ------------------------------------------------------
+ * pt_ctx_reproject and pt_ctx_reproject_var follow the camera: step 3 puts the point a pixel sees into the history camera as if
+ * the world had stood still.  pt_ctx_reproject_moved and pt_ctx_reproject_var_moved take a table of per-object motion records as
+ * well, so that a frame in which pt_ctx_set_object moved an object keeps the object's history.
+ *
+ * THE RECORD.  motion[i] says where the surface point of object i that is now at P was in the history frame:
+ * Pm[a] = P[a]*scale + offset[a] - two binary32 operations per component, never fused.  That covers every geometry edit
+ * pt_ctx_set_object takes: a translation of a sphere or a mesh, and a sphere's radius.  Translation and uniform scale keep
+ * normals, so the normal test is unchanged.
+ * - IDENTITY, "did not move", is recognised by its bits: the scale word equals 1.0f and the three offset words equal +0.0f.
+ * - A record with scale == 0 is the MARKER "this object has no usable history".
+ * - Any other record needs a finite scale > 0 and finite offsets.
+ * pt_object_motion_between(now, before, out) makes the record of one edit.  The marker when kind, tri_offset or tri_count differ;
+ * when any word of color, emission or reflect_type differs (the object's old radiance is then not its new radiance); when a
+ * sphere's now->radius is 0; when a position or (of a sphere) a radius is not finite.  Sphere: scale = |before.radius| /
+ * |now.radius|; offset[a] = before.position[a] - now.position[a]*scale.  Mesh: scale = 1; offset[a] = before.position[a] -
+ * now.position[a]; bs_center and bs_radius are not read.  Equal geometry then yields IDENTITY exactly (a difference of -0.0f is
+ * stored as +0.0f).  Should the arithmetic leave the finite numbers, or a sphere's scale come out 0, the record is the marker.
+ * PT_ERR_INVALID for a NULL pointer.  Host only.
+ *
+ * `motion` is a HOST array of n_motion records, indexed by object id.  The call copies it into scratch of the context, 16 B per
+ * record, on the call's stream: the scratch grows on demand, lies outside the ray-queue budget, is freed by pt_ctx_destroy and is
+ * shared with nothing.  The call changes no other state of the context (pt_ctx_reproject_var_moved: but for
+ * pt_ctx_reproject_var's plane of s values).
+ *
+ * THE ARITHMETIC of pt_ctx_reproject_moved is pt_ctx_reproject's, word for word, with this inserted ahead of step 2 for a pixel
+ * with id = object_id[idx] >= 0:
+ *    rec = (uint32)id < n_motion ? motion[id] : IDENTITY.  An id beyond the table is never an error and never a read outside it.
+ *    rec is the marker: step 1 - out = color, len_out = wt.
+ *    rec is IDENTITY: steps 2-5 exactly as they are.
+ *    Otherwise step 2 is never taken, not even under bitwise-equal cameras, and step 3 runs with v = Pm - L'.  The rest is
+ *    unchanged: a, t, w, px, pr, zexp = sqrt(dot(v, v)), the four taps and their tests, the blend.
+ * pt_ctx_reproject_var_moved is pt_ctx_reproject_var with "colour, length and taps are pt_ctx_reproject_moved's": the moments
+ * ride the same taps; the spatial estimate does not read the table.
+ * - Delegation: with motion == NULL, n_motion == 0, or every record IDENTITY (the host checks in O(n_motion)), the call is
+ *   today's launch of pt_ctx_reproject / pt_ctx_reproject_var, unchanged, and copies nothing: their bytes by construction, and
+ *   a loop in which nothing moves pays nothing.
+ * - PT_ERR_INVALID, all refused before any device is touched: pt_ctx_reproject's (pt_ctx_reproject_var's) own in their order,
+ *   then n_motion above 2^20; motion == NULL with n_motion != 0; a record that is neither IDENTITY nor a marker and has a
+ *   non-finite or negative scale or a non-finite offset.
+ * - Out of scope: the table describes the FIRST-HIT guides.  With PT_AOV_THROUGH_DELTA guides the id is the reflected object's and
+ *   the depth is unfolded, so the map is meaningless there.  Light that changed elsewhere - the moved object's shadow, its bounce
+ *   light - is stale history that no reprojection detects: a matter for the max_history policy on frames in which something
+ *   moved (profiles/reproject_moved_cpu_study.json).
+ * pt_reproject_project_moved_host is pt_reproject_project_host with the record `rec` (not NULL; a marker is refused with
+ * PT_ERR_INVALID, as a record the calls refuse is): step 3 with the mapped point, the host instantiation of what the moved
+ * kernels compile.  With an IDENTITY record it is pt_reproject_project_host. */
+typedef struct pt_object_motion {
+    float offset[3];
+    float scale;
+} pt_object_motion; /* 16 B */
+int pt_object_motion_between(const pt_object *now, const pt_object *before, pt_object_motion *out); /* host only */
+int pt_ctx_reproject_moved(pt_ctx *ctx, uint32_t width, uint32_t height, const pt_reproject_params *params,
+                           const pt_camera *cam, const float *d_color, const float *d_depth,
+                           const int32_t *d_object_id, const float *d_normal /* may be NULL */,
+                           const pt_camera *hist_cam, const float *d_hist_color, const float *d_hist_len,
+                           const float *d_hist_depth, const int32_t *d_hist_object_id,
+                           const float *d_hist_normal /* may be NULL */,
+                           float *d_out_color, float *d_out_len,
+                           const pt_object_motion *motion /* host */, uint32_t n_motion, void *hip_stream);
+int pt_ctx_reproject_var_moved(pt_ctx *ctx, uint32_t width, uint32_t height, const pt_reproject_var_params *params,
+                               const pt_camera *cam, const float *d_color, const float *d_depth,
+                               const int32_t *d_object_id, const float *d_normal /* may be NULL */,
+                               const pt_camera *hist_cam, const float *d_hist_color, const float *d_hist_len,
+                               const float *d_hist_moments, const float *d_hist_depth,
+                               const int32_t *d_hist_object_id, const float *d_hist_normal /* may be NULL */,
+                               float *d_out_color, float *d_out_len, float *d_out_moments, float *d_error,
+                               const pt_object_motion *motion /* host */, uint32_t n_motion, void *hip_stream);
+/* host only, no device */
+int pt_reproject_project_moved_host(const pt_camera *cam, const pt_camera *hist_cam, uint32_t width,
+                                    uint32_t height, uint32_t idx, float depth, const pt_object_motion *rec,
+                                    float *px, float *pr, float *zexp);
+
 /* ---- tracing at low resolution and filling the frame in through the guides ---------------------------------------------
  * pt_ctx_upsample fills a frame of width x height pixels from a colour frame traced at lo_width x lo_height: a joint bilateral
  * upsampler (Kopf et al. 2007) over the first-hit guides of BOTH sizes.  The paths, about nine intersections per sample, are

@@ -76,6 +76,10 @@ class pt_reproject_var_params(C.Structure):
                 ("min_frames", C.c_uint32), ("radius", C.c_uint32), ("flags", C.c_uint32)]
 
 
+class pt_object_motion(C.Structure):
+    _fields_ = [("offset", C.c_float * 3), ("scale", C.c_float)]
+
+
 class pt_upsample_params(C.Structure):
     _fields_ = [("depth_tol", C.c_float), ("normal_min", C.c_float), ("flags", C.c_uint32)]
 
@@ -214,6 +218,11 @@ def lib():
     L.pt_ctx_reproject_var.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(pt_reproject_var_params), C.POINTER(pt_camera)] + \
         [C.c_void_p] * 4 + [C.POINTER(pt_camera)] + [C.c_void_p] * 11
     L.pt_reproject_project_host.argtypes = [C.POINTER(pt_camera), C.POINTER(pt_camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_float] + \
+        [C.POINTER(C.c_float)] * 3
+    L.pt_object_motion_between.argtypes = [C.POINTER(pt_object), C.POINTER(pt_object), C.POINTER(pt_object_motion)]
+    L.pt_ctx_reproject_moved.argtypes = L.pt_ctx_reproject.argtypes[:-1] + [C.POINTER(pt_object_motion), C.c_uint32, C.c_void_p]
+    L.pt_ctx_reproject_var_moved.argtypes = L.pt_ctx_reproject_var.argtypes[:-1] + [C.POINTER(pt_object_motion), C.c_uint32, C.c_void_p]
+    L.pt_reproject_project_moved_host.argtypes = L.pt_reproject_project_host.argtypes[:6] + [C.POINTER(pt_object_motion)] + \
         [C.POINTER(C.c_float)] * 3
     L.pt_upsample_defaults.argtypes = [C.POINTER(pt_upsample_params)]
     L.pt_ctx_upsample.argtypes = [C.c_void_p] + [C.c_uint32] * 4 + [C.POINTER(pt_upsample_params)] + [C.c_void_p] * 12
@@ -466,6 +475,35 @@ class Context:
                                           ptr(h.get("len")), ptr(h.get("moments")), ptr(h.get("depth")), ptr(h.get("object_id")),
                                           ptr(h.get("normal")), ptr(out_color), ptr(out_len), ptr(out_moments), ptr(error),
                                           C.c_void_p(stream or 0)))
+
+    def reproject_var_moved(self, width, height, cam, color, depth, object_id, out_color, out_len, out_moments, error, motion,
+                            normal=None, history=None, weight=1, max_history=0.0, depth_tol=0.0, normal_min=0.0, min_frames=0,
+                            radius=0, stream=None):
+        """reproject_var() with history carried on objects that set_object() moved (pt_ctx_reproject_var_moved).  `motion`: a
+        sequence indexed by object id of pt_object_motion records or (ox, oy, oz, scale) tuples, as object_motion_between()
+        makes them - host data, copied by the call; empty, or all (0, 0, 0, 1), is reproject_var() itself."""
+        p = pt_reproject_var_params(weight, max_history, depth_tol, normal_min, min_frames, radius, 0)
+        ptr = lambda q: C.c_void_p(q) if q else None  # noqa: E731
+        h = history or {}
+        table = _motion_table(motion)
+        _check(lib().pt_ctx_reproject_var_moved(self._h, width, height, C.byref(p), _camera(cam), ptr(color), ptr(depth),
+                                                ptr(object_id), ptr(normal), _camera(h["cam"]) if history else None,
+                                                ptr(h.get("color")), ptr(h.get("len")), ptr(h.get("moments")), ptr(h.get("depth")),
+                                                ptr(h.get("object_id")), ptr(h.get("normal")), ptr(out_color), ptr(out_len),
+                                                ptr(out_moments), ptr(error), table, len(motion), C.c_void_p(stream or 0)))
+
+    def reproject_moved(self, width, height, cam, color, depth, object_id, out_color, out_len, motion, normal=None, history=None,
+                        weight=1, max_history=0.0, depth_tol=0.0, normal_min=0.0, stream=None):
+        """reproject() with history carried on objects that set_object() moved (pt_ctx_reproject_moved); `motion` as for
+        reproject_var_moved()."""
+        p = pt_reproject_params(weight, max_history, depth_tol, normal_min, 0)
+        ptr = lambda q: C.c_void_p(q) if q else None  # noqa: E731
+        h = history or {}
+        table = _motion_table(motion)
+        _check(lib().pt_ctx_reproject_moved(self._h, width, height, C.byref(p), _camera(cam), ptr(color), ptr(depth), ptr(object_id),
+                                            ptr(normal), _camera(h["cam"]) if history else None, ptr(h.get("color")),
+                                            ptr(h.get("len")), ptr(h.get("depth")), ptr(h.get("object_id")), ptr(h.get("normal")),
+                                            ptr(out_color), ptr(out_len), table, len(motion), C.c_void_p(stream or 0)))
 
     def upsample(self, width, height, lo_width, lo_height, lo, depth, object_id, out_color, normal=None, albedo=None,
                  out_weight=None, depth_tol=0.0, normal_min=0.0, stream=None):
@@ -748,6 +786,25 @@ def upsample_tap_host(size, lo_size, coord):
     first, frac = C.c_int32(), C.c_float()
     _check(lib().pt_upsample_tap_host(size, lo_size, coord, C.byref(first), C.byref(frac)))
     return first.value, frac.value
+
+
+def _motion_table(motion):
+    """a ctypes array of pt_object_motion (None when empty) from records or (ox, oy, oz, scale) tuples"""
+    if not len(motion):
+        return None
+    arr = (pt_object_motion * len(motion))()
+    for i, r in enumerate(motion):
+        arr[i] = r if isinstance(r, pt_object_motion) else pt_object_motion((C.c_float * 3)(*r[:3]), r[3])
+    return arr
+
+
+def object_motion_between(now, before):
+    """The motion record of one set_object() edit: where the surface point of `now` (a pt_object) was on `before`
+    (pt_object_motion_between) - (0, 0, 0, 1) for equal geometry, scale 0 (the marker: no usable history) when the material or
+    the kind changed."""
+    r = pt_object_motion()
+    _check(lib().pt_object_motion_between(C.byref(now), C.byref(before), C.byref(r)))
+    return r
 
 
 def reproject_project_host(cam, hist_cam, width, height, idx, depth):

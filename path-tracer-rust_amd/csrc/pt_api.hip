@@ -396,6 +396,8 @@ struct pt_ctx {
     DevBuf<unsigned long long> pr_mid;
     // pt_ctx_reproject_var's scratch, its own too: the frame's s values, one float per pixel, grown on demand
     DevBuf<float> rv_s;
+    // pt_ctx_reproject*_moved's scratch, its own too: the call's motion table, 16 B per record, grown on demand
+    DevBuf<pt_object_motion> rm_table;
     // The adaptive calls: the frame kept between calls (pt_ctx_set_scene drops it), and their scratch, kept too and grown on
     // demand: the compact accumulator of a step's tiles, the step's open-tile list, the counters (u64 [0]: the sum of E at the
     // end; u32 [2], [3]: the tiles a step left open / closed; u32 [4]: the list's length; u32 [5..7]: k_tile_select's counts),
@@ -3050,6 +3052,73 @@ int pt_ctx_reproject_var(pt_ctx *c, uint32_t width, uint32_t height, const pt_re
         if (rs) return rs;
         v.s_plane = c->rv_s.p;
         launch_reproject_var(st, v);
+        return PT_OK;
+    });
+}
+
+// the moved calls' table, copied into the context's scratch on the call's stream (the call waits for the stream before it returns,
+// so the caller's array outlives the copy)
+static int upload_motion(pt_ctx *c, hipStream_t st, const pt_object_motion *motion, uint32_t n_motion, ReprojectMotion &m) {
+    const int rt = c->rm_table.ensure(n_motion);
+    if (rt) return rt;
+    const hipError_t e = hipMemcpyAsync(c->rm_table.p, motion, (size_t)n_motion * sizeof(pt_object_motion), hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) {
+        set_error(std::string("uploading the motion table: ") + hipGetErrorString(e));
+        return PT_ERR_HIP;
+    }
+    m = ReprojectMotion{c->rm_table.p, n_motion};
+    return PT_OK;
+}
+
+int pt_ctx_reproject_moved(pt_ctx *c, uint32_t width, uint32_t height, const pt_reproject_params *params, const pt_camera *cam,
+                           const float *d_color, const float *d_depth, const int32_t *d_object_id, const float *d_normal,
+                           const pt_camera *hist_cam, const float *d_hist_color, const float *d_hist_len, const float *d_hist_depth,
+                           const int32_t *d_hist_object_id, const float *d_hist_normal, float *d_out_color, float *d_out_len,
+                           const pt_object_motion *motion, uint32_t n_motion, void *hip_stream) {
+    ReprojectFrame f;
+    int how = host::kMotionPlain;
+    const int rc = host::check_reproject_moved(c, width, height, params, cam, d_color, d_depth, d_object_id, d_normal, hist_cam,
+                                               d_hist_color, d_hist_len, d_hist_depth, d_hist_object_id, d_hist_normal, d_out_color,
+                                               d_out_len, motion, n_motion, f, &how);
+    if (rc) return rc;
+    return run_image_pass(c, hip_stream, [&](hipStream_t st) {
+        if (how == host::kMotionPlain || !f.hist_color) {  // nothing moved, or no history for it to move in
+            launch_reproject(st, f);
+            return PT_OK;
+        }
+        ReprojectMotion m;
+        const int ru = upload_motion(c, st, motion, n_motion, m);
+        if (ru) return ru;
+        launch_reproject_moved(st, f, m);
+        return PT_OK;
+    });
+}
+
+int pt_ctx_reproject_var_moved(pt_ctx *c, uint32_t width, uint32_t height, const pt_reproject_var_params *params, const pt_camera *cam,
+                               const float *d_color, const float *d_depth, const int32_t *d_object_id, const float *d_normal,
+                               const pt_camera *hist_cam, const float *d_hist_color, const float *d_hist_len, const float *d_hist_moments,
+                               const float *d_hist_depth, const int32_t *d_hist_object_id, const float *d_hist_normal, float *d_out_color,
+                               float *d_out_len, float *d_out_moments, float *d_error, const pt_object_motion *motion, uint32_t n_motion,
+                               void *hip_stream) {
+    ReprojectVarFrame v;
+    int how = host::kMotionPlain;
+    const int rc = host::check_reproject_var_moved(c, width, height, params, cam, d_color, d_depth, d_object_id, d_normal, hist_cam,
+                                                   d_hist_color, d_hist_len, d_hist_moments, d_hist_depth, d_hist_object_id,
+                                                   d_hist_normal, d_out_color, d_out_len, d_out_moments, d_error, motion, n_motion, v,
+                                                   &how);
+    if (rc) return rc;
+    return run_image_pass(c, hip_stream, [&](hipStream_t st) {
+        const int rs = c->rv_s.ensure((size_t)width * height);
+        if (rs) return rs;
+        v.s_plane = c->rv_s.p;
+        if (how == host::kMotionPlain || !v.f.hist_color) {
+            launch_reproject_var(st, v);
+            return PT_OK;
+        }
+        ReprojectMotion m;
+        const int ru = upload_motion(c, st, motion, n_motion, m);
+        if (ru) return ru;
+        launch_reproject_var_moved(st, v, m);
         return PT_OK;
     });
 }

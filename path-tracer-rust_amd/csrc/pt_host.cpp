@@ -1824,6 +1824,50 @@ int check_reproject_var(const void *ctx, uint32_t width, uint32_t height, const 
     return PT_OK;
 }
 
+// ---- pt_ctx_reproject_moved, pt_ctx_reproject_var_moved: the plain call's refusals, then the table's
+int check_reproject_motion(int rc_plain, const pt_object_motion *motion, uint32_t n_motion, int *how) {
+    if (rc_plain) return rc_plain;
+    if (n_motion > kReprojectMaxMotion) return refuse("n_motion exceeds 2^20");
+    if (!motion && n_motion) return refuse("motion is NULL with n_motion != 0");
+    bool plain = true;
+    for (uint32_t i = 0; i < (motion ? n_motion : 0u); ++i) {
+        const pt_object_motion &r = motion[i];
+        if (reproject_rec_identity(r) || reproject_rec_marker(r)) {
+            plain = plain && !reproject_rec_marker(r);
+            continue;
+        }
+        plain = false;
+        const bool fin = std::isfinite(r.offset[0]) && std::isfinite(r.offset[1]) && std::isfinite(r.offset[2]);
+        if (!(r.scale > 0.0f && r.scale < __builtin_inff()) || !fin)
+            return refuse("motion: a record that is neither IDENTITY nor the marker needs a finite scale > 0 and finite offsets");
+    }
+    *how = plain ? kMotionPlain : kMotionTable;
+    return PT_OK;
+}
+
+int check_reproject_moved(const void *ctx, uint32_t width, uint32_t height, const pt_reproject_params *params, const pt_camera *cam,
+                          const float *d_color, const float *d_depth, const int32_t *d_object_id, const float *d_normal,
+                          const pt_camera *hist_cam, const float *d_hist_color, const float *d_hist_len, const float *d_hist_depth,
+                          const int32_t *d_hist_object_id, const float *d_hist_normal, float *d_out_color, float *d_out_len,
+                          const pt_object_motion *motion, uint32_t n_motion, ReprojectFrame &f, int *how) {
+    return check_reproject_motion(check_reproject(ctx, width, height, params, cam, d_color, d_depth, d_object_id, d_normal, hist_cam,
+                                                  d_hist_color, d_hist_len, d_hist_depth, d_hist_object_id, d_hist_normal, d_out_color,
+                                                  d_out_len, f),
+                                  motion, n_motion, how);
+}
+
+int check_reproject_var_moved(const void *ctx, uint32_t width, uint32_t height, const pt_reproject_var_params *params,
+                              const pt_camera *cam, const float *d_color, const float *d_depth, const int32_t *d_object_id,
+                              const float *d_normal, const pt_camera *hist_cam, const float *d_hist_color, const float *d_hist_len,
+                              const float *d_hist_moments, const float *d_hist_depth, const int32_t *d_hist_object_id,
+                              const float *d_hist_normal, float *d_out_color, float *d_out_len, float *d_out_moments, float *d_error,
+                              const pt_object_motion *motion, uint32_t n_motion, ReprojectVarFrame &v, int *how) {
+    return check_reproject_motion(check_reproject_var(ctx, width, height, params, cam, d_color, d_depth, d_object_id, d_normal, hist_cam,
+                                                      d_hist_color, d_hist_len, d_hist_moments, d_hist_depth, d_hist_object_id,
+                                                      d_hist_normal, d_out_color, d_out_len, d_out_moments, d_error, v),
+                                  motion, n_motion, how);
+}
+
 // ---- pt_ctx_upsample (ptrace.h, pt_upsample.h)
 int check_upsample(const void *ctx, uint32_t width, uint32_t height, uint32_t lo_width, uint32_t lo_height,
                    const pt_upsample_params *params, const float *d_lo_color, const float *d_lo_depth, const int32_t *d_lo_object_id,

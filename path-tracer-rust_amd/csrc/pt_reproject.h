@@ -3,8 +3,9 @@
 // 2017).  The arithmetic is the contract in include/ptrace.h ("THE ARITHMETIC" of pt_ctx_reproject), operation for operation.
 // Steps 3 to 5 - and the pixel that strings them together - are stated once, below, for host and device:
 // pt_reproject_project_host (host/scene_io.cpp) is the host instantiation of the projection the kernel compiles, as
-// pt_present_quantize_host is of pt_present.h.  A translation unit of its own: pt_kernels.s, and so pt_kernel_isa_hash(),
-// describes the pass kernels only.
+// pt_present_quantize_host is of pt_present.h.  pt_ctx_reproject_moved and pt_ctx_reproject_var_moved - history carried through
+// pt_ctx_set_object's edits by a per-object motion table - are the same functions with MOVED compiled in.  A translation unit
+// of its own: pt_kernels.s, and so pt_kernel_isa_hash(), describes the pass kernels only.
 #pragma once
 
 #include "../../include/ptrace.h"
@@ -63,15 +64,50 @@ struct ReprojectPos {
     float px, pr, zexp;
 };
 
+// ---- pt_ctx_reproject_moved: the per-object motion table ("THE RECORD" in include/ptrace.h).  Device memory on the device (the
+// context's scratch, 16-byte aligned), the caller's array on the host.
+struct ReprojectMotion {
+    const pt_object_motion *table;
+    uint32_t n;
+};
+PT_HD uint32_t reproject_bits(float v) { return __builtin_bit_cast(uint32_t, v); }
+// IDENTITY by its bits: scale 1.0f, the three offsets +0.0f
+PT_HD bool reproject_rec_identity(const pt_object_motion &r) {
+    return reproject_bits(r.scale) == 0x3f800000u && (reproject_bits(r.offset[0]) | reproject_bits(r.offset[1]) | reproject_bits(r.offset[2])) == 0u;
+}
+// the MARKER: scale == 0 (either sign)
+PT_HD bool reproject_rec_marker(const pt_object_motion &r) { return r.scale == 0.0f; }
+// the record of object `id` (>= 0): an id beyond the table reads nothing and stands for IDENTITY.  One 16-byte load.
+PT_HD pt_object_motion reproject_rec(const ReprojectMotion &m, int32_t id) {
+    pt_object_motion r = {{0.0f, 0.0f, 0.0f}, 1.0f};
+    if ((uint32_t)id < m.n) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        const float4 q = *reinterpret_cast<const float4 *>(m.table + (uint32_t)id);
+        r.offset[0] = q.x, r.offset[1] = q.y, r.offset[2] = q.z, r.scale = q.w;
+#else
+        r = m.table[(uint32_t)id];
+#endif
+    }
+    return r;
+}
+
 // step 3 up to the reject test: where the point pixel idx sees at `depth` lies in the history frame.  false: no position.
-PT_HD bool reproject_project(const ReprojectView &V, uint32_t W, uint32_t H, uint32_t idx, float depth, ReprojectPos &o) {
+// MOVED (pt_ctx_reproject_moved): the point goes through the object's record first - Pm[a] = P[a]*scale + offset[a], two
+// operations per component - unless the record is IDENTITY, which leaves P's bits alone.
+template <bool MOVED = false>
+PT_HD bool reproject_project(const ReprojectView &V, uint32_t W, uint32_t H, uint32_t idx, float depth, ReprojectPos &o,
+                             const pt_object_motion *rec = nullptr) {
     const uint32_t x = idx % W, r = idx / W, y = H - 1u - r;
     const float fw = (float)W, fh = (float)H;
     const float sx = ((float)x + 0.5f) / fw - 0.5f;
     const float sy = ((float)y + 0.5f) / fh - 0.5f;
     const vec3 S = (V.C + V.su * sx) + V.sv * sy;
     const vec3 g = V.L - S;
-    const vec3 P = V.L + (g * (1.0f / __builtin_sqrtf(dot(g, g)))) * depth;
+    vec3 P = V.L + (g * (1.0f / __builtin_sqrtf(dot(g, g)))) * depth;
+    if constexpr (MOVED) {
+        const vec3 Pm = mk(P.x * rec->scale + rec->offset[0], P.y * rec->scale + rec->offset[1], P.z * rec->scale + rec->offset[2]);
+        if (!reproject_rec_identity(*rec)) P = Pm;
+    }
     const vec3 v = P - V.hL;
     const float a = dot(v, V.hD);
     if (!(a > 0.0f)) return false;
@@ -197,9 +233,15 @@ PT_HD int32_t reproject_own(const int32_t *p) {
 // steps 1 to 5 for pixel idx (< width * height): the colour and the length it ends with.  The pixel's own colour is read before
 // anything is returned, so the caller may store into color[idx].  MOM: pt_ctx_reproject_var's moments too - *s_out is the
 // pixel's s = (r + g) + b of the input colour, *mom its (m1, m2).
-template <bool MOM>
+// MOVED (pt_ctx_reproject_moved): the object's record, read as soon as the id is known, decides - the marker ends at step 1,
+// IDENTITY runs the steps as they are, any other record maps the point and never takes step 2.  Under a still camera a wave then
+// holds one-tap and four-tap lanes: both go through the ONE four-tap gather, the one-tap lanes with their own pixel as tap 0
+// (b = 1) and three taps that are outside (never taken, so the sums are the one-tap sums bit for bit; they read the lane's own
+// history pixel again, a line it has in flight already).  No lane waits for another's second gather.  Without MOVED nothing of it
+// is compiled.
+template <bool MOM, bool MOVED = false>
 PT_HD void reproject_pixel_t(const ReprojectFrame &f, uint32_t idx, float out[3], float *len_out, const ReprojectMom *hist_moments,
-                             ReprojectMom *mom, float *s_out) {
+                             ReprojectMom *mom, float *s_out, const ReprojectMotion *motion = nullptr) {
     const size_t i3 = (size_t)idx * 3u;
     float col[3];
 #pragma unroll
@@ -214,6 +256,8 @@ PT_HD void reproject_pixel_t(const ReprojectFrame &f, uint32_t idx, float out[3]
     if (!f.hist_color) return;
     const int32_t id = reproject_own(f.object_id + idx);
     if (id < 0) return;
+    pt_object_motion rec = {{0.0f, 0.0f, 0.0f}, 1.0f};
+    if constexpr (MOVED) rec = reproject_rec(*motion, id);
     const float depth = reproject_own(f.depth + idx);
     const bool normals = f.normal && f.hist_normal;
     vec3 N = mk(0.0f, 0.0f, 0.0f);
@@ -221,34 +265,48 @@ PT_HD void reproject_pixel_t(const ReprojectFrame &f, uint32_t idx, float out[3]
         const float n[3] = {reproject_own(f.normal + i3), reproject_own(f.normal + i3 + 1), reproject_own(f.normal + i3 + 2)};
         N = reproject_normal(n);
     }
-    if (f.view.same) {
+    if constexpr (MOVED) {
+        if (reproject_rec_marker(rec)) return;
+    } else if (f.view.same) {
         const ReprojectTap tap[1] = {{idx, 1.0f, true}};
         reproject_gather<1, MOM>(f, tap, depth, id, normals, N, col, out, len_out, hist_moments, mom);
         return;
     }
-    ReprojectPos p;
-    if (!reproject_project(f.view, f.width, f.height, idx, depth, p)) return;
-    const float flx = __builtin_floorf(p.px), flr = __builtin_floorf(p.pr);
-    const int32_t x0 = (int32_t)flx, r0 = (int32_t)flr;  // in [-1, width - 1] and [-1, height - 1]
-    const float fx = p.px - flx, fr = p.pr - flr;
-    const int32_t xmax = (int32_t)f.width - 1, rmax = (int32_t)f.height - 1;
     ReprojectTap tap[4];
+    float zexp;
+    if (MOVED && f.view.same && reproject_rec_identity(rec)) {  // step 2 in the four-tap gather's shape
+        tap[0] = {idx, 1.0f, true};
 #pragma unroll
-    for (int32_t j = 0; j < 2; ++j) {
+        for (int t = 1; t < 4; ++t) tap[t] = {idx, 0.0f, false};
+        zexp = depth;
+    } else {
+        ReprojectPos p;
+        if (!reproject_project<MOVED>(f.view, f.width, f.height, idx, depth, p, &rec)) return;
+        const float flx = __builtin_floorf(p.px), flr = __builtin_floorf(p.pr);
+        const int32_t x0 = (int32_t)flx, r0 = (int32_t)flr;  // in [-1, width - 1] and [-1, height - 1]
+        const float fx = p.px - flx, fr = p.pr - flr;
+        const int32_t xmax = (int32_t)f.width - 1, rmax = (int32_t)f.height - 1;
 #pragma unroll
-        for (int32_t i = 0; i < 2; ++i) {
-            const int32_t qx = x0 + i, qr = r0 + j;
-            ReprojectTap &t = tap[j * 2 + i];
-            t.inside = qx >= 0 && qr >= 0 && qx <= xmax && qr <= rmax;
-            const int32_t cx = qx < 0 ? 0 : (qx > xmax ? xmax : qx), cr = qr < 0 ? 0 : (qr > rmax ? rmax : qr);
-            t.q = (uint32_t)cr * f.width + (uint32_t)cx;
-            t.b = (i ? fx : 1.0f - fx) * (j ? fr : 1.0f - fr);
+        for (int32_t j = 0; j < 2; ++j) {
+#pragma unroll
+            for (int32_t i = 0; i < 2; ++i) {
+                const int32_t qx = x0 + i, qr = r0 + j;
+                ReprojectTap &t = tap[j * 2 + i];
+                t.inside = qx >= 0 && qr >= 0 && qx <= xmax && qr <= rmax;
+                const int32_t cx = qx < 0 ? 0 : (qx > xmax ? xmax : qx), cr = qr < 0 ? 0 : (qr > rmax ? rmax : qr);
+                t.q = (uint32_t)cr * f.width + (uint32_t)cx;
+                t.b = (i ? fx : 1.0f - fx) * (j ? fr : 1.0f - fr);
+            }
         }
+        zexp = p.zexp;
     }
-    reproject_gather<4, MOM>(f, tap, p.zexp, id, normals, N, col, out, len_out, hist_moments, mom);
+    reproject_gather<4, MOM>(f, tap, zexp, id, normals, N, col, out, len_out, hist_moments, mom);
 }
 PT_HD void reproject_pixel(const ReprojectFrame &f, uint32_t idx, float out[3], float *len_out) {
     reproject_pixel_t<false>(f, idx, out, len_out, nullptr, nullptr, nullptr);
+}
+PT_HD void reproject_pixel_moved(const ReprojectFrame &f, const ReprojectMotion &m, uint32_t idx, float out[3], float *len_out) {
+    reproject_pixel_t<false, true>(f, idx, out, len_out, nullptr, nullptr, nullptr, &m);
 }
 
 // ---- pt_ctx_reproject_var: the variance and the error map ("THE ARITHMETIC" of pt_ctx_reproject_var in include/ptrace.h)
@@ -264,10 +322,11 @@ PT_HD float reproject_var_error(float v, float k, const float out[3]) {
 // Kernel A's pixel: pt_ctx_reproject's colour and length, the moments, the s plane, and d_error - final where the history is
 // long, kReprojectVarShort where the spatial estimate has to stand in.  Everything the pixel reads of planes it may share with
 // an output (its own colour) is read before the first store.
-PT_HD void reproject_var_pixel(const ReprojectVarFrame &v, uint32_t idx) {
+template <bool MOVED = false>
+PT_HD void reproject_var_pixel(const ReprojectVarFrame &v, uint32_t idx, const ReprojectMotion *motion = nullptr) {
     float out[3], len, s;
     ReprojectMom mom;
-    reproject_pixel_t<true>(v.f, idx, out, &len, v.hist_moments, &mom, &s);
+    reproject_pixel_t<true, MOVED>(v.f, idx, out, &len, v.hist_moments, &mom, &s, motion);
     float *o = v.f.out_color + (size_t)idx * 3u;
     o[0] = out[0];
     o[1] = out[1];
@@ -345,6 +404,24 @@ int check_reproject_var(const void *ctx, uint32_t width, uint32_t height, const 
                         const pt_camera *hist_cam, const float *d_hist_color, const float *d_hist_len, const float *d_hist_moments,
                         const float *d_hist_depth, const int32_t *d_hist_object_id, const float *d_hist_normal, float *d_out_color,
                         float *d_out_len, float *d_out_moments, float *d_error, ReprojectVarFrame &v);
+// How a pt_ctx_reproject*_moved call runs its table.  kMotionPlain: motion NULL, n_motion 0 or every record IDENTITY - the
+// plain launch, unchanged.  kMotionTable: the moved kernels.
+constexpr int kMotionPlain = 0, kMotionTable = 1;
+constexpr uint32_t kReprojectMaxMotion = 1u << 20;
+// the moved calls' own refusals, in the header's order, after the plain call's have passed (rc_plain is its verdict and is
+// returned when not PT_OK); PT_OK: *how is kMotionPlain or kMotionTable.  O(n_motion) on the host, no device.
+int check_reproject_motion(int rc_plain, const pt_object_motion *motion, uint32_t n_motion, int *how);
+int check_reproject_moved(const void *ctx, uint32_t width, uint32_t height, const pt_reproject_params *params, const pt_camera *cam,
+                          const float *d_color, const float *d_depth, const int32_t *d_object_id, const float *d_normal,
+                          const pt_camera *hist_cam, const float *d_hist_color, const float *d_hist_len, const float *d_hist_depth,
+                          const int32_t *d_hist_object_id, const float *d_hist_normal, float *d_out_color, float *d_out_len,
+                          const pt_object_motion *motion, uint32_t n_motion, ReprojectFrame &f, int *how);
+int check_reproject_var_moved(const void *ctx, uint32_t width, uint32_t height, const pt_reproject_var_params *params,
+                              const pt_camera *cam, const float *d_color, const float *d_depth, const int32_t *d_object_id,
+                              const float *d_normal, const pt_camera *hist_cam, const float *d_hist_color, const float *d_hist_len,
+                              const float *d_hist_moments, const float *d_hist_depth, const int32_t *d_hist_object_id,
+                              const float *d_hist_normal, float *d_out_color, float *d_out_len, float *d_out_moments, float *d_error,
+                              const pt_object_motion *motion, uint32_t n_motion, ReprojectVarFrame &v, int *how);
 }  // namespace host
 
 #if defined(__HIPCC__)
@@ -352,6 +429,9 @@ int check_reproject_var(const void *ctx, uint32_t width, uint32_t height, const 
 void launch_reproject(hipStream_t st, const ReprojectFrame &f);
 // kernel A, one lane per pixel, then kernel B, one workgroup per tile of 32 x 8
 void launch_reproject_var(hipStream_t st, const ReprojectVarFrame &v);
+// the same with the motion table (device memory, 16-byte aligned)
+void launch_reproject_moved(hipStream_t st, const ReprojectFrame &f, const ReprojectMotion &m);
+void launch_reproject_var_moved(hipStream_t st, const ReprojectVarFrame &v, const ReprojectMotion &m);
 #endif
 
 }  // namespace pt

@@ -91,14 +91,53 @@ __global__ __launch_bounds__(kRvTileW *kRvTileH) void k_reproject_var_spatial(co
     v.error[idx] = reproject_var_short_pixel(v, tile, idx);
 }
 
+// ---- pt_ctx_reproject_moved / pt_ctx_reproject_var_moved: the same two kernels with the per-object motion table
+// (reproject_pixel_t<MOM, true>).  The compulsory bytes are the plain kernels' plus the table's 16 B per object once: the record
+// is one 16-byte load by object id, issued as soon as the id is known and long before the taps' addresses are; a wave's lanes
+// mostly share an object, so it is one line of L1 or L2.  The table is a kernel argument of its own, so that ReprojectFrame,
+// and with it every plain kernel, stays what it is.
+__global__ __launch_bounds__(kReprojectBlock) void k_reproject_moved(const ReprojectFrame f, const ReprojectMotion m, uint32_t npix) {
+    const uint32_t idx = blockIdx.x * kReprojectBlock + threadIdx.x;
+    if (idx >= npix) return;
+    float out[3], len;
+    reproject_pixel_moved(f, m, idx, out, &len);
+    float *o = f.out_color + (size_t)idx * 3u;
+    o[0] = out[0];
+    o[1] = out[1];
+    o[2] = out[2];
+    f.out_len[idx] = len;
+}
+
+__global__ __launch_bounds__(kReprojectBlock) void k_reproject_var_moved(const ReprojectVarFrame v, const ReprojectMotion m, uint32_t npix) {
+    const uint32_t idx = blockIdx.x * kReprojectBlock + threadIdx.x;
+    if (idx >= npix) return;
+    reproject_var_pixel<true>(v, idx, &m);
+}
+
+void launch_var_spatial(hipStream_t st, const ReprojectVarFrame &v) {
+    // a grid of one dimension: a frame of one column and 2^28 rows is 2^25 tiles down, more than a grid's y takes
+    const uint32_t tiles_x = (v.f.width + kRvTileW - 1u) / kRvTileW, tiles_y = (v.f.height + kRvTileH - 1u) / kRvTileH;
+    hipLaunchKernelGGL(k_reproject_var_spatial, dim3(tiles_x * tiles_y), dim3(kRvTileW * kRvTileH), 0, st, v, tiles_x);
+}
+
 }  // namespace
+
+void launch_reproject_moved(hipStream_t st, const ReprojectFrame &f, const ReprojectMotion &m) {
+    const uint32_t npix = f.width * f.height;
+    hipLaunchKernelGGL(k_reproject_moved, dim3((npix + kReprojectBlock - 1u) / kReprojectBlock), dim3(kReprojectBlock), 0, st, f, m, npix);
+}
+
+void launch_reproject_var_moved(hipStream_t st, const ReprojectVarFrame &v, const ReprojectMotion &m) {
+    const uint32_t npix = v.f.width * v.f.height;
+    hipLaunchKernelGGL(k_reproject_var_moved, dim3((npix + kReprojectBlock - 1u) / kReprojectBlock), dim3(kReprojectBlock), 0, st, v, m,
+                       npix);
+    launch_var_spatial(st, v);  // the spatial estimate does not read the table
+}
 
 void launch_reproject_var(hipStream_t st, const ReprojectVarFrame &v) {
     const uint32_t npix = v.f.width * v.f.height;  // at most 2^28
     hipLaunchKernelGGL(k_reproject_var, dim3((npix + kReprojectBlock - 1u) / kReprojectBlock), dim3(kReprojectBlock), 0, st, v, npix);
-    // a grid of one dimension: a frame of one column and 2^28 rows is 2^25 tiles down, more than a grid's y takes
-    const uint32_t tiles_x = (v.f.width + kRvTileW - 1u) / kRvTileW, tiles_y = (v.f.height + kRvTileH - 1u) / kRvTileH;
-    hipLaunchKernelGGL(k_reproject_var_spatial, dim3(tiles_x * tiles_y), dim3(kRvTileW * kRvTileH), 0, st, v, tiles_x);
+    launch_var_spatial(st, v);
 }
 
 void launch_reproject(hipStream_t st, const ReprojectFrame &f) {

@@ -39,7 +39,7 @@ static void usage() {
             "              [--adaptive X [--tile N] [--spp-map FILE.pfm] [--error-map FILE.pfm] [--adaptive-checkpoint FILE]]\n"
             "              [--denoise-var [N]] [--preview FILE.ppm [--preview-size WxH] [--exposure E]]\n"
             "              [--trace-scale K [--retrace]]\n"
-            "              [--orbit N [--orbit-step DEG] [--move I:DX,DY,DZ]]\n"
+            "              [--orbit N [--orbit-step DEG] [--move I:DX,DY,DZ [--move-history [F]]]]\n"
             "  --checkpoint FILE: continue from the samples FILE holds (if it exists), render up to <samplesPerPixel> in all and\n"
             "                     save them to FILE; one GPU only; the seed defaults to 0 instead of the clock, so that the same\n"
             "                     command continues the same frame\n"
@@ -88,7 +88,12 @@ static void usage() {
             "           --denoise-var\n"
             "  --move I:DX,DY,DZ: with --orbit: in frame k object I stands at its position + k * (DX, DY, DZ), in binary32, set\n"
             "           through pt_ctx_set_object - no pt_ctx_set_scene per frame; a frame in which the object moved passes no\n"
-            "           history to the reprojection; the frame's stderr line adds what the edit took and whether it rebuilt\n");
+            "           history to the reprojection; the frame's stderr line adds what the edit took and whether it rebuilt\n"
+            "  --move-history [F]: with --move: a frame in which the object moved passes its history on after all, through\n"
+            "           pt_ctx_reproject_var_moved with the object's record (pt_object_motion_between of the object in frame k and in\n"
+            "           frame k-1); with F, max_history on such a frame is F frames' samples (F * <samplesPerPixel>), which bounds how\n"
+            "           long the light the object changed elsewhere stays; without F it stays pt_reproject_var_defaults' 64 samples,\n"
+            "           the pick of profiles/reproject_moved_cpu_study.json; not with --aov-chain\n");
 }
 
 static std::vector<std::string> scene_ids(const std::string &root) {
@@ -534,9 +539,12 @@ struct OrbitSide {
 
 // --orbit N: the viewport loop of INTEGRATION.md on one context on one GPU, the camera moved with pt_ctx_set_camera
 // --move I:DX,DY,DZ: object `index` stands at its position + k * d in frame k (index < 0: nothing moves)
+// --move-history [F]: carry: a move frame keeps its history, capped at `history` frames' samples (0: the library's default)
 struct OrbitMove {
     long index = -1;
     float d[3] = {0.0f, 0.0f, 0.0f};
+    bool carry = false;
+    float history = 0.0f;
 };
 
 static int render_orbit(const pt_config *cfg, pt_scene *sc, uint32_t frames, double step, const std::string &preview, uint32_t ow,
@@ -582,9 +590,11 @@ static int render_orbit(const pt_config *cfg, pt_scene *sc, uint32_t frames, dou
     pt_camera hist_cam = cam0;
     for (uint32_t k = 0; k < frames && !rc; ++k) {
         const pt_camera cam = orbit_camera(cam0, (double)k * step);
-        // a frame in which an object moved passes no history on: the reprojection follows the camera, not the objects
+        // a frame in which an object moved passes no history on: the reprojection follows the camera, not the objects - unless
+        // --move-history hands it the object's record
         const bool moves = mv.index >= 0 && k != 0u && (mv.d[0] != 0.0f || mv.d[1] != 0.0f || mv.d[2] != 0.0f);
-        const bool hh = k != 0u && !moves;
+        const bool carried = moves && mv.carry;
+        const bool hh = k != 0u && (!moves || carried);
         int rebuilt = 0, edit_rebuilt = 0;
         pt_stats st;
         const clk::time_point t0 = clk::now();
@@ -601,7 +611,20 @@ static int render_orbit(const pt_config *cfg, pt_scene *sc, uint32_t frames, dou
         pt_reproject_var_params rp;
         memset(&rp, 0, sizeof rp);
         rp.weight = cfg->spp;
-        if (!rc)
+        if (!rc && carried) {
+            pt_object now = objs[mv.index], before = objs[mv.index];
+            for (int a = 0; a < 3; ++a) {
+                now.position[a] = objs[mv.index].position[a] + (float)k * mv.d[a];
+                before.position[a] = objs[mv.index].position[a] + (float)(k - 1u) * mv.d[a];
+            }
+            std::vector<pt_object_motion> table(n_objs, pt_object_motion{{0.0f, 0.0f, 0.0f}, 1.0f});
+            rc = pt_object_motion_between(&now, &before, &table[mv.index]);
+            rp.max_history = mv.history * (float)cfg->spp;  // 0: the default
+            if (!rc)
+                rc = pt_ctx_reproject_var_moved(ctx, w, h, &rp, &cam, cur->color, cur->depth, cur->id, cur->normal, &hist_cam, hist->color,
+                                                hist->len, hist->moments, hist->depth, hist->id, hist->normal, cur->color, cur->len,
+                                                cur->moments, d_error, table.data(), n_objs, nullptr);
+        } else if (!rc)
             rc = pt_ctx_reproject_var(ctx, w, h, &rp, &cam, cur->color, cur->depth, cur->id, cur->normal, hh ? &hist_cam : nullptr,
                                       hh ? hist->color : nullptr, hh ? hist->len : nullptr, hh ? hist->moments : nullptr,
                                       hh ? hist->depth : nullptr, hh ? hist->id : nullptr, hh ? hist->normal : nullptr, cur->color,
@@ -796,6 +819,20 @@ int main(int argc, char **argv) {
                 return 1;
             }
         }
+        else if (a == "--move-history") {
+            orbit_move.carry = true;
+            // the optional F: taken when the next argument is a number
+            char *e = nullptr;
+            const float f = i + 1 < argc ? strtof(argv[i + 1], &e) : 0.0f;
+            if (i + 1 < argc && e != argv[i + 1] && !*e) {
+                ++i;
+                orbit_move.history = f;
+                if (!(f >= 1.0f) || !std::isfinite(f)) {
+                    fprintf(stderr, "--move-history takes F >= 1 frames, a finite number (or none: the library's max_history)\n");
+                    return 1;
+                }
+            }
+        }
         else if (a == "--orbit-step") {
             char *e = nullptr;
             const char *v = next();
@@ -846,6 +883,10 @@ int main(int argc, char **argv) {
     }
     if (orbit_move.index >= 0 && !orbit_frames) {
         fprintf(stderr, "--move goes with --orbit N\n");
+        return 1;
+    }
+    if (orbit_move.carry && (orbit_move.index < 0 || g_aov_chain)) {
+        fprintf(stderr, "--move-history goes with --move I:DX,DY,DZ and not with --aov-chain: it carries the moved object's history\n");
         return 1;
     }
     if (orbit_frames && preview.empty()) {

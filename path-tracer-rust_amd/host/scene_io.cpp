@@ -1249,6 +1249,64 @@ int pt_reproject_project_host(const pt_camera *cam, const pt_camera *hist_cam, u
     return PT_OK;
 }
 
+int pt_reproject_project_moved_host(const pt_camera *cam, const pt_camera *hist_cam, uint32_t width, uint32_t height, uint32_t idx,
+                                    float depth, const pt_object_motion *rec, float *px, float *pr, float *zexp) {
+    if (!cam || !hist_cam || !rec || !px || !pr || !zexp) {
+        pt::set_error("NULL argument");
+        return PT_ERR_INVALID;
+    }
+    if (width == 0 || height == 0 || (uint64_t)width * height > (1ull << 28) || idx >= (uint64_t)width * height) {
+        pt::set_error("an empty frame, one above 2^28 pixels, or idx outside it");
+        return PT_ERR_INVALID;
+    }
+    int how;
+    if (pt::reproject_rec_marker(*rec) || pt::host::check_reproject_motion(PT_OK, rec, 1u, &how)) {
+        pt::set_error("rec is the marker, or a record pt_ctx_reproject_moved refuses");
+        return PT_ERR_INVALID;
+    }
+    pt::ReprojectView v;
+    pt::host::reproject_view(*cam, hist_cam, v);
+    pt::ReprojectPos p;
+    if (!pt::reproject_project<true>(v, width, height, idx, depth, p, rec)) return 1;  // no position
+    *px = p.px;
+    *pr = p.pr;
+    *zexp = p.zexp;
+    return PT_OK;
+}
+
+// the record of one pt_ctx_set_object edit ("THE RECORD" in ptrace.h); every operation binary32, in the header's order
+int pt_object_motion_between(const pt_object *now, const pt_object *before, pt_object_motion *out) {
+    if (!now || !before || !out) {
+        pt::set_error("NULL argument");
+        return PT_ERR_INVALID;
+    }
+    const pt_object_motion marker = {{0.0f, 0.0f, 0.0f}, 0.0f};
+    *out = marker;
+    if (now->kind != before->kind || now->tri_offset != before->tri_offset || now->tri_count != before->tri_count) return PT_OK;
+    if (memcmp(now->color, before->color, sizeof now->color) || memcmp(now->emission, before->emission, sizeof now->emission) ||
+        now->reflect_type != before->reflect_type)
+        return PT_OK;
+    const bool sphere = now->kind == PT_SPHERE;
+    for (int a = 0; a < 3; ++a)
+        if (!std::isfinite(now->position[a]) || !std::isfinite(before->position[a])) return PT_OK;
+    float scale = 1.0f;
+    if (sphere) {
+        if (!std::isfinite(now->radius) || !std::isfinite(before->radius) || now->radius == 0.0f) return PT_OK;
+        scale = fabsf(before->radius) / fabsf(now->radius);
+    }
+    pt_object_motion r = {{0.0f, 0.0f, 0.0f}, scale};
+    for (int a = 0; a < 3; ++a) {
+        const float prod = sphere ? now->position[a] * scale : now->position[a];
+        const float o = before->position[a] - prod;
+        r.offset[a] = o == 0.0f ? 0.0f : o;  // -0 is stored as +0
+    }
+    if (!(r.scale > 0.0f) || !std::isfinite(r.scale) || !std::isfinite(r.offset[0]) || !std::isfinite(r.offset[1]) ||
+        !std::isfinite(r.offset[2]))
+        return PT_OK;  // the marker
+    *out = r;
+    return PT_OK;
+}
+
 int pt_upsample_tap_host(uint32_t size, uint32_t lo_size, uint32_t coord, int32_t *first, float *frac) {
     if (!first || !frac) {
         pt::set_error("NULL argument");
