@@ -1,17 +1,25 @@
 """Python binding of libptrace_hip.so (C ABI in include/ptrace.h) for bench.py, smoke() and the rank harness.
 
 Import with importlib.import_module("path-tracer-rust_amd").  This module is plumbing only: it loads the
-in-tree shared library (and fails loudly if it is missing — there is no Python or CPU fallback), mirrors the
-POD structs, and provides the band partition / framebuffer gather used when one process per GPU renders a
+in-tree shared library (and fails loudly if it is missing — there is no Python or CPU fallback), re-exports the
+structs and constants of abi.py, and provides the band partition / framebuffer gather used when one process per GPU renders a
 contiguous band of the reference's `pixels` vector (src/render/mod.rs:1017-1024: pixels are independent).
 """
 import ctypes as C
 import os
 
+from . import abi
+from .abi import (PT_AOV_MAX_CHAIN, PT_AOV_THROUGH_DELTA, PT_CANCELLED, PT_DENOISE_NO_DEMODULATE, PT_ERR_HIP, PT_ERR_INVALID,  # noqa: F401
+                  PT_ERR_IO, PT_ERR_NO_DEVICE, PT_ERR_PARSE, PT_FLAG_NO_BVH, PT_FLAG_SEPARATE_KERNELS, PT_OK,
+                  PT_PRESENT_FRAMEBUFFER_ORDER, PT_PRESENT_RGB8, PT_PRESENT_RGBA8, PT_SCATTER_BY_ID, PT_SCATTER_BY_RANK,
+                  PT_SCATTER_DEFER_REFRACT, PT_SCATTER_GIVEN, PT_SCATTER_NOT_SHADED, PT_SCATTER_REFRACT_ONLY, TABLE_NAMES, f3,
+                  pt_adaptive_info, pt_adaptive_params, pt_adaptive_stats, pt_aov_params, pt_camera, pt_config, pt_denoise_params,
+                  pt_denoise_var_params, pt_noise_stats, pt_noise_target, pt_object, pt_object_motion, pt_present_params,
+                  pt_reproject_params, pt_reproject_var_params, pt_scatter_item, pt_scatter_out, pt_scatter_surface,
+                  pt_select_params, pt_stats, pt_triangle, pt_upsample_params)
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PT_LIB") or os.path.join(_HERE, "libptrace_hip.so")  # PT_LIB: A/B builds when tuning
-
-f3 = C.c_float * 3
 
 
 class PtraceError(RuntimeError):
@@ -20,130 +28,7 @@ class PtraceError(RuntimeError):
         self.code = code
 
 
-class pt_camera(C.Structure):
-    _fields_ = [("position", f3), ("direction", f3), ("focal_length", C.c_float),
-                ("sensor_width", C.c_float), ("aspect_ratio", C.c_float)]
-
-
-class pt_triangle(C.Structure):
-    _fields_ = [("a", f3), ("b", f3), ("c", f3)]
-
-
-class pt_object(C.Structure):
-    _fields_ = [("kind", C.c_uint32), ("position", f3), ("radius", C.c_float), ("color", f3),
-                ("emission", f3), ("reflect_type", C.c_uint32), ("tri_offset", C.c_uint32),
-                ("tri_count", C.c_uint32), ("bs_center", f3), ("bs_radius", C.c_float)]
-
-
-class pt_config(C.Structure):
-    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("spp", C.c_uint32), ("backend", C.c_uint32),
-                ("seed", C.c_uint64), ("idx_begin", C.c_uint32), ("idx_end", C.c_uint32),
-                ("rays_per_pass", C.c_uint32), ("flags", C.c_uint32), ("chunk_pixels", C.c_uint32),
-                ("chunk_first", C.c_uint32), ("chunk_step", C.c_uint32), ("progress_ms", C.c_uint32)]
-
-
-class pt_stats(C.Structure):
-    _fields_ = [("ray_bounces", C.c_uint64), ("samples", C.c_uint64), ("intersect_rays", C.c_uint64),
-                ("intersect_launches", C.c_uint32), ("passes", C.c_uint32), ("ms_total", C.c_double),
-                ("ms_device", C.c_double), ("ms_intersect", C.c_double)]
-
-
-class pt_denoise_params(C.Structure):
-    _fields_ = [("levels", C.c_uint32), ("sigma_color", C.c_float), ("sigma_normal_pow", C.c_float),
-                ("sigma_depth", C.c_float), ("flags", C.c_uint32)]
-
-
-class pt_aov_params(C.Structure):
-    _fields_ = [("flags", C.c_uint32), ("max_chain", C.c_uint32)]
-
-
-class pt_denoise_var_params(C.Structure):
-    _fields_ = [("levels", C.c_uint32), ("sigma_var", C.c_float), ("sigma_depth", C.c_float), ("flags", C.c_uint32)]
-
-
-class pt_present_params(C.Structure):
-    _fields_ = [("out_width", C.c_uint32), ("out_height", C.c_uint32), ("exposure", C.c_float), ("format", C.c_uint32),
-                ("flags", C.c_uint32)]
-
-
-class pt_reproject_params(C.Structure):
-    _fields_ = [("weight", C.c_uint32), ("max_history", C.c_float), ("depth_tol", C.c_float), ("normal_min", C.c_float),
-                ("flags", C.c_uint32)]
-
-
-class pt_reproject_var_params(C.Structure):
-    _fields_ = [("weight", C.c_uint32), ("max_history", C.c_float), ("depth_tol", C.c_float), ("normal_min", C.c_float),
-                ("min_frames", C.c_uint32), ("radius", C.c_uint32), ("flags", C.c_uint32)]
-
-
-class pt_object_motion(C.Structure):
-    _fields_ = [("offset", C.c_float * 3), ("scale", C.c_float)]
-
-
-class pt_upsample_params(C.Structure):
-    _fields_ = [("depth_tol", C.c_float), ("normal_min", C.c_float), ("flags", C.c_uint32)]
-
-
-class pt_select_params(C.Structure):
-    _fields_ = [("weight_max", C.c_float), ("len_max", C.c_float), ("flags", C.c_uint32)]
-
-
-class pt_scatter_item(C.Structure):
-    _fields_ = [("o", C.c_float * 3), ("d", C.c_float * 3), ("thr", C.c_float * 3), ("pixel", C.c_uint32), ("sample", C.c_uint32),
-                ("depth", C.c_uint32), ("branch", C.c_uint32)]
-
-
-class pt_scatter_surface(C.Structure):
-    _fields_ = [("x", C.c_float * 3), ("n", C.c_float * 3), ("color", C.c_float * 3), ("emission", C.c_float * 3),
-                ("reflect", C.c_uint32)]
-
-
-class pt_scatter_out(C.Structure):
-    _fields_ = [("hit", C.c_int32), ("n_rays", C.c_uint32), ("emits", C.c_uint32), ("deferred", C.c_uint32),
-                ("x", C.c_float * 3), ("contrib", C.c_float * 3), ("d0", C.c_float * 3), ("thr0", C.c_float * 3),
-                ("d1", C.c_float * 3), ("thr1", C.c_float * 3), ("depth0", C.c_uint32), ("branch0", C.c_uint32),
-                ("depth1", C.c_uint32), ("branch1", C.c_uint32)]
-
-
-PT_SCATTER_GIVEN, PT_SCATTER_BY_ID, PT_SCATTER_BY_RANK = 0, 1, 2
-PT_SCATTER_DEFER_REFRACT, PT_SCATTER_REFRACT_ONLY = 0x10, 0x20
-PT_SCATTER_NOT_SHADED = -2
-
-
-class pt_noise_stats(C.Structure):
-    _fields_ = [("spp_min", C.c_uint32), ("spp_max", C.c_uint32), ("spp_a_min", C.c_uint32), ("spp_b_min", C.c_uint32),
-                ("pixels", C.c_uint64), ("mean_error", C.c_double), ("histogram", C.c_uint32 * 64)]
-
-
-class pt_noise_target(C.Structure):
-    _fields_ = [("mean_error", C.c_float), ("quantile", C.c_float), ("quantile_error", C.c_float), ("min_spp", C.c_uint32)]
-
-
-class pt_adaptive_params(C.Structure):
-    _fields_ = [("tile_error", C.c_float), ("tile", C.c_uint32), ("min_spp", C.c_uint32)]
-
-
-class pt_adaptive_stats(C.Structure):
-    _fields_ = [("tiles", C.c_uint32), ("tiles_open", C.c_uint32), ("levels", C.c_uint32), ("level_spp", C.c_uint32 * 32),
-                ("tiles_closed", C.c_uint32 * 32), ("samples", C.c_uint64), ("mean_error", C.c_double)]
-
-
-class pt_adaptive_info(C.Structure):
-    _fields_ = [("tiles", C.c_uint32), ("tiles_open", C.c_uint32), ("tiles_at_cap", C.c_uint32), ("spp_min", C.c_uint32),
-                ("spp_max", C.c_uint32), ("samples", C.c_uint64), ("mean_error", C.c_double)]
-
-
-# the device tables of a scene, by their PT_TABLE_* index (pt_ctx_table_hashes)
-TABLE_NAMES = ("objs", "obj_pairs", "tri_pairs", "mats", "tri_shade", "bvh_nodes", "bvh_nodes4", "sph_pairs", "flat_pairs", "cand_pairs",
-               "rank_id", "surf", "tri_rank", "bvh_meshes")
-PT_DENOISE_NO_DEMODULATE = 1
-PT_AOV_THROUGH_DELTA, PT_AOV_MAX_CHAIN = 1, 16
-PT_PRESENT_RGBA8, PT_PRESENT_RGB8 = 0, 1
-PT_PRESENT_FRAMEBUFFER_ORDER = 1
-PT_OK, PT_ERR_INVALID, PT_ERR_NO_DEVICE, PT_ERR_HIP, PT_CANCELLED = 0, -1, -2, -3, -4
-PT_ERR_IO, PT_ERR_PARSE = -6, -7
-BACKEND_WAVEFRONT, BACKEND_MEGAKERNEL = 0, 1
-PT_FLAG_NO_BVH, PT_FLAG_SEPARATE_KERNELS = 1, 2
+BACKEND_WAVEFRONT, BACKEND_MEGAKERNEL = abi.PT_BACKEND_WAVEFRONT, abi.PT_BACKEND_MEGAKERNEL
 BACKENDS = {"wavefront": BACKEND_WAVEFRONT, "megakernel": BACKEND_MEGAKERNEL}
 
 _lib = None
@@ -157,108 +42,8 @@ def lib():
     if not os.path.exists(LIB_PATH):
         raise ImportError("%s is missing: build it with `make -C %s` (hipcc, gfx950); there is no fallback path"
                           % (LIB_PATH, _HERE))
-    L = C.CDLL(LIB_PATH)
-    L.pt_version.restype = C.c_char_p
-    L.pt_build_flags.restype = C.c_char_p
-    L.pt_kernel_isa_hash.restype = C.c_char_p
-    L.pt_last_error.restype = C.c_char_p
-    L.pt_device_count.restype = C.c_int
-    L.pt_ctx_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
-    L.pt_ctx_destroy.argtypes = [C.c_void_p]
-    L.pt_ctx_destroy.restype = None
-    L.pt_ctx_set_scene.argtypes = [C.c_void_p, C.POINTER(pt_camera), C.POINTER(pt_object), C.c_uint32,
-                                   C.POINTER(pt_triangle), C.c_uint32]
-    L.pt_ctx_set_camera.argtypes = [C.c_void_p, C.POINTER(pt_camera), C.POINTER(C.c_int)]
-    L.pt_ctx_camera_reach.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
-    L.pt_ctx_reserve_camera_reach.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int)]
-    L.pt_ctx_set_object.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(pt_object), C.POINTER(C.c_int)]
-    L.pt_ctx_table_hashes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
-    L.pt_scene_reach.argtypes = [C.POINTER(pt_camera), C.POINTER(pt_object), C.c_uint32, C.POINTER(pt_triangle), C.c_uint32,
-                                 C.POINTER(C.c_float), C.POINTER(C.c_float)]
-    L.pt_ctx_render.argtypes = [C.c_void_p, C.POINTER(pt_config), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                C.c_void_p, C.POINTER(pt_stats)]
-    L.pt_ctx_accumulate.argtypes = L.pt_ctx_render.argtypes
-    L.pt_ctx_accum_info.argtypes = [C.c_void_p, C.POINTER(pt_config), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-    L.pt_ctx_accum_reset.argtypes = [C.c_void_p]
-    L.pt_ctx_accum_save.argtypes = [C.c_void_p, C.c_char_p]
-    L.pt_ctx_accum_load.argtypes = [C.c_void_p, C.c_char_p]
-    L.pt_ctx_accum_track_noise.argtypes = [C.c_void_p, C.c_int]
-    L.pt_ctx_accum_noise.argtypes = [C.c_void_p, C.POINTER(pt_config), C.c_void_p, C.POINTER(pt_noise_stats), C.c_void_p]
-    L.pt_ctx_accumulate_until.argtypes = [C.c_void_p, C.POINTER(pt_config), C.POINTER(pt_noise_target), C.c_void_p, C.c_void_p,
-                                          C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(pt_stats), C.POINTER(pt_noise_stats)]
-    L.pt_ctx_render_adaptive.argtypes = [C.c_void_p, C.POINTER(pt_config), C.POINTER(pt_adaptive_params), C.c_void_p, C.c_void_p,
-                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(pt_stats),
-                                         C.POINTER(pt_adaptive_stats)]
-    L.pt_ctx_accumulate_adaptive.argtypes = L.pt_ctx_render_adaptive.argtypes
-    L.pt_ctx_adaptive_info.argtypes = [C.c_void_p, C.POINTER(pt_config), C.POINTER(pt_adaptive_params), C.POINTER(pt_adaptive_info)]
-    L.pt_ctx_adaptive_resolve.argtypes = [C.c_void_p, C.POINTER(pt_config), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.pt_ctx_adaptive_reset.argtypes = [C.c_void_p]
-    L.pt_ctx_adaptive_save.argtypes = [C.c_void_p, C.c_char_p]
-    L.pt_ctx_adaptive_load.argtypes = [C.c_void_p, C.c_char_p]
-    L.pt_ctx_render_aov.argtypes = [C.c_void_p, C.POINTER(pt_config), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                    C.c_void_p]
-    L.pt_aov_defaults.argtypes = [C.POINTER(pt_aov_params)]
-    L.pt_ctx_render_aov_ex.argtypes = [C.c_void_p, C.POINTER(pt_config), C.POINTER(pt_aov_params), C.c_void_p, C.c_void_p,
-                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.pt_denoise_defaults.argtypes = [C.POINTER(pt_denoise_params)]
-    L.pt_ctx_denoise.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(pt_denoise_params), C.c_void_p, C.c_void_p,
-                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.pt_denoise_var_defaults.argtypes = [C.POINTER(pt_denoise_var_params)]
-    L.pt_ctx_denoise_var.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(pt_denoise_var_params), C.c_void_p,
-                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.pt_ctx_present.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(pt_present_params), C.c_void_p, C.c_void_p,
-                                 C.c_void_p]
-    L.pt_present_thresholds.argtypes = [C.POINTER(C.c_uint32)]
-    L.pt_present_quantize_host.argtypes = [C.POINTER(C.c_float), C.c_size_t, C.c_float, C.POINTER(C.c_uint8)]
-    L.pt_write_ppm8.argtypes = [C.c_char_p, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32]
-    L.pt_reproject_defaults.argtypes = [C.POINTER(pt_reproject_params)]
-    L.pt_ctx_reproject.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(pt_reproject_params), C.POINTER(pt_camera)] + \
-        [C.c_void_p] * 4 + [C.POINTER(pt_camera)] + [C.c_void_p] * 8
-    L.pt_reproject_var_defaults.argtypes = [C.POINTER(pt_reproject_var_params)]
-    L.pt_ctx_reproject_var.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(pt_reproject_var_params), C.POINTER(pt_camera)] + \
-        [C.c_void_p] * 4 + [C.POINTER(pt_camera)] + [C.c_void_p] * 11
-    L.pt_reproject_project_host.argtypes = [C.POINTER(pt_camera), C.POINTER(pt_camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_float] + \
-        [C.POINTER(C.c_float)] * 3
-    L.pt_object_motion_between.argtypes = [C.POINTER(pt_object), C.POINTER(pt_object), C.POINTER(pt_object_motion)]
-    L.pt_ctx_reproject_moved.argtypes = L.pt_ctx_reproject.argtypes[:-1] + [C.POINTER(pt_object_motion), C.c_uint32, C.c_void_p]
-    L.pt_ctx_reproject_var_moved.argtypes = L.pt_ctx_reproject_var.argtypes[:-1] + [C.POINTER(pt_object_motion), C.c_uint32, C.c_void_p]
-    L.pt_reproject_project_moved_host.argtypes = L.pt_reproject_project_host.argtypes[:6] + [C.POINTER(pt_object_motion)] + \
-        [C.POINTER(C.c_float)] * 3
-    L.pt_upsample_defaults.argtypes = [C.POINTER(pt_upsample_params)]
-    L.pt_ctx_upsample.argtypes = [C.c_void_p] + [C.c_uint32] * 4 + [C.POINTER(pt_upsample_params)] + [C.c_void_p] * 12
-    L.pt_upsample_tap_host.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_float)]
-    L.pt_ctx_select_pixels.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(pt_select_params), C.c_void_p, C.c_void_p,
-                                       C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p]
-    L.pt_ctx_render_masked.argtypes = [C.c_void_p, C.POINTER(pt_config), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                       C.POINTER(pt_stats), C.POINTER(C.c_uint32)]
-    L.pt_ctx_scatter.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(pt_scatter_item), C.POINTER(pt_scatter_surface),
-                                 C.c_uint32, C.POINTER(pt_scatter_out)]
-    L.pt_write_pfm.argtypes = [C.c_char_p, C.POINTER(C.c_float), C.c_uint32, C.c_uint32, C.c_uint32]
-    L.pt_ctx_set_profiling.argtypes = [C.c_void_p, C.c_int]
-    L.pt_ctx_pass_kernel.argtypes = [C.c_void_p, C.c_uint32]
-    L.pt_ctx_pass_kernel.restype = C.c_char_p
-    L.pt_scene_load.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p)]
-    L.pt_scene_free.argtypes = [C.c_void_p]
-    L.pt_scene_free.restype = None
-    L.pt_scene_id.argtypes = [C.c_void_p]
-    L.pt_scene_id.restype = C.c_char_p
-    L.pt_scene_camera.argtypes = [C.c_void_p]
-    L.pt_scene_camera.restype = C.POINTER(pt_camera)
-    L.pt_scene_objects.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
-    L.pt_scene_objects.restype = C.POINTER(pt_object)
-    L.pt_scene_triangles.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
-    L.pt_scene_triangles.restype = C.POINTER(pt_triangle)
-    L.pt_write_ppm.argtypes = [C.c_char_p, C.POINTER(C.c_float), C.c_uint32, C.c_uint32, C.c_uint32, C.c_char_p,
-                               C.c_uint64]
-    L.pt_image_hash.argtypes = [C.POINTER(C.c_float), C.c_size_t]
-    L.pt_image_hash.restype = C.c_uint64
-    L.pt_comm_unique_id.argtypes = [C.c_char_p]
-    L.pt_comm_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_void_p)]
-    L.pt_comm_destroy.argtypes = [C.c_void_p]
-    L.pt_comm_destroy.restype = None
-    L.pt_comm_gather_frame.argtypes = [C.c_void_p, C.POINTER(pt_config), C.c_void_p, C.c_void_p, C.c_void_p]
-    _lib = L
-    return L
+    _lib = abi.load(LIB_PATH)
+    return _lib
 
 
 def _check(rc):

@@ -16,9 +16,9 @@ import ptlib
 from test_gpu_aov import oracle_rays, resolve, to_fixed, to_fixed_signed
 
 F32 = np.float32
-MAX_CHAIN = 16  # PT_AOV_MAX_CHAIN
+MAX_CHAIN = ptlib.abi.PT_AOV_MAX_CHAIN
 DEFAULT_CHAIN = 8
-DIFFUSE = 0
+DIFFUSE = ptlib.abi.PT_DIFFUSE
 _NO_DRAWS = (F32(0), F32(0), F32(0))  # depth 0: no roulette, both subtrees - scatter() reads none of them
 MISS, SURFACE, CAP = 0, 1, 2  # how a chain ends: no hit, a diffuse surface, a delta surface after max_chain steps
 

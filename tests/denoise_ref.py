@@ -7,29 +7,18 @@ import ctypes as C
 
 import numpy as np
 
+from ptlib import abi, PtDenoiseParams
+
 F32 = np.float32
-NO_DEMODULATE = 1
+NO_DEMODULATE = abi.PT_DENOISE_NO_DEMODULATE
 B = (F32(0.375), F32(0.25), F32(0.0625))
 ZERO, ONE, EIGHTH = F32(0.0), F32(1.0), F32(0.125)
-
-
-class PtDenoiseParams(C.Structure):
-    _fields_ = [("levels", C.c_uint32), ("sigma_color", C.c_float), ("sigma_normal_pow", C.c_float),
-                ("sigma_depth", C.c_float), ("flags", C.c_uint32)]
-
-
-def bind(L):
-    """argtypes of the two entry points on a loaded libptrace_hip"""
-    L.pt_denoise_defaults.argtypes = [C.POINTER(PtDenoiseParams)]
-    L.pt_ctx_denoise.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(PtDenoiseParams), C.c_void_p, C.c_void_p,
-                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    return L
 
 
 def defaults(L):
     """(levels, sigma_color, sigma_depth) as pt_denoise_defaults reports them"""
     p = PtDenoiseParams()
-    assert bind(L).pt_denoise_defaults(C.byref(p)) == 0
+    assert L.pt_denoise_defaults(C.byref(p)) == 0
     return p.levels, p.sigma_color, p.sigma_depth
 
 

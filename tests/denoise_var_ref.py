@@ -7,28 +7,17 @@ import ctypes as C
 import numpy as np
 
 from denoise_ref import B, F32, NO_DEMODULATE, ONE, ZERO, fall, pos, prepare  # noqa: F401
+from ptlib import PtDenoiseVarParams
 
 G = (F32(0.5), F32(0.25))
 EV_MAX = F32(12.0)
 EPS = F32(2.0 ** -20)
 
 
-class PtDenoiseVarParams(C.Structure):
-    _fields_ = [("levels", C.c_uint32), ("sigma_var", C.c_float), ("sigma_depth", C.c_float), ("flags", C.c_uint32)]
-
-
-def bind(L):
-    """argtypes of the two entry points on a loaded libptrace_hip"""
-    L.pt_denoise_var_defaults.argtypes = [C.POINTER(PtDenoiseVarParams)]
-    L.pt_ctx_denoise_var.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(PtDenoiseVarParams), C.c_void_p,
-                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    return L
-
-
 def defaults(L):
     """(levels, sigma_var, sigma_depth) as pt_denoise_var_defaults reports them"""
     p = PtDenoiseVarParams()
-    assert bind(L).pt_denoise_var_defaults(C.byref(p)) == 0
+    assert L.pt_denoise_var_defaults(C.byref(p)) == 0
     return p.levels, p.sigma_var, p.sigma_depth
 
 

@@ -1,28 +1,13 @@
 """pt_ctx_select_pixels' predicate (include/ptrace.h, "THE PREDICATE") in numpy binary32, the ctypes declarations of it and of
 pt_ctx_render_masked, and the planes the tests feed it.  Shared by tests/test_masked_abi.py and tests/test_gpu_masked.py."""
-import ctypes as C
 
 import numpy as np
 
-from ptlib import PtConfig, PtStats
 
 F32 = np.float32
 U8 = np.uint8
 SIZES = ((1, 1), (7, 5), (257, 3), (64, 1))
 PARAMS = dict(weight_max=0.0, len_max=8.0)  # what the loop passes: the fallback's weight, one frame of 8 samples
-
-
-class PtSelectParams(C.Structure):
-    _fields_ = [("weight_max", C.c_float), ("len_max", C.c_float), ("flags", C.c_uint32)]
-
-
-def bind(L):
-    L.pt_ctx_select_pixels.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(PtSelectParams), C.c_void_p, C.c_void_p,
-                                       C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p]
-    L.pt_ctx_render_masked.argtypes = [C.c_void_p, C.POINTER(PtConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                       C.POINTER(PtStats), C.POINTER(C.c_uint32)]
-    L.pt_last_error.restype = C.c_char_p
-    return L
 
 
 def select(weight=None, length=None, weight_max=0.0, len_max=0.0):

@@ -1,29 +1,15 @@
 """pt_ctx_present restated: the contract of include/ptrace.h ("THE ARITHMETIC" of pt_ctx_present) with Python integers for S and
-numpy.float32 / float64 for the conversions.  The table is an argument (pt_present_thresholds gives the library's).  Also the
-ctypes prototypes of the four entry points, which the tests of pt_ctx_present bind for themselves."""
+numpy.float32 / float64 for the conversions.  The table is an argument (pt_present_thresholds gives the library's)."""
 import ctypes as C
 
 import numpy as np
 
+from ptlib import abi
+
 F32 = np.float32
-RGBA8, RGB8 = 0, 1
-FRAMEBUFFER_ORDER = 1
+RGBA8, RGB8 = abi.PT_PRESENT_RGBA8, abi.PT_PRESENT_RGB8
+FRAMEBUFFER_ORDER = abi.PT_PRESENT_FRAMEBUFFER_ORDER
 ONE_BITS = 0x3F800000
-
-
-class PtPresentParams(C.Structure):
-    _fields_ = [("out_width", C.c_uint32), ("out_height", C.c_uint32), ("exposure", C.c_float), ("format", C.c_uint32),
-                ("flags", C.c_uint32)]
-
-
-def bind(L):
-    L.pt_ctx_present.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(PtPresentParams), C.c_void_p, C.c_void_p,
-                                 C.c_void_p]
-    L.pt_present_thresholds.argtypes = [C.POINTER(C.c_uint32)]
-    L.pt_present_quantize_host.argtypes = [C.c_void_p, C.c_size_t, C.c_float, C.c_void_p]
-    L.pt_write_ppm8.argtypes = [C.c_char_p, C.c_void_p, C.c_uint32, C.c_uint32]
-    L.pt_last_error.restype = C.c_char_p
-    return L
 
 
 def thresholds(L):

@@ -5,9 +5,11 @@ The scene loader in this file is an independent Python reading of the reference'
 product's C++ loader; it is test code only.
 """
 import ctypes as C
+import importlib
 import json
 import os
 import subprocess
+import sys
 
 import numpy as np
 
@@ -16,35 +18,20 @@ PKG = os.path.join(ROOT, "path-tracer-rust_amd")
 ORACLE_SO = os.path.join(ROOT, "oracle", "libpt_oracle.so")
 PRODUCT_SO = os.path.join(PKG, "libptrace_hip.so")
 
-f3 = C.c_float * 3
+if ROOT not in sys.path:  # the tools import this module without the tests' conftest
+    sys.path.insert(0, ROOT)
+abi = importlib.import_module("path-tracer-rust_amd.abi")  # include/ptrace.h as ctypes: structs, constants, signatures
 
-
-class PtCamera(C.Structure):
-    _fields_ = [("position", f3), ("direction", f3), ("focal_length", C.c_float),
-                ("sensor_width", C.c_float), ("aspect_ratio", C.c_float)]
-
-
-class PtTriangle(C.Structure):
-    _fields_ = [("a", f3), ("b", f3), ("c", f3)]
-
-
-class PtObject(C.Structure):
-    _fields_ = [("kind", C.c_uint32), ("position", f3), ("radius", C.c_float), ("color", f3),
-                ("emission", f3), ("reflect_type", C.c_uint32), ("tri_offset", C.c_uint32),
-                ("tri_count", C.c_uint32), ("bs_center", f3), ("bs_radius", C.c_float)]
-
-
-class PtConfig(C.Structure):
-    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("spp", C.c_uint32), ("backend", C.c_uint32),
-                ("seed", C.c_uint64), ("idx_begin", C.c_uint32), ("idx_end", C.c_uint32),
-                ("rays_per_pass", C.c_uint32), ("flags", C.c_uint32), ("chunk_pixels", C.c_uint32),
-                ("chunk_first", C.c_uint32), ("chunk_step", C.c_uint32), ("progress_ms", C.c_uint32)]
-
-
-class PtStats(C.Structure):
-    _fields_ = [("ray_bounces", C.c_uint64), ("samples", C.c_uint64), ("intersect_rays", C.c_uint64),
-                ("intersect_launches", C.c_uint32), ("passes", C.c_uint32), ("ms_total", C.c_double),
-                ("ms_device", C.c_double), ("ms_intersect", C.c_double)]
+f3 = abi.f3
+# the names the tests use for the structs of ptrace.h (this is the only file that holds such aliases)
+PtCamera, PtTriangle, PtObject, PtConfig, PtStats = abi.pt_camera, abi.pt_triangle, abi.pt_object, abi.pt_config, abi.pt_stats
+PtScatterItem, PtScatterSurface, PtScatterOut = abi.pt_scatter_item, abi.pt_scatter_surface, abi.pt_scatter_out
+PtNoiseStats, PtNoiseTarget = abi.pt_noise_stats, abi.pt_noise_target
+PtAdaptiveParams, PtAdaptiveStats, PtAdaptiveInfo = abi.pt_adaptive_params, abi.pt_adaptive_stats, abi.pt_adaptive_info
+PtAovParams, PtDenoiseParams, PtDenoiseVarParams = abi.pt_aov_params, abi.pt_denoise_params, abi.pt_denoise_var_params
+PtPresentParams, PtUpsampleParams, PtSelectParams = abi.pt_present_params, abi.pt_upsample_params, abi.pt_select_params
+PtReprojectParams, PtReprojectVarParams = abi.pt_reproject_params, abi.pt_reproject_var_params
+PtObjectMotion = abi.pt_object_motion
 
 
 class PtoScene(C.Structure):
@@ -62,12 +49,12 @@ class PtoCounters(C.Structure):
                 ("sphere_tests", C.c_uint64), ("triangle_tests", C.c_uint64)]
 
 
-PT_SPHERE, PT_MESH = 0, 1
-REFLECT = {"Diffuse": 0, "Specular": 1, "Refract": 2}
-BACKEND_WAVEFRONT, BACKEND_MEGAKERNEL = 0, 1
-FLAG_NO_BVH = 1
-PROGRESS_EVERY_PASS = 0xffffffff
-PT_CANCELLED = -4
+PT_SPHERE, PT_MESH = abi.PT_SPHERE, abi.PT_MESH
+REFLECT = {"Diffuse": abi.PT_DIFFUSE, "Specular": abi.PT_SPECULAR, "Refract": abi.PT_REFRACT}
+BACKEND_WAVEFRONT, BACKEND_MEGAKERNEL = abi.PT_BACKEND_WAVEFRONT, abi.PT_BACKEND_MEGAKERNEL
+FLAG_NO_BVH = abi.PT_FLAG_NO_BVH
+PROGRESS_EVERY_PASS = abi.PT_PROGRESS_EVERY_PASS
+PT_CANCELLED = abi.PT_CANCELLED
 
 fp = C.POINTER(C.c_float)
 i32p = C.POINTER(C.c_int32)
@@ -148,98 +135,19 @@ def oracle():
     return L
 
 
-PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_float)
+PROGRESS_FN = abi.pt_progress_fn
 
 _product = None
 
 
 def product():
-    """Load libptrace_hip.so (the product).  Never falls back to anything."""
+    """Load libptrace_hip.so (the product) with every prototype of ptrace.h declared.  Never falls back to anything."""
     global _product
-    if _product is not None:
-        return _product
-    if not os.path.exists(PRODUCT_SO):
-        raise RuntimeError("libptrace_hip.so is not built: run `python -c 'import __graft_entry__ as g; g.build()'`")
-    L = C.CDLL(PRODUCT_SO)
-    L.pt_version.restype = C.c_char_p
-    L.pt_last_error.restype = C.c_char_p
-    L.pt_abi_version.restype = C.c_int
-    L.pt_device_count.restype = C.c_int
-    L.pt_camera_basis.argtypes = [C.POINTER(PtCamera), fp, fp, fp]
-    L.pt_mesh_bounding_sphere.argtypes = [C.POINTER(PtTriangle), C.c_uint32, fp, fp]
-    L.pt_config_pixels.argtypes = [C.POINTER(PtConfig)]
-    L.pt_config_pixels.restype = C.c_uint32
-    L.pt_ctx_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
-    L.pt_ctx_destroy.argtypes = [C.c_void_p]
-    L.pt_ctx_destroy.restype = None
-    L.pt_ctx_set_scene.argtypes = [C.c_void_p, C.POINTER(PtCamera), C.POINTER(PtObject), C.c_uint32,
-                                   C.POINTER(PtTriangle), C.c_uint32]
-    L.pt_ctx_render.argtypes = [C.c_void_p, C.POINTER(PtConfig), C.c_void_p, C.c_void_p, C.c_void_p,
-                                C.c_void_p, C.c_void_p, C.POINTER(PtStats)]
-    L.pt_ctx_set_profiling.argtypes = [C.c_void_p, C.c_int]
-    L.pt_ctx_set_memory_budget.argtypes = [C.c_void_p, C.c_size_t]
-    L.pt_ctx_pass_kernel.argtypes = [C.c_void_p, C.c_uint32]
-    L.pt_ctx_pass_kernel.restype = C.c_char_p
-    L.pt_render_multi.argtypes = [C.POINTER(PtConfig), C.c_uint32, C.POINTER(PtCamera), C.POINTER(PtObject), C.c_uint32,
-                                  C.POINTER(PtTriangle), C.c_uint32, fp, C.c_void_p, C.c_void_p, C.c_void_p,
-                                  C.POINTER(PtStats)]
-    L.pt_ctx_snapshot.argtypes = [C.c_void_p, C.c_void_p, u32p]
-    L.pt_device_malloc.argtypes = [C.c_int, C.c_size_t, C.POINTER(C.c_void_p)]
-    L.pt_device_free.argtypes = [C.c_int, C.c_void_p]
-    L.pt_device_download.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
-    L.pt_image_hash.argtypes = [fp, C.c_size_t]
-    L.pt_image_hash.restype = C.c_uint64
-    L.pt_siphash.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_char_p, C.c_size_t]
-    L.pt_siphash.restype = C.c_uint64
-    L.pt_host_sincos.argtypes = [C.c_float, fp, fp]
-    L.pt_host_sincos.restype = None
-    L.pt_ctx_numerics_probe.argtypes = [C.c_void_p, fp, C.c_uint32, fp, fp, fp, fp, u32p]
-    L.pt_ctx_radiance.argtypes = [C.c_void_p, fp, fp, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32,
-                                  fp, C.POINTER(PtStats)]
-    L.pt_ctx_numerics_sweep.argtypes = [C.c_void_p, u64p]
-    L.pt_ctx_sincos_sweep.argtypes = [C.c_void_p, u64p]
-    L.pt_ctx_primary_rays.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, u32p, u32p, C.c_uint32, C.c_uint32, fp, fp]
-    L.pt_ctx_intersect_streams.argtypes = [C.c_void_p, fp, fp, C.c_uint32, C.c_uint32, fp, i32p]
-    L.pt_ctx_intersect.argtypes = [C.c_void_p, fp, fp, C.c_uint32, fp, i32p, i32p, fp, fp]
-    L.pt_ctx_intersect_bounds.argtypes = [C.c_void_p, C.c_uint32, fp, fp, C.c_uint32, i32p, fp, fp, fp]
-    L.pt_ctx_orbit_point.argtypes = [C.c_void_p, fp, fp, C.c_uint32, i32p, fp, i32p, fp]
-    L.pt_ctx_set_mesh_bounds.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(PtTriangle)]
-    L.pt_mesh_bounding_box.argtypes = [C.POINTER(PtTriangle), C.c_uint32, C.POINTER(PtTriangle)]
-    L.pt_scene_bounding_box.argtypes = [C.c_void_p, C.c_uint32]
-    L.pt_scene_bounding_box.restype = C.POINTER(PtTriangle)
-    L.pt_comm_unique_id.argtypes = [C.c_char_p]
-    L.pt_comm_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_void_p)]
-    L.pt_comm_destroy.argtypes = [C.c_void_p]
-    L.pt_comm_destroy.restype = None
-    L.pt_comm_gather_frame.argtypes = [C.c_void_p, C.POINTER(PtConfig), C.c_void_p, C.c_void_p, C.c_void_p]
-    L.pt_render.argtypes = [C.POINTER(PtConfig), C.POINTER(PtCamera), C.POINTER(PtObject), C.c_uint32,
-                            C.POINTER(PtTriangle), C.c_uint32, fp, C.c_void_p, C.c_void_p, C.c_void_p,
-                            C.POINTER(PtStats)]
-    L.pt_scene_load.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p)]
-    L.pt_scene_load_ex.argtypes = [C.c_char_p, C.c_char_p, C.c_uint32, C.POINTER(C.c_void_p)]
-    L.pt_load_off_ex.argtypes = [C.c_char_p, C.c_float, C.c_uint32, C.POINTER(C.POINTER(PtTriangle)), u32p]
-    L.pt_scene_free.argtypes = [C.c_void_p]
-    L.pt_scene_free.restype = None
-    L.pt_scene_save.argtypes = [C.c_void_p, C.c_char_p]
-    L.pt_scene_set_camera.argtypes = [C.c_void_p, C.POINTER(PtCamera)]
-    L.pt_scene_id.argtypes = [C.c_void_p]
-    L.pt_scene_id.restype = C.c_char_p
-    L.pt_scene_camera.argtypes = [C.c_void_p]
-    L.pt_scene_camera.restype = C.POINTER(PtCamera)
-    L.pt_scene_objects.argtypes = [C.c_void_p, u32p]
-    L.pt_scene_objects.restype = C.POINTER(PtObject)
-    L.pt_scene_triangles.argtypes = [C.c_void_p, u32p]
-    L.pt_scene_triangles.restype = C.POINTER(PtTriangle)
-    L.pt_load_off.argtypes = [C.c_char_p, C.c_float, C.POINTER(C.POINTER(PtTriangle)), u32p]
-    L.pt_free.argtypes = [C.c_void_p]
-    L.pt_free.restype = None
-    L.pt_gamma_correction.argtypes = [C.c_float]
-    L.pt_gamma_correction.restype = C.c_float
-    L.pt_to_int_with_gamma_correction.argtypes = [C.c_float]
-    L.pt_to_int_with_gamma_correction.restype = C.c_uint32
-    L.pt_write_ppm.argtypes = [C.c_char_p, fp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_char_p, C.c_uint64]
-    _product = L
-    return L
+    if _product is None:
+        if not os.path.exists(PRODUCT_SO):
+            raise RuntimeError("libptrace_hip.so is not built: run `python -c 'import __graft_entry__ as g; g.build()'`")
+        _product = abi.load(PRODUCT_SO)
+    return _product
 
 
 # ---------------------------------------------------------------------------- python scene reader

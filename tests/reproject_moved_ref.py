@@ -2,39 +2,21 @@
 object edits") in numpy binary32.  It stands on tests/reproject_ref.py and tests/reproject_var_ref.py for everything that is
 unchanged - the projection's camera half, the taps, their tests, the blend, the moments, the spatial estimate - and states only
 what is new: the record lookup, the map Pm[a] = P[a]*scale + offset[a], the rule that a moved pixel never takes step 2, and,
-independently of host/scene_io.cpp, pt_object_motion_between.  Nothing is shared with csrc/pt_reproject.h.  Also the ctypes
-prototypes of the entry points, which the tests bind for themselves."""
+independently of host/scene_io.cpp, pt_object_motion_between.  Nothing is shared with csrc/pt_reproject.h."""
 import contextlib
-import ctypes as C
 
 import numpy as np
 
 import ptlib
+from ptlib import PtObjectMotion
 import reproject_ref as ref
 import reproject_var_ref as vref
 from reproject_ref import F32, I32
-from reproject_var_ref import PtReprojectVarParams
 
 IDENTITY = (0.0, 0.0, 0.0, 1.0)   # offset, scale
 MARKER = (0.0, 0.0, 0.0, 0.0)
 MAX_MOTION = 1 << 20
-PT_SPHERE, PT_MESH = 0, 1
-
-
-class PtObjectMotion(C.Structure):
-    _fields_ = [("offset", C.c_float * 3), ("scale", C.c_float)]
-
-
-def bind(L):
-    vref.bind(L)
-    cam = C.POINTER(ptlib.PtCamera)
-    mot = C.POINTER(PtObjectMotion)
-    L.pt_object_motion_between.argtypes = [C.POINTER(ptlib.PtObject), C.POINTER(ptlib.PtObject), mot]
-    L.pt_ctx_reproject_moved.argtypes = L.pt_ctx_reproject.argtypes[:-1] + [mot, C.c_uint32, C.c_void_p]
-    L.pt_ctx_reproject_var_moved.argtypes = L.pt_ctx_reproject_var.argtypes[:-1] + [mot, C.c_uint32, C.c_void_p]
-    L.pt_reproject_project_moved_host.argtypes = [cam, cam, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, mot, ptlib.fp, ptlib.fp,
-                                                  ptlib.fp]
-    return L
+PT_SPHERE, PT_MESH = ptlib.abi.PT_SPHERE, ptlib.abi.PT_MESH
 
 
 def table(records):

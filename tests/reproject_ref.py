@@ -1,30 +1,15 @@
 """pt_ctx_reproject restated: the contract of include/ptrace.h ("THE ARITHMETIC" of pt_ctx_reproject) in numpy binary32, one numpy
 operation per operation of the contract, over whole frames at once.  Nothing is shared with csrc/pt_reproject.h.  Cameras are the
-dicts of tests/kats_camera.py.  Also the ctypes prototypes of the entry points, which the tests bind for themselves."""
+dicts of tests/kats_camera.py."""
 import ctypes as C
 
 import numpy as np
 
 import ptlib
+from ptlib import PtReprojectParams
 
 F32 = np.float32
 I32 = np.int32
-
-
-class PtReprojectParams(C.Structure):
-    _fields_ = [("weight", C.c_uint32), ("max_history", C.c_float), ("depth_tol", C.c_float), ("normal_min", C.c_float),
-                ("flags", C.c_uint32)]
-
-
-def bind(L):
-    cam = C.POINTER(ptlib.PtCamera)
-    L.pt_reproject_defaults.argtypes = [C.POINTER(PtReprojectParams)]
-    L.pt_ctx_reproject.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(PtReprojectParams), cam, C.c_void_p, C.c_void_p,
-                                   C.c_void_p, C.c_void_p, cam, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                   C.c_void_p, C.c_void_p, C.c_void_p]
-    L.pt_reproject_project_host.argtypes = [cam, cam, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, ptlib.fp, ptlib.fp, ptlib.fp]
-    L.pt_last_error.restype = C.c_char_p
-    return L
 
 
 def defaults(L):

@@ -2,32 +2,17 @@
 one numpy operation per operation of the contract, over whole frames at once.  It stands on tests/reproject_ref.py: the colour
 and the length are its reproject(), and the moments are its reproject() again, applied to the pair (s, s*s) in place of the
 colour and to the history moments in place of the history colour - "the colour's blend applied to the pair", with the same taps
-and the same b because the guides are the same.  Nothing is shared with csrc/pt_reproject.h.  Also the ctypes prototypes of the
-entry points, which the tests bind for themselves."""
+and the same b because the guides are the same.  Nothing is shared with csrc/pt_reproject.h."""
 import ctypes as C
 
 import numpy as np
 
-import ptlib
+from ptlib import PtReprojectVarParams
 import reproject_ref as ref
 from reproject_ref import F32, I32
 
 E_MAX = F32(12.0)
 MAX_RADIUS = 3
-
-
-class PtReprojectVarParams(C.Structure):
-    _fields_ = [("weight", C.c_uint32), ("max_history", C.c_float), ("depth_tol", C.c_float), ("normal_min", C.c_float),
-                ("min_frames", C.c_uint32), ("radius", C.c_uint32), ("flags", C.c_uint32)]
-
-
-def bind(L):
-    ref.bind(L)
-    cam = C.POINTER(ptlib.PtCamera)
-    L.pt_reproject_var_defaults.argtypes = [C.POINTER(PtReprojectVarParams)]
-    L.pt_ctx_reproject_var.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(PtReprojectVarParams), cam] + \
-        [C.c_void_p] * 4 + [cam] + [C.c_void_p] * 6 + [C.c_void_p] * 4 + [C.c_void_p]
-    return L
 
 
 def defaults(L):

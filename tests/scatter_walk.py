@@ -9,6 +9,7 @@ import functools
 import numpy as np
 
 import ptlib
+from ptlib import PtScatterItem, PtScatterSurface
 
 SEED = 11
 FRAMES = [("cornell", 16, 12, 8), ("three-spheres", 16, 12, 8), ("mesh", 12, 8, 4)]
@@ -92,29 +93,8 @@ def kinds(W):
 
 
 # ---- pt_ctx_scatter at the ABI (include/ptrace.h): the structs, the binding, arrays from cases and walks -----------------------
-GIVEN, BY_ID, BY_RANK, DEFER_REFRACT, REFRACT_ONLY, NOT_SHADED = 0, 1, 2, 0x10, 0x20, -2
+GIVEN, BY_ID, BY_RANK, DEFER_REFRACT, REFRACT_ONLY, NOT_SHADED = ptlib.abi.PT_SCATTER_GIVEN, ptlib.abi.PT_SCATTER_BY_ID, ptlib.abi.PT_SCATTER_BY_RANK, ptlib.abi.PT_SCATTER_DEFER_REFRACT, ptlib.abi.PT_SCATTER_REFRACT_ONLY, ptlib.abi.PT_SCATTER_NOT_SHADED
 f3 = C.c_float * 3
-
-
-class PtScatterItem(C.Structure):
-    _fields_ = [("o", f3), ("d", f3), ("thr", f3), ("pixel", C.c_uint32), ("sample", C.c_uint32), ("depth", C.c_uint32),
-                ("branch", C.c_uint32)]
-
-
-class PtScatterSurface(C.Structure):
-    _fields_ = [("x", f3), ("n", f3), ("color", f3), ("emission", f3), ("reflect", C.c_uint32)]
-
-
-class PtScatterOut(C.Structure):
-    _fields_ = [("hit", C.c_int32), ("n_rays", C.c_uint32), ("emits", C.c_uint32), ("deferred", C.c_uint32), ("x", f3),
-                ("contrib", f3), ("d0", f3), ("thr0", f3), ("d1", f3), ("thr1", f3), ("depth0", C.c_uint32), ("branch0", C.c_uint32),
-                ("depth1", C.c_uint32), ("branch1", C.c_uint32)]
-
-
-def bind(L):
-    L.pt_ctx_scatter.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(PtScatterItem), C.POINTER(PtScatterSurface),
-                                 C.c_uint32, C.POINTER(PtScatterOut)]
-    return L
 
 
 def _f3(v):

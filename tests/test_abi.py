@@ -1,9 +1,13 @@
 """No-GPU checks of the boundary: the C-ABI library loads, exports every symbol include/ptrace.h declares,
 and its host-only entry points (camera basis, Mesh::new bounds, gamma, PPM bytes) agree with the oracle.
-No compute entry point is called with real work here."""
+No compute entry point is called with real work here.  Also: abi.py, the one description of the header in Python,
+against the header's text (names, prototypes), against the C compiler (layouts, constants), and alone in the tree."""
+import ast
 import ctypes as C
+import glob
 import os
 import re
+import subprocess
 
 import numpy as np
 import pytest
@@ -11,6 +15,7 @@ import pytest
 import ptlib
 from ptlib import _np_f
 
+abi = ptlib.abi
 L = ptlib.product()
 O = ptlib.oracle()
 HEADER = os.path.join(ptlib.ROOT, "include", "ptrace.h")
@@ -30,6 +35,155 @@ def test_every_declared_symbol_is_exported():
         assert must in names
     for n in names:
         assert hasattr(L, n), "libptrace_hip.so does not export " + n
+
+
+def header_text():
+    text = re.sub(r"/\*.*?\*/", " ", open(HEADER).read(), flags=re.S)
+    return re.sub(r"//[^\n]*", " ", text)
+
+
+def split_top_level(text):
+    parts, depth, cur = [], 0, ""
+    for ch in text:
+        depth += (ch in "([") - (ch in ")]")
+        if ch == "," and depth == 0:
+            parts.append(cur.strip())
+            cur = ""
+        else:
+            cur += ch
+    return parts + [cur.strip()] if cur.strip() else parts
+
+
+def header_prototypes():
+    """{function: (return type, [parameter declarations])} as the header writes them"""
+    text = re.sub(r"^\s*#.*$", "", header_text(), flags=re.M)
+    text = re.sub(r"typedef\s+struct\s+\w+\s*\{.*?\}\s*\w+\s*;|enum\s*\{.*?\}\s*;|typedef[^;{]*;", "", text, flags=re.S)
+    protos = {}
+    for m in re.finditer(r"([\w\s\*]+?)\b(pt_[a-z0-9_]+)\s*\(((?:[^()]|\([^()]*\))*)\)\s*;", text):
+        params = m.group(3).strip()
+        protos[m.group(2)] = (m.group(1).strip(), [] if params == "void" else split_top_level(params))
+    return protos
+
+
+def header_structs():
+    return re.findall(r"typedef\s+struct\s+\w+\s*\{.*?\}\s*(\w+)\s*;", header_text(), flags=re.S)
+
+
+def abi_structs():
+    return {n: c for n, c in vars(abi).items() if isinstance(c, type) and issubclass(c, C.Structure) and c is not C.Structure}
+
+
+SCALARS = {"uint32_t": C.c_uint32, "uint64_t": C.c_uint64, "size_t": C.c_size_t, "int": C.c_int, "float": C.c_float,
+           "double": C.c_double}
+
+
+def type_mismatch(c_decl, ctype, is_return=False):
+    """None if the ctypes entry is of the class the header's declaration asks for, else what is wrong"""
+    decl = re.sub(r"\b(const|volatile|struct)\b", " ", c_decl)
+    if "*" in decl or "[" in decl or "pt_progress_fn" in decl:
+        if ctype in (C.c_void_p, C.c_char_p) or (isinstance(ctype, type) and issubclass(ctype, C._CFuncPtr)):
+            return None
+        if not (isinstance(ctype, type) and issubclass(ctype, C._Pointer)):
+            return "%r is no pointer type" % (ctype,)
+        target = ctype._type_
+        while issubclass(target, C._Pointer):
+            target = target._type_
+        base = re.match(r"\s*(\w+)", decl).group(1)
+        if issubclass(target, C.Structure) and target.__name__ != base:
+            return "points at %s, the header says %s" % (target.__name__, base)
+        return None
+    words = decl.split()
+    base = " ".join(words if is_return else words[:-1])
+    want = None if (is_return and base == "void") else SCALARS.get(base, "no rule for " + base)
+    return None if ctype is want else "%r where the header says %s" % (ctype, base)
+
+
+def prototype_mismatches(table):
+    bad = []
+    for name, (ret, params) in header_prototypes().items():
+        restype, argtypes = table[name]
+        if len(argtypes) != len(params):
+            bad.append("%s: %d parameters, the header has %d" % (name, len(argtypes), len(params)))
+            continue
+        for what, decl, ctype in [("return", ret, restype)] + [(p, p, a) for p, a in zip(params, argtypes)]:
+            wrong = type_mismatch(decl, ctype, what == "return")
+            if wrong:
+                bad.append("%s, %s: %s" % (name, what, wrong))
+    return bad
+
+
+def test_signature_table_covers_the_header():
+    assert sorted(abi.SIGNATURES) == declared_functions() == sorted(header_prototypes())
+    for n in abi.SIGNATURES:
+        assert hasattr(L, n), "libptrace_hip.so does not export " + n
+        assert getattr(L, n).argtypes == abi.SIGNATURES[n][1], n  # load() declared it
+
+
+def test_prototypes_match_the_header():
+    assert prototype_mismatches(abi.SIGNATURES) == []
+    # the check can fail: one argument dropped, one uint64_t narrowed
+    dropped = dict(abi.SIGNATURES, pt_ctx_set_scene=(C.c_int, abi.SIGNATURES["pt_ctx_set_scene"][1][:-1]))
+    assert prototype_mismatches(dropped) == ["pt_ctx_set_scene: 5 parameters, the header has 6"]
+    narrowed = dict(abi.SIGNATURES, pt_bvh_refs_fit=(C.c_int, [C.c_uint64, C.c_uint32]))
+    assert len(prototype_mismatches(narrowed)) == 1 and "pt_bvh_refs_fit" in prototype_mismatches(narrowed)[0]
+    wrong_struct = dict(abi.SIGNATURES, pt_aov_defaults=(C.c_int, [C.POINTER(abi.pt_config)]))
+    assert len(prototype_mismatches(wrong_struct)) == 1
+
+
+def test_layouts_and_constants_match_the_compiler(tmp_path):
+    """sizeof, every offsetof and every PT_* value as the C compiler sees include/ptrace.h, against ctypes"""
+    structs = abi_structs()
+    assert len(structs) == 22 and sorted(structs) == sorted(header_structs())
+    consts = {n: v for n, v in vars(abi).items() if n.startswith("PT_") and isinstance(v, int)}
+    assert len(consts) >= 45 and "PT_TABLE_COUNT" in consts and "PT_CANCELLED" in consts
+    want, prog = [], ["#include <stdio.h>", "#include <stddef.h>", '#include "ptrace.h"', "int main(void) {"]
+    for n, c in sorted(structs.items()):
+        prog.append('printf("%s %%zu\\n", sizeof(%s));' % (n, n))
+        want.append("%s %d" % (n, C.sizeof(c)))
+        for field, _ in c._fields_:
+            prog.append('printf("%s.%s %%zu\\n", offsetof(%s, %s));' % (n, field, n, field))
+            want.append("%s.%s %d" % (n, field, getattr(c, field).offset))
+    for n, v in sorted(consts.items()):
+        prog.append('printf("%s %%lld\\n", (long long)(%s));' % (n, n))
+        want.append("%s %d" % (n, v))
+    prog.append('printf("pipelines %lld\\n", (long long)PT_FLAG_PIPELINES(19));')
+    want.append("pipelines %d" % abi.PT_FLAG_PIPELINES(19))
+    prog.append("return 0; }")
+    (tmp_path / "layout.c").write_text("\n".join(prog) + "\n")
+    exe = str(tmp_path / "layout")
+    subprocess.check_call([os.environ.get("CC", "cc"), "-std=c11", "-I", os.path.dirname(HEADER), str(tmp_path / "layout.c"), "-o", exe])
+    assert subprocess.check_output([exe]).decode().split("\n")[:-1] == want
+    assert abi.TABLE_NAMES[abi.PT_TABLE_BVH_MESHES] == "bvh_meshes" and len(abi.TABLE_NAMES) == abi.PT_TABLE_COUNT
+
+
+def test_abi_py_is_the_only_description():
+    """Outside abi.py nothing assigns a pt_* function's argtypes or restype, and no class restates a struct of ptrace.h."""
+    layouts = {tuple(f for f, _ in c._fields_): n for n, c in abi_structs().items()}
+    files = [p for d in ("path-tracer-rust_amd", "tests", "tools") for p in glob.glob(os.path.join(ptlib.ROOT, d, "*.py"))]
+    assert len(files) > 100 and os.path.join(ptlib.PKG, "abi.py") in files
+    bad = []
+    for path in files:
+        if path == os.path.join(ptlib.PKG, "abi.py"):
+            continue
+        text = open(path).read()
+        for m in re.finditer(r"\.(pt_[a-z0-9_]+)\.(argtypes|restype)\s*=(?!=)", text):
+            bad.append("%s assigns %s.%s" % (os.path.relpath(path, ptlib.ROOT), m.group(1), m.group(2)))
+        for node in ast.walk(ast.parse(text)):
+            if not (isinstance(node, ast.ClassDef) and any("Structure" in ast.unparse(b) for b in node.bases)):
+                continue
+            for st in node.body:
+                if isinstance(st, ast.Assign) and ast.unparse(st.targets[0]) == "_fields_" and isinstance(st.value, ast.List):
+                    names = tuple(e.elts[0].value for e in st.value.elts if isinstance(e, ast.Tuple) and isinstance(e.elts[0], ast.Constant))
+                    if names in layouts:
+                        bad.append("%s: class %s restates %s" % (os.path.relpath(path, ptlib.ROOT), node.name, layouts[names]))
+    assert bad == []
+
+
+def test_declare_names_every_missing_symbol():
+    with pytest.raises(AttributeError) as e:
+        abi.declare(O)  # the oracle exports none of them
+    assert "pt_ctx_render," in str(e.value) and "pt_write_pfm" in str(e.value)
+    assert abi.declare(C.CDLL(ptlib.ORACLE_SO), partial=True).pto_render.argtypes is None
 
 
 def test_version_and_struct_sizes():

@@ -10,7 +10,7 @@ import subprocess
 import ptlib
 
 ROOT = ptlib.ROOT
-PT_ERR_INVALID = -1
+PT_ERR_INVALID = ptlib.abi.PT_ERR_INVALID
 NAMES = ("pt_ctx_accumulate", "pt_ctx_accum_info", "pt_ctx_accum_reset", "pt_ctx_accum_save", "pt_ctx_accum_load")
 # parameter kinds, p = pointer, i = integer (the header's declarations, in order)
 KINDS = {"pt_ctx_accumulate": "pppppppp", "pt_ctx_accum_info": "pppp", "pt_ctx_accum_reset": "p",
@@ -23,12 +23,6 @@ def _header():
 
 def _lib():
     L = ptlib.product()
-    L.pt_ctx_accumulate.argtypes = [C.c_void_p, C.POINTER(ptlib.PtConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                    C.c_void_p, C.POINTER(ptlib.PtStats)]
-    L.pt_ctx_accum_info.argtypes = [C.c_void_p, C.POINTER(ptlib.PtConfig), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-    L.pt_ctx_accum_reset.argtypes = [C.c_void_p]
-    L.pt_ctx_accum_save.argtypes = [C.c_void_p, C.c_char_p]
-    L.pt_ctx_accum_load.argtypes = [C.c_void_p, C.c_char_p]
     return L
 
 

@@ -12,27 +12,11 @@ import numpy as np
 import adaptive_ref
 import noise_ref
 import ptlib
-from ptlib import PtConfig, PtStats
+from ptlib import PtAdaptiveParams, PtAdaptiveStats, PtConfig, PtStats
 
 ROOT = ptlib.ROOT
-PT_ERR_INVALID = -1
+PT_ERR_INVALID = ptlib.abi.PT_ERR_INVALID
 f32 = np.float32
-
-
-class PtAdaptiveParams(C.Structure):
-    _fields_ = [("tile_error", C.c_float), ("tile", C.c_uint32), ("min_spp", C.c_uint32)]
-
-
-class PtAdaptiveStats(C.Structure):
-    _fields_ = [("tiles", C.c_uint32), ("tiles_open", C.c_uint32), ("levels", C.c_uint32), ("level_spp", C.c_uint32 * 32),
-                ("tiles_closed", C.c_uint32 * 32), ("samples", C.c_uint64), ("mean_error", C.c_double)]
-
-
-def bind(L):
-    L.pt_ctx_render_adaptive.argtypes = [C.c_void_p, C.POINTER(PtConfig), C.POINTER(PtAdaptiveParams), C.c_void_p, C.c_void_p,
-                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PtStats),
-                                         C.POINTER(PtAdaptiveStats)]
-    return L
 
 
 def test_header_declares_it_and_abi_stays_5():
@@ -80,7 +64,7 @@ def test_rust_shim_and_python_binding_follow_the_header():
 
 
 def test_refusals_come_in_the_stated_order_without_a_device():
-    L = bind(ptlib.product())
+    L = ptlib.product()
     cfg = PtConfig(64, 40, 256, 0, 1, 0, 0, 0, 0)
     buf = C.c_void_p(256)  # never dereferenced: every call below is refused before a device is touched
     st, ast = PtStats(), PtAdaptiveStats()

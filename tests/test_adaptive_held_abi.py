@@ -10,31 +10,13 @@ import subprocess
 
 import adaptive_ref
 import ptlib
-from ptlib import PtConfig, PtStats
-from test_adaptive_abi import PtAdaptiveParams, PtAdaptiveStats
-from test_adaptive_abi import bind as bind_adaptive
+from ptlib import PtAdaptiveInfo, PtAdaptiveParams, PtAdaptiveStats, PtConfig, PtStats
 
 ROOT = ptlib.ROOT
-PT_ERR_INVALID = -1
+PT_ERR_INVALID = ptlib.abi.PT_ERR_INVALID
 NONE = (1 << 64) - 1  # "no E"
 NEW = ("pt_ctx_accumulate_adaptive", "pt_ctx_adaptive_info", "pt_ctx_adaptive_resolve", "pt_ctx_adaptive_reset",
        "pt_ctx_adaptive_save", "pt_ctx_adaptive_load")
-
-
-class PtAdaptiveInfo(C.Structure):
-    _fields_ = [("tiles", C.c_uint32), ("tiles_open", C.c_uint32), ("tiles_at_cap", C.c_uint32), ("spp_min", C.c_uint32),
-                ("spp_max", C.c_uint32), ("samples", C.c_uint64), ("mean_error", C.c_double)]
-
-
-def bind(L):
-    bind_adaptive(L)
-    L.pt_ctx_accumulate_adaptive.argtypes = L.pt_ctx_render_adaptive.argtypes
-    L.pt_ctx_adaptive_info.argtypes = [C.c_void_p, C.POINTER(PtConfig), C.POINTER(PtAdaptiveParams), C.POINTER(PtAdaptiveInfo)]
-    L.pt_ctx_adaptive_resolve.argtypes = [C.c_void_p, C.POINTER(PtConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.pt_ctx_adaptive_reset.argtypes = [C.c_void_p]
-    L.pt_ctx_adaptive_save.argtypes = [C.c_void_p, C.c_char_p]
-    L.pt_ctx_adaptive_load.argtypes = [C.c_void_p, C.c_char_p]
-    return L
 
 
 # ---- the ABI ---------------------------------------------------------------------------------------------------------
@@ -84,7 +66,7 @@ def test_rust_shim_and_python_binding_follow_the_header():
 
 
 def test_refusals_come_in_the_stated_order_without_a_device():
-    L = bind(ptlib.product())
+    L = ptlib.product()
     cfg = PtConfig(64, 40, 256, 0, 1, 0, 0, 0, 0)
     buf = C.c_void_p(256)  # never dereferenced: every call below is refused before a device is touched
     st, ast, info = PtStats(), PtAdaptiveStats(), PtAdaptiveInfo()

@@ -14,7 +14,7 @@ import numpy as np
 import ptlib
 
 ROOT = ptlib.ROOT
-PT_ERR_INVALID, PT_ERR_IO = -1, -6
+PT_ERR_INVALID, PT_ERR_IO = ptlib.abi.PT_ERR_INVALID, ptlib.abi.PT_ERR_IO
 NAMES = ("pt_ctx_render_aov", "pt_write_pfm")
 # parameter kinds, p = pointer, i = integer (the header's declarations, in order)
 KINDS = {"pt_ctx_render_aov": "ppppppp", "pt_write_pfm": "ppiii"}
@@ -27,13 +27,6 @@ def _header():
 
 def _lib():
     L = ptlib.product()
-    L.pt_ctx_render_aov.argtypes = [C.c_void_p, C.POINTER(ptlib.PtConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                    C.c_void_p]
-    L.pt_write_pfm.argtypes = [C.c_char_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
-    L.pt_write_ppm.argtypes = [C.c_char_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_char_p, C.c_uint64]
-    L.pt_to_int_with_gamma_correction.argtypes = [C.c_float]
-    L.pt_to_int_with_gamma_correction.restype = C.c_uint32
-    L.pt_last_error.restype = C.c_char_p
     return L
 
 

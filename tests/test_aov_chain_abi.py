@@ -12,15 +12,12 @@ import subprocess
 import pytest
 
 import ptlib
+from ptlib import PtAovParams
 
 ROOT = ptlib.ROOT
-PT_ERR_INVALID = -1
-THROUGH_DELTA, MAX_CHAIN = 1, 16
+PT_ERR_INVALID = ptlib.abi.PT_ERR_INVALID
+THROUGH_DELTA, MAX_CHAIN = ptlib.abi.PT_AOV_THROUGH_DELTA, ptlib.abi.PT_AOV_MAX_CHAIN
 KINDS = {"pt_aov_defaults": "p", "pt_ctx_render_aov_ex": "ppppppppp"}
-
-
-class PtAovParams(C.Structure):
-    _fields_ = [("flags", C.c_uint32), ("max_chain", C.c_uint32)]
 
 
 def _header():
@@ -29,9 +26,6 @@ def _header():
 
 def _lib():
     L = ptlib.product()
-    L.pt_aov_defaults.argtypes = [C.POINTER(PtAovParams)]
-    L.pt_ctx_render_aov_ex.argtypes = [C.c_void_p, C.POINTER(ptlib.PtConfig), C.POINTER(PtAovParams)] + [C.c_void_p] * 6
-    L.pt_last_error.restype = C.c_char_p
     return L
 
 

@@ -3,7 +3,6 @@
 A generator that produces no boundary rays would pass every device test, so the ray set is tested itself: the oracle's
 verdict flips across the ulp variants, exact ties occur, the clamp family is there, every scene has hits and misses, the
 tables the rays are aimed at are the product's, and the set is a function of the seed."""
-import ctypes as C
 
 import numpy as np
 import pytest
@@ -132,7 +131,6 @@ def test_tables_are_the_products(sets):
     rank_id, one BVH per mesh of kBvhMinTris (16) or more triangles, the four-wide tree is the smaller, the filter records add up, the
     references fit the walkers' 26 bits, and the largest mesh has more nodes than the LDS stages (512)."""
     L = ptlib.product()
-    L.pt_bvh_refs_fit.argtypes = [C.c_uint64, C.c_uint64]
     most = 0
     for rs, _ in sets:
         sc, tb = rs.scene, rs.tables

@@ -21,7 +21,7 @@ from ptlib import PtCamera, PtObject, PtTriangle
 
 ROOT = ptlib.ROOT
 F32 = np.float32
-PT_ERR_INVALID = -1
+PT_ERR_INVALID = ptlib.abi.PT_ERR_INVALID
 fp = C.POINTER(C.c_float)
 SCENES = ("single-sphere", "cartesian", "two-spheres", "three-spheres", "cornell", "mesh")
 NEW = ("pt_ctx_set_camera", "pt_ctx_camera_reach", "pt_ctx_reserve_camera_reach", "pt_scene_reach")
@@ -30,10 +30,6 @@ NEW = ("pt_ctx_set_camera", "pt_ctx_camera_reach", "pt_ctx_reserve_camera_reach"
 @pytest.fixture(scope="module")
 def L():
     L = ptlib.product()
-    L.pt_ctx_set_camera.argtypes = [C.c_void_p, C.POINTER(PtCamera), C.POINTER(C.c_int)]
-    L.pt_ctx_camera_reach.argtypes = [C.c_void_p, fp, fp]
-    L.pt_ctx_reserve_camera_reach.argtypes = [C.c_void_p, fp, fp, C.POINTER(C.c_int)]
-    L.pt_scene_reach.argtypes = [C.POINTER(PtCamera), C.POINTER(PtObject), C.c_uint32, C.POINTER(PtTriangle), C.c_uint32, fp, fp]
     return L
 
 

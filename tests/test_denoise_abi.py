@@ -24,10 +24,11 @@ import pytest
 
 import denoise_ref
 import ptlib
-from denoise_ref import F32, PtDenoiseParams
+from ptlib import PtDenoiseParams
+from denoise_ref import F32
 
 ROOT = ptlib.ROOT
-PT_ERR_INVALID = -1
+PT_ERR_INVALID = ptlib.abi.PT_ERR_INVALID
 MEASURED = {"cornell": 0.381820, "mesh": 0.316506}  # profiles/denoise_cpu_study.json, "chosen"
 R = {sid: 1.15 * v for sid, v in MEASURED.items()}
 BIG = float(2.0 ** 16)  # a sigma_color so large that fall(xc) is exactly 1 for colour differences up to 1
@@ -38,8 +39,7 @@ def _header():
 
 
 def _lib():
-    L = denoise_ref.bind(ptlib.product())
-    L.pt_last_error.restype = C.c_char_p
+    L = ptlib.product()
     return L
 
 

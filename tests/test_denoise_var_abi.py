@@ -24,10 +24,11 @@ import denoise_ref
 import denoise_var_inputs as inp
 import denoise_var_ref as ref
 import ptlib
-from denoise_var_ref import F32, PtDenoiseVarParams
+from ptlib import PtDenoiseVarParams
+from denoise_var_ref import F32
 
 ROOT = ptlib.ROOT
-PT_ERR_INVALID = -1
+PT_ERR_INVALID = ptlib.abi.PT_ERR_INVALID
 BIG = float(2.0 ** 16)  # a sigma_var so large that, with e = 12, fall(xc) is exactly 1 for colour differences up to 1
 STUDY = json.load(open(os.path.join(ROOT, "profiles", "denoise_var_cpu_study.json")))
 CELLS = [(sid, n) for sid in inp.SCENES for n in inp.SPP]
@@ -38,8 +39,7 @@ def _header():
 
 
 def _lib():
-    L = ref.bind(ptlib.product())
-    L.pt_last_error.restype = C.c_char_p
+    L = ptlib.product()
     return L
 
 
@@ -286,7 +286,7 @@ def cell_ratios(cell, levels, sigma_var, sigma_depth):
     noisy, e, albedo, normal, depth, conv = inp.inputs(*cell)
     base = inp.rmse(noisy, conv)
     out = ref.denoise_var(noisy, e, inp.W, inp.H, albedo, normal, depth, levels, sigma_var, sigma_depth)
-    flv, fsc, fsd = denoise_ref.defaults(denoise_ref.bind(ptlib.product()))
+    flv, fsc, fsd = denoise_ref.defaults(ptlib.product())
     fixed = denoise_ref.denoise(noisy, inp.W, inp.H, albedo, normal, depth, flv, fsc, fsd)
     return inp.rmse(out, conv) / base, inp.rmse(fixed, conv) / base
 

@@ -14,20 +14,10 @@ from ptlib import PtConfig, PtStats
 pytestmark = pytest.mark.gpu
 
 WAVE, MEGA = ptlib.BACKEND_WAVEFRONT, ptlib.BACKEND_MEGAKERNEL
-NO_BVH, SEPARATE = 1, 2
-PT_ERR_INVALID, PT_CANCELLED, PT_ERR_IO, PT_ERR_PARSE = -1, -4, -6, -7
+NO_BVH, SEPARATE = ptlib.abi.PT_FLAG_NO_BVH, ptlib.abi.PT_FLAG_SEPARATE_KERNELS
+PT_ERR_INVALID, PT_CANCELLED, PT_ERR_IO, PT_ERR_PARSE = ptlib.abi.PT_ERR_INVALID, ptlib.abi.PT_CANCELLED, ptlib.abi.PT_ERR_IO, ptlib.abi.PT_ERR_PARSE
 W, H, SEED = 64, 40, 8
 TOL = 1e-4
-
-
-def _bind(L):
-    L.pt_ctx_accumulate.argtypes = [C.c_void_p, C.POINTER(PtConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                    C.c_void_p, C.POINTER(PtStats)]
-    L.pt_ctx_accum_info.argtypes = [C.c_void_p, C.POINTER(PtConfig), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-    L.pt_ctx_accum_reset.argtypes = [C.c_void_p]
-    L.pt_ctx_accum_save.argtypes = [C.c_void_p, C.c_char_p]
-    L.pt_ctx_accum_load.argtypes = [C.c_void_p, C.c_char_p]
-    return L
 
 
 class Dev:
@@ -89,7 +79,7 @@ def cfg_of(spp, backend=WAVE, seed=SEED, w=W, h=H, flags=0, rays_per_pass=0, ban
 
 @pytest.fixture(scope="module")
 def L():
-    L = _bind(ptlib.product())
+    L = ptlib.product()
     assert L.pt_device_count() >= 1, "no HIP device visible: the product has no CPU fallback"
     return L
 

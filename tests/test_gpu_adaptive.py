@@ -9,16 +9,14 @@ import pytest
 import adaptive_ref
 import noise_ref
 import ptlib
-from ptlib import PtStats
-from test_adaptive_abi import PtAdaptiveParams, PtAdaptiveStats, bind as bind_adaptive
-from test_gpu_accumulate import MEGA, NO_BVH, _bind
+from ptlib import PtAdaptiveParams, PtAdaptiveStats, PtStats
+from test_gpu_accumulate import MEGA, NO_BVH
 from test_gpu_accumulate import cfg_of as cfg_small
 from test_gpu_noise import NDev
-from test_noise_abi import bind as bind_noise
 
 pytestmark = pytest.mark.gpu
 
-PT_ERR_INVALID, PT_CANCELLED = -1, -4
+PT_ERR_INVALID, PT_CANCELLED = ptlib.abi.PT_ERR_INVALID, ptlib.abi.PT_CANCELLED
 W, H, TILE, TILE_ERROR, CAP, SEED = 96, 64, 8, 0.08, 256, 8
 f32 = np.float32
 
@@ -30,7 +28,7 @@ def cfg_of(spp, backend=MEGA, w=W, h=H, **kw):
 
 @pytest.fixture(scope="module")
 def L():
-    L = bind_adaptive(bind_noise(_bind(ptlib.product())))
+    L = ptlib.product()
     assert L.pt_device_count() >= 1, "no HIP device visible: the product has no CPU fallback"
     return L
 

@@ -35,7 +35,6 @@ def test_cli_adaptive_writes_the_librarys_frame_and_the_counts(L, scenes, tmp_pa
     finally:
         d.close()
     ref = str(tmp_path / "ref.ppm")
-    L.pt_write_ppm.argtypes = [C.c_char_p, C.POINTER(C.c_float), C.c_uint32, C.c_uint32, C.c_uint32, C.c_char_p, C.c_uint64]
     img = np.ascontiguousarray(want["img"])
     assert L.pt_write_ppm(ref.encode(), img.ctypes.data_as(C.POINTER(C.c_float)), W, H, CAP, b"cornell", 0) == 0
     assert np.array_equal(ppm_body(tmp_path / "a" / files[0]), ppm_body(ref))

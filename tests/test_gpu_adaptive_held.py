@@ -10,24 +10,22 @@ import pytest
 
 import adaptive_ref
 import ptlib
-from ptlib import PtStats
-from test_adaptive_abi import PtAdaptiveParams, PtAdaptiveStats
-from test_adaptive_held_abi import PtAdaptiveInfo, bind as bind_held, parse_adaptive_checkpoint
-from test_gpu_accumulate import NO_BVH, _bind
+from ptlib import PtAdaptiveInfo, PtAdaptiveParams, PtAdaptiveStats, PtStats
+from test_adaptive_held_abi import parse_adaptive_checkpoint
+from test_gpu_accumulate import NO_BVH
 from test_gpu_adaptive import CAP, H, SEED, TILE, TILE_ERROR, W, ADev, cfg_of
 from test_gpu_noise import NDev
-from test_noise_abi import bind as bind_noise
 
 pytestmark = pytest.mark.gpu
 
-PT_ERR_INVALID, PT_CANCELLED, PT_ERR_PARSE = -1, -4, -7
+PT_ERR_INVALID, PT_CANCELLED, PT_ERR_PARSE = ptlib.abi.PT_ERR_INVALID, ptlib.abi.PT_CANCELLED, ptlib.abi.PT_ERR_PARSE
 f32 = np.float32
 CASES = [("cornell", 0), ("mesh", 0), ("mesh", NO_BVH)]
 
 
 @pytest.fixture(scope="module")
 def L():
-    L = bind_held(bind_noise(_bind(ptlib.product())))
+    L = ptlib.product()
     assert L.pt_device_count() >= 1, "no HIP device visible: the product has no CPU fallback"
     return L
 

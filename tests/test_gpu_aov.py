@@ -14,20 +14,11 @@ from ptlib import PtConfig, PtStats
 
 pytestmark = pytest.mark.gpu
 
-PT_ERR_INVALID = -1
-NO_BVH = 1
+PT_ERR_INVALID = ptlib.abi.PT_ERR_INVALID
+NO_BVH = ptlib.abi.PT_FLAG_NO_BVH
 W, H, SEED = 64, 40, 8
 F32 = np.float32
 TWO32 = 4294967296.0
-
-
-def _bind(L):
-    L.pt_ctx_render_aov.argtypes = [C.c_void_p, C.POINTER(PtConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                    C.c_void_p]
-    L.pt_ctx_accumulate.argtypes = [C.c_void_p, C.POINTER(PtConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                    C.c_void_p, C.POINTER(PtStats)]
-    L.pt_ctx_accum_info.argtypes = [C.c_void_p, C.POINTER(PtConfig), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-    return L
 
 
 # ------------------------------------------------------------------------------------------------------- the rebuild
@@ -184,7 +175,7 @@ def generated_bvh_scene():
 # ------------------------------------------------------------------------------------------------------- tests
 @pytest.fixture(scope="module")
 def L():
-    return _bind(ptlib.product())
+    return ptlib.product()
 
 
 @pytest.mark.parametrize("sid", ["cornell", "three-spheres", "mesh", "mesh-hdodec", "generated-bvh"])

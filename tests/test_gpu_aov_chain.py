@@ -12,32 +12,19 @@ import pytest
 
 import aov_chain_ref as R
 import ptlib
-from ptlib import PtConfig, PtStats
+from ptlib import PtAovParams, PtStats
 from test_gpu_aov import (F32, H, NO_BVH, PT_ERR_INVALID, SEED, W, call_pixels, cfg_of, oracle_rays, pfm_to_framebuffer, read_pfm,
                           scene)
 
 pytestmark = pytest.mark.gpu
 
-THROUGH_DELTA, MAX_CHAIN = 1, 16
+THROUGH_DELTA, MAX_CHAIN = ptlib.abi.PT_AOV_THROUGH_DELTA, ptlib.abi.PT_AOV_MAX_CHAIN
 NAMES = ("albedo", "normal", "depth", "object_id", "chain")
-
-
-class PtAovParams(C.Structure):
-    _fields_ = [("flags", C.c_uint32), ("max_chain", C.c_uint32)]
-
-
-def _bind(L):
-    L.pt_ctx_render_aov.argtypes = [C.c_void_p, C.POINTER(PtConfig)] + [C.c_void_p] * 5
-    L.pt_ctx_render_aov_ex.argtypes = [C.c_void_p, C.POINTER(PtConfig), C.POINTER(PtAovParams)] + [C.c_void_p] * 6
-    L.pt_ctx_accumulate.argtypes = [C.c_void_p, C.POINTER(PtConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                    C.c_void_p, C.POINTER(PtStats)]
-    L.pt_ctx_accum_info.argtypes = [C.c_void_p, C.POINTER(PtConfig), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-    return L
 
 
 @pytest.fixture(scope="module")
 def L():
-    return _bind(ptlib.product())
+    return ptlib.product()
 
 
 # ------------------------------------------------------------------------------------------------------- scenes and records

@@ -23,7 +23,7 @@ pytestmark = pytest.mark.gpu
 SEED = 20261016
 TOL = 1e-4
 COUNTS = (1, 63, 64, 65, 4095, 4097)  # partial waves and partial streams; then the full set
-FLAG_SEPARATE_KERNELS = 2
+FLAG_SEPARATE_KERNELS = ptlib.abi.PT_FLAG_SEPARATE_KERNELS
 # pt_ctx_radiance probes (test_pass_kernels_first_hit): every target of these ray families with all its variants ...
 PROBE_ALL_KINDS = ("tie", "box", "tiny_dir", "sphere")
 # ... and of every other family this many targets, those whose oracle verdict flips across their variants first

@@ -15,28 +15,17 @@ import pytest
 
 import denoise_ref
 import ptlib
-from denoise_ref import F32, NO_DEMODULATE, PtDenoiseParams
-from ptlib import PtConfig, PtStats
+from denoise_ref import F32, NO_DEMODULATE
+from ptlib import PtDenoiseParams, PtStats
 from test_gpu_aov import cfg_of, pfm_to_framebuffer, read_pfm, scene
 
 pytestmark = pytest.mark.gpu
 
-PT_ERR_INVALID = -1
+PT_ERR_INVALID = ptlib.abi.PT_ERR_INVALID
 SEED = 8
 R_CORNELL = 1.15 * 0.381820  # tests/test_denoise_abi.py: 1.15 x the CPU study's ratio at the defaults
 SIZES = ((64, 40), (67, 41), (5, 3), (1, 1), (300, 7))
 NON_DEFAULT = (0.75, 0.4)  # (sigma_color, sigma_depth)
-
-
-def _bind(L):
-    denoise_ref.bind(L)
-    L.pt_ctx_render_aov.argtypes = [C.c_void_p, C.POINTER(PtConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                    C.c_void_p]
-    L.pt_ctx_accumulate.argtypes = [C.c_void_p, C.POINTER(PtConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                    C.c_void_p, C.POINTER(PtStats)]
-    L.pt_ctx_accum_info.argtypes = [C.c_void_p, C.POINTER(PtConfig), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-    L.pt_last_error.restype = C.c_char_p
-    return L
 
 
 class Frame:
@@ -102,7 +91,7 @@ def assert_bytes(got, want, what):
 
 @pytest.fixture(scope="module")
 def L():
-    return _bind(ptlib.product())
+    return ptlib.product()
 
 
 # ------------------------------------------------------------------------------------------------ bit for bit
@@ -173,7 +162,7 @@ CHILD_FRAMES = ((67, 41), (300, 200), (5, 3))
 def child_main():
     """python tests/test_gpu_denoise.py --child: sha256 of pt_ctx_denoise's output for every frame of CHILD_FRAMES and every
     level count, in the form PT_DN_LDS_MAXSTEP selects, as one JSON line"""
-    L = _bind(ptlib.product())
+    L = ptlib.product()
     out = {}
     fr = Frame(L, scene("mesh"), max(w * h for w, h in CHILD_FRAMES))
     try:

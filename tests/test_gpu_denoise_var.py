@@ -19,35 +19,18 @@ import pytest
 import denoise_ref
 import denoise_var_ref as ref
 import ptlib
-from denoise_ref import PtDenoiseParams
-from denoise_var_ref import F32, NO_DEMODULATE, PtDenoiseVarParams
-from ptlib import PtConfig, PtStats
-from test_adaptive_abi import PtAdaptiveParams, PtAdaptiveStats, bind as bind_adaptive
+from denoise_var_ref import F32, NO_DEMODULATE
+from ptlib import PtAdaptiveParams, PtAdaptiveStats, PtDenoiseParams, PtDenoiseVarParams, PtNoiseStats, PtStats
 from test_gpu_aov import cfg_of, pfm_to_framebuffer, read_pfm, scene
-from test_noise_abi import PtNoiseStats, bind as bind_noise
 
 pytestmark = pytest.mark.gpu
 
-PT_ERR_INVALID = -1
+PT_ERR_INVALID = ptlib.abi.PT_ERR_INVALID
 SEED = 8
 SIZES = ((64, 40), (67, 41), (5, 3), (1, 1), (300, 7))
 NON_DEFAULT = (0.6, 0.4)  # (sigma_var, sigma_depth)
 STUDY = json.load(open(os.path.join(ptlib.ROOT, "profiles", "denoise_var_cpu_study.json")))
 BUFS = (("color", 3), ("error", 1), ("albedo", 3), ("normal", 3), ("depth", 1), ("out", 3))
-
-
-def _bind(L):
-    ref.bind(L)
-    denoise_ref.bind(L)
-    bind_adaptive(bind_noise(L))
-    L.pt_ctx_render_aov.argtypes = [C.c_void_p, C.POINTER(PtConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                    C.c_void_p]
-    L.pt_ctx_accumulate.argtypes = [C.c_void_p, C.POINTER(PtConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                    C.c_void_p, C.POINTER(PtStats)]
-    L.pt_ctx_accum_info.argtypes = [C.c_void_p, C.POINTER(PtConfig), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-    L.pt_ctx_accum_reset.argtypes = [C.c_void_p]
-    L.pt_last_error.restype = C.c_char_p
-    return L
 
 
 def hip_runtime():
@@ -158,7 +141,7 @@ def assert_bytes(got, want, what):
 
 @pytest.fixture(scope="module")
 def L():
-    L = _bind(ptlib.product())
+    L = ptlib.product()
     assert L.pt_device_count() >= 1, "no HIP device visible: the product has no CPU fallback"
     return L
 
@@ -277,7 +260,7 @@ CHILD_FRAMES = ((67, 41), (300, 200), (5, 3))
 def child_main():
     """python tests/test_gpu_denoise_var.py --child: sha256 of pt_ctx_denoise_var's output for every frame of CHILD_FRAMES and
     every level count, in the form PT_DN_LDS_MAXSTEP selects, as one JSON line"""
-    L = _bind(ptlib.product())
+    L = ptlib.product()
     out = {}
     fr = Frame(L, scene("mesh"), max(w * h for w, h in CHILD_FRAMES))
     try:

@@ -23,7 +23,6 @@ import frame_sums as fs
 import ptlib
 import scatter_walk
 from ptlib import PtConfig
-from test_gpu_accumulate import _bind
 from test_gpu_boundary_rays import _new_ctx
 from test_gpu_frame_sums import Out, _accumulate, _render, _saved, assert_frame, assert_planes
 
@@ -38,7 +37,7 @@ CONTEXTS = {"one_stream": {"PT_STREAMS": "1"}, "four_streams": {"PT_STREAMS": "4
 
 @pytest.fixture(scope="module")
 def L():
-    L = _bind(ptlib.product())
+    L = ptlib.product()
     assert L.pt_device_count() >= 1, "no HIP device visible: the product has no CPU fallback"
     return L
 

@@ -25,7 +25,7 @@ from test_gpu_boundary_rays import _new_ctx
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "frame_plan_frames_parent.json")
 SEED = 4
-SEPARATE_KERNELS = 2  # PT_FLAG_SEPARATE_KERNELS
+SEPARATE_KERNELS = ptlib.abi.PT_FLAG_SEPARATE_KERNELS
 BY_HAND = {"PT_STREAMS": "4", "PT_TAPER_CUT": "4", "PT_TAPER_PIECES": "4"}
 # name: (scene, width, height, spp, tuning environment, memory budget, flags, rays_per_pass)
 FRAMES = {
@@ -94,8 +94,7 @@ def test_the_recorded_frames_reach_their_branches():
 
 
 if __name__ == "__main__":
-    ptlib.PRODUCT_SO = os.path.abspath(sys.argv[1])
-    lib = ptlib.product()
+    lib = ptlib.abi.declare(C.CDLL(os.path.abspath(sys.argv[1])), partial=True)  # an older commit lacks newer entry points
     rec = {"commit": sys.argv[2], "frames": {name: frame(lib, name) for name in FRAMES}}
     with open(sys.argv[3] if len(sys.argv) > 3 else GOLDEN, "w") as f:
         json.dump(rec, f, indent=1)

@@ -20,13 +20,12 @@ import frame_sums as fs
 import noise_ref
 import ptlib
 from ptlib import PtConfig, PtObject, PtStats, _np_f
-from test_gpu_accumulate import _bind
 from test_gpu_boundary_rays import PASS_FORMS, _new_ctx
 from test_gpu_noise import deal
 
 pytestmark = pytest.mark.gpu
 
-PT_ERR_INVALID = -1
+PT_ERR_INVALID = ptlib.abi.PT_ERR_INVALID
 # test_gpu_boundary_rays' forms and the megakernel that scans every triangle (k_mega)
 FORMS = PASS_FORMS + [("mega_no_bvh", {}, ptlib.BACKEND_MEGAKERNEL, ptlib.FLAG_NO_BVH, (None, None))]
 FORM_IDS = [f[0] for f in FORMS]
@@ -36,11 +35,8 @@ BVH_MIN_TRIS = 16  # csrc/pt_device.h kBvhMinTris: a mesh of that many triangles
 
 @pytest.fixture(scope="module")
 def L():
-    L = _bind(ptlib.product())
+    L = ptlib.product()
     assert L.pt_device_count() >= 1, "no HIP device visible: the product has no CPU fallback"
-    L.pt_ctx_accum_track_noise.argtypes = [C.c_void_p, C.c_int]
-    L.pt_ctx_set_object.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(PtObject), C.POINTER(C.c_int)]
-    L.pt_ctx_table_hashes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     return L
 
 

@@ -29,7 +29,7 @@ pytestmark = pytest.mark.gpu
 
 SEED = 20261016
 TOL = 1e-4
-FLAG_SEPARATE_KERNELS = 2
+FLAG_SEPARATE_KERNELS = ptlib.abi.PT_FLAG_SEPARATE_KERNELS
 M_STREAMS = 4  # the stream-length rungs: PT_STREAMS=4 and a frame of m x 4 pixels
 LINE = re.compile(r"^(k_\S+): \d+ bytes of LDS per workgroup \(\+ \d+ of padding\)")
 WHICH = {"k_pass_cand": 0, "k_pass_cand<BVH>": 0, "k_pass": 0, "k_intersect_cand": 1, "k_mega_cand": 2, "k_mega": 2}

@@ -10,15 +10,13 @@ import pytest
 
 import masked_ref as ref
 import ptlib
-import upsample_ref
-from masked_ref import F32, U8, PtSelectParams
-from ptlib import PtConfig, PtStats
-from test_adaptive_abi import PtAdaptiveParams, PtAdaptiveStats
+from masked_ref import F32, U8
+from ptlib import PtAdaptiveParams, PtAdaptiveStats, PtConfig, PtSelectParams, PtStats
 
 pytestmark = pytest.mark.gpu
 
-PT_ERR_INVALID, PT_CANCELLED = -1, -4
-NO_BVH = 1
+PT_ERR_INVALID, PT_CANCELLED = ptlib.abi.PT_ERR_INVALID, ptlib.abi.PT_CANCELLED
+NO_BVH = ptlib.abi.PT_FLAG_NO_BVH
 GUARD = 64          # floats or bytes behind each output
 SENTINEL = F32(-3)  # no resolved colour: they are clamped to [0, 1]
 W, H, SEED = 67, 41, 7
@@ -38,17 +36,11 @@ def hip_runtime():
 
 @pytest.fixture(scope="module")
 def L():
-    L = upsample_ref.bind(ref.bind(ptlib.product()))
+    L = ptlib.product()
     assert L.pt_device_count() >= 1, "no HIP device visible: the product has no CPU fallback"
     frame = [C.c_void_p, C.POINTER(PtConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PtStats)]
     adaptive = [C.c_void_p, C.POINTER(PtConfig), C.POINTER(PtAdaptiveParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                 C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PtStats), C.POINTER(PtAdaptiveStats)]
-    L.pt_ctx_accumulate.argtypes = frame
-    L.pt_ctx_accum_info.argtypes = [C.c_void_p, C.POINTER(PtConfig), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-    L.pt_ctx_render_adaptive.argtypes = adaptive
-    L.pt_ctx_accumulate_adaptive.argtypes = adaptive
-    L.pt_ctx_adaptive_resolve.argtypes = [C.c_void_p, C.POINTER(PtConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.pt_ctx_render_aov.argtypes = [C.c_void_p, C.POINTER(PtConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     return L
 
 

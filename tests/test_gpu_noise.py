@@ -13,13 +13,12 @@ import pytest
 
 import noise_ref
 import ptlib
-from ptlib import PtStats
-from test_gpu_accumulate import Dev, MEGA, NO_BVH, WAVE, _bind, cfg_of
-from test_noise_abi import PtNoiseStats, PtNoiseTarget, bind
+from ptlib import PtNoiseStats, PtNoiseTarget, PtStats
+from test_gpu_accumulate import Dev, MEGA, NO_BVH, WAVE, cfg_of
 
 pytestmark = pytest.mark.gpu
 
-PT_ERR_INVALID, PT_CANCELLED, PT_ERR_PARSE = -1, -4, -7
+PT_ERR_INVALID, PT_CANCELLED, PT_ERR_PARSE = ptlib.abi.PT_ERR_INVALID, ptlib.abi.PT_CANCELLED, ptlib.abi.PT_ERR_PARSE
 W, H, SEED = 64, 40, 8
 BW, BH = 96, 64  # the frames of the behaviour tests (the goldens' size)
 STUDY = json.load(open(os.path.join(ptlib.ROOT, "profiles", "noise_cpu_study.json")))
@@ -28,7 +27,7 @@ f32 = np.float32
 
 @pytest.fixture(scope="module")
 def L():
-    L = bind(_bind(ptlib.product()))
+    L = ptlib.product()
     assert L.pt_device_count() >= 1, "no HIP device visible: the product has no CPU fallback"
     return L
 
@@ -463,8 +462,6 @@ def test_refusals_and_lifetime(L, cornell, mesh, tmp_path):
         bad_na = bytearray(data[:-8])
         struct.pack_into("<I", bad_na, 68 + 4, 9)  # nA = 9 > c = 8, under a valid hash
         h = L.pt_siphash
-        h.restype = C.c_uint64
-        h.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_char_p, C.c_size_t]
         bad_na += struct.pack("<Q", h(1, 3, 0, 0, bytes(bad_na), len(bad_na)))
         damaged = {
             "truncated": data[:-100],

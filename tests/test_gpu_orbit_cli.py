@@ -10,16 +10,13 @@ import pytest
 
 import ptlib
 import reproject_ref
-from denoise_var_ref import PtDenoiseVarParams
-from present_ref import PtPresentParams
-from ptlib import PtCamera, PtConfig, PtStats
-from reproject_var_ref import PtReprojectVarParams
+from ptlib import PtConfig, PtDenoiseVarParams, PtPresentParams, PtReprojectVarParams, PtStats
 
 pytestmark = pytest.mark.gpu
 
 W, H, SPP, SEED, FRAMES = 48, 32, 2, 5, 3
 CLI = os.path.join(ptlib.PKG, "ptrace")
-PT_PRESENT_RGB8 = 1
+PT_PRESENT_RGB8 = ptlib.abi.PT_PRESENT_RGB8
 
 
 def cam_dict(cam):
@@ -30,11 +27,6 @@ def cam_dict(cam):
 def loop_with_set_scene(L, sc, step, out_size=None, exposure=0.0):
     """frames 0..FRAMES-1 as RGB8 bytes: pt_ctx_set_scene -> render -> render_aov -> reproject_var -> denoise_var -> present"""
     vp = C.c_void_p
-    L.pt_ctx_render_aov.argtypes = [vp, C.POINTER(PtConfig)] + [vp] * 5
-    L.pt_ctx_reproject_var.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(PtReprojectVarParams), C.POINTER(PtCamera)] + [vp] * 4 + \
-                                      [C.POINTER(PtCamera)] + [vp] * 6 + [vp] * 5
-    L.pt_ctx_denoise_var.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(PtDenoiseVarParams)] + [vp] * 7
-    L.pt_ctx_present.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(PtPresentParams)] + [vp] * 3
     n = W * H
     ow, oh = out_size or (W, H)
     ctx = vp()

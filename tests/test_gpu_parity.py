@@ -863,7 +863,7 @@ def test_concurrent_pipelines_same_image(gpu):
     assert np.array_equal(img, whole[130:1500])
 
 
-PT_FLAG_SEPARATE_KERNELS = 2
+PT_FLAG_SEPARATE_KERNELS = ptlib.abi.PT_FLAG_SEPARATE_KERNELS
 
 
 def _render_flags(gpu, sc, w, h, spp, seed, flags, rays_per_pass=0, chunks=None):
@@ -1562,7 +1562,7 @@ def test_large_call_in_parts_cancel_and_snapshot(gpu):
 # it, the exhaustive sqrt / reciprocal sweep, memory-aware pass sizing
 import kats_shading
 
-FLAG_SEPARATE_KERNELS = 2
+FLAG_SEPARATE_KERNELS = ptlib.abi.PT_FLAG_SEPARATE_KERNELS
 # every device path: (backend, flags, the kernel it must report for scenes without BVH meshes)
 DEVICE_PATHS = [(0, 0, b"k_pass_cand"), (0, ptlib.FLAG_NO_BVH, b"k_pass"), (0, FLAG_SEPARATE_KERNELS, b"k_intersect_cand"),
                 (0, FLAG_SEPARATE_KERNELS | ptlib.FLAG_NO_BVH, b"k_intersect"),

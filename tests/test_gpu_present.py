@@ -11,12 +11,12 @@ import pytest
 
 import present_ref as ref
 import ptlib
-from present_ref import F32, FRAMEBUFFER_ORDER, ONE_BITS, RGB8, RGBA8, PtPresentParams
-from ptlib import PtConfig, PtStats
+from present_ref import F32, FRAMEBUFFER_ORDER, ONE_BITS, RGB8, RGBA8
+from ptlib import PtConfig, PtPresentParams, PtStats
 
 pytestmark = pytest.mark.gpu
 
-PT_ERR_INVALID = -1
+PT_ERR_INVALID = ptlib.abi.PT_ERR_INVALID
 GUARD = 64
 RESAMPLE = (((7, 5), (3, 2)), ((8, 8), (4, 4)), ((7, 5), (7, 2)), ((5, 3), (11, 7)), ((67, 33), (1, 1)), ((130, 3), (64, 1)),
             ((257, 129), (100, 50)))
@@ -79,12 +79,8 @@ class Dev:
 
 @pytest.fixture(scope="module")
 def L():
-    L = ref.bind(ptlib.product())
+    L = ptlib.product()
     assert L.pt_device_count() >= 1
-    L.pt_ctx_accumulate.argtypes = L.pt_ctx_render.argtypes
-    L.pt_ctx_accum_info.argtypes = [C.c_void_p, C.POINTER(PtConfig), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-    L.pt_ctx_denoise.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                 C.c_void_p, C.c_void_p]
     return L
 
 

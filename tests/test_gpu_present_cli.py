@@ -37,7 +37,7 @@ def test_preview_at_a_size_is_the_restatement(tmp_path):
     out = run(tmp_path, "--preview", str(tmp_path / "p.ppm"), "--preview-size", "32x24", "--aov", "1")
     (beauty,) = glob.glob(str(out / "*-beauty.pfm"))
     frame = pfm_to_framebuffer(read_pfm(beauty))
-    table = ref.thresholds(ref.bind(ptlib.product()))
+    table = ref.thresholds(ptlib.product())
     got = ref.read_p6(str(tmp_path / "p.ppm"))
     assert got.shape == (24, 32, 3)
     assert np.array_equal(got, ref.present(table, frame, 72, 48, 32, 24, fmt=ref.RGB8))

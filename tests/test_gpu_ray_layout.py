@@ -28,7 +28,6 @@ import frame_sums as fs
 import ptlib
 import scatter_walk
 from ptlib import PtConfig, PtStats, _np_f
-from test_gpu_accumulate import _bind
 from test_gpu_boundary_rays import _new_ctx
 from test_gpu_frame_sums import Out, _accumulate, _render, _saved, assert_frame, assert_planes
 
@@ -44,7 +43,7 @@ KERNEL = {"cornell": "k_pass_cand", "three-spheres": "k_pass_cand", "mesh": "k_p
 
 @pytest.fixture(scope="module")
 def L():
-    L = _bind(ptlib.product())
+    L = ptlib.product()
     assert L.pt_device_count() >= 1, "no HIP device visible: the product has no CPU fallback"
     return L
 

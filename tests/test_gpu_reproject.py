@@ -12,8 +12,8 @@ import pytest
 import kats_camera as kc
 import ptlib
 import reproject_ref as ref
-from ptlib import PtConfig, PtStats
-from reproject_ref import F32, I32, PtReprojectParams
+from ptlib import PtConfig, PtReprojectParams, PtStats
+from reproject_ref import F32, I32
 
 pytestmark = pytest.mark.gpu
 
@@ -108,9 +108,8 @@ class Dev:
 
 @pytest.fixture(scope="module")
 def L():
-    L = ref.bind(ptlib.product())
+    L = ptlib.product()
     assert L.pt_device_count() >= 1
-    L.pt_ctx_render_aov.argtypes = [C.c_void_p, C.POINTER(PtConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     return L
 
 

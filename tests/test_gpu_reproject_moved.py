@@ -17,10 +17,9 @@ import reproject_ref as ref
 import reproject_var_ref as rv
 import test_gpu_reproject as base
 import test_gpu_reproject_var as vbase
-from ptlib import PtConfig
-from reproject_moved_ref import IDENTITY, MARKER, PtObjectMotion
-from reproject_ref import F32, I32, PtReprojectParams
-from reproject_var_ref import PtReprojectVarParams
+from ptlib import PtConfig, PtObjectMotion, PtReprojectParams, PtReprojectVarParams
+from reproject_moved_ref import IDENTITY, MARKER
+from reproject_ref import F32, I32
 
 pytestmark = pytest.mark.gpu
 
@@ -92,13 +91,8 @@ class Dev(vbase.Dev):
 
 @pytest.fixture(scope="module")
 def L():
-    L = mref.bind(ptlib.product())
+    L = ptlib.product()
     assert L.pt_device_count() >= 1
-    L.pt_ctx_render_aov.argtypes = [C.c_void_p, C.POINTER(PtConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.pt_ctx_set_object.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(ptlib.PtObject), C.POINTER(C.c_int)]
-    L.pt_ctx_table_hashes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
-    L.pt_ctx_accumulate.argtypes = [C.c_void_p, C.POINTER(PtConfig)] + [C.c_void_p] * 5 + [C.POINTER(ptlib.PtStats)]
-    L.pt_ctx_accum_info.argtypes = [C.c_void_p, C.POINTER(PtConfig), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     return L
 
 

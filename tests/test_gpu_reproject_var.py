@@ -15,9 +15,8 @@ import ptlib
 import reproject_ref as ref
 import reproject_var_ref as rv
 import test_gpu_reproject as base
-from ptlib import PtConfig
-from reproject_ref import F32, I32, PtReprojectParams
-from reproject_var_ref import PtReprojectVarParams
+from ptlib import PtConfig, PtReprojectParams, PtReprojectVarParams
+from reproject_ref import F32, I32
 
 pytestmark = pytest.mark.gpu
 
@@ -120,9 +119,8 @@ class Dev:
 
 @pytest.fixture(scope="module")
 def L():
-    L = dvr.bind(rv.bind(ptlib.product()))
+    L = ptlib.product()
     assert L.pt_device_count() >= 1
-    L.pt_ctx_render_aov.argtypes = [C.c_void_p, C.POINTER(PtConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     return L
 
 
@@ -346,7 +344,7 @@ def test_leaves_the_context_alone(L):
 def denoise_var(L, d, w, h, color, sigma_var):
     """pt_ctx_denoise_var of the plane `color` with d_error as it stands, guided by albedo, normal and depth: (w*h, 3)"""
     levels, _, sigma_depth = dvr.defaults(L)
-    p = dvr.PtDenoiseVarParams(levels, sigma_var, sigma_depth, 0)
+    p = ptlib.PtDenoiseVarParams(levels, sigma_var, sigma_depth, 0)
     P = d.p
     rc = L.pt_ctx_denoise_var(d.ctx, w, h, C.byref(p), P[color], P["err"], P["albedo"], P["normal"], P["depth"], P["dn"], None)
     assert rc == 0, (rc, L.pt_last_error())

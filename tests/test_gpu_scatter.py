@@ -18,8 +18,9 @@ import boundary_rays
 import kats_scatter as ks
 import lds_layouts
 import ptlib
+from ptlib import PtScatterOut
 import scatter_walk as sw
-from scatter_walk import PtScatterOut, bits
+from scatter_walk import bits
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -28,7 +29,7 @@ MODES = {"all": 0, "defer": sw.DEFER_REFRACT, "refract_only": sw.REFRACT_ONLY}
 
 @pytest.fixture(scope="module")
 def L():
-    L = sw.bind(ptlib.product())
+    L = ptlib.product()
     assert L.pt_device_count() >= 1, "no HIP device visible: the product has no CPU fallback"
     return L
 
@@ -232,7 +233,7 @@ def test_by_rank_refused_without_candidate_tables(L):
     assert L.pt_ctx_create(0, C.byref(c)) == 0, L.pt_last_error()
     try:
         assert L.pt_ctx_set_scene(c, C.byref(sc.cam), sc.objs, sc.n_objs, sc.tris, sc.n_tris) == 0, L.pt_last_error()
-        items = (sw.PtScatterItem * 2)(sw.item((0.05, 0.05, 6), (0, 0, -1), (1, 1, 1), 0, 0, 0, 1),
+        items = (ptlib.PtScatterItem * 2)(sw.item((0.05, 0.05, 6), (0, 0, -1), (1, 1, 1), 0, 0, 0, 1),
                                        sw.item((-3.45, -2.45, 6), (0, 0, -1), (1, 1, 1), 1, 0, 0, 1))
         out = (PtScatterOut * 2)()
         assert L.pt_ctx_scatter(c, 1, sw.BY_RANK, items, None, 2, out) == -1

@@ -12,12 +12,12 @@ import pytest
 
 import ptlib
 import reproject_ref
-from ptlib import PtCamera, PtConfig, PtStats, PtTriangle
+from ptlib import PtAdaptiveInfo, PtAdaptiveParams, PtConfig, PtStats, PtTriangle
 
 pytestmark = pytest.mark.gpu
 
-PT_ERR_INVALID = -1
-NO_BVH = 1
+PT_ERR_INVALID = ptlib.abi.PT_ERR_INVALID
+NO_BVH = ptlib.abi.PT_FLAG_NO_BVH
 W, H, SEED = 48, 32, 11
 F32 = np.float32
 fp = C.POINTER(C.c_float)
@@ -25,38 +25,9 @@ i32p = C.POINTER(C.c_int32)
 u32p = C.POINTER(C.c_uint32)
 
 
-class PtAdaptiveParams(C.Structure):
-    _fields_ = [("tile_error", C.c_float), ("tile", C.c_uint32), ("min_spp", C.c_uint32)]
-
-
-class PtAdaptiveInfo(C.Structure):
-    _fields_ = [("tiles", C.c_uint32), ("tiles_open", C.c_uint32), ("tiles_at_cap", C.c_uint32), ("spp_min", C.c_uint32),
-                ("spp_max", C.c_uint32), ("samples", C.c_uint64), ("mean_error", C.c_double)]
-
-
-def _bind(L):
-    frame = [C.c_void_p, C.POINTER(PtConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PtStats)]
-    L.pt_ctx_set_camera.argtypes = [C.c_void_p, C.POINTER(PtCamera), C.POINTER(C.c_int)]
-    L.pt_ctx_camera_reach.argtypes = [C.c_void_p, fp, fp]
-    L.pt_ctx_reserve_camera_reach.argtypes = [C.c_void_p, fp, fp, C.POINTER(C.c_int)]
-    L.pt_scene_reach.argtypes = [C.POINTER(PtCamera), C.POINTER(ptlib.PtObject), C.c_uint32, C.POINTER(PtTriangle), C.c_uint32, fp, fp]
-    L.pt_ctx_render_aov.argtypes = [C.c_void_p, C.POINTER(PtConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.pt_ctx_accumulate.argtypes = frame
-    L.pt_ctx_accum_info.argtypes = [C.c_void_p, C.POINTER(PtConfig), u32p, u32p]
-    L.pt_ctx_accum_save.argtypes = [C.c_void_p, C.c_char_p]
-    L.pt_ctx_accum_load.argtypes = [C.c_void_p, C.c_char_p]
-    L.pt_ctx_accumulate_adaptive.argtypes = [C.c_void_p, C.POINTER(PtConfig), C.POINTER(PtAdaptiveParams), C.c_void_p, C.c_void_p,
-                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PtStats),
-                                             C.c_void_p]
-    L.pt_ctx_adaptive_info.argtypes = [C.c_void_p, C.POINTER(PtConfig), C.POINTER(PtAdaptiveParams), C.POINTER(PtAdaptiveInfo)]
-    L.pt_ctx_adaptive_save.argtypes = [C.c_void_p, C.c_char_p]
-    L.pt_ctx_adaptive_load.argtypes = [C.c_void_p, C.c_char_p]
-    return L
-
-
 @pytest.fixture(scope="module")
 def L():
-    return _bind(ptlib.product())
+    return ptlib.product()
 
 
 # ------------------------------------------------------------------------------------------------------- scenes and cameras
@@ -207,7 +178,7 @@ class Dev:
         return lo.value, hi.value
 
     def adaptive(self, cfg, par):
-        st, astats = PtStats(), (C.c_uint64 * 64)()  # (pt_adaptive_stats is 288 bytes: not read here)
+        st, astats = PtStats(), ptlib.PtAdaptiveStats()  # (not read here)
         assert self.L.pt_ctx_accumulate_adaptive(self.ctx, C.byref(cfg), C.byref(par), self.bufs[0], None, None, None, None, None, None,
                                                  C.byref(st), astats) == 0, self.L.pt_last_error()
         return self.fetch(0, cfg.width * cfg.height * 3).tobytes()

@@ -16,12 +16,12 @@ import numpy as np
 import pytest
 
 import ptlib
-from ptlib import PtCamera, PtConfig, PtObject, PtStats, PtTriangle
+from ptlib import PtConfig, PtObject, PtStats, PtTriangle
 
 pytestmark = pytest.mark.gpu
 
-PT_ERR_INVALID = -1
-NO_BVH, SEPARATE = 1, 2
+PT_ERR_INVALID = ptlib.abi.PT_ERR_INVALID
+NO_BVH, SEPARATE = ptlib.abi.PT_FLAG_NO_BVH, ptlib.abi.PT_FLAG_SEPARATE_KERNELS
 W, H, SEED = 64, 48, 23
 F32 = np.float32
 fp = C.POINTER(C.c_float)
@@ -36,15 +36,6 @@ INEXACT = (0.1, -1.0 / 3.0, 0.07)
 def L():
     L = ptlib.product()
     frame = [C.c_void_p, C.POINTER(PtConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PtStats)]
-    L.pt_ctx_set_object.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(PtObject), C.POINTER(C.c_int)]
-    L.pt_ctx_table_hashes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
-    L.pt_ctx_set_camera.argtypes = [C.c_void_p, C.POINTER(PtCamera), C.POINTER(C.c_int)]
-    L.pt_ctx_camera_reach.argtypes = [C.c_void_p, fp, fp]
-    L.pt_ctx_reserve_camera_reach.argtypes = [C.c_void_p, fp, fp, C.POINTER(C.c_int)]
-    L.pt_ctx_render_aov.argtypes = [C.c_void_p, C.POINTER(PtConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.pt_ctx_accumulate.argtypes = frame
-    L.pt_ctx_accum_info.argtypes = [C.c_void_p, C.POINTER(PtConfig), u32p, u32p]
-    L.pt_ctx_accum_save.argtypes = [C.c_void_p, C.c_char_p]
     return L
 
 

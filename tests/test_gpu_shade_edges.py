@@ -25,8 +25,9 @@ import pytest
 
 import kats_scatter as ks
 import ptlib
+from ptlib import PtScatterOut
 import scatter_walk as sw
-from scatter_walk import PtScatterOut, bits
+from scatter_walk import bits
 
 f32 = np.float32
 EXTRA_DRAWS = {"r1_last": (0, 5916095), "r2_one": (0, 7511904)}  # name -> (pixel, sample); depth 0, branch 1
@@ -114,7 +115,7 @@ def _sphere_rays(sc):
 
 @pytest.fixture(scope="module")
 def L():
-    L = sw.bind(ptlib.product())
+    L = ptlib.product()
     assert L.pt_device_count() >= 1, "no HIP device visible: the product has no CPU fallback"
     return L
 
@@ -167,7 +168,7 @@ def test_cornell_spheres_at_pole_and_grazing(L):
     t, oid, _, x, nrm = ptlib.oracle_intersect(sc, o, d)
     for r, hit in zip(rays, oid):
         assert hit == r[4], (r[0], hit)  # the ray reaches the sphere it was aimed at
-    items = (sw.PtScatterItem * len(rays))(*[sw.item(o[i], d[i], (1, 1, 1), 40 + i, 2 * i + 1, rays[i][3], 1) for i in range(len(rays))])
+    items = (ptlib.PtScatterItem * len(rays))(*[sw.item(o[i], d[i], (1, 1, 1), 40 + i, 2 * i + 1, rays[i][3], 1) for i in range(len(rays))])
     ctx = C.c_void_p()
     assert L.pt_ctx_create(0, C.byref(ctx)) == 0, L.pt_last_error()
     try:

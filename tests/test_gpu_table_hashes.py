@@ -19,7 +19,6 @@ import pytest
 
 import ptlib
 import test_gpu_set_object as so
-from ptlib import PtCamera, PtObject
 
 pytestmark = pytest.mark.gpu
 
@@ -30,16 +29,6 @@ SPHERE_MOVE = (0.1, 1.0 / 3.0, 0.07)
 MESH_MOVE = (0.125, -0.5, 1.0)
 # lens centres far outside the box pt_ctx_reserve_camera_reach left
 FAR_CAMERA = {"cornell-sphere": ((0.0, 0.5, 40.0), (0.0, -0.0625, -1.0)), "bvh19": ((0.5, 7.0, -200.0), (0.0, -0.3125, 1.0))}
-
-
-def bind(L):
-    fp = C.POINTER(C.c_float)
-    L.pt_ctx_set_object.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(PtObject), C.POINTER(C.c_int)]
-    L.pt_ctx_table_hashes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
-    L.pt_ctx_set_camera.argtypes = [C.c_void_p, C.POINTER(PtCamera), C.POINTER(C.c_int)]
-    L.pt_ctx_camera_reach.argtypes = [C.c_void_p, fp, fp]
-    L.pt_ctx_reserve_camera_reach.argtypes = [C.c_void_p, fp, fp, C.POINTER(C.c_int)]
-    return L
 
 
 def states(L, sid):
@@ -77,7 +66,7 @@ def states(L, sid):
 
 @pytest.fixture(scope="module")
 def L():
-    return bind(ptlib.product())
+    return ptlib.product()
 
 
 @pytest.mark.parametrize("sid", SCENES)
@@ -94,7 +83,7 @@ def test_tables_are_the_recorded_ones(L, sid):
 
 if __name__ == "__main__":
     ptlib.PRODUCT_SO = os.path.abspath(sys.argv[1])
-    lib = bind(ptlib.product())
+    lib = ptlib.product()
     rec = {"commit": sys.argv[2], "scenes": {sid: dict(states(lib, sid)) for sid in SCENES}}
     with open(sys.argv[3] if len(sys.argv) > 3 else GOLDEN, "w") as f:
         json.dump(rec, f, indent=1)

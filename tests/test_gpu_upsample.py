@@ -10,8 +10,8 @@ import pytest
 
 import ptlib
 import upsample_ref as ref
-from ptlib import PtConfig, PtStats
-from upsample_ref import CASES, F32, I32, PARAMS, PtUpsampleParams
+from ptlib import PtConfig, PtStats, PtUpsampleParams
+from upsample_ref import CASES, F32, I32, PARAMS
 
 pytestmark = pytest.mark.gpu
 
@@ -90,9 +90,8 @@ class Dev:
 
 @pytest.fixture(scope="module")
 def L():
-    L = ref.bind(ptlib.product())
+    L = ptlib.product()
     assert L.pt_device_count() >= 1
-    L.pt_ctx_render_aov.argtypes = [C.c_void_p, C.POINTER(PtConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     return L
 
 

@@ -37,8 +37,7 @@ def without_time(path):
 def planes():
     """what the CLI's calls write, made here through the C ABI: the plain frame, and the low-resolution colour with the guides of
     both sizes"""
-    L = ref.bind(ptlib.product())
-    L.pt_ctx_render_aov.argtypes = [C.c_void_p, C.POINTER(PtConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L = ptlib.product()
     sc = ptlib.load_scene_py(ptlib.scene_path("cornell"))
     ctx = C.c_void_p()
     assert L.pt_ctx_create(0, C.byref(ctx)) == 0, L.pt_last_error()
@@ -83,7 +82,6 @@ def planes():
 def written_by_the_library(L, tmp_path, name, rgb, W, H):
     path = str(tmp_path / name)
     rgb = np.ascontiguousarray(rgb, dtype=F32)
-    L.pt_write_ppm.argtypes = [C.c_char_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_char_p, C.c_uint64]
     assert L.pt_write_ppm(path.encode(), rgb.ctypes.data_as(C.c_void_p), W, H, SPP, b"cornell", 0) == 0
     return path
 

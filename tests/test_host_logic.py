@@ -1,6 +1,5 @@
 """Host-side pieces of the device layout that can be checked without a GPU: the round-robin deal of pixels to ray
 streams (pt_device.h: stream_pixel / stream_pixel_count / global_pixel) and the bookkeeping word."""
-import ctypes as C
 import os
 import subprocess
 import textwrap
@@ -240,7 +239,6 @@ def test_bvh_reference_limit():
     """The BVH walkers pack a node index or a leaf code (first pair record << 1 | records - 1: leaves of one or two records) into 26 bits of a queue entry
     (csrc/pt_device.h: WalkQueue, LeafLds); flatten_scene refuses a scene beyond that instead of letting references wrap."""
     L = ptlib.product()
-    L.pt_bvh_refs_fit.argtypes = [C.c_uint64, C.c_uint64]
     assert L.pt_bvh_refs_fit(141, 300) == 1                      # mesh.json
     assert L.pt_bvh_refs_fit((1 << 26) - 1, 1000) == 1
     assert L.pt_bvh_refs_fit(1 << 26, 1000) == 0                 # node indices need 27 bits
@@ -250,7 +248,6 @@ def test_bvh_reference_limit():
 
 def test_build_flags_are_reported():
     L = ptlib.product()
-    L.pt_build_flags.restype = C.c_char_p
     flags = L.pt_build_flags().decode()
     # "<set of the general unit> | flat: <set of k_pass_cand without walks>" (Makefile: MLLVM, MLLVM_FLAT)
     general, sep, flat = flags.partition("| flat:")

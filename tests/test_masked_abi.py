@@ -20,11 +20,11 @@ import pytest
 
 import masked_ref as ref
 import ptlib
-from masked_ref import F32, PtSelectParams
-from ptlib import PtConfig
+from masked_ref import F32
+from ptlib import PtConfig, PtSelectParams
 
 ROOT = ptlib.ROOT
-PT_ERR_INVALID = -1
+PT_ERR_INVALID = ptlib.abi.PT_ERR_INVALID
 SELECT_NAMES = ["ctx", "width", "height", "params", "d_weight", "d_len", "d_mask", "n_selected", "hip_stream"]
 MASKED_NAMES = ["ctx", "cfg", "d_mask", "d_rgb", "hip_stream", "cancel", "stats", "n_pixels"]
 
@@ -36,7 +36,7 @@ def _header(strip=True):
 
 @pytest.fixture(scope="module")
 def L():
-    return ref.bind(ptlib.product())
+    return ptlib.product()
 
 
 # ---------------------------------------------------------------------------------------------------------- the ABI

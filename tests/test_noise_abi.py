@@ -12,29 +12,12 @@ import numpy as np
 
 import noise_ref
 import ptlib
-from ptlib import PtConfig, PtStats
+from ptlib import PtConfig, PtNoiseStats, PtNoiseTarget, PtStats
 
 ROOT = ptlib.ROOT
-PT_ERR_INVALID = -1
+PT_ERR_INVALID = ptlib.abi.PT_ERR_INVALID
 NAMES = ("pt_ctx_accum_track_noise", "pt_ctx_accum_noise", "pt_ctx_accumulate_until", "pt_noise_stats", "pt_noise_target")
 f32 = np.float32
-
-
-class PtNoiseStats(C.Structure):
-    _fields_ = [("spp_min", C.c_uint32), ("spp_max", C.c_uint32), ("spp_a_min", C.c_uint32), ("spp_b_min", C.c_uint32),
-                ("pixels", C.c_uint64), ("mean_error", C.c_double), ("histogram", C.c_uint32 * 64)]
-
-
-class PtNoiseTarget(C.Structure):
-    _fields_ = [("mean_error", C.c_float), ("quantile", C.c_float), ("quantile_error", C.c_float), ("min_spp", C.c_uint32)]
-
-
-def bind(L):
-    L.pt_ctx_accum_track_noise.argtypes = [C.c_void_p, C.c_int]
-    L.pt_ctx_accum_noise.argtypes = [C.c_void_p, C.POINTER(PtConfig), C.c_void_p, C.POINTER(PtNoiseStats), C.c_void_p]
-    L.pt_ctx_accumulate_until.argtypes = [C.c_void_p, C.POINTER(PtConfig), C.POINTER(PtNoiseTarget), C.c_void_p, C.c_void_p,
-                                          C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PtStats), C.POINTER(PtNoiseStats)]
-    return L
 
 
 def _header():
@@ -91,7 +74,7 @@ def test_rust_shim_and_python_binding_offer_them():
 
 
 def test_refusals_without_a_device():
-    L = bind(ptlib.product())
+    L = ptlib.product()
     cfg = PtConfig(64, 40, 256, 0, 1, 0, 0, 0, 0)
     buf = C.c_void_p(256)  # never dereferenced: every call below is refused before a device is touched
     ns, st = PtNoiseStats(), PtStats()

@@ -20,10 +20,11 @@ import pytest
 
 import present_ref as ref
 import ptlib
-from present_ref import F32, ONE_BITS, PtPresentParams
+from ptlib import PtPresentParams
+from present_ref import F32, ONE_BITS
 
 ROOT = ptlib.ROOT
-PT_ERR_INVALID = -1
+PT_ERR_INVALID = ptlib.abi.PT_ERR_INVALID
 SIZE_PAIRS = (((7, 5), (3, 2)), ((8, 8), (4, 4)), ((7, 5), (7, 2)), ((5, 3), (11, 7)), ((67, 33), (1, 1)), ((130, 3), (64, 1)),
               ((257, 129), (100, 50)))
 
@@ -35,7 +36,7 @@ def _header(strip=True):
 
 @pytest.fixture(scope="module")
 def L():
-    return ref.bind(ptlib.product())
+    return ptlib.product()
 
 
 @pytest.fixture(scope="module")

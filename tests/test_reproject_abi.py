@@ -19,11 +19,12 @@ import pytest
 
 import kats_camera as kc
 import ptlib
+from ptlib import PtReprojectParams
 import reproject_ref as ref
-from reproject_ref import F32, I32, PtReprojectParams
+from reproject_ref import F32, I32
 
 ROOT = ptlib.ROOT
-PT_ERR_INVALID = -1
+PT_ERR_INVALID = ptlib.abi.PT_ERR_INVALID
 NO_POSITION = 1
 FRAMES = ((1, 1), (7, 5), (450, 300), (1024, 768))
 DEPTHS = tuple(2.0 ** e for e in range(-3, 7))
@@ -59,7 +60,7 @@ def _header(strip=True):
 
 @pytest.fixture(scope="module")
 def L():
-    return ref.bind(ptlib.product())
+    return ptlib.product()
 
 
 def host_project(L, cam, hist, w, h, idx, depth):

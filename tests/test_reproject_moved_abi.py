@@ -20,14 +20,15 @@ import pytest
 
 import kats_camera as kc
 import ptlib
+from ptlib import PtObjectMotion
 import reproject_moved_ref as mref
 import reproject_ref as ref
-from reproject_moved_ref import IDENTITY, MARKER, PtObjectMotion
+from reproject_moved_ref import IDENTITY, MARKER
 from reproject_ref import F32
 from test_reproject_abi import DEPTHS, FRAMES, PAIRS, _ray64, pixels_of
 
 ROOT = ptlib.ROOT
-PT_ERR_INVALID = -1
+PT_ERR_INVALID = ptlib.abi.PT_ERR_INVALID
 NO_POSITION = 1
 RECORDS = {"translated": (0.07, -0.03, 0.05, 1.0), "scaled": (0.1, 0.0, -0.3, 0.75), "grown": (-0.2, 0.04, 0.0, 1.25)}
 
@@ -39,7 +40,7 @@ def _header(strip=True):
 
 @pytest.fixture(scope="module")
 def L():
-    return mref.bind(ptlib.product())
+    return ptlib.product()
 
 
 def host_project_moved(L, cam, hist, w, h, idx, depth, rec):
@@ -275,7 +276,6 @@ def test_project_moved_host_is_the_restatement(L, name, cam, hist):
 
 
 def test_project_moved_host_identity_is_the_plain_call(L):
-    ref.bind(L)
     for name, cam, hist in PAIRS + [("same", kc.CORNELL_CAM, dict(kc.CORNELL_CAM))]:
         a, b = ref.pt_camera(cam), ref.pt_camera(hist)
         for w, h in FRAMES:

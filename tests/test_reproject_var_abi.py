@@ -20,13 +20,13 @@ import pytest
 
 import kats_camera as kc
 import ptlib
+from ptlib import PtReprojectVarParams
 import reproject_ref as ref
 import reproject_var_ref as rv
 from reproject_ref import F32, I32
-from reproject_var_ref import PtReprojectVarParams
 
 ROOT = ptlib.ROOT
-PT_ERR_INVALID = -1
+PT_ERR_INVALID = ptlib.abi.PT_ERR_INVALID
 CAM = kc.CORNELL_CAM
 REL = 1e-5  # the binary32 rounding of a handful of operations
 
@@ -44,7 +44,7 @@ def _doc():
 
 @pytest.fixture(scope="module")
 def L():
-    return rv.bind(ptlib.product())
+    return ptlib.product()
 
 
 # ---------------------------------------------------------------------------------------------------------- the ABI

@@ -19,11 +19,11 @@ import pytest
 
 import kats_scatter as ks
 import ptlib
+from ptlib import PtScatterItem, PtScatterOut, PtScatterSurface
 import scatter_walk as sw
-from scatter_walk import PtScatterItem, PtScatterOut, PtScatterSurface
 
 ROOT = ptlib.ROOT
-PT_ERR_INVALID, PT_ERR_NO_DEVICE = -1, -2
+PT_ERR_INVALID, PT_ERR_NO_DEVICE = ptlib.abi.PT_ERR_INVALID, ptlib.abi.PT_ERR_NO_DEVICE
 NAMES = ["ctx", "seed", "form", "items", "surfaces", "n", "out"]
 f32 = np.float32
 
@@ -35,7 +35,7 @@ def _header(strip=True):
 
 @pytest.fixture(scope="module")
 def L():
-    return sw.bind(ptlib.product())
+    return ptlib.product()
 
 
 # ---------------------------------------------------------------------------------------------------------- the ABI

@@ -215,9 +215,6 @@ def test_saved_bytes_equal_the_files_the_reference_wrote(sid, tmp_path):
 
 # ---------------------------------------------------------------------------------------------------------------
 # built-in scenes (setup_scenes, scenes.rs:43-318)
-L.pt_scene_builtin.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p)]
-L.pt_builtin_scene_id.restype = C.c_char_p
-L.pt_builtin_scene_id.argtypes = [C.c_uint32]
 BUILTIN_ORDER = ["single-sphere", "cartesian", "two-spheres", "three-spheres", "cornell", "mesh"]
 
 

@@ -19,7 +19,7 @@ import ptlib
 from ptlib import PtObject
 
 ROOT = ptlib.ROOT
-PT_ERR_INVALID = -1
+PT_ERR_INVALID = ptlib.abi.PT_ERR_INVALID
 NEW = ("pt_ctx_set_object", "pt_ctx_table_hashes")
 TABLES = ("OBJS", "OBJ_PAIRS", "TRI_PAIRS", "MATS", "TRI_SHADE", "BVH_NODES", "BVH_NODES4", "SPH_PAIRS", "FLAT_PAIRS", "CAND_PAIRS",
           "RANK_ID", "SURF", "TRI_RANK", "BVH_MESHES")
@@ -79,8 +79,6 @@ def test_rust_shim_and_python_binding_mirror_them():
 
 def test_refusals_without_a_device():
     L = ptlib.product()
-    L.pt_ctx_set_object.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(PtObject), C.POINTER(C.c_int)]
-    L.pt_ctx_table_hashes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     obj = PtObject()
     obj.kind, obj.reflect_type, obj.radius = 9, 9, float("nan")  # everything after the context is wrong too: ctx comes first
     rebuilt = C.c_int(-7)

@@ -19,11 +19,12 @@ import numpy as np
 import pytest
 
 import ptlib
+from ptlib import PtUpsampleParams
 import upsample_ref as ref
-from upsample_ref import F32, I32, PtUpsampleParams
+from upsample_ref import F32, I32
 
 ROOT = ptlib.ROOT
-PT_ERR_INVALID = -1
+PT_ERR_INVALID = ptlib.abi.PT_ERR_INVALID
 AXES = ((1, 1), (7, 3), (3, 7), (257, 129), (33, 33), (16384, 1), (1, 16384))
 NAMES = ["ctx", "width", "height", "lo_width", "lo_height", "params", "d_lo_color", "d_lo_depth", "d_lo_object_id", "d_lo_normal",
          "d_lo_albedo", "d_depth", "d_object_id", "d_normal", "d_albedo", "d_out_color", "d_out_weight", "hip_stream"]
@@ -36,7 +37,7 @@ def _header(strip=True):
 
 @pytest.fixture(scope="module")
 def L():
-    return ref.bind(ptlib.product())
+    return ptlib.product()
 
 
 def host_tap(L, size, lo, coord):

@@ -1,27 +1,16 @@
 """pt_ctx_upsample restated: the contract of include/ptrace.h ("THE ARITHMETIC" of pt_ctx_upsample) in numpy binary32, one numpy
 operation per operation of the contract, over whole frames at once.  Nothing is shared with csrc/pt_upsample.h: the tap position
-is written with // and %.  Also the ctypes prototypes of the entry points, which the tests bind for themselves, and the synthetic
+is written with // and %.  Also the synthetic
 inputs the GPU tests and the CPU test of their coverage share."""
 import ctypes as C
 
 import numpy as np
 
+from ptlib import PtUpsampleParams
+
 F32 = np.float32
 I32 = np.int32
 MAX_SIZE = 1 << 14
-
-
-class PtUpsampleParams(C.Structure):
-    _fields_ = [("depth_tol", C.c_float), ("normal_min", C.c_float), ("flags", C.c_uint32)]
-
-
-def bind(L):
-    L.pt_upsample_defaults.argtypes = [C.POINTER(PtUpsampleParams)]
-    L.pt_ctx_upsample.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(PtUpsampleParams)] + \
-        [C.c_void_p] * 12
-    L.pt_upsample_tap_host.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_float)]
-    L.pt_last_error.restype = C.c_char_p
-    return L
 
 
 def defaults(L):

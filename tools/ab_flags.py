@@ -11,9 +11,7 @@ import numpy as np
 import ptlib
 from ptlib import PtConfig, PtStats
 
-if os.environ.get("PT_LIB"):
-    ptlib.PRODUCT_SO = os.environ["PT_LIB"]
-L = ptlib.product()
+L = ptlib.abi.load(os.environ.get("PT_LIB") or ptlib.PRODUCT_SO)
 W, H = 1024, 768
 
 

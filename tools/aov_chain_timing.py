@@ -28,7 +28,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import ptlib  # noqa: E402
-from ptlib import PtConfig  # noqa: E402
+from ptlib import PtAovParams, PtConfig  # noqa: E402
 
 W, H = 1024, 768
 SPPS = (8, 1)
@@ -37,11 +37,7 @@ BUDGET = 1.10
 BUDGETED = ("mesh",)
 WINDOW_MS = 250.0
 ROUNDS = 5
-THROUGH_DELTA = 1
-
-
-class PtAovParams(C.Structure):
-    _fields_ = [("flags", C.c_uint32), ("max_chain", C.c_uint32)]
+THROUGH_DELTA = ptlib.abi.PT_AOV_THROUGH_DELTA
 
 
 def hip_runtime():
@@ -54,9 +50,6 @@ def hip_runtime():
 
 def main():
     L = ptlib.product()
-    L.pt_kernel_isa_hash.restype = C.c_char_p
-    L.pt_ctx_render_aov.argtypes = [C.c_void_p, C.POINTER(PtConfig)] + [C.c_void_p] * 5
-    L.pt_ctx_render_aov_ex.argtypes = [C.c_void_p, C.POINTER(PtConfig), C.POINTER(PtAovParams)] + [C.c_void_p] * 6
     assert L.pt_device_count() >= 1, "aov_chain_timing needs a GPU: there is nothing to time without one"
     hip = hip_runtime()
     hip.hipEventElapsedTime.argtypes = [C.POINTER(C.c_float), C.c_void_p, C.c_void_p]

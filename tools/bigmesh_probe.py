@@ -11,9 +11,7 @@ import numpy as np
 import ptlib
 from ptlib import PtConfig, PtStats
 
-if os.environ.get("PT_LIB"):
-    ptlib.PRODUCT_SO = os.environ["PT_LIB"]
-L = ptlib.product()
+L = ptlib.abi.load(os.environ.get("PT_LIB") or ptlib.PRODUCT_SO)
 steps = int(sys.argv[1]) if len(sys.argv) > 1 else 256
 spp = int(sys.argv[2]) if len(sys.argv) > 2 else 64
 W = int(sys.argv[3]) if len(sys.argv) > 3 else 1024

@@ -34,9 +34,7 @@ def hip_runtime():
 
 
 def main():
-    L = denoise_ref.bind(ptlib.product())
-    L.pt_ctx_render_aov.argtypes = [C.c_void_p, C.POINTER(PtConfig)] + [C.c_void_p] * 5
-    L.pt_kernel_isa_hash.restype = C.c_char_p
+    L = ptlib.product()
     hip = hip_runtime()
     hip.hipEventElapsedTime.argtypes = [C.POINTER(C.c_float), C.c_void_p, C.c_void_p]
     sc = ptlib.load_scene_py(ptlib.scene_path("cornell"))
@@ -67,7 +65,7 @@ def main():
         assert hip.hipEventCreate(C.byref(e0)) == 0 and hip.hipEventCreate(C.byref(e1)) == 0
 
         def window(levels, n):
-            p = denoise_ref.PtDenoiseParams(levels, 0, 0, 0, 0)
+            p = ptlib.PtDenoiseParams(levels, 0, 0, 0, 0)
             assert hip.hipEventRecord(e0, stream) == 0
             for _ in range(n):
                 assert L.pt_ctx_denoise(ctx, W, H, C.byref(p), color, albedo, normal, depth, out, stream) == 0

@@ -23,17 +23,13 @@ import denoise_ref  # noqa: E402
 import denoise_var_ref  # noqa: E402
 import ptlib  # noqa: E402
 from denoise_timing import hip_runtime  # noqa: E402
-from ptlib import PtConfig, PtStats  # noqa: E402
-from test_noise_abi import PtNoiseStats, bind as bind_noise  # noqa: E402
+from ptlib import PtConfig, PtNoiseStats, PtStats  # noqa: E402
 
 W, H, SPP = 1024, 768, 16
 
 
 def main():
-    L = bind_noise(denoise_var_ref.bind(denoise_ref.bind(ptlib.product())))
-    L.pt_ctx_render_aov.argtypes = [C.c_void_p, C.POINTER(PtConfig)] + [C.c_void_p] * 5
-    L.pt_ctx_accumulate.argtypes = [C.c_void_p, C.POINTER(PtConfig)] + [C.c_void_p] * 5 + [C.POINTER(PtStats)]
-    L.pt_kernel_isa_hash.restype = C.c_char_p
+    L = ptlib.product()
     hip = hip_runtime()
     hip.hipEventElapsedTime.argtypes = [C.POINTER(C.c_float), C.c_void_p, C.c_void_p]
     sc = ptlib.load_scene_py(ptlib.scene_path("cornell"))
@@ -66,9 +62,9 @@ def main():
 
         def call(which, levels):
             if which == "denoise_var":
-                p = denoise_var_ref.PtDenoiseVarParams(levels, 0, 0, 0)
+                p = ptlib.PtDenoiseVarParams(levels, 0, 0, 0)
                 return L.pt_ctx_denoise_var(ctx, W, H, C.byref(p), color, error, albedo, normal, depth, out, stream)
-            p = denoise_ref.PtDenoiseParams(levels, 0, 0, 0, 0)
+            p = ptlib.PtDenoiseParams(levels, 0, 0, 0, 0)
             return L.pt_ctx_denoise(ctx, W, H, C.byref(p), color, albedo, normal, depth, out, stream)
 
         def window(which, levels, n):

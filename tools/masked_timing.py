@@ -36,8 +36,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import masked_ref as ref  # noqa: E402
 import ptlib  # noqa: E402
 import upsample_ref  # noqa: E402
-from masked_ref import PtSelectParams  # noqa: E402
-from ptlib import PtConfig, PtStats  # noqa: E402
+from ptlib import PtConfig, PtSelectParams, PtStats  # noqa: E402
 
 SIZES = ((1024, 768), (4096, 4096))
 WINDOW_MS = 250.0
@@ -47,8 +46,8 @@ LOOP_SIZE = (1024, 768)
 LOOP_SPP = 8
 FRAMES = 7
 COPY_BYTES = 24
-PT_CANCELLED = -4
-MEGAKERNEL = 1
+PT_CANCELLED = ptlib.abi.PT_CANCELLED
+MEGAKERNEL = ptlib.abi.PT_BACKEND_MEGAKERNEL
 
 
 def hip_runtime():
@@ -60,9 +59,7 @@ def hip_runtime():
 
 
 def main():
-    L = upsample_ref.bind(ref.bind(ptlib.product()))
-    L.pt_kernel_isa_hash.restype = C.c_char_p
-    L.pt_ctx_render_aov.argtypes = [C.c_void_p, C.POINTER(PtConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L = ptlib.product()
     assert L.pt_device_count() >= 1, "masked_timing needs a GPU: there is nothing to time without one"
     hip = hip_runtime()
     hip.hipEventElapsedTime.argtypes = [C.POINTER(C.c_float), C.c_void_p, C.c_void_p]

@@ -20,8 +20,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import ptlib  # noqa: E402
-from ptlib import PtConfig, PtStats  # noqa: E402
-from test_noise_abi import PtNoiseStats, bind  # noqa: E402
+from ptlib import PtConfig, PtNoiseStats, PtStats  # noqa: E402
 
 W, H = 1024, 768
 
@@ -43,10 +42,7 @@ def context(L, sc, tracked):
 
 
 def main():
-    L = bind(ptlib.product())
-    L.pt_ctx_accumulate.argtypes = [C.c_void_p, C.POINTER(PtConfig)] + [C.c_void_p] * 5 + [C.POINTER(PtStats)]
-    L.pt_ctx_accum_reset.argtypes = [C.c_void_p]
-    L.pt_kernel_isa_hash.restype = C.c_char_p
+    L = ptlib.product()
     hip = hip_runtime()
     hip.hipEventElapsedTime.argtypes = [C.POINTER(C.c_float), C.c_void_p, C.c_void_p]
     sc = ptlib.load_scene_py(ptlib.scene_path("cornell"))

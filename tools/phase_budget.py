@@ -62,8 +62,7 @@ NAMES = ["other", "load_ray", "spheres", "filter_push", "exact_batch", "finish_b
          "diffuse", "specular", "glass", "append", "glass_defer", "barrier", "bvh_wants", "walk_gate", "walk_box_batch",
          "walk_leaf_batch", "primary_ray", "emit", "push_to_ring", "append_second_ray", "roulette_rescale", "emit_fixed_point_adds"]
 
-ptlib.PRODUCT_SO = os.environ["PT_LIB"]
-L = ptlib.product()
+L = ptlib.abi.load(os.environ["PT_LIB"])
 scene = sys.argv[1] if len(sys.argv) > 1 else "cornell"
 spp = int(sys.argv[2]) if len(sys.argv) > 2 else 256
 out_path = sys.argv[3] if len(sys.argv) > 3 else None
@@ -75,7 +74,6 @@ assert L.pt_ctx_set_scene(ctx, C.byref(sc.cam), sc.objs, sc.n_objs, sc.tris, sc.
 cfg = PtConfig(W, H, spp, 0, 1, 0, 0, 512 << 20, 0, 0, 0, 0, 0)  # (the default pass size, given explicitly: no timed short passes)
 d = C.c_void_p()
 assert L.pt_device_malloc(0, W * H * 12, C.byref(d)) == 0
-L.pt_debug_phase_stats.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_uint32]
 buf = (C.c_ulonglong * 128)()
 st = PtStats()
 for rep in range(3):  # two warm frames (clocks settle), the third is read

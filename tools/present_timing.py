@@ -30,7 +30,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import present_ref  # noqa: E402
 import ptlib  # noqa: E402
-from present_ref import PtPresentParams  # noqa: E402
 
 CASES = (("1024x768 same size", (1024, 768), (0, 0), 1.0), ("4096x4096 same size", (4096, 4096), (0, 0), 1.0),
          ("4096x4096 -> 1024x1024", (4096, 4096), (1024, 1024), 2.0),
@@ -73,8 +72,7 @@ def host_loop(tmp):
 
 
 def main():
-    L = present_ref.bind(ptlib.product())
-    L.pt_kernel_isa_hash.restype = C.c_char_p
+    L = ptlib.product()
     assert L.pt_device_count() >= 1, "present_timing needs a GPU: there is nothing to time without one"
     hip = hip_runtime()
     hip.hipEventElapsedTime.argtypes = [C.POINTER(C.c_float), C.c_void_p, C.c_void_p]
@@ -118,7 +116,7 @@ def main():
         for p, nbytes in ((d_rgb, npix * 12), (d_copy, npix * 12), (d_out, (ow or w) * (oh or h) * 4)):
             assert L.pt_device_malloc(0, nbytes, C.byref(p)) == 0, L.pt_last_error()
         assert hip.hipMemcpy(d_rgb, frame.ctypes.data_as(C.c_void_p), frame.nbytes, 1) == 0
-        pp = PtPresentParams(ow, oh, 0.0, present_ref.RGBA8, 0)
+        pp = ptlib.PtPresentParams(ow, oh, 0.0, present_ref.RGBA8, 0)
 
         def present():
             assert L.pt_ctx_present(ctx, w, h, C.byref(pp), d_rgb, d_out, stream) == 0, L.pt_last_error()

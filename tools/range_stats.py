@@ -12,8 +12,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 import ptlib
 from ptlib import PtConfig, PtStats
 
-ptlib.PRODUCT_SO = os.environ["PT_LIB"]
-L = ptlib.product()
+L = ptlib.abi.load(os.environ["PT_LIB"])
 scene = sys.argv[1] if len(sys.argv) > 1 else "cornell"
 spp = int(sys.argv[2]) if len(sys.argv) > 2 else 64
 backend = int(sys.argv[3]) if len(sys.argv) > 3 else 0
@@ -31,7 +30,6 @@ assert L.pt_ctx_render(ctx, C.byref(cfg), d, None, None, None, None, C.byref(st)
 total = [[0, 0] for _ in SITES]
 for unit in ("flat", "main", "tile"):
     fn = getattr(L, "pt_debug_range_stats_" + unit)
-    fn.argtypes = [C.POINTER(C.c_ulonglong), C.c_uint32]
     out = (C.c_ulonglong * (2 * len(SITES)))()
     assert fn(out, len(out)) == len(SITES)
     for i in range(len(SITES)):

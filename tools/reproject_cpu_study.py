@@ -35,7 +35,7 @@ TRUTH_SPP = 4096
 MAX_HISTORY = (8.0, 16.0, 32.0, 64.0)
 DEPTH_TOL = (0.015625, 0.03125, 0.0625, 0.125, 0.25)
 NORMAL_MIN = (0.25, 0.5, 0.75, 0.9)
-DIFFUSE = 0
+DIFFUSE = ptlib.abi.PT_DIFFUSE
 
 
 def scene_at(cam):

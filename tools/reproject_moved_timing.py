@@ -33,8 +33,6 @@ import ptlib  # noqa: E402
 import reproject_moved_ref as mref  # noqa: E402
 import reproject_ref as ref  # noqa: E402
 from reproject_moved_ref import IDENTITY  # noqa: E402
-from reproject_ref import PtReprojectParams  # noqa: E402
-from reproject_var_ref import PtReprojectVarParams  # noqa: E402
 
 SIZES = ((1024, 768), (4096, 4096))
 WINDOW_MS = 250.0
@@ -51,8 +49,7 @@ def hip_runtime():
 
 
 def main():
-    L = mref.bind(ptlib.product())
-    L.pt_kernel_isa_hash.restype = C.c_char_p
+    L = ptlib.product()
     assert L.pt_device_count() >= 1, "reproject_moved_timing needs a GPU: there is nothing to time without one"
     hip = hip_runtime()
     hip.hipEventElapsedTime.argtypes = [C.POINTER(C.c_float), C.c_void_p, C.c_void_p]
@@ -113,8 +110,8 @@ def main():
         pixel = DEPTH * cam_d["sensor_width"] / cam_d["focal_length"] / w  # a pixel's width on the plane
         tables = {"identity": [IDENTITY] * 3, "one-object": [IDENTITY, IDENTITY, (3.0 * pixel, 0.0, 0.0, 1.0)],
                   "all-moved": [IDENTITY, (0.4 * pixel, 0.0, 0.0, 1.0), (0.4 * pixel, 0.0, 0.0, 1.0)]}
-        pp = PtReprojectParams(8, 0.0, 0.0, 0.0, 0)
-        pv = PtReprojectVarParams(8, 0.0, 0.0, 0.0, 0, 0, 0)
+        pp = ptlib.PtReprojectParams(8, 0.0, 0.0, 0.0, 0)
+        pv = ptlib.PtReprojectVarParams(8, 0.0, 0.0, 0.0, 0, 0, 0)
         guides = (B["color"], B["depth"], B["oid"], B["normal"])
 
         def plain():

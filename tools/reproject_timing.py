@@ -26,7 +26,6 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import kats_camera  # noqa: E402
 import ptlib  # noqa: E402
 import reproject_ref as ref  # noqa: E402
-from reproject_ref import PtReprojectParams  # noqa: E402
 
 CASES = (("1024x768 with normals", (1024, 768), True, 3.5), ("1024x768 without normals", (1024, 768), False, 2.5),
          ("4096x4096 with normals", (4096, 4096), True, 3.5), ("4096x4096 without normals", (4096, 4096), False, 2.5))
@@ -43,8 +42,7 @@ def hip_runtime():
 
 
 def main():
-    L = ref.bind(ptlib.product())
-    L.pt_kernel_isa_hash.restype = C.c_char_p
+    L = ptlib.product()
     assert L.pt_device_count() >= 1, "reproject_timing needs a GPU: there is nothing to time without one"
     hip = hip_runtime()
     hip.hipEventElapsedTime.argtypes = [C.POINTER(C.c_float), C.c_void_p, C.c_void_p]
@@ -104,7 +102,7 @@ def main():
                 assert L.pt_device_malloc(0, v.nbytes, C.byref(bufs[k])) == 0, L.pt_last_error()
                 assert hip.hipMemcpy(bufs[k], v.ctypes.data_as(C.c_void_p), v.nbytes, 1) == 0
             del planes
-        pp = PtReprojectParams(8, 0.0, 0.0, 0.0, 0)
+        pp = ptlib.PtReprojectParams(8, 0.0, 0.0, 0.0, 0)
         B = bufs
 
         def reproject():

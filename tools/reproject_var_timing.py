@@ -28,8 +28,6 @@ import kats_camera  # noqa: E402
 import ptlib  # noqa: E402
 import reproject_ref as ref  # noqa: E402
 import reproject_var_ref as rv  # noqa: E402
-from reproject_ref import PtReprojectParams  # noqa: E402
-from reproject_var_ref import PtReprojectVarParams  # noqa: E402
 
 SIZES = ((1024, 768), (4096, 4096))
 BUDGET = 1.5
@@ -47,8 +45,7 @@ def hip_runtime():
 
 
 def main():
-    L = rv.bind(ptlib.product())
-    L.pt_kernel_isa_hash.restype = C.c_char_p
+    L = ptlib.product()
     assert L.pt_device_count() >= 1, "reproject_var_timing needs a GPU: there is nothing to time without one"
     hip = hip_runtime()
     hip.hipEventElapsedTime.argtypes = [C.POINTER(C.c_float), C.c_void_p, C.c_void_p]
@@ -102,9 +99,9 @@ def main():
             assert L.pt_device_malloc(0, v.nbytes, C.byref(B[k])) == 0, L.pt_last_error()
             assert hip.hipMemcpy(B[k], v.ctypes.data_as(C.c_void_p), v.nbytes, 1) == 0
         del planes
-        pp = PtReprojectParams(WEIGHT, 0.0, 0.0, 0.0, 0)
-        steady_p = PtReprojectVarParams(WEIGHT, 0.0, 0.0, 0.0, 1, 0, 0)
-        first_p = PtReprojectVarParams(WEIGHT, 0.0, 0.0, 0.0, 0, 0, 0)
+        pp = ptlib.PtReprojectParams(WEIGHT, 0.0, 0.0, 0.0, 0)
+        steady_p = ptlib.PtReprojectVarParams(WEIGHT, 0.0, 0.0, 0.0, 1, 0, 0)
+        first_p = ptlib.PtReprojectVarParams(WEIGHT, 0.0, 0.0, 0.0, 0, 0, 0)
 
         def reproject():
             rc = L.pt_ctx_reproject(ctx, w, h, C.byref(pp), C.byref(cam), B["color"], B["depth"], B["oid"], B["normal"], C.byref(hist_cam),

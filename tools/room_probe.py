@@ -9,9 +9,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 import ptlib
 from ptlib import PtConfig, PtStats
 
-if os.environ.get("PT_LIB"):
-    ptlib.PRODUCT_SO = os.environ["PT_LIB"]
-L = ptlib.product()
+L = ptlib.abi.load(os.environ.get("PT_LIB") or ptlib.PRODUCT_SO)
 scene = sys.argv[1] if len(sys.argv) > 1 else "mesh"
 spp = int(sys.argv[2]) if len(sys.argv) > 2 else 256
 W, H = 1024, 768

@@ -83,10 +83,7 @@ def stats(ms):
 
 def main():
     args = [a for a in sys.argv[1:] if a != "--big"]
-    L = upsample_ref.bind(ptlib.product())
-    L.pt_kernel_isa_hash.restype = C.c_char_p
-    L.pt_ctx_render_aov.argtypes = [C.c_void_p, C.POINTER(PtConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.pt_ctx_set_camera.argtypes = [C.c_void_p, C.POINTER(PtCamera), C.POINTER(C.c_int)]
+    L = ptlib.product()
     assert L.pt_device_count() >= 1, "set_camera_timing needs a GPU: the uploads are what nobody has measured"
     mesh = ptlib.load_scene_py(ptlib.scene_path("mesh"))
     scenes = [ptlib.load_scene_py(ptlib.scene_path("cornell")), mesh, Generated(L, mesh, 100)]

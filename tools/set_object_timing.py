@@ -41,10 +41,7 @@ F32 = np.float32
 def main():
     big = "--big" in sys.argv[1:]
     args = [a for a in sys.argv[1:] if a != "--big"]
-    L = upsample_ref.bind(ptlib.product())
-    L.pt_kernel_isa_hash.restype = C.c_char_p
-    L.pt_ctx_render_aov.argtypes = [C.c_void_p, C.POINTER(PtConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.pt_ctx_set_object.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(PtObject), C.POINTER(C.c_int)]
+    L = ptlib.product()
     assert L.pt_device_count() >= 1, "set_object_timing needs a GPU: the refit is what nobody has measured"
     mesh = ptlib.load_scene_py(ptlib.scene_path("mesh"))
     scenes = [mesh, Generated(L, mesh, 100)] + ([Generated(L, mesh, 566)] if big else [])

@@ -23,11 +23,8 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 import ptlib
 from ptlib import PtConfig, PtStats
 
-if os.environ.get("PT_LIB"):
-    ptlib.PRODUCT_SO = os.environ["PT_LIB"]
-L = ptlib.product()
+L = ptlib.abi.load(os.environ.get("PT_LIB") or ptlib.PRODUCT_SO)
 assert hasattr(L, "pt_debug_tail_stats"), "not a -DPT_TAIL_STATS build: make -C path-tracer-rust_amd tail, PT_LIB=scratch/libptrace_tail.so"
-L.pt_debug_tail_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
 W, H, CAP = 1024, 768, 1 << 18
 
 sc = ptlib.load_scene_py(ptlib.scene_path(scene))

@@ -59,9 +59,7 @@ def compulsory_bytes(W, H, w, h, normals, albedo):
 
 
 def main():
-    L = ref.bind(ptlib.product())
-    L.pt_kernel_isa_hash.restype = C.c_char_p
-    L.pt_ctx_render_aov.argtypes = [C.c_void_p, C.POINTER(PtConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L = ptlib.product()
     assert L.pt_device_count() >= 1, "upsample_timing needs a GPU: there is nothing to time without one"
     hip = hip_runtime()
     hip.hipEventElapsedTime.argtypes = [C.POINTER(C.c_float), C.c_void_p, C.c_void_p]

@@ -9,8 +9,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 import ptlib
 from ptlib import PtConfig, PtStats
 
-ptlib.PRODUCT_SO = os.environ["PT_LIB"]
-L = ptlib.product()
+L = ptlib.abi.load(os.environ["PT_LIB"])
 scene = sys.argv[1] if len(sys.argv) > 1 else "mesh"
 spp = int(sys.argv[2]) if len(sys.argv) > 2 else 16
 W, H = 1024, 768
@@ -24,7 +23,6 @@ assert L.pt_device_malloc(0, W * H * 12, C.byref(d)) == 0
 st = PtStats()
 assert L.pt_ctx_render(ctx, C.byref(cfg), d, None, None, None, None, C.byref(st)) == 0, L.pt_last_error()
 out = (C.c_ulonglong * 16)()
-L.pt_debug_walk_stats.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong)]
 assert L.pt_debug_walk_stats(ctx, out) == 0
 v = list(out)
 names = ["walks", "box_batches", "items", "node_items", "popped_live", "leaf_batches", "leaf_tests", "rays", "parked",
