@@ -179,6 +179,29 @@ def test_abi_py_is_the_only_description():
     assert bad == []
 
 
+HARNESS = {"Dev", "Out", "_new_ctx", "_set_scene", "_render", "_accumulate", "cfg_of", "read_pfm", "pfm_to_framebuffer", "scene"}
+
+
+def test_gpudev_is_the_only_device_harness():
+    """Outside tests/gpudev.py no test or tool finds the HIP runtime for itself or binds hipMemcpy, and none imports a harness name
+    from a test module."""
+    files = [p for d in ("tests", "tools") for p in glob.glob(os.path.join(ptlib.ROOT, d, "*.py"))]
+    assert len(files) > 100 and os.path.join(ptlib.ROOT, "tests", "gpudev.py") in files
+    bad = []
+    for path in files:
+        text, rel = open(path).read(), os.path.relpath(path, ptlib.ROOT)
+        if os.path.basename(path) != "gpudev.py":
+            for what, pattern in (("reads /proc/self/maps", r"open\(\s*[\"']/proc/self/maps"), ("defines hip_runtime", r"def\s+_?hip_runtime\b"),
+                                  ("assigns hipMemcpy.argtypes", r"hipMemcpy\.argtypes\s*=(?!=)")):
+                if re.search(pattern, text):
+                    bad.append("%s %s" % (rel, what))
+        for node in ast.walk(ast.parse(text)):
+            if isinstance(node, ast.ImportFrom) and (node.module or "").startswith("test_"):
+                for name in sorted(HARNESS & {a.name for a in node.names}):
+                    bad.append("%s imports %s from %s" % (rel, name, node.module))
+    assert bad == []
+
+
 def test_declare_names_every_missing_symbol():
     with pytest.raises(AttributeError) as e:
         abi.declare(O)  # the oracle exports none of them

@@ -146,7 +146,8 @@ def test_cli_refuses_a_bad_chain_length(tmp_path):
 def test_restatement_statistics_of_the_test_scenes():
     """64x40, seed 8, sample 0: the counts tests/test_gpu_aov_chain.py's preconditions rest on, from the oracle alone"""
     import aov_chain_ref as R
-    from test_gpu_aov import call_pixels, scene
+    from gpudev import scene
+    from test_gpu_aov import call_pixels
 
     px = call_pixels(64, 40)
     all_mirror = R.with_reflect(scene("cornell"), lambda i, o: 1 if not any(o.emission) else None)

@@ -8,8 +8,10 @@ import subprocess
 import numpy as np
 import pytest
 
+import gpudev
 import ptlib
-from ptlib import PtConfig, PtStats
+from gpudev import L  # noqa: F401  (fixture)
+from ptlib import PtStats
 
 pytestmark = pytest.mark.gpu
 
@@ -20,68 +22,28 @@ W, H, SEED = 64, 40, 8
 TOL = 1e-4
 
 
-class Dev:
+class Dev(gpudev.Device):
     """One context, one scene, one device output buffer large enough for the call."""
 
     def __init__(self, L, sc, npix_max):
-        self.L, self.sc = L, sc
-        self.ctx = C.c_void_p()
-        assert L.pt_ctx_create(0, C.byref(self.ctx)) == 0, L.pt_last_error()
-        self.set_scene(sc)
-        self.nbytes = npix_max * 12
-        self.d_out, self.d_snap = C.c_void_p(), C.c_void_p()
-        assert L.pt_device_malloc(0, self.nbytes, C.byref(self.d_out)) == 0
-        assert L.pt_device_malloc(0, self.nbytes, C.byref(self.d_snap)) == 0
+        super().__init__(L, sc)
+        self.d_out, self.d_snap = self.alloc(npix_max * 12), self.alloc(npix_max * 12)
 
-    def set_scene(self, sc):
-        self.sc = sc
-        assert self.L.pt_ctx_set_scene(self.ctx, C.byref(sc.cam), sc.objs, sc.n_objs, sc.tris, sc.n_tris) == 0, \
-            self.L.pt_last_error()
-
-    def download(self, ptr, npix):
-        host = np.zeros((npix, 3), dtype=np.float32)
-        assert self.L.pt_device_download(0, host.ctypes.data_as(C.c_void_p), ptr, npix * 12) == 0
-        return host
-
-    def render(self, cfg):
+    def render(self, cfg, ptr=None, **kw):
         """direct: pt_ctx_render, (image, stats)"""
-        st = PtStats()
-        assert self.L.pt_ctx_render(self.ctx, C.byref(cfg), self.d_out, None, None, None, None, C.byref(st)) == 0, \
-            self.L.pt_last_error()
-        return self.download(self.d_out, self.L.pt_config_pixels(C.byref(cfg))), st
+        return super().render(cfg, ptr or self.d_out, **kw)
 
-    def accumulate(self, cfg, cancel=None, cb=None, want=0):
-        st = PtStats()
-        rc = self.L.pt_ctx_accumulate(self.ctx, C.byref(cfg), self.d_out, None, C.cast(cancel, C.c_void_p) if cancel else None,
-                                      C.cast(cb, C.c_void_p) if cb else None, None, C.byref(st))
-        assert rc == want, (rc, self.L.pt_last_error())
-        return self.download(self.d_out, self.L.pt_config_pixels(C.byref(cfg))), st
+    def accumulate(self, cfg, **kw):
+        return self.render(cfg, accumulate=True, **kw)
 
     def info(self, cfg):
         lo, hi = C.c_uint32(), C.c_uint32()
         assert self.L.pt_ctx_accum_info(self.ctx, C.byref(cfg), C.byref(lo), C.byref(hi)) == 0, self.L.pt_last_error()
         return lo.value, hi.value
 
-    def close(self):
-        self.L.pt_device_free(0, self.d_out)
-        self.L.pt_device_free(0, self.d_snap)
-        self.L.pt_ctx_destroy(self.ctx)
 
-
-def cfg_of(spp, backend=WAVE, seed=SEED, w=W, h=H, flags=0, rays_per_pass=0, band=None, chunks=None):
-    cfg = PtConfig(w, h, spp, backend, seed, 0, 0, rays_per_pass, flags)
-    if band:
-        cfg.idx_begin, cfg.idx_end = band
-    if chunks:
-        cfg.chunk_pixels, cfg.chunk_first, cfg.chunk_step = chunks
-    return cfg
-
-
-@pytest.fixture(scope="module")
-def L():
-    L = ptlib.product()
-    assert L.pt_device_count() >= 1, "no HIP device visible: the product has no CPU fallback"
-    return L
+def cfg_of(spp, backend=WAVE, seed=SEED, w=W, h=H, **kw):
+    return gpudev.config(w, h, spp, backend=backend, seed=seed, **kw)
 
 
 @pytest.fixture(scope="module")
@@ -120,8 +82,7 @@ def test_refinement_equals_one_call(dev):
 @pytest.mark.parametrize("scene", ["cornell", "mesh"])
 def test_switching_backend_and_scan_between_calls(L, request, scene):
     sc = request.getfixturevalue(scene)
-    d = Dev(L, sc, W * H)
-    try:
+    with Dev(L, sc, W * H) as d:
         npix = W * H
         steps = [(2, WAVE, 0, 0), (5, MEGA, 0, npix), (9, WAVE, SEPARATE, 2 * npix), (12, WAVE, 0, npix),
                  (16, MEGA, 0, 0)]
@@ -136,8 +97,6 @@ def test_switching_backend_and_scan_between_calls(L, request, scene):
         assert np.array_equal(img, direct)
         direct_mega, _ = d.render(cfg_of(prev, MEGA))
         assert np.array_equal(img, direct_mega)
-    finally:
-        d.close()
 
 
 @pytest.mark.parametrize("backend", [WAVE, MEGA])
@@ -150,7 +109,7 @@ def test_cancel_and_resume(dev, backend):
         if frac >= 0.4 and not flag[0]:
             n = C.c_uint32()
             assert L.pt_ctx_snapshot(dev.ctx, dev.d_snap, C.byref(n)) == 0, L.pt_last_error()
-            snaps.append((n.value, dev.download(dev.d_snap, npix)))
+            snaps.append((n.value, dev.pixels(dev.d_snap, npix)))
             flag[0] = 1
 
     cb = ptlib.PROGRESS_FN(on_progress)
@@ -180,8 +139,7 @@ def test_calls_in_parts(L, cornell, tmp_path):
     the megakernel on the uneven counts - gives the direct frame."""
     w, h = 2048, 1040  # 2 129 920 pixels: parts of 1 048 576 + 1 048 576 + 32 768
     npix, part = w * h, 1 << 20
-    d = Dev(L, cornell, npix)
-    try:
+    with Dev(L, cornell, npix) as d:
         _, st = d.accumulate(cfg_of(2, w=w, h=h))
         assert st.samples == 2 * npix and d.info(cfg_of(2, w=w, h=h)) == (2, 2)
         flag = (C.c_uint8 * 1)(0)
@@ -191,7 +149,7 @@ def test_calls_in_parts(L, cornell, tmp_path):
             if frac > 0.5 and not flag[0]:  # (part one ends at 0.49 of the call)
                 n = C.c_uint32()
                 assert L.pt_ctx_snapshot(d.ctx, d.d_snap, C.byref(n)) == 0, L.pt_last_error()
-                snaps.append((n.value, d.download(d.d_snap, npix)))
+                snaps.append((n.value, d.pixels(d.d_snap, npix)))
                 flag[0] = 1
 
         cb = ptlib.PROGRESS_FN(on_progress)
@@ -222,8 +180,6 @@ def test_calls_in_parts(L, cornell, tmp_path):
         img, st = d.accumulate(cfg_of(T, MEGA, w=w, h=h))
         assert st.samples == part * (T - k) + (npix - 2 * part) * (T - 2)
         assert np.array_equal(img, direct)
-    finally:
-        d.close()
 
 
 @pytest.mark.parametrize("kind", ["band", "chunks"])
@@ -285,8 +241,7 @@ def test_checkpoint_round_trip_and_damaged_files(L, cornell, mesh, tmp_path):
     d.close()
     data = path.read_bytes()
     assert data[:8] == b"PTACCUM1" and len(data) == 68 + 4 + 24 * W * H + 8
-    d = Dev(L, cornell, W * H)
-    try:
+    with Dev(L, cornell, W * H) as d:
         assert d.info(cfg_of(12)) == (0, 0)
         assert L.pt_ctx_accum_load(d.ctx, str(path).encode()) == 0, L.pt_last_error()
         assert d.info(cfg_of(12)) == (5, 5)
@@ -311,8 +266,6 @@ def test_checkpoint_round_trip_and_damaged_files(L, cornell, mesh, tmp_path):
         d.set_scene(mesh)
         assert L.pt_ctx_accum_load(d.ctx, str(path).encode()) == PT_ERR_INVALID
         assert d.info(cfg_of(12)) == (0, 0)
-    finally:
-        d.close()
 
 
 def test_three_calls_against_the_oracle(dev, cornell):

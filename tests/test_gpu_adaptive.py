@@ -7,11 +7,12 @@ import numpy as np
 import pytest
 
 import adaptive_ref
+import gpudev
 import noise_ref
 import ptlib
+from gpudev import L  # noqa: F401  (fixture)
 from ptlib import PtAdaptiveParams, PtAdaptiveStats, PtStats
 from test_gpu_accumulate import MEGA, NO_BVH
-from test_gpu_accumulate import cfg_of as cfg_small
 from test_gpu_noise import NDev
 
 pytestmark = pytest.mark.gpu
@@ -21,16 +22,8 @@ W, H, TILE, TILE_ERROR, CAP, SEED = 96, 64, 8, 0.08, 256, 8
 f32 = np.float32
 
 
-def cfg_of(spp, backend=MEGA, w=W, h=H, **kw):
-    """test_gpu_accumulate's cfg_of at this module's frame size"""
-    return cfg_small(spp, backend, w=w, h=h, **kw)
-
-
-@pytest.fixture(scope="module")
-def L():
-    L = ptlib.product()
-    assert L.pt_device_count() >= 1, "no HIP device visible: the product has no CPU fallback"
-    return L
+def cfg_of(spp, backend=MEGA, seed=SEED, w=W, h=H, **kw):
+    return gpudev.config(w, h, spp, backend=backend, seed=seed, **kw)
 
 
 @pytest.fixture(scope="module")
@@ -43,8 +36,7 @@ class ADev(NDev):
 
     def __init__(self, L, sc, npix_max, tracked=False):
         super().__init__(L, sc, npix_max, tracked=tracked)
-        self.d_spp = C.c_void_p()
-        assert L.pt_device_malloc(0, npix_max * 4, C.byref(self.d_spp)) == 0
+        self.d_spp = self.alloc(npix_max * 4)
 
     def adaptive(self, cfg, tile_error, tile=TILE, min_spp=0, want=0, cancel=None, cb=None, maps=True):
         par, st, ast = PtAdaptiveParams(tile_error, tile, min_spp), PtStats(), PtAdaptiveStats()
@@ -57,13 +49,8 @@ class ADev(NDev):
         n = self.L.pt_config_pixels(C.byref(cfg))
         spp, err = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=f32)
         if maps:
-            assert self.L.pt_device_download(0, spp.ctypes.data_as(C.c_void_p), self.d_spp, n * 4) == 0
-            assert self.L.pt_device_download(0, err.ctypes.data_as(C.c_void_p), self.d_err, n * 4) == 0
-        return dict(img=self.download(self.d_out, n), spp=spp, err=err, st=st, ast=ast)
-
-    def close(self):
-        self.L.pt_device_free(0, self.d_spp)
-        super().close()
+            spp, err = self.download(self.d_spp, n, np.uint32), self.download(self.d_err, n)
+        return dict(img=self.pixels(self.d_out, n), spp=spp, err=err, st=st, ast=ast)
 
 
 _uniform = {}
@@ -126,11 +113,8 @@ CASES = [("cornell", 0), ("mesh", 0), ("mesh", NO_BVH)]
 @pytest.mark.parametrize("sid,flags", CASES)
 def test_pixels_decisions_and_a_really_adaptive_frame(L, scenes, sid, flags):
     u = uniform(L, scenes, sid, flags)
-    d = ADev(L, scenes[sid], W * H)
-    try:
+    with ADev(L, scenes[sid], W * H) as d:
         r = d.adaptive(cfg_of(CAP, flags=flags), TILE_ERROR)
-    finally:
-        d.close()
     check_pixels(r, u)
     want = check_replay(r, u, W, H, TILE, TILE_ERROR)
     # test 3, on the replay built from the uniform frames (not on the code under test): the frame is really adaptive
@@ -148,12 +132,9 @@ def test_pixels_decisions_and_a_really_adaptive_frame(L, scenes, sid, flags):
 @pytest.mark.parametrize("sid,flags", CASES)
 def test_ends_of_the_range(L, scenes, sid, flags):
     u = uniform(L, scenes, sid, flags)
-    d = ADev(L, scenes[sid], W * H)
-    try:
+    with ADev(L, scenes[sid], W * H) as d:
         r0 = d.adaptive(cfg_of(CAP, flags=flags), 0.0)
         r12 = d.adaptive(cfg_of(CAP, flags=flags), 12.0)
-    finally:
-        d.close()
     # tile_error 0: nothing closes unless E is 0; every pixel of a tile still open is pt_ctx_render's at the cap
     check_pixels(r0, u)
     check_replay(r0, u, W, H, TILE, 0.0)
@@ -172,13 +153,10 @@ def test_ends_of_the_range(L, scenes, sid, flags):
 def test_partial_tiles_on_both_edges(L, scenes):
     w, h, tile, cap, te = 100, 70, 16, 64, 0.12  # 7 x 5 tiles, the right column 4 wide, the bottom row 6 high
     u = uniform(L, scenes, "cornell", 0, w=w, h=h, cap=cap)
-    d = ADev(L, scenes["cornell"], w * h)
-    try:
+    with ADev(L, scenes["cornell"], w * h) as d:
         r = d.adaptive(cfg_of(cap, w=w, h=h), te, tile=tile)
         r4 = d.adaptive(cfg_of(cap, w=w, h=h), te, tile=4)
         r32 = d.adaptive(cfg_of(cap, w=w, h=h), te, tile=32)
-    finally:
-        d.close()
     assert r["ast"].tiles == 35
     for res, t in ((r, tile), (r4, 4), (r32, 32)):
         check_pixels(res, u)
@@ -188,8 +166,7 @@ def test_partial_tiles_on_both_edges(L, scenes):
 def test_a_band_of_whole_rows_and_the_band_refusals(L, scenes):
     band = (20 * W, 46 * W)  # 26 rows from row 20: tiles are counted from the band's first row (3 full tile rows and 2 rows)
     u = uniform(L, scenes, "mesh", 0, band=band, cap=64)
-    d = ADev(L, scenes["mesh"], W * H)
-    try:
+    with ADev(L, scenes["mesh"], W * H) as d:
         r = d.adaptive(cfg_of(64, band=band), 0.12)
         assert r["ast"].tiles == 12 * 4 and len(r["spp"]) == 26 * W
         check_pixels(r, u)
@@ -199,8 +176,6 @@ def test_a_band_of_whole_rows_and_the_band_refusals(L, scenes):
                           (cfg_of(0), "")):
             assert d.adaptive(cfg, 0.1, want=PT_ERR_INVALID) is None
             assert text in L.pt_last_error().decode(), (text, L.pt_last_error())
-    finally:
-        d.close()
 
 
 def test_cancel_between_levels(L, scenes):
@@ -234,8 +209,7 @@ def test_cancel_between_levels(L, scenes):
 
 def test_isolation_from_the_held_frame_and_between_calls(L, scenes):
     u = uniform(L, scenes, "cornell", 0)
-    d = ADev(L, scenes["cornell"], W * H)
-    try:
+    with ADev(L, scenes["cornell"], W * H) as d:
         d.accumulate(cfg_of(8, w=W, h=H))
         assert d.info(cfg_of(8, w=W, h=H)) == (8, 8)
         a = d.adaptive(cfg_of(CAP), TILE_ERROR)
@@ -250,8 +224,6 @@ def test_isolation_from_the_held_frame_and_between_calls(L, scenes):
         assert np.array_equal(a["img"].view(np.uint32), b["img"].view(np.uint32))
         for x in (b, c):
             assert (x["st"].samples, x["st"].ray_bounces, x["ast"].mean_error) == (a["st"].samples, a["st"].ray_bounces, a["ast"].mean_error)
-    finally:
-        d.close()
 
 
 def test_the_tile_pass_rounds_are_counted(L, scenes):
@@ -259,12 +231,9 @@ def test_the_tile_pass_rounds_are_counted(L, scenes):
     level of 16 samples (min_spp = cap = 16; tile_error 0 leaves every tile open), rays_per_pass = 4096: the level's runs are [0, 8)
     and [8, 16), each over 16 tiles x 64 = 1024 entries in rounds of 4096 / 1024 = 4 samples - two launches per run, four in all."""
     w = h = 32
-    d = ADev(L, scenes["cornell"], w * h)
-    try:
+    with ADev(L, scenes["cornell"], w * h) as d:
         r = d.adaptive(cfg_of(16, w=w, h=h, rays_per_pass=4096), 0.0, min_spp=16)
         whole = d.adaptive(cfg_of(16, w=w, h=h), 0.0, min_spp=16)
-    finally:
-        d.close()
     assert r["ast"].levels == 1 and r["ast"].level_spp[0] == 16
     assert r["st"].passes == 4 and whole["st"].passes == 2
     assert r["st"].samples == r["ast"].samples == w * h * 16 and (r["spp"] == 16).all()

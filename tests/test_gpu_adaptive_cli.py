@@ -7,9 +7,10 @@ import subprocess
 import numpy as np
 import pytest
 
+import gpudev
 import ptlib
-from test_gpu_adaptive import ADev, L, cfg_of, scenes  # noqa: F401  (L, scenes: fixtures)
-from test_gpu_aov import pfm_to_framebuffer, read_pfm
+from gpudev import L, pfm_to_framebuffer, read_pfm  # noqa: F401  (L: fixture)
+from test_gpu_adaptive import ADev, scenes  # noqa: F401  (scenes: fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -29,11 +30,8 @@ def test_cli_adaptive_writes_the_librarys_frame_and_the_counts(L, scenes, tmp_pa
     assert "Adaptive, tile error 0.12:" in r.stdout and "wrote " + pfm in r.stdout
     files = [f for f in os.listdir(tmp_path / "a") if f.endswith(".ppm")]
     assert len(files) == 1
-    d = ADev(L, scenes["cornell"], W * H)
-    try:
-        want = d.adaptive(cfg_of(CAP, seed=3, w=W, h=H), TE, tile=0)
-    finally:
-        d.close()
+    with ADev(L, scenes["cornell"], W * H) as d:
+        want = d.adaptive(gpudev.config(W, H, CAP, backend=ptlib.BACKEND_MEGAKERNEL, seed=3), TE, tile=0)
     ref = str(tmp_path / "ref.ppm")
     img = np.ascontiguousarray(want["img"])
     assert L.pt_write_ppm(ref.encode(), img.ctypes.data_as(C.POINTER(C.c_float)), W, H, CAP, b"cornell", 0) == 0

@@ -9,11 +9,13 @@ import numpy as np
 import pytest
 
 import adaptive_ref
+import gpudev
 import ptlib
 from ptlib import PtAdaptiveInfo, PtAdaptiveParams, PtAdaptiveStats, PtStats
 from test_adaptive_held_abi import parse_adaptive_checkpoint
 from test_gpu_accumulate import NO_BVH
-from test_gpu_adaptive import CAP, H, SEED, TILE, TILE_ERROR, W, ADev, cfg_of
+from gpudev import L  # noqa: F401  (fixture)
+from test_gpu_adaptive import CAP, H, SEED, TILE, TILE_ERROR, W, ADev
 from test_gpu_noise import NDev
 
 pytestmark = pytest.mark.gpu
@@ -23,11 +25,8 @@ f32 = np.float32
 CASES = [("cornell", 0), ("mesh", 0), ("mesh", NO_BVH)]
 
 
-@pytest.fixture(scope="module")
-def L():
-    L = ptlib.product()
-    assert L.pt_device_count() >= 1, "no HIP device visible: the product has no CPU fallback"
-    return L
+def cfg_of(spp, backend=ptlib.BACKEND_MEGAKERNEL, seed=SEED, w=W, h=H, **kw):
+    return gpudev.config(w, h, spp, backend=backend, seed=seed, **kw)
 
 
 @pytest.fixture(scope="module")
@@ -40,15 +39,10 @@ class HDev(ADev):
 
     def __init__(self, L, sc, npix_max):
         super().__init__(L, sc, npix_max)
-        self.extra = [C.c_void_p() for _ in range(3)]
-        for p, size in zip(self.extra, (12, 4, 4)):
-            assert L.pt_device_malloc(0, npix_max * size, C.byref(p)) == 0
+        self.extra = [self.alloc(npix_max * size) for size in (12, 4, 4)]
 
     def _maps(self, n, d_out, d_spp, d_err):
-        spp, err = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=f32)
-        assert self.L.pt_device_download(0, spp.ctypes.data_as(C.c_void_p), d_spp, n * 4) == 0
-        assert self.L.pt_device_download(0, err.ctypes.data_as(C.c_void_p), d_err, n * 4) == 0
-        return dict(img=self.download(d_out, n), spp=spp, err=err)
+        return dict(img=self.pixels(d_out, n), spp=self.download(d_spp, n, np.uint32), err=self.download(d_err, n))
 
     def held(self, cfg, tile_error, tile=TILE, min_spp=0, want=0, cancel=None, cb=None):
         par, st, ast = PtAdaptiveParams(tile_error, tile, min_spp), PtStats(), PtAdaptiveStats()
@@ -72,11 +66,6 @@ class HDev(ADev):
         assert rc == want, (rc, self.L.pt_last_error())
         return self._maps(self.L.pt_config_pixels(C.byref(cfg)), *self.extra) if rc == 0 else None
 
-    def close(self):
-        for p in self.extra:
-            self.L.pt_device_free(0, p)
-        super().close()
-
 
 _scratch = {}
 
@@ -85,11 +74,8 @@ def scratch(L, scenes, sid, flags, tile_error, cap=CAP, tile=TILE, w=W, h=H, min
     """the reference, computed once and shared: pt_ctx_render_adaptive from zero on a context of its own"""
     key = (sid, flags, tile_error, cap, tile, w, h, min_spp, seed)
     if key not in _scratch:
-        d = ADev(L, scenes[sid], w * h)
-        try:
+        with ADev(L, scenes[sid], w * h) as d:
             _scratch[key] = d.adaptive(cfg_of(cap, w=w, h=h, flags=flags, seed=seed), tile_error, tile=tile, min_spp=min_spp)
-        finally:
-            d.close()
     return _scratch[key]
 
 
@@ -133,14 +119,11 @@ def test_cleaner(L, scenes, sid, flags):
     print("%s: tiles closed under %g that go on under %g, by the count they closed at: %s" % (
         sid, x1, x2, {c: int(((c1 == c) & (c2 > c1)).sum()) for c in reopened}))
     assert len(reopened) >= 2 and (c2 >= c1).all()
-    d = HDev(L, scenes[sid], W * H)
-    try:
+    with HDev(L, scenes[sid], W * H) as d:
         a = d.held(cfg_of(CAP, flags=flags), x1)
         same_frame(a, r1)
         assert (a["st"].samples, a["st"].ray_bounces) == (r1["st"].samples, r1["st"].ray_bounces)
         b = d.held(cfg_of(CAP, flags=flags), x2)
-    finally:
-        d.close()
     same_frame(b, r2)
     assert b["st"].samples == r2["st"].samples - r1["st"].samples
     assert b["st"].ray_bounces == r2["st"].ray_bounces - r1["st"].ray_bounces
@@ -150,13 +133,10 @@ def test_cleaner(L, scenes, sid, flags):
 @pytest.mark.parametrize("sid,flags", CASES)
 def test_higher_cap(L, scenes, sid, flags):
     ref64, ref = scratch(L, scenes, sid, flags, TILE_ERROR, cap=64), scratch(L, scenes, sid, flags, TILE_ERROR)
-    d = HDev(L, scenes[sid], W * H)
-    try:
+    with HDev(L, scenes[sid], W * H) as d:
         a = d.held(cfg_of(64, flags=flags), TILE_ERROR)
         same_frame(a, ref64)
         b = d.held(cfg_of(CAP, flags=flags), TILE_ERROR)
-    finally:
-        d.close()
     same_frame(b, ref)
     assert list(b["ast"].level_spp[:b["ast"].levels]) == [128, 256]
     assert b["st"].samples == ref["st"].samples - ref64["st"].samples
@@ -215,12 +195,9 @@ def test_off_ladder_cap(L, scenes):
     finally:
         tracked.close()
         plain.close()
-    d = HDev(L, scenes["cornell"], W * H)
-    try:
+    with HDev(L, scenes["cornell"], W * H) as d:
         a = d.held(cfg_of(100), TILE_ERROR)
         b = d.held(cfg_of(CAP), TILE_ERROR)
-    finally:
-        d.close()
     want100 = adaptive_ref.replay(maps, W, H, TILE, TILE_ERROR, lv, stop_after=4)
     want = adaptive_ref.replay(maps, W, H, TILE, TILE_ERROR, lv)
     print("closed per level %s, open at the cap %d" % (want["tiles_closed"], want["tiles_open"]))
@@ -238,8 +215,7 @@ def test_off_ladder_cap(L, scenes):
 
 def test_looser_target_traces_nothing(L, scenes):
     ref = scratch(L, scenes, "cornell", 0, TILE_ERROR)
-    d = HDev(L, scenes["cornell"], W * H)
-    try:
+    with HDev(L, scenes["cornell"], W * H) as d:
         a = d.held(cfg_of(CAP), TILE_ERROR)
         assert a["ast"].tiles_open > 0  # (the reference frame leaves tiles open at the cap)
         b = d.held(cfg_of(CAP), 0.32)
@@ -257,14 +233,11 @@ def test_looser_target_traces_nothing(L, scenes):
         assert c["st"].samples == 0 and np.array_equal(c["spp"], ref["spp"])
         e = d.held(cfg_of(CAP), TILE_ERROR)  # back to the tighter target: the tiles reopen, at the cap - nothing to trace either
         assert e["st"].samples == 0 and e["ast"].tiles_open == a["ast"].tiles_open
-    finally:
-        d.close()
 
 
 def test_isolation_and_the_key(L, scenes):
     ref = scratch(L, scenes, "cornell", 0, TILE_ERROR)
-    d = HDev(L, scenes["cornell"], W * H)
-    try:
+    with HDev(L, scenes["cornell"], W * H) as d:
         img8, _ = d.accumulate(cfg_of(8))
         a = d.held(cfg_of(64), TILE_ERROR)
         assert d.info(cfg_of(8)) == (8, 8)  # pt_ctx_accumulate's held frame is as it was ...
@@ -293,8 +266,6 @@ def test_isolation_and_the_key(L, scenes):
         assert d.resolve(cfg_of(CAP), want=PT_ERR_INVALID) is None
         assert L.pt_ctx_adaptive_save(d.ctx, b"/nonexistent/x") == PT_ERR_INVALID
         assert L.pt_ctx_adaptive_reset(d.ctx) == 0
-    finally:
-        d.close()
 
 
 def test_checkpoint(L, scenes, tmp_path):
@@ -358,12 +329,9 @@ def test_partial_tiles(L, scenes):
     w, h, tile, te = 100, 70, 16, 0.12  # 7 x 5 tiles, the right column 4 wide, the bottom row 6 high
     ref = scratch(L, scenes, "cornell", 0, te, cap=64, tile=tile, w=w, h=h)
     ref32 = scratch(L, scenes, "cornell", 0, te, cap=32, tile=tile, w=w, h=h)
-    d = HDev(L, scenes["cornell"], w * h)
-    try:
+    with HDev(L, scenes["cornell"], w * h) as d:
         a = d.held(cfg_of(32, w=w, h=h), te, tile=tile)
         same_frame(a, ref32)
         b = d.held(cfg_of(64, w=w, h=h), te, tile=tile)
-    finally:
-        d.close()
     same_frame(b, ref)
     assert b["ast"].tiles == 35 and b["st"].samples == ref["st"].samples - ref32["st"].samples

@@ -9,8 +9,9 @@ import subprocess
 import numpy as np
 import pytest
 
+import gpudev
 import ptlib
-from ptlib import PtConfig, PtStats
+from gpudev import L, pfm_to_framebuffer, read_pfm, scene  # noqa: F401  (L: fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -99,69 +100,35 @@ def call_pixels(w, h, band=None, chunks=None):
 
 
 # ------------------------------------------------------------------------------------------------------- the device
-class Dev:
+class Dev(gpudev.Device):
+    PLANES = ((3, F32), (3, F32), (1, F32), (1, np.int32))  # albedo, normal, depth, object_id
+
     def __init__(self, L, sc, npix_max):
-        self.L = L
-        self.ctx = C.c_void_p()
-        assert L.pt_ctx_create(0, C.byref(self.ctx)) == 0, L.pt_last_error()
-        if sc is not None:
-            assert L.pt_ctx_set_scene(self.ctx, C.byref(sc.cam), sc.objs, sc.n_objs, sc.tris, sc.n_tris) == 0, L.pt_last_error()
+        super().__init__(L, sc)
         self.n = npix_max
-        self.bufs = []
-        for nbytes in (npix_max * 12, npix_max * 12, npix_max * 4, npix_max * 4):
-            p = C.c_void_p()
-            assert L.pt_device_malloc(0, nbytes, C.byref(p)) == 0
-            self.bufs.append(p)
+        self.bufs = [self.alloc(npix_max * k * 4) for k, _ in self.PLANES]
 
     def call(self, cfg, which=(1, 1, 1, 1), want=0):
         ptrs = [b if on else None for b, on in zip(self.bufs, which)]
         rc = self.L.pt_ctx_render_aov(self.ctx, C.byref(cfg), *ptrs, None)
         assert rc == want, (rc, self.L.pt_last_error())
 
-    def download(self, npix):
-        out = []
-        for p, (k, dt) in zip(self.bufs, ((3, F32), (3, F32), (1, F32), (1, np.int32))):
-            host = np.zeros(npix * k, dtype=dt)
-            assert self.L.pt_device_download(0, host.ctypes.data_as(C.c_void_p), p, host.nbytes) == 0
-            out.append(host.reshape(npix, 3) if k == 3 else host)
-        return out
+    def planes(self, npix):
+        out = [self.download(p, npix * k, dt) for p, (k, dt) in zip(self.bufs, self.PLANES)]
+        return [a.reshape(npix, 3) if k == 3 else a for a, (k, _) in zip(out, self.PLANES)]
 
     def aov(self, cfg, which=(1, 1, 1, 1)):
         self.call(cfg, which)
-        return self.download(self.L.pt_config_pixels(C.byref(cfg)))
-
-    def close(self):
-        for p in self.bufs:
-            self.L.pt_device_free(0, p)
-        self.L.pt_ctx_destroy(self.ctx)
+        return self.planes(self.L.pt_config_pixels(C.byref(cfg)))
 
 
-def cfg_of(w, h, spp, seed=SEED, band=None, chunks=None, flags=0, backend=0):
-    cfg = PtConfig(w, h, spp, backend, seed, 0, 0, 0, flags)
-    if band:
-        cfg.idx_begin, cfg.idx_end = band
-    if chunks:
-        cfg.chunk_pixels, cfg.chunk_first, cfg.chunk_step = chunks
-    return cfg
+def cfg_of(w, h, spp, seed=SEED, **kw):
+    return gpudev.config(w, h, spp, seed=seed, **kw)
 
 
 def assert_bits(got, want, what):
-    g = [np.ascontiguousarray(a) for a in got]
-    for name, a, b in zip(("albedo", "normal", "depth", "object_id"), g, want):
-        b = np.ascontiguousarray(b, dtype=a.dtype).reshape(a.shape)
-        if a.tobytes() != b.tobytes():
-            bad = np.argwhere(a.view(np.uint32) != b.view(np.uint32))
-            raise AssertionError("%s %s: %d of %d words differ, first at %s: %r vs %r" % (
-                what, name, len(bad), a.size, bad[0], a[tuple(bad[0])], b[tuple(bad[0])]))
-
-
-_scenes = {}
-
-
-def scene(sid):
-    if sid not in _scenes:
-        _scenes[sid] = ptlib.load_scene_py(ptlib.scene_path(sid), triangulate=(sid == "mesh-hdodec"))
-    return _scenes[sid]
+    for name, a, b in zip(("albedo", "normal", "depth", "object_id"), got, want):
+        gpudev.same_bytes(a, np.asarray(b, dtype=a.dtype).reshape(a.shape), "%s %s" % (what, name))
 
 
 def generated_bvh_scene():
@@ -173,26 +140,18 @@ def generated_bvh_scene():
 
 
 # ------------------------------------------------------------------------------------------------------- tests
-@pytest.fixture(scope="module")
-def L():
-    return ptlib.product()
-
-
 @pytest.mark.parametrize("sid", ["cornell", "three-spheres", "mesh", "mesh-hdodec", "generated-bvh"])
 def test_bit_equal_to_the_rebuild(L, sid):
     sc = generated_bvh_scene() if sid == "generated-bvh" else scene(sid)
     pixels = call_pixels(W, H)
     rays = oracle_rays(sc, W, H, SEED, pixels, 100)
-    dev = Dev(L, sc, W * H)
-    try:
+    with Dev(L, sc, W * H) as dev:
         for spp in (1, 3, 64, 100):
             got = dev.aov(cfg_of(W, H, spp))
             assert_bits(got, rebuild(sc, W, H, SEED, pixels, spp, rays), "%s spp %d" % (sid, spp))
             if spp == 100:
                 hits = (got[3] >= 0).mean()
                 assert 0.02 < hits, (sid, hits)  # the frame sees the scene
-    finally:
-        dev.close()
 
 
 def test_large_frame_over_2_20_pixels(L):
@@ -204,11 +163,8 @@ def test_large_frame_over_2_20_pixels(L):
     for b in (1 << 20, 1 << 21):
         special += [b - 2, b - 1, b, b + 1]
     pick = np.unique(np.concatenate([np.array(special), rng.choice(npix, 4096 - len(special), replace=False)]))
-    dev = Dev(L, sc, npix)
-    try:
+    with Dev(L, sc, npix) as dev:
         got = dev.aov(cfg_of(w, h, spp))
-    finally:
-        dev.close()
     want = rebuild(sc, w, h, SEED, pick, spp)
     assert_bits([a[pick] for a in got], want, "large frame")
 
@@ -216,8 +172,7 @@ def test_large_frame_over_2_20_pixels(L):
 def test_bands_and_chunks_match_the_whole_frame(L):
     sc = scene("mesh")
     spp = 5
-    dev = Dev(L, sc, W * H)
-    try:
+    with Dev(L, sc, W * H) as dev:
         whole = dev.aov(cfg_of(W, H, spp))
         parts = [dev.aov(cfg_of(W, H, spp, band=b)) for b in ((0, 1000), (1000, 1001), (1001, W * H))]
         assert_bits([np.concatenate([p[i] for p in parts]) for i in range(4)], whole, "bands")
@@ -227,41 +182,32 @@ def test_bands_and_chunks_match_the_whole_frame(L):
             assert L.pt_config_pixels(C.byref(cfg)) == len(idx)
             got = dev.aov(cfg)
             assert_bits(got, [a[idx] for a in whole], "chunks %r %r" % (band, chunks))
-    finally:
-        dev.close()
 
 
 def test_linear_scan_gives_the_same_bits(L):
     sc = scene("mesh")
-    dev = Dev(L, sc, W * H)
-    try:
+    with Dev(L, sc, W * H) as dev:
         for spp in (3, 64):
             assert_bits(dev.aov(cfg_of(W, H, spp, flags=NO_BVH)), dev.aov(cfg_of(W, H, spp)), "NO_BVH spp %d" % spp)
         # ignored fields: backend, rays_per_pass, progress_ms, separate kernels, pipelines
         c = cfg_of(W, H, 3, flags=2 | (3 << 8), backend=1)
         c.rays_per_pass, c.progress_ms = 12345, 7
         assert_bits(dev.aov(c), dev.aov(cfg_of(W, H, 3)), "ignored fields")
-    finally:
-        dev.close()
 
 
 def test_sample_zero_is_shared_and_the_seed_matters(L):
     sc = scene("cornell")
-    dev = Dev(L, sc, W * H)
-    try:
+    with Dev(L, sc, W * H) as dev:
         a1 = dev.aov(cfg_of(W, H, 1))
         a64 = dev.aov(cfg_of(W, H, 64))
         assert_bits(a1[2:], a64[2:], "depth / id at spp 1 and 64")
         b1 = dev.aov(cfg_of(W, H, 1, seed=SEED + 1))
         assert a1[2].tobytes() != b1[2].tobytes() or a1[0].tobytes() != b1[0].tobytes()
-    finally:
-        dev.close()
 
 
 def test_null_outputs_and_errors(L):
     sc = scene("three-spheres")
-    dev = Dev(L, sc, W * H)
-    try:
+    with Dev(L, sc, W * H) as dev:
         full = dev.aov(cfg_of(W, H, 4))
         # poison the buffers with another frame's results, then write one output at a time: the others stay as they were
         other = dev.aov(cfg_of(W, H, 2, seed=99))
@@ -283,48 +229,28 @@ def test_null_outputs_and_errors(L):
             assert L.pt_ctx_render_aov(dev.ctx, C.byref(bad), *p, None) == PT_ERR_INVALID
         # spp at the limit is accepted (a 1x1 frame keeps it cheap)
         assert L.pt_ctx_render_aov(dev.ctx, C.byref(cfg_of(1, 1, 1 << 24)), None, None, p[2], None, None) == 0, L.pt_last_error()
-    finally:
-        dev.close()
-    bare = Dev(L, None, 16)
-    try:
+    with Dev(L, None, 16) as bare:
         assert L.pt_ctx_render_aov(bare.ctx, C.byref(cfg_of(4, 4, 1)), *bare.bufs, None) == PT_ERR_INVALID
-    finally:
-        bare.close()
 
 
 def test_no_disturbance_of_accumulation(L):
     sc = scene("cornell")
-    dev = Dev(L, sc, W * H)
-    out = C.c_void_p()
-    assert L.pt_device_malloc(0, W * H * 12, C.byref(out)) == 0
-    try:
-        def accumulate(spp):
-            st = PtStats()
-            assert L.pt_ctx_accumulate(dev.ctx, C.byref(cfg_of(W, H, spp)), out, None, None, None, None, C.byref(st)) == 0, \
-                L.pt_last_error()
-            host = np.zeros((W * H, 3), F32)
-            assert L.pt_device_download(0, host.ctypes.data_as(C.c_void_p), out, host.nbytes) == 0
-            return host
+    with Dev(L, sc, W * H) as dev:
+        out = dev.alloc(W * H * 12)
 
         def info():
             lo, hi = C.c_uint32(), C.c_uint32()
             assert L.pt_ctx_accum_info(dev.ctx, C.byref(cfg_of(W, H, 1)), C.byref(lo), C.byref(hi)) == 0
             return lo.value, hi.value
 
-        accumulate(8)
+        dev.render(cfg_of(W, H, 8), out, accumulate=True)
         assert info() == (8, 8)
         dev.aov(cfg_of(W, H, 16))
         dev.aov(cfg_of(W, H, 3, band=(100, 900)))
         assert info() == (8, 8)
-        got = accumulate(16)
-        st = PtStats()
-        assert L.pt_ctx_render(dev.ctx, C.byref(cfg_of(W, H, 16)), out, None, None, None, None, C.byref(st)) == 0
-        want = np.zeros((W * H, 3), F32)
-        assert L.pt_device_download(0, want.ctypes.data_as(C.c_void_p), out, want.nbytes) == 0
+        got, _ = dev.render(cfg_of(W, H, 16), out, accumulate=True)
+        want, _ = dev.render(cfg_of(W, H, 16), out)
         assert got.tobytes() == want.tobytes()
-    finally:
-        L.pt_device_free(0, out)
-        dev.close()
 
 
 def test_python_context_render_aov(L):
@@ -338,30 +264,15 @@ def test_python_context_render_aov(L):
         dev.aov(cfg_of(W, H, 1, seed=3))  # other contents
         p = [b.value for b in dev.bufs]
         ctx.render_aov(W, H, 6, seed=SEED, chunks=(32, 1, 2), albedo=p[0], normal=p[1], depth=p[2], object_id=p[3])
-        assert_bits(dev.download(len(want[2])), want, "python")
+        assert_bits(dev.planes(len(want[2])), want, "python")
         ctx.render_aov(W, H, 6, seed=SEED, chunks=(32, 1, 2), depth=p[2], no_bvh=True)
-        assert dev.download(len(want[2]))[2].tobytes() == want[2].tobytes()
+        assert dev.planes(len(want[2]))[2].tobytes() == want[2].tobytes()
         with pytest.raises(pkg.PtraceError):
             ctx.render_aov(W, H, 6)
     finally:
         dev.close()
         ctx.close()
         s.close()
-
-
-def read_pfm(path):
-    data = open(path, "rb").read()
-    magic, dims, scale, body = data.split(b"\n", 3)
-    ch = {b"PF": 3, b"Pf": 1}[magic]
-    w, h = (int(v) for v in dims.split())
-    assert float(scale) == -1.0
-    return np.frombuffer(body, dtype="<f4").reshape(h, w, ch)
-
-
-def pfm_to_framebuffer(rows):
-    """PFM row q from the bottom, column c = framebuffer index q*W + (W-1-c)"""
-    h, w, ch = rows.shape
-    return rows[:, ::-1, :].reshape(h * w, ch)
 
 
 def test_cli_writes_the_aov_files(L, tmp_path):
@@ -386,11 +297,8 @@ def test_cli_writes_the_aov_files(L, tmp_path):
     assert (mapped == vals).all()
     # the AOV files hold pt_ctx_render_aov's buffers at 4 samples, placed as the beauty image
     sc = scene("mesh")
-    dev = Dev(L, sc, w * h)
-    try:
+    with Dev(L, sc, w * h) as dev:
         want = dev.aov(cfg_of(w, h, 4, seed=3))
-    finally:
-        dev.close()
     got = [pfm_to_framebuffer(read_pfm(out / (stem + n + ".pfm"))) for n in ("albedo", "normal", "depth", "id")]
     assert got[0].tobytes() == want[0].tobytes() and got[1].tobytes() == want[1].tobytes()
     assert got[2][:, 0].tobytes() == want[2].tobytes()

@@ -11,10 +11,11 @@ import numpy as np
 import pytest
 
 import aov_chain_ref as R
+import gpudev
 import ptlib
-from ptlib import PtAovParams, PtStats
-from test_gpu_aov import (F32, H, NO_BVH, PT_ERR_INVALID, SEED, W, call_pixels, cfg_of, oracle_rays, pfm_to_framebuffer, read_pfm,
-                          scene)
+from gpudev import L, pfm_to_framebuffer, read_pfm, scene  # noqa: F401  (L: fixture)
+from ptlib import PtAovParams
+from test_gpu_aov import F32, H, NO_BVH, PT_ERR_INVALID, SEED, W, call_pixels, oracle_rays
 
 pytestmark = pytest.mark.gpu
 
@@ -22,9 +23,8 @@ THROUGH_DELTA, MAX_CHAIN = ptlib.abi.PT_AOV_THROUGH_DELTA, ptlib.abi.PT_AOV_MAX_
 NAMES = ("albedo", "normal", "depth", "object_id", "chain")
 
 
-@pytest.fixture(scope="module")
-def L():
-    return ptlib.product()
+def cfg_of(w, h, spp, seed=SEED, **kw):
+    return gpudev.config(w, h, spp, seed=seed, **kw)
 
 
 # ------------------------------------------------------------------------------------------------------- scenes and records
@@ -61,18 +61,12 @@ def record(name, spp, band=None):
 
 
 # ------------------------------------------------------------------------------------------------------- the device
-class Dev:
+class Dev(gpudev.Device):
+    PLANES = ((3, F32), (3, F32), (1, F32), (1, np.int32), (1, np.uint32))  # NAMES
+
     def __init__(self, L, sc, npix_max=W * H):
-        self.L = L
-        self.ctx = C.c_void_p()
-        assert L.pt_ctx_create(0, C.byref(self.ctx)) == 0, L.pt_last_error()
-        if sc is not None:
-            assert L.pt_ctx_set_scene(self.ctx, C.byref(sc.cam), sc.objs, sc.n_objs, sc.tris, sc.n_tris) == 0, L.pt_last_error()
-        self.bufs = []
-        for nbytes in (npix_max * 12, npix_max * 12, npix_max * 4, npix_max * 4, npix_max * 4):
-            p = C.c_void_p()
-            assert L.pt_device_malloc(0, nbytes, C.byref(p)) == 0
-            self.bufs.append(p)
+        super().__init__(L, sc)
+        self.bufs = [self.alloc(npix_max * k * 4) for k, _ in self.PLANES]
 
     def call(self, cfg, params, which=(1, 1, 1, 1, 1)):
         ptrs = [b if on else None for b, on in zip(self.bufs, which)]
@@ -80,34 +74,20 @@ class Dev:
 
     def plain(self, cfg):
         assert self.L.pt_ctx_render_aov(self.ctx, C.byref(cfg), *self.bufs[:4], None) == 0, self.L.pt_last_error()
-        return self.download(self.L.pt_config_pixels(C.byref(cfg)))[:4]
+        return self.planes(self.L.pt_config_pixels(C.byref(cfg)))[:4]
 
-    def download(self, npix):
-        out = []
-        for p, (k, dt) in zip(self.bufs, ((3, F32), (3, F32), (1, F32), (1, np.int32), (1, np.uint32))):
-            host = np.zeros(npix * k, dtype=dt)
-            assert self.L.pt_device_download(0, host.ctypes.data_as(C.c_void_p), p, host.nbytes) == 0
-            out.append(host.reshape(npix, 3) if k == 3 else host)
-        return out
+    def planes(self, npix):
+        out = [self.download(p, npix * k, dt) for p, (k, dt) in zip(self.bufs, self.PLANES)]
+        return [a.reshape(npix, 3) if k == 3 else a for a, (k, _) in zip(out, self.PLANES)]
 
     def aov(self, cfg, max_chain=0, flags=THROUGH_DELTA, which=(1, 1, 1, 1, 1)):
         assert self.call(cfg, PtAovParams(flags, max_chain), which) == 0, self.L.pt_last_error()
-        return self.download(self.L.pt_config_pixels(C.byref(cfg)))
-
-    def close(self):
-        for p in self.bufs:
-            self.L.pt_device_free(0, p)
-        self.L.pt_ctx_destroy(self.ctx)
+        return self.planes(self.L.pt_config_pixels(C.byref(cfg)))
 
 
 def assert_bits(got, want, what):
     for name, a, b in zip(NAMES, got, want):
-        a = np.ascontiguousarray(a)
-        b = np.ascontiguousarray(b, dtype=a.dtype).reshape(a.shape)
-        if a.tobytes() != b.tobytes():
-            bad = np.argwhere(a.view(np.uint32) != b.view(np.uint32))
-            raise AssertionError("%s %s: %d of %d words differ, first at %s: %r vs %r" % (
-                what, name, len(bad), a.size, bad[0], a[tuple(bad[0])], b[tuple(bad[0])]))
+        gpudev.same_bytes(a, np.asarray(b, dtype=a.dtype).reshape(a.shape), "%s %s" % (what, name))
 
 
 # ------------------------------------------------------------------------------------------------------- tests
@@ -118,15 +98,12 @@ def test_cornell_bit_equal_to_the_restatement(L):
     # the headline scene: about 8 % of the pixels see a mirror or glass first, every chain ends on a diffuse surface
     assert st["delta_pixels"] >= 0.05 * st["pixels"] and st["on_surface_after_delta"] == st["delta_pixels"]
     assert st["mirror_steps"] > 0 and st["transmissions"] > 0
-    dev = Dev(L, chain_scene("cornell"))
-    try:
+    with Dev(L, chain_scene("cornell")) as dev:
         for spp in (1, 3, 64, 100):
             got = dev.aov(cfg_of(W, H, spp))
             assert_bits(got, R.planes(rec, spp), "cornell spp %d" % spp)
         plain = dev.plain(cfg_of(W, H, 100))
         assert plain[0].tobytes() != got[0].tobytes() and plain[2].tobytes() != got[2].tobytes()  # the guides do differ
-    finally:
-        dev.close()
 
 
 def _preconditions(name, st):
@@ -146,13 +123,10 @@ def test_delta_scenes_bit_equal_to_the_restatement(L, name):
     print(name, st)
     _preconditions(name, st)
     band = (1200, 1328)  # two rows through the middle of the frame, at more than 64 samples: lanes loop, waves diverge
-    dev = Dev(L, chain_scene(name))
-    try:
+    with Dev(L, chain_scene(name)) as dev:
         for spp in (1, 3):
             assert_bits(dev.aov(cfg_of(W, H, spp)), R.planes(rec, spp), "%s spp %d" % (name, spp))
         assert_bits(dev.aov(cfg_of(W, H, 70, band=band)), R.planes(record(name, 70, band)), "%s spp 70, a band" % name)
-    finally:
-        dev.close()
 
 
 @pytest.mark.parametrize("cap", [1, 2, 8, 16])
@@ -162,20 +136,16 @@ def test_caps_on_the_all_mirror_scene(L, cap):
     st = R.stats(rec, cap)
     print(name, "cap", cap, st)
     assert st["at_cap"] > 0 and st["max_length"] == cap, st  # the cap binds
-    dev = Dev(L, chain_scene(name))
-    try:
+    with Dev(L, chain_scene(name)) as dev:
         for spp in (1, 3):
             got = dev.aov(cfg_of(W, H, spp), max_chain=cap)
             assert_bits(got, R.planes(rec, spp, cap), "cap %d spp %d" % (cap, spp))
         if cap == 8:  # max_chain 0 is 8
             assert_bits(dev.aov(cfg_of(W, H, 3), max_chain=0), got, "max_chain 0")
-    finally:
-        dev.close()
 
 
 def test_flags_zero_is_the_plain_call(L):
-    dev = Dev(L, chain_scene("cornell"))
-    try:
+    with Dev(L, chain_scene("cornell")) as dev:
         for spp in (3, 64):
             cfg = cfg_of(W, H, spp)
             dev.aov(cfg)  # other contents in every plane, the chain plane included
@@ -183,33 +153,25 @@ def test_flags_zero_is_the_plain_call(L):
             dev.aov(cfg_of(W, H, 1, seed=5))
             for params in (None, PtAovParams(0, 0)):
                 assert dev.call(cfg, params) == 0, L.pt_last_error()
-                got = dev.download(W * H)
+                got = dev.planes(W * H)
                 assert_bits(got, want + [np.zeros(W * H, np.uint32)], "flags 0, spp %d" % spp)
                 dev.aov(cfg_of(W, H, 1, seed=5))
-    finally:
-        dev.close()
 
 
 def test_a_scene_without_delta_surfaces_gives_the_plain_bits(L):
     sc = chain_scene("three-spheres")
     assert all(sc.objs[i].reflect_type == 0 for i in range(sc.n_objs))
-    dev = Dev(L, sc)
-    try:
+    with Dev(L, sc) as dev:
         for spp in (1, 5, 70):
             cfg = cfg_of(W, H, spp)
             want = dev.plain(cfg)
             assert_bits(dev.aov(cfg), want + [np.zeros(W * H, np.uint32)], "no delta surface, spp %d" % spp)
-    finally:
-        dev.close()
 
 
 def test_linear_scan_gives_the_same_bits(L):
-    dev = Dev(L, chain_scene("mesh-glass"))
-    try:
+    with Dev(L, chain_scene("mesh-glass")) as dev:
         for spp in (3, 64):
             assert_bits(dev.aov(cfg_of(W, H, spp, flags=NO_BVH)), dev.aov(cfg_of(W, H, spp)), "NO_BVH spp %d" % spp)
-    finally:
-        dev.close()
 
 
 def test_bands_and_chunks_match_the_whole_frame(L):
@@ -229,8 +191,7 @@ def test_bands_and_chunks_match_the_whole_frame(L):
 
 
 def test_each_output_may_be_null(L):
-    dev = Dev(L, chain_scene("cornell"))
-    try:
+    with Dev(L, chain_scene("cornell")) as dev:
         full = dev.aov(cfg_of(W, H, 4))
         other = dev.aov(cfg_of(W, H, 2, seed=99))
         for k in range(5):
@@ -244,13 +205,10 @@ def test_each_output_may_be_null(L):
         dev.aov(cfg_of(W, H, 2, seed=99))
         got = dev.aov(cfg_of(W, H, 4), flags=0, which=(0, 0, 0, 0, 1))
         assert not got[4].any() and all(got[i].tobytes() == other[i].tobytes() for i in range(4))
-    finally:
-        dev.close()
 
 
 def test_errors(L):
-    dev = Dev(L, chain_scene("three-spheres-delta"))
-    try:
+    with Dev(L, chain_scene("three-spheres-delta")) as dev:
         cfg = cfg_of(W, H, 4)
         on = PtAovParams(THROUGH_DELTA, 0)
         for bad in (PtAovParams(2, 0), PtAovParams(THROUGH_DELTA | 0x80000000, 0), PtAovParams(THROUGH_DELTA, MAX_CHAIN + 1),
@@ -264,42 +222,26 @@ def test_errors(L):
                     cfg_of(W, H, 4, chunks=(0, 0, 2)), cfg_of(W, H, 4, chunks=(8, 3, 3)), cfg_of(0, H, 4)):
             assert dev.call(bad, on) == PT_ERR_INVALID
         assert dev.call(cfg, PtAovParams(THROUGH_DELTA, MAX_CHAIN)) == 0, L.pt_last_error()
-    finally:
-        dev.close()
-    bare = Dev(L, None, 16)
-    try:
+    with Dev(L, None, 16) as bare:
         assert bare.call(cfg_of(4, 4, 1), PtAovParams(THROUGH_DELTA, 0)) == PT_ERR_INVALID  # no scene
-    finally:
-        bare.close()
 
 
 def test_no_disturbance_of_accumulation(L):
-    dev = Dev(L, chain_scene("cornell"))
-    out = C.c_void_p()
-    assert L.pt_device_malloc(0, W * H * 12, C.byref(out)) == 0
-    try:
-        def frame(fn, spp):
-            st = PtStats()
-            assert fn(dev.ctx, C.byref(cfg_of(W, H, spp)), out, None, None, None, None, C.byref(st)) == 0, L.pt_last_error()
-            host = np.zeros((W * H, 3), F32)
-            assert L.pt_device_download(0, host.ctypes.data_as(C.c_void_p), out, host.nbytes) == 0
-            return host
+    with Dev(L, chain_scene("cornell")) as dev:
+        out = dev.alloc(W * H * 12)
 
         def info():
             lo, hi = C.c_uint32(), C.c_uint32()
             assert L.pt_ctx_accum_info(dev.ctx, C.byref(cfg_of(W, H, 1)), C.byref(lo), C.byref(hi)) == 0
             return lo.value, hi.value
 
-        frame(L.pt_ctx_accumulate, 8)
+        dev.render(cfg_of(W, H, 8), out, accumulate=True)
         assert info() == (8, 8)
         dev.aov(cfg_of(W, H, 16))
         dev.aov(cfg_of(W, H, 3, band=(100, 900)), max_chain=2)
         assert info() == (8, 8)
-        got = frame(L.pt_ctx_accumulate, 16)
-        assert got.tobytes() == frame(L.pt_ctx_render, 16).tobytes()
-    finally:
-        L.pt_device_free(0, out)
-        dev.close()
+        got, _ = dev.render(cfg_of(W, H, 16), out, accumulate=True)
+        assert got.tobytes() == dev.render(cfg_of(W, H, 16), out)[0].tobytes()
 
 
 def test_python_context_render_aov_through_delta(L):
@@ -314,7 +256,7 @@ def test_python_context_render_aov_through_delta(L):
         p = [b.value for b in dev.bufs]
         ctx.render_aov(W, H, 6, seed=SEED, chunks=(32, 1, 2), albedo=p[0], normal=p[1], depth=p[2], object_id=p[3], chain=p[4],
                        through_delta=True, max_chain=1)
-        assert_bits(dev.download(len(want[2])), want, "python")
+        assert_bits(dev.planes(len(want[2])), want, "python")
         assert want[4].max() == 1
         with pytest.raises(pkg.PtraceError):
             ctx.render_aov(W, H, 6, depth=p[2], max_chain=3)  # max_chain without through_delta
@@ -348,18 +290,15 @@ def test_cli_denoises_with_the_chain_guides(L, tmp_path):
     s = pkg.Scene(ptlib.scene_path("cornell"))
     ctx = pkg.Context(0)
     dev = Dev(L, None, w * h)
-    color = C.c_void_p()
-    assert L.pt_device_malloc(0, w * h * 12, C.byref(color)) == 0
     try:
+        color = dev.alloc(w * h * 12)
         ctx.set_scene(s)
         p = [b.value for b in dev.bufs]
         ctx.render(color.value, w, h, spp, seed=seed)
         ctx.render_aov(w, h, guide_spp, seed=seed, albedo=p[0], normal=p[1], depth=p[2], through_delta=True)
         ctx.denoise(w, h, color.value, color.value, albedo=p[0], normal=p[1], depth=p[2])
-        want = np.zeros((w * h, 3), F32)
-        assert L.pt_device_download(0, want.ctypes.data_as(C.c_void_p), color, want.nbytes) == 0
+        want = dev.pixels(color, w * h)
     finally:
-        L.pt_device_free(0, color)
         dev.close()
         ctx.close()
         s.close()
@@ -376,11 +315,8 @@ def test_cli_writes_the_chain_plane(L, tmp_path):
     files = sorted(os.listdir(out))
     stem = [f for f in files if f.endswith(".ppm")][0][:-len(".ppm")]
     w, h = 36, 24
-    dev = Dev(L, chain_scene("cornell"), w * h)
-    try:
+    with Dev(L, chain_scene("cornell"), w * h) as dev:
         want = dev.aov(cfg_of(w, h, 4, seed=3), max_chain=3)
-    finally:
-        dev.close()
     got = [pfm_to_framebuffer(read_pfm(out / (stem + n + ".pfm"))) for n in ("albedo", "normal", "depth", "id", "chain")]
     assert got[0].tobytes() == want[0].tobytes() and got[1].tobytes() == want[1].tobytes()
     assert got[2][:, 0].tobytes() == want[2].tobytes()

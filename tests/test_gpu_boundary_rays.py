@@ -8,15 +8,16 @@ k_pass_bvh, k_pass, the separate kernels and k_mega_cand.  A pt_ctx_radiance cal
 walk queue never holds more than a few entries and the depth-first second walk of a small queue does not run there; the
 frames of every generated scene through every device path (full waves) are where that form is compared."""
 import ctypes as C
-import os
 import time
 
 import numpy as np
 import pytest
 
 import boundary_rays as br
+import gpudev
 import ptlib
-from ptlib import PtConfig, PtStats, _np_f
+from gpudev import L, new_ctx, set_scene  # noqa: F401  (L: fixture)
+from ptlib import PtStats, _np_f
 
 pytestmark = pytest.mark.gpu
 
@@ -35,34 +36,11 @@ def sets():
     return br.build(SEED)
 
 
-def _new_ctx(L, env=None):
-    """A context created under the given tuning variables (they are read when the context is created)."""
-    env = env or {}
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        ctx = C.c_void_p()
-        assert L.pt_ctx_create(0, C.byref(ctx)) == 0, L.pt_last_error()
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-    return ctx
-
-
 @pytest.fixture(scope="module")
-def gpu():
-    L = ptlib.product()
-    assert L.pt_device_count() >= 1, "no HIP device visible: the product has no CPU fallback"
-    ctx = _new_ctx(L)
+def gpu(L):
+    ctx = new_ctx(L)
     yield L, ctx
     L.pt_ctx_destroy(ctx)
-
-
-def _set_scene(L, ctx, sc):
-    assert L.pt_ctx_set_scene(ctx, C.byref(sc.cam), sc.objs, sc.n_objs, sc.tris, sc.n_tris) == 0, L.pt_last_error()
 
 
 def _has_bvh(rs):
@@ -84,7 +62,7 @@ def test_tables_match_the_contexts_kernels(gpu, sets):
     dump holds BVH meshes, and the candidate scan exactly when the dump says the records fit."""
     L, ctx = gpu
     for rs in sets:
-        _set_scene(L, ctx, rs.scene)
+        set_scene(L, ctx, rs.scene)
         name = L.pt_ctx_pass_kernel(ctx, 0).decode()
         assert name == ("k_pass_cand_bvh" if _has_bvh(rs) else "k_pass_cand"), (rs.scene.id, name)
         assert L.pt_ctx_pass_kernel(ctx, ptlib.FLAG_NO_BVH).decode() == "k_pass"
@@ -96,7 +74,7 @@ def test_query_kernel_ray_by_ray(gpu, sets):
     L, ctx = gpu
     for rs in sets:
         sc = rs.scene
-        _set_scene(L, ctx, sc)
+        set_scene(L, ctx, sc)
         want = ptlib.oracle_intersect(sc, rs.o, rs.d)
         for m in _slices(rs.n):
             o, d = np.ascontiguousarray(rs.o[:m]), np.ascontiguousarray(rs.d[:m])
@@ -119,7 +97,7 @@ def test_stream_intersect_kernels_on_boundary_rays(gpu, sets, flags):
     L, ctx = gpu
     for rs in sets:
         sc = rs.scene
-        _set_scene(L, ctx, sc)
+        set_scene(L, ctx, sc)
         t0, oid0, tid0, _, _ = ptlib.oracle_intersect(sc, rs.o, rs.d)
         want = _stream_ids(sc, oid0, tid0)
         for m in _slices(rs.n):
@@ -139,7 +117,7 @@ def test_bounds_and_orbit_point_on_boundary_rays(gpu, sets):
     O = ptlib.oracle()
     for rs in sets:
         sc = rs.scene
-        _set_scene(L, ctx, sc)
+        set_scene(L, ctx, sc)
         boxes = ptlib.oracle_boxes(sc)
         ps = sc.pto()
         for m in _slices(min(rs.n, 20000)):
@@ -220,7 +198,7 @@ def test_pass_kernels_first_hit(gpu, sets):
     intersect_scene evaluation.  (b) The same rays at depth 0 with the scene's colours kept: a different triangle or t
     changes the rest of the path (same bounce count, radiance as the shading known-answer tests compare it)."""
     L, _ = gpu
-    ctxs = [(name, _new_ctx(L, env), backend, flags, kernels) for name, env, backend, flags, kernels in PASS_FORMS]
+    ctxs = [(name, new_ctx(L, env), backend, flags, kernels) for name, env, backend, flags, kernels in PASS_FORMS]
     n_calls, secs, per_kind = 0, 0.0, np.zeros(len(br.RAY_KINDS), np.int64)
     try:
         for rs in sets:
@@ -239,7 +217,7 @@ def test_pass_kernels_first_hit(gpu, sets):
             for name, ctx, backend, flags, kernels in ctxs:
                 for tag in ("first", "shaded"):
                     sc, depth, seed, ref, ref_b = want[tag]
-                    _set_scene(L, ctx, sc)
+                    set_scene(L, ctx, sc)
                     want_kernel = kernels[0] if _has_bvh(rs) else kernels[1]
                     if want_kernel is not None:
                         assert L.pt_ctx_pass_kernel(ctx, flags).decode() == want_kernel, (name, rs.scene.id)
@@ -270,24 +248,17 @@ def test_frames_of_the_generated_scenes(gpu, sets):
     L, _ = gpu
     w, h, spp = 40, 28, 4
     paths = [(name, env, backend, flags) for name, env, backend, flags, _ in PASS_FORMS]
-    ctxs = {name: _new_ctx(L, env) for name, env, _, _ in paths}
+    devs = {name: gpudev.Device(L, env=env) for name, env, _, _ in paths}
+    outs = {name: dev.alloc(w * h * 12) for name, dev in devs.items()}
     try:
         for k, rs in enumerate(sets):
             sc = br.first_hit_variant(rs.scene, keep_color=True)
             want, cnt, _ = ptlib.oracle_render(sc, w, h, spp, 40 + k)
             ref = None
             for name, env, backend, flags in paths:
-                ctx = ctxs[name]
-                _set_scene(L, ctx, sc)
-                cfg = PtConfig(w, h, spp, backend, 40 + k, 0, 0, 0, flags)
-                dev = C.c_void_p()
-                assert L.pt_device_malloc(0, w * h * 12, C.byref(dev)) == 0
-                st = PtStats()
-                rc = L.pt_ctx_render(ctx, C.byref(cfg), dev, None, None, None, None, C.byref(st))
-                img = np.empty((w * h, 3), np.float32)
-                assert L.pt_device_download(0, _np_f(img), dev, img.nbytes) == 0
-                L.pt_device_free(0, dev)
-                assert rc == 0, L.pt_last_error()
+                dev = devs[name]
+                set_scene(L, dev.ctx, sc)
+                img, st = dev.render(gpudev.config(w, h, spp, backend=backend, seed=40 + k, flags=flags), outs[name])
                 assert st.ray_bounces == cnt.ray_bounces, (rs.scene.id, name, st.ray_bounces, cnt.ray_bounces)
                 assert float(np.abs(img - want).max()) <= TOL, (rs.scene.id, name)
                 if ref is None:
@@ -295,5 +266,5 @@ def test_frames_of_the_generated_scenes(gpu, sets):
                 else:
                     assert np.array_equal(img.view(np.uint32), ref.view(np.uint32)), (rs.scene.id, name)
     finally:
-        for ctx in ctxs.values():
-            L.pt_ctx_destroy(ctx)
+        for dev in devs.values():
+            dev.close()

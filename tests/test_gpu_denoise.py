@@ -14,10 +14,11 @@ import numpy as np
 import pytest
 
 import denoise_ref
+import gpudev
 import ptlib
 from denoise_ref import F32, NO_DEMODULATE
-from ptlib import PtDenoiseParams, PtStats
-from test_gpu_aov import cfg_of, pfm_to_framebuffer, read_pfm, scene
+from gpudev import L, pfm_to_framebuffer, read_pfm, scene  # noqa: F401  (L: fixture)
+from ptlib import PtDenoiseParams
 
 pytestmark = pytest.mark.gpu
 
@@ -28,35 +29,30 @@ SIZES = ((64, 40), (67, 41), (5, 3), (1, 1), (300, 7))
 NON_DEFAULT = (0.75, 0.4)  # (sigma_color, sigma_depth)
 
 
-class Frame:
+def cfg_of(w, h, spp, seed=SEED, **kw):
+    return gpudev.config(w, h, spp, seed=seed, **kw)
+
+
+class Frame(gpudev.Device):
     """One context and the device buffers of one frame size: color, albedo, normal, depth, object id, out."""
 
     def __init__(self, L, sc, npix_max):
-        self.L = L
-        self.ctx = C.c_void_p()
-        assert L.pt_ctx_create(0, C.byref(self.ctx)) == 0, L.pt_last_error()
-        assert L.pt_ctx_set_scene(self.ctx, C.byref(sc.cam), sc.objs, sc.n_objs, sc.tris, sc.n_tris) == 0, L.pt_last_error()
-        self.bufs = {}
+        super().__init__(L, sc)
         for name, k in (("color", 3), ("albedo", 3), ("normal", 3), ("depth", 1), ("id", 1), ("out", 3)):
-            p = C.c_void_p()
-            assert L.pt_device_malloc(0, npix_max * k * 4, C.byref(p)) == 0, L.pt_last_error()
-            self.bufs[name] = p
+            self.alloc(npix_max * k * 4, name)
+        self.bufs = self.p
 
     def get(self, name, npix):
         k = 1 if name in ("depth", "id") else 3
-        host = np.zeros(npix * k, dtype=np.int32 if name == "id" else F32)
-        assert self.L.pt_device_download(0, host.ctypes.data_as(C.c_void_p), self.bufs[name], host.nbytes) == 0
+        host = self.download(name, npix * k, np.int32 if name == "id" else F32)
         return host.reshape(npix, 3) if k == 3 else host
 
-    def render(self, w, h, spp, guide_spp, seed=SEED):
+    def trace(self, w, h, spp, guide_spp, seed=SEED):
         """the frame and its guides; returns (color, albedo, normal, depth) on the host"""
         b = self.bufs
-        st = PtStats()
-        assert self.L.pt_ctx_render(self.ctx, C.byref(cfg_of(w, h, spp, seed=seed)), b["color"], None, None, None, None,
-                                    C.byref(st)) == 0, self.L.pt_last_error()
+        _, self.stats = self.render(cfg_of(w, h, spp, seed=seed), "color")
         assert self.L.pt_ctx_render_aov(self.ctx, C.byref(cfg_of(w, h, guide_spp, seed=seed)), b["albedo"], b["normal"],
                                         b["depth"], b["id"], None) == 0, self.L.pt_last_error()
-        self.stats = st
         return tuple(self.get(n, w * h) for n in ("color", "albedo", "normal", "depth"))
 
     def denoise(self, w, h, levels=0, sigma_color=0.0, sigma_depth=0.0, flags=0, guides=(1, 1, 1), out="out", stream=None,
@@ -68,11 +64,6 @@ class Frame:
         assert rc == 0, (rc, self.L.pt_last_error())
         return self.get(out, w * h)
 
-    def close(self):
-        for p in self.bufs.values():
-            self.L.pt_device_free(0, p)
-        self.L.pt_ctx_destroy(self.ctx)
-
 
 def reference(L, host, w, h, levels=0, sigma_color=0.0, sigma_depth=0.0, flags=0, guides=(1, 1, 1)):
     d_levels, d_sc, d_sd = denoise_ref.defaults(L)
@@ -82,25 +73,16 @@ def reference(L, host, w, h, levels=0, sigma_color=0.0, sigma_depth=0.0, flags=0
 
 
 def assert_bytes(got, want, what):
-    got, want = np.ascontiguousarray(got, dtype=F32), np.ascontiguousarray(want, dtype=F32).reshape(got.shape)
-    if got.tobytes() != want.tobytes():
-        bad = np.argwhere(got.view(np.uint32) != want.view(np.uint32))
-        raise AssertionError("%s: %d of %d words differ, first at %s: %r vs %r" % (
-            what, len(bad), got.size, bad[0], got[tuple(bad[0])], want[tuple(bad[0])]))
-
-
-@pytest.fixture(scope="module")
-def L():
-    return ptlib.product()
+    got = np.ascontiguousarray(got, dtype=F32)
+    gpudev.same_bytes(got, np.asarray(want, dtype=F32).reshape(got.shape), what)
 
 
 # ------------------------------------------------------------------------------------------------ bit for bit
 @pytest.mark.parametrize("sid", ["cornell", "three-spheres", "mesh", "mesh-hdodec"])
 def test_bit_equal_to_the_rebuild(L, sid):
-    fr = Frame(L, scene(sid), 64 * 41 + 300 * 7)
-    try:
+    with Frame(L, scene(sid), 64 * 41 + 300 * 7) as fr:
         for w, h in SIZES:
-            host = fr.render(w, h, 8, 4)
+            host = fr.trace(w, h, 8, 4)
             for levels in (1, 2, 5, 8):
                 assert_bytes(fr.denoise(w, h, levels), reference(L, host, w, h, levels), "%s %dx%d levels %d" % (sid, w, h, levels))
                 sc_, sd = NON_DEFAULT
@@ -110,16 +92,13 @@ def test_bit_equal_to_the_rebuild(L, sid):
             want = reference(L, host, w, h)
             assert_bytes(fr.denoise(w, h, params=False), want, "NULL params")
             assert_bytes(fr.denoise(w, h), want, "zero params")
-    finally:
-        fr.close()
 
 
 @pytest.mark.parametrize("sid", ["cornell", "mesh"])
 def test_null_guides_and_no_demodulate(L, sid):
     w, h = 67, 41
-    fr = Frame(L, scene(sid), w * h)
-    try:
-        host = fr.render(w, h, 8, 4)
+    with Frame(L, scene(sid), w * h) as fr:
+        host = fr.trace(w, h, 8, 4)
         seen = {}
         for a in (0, 1):
             for n in (0, 1):
@@ -133,19 +112,14 @@ def test_null_guides_and_no_demodulate(L, sid):
         # NO_DEMODULATE is a NULL albedo, and the guides matter
         assert seen[(1, 1, 1, NO_DEMODULATE, (0.0, 0.0))] == seen[(0, 1, 1, 0, (0.0, 0.0))]
         assert len({seen[(a, n, d, 0, (0.0, 0.0))] for a in (0, 1) for n in (0, 1) for d in (0, 1)}) == 8
-    finally:
-        fr.close()
 
 
 def test_large_frame_on_picked_pixels(L):
     w, h = 2100, 1000
     npix = w * h
-    fr = Frame(L, scene("cornell"), npix)
-    try:
-        host = fr.render(w, h, 8, 4)
+    with Frame(L, scene("cornell"), npix) as fr:
+        host = fr.trace(w, h, 8, 4)
         got = fr.denoise(w, h)
-    finally:
-        fr.close()
     want = reference(L, host, w, h)
     rng = np.random.default_rng(11)
     special = [0, w - 1, npix - w, npix - 1, w // 2, npix - w // 2, (h // 2) * w, (h // 2) * w + w - 1]
@@ -164,14 +138,11 @@ def child_main():
     level count, in the form PT_DN_LDS_MAXSTEP selects, as one JSON line"""
     L = ptlib.product()
     out = {}
-    fr = Frame(L, scene("mesh"), max(w * h for w, h in CHILD_FRAMES))
-    try:
+    with Frame(L, scene("mesh"), max(w * h for w, h in CHILD_FRAMES)) as fr:
         for w, h in CHILD_FRAMES:
-            fr.render(w, h, 8, 4)
+            fr.trace(w, h, 8, 4)
             for levels in range(1, 9):
                 out["%dx%d/%d" % (w, h, levels)] = hashlib.sha256(fr.denoise(w, h, levels).tobytes()).hexdigest()
-    finally:
-        fr.close()
     print("HASHES " + json.dumps(out))
 
 
@@ -187,99 +158,61 @@ def test_both_forms_give_the_same_bytes(L):
     assert len(res["0"]) == len(CHILD_FRAMES) * 8
     assert res["0"] == res["128"], [k for k in res["0"] if res["0"][k] != res["128"][k]]
     # and they are the restatement's bytes (this process runs the default mix of forms)
-    fr = Frame(L, scene("mesh"), 300 * 200)
-    try:
+    with Frame(L, scene("mesh"), 300 * 200) as fr:
         for w, h in CHILD_FRAMES:
-            host = fr.render(w, h, 8, 4)
+            host = fr.trace(w, h, 8, 4)
             for levels in (3, 8):
                 want = reference(L, host, w, h, levels)
                 assert hashlib.sha256(want.tobytes()).hexdigest() == res["0"]["%dx%d/%d" % (w, h, levels)], (w, h, levels)
                 assert_bytes(fr.denoise(w, h, levels), want, "default forms %dx%d levels %d" % (w, h, levels))
-    finally:
-        fr.close()
 
 
 # ------------------------------------------------------------------------------------------------ calling conventions
-def _hip_runtime():
-    """the HIP runtime the product is bound to: the copy already mapped into this process (an earlier test may have
-    imported torch, which maps its own bundled copy too: a stream of that runtime is not one of the product's)"""
-    paths = {line.split()[-1] for line in open("/proc/self/maps") if "/libamdhip64.so" in line}
-    own = sorted(p for p in paths if "/torch/" not in p)
-    assert own, "libptrace_hip.so has not mapped a HIP runtime: %r" % sorted(paths)
-    return C.CDLL(own[0])
-
-
 def test_in_place_stream_repeat_and_growth(L):
     sc = scene("cornell")
-    fr = Frame(L, sc, 128 * 80)
-    try:
+    with Frame(L, sc, 128 * 80) as fr:
         w, h = 64, 40
-        host = fr.render(w, h, 8, 4)
+        host = fr.trace(w, h, 8, 4)
         first = fr.denoise(w, h)
         assert_bytes(first, reference(L, host, w, h), "out of place")
         assert_bytes(fr.denoise(w, h), first, "second call")  # scratch reuse leaks nothing
         # a larger frame after a smaller one (scratch grows), then the smaller again
         W2, H2 = 128, 80
-        host2 = fr.render(W2, H2, 8, 4)
+        host2 = fr.trace(W2, H2, 8, 4)
         assert_bytes(fr.denoise(W2, H2), reference(L, host2, W2, H2), "larger frame")
-        fr.render(w, h, 8, 4)
+        fr.trace(w, h, 8, 4)
         assert_bytes(fr.denoise(w, h), first, "smaller frame after the larger")
         # a caller's stream
-        hip = _hip_runtime()
-        stream = C.c_void_p()
-        assert hip.hipStreamCreate(C.byref(stream)) == 0
-        try:
+        with fr.stream() as stream:
             assert_bytes(fr.denoise(w, h, stream=stream), first, "caller's stream")
-        finally:
-            hip.hipStreamDestroy(stream)
         # in place: d_out == d_color (last: it overwrites the frame)
         assert_bytes(fr.denoise(w, h, out="color"), first, "in place")
-    finally:
-        fr.close()
 
 
 def test_runtime_errors_with_a_context(L):
-    fr = Frame(L, scene("three-spheres"), 16)
-    try:
+    with Frame(L, scene("three-spheres"), 16) as fr:
         b = fr.bufs
         bad = PtDenoiseParams(9, 0, 0, 0, 0)
         assert L.pt_ctx_denoise(fr.ctx, 4, 4, C.byref(bad), b["color"], None, None, None, b["out"], None) == PT_ERR_INVALID
         assert L.pt_ctx_denoise(fr.ctx, 4, 4, None, None, None, None, None, b["out"], None) == PT_ERR_INVALID
         assert L.pt_ctx_denoise(fr.ctx, 0, 4, None, b["color"], None, None, None, b["out"], None) == PT_ERR_INVALID
-    finally:
-        fr.close()
     # no scene is needed
-    ctx = C.c_void_p()
-    assert L.pt_ctx_create(0, C.byref(ctx)) == 0
-    p = C.c_void_p()
-    assert L.pt_device_malloc(0, 16 * 12, C.byref(p)) == 0
-    try:
-        assert L.pt_ctx_denoise(ctx, 4, 4, None, p, None, None, None, p, None) == 0, L.pt_last_error()
-    finally:
-        L.pt_device_free(0, p)
-        L.pt_ctx_destroy(ctx)
+    with gpudev.Device(L) as bare:
+        p = bare.alloc(16 * 12)
+        assert L.pt_ctx_denoise(bare.ctx, 4, 4, None, p, None, None, None, p, None) == 0, L.pt_last_error()
 
 
 def test_no_disturbance_of_accumulation(L):
     w, h = 64, 40
-    fr = Frame(L, scene("cornell"), w * h)
-    acc = C.c_void_p()
-    assert L.pt_device_malloc(0, w * h * 12, C.byref(acc)) == 0
-    try:
-        def accumulate(spp):
-            st = PtStats()
-            assert L.pt_ctx_accumulate(fr.ctx, C.byref(cfg_of(w, h, spp)), acc, None, None, None, None, C.byref(st)) == 0, \
-                L.pt_last_error()
-            host = np.zeros((w * h, 3), F32)
-            assert L.pt_device_download(0, host.ctypes.data_as(C.c_void_p), acc, host.nbytes) == 0
-            return host
+    with Frame(L, scene("cornell"), w * h) as fr:
+        acc = fr.alloc(w * h * 12)
 
         def info():
             lo, hi = C.c_uint32(), C.c_uint32()
             assert L.pt_ctx_accum_info(fr.ctx, C.byref(cfg_of(w, h, 1)), C.byref(lo), C.byref(hi)) == 0
             return lo.value, hi.value
 
-        accumulate(8)
+        fr.render(cfg_of(w, h, 8), acc, accumulate=True)
         assert info() == (8, 8)
         assert L.pt_ctx_render_aov(fr.ctx, C.byref(cfg_of(w, h, 4)), fr.bufs["albedo"], fr.bufs["normal"], fr.bufs["depth"],
                                    None, None) == 0
@@ -287,15 +220,9 @@ def test_no_disturbance_of_accumulation(L):
         assert L.pt_ctx_denoise(fr.ctx, w, h, C.byref(p), acc, fr.bufs["albedo"], fr.bufs["normal"], fr.bufs["depth"],
                                 fr.bufs["out"], None) == 0, L.pt_last_error()
         assert info() == (8, 8)
-        got = accumulate(16)
-        st = PtStats()
-        assert L.pt_ctx_render(fr.ctx, C.byref(cfg_of(w, h, 16)), acc, None, None, None, None, C.byref(st)) == 0
-        want = np.zeros((w * h, 3), F32)
-        assert L.pt_device_download(0, want.ctypes.data_as(C.c_void_p), acc, want.nbytes) == 0
+        got, _ = fr.render(cfg_of(w, h, 16), acc, accumulate=True)
+        want, _ = fr.render(cfg_of(w, h, 16), acc)
         assert got.tobytes() == want.tobytes()
-    finally:
-        L.pt_device_free(0, acc)
-        fr.close()
 
 
 # ------------------------------------------------------------------------------------------------ quality
@@ -326,13 +253,9 @@ def test_quality_on_the_devices_own_frames(L):
     w, h = 256, 192
     npix = w * h
     sc = scene("cornell")
-    hip = _hip_runtime()
-    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    fr = Frame(L, sc, npix)
-    try:
-        noisy, albedo, normal, depth = fr.render(w, h, 16, 16)
+    with Frame(L, sc, npix) as fr:
+        noisy, albedo, normal, depth = fr.trace(w, h, 16, 16)
         ids = fr.get("id", npix)
-        st = PtStats()
         # the candidates, and the objects they belong to
         colors = np.array([list(sc.objs[i].color) for i in range(sc.n_objs)], dtype=F32)
         I, A = ids.reshape(h, w), albedo.reshape(h, w, 3)
@@ -351,8 +274,7 @@ def test_quality_on_the_devices_own_frames(L):
         objects = sorted({c[2] for c in cand})
 
         def set_depth(host):
-            host = np.ascontiguousarray(host, dtype=F32)
-            assert hip.hipMemcpy(fr.bufs["depth"], host.ctypes.data_as(C.c_void_p), host.nbytes, 1) == 0  # host to device
+            fr.upload("depth", np.asarray(host, dtype=F32))
 
         def filtered():
             """(D, {a: D_a}) of the frame in the colour buffer"""
@@ -366,11 +288,8 @@ def test_quality_on_the_devices_own_frames(L):
             return full, own
 
         den, den_own = filtered()
-        assert L.pt_ctx_render(fr.ctx, C.byref(cfg_of(w, h, 4096)), fr.bufs["color"], None, None, None, None, C.byref(st)) == 0
-        conv = fr.get("color", npix)
+        conv, _ = fr.render(cfg_of(w, h, 4096), "color")
         den_conv, den_conv_own = filtered()
-    finally:
-        fr.close()
     e_noisy, e_den = rmse(noisy, conv), rmse(den, conv)
     print("cornell %dx%d: rmse noisy %.5f, denoised %.5f, ratio %.4f, R %.4f" % (w, h, e_noisy, e_den, e_den / e_noisy, R_CORNELL))
     assert e_den <= R_CORNELL * e_noisy, (e_den / e_noisy, R_CORNELL)
@@ -406,7 +325,7 @@ def test_python_context_denoise(L):
     ctx = pkg.Context(0)
     fr = Frame(L, scene("mesh"), w * h)
     try:
-        host = fr.render(w, h, 8, 4)
+        host = fr.trace(w, h, 8, 4)
         b = {k: v.value for k, v in fr.bufs.items()}
         ctx.denoise(w, h, b["color"], b["out"], albedo=b["albedo"], normal=b["normal"], depth=b["depth"])
         assert_bytes(fr.get("out", w * h), reference(L, host, w, h), "python defaults")

@@ -18,10 +18,11 @@ import pytest
 
 import denoise_ref
 import denoise_var_ref as ref
+import gpudev
 import ptlib
 from denoise_var_ref import F32, NO_DEMODULATE
+from gpudev import L, pfm_to_framebuffer, read_pfm, scene  # noqa: F401  (L: fixture)
 from ptlib import PtAdaptiveParams, PtAdaptiveStats, PtDenoiseParams, PtDenoiseVarParams, PtNoiseStats, PtStats
-from test_gpu_aov import cfg_of, pfm_to_framebuffer, read_pfm, scene
 
 pytestmark = pytest.mark.gpu
 
@@ -33,45 +34,29 @@ STUDY = json.load(open(os.path.join(ptlib.ROOT, "profiles", "denoise_var_cpu_stu
 BUFS = (("color", 3), ("error", 1), ("albedo", 3), ("normal", 3), ("depth", 1), ("out", 3))
 
 
-def hip_runtime():
-    """the HIP runtime the product is bound to: the copy already mapped into this process that is not torch's"""
-    paths = {line.split()[-1] for line in open("/proc/self/maps") if "/libamdhip64.so" in line}
-    own = sorted(p for p in paths if "/torch/" not in p)
-    assert own, "libptrace_hip.so has not mapped a HIP runtime: %r" % sorted(paths)
-    hip = C.CDLL(own[0])
-    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    return hip
+def cfg_of(w, h, spp, seed=SEED, **kw):
+    return gpudev.config(w, h, spp, seed=seed, **kw)
 
 
-class Frame:
+class Frame(gpudev.Device):
     """One noise-tracking context and the device buffers of one frame size: color, error, albedo, normal, depth, out."""
 
     def __init__(self, L, sc, npix_max):
-        self.L = L
-        self.ctx = C.c_void_p()
-        assert L.pt_ctx_create(0, C.byref(self.ctx)) == 0, L.pt_last_error()
-        assert L.pt_ctx_set_scene(self.ctx, C.byref(sc.cam), sc.objs, sc.n_objs, sc.tris, sc.n_tris) == 0, L.pt_last_error()
+        super().__init__(L, sc)
         assert L.pt_ctx_accum_track_noise(self.ctx, 1) == 0, L.pt_last_error()
-        self.bufs = {}
         for name, k in BUFS:
-            p = C.c_void_p()
-            assert L.pt_device_malloc(0, npix_max * k * 4, C.byref(p)) == 0, L.pt_last_error()
-            self.bufs[name] = p
+            self.alloc(npix_max * k * 4, name)
+        self.bufs = self.p
 
     def get(self, name, npix):
-        k = dict(BUFS)[name]
-        host = np.zeros(npix * k, dtype=F32)
-        assert self.L.pt_device_download(0, host.ctypes.data_as(C.c_void_p), self.bufs[name], host.nbytes) == 0
-        return host.reshape(npix, 3) if k == 3 else host
+        host = self.download(name, npix * dict(BUFS)[name])
+        return host.reshape(npix, 3) if host.size == npix * 3 else host
 
     def put(self, name, host):
-        host = np.ascontiguousarray(host, dtype=F32)
-        assert hip_runtime().hipMemcpy(self.bufs[name], host.ctypes.data_as(C.c_void_p), host.nbytes, 1) == 0  # host to device
+        self.upload(name, np.asarray(host, dtype=F32))
 
     def accumulate(self, w, h, spp, seed=SEED):
-        st = PtStats()
-        assert self.L.pt_ctx_accumulate(self.ctx, C.byref(cfg_of(w, h, spp, seed=seed)), self.bufs["color"], None, None, None,
-                                        None, C.byref(st)) == 0, self.L.pt_last_error()
+        self.render(cfg_of(w, h, spp, seed=seed), "color", accumulate=True)
 
     def noise(self, w, h, spp, seed=SEED):
         ns = PtNoiseStats()
@@ -87,7 +72,7 @@ class Frame:
         """(color, error, albedo, normal, depth) as they are on the device"""
         return tuple(self.get(n, w * h) for n in ("color", "error", "albedo", "normal", "depth"))
 
-    def render(self, w, h, spp=16, guide_spp=4, seed=SEED):
+    def trace(self, w, h, spp=16, guide_spp=4, seed=SEED):
         """a fresh tracked frame, its noise map and its guides; returns them on the host"""
         assert self.L.pt_ctx_accum_reset(self.ctx) == 0
         self.accumulate(w, h, spp, seed)
@@ -112,11 +97,6 @@ class Frame:
         assert rc == 0, (rc, self.L.pt_last_error())
         return self.get("out", w * h)
 
-    def close(self):
-        for p in self.bufs.values():
-            self.L.pt_device_free(0, p)
-        self.L.pt_ctx_destroy(self.ctx)
-
 
 def reference(L, host, w, h, levels=0, sigma_var=0.0, sigma_depth=0.0, flags=0, guides=(1, 1, 1)):
     d_levels, d_sv, d_sd = ref.defaults(L)
@@ -132,27 +112,16 @@ def reference_fixed(L, host, w, h, levels=0):
 
 
 def assert_bytes(got, want, what):
-    got, want = np.ascontiguousarray(got, dtype=F32), np.ascontiguousarray(want, dtype=F32).reshape(got.shape)
-    if got.tobytes() != want.tobytes():
-        bad = np.argwhere(got.view(np.uint32) != want.view(np.uint32))
-        raise AssertionError("%s: %d of %d words differ, first at %s: %r vs %r" % (
-            what, len(bad), got.size, bad[0], got[tuple(bad[0])], want[tuple(bad[0])]))
-
-
-@pytest.fixture(scope="module")
-def L():
-    L = ptlib.product()
-    assert L.pt_device_count() >= 1, "no HIP device visible: the product has no CPU fallback"
-    return L
+    got = np.ascontiguousarray(got, dtype=F32)
+    gpudev.same_bytes(got, np.asarray(want, dtype=F32).reshape(got.shape), what)
 
 
 # ------------------------------------------------------------------------------------------------ bit for bit
 @pytest.mark.parametrize("sid", ["cornell", "three-spheres", "mesh", "mesh-hdodec"])
 def test_bit_equal_to_the_rebuild(L, sid):
-    fr = Frame(L, scene(sid), 64 * 41 + 300 * 7)
-    try:
+    with Frame(L, scene(sid), 64 * 41 + 300 * 7) as fr:
         for w, h in SIZES:
-            host = fr.render(w, h)
+            host = fr.trace(w, h)
             assert np.isfinite(host[1]).all()  # 8 + 8 samples: every pixel has an estimate
             for levels in (1, 2, 5, 8):
                 assert_bytes(fr.denoise_var(w, h, levels), reference(L, host, w, h, levels),
@@ -164,16 +133,13 @@ def test_bit_equal_to_the_rebuild(L, sid):
             want = reference(L, host, w, h)
             assert_bytes(fr.denoise_var(w, h, params=False), want, "NULL params")
             assert_bytes(fr.denoise_var(w, h), want, "zero params")
-    finally:
-        fr.close()
 
 
 @pytest.mark.parametrize("sid", ["cornell", "mesh"])
 def test_null_guides_and_no_demodulate(L, sid):
     w, h = 67, 41
-    fr = Frame(L, scene(sid), w * h)
-    try:
-        host = fr.render(w, h)
+    with Frame(L, scene(sid), w * h) as fr:
+        host = fr.trace(w, h)
         seen = {}
         for a in (0, 1):
             for n in (0, 1):
@@ -186,8 +152,6 @@ def test_null_guides_and_no_demodulate(L, sid):
         # NO_DEMODULATE is a NULL albedo, and the guides matter
         assert seen[(1, 1, 1, NO_DEMODULATE)] == seen[(0, 1, 1, 0)]
         assert len({seen[(a, n, d, 0)] for a in (0, 1) for n in (0, 1) for d in (0, 1)}) == 8
-    finally:
-        fr.close()
 
 
 def test_special_error_values(L):
@@ -195,9 +159,8 @@ def test_special_error_values(L):
     frame so that every value meets every kind of neighbour."""
     w, h = 67, 41
     values = np.array([0.0, 1e-40, 2.0 ** -12, 11.999, 12.0, 13.0, np.inf, np.nan, -1.0, -0.0], dtype=F32)
-    fr = Frame(L, scene("cornell"), w * h)
-    try:
-        color, error, albedo, normal, depth = fr.render(w, h)
+    with Frame(L, scene("cornell"), w * h) as fr:
+        color, error, albedo, normal, depth = fr.trace(w, h)
         rng = np.random.default_rng(3)
         k = rng.integers(0, len(values) + 3, w * h)  # three in thirteen pixels keep the device's own estimate
         made = np.where(k < len(values), values[np.minimum(k, len(values) - 1)], error).astype(F32)
@@ -207,16 +170,13 @@ def test_special_error_values(L):
         host = (color, made, albedo, normal, depth)
         for levels in (1, 5):
             assert_bytes(fr.denoise_var(w, h, levels), reference(L, host, w, h, levels), "special values, levels %d" % levels)
-    finally:
-        fr.close()
 
 
 def test_an_adaptive_frame_as_input(L):
     """pt_ctx_render_adaptive's d_out and d_error go straight in (96x64, tile 8, target 0.08, cap 256: the shape
     tests/test_gpu_adaptive.py uses); a cap-4 frame's d_error is all +inf ("no estimate") and is filtered as e = 12."""
     w, h = 96, 64
-    fr = Frame(L, scene("cornell"), w * h)
-    try:
+    with Frame(L, scene("cornell"), w * h) as fr:
         fr.guides(w, h, 4)
         for cap, all_inf in ((256, False), (4, True)):
             par, st, ast = PtAdaptiveParams(0.08, 8, 0), PtStats(), PtAdaptiveStats()
@@ -231,19 +191,14 @@ def test_an_adaptive_frame_as_input(L):
         # all +inf is all 12
         fr.put("error", np.full(w * h, 12.0, F32))
         assert_bytes(fr.denoise_var(w, h), reference(L, host, w, h), "e = 12 against e = +inf")
-    finally:
-        fr.close()
 
 
 def test_large_frame_on_picked_pixels(L):
     w, h = 2100, 1000
     npix = w * h
-    fr = Frame(L, scene("cornell"), npix)
-    try:
-        host = fr.render(w, h, 8, 4)
+    with Frame(L, scene("cornell"), npix) as fr:
+        host = fr.trace(w, h, 8, 4)
         got = fr.denoise_var(w, h)
-    finally:
-        fr.close()
     want = reference(L, host, w, h)
     rng = np.random.default_rng(11)
     special = [0, w - 1, npix - w, npix - 1, w // 2, npix - w // 2, (h // 2) * w, (h // 2) * w + w - 1]
@@ -262,14 +217,11 @@ def child_main():
     every level count, in the form PT_DN_LDS_MAXSTEP selects, as one JSON line"""
     L = ptlib.product()
     out = {}
-    fr = Frame(L, scene("mesh"), max(w * h for w, h in CHILD_FRAMES))
-    try:
+    with Frame(L, scene("mesh"), max(w * h for w, h in CHILD_FRAMES)) as fr:
         for w, h in CHILD_FRAMES:
-            fr.render(w, h)
+            fr.trace(w, h)
             for levels in range(1, 9):
                 out["%dx%d/%d" % (w, h, levels)] = hashlib.sha256(fr.denoise_var(w, h, levels).tobytes()).hexdigest()
-    finally:
-        fr.close()
     print("HASHES " + json.dumps(out))
 
 
@@ -285,24 +237,20 @@ def test_both_forms_give_the_same_bytes(L):
     assert len(res["0"]) == len(CHILD_FRAMES) * 8
     assert res["0"] == res["128"], [k for k in res["0"] if res["0"][k] != res["128"][k]]
     # and they are the restatement's bytes (this process runs the default mix of forms)
-    fr = Frame(L, scene("mesh"), 300 * 200)
-    try:
+    with Frame(L, scene("mesh"), 300 * 200) as fr:
         for w, h in CHILD_FRAMES:
-            host = fr.render(w, h)
+            host = fr.trace(w, h)
             for levels in (3, 8):
                 want = reference(L, host, w, h, levels)
                 assert hashlib.sha256(want.tobytes()).hexdigest() == res["0"]["%dx%d/%d" % (w, h, levels)], (w, h, levels)
                 assert_bytes(fr.denoise_var(w, h, levels), want, "default forms %dx%d levels %d" % (w, h, levels))
-    finally:
-        fr.close()
 
 
 # ------------------------------------------------------------------------------------------------ calling conventions
 def test_in_place_stream_repeat_growth_and_the_other_filter(L):
-    fr = Frame(L, scene("cornell"), 128 * 80)
-    try:
+    with Frame(L, scene("cornell"), 128 * 80) as fr:
         w, h = 64, 40
-        host = fr.render(w, h)
+        host = fr.trace(w, h)
         first = fr.denoise_var(w, h)
         assert_bytes(first, reference(L, host, w, h), "out of place")
         assert_bytes(fr.denoise_var(w, h), first, "second call")  # scratch reuse leaks nothing
@@ -315,27 +263,19 @@ def test_in_place_stream_repeat_growth_and_the_other_filter(L):
         assert_bytes(fr.denoise_var(w, h, 2), reference(L, host, w, h, 2), "pt_ctx_denoise_var, 2 levels, after")
         # a larger frame after a smaller one (scratch grows), then the smaller again
         W2, H2 = 128, 80
-        host2 = fr.render(W2, H2)
+        host2 = fr.trace(W2, H2)
         assert_bytes(fr.denoise_var(W2, H2), reference(L, host2, W2, H2), "larger frame")
-        fr.render(w, h)
+        fr.trace(w, h)
         assert_bytes(fr.denoise_var(w, h), first, "smaller frame after the larger")
         # a caller's stream
-        hip = hip_runtime()
-        stream = C.c_void_p()
-        assert hip.hipStreamCreate(C.byref(stream)) == 0
-        try:
+        with fr.stream() as stream:
             assert_bytes(fr.denoise_var(w, h, stream=stream), first, "caller's stream")
-        finally:
-            hip.hipStreamDestroy(stream)
         # in place: d_out == d_color (last: it overwrites the frame)
         assert_bytes(fr.denoise_var(w, h, out="color"), first, "in place")
-    finally:
-        fr.close()
 
 
 def test_runtime_errors_with_a_context(L):
-    fr = Frame(L, scene("three-spheres"), 16)
-    try:
+    with Frame(L, scene("three-spheres"), 16) as fr:
         b = fr.bufs
         call = lambda *a: L.pt_ctx_denoise_var(fr.ctx, *a)  # noqa: E731
         bad = PtDenoiseVarParams(9, 0, 0, 0)
@@ -345,19 +285,10 @@ def test_runtime_errors_with_a_context(L):
         assert b"d_error" in L.pt_last_error()
         assert call(4, 4, None, b["color"], b["error"], None, None, None, None, None) == PT_ERR_INVALID
         assert call(0, 4, None, b["color"], b["error"], None, None, None, b["out"], None) == PT_ERR_INVALID
-    finally:
-        fr.close()
     # no scene is needed
-    ctx = C.c_void_p()
-    assert L.pt_ctx_create(0, C.byref(ctx)) == 0
-    p, e = C.c_void_p(), C.c_void_p()
-    assert L.pt_device_malloc(0, 16 * 12, C.byref(p)) == 0 and L.pt_device_malloc(0, 16 * 4, C.byref(e)) == 0
-    try:
-        assert L.pt_ctx_denoise_var(ctx, 4, 4, None, p, e, None, None, None, p, None) == 0, L.pt_last_error()
-    finally:
-        L.pt_device_free(0, p)
-        L.pt_device_free(0, e)
-        L.pt_ctx_destroy(ctx)
+    with gpudev.Device(L) as bare:
+        p, e = bare.alloc(16 * 12), bare.alloc(16 * 4)
+        assert L.pt_ctx_denoise_var(bare.ctx, 4, 4, None, p, e, None, None, None, p, None) == 0, L.pt_last_error()
 
 
 def test_no_disturbance_of_accumulation(L):
@@ -367,8 +298,7 @@ def test_no_disturbance_of_accumulation(L):
     npix = w * h
 
     def run(with_denoise):
-        fr = Frame(L, scene("cornell"), npix)
-        try:
+        with Frame(L, scene("cornell"), npix) as fr:
             fr.accumulate(w, h, 16)
             fr.noise(w, h, 16)
             fr.guides(w, h, 4)
@@ -380,11 +310,7 @@ def test_no_disturbance_of_accumulation(L):
             fr.accumulate(w, h, 32)
             fr.noise(w, h, 32)
             got, err = fr.get("color", npix), fr.get("error", npix)
-            st = PtStats()
-            assert L.pt_ctx_render(fr.ctx, C.byref(cfg_of(w, h, 32)), fr.bufs["out"], None, None, None, None, C.byref(st)) == 0
-            return got, err, fr.get("out", npix)
-        finally:
-            fr.close()
+            return got, err, fr.render(cfg_of(w, h, 32), "out")[0]
 
     got, err, want = run(True)
     assert got.tobytes() == want.tobytes()
@@ -405,11 +331,8 @@ def test_quality_on_the_devices_own_frames(L, sid):
     seeds: DESIGN.md records that the estimate behaves the same.)"""
     w, h = 96, 64
     npix = w * h
-    fr = Frame(L, scene(sid), npix)
-    try:
-        st = PtStats()
-        assert L.pt_ctx_render(fr.ctx, C.byref(cfg_of(w, h, 4096)), fr.bufs["out"], None, None, None, None, C.byref(st)) == 0
-        conv = fr.get("out", npix)
+    with Frame(L, scene(sid), npix) as fr:
+        conv, _ = fr.render(cfg_of(w, h, 4096), "out")
         fr.guides(w, h, 16)
         cells = {}
         for n in (16, 256):
@@ -417,8 +340,6 @@ def test_quality_on_the_devices_own_frames(L, sid):
             fr.noise(w, h, n)
             noisy = fr.get("color", npix)
             cells[n] = (rmse(noisy, conv), rmse(fr.denoise_var(w, h), conv), rmse(fr.denoise(w, h), conv))
-    finally:
-        fr.close()
     for n, (e_noisy, e_var, e_fixed) in cells.items():
         bound = 1.15 * STUDY["chosen"]["ratio"]["%s_%d" % (sid, n)]
         print("%s n %d: rmse noisy %.5f, guided ratio %.4f (bound %.4f), pt_ctx_denoise ratio %.4f"
@@ -438,7 +359,7 @@ def test_python_context_denoise_var(L):
     ctx = pkg.Context(0)
     fr = Frame(L, scene("mesh"), w * h)
     try:
-        host = fr.render(w, h)
+        host = fr.trace(w, h)
         b = {k: v.value for k, v in fr.bufs.items()}
         ctx.denoise_var(w, h, b["color"], b["error"], b["out"], albedo=b["albedo"], normal=b["normal"], depth=b["depth"])
         assert_bytes(fr.get("out", w * h), reference(L, host, w, h), "python defaults")

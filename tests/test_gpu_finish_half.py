@@ -14,17 +14,17 @@ The frames, each the smallest that reaches its case:
 - an emitter of emission (1.5, 0, 0), and a wall whose diffuse colour has a zero channel: sums of zero reach the adds.
 Every frame is rendered twice in one context (the second frame finds the accumulators and the staged records of the first), and
 all of it again with PT_GLASS_DEFER=1 (glass hits collected per wave and shaded 64 at a time: DEFER's readers of the second ray)."""
-import ctypes as C
 import json
 
 import pytest
 
 import frame_sums as fs
+import gpudev
 import ptlib
 import scatter_walk
+from gpudev import L, same_bytes  # noqa: F401  (L: fixture)
 from ptlib import PtConfig
-from test_gpu_boundary_rays import _new_ctx
-from test_gpu_frame_sums import Out, _accumulate, _render, _saved, assert_frame, assert_planes
+from test_gpu_frame_sums import _saved, assert_planes
 
 pytestmark = pytest.mark.gpu
 
@@ -36,18 +36,11 @@ CONTEXTS = {"one_stream": {"PT_STREAMS": "1"}, "four_streams": {"PT_STREAMS": "4
 
 
 @pytest.fixture(scope="module")
-def L():
-    L = ptlib.product()
-    assert L.pt_device_count() >= 1, "no HIP device visible: the product has no CPU fallback"
-    return L
-
-
-@pytest.fixture(scope="module")
 def ctxs(L):
-    made = {name: _new_ctx(L, env) for name, env in CONTEXTS.items()}
+    made = {name: gpudev.Device(L, env=env) for name, env in CONTEXTS.items()}
     yield made
-    for c in made.values():
-        L.pt_ctx_destroy(c)
+    for d in made.values():
+        d.close()
 
 
 def _cornell(tmp, name, camera=None, edit=None):
@@ -144,24 +137,25 @@ def test_the_frames_reach_their_cases(walks):
 @pytest.mark.parametrize("case", CASES, ids=CASE_IDS)
 def test_frame_is_k_pass_and_the_oracle_sums(L, ctxs, scenes, walks, case, tmp_path):
     (name, sid, w, h, spp, _), cname = case
-    ctx, sc = ctxs[cname], scenes[sid]
+    dev, sc = ctxs[cname], scenes[sid]
+    ctx = dev.ctx
     W, total = walks[name]
     what = "%s %s" % (name, cname)
-    out = Out(L, w * h)
+    out = dev.alloc(w * h * 12)
     try:
-        assert L.pt_ctx_set_scene(ctx, C.byref(sc.cam), sc.objs, sc.n_objs, sc.tris, sc.n_tris) == 0, L.pt_last_error()
+        gpudev.set_scene(L, ctx, sc)
         assert L.pt_ctx_pass_kernel(ctx, 0).decode() == "k_pass_cand" and L.pt_ctx_pass_kernel(ctx, ptlib.FLAG_NO_BVH).decode() == "k_pass"
         cfg = PtConfig(w, h, spp, 0, SEED, 0, 0, 0, 0)
-        want, st_ref = _render(L, ctx, PtConfig(w, h, spp, 0, SEED, 0, 0, 0, ptlib.FLAG_NO_BVH), out)
+        want, st_ref = dev.render(PtConfig(w, h, spp, 0, SEED, 0, 0, 0, ptlib.FLAG_NO_BVH), out)
         assert st_ref.ray_bounces == W.n, (what, st_ref.ray_bounces, W.n)
         for turn in ("first frame", "second frame"):
-            got, st = _render(L, ctx, cfg, out)
+            got, st = dev.render(cfg, out)
             assert st.ray_bounces == W.n, (what, turn, st.ray_bounces, W.n)
-            assert_frame(got, want, "%s, %s against k_pass" % (what, turn))
-        img, st = _accumulate(L, ctx, cfg, out)
+            same_bytes(got, want, "%s, %s against k_pass" % (what, turn))
+        img, st = dev.render(cfg, out, accumulate=True)
         assert st.ray_bounces == W.n, (what, st.ray_bounces, W.n)
         assert_planes(_saved(L, ctx, tmp_path / "frame.ptacc")["sums"], fs.planes(total), what)
-        assert_frame(img, fs.resolved(total, spp, clamp=True), what + " resolved")
-        assert_frame(img, want, what + " accumulated against k_pass")
+        same_bytes(img, fs.resolved(total, spp, clamp=True), what + " resolved")
+        same_bytes(img, want, what + " accumulated against k_pass")
     finally:
-        out.close()
+        dev.free(out)

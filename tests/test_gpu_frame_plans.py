@@ -16,12 +16,11 @@ import json
 import os
 import sys
 
-import numpy as np
 import pytest
 
+import gpudev
 import ptlib
-from ptlib import PtConfig, PtStats
-from test_gpu_boundary_rays import _new_ctx
+from gpudev import L  # noqa: F401  (fixture)
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "frame_plan_frames_parent.json")
 SEED = 4
@@ -42,30 +41,12 @@ def frame(L, name):
     """-> {passes, intersect_launches, samples, ray_bounces, image_hash} of one frame in a context of its own"""
     sid, w, h, spp, env, budget, flags, rpp = FRAMES[name]
     sc = ptlib.load_scene_py(ptlib.scene_path(sid))
-    ctx = _new_ctx(L, env)
-    d_out = C.c_void_p()
-    try:
-        assert L.pt_ctx_set_scene(ctx, C.byref(sc.cam), sc.objs, sc.n_objs, sc.tris, sc.n_tris) == 0, L.pt_last_error()
-        assert L.pt_ctx_set_memory_budget(ctx, budget) == 0
-        assert L.pt_device_malloc(0, w * h * 12, C.byref(d_out)) == 0, L.pt_last_error()
-        cfg = PtConfig(w, h, spp, ptlib.BACKEND_WAVEFRONT, SEED, 0, 0, rpp, flags)
-        st = PtStats()
-        assert L.pt_ctx_render(ctx, C.byref(cfg), d_out, None, None, None, None, C.byref(st)) == 0, L.pt_last_error()
-        img = np.zeros((w * h, 3), np.float32)
-        assert L.pt_device_download(0, img.ctypes.data_as(C.c_void_p), d_out, w * h * 12) == 0
-    finally:
-        if d_out:
-            L.pt_device_free(0, d_out)
-        L.pt_ctx_destroy(ctx)
+    with gpudev.Device(L, sc, env=env) as dev:
+        assert L.pt_ctx_set_memory_budget(dev.ctx, budget) == 0
+        cfg = gpudev.config(w, h, spp, backend=ptlib.BACKEND_WAVEFRONT, seed=SEED, rays_per_pass=rpp, flags=flags)
+        img, st = dev.render(cfg, dev.alloc(w * h * 12))
     return {"passes": st.passes, "intersect_launches": st.intersect_launches, "samples": st.samples, "ray_bounces": st.ray_bounces,
             "image_hash": "%016x" % L.pt_image_hash(ptlib._np_f(img), img.size)}
-
-
-@pytest.fixture(scope="module")
-def L():
-    L = ptlib.product()
-    assert L.pt_device_count() >= 1, "no HIP device visible: the product has no CPU fallback"
-    return L
 
 
 @pytest.mark.gpu

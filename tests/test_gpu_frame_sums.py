@@ -17,10 +17,12 @@ import pytest
 
 import boundary_rays as br
 import frame_sums as fs
+import gpudev
 import noise_ref
 import ptlib
 from ptlib import PtConfig, PtObject, PtStats, _np_f
-from test_gpu_boundary_rays import PASS_FORMS, _new_ctx
+from gpudev import L, same_bytes  # noqa: F401  (L: fixture)
+from test_gpu_boundary_rays import PASS_FORMS
 from test_gpu_noise import deal
 
 pytestmark = pytest.mark.gpu
@@ -33,13 +35,6 @@ FULL_TABLE_FORMS = ("pass_cand", "mega")
 BVH_MIN_TRIS = 16  # csrc/pt_device.h kBvhMinTris: a mesh of that many triangles gets a BVH
 
 
-@pytest.fixture(scope="module")
-def L():
-    L = ptlib.product()
-    assert L.pt_device_count() >= 1, "no HIP device visible: the product has no CPU fallback"
-    return L
-
-
 def _has_bvh(sc):
     return any(sc.objs[i].kind == ptlib.PT_MESH and sc.objs[i].tri_count >= BVH_MIN_TRIS for i in range(sc.n_objs))
 
@@ -47,38 +42,10 @@ def _has_bvh(sc):
 def _set_scene(L, ctx, sc, form):
     """the scene set, and the context's kernel for the form's flags the one the form is named for"""
     name, _, _, flags, kernels = form
-    assert L.pt_ctx_set_scene(ctx, C.byref(sc.cam), sc.objs, sc.n_objs, sc.tris, sc.n_tris) == 0, L.pt_last_error()
+    gpudev.set_scene(L, ctx, sc)
     want = kernels[0] if _has_bvh(sc) else kernels[1]
     if want is not None:
         assert L.pt_ctx_pass_kernel(ctx, flags).decode() == want, (name, sc.id)
-
-
-class Out:
-    """a device buffer of npix pixels"""
-
-    def __init__(self, L, npix):
-        self.L, self.npix, self.p = L, npix, C.c_void_p()
-        assert L.pt_device_malloc(0, npix * 12, C.byref(self.p)) == 0
-
-    def get(self, npix):
-        host = np.zeros((npix, 3), np.float32)
-        assert self.L.pt_device_download(0, host.ctypes.data_as(C.c_void_p), self.p, npix * 12) == 0
-        return host
-
-    def close(self):
-        self.L.pt_device_free(0, self.p)
-
-
-def _accumulate(L, ctx, cfg, out):
-    st = PtStats()
-    assert L.pt_ctx_accumulate(ctx, C.byref(cfg), out.p, None, None, None, None, C.byref(st)) == 0, L.pt_last_error()
-    return out.get(L.pt_config_pixels(C.byref(cfg))), st
-
-
-def _render(L, ctx, cfg, out):
-    st = PtStats()
-    assert L.pt_ctx_render(ctx, C.byref(cfg), out.p, None, None, None, None, C.byref(st)) == 0, L.pt_last_error()
-    return out.get(L.pt_config_pixels(C.byref(cfg))), st
 
 
 def _saved(L, ctx, path):
@@ -96,15 +63,6 @@ def assert_planes(got, want, what):
             what, len(bad), got.size, p, c, int(got[c, p]), int(got[c, p]), int(want[c, p]), int(want[c, p])))
 
 
-def assert_frame(got, want, what):
-    g, w = np.ascontiguousarray(got).view(np.uint32), np.ascontiguousarray(want).view(np.uint32)
-    bad = np.argwhere(g != w)
-    if g.shape != w.shape or len(bad):
-        p, c = (int(v) for v in bad[0])
-        raise AssertionError("%s: %d floats differ, first at pixel %d channel %d: device %r, restated %r" % (
-            what, len(bad), p, c, float(got[p, c]), float(want[p, c])))
-
-
 # ---- 1. frames, raw sums ------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("form", FORMS, ids=FORM_IDS)
 def test_every_pixel_sum_is_the_restated_integer(L, form, tmp_path):
@@ -112,8 +70,8 @@ def test_every_pixel_sum_is_the_restated_integer(L, form, tmp_path):
     every pixel and every channel; the frame the call returned and pt_ctx_render's are those sums resolved and clamped, bit for
     bit (pixels that are exactly 1.0 and exactly 0.0 among them); the bounce counts are the walk's ray count."""
     name, env, backend, flags, _ = form
-    ctx = _new_ctx(L, env)
-    out = Out(L, 16 * 12)
+    dev = gpudev.Device(L, env=env)
+    ctx, out = dev.ctx, dev.alloc(16 * 12 * 12)
     compared = 0
     try:
         for frame in fs.WALKS:
@@ -123,21 +81,20 @@ def test_every_pixel_sum_is_the_restated_integer(L, form, tmp_path):
             what = "%s %s seed %x" % (name, sid, seed)
             _set_scene(L, ctx, W.scene, form)
             cfg = PtConfig(w, h, spp, backend, seed, 0, 0, 0, flags)
-            img, st = _accumulate(L, ctx, cfg, out)
+            img, st = dev.render(cfg, out, accumulate=True)
             f = _saved(L, ctx, tmp_path / "frame.ptacc")
             assert f["version"] == 1 and f["counts"].tolist() == [spp] and f["total"] == w * h, what
             assert_planes(f["sums"], fs.planes(total), what)
             compared += f["sums"].size
             want = fs.resolved(total, spp, clamp=True)
             assert (want == 1.0).any() and (want == 0.0).any()
-            assert_frame(img, want, what + " pt_ctx_accumulate's frame")
+            same_bytes(img, want, what + " pt_ctx_accumulate's frame")
             assert st.ray_bounces == W.n, (what, st.ray_bounces, W.n)
-            img, st = _render(L, ctx, cfg, out)
-            assert_frame(img, want, what + " pt_ctx_render's frame")
+            img, st = dev.render(cfg, out)
+            same_bytes(img, want, what + " pt_ctx_render's frame")
             assert st.ray_bounces == W.n, (what, st.ray_bounces, W.n)
     finally:
-        out.close()
-        L.pt_ctx_destroy(ctx)
+        dev.close()
     print("%s: %d pixel sums compared, all equal" % (name, compared))
 
 
@@ -153,38 +110,36 @@ def test_sums_cross_launches(L, cornell, tmp_path):
     """rays_per_pass = the frame's pixels: one sample per pass, every pixel's sum is added to by 8 launches"""
     (sid, w, h, spp, seed), W, sums = cornell
     form = FORMS[0]
-    ctx = _new_ctx(L)
-    out = Out(L, w * h)
+    dev = gpudev.Device(L)
+    ctx, out = dev.ctx, dev.alloc(w * h * 12)
     try:
         _set_scene(L, ctx, W.scene, form)
-        img, st = _accumulate(L, ctx, PtConfig(w, h, spp, 0, seed, 0, 0, w * h, 0), out)
+        img, st = dev.render(PtConfig(w, h, spp, 0, seed, 0, 0, w * h, 0), out, accumulate=True)
         assert st.passes == spp and st.ray_bounces == W.n, st.passes
         total = fs.total_over(sums, range(spp))
         assert_planes(_saved(L, ctx, tmp_path / "passes.ptacc")["sums"], fs.planes(total), "8 passes")
-        assert_frame(img, fs.resolved(total, spp, clamp=True), "8 passes")
+        same_bytes(img, fs.resolved(total, spp, clamp=True), "8 passes")
     finally:
-        out.close()
-        L.pt_ctx_destroy(ctx)
+        dev.close()
 
 
 def test_a_band_holds_its_pixels_sums(L, cornell, tmp_path):
     """the band [37, 151) of cornell - neither end on a row or a wave boundary - holds restated[37:151]"""
     (sid, w, h, spp, seed), W, sums = cornell
     b, e = 37, 151
-    ctx = _new_ctx(L)
-    out = Out(L, w * h)
+    dev = gpudev.Device(L)
+    ctx, out = dev.ctx, dev.alloc(w * h * 12)
     try:
         _set_scene(L, ctx, W.scene, FORMS[0])
-        img, st = _accumulate(L, ctx, PtConfig(w, h, spp, 0, seed, b, e, 0, 0), out)
+        img, st = dev.render(PtConfig(w, h, spp, 0, seed, b, e, 0, 0), out, accumulate=True)
         f = _saved(L, ctx, tmp_path / "band.ptacc")
         assert (f["idx_begin"], f["idx_end"], f["total"]) == (b, e, e - b)
         total = fs.total_over(sums, range(spp))
         assert_planes(f["sums"], fs.planes(total, b, e), "band")
-        assert_frame(img, fs.resolved(total[b:e], spp, clamp=True), "band")
+        same_bytes(img, fs.resolved(total[b:e], spp, clamp=True), "band")
         assert st.ray_bounces == sum(1 for k in W.keys if b <= k[0] < e)
     finally:
-        out.close()
-        L.pt_ctx_destroy(ctx)
+        dev.close()
 
 
 def test_half_a_holds_the_samples_the_schedule_deals_it(L, cornell, tmp_path):
@@ -199,26 +154,25 @@ def test_half_a_holds_the_samples_the_schedule_deals_it(L, cornell, tmp_path):
         runs += r
     assert runs == [(0, 2, True), (2, 6, False), (6, 8, True)] and n_a == 4
     in_a = [s for s0, s1, to_a in runs if to_a for s in range(s0, s1)]
-    ctx = _new_ctx(L)
-    out = Out(L, w * h)
+    dev = gpudev.Device(L)
+    ctx, out = dev.ctx, dev.alloc(w * h * 12)
     try:
         _set_scene(L, ctx, W.scene, FORMS[0])
         assert L.pt_ctx_accum_track_noise(ctx, 1) == 0, L.pt_last_error()
-        _accumulate(L, ctx, PtConfig(w, h, 2, 0, seed, 0, 0, 0, 0), out)
+        dev.render(PtConfig(w, h, 2, 0, seed, 0, 0, 0, 0), out, accumulate=True)
         f = _saved(L, ctx, tmp_path / "half2.ptacc")
         assert f["version"] == 2 and f["counts"].tolist() == [2] and f["n_a"].tolist() == [2]
         assert_planes(f["sums"], fs.planes(fs.total_over(sums, range(2))), "held at 2")
         assert_planes(f["a"], fs.planes(fs.total_over(sums, range(2))), "half A at 2")
-        img, _ = _accumulate(L, ctx, PtConfig(w, h, spp, 0, seed, 0, 0, 0, 0), out)
+        img, _ = dev.render(PtConfig(w, h, spp, 0, seed, 0, 0, 0, 0), out, accumulate=True)
         f = _saved(L, ctx, tmp_path / "half8.ptacc")
         assert f["version"] == 2 and f["counts"].tolist() == [spp] and f["n_a"].tolist() == [len(in_a)]
         total = fs.total_over(sums, range(spp))
         assert_planes(f["sums"], fs.planes(total), "held at 8")
         assert_planes(f["a"], fs.planes(fs.total_over(sums, in_a)), "half A at 8")
-        assert_frame(img, fs.resolved(total, spp, clamp=True), "tracked frame")
+        same_bytes(img, fs.resolved(total, spp, clamp=True), "tracked frame")
     finally:
-        out.close()
-        L.pt_ctx_destroy(ctx)
+        dev.close()
 
 
 # ---- 2. to_fixed and k_resolve at their edges ---------------------------------------------------------------------------------
@@ -261,7 +215,8 @@ def test_to_fixed_and_resolve_at_their_edges(L, form, probe_scenes):
     sample.  The full table on the default wavefront form and the megakernel, n in {1, 3, 65, 1000} on the others."""
     name, env, backend, flags, _ = form
     cases = fs.table_cases(fs.SAMPLE_COUNTS if name in FULL_TABLE_FORMS else fs.SUBSET_COUNTS)
-    ctx = _new_ctx(L, env)
+    dev = gpudev.Device(L, env=env)
+    ctx = dev.ctx
     n_calls, secs = 0, 0.0
     try:
         for sc, index in probe_scenes:
@@ -279,7 +234,7 @@ def test_to_fixed_and_resolve_at_their_edges(L, form, probe_scenes):
                 assert got.view(np.uint32).tolist() == want.view(np.uint32).tolist(), (
                     name, sc.id, n, [float(e) for e in triple], got.tolist(), want.tolist())
     finally:
-        L.pt_ctx_destroy(ctx)
+        dev.close()
     print("%s: %d pt_ctx_radiance calls, %.3f ms per call" % (name, n_calls, 1e3 * secs / max(n_calls, 1)))
 
 
@@ -288,7 +243,8 @@ def test_the_door_leaves_the_scene_untouched(L, probe_scenes):
     """pt_ctx_set_object, pt_ctx_set_scene and pt_render refuse an emission or colour component that is infinite, NaN or negative
     with PT_ERR_INVALID and a message naming the field; the context keeps the scene it had: the same tables, the same radiance"""
     sc, index = probe_scenes[1]
-    ctx = _new_ctx(L)
+    dev = gpudev.Device(L)
+    ctx = dev.ctx
     try:
         _set_scene(L, ctx, sc, FORMS[0])
         before = (C.c_uint64 * 14)()
@@ -315,4 +271,4 @@ def test_the_door_leaves_the_scene_untouched(L, probe_scenes):
         got, _ = _radiance(L, ctx, 3, 0, 0)
         assert got.tolist() == want.tolist()
     finally:
-        L.pt_ctx_destroy(ctx)
+        dev.close()

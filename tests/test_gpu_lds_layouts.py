@@ -13,7 +13,6 @@ normal.  A frame alone can miss a wrong record whose object few pixels see.
 Every context runs with PT_LDS_PAD=0, under which the library says on stderr the layout each launcher of the context runs with
 whenever it changes; the test reads those lines and checks that each case ran the layout the CPU ladder expects for it."""
 import ctypes as C
-import os
 import re
 import time
 
@@ -21,9 +20,10 @@ import numpy as np
 import pytest
 
 import boundary_rays as br
+import gpudev
 import lds_layouts as ll
 import ptlib
-from ptlib import PtConfig, PtStats, _np_f
+from ptlib import PtStats, _np_f
 
 pytestmark = pytest.mark.gpu
 
@@ -56,22 +56,6 @@ class _Said:
         return list(last)
 
 
-def _new_ctx(L, env):
-    env = dict(env, PT_LDS_PAD="0")
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        ctx = C.c_void_p()
-        assert L.pt_ctx_create(0, C.byref(ctx)) == 0, L.pt_last_error()
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-    return ctx
-
-
 def _forms(rung):
     """(name, tuning environment, backend, flags, which launcher's line must equal the rung's, or None)."""
     env = rung.env
@@ -90,10 +74,6 @@ def _forms(rung):
         if any(rung.scene.objs[i].reflect_type == ptlib.REFLECT["Refract"] for i in range(rung.scene.n_objs)):
             out.append(("glass_defer", dict(env, PT_GLASS_DEFER="1"), 0, 0, None))
     return out
-
-
-def _set_scene(L, ctx, sc):
-    assert L.pt_ctx_set_scene(ctx, C.byref(sc.cam), sc.objs, sc.n_objs, sc.tris, sc.n_tris) == 0, L.pt_last_error()
 
 
 def _frame(rung):
@@ -115,7 +95,7 @@ def test_ladder_frames_and_table_edge_rays(ladder, capfd):
         key = tuple(sorted(env.items()))
         if key not in ctxs:
             said.now(None)  # (whatever was said before belongs to no context of this test)
-            ctxs[key] = _new_ctx(L, env)
+            ctxs[key] = gpudev.Device(L, env=dict(env, PT_LDS_PAD="0"))
         return key, ctxs[key]
 
     try:
@@ -127,17 +107,11 @@ def test_ladder_frames_and_table_edge_rays(ladder, capfd):
                 want, cnt, _ = ptlib.oracle_render(sc, w, h, spp, seed)
                 ref = None
                 for form, env, backend, flags, which in _forms(rung):
-                    key, ctx = ctx_for(env)
-                    _set_scene(L, ctx, sc)
-                    cfg = PtConfig(w, h, spp, backend, seed, 0, 0, 0, flags)
-                    dev = C.c_void_p()
-                    assert L.pt_device_malloc(0, w * h * 12, C.byref(dev)) == 0
-                    st = PtStats()
-                    rc = L.pt_ctx_render(ctx, C.byref(cfg), dev, None, None, None, None, C.byref(st))
-                    img = np.empty((w * h, 3), np.float32)
-                    assert L.pt_device_download(0, _np_f(img), dev, img.nbytes) == 0
-                    L.pt_device_free(0, dev)
-                    assert rc == 0, (rung.cliff, rung.side, form, L.pt_last_error())
+                    key, dev = ctx_for(env)
+                    dev.set_scene(sc)
+                    out = dev.alloc(w * h * 12)
+                    img, st = dev.render(gpudev.config(w, h, spp, backend=backend, seed=seed, flags=flags), out)
+                    dev.free(out)
                     n_frames += 1
                     lines = said.now(key)
                     if which is not None:
@@ -161,12 +135,12 @@ def test_ladder_frames_and_table_edge_rays(ladder, capfd):
                     if tag == "first":
                         assert all(c.ray_bounces == 1 for _, c in refs), rung.cliff
                     for form, env, backend, flags, which in _forms(rung)[:3]:
-                        key, ctx = ctx_for(env)
-                        _set_scene(L, ctx, scp)
+                        key, dev = ctx_for(env)
+                        dev.set_scene(scp)
                         for j, ((o, d), (want_rgb, want_cnt)) in enumerate(zip(rays, refs)):
                             out = np.zeros(3, np.float32)
                             st = PtStats()
-                            rc = L.pt_ctx_radiance(ctx, _np_f(np.ascontiguousarray(o)), _np_f(np.ascontiguousarray(d)), depth, 1,
+                            rc = L.pt_ctx_radiance(dev.ctx, _np_f(np.ascontiguousarray(o)), _np_f(np.ascontiguousarray(d)), depth, 1,
                                                    pseed, j, backend, flags, _np_f(out), C.byref(st))
                             assert rc == 0, L.pt_last_error()
                             n_rays += 1
@@ -180,8 +154,8 @@ def test_ladder_frames_and_table_edge_rays(ladder, capfd):
                         if which is not None:
                             ran.append((rung, form + " probe " + tag, which, lines[which]))
     finally:
-        for ctx in ctxs.values():
-            L.pt_ctx_destroy(ctx)
+        for dev in ctxs.values():
+            dev.close()
     # every case ran with the layout the CPU ladder expects for it
     for rung, form, which, line in ran:
         assert line == rung.lines[which], (rung.cliff, rung.side, form, line, rung.lines[which])

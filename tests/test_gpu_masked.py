@@ -8,9 +8,11 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import gpudev
 import masked_ref as ref
 import ptlib
 from masked_ref import F32, U8
+from gpudev import L  # noqa: F401  (fixture)
 from ptlib import PtAdaptiveParams, PtAdaptiveStats, PtConfig, PtSelectParams, PtStats
 
 pytestmark = pytest.mark.gpu
@@ -24,59 +26,15 @@ N = W * H
 MASKS = ("empty", "first", "last", "63", "64", "65", "row", "checker", "ones", "random")
 
 
-def hip_runtime():
-    """the HIP runtime the product is bound to: the copy already mapped into this process that is not torch's"""
-    paths = {line.split()[-1] for line in open("/proc/self/maps") if "/libamdhip64.so" in line}
-    own = sorted(p for p in paths if "/torch/" not in p)
-    assert own, "libptrace_hip.so has not mapped a HIP runtime: %r" % sorted(paths)
-    hip = C.CDLL(own[0])
-    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    return hip
-
-
-@pytest.fixture(scope="module")
-def L():
-    L = ptlib.product()
-    assert L.pt_device_count() >= 1, "no HIP device visible: the product has no CPU fallback"
-    frame = [C.c_void_p, C.POINTER(PtConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PtStats)]
-    adaptive = [C.c_void_p, C.POINTER(PtConfig), C.POINTER(PtAdaptiveParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PtStats), C.POINTER(PtAdaptiveStats)]
-    return L
-
-
-class Dev:
+class Dev(gpudev.Device):
     """a context (with a scene, if one is given) and device buffers that go with it"""
 
     def __init__(self, L, sid=None):
-        self.L, self.hip, self.bufs = L, hip_runtime(), []
-        self.ctx = C.c_void_p()
-        assert L.pt_ctx_create(0, C.byref(self.ctx)) == 0, L.pt_last_error()
-        if sid:
-            sc = ptlib.load_scene_py(ptlib.scene_path(sid))
-            assert L.pt_ctx_set_scene(self.ctx, C.byref(sc.cam), sc.objs, sc.n_objs, sc.tris, sc.n_tris) == 0, L.pt_last_error()
-
-    def alloc(self, nbytes):
-        p = C.c_void_p()
-        assert self.L.pt_device_malloc(0, nbytes, C.byref(p)) == 0, self.L.pt_last_error()
-        self.bufs.append(p)
-        return p
-
-    def upload(self, p, host, offset=0):
-        host = np.ascontiguousarray(host)
-        assert self.hip.hipMemcpy(C.c_void_p(p.value + offset), host.ctypes.data_as(C.c_void_p), host.nbytes, 1) == 0  # host to device
-
-    def download(self, p, count, dtype=F32, offset=0):
-        host = np.zeros(count, dtype=dtype)
-        assert self.L.pt_device_download(0, host.ctypes.data_as(C.c_void_p), C.c_void_p(p.value + offset), host.nbytes) == 0
-        return host
+        super().__init__(L, ptlib.load_scene_py(ptlib.scene_path(sid)) if sid else None)
 
     def render(self, cfg, d_out=None):
         """pt_ctx_render: (the frame as (pixels, 3), its stats)"""
-        n = self.L.pt_config_pixels(C.byref(cfg))
-        d_out = d_out or self.alloc(n * 12)
-        st = PtStats()
-        assert self.L.pt_ctx_render(self.ctx, C.byref(cfg), d_out, None, None, None, None, C.byref(st)) == 0, self.L.pt_last_error()
-        return self.download(d_out, n * 3).reshape(n, 3), st
+        return super().render(cfg, d_out or self.alloc(self.L.pt_config_pixels(C.byref(cfg)) * 12))
 
     def masked(self, cfg, mask, want=0, cancel=None, mask_offset=0, d_mask=None, d_rgb=None, fill=True):
         """pt_ctx_render_masked into a frame of sentinels: (the frame as (pixels, 3), *n_pixels, the stats); the floats behind
@@ -86,23 +44,16 @@ class Dev:
         d_rgb = d_rgb or self.alloc((n * 3 + GUARD) * 4)
         self.upload(d_mask, np.asarray(mask, dtype=U8), mask_offset)
         if fill:
-            self.upload(d_rgb, np.full(n * 3 + GUARD, SENTINEL, dtype=F32))
+            self.fill_guarded(d_rgb, n * 3, GUARD, SENTINEL)
         st, count = PtStats(), C.c_uint32(12345)
         rc = self.L.pt_ctx_render_masked(self.ctx, C.byref(cfg), C.c_void_p(d_mask.value + mask_offset), d_rgb, None,
                                          C.cast(cancel, C.c_void_p) if cancel else None, C.byref(st), C.byref(count))
         assert rc == want, (rc, self.L.pt_last_error())
-        got = self.download(d_rgb, n * 3 + GUARD)
-        assert (got[n * 3:] == SENTINEL).all(), "floats behind the frame were written"
-        return got[:n * 3].reshape(n, 3), count.value, st
-
-    def close(self):
-        for p in self.bufs:
-            self.L.pt_device_free(0, p)
-        self.L.pt_ctx_destroy(self.ctx)
+        return self.read_guarded(d_rgb, n * 3, GUARD, SENTINEL, "the frame").reshape(n, 3), count.value, st
 
 
-def cfg_of(spp, w=W, h=H, backend=0, seed=SEED, band=(0, 0), flags=0):
-    return PtConfig(w, h, spp, backend, seed, band[0], band[1], 0, flags)
+def cfg_of(spp, w=W, h=H, backend=0, seed=SEED, **kw):
+    return gpudev.config(w, h, spp, backend=backend, seed=seed, **kw)
 
 
 @pytest.fixture(scope="module")
@@ -193,12 +144,12 @@ def test_select_counts_over_many_workgroups(L, devs):
     weight = ref.plane(n, 0.0, 3)
     d_w, d_m = d.alloc(n * 4), d.alloc(n + GUARD)
     d.upload(d_w, weight)
-    d.upload(d_m, np.full(n + GUARD, 0xAB, dtype=U8))
+    d.fill_guarded(d_m, n, GUARD, 0xAB, U8)
     p, count = PtSelectParams(0.0, 0.0, 0), C.c_uint32(0)
     assert L.pt_ctx_select_pixels(d.ctx, w, h, C.byref(p), d_w, None, d_m, C.byref(count), None) == 0, L.pt_last_error()
     exp, ones = ref.select(weight=weight, weight_max=0.0)
-    got = d.download(d_m, n + GUARD, U8)
-    assert got[:n].tobytes() == exp.tobytes() and (got[n:] == 0xAB).all() and count.value == ones
+    got = d.read_guarded(d_m, n, GUARD, 0xAB, "the mask", U8)
+    assert got.tobytes() == exp.tobytes() and count.value == ones
 
 
 # ----------------------------------------------------------------------------------------------------- render masked
@@ -239,15 +190,12 @@ def test_any_nonzero_byte_selects_and_the_mask_may_be_unaligned(devs):
 
 def test_a_list_that_has_to_grow(L):
     """a fresh context's first call selects every pixel: the list starts short, is grown to the length and the pass runs again"""
-    d = Dev(L, "cornell")
-    try:
+    with Dev(L, "cornell") as d:
         cfg = cfg_of(8)
         R, _ = d.render(cfg)
         mask = make_mask("ones")
         got, count, _ = d.masked(cfg, mask)
         check_frame(got, count, mask, R, "grown")
-    finally:
-        d.close()
 
 
 def test_no_bvh_gives_the_same_bytes(devs):
@@ -299,8 +247,7 @@ def test_a_raised_cancel_byte_leaves_the_frame_alone(L, devs):
 
 def test_refusals_that_need_a_context(L, devs):
     """each call breaks one rule and every rule checked after it"""
-    bare = Dev(L)
-    try:
+    with Dev(L) as bare:
         p = bare.alloc(64)
         n = C.c_uint32(77)
 
@@ -327,8 +274,6 @@ def test_refusals_that_need_a_context(L, devs):
         rc, msg = call(d, bad)
         assert rc == PT_ERR_INVALID and "backend" in msg
         assert n.value == 77
-    finally:
-        bare.close()
 
 
 # ------------------------------------------------------------------------------------------------------------- state
@@ -391,8 +336,7 @@ def test_upsample_select_retrace(L):
     the frame is the upsampled one with exactly the weight-0 pixels replaced by pt_ctx_render's"""
     (w, h), (Wf, Hf), spp = (16, 12), (33, 25), 4
     n, nl = Wf * Hf, w * h
-    d = Dev(L, "cornell")
-    try:
+    with Dev(L, "cornell") as d:
         lo = dict(color=d.alloc(nl * 12), albedo=d.alloc(nl * 12), normal=d.alloc(nl * 12), depth=d.alloc(nl * 4), oid=d.alloc(nl * 4))
         hi = dict(albedo=d.alloc(n * 12), normal=d.alloc(n * 12), depth=d.alloc(n * 4), oid=d.alloc(n * 4))
         d_up, d_weight, d_mask = d.alloc((n * 3 + GUARD) * 4), d.alloc(n * 4), d.alloc(n)
@@ -400,7 +344,7 @@ def test_upsample_select_retrace(L):
         d.render(lcfg, lo["color"])
         assert L.pt_ctx_render_aov(d.ctx, C.byref(lcfg), lo["albedo"], lo["normal"], lo["depth"], lo["oid"], None) == 0, L.pt_last_error()
         assert L.pt_ctx_render_aov(d.ctx, C.byref(cfg), hi["albedo"], hi["normal"], hi["depth"], hi["oid"], None) == 0, L.pt_last_error()
-        d.upload(d_up, np.full(n * 3 + GUARD, SENTINEL, dtype=F32))
+        d.fill_guarded(d_up, n * 3, GUARD, SENTINEL)
         assert L.pt_ctx_upsample(d.ctx, Wf, Hf, w, h, None, lo["color"], lo["depth"], lo["oid"], lo["normal"], lo["albedo"], hi["depth"],
                                  hi["oid"], hi["normal"], hi["albedo"], d_up, d_weight, None) == 0, L.pt_last_error()
         up = d.download(d_up, n * 3).reshape(n, 3)
@@ -413,10 +357,7 @@ def test_upsample_select_retrace(L):
         assert 0 < ones.value < n
         count = C.c_uint32(0)
         assert L.pt_ctx_render_masked(d.ctx, C.byref(cfg), d_mask, d_up, None, None, None, C.byref(count)) == 0, L.pt_last_error()
-        got = d.download(d_up, n * 3 + GUARD)
-        assert (got[n * 3:] == SENTINEL).all() and count.value == ones.value
-        got = got[:n * 3].reshape(n, 3)
+        got = d.read_guarded(d_up, n * 3, GUARD, SENTINEL, "the upsampled frame").reshape(n, 3)
+        assert count.value == ones.value
         R, _ = d.render(cfg)
         assert got[fallback].tobytes() == R[fallback].tobytes() and got[~fallback].tobytes() == up[~fallback].tobytes()
-    finally:
-        d.close()

@@ -11,10 +11,12 @@ import subprocess
 import numpy as np
 import pytest
 
+import gpudev
 import noise_ref
 import ptlib
+from gpudev import L  # noqa: F401  (fixture)
 from ptlib import PtNoiseStats, PtNoiseTarget, PtStats
-from test_gpu_accumulate import Dev, MEGA, NO_BVH, WAVE, cfg_of
+from test_gpu_accumulate import MEGA, NO_BVH, WAVE
 
 pytestmark = pytest.mark.gpu
 
@@ -23,13 +25,6 @@ W, H, SEED = 64, 40, 8
 BW, BH = 96, 64  # the frames of the behaviour tests (the goldens' size)
 STUDY = json.load(open(os.path.join(ptlib.ROOT, "profiles", "noise_cpu_study.json")))
 f32 = np.float32
-
-
-@pytest.fixture(scope="module")
-def L():
-    L = ptlib.product()
-    assert L.pt_device_count() >= 1, "no HIP device visible: the product has no CPU fallback"
-    return L
 
 
 @pytest.fixture(scope="module")
@@ -42,15 +37,30 @@ def mesh():
     return ptlib.load_scene_py(ptlib.scene_path("mesh"))
 
 
-class NDev(Dev):
-    """Dev with the noise entry points; tracked=True switches tracking on before any frame"""
+def cfg_of(spp, backend=WAVE, seed=SEED, w=W, h=H, **kw):
+    return gpudev.config(w, h, spp, backend=backend, seed=seed, **kw)
+
+
+class NDev(gpudev.Device):
+    """one context, one scene, an output frame and an error map, with the accumulate and the noise entry points; tracked=True
+    switches tracking on before any frame"""
 
     def __init__(self, L, sc, npix_max, tracked=True):
-        super().__init__(L, sc, npix_max)
-        self.d_err = C.c_void_p()
-        assert L.pt_device_malloc(0, npix_max * 4, C.byref(self.d_err)) == 0
+        super().__init__(L, sc)
+        self.d_out, self.d_err = self.alloc(npix_max * 12), self.alloc(npix_max * 4)
         if tracked:
             assert L.pt_ctx_accum_track_noise(self.ctx, 1) == 0, L.pt_last_error()
+
+    def render(self, cfg, ptr=None, **kw):
+        return super().render(cfg, ptr or self.d_out, **kw)
+
+    def accumulate(self, cfg, **kw):
+        return self.render(cfg, accumulate=True, **kw)
+
+    def info(self, cfg):
+        lo, hi = C.c_uint32(), C.c_uint32()
+        assert self.L.pt_ctx_accum_info(self.ctx, C.byref(cfg), C.byref(lo), C.byref(hi)) == 0, self.L.pt_last_error()
+        return lo.value, hi.value
 
     def noise(self, cfg, want=0, with_map=True):
         ns = PtNoiseStats()
@@ -58,10 +68,7 @@ class NDev(Dev):
         assert rc == want, (rc, self.L.pt_last_error())
         if rc or not with_map:
             return ns, None
-        n = self.L.pt_config_pixels(C.byref(cfg))
-        err = np.zeros(n, dtype=f32)
-        assert self.L.pt_device_download(0, err.ctypes.data_as(C.c_void_p), self.d_err, n * 4) == 0
-        return ns, err
+        return ns, self.download(self.d_err, self.L.pt_config_pixels(C.byref(cfg)))
 
     def until(self, cfg, tgt, want=0, cancel=None, cb=None):
         st, ns = PtStats(), PtNoiseStats()
@@ -69,15 +76,11 @@ class NDev(Dev):
                                             C.cast(cancel, C.c_void_p) if cancel else None,
                                             C.cast(cb, C.c_void_p) if cb else None, None, C.byref(st), C.byref(ns))
         assert rc == want, (rc, self.L.pt_last_error())
-        return self.download(self.d_out, self.L.pt_config_pixels(C.byref(cfg))), st, ns
+        return self.pixels(self.d_out, self.L.pt_config_pixels(C.byref(cfg))), st, ns
 
     def saved(self, path):
         assert self.L.pt_ctx_accum_save(self.ctx, str(path).encode()) == 0, self.L.pt_last_error()
         return noise_ref.parse_checkpoint(open(path, "rb").read())
-
-    def close(self):
-        self.L.pt_device_free(0, self.d_err)
-        super().close()
 
 
 def deal(c, n_a, t):
@@ -148,8 +151,7 @@ def test_tracking_changes_no_image(L, request, scene, backend, flags):
 # ---- 2. A is what the rule says -------------------------------------------------------------------------------------
 
 def test_half_a_is_what_the_rule_says(L, cornell, tmp_path):
-    d = NDev(L, cornell, W * H)
-    try:
+    with NDev(L, cornell, W * H) as d:
         runs, n_a = [], 0
         prev = 0
         for t in (8, 24, 64):
@@ -158,8 +160,6 @@ def test_half_a_is_what_the_rule_says(L, cornell, tmp_path):
             runs += r
             prev = t
         f = d.saved(tmp_path / "tracked.ptacc")
-    finally:
-        d.close()
     assert f["version"] == 2 and f["counts"].tolist() == [64] and f["n_a"].tolist() == [n_a] == [32]
     S = plain_sums(L, cornell, [s for r in runs for s in r[:2]], tmp_path)
     want = np.zeros_like(f["a"])
@@ -175,8 +175,7 @@ def test_half_a_is_what_the_rule_says(L, cornell, tmp_path):
 @pytest.mark.parametrize("backend", [WAVE, MEGA])
 def test_half_a_after_a_cancelled_call(L, cornell, tmp_path, backend):
     npix, T = W * H, 32
-    d = NDev(L, cornell, npix)
-    try:
+    with NDev(L, cornell, npix) as d:
         flag = (C.c_uint8 * 1)(0)
 
         def on_progress(user, frac):
@@ -200,8 +199,6 @@ def test_half_a_after_a_cancelled_call(L, cornell, tmp_path, backend):
         assert np.array_equal(img2, d.render(cfg_of(T))[0])
         f2 = d.saved(tmp_path / "resumed.ptacc")
         assert f2["counts"].tolist() == [T] and f2["n_a"].tolist() == [n_a2]
-    finally:
-        d.close()
     S = plain_sums(L, cornell, [n_a, c, T] + [s for r in runs for s in r[:2]], tmp_path)
     assert np.array_equal(f["sums"], S[c]) and np.array_equal(f["a"], S[n_a])
     want = S[n_a].copy()
@@ -243,27 +240,20 @@ def check_against_reference(d, cfg, f):
                                          ("mesh", dict(chunks=(64, 1, 3)))])
 def test_kernel_is_the_contract(L, request, tmp_path, scene, extra):
     sc = request.getfixturevalue(scene)
-    d = NDev(L, sc, BW * BH)
-    try:
+    with NDev(L, sc, BW * BH) as d:
         for t in (8, 24, 64):
             d.accumulate(cfg_of(t, w=BW, h=BH, **extra))
         f = d.saved(tmp_path / "k.ptacc")
         assert f["n_a"].tolist() == [32]
         ns, err = check_against_reference(d, cfg_of(1, w=BW, h=BH, **extra), f)
         assert 0.0 < ns.mean_error < 12.0 and err.min() >= 0.0 and err.max() <= 12.0 and (err > 0).any()
-    finally:
-        d.close()
 
 
 def test_kernel_on_unequal_halves_from_a_plain_checkpoint(L, mesh, tmp_path):
-    plain = NDev(L, mesh, BW * BH, tracked=False)
-    try:
+    with NDev(L, mesh, BW * BH, tracked=False) as plain:
         plain.accumulate(cfg_of(10, w=BW, h=BH))
         assert plain.saved(tmp_path / "v1.ptacc")["version"] == 1
-    finally:
-        plain.close()
-    d = NDev(L, mesh, BW * BH)
-    try:
+    with NDev(L, mesh, BW * BH) as d:
         assert L.pt_ctx_accum_load(d.ctx, str(tmp_path / "v1.ptacc").encode()) == 0, L.pt_last_error()
         d.noise(cfg_of(1, w=BW, h=BH), want=PT_ERR_INVALID)  # everything so far is B: no estimate yet
         f0 = d.saved(tmp_path / "v1_as_v2.ptacc")
@@ -275,8 +265,6 @@ def test_kernel_on_unequal_halves_from_a_plain_checkpoint(L, mesh, tmp_path):
         assert f["counts"].tolist() == [30] and f["n_a"].tolist() == [12]
         ns, _ = check_against_reference(d, cfg_of(1, w=BW, h=BH), f)
         assert (ns.spp_a_min, ns.spp_b_min) == (12, 18)
-    finally:
-        d.close()
 
 
 def test_kernel_on_a_frame_of_several_parts(L, cornell, tmp_path):
@@ -284,8 +272,7 @@ def test_kernel_on_a_frame_of_several_parts(L, cornell, tmp_path):
     without an estimate (+inf in the map)"""
     w, h = 2048, 1040
     npix, part = w * h, 1 << 20
-    d = NDev(L, cornell, npix)
-    try:
+    with NDev(L, cornell, npix) as d:
         flag = (C.c_uint8 * 1)(0)
 
         def on_progress(user, frac):
@@ -307,8 +294,6 @@ def test_kernel_on_a_frame_of_several_parts(L, cornell, tmp_path):
         f = d.saved(tmp_path / "parts_done.ptacc")
         assert f["counts"].tolist() == [8, 8, 8] and f["n_a"][0] == 4 and f["n_a"][2] == 4
         check_against_reference(d, cfg_of(1, w=w, h=h), f)
-    finally:
-        d.close()
 
 
 # ---- 4. it behaves like an error estimate ---------------------------------------------------------------------------
@@ -325,8 +310,7 @@ def test_estimate_falls_and_tracks_the_actual_error(L, request, scene):
     gold = np.load(os.path.join(ptlib.ROOT, "tests", "golden", "denoise_%s_%dx%d_4096.npz" % (scene, BW, BH)))
     assert int(gold["seed"]) == 5 and int(gold["spp"]) == 4096
     truth = gold["frame"].reshape(BW * BH, 3).T.astype(f32)
-    d = NDev(L, sc, BW * BH)
-    try:
+    with NDev(L, sc, BW * BH) as d:
         got = {}
         for t in (16, 256):
             img, _ = d.accumulate(cfg_of(t, w=BW, h=BH, seed=11))
@@ -341,16 +325,13 @@ def test_estimate_falls_and_tracks_the_actual_error(L, request, scene):
         assert got[256][0] / got[16][0] <= b["fall_256_over_16"]
         for t in (16, 256):
             assert b["ratio_lo"][str(t)] <= got[t][0] / got[t][1] <= b["ratio_hi"][str(t)], (t, got[t])
-    finally:
-        d.close()
 
 
 # ---- 5. until -------------------------------------------------------------------------------------------------------
 
 def test_until_stops_at_the_target(L, cornell):
     target, cap = STUDY["bounds"]["cornell"]["target"], 1024  # between the study's rows for 64 and 256 samples
-    d = NDev(L, cornell, BW * BH)
-    try:
+    with NDev(L, cornell, BW * BH) as d:
         fracs = []
         cb = ptlib.PROGRESS_FN(lambda user, frac: fracs.append(frac))
         cfg = cfg_of(cap, w=BW, h=BH, seed=11)
@@ -374,13 +355,10 @@ def test_until_stops_at_the_target(L, cornell):
         below = float(np.nextafter(f32(edge), f32(0)))
         _, st, ns3 = d.until(cfg_of(2 * reached, w=BW, h=BH, seed=11), PtNoiseTarget(0.0, 0.9, below, 0))
         assert ns3.spp_max == 2 * reached and st.samples == BW * BH * reached
-    finally:
-        d.close()
 
 
 def test_until_unreachable_target_ends_at_the_cap(L, cornell):
-    d = NDev(L, cornell, W * H)
-    try:
+    with NDev(L, cornell, W * H) as d:
         img, st, ns = d.until(cfg_of(48, MEGA), PtNoiseTarget(1e-6, 0.0, 0.0, 8))  # 8, 16, 32, 48
         assert ns.spp_max == ns.spp_min == 48 and ns.mean_error > 1e-6 and st.samples == W * H * 48
         assert np.array_equal(img, d.render(cfg_of(48))[0])
@@ -389,14 +367,11 @@ def test_until_unreachable_target_ends_at_the_cap(L, cornell):
         img, st, ns = d.until(cfg_of(3), PtNoiseTarget(0.5, 0.0, 0.0, 0))
         assert ns.spp_max == 3 and ns.pixels == 0 and ns.mean_error == float("inf")
         assert np.array_equal(img, d.render(cfg_of(3))[0])
-    finally:
-        d.close()
 
 
 def test_until_cancel_and_continue(L, cornell):
     npix = W * H
-    d = NDev(L, cornell, npix)
-    try:
+    with NDev(L, cornell, npix) as d:
         flag = (C.c_uint8 * 1)(0)
 
         def on_progress(user, frac):
@@ -414,27 +389,21 @@ def test_until_cancel_and_continue(L, cornell):
         img, st, ns = d.until(cfg_of(64), tgt)
         assert ns.spp_max == 64 and st.samples == npix * (64 - k)
         assert np.array_equal(img, d.render(cfg_of(64))[0])
-    finally:
-        d.close()
 
 
 def test_until_needs_tracking(L, cornell):
-    d = NDev(L, cornell, W * H, tracked=False)
-    try:
+    with NDev(L, cornell, W * H, tracked=False) as d:
         d.until(cfg_of(32), PtNoiseTarget(0.1, 0.0, 0.0, 0), want=PT_ERR_INVALID)
         assert d.info(cfg_of(32)) == (0, 0)
         d.accumulate(cfg_of(8))
         d.until(cfg_of(32), PtNoiseTarget(0.1, 0.0, 0.0, 0), want=PT_ERR_INVALID)
         assert d.info(cfg_of(32)) == (8, 8)
-    finally:
-        d.close()
 
 
 # ---- 6. refusals and lifetime ---------------------------------------------------------------------------------------
 
 def test_refusals_and_lifetime(L, cornell, mesh, tmp_path):
-    d = NDev(L, cornell, W * H, tracked=False)
-    try:
+    with NDev(L, cornell, W * H, tracked=False) as d:
         d.accumulate(cfg_of(8))
         d.noise(cfg_of(8), want=PT_ERR_INVALID)  # tracking off
         assert L.pt_ctx_accum_track_noise(d.ctx, 1) == PT_ERR_INVALID and b"pt_ctx_accum_reset" in L.pt_last_error()
@@ -477,8 +446,7 @@ def test_refusals_and_lifetime(L, cornell, mesh, tmp_path):
             ns2, _ = d.noise(cfg_of(8), with_map=False)
             assert ns2.mean_error == ns.mean_error, name
         # the round trip: a version-2 file switches tracking on for its frame in a context that was not tracking
-        other = NDev(L, cornell, W * H, tracked=False)
-        try:
+        with NDev(L, cornell, W * H, tracked=False) as other:
             assert L.pt_ctx_accum_load(other.ctx, str(tmp_path / "before.ptacc").encode()) == 0, L.pt_last_error()
             ns3, _ = other.noise(cfg_of(8), with_map=False)
             assert ns3.mean_error == ns.mean_error and ns3.histogram[:] == ns.histogram[:]
@@ -486,8 +454,6 @@ def test_refusals_and_lifetime(L, cornell, mesh, tmp_path):
             assert st.samples == W * H * 8 and np.array_equal(img, other.render(cfg_of(16))[0])
             n_a = deal(8, deal(3, deal(0, 0, 3)[1], 8)[1], 16)[1]
             assert other.saved(tmp_path / "other.ptacc")["n_a"].tolist() == [n_a]
-        finally:
-            other.close()
         # reset and set_scene drop A with the held sums
         assert L.pt_ctx_accum_reset(d.ctx) == 0
         d.noise(cfg_of(8), want=PT_ERR_INVALID)
@@ -501,8 +467,6 @@ def test_refusals_and_lifetime(L, cornell, mesh, tmp_path):
         d.noise(cfg_of(8), want=PT_ERR_INVALID)
         f = d.saved(tmp_path / "newkey.ptacc")
         assert f["seed"] == SEED + 1 and f["n_a"].tolist() == [4]
-    finally:
-        d.close()
 
 
 # ---- 7. CLI ---------------------------------------------------------------------------------------------------------

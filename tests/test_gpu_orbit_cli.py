@@ -8,6 +8,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import gpudev
 import ptlib
 import reproject_ref
 from ptlib import PtConfig, PtDenoiseVarParams, PtPresentParams, PtReprojectVarParams, PtStats
@@ -26,19 +27,10 @@ def cam_dict(cam):
 
 def loop_with_set_scene(L, sc, step, out_size=None, exposure=0.0):
     """frames 0..FRAMES-1 as RGB8 bytes: pt_ctx_set_scene -> render -> render_aov -> reproject_var -> denoise_var -> present"""
-    vp = C.c_void_p
     n = W * H
     ow, oh = out_size or (W, H)
-    ctx = vp()
-    assert L.pt_ctx_create(0, C.byref(ctx)) == 0, L.pt_last_error()
-    bufs = []
-
-    def dev(nbytes):
-        p = vp()
-        assert L.pt_device_malloc(0, nbytes, C.byref(p)) == 0
-        bufs.append(p)
-        return p
-
+    own = gpudev.Device(L)
+    ctx, dev = own.ctx, own.alloc
     # a side: colour, len, moments, depth, object id, normal
     sides = [[dev(n * k * 4) for k in (3, 1, 2, 1, 1, 3)] for _ in range(2)]
     albedo, error, shown, px = dev(n * 12), dev(n * 4), dev(n * 12), dev(ow * oh * 3)
@@ -53,7 +45,7 @@ def loop_with_set_scene(L, sc, step, out_size=None, exposure=0.0):
             d = reproject_ref.orbit(cam_dict(sc.cam), k * step)
             cam = ptlib.make_camera(d["position"], d["direction"], d["focal_length"], d["sensor_width"], d["aspect_ratio"])
             st = PtStats()
-            assert L.pt_ctx_set_scene(ctx, C.byref(cam), sc.objs, sc.n_objs, sc.tris, sc.n_tris) == 0, L.pt_last_error()
+            own.set_scene(sc, cam)
             assert L.pt_ctx_render(ctx, C.byref(cfg), cur[0], None, None, None, None, C.byref(st)) == 0, L.pt_last_error()
             assert L.pt_ctx_render_aov(ctx, C.byref(cfg), albedo, cur[5], cur[3], cur[4], None) == 0, L.pt_last_error()
             h = [hist[0], hist[1], hist[2], hist[3], hist[4], hist[5]] if hist_cam is not None else [None] * 6
@@ -62,15 +54,11 @@ def loop_with_set_scene(L, sc, step, out_size=None, exposure=0.0):
                                           cur[0], cur[1], cur[2], error, None) == 0, L.pt_last_error()
             assert L.pt_ctx_denoise_var(ctx, W, H, C.byref(dp), cur[0], error, albedo, cur[5], cur[3], shown, None) == 0, L.pt_last_error()
             assert L.pt_ctx_present(ctx, W, H, C.byref(pp), shown, px, None) == 0, L.pt_last_error()
-            host = np.zeros(ow * oh * 3, np.uint8)
-            assert L.pt_device_download(0, host.ctypes.data_as(vp), px, host.nbytes) == 0
-            frames.append(host.tobytes())
+            frames.append(own.download(px, ow * oh * 3, np.uint8).tobytes())
             cur, hist = hist, cur
             hist_cam = cam
     finally:
-        for p in bufs:
-            L.pt_device_free(0, p)
-        L.pt_ctx_destroy(ctx)
+        own.close()
     return frames
 
 

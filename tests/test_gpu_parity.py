@@ -9,6 +9,7 @@ import os
 import numpy as np
 import pytest
 
+import gpudev
 import ptlib
 from ptlib import PtConfig, PtStats, PtoConfig, _np_f
 
@@ -471,28 +472,11 @@ def test_mesh_walk_forms_agree(gpu):
     res = {}
     for name, env, flags in (("queue", {}, 0), ("tiny queue", {"PT_WALK_QUEUE_CAP": "128"}, 0),
                              ("k_pass_bvh", {"PT_CAND_BVH": "0"}, 0), ("full scan", {}, ptlib.FLAG_NO_BVH)):
-        old = {k: os.environ.get(k) for k in env}
-        os.environ.update(env)
-        try:
-            ctx = C.c_void_p()
-            assert L.pt_ctx_create(0, C.byref(ctx)) == 0  # the tuning variables are read here
-        finally:
-            for k, v in old.items():
-                if v is None:
-                    os.environ.pop(k, None)
-                else:
-                    os.environ[k] = v
-        assert L.pt_ctx_set_scene(ctx, C.byref(sc.cam), sc.objs, sc.n_objs, sc.tris, sc.n_tris) == 0, L.pt_last_error()
+        dev = gpudev.Device(L, sc, env=env)  # the tuning variables are read here
+        ctx = dev.ctx
         kernel = L.pt_ctx_pass_kernel(ctx, flags).decode()
-        cfg = PtConfig(w, h, spp, 0, 3, 0, 0, 0, flags)
-        d = C.c_void_p()
-        assert L.pt_device_malloc(0, w * h * 12, C.byref(d)) == 0
-        st = PtStats()
-        assert L.pt_ctx_render(ctx, C.byref(cfg), d, None, None, None, None, C.byref(st)) == 0, L.pt_last_error()
-        img = np.empty((w * h, 3), np.float32)
-        assert L.pt_device_download(0, _np_f(img), d, img.nbytes) == 0
-        L.pt_device_free(0, d)
-        L.pt_ctx_destroy(ctx)
+        img, st = dev.render(PtConfig(w, h, spp, 0, 3, 0, 0, 0, flags), dev.alloc(w * h * 12))
+        dev.close()
         res[name] = (kernel, img, st.ray_bounces)
     assert res["queue"][0] == "k_pass_cand_bvh" and res["tiny queue"][0] == "k_pass_cand_bvh"
     assert res["k_pass_bvh"][0] == "k_pass_bvh" and res["full scan"][0] == "k_pass"
@@ -534,27 +518,10 @@ def test_wide_bvh_through_the_walk_queue(gpu):
     w, h, spp = 160, 120, 8
     res = {}
     for name, env in (("queue", {}), ("tiny queue", {"PT_WALK_QUEUE_CAP": "128"}), ("k_pass_bvh", {"PT_CAND_BVH": "0"})):
-        old = {k: os.environ.get(k) for k in env}
-        os.environ.update(env)
-        try:
-            ctx = C.c_void_p()
-            assert L.pt_ctx_create(0, C.byref(ctx)) == 0
-        finally:
-            for k, v in old.items():
-                if v is None:
-                    os.environ.pop(k, None)
-                else:
-                    os.environ[k] = v
-        assert L.pt_ctx_set_scene(ctx, C.byref(sc.cam), sc.objs, sc.n_objs, sc.tris, sc.n_tris) == 0, L.pt_last_error()
+        dev = gpudev.Device(L, sc, env=env)  # the tuning variables are read here
+        ctx = dev.ctx
         kernel = L.pt_ctx_pass_kernel(ctx, 0).decode()
-        cfg = PtConfig(w, h, spp, 0, 5, 0, 0, 0, 0)
-        d = C.c_void_p()
-        assert L.pt_device_malloc(0, w * h * 12, C.byref(d)) == 0
-        st = PtStats()
-        assert L.pt_ctx_render(ctx, C.byref(cfg), d, None, None, None, None, C.byref(st)) == 0, L.pt_last_error()
-        img = np.empty((w * h, 3), np.float32)
-        assert L.pt_device_download(0, _np_f(img), d, img.nbytes) == 0
-        L.pt_device_free(0, d)
+        img, st = dev.render(PtConfig(w, h, spp, 0, 5, 0, 0, 0, 0), dev.alloc(w * h * 12))
         if name == "queue":  # single rays against the oracle's scan (k_query: depth-first, u32 stacks)
             rng = np.random.default_rng(11)
             n = 4000
@@ -572,7 +539,7 @@ def test_wide_bvh_through_the_walk_queue(gpu):
             assert (out[1][1] == 2).mean() > 0.2
             assert np.array_equal(out[0][1], out[1][1]) and np.array_equal(out[0][2], out[1][2])
             assert np.array_equal(out[0][0].view(np.uint32), out[1][0].view(np.uint32))
-        L.pt_ctx_destroy(ctx)
+        dev.close()
         res[name] = (kernel, img, st.ray_bounces)
     assert res["queue"][0] == "k_pass_cand_bvh" and res["k_pass_bvh"][0] == "k_pass_bvh"
     assert res["queue"][1].max() > 0.0
@@ -1702,21 +1669,11 @@ def test_small_wave_stacks_hold_primaries_back(gpu):
         res = {}
         for name, env in (("1024", {}), ("512", {"PT_WAVE_STACK": "512"}), ("glass deferred", {"PT_GLASS_DEFER": "1"}),
                           ("nodes from L2", {"PT_NODES_LDS": "0"})):
-            old = {k: os.environ.get(k) for k in env}
-            os.environ.update(env)
-            try:
-                ctx = C.c_void_p()
-                assert L.pt_ctx_create(0, C.byref(ctx)) == 0  # the tuning variables are read here
-            finally:
-                for k, v in old.items():
-                    if v is None:
-                        os.environ.pop(k, None)
-                    else:
-                        os.environ[k] = v
-            assert L.pt_ctx_set_scene(ctx, C.byref(sc.cam), sc.objs, sc.n_objs, sc.tris, sc.n_tris) == 0, L.pt_last_error()
+            dev = gpudev.Device(L, sc, env=env)  # the tuning variables are read here
+            ctx = dev.ctx
             assert L.pt_ctx_pass_kernel(ctx, 0).decode().startswith("k_pass_cand")
             img, st = _render_dev(L, ctx, sc, w, h, spp, 9)
-            L.pt_ctx_destroy(ctx)
+            dev.close()
             res[name] = (img, st.ray_bounces)
         for name in res:
             assert res[name][1] == res["1024"][1], (sid, name)
@@ -1737,27 +1694,8 @@ def test_megakernel_items_and_rounds_do_not_change_the_image(gpu):
         res = {}
         for name, env, backend, rpp in (("wavefront", {}, 0, 0), ("mega", {}, 1, 0), ("tiny items", {"PT_MEGA_ITEMS": "256"}, 1, 0),
                                         ("one item", {"PT_MEGA_ITEMS": "1"}, 1, 0), ("short rounds", {}, 1, w * h * 5)):
-            old = {k: os.environ.get(k) for k in env}
-            os.environ.update(env)
-            try:
-                ctx = C.c_void_p()
-                assert L.pt_ctx_create(0, C.byref(ctx)) == 0  # the tuning variables are read here
-            finally:
-                for k, v in old.items():
-                    if v is None:
-                        os.environ.pop(k, None)
-                    else:
-                        os.environ[k] = v
-            assert L.pt_ctx_set_scene(ctx, C.byref(sc.cam), sc.objs, sc.n_objs, sc.tris, sc.n_tris) == 0, L.pt_last_error()
-            cfg = PtConfig(w, h, spp, backend, 13, 0, 0, rpp, 0)
-            d = C.c_void_p()
-            assert L.pt_device_malloc(0, w * h * 12, C.byref(d)) == 0
-            st = PtStats()
-            assert L.pt_ctx_render(ctx, C.byref(cfg), d, None, None, None, None, C.byref(st)) == 0, L.pt_last_error()
-            img = np.empty((w * h, 3), np.float32)
-            assert L.pt_device_download(0, _np_f(img), d, img.nbytes) == 0
-            L.pt_device_free(0, d)
-            L.pt_ctx_destroy(ctx)
+            with gpudev.Device(L, sc, env=env) as dev:  # the tuning variables are read here
+                img, st = dev.render(PtConfig(w, h, spp, backend, 13, 0, 0, rpp, 0), dev.alloc(w * h * 12))
             res[name] = (img, st.ray_bounces, st.passes)
         assert res["short rounds"][2] >= spp // 5
         for name in ("mega", "tiny items", "one item", "short rounds"):

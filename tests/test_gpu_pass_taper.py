@@ -17,17 +17,16 @@ The frames (PT_TAPER_CUT streams cut into PT_TAPER_PIECES pieces; knobs set by h
 Each frame is rendered twice in one context, and accumulated in two calls - the second starts from the held sums of the first and
 flushes on top of them.  The bounce counts are the oracle's ray count; passes and launches are those of the same frame with the
 taper off."""
-import ctypes as C
-
 import pytest
 
 import frame_sums as fs
+import gpudev
 import ptlib
 import scatter_walk
+from gpudev import L, same_bytes  # noqa: F401  (L: fixture)
 from ptlib import PtConfig
-from test_gpu_boundary_rays import _new_ctx
 from test_gpu_finish_half import GLASS, _cornell
-from test_gpu_frame_sums import Out, _accumulate, _render, _saved, assert_frame, assert_planes
+from test_gpu_frame_sums import _saved, assert_planes
 
 pytestmark = pytest.mark.gpu
 
@@ -57,18 +56,11 @@ CASE_IDS = ["%s-%s" % (f[0], c[0]) for f, c in CASES]
 
 
 @pytest.fixture(scope="module")
-def L():
-    L = ptlib.product()
-    assert L.pt_device_count() >= 1, "no HIP device visible: the product has no CPU fallback"
-    return L
-
-
-@pytest.fixture(scope="module")
 def ctxs(L):
-    made = {name: _new_ctx(L, env) for name, env in CONTEXTS.items()}
+    made = {name: gpudev.Device(L, env=env) for name, env in CONTEXTS.items()}
     yield made
-    for c in made.values():
-        L.pt_ctx_destroy(c)
+    for d in made.values():
+        d.close()
 
 
 @pytest.fixture(scope="module")
@@ -108,36 +100,37 @@ def test_the_frames_reach_their_cases(walks):
 @pytest.mark.parametrize("case", CASES, ids=CASE_IDS)
 def test_tapered_frame_is_k_pass_and_the_oracle_sums(L, ctxs, scenes, walks, case, tmp_path):
     (name, sid, w, h, spp, _), (cname, off_name) = case
-    ctx, off, sc = ctxs[cname], ctxs[off_name], scenes[sid]
+    dev, dev_off, sc = ctxs[cname], ctxs[off_name], scenes[sid]
+    ctx, off = dev.ctx, dev_off.ctx
     W, sums = walks[name]
     total = fs.total_over(sums, range(spp))
     what = "%s %s" % (name, cname)
-    out = Out(L, w * h)
+    out = dev.alloc(w * h * 12)
     try:
         for c in (ctx, off):
-            assert L.pt_ctx_set_scene(c, C.byref(sc.cam), sc.objs, sc.n_objs, sc.tris, sc.n_tris) == 0, L.pt_last_error()
+            gpudev.set_scene(L, c, sc)
             assert L.pt_ctx_pass_kernel(c, 0).decode() == ("k_pass_cand_bvh" if sid == "mesh" else "k_pass_cand")
         assert L.pt_ctx_pass_kernel(ctx, ptlib.FLAG_NO_BVH).decode() == "k_pass"
         cfg = PtConfig(w, h, spp, 0, SEED, 0, 0, 0, 0)
-        want, st_ref = _render(L, ctx, PtConfig(w, h, spp, 0, SEED, 0, 0, 0, ptlib.FLAG_NO_BVH), out)
+        want, st_ref = dev.render(PtConfig(w, h, spp, 0, SEED, 0, 0, 0, ptlib.FLAG_NO_BVH), out)
         assert st_ref.ray_bounces == W.n, (what, st_ref.ray_bounces, W.n)
-        plain, st_off = _render(L, off, cfg, out)
+        plain, st_off = dev_off.render(cfg, out)
         assert st_off.ray_bounces == W.n, (what, st_off.ray_bounces, W.n)
-        assert_frame(plain, want, what + ", taper off against k_pass")
+        same_bytes(plain, want, what + ", taper off against k_pass")
         for turn in ("first frame", "second frame"):
-            got, st = _render(L, ctx, cfg, out)
+            got, st = dev.render(cfg, out)
             assert st.ray_bounces == W.n, (what, turn, st.ray_bounces, W.n)
             assert (st.passes, st.intersect_launches) == (st_off.passes, st_off.intersect_launches), (what, turn)
-            assert_frame(got, want, "%s, %s against k_pass" % (what, turn))
+            same_bytes(got, want, "%s, %s against k_pass" % (what, turn))
         # two calls: the second gathers the held sums of the first into the accumulators and the pieces add on top
         first = max(1, spp // 2)
         assert L.pt_ctx_accum_reset(ctx) == 0
-        _, st1 = _accumulate(L, ctx, PtConfig(w, h, first, 0, SEED, 0, 0, 0, 0), out)
+        _, st1 = dev.render(PtConfig(w, h, first, 0, SEED, 0, 0, 0, 0), out, accumulate=True)
         assert_planes(_saved(L, ctx, tmp_path / "first.ptacc")["sums"], fs.planes(fs.total_over(sums, range(first))), what + " first call")
-        img, st2 = _accumulate(L, ctx, cfg, out)
+        img, st2 = dev.render(cfg, out, accumulate=True)
         assert st1.ray_bounces + st2.ray_bounces == W.n, (what, st1.ray_bounces, st2.ray_bounces, W.n)
         assert_planes(_saved(L, ctx, tmp_path / "frame.ptacc")["sums"], fs.planes(total), what)
-        assert_frame(img, fs.resolved(total, spp, clamp=True), what + " resolved")
-        assert_frame(img, want, what + " accumulated against k_pass")
+        same_bytes(img, fs.resolved(total, spp, clamp=True), what + " resolved")
+        same_bytes(img, want, what + " accumulated against k_pass")
     finally:
-        out.close()
+        dev.free(out)

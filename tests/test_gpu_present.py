@@ -9,10 +9,12 @@ import os
 import numpy as np
 import pytest
 
+import gpudev
 import present_ref as ref
 import ptlib
 from present_ref import F32, FRAMEBUFFER_ORDER, ONE_BITS, RGB8, RGBA8
-from ptlib import PtConfig, PtPresentParams, PtStats
+from gpudev import L  # noqa: F401  (fixture)
+from ptlib import PtPresentParams
 
 pytestmark = pytest.mark.gpu
 
@@ -22,39 +24,12 @@ RESAMPLE = (((7, 5), (3, 2)), ((8, 8), (4, 4)), ((7, 5), (7, 2)), ((5, 3), (11, 
             ((257, 129), (100, 50)))
 
 
-def hip_runtime():
-    """the HIP runtime the product is bound to: the copy already mapped into this process that is not torch's"""
-    paths = {line.split()[-1] for line in open("/proc/self/maps") if "/libamdhip64.so" in line}
-    own = sorted(p for p in paths if "/torch/" not in p)
-    assert own, "libptrace_hip.so has not mapped a HIP runtime: %r" % sorted(paths)
-    hip = C.CDLL(own[0])
-    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    hip.hipStreamCreate.argtypes = [C.POINTER(C.c_void_p)]
-    hip.hipStreamDestroy.argtypes = [C.c_void_p]
-    return hip
-
-
-class Dev:
+class Dev(gpudev.Device):
     """one context, a frame buffer and an output buffer with guard bytes behind whatever a call writes"""
 
     def __init__(self, L, max_pix=257 * 129, max_out=257 * 129):
-        self.L = L
-        self.ctx = C.c_void_p()
-        assert L.pt_ctx_create(0, C.byref(self.ctx)) == 0, L.pt_last_error()
-        self.d_rgb, self.d_out = C.c_void_p(), C.c_void_p()
-        self.out_bytes = max_out * 4 + GUARD
-        assert L.pt_device_malloc(0, max_pix * 12, C.byref(self.d_rgb)) == 0, L.pt_last_error()
-        assert L.pt_device_malloc(0, self.out_bytes, C.byref(self.d_out)) == 0, L.pt_last_error()
-        self.hip = hip_runtime()
-
-    def upload(self, ptr, host):
-        host = np.ascontiguousarray(host)
-        assert self.hip.hipMemcpy(ptr, host.ctypes.data_as(C.c_void_p), host.nbytes, 1) == 0  # host to device
-
-    def download(self, ptr, nbytes, dtype=np.uint8):
-        host = np.zeros(nbytes // np.dtype(dtype).itemsize, dtype=dtype)
-        assert self.L.pt_device_download(0, host.ctypes.data_as(C.c_void_p), ptr, nbytes) == 0
-        return host
+        super().__init__(L)
+        self.d_rgb, self.d_out = self.alloc(max_pix * 12), self.alloc(max_out * 4 + GUARD)
 
     def put(self, frame):
         self.upload(self.d_rgb, np.ascontiguousarray(frame, dtype=F32))
@@ -63,25 +38,11 @@ class Dev:
         """the bytes the call wrote, (oh, ow, bpp); the guard behind them is checked on the way"""
         bpp = 4 if fmt == RGBA8 else 3
         n = (ow or w) * (oh or h) * bpp
-        self.upload(self.d_out, np.full(n + GUARD, 0xA5, dtype=np.uint8))
+        self.fill_guarded(self.d_out, n, GUARD, 0xA5, np.uint8)
         p = PtPresentParams(ow, oh, exposure, fmt, flags)
         rc = self.L.pt_ctx_present(self.ctx, w, h, C.byref(p) if params else None, d_rgb or self.d_rgb, self.d_out, stream)
         assert rc == 0, (rc, self.L.pt_last_error())
-        got = self.download(self.d_out, n + GUARD)
-        assert (got[n:] == 0xA5).all(), "bytes behind d_out were written"
-        return got[:n].reshape(oh or h, ow or w, bpp)
-
-    def close(self):
-        self.L.pt_device_free(0, self.d_rgb)
-        self.L.pt_device_free(0, self.d_out)
-        self.L.pt_ctx_destroy(self.ctx)
-
-
-@pytest.fixture(scope="module")
-def L():
-    L = ptlib.product()
-    assert L.pt_device_count() >= 1
-    return L
+        return self.read_guarded(self.d_out, n, GUARD, 0xA5, "d_out", np.uint8).reshape(oh or h, ow or w, bpp)
 
 
 @pytest.fixture(scope="module")
@@ -91,9 +52,8 @@ def table(L):
 
 @pytest.fixture(scope="module")
 def dev(L):
-    d = Dev(L)
-    yield d
-    d.close()
+    with Dev(L) as d:
+        yield d
 
 
 def to_int(L, values):
@@ -204,29 +164,22 @@ def test_streams_and_repeats(dev, table):
     w, h = 67, 33
     frame = threshold_frame(table, np.random.default_rng(11), w * h)
     dev.put(frame)
-    st = C.c_void_p()
-    assert dev.hip.hipStreamCreate(C.byref(st)) == 0
-    try:
+    with dev.stream() as st:
         for ow, oh, fmt in ((0, 0, RGBA8), (0, 0, RGB8), (31, 9, RGBA8), (31, 9, RGB8), (1, 1, RGB8)):
             a = dev.present(w, h, ow, oh, fmt=fmt)  # (the guard bytes behind d_out are checked by every call)
             assert np.array_equal(a, dev.present(w, h, ow, oh, fmt=fmt, stream=st)), (ow, oh, fmt)
             assert np.array_equal(a, dev.present(w, h, ow, oh, fmt=fmt)), (ow, oh, fmt)
-    finally:
-        assert dev.hip.hipStreamDestroy(st) == 0
 
 
 # ---------------------------------------------------------------------------------------------------- no state touched
 def test_leaves_the_context_alone(L, table):
     sc = ptlib.load_scene_py(ptlib.scene_path("cornell"))
     w, h = 32, 24
-    d = Dev(L, w * h, w * h)
-    try:
-        assert L.pt_ctx_set_scene(d.ctx, C.byref(sc.cam), sc.objs, sc.n_objs, sc.tris, sc.n_tris) == 0, L.pt_last_error()
-        cfg = PtConfig(w, h, 4, 0, 3, 0, 0, 0, 0)
-        st = PtStats()
-        assert L.pt_ctx_accumulate(d.ctx, C.byref(cfg), d.d_rgb, None, None, None, None, C.byref(st)) == 0, L.pt_last_error()
-        d_dn = C.c_void_p()
-        assert L.pt_device_malloc(0, w * h * 12, C.byref(d_dn)) == 0
+    with Dev(L, w * h, w * h) as d:
+        d.set_scene(sc)
+        cfg = gpudev.config(w, h, 4, seed=3)
+        d.render(cfg, d.d_rgb, accumulate=True)
+        d_dn = d.alloc(w * h * 12)
 
         def info():
             lo, hi = C.c_uint32(), C.c_uint32()
@@ -235,30 +188,25 @@ def test_leaves_the_context_alone(L, table):
 
         def denoise():
             assert L.pt_ctx_denoise(d.ctx, w, h, None, d.d_rgb, None, None, None, d_dn, None) == 0, L.pt_last_error()
-            return d.download(d_dn, w * h * 12)
+            return d.download(d_dn, w * h * 12, np.uint8)
 
         before, dn_before = info(), denoise()
         assert before == (4, 4)
-        frame = d.download(d.d_rgb, w * h * 12, F32).reshape(w * h, 3)
+        frame = d.pixels(d.d_rgb, w * h)
         assert np.array_equal(d.present(w, h, 13, 5), ref.present(table, frame, w, h, 13, 5))
         assert np.array_equal(d.present(w, h), ref.present(table, frame, w, h))
         assert info() == before
         assert np.array_equal(denoise(), dn_before)
-        assert np.array_equal(d.download(d.d_rgb, w * h * 12, F32).reshape(w * h, 3), frame)  # the frame itself is read only
-        L.pt_device_free(0, d_dn)
-    finally:
-        d.close()
+        assert np.array_equal(d.pixels(d.d_rgb, w * h), frame)  # the frame itself is read only
 
 
 # --------------------------------------------------------------------------------------------------------- end to end
 def test_end_to_end_render_present_and_callback(L, table, tmp_path):
     sc = ptlib.load_scene_py(ptlib.scene_path("cornell"))
     w, h, spp = 64, 48, 8
-    d = Dev(L, w * h, w * h)
-    d_snap = C.c_void_p()
-    assert L.pt_device_malloc(0, w * h * 12, C.byref(d_snap)) == 0
-    try:
-        assert L.pt_ctx_set_scene(d.ctx, C.byref(sc.cam), sc.objs, sc.n_objs, sc.tris, sc.n_tris) == 0, L.pt_last_error()
+    with Dev(L, w * h, w * h) as d:
+        d_snap = d.alloc(w * h * 12)
+        d.set_scene(sc)
         seen = []
 
         def on_progress(user, frac):
@@ -267,24 +215,18 @@ def test_end_to_end_render_present_and_callback(L, table, tmp_path):
                 return
             p = PtPresentParams(32, 24, 0.0, RGB8, 0)
             rc = L.pt_ctx_present(d.ctx, w, h, C.byref(p), d_snap, d.d_out, None)
-            seen.append((rc, n.value, d.download(d_snap, w * h * 12, F32), d.download(d.d_out, 32 * 24 * 3)))
+            seen.append((rc, n.value, d.pixels(d_snap, w * h), d.download(d.d_out, 32 * 24 * 3, np.uint8)))
 
         cb = ptlib.PROGRESS_FN(on_progress)
-        cfg = PtConfig(w, h, spp, 0, 8, 0, 0, 1, 0)  # passes of one sample: the callback fires between them
+        cfg = gpudev.config(w, h, spp, seed=8, rays_per_pass=1)  # passes of one sample: the callback fires between them
         cfg.progress_ms = ptlib.PROGRESS_EVERY_PASS
-        st = PtStats()
-        rc = L.pt_ctx_render(d.ctx, C.byref(cfg), d.d_rgb, None, None, C.cast(cb, C.c_void_p), None, C.byref(st))
-        assert rc == 0, L.pt_last_error()
+        frame, _ = d.render(cfg, d.d_rgb, cb=cb)
         assert len(seen) == 1
         rc, n, snap, got = seen[0]
         assert rc == 0 and 1 <= n <= spp
         assert np.array_equal(got.reshape(24, 32, 3), ref.present(table, snap.reshape(w * h, 3), w, h, 32, 24, fmt=RGB8))
         # the finished frame
-        frame = d.download(d.d_rgb, w * h * 12, F32).reshape(w * h, 3)
         path = tmp_path / "f.ppm"
         assert L.pt_write_ppm(os.fsencode(str(path)), frame.ctypes.data_as(C.POINTER(C.c_float)), w, h, spp, b"cornell", 0) == 0
         assert np.array_equal(d.present(w, h, fmt=RGB8), ref.read_p3(str(path)))
         assert np.array_equal(d.present(w, h, 32, 24), ref.present(table, frame, w, h, 32, 24))
-    finally:
-        L.pt_device_free(0, d_snap)
-        d.close()

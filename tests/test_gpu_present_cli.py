@@ -10,7 +10,7 @@ import pytest
 
 import present_ref as ref
 import ptlib
-from test_gpu_aov import pfm_to_framebuffer, read_pfm
+from gpudev import pfm_to_framebuffer, read_pfm
 
 pytestmark = pytest.mark.gpu
 

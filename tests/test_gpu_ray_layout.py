@@ -25,11 +25,12 @@ import pytest
 
 import boundary_rays as br
 import frame_sums as fs
+import gpudev
 import ptlib
 import scatter_walk
+from gpudev import L, same_bytes  # noqa: F401  (L: fixture)
 from ptlib import PtConfig, PtStats, _np_f
-from test_gpu_boundary_rays import _new_ctx
-from test_gpu_frame_sums import Out, _accumulate, _render, _saved, assert_frame, assert_planes
+from test_gpu_frame_sums import _saved, assert_planes
 
 pytestmark = pytest.mark.gpu
 
@@ -42,69 +43,61 @@ KERNEL = {"cornell": "k_pass_cand", "three-spheres": "k_pass_cand", "mesh": "k_p
 
 
 @pytest.fixture(scope="module")
-def L():
-    L = ptlib.product()
-    assert L.pt_device_count() >= 1, "no HIP device visible: the product has no CPU fallback"
-    return L
+def dev(L):
+    with gpudev.Device(L) as dev:
+        yield dev
 
 
-@pytest.fixture(scope="module")
-def ctx(L):
-    ctx = _new_ctx(L)
-    yield ctx
-    L.pt_ctx_destroy(ctx)
-
-
-def _set_scene(L, ctx, sc):
+def _set_scene(L, dev, sc):
     """the scene set; the default form runs the candidate scan on it and PT_FLAG_NO_BVH the scan of every triangle"""
-    assert L.pt_ctx_set_scene(ctx, C.byref(sc.cam), sc.objs, sc.n_objs, sc.tris, sc.n_tris) == 0, L.pt_last_error()
-    assert L.pt_ctx_pass_kernel(ctx, 0).decode() == KERNEL[sc.id], sc.id
-    assert L.pt_ctx_pass_kernel(ctx, ptlib.FLAG_NO_BVH).decode() == "k_pass", sc.id
+    gpudev.set_scene(L, dev.ctx, sc)
+    assert L.pt_ctx_pass_kernel(dev.ctx, 0).decode() == KERNEL[sc.id], sc.id
+    assert L.pt_ctx_pass_kernel(dev.ctx, ptlib.FLAG_NO_BVH).decode() == "k_pass", sc.id
 
 
-def _both(L, ctx, out, w, h, spp, what):
+def _both(L, dev, out, w, h, spp, what):
     """the frame through the candidate scan and through k_pass: the same floats and the same bounce count"""
-    got, st = _render(L, ctx, PtConfig(w, h, spp, 0, SEED, 0, 0, 0, 0), out)
-    want, st_ref = _render(L, ctx, PtConfig(w, h, spp, 0, SEED, 0, 0, 0, ptlib.FLAG_NO_BVH), out)
+    got, st = dev.render(PtConfig(w, h, spp, 0, SEED, 0, 0, 0, 0), out)
+    want, st_ref = dev.render(PtConfig(w, h, spp, 0, SEED, 0, 0, 0, ptlib.FLAG_NO_BVH), out)
     assert st.ray_bounces == st_ref.ray_bounces and st.ray_bounces >= w * h * spp, (what, st.ray_bounces, st_ref.ray_bounces)
-    assert_frame(got, want, what + " against k_pass")
+    same_bytes(got, want, what + " against k_pass")
     assert np.isfinite(got).all() and got.max() > 0.0, what
     return got, st.ray_bounces
 
 
 @pytest.mark.parametrize("frame", FRAMES, ids=FRAME_IDS)
-def test_frame_is_the_scan_of_every_triangle(L, ctx, frame):
+def test_frame_is_the_scan_of_every_triangle(L, dev, frame):
     sid, w, h, spp = frame
     sc = scatter_walk._scene(sid)
-    out = Out(L, w * h)
+    out = dev.alloc(w * h * 12)
     try:
-        _set_scene(L, ctx, sc)
-        _both(L, ctx, out, w, h, spp, FRAME_IDS[FRAMES.index(frame)])
+        _set_scene(L, dev, sc)
+        _both(L, dev, out, w, h, spp, FRAME_IDS[FRAMES.index(frame)])
     finally:
-        out.close()
+        dev.free(out)
 
 
 @pytest.mark.parametrize("frame", scatter_walk.FRAMES, ids=FRAME_IDS[3:])
-def test_walked_frame_holds_the_oracle_sums(L, ctx, frame, tmp_path):
+def test_walked_frame_holds_the_oracle_sums(L, dev, frame, tmp_path):
     """the raw 32.32 sums of the default form are the integers frame_sums chains down the oracle's paths, and the megakernel's
     frame of cornell is the wavefront's"""
     sid, w, h, spp = frame
     W, sums = fs.frame(sid, w, h, spp, SEED)
     total = fs.total_over(sums, range(spp))
-    out = Out(L, w * h)
+    out = dev.alloc(w * h * 12)
     try:
-        _set_scene(L, ctx, W.scene)
+        _set_scene(L, dev, W.scene)
         cfg = PtConfig(w, h, spp, 0, SEED, 0, 0, 0, 0)
-        img, st = _accumulate(L, ctx, cfg, out)
+        img, st = dev.render(cfg, out, accumulate=True)
         assert st.ray_bounces == W.n, (sid, st.ray_bounces, W.n)
-        assert_planes(_saved(L, ctx, tmp_path / "frame.ptacc")["sums"], fs.planes(total), sid)
-        assert_frame(img, fs.resolved(total, spp, clamp=True), sid)
+        assert_planes(_saved(L, dev.ctx, tmp_path / "frame.ptacc")["sums"], fs.planes(total), sid)
+        same_bytes(img, fs.resolved(total, spp, clamp=True), sid)
         if sid == "cornell":
-            mega, st_m = _render(L, ctx, PtConfig(w, h, spp, ptlib.BACKEND_MEGAKERNEL, SEED, 0, 0, 0, 0), out)
+            mega, st_m = dev.render(PtConfig(w, h, spp, ptlib.BACKEND_MEGAKERNEL, SEED, 0, 0, 0, 0), out)
             assert st_m.ray_bounces == W.n
-            assert_frame(mega, img, "megakernel against wavefront")
+            same_bytes(mega, img, "megakernel against wavefront")
     finally:
-        out.close()
+        dev.free(out)
 
 
 @pytest.fixture(scope="module")
@@ -150,27 +143,27 @@ def _check_table_order(tabs):
     return flat["axis"][:ne].tolist(), flat["axis"][ne:].tolist()
 
 
-def test_second_group_and_unfiltered_records(L, ctx, cornell_odd):
+def test_second_group_and_unfiltered_records(L, dev, cornell_odd):
     tabs = br.scene_tables(cornell_odd)
     assert _check_table_order(tabs) == ([0, 1, 1, 2], [0, 2]) and tabs["n_other_pairs"] == 1
-    out = Out(L, 16 * 12)
+    out = dev.alloc(16 * 12 * 12)
     try:
-        _set_scene(L, ctx, cornell_odd)
-        _both(L, ctx, out, 16, 12, 8, "cornell_odd")
+        _set_scene(L, dev, cornell_odd)
+        _both(L, dev, out, 16, 12, 8, "cornell_odd")
     finally:
-        out.close()
+        dev.free(out)
 
 
-def test_two_axes_only(L, ctx, cornell_xy):
+def test_two_axes_only(L, dev, cornell_xy):
     tabs = br.scene_tables(cornell_xy)
     assert _check_table_order(tabs) == ([0, 1, 1], []) and tabs["n_other_pairs"] == 0
-    out = Out(L, 16 * 12)
+    out = dev.alloc(16 * 12 * 12)
     try:
-        _set_scene(L, ctx, cornell_xy)
-        _, bounces = _both(L, ctx, out, 16, 12, 8, "cornell_xy")
+        _set_scene(L, dev, cornell_xy)
+        _, bounces = _both(L, dev, out, 16, 12, 8, "cornell_xy")
         assert bounces > 16 * 12 * 8  # (paths go on past the first hit)
     finally:
-        out.close()
+        dev.free(out)
 
 
 GRAZE = np.float32(1.0 / 64.0)
@@ -202,9 +195,9 @@ def _probe_dirs():
 
 
 @pytest.mark.parametrize("sid", ["cornell", "cornell_xy", "cornell_odd"])
-def test_single_rays_at_the_filters_edges(L, ctx, sid, cornell_xy, cornell_odd):
+def test_single_rays_at_the_filters_edges(L, dev, sid, cornell_xy, cornell_odd):
     sc = {"cornell_xy": cornell_xy, "cornell_odd": cornell_odd}.get(sid) or scatter_walk._scene(sid)
-    _set_scene(L, ctx, sc)
+    _set_scene(L, dev, sc)
     o = np.array(PROBE_O, np.float32)
     dirs = _probe_dirs()
     assert len(dirs) == 3 * (4 + 1 + 6)
@@ -214,7 +207,7 @@ def test_single_rays_at_the_filters_edges(L, ctx, sid, cornell_xy, cornell_odd):
         res = []
         for flags in (0, ptlib.FLAG_NO_BVH):
             out, st = np.zeros(3, np.float32), PtStats()
-            rc = L.pt_ctx_radiance(ctx, _np_f(o), _np_f(d), 0, 65, SEED, k, 0, flags, _np_f(out), C.byref(st))
+            rc = L.pt_ctx_radiance(dev.ctx, _np_f(o), _np_f(d), 0, 65, SEED, k, 0, flags, _np_f(out), C.byref(st))
             assert rc == 0, L.pt_last_error()
             res.append((out.view(np.uint32).tolist(), st.ray_bounces))
         assert res[0] == res[1], (sid, name, d.tolist(), res)

@@ -9,10 +9,12 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import gpudev
 import kats_camera as kc
 import ptlib
 import reproject_ref as ref
-from ptlib import PtConfig, PtReprojectParams, PtStats
+from gpudev import L  # noqa: F401  (fixture)
+from ptlib import PtConfig, PtReprojectParams
 from reproject_ref import F32, I32
 
 pytestmark = pytest.mark.gpu
@@ -30,43 +32,17 @@ CAMERAS = {
 PARAMS = dict(weight=4, max_history=64.0, depth_tol=0.05, normal_min=0.5)
 
 
-def hip_runtime():
-    """the HIP runtime the product is bound to: the copy already mapped into this process that is not torch's"""
-    paths = {line.split()[-1] for line in open("/proc/self/maps") if "/libamdhip64.so" in line}
-    own = sorted(p for p in paths if "/torch/" not in p)
-    assert own, "libptrace_hip.so has not mapped a HIP runtime: %r" % sorted(paths)
-    hip = C.CDLL(own[0])
-    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    hip.hipStreamCreate.argtypes = [C.POINTER(C.c_void_p)]
-    hip.hipStreamDestroy.argtypes = [C.c_void_p]
-    return hip
-
-
 NAMES = ("color", "depth", "oid", "normal", "hcolor", "hlen", "hdepth", "hoid", "hnormal", "out", "len")
 FLOATS = dict(color=3, depth=1, oid=1, normal=3, hcolor=3, hlen=1, hdepth=1, hoid=1, hnormal=3, out=3, len=1)
 
 
-class Dev:
+class Dev(gpudev.Device):
     """one context and the eleven planes of a call, the two outputs with guard floats behind whatever a call writes"""
 
     def __init__(self, L, max_pix=MAXPIX):
-        self.L = L
-        self.ctx = C.c_void_p()
-        assert L.pt_ctx_create(0, C.byref(self.ctx)) == 0, L.pt_last_error()
-        self.hip = hip_runtime()
-        self.p = {}
+        super().__init__(L)
         for name in NAMES:
-            self.p[name] = C.c_void_p()
-            assert L.pt_device_malloc(0, (max_pix * FLOATS[name] + GUARD) * 4, C.byref(self.p[name])) == 0, L.pt_last_error()
-
-    def upload(self, name, host):
-        host = np.ascontiguousarray(host)
-        assert self.hip.hipMemcpy(self.p[name], host.ctypes.data_as(C.c_void_p), host.nbytes, 1) == 0  # host to device
-
-    def download(self, name, count, dtype=F32):
-        host = np.zeros(count, dtype=dtype)
-        assert self.L.pt_device_download(0, host.ctypes.data_as(C.c_void_p), self.p[name], host.nbytes) == 0
-        return host
+            self.alloc((max_pix * FLOATS[name] + GUARD) * 4, name)
 
     def put(self, cur, hist=None):
         for name, key in (("color", "color"), ("depth", "depth"), ("oid", "oid"), ("normal", "normal")):
@@ -80,12 +56,8 @@ class Dev:
         """the two outputs of one call, (w*h, 3) and (w*h,); the guards behind them are checked on the way"""
         n = w * h
         out = "color" if in_place else "out"
-        if not in_place:
-            self.upload("out", np.full(n * 3 + GUARD, -3.0, dtype=F32))
-        else:  # the guard of the colour plane, behind the frame
-            tail = np.full(GUARD, -3.0, dtype=F32)
-            assert self.hip.hipMemcpy(C.c_void_p(self.p["color"].value + n * 12), tail.ctypes.data_as(C.c_void_p), tail.nbytes, 1) == 0
-        self.upload("len", np.full(n + GUARD, -3.0, dtype=F32))
+        self.fill_guarded(out, n * 3, GUARD, -3.0, tail_only=in_place)  # (in place: behind the frame)
+        self.fill_guarded("len", n, GUARD, -3.0)
         p = PtReprojectParams(params["weight"], params["max_history"], params["depth_tol"], params["normal_min"], 0)
         a = ref.pt_camera(cam)
         b = ref.pt_camera(hist_cam) if hist_cam is not None else None
@@ -95,29 +67,14 @@ class Dev:
                                      P["oid"], P["normal"] if normal else None, C.byref(b) if b is not None else None, *hist,
                                      P["hnormal"] if hist_normal else None, P[out], P["len"], stream)
         assert rc == 0, (rc, self.L.pt_last_error())
-        got = self.download(out, n * 3 + GUARD)
-        ln = self.download("len", n + GUARD)
-        assert (got[n * 3:] == -3.0).all() and (ln[n:] == -3.0).all(), "floats behind an output were written"
-        return got[:n * 3].reshape(n, 3), ln[:n]
-
-    def close(self):
-        for p in self.p.values():
-            self.L.pt_device_free(0, p)
-        self.L.pt_ctx_destroy(self.ctx)
-
-
-@pytest.fixture(scope="module")
-def L():
-    L = ptlib.product()
-    assert L.pt_device_count() >= 1
-    return L
+        got = self.read_guarded(out, n * 3, GUARD, -3.0, "the colour output")
+        return got.reshape(n, 3), self.read_guarded("len", n, GUARD, -3.0, "the length output")
 
 
 @pytest.fixture(scope="module")
 def dev(L):
-    d = Dev(L)
-    yield d
-    d.close()
+    with Dev(L) as d:
+        yield d
 
 
 # ------------------------------------------------------------------------------------------------------ the inputs
@@ -155,10 +112,7 @@ def want(w, h, cam, cur, hist_cam=None, hist=None, normal=True, hist_normal=True
 
 def same_bytes(got, exp, what):
     for name, a, b in (("colour", got[0], exp[0]), ("length", got[1], exp[1])):
-        if a.tobytes() != b.tobytes():
-            bad = np.argwhere(a.view(np.uint32) != b.view(np.uint32))
-            raise AssertionError("%s %s: %d of %d words differ, first at %s: %r vs %r" % (
-                what, name, len(bad), a.size, bad[0], a[tuple(bad[0])], b[tuple(bad[0])]))
+        gpudev.same_bytes(a, b, "%s %s" % (what, name))
 
 
 # --------------------------------------------------------------------------------------------------- synthetic frames
@@ -235,14 +189,10 @@ def test_in_place_and_on_a_stream(dev, camera):
     cur, hist = synthetic(w, h)
     dev.put(cur, hist)
     exp = want(w, h, cam, cur, hist_cam, hist)
-    st = C.c_void_p()
-    assert dev.hip.hipStreamCreate(C.byref(st)) == 0
-    try:
+    with dev.stream() as st:
         same_bytes(dev.reproject(w, h, cam, hist_cam, stream=st), exp, "stream")
         same_bytes(dev.reproject(w, h, cam, hist_cam), exp, "again")
         same_bytes(dev.reproject(w, h, cam, hist_cam, in_place=True, stream=st), exp, "in place")  # d_out_color == d_color
-    finally:
-        assert dev.hip.hipStreamDestroy(st) == 0
 
 
 def test_still_camera_accumulates_a_running_mean(dev):
@@ -264,19 +214,12 @@ def test_still_camera_accumulates_a_running_mean(dev):
 
 
 # ---------------------------------------------------------------------------------------------------- no state touched
-def render(L, ctx, d_out, w, h, spp, seed):
-    cfg = PtConfig(w, h, spp, 0, seed, 0, 0, 0, 0)
-    st = PtStats()
-    assert L.pt_ctx_render(ctx, C.byref(cfg), d_out, None, None, None, None, C.byref(st)) == 0, L.pt_last_error()
-
-
 def test_leaves_the_context_alone(L):
     sc = ptlib.load_scene_py(ptlib.scene_path("cornell"))
     w, h = 33, 25
-    d = Dev(L, w * h)
-    try:
-        assert L.pt_ctx_set_scene(d.ctx, C.byref(sc.cam), sc.objs, sc.n_objs, sc.tris, sc.n_tris) == 0, L.pt_last_error()
-        render(L, d.ctx, d.p["hcolor"], w, h, 4, 3)
+    with Dev(L, w * h) as d:
+        d.set_scene(sc)
+        d.render(gpudev.config(w, h, 4, seed=3), d.p["hcolor"])
         before = d.download("hcolor", w * h * 3)
         cur, hist = synthetic(w, h)
         d.put(cur, hist)
@@ -285,10 +228,8 @@ def test_leaves_the_context_alone(L):
         for name, key in (("color", "color"), ("depth", "depth"), ("normal", "normal"), ("hcolor", "color"), ("hlen", "len")):
             src = cur if not name.startswith("h") else hist
             assert d.download(name, src[key].size).tobytes() == src[key].tobytes(), name  # the inputs are read only
-        render(L, d.ctx, d.p["hcolor"], w, h, 4, 3)
+        d.render(gpudev.config(w, h, 4, seed=3), d.p["hcolor"])
         assert d.download("hcolor", w * h * 3).tobytes() == before.tobytes()
-    finally:
-        d.close()
 
 
 # --------------------------------------------------------------------------------------------------------- end to end
@@ -306,15 +247,13 @@ def test_end_to_end_on_cornell(L):
     sc = ptlib.load_scene_py(ptlib.scene_path("cornell"))
     cam_a = ref.cam_dict(sc.cam)
     cam_b = ref.orbit(cam_a, ref.ORBIT_DEGREES)
-    d = Dev(L, n)
-    d_truth = C.c_void_p()
-    assert L.pt_device_malloc(0, n * 12, C.byref(d_truth)) == 0
-    try:
+    with Dev(L, n) as d:
+        d_truth = d.alloc(n * 12)
         frames = {}
         for name, cam, seed in (("a", cam_a, 11), ("b", cam_b, 12)):
             c = ref.pt_camera(cam)
-            assert L.pt_ctx_set_scene(d.ctx, C.byref(c), sc.objs, sc.n_objs, sc.tris, sc.n_tris) == 0, L.pt_last_error()
-            render(L, d.ctx, d.p["color"], w, h, spp, seed)
+            d.set_scene(sc, c)
+            d.render(gpudev.config(w, h, spp, seed=seed), d.p["color"])
             cfg = PtConfig(w, h, spp, 0, seed, 0, 0, 0, 0)
             assert L.pt_ctx_render_aov(d.ctx, C.byref(cfg), None, d.p["normal"], d.p["depth"], d.p["oid"], None) == 0, L.pt_last_error()
             frames[name] = dict(color=d.download("color", n * 3).reshape(n, 3), depth=d.download("depth", n),
@@ -324,9 +263,8 @@ def test_end_to_end_on_cornell(L):
                 assert first[0].tobytes() == frames["a"]["color"].tobytes() and (first[1] == spp).all()
                 frames["a"]["len"] = first[1]
             else:
-                render(L, d.ctx, d_truth, w, h, 4096, 1012)
-        truth = np.zeros((n, 3), dtype=F32)
-        assert L.pt_device_download(0, truth.ctypes.data_as(C.c_void_p), d_truth, truth.nbytes) == 0
+                d.render(gpudev.config(w, h, 4096, seed=1012), d_truth)
+        truth = d.pixels(d_truth, n)
         a, b = frames["a"], frames["b"]
         d.put(b, a)
         params = dict(ref.defaults(L), weight=spp)
@@ -340,6 +278,3 @@ def test_end_to_end_on_cornell(L):
         print("share %.4f, error with history %.5f, without %.5f, over %d pixels" % (share, with_history, without, found.sum()))
         assert share >= 0.75, share                                                                       # (b)
         assert with_history < without, (with_history, without)                                            # (c)
-    finally:
-        L.pt_device_free(0, d_truth)
-        d.close()

@@ -11,12 +11,14 @@ import subprocess
 import numpy as np
 import pytest
 
+import gpudev
 import ptlib
 import reproject_moved_ref as mref
 import reproject_ref as ref
 import reproject_var_ref as rv
 import test_gpu_reproject as base
 import test_gpu_reproject_var as vbase
+from gpudev import L  # noqa: F401  (fixture)
 from ptlib import PtConfig, PtObjectMotion, PtReprojectParams, PtReprojectVarParams
 from reproject_moved_ref import IDENTITY, MARKER
 from reproject_ref import F32, I32
@@ -57,11 +59,9 @@ class Dev(vbase.Dev):
 
     def reproject_moved(self, w, h, cam, hist_cam, motion, n_motion=None, normal=True, in_place=False, stream=None, params=PARAMS):
         n = w * h
-        if in_place:
-            self.upload("color", np.full(base.GUARD, -3.0, dtype=F32), at=n * 12)
-        else:
-            self.upload("out", np.full(n * 3 + base.GUARD, -3.0, dtype=F32))
-        self.upload("len", np.full(n + base.GUARD, -3.0, dtype=F32))
+        out = "color" if in_place else "out"
+        self.fill_guarded(out, n * 3, base.GUARD, -3.0, tail_only=in_place)
+        self.fill_guarded("len", n, base.GUARD, -3.0)
         p = PtReprojectParams(params["weight"], params["max_history"], params["depth_tol"], params["normal_min"], 0)
         a, b = ref.pt_camera(cam), ref.pt_camera(hist_cam)
         P = self.p
@@ -71,10 +71,8 @@ class Dev(vbase.Dev):
                                            P["hnormal"] if normal else None, P["color" if in_place else "out"], P["len"], t,
                                            len(motion) if n_motion is None else n_motion, stream)
         assert rc == 0, (rc, self.L.pt_last_error())
-        got = self.download("color" if in_place else "out", n * 3 + base.GUARD)
-        ln = self.download("len", n + base.GUARD)
-        assert (got[n * 3:] == -3.0).all() and (ln[n:] == -3.0).all(), "floats behind an output were written"
-        return got[:n * 3].reshape(n, 3), ln[:n]
+        got = self.read_guarded(out, n * 3, base.GUARD, -3.0, "the colour output")
+        return got.reshape(n, 3), self.read_guarded("len", n, base.GUARD, -3.0, "the length output")
 
     def plain(self, w, h, cam, hist_cam, normal=True):
         """pt_ctx_reproject's two outputs on the planes as they are"""
@@ -90,17 +88,9 @@ class Dev(vbase.Dev):
 
 
 @pytest.fixture(scope="module")
-def L():
-    L = ptlib.product()
-    assert L.pt_device_count() >= 1
-    return L
-
-
-@pytest.fixture(scope="module")
 def dev(L):
-    d = Dev(L)
-    yield d
-    d.close()
+    with Dev(L) as d:
+        yield d
 
 
 # ------------------------------------------------------------------------------------------------------ the inputs
@@ -165,9 +155,7 @@ def test_is_the_restatement(dev, size, camera):
     w, h = size
     cam, hist_cam = CAMERAS[camera]
     cur, hist = synthetic(w, h)
-    st = C.c_void_p()
-    assert dev.hip.hipStreamCreate(C.byref(st)) == 0
-    try:
+    with dev.stream() as st:
         for normal in (True, False):
             dev.put(cur, hist)
             vbase.same_bytes(dev.reproject_var_moved(w, h, cam, hist_cam, MOTION, normal=normal), want_var(w, h, camera, normal),
@@ -184,8 +172,6 @@ def test_is_the_restatement(dev, size, camera):
             dev.put(cur, hist)
             same2(dev.reproject_moved(w, h, cam, hist_cam, MOTION, normal=normal, in_place=True), want_plain(w, h, camera, normal),
                   (camera, "plain in place", normal))
-    finally:
-        assert dev.hip.hipStreamDestroy(st) == 0
     # the inputs reach what they are there for: on the larger frames every kind of record has pixels, and moved pixels blend
     if w * h > 35:
         ids = cur["oid"]
@@ -274,10 +260,10 @@ def test_end_to_end_on_cornell(L):
     d = Dev(L, n)
     params = dict(rv.defaults(L), weight=spp)
     try:
-        assert L.pt_ctx_set_scene(d.ctx, C.byref(sc.cam), sc.objs, sc.n_objs, sc.tris, sc.n_tris) == 0, L.pt_last_error()
+        d.set_scene(sc)
 
         def frame(seed):
-            base.render(L, d.ctx, d.p["color"], w, h, spp, seed)
+            d.render(gpudev.config(w, h, spp, seed=seed), d.p["color"])
             cfg = PtConfig(w, h, spp, 0, seed, 0, 0, 0, 0)
             assert L.pt_ctx_render_aov(d.ctx, C.byref(cfg), None, d.p["normal"], d.p["depth"], d.p["oid"], None) == 0, L.pt_last_error()
             return dict(color=d.download("color", n * 3).reshape(n, 3), depth=d.download("depth", n), oid=d.download("oid", n, I32),
@@ -316,7 +302,7 @@ def test_end_to_end_on_cornell(L):
         on = b["oid"] == index
         print("the moved sphere: %d pixels, %d with history" % (on.sum(), (got[1][on] > spp).sum()))
         assert (got[1][on] > spp).any()
-        base.render(L, d.ctx, d.p["dn"], w, h, spp, 12)                                                    # (b)
+        d.render(gpudev.config(w, h, spp, seed=12), d.p["dn"])                                                    # (b)
         assert d.download("dn", n * 3).tobytes() == b["color"].tobytes()
         for name, src in (("color", b["color"]), ("hcolor", a["color"]), ("hlen", a["len"]), ("hmom", a["mom"])):
             assert d.download(name, src.size).tobytes() == np.ascontiguousarray(src).tobytes(), name       # the inputs are read only

@@ -11,10 +11,12 @@ import numpy as np
 import pytest
 
 import denoise_var_ref as dvr
+import gpudev
 import ptlib
 import reproject_ref as ref
 import reproject_var_ref as rv
 import test_gpu_reproject as base
+from gpudev import L  # noqa: F401  (fixture)
 from ptlib import PtConfig, PtReprojectParams, PtReprojectVarParams
 from reproject_ref import F32, I32
 
@@ -35,27 +37,13 @@ FLOATS = dict(color=3, depth=1, oid=1, normal=3, hcolor=3, hlen=1, hmom=2, hdept
 OUTS = (("out", 3), ("len", 1), ("mom", 2), ("err", 1))
 
 
-class Dev:
+class Dev(gpudev.Device):
     """one context and the planes of a call, the four outputs with guard floats behind whatever a call writes"""
 
     def __init__(self, L, max_pix=MAXPIX):
-        self.L = L
-        self.ctx = C.c_void_p()
-        assert L.pt_ctx_create(0, C.byref(self.ctx)) == 0, L.pt_last_error()
-        self.hip = base.hip_runtime()
-        self.p = {}
+        super().__init__(L)
         for name in NAMES:
-            self.p[name] = C.c_void_p()
-            assert L.pt_device_malloc(0, (max_pix * FLOATS[name] + GUARD) * 4, C.byref(self.p[name])) == 0, L.pt_last_error()
-
-    def upload(self, name, host, at=0):
-        host = np.ascontiguousarray(host)
-        assert self.hip.hipMemcpy(C.c_void_p(self.p[name].value + at), host.ctypes.data_as(C.c_void_p), host.nbytes, 1) == 0
-
-    def download(self, name, count, dtype=F32):
-        host = np.zeros(count, dtype=dtype)
-        assert self.L.pt_device_download(0, host.ctypes.data_as(C.c_void_p), self.p[name], host.nbytes) == 0
-        return host
+            self.alloc((max_pix * FLOATS[name] + GUARD) * 4, name)
 
     def put(self, cur, hist=None):
         for name, key in (("color", "color"), ("depth", "depth"), ("oid", "oid"), ("normal", "normal")):
@@ -66,19 +54,12 @@ class Dev:
                 self.upload(name, hist[key])
 
     def _guards(self, n, in_place):
-        for name, k in OUTS:
-            if name == "out" and in_place:  # the guard of the colour plane, behind the frame
-                self.upload("color", np.full(GUARD, -3.0, dtype=F32), at=n * 12)
-            else:
-                self.upload(name, np.full(n * k + GUARD, -3.0, dtype=F32))
+        for name, k in OUTS:  # (in place: the guard of the colour plane, behind the frame)
+            self.fill_guarded("color" if name == "out" and in_place else name, n * k, GUARD, -3.0, tail_only=name == "out" and in_place)
 
     def _collect(self, n, in_place):
-        got = []
-        for name, k in OUTS:
-            a = self.download("color" if name == "out" and in_place else name, n * k + GUARD)
-            assert (a[n * k:] == -3.0).all(), "floats behind %s were written" % name
-            got.append(a[:n * k].reshape(n, k) if k > 1 else a[:n])
-        return tuple(got)
+        got = [self.read_guarded("color" if name == "out" and in_place else name, n * k, GUARD, -3.0, name) for name, k in OUTS]
+        return tuple(a.reshape(n, k) if k > 1 else a for a, (_, k) in zip(got, OUTS))
 
     def reproject_var(self, w, h, cam, hist_cam=None, normal=True, hist_normal=True, history=True, in_place=False, stream=None,
                       params=PARAMS, default_params=False, ctx=None):
@@ -101,8 +82,8 @@ class Dev:
     def reproject(self, w, h, cam, hist_cam, params=PARAMS):
         """pt_ctx_reproject on the planes as they are: (colour, length)"""
         n = w * h
-        self.upload("out", np.full(n * 3 + GUARD, -3.0, dtype=F32))
-        self.upload("len", np.full(n + GUARD, -3.0, dtype=F32))
+        self.fill_guarded("out", n * 3, GUARD, -3.0)
+        self.fill_guarded("len", n, GUARD, -3.0)
         p = PtReprojectParams(params["weight"], params["max_history"], params["depth_tol"], params["normal_min"], 0)
         a, b = ref.pt_camera(cam), ref.pt_camera(hist_cam)
         P = self.p
@@ -111,24 +92,11 @@ class Dev:
         assert rc == 0, (rc, self.L.pt_last_error())
         return self.download("out", n * 3).reshape(n, 3), self.download("len", n)
 
-    def close(self):
-        for p in self.p.values():
-            self.L.pt_device_free(0, p)
-        self.L.pt_ctx_destroy(self.ctx)
-
-
-@pytest.fixture(scope="module")
-def L():
-    L = ptlib.product()
-    assert L.pt_device_count() >= 1
-    return L
-
 
 @pytest.fixture(scope="module")
 def dev(L):
-    d = Dev(L)
-    yield d
-    d.close()
+    with Dev(L) as d:
+        yield d
 
 
 # ------------------------------------------------------------------------------------------------------ the inputs
@@ -176,12 +144,7 @@ def want(w, h, cam, cur, hist_cam=None, hist=None, normal=True, hist_normal=True
 
 def same_bytes(got, exp, what):
     for name, a, b in zip(("colour", "length", "moments", "error"), got, exp):
-        a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-        assert a.shape == b.shape, (what, name, a.shape, b.shape)
-        if a.tobytes() != b.tobytes():
-            bad = np.argwhere(a.view(np.uint32) != b.view(np.uint32))
-            raise AssertionError("%s %s: %d of %d words differ, first at %s: %r vs %r" % (
-                what, name, len(bad), a.size, bad[0], a[tuple(bad[0])], b[tuple(bad[0])]))
+        gpudev.same_bytes(a, b, "%s %s" % (what, name))
 
 
 # --------------------------------------------------------------------------------------------------- synthetic frames
@@ -283,45 +246,32 @@ def test_in_place_and_on_a_stream(dev, camera):
     cur, hist = synthetic(w, h)
     dev.put(cur, hist)
     exp = want(w, h, cam, cur, hist_cam, hist)
-    st = C.c_void_p()
-    assert dev.hip.hipStreamCreate(C.byref(st)) == 0
-    try:
+    with dev.stream() as st:
         same_bytes(dev.reproject_var(w, h, cam, hist_cam, stream=st), exp, "stream")
         same_bytes(dev.reproject_var(w, h, cam, hist_cam), exp, "again")
         same_bytes(dev.reproject_var(w, h, cam, hist_cam, in_place=True, stream=st), exp, "in place")  # d_out_color == d_color
-    finally:
-        assert dev.hip.hipStreamDestroy(st) == 0
 
 
 def test_scratch_grows_and_is_reused(L, dev):
     """one context called at 7x5, then 33x25 (the s plane grows), then 7x5 again (it is reused, larger than the frame): each call
     gives the bytes a fresh context gives"""
     cam, hist_cam = CAMERAS["translated"]
-    ctx = C.c_void_p()
-    assert L.pt_ctx_create(0, C.byref(ctx)) == 0, L.pt_last_error()
-    try:
+    with gpudev.Device(L) as one:
         for w, h in ((7, 5), (33, 25), (7, 5)):
             cur, hist = synthetic(w, h)
             dev.put(cur, hist)
-            fresh = C.c_void_p()
-            assert L.pt_ctx_create(0, C.byref(fresh)) == 0, L.pt_last_error()
-            try:
-                exp = dev.reproject_var(w, h, cam, hist_cam, ctx=fresh)
-            finally:
-                L.pt_ctx_destroy(fresh)
-            same_bytes(dev.reproject_var(w, h, cam, hist_cam, ctx=ctx), exp, (w, h))
+            with gpudev.Device(L) as fresh:
+                exp = dev.reproject_var(w, h, cam, hist_cam, ctx=fresh.ctx)
+            same_bytes(dev.reproject_var(w, h, cam, hist_cam, ctx=one.ctx), exp, (w, h))
             same_bytes(exp, want(w, h, cam, cur, hist_cam, hist), (w, h))
-    finally:
-        L.pt_ctx_destroy(ctx)
 
 
 def test_leaves_the_context_alone(L):
     sc = ptlib.load_scene_py(ptlib.scene_path("cornell"))
     w, h = 33, 25
-    d = Dev(L, w * h)
-    try:
-        assert L.pt_ctx_set_scene(d.ctx, C.byref(sc.cam), sc.objs, sc.n_objs, sc.tris, sc.n_tris) == 0, L.pt_last_error()
-        base.render(L, d.ctx, d.p["dn"], w, h, 4, 3)
+    with Dev(L, w * h) as d:
+        d.set_scene(sc)
+        d.render(gpudev.config(w, h, 4, seed=3), d.p["dn"])
         rendered = d.download("dn", w * h * 3)
         cur, hist = synthetic(w, h)
         d.put(cur, hist)
@@ -334,10 +284,8 @@ def test_leaves_the_context_alone(L):
             assert d.download(name, src[key].size).tobytes() == src[key].tobytes(), name  # the inputs are read only
         again = d.reproject(w, h, cam, hist_cam)
         assert again[0].tobytes() == old[0].tobytes() and again[1].tobytes() == old[1].tobytes()
-        base.render(L, d.ctx, d.p["dn"], w, h, 4, 3)
+        d.render(gpudev.config(w, h, 4, seed=3), d.p["dn"])
         assert d.download("dn", w * h * 3).tobytes() == rendered.tobytes()
-    finally:
-        d.close()
 
 
 # ------------------------------------------------------------------------------------------------------ the consumer
@@ -391,19 +339,15 @@ def test_end_to_end_on_cornell(L):
     sc = ptlib.load_scene_py(ptlib.scene_path("cornell"))
     cam_a = ref.cam_dict(sc.cam)
     cam_b = ref.orbit(cam_a, ref.ORBIT_DEGREES)
-    d = Dev(L, n)
-    d_truth = C.c_void_p()
-    assert L.pt_device_malloc(0, n * 12, C.byref(d_truth)) == 0
     params = dict(rv.defaults(L), weight=spp)
-    try:
+    with Dev(L, n) as d:
+        d_truth = d.alloc(n * 12)
         hist = None
         for name, cam, hist_cam, seed in (("a", cam_a, None, 11), ("b", cam_b, cam_a, 12)):
             c = ref.pt_camera(cam)
-            assert L.pt_ctx_set_scene(d.ctx, C.byref(c), sc.objs, sc.n_objs, sc.tris, sc.n_tris) == 0, L.pt_last_error()
-            base.render(L, d.ctx, d_truth, w, h, 4096, 1000 + seed)
-            truth = np.zeros((n, 3), dtype=F32)
-            assert L.pt_device_download(0, truth.ctypes.data_as(C.c_void_p), d_truth, truth.nbytes) == 0
-            base.render(L, d.ctx, d.p["color"], w, h, spp, seed)
+            d.set_scene(sc, c)
+            truth, _ = d.render(gpudev.config(w, h, 4096, seed=1000 + seed), d_truth)
+            d.render(gpudev.config(w, h, spp, seed=seed), d.p["color"])
             cfg = PtConfig(w, h, spp, 0, seed, 0, 0, 0, 0)
             assert L.pt_ctx_render_aov(d.ctx, C.byref(cfg), d.p["albedo"], d.p["normal"], d.p["depth"], d.p["oid"], None) == 0, \
                 L.pt_last_error()
@@ -432,6 +376,3 @@ def test_end_to_end_on_cornell(L):
                 assert (got[1][hit] > spp).mean() >= 0.75
                 assert e_dn <= e_rep, (e_dn, e_rep)                                                       # (d)
             hist = dict(cur, color=got[0], len=got[1], mom=got[2])
-    finally:
-        L.pt_device_free(0, d_truth)
-        d.close()

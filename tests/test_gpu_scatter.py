@@ -9,15 +9,15 @@ Every comparison is of the bytes of float32 words or of integers, for equality; 
 - A generated scene (tests/boundary_rays.py) whose surf table does not fit k_pass_cand's LDS: ranks on both sides of the staged
   head, by rank against by id and against the oracle.
 The probe proves the functions, not each kernel's use of them: that stays with the bounce counts and the frame tests."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import boundary_rays
+import gpudev
 import kats_scatter as ks
 import lds_layouts
 import ptlib
+from gpudev import L  # noqa: F401  (fixture)
 from ptlib import PtScatterOut
 import scatter_walk as sw
 from scatter_walk import bits
@@ -28,18 +28,9 @@ MODES = {"all": 0, "defer": sw.DEFER_REFRACT, "refract_only": sw.REFRACT_ONLY}
 
 
 @pytest.fixture(scope="module")
-def L():
-    L = ptlib.product()
-    assert L.pt_device_count() >= 1, "no HIP device visible: the product has no CPU fallback"
-    return L
-
-
-@pytest.fixture(scope="module")
 def ctx(L):
-    c = C.c_void_p()
-    assert L.pt_ctx_create(0, C.byref(c)) == 0, L.pt_last_error()
-    yield c
-    L.pt_ctx_destroy(c)
+    with gpudev.Device(L) as dev:
+        yield dev.ctx
 
 
 def scatter(L, ctx, form, items, surfs=None, seed=ks.SEED):
@@ -153,10 +144,8 @@ def check_walk(W, got, name):
 def test_oracle_paths_by_id_and_by_rank(L, frame):
     W = sw.walk(*frame)
     sc = W.scene
-    c = C.c_void_p()
-    assert L.pt_ctx_create(0, C.byref(c)) == 0, L.pt_last_error()
-    try:
-        assert L.pt_ctx_set_scene(c, C.byref(sc.cam), sc.objs, sc.n_objs, sc.tris, sc.n_tris) == 0, L.pt_last_error()
+    with gpudev.Device(L, sc) as dev:
+        c = dev.ctx
         items = sw.walk_items(W)
         by_id = scatter(L, c, sw.BY_ID, items, seed=sw.SEED)
         check_walk(W, by_id, frame[0] + " by id")
@@ -179,8 +168,6 @@ def test_oracle_paths_by_id_and_by_rank(L, frame):
             else:
                 assert bytes(defer[i]) == bytes(by_id[i]), i
                 assert only[i].hit == (sw.NOT_SHADED if W.oid[i] >= 0 else -1) and only[i].n_rays == 0, i
-    finally:
-        L.pt_ctx_destroy(c)
 
 
 def test_scene_needed_for_the_hit_forms(L, ctx):
@@ -207,17 +194,13 @@ def test_surf_table_that_does_not_fit_lds(L):
     assert len(set(below)) >= 4 and len(set(above)) >= 4, (len(below), len(above))
     kinds = {sc.objs[int(W.oid[i])].kind for i in range(W.n) if W.oid[i] >= 0}
     assert kinds == {ptlib.PT_SPHERE, ptlib.PT_MESH}
-    c = C.c_void_p()
-    assert L.pt_ctx_create(0, C.byref(c)) == 0, L.pt_last_error()
-    try:
-        assert L.pt_ctx_set_scene(c, C.byref(sc.cam), sc.objs, sc.n_objs, sc.tris, sc.n_tris) == 0, L.pt_last_error()
+    with gpudev.Device(L, sc) as dev:
+        c = dev.ctx
         items = sw.walk_items(W)
         by_rank = scatter(L, c, sw.BY_RANK, items, seed=sw.SEED)
         by_id = scatter(L, c, sw.BY_ID, items, seed=sw.SEED)
         check_walk(W, by_rank, "ties by rank")
         assert bytes(by_rank) == bytes(by_id)
-    finally:
-        L.pt_ctx_destroy(c)
 
 
 def test_by_rank_refused_without_candidate_tables(L):
@@ -229,10 +212,8 @@ def test_by_rank_refused_without_candidate_tables(L):
         tris.append(ptlib.make_tri((x, y, 0), (x + 0.2, y, 0), (x, y + 0.2, 0)))
     sc = ptlib.Scene("many-meshes", ptlib.make_camera((0, 0, 6), (0, 0, -1)), objs, tris)
     assert not boundary_rays.scene_tables(sc)["cand_ok"]
-    c = C.c_void_p()
-    assert L.pt_ctx_create(0, C.byref(c)) == 0, L.pt_last_error()
-    try:
-        assert L.pt_ctx_set_scene(c, C.byref(sc.cam), sc.objs, sc.n_objs, sc.tris, sc.n_tris) == 0, L.pt_last_error()
+    with gpudev.Device(L, sc) as dev:
+        c = dev.ctx
         items = (ptlib.PtScatterItem * 2)(sw.item((0.05, 0.05, 6), (0, 0, -1), (1, 1, 1), 0, 0, 0, 1),
                                        sw.item((-3.45, -2.45, 6), (0, 0, -1), (1, 1, 1), 1, 0, 0, 1))
         out = (PtScatterOut * 2)()
@@ -240,5 +221,3 @@ def test_by_rank_refused_without_candidate_tables(L):
         assert "candidate tables" in L.pt_last_error().decode()
         got = scatter(L, c, sw.BY_ID, items, seed=1)  # by id still runs
         assert got[1].hit == sc.n_objs + 0 and got[1].n_rays == 1
-    finally:
-        L.pt_ctx_destroy(c)

@@ -10,9 +10,11 @@ import importlib
 import numpy as np
 import pytest
 
+import gpudev
 import ptlib
 import reproject_ref
-from ptlib import PtAdaptiveInfo, PtAdaptiveParams, PtConfig, PtStats, PtTriangle
+from gpudev import L  # noqa: F401  (fixture)
+from ptlib import PtAdaptiveInfo, PtAdaptiveParams, PtStats, PtTriangle
 
 pytestmark = pytest.mark.gpu
 
@@ -23,11 +25,6 @@ F32 = np.float32
 fp = C.POINTER(C.c_float)
 i32p = C.POINTER(C.c_int32)
 u32p = C.POINTER(C.c_uint32)
-
-
-@pytest.fixture(scope="module")
-def L():
-    return ptlib.product()
 
 
 # ------------------------------------------------------------------------------------------------------- scenes and cameras
@@ -44,8 +41,10 @@ def generated_bvh_scene():
 
 
 def scene(sid):
+    if sid != "generated-bvh":
+        return gpudev.scene(sid)
     if sid not in _scenes:
-        _scenes[sid] = generated_bvh_scene() if sid == "generated-bvh" else ptlib.load_scene_py(ptlib.scene_path(sid))
+        _scenes[sid] = generated_bvh_scene()
     return _scenes[sid]
 
 
@@ -89,29 +88,17 @@ def grow(lo, hi, lens):
     return lo, hi
 
 
-def cfg_of(w, h, spp, flags=0, backend=0, seed=SEED):
-    return PtConfig(w, h, spp, backend, seed, 0, 0, 0, flags)
+def cfg_of(w, h, spp, seed=SEED, **kw):
+    return gpudev.config(w, h, spp, seed=seed, **kw)
 
 
 # ------------------------------------------------------------------------------------------------------- the device
-class Dev:
+class Dev(gpudev.Device):
     """a context with one frame buffer and four AOV planes of up to W*H pixels"""
 
     def __init__(self, L, sc=None, cam=None):
-        self.L = L
-        self.ctx = C.c_void_p()
-        assert L.pt_ctx_create(0, C.byref(self.ctx)) == 0, L.pt_last_error()
-        self.bufs = []
-        for nbytes in (W * H * 12, W * H * 12, W * H * 12, W * H * 4, W * H * 4):
-            p = C.c_void_p()
-            assert L.pt_device_malloc(0, nbytes, C.byref(p)) == 0
-            self.bufs.append(p)
-        if sc is not None:
-            self.set_scene(sc, cam)
-
-    def set_scene(self, sc, cam=None):
-        cam = cam if cam is not None else sc.cam
-        assert self.L.pt_ctx_set_scene(self.ctx, C.byref(cam), sc.objs, sc.n_objs, sc.tris, sc.n_tris) == 0, self.L.pt_last_error()
+        super().__init__(L, sc, cam)
+        self.bufs = [self.alloc(W * H * k * 4) for k in (3, 3, 3, 1, 1)]
 
     def set_camera(self, cam):
         rebuilt = C.c_int(-7)
@@ -125,15 +112,11 @@ class Dev:
         return np.array(list(lo), F32), np.array(list(hi), F32)
 
     def fetch(self, i, n, dt=F32):
-        host = np.zeros(n, dtype=dt)
-        assert self.L.pt_device_download(0, host.ctypes.data_as(C.c_void_p), self.bufs[i], host.nbytes) == 0
-        return host
+        return self.download(self.bufs[i], n, dt)
 
     def render(self, cfg, accumulate=False):
-        st = PtStats()
-        fn = self.L.pt_ctx_accumulate if accumulate else self.L.pt_ctx_render
-        assert fn(self.ctx, C.byref(cfg), self.bufs[0], None, None, None, None, C.byref(st)) == 0, self.L.pt_last_error()
-        return self.fetch(0, cfg.width * cfg.height * 3).tobytes(), st
+        img, st = super().render(cfg, self.bufs[0], accumulate)
+        return img.tobytes(), st
 
     def aov(self, cfg):
         assert self.L.pt_ctx_render_aov(self.ctx, C.byref(cfg), self.bufs[1], self.bufs[2], self.bufs[3], self.bufs[4], None) == 0, \
@@ -187,11 +170,6 @@ class Dev:
         info = PtAdaptiveInfo()
         assert self.L.pt_ctx_adaptive_info(self.ctx, C.byref(cfg), C.byref(par), C.byref(info)) == 0, self.L.pt_last_error()
         return info
-
-    def close(self):
-        for p in self.bufs:
-            self.L.pt_device_free(0, p)
-        self.L.pt_ctx_destroy(self.ctx)
 
 
 def everything(dev, w, h, with_scan):
@@ -261,23 +239,17 @@ def test_back_and_forth_and_a_second_slow_step(L):
     """A walks out (slow), further out (slow again or fast), back in (fast, on grown tables) - after each step it renders what a
     context that was given that camera with the scene renders"""
     sc = scene("mesh")
-    a = Dev(L, sc)
-    try:
+    with Dev(L, sc) as a:
         flags = []
         for deg in (90, 170, 2, -90, 0):
             cam = orbit(sc.cam, deg)
             flags.append(a.set_camera(cam))
-            b = Dev(L, sc, cam)
-            try:
+            with Dev(L, sc, cam) as b:
                 for cfg in (cfg_of(24, 16, 4), cfg_of(24, 16, 2, flags=NO_BVH), cfg_of(24, 16, 3, backend=1)):
                     got, gs = a.render(cfg)
                     want, ws = b.render(cfg)
                     assert got == want and gs.ray_bounces == ws.ray_bounces, (deg, cfg.flags, cfg.backend)
-            finally:
-                b.close()
         assert flags[0] == 1 and flags[2] == 0 and flags[4] == 0, flags
-    finally:
-        a.close()
 
 
 # ------------------------------------------------------------------------------------------------------- the growth rule
@@ -287,8 +259,7 @@ WALK = (2, 30, 31, 90, -90, 150, 10, 0)
 def test_reach_follows_the_growth_rule_and_can_be_reserved(L):
     sc = scene("cornell")
     cams = [orbit(sc.cam, deg) for deg in WALK]
-    a = Dev(L, sc)
-    try:
+    with Dev(L, sc) as a:
         lo, hi = a.reach()
         slo, shi = scene_reach(L, sc)
         assert lo.tobytes() == slo.tobytes() and hi.tobytes() == shi.tobytes()
@@ -302,13 +273,10 @@ def test_reach_follows_the_growth_rule_and_can_be_reserved(L):
             rlo, rhi = a.reach()
             assert rlo.tobytes() == lo.tobytes() and rhi.tobytes() == hi.tobytes(), (flags, rlo, lo, rhi, hi)
         assert 0 in flags and flags.count(1) >= 2, flags
-    finally:
-        a.close()
     # the walk's bounding box reserved up front: one rebuild, then none
     lenses = np.array([lens_of(L, cam) for cam in cams])
     blo, bhi = lenses.min(axis=0), lenses.max(axis=0)
-    b = Dev(L, sc)
-    try:
+    with Dev(L, sc) as b:
         rebuilt = C.c_int(-7)
         assert L.pt_ctx_reserve_camera_reach(b.ctx, blo.ctypes.data_as(fp), bhi.ctypes.data_as(fp), C.byref(rebuilt)) == 0
         assert rebuilt.value == 1
@@ -317,11 +285,8 @@ def test_reach_follows_the_growth_rule_and_can_be_reserved(L):
         assert L.pt_ctx_reserve_camera_reach(b.ctx, blo.ctypes.data_as(fp), bhi.ctypes.data_as(fp), C.byref(rebuilt)) == 0
         assert rebuilt.value == 0  # inside now: nothing happens
         img0, _ = b.render(cfg_of(W, H, 2))
-        c = Dev(L, sc)
-        try:
+        with Dev(L, sc) as c:
             assert c.render(cfg_of(W, H, 2))[0] == img0  # the camera did not change, the frame neither
-        finally:
-            c.close()
         for cam in cams:
             assert b.set_camera(cam) == 0
             lo2, hi2 = b.reach()
@@ -337,8 +302,6 @@ def test_reach_follows_the_growth_rule_and_can_be_reserved(L):
             assert L.pt_ctx_reserve_camera_reach(b.ctx, lo_.ctypes.data_as(fp), hi_.ctypes.data_as(fp), None) == PT_ERR_INVALID
         lo2, hi2 = b.reach()
         assert lo2.tobytes() == rlo.tobytes() and hi2.tobytes() == rhi.tobytes()
-    finally:
-        b.close()
 
 
 # ------------------------------------------------------------------------------------------------------- state
@@ -432,15 +395,12 @@ def test_checkpoints_interchange(L, tmp_path, deg, path):
         assert L.pt_ctx_adaptive_load(a.ctx, gb) == 0 and L.pt_ctx_adaptive_load(b.ctx, ga) == 0, L.pt_last_error()
         assert a.adaptive_info(acfg, par).tiles == b.adaptive_info(acfg, par).tiles != 0
         # a load is the first fingerprint after a move too: a fresh move, then the other's file
-        c = Dev(L, sc)
-        try:
+        with Dev(L, sc) as c:
             assert L.pt_ctx_accum_load(c.ctx, fb) == PT_ERR_INVALID
             assert c.set_camera(cam1) == path
             assert L.pt_ctx_accum_load(c.ctx, fb) == 0, L.pt_last_error()
             assert c.set_camera(sc.cam) == 0
             assert L.pt_ctx_adaptive_load(c.ctx, gb) == PT_ERR_INVALID
-        finally:
-            c.close()
     finally:
         a.close()
         b.close()
@@ -497,14 +457,11 @@ def test_python_context_set_camera(L):
         assert np.array(lo, F32).tobytes() == slo.tobytes() and np.array(hi, F32).tobytes() == shi.tobytes()
         for deg, path in ((10, False), (90, True)):
             cam1 = orbit(sc.cam, deg)
-            b = Dev(L, sc, cam1)
-            try:
+            with Dev(L, sc, cam1) as b:
                 assert ctx.set_camera(cam_dict(cam1)) is path
                 ctx.render(b.bufs[1].value, W, H, 3, seed=SEED)
                 got = b.fetch(1, W * H * 3).tobytes()
                 assert got == b.render(cfg_of(W, H, 3))[0]
-            finally:
-                b.close()
         lo2, hi2 = ctx.camera_reach()
         assert ctx.reserve_camera_reach(lo2, hi2) is False
         assert ctx.reserve_camera_reach([v - 1.0 for v in lo2], hi2) is True

@@ -15,8 +15,10 @@ import os
 import numpy as np
 import pytest
 
+import gpudev
 import ptlib
-from ptlib import PtConfig, PtObject, PtStats, PtTriangle
+from gpudev import L  # noqa: F401  (fixture)
+from ptlib import PtObject, PtTriangle
 
 pytestmark = pytest.mark.gpu
 
@@ -30,13 +32,6 @@ u32p = C.POINTER(C.c_uint32)
 TABLES = ("objs", "obj_pairs", "tri_pairs", "mats", "tri_shade", "bvh_nodes", "bvh_nodes4", "sph_pairs", "flat_pairs", "cand_pairs",
           "rank_id", "surf", "tri_rank", "bvh_meshes")
 INEXACT = (0.1, -1.0 / 3.0, 0.07)
-
-
-@pytest.fixture(scope="module")
-def L():
-    L = ptlib.product()
-    frame = [C.c_void_p, C.POINTER(PtConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PtStats)]
-    return L
 
 
 # ------------------------------------------------------------------------------------------------------- scenes
@@ -126,19 +121,12 @@ def edited(sc, index, **changes):
 
 
 # ------------------------------------------------------------------------------------------------------- the device
-class Dev:
+class Dev(gpudev.Device):
     """a context with one frame buffer and four AOV planes of W*H pixels"""
 
     def __init__(self, L, sc):
-        self.L = L
-        self.ctx = C.c_void_p()
-        assert L.pt_ctx_create(0, C.byref(self.ctx)) == 0, L.pt_last_error()
-        self.bufs = []
-        for nbytes in (W * H * 12, W * H * 12, W * H * 12, W * H * 4, W * H * 4):
-            p = C.c_void_p()
-            assert L.pt_device_malloc(0, nbytes, C.byref(p)) == 0
-            self.bufs.append(p)
-        assert L.pt_ctx_set_scene(self.ctx, C.byref(sc.cam), sc.objs, sc.n_objs, sc.tris, sc.n_tris) == 0, L.pt_last_error()
+        super().__init__(L, sc)
+        self.bufs = [self.alloc(W * H * k * 4) for k in (3, 3, 3, 1, 1)]
 
     def set_object(self, index, obj, expect=None):
         rebuilt = C.c_int(-7)
@@ -165,15 +153,11 @@ class Dev:
         return dict(zip(TABLES, out))
 
     def fetch(self, i, n, dt=F32):
-        host = np.zeros(n, dtype=dt)
-        assert self.L.pt_device_download(0, host.ctypes.data_as(C.c_void_p), self.bufs[i], host.nbytes) == 0
-        return host
+        return self.download(self.bufs[i], n, dt)
 
     def render(self, cfg, accumulate=False):
-        st = PtStats()
-        fn = self.L.pt_ctx_accumulate if accumulate else self.L.pt_ctx_render
-        assert fn(self.ctx, C.byref(cfg), self.bufs[0], None, None, None, None, C.byref(st)) == 0, self.L.pt_last_error()
-        return self.fetch(0, cfg.width * cfg.height * 3).tobytes(), st
+        img, st = super().render(cfg, self.bufs[0], accumulate)
+        return img.tobytes(), st
 
     def aov(self, cfg):
         assert self.L.pt_ctx_render_aov(self.ctx, C.byref(cfg), self.bufs[1], self.bufs[2], self.bufs[3], self.bufs[4], None) == 0, \
@@ -216,14 +200,9 @@ class Dev:
         assert self.L.pt_ctx_accum_info(self.ctx, C.byref(cfg), C.byref(lo), C.byref(hi)) == 0
         return lo.value, hi.value
 
-    def close(self):
-        for p in self.bufs:
-            self.L.pt_device_free(0, p)
-        self.L.pt_ctx_destroy(self.ctx)
-
 
 def cfg_of(spp, flags=0, backend=0):
-    return PtConfig(W, H, spp, backend, SEED, 0, 0, 0, flags)
+    return gpudev.config(W, H, spp, backend=backend, seed=SEED, flags=flags)
 
 
 def surface_rays(sc, index):
@@ -307,8 +286,7 @@ def test_tables_equal_a_fresh_builds(L, sid):
     fixtures, where a fresh build chooses the tree the refit kept.  Both contexts hold the same box B."""
     sc, index = scene(L, sid)
     moves = (INEXACT, (0.125, -0.25, 0.5)) if sid.startswith("cornell") else ((0.125, -0.5, 1.0), (-2.25, 0.375, -0.125), (0.0, 0.0, 0.0))
-    dev = Dev(L, sc)
-    try:
+    with Dev(L, sc) as dev:
         room_to_move(dev)
         lo, hi = dev.reach()
         for mv in moves:
@@ -316,17 +294,12 @@ def test_tables_equal_a_fresh_builds(L, sid):
             if mv[0] < 0.0:
                 to = edited(to, index, color=(0.125, 0.5, 1.0), reflect_type=1)  # the material with the move
             dev.set_object(index, to.objs[index], expect=0)
-            fresh = Dev(L, to)
-            try:
+            with Dev(L, to) as fresh:
                 fresh.reserve(lo, hi)
                 flo, fhi = fresh.reach()
                 assert flo.tobytes() == lo.tobytes() and fhi.tobytes() == hi.tobytes()
                 got, want = dev.hashes(), fresh.hashes()
                 assert got == want, (sid, mv, [k for k in TABLES if got[k] != want[k]])
-            finally:
-                fresh.close()
-    finally:
-        dev.close()
 
 
 # ------------------------------------------------------------------------------------------------------- 3. MATERIAL edits
@@ -340,8 +313,7 @@ def test_material_edits(L, sid, monkeypatch):
     context does: equal frames and bounce counts on the pass kernel that defers."""
     monkeypatch.setenv("PT_GLASS_DEFER", "1")
     sc, index = scene(L, sid)
-    dev = Dev(L, sc)
-    try:
+    with Dev(L, sc) as dev:
         geometry = {k: v for k, v in dev.hashes().items() if k in GEOMETRY}
         cur = sc
         for change in (dict(color=(0.25, 0.875, 0.5)), dict(emission=(0.5, 0.25, 2.0)), dict(reflect_type=2), dict(reflect_type=1),
@@ -350,8 +322,7 @@ def test_material_edits(L, sid, monkeypatch):
             dev.set_object(index, cur.objs[index], expect=0)
             now = dev.hashes()
             assert {k: v for k, v in now.items() if k in GEOMETRY} == geometry, [k for k in GEOMETRY if now[k] != geometry[k]]
-            fresh = Dev(L, cur)
-            try:
+            with Dev(L, cur) as fresh:
                 for cfg in (cfg_of(8), cfg_of(4, backend=1), cfg_of(2, flags=SEPARATE)):
                     got, gst = dev.render(cfg)
                     want, wst = fresh.render(cfg)
@@ -360,10 +331,6 @@ def test_material_edits(L, sid, monkeypatch):
                 lo, hi = dev.reach()
                 fresh.reserve(lo, hi)
                 assert dev.hashes() == fresh.hashes()
-            finally:
-                fresh.close()
-    finally:
-        dev.close()
 
 
 # ------------------------------------------------------------------------------------------------------- 4. OUT OF REACH
@@ -391,8 +358,7 @@ def bounds_of(sc, index):
 @pytest.mark.parametrize("sid", ("cornell-sphere", "cornell-wall", "mesh"))
 def test_out_of_reach_rebuilds_and_grows_by_the_rule(L, sid):
     sc, index = scene(L, sid)
-    dev = Dev(L, sc)
-    try:
+    with Dev(L, sc) as dev:
         lo, hi = dev.reach()
         ext = hi - lo
         far = edited(sc, index, move=(float(ext[0]), 0.0, float(-0.5 * ext[2])))
@@ -402,11 +368,8 @@ def test_out_of_reach_rebuilds_and_grows_by_the_rule(L, sid):
         glo, ghi = dev.reach()
         wlo, whi = grow(lo, hi, blo, bhi)
         assert glo.tobytes() == wlo.tobytes() and ghi.tobytes() == whi.tobytes(), (glo, wlo, ghi, whi)
-        fresh = Dev(L, far)
-        try:
+        with Dev(L, far) as fresh:
             assert_same(everything(dev, far, index)[0], everything(fresh, far, index)[0], sid + " out of reach")
-        finally:
-            fresh.close()
         # a second, smaller push stays inside what the first one reserved (the overshoot doubled): the plans were dropped with the
         # rebuild, so a mesh with a BVH is refit from a new one
         room = ghi[0] - bhi[0]
@@ -416,21 +379,15 @@ def test_out_of_reach_rebuilds_and_grows_by_the_rule(L, sid):
         assert ((glo <= flo) & (fhi <= ghi)).all() and fhi[0] > bhi[0]
         dev.set_object(index, further.objs[index], expect=0)
         assert dev.reach()[0].tobytes() == glo.tobytes() and dev.reach()[1].tobytes() == ghi.tobytes()
-        fresh = Dev(L, further)
-        try:
+        with Dev(L, further) as fresh:
             assert_same(everything(dev, further, index)[0], everything(fresh, further, index)[0], sid + " second push")
-        finally:
-            fresh.close()
-    finally:
-        dev.close()
 
 
 # ------------------------------------------------------------------------------------------------------- 5. state
 def test_refusals_in_order_leave_everything(L):
     sc, index = scene(L, "bvh19")
     dev = Dev(L, sc)
-    empty = C.c_void_p()
-    assert L.pt_ctx_create(0, C.byref(empty)) == 0
+    empty = gpudev.new_ctx(L)
     try:
         cfg = cfg_of(4)
         before, _ = dev.render(cfg, accumulate=True)
@@ -517,17 +474,11 @@ def test_set_camera_and_set_object_interleave(L):
 # ------------------------------------------------------------------------------------------------------- 6. sequences
 def test_twenty_moves_do_not_drift(L):
     sc, index = scene(L, "mesh")
-    dev = Dev(L, sc)
-    try:
+    with Dev(L, sc) as dev:
         room_to_move(dev)
         cur = sc
         for k in range(20):
             cur = edited(cur, index, move=(0.013 * (1 + k % 3), -0.007, 0.011 if k % 2 else -0.017))
             dev.set_object(index, cur.objs[index], expect=0)
-        fresh = Dev(L, cur)
-        try:
+        with Dev(L, cur) as fresh:
             assert_same(everything(dev, cur, index)[0], everything(fresh, cur, index)[0], "after twenty moves")
-        finally:
-            fresh.close()
-    finally:
-        dev.close()

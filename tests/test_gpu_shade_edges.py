@@ -18,13 +18,13 @@ Every item is compared: directions and weights of every child, depth, branch, n_
 The draws cannot be injected: (pixel, sample) of r1_last and r2_one below were found like kats_scatter.DRAWS, by the sweep of
 tools/find_scatter_draws.py (its philox7 over samples 0 .. 2^24 - 1 of pixel 0, tag (1 << 8) | 1) for word 1 >> 8 = 2^24 - 1 and
 word 2 >> 8 = 1; test_draws_are_the_extremes re-checks all of them on the CPU."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
+import gpudev
 import kats_scatter as ks
 import ptlib
+from gpudev import L  # noqa: F401  (fixture)
 from ptlib import PtScatterOut
 import scatter_walk as sw
 from scatter_walk import bits
@@ -113,13 +113,6 @@ def _sphere_rays(sc):
     return rays
 
 
-@pytest.fixture(scope="module")
-def L():
-    L = ptlib.product()
-    assert L.pt_device_count() >= 1, "no HIP device visible: the product has no CPU fallback"
-    return L
-
-
 def _scatter(L, ctx, form, items, surfs, seed):
     out = (PtScatterOut * len(items))()
     for o in out:
@@ -143,13 +136,9 @@ def _compare(name, o, want, depth):
 @pytest.mark.gpu
 def test_given_surfaces_at_the_edges(L):
     assert 64 <= len(GIVEN_CASES) <= 256
-    ctx = C.c_void_p()
-    assert L.pt_ctx_create(0, C.byref(ctx)) == 0, L.pt_last_error()
-    try:
+    with gpudev.Device(L) as dev:
         items, surfs = sw.case_arrays(GIVEN_CASES)
-        got = _scatter(L, ctx, sw.GIVEN, items, surfs, ks.SEED)
-    finally:
-        L.pt_ctx_destroy(ctx)
+        got = _scatter(L, dev.ctx, sw.GIVEN, items, surfs, ks.SEED)
     kinds = {}
     for c, o in zip(GIVEN_CASES, got):
         assert o.hit == 0 and bits(o.x) == c["x"].tobytes(), c["name"]
@@ -169,13 +158,9 @@ def test_cornell_spheres_at_pole_and_grazing(L):
     for r, hit in zip(rays, oid):
         assert hit == r[4], (r[0], hit)  # the ray reaches the sphere it was aimed at
     items = (ptlib.PtScatterItem * len(rays))(*[sw.item(o[i], d[i], (1, 1, 1), 40 + i, 2 * i + 1, rays[i][3], 1) for i in range(len(rays))])
-    ctx = C.c_void_p()
-    assert L.pt_ctx_create(0, C.byref(ctx)) == 0, L.pt_last_error()
-    try:
-        assert L.pt_ctx_set_scene(ctx, C.byref(sc.cam), sc.objs, sc.n_objs, sc.tris, sc.n_tris) == 0, L.pt_last_error()
+    with gpudev.Device(L, sc) as dev:
+        ctx = dev.ctx
         got = _scatter(L, ctx, sw.BY_RANK, items, None, ks.SEED)
-    finally:
-        L.pt_ctx_destroy(ctx)
     kinds = set()
     for i, (r, g) in enumerate(zip(rays, got)):
         obj = sc.objs[r[4]]

@@ -19,6 +19,7 @@ import pytest
 
 import ptlib
 import test_gpu_set_object as so
+from gpudev import L  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -62,11 +63,6 @@ def states(L, sid):
     finally:
         dev.close()
     return out
-
-
-@pytest.fixture(scope="module")
-def L():
-    return ptlib.product()
 
 
 @pytest.mark.parametrize("sid", SCENES)

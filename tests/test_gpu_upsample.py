@@ -5,13 +5,14 @@ and taps off both row edges (257x3 <- 129x2), 33x25 <- 16x12, a low resolution L
 sizes.  That their synthetic inputs reach every path is tests/test_upsample_abi.py's test_synthetic_inputs_reach_every_path."""
 import ctypes as C
 
-import numpy as np
 import pytest
 
+import gpudev
 import ptlib
 import upsample_ref as ref
-from ptlib import PtConfig, PtStats, PtUpsampleParams
-from upsample_ref import CASES, F32, I32, PARAMS
+from gpudev import L  # noqa: F401  (fixture)
+from ptlib import PtConfig, PtUpsampleParams
+from upsample_ref import CASES, I32, PARAMS
 
 pytestmark = pytest.mark.gpu
 
@@ -21,39 +22,13 @@ NAMES = ("lcolor", "ldepth", "loid", "lnormal", "lalbedo", "depth", "oid", "norm
 FLOATS = dict(lcolor=3, ldepth=1, loid=1, lnormal=3, lalbedo=3, depth=1, oid=1, normal=3, albedo=3, out=3, weight=1)
 
 
-def hip_runtime():
-    """the HIP runtime the product is bound to: the copy already mapped into this process that is not torch's"""
-    paths = {line.split()[-1] for line in open("/proc/self/maps") if "/libamdhip64.so" in line}
-    own = sorted(p for p in paths if "/torch/" not in p)
-    assert own, "libptrace_hip.so has not mapped a HIP runtime: %r" % sorted(paths)
-    hip = C.CDLL(own[0])
-    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    hip.hipStreamCreate.argtypes = [C.POINTER(C.c_void_p)]
-    hip.hipStreamDestroy.argtypes = [C.c_void_p]
-    return hip
-
-
-class Dev:
+class Dev(gpudev.Device):
     """one context and the eleven planes of a call, the two outputs with guard floats behind whatever a call writes"""
 
     def __init__(self, L, max_pix=MAXPIX):
-        self.L = L
-        self.ctx = C.c_void_p()
-        assert L.pt_ctx_create(0, C.byref(self.ctx)) == 0, L.pt_last_error()
-        self.hip = hip_runtime()
-        self.p = {}
+        super().__init__(L)
         for name in NAMES:
-            self.p[name] = C.c_void_p()
-            assert L.pt_device_malloc(0, (max_pix * FLOATS[name] + GUARD) * 4, C.byref(self.p[name])) == 0, L.pt_last_error()
-
-    def upload(self, name, host):
-        host = np.ascontiguousarray(host)
-        assert self.hip.hipMemcpy(self.p[name], host.ctypes.data_as(C.c_void_p), host.nbytes, 1) == 0  # host to device
-
-    def download(self, name, count, dtype=F32):
-        host = np.zeros(count, dtype=dtype)
-        assert self.L.pt_device_download(0, host.ctypes.data_as(C.c_void_p), self.p[name], host.nbytes) == 0
-        return host
+            self.alloc((max_pix * FLOATS[name] + GUARD) * 4, name)
 
     def put(self, hi, lo):
         for name, key in (("depth", "depth"), ("oid", "oid"), ("normal", "normal"), ("albedo", "albedo")):
@@ -66,8 +41,8 @@ class Dev:
         """the two outputs of one call, (W*H, 3) and (W*H,) (None without d_out_weight); the guards behind them are checked on
         the way.  normal / albedo: (the frame's given, the low-resolution one given)."""
         n = W * H
-        self.upload("out", np.full(n * 3 + GUARD, -3.0, dtype=F32))
-        self.upload("weight", np.full(n + GUARD, -3.0, dtype=F32))
+        self.fill_guarded("out", n * 3, GUARD, -3.0)
+        self.fill_guarded("weight", n, GUARD, -3.0)
         p = PtUpsampleParams(params["depth_tol"], params["normal_min"], 0)
         P = self.p
         rc = self.L.pt_ctx_upsample(self.ctx, W, H, w, h, None if null_params else C.byref(p), P["lcolor"], P["ldepth"], P["loid"],
@@ -75,31 +50,17 @@ class Dev:
                                     P["normal"] if normal[0] else None, P["albedo"] if albedo[0] else None, P["out"],
                                     P["weight"] if weight else None, stream)
         assert rc == 0, (rc, self.L.pt_last_error())
-        got = self.download("out", n * 3 + GUARD)
-        wg = self.download("weight", n + GUARD)
-        assert (got[n * 3:] == -3.0).all() and (wg[n:] == -3.0).all(), "floats behind an output were written"
-        if not weight:
-            assert (wg == -3.0).all(), "d_out_weight was NULL, yet the plane was written"
-        return got[:n * 3].reshape(n, 3), (wg[:n] if weight else None)
-
-    def close(self):
-        for p in self.p.values():
-            self.L.pt_device_free(0, p)
-        self.L.pt_ctx_destroy(self.ctx)
-
-
-@pytest.fixture(scope="module")
-def L():
-    L = ptlib.product()
-    assert L.pt_device_count() >= 1
-    return L
+        got = self.read_guarded("out", n * 3, GUARD, -3.0, "the colour output").reshape(n, 3)
+        if not weight:  # the whole plane is guard
+            self.read_guarded("weight", 0, n + GUARD, -3.0, "the weight plane (d_out_weight was NULL)")
+            return got, None
+        return got, self.read_guarded("weight", n, GUARD, -3.0, "the weight output")
 
 
 @pytest.fixture(scope="module")
 def dev(L):
-    d = Dev(L)
-    yield d
-    d.close()
+    with Dev(L) as d:
+        yield d
 
 
 @pytest.fixture(scope="module")
@@ -110,12 +71,8 @@ def inputs():
 
 def same_bytes(got, exp, what):
     for name, a, b in (("colour", got[0], exp[0]), ("weight", got[1], exp[1])):
-        if a is None:
-            continue
-        if a.tobytes() != b.tobytes():
-            bad = np.argwhere(a.view(np.uint32) != b.view(np.uint32))
-            raise AssertionError("%s %s: %d of %d words differ, first at %s: %r vs %r" % (
-                what, name, len(bad), a.size, bad[0], a[tuple(bad[0])], b[tuple(bad[0])]))
+        if a is not None:
+            gpudev.same_bytes(a, b, "%s %s" % (what, name))
 
 
 BIG = (33, 25, 16, 12)
@@ -182,33 +139,19 @@ def test_on_a_stream(dev, inputs):
     hi, lo = inputs[BIG]
     dev.put(hi, lo)
     exp = ref.want(*BIG, hi, lo)
-    st = C.c_void_p()
-    assert dev.hip.hipStreamCreate(C.byref(st)) == 0
-    try:
+    with dev.stream() as st:
         same_bytes(dev.upsample(*BIG, stream=st), exp, "stream")
         same_bytes(dev.upsample(*BIG), exp, "again")
-    finally:
-        assert dev.hip.hipStreamDestroy(st) == 0
 
 
 # ---------------------------------------------------------------------------------------------------- no state touched
-def render(L, ctx, d_out, w, h, spp, seed):
-    cfg = PtConfig(w, h, spp, 0, seed, 0, 0, 0, 0)
-    st = PtStats()
-    assert L.pt_ctx_render(ctx, C.byref(cfg), d_out, None, None, None, None, C.byref(st)) == 0, L.pt_last_error()
-
-
 def test_leaves_the_context_alone(L, inputs):
     sc = ptlib.load_scene_py(ptlib.scene_path("cornell"))
     W, H, w, h = BIG
-    d = Dev(L, W * H)
-    d_frame = C.c_void_p()
-    assert L.pt_device_malloc(0, W * H * 12, C.byref(d_frame)) == 0
-    try:
-        assert L.pt_ctx_set_scene(d.ctx, C.byref(sc.cam), sc.objs, sc.n_objs, sc.tris, sc.n_tris) == 0, L.pt_last_error()
-        render(L, d.ctx, d_frame, W, H, 4, 3)
-        before = np.zeros(W * H * 3, dtype=F32)
-        assert L.pt_device_download(0, before.ctypes.data_as(C.c_void_p), d_frame, before.nbytes) == 0
+    with Dev(L, W * H) as d:
+        d_frame = d.alloc(W * H * 12)
+        d.set_scene(sc)
+        before, _ = d.render(gpudev.config(W, H, 4, seed=3), d_frame)
         hi, lo = inputs[BIG]
         d.put(hi, lo)
         same_bytes(d.upsample(*BIG), ref.want(*BIG, hi, lo), "with a scene")
@@ -217,13 +160,8 @@ def test_leaves_the_context_alone(L, inputs):
             assert d.download(name, src[key].size).tobytes() == src[key].tobytes(), name  # the inputs are read only
         for name, src in (("oid", hi), ("loid", lo)):
             assert d.download(name, src["oid"].size, I32).tobytes() == src["oid"].tobytes(), name
-        render(L, d.ctx, d_frame, W, H, 4, 3)
-        after = np.zeros(W * H * 3, dtype=F32)
-        assert L.pt_device_download(0, after.ctypes.data_as(C.c_void_p), d_frame, after.nbytes) == 0
+        after, _ = d.render(gpudev.config(W, H, 4, seed=3), d_frame)
         assert after.tobytes() == before.tobytes()
-    finally:
-        L.pt_device_free(0, d_frame)
-        d.close()
 
 
 # --------------------------------------------------------------------------------------------------------- end to end
@@ -233,10 +171,9 @@ def test_end_to_end_on_cornell(L):
     (w, h), (W, H), spp = (24, 16), (48, 32), 4
     n, nl = W * H, w * h
     sc = ptlib.load_scene_py(ptlib.scene_path("cornell"))
-    d = Dev(L, n)
-    try:
-        assert L.pt_ctx_set_scene(d.ctx, C.byref(sc.cam), sc.objs, sc.n_objs, sc.tris, sc.n_tris) == 0, L.pt_last_error()
-        render(L, d.ctx, d.p["lcolor"], w, h, spp, 11)
+    with Dev(L, n) as d:
+        d.set_scene(sc)
+        d.render(gpudev.config(w, h, spp, seed=11), "lcolor")
         cfg = PtConfig(w, h, spp, 0, 11, 0, 0, 0, 0)
         assert L.pt_ctx_render_aov(d.ctx, C.byref(cfg), d.p["lalbedo"], d.p["lnormal"], d.p["ldepth"], d.p["loid"], None) == 0, \
             L.pt_last_error()
@@ -254,5 +191,3 @@ def test_end_to_end_on_cornell(L):
         share = float((got[1][hit] > 0).mean())
         print("hit pixels %d of %d, with a tap %.4f, colour mean %.4f" % (hit.sum(), n, share, got[0].mean()))
         assert hit.sum() > n // 2 and share >= 0.75 and got[0].mean() > 0.01
-    finally:
-        d.close()

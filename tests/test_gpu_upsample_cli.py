@@ -9,10 +9,10 @@ import subprocess
 import numpy as np
 import pytest
 
+import gpudev
 import present_ref
 import ptlib
 import upsample_ref as ref
-from ptlib import PtConfig, PtStats
 from upsample_ref import F32, I32
 
 pytestmark = pytest.mark.gpu
@@ -39,43 +39,23 @@ def planes():
     both sizes"""
     L = ptlib.product()
     sc = ptlib.load_scene_py(ptlib.scene_path("cornell"))
-    ctx = C.c_void_p()
-    assert L.pt_ctx_create(0, C.byref(ctx)) == 0, L.pt_last_error()
-    assert L.pt_ctx_set_scene(ctx, C.byref(sc.cam), sc.objs, sc.n_objs, sc.tris, sc.n_tris) == 0, L.pt_last_error()
     W, H = WIDTH, RES_Y
     w, h = (W + 1) // 2, (H + 1) // 2
-    bufs = []
 
-    def dev(count):
-        p = C.c_void_p()
-        assert L.pt_device_malloc(0, count * 4, C.byref(p)) == 0
-        bufs.append(p)
-        return p
-
-    def get(p, count, dtype=F32):
-        host = np.zeros(count, dtype=dtype)
-        assert L.pt_device_download(0, host.ctypes.data_as(C.c_void_p), p, host.nbytes) == 0
-        return host
-
-    def frame(wd, ht, color):
+    def frame(dev, wd, ht, color):
         n = wd * ht
-        cfg = PtConfig(wd, ht, SPP, 0, SEED, 0, 0, 0, 0)
-        d = dict(color=dev(n * 3), albedo=dev(n * 3), normal=dev(n * 3), depth=dev(n), oid=dev(n))
-        st = PtStats()
+        cfg = gpudev.config(wd, ht, SPP, seed=SEED)
+        d = dict(color=dev.alloc(n * 12), albedo=dev.alloc(n * 12), normal=dev.alloc(n * 12), depth=dev.alloc(n * 4), oid=dev.alloc(n * 4))
         if color:
-            assert L.pt_ctx_render(ctx, C.byref(cfg), d["color"], None, None, None, None, C.byref(st)) == 0, L.pt_last_error()
-        assert L.pt_ctx_render_aov(ctx, C.byref(cfg), d["albedo"], d["normal"], d["depth"], d["oid"], None) == 0, L.pt_last_error()
-        return dict(color=get(d["color"], n * 3).reshape(n, 3), albedo=get(d["albedo"], n * 3).reshape(n, 3),
-                    normal=get(d["normal"], n * 3).reshape(n, 3), depth=get(d["depth"], n), oid=get(d["oid"], n, I32))
+            dev.render(cfg, d["color"])
+        assert L.pt_ctx_render_aov(dev.ctx, C.byref(cfg), d["albedo"], d["normal"], d["depth"], d["oid"], None) == 0, L.pt_last_error()
+        return dict(color=dev.pixels(d["color"], n), albedo=dev.pixels(d["albedo"], n), normal=dev.pixels(d["normal"], n),
+                    depth=dev.download(d["depth"], n), oid=dev.download(d["oid"], n, I32))
 
-    try:
-        full = frame(W, H, True)
-        lo = frame(w, h, True)
+    with gpudev.Device(L, sc) as dev:
+        full = frame(dev, W, H, True)
+        lo = frame(dev, w, h, True)
         params = ref.defaults(L)
-    finally:
-        for p in bufs:
-            L.pt_device_free(0, p)
-        L.pt_ctx_destroy(ctx)
     return L, (W, H, w, h), full, lo, params
 
 

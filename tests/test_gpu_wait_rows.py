@@ -24,24 +24,18 @@ import numpy as np
 import pytest
 
 import frame_sums as fs
+import gpudev
 import ptlib
 import scatter_walk
+from gpudev import L, same_bytes  # noqa: F401  (L: fixture)
 from ptlib import PtConfig, PtStats, _np_f
-from test_gpu_boundary_rays import _new_ctx
-from test_gpu_frame_sums import Out, _accumulate, _render, _saved, assert_frame, assert_planes
+from test_gpu_frame_sums import _saved, assert_planes
 
 pytestmark = pytest.mark.gpu
 
 SEED = scatter_walk.SEED
 ENVS = {"plain": {}, "defer": {"PT_GLASS_DEFER": "1"}}
 GLASS = 1  # cornell.json's object 1
-
-
-@pytest.fixture(scope="module")
-def L():
-    L = ptlib.product()
-    assert L.pt_device_count() >= 1, "no HIP device visible: the product has no CPU fallback"
-    return L
 
 
 @pytest.fixture(scope="module")
@@ -54,12 +48,12 @@ def ctxs(L):
             env = dict(ENVS[form])
             if streams:
                 env["PT_STREAMS"] = str(streams)
-            made[(form, streams)] = _new_ctx(L, env)
+            made[(form, streams)] = gpudev.Device(L, env=env)
         return made[(form, streams)]
 
     yield get
-    for ctx in made.values():
-        L.pt_ctx_destroy(ctx)
+    for dev in made.values():
+        dev.close()
 
 
 @pytest.fixture(scope="module")
@@ -75,57 +69,57 @@ def glass_closeup(tmp_path_factory):
     return ptlib.load_scene_py(str(path), base_dir=ptlib.ROOT)
 
 
-def _set_scene(L, ctx, sc, kernel="k_pass_cand"):
-    assert L.pt_ctx_set_scene(ctx, C.byref(sc.cam), sc.objs, sc.n_objs, sc.tris, sc.n_tris) == 0, L.pt_last_error()
-    assert L.pt_ctx_pass_kernel(ctx, 0).decode() == kernel, sc.id
-    assert L.pt_ctx_pass_kernel(ctx, ptlib.FLAG_NO_BVH).decode() == "k_pass", sc.id
+def _set_scene(L, dev, sc, kernel="k_pass_cand"):
+    gpudev.set_scene(L, dev.ctx, sc)
+    assert L.pt_ctx_pass_kernel(dev.ctx, 0).decode() == kernel, sc.id
+    assert L.pt_ctx_pass_kernel(dev.ctx, ptlib.FLAG_NO_BVH).decode() == "k_pass", sc.id
 
 
-def _twice_against_k_pass(L, ctx, w, h, spp, what):
+def _twice_against_k_pass(L, dev, w, h, spp, what):
     """the frame through the candidate scan, twice, and through k_pass: the same floats and the same bounce count"""
-    out = Out(L, w * h)
+    out = dev.alloc(w * h * 12)
     try:
-        want, st_ref = _render(L, ctx, PtConfig(w, h, spp, 0, SEED, 0, 0, 0, ptlib.FLAG_NO_BVH), out)
+        want, st_ref = dev.render(PtConfig(w, h, spp, 0, SEED, 0, 0, 0, ptlib.FLAG_NO_BVH), out)
         for call in (1, 2):
-            got, st = _render(L, ctx, PtConfig(w, h, spp, 0, SEED, 0, 0, 0, 0), out)
+            got, st = dev.render(PtConfig(w, h, spp, 0, SEED, 0, 0, 0, 0), out)
             assert st.ray_bounces == st_ref.ray_bounces and st.ray_bounces >= w * h * spp, (what, call, st.ray_bounces, st_ref.ray_bounces)
-            assert_frame(got, want, "%s, call %d, against k_pass" % (what, call))
+            same_bytes(got, want, "%s, call %d, against k_pass" % (what, call))
         assert np.isfinite(want).all() and want.max() > 0.0, what
     finally:
-        out.close()
+        dev.free(out)
 
 
-def _twice_against_oracle(L, ctx, W, sums, tmp_path, what):
+def _twice_against_oracle(L, dev, W, sums, tmp_path, what):
     """the raw sums of the frame, accumulated twice from nothing, are the integers chained down the oracle's paths"""
     total = fs.total_over(sums, range(W.spp))
-    out = Out(L, W.width * W.height)
+    out = dev.alloc(W.width * W.height * 12)
     try:
         for call in (1, 2):
-            assert L.pt_ctx_accum_reset(ctx) == 0, L.pt_last_error()
-            _, st = _accumulate(L, ctx, PtConfig(W.width, W.height, W.spp, 0, SEED, 0, 0, 0, 0), out)
+            assert L.pt_ctx_accum_reset(dev.ctx) == 0, L.pt_last_error()
+            _, st = dev.render(PtConfig(W.width, W.height, W.spp, 0, SEED, 0, 0, 0, 0), out, accumulate=True)
             assert st.ray_bounces == W.n, (what, call, st.ray_bounces, W.n)
-            assert_planes(_saved(L, ctx, tmp_path / "frame.ptacc")["sums"], fs.planes(total), "%s, call %d" % (what, call))
+            assert_planes(_saved(L, dev.ctx, tmp_path / "frame.ptacc")["sums"], fs.planes(total), "%s, call %d" % (what, call))
     finally:
-        out.close()
+        dev.free(out)
 
 
 @pytest.mark.parametrize("form", list(ENVS))
 @pytest.mark.parametrize("size", [(7, 9), (8, 8), (13, 5)], ids=["63", "64", "65"])
 def test_chunk_boundaries_of_one_stream(L, ctxs, form, size):
-    ctx = ctxs(form, 1)
-    _set_scene(L, ctx, scatter_walk._scene("cornell"))
-    _twice_against_k_pass(L, ctx, size[0], size[1], 1, "cornell %dx%d @1, one stream, %s" % (size + (form,)))
+    dev = ctxs(form, 1)
+    _set_scene(L, dev, scatter_walk._scene("cornell"))
+    _twice_against_k_pass(L, dev, size[0], size[1], 1, "cornell %dx%d @1, one stream, %s" % (size + (form,)))
 
 
 @pytest.mark.parametrize("form", list(ENVS))
 @pytest.mark.parametrize("streams", [1, 4])
 def test_primary_trips_between_pops_and_the_fading_tail(L, ctxs, form, streams, tmp_path):
     W, sums = fs.frame("cornell", 16, 12, 8, SEED)
-    ctx = ctxs(form, streams)
-    _set_scene(L, ctx, W.scene)
+    dev = ctxs(form, streams)
+    _set_scene(L, dev, W.scene)
     what = "cornell 16x12 @8, %d stream(s), %s" % (streams, form)
-    _twice_against_k_pass(L, ctx, 16, 12, 8, what)
-    _twice_against_oracle(L, ctx, W, sums, tmp_path, what)
+    _twice_against_k_pass(L, dev, 16, 12, 8, what)
+    _twice_against_oracle(L, dev, W, sums, tmp_path, what)
 
 
 @pytest.mark.parametrize("form", list(ENVS))
@@ -135,19 +129,19 @@ def test_splits_on_glass_take_their_word_from_the_row(L, ctxs, form, glass_close
     assert first.sum() == 8 * 8 * 2 and (W.oid[:W.n][first] == GLASS).all(), "every primary ray hits the glass sphere"
     assert sum(len(c) == 2 for c in W.children[:W.n]) >= 64, "and splits"
     for streams in (0, 1):
-        ctx = ctxs(form, streams)
-        _set_scene(L, ctx, glass_closeup)
+        dev = ctxs(form, streams)
+        _set_scene(L, dev, glass_closeup)
         what = "glass close-up 8x8 @2, streams %d, %s" % (streams, form)
-        _twice_against_k_pass(L, ctx, 8, 8, 2, what)
-        _twice_against_oracle(L, ctx, W, fs.walk_sums(W), tmp_path, what)
+        _twice_against_k_pass(L, dev, 8, 8, 2, what)
+        _twice_against_oracle(L, dev, W, fs.walk_sums(W), tmp_path, what)
 
 
 def test_parked_rays_carry_throughput_and_word(L, ctxs, tmp_path):
     W, sums = fs.frame("mesh", 12, 8, 4, SEED)
-    ctx = ctxs("plain")
-    _set_scene(L, ctx, W.scene, "k_pass_cand_bvh")
-    _twice_against_k_pass(L, ctx, 12, 8, 4, "mesh 12x8 @4")
-    _twice_against_oracle(L, ctx, W, sums, tmp_path, "mesh 12x8 @4")
+    dev = ctxs("plain")
+    _set_scene(L, dev, W.scene, "k_pass_cand_bvh")
+    _twice_against_k_pass(L, dev, 12, 8, 4, "mesh 12x8 @4")
+    _twice_against_oracle(L, dev, W, sums, tmp_path, "mesh 12x8 @4")
 
 
 PROBE_O = np.array((0.3, 0.4, 2.0), np.float32)  # inside the room, every target in plain view
@@ -157,15 +151,15 @@ PROBE_AT = {"mirror": (-1.3, -1.2, -1.3), "glass": (1.3, -1.2, -0.2), "emitter":
 
 @pytest.mark.parametrize("form", list(ENVS))
 def test_one_probe_per_material(L, ctxs, form):
-    ctx = ctxs(form)
-    _set_scene(L, ctx, scatter_walk._scene("cornell"))
+    dev = ctxs(form)
+    _set_scene(L, dev, scatter_walk._scene("cornell"))
     for k, (name, at) in enumerate(PROBE_AT.items()):
         d = np.array(at, np.float64) - PROBE_O
         d = (d / np.linalg.norm(d)).astype(np.float32)
         res = []
         for flags in (0, 0, ptlib.FLAG_NO_BVH):
             out, st = np.zeros(3, np.float32), PtStats()
-            rc = L.pt_ctx_radiance(ctx, _np_f(PROBE_O), _np_f(d), 0, 65, SEED, k, 0, flags, _np_f(out), C.byref(st))
+            rc = L.pt_ctx_radiance(dev.ctx, _np_f(PROBE_O), _np_f(d), 0, 65, SEED, k, 0, flags, _np_f(out), C.byref(st))
             assert rc == 0, L.pt_last_error()
             res.append((out.view(np.uint32).tolist(), st.ray_bounces))
         assert res[0] == res[1] == res[2], (form, name, res)

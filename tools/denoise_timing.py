@@ -19,23 +19,16 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import denoise_ref  # noqa: E402
+import gpudev  # noqa: E402
 import ptlib  # noqa: E402
 from ptlib import PtConfig, PtStats  # noqa: E402
 
 W, H, SPP = 1024, 768, 16
 
 
-def hip_runtime():
-    for line in open("/proc/self/maps"):
-        path = line.split()[-1]
-        if "/libamdhip64.so" in path:
-            return C.CDLL(path)
-    raise RuntimeError("no HIP runtime mapped")
-
-
-def main():
+def main(stream):
     L = ptlib.product()
-    hip = hip_runtime()
+    hip = gpudev.hip_runtime()
     hip.hipEventElapsedTime.argtypes = [C.POINTER(C.c_float), C.c_void_p, C.c_void_p]
     sc = ptlib.load_scene_py(ptlib.scene_path("cornell"))
     npix = W * H
@@ -60,8 +53,7 @@ def main():
         for _ in range(3):  # the last of three: the pass rate is measured by then
             assert L.pt_ctx_render(ctx, C.byref(cfg), color, None, None, None, None, C.byref(st)) == 0
         assert L.pt_ctx_render_aov(ctx, C.byref(cfg), albedo, normal, depth, None, None) == 0
-        stream, e0, e1 = C.c_void_p(), C.c_void_p(), C.c_void_p()
-        assert hip.hipStreamCreate(C.byref(stream)) == 0
+        e0, e1 = C.c_void_p(), C.c_void_p()
         assert hip.hipEventCreate(C.byref(e0)) == 0 and hip.hipEventCreate(C.byref(e1)) == 0
 
         def window(levels, n):
@@ -86,7 +78,6 @@ def main():
         doc["forms"][form] = res
         hip.hipEventDestroy(e0)
         hip.hipEventDestroy(e1)
-        hip.hipStreamDestroy(stream)
         for p in bufs:
             L.pt_device_free(0, p)
         L.pt_ctx_destroy(ctx)
@@ -98,4 +89,5 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    with gpudev.stream() as own:
+        main(own)

@@ -21,16 +21,16 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import denoise_ref  # noqa: E402
 import denoise_var_ref  # noqa: E402
+import gpudev  # noqa: E402
 import ptlib  # noqa: E402
-from denoise_timing import hip_runtime  # noqa: E402
 from ptlib import PtConfig, PtNoiseStats, PtStats  # noqa: E402
 
 W, H, SPP = 1024, 768, 16
 
 
-def main():
+def main(stream):
     L = ptlib.product()
-    hip = hip_runtime()
+    hip = gpudev.hip_runtime()
     hip.hipEventElapsedTime.argtypes = [C.POINTER(C.c_float), C.c_void_p, C.c_void_p]
     sc = ptlib.load_scene_py(ptlib.scene_path("cornell"))
     npix = W * H
@@ -56,8 +56,7 @@ def main():
         assert L.pt_ctx_accumulate(ctx, C.byref(cfg), color, None, None, None, None, C.byref(st)) == 0
         assert L.pt_ctx_accum_noise(ctx, C.byref(cfg), error, C.byref(ns), None) == 0
         assert L.pt_ctx_render_aov(ctx, C.byref(cfg), albedo, normal, depth, None, None) == 0
-        stream, e0, e1 = C.c_void_p(), C.c_void_p(), C.c_void_p()
-        assert hip.hipStreamCreate(C.byref(stream)) == 0
+        e0, e1 = C.c_void_p(), C.c_void_p()
         assert hip.hipEventCreate(C.byref(e0)) == 0 and hip.hipEventCreate(C.byref(e1)) == 0
 
         def call(which, levels):
@@ -89,7 +88,6 @@ def main():
         doc["forms"][form] = res
         hip.hipEventDestroy(e0)
         hip.hipEventDestroy(e1)
-        hip.hipStreamDestroy(stream)
         for p in bufs:
             L.pt_device_free(0, p)
         L.pt_ctx_destroy(ctx)
@@ -101,4 +99,5 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    with gpudev.stream() as own:
+        main(own)

@@ -19,18 +19,11 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+import gpudev  # noqa: E402
 import ptlib  # noqa: E402
 from ptlib import PtConfig, PtNoiseStats, PtStats  # noqa: E402
 
 W, H = 1024, 768
-
-
-def hip_runtime():
-    for line in open("/proc/self/maps"):
-        path = line.split()[-1]
-        if "/libamdhip64.so" in path:
-            return C.CDLL(path)
-    raise RuntimeError("no HIP runtime mapped")
 
 
 def context(L, sc, tracked):
@@ -41,9 +34,9 @@ def context(L, sc, tracked):
     return ctx
 
 
-def main():
+def main(stream):
     L = ptlib.product()
-    hip = hip_runtime()
+    hip = gpudev.hip_runtime()
     hip.hipEventElapsedTime.argtypes = [C.POINTER(C.c_float), C.c_void_p, C.c_void_p]
     sc = ptlib.load_scene_py(ptlib.scene_path("cornell"))
     npix = W * H
@@ -56,8 +49,7 @@ def main():
     st, ns = PtStats(), PtNoiseStats()
     cfg = PtConfig(W, H, 64, 0, 1, 0, 0, 0, 0)
     assert L.pt_ctx_accumulate(ctx, C.byref(cfg), out, None, None, None, None, C.byref(st)) == 0
-    stream, e0, e1 = C.c_void_p(), C.c_void_p(), C.c_void_p()
-    assert hip.hipStreamCreate(C.byref(stream)) == 0
+    e0, e1 = C.c_void_p(), C.c_void_p()
     assert hip.hipEventCreate(C.byref(e0)) == 0 and hip.hipEventCreate(C.byref(e1)) == 0
 
     def window(d_err, n):
@@ -81,7 +73,6 @@ def main():
     doc["accum_noise"]["mean_error"] = ns.mean_error
     hip.hipEventDestroy(e0)
     hip.hipEventDestroy(e1)
-    hip.hipStreamDestroy(stream)
     L.pt_ctx_destroy(ctx)
 
     # 2. eight calls of 512 samples, tracking on / off interleaved
@@ -116,4 +107,5 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    with gpudev.stream() as own:
+        main(own)

@@ -28,6 +28,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+import gpudev  # noqa: E402
 import present_ref  # noqa: E402
 import ptlib  # noqa: E402
 
@@ -48,14 +49,6 @@ uint64_t gamma_loop(const float *v, size_t n) {
 """
 
 
-def hip_runtime():
-    for line in open("/proc/self/maps"):
-        path = line.split()[-1]
-        if "/libamdhip64.so" in path and "/torch/" not in path:
-            return C.CDLL(path)
-    raise RuntimeError("no HIP runtime mapped")
-
-
 def host_loop(tmp):
     """the C loop over pt_to_int_with_gamma_correction, or None if no C compiler is at hand"""
     src, so = os.path.join(tmp, "gamma_loop.c"), os.path.join(tmp, "gamma_loop.so")
@@ -71,20 +64,16 @@ def host_loop(tmp):
     return lib.gamma_loop
 
 
-def main():
+def main(stream):
     L = ptlib.product()
     assert L.pt_device_count() >= 1, "present_timing needs a GPU: there is nothing to time without one"
-    hip = hip_runtime()
+    hip = gpudev.hip_runtime()
     hip.hipEventElapsedTime.argtypes = [C.POINTER(C.c_float), C.c_void_p, C.c_void_p]
-    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    hip.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
-    hip.hipStreamSynchronize.argtypes = [C.c_void_p]
     hip.hipEventRecord.argtypes = [C.c_void_p, C.c_void_p]
     hip.hipEventSynchronize.argtypes = [C.c_void_p]
     ctx = C.c_void_p()
     assert L.pt_ctx_create(0, C.byref(ctx)) == 0, L.pt_last_error()
-    stream, e0, e1 = C.c_void_p(), C.c_void_p(), C.c_void_p()
-    assert hip.hipStreamCreate(C.byref(stream)) == 0
+    e0, e1 = C.c_void_p(), C.c_void_p()
     assert hip.hipEventCreate(C.byref(e0)) == 0 and hip.hipEventCreate(C.byref(e1)) == 0
     tmp = tempfile.mkdtemp()
     gamma_loop = host_loop(tmp)
@@ -154,7 +143,6 @@ def main():
             L.pt_device_free(0, p)
     hip.hipEventDestroy(e0)
     hip.hipEventDestroy(e1)
-    hip.hipStreamDestroy(stream)
     L.pt_ctx_destroy(ctx)
     path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "present_timing.json")
     with open(path, "w") as f:
@@ -164,4 +152,5 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    with gpudev.stream() as own:
+        main(own)

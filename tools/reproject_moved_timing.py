@@ -28,6 +28,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+import gpudev  # noqa: E402
 import kats_camera  # noqa: E402
 import ptlib  # noqa: E402
 import reproject_moved_ref as mref  # noqa: E402
@@ -40,26 +41,16 @@ DEPTH = 6.0
 BUDGET = 1.10
 
 
-def hip_runtime():
-    for line in open("/proc/self/maps"):
-        path = line.split()[-1]
-        if "/libamdhip64.so" in path and "/torch/" not in path:
-            return C.CDLL(path)
-    raise RuntimeError("no HIP runtime mapped")
-
-
-def main():
+def main(stream):
     L = ptlib.product()
     assert L.pt_device_count() >= 1, "reproject_moved_timing needs a GPU: there is nothing to time without one"
-    hip = hip_runtime()
+    hip = gpudev.hip_runtime()
     hip.hipEventElapsedTime.argtypes = [C.POINTER(C.c_float), C.c_void_p, C.c_void_p]
-    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
     hip.hipEventRecord.argtypes = [C.c_void_p, C.c_void_p]
     hip.hipEventSynchronize.argtypes = [C.c_void_p]
     ctx = C.c_void_p()
     assert L.pt_ctx_create(0, C.byref(ctx)) == 0, L.pt_last_error()
-    stream, e0, e1 = C.c_void_p(), C.c_void_p(), C.c_void_p()
-    assert hip.hipStreamCreate(C.byref(stream)) == 0
+    e0, e1 = C.c_void_p(), C.c_void_p()
     assert hip.hipEventCreate(C.byref(e0)) == 0 and hip.hipEventCreate(C.byref(e1)) == 0
     doc = {"command": "python tools/reproject_moved_timing.py", "isa_hash": L.pt_kernel_isa_hash().decode(),
            "method": "median of 5 HIP-event windows of N back-to-back calls (window >= %.0f ms) / N, after a warm-up; the yardstick "
@@ -159,7 +150,6 @@ def main():
             L.pt_device_free(0, p)
     hip.hipEventDestroy(e0)
     hip.hipEventDestroy(e1)
-    hip.hipStreamDestroy(stream)
     L.pt_ctx_destroy(ctx)
     path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "reproject_moved_timing.json")
     with open(path, "w") as f:
@@ -169,4 +159,5 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    with gpudev.stream() as own:
+        main(own)
