@@ -743,10 +743,7 @@ int render_wavefront(pt_ctx *c, const FrameForm &form, const pt_config *cfg, con
     host::FrameRequest req = host::first_request(pin);
     host::FramePlan plan;
     for (;;) {
-        if (host::plan_frame(pin, req, plan) != host::kPlanOk) {
-            set_error("rays per pass too large");
-            return PT_ERR_INVALID;
-        }
+        if (host::plan_frame(pin, req, plan) != host::kPlanOk) return refuse("rays per pass too large");
         const int rc = ensure_pass_buffers(c, form, plan);
         if (!rc) break;
         if (rc != PT_ERR_NOMEM_INTERNAL) return rc;
@@ -1129,10 +1126,7 @@ int run_frame_call(pt_ctx *c, const pt_config *cfg, const FrameParams &F, const 
 
 // The prologue of a frame call: a scene, a valid cfg (its band in *ib, *ie), the context's device current
 int frame_prologue(pt_ctx *c, const pt_config *cfg, uint32_t *ib, uint32_t *ie) {
-    if (!c->has_scene) {
-        set_error("no scene set");
-        return PT_ERR_INVALID;
-    }
+    if (!c->has_scene) return refuse("no scene set");
     const int rc = check_cfg(cfg, ib, ie);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device));
@@ -1425,6 +1419,64 @@ int run_image_pass(pt_ctx *c, void *hip_stream, Launch launch) {
     return PT_OK;
 }
 
+// A host-array query once its arguments are checked: host arrays staged on the device, one launch, the results copied back.  The
+// context's device is made current, and every copy, clear and the launch go to the context's stream in the order they are asked for.
+// The FIRST failure - a buffer's (DevBuf::ensure's code and message) or HIP's ("<call>: <what HIP says>", PT_ERR_HIP) - is the
+// call's, and every step after it does nothing.  finish() waits for the stream whenever anything was issued on it, failure or not:
+// the copies read and write the CALLER's arrays, which are the caller's again the moment the call returns.
+class HostCall {
+   public:
+    HostCall(pt_ctx *c, const char *name) : name_(name), st_(c->stream) { hip(hipSetDevice(c->device)); }
+    HostCall(const HostCall &) = delete;
+    bool ok() const { return rc_ == PT_OK; }
+    // a buffer of at least `count` records, cleared if asked
+    template <class T>
+    void room(DevBuf<T> &b, size_t count, bool zero = false) {
+        if (ok()) rc_ = b.ensure(count);
+        if (ok() && zero) issued(hipMemsetAsync(b.p, 0, count * sizeof(T), st_));
+    }
+    // ... filled with the host's
+    template <class T>
+    void in(DevBuf<T> &b, const T *src, size_t count) {
+        room(b, count);
+        if (ok()) issued(hipMemcpyAsync(b.p, src, count * sizeof(T), hipMemcpyHostToDevice, st_));
+    }
+    // launch(stream): the call's kernel; what the launch itself reports is picked up here, before any result is copied
+    template <class Launch>
+    void run(Launch launch) {
+        if (!ok()) return;
+        launch(st_);
+        issued(hipGetLastError());
+    }
+    // the buffer's first `count` records to the host (NULL: an output the caller did not ask for)
+    template <class T>
+    void out(T *dst, const DevBuf<T> &b, size_t count) {
+        if (dst && ok()) issued(hipMemcpyAsync(dst, b.p, count * sizeof(T), hipMemcpyDeviceToHost, st_));
+    }
+    int finish() {
+        if (issued_) {
+            const hipError_t e = hipStreamSynchronize(st_);
+            if (ok()) hip(e);
+        }
+        return rc_;
+    }
+
+   private:
+    void hip(hipError_t e) {
+        if (e == hipSuccess) return;
+        set_error(std::string(name_) + ": " + hipGetErrorString(e));
+        rc_ = PT_ERR_HIP;
+    }
+    void issued(hipError_t e) {
+        issued_ = true;
+        hip(e);
+    }
+    const char *name_;
+    hipStream_t st_;
+    int rc_ = PT_OK;
+    bool issued_ = false;
+};
+
 // pt_*_defaults: the values a zero field of a pass's parameters stands for
 template <class Params>
 int give_defaults(Params *out, const Params &defaults) {
@@ -1453,38 +1505,26 @@ uint32_t pt_config_pixels(const pt_config *cfg) {
 }
 
 int pt_camera_basis(const pt_camera *cam, float lens_center[3], float su[3], float sv[3]) {
-    if (!cam || !lens_center || !su || !sv) {
-        set_error("NULL argument");
-        return PT_ERR_INVALID;
-    }
+    if (!cam || !lens_center || !su || !sv) return refuse("NULL argument");
     host::camera_basis(*cam, lens_center, su, sv);
     return PT_OK;
 }
 
 int pt_mesh_bounding_sphere(const pt_triangle *tris, uint32_t n_tris, float center[3], float *radius) {
-    if (!tris || !center || !radius || n_tris == 0) {
-        set_error("NULL argument or empty mesh");
-        return PT_ERR_INVALID;
-    }
+    if (!tris || !center || !radius || n_tris == 0) return refuse("NULL argument or empty mesh");
     host::mesh_bounding_sphere(tris, n_tris, center, radius);
     return PT_OK;
 }
 
 int pt_ctx_create(int device, pt_ctx **out) {
-    if (!out) {
-        set_error("out is NULL");
-        return PT_ERR_INVALID;
-    }
+    if (!out) return refuse("out is NULL");
     *out = nullptr;
     const int n = device_count_quiet();
     if (n <= 0) {
         set_error("no HIP device: libptrace_hip has no CPU fallback");
         return PT_ERR_NO_DEVICE;
     }
-    if (device < 0 || device >= n) {
-        set_error("device index out of range");
-        return PT_ERR_INVALID;
-    }
+    if (device < 0 || device >= n) return refuse("device index out of range");
     HIP_TRY(hipSetDevice(device));
     int cus = 0;  // (every launch of the megakernel and the tile pass is sized by it: never 0)
     HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
@@ -1617,10 +1657,7 @@ static int upload_flat(pt_ctx *c, const host::FlatScene &fs, const pt_object *ob
 
 int pt_ctx_set_scene(pt_ctx *c, const pt_camera *cam, const pt_object *objs, uint32_t n_objs,
                      const pt_triangle *tris, uint32_t n_tris) {
-    if (!c || !cam || (!objs && n_objs) || (!tris && n_tris)) {
-        set_error("NULL argument");
-        return PT_ERR_INVALID;
-    }
+    if (!c || !cam || (!objs && n_objs) || (!tris && n_tris)) return refuse("NULL argument");
     host::FlatScene fs;
     host::Reach reach;
     std::string err;
@@ -1708,10 +1745,7 @@ static int refit_plan_for(pt_ctx *c, uint32_t index, pt_ctx::DevRefit **out) {
         return PT_OK;
     }
     host::RefitPlan plan;
-    if (!host::build_refit_plan(c->fs, index, plan)) {
-        set_error("internal: refit plan asked for an object without a BVH");
-        return PT_ERR_INVALID;
-    }
+    if (!host::build_refit_plan(c->fs, index, plan)) return refuse("internal: refit plan asked for an object without a BVH");
     pt_ctx::DevRefit &d = c->refit[index];
     const pt_object &o = c->h_objs[index];
     int rc;
@@ -1884,10 +1918,7 @@ int pt_scene_reach(const pt_camera *cam, const pt_object *objs, uint32_t n_objs,
 }
 
 int pt_device_malloc(int device, size_t bytes, void **out) {
-    if (!out) {
-        set_error("out is NULL");
-        return PT_ERR_INVALID;
-    }
+    if (!out) return refuse("out is NULL");
     *out = nullptr;
     if (device_count_quiet() <= 0) {
         set_error("no HIP device");
@@ -1912,10 +1943,7 @@ int pt_device_free(int device, void *p) {
 }
 
 int pt_device_download(int device, void *dst_host, const void *src_device, size_t bytes) {
-    if (!dst_host || !src_device) {
-        set_error("NULL argument");
-        return PT_ERR_INVALID;
-    }
+    if (!dst_host || !src_device) return refuse("NULL argument");
     HIP_TRY(hipSetDevice(device));
     HIP_TRY(hipMemcpy(dst_host, src_device, bytes, hipMemcpyDeviceToHost));
     return PT_OK;
@@ -1929,19 +1957,13 @@ const char *pt_ctx_pass_kernel(const pt_ctx *c, uint32_t flags) {
 int pt_bvh_refs_fit(uint64_t n_bvh_nodes, uint64_t n_pair_records) { return host::bvh_refs_fit(n_bvh_nodes, n_pair_records) ? 1 : 0; }
 
 int pt_ctx_set_memory_budget(pt_ctx *c, size_t bytes) {
-    if (!c) {
-        set_error("ctx is NULL");
-        return PT_ERR_INVALID;
-    }
+    if (!c) return refuse("ctx is NULL");
     c->mem_budget = bytes;
     return PT_OK;
 }
 
 int pt_ctx_set_profiling(pt_ctx *c, int enabled) {
-    if (!c) {
-        set_error("ctx is NULL");
-        return PT_ERR_INVALID;
-    }
+    if (!c) return refuse("ctx is NULL");
     c->profiling = enabled != 0;
     return PT_OK;
 }
@@ -2018,19 +2040,13 @@ static int render_pipelined(pt_ctx *c, const pt_config *cfg, uint32_t n, uint32_
 
 int pt_ctx_render(pt_ctx *c, const pt_config *cfg, void *d_out_rgb, void *hip_stream, const volatile uint8_t *cancel,
                   pt_progress_fn cb, void *user, pt_stats *stats) {
-    if (!c || !d_out_rgb) {
-        set_error("NULL argument");
-        return PT_ERR_INVALID;
-    }
+    if (!c || !d_out_rgb) return refuse("NULL argument");
     uint32_t ib = 0, ie = 0;
     int rc = frame_prologue(c, cfg, &ib, &ie);
     if (rc) return rc;
     const uint32_t n_pipes = (cfg->flags >> 8) & 15u;
     if (n_pipes > 1u && cfg->backend == PT_BACKEND_WAVEFRONT) {
-        if (n_pipes > 8u) {
-            set_error("at most 8 concurrent pipelines");
-            return PT_ERR_INVALID;
-        }
+        if (n_pipes > 8u) return refuse("at most 8 concurrent pipelines");
         if (stats) memset(stats, 0, sizeof *stats);
         const double t0p = now_ms();
         rc = render_pipelined(c, cfg, n_pipes, ib, ie, (float *)d_out_rgb, cancel, cb, user, stats);
@@ -2062,17 +2078,12 @@ int pt_ctx_render(pt_ctx *c, const pt_config *cfg, void *d_out_rgb, void *hip_st
 
 int pt_ctx_accumulate(pt_ctx *c, const pt_config *cfg, void *d_out_rgb, void *hip_stream, const volatile uint8_t *cancel,
                       pt_progress_fn cb, void *user, pt_stats *stats) {
-    if (!c || !d_out_rgb || !cfg) {
-        set_error("NULL argument");
-        return PT_ERR_INVALID;
-    }
+    if (!c || !d_out_rgb || !cfg) return refuse("NULL argument");
     uint32_t ib = 0, ie = 0;
     int rc = frame_prologue(c, cfg, &ib, &ie);
     if (rc) return rc;
-    if (((cfg->flags >> 8) & 15u) > 1u) {
-        set_error("pt_ctx_accumulate does not take PT_FLAG_PIPELINES: its accumulators live in child contexts");
-        return PT_ERR_INVALID;
-    }
+    if (((cfg->flags >> 8) & 15u) > 1u)
+        return refuse("pt_ctx_accumulate does not take PT_FLAG_PIPELINES: its accumulators live in child contexts");
     const host::AccumKey key = host::accum_key(cfg, ib, ie);
     const uint32_t total = owned_pixels(cfg, ib, ie);
     HeldFrame &h = c->held;
@@ -2095,10 +2106,7 @@ int pt_ctx_accumulate(pt_ctx *c, const pt_config *cfg, void *d_out_rgb, void *hi
 }
 
 int pt_ctx_accum_info(const pt_ctx *c, const pt_config *cfg, uint32_t *spp_min, uint32_t *spp_max) {
-    if (!c || !cfg || !spp_min || !spp_max) {
-        set_error("NULL argument");
-        return PT_ERR_INVALID;
-    }
+    if (!c || !cfg || !spp_min || !spp_max) return refuse("NULL argument");
     uint32_t ib = 0, ie = 0;
     const int rc = check_cfg(cfg, &ib, &ie);
     if (rc) return rc;
@@ -2110,25 +2118,16 @@ int pt_ctx_accum_info(const pt_ctx *c, const pt_config *cfg, uint32_t *spp_min, 
 }
 
 int pt_ctx_accum_reset(pt_ctx *c) {
-    if (!c) {
-        set_error("ctx is NULL");
-        return PT_ERR_INVALID;
-    }
+    if (!c) return refuse("ctx is NULL");
     if (c->held.sums.p) HIP_TRY(hipSetDevice(c->device));
     c->held.drop();
     return PT_OK;
 }
 
 int pt_ctx_accum_save(pt_ctx *c, const char *path) {
-    if (!c || !path) {
-        set_error("NULL argument");
-        return PT_ERR_INVALID;
-    }
+    if (!c || !path) return refuse("NULL argument");
     const HeldFrame &h = c->held;
-    if (!h.held()) {
-        set_error("nothing accumulated on this context");
-        return PT_ERR_INVALID;
-    }
+    if (!h.held()) return refuse("nothing accumulated on this context");
     HIP_TRY(hipSetDevice(c->device));
     host::Checkpoint ck;
     static_cast<host::FrameCounts &>(ck) = h;
@@ -2144,14 +2143,8 @@ int pt_ctx_accum_save(pt_ctx *c, const char *path) {
 }
 
 int pt_ctx_accum_load(pt_ctx *c, const char *path) {
-    if (!c || !path) {
-        set_error("NULL argument");
-        return PT_ERR_INVALID;
-    }
-    if (!c->has_scene) {
-        set_error("no scene set: a checkpoint is loaded under the scene it was rendered from");
-        return PT_ERR_INVALID;
-    }
+    if (!c || !path) return refuse("NULL argument");
+    if (!c->has_scene) return refuse("no scene set: a checkpoint is loaded under the scene it was rendered from");
     host::Checkpoint ck;
     std::vector<uint8_t> b;
     const int rc = read_checkpoint(path, host::ckpt_decode, ck, b);
@@ -2169,14 +2162,9 @@ int pt_ctx_accum_load(pt_ctx *c, const char *path) {
 }
 
 int pt_ctx_accum_track_noise(pt_ctx *c, int enabled) {
-    if (!c) {
-        set_error("ctx is NULL");
-        return PT_ERR_INVALID;
-    }
-    if (c->held.held()) {
-        set_error("an accumulator is held: tracking applies to frames started after the call - call pt_ctx_accum_reset first");
-        return PT_ERR_INVALID;
-    }
+    if (!c) return refuse("ctx is NULL");
+    if (c->held.held())
+        return refuse("an accumulator is held: tracking applies to frames started after the call - call pt_ctx_accum_reset first");
     c->acc_track = enabled != 0;
     return PT_OK;
 }
@@ -2232,29 +2220,18 @@ static int held_tracked_frame(const pt_ctx *c, const pt_config *cfg) {
     uint32_t ib = 0, ie = 0;
     const int rc = check_cfg(cfg, &ib, &ie);
     if (rc) return rc;
-    if (!c->held.holds(host::accum_key(cfg, ib, ie))) {
-        set_error("cfg does not name the frame this context holds");
-        return PT_ERR_INVALID;
-    }
-    if (!c->held.tracked()) {
-        set_error("the held frame is not noise-tracked (pt_ctx_accum_track_noise before the frame is started)");
-        return PT_ERR_INVALID;
-    }
+    if (!c->held.holds(host::accum_key(cfg, ib, ie))) return refuse("cfg does not name the frame this context holds");
+    if (!c->held.tracked())
+        return refuse("the held frame is not noise-tracked (pt_ctx_accum_track_noise before the frame is started)");
     return PT_OK;
 }
 
 int pt_ctx_accum_noise(pt_ctx *c, const pt_config *cfg, float *d_error, pt_noise_stats *out, void *hip_stream) {
-    if (!c || !cfg || !out) {
-        set_error("NULL argument");
-        return PT_ERR_INVALID;
-    }
+    if (!c || !cfg || !out) return refuse("NULL argument");
     int rc = held_tracked_frame(c, cfg);
     if (rc) return rc;
     rc = accum_noise(c, d_error, out, hip_stream ? (hipStream_t)hip_stream : c->stream);
-    if (rc == kNoiseNone) {
-        set_error("no part of the frame has samples in both halves yet: accumulate more");
-        return PT_ERR_INVALID;
-    }
+    if (rc == kNoiseNone) return refuse("no part of the frame has samples in both halves yet: accumulate more");
     return rc;
 }
 
@@ -2421,20 +2398,10 @@ int pt_ctx_adaptive_load(pt_ctx *c, const char *path) {
 
 int pt_ctx_radiance(pt_ctx *c, const float o[3], const float d[3], uint32_t depth, uint32_t n_samples, uint64_t seed,
                     uint32_t pixel, uint32_t backend, uint32_t flags, float out_rgb[3], pt_stats *stats) {
-    if (!c || !o || !d || !out_rgb) {
-        set_error("NULL argument");
-        return PT_ERR_INVALID;
-    }
-    if (!c->has_scene) {
-        set_error("no scene set");
-        return PT_ERR_INVALID;
-    }
-    if (n_samples == 0u || n_samples > (1u << 24) || depth >= (uint32_t)kMaxDepth ||
-        (backend != PT_BACKEND_WAVEFRONT && backend != PT_BACKEND_MEGAKERNEL) || ((flags >> 8) & 15u) > 1u) {
-        set_error("n_samples outside 1..2^24, depth >= MAX_DEPTH, unknown backend, or PT_FLAG_PIPELINES (not offered for a one-ray call)");
-        return PT_ERR_INVALID;
-    }
-    HIP_TRY(hipSetDevice(c->device));
+    int rc = host::check_radiance(c, c && c->has_scene, o, d, depth, n_samples, backend, flags, out_rgb);
+    if (rc) return rc;
+    HostCall q(c, "pt_ctx_radiance");
+    if (!q.ok()) return q.finish();
     // a frame of ONE pixel whose samples all start with the given ray: the pixel index is only the RNG counter
     pt_config cfg{};
     cfg.width = 1;
@@ -2457,21 +2424,16 @@ int pt_ctx_radiance(pt_ctx *c, const float o[3], const float d[3], uint32_t dept
     if (stats) memset(stats, 0, sizeof *stats);
     const double t0 = now_ms();
     pt_stats ps{};
-    hipStream_t st = c->stream;
-    int rc = (backend == PT_BACKEND_WAVEFRONT ? render_wavefront : render_mega)(c, form_for(c, flags), &cfg, F, st, nullptr, nullptr,
-                                                                              nullptr, ps, 0u, nullptr);
+    rc = (backend == PT_BACKEND_WAVEFRONT ? render_wavefront : render_mega)(c, form_for(c, flags), &cfg, F, c->stream, nullptr, nullptr,
+                                                                          nullptr, ps, 0u, nullptr);
     if (rc != PT_OK) return rc;
     DevBuf<float> d_out;
-    if ((rc = d_out.ensure(3))) return rc;
-    launch_resolve(st, c->acc.p, d_out.p, 1u, n_samples, c->live.streams, c->live.m, false);  // the mean, not clamped
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e == hipSuccess) e = hipMemcpy(out_rgb, d_out.p, 3 * sizeof(float), hipMemcpyDeviceToHost);
-    d_out.release();
-    if (e != hipSuccess) {
-        set_error(std::string("pt_ctx_radiance: ") + hipGetErrorString(e));
-        return PT_ERR_HIP;
-    }
+    q.room(d_out, 3);
+    q.run([&](hipStream_t st) {
+        launch_resolve(st, c->acc.p, d_out.p, 1u, n_samples, c->live.streams, c->live.m, false);  // the mean, not clamped
+    });
+    q.out(out_rgb, d_out, 3);
+    if ((rc = q.finish())) return rc;
     if (stats) {
         *stats = ps;
         stats->ms_total = now_ms() - t0;
@@ -2480,93 +2442,63 @@ int pt_ctx_radiance(pt_ctx *c, const float o[3], const float d[3], uint32_t dept
 }
 
 int pt_ctx_intersect_streams(pt_ctx *c, const float *o, const float *d, uint32_t n, uint32_t flags, float *t, int32_t *id) {
-    if (!c || !o || !d || !t || !id) {
-        set_error("NULL argument");
-        return PT_ERR_INVALID;
-    }
-    if (!c->has_scene) {
-        set_error("no scene set");
-        return PT_ERR_INVALID;
-    }
+    if (!c || !o || !d || !t || !id) return refuse("NULL argument");
+    if (!c->has_scene) return refuse("no scene set");
     if (n == 0) return PT_OK;
-    HIP_TRY(hipSetDevice(c->device));
     // the rays as ray streams of 4096 slots (the queue layout of the wavefront pipeline), one workgroup per stream
-    const uint32_t cap = 4096u, K = (n + cap - 1u) / cap;
-    std::vector<char> hq(queue_bytes(K, cap), 0);  // slice b: [od0: cap x 16][tp: cap x 16][od1: cap x 8]
-    std::vector<uint32_t> hc(K);
-    for (uint32_t i = 0; i < n; ++i) {
-        char *slice = hq.data() + (size_t)(i / cap) * cap * kRayBytes;
-        const uint32_t j = i % cap;
-        const float4 a = make_float4(o[3 * i], o[3 * i + 1], o[3 * i + 2], d[3 * i]);
-        const float2 bq = make_float2(d[3 * i + 1], d[3 * i + 2]);
-        memcpy(slice + (size_t)j * 16u, &a, sizeof a);
-        memcpy(slice + (size_t)cap * 32u + (size_t)j * 8u, &bq, sizeof bq);
-    }
-    for (uint32_t b = 0; b < K; ++b) hc[b] = (n - b * cap) < cap ? (n - b * cap) : cap;
+    const uint32_t cap = 4096u;
+    std::vector<char> hq;
+    std::vector<uint32_t> hc;
+    host::pack_ray_streams(o, d, n, cap, hq, hc);
+    const uint32_t K = (uint32_t)hc.size();
+    HostCall q(c, "pt_ctx_intersect_streams");
     DevBuf<char> d0;
     DevBuf<float2> dh;
     DevBuf<uint32_t> dc;
     DevBuf<unsigned long long> dr;
-    int rc;
-    if ((rc = d0.ensure(hq.size())) || (rc = dh.ensure((size_t)K * cap)) || (rc = dc.ensure(K)) || (rc = dr.ensure(K))) return rc;
-    hipStream_t st = c->stream;
-    hipError_t e = hipMemcpyAsync(d0.p, hq.data(), hq.size(), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(dc.p, hc.data(), K * sizeof(uint32_t), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemsetAsync(dr.p, 0, K * sizeof(unsigned long long), st);
-    if (e == hipSuccess) {
+    q.in(d0, hq.data(), hq.size());
+    q.in(dc, hc.data(), K);
+    q.room(dr, K, true);
+    q.room(dh, (size_t)K * cap);
+    q.run([&](hipStream_t st) {
         const DevScene S = form_for(c, flags).scene;
-        RayQueue q;
-        q.buf = d0.p;
-        launch_intersect(st, K, S, lds_layout(S, 1u, c->tune.lds_pad), q, dh.p, dc.p, cap, dr.p);
-        e = hipGetLastError();
-    }
+        launch_intersect(st, K, S, lds_layout(S, 1u, c->tune.lds_pad), RayQueue{d0.p}, dh.p, dc.p, cap, dr.p);
+    });
     std::vector<float2> hh((size_t)K * cap);
-    if (e == hipSuccess) e = hipMemcpyAsync(hh.data(), dh.p, hh.size() * sizeof(float2), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    d0.release();
-    dh.release();
-    dc.release();
-    dr.release();
-    if (e != hipSuccess) {
-        set_error(std::string("pt_ctx_intersect_streams: ") + hipGetErrorString(e));
-        return PT_ERR_HIP;
-    }
-    for (uint32_t i = 0; i < n; ++i) {
-        t[i] = hh[i].x;
-        memcpy(&id[i], &hh[i].y, sizeof(int32_t));
-    }
-    return PT_OK;
+    q.out(hh.data(), dh, hh.size());
+    const int rc = q.finish();
+    if (rc == PT_OK) host::unpack_stream_hits(hh.data(), n, t, id);
+    return rc;
+}
+
+// the rays of an interactive query (pt_ctx_intersect, bounds_query: once per click) into the context's scratch, which persists
+// from call to call, and room there for every output of n rays
+static void stage_rays(HostCall &q, pt_ctx *c, const float *o, const float *d, uint32_t n) {
+    q.in(c->q_o, o, 3 * (size_t)n);
+    q.in(c->q_d, d, 3 * (size_t)n);
+    q.room(c->q_t, n);
+    q.room(c->q_x, 3 * (size_t)n);
+    q.room(c->q_n, 3 * (size_t)n);
+    q.room(c->q_oid, n);
+    q.room(c->q_tid, n);
 }
 
 int pt_ctx_intersect(pt_ctx *c, const float *o, const float *d, uint32_t n, float *t, int32_t *object_id,
                      int32_t *tri_id, float *x, float *normal) {
-    if (!c || !o || !d) {
-        set_error("NULL argument");
-        return PT_ERR_INVALID;
-    }
-    if (!c->has_scene) {
-        set_error("no scene set");
-        return PT_ERR_INVALID;
-    }
+    if (!c || !o || !d) return refuse("NULL argument");
+    if (!c->has_scene) return refuse("no scene set");
     if (n == 0) return PT_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    int rc;
-    if ((rc = c->q_o.ensure(3 * (size_t)n)) || (rc = c->q_d.ensure(3 * (size_t)n)) || (rc = c->q_t.ensure(n)) ||
-        (rc = c->q_x.ensure(3 * (size_t)n)) || (rc = c->q_n.ensure(3 * (size_t)n)) || (rc = c->q_oid.ensure(n)) ||
-        (rc = c->q_tid.ensure(n)))
-        return rc;
-    hipStream_t st = c->stream;
-    HIP_TRY(hipMemcpyAsync(c->q_o.p, o, 3 * (size_t)n * sizeof(float), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(c->q_d.p, d, 3 * (size_t)n * sizeof(float), hipMemcpyHostToDevice, st));
-    launch_query(st, c->scene, c->q_o.p, c->q_d.p, n, c->q_t.p, c->q_oid.p, c->q_tid.p, c->q_x.p, c->q_n.p);
-    HIP_TRY(hipGetLastError());
-    if (t) HIP_TRY(hipMemcpyAsync(t, c->q_t.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, st));
-    if (object_id) HIP_TRY(hipMemcpyAsync(object_id, c->q_oid.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    if (tri_id) HIP_TRY(hipMemcpyAsync(tri_id, c->q_tid.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    if (x) HIP_TRY(hipMemcpyAsync(x, c->q_x.p, 3 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost, st));
-    if (normal) HIP_TRY(hipMemcpyAsync(normal, c->q_n.p, 3 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return PT_OK;
+    HostCall q(c, "pt_ctx_intersect");
+    stage_rays(q, c, o, d, n);
+    q.run([&](hipStream_t st) {
+        launch_query(st, c->scene, c->q_o.p, c->q_d.p, n, c->q_t.p, c->q_oid.p, c->q_tid.p, c->q_x.p, c->q_n.p);
+    });
+    q.out(t, c->q_t, n);
+    q.out(object_id, c->q_oid, n);
+    q.out(tri_id, c->q_tid, n);
+    q.out(x, c->q_x, 3 * (size_t)n);
+    q.out(normal, c->q_n, 3 * (size_t)n);
+    return q.finish();
 }
 
 // device form of the bounding boxes (rebuilt after pt_ctx_set_scene / pt_ctx_set_mesh_bounds)
@@ -2585,39 +2517,21 @@ static int upload_boxes(pt_ctx *c) {
 
 static int bounds_query(pt_ctx *c, uint32_t mode, uint32_t object, const float *o, const float *d, uint32_t n, int32_t *hit,
                         float *t, float *x, float *normal, int32_t *object_id) {
-    if (!c || !o || !d) {
-        set_error("NULL argument");
-        return PT_ERR_INVALID;
-    }
-    if (!c->has_scene) {
-        set_error("no scene set");
-        return PT_ERR_INVALID;
-    }
-    if (mode == 0u && object >= c->h_objs.size()) {
-        set_error("object index out of range");
-        return PT_ERR_INVALID;
-    }
-    if (n == 0) return PT_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    int rc = upload_boxes(c);
-    if (rc) return rc;
-    if ((rc = c->q_o.ensure(3 * (size_t)n)) || (rc = c->q_d.ensure(3 * (size_t)n)) || (rc = c->q_t.ensure(n)) ||
-        (rc = c->q_x.ensure(3 * (size_t)n)) || (rc = c->q_n.ensure(3 * (size_t)n)) || (rc = c->q_oid.ensure(n)) ||
-        (rc = c->q_tid.ensure(n)))
-        return rc;
-    hipStream_t st = c->stream;
-    HIP_TRY(hipMemcpyAsync(c->q_o.p, o, 3 * (size_t)n * sizeof(float), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(c->q_d.p, d, 3 * (size_t)n * sizeof(float), hipMemcpyHostToDevice, st));
-    launch_bounds(st, c->scene, c->d_boxes.p, mode, object, c->q_o.p, c->q_d.p, n, c->q_tid.p, c->q_t.p, c->q_x.p, c->q_n.p,
-                  c->q_oid.p);
-    HIP_TRY(hipGetLastError());
-    if (hit) HIP_TRY(hipMemcpyAsync(hit, c->q_tid.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    if (t) HIP_TRY(hipMemcpyAsync(t, c->q_t.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, st));
-    if (x) HIP_TRY(hipMemcpyAsync(x, c->q_x.p, 3 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost, st));
-    if (normal) HIP_TRY(hipMemcpyAsync(normal, c->q_n.p, 3 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost, st));
-    if (object_id) HIP_TRY(hipMemcpyAsync(object_id, c->q_oid.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return PT_OK;
+    int rc = host::check_bounds_query(c, c && c->has_scene, mode, object, c ? (uint32_t)c->h_objs.size() : 0u, o, d);
+    if (rc || n == 0) return rc;
+    HostCall q(c, mode ? "pt_ctx_orbit_point" : "pt_ctx_intersect_bounds");
+    if (q.ok() && (rc = upload_boxes(c))) return rc;
+    stage_rays(q, c, o, d, n);
+    q.run([&](hipStream_t st) {
+        launch_bounds(st, c->scene, c->d_boxes.p, mode, object, c->q_o.p, c->q_d.p, n, c->q_tid.p, c->q_t.p, c->q_x.p, c->q_n.p,
+                      c->q_oid.p);
+    });
+    q.out(hit, c->q_tid, n);
+    q.out(t, c->q_t, n);
+    q.out(x, c->q_x, 3 * (size_t)n);
+    q.out(normal, c->q_n, 3 * (size_t)n);
+    q.out(object_id, c->q_oid, n);
+    return q.finish();
 }
 
 int pt_ctx_intersect_bounds(pt_ctx *c, uint32_t object, const float *o, const float *d, uint32_t n, int32_t *hit, float *t,
@@ -2631,24 +2545,16 @@ int pt_ctx_orbit_point(pt_ctx *c, const float *o, const float *d, uint32_t n, in
 }
 
 int pt_ctx_set_mesh_bounds(pt_ctx *c, uint32_t object, const pt_triangle box[12]) {
-    if (!c || !box) {
-        set_error("NULL argument");
-        return PT_ERR_INVALID;
-    }
-    if (!c->has_scene || object >= c->h_objs.size() || c->h_objs[object].kind != PT_MESH) {
-        set_error("no scene set, or object is not a mesh of it");
-        return PT_ERR_INVALID;
-    }
+    if (!c || !box) return refuse("NULL argument");
+    if (!c->has_scene || object >= c->h_objs.size() || c->h_objs[object].kind != PT_MESH)
+        return refuse("no scene set, or object is not a mesh of it");
     memcpy(&c->h_boxes[(size_t)12 * object], box, 12 * sizeof(pt_triangle));
     c->boxes_dirty = true;
     return PT_OK;
 }
 
 int pt_mesh_bounding_box(const pt_triangle *tris, uint32_t n_tris, pt_triangle out[12]) {
-    if (!tris || !out || n_tris == 0) {
-        set_error("NULL argument or empty mesh");
-        return PT_ERR_INVALID;
-    }
+    if (!tris || !out || n_tris == 0) return refuse("NULL argument or empty mesh");
     host::mesh_bounding_box(tris, n_tris, out);
     return PT_OK;
 }
@@ -2656,15 +2562,10 @@ int pt_mesh_bounding_box(const pt_triangle *tris, uint32_t n_tris, pt_triangle o
 void pt_host_sincos(float y, float *s, float *c) { sincos_f32(y, s, c); }
 
 int pt_ctx_snapshot(pt_ctx *c, void *d_out_rgb, uint32_t *spp_done) {
-    if (!c || !d_out_rgb) {
-        set_error("NULL argument");
-        return PT_ERR_INVALID;
-    }
-    if (c->live.npix == 0 || c->live.spp_issued == 0) {
-        set_error("no frame in progress on this context (call from the progress callback of pt_ctx_render; under "
-                  "PT_FLAG_PIPELINES the accumulators live in child contexts and no snapshot is offered)");
-        return PT_ERR_INVALID;
-    }
+    if (!c || !d_out_rgb) return refuse("NULL argument");
+    if (c->live.npix == 0 || c->live.spp_issued == 0)
+        return refuse("no frame in progress on this context (call from the progress callback of pt_ctx_render; under "
+                      "PT_FLAG_PIPELINES the accumulators live in child contexts and no snapshot is offered)");
     HIP_TRY(hipSetDevice(c->device));
     // stream order: the resolve runs after every pass issued so far, i.e. over live.spp_issued samples per pixel.  A call
     // rendered in parts: the finished parts are copied from the call's own output, the part in progress is resolved,
@@ -2694,73 +2595,39 @@ int pt_ctx_snapshot(pt_ctx *c, void *d_out_rgb, uint32_t *spp_done) {
 
 int pt_ctx_numerics_probe(pt_ctx *c, const float *in, uint32_t n, float *out_sin, float *out_cos, float *out_sqrt,
                           float *out_rcp, uint32_t *out_philox) {
-    if (!c || !in || !out_sin || !out_cos || !out_sqrt || !out_rcp || !out_philox || n == 0) {
-        set_error("NULL argument");
-        return PT_ERR_INVALID;
-    }
-    HIP_TRY(hipSetDevice(c->device));
+    if (!c || !in || !out_sin || !out_cos || !out_sqrt || !out_rcp || !out_philox || n == 0) return refuse("NULL argument");
+    HostCall q(c, "pt_ctx_numerics_probe");
     DevBuf<float> d_in, d_s, d_c, d_q, d_r;
     DevBuf<uint32_t> d_p;
-    int rc;
-    if ((rc = d_in.ensure(n)) || (rc = d_s.ensure(n)) || (rc = d_c.ensure(n)) || (rc = d_q.ensure(n)) ||
-        (rc = d_r.ensure(n)) || (rc = d_p.ensure(4 * (size_t)n)))
-        return rc;
-    hipError_t e = hipMemcpy(d_in.p, in, (size_t)n * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        launch_numerics(c->stream, d_in.p, n, d_s.p, d_c.p, d_q.p, d_r.p, d_p.p);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = hipMemcpy(out_sin, d_s.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(out_cos, d_c.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(out_sqrt, d_q.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(out_rcp, d_r.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(out_philox, d_p.p, 4 * (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost);
-    d_in.release();
-    d_s.release();
-    d_c.release();
-    d_q.release();
-    d_r.release();
-    d_p.release();
-    if (e != hipSuccess) {
-        set_error(std::string("numerics probe: ") + hipGetErrorString(e));
-        return PT_ERR_HIP;
-    }
-    return PT_OK;
+    q.in(d_in, in, n);
+    q.room(d_s, n);
+    q.room(d_c, n);
+    q.room(d_q, n);
+    q.room(d_r, n);
+    q.room(d_p, 4 * (size_t)n);
+    q.run([&](hipStream_t st) { launch_numerics(st, d_in.p, n, d_s.p, d_c.p, d_q.p, d_r.p, d_p.p); });
+    q.out(out_sin, d_s, n);
+    q.out(out_cos, d_c, n);
+    q.out(out_sqrt, d_q, n);
+    q.out(out_rcp, d_r, n);
+    q.out(out_philox, d_p, 4 * (size_t)n);
+    return q.finish();
 }
 
+static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "the sweeps' counters are copied into the caller's uint64_t as they are");
+
 int pt_ctx_numerics_sweep(pt_ctx *c, uint64_t out[4]) {
-    if (!c || !out) {
-        set_error("NULL argument");
-        return PT_ERR_INVALID;
-    }
-    HIP_TRY(hipSetDevice(c->device));
+    if (!c || !out) return refuse("NULL argument");
+    HostCall q(c, "pt_ctx_numerics_sweep");
     DevBuf<unsigned long long> d;
-    int rc = d.ensure(4);
-    if (rc) return rc;
-    hipError_t e = hipMemsetAsync(d.p, 0, 4 * sizeof(unsigned long long), c->stream);
-    if (e == hipSuccess) {
-        launch_numerics_sweep(c->stream, d.p);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    unsigned long long h[4] = {0, 0, 0, 0};
-    if (e == hipSuccess) e = hipMemcpy(h, d.p, sizeof h, hipMemcpyDeviceToHost);
-    d.release();
-    if (e != hipSuccess) {
-        set_error(std::string("numerics sweep: ") + hipGetErrorString(e));
-        return PT_ERR_HIP;
-    }
-    for (int i = 0; i < 4; ++i) out[i] = h[i];
-    return PT_OK;
+    q.room(d, 4, true);
+    q.run([&](hipStream_t st) { launch_numerics_sweep(st, d.p); });
+    q.out(reinterpret_cast<unsigned long long *>(out), d, 4);
+    return q.finish();
 }
 
 int pt_ctx_sincos_sweep(pt_ctx *c, uint64_t out[2]) {
-    if (!c || !out) {
-        set_error("NULL argument");
-        return PT_ERR_INVALID;
-    }
-    HIP_TRY(hipSetDevice(c->device));
+    if (!c || !out) return refuse("NULL argument");
     // the host instantiation of the shared numerics header on the 2^24 arguments shade_surface can form (mod.rs:691,703)
     const uint32_t n = 1u << 24;
     std::vector<uint32_t> hs(n), hc(n);
@@ -2771,84 +2638,41 @@ int pt_ctx_sincos_sweep(pt_ctx *c, uint64_t out[2]) {
         memcpy(&hs[k], &s, 4);
         memcpy(&hc[k], &co, 4);
     }
+    HostCall q(c, "pt_ctx_sincos_sweep");
     DevBuf<uint32_t> ds, dc;
     DevBuf<unsigned long long> d;
-    int rc;
-    if ((rc = ds.ensure(n)) || (rc = dc.ensure(n)) || (rc = d.ensure(2))) return rc;
-    hipError_t e = hipMemcpy(ds.p, hs.data(), (size_t)n * 4u, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dc.p, hc.data(), (size_t)n * 4u, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemsetAsync(d.p, 0, 2 * sizeof(unsigned long long), c->stream);
-    if (e == hipSuccess) {
-        launch_sincos_sweep(c->stream, ds.p, dc.p, d.p);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    unsigned long long h[2] = {0, 0};
-    if (e == hipSuccess) e = hipMemcpy(h, d.p, sizeof h, hipMemcpyDeviceToHost);
-    ds.release();
-    dc.release();
-    d.release();
-    if (e != hipSuccess) {
-        set_error(std::string("sincos sweep: ") + hipGetErrorString(e));
-        return PT_ERR_HIP;
-    }
-    out[0] = h[0];
-    out[1] = h[1];
-    return PT_OK;
+    q.in(ds, hs.data(), n);
+    q.in(dc, hc.data(), n);
+    q.room(d, 2, true);
+    q.run([&](hipStream_t st) { launch_sincos_sweep(st, ds.p, dc.p, d.p); });
+    q.out(reinterpret_cast<unsigned long long *>(out), d, 2);
+    return q.finish();
 }
 
 int pt_ctx_primary_rays(pt_ctx *c, uint32_t width, uint32_t height, uint64_t seed, const uint32_t *pixel, const uint32_t *sample,
                         uint32_t n, uint32_t form, float *o, float *d) {
-    if (!c || !pixel || !sample || !o || !d || n == 0 || form > 1u) {
-        set_error("NULL argument, n == 0 or an unknown form");
-        return PT_ERR_INVALID;
-    }
-    if (!c->has_scene) {
-        set_error("no scene (the camera comes with it): call pt_ctx_set_scene first");
-        return PT_ERR_INVALID;
-    }
     pt_config cfg{};
-    cfg.width = width;
-    cfg.height = height;
-    cfg.spp = 1;
-    cfg.seed = seed;
     uint32_t ib = 0, ie = 0;
-    int rc = check_cfg(&cfg, &ib, &ie);
+    const int rc = host::check_primary_rays(c, c && c->has_scene, width, height, seed, pixel, sample, n, form, o, d, cfg, &ib, &ie);
     if (rc) return rc;
-    for (uint32_t i = 0; i < n; ++i)
-        if (pixel[i] >= (uint64_t)width * height || sample[i] >= (1u << 24)) {
-            set_error("pixel index outside the frame or sample >= 2^24");
-            return PT_ERR_INVALID;
-        }
-    HIP_TRY(hipSetDevice(c->device));
+    HostCall q(c, "pt_ctx_primary_rays");
     const FrameParams F = make_frame(c, &cfg, ib, ie);
     DevBuf<uint32_t> dp, dsm;
     DevBuf<float> d_o, d_d;
-    if ((rc = dp.ensure(n)) || (rc = dsm.ensure(n)) || (rc = d_o.ensure(3 * (size_t)n)) || (rc = d_d.ensure(3 * (size_t)n))) return rc;
-    hipError_t e = hipMemcpy(dp.p, pixel, (size_t)n * 4u, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dsm.p, sample, (size_t)n * 4u, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        launch_primary_rays(c->stream, F, dp.p, dsm.p, n, form, d_o.p, d_d.p);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = hipMemcpy(o, d_o.p, 3 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(d, d_d.p, 3 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost);
-    dp.release();
-    dsm.release();
-    d_o.release();
-    d_d.release();
-    if (e != hipSuccess) {
-        set_error(std::string("primary rays: ") + hipGetErrorString(e));
-        return PT_ERR_HIP;
-    }
-    return PT_OK;
+    q.in(dp, pixel, n);
+    q.in(dsm, sample, n);
+    q.room(d_o, 3 * (size_t)n);
+    q.room(d_d, 3 * (size_t)n);
+    q.run([&](hipStream_t st) { launch_primary_rays(st, F, dp.p, dsm.p, n, form, d_o.p, d_d.p); });
+    q.out(o, d_o, 3 * (size_t)n);
+    q.out(d, d_d, 3 * (size_t)n);
+    return q.finish();
 }
 
 int pt_ctx_scatter(pt_ctx *c, uint64_t seed, uint32_t form, const pt_scatter_item *items, const pt_scatter_surface *surfaces,
                    uint32_t n, pt_scatter_out *out) {
     std::vector<ScatterSurf> given;
-    int rc = host::check_scatter(c, form, items, surfaces, n, out, given);
+    const int rc = host::check_scatter(c, form, items, surfaces, n, out, given);
     if (rc) return rc;
     if (device_count_quiet() <= 0) {
         set_error("no HIP device: libptrace_hip has no CPU fallback");
@@ -2857,7 +2681,6 @@ int pt_ctx_scatter(pt_ctx *c, uint64_t seed, uint32_t form, const pt_scatter_ite
     const uint32_t src = form & kScatterSourceMask;
     if (src != PT_SCATTER_GIVEN && !c->has_scene) return refuse("no scene set");
     if (src == PT_SCATTER_BY_RANK && !c->cand_ok) return refuse("PT_SCATTER_BY_RANK: the scene has no candidate tables");
-    HIP_TRY(hipSetDevice(c->device));
     ScatterCall call{};
     call.n = n;
     call.form = form;
@@ -2869,29 +2692,21 @@ int pt_ctx_scatter(pt_ctx *c, uint64_t seed, uint32_t form, const pt_scatter_ite
         const size_t room = scatter_head_room(c->scene) / sizeof(SurfRec);
         call.head = (uint32_t)std::min<size_t>(lds_layout(F, 1u, c->tune.lds_pad).surf_head, room);
     }
+    HostCall q(c, "pt_ctx_scatter");
     DevBuf<pt_scatter_item> d_items;
     DevBuf<ScatterSurf> d_surf;
     DevBuf<pt_scatter_out> d_out;
-    if ((rc = d_items.ensure(n)) || (rc = d_out.ensure(n)) || (!given.empty() && (rc = d_surf.ensure(n)))) return rc;
-    hipStream_t st = c->stream;
-    hipError_t e = hipMemcpyAsync(d_items.p, items, (size_t)n * sizeof(pt_scatter_item), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && !given.empty())
-        e = hipMemcpyAsync(d_surf.p, given.data(), (size_t)n * sizeof(ScatterSurf), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) {
+    q.in(d_items, items, n);
+    if (!given.empty()) q.in(d_surf, given.data(), n);
+    q.room(d_out, n);
+    q.run([&](hipStream_t st) {
         call.items = d_items.p;
         call.surf = d_surf.p;
         call.out = d_out.p;
         launch_scatter(st, c->scene, call);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out.p, (size_t)n * sizeof(pt_scatter_out), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    else (void)hipStreamSynchronize(st);  // (the host arrays of the copies issued so far stay the caller's until they have run)
-    if (e != hipSuccess) {
-        set_error(std::string("scatter: ") + hipGetErrorString(e));
-        return PT_ERR_HIP;
-    }
-    return PT_OK;
+    });
+    q.out(out, d_out, n);
+    return q.finish();
 }
 
 int pt_ctx_render_aov(pt_ctx *c, const pt_config *cfg, float *d_albedo, float *d_normal, float *d_depth, int32_t *d_object_id,
@@ -3309,10 +3124,7 @@ static int render_band_to_host(int dev, const pt_config *cfg, const pt_camera *c
 int pt_render(const pt_config *cfg, const pt_camera *cam, const pt_object *objs, uint32_t n_objs,
               const pt_triangle *tris, uint32_t n_tris, float *out_rgb, const volatile uint8_t *cancel,
               pt_progress_fn cb, void *user, pt_stats *stats) {
-    if (!out_rgb) {
-        set_error("out_rgb is NULL");
-        return PT_ERR_INVALID;
-    }
+    if (!out_rgb) return refuse("out_rgb is NULL");
     int dev = 0;
     if (const char *e = getenv("PT_DEVICE")) dev = atoi(e);
     return render_band_to_host(dev, cfg, cam, objs, n_objs, tris, n_tris, out_rgb, cancel, cb, user, stats, nullptr);
@@ -3321,10 +3133,7 @@ int pt_render(const pt_config *cfg, const pt_camera *cam, const pt_object *objs,
 int pt_render_multi(const pt_config *cfg, uint32_t n_ranks, const pt_camera *cam, const pt_object *objs,
                     uint32_t n_objs, const pt_triangle *tris, uint32_t n_tris, float *out_rgb,
                     const volatile uint8_t *cancel, pt_progress_fn cb, void *user, pt_stats *stats) {
-    if (!out_rgb || n_ranks == 0 || n_ranks > 64) {
-        set_error("out_rgb is NULL or n_ranks outside 1..64");
-        return PT_ERR_INVALID;
-    }
+    if (!out_rgb || n_ranks == 0 || n_ranks > 64) return refuse("out_rgb is NULL or n_ranks outside 1..64");
     uint32_t ib = 0, ie = 0;
     int rc = check_cfg(cfg, &ib, &ie);
     if (rc) return rc;

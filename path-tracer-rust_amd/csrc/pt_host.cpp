@@ -1977,5 +1977,62 @@ int check_scatter(const void *ctx, uint32_t form, const pt_scatter_item *items, 
     return PT_OK;
 }
 
+// ---- host-array queries (ptrace.h, pt_host.h)
+int check_radiance(const void *ctx, bool has_scene, const float *o, const float *d, uint32_t depth, uint32_t n_samples, uint32_t backend,
+                   uint32_t flags, const float *out_rgb) {
+    if (!ctx || !o || !d || !out_rgb) return refuse("NULL argument");
+    if (!has_scene) return refuse("no scene set");
+    if (n_samples == 0u || n_samples > (1u << 24) || depth >= (uint32_t)kMaxDepth ||
+        (backend != PT_BACKEND_WAVEFRONT && backend != PT_BACKEND_MEGAKERNEL) || ((flags >> 8) & 15u) > 1u)
+        return refuse("n_samples outside 1..2^24, depth >= MAX_DEPTH, unknown backend, or PT_FLAG_PIPELINES (not offered for a one-ray call)");
+    return PT_OK;
+}
+
+int check_primary_rays(const void *ctx, bool has_scene, uint32_t width, uint32_t height, uint64_t seed, const uint32_t *pixel,
+                       const uint32_t *sample, uint32_t n, uint32_t form, const float *o, const float *d, pt_config &cfg,
+                       uint32_t *idx_begin, uint32_t *idx_end) {
+    if (!ctx || !pixel || !sample || !o || !d || n == 0 || form > 1u) return refuse("NULL argument, n == 0 or an unknown form");
+    if (!has_scene) return refuse("no scene (the camera comes with it): call pt_ctx_set_scene first");
+    cfg = pt_config{};
+    cfg.width = width;
+    cfg.height = height;
+    cfg.spp = 1;
+    cfg.seed = seed;
+    const int rc = check_cfg(&cfg, idx_begin, idx_end);
+    if (rc) return rc;
+    for (uint32_t i = 0; i < n; ++i)
+        if (pixel[i] >= (uint64_t)width * height || sample[i] >= (1u << 24))
+            return refuse("pixel index outside the frame or sample >= 2^24");
+    return PT_OK;
+}
+
+int check_bounds_query(const void *ctx, bool has_scene, uint32_t mode, uint32_t object, uint32_t n_objs, const float *o, const float *d) {
+    if (!ctx || !o || !d) return refuse("NULL argument");
+    if (!has_scene) return refuse("no scene set");
+    if (mode == 0u && object >= n_objs) return refuse("object index out of range");
+    return PT_OK;
+}
+
+void pack_ray_streams(const float *o, const float *d, uint32_t n, uint32_t cap, std::vector<char> &bytes, std::vector<uint32_t> &counts) {
+    const uint32_t K = (n + cap - 1u) / cap;
+    bytes.assign(queue_bytes(K, cap), 0);  // slice b: [od0: cap x 16][tp: cap x 16][od1: cap x 8]
+    counts.resize(K);
+    for (uint32_t i = 0; i < n; ++i) {
+        char *slice = bytes.data() + (size_t)(i / cap) * cap * kRayBytes;
+        const uint32_t j = i % cap;
+        const float od0[4] = {o[3 * i], o[3 * i + 1], o[3 * i + 2], d[3 * i]}, od1[2] = {d[3 * i + 1], d[3 * i + 2]};
+        memcpy(slice + (size_t)j * 16u, od0, sizeof od0);
+        memcpy(slice + (size_t)cap * 32u + (size_t)j * 8u, od1, sizeof od1);
+    }
+    for (uint32_t b = 0; b < K; ++b) counts[b] = (n - b * cap) < cap ? (n - b * cap) : cap;
+}
+
+void unpack_stream_hits(const void *hits, uint32_t n, float *t, int32_t *id) {
+    for (uint32_t i = 0; i < n; ++i) {
+        memcpy(&t[i], (const char *)hits + (size_t)i * 8u, 4);
+        memcpy(&id[i], (const char *)hits + (size_t)i * 8u + 4u, 4);
+    }
+}
+
 }  // namespace host
 }  // namespace pt

@@ -500,5 +500,24 @@ void adckpt_encode_head(const AdaptiveCheckpoint &ck, std::vector<uint8_t> &b);
 // as ckpt_decode; kCkptBad also for nA > count, a count above 2^24, an E where a half is empty, sizes that do not fit the tiles
 int adckpt_decode(uint64_t file_size, const uint8_t *b, size_t n, AdaptiveCheckpoint &out, std::string &why);
 
+// ---- host-array queries (pt_ctx_radiance .. pt_ctx_scatter, ptrace.h; pt_api.hip: HostCall): pure, tested on the CPU
+// (host/query_check.cpp).  The refusals of the calls that test more than "NULL / no scene", in each call's order: PT_ERR_INVALID +
+// message.  ctx is never dereferenced; the arrays are only read past the refusals that do not need them.
+int check_radiance(const void *ctx, bool has_scene, const float *o, const float *d, uint32_t depth, uint32_t n_samples, uint32_t backend,
+                   uint32_t flags, const float *out_rgb);
+// PT_OK: cfg is the width x height frame of one sample the rays belong to, [*idx_begin, *idx_end) its band (check_cfg's)
+int check_primary_rays(const void *ctx, bool has_scene, uint32_t width, uint32_t height, uint64_t seed, const uint32_t *pixel,
+                       const uint32_t *sample, uint32_t n, uint32_t form, const float *o, const float *d, pt_config &cfg,
+                       uint32_t *idx_begin, uint32_t *idx_end);
+// pt_ctx_intersect_bounds (mode 0: `object` of n_objs) and pt_ctx_orbit_point (mode 1)
+int check_bounds_query(const void *ctx, bool has_scene, uint32_t mode, uint32_t object, uint32_t n_objs, const float *o, const float *d);
+// n rays (o, d: 3 floats each) as K = ceil(n / cap) slices of a ray queue (pt_kernels.h: RayQueue), cap * kRayBytes bytes each.
+// Slot j of slice b is ray b * cap + j: od0 = (ox, oy, oz, dx), tp = 0, od1 = (dy, dz).  counts[b]: the rays of slice b,
+// min(cap, n - b * cap); the slots behind them are zero.
+void pack_ray_streams(const float *o, const float *d, uint32_t n, uint32_t cap, std::vector<char> &bytes, std::vector<uint32_t> &counts);
+// the inverse for the intersect step's results - per slot, one slice after the other, a float2 (hit distance, hit id as bits); this
+// header is also compiled without HIP's vector types, hence the bytes - of the first n rays
+void unpack_stream_hits(const void *hits, uint32_t n, float *t, int32_t *id);
+
 }  // namespace host
 }  // namespace pt
