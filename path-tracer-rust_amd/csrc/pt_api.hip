@@ -109,95 +109,89 @@ struct DevTable {
     }
 };
 
-// The frame pt_ctx_accumulate keeps between calls, and its one owner: host::FrameCounts plus the device planes - the sums, [3]
-// planes of `total` u64, and for a noise-tracked frame the sums of half A of its samples in `a`, laid out as `sums` (half B: sums
-// - a).  start() is the only place that gives the counts any entries, after the planes are allocated and filled: a frame is held
-// whole or not at all.
-struct HeldFrame : host::FrameCounts {
-    DevBuf<unsigned long long> sums, a;
+// The device buffers of one state, made large enough and filled one after the other: each from host bytes (a checkpoint's: on the
+// device when done() returns) or, from NULL, with a byte value on `st`.  The first failure stops the rest; done() returns it - a
+// HIP failure's message begins "uploading the checkpoint: " or, when nothing was uploaded, with `clearing`.
+struct DevFill {
+    hipStream_t st;
+    const char *clearing;
+    int rc = PT_OK;
+    bool uploaded = false;
+    template <class T>
+    void operator()(DevBuf<T> &d, size_t count, const void *from, int byte = 0) {
+        if (rc || (rc = d.ensure(count))) return;
+        uploaded = uploaded || from;
+        hip(from ? hipMemcpy(d.p, from, count * sizeof(T), hipMemcpyHostToDevice) : hipMemsetAsync(d.p, byte, count * sizeof(T), st));
+    }
+    void hip(hipError_t e) {
+        if (e != hipSuccess) rc = PT_ERR_HIP, set_error(std::string(uploaded ? "uploading the checkpoint: " : clearing) + hipGetErrorString(e));
+    }
+    int done() {
+        if (!rc && uploaded) hip(hipStreamSynchronize(st));
+        return rc;
+    }
+};
 
+// The device planes of a held frame and their one owner: the sums, [3] planes of `total` u64, and the sums of half A of the
+// samples in `a`, laid out as `sums` (half B: sums - a) - only when asked for: an untracked frame allocates no half A.
+struct HeldPlanes {
+    DevBuf<unsigned long long> sums, a;
+    void release() { sums.release(), a.release(); }
+    void fill(DevFill &fill, uint32_t total, bool with_a, const uint8_t *from_sums, const uint8_t *from_a) {
+        fill(sums, 3 * (size_t)total, from_sums);
+        if (with_a) fill(a, 3 * (size_t)total, from_a);
+    }
+};
+
+// The frame pt_ctx_accumulate keeps between calls, and its one owner: host::FrameCounts plus the planes, half A's for a noise-
+// tracked frame.  start() is the only place that gives the counts any entries, after the planes are allocated and filled: a frame
+// is held whole or not at all.
+struct HeldFrame : host::FrameCounts, HeldPlanes {
     void drop() {
         static_cast<host::FrameCounts &>(*this) = {};
-        sums.release();
-        a.release();
+        release();
     }
-    // Hold the frame f in place of whatever was held.  The planes come from the host bytes from_sums / from_a (a checkpoint's:
-    // they are on the device when this returns) or start at zero on `st` (NULL).  On any failure nothing is held.
+    // Hold the frame f in place of whatever was held.  The planes come from the host bytes from_sums / from_a (a checkpoint's)
+    // or start at zero on `st` (NULL).  On any failure nothing is held, and the memory is given back.
     int start(host::FrameCounts f, const uint8_t *from_sums, const uint8_t *from_a, hipStream_t st) {
         drop();
-        const size_t bytes = 3 * (size_t)f.total * sizeof(unsigned long long);
-        int rc = sums.ensure(3 * (size_t)f.total);
-        if (!rc && f.tracked()) rc = a.ensure(3 * (size_t)f.total);
-        if (rc) {
-            drop();
-            return rc;
-        }
-        auto fill = [&](unsigned long long *d, const uint8_t *from) {
-            return from ? hipMemcpy(d, from, bytes, hipMemcpyHostToDevice) : hipMemsetAsync(d, 0, bytes, st);
-        };
-        hipError_t e = fill(sums.p, from_sums);
-        if (e == hipSuccess && f.tracked()) e = fill(a.p, from_a);
-        if (e == hipSuccess && from_sums) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) {
-            set_error(std::string(from_sums ? "uploading the checkpoint: " : "clearing the held sums: ") + hipGetErrorString(e));
-            drop();
-            return PT_ERR_HIP;
-        }
-        static_cast<host::FrameCounts &>(*this) = std::move(f);
-        return PT_OK;
+        DevFill fill{st, "clearing the held sums: "};
+        HeldPlanes::fill(fill, f.total, f.tracked(), from_sums, from_a);
+        if (fill.done()) drop();
+        else static_cast<host::FrameCounts &>(*this) = std::move(f);
+        return fill.rc;
     }
 };
 
 // The adaptive frame a context keeps between calls (pt_ctx_accumulate_adaptive), and its one owner: host::AdaptiveFrame plus the
-// device side - the held sums and half A's ([3] planes of `total` u64 each) and the tiles' table (per tile the count, nA and the
-// last E).  start() is the only place that makes a frame held, after everything is allocated and filled: a frame is held whole or
-// not at all.  forget() stops holding it and keeps the memory for the next frame (pt_ctx_render_adaptive renders frame after
-// frame); drop() gives the memory back.
-struct HeldAdaptive : host::AdaptiveFrame {
-    DevBuf<unsigned long long> sums, a, err;
+// device side - the planes, both of them, and the tiles' table (per tile the count, nA and the last E).  start() is the only place
+// that makes a frame held, after everything is allocated and filled: a frame is held whole or not at all.  forget() stops holding
+// it and keeps the memory for the next frame (pt_ctx_render_adaptive renders frame after frame); drop() gives the memory back.
+struct HeldAdaptive : host::AdaptiveFrame, HeldPlanes {
+    DevBuf<unsigned long long> err;
     DevBuf<uint32_t> cnt, na;
     host::TileGeometry geo{};
 
     void forget() { static_cast<host::AdaptiveFrame &>(*this) = {}; }
     void drop() {
         forget();
-        sums.release();
-        a.release();
-        err.release();
-        cnt.release();
-        na.release();
+        release(), err.release(), cnt.release(), na.release();
     }
     // Hold the frame f (tiles as g cuts it) in place of whatever was held.  The state comes from a checkpoint - the table and the
-    // host bytes from_sums / from_a, on the device when this returns - or starts at zero on `st` (table NULL).  On any failure
-    // nothing is held.
+    // host bytes from_sums / from_a - or starts at zero on `st` (table NULL).  On any failure nothing is held, and the memory is
+    // given back.
     int start(const host::AdaptiveFrame &f, const host::TileGeometry &g, const host::TileTable *table, const uint8_t *from_sums,
               const uint8_t *from_a, hipStream_t st) {
         forget();
-        const size_t planes = 3 * (size_t)f.total, bytes = planes * sizeof(unsigned long long);
-        int rc;
-        if ((rc = sums.ensure(planes)) || (rc = a.ensure(planes)) || (rc = err.ensure(f.tiles)) || (rc = cnt.ensure(f.tiles)) ||
-            (rc = na.ensure(f.tiles)))
-            return rc;
-        hipError_t e;
-        if (table) {
-            if ((e = hipMemcpy(sums.p, from_sums, bytes, hipMemcpyHostToDevice)) == hipSuccess &&
-                (e = hipMemcpy(a.p, from_a, bytes, hipMemcpyHostToDevice)) == hipSuccess &&
-                (e = hipMemcpy(err.p, table->err.data(), (size_t)f.tiles * sizeof(unsigned long long), hipMemcpyHostToDevice)) == hipSuccess &&
-                (e = hipMemcpy(cnt.p, table->cnt.data(), (size_t)f.tiles * sizeof(uint32_t), hipMemcpyHostToDevice)) == hipSuccess)
-                e = hipMemcpy(na.p, table->na.data(), (size_t)f.tiles * sizeof(uint32_t), hipMemcpyHostToDevice);
-        } else {
-            if ((e = hipMemsetAsync(sums.p, 0, bytes, st)) == hipSuccess && (e = hipMemsetAsync(a.p, 0, bytes, st)) == hipSuccess &&
-                (e = hipMemsetAsync(err.p, 0xff, (size_t)f.tiles * sizeof(unsigned long long), st)) == hipSuccess &&  // kTileNoError
-                (e = hipMemsetAsync(cnt.p, 0, (size_t)f.tiles * sizeof(uint32_t), st)) == hipSuccess)
-                e = hipMemsetAsync(na.p, 0, (size_t)f.tiles * sizeof(uint32_t), st);
-        }
-        if (e != hipSuccess) {
-            set_error(std::string(table ? "uploading the checkpoint: " : "clearing the held adaptive frame: ") + hipGetErrorString(e));
-            return PT_ERR_HIP;
-        }
-        static_cast<host::AdaptiveFrame &>(*this) = f;
         geo = g;
-        return PT_OK;
+        DevFill fill{st, "clearing the held adaptive frame: "};
+        HeldPlanes::fill(fill, f.total, true, from_sums, from_a);
+        fill(err, f.tiles, table ? table->err.data() : nullptr, 0xff);  // kTileNoError
+        fill(cnt, f.tiles, table ? table->cnt.data() : nullptr);
+        fill(na, f.tiles, table ? table->na.data() : nullptr);
+        if (fill.done()) drop();
+        else static_cast<host::AdaptiveFrame &>(*this) = f;
+        return fill.rc;
     }
     // the tiles' table as the device holds it (the host waits for `st`)
     int download(host::TileTable &t, hipStream_t st) const {
@@ -1405,6 +1399,33 @@ int read_checkpoint(const char *path, Decode decode, Ckpt &ck, std::vector<uint8
     return PT_OK;
 }
 
+// pt_ctx_accum_save's and pt_ctx_adaptive_save's steps behind the file's head in b (the context's device is current): the planes
+// (half A's when with_a), the seal, the file written beside `path` and renamed
+int save_checkpoint(std::vector<uint8_t> &b, const HeldPlanes &h, uint32_t total, bool with_a, const char *path) {
+    const size_t at = b.size(), plane = 3 * (size_t)total * sizeof(unsigned long long);
+    b.resize(at + (with_a ? 2u : 1u) * plane);
+    HIP_TRY(hipMemcpy(b.data() + at, h.sums.p, plane, hipMemcpyDeviceToHost));
+    if (with_a) HIP_TRY(hipMemcpy(b.data() + at + plane, h.a.p, plane, hipMemcpyDeviceToHost));
+    host::ckpt_seal(b);
+    return write_renamed(b, path);
+}
+
+// pt_ctx_accum_load's and pt_ctx_adaptive_load's steps up to "the file is decoded into ck and b, it belongs to this context's
+// scene, and the device is current": nothing the context holds is touched
+template <class Ckpt, class Decode>
+int load_checkpoint(pt_ctx *c, const char *path, Decode decode, Ckpt &ck, std::vector<uint8_t> &b) {
+    if (!c || !path) return refuse("NULL argument");
+    if (!c->has_scene) return refuse("no scene set: a checkpoint is loaded under the scene it was rendered from");
+    const int rc = read_checkpoint(path, decode, ck, b);
+    if (rc) return rc;
+    if (ck.scene_fp != scene_fp_of(c)) {
+        set_error(std::string(path) + " was rendered from another scene than the one set on this context");
+        return PT_ERR_INVALID;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    return PT_OK;
+}
+
 // An image pass once its arguments are checked (host::check_*: everything that can be refused is refused there, before the device is
 // touched): the context's device is made current, the pass runs on the caller's stream or the context's - launch(st) grows what
 // scratch it needs and issues the kernels; its error is the call's - and the call waits for it.
@@ -2134,26 +2155,14 @@ int pt_ctx_accum_save(pt_ctx *c, const char *path) {
     ck.scene_fp = scene_fp_of(c);
     std::vector<uint8_t> b;
     host::ckpt_encode_head(ck, b);
-    const size_t at = b.size(), plane = 3 * (size_t)h.total * sizeof(unsigned long long);
-    b.resize(at + (h.tracked() ? 2u : 1u) * plane);
-    HIP_TRY(hipMemcpy(b.data() + at, h.sums.p, plane, hipMemcpyDeviceToHost));
-    if (h.tracked()) HIP_TRY(hipMemcpy(b.data() + at + plane, h.a.p, plane, hipMemcpyDeviceToHost));
-    host::ckpt_seal(b);
-    return write_renamed(b, path);
+    return save_checkpoint(b, h, h.total, h.tracked(), path);
 }
 
 int pt_ctx_accum_load(pt_ctx *c, const char *path) {
-    if (!c || !path) return refuse("NULL argument");
-    if (!c->has_scene) return refuse("no scene set: a checkpoint is loaded under the scene it was rendered from");
     host::Checkpoint ck;
     std::vector<uint8_t> b;
-    const int rc = read_checkpoint(path, host::ckpt_decode, ck, b);
+    const int rc = load_checkpoint(c, path, host::ckpt_decode, ck, b);
     if (rc) return rc;
-    if (ck.scene_fp != scene_fp_of(c)) {
-        set_error(std::string(path) + " was rendered from another scene than the one set on this context");
-        return PT_ERR_INVALID;
-    }
-    HIP_TRY(hipSetDevice(c->device));
     // a file of a noise-tracked frame brings half A; a plain one loaded into a tracking context starts it empty (all held
     // samples then count as half B)
     const uint8_t *half_a = ck.tracked() ? b.data() + ck.a_at : nullptr;
@@ -2369,26 +2378,14 @@ int pt_ctx_adaptive_save(pt_ctx *c, const char *path) {
     if (rc) return rc;
     std::vector<uint8_t> b;
     host::adckpt_encode_head(ck, b);
-    const size_t at = b.size(), plane = 3 * (size_t)h.total * sizeof(unsigned long long);
-    b.resize(at + 2u * plane);
-    HIP_TRY(hipMemcpy(b.data() + at, h.sums.p, plane, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(b.data() + at + plane, h.a.p, plane, hipMemcpyDeviceToHost));
-    host::ckpt_seal(b);
-    return write_renamed(b, path);
+    return save_checkpoint(b, h, h.total, true, path);
 }
 
 int pt_ctx_adaptive_load(pt_ctx *c, const char *path) {
-    if (!c || !path) return refuse("NULL argument");
-    if (!c->has_scene) return refuse("no scene set: a checkpoint is loaded under the scene it was rendered from");
     host::AdaptiveCheckpoint ck;
     std::vector<uint8_t> b;
-    int rc = read_checkpoint(path, host::adckpt_decode, ck, b);
+    int rc = load_checkpoint(c, path, host::adckpt_decode, ck, b);
     if (rc) return rc;
-    if (ck.scene_fp != scene_fp_of(c)) {
-        set_error(std::string(path) + " was rendered from another scene than the one set on this context");
-        return PT_ERR_INVALID;
-    }
-    HIP_TRY(hipSetDevice(c->device));
     host::TileGeometry geo;
     uint32_t tile_shift = 0;
     while ((1u << tile_shift) < ck.key.tile) ++tile_shift;

@@ -1306,16 +1306,73 @@ T get(const uint8_t *&r) {
     r += sizeof v;
     return v;
 }
+
+// The wire form both formats share.  The head: magic, u32 version, the key (7 x u32, u64 seed).
+void put_head(std::vector<uint8_t> &b, const char (&magic)[8], uint32_t version, const AccumKey &k) {
+    b.insert(b.end(), magic, magic + 8);
+    put<uint32_t>(b, version);
+    for (uint32_t v : {k.width, k.height, k.idx_begin, k.idx_end, k.chunk_pixels, k.chunk_first, k.chunk_step}) put<uint32_t>(b, v);
+    put<uint64_t>(b, k.seed);
+}
+AccumKey get_key(const uint8_t *&r) {
+    AccumKey k;
+    for (uint32_t *v : {&k.width, &k.height, &k.idx_begin, &k.idx_end, &k.chunk_pixels, &k.chunk_first, &k.chunk_step}) *v = get<uint32_t>(r);
+    k.seed = get<uint64_t>(r);
+    return k;
+}
+// the pt_config a key stands for (one sample), and whether the key is one check_cfg accepts and accum_key writes: [ib, ie) its band
+bool key_frame(const AccumKey &k, pt_config &kc, uint32_t &ib, uint32_t &ie) {
+    kc = pt_config{};
+    kc.width = k.width;
+    kc.height = k.height;
+    kc.spp = 1;
+    kc.idx_begin = k.idx_begin;
+    kc.idx_end = k.idx_end;
+    kc.chunk_pixels = k.chunk_pixels;
+    kc.chunk_first = k.chunk_first;
+    kc.chunk_step = k.chunk_step;
+    kc.seed = k.seed;
+    return check_cfg(&kc, &ib, &ie) == PT_OK && accum_key(&kc, ib, ie) == k;
+}
+
+// The frame of a sealed file, whose order of refusals is part of the contract: too short, the first `head` bytes asked for, magic,
+// version (1 .. versions), the format's header - header(version, r, want_size) reads its fields from r, behind the version, and
+// says what is wrong with them or how long they imply the file to be -, truncated / trailing bytes, the whole file asked for, the
+// trailing hash, the format's body - body(): what lies behind the header, or what is wrong with it.  Nothing behind the header
+// is looked at before the file's size is the one the header implies.
+template <class Header, class Body>
+int sealed_decode(uint64_t file_size, const uint8_t *b, size_t n, const char (&magic)[8], uint32_t versions, size_t head, SealedFile &out,
+                  std::string &why, Header header, Body body) {
+    auto bad = [&](const char *w) {
+        why = w;
+        return kCkptBad;
+    };
+    auto more = [&](size_t need) {
+        out.need = need;
+        return kCkptMore;
+    };
+    if (file_size < head + 8) return bad("too short");
+    if (n < head) return more(head);
+    if (memcmp(b, magic, 8) != 0) return bad("wrong magic");
+    const uint8_t *r = b + 8;
+    const uint32_t version = get<uint32_t>(r);
+    if (version < 1u || version > versions) return bad("unknown format version");
+    uint64_t want_size = 0;
+    if (const char *w = header(version, r, want_size)) return bad(w);
+    if (file_size != want_size) return bad(file_size < want_size ? "truncated" : "trailing bytes");
+    if (n < want_size) return more((size_t)want_size);
+    uint64_t tag;
+    memcpy(&tag, b + want_size - 8, 8);
+    if (tag != pt_siphash(1, 3, 0, 0, b, (size_t)want_size - 8)) return bad("bad trailing hash");
+    if (const char *w = body()) return bad(w);
+    return kCkptOk;
+}
 }  // namespace
 
 void ckpt_encode_head(const Checkpoint &ck, std::vector<uint8_t> &b) {
     const size_t halves = ck.tracked() ? 2u : 1u;
     b.reserve(b.size() + kCkptHead + halves * (4 * ck.cnt.size() + 24 * (size_t)ck.total) + 8);
-    b.insert(b.end(), kCkptMagic, kCkptMagic + 8);
-    put<uint32_t>(b, ck.tracked() ? kCkptVersionTracked : kCkptVersion);
-    const AccumKey &k = ck.key;
-    for (uint32_t v : {k.width, k.height, k.idx_begin, k.idx_end, k.chunk_pixels, k.chunk_first, k.chunk_step}) put<uint32_t>(b, v);
-    put<uint64_t>(b, k.seed);
+    put_head(b, kCkptMagic, ck.tracked() ? kCkptVersionTracked : kCkptVersion, ck.key);
     put<uint64_t>(b, ck.scene_fp);
     put<uint32_t>(b, ck.total);
     put<uint32_t>(b, ck.part_px);
@@ -1327,69 +1384,40 @@ void ckpt_encode_head(const Checkpoint &ck, std::vector<uint8_t> &b) {
 void ckpt_seal(std::vector<uint8_t> &b) { put<uint64_t>(b, pt_siphash(1, 3, 0, 0, b.data(), b.size())); }
 
 int ckpt_decode(uint64_t file_size, const uint8_t *b, size_t n, Checkpoint &out, std::string &why) {
-    auto bad = [&](const char *w) {
-        why = w;
-        return kCkptBad;
+    uint32_t n_parts = 0;
+    size_t halves = 1;
+    auto header = [&](uint32_t version, const uint8_t *r, uint64_t &want_size) -> const char * {
+        halves = version == kCkptVersionTracked ? 2u : 1u;
+        out.key = get_key(r);
+        out.scene_fp = get<uint64_t>(r);
+        const uint32_t total = out.total = get<uint32_t>(r), part_px = out.part_px = get<uint32_t>(r);
+        n_parts = get<uint32_t>(r);
+        // the key must be a valid frame's, and the sizes must be the ones it implies
+        pt_config kc;
+        uint32_t ib = 0, ie = 0;
+        if (!key_frame(out.key, kc, ib, ie)) return "the frame key is not a valid frame";
+        const uint32_t want_total = owned_pixels(&kc, ib, ie);
+        if (total != want_total || want_total == 0u || part_px != part_pixels(total, true) || n_parts != part_count(total, part_px))
+            return "sizes that do not fit each other";
+        out.sums_at = kCkptHead + halves * 4 * (size_t)n_parts;
+        out.a_at = out.sums_at + 24 * (size_t)total;
+        want_size = kCkptHead + halves * (4ull * n_parts + 24ull * total) + 8ull;
+        return nullptr;
     };
-    auto more = [&](size_t need) {
-        out.need = need;
-        return kCkptMore;
+    auto body = [&]() -> const char * {
+        out.cnt.resize(n_parts);
+        memcpy(out.cnt.data(), b + kCkptHead, 4 * (size_t)n_parts);
+        for (uint32_t v : out.cnt)
+            if (v > (1u << 24)) return "a sample count above 2^24";
+        out.na.assign(halves == 2u ? n_parts : 0u, 0u);
+        if (halves == 2u) {
+            memcpy(out.na.data(), b + kCkptHead + 4 * (size_t)n_parts, 4 * (size_t)n_parts);
+            for (uint32_t i = 0; i < n_parts; ++i)
+                if (out.na[i] > out.cnt[i]) return "half A holds more samples than the part";
+        }
+        return nullptr;
     };
-    if (file_size < kCkptHead + 8) return bad("too short");
-    if (n < kCkptHead) return more(kCkptHead);
-    const uint8_t *r = b;
-    if (memcmp(r, kCkptMagic, 8) != 0) return bad("wrong magic");
-    r += 8;
-    const uint32_t version = get<uint32_t>(r);
-    if (version != kCkptVersion && version != kCkptVersionTracked) return bad("unknown format version");
-    const uint64_t halves = version == kCkptVersionTracked ? 2u : 1u;
-    AccumKey &k = out.key;
-    k.width = get<uint32_t>(r);
-    k.height = get<uint32_t>(r);
-    k.idx_begin = get<uint32_t>(r);
-    k.idx_end = get<uint32_t>(r);
-    k.chunk_pixels = get<uint32_t>(r);
-    k.chunk_first = get<uint32_t>(r);
-    k.chunk_step = get<uint32_t>(r);
-    k.seed = get<uint64_t>(r);
-    out.scene_fp = get<uint64_t>(r);
-    const uint32_t total = out.total = get<uint32_t>(r), part_px = out.part_px = get<uint32_t>(r), n_parts = get<uint32_t>(r);
-    // the key must be one check_cfg accepts and accum_key writes, and the sizes must be the ones it implies
-    pt_config kc{};
-    kc.width = k.width;
-    kc.height = k.height;
-    kc.spp = 1;
-    kc.idx_begin = k.idx_begin;
-    kc.idx_end = k.idx_end;
-    kc.chunk_pixels = k.chunk_pixels;
-    kc.chunk_first = k.chunk_first;
-    kc.chunk_step = k.chunk_step;
-    kc.seed = k.seed;
-    uint32_t ib = 0, ie = 0;
-    if (check_cfg(&kc, &ib, &ie) != PT_OK || !(accum_key(&kc, ib, ie) == k)) return bad("the frame key is not a valid frame");
-    const uint32_t want_total = owned_pixels(&kc, ib, ie);
-    if (total != want_total || want_total == 0u || part_px != part_pixels(total, true) || n_parts != part_count(total, part_px))
-        return bad("sizes that do not fit each other");
-    // (nothing behind the header is looked at before the file's size is the one the header implies)
-    const uint64_t want_size = kCkptHead + halves * (4ull * n_parts + 24ull * total) + 8ull;
-    if (file_size != want_size) return bad(file_size < want_size ? "truncated" : "trailing bytes");
-    if (n < want_size) return more((size_t)want_size);
-    uint64_t tag;
-    memcpy(&tag, b + want_size - 8, 8);
-    if (tag != pt_siphash(1, 3, 0, 0, b, (size_t)want_size - 8)) return bad("bad trailing hash");
-    out.cnt.resize(n_parts);
-    memcpy(out.cnt.data(), b + kCkptHead, 4 * (size_t)n_parts);
-    for (uint32_t v : out.cnt)
-        if (v > (1u << 24)) return bad("a sample count above 2^24");
-    out.na.assign(halves == 2u ? n_parts : 0u, 0u);
-    if (halves == 2u) {
-        memcpy(out.na.data(), b + kCkptHead + 4 * (size_t)n_parts, 4 * (size_t)n_parts);
-        for (uint32_t i = 0; i < n_parts; ++i)
-            if (out.na[i] > out.cnt[i]) return bad("half A holds more samples than the part");
-    }
-    out.sums_at = kCkptHead + halves * 4 * (size_t)n_parts;
-    out.a_at = out.sums_at + 24 * (size_t)total;
-    return kCkptOk;
+    return sealed_decode(file_size, b, n, kCkptMagic, kCkptVersionTracked, kCkptHead, out, why, header, body);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1535,11 +1563,7 @@ constexpr size_t kAdCkptHead = 8 + 4 + 7 * 4 + 8 + 2 * 4 + 8 + 2 * 4;  // 72 byt
 
 void adckpt_encode_head(const AdaptiveCheckpoint &ck, std::vector<uint8_t> &b) {
     b.reserve(b.size() + kAdCkptHead + 16 * (size_t)ck.tiles + 48 * (size_t)ck.total + 8);
-    b.insert(b.end(), kAdCkptMagic, kAdCkptMagic + 8);
-    put<uint32_t>(b, kAdCkptVersion);
-    const AccumKey &k = ck.key.frame;
-    for (uint32_t v : {k.width, k.height, k.idx_begin, k.idx_end, k.chunk_pixels, k.chunk_first, k.chunk_step}) put<uint32_t>(b, v);
-    put<uint64_t>(b, k.seed);
+    put_head(b, kAdCkptMagic, kAdCkptVersion, ck.key.frame);
     put<uint32_t>(b, ck.key.tile);
     put<uint32_t>(b, ck.key.n0);
     put<uint64_t>(b, ck.scene_fp);
@@ -1553,76 +1577,44 @@ void adckpt_encode_head(const AdaptiveCheckpoint &ck, std::vector<uint8_t> &b) {
 }
 
 int adckpt_decode(uint64_t file_size, const uint8_t *b, size_t n, AdaptiveCheckpoint &out, std::string &why) {
-    auto bad = [&](const char *w) {
-        why = w;
-        return kCkptBad;
+    auto header = [&](uint32_t, const uint8_t *r, uint64_t &want_size) -> const char * {
+        const AccumKey &k = out.key.frame = get_key(r);
+        const uint32_t tile = out.key.tile = get<uint32_t>(r), n0 = out.key.n0 = get<uint32_t>(r);
+        out.scene_fp = get<uint64_t>(r);
+        const uint32_t total = out.total = get<uint32_t>(r), tiles = out.tiles = get<uint32_t>(r);
+        // the key must be one the call accepts and writes, and the sizes must be the ones it implies
+        pt_config kc;
+        pt_adaptive_params kp{};
+        kp.tile = tile;
+        uint32_t ib = 0, ie = 0, tile_shift = 0;
+        if (!key_frame(k, kc, ib, ie) || check_adaptive_cfg(kc) != PT_OK) return "the frame key is not a valid frame";
+        if (tile == 0u || check_adaptive_params(kp, &tile_shift) != PT_OK || n0 == 0u || n0 % 8u != 0u || n0 > 0xfffffff8u)
+            return "the tile edge or n_0 is not one the call writes";
+        TileGeometry g{};
+        if (total != ie - ib || tile_geometry(k.width, total / k.width, tile_shift, g) != PT_OK || tiles != g.tiles || tiles == 0u)
+            return "sizes that do not fit each other";
+        out.sums_at = kAdCkptHead + 16 * (size_t)tiles;
+        out.a_at = out.sums_at + 24 * (size_t)total;
+        want_size = kAdCkptHead + 16ull * tiles + 48ull * total + 8ull;
+        return nullptr;
     };
-    auto more = [&](size_t need) {
-        out.need = need;
-        return kCkptMore;
+    auto body = [&]() -> const char * {
+        TileTable &t = out.table;
+        t.cnt.resize(out.tiles);
+        t.na.resize(out.tiles);
+        t.err.resize(out.tiles);
+        const uint8_t *r = b + kAdCkptHead;
+        for (uint32_t i = 0; i < out.tiles; ++i) {
+            t.cnt[i] = get<uint32_t>(r);
+            t.na[i] = get<uint32_t>(r);
+            t.err[i] = get<uint64_t>(r);
+            if (t.cnt[i] > (1u << 24)) return "a sample count above 2^24";
+            if (t.na[i] > t.cnt[i]) return "half A holds more samples than the tile";
+            if (t.err[i] != kTileNoError && (t.na[i] == 0u || t.na[i] == t.cnt[i])) return "an E of a tile with an empty half";
+        }
+        return nullptr;
     };
-    if (file_size < kAdCkptHead + 8) return bad("too short");
-    if (n < kAdCkptHead) return more(kAdCkptHead);
-    const uint8_t *r = b;
-    if (memcmp(r, kAdCkptMagic, 8) != 0) return bad("wrong magic");
-    r += 8;
-    if (get<uint32_t>(r) != kAdCkptVersion) return bad("unknown format version");
-    AccumKey &k = out.key.frame;
-    k.width = get<uint32_t>(r);
-    k.height = get<uint32_t>(r);
-    k.idx_begin = get<uint32_t>(r);
-    k.idx_end = get<uint32_t>(r);
-    k.chunk_pixels = get<uint32_t>(r);
-    k.chunk_first = get<uint32_t>(r);
-    k.chunk_step = get<uint32_t>(r);
-    k.seed = get<uint64_t>(r);
-    const uint32_t tile = out.key.tile = get<uint32_t>(r), n0 = out.key.n0 = get<uint32_t>(r);
-    out.scene_fp = get<uint64_t>(r);
-    const uint32_t total = out.total = get<uint32_t>(r), tiles = out.tiles = get<uint32_t>(r);
-    // the key must be one the call accepts and writes, and the sizes must be the ones it implies
-    pt_config kc{};
-    kc.width = k.width;
-    kc.height = k.height;
-    kc.spp = 1;
-    kc.idx_begin = k.idx_begin;
-    kc.idx_end = k.idx_end;
-    kc.chunk_pixels = k.chunk_pixels;
-    kc.chunk_first = k.chunk_first;
-    kc.chunk_step = k.chunk_step;
-    kc.seed = k.seed;
-    pt_adaptive_params kp{};
-    kp.tile = tile;
-    uint32_t ib = 0, ie = 0, tile_shift = 0;
-    if (check_cfg(&kc, &ib, &ie) != PT_OK || !(accum_key(&kc, ib, ie) == k) || check_adaptive_cfg(kc) != PT_OK)
-        return bad("the frame key is not a valid frame");
-    if (tile == 0u || check_adaptive_params(kp, &tile_shift) != PT_OK || n0 == 0u || n0 % 8u != 0u || n0 > 0xfffffff8u)
-        return bad("the tile edge or n_0 is not one the call writes");
-    TileGeometry g{};
-    if (total != ie - ib || tile_geometry(k.width, total / k.width, tile_shift, g) != PT_OK || tiles != g.tiles || tiles == 0u)
-        return bad("sizes that do not fit each other");
-    // (nothing behind the header is looked at before the file's size is the one the header implies)
-    const uint64_t want_size = kAdCkptHead + 16ull * tiles + 48ull * total + 8ull;
-    if (file_size != want_size) return bad(file_size < want_size ? "truncated" : "trailing bytes");
-    if (n < want_size) return more((size_t)want_size);
-    uint64_t tag;
-    memcpy(&tag, b + want_size - 8, 8);
-    if (tag != pt_siphash(1, 3, 0, 0, b, (size_t)want_size - 8)) return bad("bad trailing hash");
-    TileTable &t = out.table;
-    t.cnt.resize(tiles);
-    t.na.resize(tiles);
-    t.err.resize(tiles);
-    r = b + kAdCkptHead;
-    for (uint32_t i = 0; i < tiles; ++i) {
-        t.cnt[i] = get<uint32_t>(r);
-        t.na[i] = get<uint32_t>(r);
-        t.err[i] = get<uint64_t>(r);
-        if (t.cnt[i] > (1u << 24)) return bad("a sample count above 2^24");
-        if (t.na[i] > t.cnt[i]) return bad("half A holds more samples than the tile");
-        if (t.err[i] != kTileNoError && (t.na[i] == 0u || t.na[i] == t.cnt[i])) return bad("an E of a tile with an empty half");
-    }
-    out.sums_at = kAdCkptHead + 16 * (size_t)tiles;
-    out.a_at = out.sums_at + 24 * (size_t)total;
-    return kCkptOk;
+    return sealed_decode(file_size, b, n, kAdCkptMagic, kAdCkptVersion, kAdCkptHead, out, why, header, body);
 }
 
 // ---- pt_ctx_denoise, pt_ctx_denoise_var (ptrace.h, pt_denoise.h)

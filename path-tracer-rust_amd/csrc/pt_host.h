@@ -358,12 +358,14 @@ inline bool deal_to_a(uint32_t cnt, uint32_t na) { return na <= cnt - na; }
 
 // ---- checkpoint file (pt_ctx_accum_save / _load, ptrace.h): little-endian, the byte order of every target of this library.
 // What a file says besides its planes: the frame (tracked: version 2, which brings half A; plain: version 1), the fingerprint
-// of its scene, and where its planes of 24 * total bytes lie - the held sums at sums_at, half A's at a_at.
-struct Checkpoint : FrameCounts {
+// of its scene, and where its planes of 24 * total bytes lie - the held sums at sums_at, half A's at a_at.  SealedFile: what
+// this format and the held adaptive frame's (below) say alike.
+struct SealedFile {
     uint64_t scene_fp = 0;
     size_t sums_at = 0, a_at = 0;
-    size_t need = 0;  // kCkptMore: the leading bytes of the file ckpt_decode asks for
+    size_t need = 0;  // kCkptMore: the leading bytes of the file the decoder asks for
 };
+struct Checkpoint : FrameCounts, SealedFile {};
 // the file up to its planes (header, counts, half A's counts) appended to b; the planes follow (the held sums, then half A's),
 // then ckpt_seal's hash of everything before it
 void ckpt_encode_head(const Checkpoint &ck, std::vector<uint8_t> &b);
@@ -489,11 +491,8 @@ class AdaptiveSchedule {
 };
 
 // ---- checkpoint of the held adaptive frame (pt_ctx_adaptive_save / _load, ptrace.h): as the held accumulate frame's
-struct AdaptiveCheckpoint : AdaptiveFrame {
+struct AdaptiveCheckpoint : AdaptiveFrame, SealedFile {
     TileTable table;
-    uint64_t scene_fp = 0;
-    size_t sums_at = 0, a_at = 0;  // the planes of 24 * total bytes each
-    size_t need = 0;               // kCkptMore: the leading bytes adckpt_decode asks for
 };
 // the file up to its planes appended to b; the planes follow (the held sums, then half A's), then ckpt_seal's hash
 void adckpt_encode_head(const AdaptiveCheckpoint &ck, std::vector<uint8_t> &b);

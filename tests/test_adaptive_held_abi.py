@@ -10,6 +10,7 @@ import subprocess
 
 import adaptive_ref
 import ptlib
+from test_host_logic import _host_tool, ckpt_check_tool
 from ptlib import PtAdaptiveInfo, PtAdaptiveParams, PtAdaptiveStats, PtConfig, PtStats
 
 ROOT = ptlib.ROOT
@@ -107,15 +108,6 @@ def test_refusals_come_in_the_stated_order_without_a_device():
 
 
 # ---- which class is next ---------------------------------------------------------------------------------------------
-
-def _host_tool(tmp_path, name, source):
-    src = tmp_path / (name + ".cpp")
-    src.write_text(source)
-    exe = str(tmp_path / name)
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-I", os.path.join(ptlib.PKG, "csrc"), "-I", os.path.join(ROOT, "include"),
-                           str(src), "-o", exe, "-L", ptlib.PKG, "-lptrace_hip", "-Wl,-rpath," + ptlib.PKG])
-    return lambda *args: subprocess.check_output([exe] + [str(a) for a in args]).decode()
-
 
 SCHED_SRC = r"""
 #include <cstdio>
@@ -232,73 +224,6 @@ def test_class_scheduler(tmp_path):
 
 # ---- the checkpoint codec --------------------------------------------------------------------------------------------
 
-ADCKPT_SRC = r"""
-#include <cstdio>
-#include <cstdlib>
-#include <map>
-#include <string>
-#include <vector>
-#include "ptrace.h"
-#include "pt_host.h"
-using namespace pt;
-// the loader's reads (pt_api.hip: read_checkpoint): what the decoder asks for, until it says OK or BAD
-static int load(const std::vector<uint8_t> &file, host::AdaptiveCheckpoint &ck, std::string &why) {
-    size_t n = 0;
-    for (int guard = 0; guard < 8; ++guard) {
-        const int d = host::adckpt_decode(file.size(), file.data(), n, ck, why);
-        if (d != host::kCkptMore) return d;
-        if (ck.need <= n || ck.need > file.size()) { why = "asked for bytes the file does not have"; return -1; }
-        n = ck.need;
-    }
-    why = "never finished";
-    return -1;
-}
-// argv: FILE [sweep]: decode the file and print its fields, then whether encoding them again gives the file's bytes; with
-// `sweep`, every truncation and every single-byte flip of it instead, counted by the decoder's answer
-int main(int argc, char **argv) {
-    FILE *f = fopen(argv[1], "rb");
-    if (!f) return 2;
-    std::vector<uint8_t> b;
-    uint8_t buf[1 << 16];
-    for (size_t n; (n = fread(buf, 1, sizeof buf, f)) != 0;) b.insert(b.end(), buf, buf + n);
-    fclose(f);
-    std::string why;
-    if (argc > 2) {
-        std::map<std::string, int> cut, flip;
-        for (size_t n = 0; n < b.size(); ++n) {
-            host::AdaptiveCheckpoint ck;
-            std::vector<uint8_t> c(b.begin(), b.begin() + n);
-            cut[load(c, ck, why) == host::kCkptBad ? why : std::string("NOT REFUSED")]++;
-        }
-        for (size_t i = 0; i < b.size(); ++i)
-            for (int bit : {0, 7}) {
-                host::AdaptiveCheckpoint ck;
-                std::vector<uint8_t> c = b;
-                c[i] ^= (uint8_t)(1u << bit);
-                flip[load(c, ck, why) == host::kCkptBad ? why : std::string("NOT REFUSED")]++;
-            }
-        for (auto &kv : cut) printf("cut|%s|%d\n", kv.first.c_str(), kv.second);
-        for (auto &kv : flip) printf("flip|%s|%d\n", kv.first.c_str(), kv.second);
-        return 0;
-    }
-    host::AdaptiveCheckpoint ck;
-    const int d = load(b, ck, why);
-    if (d != host::kCkptOk) { printf("BAD %s\n", why.c_str()); return 0; }
-    const host::AccumKey &k = ck.key.frame;
-    printf("OK key %u %u %u %u %u %u %u %llu tile %u n0 %u fp %llu total %u tiles %u sums_at %zu a_at %zu table", k.width, k.height,
-           k.idx_begin, k.idx_end, k.chunk_pixels, k.chunk_first, k.chunk_step, (unsigned long long)k.seed, ck.key.tile, ck.key.n0,
-           (unsigned long long)ck.scene_fp, ck.total, ck.tiles, ck.sums_at, ck.a_at);
-    for (uint32_t i = 0; i < ck.tiles; ++i) printf(" %u:%u:%llu", ck.table.cnt[i], ck.table.na[i], ck.table.err[i]);
-    std::vector<uint8_t> again;
-    host::adckpt_encode_head(ck, again);
-    again.insert(again.end(), b.begin() + ck.sums_at, b.begin() + ck.sums_at + 48 * (size_t)ck.total);
-    host::ckpt_seal(again);
-    printf(" %s\n", again == b ? "SAME" : "DIFF");
-    return 0;
-}
-"""
-
-
 def adaptive_checkpoint(L, key, tile, n0, fp, total, table, sums, a, version=1, magic=b"PTADAPT1"):
     """a checkpoint file from the layout include/ptrace.h documents; key as PTACCUM1's; table: (count, nA, E) per tile"""
     b = magic + struct.pack("<I", version) + struct.pack("<7IQ", *key) + struct.pack("<2I", tile, n0) + struct.pack("<Q", fp)
@@ -321,12 +246,12 @@ def parse_adaptive_checkpoint(data):
 def test_checkpoint_codec(tmp_path):
     import numpy as np
     L = ptlib.product()
-    tool = _host_tool(tmp_path, "adckpt", ADCKPT_SRC)
+    tool = ckpt_check_tool(tmp_path)
 
     def run(data, *args):
         p = tmp_path / "c.ptad"
         p.write_bytes(data)
-        return tool(p, *args).strip()
+        return tool("adaptive", p, *args).strip()
 
     planes = lambda total, salt: (np.arange(3 * total, dtype="<u8") * np.uint64(0x9e3779b97f4a7c15) + np.uint64(salt)).tobytes()
     # a band of four rows of a 10 x 8 frame in tiles of 4: 3 tiles, the last one 2 wide

@@ -268,6 +268,35 @@ def test_checkpoint_round_trip_and_damaged_files(L, cornell, mesh, tmp_path):
         assert d.info(cfg_of(12)) == (0, 0)
 
 
+def test_saved_files_are_the_documented_layout(L, cornell, tmp_path):
+    """What pt_ctx_accum_save writes is the layout include/ptrace.h documents, byte for byte: the file's parsed fields and its own
+    planes, put together again by the builder of the codec test, are the file; its counts are what pt_ctx_accum_info reports; and
+    a fresh context that loads it saves the same bytes.  A plain frame at 3 samples, a noise-tracked one at 8."""
+    from noise_ref import parse_checkpoint
+    from test_host_logic import _checkpoint
+    w, h = 16, 8
+    for spp, track in ((3, False), (8, True)):
+        first, second = tmp_path / ("first%d.ptacc" % spp), tmp_path / ("second%d.ptacc" % spp)
+        with Dev(L, cornell, w * h) as d:
+            assert L.pt_ctx_accum_track_noise(d.ctx, int(track)) == 0
+            d.accumulate(cfg_of(spp, w=w, h=h))
+            held = d.info(cfg_of(spp, w=w, h=h))
+            assert L.pt_ctx_accum_save(d.ctx, str(first).encode()) == 0, L.pt_last_error()
+        data = first.read_bytes()
+        f = parse_checkpoint(data)
+        key = tuple(f[k] for k in ("width", "height", "idx_begin", "idx_end", "chunk_pixels", "chunk_first", "chunk_step", "seed"))
+        assert f["version"] == (2 if track else 1) and key == (w, h, 0, w * h, 0, 0, 0, SEED) and f["total"] == w * h
+        rebuilt = _checkpoint(L, key, f["fingerprint"], f["total"], f["part_px"], f["counts"].tolist(),
+                              f["n_a"].tolist() if track else None, f["sums"].tobytes(), f["a"].tobytes() if track else None)
+        assert rebuilt == data
+        assert (int(f["counts"].min()), int(f["counts"].max())) == held == (spp, spp)
+        assert not track or f["n_a"].tolist() == [4]  # samples [0, 4) of a tracked frame's first call go to half A
+        with Dev(L, cornell, w * h) as d:
+            assert L.pt_ctx_accum_load(d.ctx, str(first).encode()) == 0, L.pt_last_error()
+            assert L.pt_ctx_accum_save(d.ctx, str(second).encode()) == 0, L.pt_last_error()
+        assert second.read_bytes() == data
+
+
 def test_three_calls_against_the_oracle(dev, cornell):
     for t in (2, 5, 9):
         img, _ = dev.accumulate(cfg_of(t, MEGA if t == 5 else WAVE))

@@ -12,7 +12,7 @@ import adaptive_ref
 import gpudev
 import ptlib
 from ptlib import PtAdaptiveInfo, PtAdaptiveParams, PtAdaptiveStats, PtStats
-from test_adaptive_held_abi import parse_adaptive_checkpoint
+from test_adaptive_held_abi import NONE, adaptive_checkpoint, parse_adaptive_checkpoint
 from test_gpu_accumulate import NO_BVH
 from gpudev import L  # noqa: F401  (fixture)
 from test_gpu_adaptive import CAP, H, SEED, TILE, TILE_ERROR, W, ADev
@@ -300,6 +300,32 @@ def test_checkpoint(L, scenes, tmp_path):
     finally:
         d.close()
         e.close()
+
+
+def test_saved_files_are_the_documented_layout(L, scenes, tmp_path):
+    """What pt_ctx_adaptive_save writes is the layout include/ptrace.h documents, byte for byte: the file's parsed fields and its
+    own planes, put together again by the builder of the codec test, are the file; its counts are what pt_ctx_adaptive_info
+    reports; and a fresh context that loads it saves the same bytes.  16 x 8 in tiles of 4 at the smallest min_spp (1: n_0 = 8;
+    0 stands for 16) and the smallest cap (1 sample, below n_0: no tile has an E), and at a cap of n_0, where every tile has one."""
+    w, h, tile, min_spp = 16, 8, 4, 1
+    for cap in (1, 8):
+        first, second = tmp_path / ("first%d.ptad" % cap), tmp_path / ("second%d.ptad" % cap)
+        with HDev(L, scenes["cornell"], w * h) as d:
+            d.held(cfg_of(cap, w=w, h=h), TILE_ERROR, tile=tile, min_spp=min_spp)
+            info = d.ainfo(cfg_of(cap, w=w, h=h), TILE_ERROR, tile=tile, min_spp=min_spp)
+            assert L.pt_ctx_adaptive_save(d.ctx, str(first).encode()) == 0, L.pt_last_error()
+        data = first.read_bytes()
+        f = parse_adaptive_checkpoint(data)
+        assert (f["version"], f["key"], f["tile"], f["n0"], f["total"]) == (1, (w, h, 0, w * h, 0, 0, 0, SEED), tile, 8, w * h)
+        assert adaptive_checkpoint(L, f["key"], f["tile"], f["n0"], f["fp"], f["total"], f["table"], f["sums"], f["a"]) == data
+        counts = [t[0] for t in f["table"]]
+        assert (len(counts), min(counts), max(counts)) == (info.tiles, info.spp_min, info.spp_max) == (8, cap, cap)
+        assert sum(tile * tile * c for c in counts) == info.samples
+        assert all((t[2] == NONE) == (cap == 1) for t in f["table"])
+        with HDev(L, scenes["cornell"], w * h) as d:
+            assert L.pt_ctx_adaptive_load(d.ctx, str(first).encode()) == 0, L.pt_last_error()
+            assert L.pt_ctx_adaptive_save(d.ctx, str(second).encode()) == 0, L.pt_last_error()
+        assert second.read_bytes() == data
 
 
 def test_cli_adaptive_checkpoint(tmp_path):

@@ -519,46 +519,12 @@ def _host_tool(tmp_path, name, source):
     return lambda *args: subprocess.check_output([exe] + [str(a) for a in args]).decode()
 
 
-CKPT_SRC = r"""
-#include <cstdio>
-#include <cstdlib>
-#include <string>
-#include <vector>
-#include "ptrace.h"
-#include "pt_host.h"
-using namespace pt;
-// argv: FILE [N]: decode the file from its first N bytes (default: all of them).  Prints MORE <need> / BAD <reason> / OK and the
-// fields, then whether encoding the decoded fields, the planes at their offsets and the seal gives the file's bytes again.
-int main(int argc, char **argv) {
-    FILE *f = fopen(argv[1], "rb");
-    if (!f) return 2;
-    std::vector<uint8_t> b;
-    uint8_t buf[1 << 16];
-    for (size_t n; (n = fread(buf, 1, sizeof buf, f)) != 0;) b.insert(b.end(), buf, buf + n);
-    fclose(f);
-    const size_t n = argc > 2 ? strtoull(argv[2], 0, 10) : b.size();
-    host::Checkpoint ck;
-    std::string why;
-    const int d = host::ckpt_decode(b.size(), b.data(), n, ck, why);
-    if (d == host::kCkptMore) { printf("MORE %zu\n", ck.need); return 0; }
-    if (d == host::kCkptBad) { printf("BAD %s\n", why.c_str()); return 0; }
-    const host::AccumKey &k = ck.key;
-    printf("OK key %u %u %u %u %u %u %u %llu fp %llu total %u part_px %u tracked %d sums_at %zu a_at %zu cnt", k.width, k.height, k.idx_begin,
-           k.idx_end, k.chunk_pixels, k.chunk_first, k.chunk_step, (unsigned long long)k.seed, (unsigned long long)ck.scene_fp, ck.total,
-           ck.part_px, (int)ck.tracked(), ck.sums_at, ck.a_at);
-    for (uint32_t v : ck.cnt) printf(" %u", v);
-    printf(" na");
-    for (uint32_t v : ck.na) printf(" %u", v);
-    std::vector<uint8_t> again;
-    host::ckpt_encode_head(ck, again);
-    const size_t plane = 24 * (size_t)ck.total;
-    again.insert(again.end(), b.begin() + ck.sums_at, b.begin() + ck.sums_at + plane);
-    if (ck.tracked()) again.insert(again.end(), b.begin() + ck.a_at, b.begin() + ck.a_at + plane);
-    host::ckpt_seal(again);
-    printf(" %s\n", again == b ? "SAME" : "DIFF");
-    return 0;
-}
-"""
+def ckpt_check_tool(tmp_path):
+    """host/ckpt_check.cpp built by `make ckpt-check` (AddressSanitizer and UBSan; its own run must pass): ckpt_check ARGS' output"""
+    r = subprocess.run(["make", "-C", ptlib.PKG, "ckpt-check", "B=%s" % tmp_path], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and "ckpt_check: ok" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
+    exe = str(tmp_path / "ckpt_check")
+    return lambda *args: subprocess.check_output([exe] + [str(a) for a in args]).decode()
 
 
 def _checkpoint(L, key, fp, total, part_px, counts, n_a, sums, a, version=None, seal=True):
@@ -580,12 +546,12 @@ def test_checkpoint_codec(tmp_path):
     reason, in the loader's order."""
     import numpy as np
     L = ptlib.product()
-    tool = _host_tool(tmp_path, "ckpt", CKPT_SRC)
+    tool = ckpt_check_tool(tmp_path)
 
     def run(data, *n):
         p = tmp_path / "c.ptacc"
         p.write_bytes(data)
-        return tool(p, *n).strip()
+        return tool("accum", p, *n).strip()
 
     planes = lambda total, salt: (np.arange(3 * total, dtype="<u8") * np.uint64(0x9e3779b97f4a7c15) + np.uint64(salt)).tobytes()
     # version 1: a whole 8x4 frame, one part
@@ -607,6 +573,17 @@ def test_checkpoint_codec(tmp_path):
     # the loader's two reads: the header, then the whole file - and nothing behind the header when the size does not fit it
     assert run(v2, 0) == "MORE 68" and run(v2, 68) == "MORE %d" % len(v2) and run(v2, 67) == "MORE 68"
     assert run(v2[:-10], 68) == "BAD truncated" and run(v2 + b"\0" * 4, 68) == "BAD trailing bytes"
+    # every truncation and every flip of the lowest and highest bit of every byte is refused, each for a reason of the loader's
+    for good in (v1, v2):
+        got = {}
+        for line in run(good, "sweep").splitlines():
+            kind, why, n = line.split("|")
+            got.setdefault(kind, {})[why] = int(n)
+        assert sum(got["cut"].values()) == len(good) and set(got["cut"]) == {"too short", "truncated"}
+        assert sum(got["flip"].values()) == 2 * len(good) and "NOT REFUSED" not in got["flip"]
+        assert got["flip"]["bad trailing hash"] >= 2 * (len(good) - 68)  # whatever lies behind the header is the hash's business
+        assert set(got["flip"]) <= {"bad trailing hash", "wrong magic", "unknown format version", "the frame key is not a valid frame",
+                                    "sizes that do not fit each other", "truncated", "trailing bytes"}
 
     def resealed(data, at, fmt, value):
         import struct
