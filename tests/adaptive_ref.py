@@ -68,8 +68,10 @@ def replay(maps, width, rows, tile, tile_error, lv, stop_after=None):
             e = np.asarray(maps[j], dtype=f32)
             err[live] = e[live]
             fixed = np.floor(e.astype(np.float64) * float(1 << noise_ref.FRAC_BITS)).astype(np.uint64)
+            tile_sum = np.zeros(n_tiles, dtype=np.uint64)
+            np.add.at(tile_sum, tid, fixed)  # integers: one pass over the pixels whatever the number of tiles (34 320 at 1056 x 520)
             for t in np.nonzero(is_open)[0]:
-                E = int(fixed[tid == t].sum(dtype=np.uint64))
+                E = int(tile_sum[t])
                 last_e[t] = E
                 if E <= q * int(pixels[t]):
                     is_open[t] = False

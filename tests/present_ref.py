@@ -80,10 +80,61 @@ def mean(frame, w, h, ow, oh, exposure=0.0, flags=0):
     return out
 
 
-def present(table, frame, w, h, ow=0, oh=0, exposure=0.0, fmt=RGBA8, flags=0):
-    """the bytes pt_ctx_present writes: (oh, ow, 4 or 3) uint8"""
+# ------------------------------------------------------------------------------- the same arithmetic for full-size frames
+# mean() above is triple-nested Python over big integers: the independent form, and too slow beyond a few thousand pixels.  The
+# forms below are the same integers computed separably - rows, then columns - in uint64, and the same count of thresholds by a
+# binary search.  tests/test_present_abi.py holds them equal to the slow forms on every small shape.
+def overlaps(n, on):
+    """the pairs (X, x) of an output cell and a source pixel that overlap, in order, and the integer length of each overlap: cut the
+    axis of n * on units at every multiple of n (a cell's border) and of on (a pixel's border); each piece lies in one cell and one
+    pixel.  Three int64 / uint64 arrays."""
+    cuts = np.union1d(np.arange(on + 1, dtype=np.int64) * n, np.arange(n + 1, dtype=np.int64) * on)
+    lo = cuts[:-1]
+    return lo // n, lo // on, (cuts[1:] - lo).astype(np.uint64)
+
+
+def fold(a, n, on):
+    """axis 0 of the uint64 array a (n source pixels) folded into `on` cells: out[X] = sum over x of weight(X, x) * a[x]"""
+    assert a.dtype == np.uint64 and a.shape[0] == n
+    X, x, wgt = overlaps(n, on)
+    first = np.searchsorted(X, np.arange(on))  # every cell has a piece, and X does not decrease
+    return np.add.reduceat(a[x] * wgt.reshape((-1,) + (1,) * (a.ndim - 1)), first, axis=0)
+
+
+def sums_separable(frame, w, h, ow, oh, exposure=0.0, flags=0):
+    """step 4's S per output pixel and channel, (oh, ow, 3) uint64: rows first, then columns.  Every partial sum is at most the
+    final S, and S < 2^60 by the contract (asserted), so nothing wraps."""
+    c = clamp(display(frame, w, h, flags), exposure)
+    q = np.floor(c.astype(np.float64) * 4294967296.0).astype(np.uint64)  # (h, w, 3)
+    mid = fold(q, h, oh)                                  # (oh, w, 3)
+    S = fold(np.ascontiguousarray(mid.transpose(1, 0, 2)), w, ow).transpose(1, 0, 2)  # (oh, ow, 3)
+    assert int(S.max()) < 1 << 60
+    return np.ascontiguousarray(S)
+
+
+def mean_separable(frame, w, h, ow, oh, exposure=0.0, flags=0):
+    """mean() through sums_separable(): uint64 -> binary64 rounds to nearest even, one division, one rounding to binary32"""
+    if (ow, oh) == (w, h):
+        return clamp(display(frame, w, h, flags), exposure)
+    S = sums_separable(frame, w, h, ow, oh, exposure, flags)
+    return (S.astype(np.float64) / (np.float64(w * h) * np.float64(4294967296.0))).astype(F32)
+
+
+def byte_sorted(table, m):
+    """byte() by binary search: T[1..255] increases strictly, so the count of k with T[k] <= bits is where bits would be put in"""
+    t = np.asarray(table, dtype=np.uint32)[1:]
+    assert (np.diff(t.astype(np.int64)) > 0).all()
+    b = np.ascontiguousarray(m, dtype=F32).view(np.uint32)
+    return np.searchsorted(t, b, side="right").astype(np.uint8)
+
+
+def present(table, frame, w, h, ow=0, oh=0, exposure=0.0, fmt=RGBA8, flags=0, separable=False):
+    """the bytes pt_ctx_present writes: (oh, ow, 4 or 3) uint8.  separable: through the forms for full-size frames."""
     ow, oh = (ow, oh) if ow or oh else (w, h)
-    b = byte(table, mean(frame, w, h, ow, oh, exposure, flags))
+    if separable:
+        b = byte_sorted(table, mean_separable(frame, w, h, ow, oh, exposure, flags))
+    else:
+        b = byte(table, mean(frame, w, h, ow, oh, exposure, flags))
     if fmt == RGBA8:
         b = np.concatenate([b, np.full((oh, ow, 1), 255, dtype=np.uint8)], axis=2)
     return b

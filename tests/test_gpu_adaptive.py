@@ -163,6 +163,54 @@ def test_partial_tiles_on_both_edges(L, scenes):
         check_replay(res, u, w, h, t, te)
 
 
+def test_full_size_frame_takes_the_resolve_loop_round_twice(L, scenes):
+    """1056 x 520 in tiles of 4 at a cap of 32: 549 120 pixels > 2048 * 256 = 524 288 (stride_grid's cap times kTileBlock), so
+    k_tile_resolve's grid-stride loop takes a second turn and k_tile_select's runs over 34 320 tiles (135 workgroups);
+    k_tile_level takes 34 320 open tiles, 16 to a workgroup.  The levels are 16 and 32.  The same frame in tiles of 32 (33 x 17 of
+    them, the bottom row 8 high) is k_tile_level's four-trip form: 1024 pixels a tile, 256 a trip.  Everything is exact,
+    as on the small frames: check_pixels and check_replay through uniform().  The maps are optional: without them the image and the
+    statistics are the same.  Then the held form of the same frame, and pt_ctx_adaptive_resolve - the resolve kernel launched on
+    its own - gives the three outputs again."""
+    w, h, tile, cap, te = 1056, 520, 4, 32, 0.12
+    npix = w * h
+    assert npix == 549120 and npix > 2048 * 256 and -(-npix // 256) > 2048  # the resolve loop's second turn
+    tid, n_tiles = adaptive_ref.tile_ids(w, h, tile)
+    assert n_tiles == 34320 and n_tiles > 10000 and (1 << (2 * 5)) // 256 == 4  # tens of thousands of tiles; four trips at edge 32
+    u = uniform(L, scenes, "cornell", 0, w=w, h=h, cap=cap)
+    assert u["levels"] == [16, 32]
+    with ADev(L, scenes["cornell"], npix) as d:
+        cfg = cfg_of(cap, w=w, h=h)
+        r = d.adaptive(cfg, te, tile=tile)
+        bare = d.adaptive(cfg, te, tile=tile, maps=False)
+        r32 = d.adaptive(cfg, te, tile=32)
+        # the held form, and the resolve of what it holds into the same three buffers
+        par, st, ast = PtAdaptiveParams(te, tile, 0), PtStats(), PtAdaptiveStats()
+        rc = L.pt_ctx_accumulate_adaptive(d.ctx, C.byref(cfg), C.byref(par), d.d_out, d.d_spp, d.d_err, None, None, None, None,
+                                          C.byref(st), C.byref(ast))
+        assert rc == 0, (rc, L.pt_last_error())
+        held = dict(img=d.pixels(d.d_out, npix), spp=d.download(d.d_spp, npix, np.uint32), err=d.download(d.d_err, npix))
+        d.upload(d.d_out, np.full(npix * 3, -3.0, dtype=f32))
+        d.upload(d.d_spp, np.full(npix, 0xA5A5A5A5, dtype=np.uint32))
+        d.upload(d.d_err, np.full(npix, -3.0, dtype=f32))
+        assert L.pt_ctx_adaptive_resolve(d.ctx, C.byref(cfg), d.d_out, d.d_spp, d.d_err, None) == 0, L.pt_last_error()
+        resolved = dict(img=d.pixels(d.d_out, npix), spp=d.download(d.d_spp, npix, np.uint32), err=d.download(d.d_err, npix))
+    check_pixels(r, u)
+    want = check_replay(r, u, w, h, tile, te)
+    # on the replay built from the uniform frames: both levels run, some tiles close at the first and some go on
+    assert want["tiles"] == n_tiles and want["level_spp"] == [16, 32] and 0 < want["tiles_closed"][0] < n_tiles
+    assert np.array_equal(bare["img"].view(np.uint32), r["img"].view(np.uint32))
+    assert (bare["st"].samples, bare["st"].ray_bounces) == (r["st"].samples, r["st"].ray_bounces)
+    for name in ("samples", "mean_error", "tiles_open"):
+        assert getattr(bare["ast"], name) == getattr(r["ast"], name), name
+    check_pixels(r32, u)
+    check_replay(r32, u, w, h, 32, te)
+    assert r32["ast"].tiles == 33 * 17
+    for k in ("img", "spp", "err"):
+        assert np.array_equal(held[k].view(np.uint32), r[k].view(np.uint32)), ("held", k)
+        assert np.array_equal(resolved[k].view(np.uint32), r[k].view(np.uint32)), ("resolved", k)
+    assert (ast.samples, ast.mean_error, ast.tiles, ast.tiles_open) == (r["ast"].samples, r["ast"].mean_error, n_tiles, r["ast"].tiles_open)
+
+
 def test_a_band_of_whole_rows_and_the_band_refusals(L, scenes):
     band = (20 * W, 46 * W)  # 26 rows from row 20: tiles are counted from the band's first row (3 full tile rows and 2 rows)
     u = uniform(L, scenes, "mesh", 0, band=band, cap=64)

@@ -2,7 +2,9 @@
 integers and numpy binary32 / binary64.  Every comparison is of bytes, for equality.  The frames are the smallest that reach every
 path: the same-size stream (33 x 25: two workgroups would need 257 pixels - 825 gives four, with a tail), the two resampling
 passes on shrinking, enlarging, an axis that keeps its size, one output pixel, several lanes per output pixel (130 -> 64 does not
-group, 67 -> 1 does: 67 >= 8), and 257 x 129 -> 100 x 50, which spans several workgroups and a wave's tail."""
+group, 67 -> 1 does: 67 >= 8), and 257 x 129 -> 100 x 50, which spans several workgroups and a wave's tail.  The full-size cases
+behind them cross what the small ones cannot: every `group` of the column pass, every grid-stride loop's second turn, gridDim.y's
+cap, and sums of 2^53 and more; each asserts, from the launcher's rule restated here, that it takes the path it is there for."""
 import ctypes as C
 import os
 
@@ -138,6 +140,190 @@ def test_resampling_a_constant_frame_lands_on_the_thresholds(dev, table):
             assert c >= 2.0 ** -8
             dev.put(np.full((w * h, 3), c, dtype=F32))
             assert (dev.present(w, h, ow, oh, fmt=RGB8) == want).all(), (k, d)
+
+
+# ------------------------------------------------------------------------- full-size frames: every group, every grid wrap
+# The launch rules of csrc/pt_present.hip, restated, so that each case below can assert that it reaches the path it is there for:
+# a retune of the launcher then fails the premise instead of silently losing the coverage.
+BLOCK, MAX_GRID, MAX_GRID_Y = 256, 2048, 32768  # kPresentBlock, kPresentMaxGrid, kPresentMaxGridY
+
+
+def grid_for(n, per_block, cap=MAX_GRID):
+    blocks = -(-n // per_block)
+    if blocks <= 1:
+        return 1
+    turns = -(-blocks // cap)
+    return -(-blocks // turns)
+
+
+def turns_of(n, per_block):
+    """how often the grid-stride loop over n items runs in the busiest workgroup"""
+    return -(-n // (grid_for(n, per_block) * per_block))
+
+
+def group_of(w, ow):
+    """launch_present's lanes per output pixel: doubles while group * 8 * OW <= W, at most 64"""
+    g = 1
+    while g < 64 and g * 8 * ow <= w:
+        g *= 2
+    return g
+
+
+@pytest.fixture(scope="module")
+def bigdev(L):
+    # the largest source is 4096 x 1024 (test_sums_beyond_2_53), the largest output 2100 x 1000 (test_same_size_grid_turns)
+    with Dev(L, 4096 * 1024, 2100 * 1000) as d:
+        yield d
+
+
+# (W, H, OW, OH, group).  OW = 1: the widths 8..15, 16..31, ..., >= 256 give group 2, 4, ..., 64 in turn (g * 8 <= W); none is a
+# multiple of its group, so the lanes of a group hold spans of different lengths and the last ones may hold nothing.  OW = 3:
+# g * 24 <= W, 500 stops at 32 and 800 at 64.  Heights 1 to 3.
+GROUPS = ((5, 1, 1, 1, 1), (13, 2, 1, 1, 2), (21, 3, 1, 2, 4), (45, 1, 1, 1, 8), (100, 2, 1, 1, 16), (200, 3, 1, 2, 32),
+          (300, 1, 1, 1, 64), (500, 2, 3, 1, 32), (800, 3, 3, 2, 64))
+
+
+@pytest.mark.parametrize("w,h,ow,oh,group", GROUPS, ids=["%dx%d->%dx%d:g%d" % c for c in GROUPS])
+def test_every_group_of_the_column_pass(dev, table, w, h, ow, oh, group):
+    assert group_of(w, ow) == group and (group == 1 or w % group != 0)
+    frame = threshold_frame(table, np.random.default_rng(w * 1000 + ow), w * h)
+    dev.put(frame)
+    for flags in (0, FRAMEBUFFER_ORDER):
+        want = ref.present(table, frame, w, h, ow, oh, flags=flags)  # the slow, independent form
+        assert np.array_equal(want, ref.present(table, frame, w, h, ow, oh, flags=flags, separable=True))
+        got = dev.present(w, h, ow, oh, flags=flags)
+        assert np.array_equal(got, want), (flags, got.tolist(), want.tolist())
+        assert np.array_equal(dev.present(w, h, ow, oh, fmt=RGB8, flags=flags), want[:, :, :3]), flags
+
+
+def test_groups_cover_every_power_of_two():
+    assert sorted({c[4] for c in GROUPS}) == [1, 2, 4, 8, 16, 32, 64]
+
+
+# k_present_same's grid-stride loop takes a second turn above kPresentMaxGrid * kPresentBlock = 524 288 pixels:
+# 1056 x 520 = 549 120 > 524 288 (two turns), 2100 x 1000 = 2 100 000 > 4 * 524 288 (five).  With `flip` the source index is
+# npix - 1 - o, so both orders run.
+@pytest.mark.parametrize("w,h,turns", [(1056, 520, 2), (2100, 1000, 5)], ids=["1056x520", "2100x1000"])
+def test_same_size_grid_turns(L, bigdev, table, w, h, turns):
+    npix = w * h
+    assert npix > (turns - 1) * MAX_GRID * BLOCK and turns_of(npix, BLOCK) == turns
+    frame = threshold_frame(table, np.random.default_rng(w), npix)
+    bigdev.put(frame)
+    host = ref.quantize_host(L, frame)  # the host instantiation of the kernel's per-value steps, in framebuffer order
+    for flags in (0, FRAMEBUFFER_ORDER):
+        want = ref.present(table, frame, w, h, flags=flags, separable=True)
+        assert np.array_equal(want[:, :, :3].reshape(npix, 3), host if flags else host[::-1])
+        for fmt in (RGBA8, RGB8):
+            got = bigdev.present(w, h, fmt=fmt, flags=flags)
+            exp = want if fmt == RGBA8 else want[:, :, :3]
+            assert np.array_equal(got, exp), (flags, fmt, np.argwhere(got != exp)[:5])
+
+
+# The two resampling kernels' loops wrapping, each case named by the constant it crosses:
+# - "rows-y": OH = 40 000 > kPresentMaxGridY = 32 768, so gridDim.y is capped and both kernels' Y loops take a second turn;
+# - "rows-x": W = 600 000 > kPresentMaxGrid * kPresentBlock = 524 288, k_present_rows' x loop takes a second turn; the column pass
+#   runs at group 64 over spans of 600 columns;
+# - "cols-x": OW = 600 000 > kPresentMaxGrid * (kPresentBlock / group) = 524 288 at group 1, k_present_cols' X loop takes a second
+#   turn.
+WRAPS = {"rows-y": ((3, 50000), (2, 40000)), "rows-x": ((600000, 2), (1000, 1)), "cols-x": ((4, 2), (600000, 1))}
+
+
+@pytest.mark.parametrize("case", list(WRAPS))
+def test_resampling_grid_wraps(bigdev, table, case):
+    (w, h), (ow, oh) = WRAPS[case]
+    group = group_of(w, ow)
+    if case == "rows-y":
+        assert oh > MAX_GRID_Y
+    elif case == "rows-x":
+        assert w > MAX_GRID * BLOCK and turns_of(w, BLOCK) == 2 and group == 64
+    else:
+        assert group == 1 and ow > MAX_GRID * BLOCK and turns_of(ow, BLOCK // group) == 2
+    frame = threshold_frame(table, np.random.default_rng(w * 1000 + ow), w * h)
+    bigdev.put(frame)
+    for flags in (0, FRAMEBUFFER_ORDER):
+        want = ref.present(table, frame, w, h, ow, oh, flags=flags, separable=True)
+        got = bigdev.present(w, h, ow, oh, flags=flags)
+        assert np.array_equal(got, want), (flags, np.argwhere(got != want)[:5])
+        assert np.array_equal(bigdev.present(w, h, ow, oh, fmt=RGB8, flags=flags), want[:, :, :3]), flags
+
+
+def test_sums_beyond_2_53(bigdev, table):
+    """S >= 2^53, where present_mean's u64 -> binary64 conversion first rounds: it needs W*H*c > 2^21, here 4096 x 1024 = 2^22
+    pixels of channels in [0.5, 1).  The premise is asserted on the restatement's integers: every output channel has S >= 2^53.
+    These S are multiples of 2^8 - a value of [0.5, 1) has 24 bits, so its q = c * 2^32 ends in eight zeros - and binary64 holds
+    each exactly: that the conversion really ROUNDS is test_conversion_of_sums_rounds_to_nearest_even's premise, on a frame built
+    for it.  The same frame at constant 1.0 has S = W*H*2^32 exactly and the byte must be 255."""
+    w, h = 4096, 1024
+    npix = w * h
+    rng = np.random.default_rng(53)
+    frame = ref.bits_to_f32((0x3F000000 + rng.integers(0, 1 << 23, size=npix * 3)).astype(np.uint32)).reshape(npix, 3)
+    assert frame.min() >= 0.5 and frame.max() < 1.0
+    bigdev.put(frame)
+    div = np.float64(npix) * np.float64(4294967296.0)
+    for ow, oh in ((1, 1), (3, 2)):
+        S = ref.sums_separable(frame, w, h, ow, oh)
+        ints = [int(v) for v in S.ravel()]
+        assert min(ints) >= 1 << 53 and max(ints) < 1 << 60
+        want = ref.byte_sorted(table, (S.astype(np.float64) / div).astype(F32))
+        for fmt in (RGBA8, RGB8):
+            got = bigdev.present(w, h, ow, oh, fmt=fmt)
+            assert np.array_equal(got[:, :, :3], want), (ow, oh, fmt, got.tolist(), want.tolist(), ints)
+    bigdev.put(np.ones((npix, 3), dtype=F32))
+    for ow, oh in ((1, 1), (3, 2)):
+        assert (ref.sums_separable(np.ones((npix, 3), dtype=F32), w, h, ow, oh) == np.uint64(npix << 32)).all()
+        assert (bigdev.present(w, h, ow, oh) == 255).all(), (ow, oh)
+
+
+def frame_for_sums(targets, npix):
+    """A frame of npix pixels whose channel c sums to targets[c] exactly in step 4's fixed point (one output pixel, every weight
+    1): pixel 0 holds the target's low eight bits (j * 2^-32, j < 256), the others one of two neighbouring multiples of 2^-24."""
+    out = np.zeros((npix, 3), dtype=F32)
+    for c, target in enumerate(targets):
+        j = target % 256
+        rest = target - j
+        qb = rest // (npix - 1) // 256 * 256
+        more, left = divmod(rest - qb * (npix - 1), 256)
+        assert left == 0 and 0 <= more <= npix - 1 and qb + 256 <= 1 << 32
+        q = np.full(npix, qb, dtype=np.int64)
+        q[1:1 + more] += 256
+        q[0] = j
+        assert int(q.sum()) == target
+        out[:, c] = (q.astype(np.float64) / 4294967296.0).astype(F32)
+        assert ((out[:, c].astype(np.float64) * 4294967296.0).astype(np.int64) == q).all()  # each value is held exactly
+    return out
+
+
+def test_conversion_of_sums_rounds_to_nearest_even(bigdev, table):
+    """The contract's mean is (float)((double)S / divisor): S is rounded to binary64 FIRST, to nearest even, then divided, then
+    rounded to binary32 - two roundings, on purpose.  At S >= 2^53 the first one is real, and this frame makes it decide a byte.
+    4096 x 1024 -> 1 x 1, so the divisor is 2^54 and the division exact.  T[k] = M * 2^-24 is a threshold in [0.5, 1) with M
+    even; tie = (M - 1/2) * 2^30 is the S halfway between T[k] and the float below it.
+    - S = tie - 1 is odd, halfway between the binary64 values tie - 2 and tie: nearest even is tie, which then ties to T[k]:
+      byte k.  A conversion that truncates gives tie - 2, and the exact quotient (one rounding) lies below the tie: both k - 1.
+    - S = tie - 3 goes to tie - 4: byte k - 1.  A conversion that rounds halves up gives tie - 2, the same byte; one that rounds
+      everything up gives tie - 2 as well.
+    - S = tie + 1 goes to tie (nearest even, down): byte k.
+    All of it is asserted on the restatement's integers before the device is asked."""
+    w, h = 4096, 1024
+    npix = w * h
+    k = next(k for k in range(1, 256) if 0x3F000000 <= table[k] < ONE_BITS and table[k] % 2 == 0)
+    M = (int(table[k]) & 0x7FFFFF) | 0x800000
+    tie = (2 * M - 1) << 29
+    targets = (tie - 1, tie - 3, tie + 1)
+    frame = frame_for_sums(targets, npix)
+    S = ref.sums_separable(frame, w, h, 1, 1)
+    assert [int(v) for v in S.ravel()] == list(targets)
+    assert all(1 << 53 <= v < 1 << 54 and int(float(v)) != v for v in targets)  # binary64 holds none of them: the conversion rounds
+    assert [int(float(v)) for v in targets] == [tie, tie - 4, tie]
+    want = ref.byte_sorted(table, (S.astype(np.float64) / (np.float64(npix) * np.float64(4294967296.0))).astype(F32))
+    assert want.ravel().tolist() == [k, k - 1, k]
+    once = ref.byte_sorted(table, np.array([float(np.float32(v / 2.0 ** 54)) for v in (tie - 2,)], dtype=F32))  # what truncating gives
+    assert once.tolist() == [k - 1]
+    bigdev.put(frame)
+    for fmt in (RGBA8, RGB8):
+        for flags in (0, FRAMEBUFFER_ORDER):
+            got = bigdev.present(w, h, 1, 1, fmt=fmt, flags=flags)
+            assert got[0, 0, :3].tolist() == [k, k - 1, k], (fmt, flags, got.tolist(), k)
 
 
 # --------------------------------------------------------------------------------------------------------- exposure

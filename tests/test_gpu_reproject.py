@@ -136,6 +136,54 @@ def test_is_the_restatement(dev, size, camera):
         assert 0.1 < ok.mean() < 0.9
 
 
+# ------------------------------------------------------------------------------------- thin, long and full-size frames
+# A tuple of its own, so that the parametrisations over FRAMES keep their cost.  The calls of this family check only
+# width * height <= 2^28: an axis may be longer than the 2^14 pt_ctx_upsample stops at.
+# - 100 x 30: 4 x 4 tiles of kernel B (32 x 8), the first frame with a tile that has neighbours on all four sides (W >= 65, H >= 17);
+# - 65536 x 4: a width of 2^16 > 2^14, 2048 tiles across and one down, a row of 1024 workgroups of 256;
+# - 3 x 40 000: tiles_x = 1 with 5000 tile rows, a height above 2^14, every workgroup of 256 spans 85 rows;
+# - 1 x 262 144: a height of 2^18, one column: every tap beside it is outside the frame;
+# - 1024 x 768: the documented frame, 3072 workgroups, 32 x 96 tiles.
+# synthetic() seeds from w * 100 + h: 10030, 6553604, 40300, 262244 and 103168 - none is the seed of another shape here.
+LARGE = ((100, 30), (65536, 4), (3, 40000), (1, 262144), (1024, 768))
+LARGE_IDS = ["%dx%d" % s for s in LARGE]
+MAXPIX_LARGE = max(w * h for w, h in LARGE)
+_seeds = [w * 100 + h for w, h in FRAMES + LARGE]
+assert len(set(_seeds)) == len(_seeds)
+
+
+def tiles_of(w, h):
+    """kernel B's grid: (tiles_x, tiles_y) of 32 x 8"""
+    return -(-w // 32), -(-h // 8)
+
+
+@pytest.fixture(scope="module")
+def bigdev(L):
+    with Dev(L, MAXPIX_LARGE) as d:
+        yield d
+
+
+@pytest.mark.parametrize("size", LARGE, ids=LARGE_IDS)
+@pytest.mark.parametrize("camera", ["identical", "translated"])
+def test_large_frames_are_the_restatement(bigdev, size, camera):
+    w, h = size
+    assert w * h <= 1 << 28  # all the validator asks
+    premise = {(100, 30): tiles_of(w, h) == (4, 4), (65536, 4): w > 1 << 14 and tiles_of(w, h) == (2048, 1),
+               (3, 40000): h > 1 << 14 and tiles_of(w, h) == (1, 5000), (1, 262144): h == 1 << 18 and w == 1,
+               (1024, 768): -(-w * h // 256) == 3072 and tiles_of(w, h) == (32, 96)}
+    assert premise[size]
+    cam, hist_cam = CAMERAS[camera]
+    cur, hist = synthetic(w, h)
+    bigdev.put(cur, hist)
+    exp = want(w, h, cam, cur, hist_cam, hist)
+    got = bigdev.reproject(w, h, cam, hist_cam)
+    same_bytes(got, exp, (size, camera))
+    assert not (got[0] == -3.0).any() and not (got[1] == -3.0).any()  # no pixel still holds the fill pattern
+    blended = exp[1] > PARAMS["weight"]
+    print("%dx%d %s: %d of %d pixels blend" % (w, h, camera, blended.sum(), w * h))
+    assert blended.any() and not blended.all()
+
+
 @pytest.mark.parametrize("camera", ["identical", "translated"])
 def test_optional_normals(dev, camera):
     w, h = 33, 25

@@ -180,6 +180,43 @@ def test_is_the_restatement(dev, size, camera):
         assert (ln[(ids == 1) | (ids == 2)] > PARAMS["weight"]).any(), camera
 
 
+# ------------------------------------------------------------------------------------- thin, long and full-size frames
+# tests/test_gpu_reproject.py's LARGE (it says what each shape crosses) through both moved calls with ONE moving object: a table
+# of two records, IDENTITY and a translation, so object 1 moves and ids 2..5 lie beyond the table.  The camera stands still - the
+# drag loop - so a wave mixes step 2's single tap with four-tap lanes.  The spatial window is the smallest (radius 1): the window
+# does not read the table, and tests/test_gpu_reproject_var.py runs it at every radius on these shapes.
+ONE_MOVING = (IDENTITY, (0.11, -0.05, 0.02, 1.0))
+LARGE_PARAMS = dict(PARAMS, radius=1)
+
+
+@pytest.fixture(scope="module")
+def bigdev(L):
+    with Dev(L, base.MAXPIX_LARGE) as d:
+        yield d
+
+
+@pytest.mark.parametrize("size", base.LARGE, ids=base.LARGE_IDS)
+def test_large_frames_with_one_moving_object(bigdev, size):
+    w, h = size
+    cam, hist_cam = CAMERAS["identical"]
+    cur, hist = synthetic(w, h)
+    bigdev.put(cur, hist)
+    exp = mref.reproject_var_moved(w, h, cam, cur["color"], cur["depth"], cur["oid"], cur["normal"], motion=ONE_MOVING,
+                                   **hist_kw(hist_cam, hist), **LARGE_PARAMS)
+    got = bigdev.reproject_var_moved(w, h, cam, hist_cam, ONE_MOVING, params=LARGE_PARAMS)
+    vbase.same_bytes(got, exp, (size, "var"))
+    vbase.no_fill_left(got)
+    exp2 = mref.reproject_moved(w, h, cam, cur["color"], cur["depth"], cur["oid"], cur["normal"], motion=ONE_MOVING,
+                                **hist_kw(hist_cam, hist, var=False), **{k: PARAMS[k] for k in PLAIN_KEYS})
+    got2 = bigdev.reproject_moved(w, h, cam, hist_cam, ONE_MOVING, params=LARGE_PARAMS)
+    same2(got2, exp2, (size, "plain"))
+    vbase.no_fill_left(got2)
+    assert exp2[0].tobytes() == exp[0].tobytes() and exp2[1].tobytes() == exp[1].tobytes()  # "colour and length are the moved call's"
+    moving = cur["oid"] == 1
+    print("%dx%d: %d pixels of the moving object, %d of them blend" % (w, h, moving.sum(), (exp[1][moving] > PARAMS["weight"]).sum()))
+    assert moving.any() and (cur["oid"] >= 2).any() and (exp[1][~moving] > PARAMS["weight"]).any()
+
+
 @pytest.mark.parametrize("camera", list(CAMERAS))
 def test_delegation(dev, camera):
     """motion NULL, n_motion 0 and an all-IDENTITY table each give the plain calls' bytes on the same inputs"""

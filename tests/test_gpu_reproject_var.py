@@ -184,6 +184,94 @@ def test_is_the_restatement_and_the_old_kernel(dev, size, camera):
                 assert np.isfinite(got[3][~long]).any()
 
 
+# ------------------------------------------------------------------------------------- thin, long and full-size frames
+# tests/test_gpu_reproject.py's LARGE says what each shape crosses; kernel B's grid is one-dimensional, blockIdx.x % tiles_x and
+# blockIdx.x / tiles_x, so tiles_x = 1 over 5000 tile rows (3 x 40 000), its transpose (65536 x 4: 2048 x 1) and one column of
+# 32 768 tiles (1 x 262 144) are the shapes at which a wrong tiles_x shows.
+LARGE = base.LARGE
+
+
+@pytest.fixture(scope="module")
+def bigdev(L):
+    with Dev(L, base.MAXPIX_LARGE) as d:
+        yield d
+
+
+def no_fill_left(got):
+    for a in got:
+        assert not (a == -3.0).any()  # no output word still holds the fill pattern
+
+
+@pytest.mark.parametrize("size", LARGE, ids=base.LARGE_IDS)
+@pytest.mark.parametrize("camera", ["identical", "translated"])
+def test_large_frames_are_the_restatement(bigdev, size, camera):
+    w, h = size
+    cam, hist_cam = CAMERAS[camera]
+    cur, hist = synthetic(w, h)
+    bigdev.put(cur, hist)
+    got = bigdev.reproject_var(w, h, cam, hist_cam)
+    exp = want(w, h, cam, cur, hist_cam, hist, parts=True)
+    same_bytes(got, exp[:4], (size, camera))
+    no_fill_left(got)
+    long = exp[4]["long"]
+    print("%dx%d %s: %d of %d pixels short, tiles %s" % (w, h, camera, (~long).sum(), w * h, base.tiles_of(w, h)))
+    assert 0 < long.mean() < 1 and np.isfinite(got[3][~long]).any()
+    if camera == "identical" and w > TILE[0]:
+        cls = tile_class(w, h)
+        assert long[cls == 1].all() and not long[cls == 2].any() and 0 < long[cls == 0].mean() < 1
+
+
+# Every pixel short: the first-frame form (each pixel ends with wt = 4 samples, below min_frames * wt = 16), so every workgroup of
+# kernel B stages its tile and halo and every lane runs the window - which the mixed layouts above never ask of an interior tile.
+# - 100 x 30: 4 x 4 tiles; tile (1, 1) has full neighbours on all four sides (W >= 65, H >= 17), the last column is 4 wide and the
+#   last row 6 high;
+# - 3 x 40 000: tiles_x = 1, 5000 tile rows, the window leaves the frame left and right of every pixel;
+# - 1024 x 768: 32 x 96 full tiles, the 49-tap window over 786 432 pixels.
+SHORT = ((100, 30), (3, 40000), (1024, 768))
+_short = {}
+
+
+def short_frame(w, h):
+    """A frame for the window: the object ids and depths lie in blocks whose borders fall, in every tile of 32 x 8, on the tile's
+    own border (x % 32 == 0, r % 8 == 0), inside it (x % 32 == 16) and three pixels before its far border (x % 32 == 29,
+    r % 8 == 5) - the first column and row of the NEXT tile's halo, so a block's corner sits in a halo's corner.  A tenth of the
+    pixels get a random id and plane, as in the other frames."""
+    if (w, h) not in _short:
+        cur, _ = base.synthetic(w, h)
+        n = w * h
+        rng = np.random.default_rng(w * 1000 + h + 7)
+        x, r = np.arange(n) % w, np.arange(n) // w
+        bx = (x // TILE[0]) * 3 + (x % TILE[0] >= 16) + (x % TILE[0] >= 29)
+        by = (r // TILE[1]) * 2 + (r % TILE[1] >= 5)
+        planes = np.array([2.0, 6.0, 6.25, 9.0, np.inf], dtype=F32)
+        depth = np.where(rng.random(n) < 0.1, planes[rng.integers(0, 5, n)], planes[(bx + 2 * by) % 4]).astype(F32)
+        oid = np.where(rng.random(n) < 0.1, rng.integers(-1, 3, n), (bx + by) % 3).astype(I32)
+        _short[(w, h)] = dict(cur, depth=depth, oid=oid)
+    return _short[(w, h)]
+
+
+@pytest.mark.parametrize("size", SHORT, ids=["%dx%d" % s for s in SHORT])
+@pytest.mark.parametrize("radius", [1, 2, 3])
+def test_every_pixel_short(bigdev, size, radius):
+    w, h = size
+    tiles = base.tiles_of(w, h)
+    assert tiles == {(100, 30): (4, 4), (3, 40000): (1, 5000), (1024, 768): (32, 96)}[size]
+    if size == (100, 30):
+        assert w >= 2 * TILE[0] + 1 and h >= 2 * TILE[1] + 1 and tiles[0] >= 3 and tiles[1] >= 3  # an interior tile exists
+    cur = short_frame(w, h)
+    bigdev.put(cur)
+    params = dict(PARAMS, radius=radius)
+    assert params["min_frames"] > 1
+    got = bigdev.reproject_var(w, h, CUR, None, history=False, hist_normal=False, params=params)
+    exp = want(w, h, CUR, cur, params=params, parts=True)
+    assert not exp[4]["long"].any()  # the premise: every lane of every tile runs the window
+    same_bytes(got, exp[:4], (size, radius))
+    no_fill_left(got)
+    cnt = exp[4]["cnt"]
+    print("%dx%d radius %d: taps taken %d..%d, %d pixels without an estimate" % (w, h, radius, cnt.min(), cnt.max(), (cnt < 2).sum()))
+    assert cnt.max() > cnt.min() and cnt.max() > 2 * radius + 1 and np.isfinite(got[3]).any()
+
+
 @pytest.mark.parametrize("camera", ["identical", "translated"])
 def test_optional_normals(dev, camera):
     w, h = 33, 25

@@ -2,7 +2,9 @@
 Every comparison is of bytes, for equality, with guard floats behind both outputs.  The cases (upsample_ref.CASES, frame <- low
 resolution) are the smallest that reach every path: one pixel, no integer ratio (7x5 <- 3x2), two workgroups with a one-lane tail
 and taps off both row edges (257x3 <- 129x2), 33x25 <- 16x12, a low resolution LARGER than the frame (16x12 <- 33x25) and equal
-sizes.  That their synthetic inputs reach every path is tests/test_upsample_abi.py's test_synthetic_inputs_reach_every_path."""
+sizes.  upsample_ref.LARGE holds the shapes at the limits: axes of 2^14, the largest numerators of the three divisions, and the
+documented 1024x768 <- 512x384 in the four template instances.  That the synthetic inputs of both tuples reach every path is
+tests/test_upsample_abi.py's test_synthetic_inputs_reach_every_path."""
 import ctypes as C
 
 import pytest
@@ -84,6 +86,62 @@ def test_is_the_restatement(dev, inputs, case):
     hi, lo = inputs[case]
     dev.put(hi, lo)
     same_bytes(dev.upsample(*case), ref.want(*case, hi, lo), case)
+
+
+# ------------------------------------------------------------------------------------- axis limits and full-size frames
+# upsample_ref.LARGE says which constant each shape crosses.  The premises are asserted here from csrc/pt_upsample.h's numbers.
+MAX_SIZE, DIV_BOUND = ref.MAX_SIZE, 1 << 30  # kUpsampleMaxSize; upsample_div is proved for numerators below 2^30
+FRAME = (1024, 768, 512, 384)
+
+
+@pytest.fixture(scope="module")
+def bigdev(L):
+    with Dev(L, max(max(c[0] * c[1], c[2] * c[3]) for c in ref.LARGE)) as d:
+        yield d
+
+
+_large = {}
+
+
+def large_inputs(case):
+    """the synthetic planes of a LARGE case, made once and left unchanged"""
+    if case not in _large:
+        _large[case] = ref.synthetic(*case)
+    return _large[case]
+
+
+def numerators(W, H, w, h):
+    """the largest numerator each of the three divisions of a pixel sees: idx / W, ax / 2W, ar / 2H"""
+    return W * H - 1, (2 * (W - 1) + 1) * w + W, (2 * (H - 1) + 1) * h + H
+
+
+@pytest.mark.parametrize("case", ref.LARGE[:-1], ids=["%dx%d<-%dx%d" % c for c in ref.LARGE[:-1]])
+def test_axis_limits_are_the_restatement(bigdev, case):
+    W, H, w, h = case
+    assert MAX_SIZE in case and max(case) <= MAX_SIZE
+    assert max(numerators(*case)) > 1 << 10 and max(numerators(*case)) < DIV_BOUND  # above what the small cases reach, within the proof
+    if case == (16384, 2, 16384, 3):
+        assert numerators(*case)[1] == 1 << 29  # (2x + 1) * w + W at its bound exactly
+    if case == (16384, 16, 16384, 16):
+        assert numerators(*case)[0] == (1 << 18) - 1 and W == MAX_SIZE  # idx / W with W at the limit
+    hi, lo = large_inputs(case)
+    bigdev.put(hi, lo)
+    same_bytes(bigdev.upsample(*case), ref.want(*case, hi, lo), case)
+
+
+@pytest.mark.parametrize("normal", [True, False], ids=["normals", "no-normals"])
+@pytest.mark.parametrize("albedo", [True, False], ids=["albedos", "no-albedos"])
+def test_full_frame_in_every_instance(bigdev, normal, albedo):
+    """1024x768 <- 512x384 (3072 workgroups of 256; numerators up to 786 431, 1 049 088 and 590 208) through each of k_upsample's
+    four template instances, the whole frame against the restatement"""
+    assert FRAME == ref.LARGE[-1] and -(-FRAME[0] * FRAME[1] // 256) == 3072
+    assert numerators(*FRAME) == (786431, 1049088, 590208)
+    hi, lo = large_inputs(FRAME)
+    bigdev.put(hi, lo)
+    kw = dict(normal=(normal, normal), albedo=(albedo, albedo))
+    got = bigdev.upsample(*FRAME, **kw)
+    same_bytes(got, ref.want(*FRAME, hi, lo, **kw), (FRAME, kw))
+    assert not (got[0] == -3.0).any() and not (got[1] == -3.0).any()  # no pixel still holds the fill pattern
 
 
 @pytest.mark.parametrize("case", [BIG, (16, 12, 33, 25)], ids=["down", "up"])

@@ -251,6 +251,47 @@ def test_ref_constant_frame_keeps_its_fixed_point(src, dst, table):
             assert (m == c).all()
 
 
+@pytest.mark.parametrize("src,dst", SIZE_PAIRS)
+def test_ref_separable_form_is_the_slow_form(src, dst, table):
+    """the forms tests/test_gpu_present.py uses on full-size frames (rows then columns in uint64, the byte by binary search) give
+    what the independent slow forms give, on every resampling shape of the GPU tests, both formats and both orders - and the
+    overlaps are the weights"""
+    (w, h), (ow, oh) = src, dst
+    for n, on in zip(src, dst):
+        X, x, wgt = ref.overlaps(n, on)
+        dense = np.zeros((on, n), dtype=np.int64)
+        dense[X, x] = wgt.astype(np.int64)
+        assert dense.tolist() == ref.weights(n, on) and (wgt > 0).all()
+    rng = np.random.default_rng(w * 1000 + ow)
+    k = rng.integers(1, 256, size=w * h * 3)
+    frame = ref.bits_to_f32((table[k].astype(np.int64) + rng.integers(-2, 3, size=w * h * 3)).astype(np.uint32)).reshape(w * h, 3).copy()
+    frame[::7] = (rng.random((len(frame[::7]), 3)) * 1.25 - 0.125).astype(F32)
+    for flags in (0, ref.FRAMEBUFFER_ORDER):
+        for exposure in (0.0, 0.5):
+            slow = ref.mean(frame, w, h, ow, oh, exposure, flags)
+            assert ref.mean_separable(frame, w, h, ow, oh, exposure, flags).tobytes() == slow.tobytes(), (flags, exposure)
+        for fmt in (ref.RGBA8, ref.RGB8):
+            assert np.array_equal(ref.present(table, frame, w, h, ow, oh, fmt=fmt, flags=flags, separable=True),
+                                  ref.present(table, frame, w, h, ow, oh, fmt=fmt, flags=flags)), (flags, fmt)
+    assert np.array_equal(ref.present(table, frame, w, h, separable=True), ref.present(table, frame, w, h))  # the same size
+
+
+def test_ref_separable_form_rounds_large_sums_as_the_slow_form_does(table):
+    """S >= 2^53: the conversion to binary64 rounds, to nearest even, in both forms - Python's float(int) and numpy's uint64 ->
+    float64 - and byte_sorted is byte on every threshold's neighbourhood"""
+    S = np.array([(1 << 53) + 1, (1 << 53) + 3, (1 << 54) + 2, (1 << 54) + 6, (1 << 59) + 96, (1 << 60) - 1, 13510798882111489],
+                 dtype=np.uint64)
+    assert [float(int(v)) for v in S] == S.astype(np.float64).tolist()
+    assert [float(int(v)) for v in S[:4]] == [2.0 ** 53, 2.0 ** 53 + 4, 2.0 ** 54, 2.0 ** 54 + 8]  # ties go to even
+    around = (table[1:, None].astype(np.int64) + np.arange(-3, 4)).ravel().astype(np.uint32)
+    bits = np.concatenate([around, np.arange(0, ONE_BITS + 1, 40009, dtype=np.uint32), np.array([0, ONE_BITS], dtype=np.uint32)])
+    v = ref.bits_to_f32(bits)
+    assert np.array_equal(ref.byte_sorted(table, v), ref.byte(table, v))
+    # a frame of ones folds to W*H*2^32 exactly, whatever the ratio
+    w, h = 67, 33
+    assert (ref.sums_separable(np.ones((w * h, 3), dtype=F32), w, h, 3, 2) == np.uint64(w * h << 32)).all()
+
+
 def test_ref_orders_and_formats(table):
     w, h = 3, 2
     frame = (np.arange(w * h * 3, dtype=F32) / F32(w * h * 3)).reshape(w * h, 3)

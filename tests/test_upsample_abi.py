@@ -345,12 +345,14 @@ def test_ref_demodulation_puts_the_frames_albedo_on_an_edge_pixel():
 
 
 # --------------------------------------------------------------------------- the GPU tests' inputs reach every path
-@pytest.mark.parametrize("case", ref.CASES, ids=["%dx%d<-%dx%d" % c for c in ref.CASES])
+@pytest.mark.parametrize("case", ref.CASES + ref.LARGE, ids=["%dx%d<-%dx%d" % c for c in ref.CASES + ref.LARGE])
 def test_synthetic_inputs_reach_every_path(case):
     """What keeps the byte comparison on the GPU from being empty, checked in the restatement alone.  On every case of more than
     64 frame pixels there is a pixel of each kind.  One kind cannot exist in one case: with a low-resolution frame LARGER on both
     axes every frame pixel's centre lies between two low-resolution centres (x0 = -1 needs w < W, x0 = w-1 needs w <= W), so no tap
-    is outside it - that is asserted instead."""
+    is outside it - that is asserted instead.  Another cannot exist where a low-resolution axis is ONE pixel long (three of
+    upsample_ref.LARGE): of the two taps along it one is always outside, so no pixel takes all four - asserted instead, with what
+    can exist there: each of the four tap positions is taken by some pixel, taps on both sides of both axes."""
     W, H, w, h = case
     hi, lo = ref.synthetic(W, H, w, h)
     for k in ("depth", "oid", "normal", "albedo"):
@@ -361,7 +363,11 @@ def test_synthetic_inputs_reach_every_path(case):
     print(case, kinds)
     if W * H > 64:
         for k in ("all_four", "some", "fallback", "miss_taken"):
+            if k == "all_four" and (w == 1 or h == 1):
+                assert kinds[k] == 0, (k, kinds)
+                continue
             assert kinds[k] > 0, (k, kinds)
+        assert det["taken"].any(axis=0).all(), det["taken"].sum(axis=0)  # each of the four tap positions, somewhere
         if w > W and h > H:
             assert kinds["outside"] == 0
         else:

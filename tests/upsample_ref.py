@@ -115,6 +115,16 @@ def upsample(W, H, w, h, lo_color, lo_depth, lo_object_id, depth, object_id, lo_
 
 # ------------------------------------------------------------------------------- the inputs of the GPU tests (and of one CPU test)
 CASES = ((1, 1, 1, 1), (7, 5, 3, 2), (257, 3, 129, 2), (33, 25, 16, 12), (16, 12, 33, 25), (33, 25, 33, 25))  # frame <- low
+# The shapes at the limits csrc/pt_upsample.h argues, a tuple of its own so that the parametrisations over CASES keep their cost.
+# With S = kUpsampleMaxSize = 2^14, the largest size of an axis:
+# - 16384x2 <- 8192x1, 16384x3 <- 5461x2, 2x16384 <- 1x8191: an axis at the limit on either side, an integer ratio and none, a
+#   low-resolution axis of one pixel (every tap pair has one tap outside it);
+# - 16384x2 <- 16384x3: both widths at the limit, where the numerator (2x + 1) * w + W reaches (2S - 1) * S + S = 2^29 exactly,
+#   the bound upsample_div is proved for (n < 2^30), at the divisor 2W = 2^15;
+# - 16384x16 <- 16384x16: idx reaches 2^18 - 1 with W at the limit, so idx / W runs the division by the largest W over 16 rows;
+# - 1024x768 <- 512x384: the documented preview loop, 3072 workgroups, the shape the four template instances are timed at.
+LARGE = ((16384, 2, 8192, 1), (16384, 3, 5461, 2), (2, 16384, 1, 8191), (16384, 2, 16384, 3), (16384, 16, 16384, 16),
+         (1024, 768, 512, 384))
 PARAMS = dict(depth_tol=0.05, normal_min=0.5)
 
 
