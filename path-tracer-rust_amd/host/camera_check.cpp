@@ -210,6 +210,6 @@ int main(int argc, char **argv) {
         }
         CHECK(rebuilds == 2u);
     }
-    printf("camera_check: OK\n");
+    printf("camera_check: ok\n");
     return 0;
 }

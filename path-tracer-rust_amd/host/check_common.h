@@ -1,7 +1,8 @@
-// check_common.h — what the stand-alone check programs under host/ share (make <name>-check builds each with
-// -fsanitize=address,undefined and runs it; no device, no Python): the library's error channel, which lives in csrc/pt_api.hip and
-// so is not linked here, CHECK, the refusal test, the random numbers, and the cameras and frames of the two reproject programs.
-// Each program is one translation unit of its own beside host/scene_io.cpp and csrc/pt_host.cpp: the definitions below are its.
+// check_common.h — what the stand-alone host programs under host/ share (<name>_check judges itself, <name>_probe and <name>_dump
+// print what a test asks for; the Makefile's one rule builds each with -fsanitize=address,undefined; no device, no Python): the
+// library's error channel, which lives in csrc/pt_api.hip and so is not linked here, CHECK, the refusal test, the random numbers, and
+// the cameras and frames of the reproject programs.  Each program is one translation unit of its own, linked against
+// host/scene_io.cpp and csrc/pt_host.cpp compiled once for all of them: the definitions below are its.
 #pragma once
 
 #include <cmath>

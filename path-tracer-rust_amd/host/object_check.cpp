@@ -414,6 +414,6 @@ int main(int argc, char **argv) {
         CHECK(flatten(sc, fresh, &B, nullptr));
         CHECK(same_tables(fs, fresh));
     }
-    printf("object_check: OK\n");
+    printf("object_check: ok\n");
     return 0;
 }

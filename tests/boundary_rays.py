@@ -11,8 +11,8 @@ such rays from a seed:
   16, 17, 64, 500 and 5 000 triangles (soups and closed surfaces; the largest keeps its nodes in global memory); exact
   ties; spheres (tangent rays, origins inside and 1e-4 from the surface);
 * ray families aimed at vertices, edges (f32 lerp) and centroids; at the corners and faces of the padded BVH boxes and
-  the edges of the flat filter records READ FROM THE PRODUCT'S OWN TABLES (host::flatten_scene, dumped by a small C++
-  helper linked against libptrace_hip.so - the padding formulas are not restated here); directions with exact +-0
+  the edges of the flat filter records READ FROM THE PRODUCT'S OWN TABLES (host::flatten_scene, dumped by
+  host/tables_dump.cpp over the library's host code - the padding formulas are not restated here); directions with exact +-0
   components and components of 1e-19 .. 1e-38 and subnormal (the +-1e18 clamp and v_rcp_f32's sign decide); origins on
   the surfaces, taken from the oracle's own hit points as the path tracer's bounce rays are.
 
@@ -24,7 +24,6 @@ import atexit
 import ctypes as C
 import os
 import shutil
-import subprocess
 import tempfile
 
 import numpy as np
@@ -38,45 +37,6 @@ VARIANTS = 1 + 2 * len(ULP_STEPS)  # the target ray, then origin +-1/2 ulp, then
 RAY_KINDS = ["vertex", "edge", "centroid", "box", "flat_edge", "zero_dir", "tiny_dir", "surface", "sphere", "tie"]
 
 # ---------------------------------------------------------------------------------------------------------- tables
-DUMP_SRC = r"""
-#include <cstdio>
-#include <cstdint>
-#include <string>
-#include <vector>
-#include "ptrace.h"
-#include "pt_host.h"
-using namespace pt;
-// argv[1]: scene file (u32 n_objs, u32 n_tris, pt_camera, pt_object[n_objs], pt_triangle[n_tris]); argv[2]: output file.
-// Writes host::flatten_scene's tables - what pt_ctx_set_scene uploads - as a count header followed by the raw records.
-template <class T> static void put(FILE *f, const std::vector<T> &v) { if (!v.empty()) fwrite(v.data(), sizeof(T), v.size(), f); }
-int main(int argc, char **argv) {
-    FILE *in = fopen(argv[1], "rb");
-    uint32_t n[2];
-    if (!in || fread(n, 4, 2, in) != 2) { printf("FAIL read\n"); return 1; }
-    pt_camera cam;
-    std::vector<pt_object> objs(n[0]);
-    std::vector<pt_triangle> tris(n[1] ? n[1] : 1);
-    if (fread(&cam, sizeof cam, 1, in) != 1 || fread(objs.data(), sizeof(pt_object), n[0], in) != n[0] ||
-        fread(tris.data(), sizeof(pt_triangle), n[1], in) != n[1]) { printf("FAIL read\n"); return 1; }
-    fclose(in);
-    host::FlatScene fs;
-    std::string err;
-    if (!host::flatten_scene(cam, objs.data(), n[0], tris.data(), n[1], fs, err)) { printf("FAIL flatten %s\n", err.c_str()); return 1; }
-    FILE *out = fopen(argv[2], "wb");
-    const uint32_t h[16] = {(uint32_t)fs.objs.size(), (uint32_t)fs.tri_pairs.size(), (uint32_t)fs.bvh_nodes.size(),
-                            (uint32_t)fs.bvh_nodes4.size(), (uint32_t)fs.flat_pairs.size(), (uint32_t)fs.cand_pairs.size(),
-                            (uint32_t)fs.bvh_meshes.size(), fs.n_flat_exact, fs.n_other_pairs, (uint32_t)fs.tri_rank.size(),
-                            (uint32_t)fs.rank_id.size(), (uint32_t)fs.cand_ok, fs.bvh_stack, 0, 0, 0};
-    fwrite(h, 4, 16, out);
-    put(out, fs.objs); put(out, fs.tri_pairs); put(out, fs.bvh_nodes); put(out, fs.bvh_nodes4); put(out, fs.flat_pairs);
-    put(out, fs.cand_pairs); put(out, fs.bvh_meshes); put(out, fs.tri_rank); put(out, fs.rank_id);
-    fclose(out);
-    printf("OK %zu %zu %zu %zu %zu %zu %zu\n", sizeof(ObjRec), sizeof(TriPairRec), sizeof(BvhNode), sizeof(BvhNode4),
-           sizeof(FlatPairRec), sizeof(CandPairRec), sizeof(BvhMeshRec));
-    return 0;
-}
-"""
-
 _f2 = (np.float32, (2,))
 _u2 = (np.uint32, (2,))
 OBJ_DT = np.dtype([("c", np.float32, (3,)), ("rr", np.float32), ("kind", np.uint32), ("tri_begin", np.uint32),
@@ -94,36 +54,34 @@ MESH_DT = np.dtype([("c", np.float32, (3,)), ("rr", np.float32), ("root", np.int
 NO_PAIR = 0xffffffff
 NO_TRI = 0x7fffffff
 
-_helper = None
+_work = None
 
 
-def _dump_helper():
-    global _helper
-    if _helper is None:
-        d = tempfile.mkdtemp(prefix="pt_tables_")
-        atexit.register(shutil.rmtree, d, True)
-        src = os.path.join(d, "dump.cpp")
-        with open(src, "w") as f:
-            f.write(DUMP_SRC)
-        exe = os.path.join(d, "dump")
-        subprocess.check_call(["g++", "-O1", "-std=c++17", "-I", os.path.join(ptlib.PKG, "csrc"), "-I",
-                               os.path.join(ptlib.ROOT, "include"), src, "-o", exe, "-L", ptlib.PKG, "-lptrace_hip",
-                               "-Wl,-rpath," + ptlib.PKG])
-        _helper = exe
-    return _helper
+def workdir():
+    """this process's directory for the files the two table generators (host/tables_dump.cpp, host/layout_dump.cpp) read and write"""
+    global _work
+    if _work is None:
+        _work = tempfile.mkdtemp(prefix="pt_tables_")
+        atexit.register(shutil.rmtree, _work, True)
+    return _work
 
 
-def scene_tables(sc):
-    """host::flatten_scene's tables of a scene (the records pt_ctx_set_scene uploads), as numpy record arrays."""
-    exe = _dump_helper()
-    d = os.path.dirname(exe)
-    path_in, path_out = os.path.join(d, "scene.bin"), os.path.join(d, "tables.bin")
-    with open(path_in, "wb") as f:
+def write_scene(sc, path):
+    """The scene file of the two generators: u32 n_objs, u32 n_tris, pt_camera, pt_object[n_objs], pt_triangle[n_tris]."""
+    with open(path, "wb") as f:
         f.write(np.array([sc.n_objs, sc.n_tris], np.uint32).tobytes())
         f.write(bytes(sc.cam))
         f.write(bytes(sc.objs)[:sc.n_objs * C.sizeof(ptlib.PtObject)])
         f.write(bytes(sc.tris)[:sc.n_tris * C.sizeof(ptlib.PtTriangle)])
-    out = subprocess.check_output([exe, path_in, path_out]).decode().split()
+    return path
+
+
+def scene_tables(sc):
+    """host::flatten_scene's tables of a scene (the records pt_ctx_set_scene uploads), as numpy record arrays.  The generator is the
+    PLAIN build of host/tables_dump.cpp: GPU tests come through here, and no sanitizer build runs on a GPU machine
+    (tests/test_boundary_rays.py holds the sanitized build to the same bytes)."""
+    path_in, path_out = write_scene(sc, os.path.join(workdir(), "scene.bin")), os.path.join(workdir(), "tables.bin")
+    out = ptlib.host_program("tables_dump", sanitize=False)(path_in, path_out).split()
     sizes = [int(v) for v in out[1:]]
     assert out[0] == "OK" and sizes == [t.itemsize for t in (OBJ_DT, PAIR_DT, NODE_DT, NODE4_DT, FLAT_DT, CAND_DT, MESH_DT)], out
     raw = open(path_out, "rb").read()

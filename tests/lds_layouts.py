@@ -7,17 +7,12 @@ one candidate pair record, one shading record, one BVH node or one pixel per str
 offset at a cliff reads records that were never written, silently, for the objects at the end of the staged table only.
 
 This module builds, from a seed and in binary32, a pair of scenes (or of stream lengths m, set through PT_STREAMS) for every
-cliff: one just inside and one just outside, one step of its knob apart.  The layouts are never restated here: a small C++
-helper compiles pt_layout.h with the host compiler, fills the DevScene counts from host::flatten_scene (the tables
+cliff: one just inside and one just outside, one step of its knob apart.  The layouts are never restated here:
+host/layout_dump.cpp compiles pt_layout.h with the host compiler, fills the DevScene counts from host::flatten_scene (the tables
 pt_ctx_set_scene uploads) and prints lds_layout's answer and the line the library itself writes to stderr under PT_LDS_PAD.
-The knob of a pair is found by bisection over what that helper says.
+The knob of a pair is found by bisection over what that program says.
 """
-import atexit
-import ctypes as C
 import os
-import shutil
-import subprocess
-import tempfile
 
 import numpy as np
 
@@ -32,94 +27,18 @@ SW_DEFER = 4        # PT_GLASS_DEFER=1
 SW_NO_NODES = 8     # PT_NODES_LDS=0
 SW_ENV = {SW_NO_CAND: ("PT_CAND_SCAN", "0"), SW_NO_CAND_BVH: ("PT_CAND_BVH", "0"), SW_DEFER: ("PT_GLASS_DEFER", "1"),
           SW_NO_NODES: ("PT_NODES_LDS", "0")}
-
-LAYOUT_SRC = r"""
-#include <cstdio>
-#include <cstdint>
-#include <cstdlib>
-#include <string>
-#include <vector>
-#include "ptrace.h"
-#include "pt_host.h"
-#include "pt_layout.h"
-using namespace pt;
-// argv[1]: scene file (u32 n_objs, u32 n_tris, pt_camera, pt_object[n_objs], pt_triangle[n_tris]); argv[2..]: queries "m,switches".
-// The DevScene counts as pt_ctx_set_scene and cand_scan_for set them; then lds_layout and its three stderr lines per query.
-int main(int argc, char **argv) {
-    FILE *in = fopen(argv[1], "rb");
-    uint32_t n[2];
-    if (!in || fread(n, 4, 2, in) != 2) { printf("FAIL read\n"); return 1; }
-    pt_camera cam;
-    std::vector<pt_object> objs(n[0]);
-    std::vector<pt_triangle> tris(n[1] ? n[1] : 1);
-    if (fread(&cam, sizeof cam, 1, in) != 1 || fread(objs.data(), sizeof(pt_object), n[0], in) != n[0] ||
-        fread(tris.data(), sizeof(pt_triangle), n[1], in) != n[1]) { printf("FAIL read\n"); return 1; }
-    fclose(in);
-    host::FlatScene fs;
-    std::string err;
-    if (!host::flatten_scene(cam, objs.data(), n[0], tris.data(), n[1], fs, err)) { printf("FAIL flatten %s\n", err.c_str()); return 1; }
-    bool glass = false;
-    for (uint32_t i = 0; i < n[0]; ++i) glass = glass || objs[i].reflect_type == PT_REFRACT;
-    for (int a = 2; a < argc; ++a) {
-        unsigned m = 0, sw = 0;
-        if (sscanf(argv[a], "%u,%u", &m, &sw) != 2) { printf("FAIL query\n"); return 1; }
-        DevScene S{};
-        const uint32_t nodes = (uint32_t)fs.bvh_nodes.size();
-        S.n_objs = n[0];
-        S.n_tris = n[1];
-        S.n_cand_pairs = (uint32_t)fs.cand_pairs.size();
-        S.n_bvh_nodes4 = (uint32_t)fs.bvh_nodes4.size();
-        S.n_bvh_nodes = nodes;
-        S.bvh_stack = fs.bvh_stack;
-        const bool ref16 = nodes < 0x8000u && ((uint64_t)fs.bvh_pair_span << kBvhLeafBits) < 0x8000u;
-        S.bvh_in_lds = ref16 ? 2u : 0u;
-        S.nodes_in_lds_ok = (sw & 8u) ? 0u : 1u;
-        S.glass_defer_ok = ((sw & 4u) && glass) ? 1u : 0u;
-        S.cand_scan = (!(sw & 1u) && fs.cand_ok && !(nodes != 0u && (sw & 2u))) ? 1u : 0u;
-        const LdsLayout L = lds_layout(S, m, 0u);
-        printf("Q %u %u %u %u %u %u %u %u %u %u %d %d %d %u %u %zu %d %zu %d %u %u %u %zu\n", S.n_objs, S.n_tris, S.n_cand_pairs,
-               S.n_bvh_nodes, S.n_bvh_nodes4, S.bvh_stack, S.cand_scan, L.pass, L.m, L.bvh_in_lds, (int)L.staged, (int)L.defer,
-               (int)L.nodes_lds, L.surf_staged, L.surf_head, L.pass_lds, (int)L.isect_staged, L.isect_lds, (int)L.mega_cand,
-               L.mega_depth, L.mega_spare_off, L.mega_surf_off, L.mega_lds);
-        for (int w = 0; w < 3; ++w) printf("L%d %s\n", w, lds_layout_line(L, w).c_str());
-    }
-    return 0;
-}
-"""
 Q_FIELDS = ("n_objs", "n_tris", "n_cand_pairs", "n_bvh_nodes", "n_bvh_nodes4", "bvh_stack", "cand_scan", "pass", "m", "bvh_in_lds",
             "staged", "defer", "nodes_lds", "surf_staged", "surf_head", "pass_lds", "isect_staged", "isect_lds", "mega_cand",
             "mega_depth", "mega_spare_off", "mega_surf_off", "mega_lds")
 PASS_PLAIN, PASS_DEFER, PASS_CAND, PASS_CAND_BVH = 0, 1, 2, 3
 
-_helper = None
-
-
-def _layout_helper():
-    global _helper
-    if _helper is None:
-        d = tempfile.mkdtemp(prefix="pt_layouts_")
-        atexit.register(shutil.rmtree, d, True)
-        src = os.path.join(d, "layout.cpp")
-        with open(src, "w") as f:
-            f.write(LAYOUT_SRC)
-        exe = os.path.join(d, "layout")
-        subprocess.check_call(["g++", "-O1", "-std=c++17", "-I", os.path.join(ptlib.PKG, "csrc"), "-I",
-                               os.path.join(ptlib.ROOT, "include"), src, "-o", exe, "-L", ptlib.PKG, "-lptrace_hip",
-                               "-Wl,-rpath," + ptlib.PKG])
-        _helper = exe
-    return _helper
-
 
 def layouts(sc, queries):
-    """lds_layout for scene sc at each (m, switches) of queries: [(dict of the fields, [the three stderr lines])]."""
-    exe = _layout_helper()
-    path = os.path.join(os.path.dirname(exe), "scene.bin")
-    with open(path, "wb") as f:
-        f.write(np.array([sc.n_objs, sc.n_tris], np.uint32).tobytes())
-        f.write(bytes(sc.cam))
-        f.write(bytes(sc.objs)[:sc.n_objs * C.sizeof(ptlib.PtObject)])
-        f.write(bytes(sc.tris)[:sc.n_tris * C.sizeof(ptlib.PtTriangle)])
-    out = subprocess.check_output([exe, path] + ["%d,%d" % q for q in queries]).decode().splitlines()
+    """lds_layout for scene sc at each (m, switches) of queries: [(dict of the fields, [the three stderr lines])].  The generator
+    is the PLAIN build of host/layout_dump.cpp: GPU tests come through here, and no sanitizer build runs on a GPU machine
+    (tests/test_lds_layouts.py holds the sanitized build to the same bytes)."""
+    path = br.write_scene(sc, os.path.join(br.workdir(), "layout_scene.bin"))
+    out = ptlib.host_program("layout_dump", sanitize=False)(path, *["%d,%d" % q for q in queries]).splitlines()
     assert len(out) == 4 * len(queries), out[:3]
     res = []
     for k in range(len(queries)):

@@ -135,6 +135,45 @@ def oracle():
     return L
 
 
+def _make(*words):
+    """make -C PKG <words>; a failure shows the tail of make's output.  Returns the output."""
+    r = subprocess.run(["make", "-C", PKG, "-j4"] + list(words), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900)
+    assert r.returncode == 0, "make %s failed:\n%s" % (" ".join(words), r.stdout[-6000:])
+    return r.stdout
+
+
+def _sanitized(exe):
+    """the program was linked with the AddressSanitizer and UBSan runtimes (make says which flags only when it has to build)"""
+    image = open(exe, "rb").read()
+    return b"__asan_init" in image and b"__ubsan_handle" in image
+
+
+_host_programs = {}
+
+
+def host_program(name, sanitize=True):
+    """host/<name>.cpp built by the Makefile's rule for host programs - at most once per process - under AddressSanitizer and
+    UBSan, or plain (sanitize=False: the two table generators that GPU tests reach, nothing else): tool(*args, input=None) ->
+    what the program writes to stdout; a non-zero exit status raises."""
+    if (name, sanitize) not in _host_programs:
+        _make("host-program", "P=" + name, *([] if sanitize else ["SAN="]))
+        exe = os.path.join(PKG, "build", "host-san" if sanitize else "host-plain", name)
+        assert _sanitized(exe) == sanitize, exe
+        _host_programs[name, sanitize] = exe
+    exe = _host_programs[name, sanitize]
+    return lambda *args, input=None: subprocess.check_output([exe] + [str(a) for a in args], input=input).decode()
+
+
+def host_check(name):
+    """`make <name>-check`: host/<name>_check.cpp (- for _) built under the sanitizers and run; it must exit 0 and close with
+    "<name>_check: ok" (some add counts in brackets).  Returns what make and the program wrote."""
+    prog = name.replace("-", "_") + "_check"
+    out = _make("--no-print-directory", name + "-check")
+    assert (out.splitlines()[-1] + " ").startswith(prog + ": ok "), out[-6000:]
+    assert _sanitized(os.path.join(PKG, "build", "host-san", prog))
+    return out
+
+
 PROGRESS_FN = abi.pt_progress_fn
 
 _product = None

@@ -177,3 +177,14 @@ def test_ray_set_is_a_function_of_the_seed():
         assert bytes(x.scene.tris)[:x.scene.n_tris * 36] == bytes(y.scene.tris)[:y.scene.n_tris * 36]
     assert any(not np.array_equal(x.o, z.o) for x, z in zip(a, c) if x.o.shape == z.o.shape) or \
         any(x.o.shape != z.o.shape for x, z in zip(a, c))
+
+
+def test_tables_dump_is_clean_under_the_sanitizers(tmp_path):
+    """tests/boundary_rays.py asks the plain build of host/tables_dump.cpp (GPU tests come through it); here the build under
+    AddressSanitizer and UBSan runs on the smallest scene of build_scenes: it exits 0, prints what the plain build prints and
+    writes the same bytes."""
+    sc = min((s for _, s in br.build_scenes(SEED)), key=lambda s: s.n_objs + s.n_tris)
+    path = br.write_scene(sc, tmp_path / "scene.bin")
+    said = [ptlib.host_program("tables_dump", sanitize=san)(path, tmp_path / ("tables%d.bin" % san)) for san in (True, False)]
+    assert said[0] == said[1] and said[0].startswith("OK ")
+    assert (tmp_path / "tables1.bin").read_bytes() == (tmp_path / "tables0.bin").read_bytes() != b""

@@ -155,8 +155,5 @@ def test_refusals_without_a_device(L):
 
 
 # ---------------------------------------------------------------------------------------------------------- make camera-check
-def test_camera_check_builds_and_passes(tmp_path):
-    r = subprocess.run(["make", "-C", ptlib.PKG, "camera-check", "B=" + str(tmp_path)], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    assert "camera_check: OK" in r.stdout
-    assert "-fsanitize=address,undefined" in r.stdout and "--cuda-host-only" in r.stdout
+def test_camera_check_builds_and_passes():
+    ptlib.host_check("camera")

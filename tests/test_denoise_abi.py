@@ -143,11 +143,8 @@ def test_invalid_arguments_are_refused_without_a_device():
 
 
 # ---------------------------------------------------------------------------------------------------------- make denoise-check
-def test_denoise_check_builds_and_passes(tmp_path):
-    r = subprocess.run(["make", "-C", ptlib.PKG, "denoise-check", "B=" + str(tmp_path)], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    assert "denoise_check: ok" in r.stdout
-    assert "-fsanitize=address,undefined" in r.stdout and "--cuda-host-only" in r.stdout
+def test_denoise_check_builds_and_passes():
+    ptlib.host_check("denoise")
 
 
 # ------------------------------------------------------------------------------------------- known answers on the rebuild

@@ -1,71 +1,13 @@
 """Host-side pieces of the device layout that can be checked without a GPU: the round-robin deal of pixels to ray
-streams (pt_device.h: stream_pixel / stream_pixel_count / global_pixel) and the bookkeeping word."""
+streams (pt_device.h: stream_pixel / stream_pixel_count / global_pixel) and the bookkeeping word.  The C++ side of each test is a
+program under path-tracer-rust_amd/host/ (ptlib.host_program: built under AddressSanitizer and UBSan)."""
 import os
-import subprocess
-import textwrap
 
 import ptlib
 
-SRC = textwrap.dedent(r"""
-    #include <cstdio>
-    #include <cstdint>
-    #include <vector>
-    #include "pt_device.h"
-    using namespace pt;
-    struct P { uint32_t idx_begin, chunk_pixels, chunk_first, chunk_step, k_begin; };
-    int main() {
-        // 1. every pixel of a call belongs to exactly one (stream, slot); the accumulator slot k_resolve reads back is
-        //    the one k_pass / k_shade wrote
-        const uint32_t cases[][2] = {{1, 1}, {7, 3}, {786432, 16050}, {98304, 16384}, {3072, 1536}, {1000, 999}, {5, 64}};
-        for (auto &c : cases) {
-            const uint32_t npix = c[0], K = c[1];
-            const uint32_t m = (npix + K - 1) / K;
-            std::vector<int> seen(npix, 0);
-            uint64_t total = 0;
-            for (uint32_t b = 0; b < K; ++b) {
-                const uint32_t mb = stream_pixel_count(npix, K, b);
-                if (mb > m) { printf("FAIL count %u %u %u\n", npix, K, b); return 1; }
-                total += mb;
-                for (uint32_t j = 0; j < mb; ++j) {
-                    const uint32_t p = stream_pixel(K, b, j);
-                    if (p >= npix || seen[p]++) { printf("FAIL deal %u %u\n", npix, K); return 1; }
-                    if (p % K != b || p / K != j) { printf("FAIL resolve %u %u\n", npix, K); return 1; }  // k_resolve's inverse
-                }
-            }
-            if (total != npix) { printf("FAIL total %u %u\n", npix, K); return 1; }
-        }
-        // 2. interleaved partition: ranks' global pixels are disjoint and cover the band
-        {
-            const uint32_t W = 37, H = 11, step = 3;
-            std::vector<int> seen(W * H, 0);
-            for (uint32_t r = 0; r < step; ++r) {
-                P f{0, W, r, step};
-                uint32_t owned = 0;
-                for (uint32_t ck = r; ck * W < W * H; ck += step) owned += W;
-                for (uint32_t k = 0; k < owned; ++k) {
-                    const uint32_t g = global_pixel(f, k);
-                    if (g >= W * H || seen[g]++) { printf("FAIL chunks\n"); return 1; }
-                }
-            }
-            for (int v : seen) if (v != 1) { printf("FAIL cover\n"); return 1; }
-        }
-        // 3. the bookkeeping word round-trips at its limits
-        const uint32_t w = pack_word(1023, 32767, 11, 7);
-        if (word_pix(w) != 1023 || word_sample(w) != 32767 || word_depth(w) != 11 || word_branch(w) != 7) { printf("FAIL word\n"); return 1; }
-        printf("OK\n");
-        return 0;
-    }
-""")
 
-
-def test_stream_deal_and_partition(tmp_path):
-    src = tmp_path / "t.cpp"
-    src.write_text(SRC)
-    exe = str(tmp_path / "t")
-    inc = os.path.join(ptlib.PKG, "csrc")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-I", inc, "-I", os.path.join(ptlib.ROOT, "include"), str(src),
-                           "-o", exe])
-    assert subprocess.check_output([exe]).decode().strip() == "OK"
+def test_stream_deal_and_partition():
+    assert ptlib.host_program("stream_deal_check")().strip() == "OK"
 
 
 def test_rust_shim_mirrors_the_header():
@@ -114,124 +56,16 @@ def test_rust_shim_mirrors_the_header():
         assert call + "(" in body, call
     assert "pt_ctx_snapshot(" in rust[rust.index('extern "C" fn on_progress'):rust.index("pub fn render_pixels_hip")]
 
-FLATTEN_SRC = r"""
-#include <cstdio>
-#include <cstdint>
-#include <string>
-#include <vector>
-#include "ptrace.h"
-#include "pt_host.h"
-using namespace pt;
-static int depth_of(const host::FlatScene &fs, int32_t ref, std::vector<int> &leaf_hits, uint32_t pair_lo, uint32_t pair_hi, bool &ok) {
-    if (ref < 0) {
-        const uint32_t code = (uint32_t)~ref, first = leaf_first(code), cnt = leaf_count(code);
-        if (cnt < 1 || cnt > kBvhLeafPairs || first < pair_lo || first + cnt > pair_hi) ok = false;
-        for (uint32_t r = 0; r < cnt && ok; ++r)
-            for (int hf = 0; hf < 2; ++hf)
-                if (fs.tri_pairs[first + r].id[hf] != kNoTri) leaf_hits[fs.tri_pairs[first + r].id[hf]]++;
-        return 0;
-    }
-    const BvhNode &n = fs.bvh_nodes[ref];
-    const int a = depth_of(fs, n.c[0], leaf_hits, pair_lo, pair_hi, ok), b = depth_of(fs, n.c[1], leaf_hits, pair_lo, pair_hi, ok);
-    return 1 + (a > b ? a : b);
-}
-// the four-wide tree below ref4: every leaf reference it holds, and that each of its boxes is a box of the binary tree
-// (the child boxes of some binary node: collected in `bin_boxes` as lo.x of each, a cheap identity)
-static void walk4(const host::FlatScene &fs, int32_t ref4, std::vector<int32_t> &leaves, bool &ok, int depth, int &deepest) {
-    if (ref4 < 0) { leaves.push_back(ref4); return; }
-    if ((size_t)ref4 >= fs.bvh_nodes4.size() || depth > 64) { ok = false; return; }
-    deepest = depth > deepest ? depth : deepest;
-    const BvhNode4 &n = fs.bvh_nodes4[(size_t)ref4];
-    int live = 0;
-    for (int j = 0; j < 4; ++j) {
-        const bool filler = n.lox[j] != n.lox[j];  // NaN
-        if (filler) {
-            // a filler box is NaN in every bound (never hit: pt_device.h) and repeats child 0's reference; fillers come last
-            if (n.hix[j] == n.hix[j] || n.loy[j] == n.loy[j] || n.hiz[j] == n.hiz[j] || n.c[j] != n.c[0] || j < 2) ok = false;
-            continue;
-        }
-        if (live != j) ok = false;
-        ++live;
-        bool found = false;  // the box is one of the binary tree's child boxes, with the same reference kind
-        for (const BvhNode &b : fs.bvh_nodes)
-            for (int h = 0; h < 2; ++h)
-                if (b.lox[h] == n.lox[j] && b.loy[h] == n.loy[j] && b.loz[h] == n.loz[j] && b.hix[h] == n.hix[j] && b.hiy[h] == n.hiy[j] &&
-                    b.hiz[h] == n.hiz[j] && ((b.c[h] < 0) == (n.c[j] < 0)) && (b.c[h] >= 0 || b.c[h] == n.c[j]))
-                    found = true;
-        if (!found) ok = false;
-        walk4(fs, n.c[j], leaves, ok, depth + 1, deepest);
-    }
-}
-static void leaves2(const host::FlatScene &fs, int32_t ref, std::vector<int32_t> &leaves) {
-    if (ref < 0) { leaves.push_back(ref); return; }
-    leaves2(fs, fs.bvh_nodes[(size_t)ref].c[0], leaves);
-    leaves2(fs, fs.bvh_nodes[(size_t)ref].c[1], leaves);
-}
-int main(int argc, char **argv) {
-    pt_scene *sc = nullptr;
-    if (pt_scene_load(argv[1], argv[2], &sc) != 0) { printf("FAIL load %s\n", pt_last_error()); return 1; }
-    uint32_t n_objs, n_tris;
-    const pt_object *objs = pt_scene_objects(sc, &n_objs);
-    const pt_triangle *tris = pt_scene_triangles(sc, &n_tris);
-    host::FlatScene fs;
-    std::string err;
-    if (!host::flatten_scene(*pt_scene_camera(sc), objs, n_objs, tris, n_tris, fs, err)) { printf("FAIL flatten %s\n", err.c_str()); return 1; }
-    // ranks: rank_id and tri_rank are inverse on the triangles; objects from the last to the first
-    if (fs.tri_rank.size() < n_tris) { printf("FAIL tri_rank size\n"); return 1; }
-    for (uint32_t k = 0; k < n_tris; ++k)
-        if (fs.rank_id[fs.tri_rank[k]] != n_objs + k) { printf("FAIL tri_rank %u\n", k); return 1; }
-    // the BVH mesh list: exactly the objects with a BVH, in visiting order
-    size_t q = 0;
-    uint32_t deepest = 0;
-    for (uint32_t v = 0; v < n_objs; ++v) {
-        const ObjRec &r = fs.objs[n_objs - 1u - v];
-        if (r.kind != kKindMesh || r.bvh_root == kNoBvh) continue;
-        if (q >= fs.bvh_meshes.size() || fs.bvh_meshes[q].root != r.bvh_root || fs.bvh_meshes[q].rr != r.rr ||
-            fs.bvh_meshes[q].cx != r.cx) { printf("FAIL bvh_meshes %zu\n", q); return 1; }
-        ++q;
-        // the tree: every triangle of the mesh in exactly one leaf, leaves within the mesh's records, depth within the stack
-        std::vector<int> hits(n_tris, 0);
-        bool ok = true;
-        const int d = depth_of(fs, r.bvh_root, hits, r.pair_begin, r.pair_begin + r.pair_count, ok);
-        if (!ok) { printf("FAIL leaf\n"); return 1; }
-        for (uint32_t k = 0; k < n_tris; ++k)
-            if (hits[k] != ((k >= r.tri_begin && k < r.tri_begin + r.tri_count) ? 1 : 0)) { printf("FAIL cover %u\n", k); return 1; }
-        deepest = (uint32_t)d > deepest ? (uint32_t)d : deepest;
-        // the four-wide form of the same tree (the walk queue's): the same leaves in the same order, each once, every box one
-        // of the binary tree's, at most half as deep (+1)
-        std::vector<int32_t> l2, l4;
-        leaves2(fs, r.bvh_root, l2);
-        int deep4 = 0;
-        walk4(fs, fs.bvh_meshes[q - 1].root4, l4, ok, 1, deep4);
-        if (!ok || l2 != l4 || 2 * deep4 > d + 2) { printf("FAIL four-wide tree %d %zu %zu %d %d\n", (int)ok, l2.size(), l4.size(), deep4, d); return 1; }
-        if (fs.bvh_nodes4.size() * 2 > fs.bvh_nodes.size() + 2) { printf("FAIL four-wide node count %zu %zu\n", fs.bvh_nodes4.size(), fs.bvh_nodes.size()); return 1; }
-    }
-    if (q != fs.bvh_meshes.size()) { printf("FAIL bvh_meshes count\n"); return 1; }
-    if (q != 0 && (fs.bvh_stack < deepest + 1u || fs.bvh_stack > kBvhStack)) { printf("FAIL stack %u %u\n", fs.bvh_stack, deepest); return 1; }
-    // the candidate records are those of the meshes without a BVH
-    size_t want = 0;
-    for (uint32_t i = 0; i < n_objs; ++i)
-        if (fs.objs[i].kind == kKindMesh && fs.objs[i].bvh_root == kNoBvh) want += fs.objs[i].pair_count;
-    if (fs.cand_pairs.size() != want || !fs.cand_ok) { printf("FAIL cand %zu %zu\n", fs.cand_pairs.size(), want); return 1; }
-    printf("OK %zu %u %u\n", fs.bvh_meshes.size(), fs.bvh_stack, deepest);
-    return 0;
-}
-"""
 
-
-def test_flatten_tables_of_the_walk_queue(tmp_path):
+def test_flatten_tables_of_the_walk_queue():
     """flatten_scene's tables for k_pass_cand<.., BVH> on mesh.json and cornell.json: tri_rank inverts rank_id, the BVH mesh
     list holds the meshes with a BVH in visiting order, every triangle of such a mesh sits in exactly one leaf of at most
     kBvhLeafPairs records inside the mesh's record range, the advertised stack depth covers the tree, and the candidate
     records are exactly those of the meshes without a BVH."""
-    src = tmp_path / "f.cpp"
-    src.write_text(FLATTEN_SRC)
-    exe = str(tmp_path / "f")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-I", os.path.join(ptlib.PKG, "csrc"), "-I", os.path.join(ptlib.ROOT, "include"),
-                           str(src), "-o", exe, "-L", ptlib.PKG, "-lptrace_hip", "-Wl,-rpath," + ptlib.PKG])
-    out = subprocess.check_output([exe, ptlib.scene_path("mesh"), ptlib.ROOT]).decode().split()
+    tool = ptlib.host_program("flatten_tables_check")
+    out = tool(ptlib.scene_path("mesh"), ptlib.ROOT).split()
     assert out[0] == "OK" and out[1] == "1" and int(out[2]) > int(out[3]) >= 5  # one BVH mesh; stack deeper than the tree
-    out = subprocess.check_output([exe, ptlib.scene_path("cornell"), ptlib.ROOT]).decode().split()
+    out = tool(ptlib.scene_path("cornell"), ptlib.ROOT).split()
     assert out[:2] == ["OK", "0"]
 
 
@@ -254,183 +88,41 @@ def test_build_flags_are_reported():
     assert sep and all(tok.startswith("-") or tok == "" for part in (general, flat) for tok in part.split(" ")), flags
 
 
-SIGN_SRC = r"""
-#include <cstdio>
-#include <string>
-#include <vector>
-#include "ptrace.h"
-#include "pt_host.h"
-using namespace pt;
-// argv[1] = 0: two quads in the plane z = 1 made of well-shaped triangles; 1: the same plane, but one triangle whose two edge
-// products nearly cancel (a sliver: e1 = (1, 1), e2 = (1, 1.0005)): the plane normal's component is 0.0005 of the products
-int main(int argc, char **argv) {
-    const bool sliver = argv[1][0] == '1';
-    pt_camera cam = {{0, 0, 5}, {0, 0, -1}, 0.035f, 0.036f, 1.5f};
-    std::vector<pt_triangle> tris;
-    tris.push_back({{0, 0, 1}, {1, 0, 1}, {0, 1, 1}});
-    tris.push_back({{1, 0, 1}, {1, 1, 1}, {0, 1, 1}});
-    if (sliver) tris[1] = {{0, 0, 1}, {1, 1, 1}, {1, 1.0005f, 1}};
-    pt_object o{};
-    o.kind = PT_MESH;
-    o.tri_count = 2;
-    o.bs_radius = 100.0f;
-    host::FlatScene fs;
-    std::string err;
-    if (!host::flatten_scene(cam, &o, 1, tris.data(), 2, fs, err)) { printf("FAIL %s\n", err.c_str()); return 1; }
-    if (fs.flat_pairs.size() != 1) { printf("FAIL flat_pairs %zu\n", fs.flat_pairs.size()); return 1; }
-    printf("OK axis %u sign_exact %u\n", fs.flat_pairs[0].axis, fs.flat_pairs[0].sign_exact);
-    return 0;
-}
-"""
-
-
-def test_flat_filter_sign_rule_needs_well_shaped_triangles(tmp_path):
+def test_flat_filter_sign_rule_needs_well_shaped_triangles():
     """FlatPairRec.sign_exact (filter_flat drops rays that do not move towards the plane: the sign of Triangle::intersect's
     distance is then known exactly) is only set when the two edge products whose difference is the plane normal do not
     nearly cancel; a sliver keeps the conservative distance test.  cornell.json's walls all qualify."""
-    src = tmp_path / "s.cpp"
-    src.write_text(SIGN_SRC)
-    exe = str(tmp_path / "s")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-I", os.path.join(ptlib.PKG, "csrc"), "-I", os.path.join(ptlib.ROOT, "include"),
-                           str(src), "-o", exe, "-L", ptlib.PKG, "-lptrace_hip", "-Wl,-rpath," + ptlib.PKG])
-    assert subprocess.check_output([exe, "0"]).decode().split() == ["OK", "axis", "2", "sign_exact", "1"]
-    assert subprocess.check_output([exe, "1"]).decode().split() == ["OK", "axis", "2", "sign_exact", "0"]
+    tool = ptlib.host_program("sign_rule_probe")
+    assert tool("0").split() == ["OK", "axis", "2", "sign_exact", "1"]
+    assert tool("1").split() == ["OK", "axis", "2", "sign_exact", "0"]
 
 
-DOOR_SRC = r"""
-#include <cmath>
-#include <cstdio>
-#include <string>
-#include <vector>
-#include "ptrace.h"
-#include "pt_host.h"
-using namespace pt;
-// a sphere and a two-triangle mesh; each colour and emission component of each object in turn set to a value the door must
-// refuse (the message names the object and the field) or must let through
-int main() {
-    pt_camera cam = {{0, 0, 5}, {0, 0, -1}, 0.035f, 0.036f, 1.5f};
-    std::vector<pt_triangle> tris = {{{0, 0, 1}, {1, 0, 1}, {0, 1, 1}}, {{1, 0, 1}, {1, 1, 1}, {0, 1, 1}}};
-    pt_object objs[2] = {};
-    objs[0].kind = PT_SPHERE, objs[0].radius = 1.0f, objs[0].position[2] = -3.0f;
-    objs[1].kind = PT_MESH, objs[1].tri_count = 2, objs[1].bs_radius = 100.0f;
-    for (pt_object &o : objs) o.color[0] = 0.75f, o.color[1] = 0.5f, o.color[2] = 0.25f, o.emission[1] = 12.0f;
-    host::FlatScene fs;
-    std::string err;
-    if (!host::flatten_scene(cam, objs, 2, tris.data(), 2, fs, err)) { printf("FAIL clean scene: %s\n", err.c_str()); return 1; }
-    const float bad[] = {-1.0f, -1e-45f, NAN, INFINITY, -INFINITY}, fine[] = {-0.0f, 0.0f, 1e-45f, 4294967296.0f, 3e38f};
-    int refusals = 0;
-    for (int i = 0; i < 2; ++i)
-        for (int k = 0; k < 6; ++k) {
-            float *f = k < 3 ? &objs[i].color[k] : &objs[i].emission[k - 3];
-            const float keep = *f;
-            const std::string want = "object " + std::to_string(i) + ": a component of " + (k < 3 ? "color" : "emission") +
-                                     " is negative or not finite";
-            for (float v : bad) {
-                *f = v;
-                err.clear();
-                if (host::flatten_scene(cam, objs, 2, tris.data(), 2, fs, err) || err != want) {
-                    printf("FAIL object %d field %d value %g: `%s`\n", i, k, v, err.c_str());
-                    return 1;
-                }
-                if (host::bad_material(objs[i]) == nullptr) { printf("FAIL bad_material %d %d %g\n", i, k, v); return 1; }
-                ++refusals;
-            }
-            for (float v : fine) {
-                *f = v;
-                if (!host::flatten_scene(cam, objs, 2, tris.data(), 2, fs, err)) { printf("FAIL refused %g: %s\n", v, err.c_str()); return 1; }
-            }
-            *f = keep;
-        }
-    printf("OK %d\n", refusals);
-    return 0;
-}
-"""
-
-
-def test_the_door_refuses_negative_and_non_finite_materials(tmp_path):
+def test_the_door_refuses_negative_and_non_finite_materials():
     """flatten_scene - what pt_ctx_set_scene, and through it pt_render and pt_render_multi, build a scene with - refuses a colour
     or emission component that is negative, NaN or infinite, naming the object and the field, and lets -0.0f, denormals and
     large finite values through: to_fixed (csrc/pt_device.h) is defined for finite values >= 0 only.  pt_ctx_set_object's
     refusals (check_object_edit) are in host/object_check.cpp."""
     import re
-    src = tmp_path / "door.cpp"
-    src.write_text(DOOR_SRC)
-    exe = str(tmp_path / "door")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-I", os.path.join(ptlib.PKG, "csrc"), "-I", os.path.join(ptlib.ROOT, "include"),
-                           str(src), "-o", exe, "-L", ptlib.PKG, "-lptrace_hip", "-Wl,-rpath," + ptlib.PKG])
-    assert subprocess.check_output([exe]).decode().split() == ["OK", "60"]
+    assert ptlib.host_program("door_check")().split() == ["OK", "60"]
     h = open(os.path.join(ptlib.ROOT, "include", "ptrace.h")).read()
     assert "a component of color or emission that is negative or not finite" in re.sub(r"\s*\n \* ", " ", h)
     assert "SATURATES at 4294967040" in h and "WRAPS at 2^32 radiance units" in h
 
 
-PLAN_SRC = r"""
-#include <cstdio>
-#include <cstdlib>
-#include "ptrace.h"
-#include "pt_host.h"
-using namespace pt;
-// argv: npix spp want default(0/1) stack_form stack_park cand_scan has_bvh streams per_stream wave_stack n_cus budget groups_per_cu
-// prints OK spp_pass m K cap bytes0 bytes1 retries.  groups_per_cu by hand: plan_pass itself, once (RETRY: it asks for a smaller pass);
-// groups_per_cu 0: the library's, through host::plan_frame, which follows plan_pass's retries (no taper)
-int main(int argc, char **argv) {
-    if (argc != 15) return 2;
-    host::PassPlanIn in;
-    in.npix = strtoull(argv[1], 0, 10);
-    in.spp = (uint32_t)strtoul(argv[2], 0, 10);
-    in.want = strtoull(argv[3], 0, 10);
-    in.want_is_default = argv[4][0] == '1';
-    in.stack_form = argv[5][0] == '1';
-    in.stack_park = argv[6][0] == '1';
-    in.cand_scan = argv[7][0] == '1';
-    in.has_bvh = argv[8][0] == '1';
-    in.streams = strtoull(argv[9], 0, 10);
-    in.per_stream = (uint32_t)strtoul(argv[10], 0, 10);
-    in.wave_stack = (uint32_t)strtoul(argv[11], 0, 10);
-    in.n_cus = (uint32_t)strtoul(argv[12], 0, 10);
-    in.stack_budget = (size_t)strtoull(argv[13], 0, 10);
-    in.groups_per_cu = (uint32_t)strtoul(argv[14], 0, 10);
-    host::FramePlan f;
-    int rc;
-    if (in.groups_per_cu) {
-        uint64_t next = in.want;
-        rc = host::plan_pass(in, f.pass, &next);
-    } else {
-        host::FramePlanIn fin;
-        fin.pass = in;
-        fin.rays_per_pass = in.want_is_default ? 0u : in.want;
-        host::FrameRequest req;
-        req.want = in.want;
-        req.stack_budget = in.stack_budget;
-        rc = host::plan_frame(fin, req, f);
-    }
-    if (rc == host::kPlanTooLarge) { printf("TOOLARGE\n"); return 0; }
-    if (rc == host::kPlanRetry) { printf("RETRY\n"); return 0; }
-    printf("OK %u %u %u %u %zu %zu %d\n", f.pass.spp_pass, f.pass.m, f.pass.K, f.pass.cap, f.pass.bytes0, f.pass.bytes1, f.retries);
-    return 0;
-}
-"""
-
-
-def test_pass_plan(tmp_path):
+def test_pass_plan():
     """host::plan_pass - how a wavefront frame is cut into passes and streams; host::plan_frame follows its retries - on the CPU:
     the bench frame (six passes of 683 samples, stacks of 1024 slots per wave, nothing in the second container), mesh.json (parking areas), a frame of few
     samples (at most 64 pixels per stream), the memory budget (passes halved until the stacks fit), small stacks on request,
     tiny passes (smaller stacks), the level-by-level forms (slices of 4 slots per primary ray, two containers), and a pass
     that 32-bit slot indices cannot hold."""
-    src = tmp_path / "p.cpp"
-    src.write_text(PLAN_SRC)
-    exe = str(tmp_path / "p")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-I", os.path.join(ptlib.PKG, "csrc"), "-I", os.path.join(ptlib.ROOT, "include"),
-                           str(src), "-o", exe, "-L", ptlib.PKG, "-lptrace_hip", "-Wl,-rpath," + ptlib.PKG])
+    tool = ptlib.host_program("pass_plan_probe")
 
     def plan(npix, spp, want, default=1, stack=1, park=0, cand=1, bvh=0, streams=0, per_stream=0, wave_stack=0, n_cus=256, budget=0, groups=None,
              follow=False):
         # workgroups a CU holds, by hand: five for k_pass_cand without walks (its waves per SIMD when these figures were pinned).
         # follow: through host::plan_frame, which derives them and follows plan_pass's retries
         groups = 0 if follow else groups or (4 if bvh or not stack else 5)
-        out = subprocess.check_output([exe] + [str(v) for v in (npix, spp, want, default, stack, park, cand, bvh, streams, per_stream,
-                                                                wave_stack, n_cus, budget, groups)]).decode().split()
+        out = tool(npix, spp, want, default, stack, park, cand, bvh, streams, per_stream, wave_stack, n_cus, budget, groups).split()
         if out[0] != "OK":
             return out[0]
         spp_pass, m, K, cap, b0, b1, retries = map(int, out[1:])
@@ -466,65 +158,10 @@ def test_pass_plan(tmp_path):
     assert retries >= 1 and K * cap <= 0x7fffffff
 
 
-PASS_SRC = r"""
-#include <cstdio>
-#include <cstdint>
-#include "pt_host.h"
-using namespace pt;
-int main() {
-    const uint64_t npix = 1024u * 768u, probe = 1u << 20;
-    // nothing measured yet: the probe (1 Mi primary rays = one sample per pixel of this frame)
-    if (host::next_pass_samples(0.0, 100.0, npix, probe, 0, 4096, 683) != 1) { printf("FAIL probe\n"); return 1; }
-    // a tiny frame's probe is never less than one sample
-    if (host::next_pass_samples(0.0, 100.0, 4096u * 4096u, probe, 0, 100, 32) != 1) { printf("FAIL probe floor\n"); return 1; }
-    // a measured rate is followed, but a pass grows at most sixteen-fold (short passes measure overheads), plus the fifth by which a
-    // pass may be stretched: 19 after 1, 292 after 16
-    const double rate = 5.5e6;  // primary samples per ms: cornell.json on an MI355X
-    if (host::next_pass_samples(rate, 100.0, npix, probe, 1, 4095, 683) != 19) { printf("FAIL growth\n"); return 1; }
-    if (host::next_pass_samples(rate, 100.0, npix, probe, 16, 4079, 683) != 292) { printf("FAIL growth 2 %u\n", host::next_pass_samples(rate, 100.0, npix, probe, 16, 4079, 683)); return 1; }
-    // steady state: 699 samples would fit 100 ms, the plan allows 683: the bench frame is six equal passes of 683
-    if (host::next_pass_samples(rate, 100.0, npix, probe, 683, 4096, 683) != 683) { printf("FAIL steady\n"); return 1; }
-    // equal passes over what is left, each at most a fifth longer than the target rather than one pass more:
-    // mesh.json's rate fits 448 samples into 100 ms; 1024 left -> two passes of 512 (114 ms), not three of 342
-    if (host::next_pass_samples(3.52e6, 100.0, npix, probe, 512, 1024, 683) != 512) { printf("FAIL stretch\n"); return 1; }
-    if (host::next_pass_samples(3.52e6, 100.0, npix, probe, 512, 1100, 683) != 367) { printf("FAIL equal %u\n", host::next_pass_samples(3.52e6, 100.0, npix, probe, 512, 1100, 683)); return 1; }
-    // a scene fifty times dearer: passes of a tenth of a second are a handful of samples; never zero, never beyond what is left
-    if (host::next_pass_samples(rate / 50.0, 100.0, npix, probe, 8, 10000, 683) != 15) { printf("FAIL dear %u\n", host::next_pass_samples(rate / 50.0, 100.0, npix, probe, 8, 10000, 683)); return 1; }
-    if (host::next_pass_samples(1.0, 100.0, npix, probe, 1, 3, 683) != 1) { printf("FAIL floor\n"); return 1; }
-    if (host::next_pass_samples(rate, 100.0, npix, probe, 683, 5, 683) != 5) { printf("FAIL left\n"); return 1; }
-    printf("OK\n");
-    return 0;
-}
-"""
-
-
-def test_pass_length_follows_the_measured_rate(tmp_path):
+def test_pass_length_follows_the_measured_rate():
     """host::next_pass_samples (render_wavefront / render_mega): the probe, the sixteen-fold growth limit, the plan's cap, equal
     passes stretched by at most a fifth, floors - the arithmetic behind "a cancel comes back within a tenth of a second"."""
-    src = tmp_path / "p.cpp"
-    src.write_text(PASS_SRC)
-    exe = str(tmp_path / "p")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-I", os.path.join(ptlib.PKG, "csrc"), "-I", os.path.join(ptlib.ROOT, "include"),
-                           str(src), "-o", exe, "-L", ptlib.PKG, "-lptrace_hip", "-Wl,-rpath," + ptlib.PKG])
-    assert subprocess.check_output([exe]).decode().strip() == "OK"
-
-
-def _host_tool(tmp_path, name, source):
-    """a small g++ program over csrc/pt_host.h, linked against the library"""
-    src = tmp_path / (name + ".cpp")
-    src.write_text(source)
-    exe = str(tmp_path / name)
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-I", os.path.join(ptlib.PKG, "csrc"), "-I", os.path.join(ptlib.ROOT, "include"),
-                           str(src), "-o", exe, "-L", ptlib.PKG, "-lptrace_hip", "-Wl,-rpath," + ptlib.PKG])
-    return lambda *args: subprocess.check_output([exe] + [str(a) for a in args]).decode()
-
-
-def ckpt_check_tool(tmp_path):
-    """host/ckpt_check.cpp built by `make ckpt-check` (AddressSanitizer and UBSan; its own run must pass): ckpt_check ARGS' output"""
-    r = subprocess.run(["make", "-C", ptlib.PKG, "ckpt-check", "B=%s" % tmp_path], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "ckpt_check: ok" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
-    exe = str(tmp_path / "ckpt_check")
-    return lambda *args: subprocess.check_output([exe] + [str(a) for a in args]).decode()
+    assert ptlib.host_program("pass_length_check")().strip() == "OK"
 
 
 def _checkpoint(L, key, fp, total, part_px, counts, n_a, sums, a, version=None, seal=True):
@@ -546,7 +183,8 @@ def test_checkpoint_codec(tmp_path):
     reason, in the loader's order."""
     import numpy as np
     L = ptlib.product()
-    tool = ckpt_check_tool(tmp_path)
+    ptlib.host_check("ckpt")  # its own run must pass
+    tool = ptlib.host_program("ckpt_check")
 
     def run(data, *n):
         p = tmp_path / "c.ptacc"
@@ -614,53 +252,13 @@ def test_checkpoint_codec(tmp_path):
     assert run(bytes(bad_hash_and_count)) == "BAD bad trailing hash"
 
 
-SCHED_SRC = r"""
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
-#include "ptrace.h"
-#include "pt_host.h"
-using namespace pt;
-// argv: spp megakernel total n_parts cnt.. [na..]: the jobs of one pt_ctx_accumulate call that is not cancelled, in order, with the
-// half each goes to, the counts following as keep_job moves them (pt_api.hip); then the counts at the end
-int main(int argc, char **argv) {
-    const uint32_t spp = (uint32_t)atoi(argv[1]);
-    const bool mega = atoi(argv[2]) != 0;
-    host::FrameCounts f;
-    f.total = (uint32_t)atoi(argv[3]);
-    f.part_px = host::part_pixels(f.total, true);
-    const int n_parts = atoi(argv[4]);
-    if ((uint32_t)n_parts != host::part_count(f.total, f.part_px)) return 2;
-    for (int i = 0; i < n_parts; ++i) f.cnt.push_back((uint32_t)atoi(argv[5 + i]));
-    for (int i = 5 + n_parts; i < argc; ++i) f.na.push_back((uint32_t)atoi(argv[i]));
-    for (const host::Job &j : host::accum_jobs(f, spp, mega)) {
-        const uint32_t end = j.s_end ? j.s_end : spp;
-        if (j.s_first >= end) continue;  // run_frame_call: nothing left to trace here
-        const bool to_a = f.tracked() && host::deal_to_a(f.cnt[j.part_lo], f.na[j.part_lo]);
-        printf("job %u %u %u %u %d %u %u %.9g %.9g %.9g\n", j.k0, j.n, j.s_first, end, (int)to_a, j.part_lo, j.part_hi, j.base, j.scale,
-               j.boundary);
-        for (uint32_t i = j.part_lo; i < j.part_hi; ++i) {
-            if (to_a) f.na[i] += end - j.s_first;
-            f.cnt[i] = end;
-        }
-    }
-    printf("cnt");
-    for (uint32_t v : f.cnt) printf(" %u", v);
-    printf(" na");
-    for (uint32_t v : f.na) printf(" %u", v);
-    printf("\n");
-    return 0;
-}
-"""
-
-
-def test_accumulate_schedule_is_the_deal(tmp_path):
+def test_accumulate_schedule_is_the_deal():
     """host::accum_jobs and host::deal_to_a - what pt_ctx_accumulate renders and which half keep_job gives it to - against
     deal(), the header's rule as tests/test_gpu_noise.py restates it: the issue's sequence 0 -> 8 -> 24 -> 64, a part already at
     the target, an untracked frame, parts of 2^20 pixels, and the megakernel's whole-call job only when every part is even."""
     import numpy as np
     from test_gpu_noise import deal
-    tool = _host_tool(tmp_path, "sched", SCHED_SRC)
+    tool = ptlib.host_program("accum_schedule_probe")
     f32 = np.float32
 
     def call(spp, mega, total, cnt, na=None):
@@ -712,49 +310,12 @@ def test_accumulate_schedule_is_the_deal(tmp_path):
         assert cnt2 == [24, 24] and na2 == ([deal(c, a, 24)[1] for c, a in zip(cnt, na)] if na else [])
 
 
-NOISE_SRC = r"""
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include "ptrace.h"
-#include "pt_host.h"
-using namespace pt;
-// argv: pixels stats.mean_error target.mean_error target.quantile target.quantile_error [bin count]..: the quantile bin, the bits of
-// its upper edge, whether the target is met
-int main(int argc, char **argv) {
-    if (argv[1][0] == 'w') {  // w nA nB ..: the bits of a part's weight, pair by pair
-        for (int i = 2; i + 1 < argc; i += 2) {
-            const float w = host::noise_part_weight((uint32_t)atoi(argv[i]), (uint32_t)atoi(argv[i + 1]));
-            uint32_t bits;
-            memcpy(&bits, &w, 4);
-            printf("%u\n", bits);
-        }
-        return 0;
-    }
-    pt_noise_stats s{};
-    s.pixels = strtoull(argv[1], 0, 10);
-    s.mean_error = atof(argv[2]);
-    pt_noise_target t{};
-    t.mean_error = (float)atof(argv[3]);
-    t.quantile = (float)atof(argv[4]);
-    t.quantile_error = (float)atof(argv[5]);
-    for (int i = 6; i + 1 < argc; i += 2) s.histogram[atoi(argv[i])] = (uint32_t)atoi(argv[i + 1]);
-    const uint32_t b = host::noise_quantile_bin(s, t.quantile);
-    const float up = host::noise_bin_upper(b);
-    uint32_t bits;
-    memcpy(&bits, &up, 4);
-    printf("%u %u %d\n", b, bits, (int)host::noise_target_met(s, t));
-    return 0;
-}
-"""
-
-
-def test_noise_target_decision(tmp_path):
+def test_noise_target_decision():
     """host::noise_quantile_bin / noise_bin_upper / noise_target_met / noise_part_weight - pt_ctx_accumulate_until's decision
     and pt_ctx_accum_noise's weights - on hand-made histograms, against tests/noise_ref.py's restatement of the header."""
     import numpy as np
     import noise_ref
-    tool = _host_tool(tmp_path, "noise", NOISE_SRC)
+    tool = ptlib.host_program("noise_target_probe")
     bits = lambda v: int(np.array([v], dtype=np.float32).view(np.uint32)[0])
 
     def ask(pixels, hist, mean=0.0, t_mean=0.0, q=0.0, q_err=0.0):
@@ -797,84 +358,11 @@ def test_noise_target_decision(tmp_path):
     assert got == [bits(noise_ref.weight(a, b)) for a, b in pairs]
 
 
-SCHEDULE_SRC = r"""
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-#include "ptrace.h"
-#include "pt_host.h"
-using namespace pt;
-static uint64_t num(const char *s) { return strtoull(s, 0, 0); }
-// argv[1] names the function, the rest are its arguments in order; prints its results (a refusal: REFUSED and the message)
-int main(int argc, char **argv) {
-    const char *f = argv[1];
-    auto arg = [&](int i) { return num(argv[1 + i]); };
-    if (!strcmp(f, "rounds")) {  // entries spp_left rays_per_pass item_mult n_cus s_here..: the plan, then each launch
-        const host::RoundPlan p = host::plan_rounds(arg(1), (uint32_t)arg(2), arg(3), (uint32_t)arg(4), (uint32_t)arg(5));
-        printf("%u %u", p.round_spp, p.n_split);
-        for (int i = 6; 1 + i < argc; ++i) {
-            const host::RoundLaunch l = host::round_launch(arg(1), p.n_split, (uint32_t)arg(i), (uint32_t)arg(5));
-            printf(" %u %u %u", l.split, l.lane_spp, l.grid);
-        }
-        printf("\n");
-    } else if (!strcmp(f, "launch")) {  // entries n_split s_here n_cus
-        const host::RoundLaunch l = host::round_launch(arg(1), (uint32_t)arg(2), (uint32_t)arg(3), (uint32_t)arg(4));
-        printf("%u %u %u\n", l.split, l.lane_spp, l.grid);
-    } else if (!strcmp(f, "split")) {  // c T
-        printf("%u\n", host::tracked_split((uint32_t)arg(1), (uint32_t)arg(2)));
-    } else if (!strcmp(f, "adaptive") || !strcmp(f, "until")) {  // [held] min_spp cap: the counts up to the cap
-        const bool ad = f[0] == 'a';
-        const uint32_t cap = (uint32_t)arg(ad ? 2 : 3);
-        uint32_t t = ad ? host::adaptive_first_level((uint32_t)arg(1), cap) : host::until_first_target((uint32_t)arg(1), (uint32_t)arg(2), cap);
-        for (int i = 0; i < 40; ++i, t = host::next_target(t, cap)) {
-            printf("%u ", t);
-            if (t >= cap) break;
-        }
-        printf("\n");
-    } else if (!strcmp(f, "params")) {  // tile_error tile
-        pt_adaptive_params p{(float)atof(argv[2]), (uint32_t)arg(2), 0u};
-        uint32_t shift = 99;
-        if (host::check_adaptive_params(p, &shift)) printf("REFUSED %s\n", pt_last_error());
-        else printf("%u\n", shift);
-    } else if (!strcmp(f, "cfg")) {  // width idx_begin idx_end chunk_step flags
-        pt_config c{};
-        c.width = (uint32_t)arg(1), c.idx_begin = (uint32_t)arg(2), c.idx_end = (uint32_t)arg(3), c.chunk_step = (uint32_t)arg(4), c.flags = (uint32_t)arg(5);
-        if (host::check_adaptive_cfg(c)) printf("REFUSED %s\n", pt_last_error());
-        else printf("OK\n");
-    } else if (!strcmp(f, "target")) {  // mean_error quantile quantile_error
-        pt_noise_target t{(float)atof(argv[2]), (float)atof(argv[3]), (float)atof(argv[4]), 0u};
-        if (host::check_noise_target(t)) printf("REFUSED %s\n", pt_last_error());
-        else printf("OK\n");
-    } else if (!strcmp(f, "tiles")) {  // width rows tile_shift [err_sum (spp err)..]: err "-" = no error yet
-        host::TileGeometry g{};
-        if (host::tile_geometry((uint32_t)arg(1), (uint32_t)arg(2), (uint32_t)arg(3), g)) { printf("REFUSED %s\n", pt_last_error()); return 0; }
-        printf("%u %u %u", g.tile_shift, g.tiles_x, g.tiles);
-        if (argc > 5) {
-            std::vector<uint32_t> spp;
-            std::vector<unsigned long long> err;
-            for (int i = 5; 1 + i + 1 < argc; i += 2) {
-                spp.push_back((uint32_t)arg(i));
-                err.push_back(argv[1 + i + 1][0] == '-' ? kTileNoError : arg(i + 1));
-            }
-            if (spp.size() != g.tiles) return 2;
-            const host::TileTotals t = host::tile_totals((uint32_t)arg(1), (uint32_t)arg(2), g, spp.data(), err.data(), arg(4));
-            printf(" %llu %llu %.17g", (unsigned long long)t.samples, (unsigned long long)t.est_pixels, t.mean_error);
-        }
-        printf("\n");
-    } else {
-        return 2;
-    }
-    return 0;
-}
-"""
-
-
-def test_rounds_schedules_and_tiles(tmp_path):
+def test_rounds_schedules_and_tiles():
     """The host arithmetic of the megakernel's and the tile pass's rounds (host::plan_rounds / round_launch), the sample schedules
     of the calls that render to a noise target (tracked_split, next_target and the two first counts), and pt_ctx_render_adaptive's
     refusals, tile geometry and totals - on values worked by hand from their definitions."""
-    tool = _host_tool(tmp_path, "schedule", SCHEDULE_SRC)
+    tool = ptlib.host_program("rounds_probe")
     ask = lambda *a: tool(*a).strip()
     nums = lambda *a: [int(v) for v in ask(*a).split()]
     # the bench frame on 256 CUs: 256 Mi / 786432 = 341 samples per round; 8 x 256 x 2048 items are wanted, 786432 x 8 reaches
@@ -897,7 +385,7 @@ def test_rounds_schedules_and_tiles(tmp_path):
                     (0, 1 << 24, 1 << 23), (0, 0xffffffff, 0x80000000), (0xfffffff0, 0xffffffff, 0xfffffff8)):
         assert nums("split", c, t) == [m], (c, t)
     # accum_jobs cuts a tracked part at exactly this value
-    sched = _host_tool(tmp_path, "sched", SCHED_SRC)
+    sched = ptlib.host_program("accum_schedule_probe")
     for c, na, t in ((0, 0, 16), (16, 8, 32), (64, 32, 100), (0, 0, 10), (0, 0, 3)):
         jobs = [ln.split() for ln in sched(t, 0, 96 * 64, 1, c, na).strip().split("\n")[:-1]]
         m = nums("split", c, t)[0]

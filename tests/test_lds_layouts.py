@@ -101,3 +101,12 @@ def test_coverage_of_the_existing_suite(capsys):
         for k in ll.LADDER_KINDS:
             print("%-40s %-14s %s" % (k, "yes" if k in old else "no", "yes" if k in new else "no"))
     assert set(ll.LADDER_KINDS) <= new
+
+
+def test_layout_dump_is_clean_under_the_sanitizers(tmp_path):
+    """tests/lds_layouts.py asks the plain build of host/layout_dump.cpp (GPU tests come through it); here the build under
+    AddressSanitizer and UBSan runs on one scene with two queries: it exits 0 and prints the plain build's bytes."""
+    path = br.write_scene(ll._cornell(), tmp_path / "scene.bin")
+    args = (path, "1,0", "64,%d" % ll.SW_DEFER)
+    clean = ptlib.host_program("layout_dump")(*args)
+    assert clean == ptlib.host_program("layout_dump", sanitize=False)(*args) and clean.count("\n") == 8

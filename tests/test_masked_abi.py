@@ -193,8 +193,5 @@ def test_the_gpu_tests_planes_hold_every_kind_of_value(size):
 
 
 # -------------------------------------------------------------------------------------------- the stand-alone program
-def test_select_check_builds_and_passes(tmp_path):
-    r = subprocess.run(["make", "-C", ptlib.PKG, "select-check", "B=" + str(tmp_path)], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    assert "select_check: ok" in r.stdout
-    assert "-fsanitize=address,undefined" in r.stdout and "--cuda-host-only" in r.stdout
+def test_select_check_builds_and_passes():
+    ptlib.host_check("select")

@@ -335,10 +335,8 @@ def test_moved_projection_lands_on_the_old_point(L):
 
 
 # ------------------------------------------------------------------------------------------- the stand-alone program
-def test_make_reproject_moved_check(tmp_path):
+def test_make_reproject_moved_check():
     """the host side - pt_object_motion_between, the mapped projection, the table's refusals, and the moved pixel with its record
     reads, taps and window over buffers of the exact size - under AddressSanitizer and UBSan, as a program of its own: no device,
     nothing loaded into this process"""
-    r = subprocess.run(["make", "-C", ptlib.PKG, "reproject-moved-check", "B=%s" % tmp_path], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    assert "reproject_moved_check: ok" in r.stdout
+    ptlib.host_check("reproject-moved")

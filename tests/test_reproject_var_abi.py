@@ -409,9 +409,7 @@ def test_documents_quote_the_timing_profile():
 
 
 # ------------------------------------------------------------------------------------------- the stand-alone program
-def test_make_reproject_var_check(tmp_path):
+def test_make_reproject_var_check():
     """the host side - refusals, projection, gather with moments, spatial window - over buffers of the exact size under
     AddressSanitizer and UBSan, as a program of its own: no device, nothing loaded into this process"""
-    r = subprocess.run(["make", "-C", ptlib.PKG, "reproject-var-check", "B=%s" % tmp_path], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    assert "reproject_var_check: ok" in r.stdout
+    ptlib.host_check("reproject-var")

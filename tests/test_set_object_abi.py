@@ -110,8 +110,5 @@ def test_one_statement_of_the_triangle_arithmetic_and_a_unit_of_its_own():
     assert "pt_refit" not in open(os.path.join(pkg, "csrc", "pt_device.h")).read()
 
 
-def test_object_check_builds_and_passes(tmp_path):
-    r = subprocess.run(["make", "-C", ptlib.PKG, "object-check", "B=" + str(tmp_path)], capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    assert "object_check: OK" in r.stdout
-    assert "-fsanitize=address,undefined" in r.stdout and "--cuda-host-only" in r.stdout
+def test_object_check_builds_and_passes():
+    ptlib.host_check("object")

@@ -10,53 +10,23 @@ what lds_layout decides is asked of the header itself through tests/lds_layouts.
   existed (tests/golden/wait_rows_parent_layouts.json, written from the header of the commit before)."""
 import json
 import os
-import subprocess
 
 import pytest
 
 import lds_layouts
 import ptlib
 
-BUDGET_SRC = r"""
-#include <cstdio>
-#include "ptrace.h"
-#include "pt_host.h"
-#include "pt_layout.h"
-using namespace pt;
-// the budget per workgroup without and with walks, the waves per SIMD, the bytes of the rows, and the bench pass's stream length
-int main() {
-    host::FramePlanIn in;
-    in.pass.npix = 1024u * 768u;
-    in.pass.spp = 4096;
-    in.pass.stack_form = true;
-    in.pass.cand_scan = true;
-    in.pass.n_cus = 256;
-    host::FrameRequest req;
-    req.want = 512ull << 20;
-    host::FramePlan f;
-    if (host::plan_frame(in, req, f) != host::kPlanOk || f.retries != 0) return 1;
-    const host::PassPlan &p = f.pass;
-    printf("%zu %zu %d %zu %zu %u %u\n", pass_cand_lds_budget(false), pass_cand_lds_budget(true), (int)PT_CAND_WAVES,
-           pass_lds_wait_bytes(false), pass_lds_wait_bytes(true), p.m, p.K);
-    return 0;
-}
-"""
 FIELDS = ("isect_staged", "isect_lds", "mega_cand", "mega_depth", "mega_spare_off", "mega_surf_off", "mega_lds")
 
 
-@pytest.fixture(scope="module")
-def header(tmp_path_factory):
-    d = tmp_path_factory.mktemp("wait_rows_layout")
-    src = d / "b.cpp"
-    src.write_text(BUDGET_SRC)
-    exe = str(d / "b")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-I", os.path.join(ptlib.PKG, "csrc"), "-I", os.path.join(ptlib.ROOT, "include"),
-                           str(src), "-o", exe, "-L", ptlib.PKG, "-lptrace_hip", "-Wl,-rpath," + ptlib.PKG])
-    v = [int(x) for x in subprocess.check_output([exe]).decode().split()]
+def read_header():
+    """what host/wait_rows_probe.cpp reads from the header"""
+    v = [int(x) for x in ptlib.host_program("wait_rows_probe")().split()]
     return dict(zip(("budget", "budget_bvh", "waves", "rows", "rows_bvh", "bench_m", "bench_k"), v))
 
 
-def test_cornell_stays_staged_within_the_budget(header):
+def test_cornell_stays_staged_within_the_budget():
+    header = read_header()
     assert header["waves"] == 6 and header["rows"] == 256 * 16 and header["rows_bvh"] == 0
     assert header["budget"] * 6 <= 160 * 1024 and header["budget_bvh"] * 4 <= 160 * 1024
     resident = 256 * header["waves"]
@@ -74,7 +44,8 @@ def test_cornell_stays_staged_within_the_budget(header):
     assert a["pass_lds"] >= 4 * 4480 + header["rows"] and b["pass_lds"] > a["pass_lds"]
 
 
-def test_walks_have_no_rows_and_stay_within_their_budget(header):
+def test_walks_have_no_rows_and_stay_within_their_budget():
+    header = read_header()
     sc = ptlib.load_scene_py(ptlib.scene_path("mesh"))
     for m in (1, 22, 64):
         L, _ = lds_layouts.layout(sc, m, 0)
@@ -82,7 +53,8 @@ def test_walks_have_no_rows_and_stay_within_their_budget(header):
 
 
 @pytest.mark.parametrize("seed", [0, 1, 2])
-def test_the_ladder_still_brackets_every_cliff(seed, header):
+def test_the_ladder_still_brackets_every_cliff(seed):
+    header = read_header()
     rungs = lds_layouts.build(seed)  # (asserts that each knob range holds its cliff)
     assert [r[0] for r in rungs] == [c["name"] for c in lds_layouts.CLIFFS]
     for name, inside, outside in rungs:
