@@ -686,6 +686,44 @@ extern "C" {
         stats: *mut PtStats,
         n_pixels: *mut u32,
     ) -> i32;
+    // pt_ctx_reproject_var_moved with a plane of per-pixel sample counts (what pt_ctx_render_adaptive writes as d_spp, or
+    // pt_ctx_spp_plane makes of a mask): count 0 = not traced this frame, the history is carried through; d_spp null = the moved call
+    pub fn pt_ctx_reproject_var_weighted(
+        ctx: *mut PtCtx,
+        width: u32,
+        height: u32,
+        params: *const PtReprojectVarParams,
+        cam: *const PtCamera,
+        d_color: *const f32,
+        d_depth: *const f32,
+        d_object_id: *const i32,
+        d_normal: *const f32,
+        d_spp: *const u32,
+        hist_cam: *const PtCamera,
+        d_hist_color: *const f32,
+        d_hist_len: *const f32,
+        d_hist_moments: *const f32,
+        d_hist_depth: *const f32,
+        d_hist_object_id: *const i32,
+        d_hist_normal: *const f32,
+        d_out_color: *mut f32,
+        d_out_len: *mut f32,
+        d_out_moments: *mut f32,
+        d_error: *mut f32,
+        motion: *const PtObjectMotion,
+        n_motion: u32,
+        hip_stream: *mut c_void,
+    ) -> i32;
+    pub fn pt_ctx_spp_plane(
+        ctx: *mut PtCtx,
+        width: u32,
+        height: u32,
+        base: u32,
+        d_mask: *const u8,
+        masked: u32,
+        d_spp: *mut u32,
+        hip_stream: *mut c_void,
+    ) -> i32;
     // host arrays of n; `surfaces` is read by PT_SCATTER_GIVEN alone
     pub fn pt_ctx_scatter(
         ctx: *mut PtCtx,

@@ -1321,6 +1321,59 @@ int pt_ctx_render_masked(pt_ctx *ctx, const pt_config *cfg, const uint8_t *d_mas
                          void *hip_stream, const volatile uint8_t *cancel, pt_stats *stats,
                          uint32_t *n_pixels /* host, may be NULL */);
 
+/* ---- reprojection with per-pixel sample counts ---------------------------------------------------------------------------
+ * pt_ctx_reproject_var and pt_ctx_reproject_var_moved assume that every pixel of the frame holds the same number of samples,
+ * pt_reproject_var_params.weight: that one number is the blend factor's numerator, the history length that is carried, the
+ * `long` test and the scale k of the error map.  Two calls produce frames for which it is false: pt_ctx_render_adaptive /
+ * pt_ctx_accumulate_adaptive, whose d_spp holds every pixel's own count, and pt_ctx_select_pixels + pt_ctx_render_masked at a
+ * multiple of the frame's samples.  pt_ctx_reproject_var_weighted is pt_ctx_reproject_var_moved with one more input, d_spp: a
+ * plane of width * height uint32 in framebuffer order, device memory, the samples each pixel of d_color holds - the layout
+ * pt_ctx_render_adaptive writes as its d_spp for a cfg without a band.  A count of 0 means "this pixel was not traced this
+ * frame": its colour is not data, and its history is carried through as it is, so a host may trace a subset of the pixels per
+ * frame under a still or slowly moving camera.
+ * - Everything pt_ctx_reproject_var_moved states carries over word for word: the buffers, the history set, aliasing, the scratch
+ *   plane of s values, the motion table and its scratch, `hip_stream`, blocking, "no scene is needed".  d_spp may alias no output.
+ * - PT_ERR_INVALID: pt_ctx_reproject_var_moved's refusals in its order.  d_spp is never refused.
+ * - Delegation: with d_spp == NULL the call is pt_ctx_reproject_var_moved with the same arguments: that call's launches, and its
+ *   bytes by construction.
+ *
+ * THE ARITHMETIC is pt_ctx_reproject_var_moved's, with these changes and no others.  w0 = (float)weight (0 stands for 1), the
+ * uniform value as before.  For pixel idx, c = spp[idx] and wp = (float)c; a count above 2^24 is converted round-to-nearest
+ * and is not checked.
+ * c > 0.  Every wt in steps 1 and 5 of pt_ctx_reproject, in the moments and in k = wt / len_out, is wp.
+ *    long = len_out >= (float)min_frames * wp; the product is formed on the device in binary32 (exact for the counts the
+ *    library produces).
+ * c == 0.  Where step 1 applies (no history, id < 0, the marker, rejected, no tap with bsum > 0): out = color[idx] as stored,
+ *    len_out = 0, m1 = s, m2 = s*s, e = +inf.  Otherwise h, h1, h2 and n = nsum / bsum as before; n' = n, and if
+ *    n' > max_history, n' = max_history; out[c] = h[c], m1 = h1, m2 = h2 - the values themselves, not h + (x - h)*0: a NaN
+ *    colour does not leak and -0 stays -0; len_out = n'; long = len_out >= (float)min_frames * w0 (the host-formed product);
+ *    long: e = the error of pos(m2 - m1*m1) with k = w0 / len_out over out; not long: e = +inf - there is no spatial
+ *    estimate without a colour.
+ * Spatial estimate (pixels with c > 0 that are not long).  As before, with one more condition on every q but the centre:
+ *    spp[q] == spp[idx].  A neighbour with another count holds values of another variance; one with count 0 holds no data.
+ *    k = wp / len_out.
+ * The plane of s values is written for every pixel as before; the value of a c == 0 pixel is never read by a taken tap.
+ * CONSEQUENCE.  A plane that holds the constant w everywhere gives, bit for bit, pt_ctx_reproject_var_moved with weight = w,
+ * on all four outputs.
+ *
+ * pt_ctx_spp_plane builds the plane of a boosted frame: spp[p] = (d_mask && mask[p] != 0) ? masked : base, with d_mask
+ * pt_ctx_select_pixels' byte mask (width * height bytes, device; may be NULL) and d_spp width * height uint32 (device).
+ * - An image pass: no scene is needed, no scratch is taken, no state of the context changes; `hip_stream` as for
+ *   pt_ctx_render; blocking.  d_spp may not alias d_mask.
+ * - PT_ERR_INVALID, all refused before any device is touched, checked in this order: width or height 0; width * height above
+ *   2^28; NULL d_spp; NULL ctx.  PT_ERR_HIP: a HIP call failed. */
+int pt_ctx_reproject_var_weighted(pt_ctx *ctx, uint32_t width, uint32_t height, const pt_reproject_var_params *params,
+                                  const pt_camera *cam, const float *d_color, const float *d_depth,
+                                  const int32_t *d_object_id, const float *d_normal /* may be NULL */,
+                                  const uint32_t *d_spp /* width*height u32, device; NULL = uniform */,
+                                  const pt_camera *hist_cam, const float *d_hist_color, const float *d_hist_len,
+                                  const float *d_hist_moments, const float *d_hist_depth,
+                                  const int32_t *d_hist_object_id, const float *d_hist_normal /* may be NULL */,
+                                  float *d_out_color, float *d_out_len, float *d_out_moments, float *d_error,
+                                  const pt_object_motion *motion /* host, may be NULL */, uint32_t n_motion, void *hip_stream);
+int pt_ctx_spp_plane(pt_ctx *ctx, uint32_t width, uint32_t height, uint32_t base, const uint8_t *d_mask /* may be NULL */,
+                     uint32_t masked, uint32_t *d_spp, void *hip_stream);
+
 /* ---- the one collective of the path: the framebuffer gather over RCCL (xGMI) ---------------------------------
  * One process (or thread) per GPU renders its rows with pt_ctx_render (chunk_first = rank, chunk_step = n_ranks) into
  * device memory; pt_comm_gather_frame then gives EVERY rank the whole frame in device memory: one in-place

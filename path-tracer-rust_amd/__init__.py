@@ -277,6 +277,31 @@ class Context:
                                                 ptr(h.get("object_id")), ptr(h.get("normal")), ptr(out_color), ptr(out_len),
                                                 ptr(out_moments), ptr(error), table, len(motion), C.c_void_p(stream or 0)))
 
+    def reproject_var_weighted(self, width, height, cam, color, depth, object_id, out_color, out_len, out_moments, error, spp=None,
+                               motion=None, normal=None, history=None, weight=1, max_history=0.0, depth_tol=0.0, normal_min=0.0,
+                               min_frames=0, radius=0, stream=None):
+        """reproject_var_moved() for a frame whose pixels hold different numbers of samples (pt_ctx_reproject_var_weighted).
+        `spp`: a device pointer to pixels uint32, the samples each pixel of `color` holds - render_adaptive()'s spp plane, or
+        what spp_plane() makes of a mask; a count of 0 means "not traced this frame": the pixel's history is carried through as
+        it is.  spp=None is reproject_var_moved(); motion=None is an empty table.  `weight` stays the uniform value: it scales
+        the error of the pixels without samples."""
+        p = pt_reproject_var_params(weight, max_history, depth_tol, normal_min, min_frames, radius, 0)
+        ptr = lambda q: C.c_void_p(q) if q else None  # noqa: E731
+        h = history or {}
+        motion = () if motion is None else motion
+        table = _motion_table(motion)
+        _check(lib().pt_ctx_reproject_var_weighted(self._h, width, height, C.byref(p), _camera(cam), ptr(color), ptr(depth),
+                                                   ptr(object_id), ptr(normal), ptr(spp), _camera(h["cam"]) if history else None,
+                                                   ptr(h.get("color")), ptr(h.get("len")), ptr(h.get("moments")), ptr(h.get("depth")),
+                                                   ptr(h.get("object_id")), ptr(h.get("normal")), ptr(out_color), ptr(out_len),
+                                                   ptr(out_moments), ptr(error), table, len(motion), C.c_void_p(stream or 0)))
+
+    def spp_plane(self, width, height, spp, base, mask=None, masked=0, stream=None):
+        """The plane of counts of a boosted frame (pt_ctx_spp_plane): spp[p] = masked where mask[p] != 0, else base.  Device
+        pointers: `spp` pixels uint32, `mask` pixels bytes (select_pixels()'s) or None."""
+        ptr = lambda q: C.c_void_p(q) if q else None  # noqa: E731
+        _check(lib().pt_ctx_spp_plane(self._h, width, height, base, ptr(mask), masked, ptr(spp), C.c_void_p(stream or 0)))
+
     def reproject_moved(self, width, height, cam, color, depth, object_id, out_color, out_len, motion, normal=None, history=None,
                         weight=1, max_history=0.0, depth_tol=0.0, normal_min=0.0, stream=None):
         """reproject() with history carried on objects that set_object() moved (pt_ctx_reproject_moved); `motion` as for

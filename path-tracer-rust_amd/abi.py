@@ -253,6 +253,9 @@ SIGNATURES = {  # name: (restype, argtypes), in the header's order
     "pt_upsample_tap_host": (c_int, [c_uint32, c_uint32, c_uint32, P(c_int32), P(c_float)]),
     "pt_ctx_select_pixels": (c_int, [vp, c_uint32, c_uint32, P(pt_select_params), vp, vp, vp, P(c_uint32), vp]),
     "pt_ctx_render_masked": (c_int, [vp, P(pt_config), vp, vp, vp, vp, P(pt_stats), P(c_uint32)]),
+    "pt_ctx_reproject_var_weighted": (c_int, [vp, c_uint32, c_uint32, P(pt_reproject_var_params), P(pt_camera), vp, vp, vp, vp, vp,
+        P(pt_camera), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, P(pt_object_motion), c_uint32, vp]),
+    "pt_ctx_spp_plane": (c_int, [vp, c_uint32, c_uint32, c_uint32, vp, c_uint32, vp, vp]),
     "pt_comm_unique_id": (c_int, [c_char_p]),
     "pt_comm_create": (c_int, [c_int, c_int, c_int, c_char_p, P(vp)]),
     "pt_comm_destroy": (None, [vp]),

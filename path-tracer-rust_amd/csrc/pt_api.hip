@@ -2935,6 +2935,51 @@ int pt_ctx_reproject_var_moved(pt_ctx *c, uint32_t width, uint32_t height, const
     });
 }
 
+int pt_ctx_reproject_var_weighted(pt_ctx *c, uint32_t width, uint32_t height, const pt_reproject_var_params *params,
+                                  const pt_camera *cam, const float *d_color, const float *d_depth, const int32_t *d_object_id,
+                                  const float *d_normal, const uint32_t *d_spp, const pt_camera *hist_cam, const float *d_hist_color,
+                                  const float *d_hist_len, const float *d_hist_moments, const float *d_hist_depth,
+                                  const int32_t *d_hist_object_id, const float *d_hist_normal, float *d_out_color, float *d_out_len,
+                                  float *d_out_moments, float *d_error, const pt_object_motion *motion, uint32_t n_motion,
+                                  void *hip_stream) {
+    if (!d_spp)  // uniform: pt_ctx_reproject_var_moved itself, its launches and so its bytes
+        return pt_ctx_reproject_var_moved(c, width, height, params, cam, d_color, d_depth, d_object_id, d_normal, hist_cam, d_hist_color,
+                                          d_hist_len, d_hist_moments, d_hist_depth, d_hist_object_id, d_hist_normal, d_out_color,
+                                          d_out_len, d_out_moments, d_error, motion, n_motion, hip_stream);
+    ReprojectVarFrame v;
+    ReprojectWeights wts;
+    int how = host::kMotionPlain;
+    const int rc = host::check_reproject_var_weighted(c, width, height, params, cam, d_color, d_depth, d_object_id, d_normal, d_spp, hist_cam,
+                                                      d_hist_color, d_hist_len, d_hist_moments, d_hist_depth, d_hist_object_id,
+                                                      d_hist_normal, d_out_color, d_out_len, d_out_moments, d_error, motion, n_motion, v,
+                                                      &how, wts);
+    if (rc) return rc;
+    return run_image_pass(c, hip_stream, [&](hipStream_t st) {
+        const int rs = c->rv_s.ensure((size_t)width * height);
+        if (rs) return rs;
+        v.s_plane = c->rv_s.p;
+        if (how == host::kMotionPlain || !v.f.hist_color) {  // nothing moved, or no history for it to move in
+            launch_reproject_var_weighted(st, v, wts, nullptr);
+            return PT_OK;
+        }
+        ReprojectMotion m;
+        const int ru = upload_motion(c, st, motion, n_motion, m);
+        if (ru) return ru;
+        launch_reproject_var_weighted(st, v, wts, &m);
+        return PT_OK;
+    });
+}
+
+int pt_ctx_spp_plane(pt_ctx *c, uint32_t width, uint32_t height, uint32_t base, const uint8_t *d_mask, uint32_t masked, uint32_t *d_spp,
+                     void *hip_stream) {
+    const int rc = host::check_spp_plane(c, width, height, d_spp);
+    if (rc) return rc;
+    return run_image_pass(c, hip_stream, [&](hipStream_t st) {
+        launch_spp_plane(st, d_mask, width * height, base, masked, d_spp);
+        return PT_OK;
+    });
+}
+
 int pt_upsample_defaults(pt_upsample_params *out) {
     return give_defaults(out, pt_upsample_params{kUpsampleDepthTol, kUpsampleNormalMin, 0u});
 }

@@ -1860,6 +1860,23 @@ int check_reproject_var_moved(const void *ctx, uint32_t width, uint32_t height, 
                                   motion, n_motion, how);
 }
 
+// ---- pt_ctx_reproject_var_weighted: pt_ctx_reproject_var_moved's refusals; the plane is never refused
+int check_reproject_var_weighted(const void *ctx, uint32_t width, uint32_t height, const pt_reproject_var_params *params,
+                                 const pt_camera *cam, const float *d_color, const float *d_depth, const int32_t *d_object_id,
+                                 const float *d_normal, const uint32_t *d_spp, const pt_camera *hist_cam, const float *d_hist_color,
+                                 const float *d_hist_len, const float *d_hist_moments, const float *d_hist_depth,
+                                 const int32_t *d_hist_object_id, const float *d_hist_normal, float *d_out_color, float *d_out_len,
+                                 float *d_out_moments, float *d_error, const pt_object_motion *motion, uint32_t n_motion,
+                                 ReprojectVarFrame &v, int *how, ReprojectWeights &wts) {
+    const int rc = check_reproject_var_moved(ctx, width, height, params, cam, d_color, d_depth, d_object_id, d_normal, hist_cam, d_hist_color,
+                                             d_hist_len, d_hist_moments, d_hist_depth, d_hist_object_id, d_hist_normal, d_out_color,
+                                             d_out_len, d_out_moments, d_error, motion, n_motion, v, how);
+    if (rc) return rc;
+    wts.spp = d_spp;
+    wts.min_frames = (float)(params && params->min_frames ? params->min_frames : kReprojectVarMinFrames);
+    return PT_OK;
+}
+
 // ---- pt_ctx_upsample (ptrace.h, pt_upsample.h)
 int check_upsample(const void *ctx, uint32_t width, uint32_t height, uint32_t lo_width, uint32_t lo_height,
                    const pt_upsample_params *params, const float *d_lo_color, const float *d_lo_depth, const int32_t *d_lo_object_id,
@@ -1918,6 +1935,14 @@ int check_select_pixels(const void *ctx, uint32_t width, uint32_t height, const 
     f.mask = d_mask;
     f.weight_max = P.weight_max;
     f.len_max = P.len_max;
+    return PT_OK;
+}
+
+int check_spp_plane(const void *ctx, uint32_t width, uint32_t height, const uint32_t *d_spp) {
+    if (!width || !height) return refuse("width and height must be positive");
+    if ((uint64_t)width * height > (1ull << 28)) return refuse("width*height exceeds 2^28");
+    if (!d_spp) return refuse("d_spp is NULL");
+    if (!ctx) return refuse("ctx is NULL");
     return PT_OK;
 }
 

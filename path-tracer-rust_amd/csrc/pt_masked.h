@@ -1,7 +1,8 @@
 // pt_masked.h — pt_ctx_select_pixels and the device side of pt_ctx_render_masked beside the trace (pt_masked.hip): the select
 // pass that turns the viewport loop's planes (pt_ctx_upsample's d_out_weight, pt_ctx_reproject*'s d_out_len) into a byte mask
 // and counts it, the compaction of a mask into a list of call indices, and the scatter of the compact accumulator into a frame
-// through k_resolve's arithmetic.  The predicate is the contract in include/ptrace.h, stated once, below, for host and device.
+// through k_resolve's arithmetic - and pt_ctx_spp_plane, which turns such a mask into the plane of per-pixel sample counts
+// pt_ctx_reproject_var_weighted reads.  The predicate is the contract in include/ptrace.h, stated once, below, for host and device.
 // The trace itself is the tile pass (pt_tile.h) over a grid of 1x1 tiles.  A translation unit of its own: pt_kernels.s, and so
 // pt_kernel_isa_hash(), describes the pass kernels only.
 #pragma once
@@ -31,7 +32,12 @@ PT_HD uint32_t select_pixel(const SelectFrame &f, uint32_t p) {
                        f.len_max);
 }
 
+// pt_ctx_spp_plane: the count of a pixel whose mask byte is m (no mask: m = 0)
+PT_HD uint32_t spp_plane_value(uint32_t m, uint32_t base, uint32_t masked) { return m != 0u ? masked : base; }
+
 namespace host {
+// pt_ctx_spp_plane's refusals in the header's order.  No device is touched.
+int check_spp_plane(const void *ctx, uint32_t width, uint32_t height, const uint32_t *d_spp);
 // pt_ctx_select_pixels' refusals in the header's order (PT_ERR_INVALID + message); PT_OK: `f` holds the call, all but `count`.
 // No device is touched.
 int check_select_pixels(const void *ctx, uint32_t width, uint32_t height, const pt_select_params *params, const float *d_weight,
@@ -52,6 +58,9 @@ void launch_masked_compact(hipStream_t st, const uint8_t *mask, uint32_t n, uint
 
 // rgb[3 * list[k] + c] = clamp(mean of acc[c * n + k] over spp samples), k < n (> 0): k_resolve's arithmetic; nothing else is written
 void launch_masked_scatter(hipStream_t st, const uint32_t *list, uint32_t n, const unsigned long long *acc, uint32_t spp, float *rgb);
+
+// spp[p] = spp_plane_value(mask ? mask[p] : 0, base, masked), p < n (> 0): sixteen pixels per lane
+void launch_spp_plane(hipStream_t st, const uint8_t *mask, uint32_t n, uint32_t base, uint32_t masked, uint32_t *spp);
 #endif
 
 }  // namespace pt

@@ -1,4 +1,4 @@
-// pt_masked.hip — the kernels of pt_ctx_select_pixels and pt_ctx_render_masked beside the trace.  gfx950, wave64.  Built like
+// pt_masked.hip — the kernels of pt_ctx_select_pixels, pt_ctx_render_masked beside the trace, and pt_ctx_spp_plane.  gfx950, wave64.  Built like
 // pt_adaptive.hip (-ffp-contract=off, correctly rounded /, no -mllvm options): the scatter's mean is k_resolve's, bit for bit.
 //
 // k_select: memory-bound, 4 or 8 B read and 1 B written per pixel.  A lane takes four consecutive pixels - one 16-byte load per
@@ -25,6 +25,7 @@ namespace {
 constexpr uint32_t kSelectBlock = 256, kSelectMaxGrid = 2048;
 constexpr uint32_t kCompactBlock = 1024, kCompactBytes = 16;  // lanes of a workgroup, mask bytes of a lane
 constexpr uint32_t kScatterBlock = 256;
+constexpr uint32_t kSppBlock = 256, kSppPixels = 16;  // lanes of a workgroup, pixels of a lane
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -142,9 +143,44 @@ __global__ __launch_bounds__(kScatterBlock) void k_masked_scatter(const uint32_t
     }
 }
 
+// k_spp_plane (pt_ctx_spp_plane): 1 B read and 4 B written per pixel.  A lane takes sixteen consecutive pixels: one 16-byte
+// load of the mask, non-temporal (each byte is read once), and four 16-byte stores of counts - plain stores, the next pass reads
+// the plane - where the pointers allow it (both aligned to 16 bytes); byte loads and single stores otherwise and on the frame's
+// last, partial group.  Without a mask nothing is read.
+template <bool VEC>
+__global__ __launch_bounds__(kSppBlock) void k_spp_plane(const uint8_t *__restrict__ mask, uint32_t n, uint32_t base, uint32_t masked,
+                                                         uint32_t *__restrict__ spp) {
+    // n <= 2^28 and the grid covers it in whole workgroups: p0 < 2^28 + 4096
+    const uint32_t p0 = (blockIdx.x * kSppBlock + threadIdx.x) * kSppPixels;
+    if (p0 >= n) return;
+    if (VEC && p0 + kSppPixels <= n) {
+        u32x4 v = {0u, 0u, 0u, 0u};
+        if (mask) v = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(mask + p0));
+#pragma unroll
+        for (uint32_t q = 0; q < 4u; ++q) {
+            u32x4 o;
+#pragma unroll
+            for (uint32_t j = 0; j < 4u; ++j) o[j] = spp_plane_value((v[q] >> (8u * j)) & 0xffu, base, masked);
+            *reinterpret_cast<u32x4 *>(spp + p0 + 4u * q) = o;
+        }
+    } else {
+        const uint32_t end = p0 + kSppPixels < n ? p0 + kSppPixels : n;
+        for (uint32_t p = p0; p < end; ++p) spp[p] = spp_plane_value(mask ? mask[p] : 0u, base, masked);
+    }
+}
+
 bool aligned(const void *p, uintptr_t to) { return p == nullptr || ((uintptr_t)p & (to - 1u)) == 0u; }
 
 }  // namespace
+
+void launch_spp_plane(hipStream_t st, const uint8_t *mask, uint32_t n, uint32_t base, uint32_t masked, uint32_t *spp) {
+    constexpr uint32_t per_block = kSppBlock * kSppPixels;
+    const dim3 grid((n + per_block - 1u) / per_block), block(kSppBlock);  // n >= 1
+    if (aligned(mask, 16u) && aligned(spp, 16u))
+        hipLaunchKernelGGL((k_spp_plane<true>), grid, block, 0, st, mask, n, base, masked, spp);
+    else
+        hipLaunchKernelGGL((k_spp_plane<false>), grid, block, 0, st, mask, n, base, masked, spp);
+}
 
 void launch_select(hipStream_t st, const SelectFrame &f) {
     const uint32_t blocks = ((f.npix + 3u) / 4u + kSelectBlock - 1u) / kSelectBlock;  // npix >= 1

@@ -4,8 +4,9 @@
 // Steps 3 to 5 - and the pixel that strings them together - are stated once, below, for host and device:
 // pt_reproject_project_host (host/scene_io.cpp) is the host instantiation of the projection the kernel compiles, as
 // pt_present_quantize_host is of pt_present.h.  pt_ctx_reproject_moved and pt_ctx_reproject_var_moved - history carried through
-// pt_ctx_set_object's edits by a per-object motion table - are the same functions with MOVED compiled in.  A translation unit
-// of its own: pt_kernels.s, and so pt_kernel_isa_hash(), describes the pass kernels only.
+// pt_ctx_set_object's edits by a per-object motion table - are the same functions with MOVED compiled in, and
+// pt_ctx_reproject_var_weighted - a plane of per-pixel sample counts in place of the one weight - with WEIGHTED.  A translation
+// unit of its own: pt_kernels.s, and so pt_kernel_isa_hash(), describes the pass kernels only.
 #pragma once
 
 #include "../../include/ptrace.h"
@@ -91,6 +92,14 @@ PT_HD pt_object_motion reproject_rec(const ReprojectMotion &m, int32_t id) {
     return r;
 }
 
+// ---- pt_ctx_reproject_var_weighted: the plane of per-pixel sample counts ("THE ARITHMETIC" of pt_ctx_reproject_var_weighted in
+// include/ptrace.h).  A kernel argument of its own, as the motion table is: ReprojectFrame and ReprojectVarFrame stay what they
+// are.  The uniform value w0 is the frame's f.wt, and (float)min_frames * w0 its long_len.
+struct ReprojectWeights {
+    const uint32_t *spp;  // width * height counts; 0: the pixel holds no samples this frame
+    float min_frames;     // (float)min_frames: a pixel with count c > 0 is long from min_frames * (float)c samples on
+};
+
 // step 3 up to the reject test: where the point pixel idx sees at `depth` lies in the history frame.  false: no position.
 // MOVED (pt_ctx_reproject_moved): the point goes through the object's record first - Pm[a] = P[a]*scale + offset[a], two
 // operations per component - unless the record is IDENTITY, which leaves P's bits alone.
@@ -153,10 +162,12 @@ struct ReprojectTap {
 // MOM (pt_ctx_reproject_var): the taps' moments ride along - read with the rest, summed with the same b over the same taps, and
 // blended with the same k as the colour; `mom` holds (s, s*s) on entry and (m1, m2) on return.  Without MOM nothing of it is
 // compiled.
-template <int NT, bool MOM = false>
+// WEIGHTED (pt_ctx_reproject_var_weighted): wp, the pixel's own count as a float, stands in for f.wt; `empty` (count 0) carries
+// the history through as it is - the values themselves, not a blend by 0, so that the pixel's colour never enters them.
+template <int NT, bool MOM = false, bool WEIGHTED = false>
 PT_HD bool reproject_gather(const ReprojectFrame &f, const ReprojectTap (&tap)[NT], float zexp, int32_t id, bool normals, vec3 N,
                             const float col[3], float out[3], float *len_out, const ReprojectMom *hist_moments = nullptr,
-                            ReprojectMom *mom = nullptr) {
+                            ReprojectMom *mom = nullptr, float wp = 0.0f, bool empty = false) {
     float hlen[NT], hdepth[NT];
     int32_t hid[NT];
 #pragma unroll
@@ -196,10 +207,26 @@ PT_HD bool reproject_gather(const ReprojectFrame &f, const ReprojectTap (&tap)[N
         bsum = take ? bsum + b : bsum;
     }
     if (!(bsum > 0.0f)) return false;
-    float n = nsum / bsum + f.wt;
+    float wt = f.wt;
+    if constexpr (WEIGHTED) {
+        wt = wp;
+        if (empty) {
+            float n = nsum / bsum;
+            if (n > f.max_history) n = f.max_history;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) out[c] = s[c] / bsum;
+            if constexpr (MOM) {
+                mom->m1 = a1 / bsum;
+                mom->m2 = a2 / bsum;
+            }
+            *len_out = n;
+            return true;
+        }
+    }
+    float n = nsum / bsum + wt;
     if (n > f.max_history) n = f.max_history;
-    if (n < f.wt) n = f.wt;
-    const float k = f.wt / n;
+    if (n < wt) n = wt;
+    const float k = wt / n;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         const float h = s[c] / bsum;
@@ -229,6 +256,13 @@ PT_HD int32_t reproject_own(const int32_t *p) {
     return *p;
 #endif
 }
+PT_HD uint32_t reproject_own(const uint32_t *p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_nontemporal_load(p);
+#else
+    return *p;
+#endif
+}
 
 // steps 1 to 5 for pixel idx (< width * height): the colour and the length it ends with.  The pixel's own colour is read before
 // anything is returned, so the caller may store into color[idx].  MOM: pt_ctx_reproject_var's moments too - *s_out is the
@@ -239,14 +273,28 @@ PT_HD int32_t reproject_own(const int32_t *p) {
 // (b = 1) and three taps that are outside (never taken, so the sums are the one-tap sums bit for bit; they read the lane's own
 // history pixel again, a line it has in flight already).  No lane waits for another's second gather.  Without MOVED nothing of it
 // is compiled.
-template <bool MOM, bool MOVED = false>
+// WEIGHTED (pt_ctx_reproject_var_weighted): the pixel's count - one more of its own loads, issued with the colour's - is handed
+// back in *count_out; as a float it is the pixel's wt in every step, and a count of 0 takes the history as it is.  Without
+// WEIGHTED nothing of it is compiled.
+template <bool MOM, bool MOVED = false, bool WEIGHTED = false>
 PT_HD void reproject_pixel_t(const ReprojectFrame &f, uint32_t idx, float out[3], float *len_out, const ReprojectMom *hist_moments,
-                             ReprojectMom *mom, float *s_out, const ReprojectMotion *motion = nullptr) {
+                             ReprojectMom *mom, float *s_out, const ReprojectMotion *motion = nullptr,
+                             const ReprojectWeights *weights = nullptr, uint32_t *count_out = nullptr) {
     const size_t i3 = (size_t)idx * 3u;
     float col[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) out[c] = col[c] = reproject_own(f.color + i3 + c);
-    *len_out = f.wt;
+    float wp = 0.0f;
+    bool empty = false;
+    if constexpr (WEIGHTED) {
+        const uint32_t count = reproject_own(weights->spp + idx);
+        *count_out = count;
+        wp = (float)count;
+        empty = count == 0u;
+        *len_out = wp;
+    } else {
+        *len_out = f.wt;
+    }
     if constexpr (MOM) {
         const float s = (col[0] + col[1]) + col[2];
         *s_out = s;
@@ -269,7 +317,7 @@ PT_HD void reproject_pixel_t(const ReprojectFrame &f, uint32_t idx, float out[3]
         if (reproject_rec_marker(rec)) return;
     } else if (f.view.same) {
         const ReprojectTap tap[1] = {{idx, 1.0f, true}};
-        reproject_gather<1, MOM>(f, tap, depth, id, normals, N, col, out, len_out, hist_moments, mom);
+        reproject_gather<1, MOM, WEIGHTED>(f, tap, depth, id, normals, N, col, out, len_out, hist_moments, mom, wp, empty);
         return;
     }
     ReprojectTap tap[4];
@@ -300,7 +348,7 @@ PT_HD void reproject_pixel_t(const ReprojectFrame &f, uint32_t idx, float out[3]
         }
         zexp = p.zexp;
     }
-    reproject_gather<4, MOM>(f, tap, zexp, id, normals, N, col, out, len_out, hist_moments, mom);
+    reproject_gather<4, MOM, WEIGHTED>(f, tap, zexp, id, normals, N, col, out, len_out, hist_moments, mom, wp, empty);
 }
 PT_HD void reproject_pixel(const ReprojectFrame &f, uint32_t idx, float out[3], float *len_out) {
     reproject_pixel_t<false>(f, idx, out, len_out, nullptr, nullptr, nullptr);
@@ -322,11 +370,15 @@ PT_HD float reproject_var_error(float v, float k, const float out[3]) {
 // Kernel A's pixel: pt_ctx_reproject's colour and length, the moments, the s plane, and d_error - final where the history is
 // long, kReprojectVarShort where the spatial estimate has to stand in.  Everything the pixel reads of planes it may share with
 // an output (its own colour) is read before the first store.
-template <bool MOVED = false>
-PT_HD void reproject_var_pixel(const ReprojectVarFrame &v, uint32_t idx, const ReprojectMotion *motion = nullptr) {
+// WEIGHTED: a pixel with a count is long from min_frames * wp samples on, the product formed here, and its k is wp / len; a
+// pixel without one is long by the frame's long_len, its k is w0 / len, and it is never marked: no spatial estimate without a colour.
+template <bool MOVED = false, bool WEIGHTED = false>
+PT_HD void reproject_var_pixel(const ReprojectVarFrame &v, uint32_t idx, const ReprojectMotion *motion = nullptr,
+                               const ReprojectWeights *weights = nullptr) {
     float out[3], len, s;
     ReprojectMom mom;
-    reproject_pixel_t<true, MOVED>(v.f, idx, out, &len, v.hist_moments, &mom, &s, motion);
+    uint32_t count = 0u;
+    reproject_pixel_t<true, MOVED, WEIGHTED>(v.f, idx, out, &len, v.hist_moments, &mom, &s, motion, weights, &count);
     float *o = v.f.out_color + (size_t)idx * 3u;
     o[0] = out[0];
     o[1] = out[1];
@@ -334,17 +386,29 @@ PT_HD void reproject_var_pixel(const ReprojectVarFrame &v, uint32_t idx, const R
     v.f.out_len[idx] = len;
     v.out_moments[idx] = mom;
     v.s_plane[idx] = s;
-    v.error[idx] = len >= v.long_len ? reproject_var_error(reproject_var_temporal(mom), v.f.wt / len, out) : kReprojectVarShort;
+    if constexpr (WEIGHTED) {
+        const float wp = (float)count, vt = reproject_var_temporal(mom);
+        if (count == 0u)
+            v.error[idx] = len >= v.long_len ? reproject_var_error(vt, v.f.wt / len, out) : __builtin_inff();
+        else
+            v.error[idx] = len >= weights->min_frames * wp ? reproject_var_error(vt, wp / len, out) : kReprojectVarShort;
+    } else {
+        v.error[idx] = len >= v.long_len ? reproject_var_error(reproject_var_temporal(mom), v.f.wt / len, out) : kReprojectVarShort;
+    }
 }
 
 // The spatial estimate of the pixel at column x, row r: the window of s values around it, in the contract's tap order (dy outside,
 // dx inside; taps outside the frame skipped, the centre always taken).  src(qx, qr, s, id, depth) reads a pixel of the frame:
 // global planes on the host, the staged tile on the device.  false: fewer than two taps, no estimate.
-template <class Src>
+// WEIGHTED: src.count(qx, qr) is a pixel's count, and a q other than the centre is taken only when its count is the centre's - a
+// neighbour with another count holds values of another variance, one with count 0 holds no data.
+template <class Src, bool WEIGHTED = false>
 PT_HD bool reproject_var_spatial(const Src &src, int32_t W, int32_t H, int32_t R, float depth_tol, int32_t x, int32_t r, float *vs) {
     float s0, z0;
     int32_t id0;
     src(x, r, s0, id0, z0);
+    uint32_t c0 = 0u;
+    if constexpr (WEIGHTED) c0 = src.count(x, r);
     float S1 = 0.0f, S2 = 0.0f;
     uint32_t cnt = 0;
     for (int32_t dy = -R; dy <= R; ++dy) {
@@ -361,6 +425,7 @@ PT_HD bool reproject_var_spatial(const Src &src, int32_t W, int32_t H, int32_t R
                 const float zm = z0 > zq ? z0 : zq;
                 take = take && __builtin_fabsf(z0 - zq) <= depth_tol * zm;
             }
+            if constexpr (WEIGHTED) take = take && src.count(qx, qr) == c0;
             take = take || (dx == 0 && dy == 0);
             S1 = take ? S1 + sq : S1;
             S2 = take ? S2 + sq * sq : S2;
@@ -374,17 +439,19 @@ PT_HD bool reproject_var_spatial(const Src &src, int32_t W, int32_t H, int32_t R
 }
 
 // Kernel B's pixel, for one kernel A marked short: e from max(vs, vt), or +inf without a spatial estimate.  It reads the pixel's
-// own outputs of kernel A and writes d_error[idx] alone.
-template <class Src>
+// own outputs of kernel A and writes d_error[idx] alone.  WEIGHTED: k = wp / len_out, wp the pixel's own count (> 0: it is marked).
+template <class Src, bool WEIGHTED = false>
 PT_HD float reproject_var_short_pixel(const ReprojectVarFrame &v, const Src &src, uint32_t idx) {
     const int32_t W = (int32_t)v.f.width, H = (int32_t)v.f.height;
+    const int32_t x = (int32_t)(idx % v.f.width), r = (int32_t)(idx / v.f.width);
     float vs;
-    if (!reproject_var_spatial(src, W, H, (int32_t)v.radius, v.f.depth_tol, (int32_t)(idx % v.f.width), (int32_t)(idx / v.f.width), &vs))
-        return __builtin_inff();
+    if (!reproject_var_spatial<Src, WEIGHTED>(src, W, H, (int32_t)v.radius, v.f.depth_tol, x, r, &vs)) return __builtin_inff();
     const float vt = reproject_var_temporal(v.out_moments[idx]);
     const float *o = v.f.out_color + (size_t)idx * 3u;
     const float out[3] = {o[0], o[1], o[2]};
-    return reproject_var_error(vs > vt ? vs : vt, v.f.wt / v.f.out_len[idx], out);
+    float wt = v.f.wt;
+    if constexpr (WEIGHTED) wt = (float)src.count(x, r);
+    return reproject_var_error(vs > vt ? vs : vt, wt / v.f.out_len[idx], out);
 }
 
 namespace host {
@@ -422,6 +489,15 @@ int check_reproject_var_moved(const void *ctx, uint32_t width, uint32_t height, 
                               const float *d_hist_moments, const float *d_hist_depth, const int32_t *d_hist_object_id,
                               const float *d_hist_normal, float *d_out_color, float *d_out_len, float *d_out_moments, float *d_error,
                               const pt_object_motion *motion, uint32_t n_motion, ReprojectVarFrame &v, int *how);
+// pt_ctx_reproject_var_weighted's refusals: pt_ctx_reproject_var_moved's, in its order - d_spp is never refused.  PT_OK: `v` and
+// *how as there, and `wts` holds the plane (NULL: the call is pt_ctx_reproject_var_moved) and (float)min_frames.
+int check_reproject_var_weighted(const void *ctx, uint32_t width, uint32_t height, const pt_reproject_var_params *params,
+                                 const pt_camera *cam, const float *d_color, const float *d_depth, const int32_t *d_object_id,
+                                 const float *d_normal, const uint32_t *d_spp, const pt_camera *hist_cam, const float *d_hist_color,
+                                 const float *d_hist_len, const float *d_hist_moments, const float *d_hist_depth,
+                                 const int32_t *d_hist_object_id, const float *d_hist_normal, float *d_out_color, float *d_out_len,
+                                 float *d_out_moments, float *d_error, const pt_object_motion *motion, uint32_t n_motion,
+                                 ReprojectVarFrame &v, int *how, ReprojectWeights &wts);
 }  // namespace host
 
 #if defined(__HIPCC__)
@@ -432,6 +508,8 @@ void launch_reproject_var(hipStream_t st, const ReprojectVarFrame &v);
 // the same with the motion table (device memory, 16-byte aligned)
 void launch_reproject_moved(hipStream_t st, const ReprojectFrame &f, const ReprojectMotion &m);
 void launch_reproject_var_moved(hipStream_t st, const ReprojectVarFrame &v, const ReprojectMotion &m);
+// the same with the plane of counts (device memory); m NULL: nothing moved
+void launch_reproject_var_weighted(hipStream_t st, const ReprojectVarFrame &v, const ReprojectWeights &wts, const ReprojectMotion *m);
 #endif
 
 }  // namespace pt

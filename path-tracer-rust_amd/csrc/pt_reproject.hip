@@ -63,9 +63,22 @@ struct RvTile {
     }
 };
 
-__global__ __launch_bounds__(kRvTileW *kRvTileH) void k_reproject_var_spatial(const ReprojectVarFrame v, uint32_t tiles_x) {
+// (pt_ctx_reproject_var_weighted's form, WEIGHTED, stages the counts as a fourth plane - 8512 B - because a tap is then taken
+// only when its count is the centre's; the early return is the same.  Without WEIGHTED nothing of it is compiled.)
+struct RvTileWeighted : RvTile {
+    const uint32_t *c;
+    __device__ uint32_t count(int32_t qx, int32_t qr) const { return c[(qr - r0) * pitch + (qx - x0)]; }
+};
+
+template <bool WEIGHTED>
+__device__ __forceinline__ void rv_spatial_tile(const ReprojectVarFrame &v, uint32_t tiles_x, const uint32_t *spp) {
     __shared__ float sh_s[kRvStageW * kRvStageH], sh_z[kRvStageW * kRvStageH];
     __shared__ int32_t sh_id[kRvStageW * kRvStageH];
+    uint32_t *sh_c = nullptr;
+    if constexpr (WEIGHTED) {
+        __shared__ uint32_t counts[kRvStageW * kRvStageH];
+        sh_c = counts;
+    }
     const int32_t W = (int32_t)v.f.width, H = (int32_t)v.f.height;
     const int32_t tx = (int32_t)(threadIdx.x % kRvTileW), ty = (int32_t)(threadIdx.x / kRvTileW);
     const int32_t bx = (int32_t)((blockIdx.x % tiles_x) * kRvTileW), br = (int32_t)((blockIdx.x / tiles_x) * kRvTileH);
@@ -84,11 +97,23 @@ __global__ __launch_bounds__(kRvTileW *kRvTileH) void k_reproject_var_spatial(co
         sh_s[e] = in ? v.s_plane[q] : 0.0f;
         sh_id[e] = in ? v.f.object_id[q] : 0;
         sh_z[e] = in ? v.f.depth[q] : 0.0f;
+        if constexpr (WEIGHTED) sh_c[e] = in ? spp[q] : 0u;
     }
     __syncthreads();
     if (!marked) return;
     const RvTile tile = {sh_s, sh_z, sh_id, x0, r0, pitch};
-    v.error[idx] = reproject_var_short_pixel(v, tile, idx);
+    if constexpr (WEIGHTED) {
+        RvTileWeighted wt;
+        static_cast<RvTile &>(wt) = tile;
+        wt.c = sh_c;
+        v.error[idx] = reproject_var_short_pixel<RvTileWeighted, true>(v, wt, idx);
+    } else {
+        v.error[idx] = reproject_var_short_pixel(v, tile, idx);
+    }
+}
+
+__global__ __launch_bounds__(kRvTileW *kRvTileH) void k_reproject_var_spatial(const ReprojectVarFrame v, uint32_t tiles_x) {
+    rv_spatial_tile<false>(v, tiles_x, nullptr);
 }
 
 // ---- pt_ctx_reproject_moved / pt_ctx_reproject_var_moved: the same two kernels with the per-object motion table
@@ -120,6 +145,25 @@ void launch_var_spatial(hipStream_t st, const ReprojectVarFrame &v) {
     hipLaunchKernelGGL(k_reproject_var_spatial, dim3(tiles_x * tiles_y), dim3(kRvTileW * kRvTileH), 0, st, v, tiles_x);
 }
 
+// ---- pt_ctx_reproject_var_weighted: the two var kernels with the plane of per-pixel counts (reproject_var_pixel<MOVED, true>).
+// Kernel A reads 4 B more per pixel - the pixel's own count, one non-temporal load issued with its colour's: 116 B per pixel at
+// most - and does per lane what the plain kernel does with a uniform: the count as a float is the pixel's wt, and a pixel without
+// samples takes the gathered history as it is.  Its d_error is final for every pixel without samples (+inf where it is not
+// long), so kernel B's markers are pixels with a count.  The plane and (float)min_frames are a kernel argument of their own.
+template <bool MOVED>
+__global__ __launch_bounds__(kReprojectBlock) void k_reproject_var_weighted(const ReprojectVarFrame v, const ReprojectMotion m,
+                                                                            const ReprojectWeights wts, uint32_t npix) {
+    const uint32_t idx = blockIdx.x * kReprojectBlock + threadIdx.x;
+    if (idx >= npix) return;
+    reproject_var_pixel<MOVED, true>(v, idx, &m, &wts);
+}
+
+// Kernel B with the counts: the one tile body with the fourth staged plane
+__global__ __launch_bounds__(kRvTileW *kRvTileH) void k_reproject_var_spatial_weighted(const ReprojectVarFrame v, const uint32_t *spp,
+                                                                                      uint32_t tiles_x) {
+    rv_spatial_tile<true>(v, tiles_x, spp);
+}
+
 }  // namespace
 
 void launch_reproject_moved(hipStream_t st, const ReprojectFrame &f, const ReprojectMotion &m) {
@@ -132,6 +176,17 @@ void launch_reproject_var_moved(hipStream_t st, const ReprojectVarFrame &v, cons
     hipLaunchKernelGGL(k_reproject_var_moved, dim3((npix + kReprojectBlock - 1u) / kReprojectBlock), dim3(kReprojectBlock), 0, st, v, m,
                        npix);
     launch_var_spatial(st, v);  // the spatial estimate does not read the table
+}
+
+void launch_reproject_var_weighted(hipStream_t st, const ReprojectVarFrame &v, const ReprojectWeights &wts, const ReprojectMotion *m) {
+    const uint32_t npix = v.f.width * v.f.height;
+    const dim3 grid((npix + kReprojectBlock - 1u) / kReprojectBlock), block(kReprojectBlock);
+    if (m)
+        hipLaunchKernelGGL((k_reproject_var_weighted<true>), grid, block, 0, st, v, *m, wts, npix);
+    else
+        hipLaunchKernelGGL((k_reproject_var_weighted<false>), grid, block, 0, st, v, ReprojectMotion{nullptr, 0u}, wts, npix);
+    const uint32_t tiles_x = (v.f.width + kRvTileW - 1u) / kRvTileW, tiles_y = (v.f.height + kRvTileH - 1u) / kRvTileH;
+    hipLaunchKernelGGL(k_reproject_var_spatial_weighted, dim3(tiles_x * tiles_y), dim3(kRvTileW * kRvTileH), 0, st, v, wts.spp, tiles_x);
 }
 
 void launch_reproject_var(hipStream_t st, const ReprojectVarFrame &v) {

@@ -39,7 +39,7 @@ static void usage() {
             "              [--adaptive X [--tile N] [--spp-map FILE.pfm] [--error-map FILE.pfm] [--adaptive-checkpoint FILE]]\n"
             "              [--denoise-var [N]] [--preview FILE.ppm [--preview-size WxH] [--exposure E]]\n"
             "              [--trace-scale K [--retrace]]\n"
-            "              [--orbit N [--orbit-step DEG] [--move I:DX,DY,DZ [--move-history [F]]]]\n"
+            "              [--orbit N [--orbit-step DEG] [--move I:DX,DY,DZ [--move-history [F]]] [--boost K]]\n"
             "  --checkpoint FILE: continue from the samples FILE holds (if it exists), render up to <samplesPerPixel> in all and\n"
             "                     save them to FILE; one GPU only; the seed defaults to 0 instead of the clock, so that the same\n"
             "                     command continues the same frame\n"
@@ -93,7 +93,11 @@ static void usage() {
             "           pt_ctx_reproject_var_moved with the object's record (pt_object_motion_between of the object in frame k and in\n"
             "           frame k-1); with F, max_history on such a frame is F frames' samples (F * <samplesPerPixel>), which bounds how\n"
             "           long the light the object changed elsewhere stays; without F it stays pt_reproject_var_defaults' 64 samples,\n"
-            "           the pick of profiles/reproject_moved_cpu_study.json; not with --aov-chain\n");
+            "           the pick of profiles/reproject_moved_cpu_study.json; not with --aov-chain\n"
+            "  --boost K: with --orbit: the pixels that find no history (pt_ctx_reproject's length <= the frame's samples,\n"
+            "           pt_ctx_select_pixels) are traced again at K * <samplesPerPixel> (pt_ctx_render_masked, K = 2..64), and the frame\n"
+            "           enters the loop with its true per-pixel counts (pt_ctx_spp_plane, pt_ctx_reproject_var_weighted); prints\n"
+            "           'Boosted N of W*H pixels' per frame\n");
 }
 
 static std::vector<std::string> scene_ids(const std::string &root) {
@@ -547,8 +551,9 @@ struct OrbitMove {
     float history = 0.0f;
 };
 
+// --boost K (0: off): the pixels without history traced again at K times the frame's samples, the frame blended by its true counts
 static int render_orbit(const pt_config *cfg, pt_scene *sc, uint32_t frames, double step, const std::string &preview, uint32_t ow,
-                        uint32_t oh, float exposure, const OrbitMove &mv) {
+                        uint32_t oh, float exposure, const OrbitMove &mv, uint32_t boost) {
     using clk = std::chrono::steady_clock;
     auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
     int dev = 0;
@@ -575,6 +580,11 @@ static int render_orbit(const pt_config *cfg, pt_scene *sc, uint32_t frames, dou
     if (!rc) rc = pt_ctx_set_scene(ctx, &cam0, objs, n_objs, tris, n_tris);
     if (!rc) rc = pt_device_malloc(dev, npix * 29 * sizeof(float), &d_buf);
     if (!rc) rc = pt_device_malloc(dev, px.size(), &d_px);
+    // --boost: the plane of counts (4 B per pixel), then the mask (1)
+    void *d_boost = nullptr;
+    if (!rc && boost) rc = pt_device_malloc(dev, npix * 5, &d_boost);
+    uint32_t *const d_spp = (uint32_t *)d_boost;
+    uint8_t *const d_mask = d_boost ? (uint8_t *)d_boost + npix * 4 : nullptr;
     OrbitSide side[2];
     float *d_albedo = nullptr, *d_error = nullptr, *d_shown = nullptr;
     if (!rc) {
@@ -611,19 +621,43 @@ static int render_orbit(const pt_config *cfg, pt_scene *sc, uint32_t frames, dou
         pt_reproject_var_params rp;
         memset(&rp, 0, sizeof rp);
         rp.weight = cfg->spp;
+        std::vector<pt_object_motion> table;
         if (!rc && carried) {
             pt_object now = objs[mv.index], before = objs[mv.index];
             for (int a = 0; a < 3; ++a) {
                 now.position[a] = objs[mv.index].position[a] + (float)k * mv.d[a];
                 before.position[a] = objs[mv.index].position[a] + (float)(k - 1u) * mv.d[a];
             }
-            std::vector<pt_object_motion> table(n_objs, pt_object_motion{{0.0f, 0.0f, 0.0f}, 1.0f});
+            table.assign(n_objs, pt_object_motion{{0.0f, 0.0f, 0.0f}, 1.0f});
             rc = pt_object_motion_between(&now, &before, &table[mv.index]);
             rp.max_history = mv.history * (float)cfg->spp;  // 0: the default
+        }
+        if (!rc && boost) {
+            // the lengths of the plain blend (into the planes the filter fills later) say which pixels found no history; those
+            // are traced again at boost * spp into the frame, and the frame is blended by the counts it then holds
+            const pt_reproject_params lp = {rp.weight, rp.max_history, 0.0f, 0.0f, 0u};
+            const pt_select_params sel = {0.0f, (float)cfg->spp, 0u};
+            pt_config cfg_b = *cfg;
+            cfg_b.spp = boost * cfg->spp;
+            uint32_t boosted = 0;
+            rc = pt_ctx_reproject_moved(ctx, w, h, &lp, &cam, cur->color, cur->depth, cur->id, cur->normal, hh ? &hist_cam : nullptr,
+                                        hh ? hist->color : nullptr, hh ? hist->len : nullptr, hh ? hist->depth : nullptr,
+                                        hh ? hist->id : nullptr, hh ? hist->normal : nullptr, d_shown, d_error,
+                                        table.empty() ? nullptr : table.data(), (uint32_t)table.size(), nullptr);
+            if (!rc) rc = pt_ctx_select_pixels(ctx, w, h, &sel, nullptr, d_error, d_mask, nullptr, nullptr);
+            if (!rc) rc = pt_ctx_render_masked(ctx, &cfg_b, d_mask, cur->color, nullptr, nullptr, nullptr, &boosted);
+            if (!rc) rc = pt_ctx_spp_plane(ctx, w, h, cfg->spp, d_mask, cfg_b.spp, d_spp, nullptr);
             if (!rc)
-                rc = pt_ctx_reproject_var_moved(ctx, w, h, &rp, &cam, cur->color, cur->depth, cur->id, cur->normal, &hist_cam, hist->color,
-                                                hist->len, hist->moments, hist->depth, hist->id, hist->normal, cur->color, cur->len,
-                                                cur->moments, d_error, table.data(), n_objs, nullptr);
+                rc = pt_ctx_reproject_var_weighted(ctx, w, h, &rp, &cam, cur->color, cur->depth, cur->id, cur->normal, d_spp,
+                                                   hh ? &hist_cam : nullptr, hh ? hist->color : nullptr, hh ? hist->len : nullptr,
+                                                   hh ? hist->moments : nullptr, hh ? hist->depth : nullptr, hh ? hist->id : nullptr,
+                                                   hh ? hist->normal : nullptr, cur->color, cur->len, cur->moments, d_error,
+                                                   table.empty() ? nullptr : table.data(), (uint32_t)table.size(), nullptr);
+            if (!rc) printf("Boosted %u of %zu pixels\n", boosted, npix);
+        } else if (!rc && carried) {
+            rc = pt_ctx_reproject_var_moved(ctx, w, h, &rp, &cam, cur->color, cur->depth, cur->id, cur->normal, &hist_cam, hist->color,
+                                            hist->len, hist->moments, hist->depth, hist->id, hist->normal, cur->color, cur->len,
+                                            cur->moments, d_error, table.data(), n_objs, nullptr);
         } else if (!rc)
             rc = pt_ctx_reproject_var(ctx, w, h, &rp, &cam, cur->color, cur->depth, cur->id, cur->normal, hh ? &hist_cam : nullptr,
                                       hh ? hist->color : nullptr, hh ? hist->len : nullptr, hh ? hist->moments : nullptr,
@@ -653,6 +687,7 @@ static int render_orbit(const pt_config *cfg, pt_scene *sc, uint32_t frames, dou
         printf("wrote %s\n", path.c_str());
     }
     if (rc) fprintf(stderr, "--orbit failed (%d): %s\n", rc, pt_last_error());
+    if (d_boost) pt_device_free(dev, d_boost);
     if (d_px) pt_device_free(dev, d_px);
     if (d_buf) pt_device_free(dev, d_buf);
     if (ctx) pt_ctx_destroy(ctx);
@@ -683,6 +718,7 @@ int main(int argc, char **argv) {
     double orbit_step = 2.0;
     bool orbit_step_given = false;
     OrbitMove orbit_move;
+    uint32_t boost = 0;
     for (int i = 4; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&]() -> const char * { return i + 1 < argc ? argv[++i] : ""; };
@@ -833,6 +869,14 @@ int main(int argc, char **argv) {
                 }
             }
         }
+        else if (a == "--boost") {
+            const char *v = next();
+            boost = *v && strspn(v, "0123456789") == strlen(v) ? (uint32_t)strtoul(v, nullptr, 10) : 0u;
+            if (boost < 2u || boost > 64u) {
+                fprintf(stderr, "--boost needs K = 2..64\n");
+                return 1;
+            }
+        }
         else if (a == "--orbit-step") {
             char *e = nullptr;
             const char *v = next();
@@ -879,6 +923,10 @@ int main(int argc, char **argv) {
     }
     if (orbit_step_given && !orbit_frames) {
         fprintf(stderr, "--orbit-step goes with --orbit N\n");
+        return 1;
+    }
+    if (boost && !orbit_frames) {
+        fprintf(stderr, "--boost goes with --orbit N: it boosts the pixels that find no history\n");
         return 1;
     }
     if (orbit_move.index >= 0 && !orbit_frames) {
@@ -1009,7 +1057,7 @@ int main(int argc, char **argv) {
             pt_scene_free(sc);
             return 1;
         }
-        rc = render_orbit(&cfg, sc, orbit_frames, orbit_step, preview, preview_w, preview_h, exposure, orbit_move);
+        rc = render_orbit(&cfg, sc, orbit_frames, orbit_step, preview, preview_w, preview_h, exposure, orbit_move, boost);
         pt_scene_free(sc);
         return rc ? 2 : 0;
     }
