@@ -228,6 +228,19 @@ class Context:
         ptr = lambda q: C.c_void_p(q) if q else None  # noqa: E731
         _check(lib().pt_ctx_present(self._h, width, height, C.byref(p), ptr(rgb), ptr(out), C.c_void_p(stream or 0)))
 
+    def _reproject(self, entry, params, width, height, cam, frame, history, outs, motion=None, stream=None):
+        """The one call of the five reproject methods.  `params`: the entry point's struct, filled - pt_reproject_var_params
+        brings the "moments" of `history` along; `frame`: this frame's planes in the entry point's order, `outs`: its outputs;
+        motion None: the entry point takes no table."""
+        ptr = lambda q: C.c_void_p(q) if q else None  # noqa: E731
+        h = history or {}
+        var = isinstance(params, pt_reproject_var_params)
+        keys = ("color", "len", "moments", "depth", "object_id", "normal") if var else ("color", "len", "depth", "object_id", "normal")
+        table = () if motion is None else (_motion_table(motion), len(motion))
+        _check(getattr(lib(), entry)(self._h, width, height, C.byref(params), _camera(cam), *map(ptr, frame),
+                                     _camera(h["cam"]) if history else None, *(ptr(h.get(k)) for k in keys), *map(ptr, outs), *table,
+                                     C.c_void_p(stream or 0)))
+
     def reproject(self, width, height, cam, color, depth, object_id, out_color, out_len, normal=None, history=None, weight=1,
                   max_history=0.0, depth_tol=0.0, normal_min=0.0, stream=None):
         """Carry a preview frame's history across a camera move and blend it with this frame (pt_ctx_reproject).  Device pointers
@@ -237,13 +250,8 @@ class Context:
         optionally "normal" - after the call the next frame's history is dict(cam=cam, color=out_color, len=out_len, depth=depth,
         object_id=object_id, normal=normal): pointers are swapped, nothing is copied.  weight: the samples per pixel `color`
         holds; max_history, depth_tol, normal_min: 0 = reproject_defaults().  out_color may be color."""
-        p = pt_reproject_params(weight, max_history, depth_tol, normal_min, 0)
-        ptr = lambda q: C.c_void_p(q) if q else None  # noqa: E731
-        h = history or {}
-        _check(lib().pt_ctx_reproject(self._h, width, height, C.byref(p), _camera(cam), ptr(color), ptr(depth), ptr(object_id),
-                                      ptr(normal), _camera(h["cam"]) if history else None, ptr(h.get("color")), ptr(h.get("len")),
-                                      ptr(h.get("depth")), ptr(h.get("object_id")), ptr(h.get("normal")), ptr(out_color),
-                                      ptr(out_len), C.c_void_p(stream or 0)))
+        self._reproject("pt_ctx_reproject", pt_reproject_params(weight, max_history, depth_tol, normal_min, 0), width, height, cam,
+                        (color, depth, object_id, normal), history, (out_color, out_len), stream=stream)
 
     def reproject_var(self, width, height, cam, color, depth, object_id, out_color, out_len, out_moments, error, normal=None,
                       history=None, weight=1, max_history=0.0, depth_tol=0.0, normal_min=0.0, min_frames=0, radius=0, stream=None):
@@ -253,13 +261,8 @@ class Context:
         is dict(cam=cam, color=out_color, len=out_len, moments=out_moments, depth=depth, object_id=object_id, normal=normal).
         min_frames, radius: 0 = reproject_var_defaults().  out_color may be color; out_moments and error alias nothing."""
         p = pt_reproject_var_params(weight, max_history, depth_tol, normal_min, min_frames, radius, 0)
-        ptr = lambda q: C.c_void_p(q) if q else None  # noqa: E731
-        h = history or {}
-        _check(lib().pt_ctx_reproject_var(self._h, width, height, C.byref(p), _camera(cam), ptr(color), ptr(depth), ptr(object_id),
-                                          ptr(normal), _camera(h["cam"]) if history else None, ptr(h.get("color")),
-                                          ptr(h.get("len")), ptr(h.get("moments")), ptr(h.get("depth")), ptr(h.get("object_id")),
-                                          ptr(h.get("normal")), ptr(out_color), ptr(out_len), ptr(out_moments), ptr(error),
-                                          C.c_void_p(stream or 0)))
+        self._reproject("pt_ctx_reproject_var", p, width, height, cam, (color, depth, object_id, normal), history,
+                        (out_color, out_len, out_moments, error), stream=stream)
 
     def reproject_var_moved(self, width, height, cam, color, depth, object_id, out_color, out_len, out_moments, error, motion,
                             normal=None, history=None, weight=1, max_history=0.0, depth_tol=0.0, normal_min=0.0, min_frames=0,
@@ -268,14 +271,8 @@ class Context:
         sequence indexed by object id of pt_object_motion records or (ox, oy, oz, scale) tuples, as object_motion_between()
         makes them - host data, copied by the call; empty, or all (0, 0, 0, 1), is reproject_var() itself."""
         p = pt_reproject_var_params(weight, max_history, depth_tol, normal_min, min_frames, radius, 0)
-        ptr = lambda q: C.c_void_p(q) if q else None  # noqa: E731
-        h = history or {}
-        table = _motion_table(motion)
-        _check(lib().pt_ctx_reproject_var_moved(self._h, width, height, C.byref(p), _camera(cam), ptr(color), ptr(depth),
-                                                ptr(object_id), ptr(normal), _camera(h["cam"]) if history else None,
-                                                ptr(h.get("color")), ptr(h.get("len")), ptr(h.get("moments")), ptr(h.get("depth")),
-                                                ptr(h.get("object_id")), ptr(h.get("normal")), ptr(out_color), ptr(out_len),
-                                                ptr(out_moments), ptr(error), table, len(motion), C.c_void_p(stream or 0)))
+        self._reproject("pt_ctx_reproject_var_moved", p, width, height, cam, (color, depth, object_id, normal), history,
+                        (out_color, out_len, out_moments, error), motion, stream)
 
     def reproject_var_weighted(self, width, height, cam, color, depth, object_id, out_color, out_len, out_moments, error, spp=None,
                                motion=None, normal=None, history=None, weight=1, max_history=0.0, depth_tol=0.0, normal_min=0.0,
@@ -286,15 +283,8 @@ class Context:
         it is.  spp=None is reproject_var_moved(); motion=None is an empty table.  `weight` stays the uniform value: it scales
         the error of the pixels without samples."""
         p = pt_reproject_var_params(weight, max_history, depth_tol, normal_min, min_frames, radius, 0)
-        ptr = lambda q: C.c_void_p(q) if q else None  # noqa: E731
-        h = history or {}
-        motion = () if motion is None else motion
-        table = _motion_table(motion)
-        _check(lib().pt_ctx_reproject_var_weighted(self._h, width, height, C.byref(p), _camera(cam), ptr(color), ptr(depth),
-                                                   ptr(object_id), ptr(normal), ptr(spp), _camera(h["cam"]) if history else None,
-                                                   ptr(h.get("color")), ptr(h.get("len")), ptr(h.get("moments")), ptr(h.get("depth")),
-                                                   ptr(h.get("object_id")), ptr(h.get("normal")), ptr(out_color), ptr(out_len),
-                                                   ptr(out_moments), ptr(error), table, len(motion), C.c_void_p(stream or 0)))
+        self._reproject("pt_ctx_reproject_var_weighted", p, width, height, cam, (color, depth, object_id, normal, spp), history,
+                        (out_color, out_len, out_moments, error), () if motion is None else motion, stream)
 
     def spp_plane(self, width, height, spp, base, mask=None, masked=0, stream=None):
         """The plane of counts of a boosted frame (pt_ctx_spp_plane): spp[p] = masked where mask[p] != 0, else base.  Device
@@ -306,14 +296,8 @@ class Context:
                         weight=1, max_history=0.0, depth_tol=0.0, normal_min=0.0, stream=None):
         """reproject() with history carried on objects that set_object() moved (pt_ctx_reproject_moved); `motion` as for
         reproject_var_moved()."""
-        p = pt_reproject_params(weight, max_history, depth_tol, normal_min, 0)
-        ptr = lambda q: C.c_void_p(q) if q else None  # noqa: E731
-        h = history or {}
-        table = _motion_table(motion)
-        _check(lib().pt_ctx_reproject_moved(self._h, width, height, C.byref(p), _camera(cam), ptr(color), ptr(depth), ptr(object_id),
-                                            ptr(normal), _camera(h["cam"]) if history else None, ptr(h.get("color")),
-                                            ptr(h.get("len")), ptr(h.get("depth")), ptr(h.get("object_id")), ptr(h.get("normal")),
-                                            ptr(out_color), ptr(out_len), table, len(motion), C.c_void_p(stream or 0)))
+        self._reproject("pt_ctx_reproject_moved", pt_reproject_params(weight, max_history, depth_tol, normal_min, 0), width, height,
+                        cam, (color, depth, object_id, normal), history, (out_color, out_len), motion, stream)
 
     def upsample(self, width, height, lo_width, lo_height, lo, depth, object_id, out_color, normal=None, albedo=None,
                  out_weight=None, depth_tol=0.0, normal_min=0.0, stream=None):

@@ -2829,43 +2829,9 @@ int pt_reproject_defaults(pt_reproject_params *out) {
     return give_defaults(out, pt_reproject_params{1u, kReprojectMaxHistory, kReprojectDepthTol, kReprojectNormalMin, 0u});
 }
 
-int pt_ctx_reproject(pt_ctx *c, uint32_t width, uint32_t height, const pt_reproject_params *params, const pt_camera *cam,
-                     const float *d_color, const float *d_depth, const int32_t *d_object_id, const float *d_normal,
-                     const pt_camera *hist_cam, const float *d_hist_color, const float *d_hist_len, const float *d_hist_depth,
-                     const int32_t *d_hist_object_id, const float *d_hist_normal, float *d_out_color, float *d_out_len,
-                     void *hip_stream) {
-    ReprojectFrame f;
-    const int rc = host::check_reproject(c, width, height, params, cam, d_color, d_depth, d_object_id, d_normal, hist_cam, d_hist_color,
-                                         d_hist_len, d_hist_depth, d_hist_object_id, d_hist_normal, d_out_color, d_out_len, f);
-    if (rc) return rc;
-    return run_image_pass(c, hip_stream, [&](hipStream_t st) {
-        launch_reproject(st, f);
-        return PT_OK;
-    });
-}
-
 int pt_reproject_var_defaults(pt_reproject_var_params *out) {
     return give_defaults(out, pt_reproject_var_params{1u, kReprojectMaxHistory, kReprojectDepthTol, kReprojectNormalMin,
                                                       kReprojectVarMinFrames, kReprojectVarRadius, 0u});
-}
-
-int pt_ctx_reproject_var(pt_ctx *c, uint32_t width, uint32_t height, const pt_reproject_var_params *params, const pt_camera *cam,
-                         const float *d_color, const float *d_depth, const int32_t *d_object_id, const float *d_normal,
-                         const pt_camera *hist_cam, const float *d_hist_color, const float *d_hist_len, const float *d_hist_moments,
-                         const float *d_hist_depth, const int32_t *d_hist_object_id, const float *d_hist_normal, float *d_out_color,
-                         float *d_out_len, float *d_out_moments, float *d_error, void *hip_stream) {
-    ReprojectVarFrame v;
-    const int rc = host::check_reproject_var(c, width, height, params, cam, d_color, d_depth, d_object_id, d_normal, hist_cam,
-                                             d_hist_color, d_hist_len, d_hist_moments, d_hist_depth, d_hist_object_id, d_hist_normal,
-                                             d_out_color, d_out_len, d_out_moments, d_error, v);
-    if (rc) return rc;
-    return run_image_pass(c, hip_stream, [&](hipStream_t st) {
-        const int rs = c->rv_s.ensure((size_t)width * height);
-        if (rs) return rs;
-        v.s_plane = c->rv_s.p;
-        launch_reproject_var(st, v);
-        return PT_OK;
-    });
 }
 
 // the moved calls' table, copied into the context's scratch on the call's stream (the call waits for the stream before it returns,
@@ -2882,28 +2848,66 @@ static int upload_motion(pt_ctx *c, hipStream_t st, const pt_object_motion *moti
     return PT_OK;
 }
 
+// The five reproject entry points once their arguments have names (pt_reproject.h, ReprojectArgs): the check, then on the call's
+// stream the scratch of the s plane where the call has moments, the table where something moved, and the launch
+static int run_reproject(pt_ctx *c, const ReprojectArgs &a, void *hip_stream) {
+    ReprojectCall call;
+    const int rc = host::check_reproject(a, call);
+    if (rc) return rc;
+    return run_image_pass(c, hip_stream, [&](hipStream_t st) {
+        if (call.var) {
+            const int rs = c->rv_s.ensure((size_t)a.width * a.height);
+            if (rs) return rs;
+            call.v.s_plane = c->rv_s.p;
+        }
+        ReprojectMotion m{nullptr, 0u};
+        if (call.moved()) {
+            const int ru = upload_motion(c, st, a.motion, a.n_motion, m);
+            if (ru) return ru;
+        }
+        launch_reproject(st, call, &m);
+        return PT_OK;
+    });
+}
+
+int pt_ctx_reproject(pt_ctx *c, uint32_t width, uint32_t height, const pt_reproject_params *params, const pt_camera *cam,
+                     const float *d_color, const float *d_depth, const int32_t *d_object_id, const float *d_normal,
+                     const pt_camera *hist_cam, const float *d_hist_color, const float *d_hist_len, const float *d_hist_depth,
+                     const int32_t *d_hist_object_id, const float *d_hist_normal, float *d_out_color, float *d_out_len,
+                     void *hip_stream) {
+    ReprojectArgs a{};
+    a.ctx = c, a.width = width, a.height = height, a.params = params, a.cam = cam, a.hist_cam = hist_cam;
+    a.color = d_color, a.depth = d_depth, a.object_id = d_object_id, a.normal = d_normal;
+    a.hist_color = d_hist_color, a.hist_len = d_hist_len, a.hist_depth = d_hist_depth, a.hist_object_id = d_hist_object_id;
+    a.hist_normal = d_hist_normal, a.out_color = d_out_color, a.out_len = d_out_len;
+    return run_reproject(c, a, hip_stream);
+}
+
+int pt_ctx_reproject_var(pt_ctx *c, uint32_t width, uint32_t height, const pt_reproject_var_params *params, const pt_camera *cam,
+                         const float *d_color, const float *d_depth, const int32_t *d_object_id, const float *d_normal,
+                         const pt_camera *hist_cam, const float *d_hist_color, const float *d_hist_len, const float *d_hist_moments,
+                         const float *d_hist_depth, const int32_t *d_hist_object_id, const float *d_hist_normal, float *d_out_color,
+                         float *d_out_len, float *d_out_moments, float *d_error, void *hip_stream) {
+    ReprojectArgs a{};
+    a.ctx = c, a.var = true, a.width = width, a.height = height, a.var_params = params, a.cam = cam, a.hist_cam = hist_cam;
+    a.color = d_color, a.depth = d_depth, a.object_id = d_object_id, a.normal = d_normal;
+    a.hist_color = d_hist_color, a.hist_len = d_hist_len, a.hist_moments = d_hist_moments, a.hist_depth = d_hist_depth;
+    a.hist_object_id = d_hist_object_id, a.hist_normal = d_hist_normal;
+    a.out_color = d_out_color, a.out_len = d_out_len, a.out_moments = d_out_moments, a.error = d_error;
+    return run_reproject(c, a, hip_stream);
+}
+
 int pt_ctx_reproject_moved(pt_ctx *c, uint32_t width, uint32_t height, const pt_reproject_params *params, const pt_camera *cam,
                            const float *d_color, const float *d_depth, const int32_t *d_object_id, const float *d_normal,
                            const pt_camera *hist_cam, const float *d_hist_color, const float *d_hist_len, const float *d_hist_depth,
                            const int32_t *d_hist_object_id, const float *d_hist_normal, float *d_out_color, float *d_out_len,
                            const pt_object_motion *motion, uint32_t n_motion, void *hip_stream) {
-    ReprojectFrame f;
-    int how = host::kMotionPlain;
-    const int rc = host::check_reproject_moved(c, width, height, params, cam, d_color, d_depth, d_object_id, d_normal, hist_cam,
-                                               d_hist_color, d_hist_len, d_hist_depth, d_hist_object_id, d_hist_normal, d_out_color,
-                                               d_out_len, motion, n_motion, f, &how);
-    if (rc) return rc;
-    return run_image_pass(c, hip_stream, [&](hipStream_t st) {
-        if (how == host::kMotionPlain || !f.hist_color) {  // nothing moved, or no history for it to move in
-            launch_reproject(st, f);
-            return PT_OK;
-        }
-        ReprojectMotion m;
-        const int ru = upload_motion(c, st, motion, n_motion, m);
-        if (ru) return ru;
-        launch_reproject_moved(st, f, m);
-        return PT_OK;
-    });
+    ReprojectArgs a{};
+    a.ctx = c, a.width = width, a.height = height, a.params = params, a.cam = cam, a.hist_cam = hist_cam;
+    a.color = d_color, a.depth = d_depth, a.object_id = d_object_id, a.normal = d_normal;
+    a.hist_color = d_hist_color, a.hist_len = d_hist_len, a.hist_depth = d_hist_depth, a.hist_object_id = d_hist_object_id;
+    a.hist_normal = d_hist_normal, a.out_color = d_out_color, a.out_len = d_out_len, a.motion = motion, a.n_motion = n_motion;
+    return run_reproject(c, a, hip_stream);
 }
 
 int pt_ctx_reproject_var_moved(pt_ctx *c, uint32_t width, uint32_t height, const pt_reproject_var_params *params, const pt_camera *cam,
@@ -2912,27 +2916,14 @@ int pt_ctx_reproject_var_moved(pt_ctx *c, uint32_t width, uint32_t height, const
                                const float *d_hist_depth, const int32_t *d_hist_object_id, const float *d_hist_normal, float *d_out_color,
                                float *d_out_len, float *d_out_moments, float *d_error, const pt_object_motion *motion, uint32_t n_motion,
                                void *hip_stream) {
-    ReprojectVarFrame v;
-    int how = host::kMotionPlain;
-    const int rc = host::check_reproject_var_moved(c, width, height, params, cam, d_color, d_depth, d_object_id, d_normal, hist_cam,
-                                                   d_hist_color, d_hist_len, d_hist_moments, d_hist_depth, d_hist_object_id,
-                                                   d_hist_normal, d_out_color, d_out_len, d_out_moments, d_error, motion, n_motion, v,
-                                                   &how);
-    if (rc) return rc;
-    return run_image_pass(c, hip_stream, [&](hipStream_t st) {
-        const int rs = c->rv_s.ensure((size_t)width * height);
-        if (rs) return rs;
-        v.s_plane = c->rv_s.p;
-        if (how == host::kMotionPlain || !v.f.hist_color) {
-            launch_reproject_var(st, v);
-            return PT_OK;
-        }
-        ReprojectMotion m;
-        const int ru = upload_motion(c, st, motion, n_motion, m);
-        if (ru) return ru;
-        launch_reproject_var_moved(st, v, m);
-        return PT_OK;
-    });
+    ReprojectArgs a{};
+    a.ctx = c, a.var = true, a.width = width, a.height = height, a.var_params = params, a.cam = cam, a.hist_cam = hist_cam;
+    a.color = d_color, a.depth = d_depth, a.object_id = d_object_id, a.normal = d_normal;
+    a.hist_color = d_hist_color, a.hist_len = d_hist_len, a.hist_moments = d_hist_moments, a.hist_depth = d_hist_depth;
+    a.hist_object_id = d_hist_object_id, a.hist_normal = d_hist_normal;
+    a.out_color = d_out_color, a.out_len = d_out_len, a.out_moments = d_out_moments, a.error = d_error;
+    a.motion = motion, a.n_motion = n_motion;
+    return run_reproject(c, a, hip_stream);
 }
 
 int pt_ctx_reproject_var_weighted(pt_ctx *c, uint32_t width, uint32_t height, const pt_reproject_var_params *params,
@@ -2942,32 +2933,14 @@ int pt_ctx_reproject_var_weighted(pt_ctx *c, uint32_t width, uint32_t height, co
                                   const int32_t *d_hist_object_id, const float *d_hist_normal, float *d_out_color, float *d_out_len,
                                   float *d_out_moments, float *d_error, const pt_object_motion *motion, uint32_t n_motion,
                                   void *hip_stream) {
-    if (!d_spp)  // uniform: pt_ctx_reproject_var_moved itself, its launches and so its bytes
-        return pt_ctx_reproject_var_moved(c, width, height, params, cam, d_color, d_depth, d_object_id, d_normal, hist_cam, d_hist_color,
-                                          d_hist_len, d_hist_moments, d_hist_depth, d_hist_object_id, d_hist_normal, d_out_color,
-                                          d_out_len, d_out_moments, d_error, motion, n_motion, hip_stream);
-    ReprojectVarFrame v;
-    ReprojectWeights wts;
-    int how = host::kMotionPlain;
-    const int rc = host::check_reproject_var_weighted(c, width, height, params, cam, d_color, d_depth, d_object_id, d_normal, d_spp, hist_cam,
-                                                      d_hist_color, d_hist_len, d_hist_moments, d_hist_depth, d_hist_object_id,
-                                                      d_hist_normal, d_out_color, d_out_len, d_out_moments, d_error, motion, n_motion, v,
-                                                      &how, wts);
-    if (rc) return rc;
-    return run_image_pass(c, hip_stream, [&](hipStream_t st) {
-        const int rs = c->rv_s.ensure((size_t)width * height);
-        if (rs) return rs;
-        v.s_plane = c->rv_s.p;
-        if (how == host::kMotionPlain || !v.f.hist_color) {  // nothing moved, or no history for it to move in
-            launch_reproject_var_weighted(st, v, wts, nullptr);
-            return PT_OK;
-        }
-        ReprojectMotion m;
-        const int ru = upload_motion(c, st, motion, n_motion, m);
-        if (ru) return ru;
-        launch_reproject_var_weighted(st, v, wts, &m);
-        return PT_OK;
-    });
+    ReprojectArgs a{};
+    a.ctx = c, a.var = true, a.width = width, a.height = height, a.var_params = params, a.cam = cam, a.hist_cam = hist_cam;
+    a.color = d_color, a.depth = d_depth, a.object_id = d_object_id, a.normal = d_normal, a.spp = d_spp;
+    a.hist_color = d_hist_color, a.hist_len = d_hist_len, a.hist_moments = d_hist_moments, a.hist_depth = d_hist_depth;
+    a.hist_object_id = d_hist_object_id, a.hist_normal = d_hist_normal;
+    a.out_color = d_out_color, a.out_len = d_out_len, a.out_moments = d_out_moments, a.error = d_error;
+    a.motion = motion, a.n_motion = n_motion;
+    return run_reproject(c, a, hip_stream);
 }
 
 int pt_ctx_spp_plane(pt_ctx *c, uint32_t width, uint32_t height, uint32_t base, const uint8_t *d_mask, uint32_t masked, uint32_t *d_spp,

@@ -1738,85 +1738,7 @@ void reproject_view(const pt_camera &cam, const pt_camera *hist_cam, ReprojectVi
     out.same = memcmp(&cam, hist_cam, sizeof(pt_camera)) == 0 ? 1u : 0u;  // nine floats, no padding
 }
 
-int check_reproject(const void *ctx, uint32_t width, uint32_t height, const pt_reproject_params *params, const pt_camera *cam,
-                    const float *d_color, const float *d_depth, const int32_t *d_object_id, const float *d_normal,
-                    const pt_camera *hist_cam, const float *d_hist_color, const float *d_hist_len, const float *d_hist_depth,
-                    const int32_t *d_hist_object_id, const float *d_hist_normal, float *d_out_color, float *d_out_len,
-                    ReprojectFrame &f) {
-    pt_reproject_params P{};
-    if (params) P = *params;
-    if (!finite_nonneg(P.max_history) || !finite_nonneg(P.depth_tol))
-        return refuse("pt_reproject_params: max_history or depth_tol is negative or not finite");
-    if (!(P.normal_min >= -1.0f && P.normal_min <= 1.0f)) return refuse("pt_reproject_params.normal_min is outside [-1, 1]");
-    if (P.flags) return refuse("pt_reproject_params.flags: none is defined");
-    if (!width || !height) return refuse("width and height must be positive");
-    if ((uint64_t)width * height > (1ull << 28)) return refuse("width*height exceeds 2^28");
-    if (!cam || !d_color || !d_depth || !d_object_id || !d_out_color || !d_out_len)
-        return refuse("cam, d_color, d_depth, d_object_id, d_out_color or d_out_len is NULL");
-    const int n_hist = (d_hist_color != nullptr) + (d_hist_len != nullptr) + (d_hist_depth != nullptr) + (d_hist_object_id != nullptr);
-    if (n_hist != 0 && n_hist != 4)
-        return refuse("history: d_hist_color, d_hist_len, d_hist_depth and d_hist_object_id are all NULL or none is");
-    if (n_hist && !hist_cam) return refuse("hist_cam is NULL with a history");
-    if (!ctx) return refuse("ctx is NULL");
-    f = ReprojectFrame{};
-    f.width = width;
-    f.height = height;
-    f.color = d_color;
-    f.depth = d_depth;
-    f.normal = d_normal;
-    f.object_id = d_object_id;
-    f.hist_color = d_hist_color;
-    f.hist_len = d_hist_len;
-    f.hist_depth = d_hist_depth;
-    f.hist_normal = n_hist ? d_hist_normal : nullptr;
-    f.hist_object_id = d_hist_object_id;
-    f.out_color = d_out_color;
-    f.out_len = d_out_len;
-    f.wt = (float)(P.weight ? P.weight : 1u);
-    f.max_history = P.max_history != 0.0f ? P.max_history : kReprojectMaxHistory;
-    f.depth_tol = P.depth_tol != 0.0f ? P.depth_tol : kReprojectDepthTol;
-    f.normal_min = P.normal_min != 0.0f ? P.normal_min : kReprojectNormalMin;
-    reproject_view(*cam, n_hist ? hist_cam : nullptr, f.view);
-    return PT_OK;
-}
-
-int check_reproject_var(const void *ctx, uint32_t width, uint32_t height, const pt_reproject_var_params *params, const pt_camera *cam,
-                        const float *d_color, const float *d_depth, const int32_t *d_object_id, const float *d_normal,
-                        const pt_camera *hist_cam, const float *d_hist_color, const float *d_hist_len, const float *d_hist_moments,
-                        const float *d_hist_depth, const int32_t *d_hist_object_id, const float *d_hist_normal, float *d_out_color,
-                        float *d_out_len, float *d_out_moments, float *d_error, ReprojectVarFrame &v) {
-    pt_reproject_var_params P{};
-    if (params) P = *params;
-    if (!finite_nonneg(P.max_history) || !finite_nonneg(P.depth_tol))
-        return refuse("pt_reproject_var_params: max_history or depth_tol is negative or not finite");
-    if (!(P.normal_min >= -1.0f && P.normal_min <= 1.0f)) return refuse("pt_reproject_var_params.normal_min is outside [-1, 1]");
-    if (P.radius > kReprojectVarMaxRadius) return refuse("pt_reproject_var_params.radius exceeds 3");
-    if (P.flags) return refuse("pt_reproject_var_params.flags: none is defined");
-    if (!width || !height) return refuse("width and height must be positive");
-    if ((uint64_t)width * height > (1ull << 28)) return refuse("width*height exceeds 2^28");
-    if (!cam || !d_color || !d_depth || !d_object_id || !d_out_color || !d_out_len || !d_out_moments || !d_error)
-        return refuse("cam, d_color, d_depth, d_object_id, d_out_color, d_out_len, d_out_moments or d_error is NULL");
-    const int n_hist = (d_hist_color != nullptr) + (d_hist_len != nullptr) + (d_hist_moments != nullptr) + (d_hist_depth != nullptr) +
-                       (d_hist_object_id != nullptr);
-    if (n_hist != 0 && n_hist != 5)
-        return refuse("history: d_hist_color, d_hist_len, d_hist_moments, d_hist_depth and d_hist_object_id are all NULL or none is");
-    if (n_hist && !hist_cam) return refuse("hist_cam is NULL with a history");
-    if (!ctx) return refuse("ctx is NULL");
-    // what is left is pt_ctx_reproject's call, which has passed every one of its own checks above
-    const pt_reproject_params Q = {P.weight, P.max_history, P.depth_tol, P.normal_min, 0u};
-    v = ReprojectVarFrame{};
-    const int rc = check_reproject(ctx, width, height, &Q, cam, d_color, d_depth, d_object_id, d_normal, hist_cam, d_hist_color,
-                                   d_hist_len, d_hist_depth, d_hist_object_id, d_hist_normal, d_out_color, d_out_len, v.f);
-    if (rc) return rc;
-    v.hist_moments = reinterpret_cast<const ReprojectMom *>(d_hist_moments);
-    v.out_moments = reinterpret_cast<ReprojectMom *>(d_out_moments);
-    v.error = d_error;
-    v.long_len = (float)(P.min_frames ? P.min_frames : kReprojectVarMinFrames) * v.f.wt;
-    v.radius = P.radius ? P.radius : kReprojectVarRadius;
-    return PT_OK;
-}
-
-// ---- pt_ctx_reproject_moved, pt_ctx_reproject_var_moved: the plain call's refusals, then the table's
+// ---- the motion table of pt_ctx_reproject_moved, pt_ctx_reproject_var_moved and pt_ctx_reproject_var_weighted
 int check_reproject_motion(int rc_plain, const pt_object_motion *motion, uint32_t n_motion, int *how) {
     if (rc_plain) return rc_plain;
     if (n_motion > kReprojectMaxMotion) return refuse("n_motion exceeds 2^20");
@@ -1837,43 +1759,68 @@ int check_reproject_motion(int rc_plain, const pt_object_motion *motion, uint32_
     return PT_OK;
 }
 
-int check_reproject_moved(const void *ctx, uint32_t width, uint32_t height, const pt_reproject_params *params, const pt_camera *cam,
-                          const float *d_color, const float *d_depth, const int32_t *d_object_id, const float *d_normal,
-                          const pt_camera *hist_cam, const float *d_hist_color, const float *d_hist_len, const float *d_hist_depth,
-                          const int32_t *d_hist_object_id, const float *d_hist_normal, float *d_out_color, float *d_out_len,
-                          const pt_object_motion *motion, uint32_t n_motion, ReprojectFrame &f, int *how) {
-    return check_reproject_motion(check_reproject(ctx, width, height, params, cam, d_color, d_depth, d_object_id, d_normal, hist_cam,
-                                                  d_hist_color, d_hist_len, d_hist_depth, d_hist_object_id, d_hist_normal, d_out_color,
-                                                  d_out_len, f),
-                                  motion, n_motion, how);
-}
-
-int check_reproject_var_moved(const void *ctx, uint32_t width, uint32_t height, const pt_reproject_var_params *params,
-                              const pt_camera *cam, const float *d_color, const float *d_depth, const int32_t *d_object_id,
-                              const float *d_normal, const pt_camera *hist_cam, const float *d_hist_color, const float *d_hist_len,
-                              const float *d_hist_moments, const float *d_hist_depth, const int32_t *d_hist_object_id,
-                              const float *d_hist_normal, float *d_out_color, float *d_out_len, float *d_out_moments, float *d_error,
-                              const pt_object_motion *motion, uint32_t n_motion, ReprojectVarFrame &v, int *how) {
-    return check_reproject_motion(check_reproject_var(ctx, width, height, params, cam, d_color, d_depth, d_object_id, d_normal, hist_cam,
-                                                      d_hist_color, d_hist_len, d_hist_moments, d_hist_depth, d_hist_object_id,
-                                                      d_hist_normal, d_out_color, d_out_len, d_out_moments, d_error, v),
-                                  motion, n_motion, how);
-}
-
-// ---- pt_ctx_reproject_var_weighted: pt_ctx_reproject_var_moved's refusals; the plane is never refused
-int check_reproject_var_weighted(const void *ctx, uint32_t width, uint32_t height, const pt_reproject_var_params *params,
-                                 const pt_camera *cam, const float *d_color, const float *d_depth, const int32_t *d_object_id,
-                                 const float *d_normal, const uint32_t *d_spp, const pt_camera *hist_cam, const float *d_hist_color,
-                                 const float *d_hist_len, const float *d_hist_moments, const float *d_hist_depth,
-                                 const int32_t *d_hist_object_id, const float *d_hist_normal, float *d_out_color, float *d_out_len,
-                                 float *d_out_moments, float *d_error, const pt_object_motion *motion, uint32_t n_motion,
-                                 ReprojectVarFrame &v, int *how, ReprojectWeights &wts) {
-    const int rc = check_reproject_var_moved(ctx, width, height, params, cam, d_color, d_depth, d_object_id, d_normal, hist_cam, d_hist_color,
-                                             d_hist_len, d_hist_moments, d_hist_depth, d_hist_object_id, d_hist_normal, d_out_color,
-                                             d_out_len, d_out_moments, d_error, motion, n_motion, v, how);
+// ---- the five entry points: one call (pt_reproject.h, ReprojectArgs).  A colour-only call is a var call whose min_frames and
+// radius are 0 and which has no moments, error or plane; what differs in a refusal is the params struct's name and the two
+// lists of pointers.
+int check_reproject(const ReprojectArgs &a, ReprojectCall &call) {
+    pt_reproject_var_params P{};
+    if (a.var && a.var_params) P = *a.var_params;
+    if (!a.var && a.params) P = {a.params->weight, a.params->max_history, a.params->depth_tol, a.params->normal_min, 0u, 0u, a.params->flags};
+    // (the message is put together only when there is one: an accepted call allocates nothing)
+    auto refuse_params = [&](const char *what) {
+        return refuse((std::string(a.var ? "pt_reproject_var_params" : "pt_reproject_params") + what).c_str());
+    };
+    if (!finite_nonneg(P.max_history) || !finite_nonneg(P.depth_tol))
+        return refuse_params(": max_history or depth_tol is negative or not finite");
+    if (!(P.normal_min >= -1.0f && P.normal_min <= 1.0f)) return refuse_params(".normal_min is outside [-1, 1]");
+    if (P.radius > kReprojectVarMaxRadius) return refuse_params(".radius exceeds 3");
+    if (P.flags) return refuse_params(".flags: none is defined");
+    if (!a.width || !a.height) return refuse("width and height must be positive");
+    if ((uint64_t)a.width * a.height > (1ull << 28)) return refuse("width*height exceeds 2^28");
+    if (!a.cam || !a.color || !a.depth || !a.object_id || !a.out_color || !a.out_len || (a.var && (!a.out_moments || !a.error)))
+        return refuse(a.var ? "cam, d_color, d_depth, d_object_id, d_out_color, d_out_len, d_out_moments or d_error is NULL"
+                            : "cam, d_color, d_depth, d_object_id, d_out_color or d_out_len is NULL");
+    const int n_hist = (a.hist_color != nullptr) + (a.hist_len != nullptr) + (a.hist_depth != nullptr) + (a.hist_object_id != nullptr) +
+                       (a.var && a.hist_moments != nullptr);
+    if (n_hist != 0 && n_hist != (a.var ? 5 : 4))
+        return refuse(a.var ? "history: d_hist_color, d_hist_len, d_hist_moments, d_hist_depth and d_hist_object_id are all NULL or none is"
+                            : "history: d_hist_color, d_hist_len, d_hist_depth and d_hist_object_id are all NULL or none is");
+    if (n_hist && !a.hist_cam) return refuse("hist_cam is NULL with a history");
+    if (!a.ctx) return refuse("ctx is NULL");
+    int how = kMotionPlain;
+    const int rc = check_reproject_motion(PT_OK, a.motion, a.n_motion, &how);
     if (rc) return rc;
-    wts.spp = d_spp;
-    wts.min_frames = (float)(params && params->min_frames ? params->min_frames : kReprojectVarMinFrames);
+    call = ReprojectCall{};
+    call.var = a.var;
+    call.weighted = a.var && a.spp;
+    call.how = how;
+    ReprojectFrame &f = call.v.f;
+    f.width = a.width;
+    f.height = a.height;
+    f.color = a.color;
+    f.depth = a.depth;
+    f.normal = a.normal;
+    f.object_id = a.object_id;
+    f.hist_color = a.hist_color;
+    f.hist_len = a.hist_len;
+    f.hist_depth = a.hist_depth;
+    f.hist_normal = n_hist ? a.hist_normal : nullptr;
+    f.hist_object_id = a.hist_object_id;
+    f.out_color = a.out_color;
+    f.out_len = a.out_len;
+    f.wt = (float)(P.weight ? P.weight : 1u);
+    f.max_history = P.max_history != 0.0f ? P.max_history : kReprojectMaxHistory;
+    f.depth_tol = P.depth_tol != 0.0f ? P.depth_tol : kReprojectDepthTol;
+    f.normal_min = P.normal_min != 0.0f ? P.normal_min : kReprojectNormalMin;
+    reproject_view(*a.cam, n_hist ? a.hist_cam : nullptr, f.view);
+    if (!a.var) return PT_OK;
+    call.v.hist_moments = reinterpret_cast<const ReprojectMom *>(a.hist_moments);
+    call.v.out_moments = reinterpret_cast<ReprojectMom *>(a.out_moments);
+    call.v.error = a.error;
+    call.wts.spp = a.spp;
+    call.wts.min_frames = (float)(P.min_frames ? P.min_frames : kReprojectVarMinFrames);
+    call.v.long_len = call.wts.min_frames * f.wt;
+    call.v.radius = P.radius ? P.radius : kReprojectVarRadius;
     return PT_OK;
 }
 

@@ -5,8 +5,10 @@
 // pt_reproject_project_host (host/scene_io.cpp) is the host instantiation of the projection the kernel compiles, as
 // pt_present_quantize_host is of pt_present.h.  pt_ctx_reproject_moved and pt_ctx_reproject_var_moved - history carried through
 // pt_ctx_set_object's edits by a per-object motion table - are the same functions with MOVED compiled in, and
-// pt_ctx_reproject_var_weighted - a plane of per-pixel sample counts in place of the one weight - with WEIGHTED.  A translation
-// unit of its own: pt_kernels.s, and so pt_kernel_isa_hash(), describes the pass kernels only.
+// pt_ctx_reproject_var_weighted - a plane of per-pixel sample counts in place of the one weight - with WEIGHTED.  Around the
+// kernels the five entry points are one call, at the end of this file: ReprojectArgs names what the caller passed,
+// host::check_reproject (pt_host.cpp) refuses or fills a ReprojectCall, launch_reproject (pt_reproject.hip) picks the kernels.
+// A translation unit of its own: pt_kernels.s, and so pt_kernel_isa_hash(), describes the pass kernels only.
 #pragma once
 
 #include "../../include/ptrace.h"
@@ -94,7 +96,7 @@ PT_HD pt_object_motion reproject_rec(const ReprojectMotion &m, int32_t id) {
 
 // ---- pt_ctx_reproject_var_weighted: the plane of per-pixel sample counts ("THE ARITHMETIC" of pt_ctx_reproject_var_weighted in
 // include/ptrace.h).  A kernel argument of its own, as the motion table is: ReprojectFrame and ReprojectVarFrame stay what they
-// are.  The uniform value w0 is the frame's f.wt, and (float)min_frames * w0 its long_len.
+// are.  The uniform value w0 is the frame's f.wt, and (float)min_frames * w0 its long_len.  spp NULL: the uniform call.
 struct ReprojectWeights {
     const uint32_t *spp;  // width * height counts; 0: the pixel holds no samples this frame
     float min_frames;     // (float)min_frames: a pixel with count c > 0 is long from min_frames * (float)c samples on
@@ -454,62 +456,60 @@ PT_HD float reproject_var_short_pixel(const ReprojectVarFrame &v, const Src &src
     return reproject_var_error(vs > vt ? vs : vt, wt / v.f.out_len[idx], out);
 }
 
+// ---- A call of any of the five entry points.  They are ONE call with three optional parts: the moments planes make it a _var
+// call, a motion table that is not all IDENTITY a _moved one, a plane of counts the _weighted one.
+namespace host {
+// How a call runs its table.  kMotionPlain: motion NULL, n_motion 0 or every record IDENTITY - the plain kernels, unchanged.
+// kMotionTable: the moved kernels.
+constexpr int kMotionPlain = 0, kMotionTable = 1;
+constexpr uint32_t kReprojectMaxMotion = 1u << 20;
+}  // namespace host
+
+// What the caller passed, by name: the arguments of include/ptrace.h without their d_ prefix.  An entry point leaves what it
+// does not take at zero.  Host pointers on the host, device pointers on the device.
+struct ReprojectArgs {
+    const void *ctx;  // tested against NULL, never dereferenced: the host programs pass any address
+    bool var;         // a pt_ctx_reproject_var* entry point: var_params and its messages, the moments and error are compulsory
+    uint32_t width, height;
+    const pt_reproject_params *params;          // without var
+    const pt_reproject_var_params *var_params;  // with var
+    const pt_camera *cam, *hist_cam;
+    const float *color, *depth, *normal;
+    const int32_t *object_id;
+    const float *hist_color, *hist_len, *hist_moments, *hist_depth, *hist_normal;
+    const int32_t *hist_object_id;
+    float *out_color, *out_len, *out_moments, *error;
+    const uint32_t *spp;  // the plane of counts; NULL: the uniform call.  Never refused.
+    const pt_object_motion *motion;
+    uint32_t n_motion;
+};
+
+// The call once it has passed: the frames with the defaults filled in, and which kernels it takes
+struct ReprojectCall {
+    ReprojectVarFrame v;   // without var, v.f alone; v.s_plane is the caller's to set
+    ReprojectWeights wts;  // the plane and (float)min_frames
+    bool var, weighted;    // weighted: var with a plane
+    int how;               // host::kMotionPlain or host::kMotionTable: what the table's records say
+    // the moved kernels and the table's upload: something moved, and there is a history for it to move in
+    bool moved() const { return how == host::kMotionTable && v.f.hist_color; }
+};
+
 namespace host {
 // the view of a camera pair; hist_cam NULL: the first frame, nothing of the history is set
 void reproject_view(const pt_camera &cam, const pt_camera *hist_cam, ReprojectView &out);
-// pt_ctx_reproject's refusals in the header's order (PT_ERR_INVALID + message); PT_OK: `f` holds the call with the defaults
-// filled in.  No device is touched.
-int check_reproject(const void *ctx, uint32_t width, uint32_t height, const pt_reproject_params *params, const pt_camera *cam,
-                    const float *d_color, const float *d_depth, const int32_t *d_object_id, const float *d_normal,
-                    const pt_camera *hist_cam, const float *d_hist_color, const float *d_hist_len, const float *d_hist_depth,
-                    const int32_t *d_hist_object_id, const float *d_hist_normal, float *d_out_color, float *d_out_len,
-                    ReprojectFrame &f);
-// pt_ctx_reproject_var's refusals in the header's order; PT_OK: `v` holds the call with the defaults filled in, but for
-// v.s_plane, which the caller owns.  No device is touched.
-int check_reproject_var(const void *ctx, uint32_t width, uint32_t height, const pt_reproject_var_params *params, const pt_camera *cam,
-                        const float *d_color, const float *d_depth, const int32_t *d_object_id, const float *d_normal,
-                        const pt_camera *hist_cam, const float *d_hist_color, const float *d_hist_len, const float *d_hist_moments,
-                        const float *d_hist_depth, const int32_t *d_hist_object_id, const float *d_hist_normal, float *d_out_color,
-                        float *d_out_len, float *d_out_moments, float *d_error, ReprojectVarFrame &v);
-// How a pt_ctx_reproject*_moved call runs its table.  kMotionPlain: motion NULL, n_motion 0 or every record IDENTITY - the
-// plain launch, unchanged.  kMotionTable: the moved kernels.
-constexpr int kMotionPlain = 0, kMotionTable = 1;
-constexpr uint32_t kReprojectMaxMotion = 1u << 20;
-// the moved calls' own refusals, in the header's order, after the plain call's have passed (rc_plain is its verdict and is
+// The refusals of all five entry points, each test made once and in the header's order (PT_ERR_INVALID + message; the
+// params struct a message names is the entry point's): the params, the size, the compulsory pointers, the history, ctx, then
+// the table's (check_reproject_motion).  PT_OK: `call` holds the call.  No device is touched.
+int check_reproject(const ReprojectArgs &a, ReprojectCall &call);
+// the table's own refusals, in the header's order, after the rest of the call has passed (rc_plain is that verdict and is
 // returned when not PT_OK); PT_OK: *how is kMotionPlain or kMotionTable.  O(n_motion) on the host, no device.
 int check_reproject_motion(int rc_plain, const pt_object_motion *motion, uint32_t n_motion, int *how);
-int check_reproject_moved(const void *ctx, uint32_t width, uint32_t height, const pt_reproject_params *params, const pt_camera *cam,
-                          const float *d_color, const float *d_depth, const int32_t *d_object_id, const float *d_normal,
-                          const pt_camera *hist_cam, const float *d_hist_color, const float *d_hist_len, const float *d_hist_depth,
-                          const int32_t *d_hist_object_id, const float *d_hist_normal, float *d_out_color, float *d_out_len,
-                          const pt_object_motion *motion, uint32_t n_motion, ReprojectFrame &f, int *how);
-int check_reproject_var_moved(const void *ctx, uint32_t width, uint32_t height, const pt_reproject_var_params *params,
-                              const pt_camera *cam, const float *d_color, const float *d_depth, const int32_t *d_object_id,
-                              const float *d_normal, const pt_camera *hist_cam, const float *d_hist_color, const float *d_hist_len,
-                              const float *d_hist_moments, const float *d_hist_depth, const int32_t *d_hist_object_id,
-                              const float *d_hist_normal, float *d_out_color, float *d_out_len, float *d_out_moments, float *d_error,
-                              const pt_object_motion *motion, uint32_t n_motion, ReprojectVarFrame &v, int *how);
-// pt_ctx_reproject_var_weighted's refusals: pt_ctx_reproject_var_moved's, in its order - d_spp is never refused.  PT_OK: `v` and
-// *how as there, and `wts` holds the plane (NULL: the call is pt_ctx_reproject_var_moved) and (float)min_frames.
-int check_reproject_var_weighted(const void *ctx, uint32_t width, uint32_t height, const pt_reproject_var_params *params,
-                                 const pt_camera *cam, const float *d_color, const float *d_depth, const int32_t *d_object_id,
-                                 const float *d_normal, const uint32_t *d_spp, const pt_camera *hist_cam, const float *d_hist_color,
-                                 const float *d_hist_len, const float *d_hist_moments, const float *d_hist_depth,
-                                 const int32_t *d_hist_object_id, const float *d_hist_normal, float *d_out_color, float *d_out_len,
-                                 float *d_out_moments, float *d_error, const pt_object_motion *motion, uint32_t n_motion,
-                                 ReprojectVarFrame &v, int *how, ReprojectWeights &wts);
 }  // namespace host
 
 #if defined(__HIPCC__)
-// one lane per pixel
-void launch_reproject(hipStream_t st, const ReprojectFrame &f);
-// kernel A, one lane per pixel, then kernel B, one workgroup per tile of 32 x 8
-void launch_reproject_var(hipStream_t st, const ReprojectVarFrame &v);
-// the same with the motion table (device memory, 16-byte aligned)
-void launch_reproject_moved(hipStream_t st, const ReprojectFrame &f, const ReprojectMotion &m);
-void launch_reproject_var_moved(hipStream_t st, const ReprojectVarFrame &v, const ReprojectMotion &m);
-// the same with the plane of counts (device memory); m NULL: nothing moved
-void launch_reproject_var_weighted(hipStream_t st, const ReprojectVarFrame &v, const ReprojectWeights &wts, const ReprojectMotion *m);
+// The kernels of a call that has passed: colour only - one lane per pixel; with moments - kernel A, one lane per pixel, then
+// kernel B, one workgroup per tile of 32 x 8.  `table` (device memory, 16-byte aligned) is read when call.moved().
+void launch_reproject(hipStream_t st, const ReprojectCall &call, const ReprojectMotion *table);
 #endif
 
 }  // namespace pt

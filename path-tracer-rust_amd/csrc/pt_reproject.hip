@@ -1,4 +1,5 @@
-// pt_reproject.hip — pt_ctx_reproject's kernel: the history frame gathered into this frame's pixels and blended by the history
+// pt_reproject.hip — the kernels of pt_ctx_reproject and its _var, _moved and _weighted forms, and launch_reproject, the one
+// launcher that picks among them: the history frame gathered into this frame's pixels and blended by the history
 // length.  The arithmetic is the contract of include/ptrace.h ("THE ARITHMETIC" of pt_ctx_reproject), operation for operation;
 // the pixel is pt_reproject.h's reproject_pixel, which the host compiles too.  Built with -ffp-contract=off and correctly
 // rounded / and sqrt, so a restatement in numpy binary32 (tests/reproject_ref.py) gives the same bytes.
@@ -139,12 +140,6 @@ __global__ __launch_bounds__(kReprojectBlock) void k_reproject_var_moved(const R
     reproject_var_pixel<true>(v, idx, &m);
 }
 
-void launch_var_spatial(hipStream_t st, const ReprojectVarFrame &v) {
-    // a grid of one dimension: a frame of one column and 2^28 rows is 2^25 tiles down, more than a grid's y takes
-    const uint32_t tiles_x = (v.f.width + kRvTileW - 1u) / kRvTileW, tiles_y = (v.f.height + kRvTileH - 1u) / kRvTileH;
-    hipLaunchKernelGGL(k_reproject_var_spatial, dim3(tiles_x * tiles_y), dim3(kRvTileW * kRvTileH), 0, st, v, tiles_x);
-}
-
 // ---- pt_ctx_reproject_var_weighted: the two var kernels with the plane of per-pixel counts (reproject_var_pixel<MOVED, true>).
 // Kernel A reads 4 B more per pixel - the pixel's own count, one non-temporal load issued with its colour's: 116 B per pixel at
 // most - and does per lane what the plain kernel does with a uniform: the count as a float is the pixel's wt, and a pixel without
@@ -166,38 +161,36 @@ __global__ __launch_bounds__(kRvTileW *kRvTileH) void k_reproject_var_spatial_we
 
 }  // namespace
 
-void launch_reproject_moved(hipStream_t st, const ReprojectFrame &f, const ReprojectMotion &m) {
-    const uint32_t npix = f.width * f.height;
-    hipLaunchKernelGGL(k_reproject_moved, dim3((npix + kReprojectBlock - 1u) / kReprojectBlock), dim3(kReprojectBlock), 0, st, f, m, npix);
-}
-
-void launch_reproject_var_moved(hipStream_t st, const ReprojectVarFrame &v, const ReprojectMotion &m) {
-    const uint32_t npix = v.f.width * v.f.height;
-    hipLaunchKernelGGL(k_reproject_var_moved, dim3((npix + kReprojectBlock - 1u) / kReprojectBlock), dim3(kReprojectBlock), 0, st, v, m,
-                       npix);
-    launch_var_spatial(st, v);  // the spatial estimate does not read the table
-}
-
-void launch_reproject_var_weighted(hipStream_t st, const ReprojectVarFrame &v, const ReprojectWeights &wts, const ReprojectMotion *m) {
-    const uint32_t npix = v.f.width * v.f.height;
+// The one launcher.  Which kernel A: by the moments, the plane and call.moved() - without a history nothing can have moved, so
+// the plain kernels run whatever the table says.  Kernel B reads neither the history nor the table.
+void launch_reproject(hipStream_t st, const ReprojectCall &call, const ReprojectMotion *table) {
+    const ReprojectVarFrame &v = call.v;
+    const uint32_t npix = v.f.width * v.f.height;  // at most 2^28: 2^20 workgroups
     const dim3 grid((npix + kReprojectBlock - 1u) / kReprojectBlock), block(kReprojectBlock);
-    if (m)
-        hipLaunchKernelGGL((k_reproject_var_weighted<true>), grid, block, 0, st, v, *m, wts, npix);
+    const bool moved = call.moved();
+    const ReprojectMotion m = moved ? *table : ReprojectMotion{nullptr, 0u};
+    if (!call.var) {
+        if (moved)
+            hipLaunchKernelGGL(k_reproject_moved, grid, block, 0, st, v.f, m, npix);
+        else
+            hipLaunchKernelGGL(k_reproject, grid, block, 0, st, v.f, npix);
+        return;
+    }
+    if (call.weighted && moved)
+        hipLaunchKernelGGL((k_reproject_var_weighted<true>), grid, block, 0, st, v, m, call.wts, npix);
+    else if (call.weighted)
+        hipLaunchKernelGGL((k_reproject_var_weighted<false>), grid, block, 0, st, v, m, call.wts, npix);
+    else if (moved)
+        hipLaunchKernelGGL(k_reproject_var_moved, grid, block, 0, st, v, m, npix);
     else
-        hipLaunchKernelGGL((k_reproject_var_weighted<false>), grid, block, 0, st, v, ReprojectMotion{nullptr, 0u}, wts, npix);
+        hipLaunchKernelGGL(k_reproject_var, grid, block, 0, st, v, npix);
+    // a grid of one dimension: a frame of one column and 2^28 rows is 2^25 tiles down, more than a grid's y takes
     const uint32_t tiles_x = (v.f.width + kRvTileW - 1u) / kRvTileW, tiles_y = (v.f.height + kRvTileH - 1u) / kRvTileH;
-    hipLaunchKernelGGL(k_reproject_var_spatial_weighted, dim3(tiles_x * tiles_y), dim3(kRvTileW * kRvTileH), 0, st, v, wts.spp, tiles_x);
-}
-
-void launch_reproject_var(hipStream_t st, const ReprojectVarFrame &v) {
-    const uint32_t npix = v.f.width * v.f.height;  // at most 2^28
-    hipLaunchKernelGGL(k_reproject_var, dim3((npix + kReprojectBlock - 1u) / kReprojectBlock), dim3(kReprojectBlock), 0, st, v, npix);
-    launch_var_spatial(st, v);
-}
-
-void launch_reproject(hipStream_t st, const ReprojectFrame &f) {
-    const uint32_t npix = f.width * f.height;  // at most 2^28: 2^20 workgroups
-    hipLaunchKernelGGL(k_reproject, dim3((npix + kReprojectBlock - 1u) / kReprojectBlock), dim3(kReprojectBlock), 0, st, f, npix);
+    const dim3 tiles(tiles_x * tiles_y), tile(kRvTileW * kRvTileH);
+    if (call.weighted)
+        hipLaunchKernelGGL(k_reproject_var_spatial_weighted, tiles, tile, 0, st, v, call.wts.spp, tiles_x);
+    else
+        hipLaunchKernelGGL(k_reproject_var_spatial, tiles, tile, 0, st, v, tiles_x);
 }
 
 }  // namespace pt

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/ptrace.h"
+#include "../csrc/pt_reproject.h"
 
 namespace pt {
 static std::string g_error;
@@ -90,4 +91,17 @@ static Frames make_frames(uint32_t n, uint32_t seed, bool var) {
         f.splane.assign(n, -1.0f);
     }
     return f;
+}
+
+// The reproject call over such frames: the frame, its whole history and the outputs - `var`: the moments and the error too;
+// `normals`: both normal planes.  ctx is the frames' address; params, spp and the table are the caller's to set.
+static pt::ReprojectArgs frames_args(Frames &fr, uint32_t w, uint32_t h, const pt_camera *cam, const pt_camera *hist_cam, bool var,
+                                     bool normals) {
+    pt::ReprojectArgs a{};
+    a.ctx = &fr, a.var = var, a.width = w, a.height = h, a.cam = cam, a.hist_cam = hist_cam;
+    a.color = fr.color.data(), a.depth = fr.depth.data(), a.object_id = fr.id.data(), a.normal = normals ? fr.normal.data() : nullptr;
+    a.hist_color = fr.hcolor.data(), a.hist_len = fr.hlen.data(), a.hist_depth = fr.hdepth.data(), a.hist_object_id = fr.hid.data();
+    a.hist_normal = normals ? fr.hnormal.data() : nullptr, a.out_color = fr.out.data(), a.out_len = fr.len.data();
+    if (var) a.hist_moments = fr.hmom.data(), a.out_moments = fr.mom.data(), a.error = fr.err.data();
+    return a;
 }

@@ -59,12 +59,18 @@ int main() {
         int32_t ibuf[4];
         const float *F = buf;
         const int32_t *I = ibuf;
-        pt::ReprojectFrame f;
+        pt::ReprojectCall call;
+        pt::ReprojectFrame &f = call.v.f;
         const void *ctx = buf;  // never dereferenced
+        // col: the frame's own planes; hc / hl: history colour (with depth and id) / length; out: colour and length
         auto check = [&](const pt_reproject_params *p, uint32_t w, uint32_t h, const pt_camera *c, const float *col, const float *hc,
                          const float *hl, const pt_camera *hcam, float *out, const void *cx) {
-            return pt::host::check_reproject(cx, w, h, p, c, col, col ? F : nullptr, col ? I : nullptr, nullptr, hcam, hc, hl, hc,
-                                             hc ? I : nullptr, nullptr, out, out, f);
+            pt::ReprojectArgs a{};
+            a.ctx = cx, a.width = w, a.height = h, a.params = p, a.cam = c, a.hist_cam = hcam;
+            a.color = col, a.depth = col ? F : nullptr, a.object_id = col ? I : nullptr;
+            a.hist_color = hc, a.hist_len = hl, a.hist_depth = hc, a.hist_object_id = hc ? I : nullptr;
+            a.out_color = out, a.out_len = out;
+            return pt::host::check_reproject(a, call);
         };
         const pt_reproject_params bad_mh = {0, -1.0f, NAN, 2.0f, 1}, bad_dt = {0, 1.0f, INFINITY, 2.0f, 1}, bad_nm = {0, 1.0f, 1.0f, NAN, 1},
                                   bad_nm2 = {0, 1.0f, 1.0f, -1.5f, 1}, bad_flags = {0, 1.0f, 1.0f, -1.0f, 1}, fine = {3, 8.0f, 0.1f, 1.0f, 0};
@@ -101,11 +107,11 @@ int main() {
             for (int with_normals = 0; with_normals < 2; ++with_normals) {
                 Frames fr = make_frames(n, w * 131u + h, false);
                 const pt_reproject_params p = {4, 64.0f, 0.05f, 0.5f, 0};
-                pt::ReprojectFrame f;
-                CHECK(pt::host::check_reproject(&fr, w, h, &p, &cam, fr.color.data(), fr.depth.data(), fr.id.data(),
-                                                with_normals ? fr.normal.data() : nullptr, hc, fr.hcolor.data(), fr.hlen.data(),
-                                                fr.hdepth.data(), fr.hid.data(), with_normals ? fr.hnormal.data() : nullptr,
-                                                fr.out.data(), fr.len.data(), f) == PT_OK);
+                pt::ReprojectCall call;
+                pt::ReprojectArgs a = frames_args(fr, w, h, &cam, hc, false, with_normals);
+                a.params = &p;
+                CHECK(pt::host::check_reproject(a, call) == PT_OK);
+                const pt::ReprojectFrame &f = call.v.f;
                 for (uint32_t i = 0; i < n; ++i) {
                     pt::reproject_pixel(f, i, &fr.out[3 * (size_t)i], &fr.len[i]);
                     CHECK(fr.len[i] >= 4.0f && fr.len[i] <= 64.0f);
@@ -124,9 +130,12 @@ int main() {
         }
         // the first frame, and in place
         Frames fr = make_frames(n, 7u, false);
-        pt::ReprojectFrame f;
-        CHECK(pt::host::check_reproject(&fr, w, h, nullptr, &cam, fr.color.data(), fr.depth.data(), fr.id.data(), nullptr, nullptr, nullptr,
-                                        nullptr, nullptr, nullptr, nullptr, fr.color.data(), fr.len.data(), f) == PT_OK);
+        pt::ReprojectCall call;
+        pt::ReprojectArgs a{};
+        a.ctx = &fr, a.width = w, a.height = h, a.cam = &cam, a.color = fr.color.data(), a.depth = fr.depth.data();
+        a.object_id = fr.id.data(), a.out_color = fr.color.data(), a.out_len = fr.len.data();
+        CHECK(pt::host::check_reproject(a, call) == PT_OK);
+        const pt::ReprojectFrame &f = call.v.f;
         const std::vector<float> before = fr.color;
         for (uint32_t i = 0; i < n; ++i) pt::reproject_pixel(f, i, &fr.color[3 * (size_t)i], &fr.len[i]);
         CHECK(fr.color == before);

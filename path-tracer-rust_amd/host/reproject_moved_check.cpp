@@ -121,21 +121,26 @@ int main() {
         const float *F = buf;
         const int32_t *Ii = ibuf;
         const void *ctx = buf;  // never dereferenced
-        pt::ReprojectFrame f;
-        pt::ReprojectVarFrame v;
-        int how = -1;
+        pt::ReprojectCall pc, vc;
+        pt::ReprojectFrame &f = pc.v.f;
+        pt::ReprojectVarFrame &v = vc.v;
+        int how = -1;  // the verdict of the last call that passed
         const pt_object_motion bad[3] = {I, M, {{0.0f, INFINITY, 0.0f}, -2.0f}}, neg[1] = {{{0.0f, 0.0f, 0.0f}, -1.0f}},
                                nan_s[1] = {{{0.0f, 0.0f, 0.0f}, NAN}}, inf_o[2] = {I, {{0.0f, 0.0f, -INFINITY}, 1.0f}},
                                fine[4] = {I, {{0.5f, 0.0f, 0.0f}, 1.0f}, M, {{0.0f, 0.0f, 0.0f}, 2.0f}}, idents[2] = {I, I},
                                marked[2] = {I, {{NAN, NAN, NAN}, -0.0f}};
-        auto plain = [&](const void *cx, const pt_object_motion *m, uint32_t n) {
-            return pt::host::check_reproject_moved(cx, 2, 2, nullptr, &cam, F, F, Ii, nullptr, &near_cam, F, F, F, Ii, nullptr, buf, buf, m, n,
-                                                   f, &how);
+        auto run = [&](bool is_var, pt::ReprojectCall &call, const void *cx, const pt_object_motion *m, uint32_t n) {
+            pt::ReprojectArgs a{};
+            a.ctx = cx, a.var = is_var, a.width = 2, a.height = 2, a.cam = &cam, a.hist_cam = &near_cam;
+            a.color = F, a.depth = F, a.object_id = Ii, a.hist_color = F, a.hist_len = F, a.hist_depth = F, a.hist_object_id = Ii;
+            a.out_color = buf, a.out_len = buf, a.motion = m, a.n_motion = n;
+            if (is_var) a.hist_moments = F, a.out_moments = buf, a.error = buf;
+            const int rc = pt::host::check_reproject(a, call);
+            if (rc == PT_OK) how = call.how;
+            return rc;
         };
-        auto var = [&](const void *cx, const pt_object_motion *m, uint32_t n) {
-            return pt::host::check_reproject_var_moved(cx, 2, 2, nullptr, &cam, F, F, Ii, nullptr, &near_cam, F, F, F, F, Ii, nullptr, buf, buf,
-                                                       buf, buf, m, n, v, &how);
-        };
+        auto plain = [&](const void *cx, const pt_object_motion *m, uint32_t n) { return run(false, pc, cx, m, n); };
+        auto var = [&](const void *cx, const pt_object_motion *m, uint32_t n) { return run(true, vc, cx, m, n); };
         // the plain call's last refusal comes first
         CHECK(refused(plain(nullptr, nullptr, (1u << 20) + 1u), "ctx") && refused(var(nullptr, nullptr, (1u << 20) + 1u), "ctx"));
         CHECK(refused(plain(ctx, nullptr, (1u << 20) + 1u), "2^20") && refused(var(ctx, nullptr, (1u << 20) + 1u), "2^20"));
@@ -169,13 +174,13 @@ int main() {
                     std::vector<pt_object_motion> table = {{{0.0f, 0.0f, 0.0f}, 1.0f}, {{0.02f, -0.01f, 0.03f}, pass ? 0.0f : 0.98f}};
                     const pt::ReprojectMotion m = {table.data(), (uint32_t)table.size()};
                     const pt_reproject_var_params p = {4, 64.0f, 0.05f, 0.5f, 2u, 2u, 0};
-                    pt::ReprojectVarFrame v, vp;
-                    int how = -1;
-                    CHECK(pt::host::check_reproject_var_moved(&fr, w, h, &p, &cam, fr.color.data(), fr.depth.data(), fr.id.data(),
-                                                              with_normals ? fr.normal.data() : nullptr, hc, fr.hcolor.data(),
-                                                              fr.hlen.data(), fr.hmom.data(), fr.hdepth.data(), fr.hid.data(),
-                                                              with_normals ? fr.hnormal.data() : nullptr, fr.out.data(), fr.len.data(),
-                                                              fr.mom.data(), fr.err.data(), table.data(), m.n, v, &how) == PT_OK);
+                    pt::ReprojectCall call;
+                    pt::ReprojectArgs a = frames_args(fr, w, h, &cam, hc, true, with_normals);
+                    a.var_params = &p, a.motion = table.data(), a.n_motion = m.n;
+                    CHECK(pt::host::check_reproject(a, call) == PT_OK);
+                    pt::ReprojectVarFrame &v = call.v;
+                    pt::ReprojectVarFrame vp;
+                    const int how = call.how;
                     CHECK(how == pt::host::kMotionTable);
                     v.s_plane = fr.splane.data();
                     vp = v;

@@ -46,14 +46,19 @@ int main() {
         int32_t ibuf[4];
         const float *F = buf;
         const int32_t *I = ibuf;
-        pt::ReprojectVarFrame v;
+        pt::ReprojectCall call;
+        pt::ReprojectVarFrame &v = call.v;
         const void *ctx = buf;  // never dereferenced
         // col: the frame's own planes; hc / hl / hm: history colour (with depth and id) / length / moments; out: colour and
         // length; om / er: moments and error
         auto check = [&](const pt_reproject_var_params *p, uint32_t w, uint32_t h, const pt_camera *c, const float *col, const float *hc,
                          const float *hl, const float *hm, const pt_camera *hcam, float *out, float *om, float *er, const void *cx) {
-            return pt::host::check_reproject_var(cx, w, h, p, c, col, col ? F : nullptr, col ? I : nullptr, nullptr, hcam, hc, hl, hm,
-                                                 hc, hc ? I : nullptr, nullptr, out, out, om, er, v);
+            pt::ReprojectArgs a{};
+            a.ctx = cx, a.var = true, a.width = w, a.height = h, a.var_params = p, a.cam = c, a.hist_cam = hcam;
+            a.color = col, a.depth = col ? F : nullptr, a.object_id = col ? I : nullptr;
+            a.hist_color = hc, a.hist_len = hl, a.hist_moments = hm, a.hist_depth = hc, a.hist_object_id = hc ? I : nullptr;
+            a.out_color = out, a.out_len = out, a.out_moments = om, a.error = er;
+            return pt::host::check_reproject(a, call);
         };
         const pt_reproject_var_params bad_mh = {0, -1.0f, NAN, 2.0f, 0, 4, 1}, bad_dt = {0, 1.0f, INFINITY, 2.0f, 0, 4, 1},
                                       bad_nm = {0, 1.0f, 1.0f, NAN, 0, 4, 1}, bad_nm2 = {0, 1.0f, 1.0f, -1.5f, 0, 4, 1},
@@ -103,12 +108,11 @@ int main() {
                 for (int with_normals = 0; with_normals < 2; ++with_normals) {
                     Frames fr = make_frames(n, w * 131u + h, true);
                     const pt_reproject_var_params p = {4, 64.0f, 0.05f, 0.5f, with_normals ? 4u : 1u, radius, 0};
-                    pt::ReprojectVarFrame v;
-                    CHECK(pt::host::check_reproject_var(&fr, w, h, &p, &cam, fr.color.data(), fr.depth.data(), fr.id.data(),
-                                                        with_normals ? fr.normal.data() : nullptr, hc, fr.hcolor.data(), fr.hlen.data(),
-                                                        fr.hmom.data(), fr.hdepth.data(), fr.hid.data(),
-                                                        with_normals ? fr.hnormal.data() : nullptr, fr.out.data(), fr.len.data(),
-                                                        fr.mom.data(), fr.err.data(), v) == PT_OK);
+                    pt::ReprojectCall call;
+                    pt::ReprojectArgs a = frames_args(fr, w, h, &cam, hc, true, with_normals);
+                    a.var_params = &p;
+                    CHECK(pt::host::check_reproject(a, call) == PT_OK);
+                    pt::ReprojectVarFrame &v = call.v;
                     v.s_plane = fr.splane.data();
                     shorts += run(v);
                     for (uint32_t i = 0; i < n; ++i) {
@@ -134,10 +138,13 @@ int main() {
         }
         // the first frame, in place: every pixel short, the colour unchanged, the moments (s, s*s)
         Frames fr = make_frames(n, 7u, true);
-        pt::ReprojectVarFrame v;
-        CHECK(pt::host::check_reproject_var(&fr, w, h, nullptr, &cam, fr.color.data(), fr.depth.data(), fr.id.data(), nullptr, nullptr,
-                                            nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, fr.color.data(), fr.len.data(),
-                                            fr.mom.data(), fr.err.data(), v) == PT_OK);
+        pt::ReprojectCall call;
+        pt::ReprojectArgs a{};
+        a.ctx = &fr, a.var = true, a.width = w, a.height = h, a.cam = &cam, a.color = fr.color.data(), a.depth = fr.depth.data();
+        a.object_id = fr.id.data(), a.out_color = fr.color.data(), a.out_len = fr.len.data(), a.out_moments = fr.mom.data();
+        a.error = fr.err.data();
+        CHECK(pt::host::check_reproject(a, call) == PT_OK);
+        pt::ReprojectVarFrame &v = call.v;
         v.s_plane = fr.splane.data();
         const std::vector<float> before = fr.color;
         CHECK(run(v) == n);

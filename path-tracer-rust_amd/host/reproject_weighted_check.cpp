@@ -39,15 +39,20 @@ int main() {
         const float *F = buf;
         const int32_t *Ii = ibuf;
         const void *ctx = buf;  // never dereferenced
-        pt::ReprojectVarFrame v;
-        pt::ReprojectWeights wts;
-        int how = -1;
+        pt::ReprojectCall rc;
+        pt::ReprojectVarFrame &v = rc.v;
+        pt::ReprojectWeights &wts = rc.wts;
+        int &how = rc.how;
         const pt_object_motion bad[2] = {I, {{0.0f, INFINITY, 0.0f}, -2.0f}}, fine[2] = {I, {{0.5f, 0.0f, 0.0f}, 1.0f}};
         pt_reproject_var_params p = {};
         auto call = [&](const void *cx, uint32_t w, const pt_reproject_var_params *pp, const uint32_t *spp, float *err,
                         const pt_object_motion *m, uint32_t n) {
-            return pt::host::check_reproject_var_weighted(cx, w, 2, pp, &cam, F, F, Ii, nullptr, spp, &near_cam, F, F, F, F, Ii, nullptr, buf,
-                                                          buf, buf, err, m, n, v, &how, wts);
+            pt::ReprojectArgs a{};
+            a.ctx = cx, a.var = true, a.width = w, a.height = 2, a.var_params = pp, a.cam = &cam, a.hist_cam = &near_cam;
+            a.color = F, a.depth = F, a.object_id = Ii, a.spp = spp;
+            a.hist_color = F, a.hist_len = F, a.hist_moments = F, a.hist_depth = F, a.hist_object_id = Ii;
+            a.out_color = buf, a.out_len = buf, a.out_moments = buf, a.error = err, a.motion = m, a.n_motion = n;
+            return pt::host::check_reproject(a, rc);
         };
         for (const uint32_t *spp : {(const uint32_t *)nullptr, (const uint32_t *)ubuf}) {
             p = {};
@@ -92,17 +97,16 @@ int main() {
                 std::vector<pt_object_motion> table = {I, {{0.02f, -0.01f, 0.03f}, 0.98f}};
                 const pt::ReprojectMotion m = {table.data(), (uint32_t)table.size()};
                 const pt_reproject_var_params p = {4, 64.0f, 0.05f, 0.5f, 2u, 2u, 0};
-                const float *normal = form & 1 ? fr.normal.data() : nullptr, *hnormal = form & 1 ? fr.hnormal.data() : nullptr;
                 std::vector<uint32_t> plane(n);
                 uint32_t seed = n + (uint32_t)form;
-                pt::ReprojectVarFrame v, vu;
-                pt::ReprojectWeights wts;
-                int how = -1;
-                CHECK(pt::host::check_reproject_var_weighted(&fr, w, h, &p, &cam, fr.color.data(), fr.depth.data(), fr.id.data(), normal,
-                                                             plane.data(), hc, fr.hcolor.data(), fr.hlen.data(), fr.hmom.data(),
-                                                             fr.hdepth.data(), fr.hid.data(), hnormal, fr.out.data(), fr.len.data(),
-                                                             fr.mom.data(), fr.err.data(), form & 2 ? table.data() : nullptr,
-                                                             form & 2 ? m.n : 0u, v, &how, wts) == PT_OK);
+                pt::ReprojectCall call;
+                pt::ReprojectArgs a = frames_args(fr, w, h, &cam, hc, true, form & 1);
+                a.var_params = &p, a.spp = plane.data(), a.motion = form & 2 ? table.data() : nullptr, a.n_motion = form & 2 ? m.n : 0u;
+                CHECK(pt::host::check_reproject(a, call) == PT_OK);
+                pt::ReprojectVarFrame &v = call.v;
+                pt::ReprojectVarFrame vu;
+                const pt::ReprojectWeights &wts = call.wts;
+                const int how = call.how;
                 CHECK(how == (form & 2 ? pt::host::kMotionTable : pt::host::kMotionPlain) && wts.spp == plane.data());
                 v.s_plane = fr.splane.data();
                 vu = v;

@@ -8,6 +8,7 @@ on every side; 37x19, 703 pixels - not a multiple of the sixteen a lane of k_spp
 tests/test_gpu_reproject_moved.py's: history lengths laid out by kernel B's tiles (all long, all short, mixed), object ids 0..5
 against a table of four records."""
 import ctypes as C
+import importlib
 
 import numpy as np
 import pytest
@@ -128,6 +129,64 @@ def test_a_null_plane_is_the_moved_call(dev, size):
                              vbase.want(w, h, cam, cur, hist_cam, hist), "the moved call is its restatement")
     dev.put(cur, hist)
     vbase.same_bytes(dev.call(w, h, CUR, spp=None), dev.call(w, h, CUR, weighted=False), "first frame")
+
+
+# ------------------------------------------------------------------------------------------------- the Python methods
+def test_the_python_methods_are_the_direct_calls(dev):
+    """The package's five Context.reproject* methods against the ctypes calls of these files, every output byte for byte: a 7x5
+    frame with normals, a history seen from another camera, a table of two records of which one moves, and a plane that holds
+    0, 2 and 8."""
+    pkg = importlib.import_module("path-tracer-rust_amd")
+    w, h = 7, 5
+    n = w * h
+    cur, hist = mbase.synthetic(w, h)
+    cam, hist_cam = CAMERAS["translated"]
+    motion = (MOTION[1], MOTION[0])  # object 0 translated, object 1 where it was
+    plane = np.array([0, 2, 8], dtype=U32)[np.arange(n) % 3]
+    P = {k: v.value for k, v in dev.p.items()}
+    frame = (w, h, cam, P["color"], P["depth"], P["oid"])
+    kw = dict(PARAMS, normal=P["normal"], history=dict(cam=hist_cam, color=P["hcolor"], len=P["hlen"], moments=P["hmom"],
+                                                       depth=P["hdepth"], object_id=P["hoid"], normal=P["hnormal"]))
+    plain_kw = {k: v for k, v in kw.items() if k not in ("min_frames", "radius")}
+
+    def var_form(method, *more, **extra):
+        dev.put(cur, hist)
+        dev._guards(n, False)
+        method(*frame, P["out"], P["len"], P["mom"], P["err"], *more, **extra, **kw)
+        return dev._collect(n, False)
+
+    def plain_form(method, *more):
+        dev.put(cur, hist)
+        dev.fill_guarded("out", n * 3, GUARD, -3.0)
+        dev.fill_guarded("len", n, GUARD, -3.0)
+        method(*frame, P["out"], P["len"], *more, **plain_kw)
+        return dev.read_guarded("out", n * 3, GUARD, -3.0, "the colour output").reshape(n, 3), dev.read_guarded("len", n, GUARD, -3.0, "len")
+
+    ctx = pkg.Context()
+    try:
+        dev.upload("spp", plane)
+        got = var_form(ctx.reproject_var_weighted, spp=P["spp"], motion=motion)
+        dev.put(cur, hist)
+        exp = dev.call(w, h, cam, hist_cam, spp=plane, motion=motion)
+        vbase.same_bytes(got, exp, "reproject_var_weighted")
+        assert ((plane == 0) & (exp[1] > 0)).any() and (exp[1] > plane).any()  # history kept as it is, and history blended
+        got = var_form(ctx.reproject_var_moved, motion)
+        dev.put(cur, hist)
+        moved = dev.call(w, h, cam, hist_cam, motion=motion, weighted=False)
+        vbase.same_bytes(got, moved, "reproject_var_moved")
+        got = var_form(ctx.reproject_var)
+        dev.put(cur, hist)
+        still = dev.reproject_var(w, h, cam, hist_cam)
+        vbase.same_bytes(got, still, "reproject_var")
+        assert moved[0].tobytes() != still[0].tobytes()  # the one record that moves was read
+        got = plain_form(ctx.reproject_moved, motion)
+        dev.put(cur, hist)
+        mbase.same2(got, mbase.Dev.reproject_moved(dev, w, h, cam, hist_cam, motion), "reproject_moved")
+        got = plain_form(ctx.reproject)
+        dev.put(cur, hist)
+        mbase.same2(got, dev.reproject(w, h, cam, hist_cam), "reproject")
+    finally:
+        ctx.close()
 
 
 # ------------------------------------------------------------------------------------------------------ a mixed plane
