@@ -275,7 +275,9 @@ uint32_t pt_config_pixels(const pt_config *cfg);
 /* Render the band [idx_begin, idx_end) (or this rank's chunks of it) into DEVICE memory: d_out_rgb holds
  * pt_config_pixels(cfg)*3 floats, pixel k of the call at element k*3+c, linear, clamped to [0,1] — for an
  * un-chunked band the memory image of the reference's Vec<Vec3> slice (mod.rs:1013-1014, 852-856).
- * `hip_stream` is a hipStream_t (NULL = the context's own stream).  Blocking.
+ * `hip_stream` is a hipStream_t (NULL = the context's own stream).  Blocking.  Everything the call reads from or writes to the
+ * caller's memory is ordered on that stream, after whatever is pending on it when the call is made, and has completed when the
+ * call returns; the same holds for every entry point that takes a `hip_stream`, under every flag and backend.
  * Cancel (both backends): *cancel is read between passes (wavefront) / rounds (megakernel), which the library sizes by MEASURED
  * time when rays_per_pass is 0 - a tiny timed first pass of a scene, then as many samples as fit 100-120 ms, the rate kept with
  * the context - so a cancel comes back within about a tenth of a second whatever a ray of the scene costs (the reference polls

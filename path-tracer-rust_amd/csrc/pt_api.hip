@@ -1990,7 +1990,7 @@ int pt_ctx_set_profiling(pt_ctx *c, int enabled) {
 }
 
 // n concurrent wavefront pipelines over the pixels of one call (PT_FLAG_PIPELINES)
-static int render_pipelined(pt_ctx *c, const pt_config *cfg, uint32_t n, uint32_t ib, uint32_t ie, float *d_out,
+static int render_pipelined(pt_ctx *c, const pt_config *cfg, uint32_t n, uint32_t ib, uint32_t ie, float *d_out, hipStream_t st,
                             const volatile uint8_t *cancel, pt_progress_fn cb, void *user, pt_stats *stats) {
     // the caller's partition of [ib, ie): chunks first, first+step, ... of C pixels (whole band: rows of the image)
     const uint32_t C = cfg->chunk_step > 1u ? cfg->chunk_pixels : cfg->width;
@@ -2049,11 +2049,12 @@ static int render_pipelined(pt_ctx *c, const pt_config *cfg, uint32_t n, uint32_
             return rcs[j];
         }
         if (rcs[j] == PT_CANCELLED) worst = PT_CANCELLED;
-        // pipeline j's k-th chunk is the call's (k*n + j)-th chunk
-        launch_scatter_chunks(c->stream, c->pipe_out[j].p, d_out, own[j], C, n, j);
+        // pipeline j's k-th chunk is the call's (k*n + j)-th chunk; the pipelines wrote library memory and have finished, the
+        // caller's buffer is only written here, on the call's stream
+        launch_scatter_chunks(st, c->pipe_out[j].p, d_out, own[j], C, n, j);
     }
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipStreamSynchronize(st));
     if (stats) add_stats_concurrent(stats, sts);
     if (worst == PT_CANCELLED) set_error("cancelled");
     return worst;
@@ -2070,7 +2071,8 @@ int pt_ctx_render(pt_ctx *c, const pt_config *cfg, void *d_out_rgb, void *hip_st
         if (n_pipes > 8u) return refuse("at most 8 concurrent pipelines");
         if (stats) memset(stats, 0, sizeof *stats);
         const double t0p = now_ms();
-        rc = render_pipelined(c, cfg, n_pipes, ib, ie, (float *)d_out_rgb, cancel, cb, user, stats);
+        rc = render_pipelined(c, cfg, n_pipes, ib, ie, (float *)d_out_rgb, hip_stream ? (hipStream_t)hip_stream : c->stream, cancel, cb,
+                              user, stats);
         if (cb && rc == PT_OK) cb(user, 1.0f);  // every pipeline has finished and the chunks are in place
         if (stats) stats->ms_total = now_ms() - t0p;
         return rc;

@@ -4,6 +4,7 @@ Importing this module loads no library and touches no device: GPU test modules a
 import contextlib
 import ctypes as C
 import os
+import threading
 
 import numpy as np
 import pytest
@@ -26,7 +27,10 @@ def hip_runtime():
         hip = C.CDLL(own[0])
         hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
         hip.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+        hip.hipMemsetAsync.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]
         hip.hipStreamCreate.argtypes = [C.POINTER(C.c_void_p)]
+        hip.hipStreamCreateWithFlags.argtypes = [C.POINTER(C.c_void_p), C.c_uint]
+        hip.hipLaunchHostFunc.argtypes = [C.c_void_p, HOST_FN, C.c_void_p]
         hip.hipStreamDestroy.argtypes = [C.c_void_p]
         hip.hipStreamSynchronize.argtypes = [C.c_void_p]
         _hip = hip
@@ -34,14 +38,66 @@ def hip_runtime():
 
 
 @contextlib.contextmanager
-def stream():
-    """a HIP stream, destroyed on exit"""
+def stream(nonblocking=False):
+    """a HIP stream, destroyed on exit.  The default is what hipStreamCreate gives, a blocking stream: it synchronises implicitly
+    with the null stream.  nonblocking=True is hipStreamNonBlocking, what torch or a GUI hands over (and what the library's own
+    context stream is): nothing orders it against the null stream's copies."""
     hip, st = hip_runtime(), C.c_void_p()
-    assert hip.hipStreamCreate(C.byref(st)) == 0
+    if nonblocking:
+        assert hip.hipStreamCreateWithFlags(C.byref(st), 1) == 0  # hipStreamNonBlocking
+    else:
+        assert hip.hipStreamCreate(C.byref(st)) == 0
     try:
         yield st
     finally:
         assert hip.hipStreamDestroy(st) == 0
+
+
+HOST_FN = C.CFUNCTYPE(None, C.c_void_p)  # hipHostFn_t
+
+
+class Gate:
+    """Holds a stream at a known point: a host function (hipLaunchHostFunc) that waits until the gate is opened.  Whatever is
+    enqueued on the stream behind it runs only after open() - or after `timeout` seconds, which is why a gate can delay a stream
+    but never hang it: a gate that ran into its timeout says so (timed_out) and check() fails the test with that.  The callback
+    makes no HIP call.  The Gate object, and with it the callback, has to stay referenced until the stream has been synchronised."""
+
+    def __init__(self, st, timeout=2.0):
+        self.timeout = timeout
+        self._open, self._done = threading.Event(), threading.Event()
+        self.released = self.timed_out = False
+        self._timer = None
+        self._fn = HOST_FN(self._wait)
+        rc = hip_runtime().hipLaunchHostFunc(st, self._fn, None)
+        assert rc == 0, "hipLaunchHostFunc: %d" % rc
+
+    def _wait(self, _user):
+        self.released = self._open.wait(self.timeout)
+        self.timed_out = not self.released
+        self._done.set()
+
+    @property
+    def finished(self):
+        """the host function has returned: the stream has moved on"""
+        return self._done.is_set()
+
+    def open(self):
+        self._open.set()
+
+    def open_after(self, seconds):
+        self._timer = threading.Timer(seconds, self._open.set)
+        self._timer.daemon = True
+        self._timer.start()
+
+    def check(self, what=""):
+        assert self.finished, "%s: the gate still holds its stream" % what
+        assert not self.timed_out, "%s: the gate was never opened and ran into its %.1f s timeout" % (what, self.timeout)
+
+    def close(self):
+        """open it, whatever happened, and stop the timer: for a finally"""
+        if self._timer is not None:
+            self._timer.cancel()
+        self._open.set()
 
 
 def new_ctx(L, env=None):
@@ -111,14 +167,14 @@ class Device:
         """an (npix, 3) float frame"""
         return self.download(ptr, npix * 3).reshape(npix, 3)
 
-    def stream(self):
-        return stream()
+    def stream(self, nonblocking=False):
+        return stream(nonblocking)
 
-    def render(self, cfg, ptr, accumulate=False, cancel=None, cb=None, want=0):
-        """pt_ctx_render (or pt_ctx_accumulate) into ptr: ((npix, 3) image, stats)"""
+    def render(self, cfg, ptr, accumulate=False, cancel=None, cb=None, want=0, stream=None):
+        """pt_ctx_render (or pt_ctx_accumulate) into ptr, on `stream` (None: the context's own): ((npix, 3) image, stats)"""
         st = PtStats()
         call = self.L.pt_ctx_accumulate if accumulate else self.L.pt_ctx_render
-        rc = call(self.ctx, C.byref(cfg), self._at(ptr), None, C.cast(cancel, C.c_void_p) if cancel else None,
+        rc = call(self.ctx, C.byref(cfg), self._at(ptr), stream, C.cast(cancel, C.c_void_p) if cancel else None,
                   C.cast(cb, C.c_void_p) if cb else None, None, C.byref(st))
         assert rc == want, (rc, self.L.pt_last_error())
         return self.pixels(ptr, self.L.pt_config_pixels(C.byref(cfg))), st
