@@ -87,6 +87,31 @@ pub struct PtDenoiseVarParams {
     pub flags: u32,
 }
 
+// pt_ctx_overlay's parameters (the editing cues drawn on a frame before pt_ctx_present); all zero = nothing drawn.
+// pt_overlay_defaults writes the defaults out, with the grid sized for a camera.
+pub const PT_OVERLAY_SKY: u32 = 1;
+pub const PT_OVERLAY_GRID: u32 = 2;
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct PtOverlayParams {
+    pub flags: u32,
+    pub n_selected: u32,
+    pub selected: [i32; 16],
+    pub radius: u32,
+    pub outline_color: [f32; 3],
+    pub outline_alpha: f32,
+    pub fill_color: [f32; 3],
+    pub fill_alpha: f32,
+    pub sky_top: [f32; 3],
+    pub sky_bottom: [f32; 3],
+    pub grid_color: [f32; 3],
+    pub grid_alpha: f32,
+    pub grid_y: f32,
+    pub grid_spacing: f32,
+    pub grid_half_width: f32,
+    pub grid_extent: f32,
+}
+
 // pt_ctx_present's parameters; all zero = the frame's own size, exposure 1, RGBA8, display order
 #[repr(C)]
 #[derive(Clone, Copy, Default, Debug)]
@@ -741,6 +766,37 @@ extern "C" {
     pub fn pt_last_error() -> *const c_char;
     pub fn pt_device_count() -> i32;
     pub fn pt_image_hash(rgb: *const f32, n_floats: usize) -> u64;
+}
+
+// include/ptrace_overlay.h: pt_ctx_overlay has a header of its own, and so a block of its own here
+extern "C" {
+    // what the viewport tab (src/views/viewport_tab.rs) draws around the picture - backdrop, ground grid, the selected object's
+    // outline - on the device frame, between the denoiser and pt_ctx_present; the context's own stream, no stream argument
+    pub fn pt_overlay_defaults(cam: *const PtCamera, out: *mut PtOverlayParams) -> i32;
+    pub fn pt_ctx_overlay(
+        ctx: *mut PtCtx,
+        width: u32,
+        height: u32,
+        params: *const PtOverlayParams,
+        cam: *const PtCamera,
+        d_rgb: *const f32,
+        d_object_id: *const i32,
+        d_depth: *const f32,
+        d_out: *mut f32,
+    ) -> i32;
+    pub fn pt_overlay_pixel_host(
+        cam: *const PtCamera,
+        width: u32,
+        height: u32,
+        params: *const PtOverlayParams,
+        idx: u32,
+        object_id: i32,
+        depth: f32,
+        selected: i32,
+        outlined: i32,
+        rgb_in: *const f32,
+        rgb_out: *mut f32,
+    ) -> i32;
 }
 
 fn v3(v: Vec3) -> [f32; 3] {

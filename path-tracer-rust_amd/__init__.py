@@ -17,6 +17,7 @@ from .abi import (PT_AOV_MAX_CHAIN, PT_AOV_THROUGH_DELTA, PT_CANCELLED, PT_DENOI
                   pt_denoise_var_params, pt_noise_stats, pt_noise_target, pt_object, pt_object_motion, pt_present_params,
                   pt_reproject_params, pt_reproject_var_params, pt_scatter_item, pt_scatter_out, pt_scatter_surface,
                   pt_select_params, pt_stats, pt_triangle, pt_upsample_params)
+from .overlay_abi import PT_OVERLAY_GRID, PT_OVERLAY_SKY, pt_overlay_params  # noqa: F401  (include/ptrace_overlay.h)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PT_LIB") or os.path.join(_HERE, "libptrace_hip.so")  # PT_LIB: A/B builds when tuning
@@ -227,6 +228,16 @@ class Context:
                               PT_PRESENT_FRAMEBUFFER_ORDER if framebuffer_order else 0)
         ptr = lambda q: C.c_void_p(q) if q else None  # noqa: E731
         _check(lib().pt_ctx_present(self._h, width, height, C.byref(p), ptr(rgb), ptr(out), C.c_void_p(stream or 0)))
+
+    def overlay(self, width, height, rgb, out, params=None, cam=None, object_id=None, depth=None):
+        """The editing cues on a whole width x height float frame in device memory (pt_ctx_overlay): the sky where object_id < 0,
+        the ground grid where depth does not hide it, and the tint and outline of the objects listed in `params`
+        (a pt_overlay_params; overlay_defaults(cam) gives one to fill in; None = copy).  Device pointers: `rgb` and `out`
+        pixels * 3 float32 (out may be rgb), `object_id` pixels int32, `depth` pixels float32 - the planes of render_aov.  Runs on
+        the context's own stream: there is no stream argument."""
+        ptr = lambda q: C.c_void_p(q) if q else None  # noqa: E731
+        _check(lib().pt_ctx_overlay(self._h, width, height, C.byref(params) if params is not None else None,
+                                    C.byref(cam) if cam is not None else None, ptr(rgb), ptr(object_id), ptr(depth), ptr(out)))
 
     def _reproject(self, entry, params, width, height, cam, frame, history, outs, motion=None, stream=None):
         """The one call of the five reproject methods.  `params`: the entry point's struct, filled - pt_reproject_var_params
@@ -512,6 +523,13 @@ def write_ppm8(path, array):
     if a.ndim != 3 or a.shape[2] != 3:
         raise ValueError("write_ppm8 wants a (height, width, 3) array, not shape %r" % (a.shape,))
     _check(lib().pt_write_ppm8(os.fsencode(path), a.ctypes.data_as(C.POINTER(C.c_uint8)), a.shape[1], a.shape[0]))
+
+
+def overlay_defaults(cam=None):
+    """pt_ctx_overlay's defaults written out (pt_overlay_defaults): with a pt_camera the grid is sized for its distance."""
+    p = pt_overlay_params()
+    _check(lib().pt_overlay_defaults(C.byref(cam) if cam is not None else None, C.byref(p)))
+    return p
 
 
 def present_thresholds():

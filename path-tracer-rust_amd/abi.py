@@ -298,13 +298,15 @@ def declare(cdll, partial=False):
     """Give every function of SIGNATURES its restype and argtypes on a loaded library and return the library.
     A symbol the library lacks raises, naming all that are missing; partial=True skips them (a library built from an
     older header)."""
+    from . import overlay_abi  # include/ptrace_overlay.h: a header of its own has a table of its own (imported here: it imports this module)
+
     missing = []
-    for table in (SIGNATURES, DEBUG_SIGNATURES):
+    for table in (SIGNATURES, overlay_abi.SIGNATURES, DEBUG_SIGNATURES):
         for name, (restype, argtypes) in table.items():
             try:
                 fn = getattr(cdll, name)
             except AttributeError:
-                if table is SIGNATURES:
+                if table is not DEBUG_SIGNATURES:
                     missing.append(name)
                 continue
             fn.restype, fn.argtypes = restype, argtypes

@@ -19,6 +19,7 @@
 #include "pt_kernels.h"
 #include "pt_masked.h"
 #include "pt_noise.h"
+#include "pt_overlay.h"
 #include "pt_present.h"
 #include "pt_probe.h"
 #include "pt_refit.h"
@@ -2823,6 +2824,18 @@ int pt_ctx_present(pt_ctx *c, uint32_t width, uint32_t height, const pt_present_
             f.mid = c->pr_mid.p;
         }
         launch_present(st, f);
+        return PT_OK;
+    });
+}
+
+// (no stream parameter: the context's own stream)
+int pt_ctx_overlay(pt_ctx *c, uint32_t width, uint32_t height, const pt_overlay_params *params, const pt_camera *cam, const float *d_rgb,
+                   const int32_t *d_object_id, const float *d_depth, float *d_out) {
+    OverlayFrame f;
+    const int rc = host::check_overlay(c, width, height, params, cam, d_rgb, d_object_id, d_depth, d_out, f);
+    if (rc) return rc;
+    return run_image_pass(c, nullptr, [&](hipStream_t st) {
+        launch_overlay(st, f);
         return PT_OK;
     });
 }

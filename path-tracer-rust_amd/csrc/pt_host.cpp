@@ -5,6 +5,7 @@
 #include "pt_denoise.h"
 #include "pt_layout.h"
 #include "pt_masked.h"
+#include "pt_overlay.h"
 #include "pt_present.h"
 #include "pt_probe.h"
 #include "pt_refit.h"
@@ -1713,6 +1714,71 @@ int check_present(const void *ctx, uint32_t width, uint32_t height, const pt_pre
     f.bpp = P.format == PT_PRESENT_RGBA8 ? 4u : 3u;
     f.flip = !(P.flags & PT_PRESENT_FRAMEBUFFER_ORDER);
     f.exposure = P.exposure == 0.0f ? 1.0f : P.exposure;
+    return PT_OK;
+}
+
+// ---- pt_ctx_overlay (ptrace_overlay.h, pt_overlay.h)
+int check_overlay_params(const pt_overlay_params *params, pt_overlay_params &P) {
+    P = pt_overlay_params{};
+    if (params) P = *params;
+    if (P.flags & ~(PT_OVERLAY_SKY | PT_OVERLAY_GRID)) return refuse("pt_overlay_params.flags: unknown bits");
+    if (P.n_selected > PT_OVERLAY_MAX_SELECTED) return refuse("pt_overlay_params.n_selected exceeds 16");
+    for (uint32_t i = 0; i < P.n_selected; ++i)
+        if (P.selected[i] < 0) return refuse("pt_overlay_params.selected: an object index is negative");
+    if (P.radius > PT_OVERLAY_MAX_RADIUS) return refuse("pt_overlay_params.radius exceeds 8");
+    const float *colours[] = {P.outline_color, P.fill_color, P.sky_top, P.sky_bottom, P.grid_color};
+    for (const float *c : colours)
+        for (int a = 0; a < 3; ++a)
+            if (!std::isfinite(c[a])) return refuse("pt_overlay_params: a colour component is not finite");
+    for (float a : {P.outline_alpha, P.fill_alpha, P.grid_alpha})
+        if (!(a >= 0.0f && a <= 1.0f)) return refuse("pt_overlay_params: an alpha is not finite or outside [0, 1]");
+    if (P.flags & PT_OVERLAY_GRID) {
+        for (float v : {P.grid_spacing, P.grid_half_width, P.grid_extent})
+            if (!(v > 0.0f && v < __builtin_inff())) return refuse("pt_overlay_params: the grid's spacing, half width and extent must be finite and positive");
+        if (!std::isfinite(P.grid_y)) return refuse("pt_overlay_params.grid_y is not finite");
+    }
+    if (!P.radius) P.radius = kOverlayRadius;
+    if (P.outline_alpha == 0.0f) P.outline_alpha = 1.0f;
+    if (P.grid_alpha == 0.0f) P.grid_alpha = 1.0f;
+    return PT_OK;
+}
+
+int overlay_view(const pt_camera &cam, OverlayFrame &f) {
+    float lens[3], su[3], sv[3];
+    camera_basis(cam, lens, su, sv);
+    if (!std::isfinite(lens[0]) || !std::isfinite(lens[1]) || !std::isfinite(lens[2])) return refuse("cam: the lens centre is not finite");
+    f.C = ld(cam.position);
+    f.L = ld(lens);
+    f.su = ld(su);
+    f.sv = ld(sv);
+    return PT_OK;
+}
+
+int check_overlay(const void *ctx, uint32_t width, uint32_t height, const pt_overlay_params *params, const pt_camera *cam,
+                  const float *d_rgb, const int32_t *d_object_id, const float *d_depth, float *d_out, OverlayFrame &f) {
+    f = OverlayFrame{};
+    const int rc = check_overlay_params(params, f.p);
+    if (rc) return rc;
+    if (!width || !height) return refuse("width and height must be positive");
+    if ((uint64_t)width * height > (1ull << 28)) return refuse("width*height exceeds 2^28");
+    if (!d_rgb) return refuse("d_rgb is NULL");
+    if (!d_out) return refuse("d_out is NULL");
+    if (!d_object_id && (f.p.n_selected || (f.p.flags & PT_OVERLAY_SKY)))
+        return refuse("d_object_id is NULL with a selection or PT_OVERLAY_SKY");
+    if (!d_depth && (f.p.flags & PT_OVERLAY_GRID)) return refuse("d_depth is NULL with PT_OVERLAY_GRID");
+    if (f.p.flags) {
+        if (!cam) return refuse("cam is NULL with PT_OVERLAY_SKY or PT_OVERLAY_GRID");
+        const int rv = overlay_view(*cam, f);
+        if (rv) return rv;
+    }
+    if (!ctx) return refuse("ctx is NULL");
+    f.width = width;
+    f.height = height;
+    f.rgb = d_rgb;
+    f.out = d_out;
+    // the planes the call does not need are not handed to the kernel: without ids it stages nothing
+    f.object_id = f.p.n_selected || (f.p.flags & PT_OVERLAY_SKY) ? d_object_id : nullptr;
+    f.depth = (f.p.flags & PT_OVERLAY_GRID) ? d_depth : nullptr;
     return PT_OK;
 }
 

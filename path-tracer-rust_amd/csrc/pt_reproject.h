@@ -102,6 +102,18 @@ struct ReprojectWeights {
     float min_frames;     // (float)min_frames: a pixel with count c > 0 is long from min_frames * (float)c samples on
 };
 
+// Step 3's first lines, stated once: the unit direction of the ray through the centre of the pixel in column x and camera row y
+// (y = H-1-r), made as render_pixel makes it - sx, sy, S, g = L - S, d = g * (1 / sqrt(dot(g, g))).  C, L, su, sv: the camera's
+// position and its pt_camera_basis.  pt_ctx_overlay's step 1 (pt_overlay.h) is this function too.
+PT_HD vec3 reproject_ray(vec3 C, vec3 L, vec3 su, vec3 sv, uint32_t W, uint32_t H, uint32_t x, uint32_t y) {
+    const float fw = (float)W, fh = (float)H;
+    const float sx = ((float)x + 0.5f) / fw - 0.5f;
+    const float sy = ((float)y + 0.5f) / fh - 0.5f;
+    const vec3 S = (C + su * sx) + sv * sy;
+    const vec3 g = L - S;
+    return g * (1.0f / __builtin_sqrtf(dot(g, g)));
+}
+
 // step 3 up to the reject test: where the point pixel idx sees at `depth` lies in the history frame.  false: no position.
 // MOVED (pt_ctx_reproject_moved): the point goes through the object's record first - Pm[a] = P[a]*scale + offset[a], two
 // operations per component - unless the record is IDENTITY, which leaves P's bits alone.
@@ -109,12 +121,8 @@ template <bool MOVED = false>
 PT_HD bool reproject_project(const ReprojectView &V, uint32_t W, uint32_t H, uint32_t idx, float depth, ReprojectPos &o,
                              const pt_object_motion *rec = nullptr) {
     const uint32_t x = idx % W, r = idx / W, y = H - 1u - r;
+    vec3 P = V.L + reproject_ray(V.C, V.L, V.su, V.sv, W, H, x, y) * depth;
     const float fw = (float)W, fh = (float)H;
-    const float sx = ((float)x + 0.5f) / fw - 0.5f;
-    const float sy = ((float)y + 0.5f) / fh - 0.5f;
-    const vec3 S = (V.C + V.su * sx) + V.sv * sy;
-    const vec3 g = V.L - S;
-    vec3 P = V.L + (g * (1.0f / __builtin_sqrtf(dot(g, g)))) * depth;
     if constexpr (MOVED) {
         const vec3 Pm = mk(P.x * rec->scale + rec->offset[0], P.y * rec->scale + rec->offset[1], P.z * rec->scale + rec->offset[2]);
         if (!reproject_rec_identity(*rec)) P = Pm;

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/ptrace.h"
+#include "../../include/ptrace_overlay.h"
 
 // --aov-chain [K]: the guides every pass of this program reads come from pt_ctx_render_aov_ex with PT_AOV_THROUGH_DELTA
 static bool g_aov_chain = false;
@@ -30,6 +31,26 @@ static int render_guides(pt_ctx *ctx, const pt_config *cfg, float *d_albedo, flo
     return pt_ctx_render_aov_ex(ctx, cfg, &g_aov, d_albedo, d_normal, d_depth, d_id, d_chain, nullptr);
 }
 
+// --select / --outline-radius / --sky / --grid: the editing cues drawn on the frame a --preview shows (pt_ctx_overlay)
+struct OverlayOpts {
+    bool on = false;
+    uint32_t flags = 0, radius = 0;  // radius 0: the library's default
+    std::vector<int32_t> selected;
+};
+static OverlayOpts g_overlay;
+
+// pt_overlay_defaults for the frame's camera with what the command line names on top, applied in place
+static int draw_overlay(pt_ctx *ctx, uint32_t w, uint32_t h, const pt_camera *cam, float *d_rgb, const int32_t *d_id, const float *d_depth) {
+    pt_overlay_params op;
+    int rc = pt_overlay_defaults(cam, &op);
+    if (rc) return rc;
+    op.flags = g_overlay.flags;
+    op.n_selected = (uint32_t)g_overlay.selected.size();
+    for (size_t i = 0; i < g_overlay.selected.size(); ++i) op.selected[i] = g_overlay.selected[i];
+    if (g_overlay.radius) op.radius = g_overlay.radius;
+    return pt_ctx_overlay(ctx, w, h, &op, cam, d_rgb, d_id, d_depth, d_rgb);
+}
+
 static void usage() {
     fprintf(stderr,
             "usage: ptrace <samplesPerPixel> <y-resolution> <scene id|index> [--width W] [--backend wavefront|megakernel]\n"
@@ -38,6 +59,7 @@ static void usage() {
             "              [--denoise [N]] [--noise-target X [--noise-map FILE.pfm]]\n"
             "              [--adaptive X [--tile N] [--spp-map FILE.pfm] [--error-map FILE.pfm] [--adaptive-checkpoint FILE]]\n"
             "              [--denoise-var [N]] [--preview FILE.ppm [--preview-size WxH] [--exposure E]]\n"
+            "              [--select I[,J...]] [--outline-radius R] [--sky] [--grid]\n"
             "              [--trace-scale K [--retrace]]\n"
             "              [--orbit N [--orbit-step DEG] [--move I:DX,DY,DZ [--move-history [F]]] [--boost K]]\n"
             "  --checkpoint FILE: continue from the samples FILE holds (if it exists), render up to <samplesPerPixel> in all and\n"
@@ -72,6 +94,11 @@ static void usage() {
             "           pixels on the GPU (pt_ctx_present, RGB8) and write them as a binary PPM; --preview-size WxH fits the frame to\n"
             "           that size by area averaging (default: the frame's own), --exposure E scales it first (default 1); one GPU\n"
             "           only\n"
+            "  --select I[,J...], --outline-radius R, --sky, --grid: with --preview (the single frame or every frame of --orbit): draw\n"
+            "           the editing cues on the frame before it is presented (pt_ctx_overlay, after the denoisers): an outline of R\n"
+            "           frame pixels (1..8, default 2) around the objects listed (at most 16 indices), a sky gradient where the first\n"
+            "           hit missed, the ground grid in y = 0 where no object hides it - pt_overlay_defaults for the frame's camera\n"
+            "           otherwise; the single frame takes a 1-sample pt_ctx_render_aov for the object ids and depths\n"
             "  --trace-scale K: K = 2..8: trace the paths at ceil(W/K) x ceil(H/K), the first-hit guides at both sizes, and fill the\n"
             "           frame in through the guides with albedo and normals (pt_ctx_upsample, default parameters); the image written\n"
             "           is the full-size frame; combines with --denoise and --preview; one GPU only; not with --checkpoint,\n"
@@ -82,7 +109,7 @@ static void usage() {
             "  --orbit N: with --preview FILE.ppm: N frames of a viewport whose camera turns about the vertical axis through the\n"
             "           origin, frame k by k * DEG degrees (--orbit-step DEG, default 2) from the scene's own camera: per frame\n"
             "           pt_ctx_set_camera, pt_ctx_render at <samplesPerPixel>, the first-hit guides, pt_ctx_reproject_var against\n"
-            "           frame k-1, pt_ctx_denoise_var (sigma_var 2) and pt_ctx_present; the frames go to FILE-000.ppm, FILE-001.ppm,\n"
+            "           frame k-1, pt_ctx_denoise_var (sigma_var 2), pt_ctx_overlay if asked for, and pt_ctx_present; the frames go to FILE-000.ppm, FILE-001.ppm,\n"
             "           ..., one line per frame to stderr (the camera update's milliseconds, whether it rebuilt the scene, the\n"
             "           frame's total); one GPU only; not with --trace-scale, --adaptive, --noise-target, --checkpoint, --denoise or\n"
             "           --denoise-var\n"
@@ -440,7 +467,7 @@ static int write_denoised(const pt_config *frame, uint32_t spp, const DeviceFram
 
 // --preview: the device frame as 8-bit display pixels (pt_ctx_present, RGB8) at ow x oh (0, 0: the frame's size), and the P6 file
 static int write_preview(const pt_config *frame, const DeviceFrame &df, const std::string &path, uint32_t ow, uint32_t oh,
-                         float exposure) {
+                         float exposure, const pt_camera *cam) {
     pt_present_params pp;
     memset(&pp, 0, sizeof pp);
     pp.out_width = ow;
@@ -449,8 +476,20 @@ static int write_preview(const pt_config *frame, const DeviceFrame &df, const st
     pp.format = PT_PRESENT_RGB8;
     if (!ow) ow = frame->width, oh = frame->height;
     std::vector<uint8_t> px((size_t)ow * oh * 3);
-    void *d_px = nullptr;
+    void *d_px = nullptr, *d_guides = nullptr;
     int rc = pt_device_malloc(df.dev, px.size(), &d_px);
+    if (!rc && g_overlay.on) {
+        // nothing has produced ids and depths for this frame: one sample of first-hit guides, then the cues in place
+        const size_t npix = (size_t)frame->width * frame->height;
+        pt_config one = *frame;
+        one.spp = 1;
+        rc = pt_device_malloc(df.dev, npix * 8, &d_guides);
+        float *d_depth = (float *)d_guides;
+        int32_t *d_id = (int32_t *)(d_depth + npix);
+        if (!rc) rc = pt_ctx_render_aov(df.ctx, &one, nullptr, nullptr, d_depth, d_id, nullptr);
+        if (!rc) rc = draw_overlay(df.ctx, frame->width, frame->height, cam, (float *)df.d_out, d_id, d_depth);
+    }
+    if (d_guides) pt_device_free(df.dev, d_guides);
     if (!rc) rc = pt_ctx_present(df.ctx, frame->width, frame->height, &pp, (const float *)df.d_out, (uint8_t *)d_px, nullptr);
     if (!rc) rc = pt_device_download(df.dev, px.data(), d_px, px.size());
     if (d_px) pt_device_free(df.dev, d_px);
@@ -667,6 +706,7 @@ static int render_orbit(const pt_config *cfg, pt_scene *sc, uint32_t frames, dou
         memset(&dp, 0, sizeof dp);
         dp.sigma_var = 2.0f;
         if (!rc) rc = pt_ctx_denoise_var(ctx, w, h, &dp, cur->color, d_error, d_albedo, cur->normal, cur->depth, d_shown, nullptr);
+        if (!rc && g_overlay.on) rc = draw_overlay(ctx, w, h, &cam, d_shown, cur->id, cur->depth);
         if (!rc) rc = pt_ctx_present(ctx, w, h, &pp, d_shown, (uint8_t *)d_px, nullptr);
         if (!rc) rc = pt_device_download(dev, px.data(), d_px, px.size());
         const clk::time_point t2 = clk::now();
@@ -752,6 +792,44 @@ int main(int argc, char **argv) {
                 fprintf(stderr, "--preview-size needs WxH, both positive\n");
                 return 1;
             }
+        }
+        else if (a == "--select") {
+            const char *v = next();
+            g_overlay.selected.clear();
+            for (const char *q = v; *q;) {
+                char *e = nullptr;
+                const long id = strtol(q, &e, 10);
+                if (e == q || id < 0 || id > INT32_MAX || (*e && *e != ',') || (*e == ',' && !e[1]) || g_overlay.selected.size() == PT_OVERLAY_MAX_SELECTED) {
+                    g_overlay.selected.clear();
+                    break;
+                }
+                g_overlay.selected.push_back((int32_t)id);
+                q = *e ? e + 1 : e;
+            }
+            if (g_overlay.selected.empty()) {
+                fprintf(stderr, "--select needs I[,J...]: 1 to 16 object indices, none negative\n");
+                return 1;
+            }
+            g_overlay.on = true;
+        }
+        else if (a == "--outline-radius") {
+            char *e = nullptr;
+            const char *v = next();
+            const unsigned long r = strtoul(v, &e, 10);
+            if (e == v || *e || r < 1 || r > PT_OVERLAY_MAX_RADIUS) {
+                fprintf(stderr, "--outline-radius needs R = 1..8 frame pixels\n");
+                return 1;
+            }
+            g_overlay.radius = (uint32_t)r;
+            g_overlay.on = true;
+        }
+        else if (a == "--sky") {
+            g_overlay.flags |= PT_OVERLAY_SKY;
+            g_overlay.on = true;
+        }
+        else if (a == "--grid") {
+            g_overlay.flags |= PT_OVERLAY_GRID;
+            g_overlay.on = true;
         }
         else if (a == "--exposure") {
             char *e = nullptr;
@@ -992,6 +1070,10 @@ int main(int argc, char **argv) {
         fprintf(stderr, "--preview-size and --exposure go with --preview FILE.ppm\n");
         return 1;
     }
+    if (preview.empty() && g_overlay.on) {
+        fprintf(stderr, "--select, --outline-radius, --sky and --grid go with --preview FILE.ppm\n");
+        return 1;
+    }
     if (denoise_var_spp && denoise_spp) {
         fprintf(stderr, "--denoise-var cannot be combined with --denoise\n");
         return 1;
@@ -1126,7 +1208,7 @@ int main(int argc, char **argv) {
         release();
         return 3;
     }
-    if (!preview.empty() && write_preview(&cfg, df, preview, preview_w, preview_h, exposure)) {
+    if (!preview.empty() && write_preview(&cfg, df, preview, preview_w, preview_h, exposure, pt_scene_camera(sc))) {
         release();
         return 3;
     }

@@ -22,6 +22,7 @@
 
 #include "../../include/ptrace.h"
 #include "../csrc/pt_host.h"
+#include "../csrc/pt_overlay.h"
 #include "../csrc/pt_present.h"
 #include "../csrc/pt_reproject.h"
 #include "../csrc/pt_upsample.h"
@@ -1226,6 +1227,68 @@ int pt_present_quantize_host(const float *in, size_t n, float exposure, uint8_t 
     const float e = exposure == 0.0f ? 1.0f : exposure;
     const uint32_t *T = pt::present_table();
     for (size_t i = 0; i < n; ++i) out[i] = (uint8_t)pt::present_byte(T, pt::present_bits(pt::present_clamp(in[i], e)));
+    return PT_OK;
+}
+
+// every default of pt_ctx_overlay written out; with a camera the grid is sized as the editing viewport sizes its own, in binary64,
+// each value rounded to binary32 once
+int pt_overlay_defaults(const pt_camera *cam, pt_overlay_params *out) {
+    if (!out) {
+        pt::set_error("out is NULL");
+        return PT_ERR_INVALID;
+    }
+    double zoom = 1.0;  // a camera 5 units from the origin
+    if (cam) {
+        const double x = cam->position[0], y = cam->position[1], z = cam->position[2];
+        zoom = sqrt(x * x + y * y + z * z) / 5.0;
+        if (!std::isfinite(zoom)) {
+            pt::set_error("cam: the position is not finite");
+            return PT_ERR_INVALID;
+        }
+    }
+    pt_overlay_params p;
+    memset(&p, 0, sizeof p);
+    p.radius = pt::kOverlayRadius;
+    p.outline_color[1] = 1.0f;
+    p.outline_alpha = 1.0f;
+    for (int c = 0; c < 3; ++c) p.fill_color[c] = 1.0f, p.sky_bottom[c] = 0.75f, p.grid_color[c] = 0.5f;
+    p.sky_top[0] = 0.25f, p.sky_top[1] = 0.5f, p.sky_top[2] = 0.75f;
+    p.grid_alpha = 0.5f;
+    const double spacing = pow(10.0, floor(log10(zoom * 1.2 + 1.0)));
+    p.grid_y = 0.0f;
+    p.grid_spacing = (float)spacing;
+    p.grid_half_width = (float)(0.01 * zoom);
+    p.grid_extent = (float)(5.0 * spacing);
+    *out = p;
+    return PT_OK;
+}
+
+int pt_overlay_pixel_host(const pt_camera *cam, uint32_t width, uint32_t height, const pt_overlay_params *params, uint32_t idx,
+                          int32_t object_id, float depth, int selected, int outlined, const float rgb_in[3], float rgb_out[3]) {
+    pt::OverlayFrame f = {};
+    const int rc = pt::host::check_overlay_params(params, f.p);
+    if (rc) return rc;
+    if (width == 0 || height == 0 || (uint64_t)width * height > (1ull << 28) || idx >= (uint64_t)width * height) {
+        pt::set_error("an empty frame, one above 2^28 pixels, or idx outside it");
+        return PT_ERR_INVALID;
+    }
+    if (!rgb_in || !rgb_out) {
+        pt::set_error("NULL argument");
+        return PT_ERR_INVALID;
+    }
+    if (f.p.flags) {
+        if (!cam) {
+            pt::set_error("cam is NULL with PT_OVERLAY_SKY or PT_OVERLAY_GRID");
+            return PT_ERR_INVALID;
+        }
+        const int rv = pt::host::overlay_view(*cam, f);
+        if (rv) return rv;
+    }
+    f.width = width;
+    f.height = height;
+    float v[3] = {rgb_in[0], rgb_in[1], rgb_in[2]};
+    pt::overlay_pixel(f, idx, object_id, depth, selected != 0, outlined != 0, v);
+    memcpy(rgb_out, v, sizeof v);
     return PT_OK;
 }
 
