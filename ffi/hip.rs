@@ -112,6 +112,33 @@ pub struct PtOverlayParams {
     pub grid_extent: f32,
 }
 
+// pt_ctx_solid's parameters (a lit solid view from the first-hit guides); every field is taken as it stands - there is no
+// "0 = default": pt_solid_defaults writes the defaults out, and a NULL pointer stands for them.
+pub const PT_SOLID_HEADLIGHT: u32 = 1;
+pub const PT_SOLID_REFLECT_SKY: u32 = 2;
+pub const PT_SOLID_MAX_SHININESS_LOG2: u32 = 10;
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct PtSolidParams {
+    pub flags: u32,
+    pub light: [f32; 3],
+    pub ambient: f32,
+    pub diffuse: f32,
+    pub specular: f32,
+    pub shininess_log2: u32,
+    pub background: [f32; 3],
+    pub sky_top: [f32; 3],
+    pub sky_bottom: [f32; 3],
+}
+
+// one record of pt_ctx_solid's looks table, a host array indexed by object id (pt_solid_look_of fills one from a PtObject)
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct PtSolidLook {
+    pub emission: [f32; 3],
+    pub reflect_type: u32,
+}
+
 // pt_ctx_present's parameters; all zero = the frame's own size, exposure 1, RGBA8, display order
 #[repr(C)]
 #[derive(Clone, Copy, Default, Debug)]
@@ -795,6 +822,42 @@ extern "C" {
         selected: i32,
         outlined: i32,
         rgb_in: *const f32,
+        rgb_out: *mut f32,
+    ) -> i32;
+}
+
+// include/ptrace_solid.h: pt_ctx_solid has a header of its own too, and so a block of its own here
+extern "C" {
+    // what the viewport tab (src/views/viewport_tab.rs) shows while the scene is edited - the objects lit and solid - from one
+    // sample of pt_ctx_render_aov's planes; `looks` is a host array; hip_stream as for pt_ctx_render
+    pub fn pt_solid_defaults(out: *mut PtSolidParams) -> i32;
+    pub fn pt_solid_look_of(obj: *const PtObject, out: *mut PtSolidLook) -> i32;
+    pub fn pt_ctx_solid(
+        ctx: *mut PtCtx,
+        width: u32,
+        height: u32,
+        params: *const PtSolidParams,
+        cam: *const PtCamera,
+        d_albedo: *const f32,
+        d_normal: *const f32,
+        d_depth: *const f32,
+        d_object_id: *const i32,
+        looks: *const PtSolidLook,
+        n_looks: u32,
+        d_out: *mut f32,
+        hip_stream: *mut c_void,
+    ) -> i32;
+    pub fn pt_solid_pixel_host(
+        cam: *const PtCamera,
+        width: u32,
+        height: u32,
+        params: *const PtSolidParams,
+        idx: u32,
+        object_id: i32,
+        depth: f32,
+        albedo: *const f32,
+        normal: *const f32,
+        look: *const PtSolidLook,
         rgb_out: *mut f32,
     ) -> i32;
 }

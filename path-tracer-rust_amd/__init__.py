@@ -18,6 +18,8 @@ from .abi import (PT_AOV_MAX_CHAIN, PT_AOV_THROUGH_DELTA, PT_CANCELLED, PT_DENOI
                   pt_reproject_params, pt_reproject_var_params, pt_scatter_item, pt_scatter_out, pt_scatter_surface,
                   pt_select_params, pt_stats, pt_triangle, pt_upsample_params)
 from .overlay_abi import PT_OVERLAY_GRID, PT_OVERLAY_SKY, pt_overlay_params  # noqa: F401  (include/ptrace_overlay.h)
+from .solid_abi import (PT_SOLID_HEADLIGHT, PT_SOLID_MAX_SHININESS_LOG2, PT_SOLID_REFLECT_SKY, pt_solid_look,  # noqa: F401
+                        pt_solid_params)  # (include/ptrace_solid.h)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PT_LIB") or os.path.join(_HERE, "libptrace_hip.so")  # PT_LIB: A/B builds when tuning
@@ -238,6 +240,17 @@ class Context:
         ptr = lambda q: C.c_void_p(q) if q else None  # noqa: E731
         _check(lib().pt_ctx_overlay(self._h, width, height, C.byref(params) if params is not None else None,
                                     C.byref(cam) if cam is not None else None, ptr(rgb), ptr(object_id), ptr(depth), ptr(out)))
+
+    def solid(self, width, height, normal, depth, object_id, out, cam, albedo=None, params=None, looks=None, stream=None):
+        """A lit solid view of a whole width x height frame from the first-hit guides in device memory (pt_ctx_solid): ambient,
+        diffuse and one highlight, times the albedo, plus the objects' emission.  Device pointers, the planes of render_aov:
+        `normal`, `albedo` (None: a clay view) and `out` pixels * 3 float32 (out may be albedo or normal), `depth` pixels
+        float32, `object_id` pixels int32.  `cam`: as for set_camera().  `params`: a pt_solid_params (solid_defaults() gives one; None = the defaults);
+        `looks`: a ctypes array of pt_solid_look indexed by object id (solid_looks(objects)), host memory, or None."""
+        ptr = lambda q: C.c_void_p(q) if q else None  # noqa: E731
+        _check(lib().pt_ctx_solid(self._h, width, height, C.byref(params) if params is not None else None, _camera(cam), ptr(albedo),
+                                  ptr(normal), ptr(depth), ptr(object_id), looks, len(looks) if looks is not None else 0, ptr(out),
+                                  C.c_void_p(stream or 0)))
 
     def _reproject(self, entry, params, width, height, cam, frame, history, outs, motion=None, stream=None):
         """The one call of the five reproject methods.  `params`: the entry point's struct, filled - pt_reproject_var_params
@@ -530,6 +543,21 @@ def overlay_defaults(cam=None):
     p = pt_overlay_params()
     _check(lib().pt_overlay_defaults(C.byref(cam) if cam is not None else None, C.byref(p)))
     return p
+
+
+def solid_defaults():
+    """pt_ctx_solid's defaults written out (pt_solid_defaults): a headlight, ambient 0.1, diffuse 1, specular 0.5 at exponent 32."""
+    p = pt_solid_params()
+    _check(lib().pt_solid_defaults(C.byref(p)))
+    return p
+
+
+def solid_looks(objects):
+    """pt_ctx_solid's looks table for a sequence (or ctypes array) of pt_object, one pt_solid_look each (pt_solid_look_of)."""
+    arr = (pt_solid_look * len(objects))()
+    for i, o in enumerate(objects):
+        _check(lib().pt_solid_look_of(C.byref(o), C.byref(arr[i])))
+    return arr
 
 
 def present_thresholds():

@@ -24,6 +24,7 @@
 #include "pt_probe.h"
 #include "pt_refit.h"
 #include "pt_reproject.h"
+#include "pt_solid.h"
 #include "pt_upsample.h"
 #include "pt_tile.h"
 
@@ -393,6 +394,8 @@ struct pt_ctx {
     DevBuf<float> rv_s;
     // pt_ctx_reproject*_moved's scratch, its own too: the call's motion table, 16 B per record, grown on demand
     DevBuf<pt_object_motion> rm_table;
+    // pt_ctx_solid's scratch, its own too: the call's looks table, 16 B per record, grown on demand
+    DevBuf<pt_solid_look> solid_looks;
     // The adaptive calls: the frame kept between calls (pt_ctx_set_scene drops it), and their scratch, kept too and grown on
     // demand: the compact accumulator of a step's tiles, the step's open-tile list, the counters (u64 [0]: the sum of E at the
     // end; u32 [2], [3]: the tiles a step left open / closed; u32 [4]: the list's length; u32 [5..7]: k_tile_select's counts),
@@ -2836,6 +2839,30 @@ int pt_ctx_overlay(pt_ctx *c, uint32_t width, uint32_t height, const pt_overlay_
     if (rc) return rc;
     return run_image_pass(c, nullptr, [&](hipStream_t st) {
         launch_overlay(st, f);
+        return PT_OK;
+    });
+}
+
+// The looks table goes the way upload_motion's table goes: copied into the context's scratch on the call's stream, which the call
+// waits for before it returns, so the caller's array outlives the copy.
+int pt_ctx_solid(pt_ctx *c, uint32_t width, uint32_t height, const pt_solid_params *params, const pt_camera *cam, const float *d_albedo,
+                 const float *d_normal, const float *d_depth, const int32_t *d_object_id, const pt_solid_look *looks, uint32_t n_looks,
+                 float *d_out, void *hip_stream) {
+    SolidFrame f;
+    const int rc = host::check_solid(c, width, height, params, cam, d_albedo, d_normal, d_depth, d_object_id, looks, n_looks, d_out, f);
+    if (rc) return rc;
+    return run_image_pass(c, hip_stream, [&](hipStream_t st) {
+        if (f.n_looks) {
+            const int rt = c->solid_looks.ensure(f.n_looks);
+            if (rt) return rt;
+            const hipError_t e = hipMemcpyAsync(c->solid_looks.p, f.looks, (size_t)f.n_looks * sizeof(pt_solid_look), hipMemcpyHostToDevice, st);
+            if (e != hipSuccess) {
+                set_error(std::string("uploading the looks table: ") + hipGetErrorString(e));
+                return PT_ERR_HIP;
+            }
+            f.looks = c->solid_looks.p;
+        }
+        launch_solid(st, f);
         return PT_OK;
     });
 }

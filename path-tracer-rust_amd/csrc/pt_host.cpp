@@ -10,6 +10,7 @@
 #include "pt_probe.h"
 #include "pt_refit.h"
 #include "pt_reproject.h"
+#include "pt_solid.h"
 #include "pt_upsample.h"
 
 #include <algorithm>
@@ -1780,6 +1781,79 @@ int check_overlay(const void *ctx, uint32_t width, uint32_t height, const pt_ove
     f.object_id = f.p.n_selected || (f.p.flags & PT_OVERLAY_SKY) ? d_object_id : nullptr;
     f.depth = (f.p.flags & PT_OVERLAY_GRID) ? d_depth : nullptr;
     return PT_OK;
+}
+
+// ---- pt_ctx_solid (ptrace_solid.h, pt_solid.h)
+int check_solid_params(const pt_solid_params *params, pt_solid_params &P) {
+    P = params ? *params : kSolidDefaults;
+    if (P.flags & ~(PT_SOLID_HEADLIGHT | PT_SOLID_REFLECT_SKY)) return refuse("pt_solid_params.flags: unknown bits");
+    if (P.shininess_log2 > PT_SOLID_MAX_SHININESS_LOG2) return refuse("pt_solid_params.shininess_log2 exceeds 10");
+    for (float v : {P.ambient, P.diffuse, P.specular})
+        if (!finite_nonneg(v)) return refuse("pt_solid_params: ambient, diffuse or specular is negative or not finite");
+    if (!(P.flags & PT_SOLID_HEADLIGHT))
+        for (float v : P.light)
+            if (!std::isfinite(v)) return refuse("pt_solid_params.light: a component is not finite");
+    const float *colours[] = {P.background, P.sky_top, P.sky_bottom};
+    for (const float *c : colours)
+        for (int a = 0; a < 3; ++a)
+            if (!finite_nonneg(c[a])) return refuse("pt_solid_params: a colour component of background, sky_top or sky_bottom is negative or not finite");
+    return PT_OK;
+}
+
+int check_solid_look(const pt_solid_look &look) {
+    if (look.reflect_type > PT_REFRACT) return refuse("looks: a reflect_type is above PT_REFRACT");
+    for (float v : look.emission)
+        if (!finite_nonneg(v)) return refuse("looks: an emission component is negative or not finite");
+    return PT_OK;
+}
+
+int check_solid_view(uint32_t width, uint32_t height, const pt_camera *cam, SolidFrame &f) {
+    if (!width || !height) return refuse("width and height must be positive");
+    if ((uint64_t)width * height > (1ull << 28)) return refuse("width*height exceeds 2^28");
+    if (!cam) return refuse("cam is NULL");
+    float lens[3], su[3], sv[3];
+    camera_basis(*cam, lens, su, sv);
+    if (!std::isfinite(lens[0]) || !std::isfinite(lens[1]) || !std::isfinite(lens[2])) return refuse("cam: the lens centre is not finite");
+    f.width = width;
+    f.height = height;
+    f.C = ld(cam->position);
+    f.L = ld(lens);
+    f.su = ld(su);
+    f.sv = ld(sv);
+    return PT_OK;
+}
+
+int check_solid(const void *ctx, uint32_t width, uint32_t height, const pt_solid_params *params, const pt_camera *cam, const float *d_albedo,
+                const float *d_normal, const float *d_depth, const int32_t *d_object_id, const pt_solid_look *looks, uint32_t n_looks,
+                float *d_out, SolidFrame &f) {
+    f = SolidFrame{};
+    int rc = check_solid_params(params, f.p);
+    if (!rc) rc = check_solid_view(width, height, cam, f);
+    if (rc) return rc;
+    if (!d_normal) return refuse("d_normal is NULL");
+    if (!d_depth) return refuse("d_depth is NULL");
+    if (!d_object_id) return refuse("d_object_id is NULL");
+    if (!d_out) return refuse("d_out is NULL");
+    if (n_looks > kSolidMaxLooks) return refuse("n_looks exceeds 2^20");
+    if (!looks && n_looks) return refuse("looks is NULL with n_looks != 0");
+    for (uint32_t i = 0; i < n_looks; ++i) {
+        rc = check_solid_look(looks[i]);
+        if (rc) return rc;
+    }
+    if (!ctx) return refuse("ctx is NULL");
+    f.albedo = d_albedo;
+    f.normal = d_normal;
+    f.depth = d_depth;
+    f.object_id = d_object_id;
+    f.out = d_out;
+    f.looks = n_looks ? looks : nullptr;
+    f.n_looks = n_looks;
+    return PT_OK;
+}
+
+bool solid_wide(const SolidFrame &f) {
+    const uintptr_t all = (uintptr_t)f.albedo | (uintptr_t)f.normal | (uintptr_t)f.depth | (uintptr_t)f.object_id | (uintptr_t)f.out;
+    return (all & 15u) == 0u && (uint64_t)f.width * f.height >= kSolidLanePixels;
 }
 
 // ---- pt_ctx_reproject (ptrace.h, pt_reproject.h)

@@ -19,6 +19,7 @@
 
 #include "../../include/ptrace.h"
 #include "../../include/ptrace_overlay.h"
+#include "../../include/ptrace_solid.h"
 
 // --aov-chain [K]: the guides every pass of this program reads come from pt_ctx_render_aov_ex with PT_AOV_THROUGH_DELTA
 static bool g_aov_chain = false;
@@ -51,6 +52,32 @@ static int draw_overlay(pt_ctx *ctx, uint32_t w, uint32_t h, const pt_camera *ca
     return pt_ctx_overlay(ctx, w, h, &op, cam, d_rgb, d_id, d_depth, d_rgb);
 }
 
+// --solid [N]: the frame a --preview shows is not the traced one but pt_ctx_solid of an N-sample pt_ctx_render_aov (0: off)
+static uint32_t g_solid = 0;
+
+// The guides at g_solid samples into the four planes given, then the lit solid view of them into d_out: the looks from the scene's
+// objects, a headlight, mirrors showing the sky - in --sky's two colours (pt_overlay_defaults') when --sky is given
+static int draw_solid(pt_ctx *ctx, const pt_config *frame, const pt_camera *cam, const pt_object *objs, uint32_t n_objs, float *d_albedo,
+                      float *d_normal, float *d_depth, int32_t *d_id, float *d_out) {
+    pt_config guides = *frame;
+    guides.spp = g_solid;
+    int rc = pt_ctx_render_aov(ctx, &guides, d_albedo, d_normal, d_depth, d_id, nullptr);
+    std::vector<pt_solid_look> looks(n_objs);
+    for (uint32_t i = 0; i < n_objs && !rc; ++i) rc = pt_solid_look_of(&objs[i], &looks[i]);
+    pt_solid_params sp;
+    if (!rc) rc = pt_solid_defaults(&sp);
+    if (rc) return rc;
+    sp.flags = PT_SOLID_HEADLIGHT | PT_SOLID_REFLECT_SKY;
+    if (g_overlay.flags & PT_OVERLAY_SKY) {
+        pt_overlay_params op;
+        rc = pt_overlay_defaults(cam, &op);
+        if (rc) return rc;
+        memcpy(sp.sky_top, op.sky_top, sizeof sp.sky_top);
+        memcpy(sp.sky_bottom, op.sky_bottom, sizeof sp.sky_bottom);
+    }
+    return pt_ctx_solid(ctx, frame->width, frame->height, &sp, cam, d_albedo, d_normal, d_depth, d_id, looks.data(), n_objs, d_out, nullptr);
+}
+
 static void usage() {
     fprintf(stderr,
             "usage: ptrace <samplesPerPixel> <y-resolution> <scene id|index> [--width W] [--backend wavefront|megakernel]\n"
@@ -59,7 +86,7 @@ static void usage() {
             "              [--denoise [N]] [--noise-target X [--noise-map FILE.pfm]]\n"
             "              [--adaptive X [--tile N] [--spp-map FILE.pfm] [--error-map FILE.pfm] [--adaptive-checkpoint FILE]]\n"
             "              [--denoise-var [N]] [--preview FILE.ppm [--preview-size WxH] [--exposure E]]\n"
-            "              [--select I[,J...]] [--outline-radius R] [--sky] [--grid]\n"
+            "              [--select I[,J...]] [--outline-radius R] [--sky] [--grid] [--solid [N]]\n"
             "              [--trace-scale K [--retrace]]\n"
             "              [--orbit N [--orbit-step DEG] [--move I:DX,DY,DZ [--move-history [F]]] [--boost K]]\n"
             "  --checkpoint FILE: continue from the samples FILE holds (if it exists), render up to <samplesPerPixel> in all and\n"
@@ -99,6 +126,13 @@ static void usage() {
             "           frame pixels (1..8, default 2) around the objects listed (at most 16 indices), a sky gradient where the first\n"
             "           hit missed, the ground grid in y = 0 where no object hides it - pt_overlay_defaults for the frame's camera\n"
             "           otherwise; the single frame takes a 1-sample pt_ctx_render_aov for the object ids and depths\n"
+            "  --solid [N]: with --preview (the single frame or every frame of --orbit): the frame shown is not the traced one but the\n"
+            "           objects lit and solid (pt_ctx_solid: ambient, diffuse and a highlight from a light at the lens, times the\n"
+            "           albedo, plus the objects' emission; mirrors show the sky) from an N-sample pt_ctx_render_aov (default 1), the\n"
+            "           cues of --select, --sky and --grid drawn on it; under --orbit a frame is pt_ctx_set_camera / pt_ctx_set_object,\n"
+            "           pt_ctx_render_aov, pt_ctx_solid, pt_ctx_overlay, pt_ctx_present - no path is traced, nothing reprojected or\n"
+            "           denoised; not with --aov-chain (its ids and depths are the reflected object's), --trace-scale, --retrace,\n"
+            "           --boost or --move-history (nothing for them to act on)\n"
             "  --trace-scale K: K = 2..8: trace the paths at ceil(W/K) x ceil(H/K), the first-hit guides at both sizes, and fill the\n"
             "           frame in through the guides with albedo and normals (pt_ctx_upsample, default parameters); the image written\n"
             "           is the full-size frame; combines with --denoise and --preview; one GPU only; not with --checkpoint,\n"
@@ -467,7 +501,8 @@ static int write_denoised(const pt_config *frame, uint32_t spp, const DeviceFram
 
 // --preview: the device frame as 8-bit display pixels (pt_ctx_present, RGB8) at ow x oh (0, 0: the frame's size), and the P6 file
 static int write_preview(const pt_config *frame, const DeviceFrame &df, const std::string &path, uint32_t ow, uint32_t oh,
-                         float exposure, const pt_camera *cam) {
+                         float exposure, pt_scene *sc) {
+    const pt_camera *cam = pt_scene_camera(sc);
     pt_present_params pp;
     memset(&pp, 0, sizeof pp);
     pp.out_width = ow;
@@ -478,7 +513,17 @@ static int write_preview(const pt_config *frame, const DeviceFrame &df, const st
     std::vector<uint8_t> px((size_t)ow * oh * 3);
     void *d_px = nullptr, *d_guides = nullptr;
     int rc = pt_device_malloc(df.dev, px.size(), &d_px);
-    if (!rc && g_overlay.on) {
+    if (!rc && g_solid) {
+        // the lit solid view of the frame's first-hit guides takes the traced frame's place, then the cues in place
+        const size_t npix = (size_t)frame->width * frame->height;
+        uint32_t n_objs = 0;
+        const pt_object *objs = pt_scene_objects(sc, &n_objs);
+        rc = pt_device_malloc(df.dev, npix * 8 * sizeof(float), &d_guides);
+        float *d_albedo = (float *)d_guides, *d_normal = d_albedo + npix * 3, *d_depth = d_normal + npix * 3;
+        int32_t *d_id = (int32_t *)(d_depth + npix);
+        if (!rc) rc = draw_solid(df.ctx, frame, cam, objs, n_objs, d_albedo, d_normal, d_depth, d_id, (float *)df.d_out);
+        if (!rc && g_overlay.on) rc = draw_overlay(df.ctx, frame->width, frame->height, cam, (float *)df.d_out, d_id, d_depth);
+    } else if (!rc && g_overlay.on) {
         // nothing has produced ids and depths for this frame: one sample of first-hit guides, then the cues in place
         const size_t npix = (size_t)frame->width * frame->height;
         pt_config one = *frame;
@@ -655,6 +700,24 @@ static int render_orbit(const pt_config *cfg, pt_scene *sc, uint32_t frames, dou
             rc = pt_ctx_set_object(ctx, (uint32_t)mv.index, &o, &edit_rebuilt);
         }
         const clk::time_point t1b = clk::now();
+        if (g_solid) {
+            // --solid: the guides, the lit solid view of them, the cues, the display pixels - no path is traced
+            if (!rc) rc = draw_solid(ctx, cfg, &cam, objs, n_objs, d_albedo, cur->normal, cur->depth, cur->id, d_shown);
+            if (!rc && g_overlay.on) rc = draw_overlay(ctx, w, h, &cam, d_shown, cur->id, cur->depth);
+            if (!rc) rc = pt_ctx_present(ctx, w, h, &pp, d_shown, (uint8_t *)d_px, nullptr);
+            if (!rc) rc = pt_device_download(dev, px.data(), d_px, px.size());
+            const clk::time_point t2 = clk::now();
+            if (rc) break;
+            char name[32];
+            snprintf(name, sizeof name, "-%03u.ppm", k);
+            const std::string path = stem + name;
+            rc = pt_write_ppm8(path.c_str(), px.data(), ow, oh);
+            if (rc) break;
+            fprintf(stderr, "frame %u: pt_ctx_set_camera %.3f ms (%s), solid frame %.3f ms\n", k, ms(t0, t1), rebuilt ? "rebuilt" : "not rebuilt",
+                    ms(t0, t2));
+            printf("wrote %s\n", path.c_str());
+            continue;
+        }
         if (!rc) rc = pt_ctx_render(ctx, cfg, cur->color, nullptr, nullptr, nullptr, nullptr, &st);
         if (!rc) rc = render_guides(ctx, cfg, d_albedo, cur->normal, cur->depth, cur->id);
         pt_reproject_var_params rp;
@@ -830,6 +893,18 @@ int main(int argc, char **argv) {
         else if (a == "--grid") {
             g_overlay.flags |= PT_OVERLAY_GRID;
             g_overlay.on = true;
+        }
+        else if (a == "--solid") {
+            g_solid = 1;
+            // the count is optional: taken when the next argument is a number
+            if (i + 1 < argc && argv[i + 1][0] != '\0' && strspn(argv[i + 1], "0123456789") == strlen(argv[i + 1])) {
+                const char *v = argv[++i];
+                g_solid = strlen(v) < 6 ? (uint32_t)strtoul(v, nullptr, 10) : 0u;
+                if (!g_solid) {
+                    fprintf(stderr, "--solid takes N = 1..99999 samples of guides (or none: 1)\n");
+                    return 1;
+                }
+            }
         }
         else if (a == "--exposure") {
             char *e = nullptr;
@@ -1070,6 +1145,19 @@ int main(int argc, char **argv) {
         fprintf(stderr, "--preview-size and --exposure go with --preview FILE.ppm\n");
         return 1;
     }
+    if (g_solid && preview.empty()) {
+        fprintf(stderr, "--solid goes with --preview FILE.ppm\n");
+        return 1;
+    }
+    if (g_solid && g_aov_chain) {
+        fprintf(stderr, "--solid cannot be combined with --aov-chain: the chain's ids and depths are the reflected object's\n");
+        return 1;
+    }
+    if (g_solid && (trace_scale || retrace || boost || orbit_move.carry)) {
+        fprintf(stderr, "--solid cannot be combined with %s: no path is traced, so it has nothing to act on\n",
+                trace_scale ? "--trace-scale" : retrace ? "--retrace" : boost ? "--boost" : "--move-history");
+        return 1;
+    }
     if (preview.empty() && g_overlay.on) {
         fprintf(stderr, "--select, --outline-radius, --sky and --grid go with --preview FILE.ppm\n");
         return 1;
@@ -1208,7 +1296,7 @@ int main(int argc, char **argv) {
         release();
         return 3;
     }
-    if (!preview.empty() && write_preview(&cfg, df, preview, preview_w, preview_h, exposure, pt_scene_camera(sc))) {
+    if (!preview.empty() && write_preview(&cfg, df, preview, preview_w, preview_h, exposure, sc)) {
         release();
         return 3;
     }

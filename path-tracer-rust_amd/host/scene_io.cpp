@@ -25,6 +25,7 @@
 #include "../csrc/pt_overlay.h"
 #include "../csrc/pt_present.h"
 #include "../csrc/pt_reproject.h"
+#include "../csrc/pt_solid.h"
 #include "../csrc/pt_upsample.h"
 
 namespace {
@@ -1288,6 +1289,53 @@ int pt_overlay_pixel_host(const pt_camera *cam, uint32_t width, uint32_t height,
     f.height = height;
     float v[3] = {rgb_in[0], rgb_in[1], rgb_in[2]};
     pt::overlay_pixel(f, idx, object_id, depth, selected != 0, outlined != 0, v);
+    memcpy(rgb_out, v, sizeof v);
+    return PT_OK;
+}
+
+// ---- pt_ctx_solid's host side (include/ptrace_solid.h)
+int pt_solid_defaults(pt_solid_params *out) {
+    if (!out) {
+        pt::set_error("out is NULL");
+        return PT_ERR_INVALID;
+    }
+    *out = pt::kSolidDefaults;
+    return PT_OK;
+}
+
+int pt_solid_look_of(const pt_object *obj, pt_solid_look *out) {
+    if (!obj || !out) {
+        pt::set_error("NULL argument");
+        return PT_ERR_INVALID;
+    }
+    memcpy(out->emission, obj->emission, sizeof out->emission);
+    out->reflect_type = obj->reflect_type;
+    return PT_OK;
+}
+
+int pt_solid_pixel_host(const pt_camera *cam, uint32_t width, uint32_t height, const pt_solid_params *params, uint32_t idx,
+                        int32_t object_id, float depth, const float albedo[3], const float normal[3], const pt_solid_look *look,
+                        float rgb_out[3]) {
+    pt::SolidFrame f = {};
+    int rc = pt::host::check_solid_params(params, f.p);
+    if (!rc) rc = pt::host::check_solid_view(width, height, cam, f);
+    if (rc) return rc;
+    if (idx >= (uint64_t)width * height) {
+        pt::set_error("idx is outside the frame");
+        return PT_ERR_INVALID;
+    }
+    if (!normal || !rgb_out) {
+        pt::set_error("NULL argument");
+        return PT_ERR_INVALID;
+    }
+    const pt_solid_look none = {{0.0f, 0.0f, 0.0f}, PT_DIFFUSE};
+    if (look) {
+        rc = pt::host::check_solid_look(*look);
+        if (rc) return rc;
+    }
+    const float clay[3] = {1.0f, 1.0f, 1.0f};
+    float v[3];
+    pt::solid_pixel(f, idx, object_id, depth, albedo ? albedo : clay, normal, look ? *look : none, v);
     memcpy(rgb_out, v, sizeof v);
     return PT_OK;
 }
