@@ -33,6 +33,9 @@ def hip_runtime():
         hip.hipLaunchHostFunc.argtypes = [C.c_void_p, HOST_FN, C.c_void_p]
         hip.hipStreamDestroy.argtypes = [C.c_void_p]
         hip.hipStreamSynchronize.argtypes = [C.c_void_p]
+        hip.hipEventRecord.argtypes = [C.c_void_p, C.c_void_p]
+        hip.hipEventSynchronize.argtypes = [C.c_void_p]
+        hip.hipEventElapsedTime.argtypes = [C.POINTER(C.c_float), C.c_void_p, C.c_void_p]
         _hip = hip
     return _hip
 

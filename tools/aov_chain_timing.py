@@ -3,8 +3,8 @@
 one GPU, both calls in the same run, alternating.
 
 Per scene (cornell, mesh) and spp (8, 1) at 1024x768, with all four guide buffers (and the chain plane for the chain call):
-after a warm-up of both calls, ROUNDS rounds of [a window of N plain calls, a window of N chain calls], each window between two
-HIP events on a caller's stream, N chosen so that a window is at least WINDOW_MS.  Both calls block, so a window holds the
+after a warm-up of both calls, ROUNDS rounds of [a window of N plain calls, a window of N chain calls], each an event window of
+tools/timing.py on a caller's stream, N chosen so that a window is at least WINDOW_MS.  Both calls block, so a window holds the
 host's turn-around per call too - the same for both.  Reported per call: the median over the rounds, the extremes, and
 chain_over_plain = the median of the per-round ratios.
 
@@ -18,7 +18,6 @@ maximum (a wave loops until its longest chain ends; lanes are consecutive sample
     python tools/aov_chain_timing.py [out.json]
 """
 import ctypes as C
-import json
 import os
 import statistics
 import sys
@@ -29,6 +28,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import gpudev  # noqa: E402
 import ptlib  # noqa: E402
+import timing  # noqa: E402
 from ptlib import PtAovParams, PtConfig  # noqa: E402
 
 W, H = 1024, 768
@@ -36,106 +36,66 @@ SPPS = (8, 1)
 SCENES = ("mesh", "cornell")
 BUDGET = 1.10
 BUDGETED = ("mesh",)
-WINDOW_MS = 250.0
+WINDOW_MS = timing.WINDOW_MS
 ROUNDS = 5
 THROUGH_DELTA = ptlib.abi.PT_AOV_THROUGH_DELTA
 
 
-def main(stream):
+def spread(values):
+    return {"median": statistics.median(values), "min": min(values), "max": max(values)}
+
+
+def main():
     L = ptlib.product()
-    assert L.pt_device_count() >= 1, "aov_chain_timing needs a GPU: there is nothing to time without one"
-    hip = gpudev.hip_runtime()
-    hip.hipEventElapsedTime.argtypes = [C.POINTER(C.c_float), C.c_void_p, C.c_void_p]
-    hip.hipEventRecord.argtypes = [C.c_void_p, C.c_void_p]
-    hip.hipEventSynchronize.argtypes = [C.c_void_p]
-    ctx = C.c_void_p()
-    assert L.pt_ctx_create(0, C.byref(ctx)) == 0, L.pt_last_error()
-    e0, e1 = C.c_void_p(), C.c_void_p()
-    assert hip.hipEventCreate(C.byref(e0)) == 0 and hip.hipEventCreate(C.byref(e1)) == 0
+    timing.need_gpu(L, "aov_chain_timing")
     n = W * H
     sizes = (n * 12, n * 12, n * 4, n * 4, n * 4)
-    bufs = {}
-    for side in ("plain", "chain"):
-        bufs[side] = []
-        for nbytes in sizes:
-            p = C.c_void_p()
-            assert L.pt_device_malloc(0, nbytes, C.byref(p)) == 0, L.pt_last_error()
-            bufs[side].append(p)
-
-    def download(side):
-        out = []
-        for p, nbytes in zip(bufs[side], sizes):
-            host = np.zeros(nbytes // 4, dtype=np.uint32)
-            assert L.pt_device_download(0, host.ctypes.data_as(C.c_void_p), p, nbytes) == 0
-            out.append(host)
-        return out
-
-    def timed(fn, calls):
-        assert hip.hipEventRecord(e0, stream) == 0
-        for _ in range(calls):
-            fn()
-        assert hip.hipEventRecord(e1, stream) == 0
-        assert hip.hipEventSynchronize(e1) == 0
-        ms = C.c_float()
-        assert hip.hipEventElapsedTime(C.byref(ms), e0, e1) == 0
-        return ms.value / calls
-
     doc = {"command": "python tools/aov_chain_timing.py", "isa_hash": L.pt_kernel_isa_hash().decode(), "size": [W, H],
            "method": "%d rounds of [N plain calls, N chain calls], each window between two HIP events on one stream (window >= %.0f ms), "
                      "after a warm-up of both; ms per call; chain_over_plain = median of the per-round ratios" % (ROUNDS, WINDOW_MS),
            "budget_rule": "scenes without a delta surface (%s): chain <= %.2f x plain" % (", ".join(BUDGETED), BUDGET),
            "max_chain": 8, "cases": {}}
     on = PtAovParams(THROUGH_DELTA, 0)
-    for sid in SCENES:
-        sc = ptlib.load_scene_py(ptlib.scene_path(sid))
-        assert L.pt_ctx_set_scene(ctx, C.byref(sc.cam), sc.objs, sc.n_objs, sc.tris, sc.n_tris) == 0, L.pt_last_error()
-        for spp in SPPS:
-            cfg = PtConfig(W, H, spp, 0, 7, 0, 0, 0, 0)
+    with gpudev.stream() as stream, gpudev.Device(L) as d, timing.Events(stream) as ev:
+        bufs = {side: [d.alloc(nbytes) for nbytes in sizes] for side in ("plain", "chain")}
 
-            def plain():
-                assert L.pt_ctx_render_aov(ctx, C.byref(cfg), *bufs["plain"][:4], stream) == 0, L.pt_last_error()
+        def download(side):
+            return [d.download(p, nbytes // 4, np.uint32) for p, nbytes in zip(bufs[side], sizes)]
 
-            def chain():
-                assert L.pt_ctx_render_aov_ex(ctx, C.byref(cfg), C.byref(on), *bufs["chain"], stream) == 0, L.pt_last_error()
+        for sid in SCENES:
+            d.set_scene(ptlib.load_scene_py(ptlib.scene_path(sid)))
+            for spp in SPPS:
+                cfg = PtConfig(W, H, spp, 0, 7, 0, 0, 0, 0)
 
-            timed(plain, 10)
-            timed(chain, 10)
-            calls = max(10, int(WINDOW_MS / max(timed(chain, 20), timed(plain, 20))) + 1)
-            rounds = [(timed(plain, calls), timed(chain, calls)) for _ in range(ROUNDS)]
-            a, b = download("plain"), download("chain")
-            plane = b[4]
-            group = 64 // min(spp, 64)  # pixels per wave
-            per_wave = plane[:n - n % group].reshape(-1, group).max(axis=1)
-            res = {"calls_per_window": calls,
-                   "plain_ms": {"median": statistics.median(r[0] for r in rounds), "min": min(r[0] for r in rounds),
-                                "max": max(r[0] for r in rounds)},
-                   "chain_ms": {"median": statistics.median(r[1] for r in rounds), "min": min(r[1] for r in rounds),
-                                "max": max(r[1] for r in rounds)},
-                   "chain_over_plain": statistics.median(r[1] / r[0] for r in rounds),
-                   "ratio_min": min(r[1] / r[0] for r in rounds), "ratio_max": max(r[1] / r[0] for r in rounds),
-                   "chain_plane_mean": float(plane.mean()), "chain_plane_max": int(plane.max()),
-                   "chain_plane_mean_of_wave_max": float(per_wave.mean()),
-                   "same_bits_as_plain": bool(all(x.tobytes() == y.tobytes() for x, y in zip(a[:4], b[:4])))}
-            if sid in BUDGETED:
-                assert res["same_bits_as_plain"] and res["chain_plane_max"] == 0, "a scene without delta surfaces must give the plain bits"
-                res["budget"] = BUDGET
-                res["verdict"] = "HIT" if res["chain_over_plain"] <= BUDGET else "MISS"
-            key = "%s %dx%d @ %d spp" % (sid, W, H, spp)
-            doc["cases"][key] = res
-            print(key, json.dumps(res), flush=True)
-    for side in bufs.values():
-        for p in side:
-            L.pt_device_free(0, p)
-    hip.hipEventDestroy(e0)
-    hip.hipEventDestroy(e1)
-    L.pt_ctx_destroy(ctx)
-    path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "aov_chain_timing.json")
-    with open(path, "w") as f:
-        json.dump(doc, f, indent=1)
-        f.write("\n")
-    print("->", path)
+                def plain():
+                    assert L.pt_ctx_render_aov(d.ctx, C.byref(cfg), *bufs["plain"][:4], stream) == 0, L.pt_last_error()
+
+                def chain():
+                    assert L.pt_ctx_render_aov_ex(d.ctx, C.byref(cfg), C.byref(on), *bufs["chain"], stream) == 0, L.pt_last_error()
+
+                ev.window(plain, 10)
+                ev.window(chain, 10)
+                calls = max(10, int(WINDOW_MS / (max(ev.window(chain, 20), ev.window(plain, 20)) / 20)) + 1)
+                rounds = [(ev.window(plain, calls) / calls, ev.window(chain, calls) / calls) for _ in range(ROUNDS)]
+                ratios = [r[1] / r[0] for r in rounds]
+                a, b = download("plain"), download("chain")
+                plane = b[4]
+                group = 64 // min(spp, 64)  # pixels per wave
+                per_wave = plane[:n - n % group].reshape(-1, group).max(axis=1)
+                res = {"calls_per_window": calls, "plain_ms": spread([r[0] for r in rounds]), "chain_ms": spread([r[1] for r in rounds]),
+                       "chain_over_plain": statistics.median(ratios), "ratio_min": min(ratios), "ratio_max": max(ratios),
+                       "chain_plane_mean": float(plane.mean()), "chain_plane_max": int(plane.max()),
+                       "chain_plane_mean_of_wave_max": float(per_wave.mean()),
+                       "same_bits_as_plain": bool(all(x.tobytes() == y.tobytes() for x, y in zip(a[:4], b[:4])))}
+                if sid in BUDGETED:
+                    assert res["same_bits_as_plain"] and res["chain_plane_max"] == 0, "a scene without delta surfaces must give the plain bits"
+                    res["budget"] = BUDGET
+                    res["verdict"] = "HIT" if res["chain_over_plain"] <= BUDGET else "MISS"
+                key = "%s %dx%d @ %d spp" % (sid, W, H, spp)
+                doc["cases"][key] = res
+                timing.report(key, res)
+    timing.write(doc, "aov_chain_timing.json")
 
 
 if __name__ == "__main__":
-    with gpudev.stream() as own:
-        main(own)
+    main()

@@ -2,11 +2,9 @@
 """HIP-event time of pt_ctx_reproject_var_weighted and pt_ctx_spp_plane on the GPU, set against pt_ctx_reproject_var in the same
 run and process, for DESIGN.md section 4.
 
-tools/reproject_moved_timing.py's method and inputs, at 1024x768 and 4096x4096, with normals: every pixel on one plane with one
-normal and a history length of 32 samples (so that a pixel of every count used here ends long), the history camera 0.01 to the
-side, so every tap is taken; after a warm-up, N back-to-back calls on a caller's stream between two HIP events, N chosen so that
-the window is at least 0.25 s; five windows give the median.  The calls block, so a window holds the host's turn-around too - the
-yardstick's as much as the weighted call's.
+tools/reproject_moved_timing.py's inputs, at 1024x768 and 4096x4096, with normals: every pixel on one plane with one normal and a
+history length of 32 samples (so that a pixel of every count used here ends long), the history camera 0.01 to the side, so every
+tap is taken.  The protocol is tools/timing.py's, on a caller's stream.
 
 The yardstick is pt_ctx_reproject_var at weight 8 (its code is unchanged).  Per size:
   steady-constant   a plane that holds 8 everywhere: the yardstick's arithmetic and its bytes plus the plane's 4 B per pixel
@@ -23,9 +21,7 @@ recorded beside each and gates nothing.  Without a budget:
     python tools/reproject_weighted_timing.py [out.json]
 """
 import ctypes as C
-import json
 import os
-import statistics
 import sys
 
 import numpy as np
@@ -37,141 +33,100 @@ import kats_camera  # noqa: E402
 import ptlib  # noqa: E402
 import reproject_moved_ref as mref  # noqa: E402
 import reproject_ref as ref  # noqa: E402
+import timing  # noqa: E402
 from reproject_moved_ref import IDENTITY  # noqa: E402
 
 SIZES = ((1024, 768), (4096, 4096))
-WINDOW_MS = 250.0
 DEPTH = 6.0
 BUDGET = 1.10
 
 
-def main(stream):
+def main():
     L = ptlib.product()
-    assert L.pt_device_count() >= 1, "reproject_weighted_timing needs a GPU: there is nothing to time without one"
-    hip = gpudev.hip_runtime()
-    hip.hipEventElapsedTime.argtypes = [C.POINTER(C.c_float), C.c_void_p, C.c_void_p]
-    hip.hipEventRecord.argtypes = [C.c_void_p, C.c_void_p]
-    hip.hipEventSynchronize.argtypes = [C.c_void_p]
-    ctx = C.c_void_p()
-    assert L.pt_ctx_create(0, C.byref(ctx)) == 0, L.pt_last_error()
-    e0, e1 = C.c_void_p(), C.c_void_p()
-    assert hip.hipEventCreate(C.byref(e0)) == 0 and hip.hipEventCreate(C.byref(e1)) == 0
+    timing.need_gpu(L, "reproject_weighted_timing")
     doc = {"command": "python tools/reproject_weighted_timing.py", "isa_hash": L.pt_kernel_isa_hash().decode(),
            "method": "median of 5 HIP-event windows of N back-to-back calls (window >= %.0f ms) / N, after a warm-up; the yardstick "
-                     "(pt_ctx_reproject_var, weight 8) is timed in the same run and process, before the cases" % WINDOW_MS,
+                     "(pt_ctx_reproject_var, weight 8) is timed in the same run and process, before the cases" % timing.WINDOW_MS,
            "inputs": "tools/reproject_moved_timing.py's: every pixel on one plane (depth %g, one normal, history length 32), the "
                      "history camera 0.01 to the side; with normals; object id 1; planes: 8 everywhere, and 4/8/16/32 by tiles of "
                      "8 x 8 with a twentieth of the tiles 0" % DEPTH,
            "budget": "steady-constant and steady-mixed: %.2f x the yardstick of the same run; the others carry none" % BUDGET,
            "cases": {}}
     rng = np.random.default_rng(1)
-
-    def timed(fn, n):
-        assert hip.hipEventRecord(e0, stream) == 0
-        for _ in range(n):
-            fn()
-        assert hip.hipEventRecord(e1, stream) == 0
-        assert hip.hipEventSynchronize(e1) == 0
-        ms = C.c_float()
-        assert hip.hipEventElapsedTime(C.byref(ms), e0, e1) == 0
-        return ms.value
-
-    def measure(fn):
-        timed(fn, 20)  # warm-up: code objects
-        n = max(20, int(WINDOW_MS / (timed(fn, 50) / 50)) + 1)
-        per = [timed(fn, n) / n for _ in range(5)]
-        return {"calls_per_window": n, "ms_median": statistics.median(per), "ms_min": min(per), "ms_max": max(per)}
-
     cam_d = kats_camera.CORNELL_CAM
     hist_d = dict(cam_d, position=(0.01, cam_d["position"][1], cam_d["position"][2]))
     cam, hist_cam = ref.pt_camera(cam_d), ref.pt_camera(hist_d)
-    for w, h in SIZES:
-        npix = w * h
-        tiles = rng.choice(np.array([4, 8, 16, 32, 0], dtype=np.uint32), size=((h + 7) // 8, (w + 7) // 8), p=[0.2375] * 4 + [0.05])
-        mixed = np.repeat(np.repeat(tiles, 8, axis=0), 8, axis=1)[:h, :w]
-        planes = dict(color=rng.random(npix * 3, dtype=np.float32), hcolor=rng.random(npix * 3, dtype=np.float32),
-                      depth=np.full(npix, DEPTH, dtype=np.float32), oid=np.ones(npix, dtype=np.int32),
-                      normal=np.tile(np.array([0.0, 0.0, 1.0], dtype=np.float32), npix), hlen=np.full(npix, 32.0, dtype=np.float32),
-                      hmom=rng.random(npix * 2, dtype=np.float32), out=np.zeros(npix * 3, dtype=np.float32),
-                      len=np.zeros(npix, dtype=np.float32), mom=np.zeros(npix * 2, dtype=np.float32), err=np.zeros(npix, dtype=np.float32),
-                      constant=np.full(npix, 8, dtype=np.uint32), mixed=np.ascontiguousarray(mixed).reshape(-1),
-                      built=np.zeros(npix, dtype=np.uint32), mask=(rng.random(npix) < 0.05).astype(np.uint8))
-        B = {}
-        for k, v in planes.items():
-            B[k] = C.c_void_p()
-            assert L.pt_device_malloc(0, v.nbytes, C.byref(B[k])) == 0, L.pt_last_error()
-            assert hip.hipMemcpy(B[k], v.ctypes.data_as(C.c_void_p), v.nbytes, 1) == 0
-        share_empty = float((planes["mixed"] == 0).mean())
-        del planes
-        pixel = DEPTH * cam_d["sensor_width"] / cam_d["focal_length"] / w  # a pixel's width on the plane
-        moved_table = mref.table([IDENTITY, (0.4 * pixel, 0.0, 0.0, 1.0)])
-        pv = ptlib.PtReprojectVarParams(8, 0.0, 0.0, 0.0, 0, 0, 0)
-        guides = (B["color"], B["depth"], B["oid"], B["normal"])
-        history = (C.byref(hist_cam), B["hcolor"], B["hlen"], B["hmom"], B["depth"], B["oid"], B["normal"])
-        outs = (B["out"], B["len"], B["mom"], B["err"])
+    with gpudev.stream() as stream, gpudev.Device(L) as d, timing.Events(stream) as ev:
+        for w, h in SIZES:
+            npix = w * h
+            tiles = rng.choice(np.array([4, 8, 16, 32, 0], dtype=np.uint32), size=((h + 7) // 8, (w + 7) // 8), p=[0.2375] * 4 + [0.05])
+            mixed = np.repeat(np.repeat(tiles, 8, axis=0), 8, axis=1)[:h, :w]
+            planes = dict(color=rng.random(npix * 3, dtype=np.float32), hcolor=rng.random(npix * 3, dtype=np.float32),
+                          depth=np.full(npix, DEPTH, dtype=np.float32), oid=np.ones(npix, dtype=np.int32),
+                          normal=np.tile(np.array([0.0, 0.0, 1.0], dtype=np.float32), npix), hlen=np.full(npix, 32.0, dtype=np.float32),
+                          hmom=rng.random(npix * 2, dtype=np.float32), out=np.zeros(npix * 3, dtype=np.float32),
+                          len=np.zeros(npix, dtype=np.float32), mom=np.zeros(npix * 2, dtype=np.float32), err=np.zeros(npix, dtype=np.float32),
+                          constant=np.full(npix, 8, dtype=np.uint32), mixed=np.ascontiguousarray(mixed).reshape(-1),
+                          built=np.zeros(npix, dtype=np.uint32), mask=(rng.random(npix) < 0.05).astype(np.uint8))
+            B = timing.upload_planes(d, planes)
+            share_empty = float((planes["mixed"] == 0).mean())
+            del planes
+            pixel = DEPTH * cam_d["sensor_width"] / cam_d["focal_length"] / w  # a pixel's width on the plane
+            moved_table = mref.table([IDENTITY, (0.4 * pixel, 0.0, 0.0, 1.0)])
+            pv = ptlib.PtReprojectVarParams(8, 0.0, 0.0, 0.0, 0, 0, 0)
+            guides = (B["color"], B["depth"], B["oid"], B["normal"])
+            history = (C.byref(hist_cam), B["hcolor"], B["hlen"], B["hmom"], B["depth"], B["oid"], B["normal"])
+            outs = (B["out"], B["len"], B["mom"], B["err"])
 
-        def yardstick(hist=history):
-            def call():
-                rc = L.pt_ctx_reproject_var(ctx, w, h, C.byref(pv), C.byref(cam), *guides, *hist, *outs, stream)
-                assert rc == 0, L.pt_last_error()
-            return call
+            def yardstick(hist=history):
+                def call():
+                    rc = L.pt_ctx_reproject_var(d.ctx, w, h, C.byref(pv), C.byref(cam), *guides, *hist, *outs, stream)
+                    assert rc == 0, L.pt_last_error()
+                return call
 
-        def weighted(plane, hist=history, table=None, n_motion=0):
-            def call():
-                rc = L.pt_ctx_reproject_var_weighted(ctx, w, h, C.byref(pv), C.byref(cam), *guides, B[plane], *hist, *outs, table, n_motion,
-                                                     stream)
-                assert rc == 0, L.pt_last_error()
-            return call
+            def weighted(plane, hist=history, table=None, n_motion=0):
+                def call():
+                    rc = L.pt_ctx_reproject_var_weighted(d.ctx, w, h, C.byref(pv), C.byref(cam), *guides, B[plane], *hist, *outs, table,
+                                                         n_motion, stream)
+                    assert rc == 0, L.pt_last_error()
+                return call
 
-        def spp_plane(mask):
-            def call():
-                rc = L.pt_ctx_spp_plane(ctx, w, h, 8, mask, 32, B["built"], stream)
-                assert rc == 0, L.pt_last_error()
-            return call
+            def spp_plane(mask):
+                def call():
+                    rc = L.pt_ctx_spp_plane(d.ctx, w, h, 8, mask, 32, B["built"], stream)
+                    assert rc == 0, L.pt_last_error()
+                return call
 
-        def copy():
-            assert hip.hipMemcpyAsync(B["out"], B["color"], npix * 12, 3, stream) == 0  # device to device
-            assert hip.hipStreamSynchronize(stream) == 0
+            def shares():
+                ln, err = d.download(B["len"], npix), d.download(B["err"], npix)
+                return {"mean_len": float(ln.mean()), "share_finite_error": float(np.isfinite(err).mean())}
 
-        def shares():
-            ln, err = np.zeros(npix, dtype=np.float32), np.zeros(npix, dtype=np.float32)
-            assert L.pt_device_download(0, ln.ctypes.data_as(C.c_void_p), B["len"], ln.nbytes) == 0
-            assert L.pt_device_download(0, err.ctypes.data_as(C.c_void_p), B["err"], err.nbytes) == 0
-            return {"mean_len": float(ln.mean()), "share_finite_error": float(np.isfinite(err).mean())}
-
-        none = (None,) * 7
-        res = {"yardstick": measure(yardstick()), "share_of_count_0": share_empty}
-        for case, fn, budget in (("steady-constant", weighted("constant"), True), ("steady-mixed", weighted("mixed"), True),
-                                 ("moved", weighted("mixed", table=moved_table, n_motion=2), False)):
-            m = measure(fn)
-            m.update(shares())
-            m["over_yardstick"] = m["ms_median"] / res["yardstick"]["ms_median"]
-            if budget:
-                m["budget"] = "HIT" if m["over_yardstick"] <= BUDGET else "MISS"
-            res[case] = m
-        first = {"yardstick": measure(yardstick(none)), "weighted": measure(weighted("constant", none))}
-        first["over_yardstick"] = first["weighted"]["ms_median"] / first["yardstick"]["ms_median"]
-        res["first-frame"] = first
-        plane = {"copy_of_the_colour_frame": measure(copy), "with_mask": measure(spp_plane(B["mask"])), "without_mask": measure(spp_plane(None))}
-        for k in ("with_mask", "without_mask"):
-            plane[k]["copies"] = plane[k]["ms_median"] / plane["copy_of_the_colour_frame"]["ms_median"]
-        plane["bytes_allow_copies"] = {"with_mask": 5.0 / 24.0, "without_mask": 4.0 / 24.0}
-        res["spp-plane"] = plane
-        name = "%dx%d" % (w, h)
-        doc["cases"][name] = res
-        print(name, json.dumps(res), flush=True)
-        for p in B.values():
-            L.pt_device_free(0, p)
-    hip.hipEventDestroy(e0)
-    hip.hipEventDestroy(e1)
-    L.pt_ctx_destroy(ctx)
-    path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "reproject_weighted_timing.json")
-    with open(path, "w") as f:
-        json.dump(doc, f, indent=1)
-        f.write("\n")
-    print("->", path)
+            copy_sync, _ = timing.copy_yardstick(B["out"], B["color"], npix * 12, stream)
+            none = (None,) * 7
+            res = {"yardstick": ev.measure(yardstick()), "share_of_count_0": share_empty}
+            for case, fn, budget in (("steady-constant", weighted("constant"), True), ("steady-mixed", weighted("mixed"), True),
+                                     ("moved", weighted("mixed", table=moved_table, n_motion=2), False)):
+                m = ev.measure(fn)
+                m.update(shares())
+                m["over_yardstick"] = m["ms_median"] / res["yardstick"]["ms_median"]
+                if budget:
+                    m["budget"] = "HIT" if m["over_yardstick"] <= BUDGET else "MISS"
+                res[case] = m
+            first = {"yardstick": ev.measure(yardstick(none)), "weighted": ev.measure(weighted("constant", none))}
+            first["over_yardstick"] = first["weighted"]["ms_median"] / first["yardstick"]["ms_median"]
+            res["first-frame"] = first
+            plane = {"copy_of_the_colour_frame": ev.measure(copy_sync), "with_mask": ev.measure(spp_plane(B["mask"])),
+                     "without_mask": ev.measure(spp_plane(None))}
+            for k in ("with_mask", "without_mask"):
+                plane[k]["copies"] = plane[k]["ms_median"] / plane["copy_of_the_colour_frame"]["ms_median"]
+            plane["bytes_allow_copies"] = {"with_mask": 5.0 / 24.0, "without_mask": 4.0 / 24.0}
+            res["spp-plane"] = plane
+            name = "%dx%d" % (w, h)
+            doc["cases"][name] = res
+            timing.report(name, res)
+            timing.free_planes(d, B)
+    timing.write(doc, "reproject_weighted_timing.json")
 
 
 if __name__ == "__main__":
-    with gpudev.stream() as own:
-        main(own)
+    main()

@@ -15,9 +15,7 @@ region: pt_ctx_set_scene per frame, then pt_ctx_set_camera per frame, wall time,
     python tools/set_camera_timing.py [--big] [out.json]
 """
 import ctypes as C
-import json
 import os
-import statistics
 import sys
 import time
 
@@ -25,10 +23,11 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+import gpudev  # noqa: E402
 import ptlib  # noqa: E402
 import reproject_ref  # noqa: E402
-import upsample_ref  # noqa: E402
-from ptlib import PtCamera, PtConfig, PtObject, PtStats, PtTriangle  # noqa: E402
+import timing  # noqa: E402
+from ptlib import PtConfig, PtObject, PtStats, PtTriangle  # noqa: E402
 
 N = 7
 BATCH = 200
@@ -77,14 +76,9 @@ def orbit(cam, deg):
     return ptlib.make_camera(d["position"], d["direction"], d["focal_length"], d["sensor_width"], d["aspect_ratio"])
 
 
-def stats(ms):
-    return {"ms_median": statistics.median(ms), "ms_min": min(ms), "ms_max": max(ms)}
-
-
 def main():
-    args = [a for a in sys.argv[1:] if a != "--big"]
     L = ptlib.product()
-    assert L.pt_device_count() >= 1, "set_camera_timing needs a GPU: the uploads are what nobody has measured"
+    timing.need_gpu(L, "set_camera_timing")
     mesh = ptlib.load_scene_py(ptlib.scene_path("mesh"))
     scenes = [ptlib.load_scene_py(ptlib.scene_path("cornell")), mesh, Generated(L, mesh, 100)]
     if "--big" in sys.argv[1:]:
@@ -96,9 +90,6 @@ def main():
                      "tools/upsample_timing.py at %dx%d @ %d spp with the camera update inside, the median of %d frames" % (N, BATCH, W, H, SPP, N),
            "per_call": {}, "per_frame": {}}
 
-    def set_scene(ctx, sc, cam):
-        assert L.pt_ctx_set_scene(ctx, C.byref(cam), sc.objs, sc.n_objs, sc.tris, sc.n_tris) == 0, L.pt_last_error()
-
     def set_camera(ctx, cam):
         rebuilt = C.c_int()
         assert L.pt_ctx_set_camera(ctx, C.byref(cam), C.byref(rebuilt)) == 0, L.pt_last_error()
@@ -107,86 +98,71 @@ def main():
     for sc in scenes:
         once = sc.n_tris > 100000  # the largest scene: seconds per rebuild, measured once
         cams = (sc.cam, orbit(sc.cam, 2.0))
-        ctx = C.c_void_p()
-        assert L.pt_ctx_create(0, C.byref(ctx)) == 0, L.pt_last_error()
-        set_scene(ctx, sc, cams[0])  # warm-up: allocations
-        ms = []
-        for k in range(1 if once else N):
+        with gpudev.Device(L, sc, cams[0]) as d:  # warm-up: allocations
+            ctx = d.ctx
+            ms = []
+            for k in range(1 if once else N):
+                t0 = time.perf_counter()
+                d.set_scene(sc, cams[(k + 1) & 1])
+                ms.append((time.perf_counter() - t0) * 1e3)
+            res = {"triangles": sc.n_tris, "set_scene": timing.stats(ms)}
+            d.set_scene(sc, cams[0])
+            assert set_camera(ctx, cams[1]) == 0 and set_camera(ctx, cams[0]) == 0, "2 degrees must stay on the fast path"
+            ms = []
+            for _ in range(N):
+                t0 = time.perf_counter()
+                for k in range(BATCH):
+                    set_camera(ctx, cams[(k + 1) & 1])
+                ms.append((time.perf_counter() - t0) * 1e3 / BATCH)
+            res["set_camera_fast"] = timing.stats(ms)
+            res["set_scene_over_set_camera_fast"] = res["set_scene"]["ms_median"] / res["set_camera_fast"]["ms_median"]
             t0 = time.perf_counter()
-            set_scene(ctx, sc, cams[(k + 1) & 1])
-            ms.append((time.perf_counter() - t0) * 1e3)
-        res = {"triangles": sc.n_tris, "set_scene": stats(ms)}
-        set_scene(ctx, sc, cams[0])
-        assert set_camera(ctx, cams[1]) == 0 and set_camera(ctx, cams[0]) == 0, "2 degrees must stay on the fast path"
-        ms = []
-        for _ in range(N):
-            t0 = time.perf_counter()
-            for k in range(BATCH):
-                set_camera(ctx, cams[(k + 1) & 1])
-            ms.append((time.perf_counter() - t0) * 1e3 / BATCH)
-        res["set_camera_fast"] = stats(ms)
-        res["set_scene_over_set_camera_fast"] = res["set_scene"]["ms_median"] / res["set_camera_fast"]["ms_median"]
-        t0 = time.perf_counter()
-        rebuilt = set_camera(ctx, orbit(sc.cam, 90.0))
-        res["set_camera_slow_once"] = {"ms": (time.perf_counter() - t0) * 1e3, "rebuilt": rebuilt}
-        doc["per_call"][sc.id] = res
-        print(sc.id, json.dumps(res), flush=True)
-        L.pt_ctx_destroy(ctx)
+            rebuilt = set_camera(ctx, orbit(sc.cam, 90.0))
+            res["set_camera_slow_once"] = {"ms": (time.perf_counter() - t0) * 1e3, "rebuilt": rebuilt}
+            doc["per_call"][sc.id] = res
+            timing.report(sc.id, res)
 
     # ---- the loop: wall time per frame, the camera update inside
-    def alloc(nbytes):
-        p = C.c_void_p()
-        assert L.pt_device_malloc(0, nbytes, C.byref(p)) == 0, L.pt_last_error()
-        return p
-
     w, h = W // 2, H // 2
     n, nl = W * H, w * h
     for sc in scenes[1:3]:
         cams = (sc.cam, orbit(sc.cam, 2.0))
-        ctx = C.c_void_p()
-        assert L.pt_ctx_create(0, C.byref(ctx)) == 0, L.pt_last_error()
-        set_scene(ctx, sc, cams[0])
-        F = {k: alloc(n * b) for k, b in (("albedo", 12), ("normal", 12), ("depth", 4), ("oid", 4), ("out", 12))}
-        Lo = {k: alloc(nl * b) for k, b in (("color", 12), ("albedo", 12), ("normal", 12), ("depth", 4), ("oid", 4))}
-        st = PtStats()
-        seed = [100]
+        with gpudev.Device(L, sc, cams[0]) as d:
+            ctx = d.ctx
+            F = {k: d.alloc(n * b) for k, b in (("albedo", 12), ("normal", 12), ("depth", 4), ("oid", 4), ("out", 12))}
+            Lo = {k: d.alloc(nl * b) for k, b in (("color", 12), ("albedo", 12), ("normal", 12), ("depth", 4), ("oid", 4))}
+            st = PtStats()
+            seed = [100]
 
-        def chain():
-            seed[0] += 1
-            lo, full = PtConfig(w, h, SPP, 0, seed[0], 0, 0, 0, 0), PtConfig(W, H, SPP, 0, seed[0], 0, 0, 0, 0)
-            assert L.pt_ctx_render(ctx, C.byref(lo), Lo["color"], None, None, None, None, C.byref(st)) == 0, L.pt_last_error()
-            assert L.pt_ctx_render_aov(ctx, C.byref(lo), Lo["albedo"], Lo["normal"], Lo["depth"], Lo["oid"], None) == 0, L.pt_last_error()
-            assert L.pt_ctx_render_aov(ctx, C.byref(full), F["albedo"], F["normal"], F["depth"], F["oid"], None) == 0, L.pt_last_error()
-            rc = L.pt_ctx_upsample(ctx, W, H, w, h, None, Lo["color"], Lo["depth"], Lo["oid"], Lo["normal"], Lo["albedo"], F["depth"],
-                                   F["oid"], F["normal"], F["albedo"], F["out"], None, None)
-            assert rc == 0, L.pt_last_error()
+            def chain():
+                seed[0] += 1
+                lo, full = PtConfig(w, h, SPP, 0, seed[0], 0, 0, 0, 0), PtConfig(W, H, SPP, 0, seed[0], 0, 0, 0, 0)
+                assert L.pt_ctx_render(ctx, C.byref(lo), Lo["color"], None, None, None, None, C.byref(st)) == 0, L.pt_last_error()
+                assert L.pt_ctx_render_aov(ctx, C.byref(lo), Lo["albedo"], Lo["normal"], Lo["depth"], Lo["oid"], None) == 0, L.pt_last_error()
+                assert L.pt_ctx_render_aov(ctx, C.byref(full), F["albedo"], F["normal"], F["depth"], F["oid"], None) == 0, L.pt_last_error()
+                rc = L.pt_ctx_upsample(ctx, W, H, w, h, None, Lo["color"], Lo["depth"], Lo["oid"], Lo["normal"], Lo["albedo"], F["depth"],
+                                       F["oid"], F["normal"], F["albedo"], F["out"], None, None)
+                assert rc == 0, L.pt_last_error()
 
-        res = {"triangles": sc.n_tris}
-        for name, update in (("set_scene_per_frame", lambda cam: set_scene(ctx, sc, cam)),
-                             ("set_camera_per_frame", lambda cam: set_camera(ctx, cam)), ("no_update", lambda cam: None)):
-            update(cams[0])
-            chain()  # warm-up: scratch, code objects, the scene's pass rate
-            total, upd = [], []
-            for k in range(N):
-                t0 = time.perf_counter()
-                update(cams[(k + 1) & 1])
-                t1 = time.perf_counter()
-                chain()
-                t2 = time.perf_counter()
-                total.append((t2 - t0) * 1e3)
-                upd.append((t1 - t0) * 1e3)
-            res[name] = {"frame": stats(total), "update": stats(upd)}
-        res["set_camera_over_set_scene"] = res["set_camera_per_frame"]["frame"]["ms_median"] / res["set_scene_per_frame"]["frame"]["ms_median"]
-        doc["per_frame"]["%s %dx%d @ %d spp" % (sc.id, W, H, SPP)] = res
-        print(sc.id, json.dumps(res), flush=True)
-        for p in list(F.values()) + list(Lo.values()):
-            L.pt_device_free(0, p)
-        L.pt_ctx_destroy(ctx)
-    path = args[0] if args else os.path.join(ROOT, "profiles", "set_camera_timing.json")
-    with open(path, "w") as f:
-        json.dump(doc, f, indent=1)
-        f.write("\n")
-    print("->", path)
+            res = {"triangles": sc.n_tris}
+            for name, update in (("set_scene_per_frame", lambda cam: d.set_scene(sc, cam)),
+                                 ("set_camera_per_frame", lambda cam: set_camera(ctx, cam)), ("no_update", lambda cam: None)):
+                update(cams[0])
+                chain()  # warm-up: scratch, code objects, the scene's pass rate
+                total, upd = [], []
+                for k in range(N):
+                    t0 = time.perf_counter()
+                    update(cams[(k + 1) & 1])
+                    t1 = time.perf_counter()
+                    chain()
+                    t2 = time.perf_counter()
+                    total.append((t2 - t0) * 1e3)
+                    upd.append((t1 - t0) * 1e3)
+                res[name] = {"frame": timing.stats(total), "update": timing.stats(upd)}
+            res["set_camera_over_set_scene"] = res["set_camera_per_frame"]["frame"]["ms_median"] / res["set_scene_per_frame"]["frame"]["ms_median"]
+            doc["per_frame"]["%s %dx%d @ %d spp" % (sc.id, W, H, SPP)] = res
+            timing.report(sc.id, res)
+    timing.write(doc, "set_camera_timing.json")
 
 
 if __name__ == "__main__":

@@ -7,14 +7,11 @@ The pass.  Sizes: 1024x768 and 4096x4096.  Cases: with albedo, out of place (12 
 12 B written: 44 B per pixel); without albedo (32 B); in place on the albedo (44 B); a frame that is all misses (the ids read,
 the background written: 16 B - the yardstick's convention counts its 12 B written against the copy's 24 B, a budget of 0.5
 copies).  The planes are synthetic: a disc of one object over a floor of another, a quarter of the frame sky, a table of three
-records.  The yardstick copies 24 B per pixel, so a case's budget is its compulsory bytes / 24 of the copy's time.  A call is far
-below a millisecond, so one call is not timed: after a warm-up of the same shape, N back-to-back calls are put between two HIP
-events on the null stream - the call blocks, so everything it issued is complete when the second event is recorded - N chosen
-so that the window is at least 0.25 s, and the window is divided by N; five such windows give the median and the spread.
-pt_ctx_solid ends in a stream synchronise, so its window holds the host's turn-around between calls too: the like-for-like
-yardstick is the copy with a stream synchronise after each ("copy_sync"); the back-to-back copy ("copy") is recorded beside it.
+records.  The yardstick copies 24 B per pixel, so a case's budget is its compulsory bytes / 24 of the copy's time.  The protocol
+is tools/timing.py's, on the null stream; the like-for-like yardstick is the copy with a stream synchronise after each
+("copy_sync"), the back-to-back copy ("copy") is recorded beside it.
 
-The loop.  On cornell and mesh.json at 1024x768, wall time per frame, median of 30 after a warm-up, of
+The loop.  On cornell and mesh.json at 1024x768, wall time per frame (timing.wall), median of 30, of
   solid:  pt_ctx_render_aov(1 spp) + pt_ctx_solid + pt_ctx_overlay (sky, grid, one object selected) + pt_ctx_present
   traced: pt_ctx_render(8 spp) + pt_ctx_render_aov(8 spp) - the front end of the traced loop, as tools/upsample_timing.py's
           "full" chain makes it, before any reprojection, denoiser, overlay or present.
@@ -22,11 +19,8 @@ The loop.  On cornell and mesh.json at 1024x768, wall time per frame, median of 
     python tools/solid_timing.py [out.json]
 """
 import ctypes as C
-import json
 import os
-import statistics
 import sys
-import time
 
 import numpy as np
 
@@ -36,10 +30,10 @@ import gpudev  # noqa: E402
 import overlay_ref  # noqa: E402
 import ptlib  # noqa: E402
 import solid_ref as ref  # noqa: E402
+import timing  # noqa: E402
 from ptlib import PtConfig, PtPresentParams, PtStats  # noqa: E402
 
 SIZES = ((1024, 768), (4096, 4096))
-WINDOW_MS = 250.0
 COPY_BYTES = 24
 CAM = dict(position=(0.5, 3.0, 4.0), direction=(-0.1, -0.6, -0.79), focal_length=0.035, sensor_width=0.036, aspect_ratio=1.5)
 LOOKS = [((0.0, 0.0, 0.0), ref.DIFFUSE), ((0.0, 0.0, 0.0), ref.SPECULAR), ((2.0, 2.0, 2.0), ref.DIFFUSE)]
@@ -48,37 +42,14 @@ LOOP_SCENES, LOOP_SIZE, LOOP_SPP, FRAMES = ("cornell", "mesh"), (1024, 768), 8, 
 
 def main():
     L = ptlib.product()
-    assert L.pt_device_count() >= 1, "solid_timing needs a GPU: there is nothing to time without one"
-    hip = gpudev.hip_runtime()
-    hip.hipEventElapsedTime.argtypes = [C.POINTER(C.c_float), C.c_void_p, C.c_void_p]
-    hip.hipEventRecord.argtypes = [C.c_void_p, C.c_void_p]
-    hip.hipEventSynchronize.argtypes = [C.c_void_p]
-    e0, e1 = C.c_void_p(), C.c_void_p()
-    assert hip.hipEventCreate(C.byref(e0)) == 0 and hip.hipEventCreate(C.byref(e1)) == 0
+    timing.need_gpu(L, "solid_timing")
     doc = {"command": "python tools/solid_timing.py", "isa_hash": L.pt_kernel_isa_hash().decode(),
            "method": "median of 5 HIP-event windows of N back-to-back calls (window >= %.0f ms) / N, after a warm-up; the ratio is "
                      "against the copy with a stream synchronise after each, the budget is compulsory bytes / %d; the loop: wall time "
-                     "per frame, median of %d after a warm-up" % (WINDOW_MS, COPY_BYTES, FRAMES),
+                     "per frame, median of %d after a warm-up" % (timing.WINDOW_MS, COPY_BYTES, FRAMES),
            "cases": {}, "loop": {}}
     rng = np.random.default_rng(1)
-
-    def timed(fn, n):
-        assert hip.hipEventRecord(e0, None) == 0
-        for _ in range(n):
-            fn()
-        assert hip.hipEventRecord(e1, None) == 0
-        assert hip.hipEventSynchronize(e1) == 0
-        ms = C.c_float()
-        assert hip.hipEventElapsedTime(C.byref(ms), e0, e1) == 0
-        return ms.value
-
-    def measure(fn):
-        timed(fn, 20)
-        n = max(20, int(WINDOW_MS / (timed(fn, 50) / 50)) + 1)
-        per = [timed(fn, n) / n for _ in range(5)]
-        return {"calls_per_window": n, "ms_median": statistics.median(per), "ms_min": min(per), "ms_max": max(per)}
-
-    with gpudev.Device(L) as d:
+    with timing.Events() as ev, gpudev.Device(L) as d:
         cam = ref.pt_camera(CAM)
         looks = ref.looks_array(LOOKS)
         s = ref.struct(ref.params(flags=ref.HEADLIGHT | ref.REFLECT_SKY))
@@ -95,15 +66,8 @@ def main():
             d.upload(d_id, oid.reshape(n))
             d.upload(d_miss, np.full(n, -1, dtype=np.int32))
             d.upload(d_z, np.where(oid.reshape(n) < 0, np.float32(np.inf), (4.0 + 8.0 * rng.random(n)).astype(np.float32)).astype(np.float32))
-
-            def copy_sync():
-                assert hip.hipMemcpyAsync(d_out, d_alb, n * 12, 3, None) == 0  # device to device
-                assert hip.hipStreamSynchronize(None) == 0
-
-            def copy():
-                assert hip.hipMemcpyAsync(d_out, d_alb, n * 12, 3, None) == 0
-
-            yard = {"copy_sync": measure(copy_sync), "copy": measure(copy)}
+            copy_sync, copy = timing.copy_yardstick(d_out, d_alb, n * 12)
+            yard = {"copy_sync": ev.measure(copy_sync), "copy": ev.measure(copy)}
             cases = (("with albedo, out of place", d_alb, d_id, d_out, 44),
                      ("without albedo, out of place", None, d_id, d_out, 32),
                      ("all misses, out of place", d_alb, d_miss, d_out, 12),
@@ -114,7 +78,7 @@ def main():
                     rc = L.pt_ctx_solid(d.ctx, w, h, C.byref(s), C.byref(cam), alb, d_n, d_z, ids, looks, len(LOOKS), out, None)
                     assert rc == 0, L.pt_last_error()
 
-                res = {"solid": measure(solid), "compulsory_bytes_per_pixel": nbytes, "budget_in_copies": nbytes / COPY_BYTES}
+                res = {"solid": ev.measure(solid), "compulsory_bytes_per_pixel": nbytes, "budget_in_copies": nbytes / COPY_BYTES}
                 res.update(yard)
                 res["solid_over_copy_sync"] = res["solid"]["ms_median"] / yard["copy_sync"]["ms_median"]
                 res["solid_over_copy"] = res["solid"]["ms_median"] / yard["copy"]["ms_median"]
@@ -158,28 +122,14 @@ def main():
                 assert L.pt_ctx_render(d.ctx, C.byref(cfg), P["color"], None, None, None, None, C.byref(st)) == 0, L.pt_last_error()
                 guides(LOOP_SPP)
 
-            res = {}
-            for name, chain in (("solid", solid_chain), ("traced_front_end", traced_front_end)):
-                chain()  # warm-up: scratch, code objects
-                times = []
-                for _ in range(FRAMES):
-                    t0 = time.perf_counter()
-                    chain()
-                    times.append((time.perf_counter() - t0) * 1e3)
-                res[name] = {"ms_median": statistics.median(times), "ms_min": min(times), "ms_max": max(times)}
+            res = {"solid": timing.wall(solid_chain, FRAMES), "traced_front_end": timing.wall(traced_front_end, FRAMES)}
             res["traced_over_solid"] = res["traced_front_end"]["ms_median"] / res["solid"]["ms_median"]
             key = "%s %dx%d: solid at 1 spp of guides, traced at %d spp" % (sid, W, H, LOOP_SPP)
             doc["loop"][key] = res
-            print(key, json.dumps(res), flush=True)
+            timing.report(key, res)
             for p in P.values():
                 d.free(p)
-    hip.hipEventDestroy(e0)
-    hip.hipEventDestroy(e1)
-    path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "solid_timing.json")
-    with open(path, "w") as f:
-        json.dump(doc, f, indent=1)
-        f.write("\n")
-    print("->", path)
+    timing.write(doc, "solid_timing.json")
 
 
 if __name__ == "__main__":
