@@ -139,6 +139,52 @@ pub struct PtSolidLook {
     pub reflect_type: u32,
 }
 
+// the tone stage (include/ptrace_tone.h): the meter's rectangle and flags, what it counts, pt_meter_exposure's parameters, and
+// pt_ctx_tonemap's - every field of those taken as it stands; pt_tonemap_defaults / pt_meter_exposure_defaults write the defaults out
+pub const PT_METER_SKIP_MISSES: u32 = 1;
+pub const PT_METER_BINS: u32 = 256;
+pub const PT_TONE_CLAMP: u32 = 0;
+pub const PT_TONE_REINHARD: u32 = 1;
+pub const PT_TONE_ACES: u32 = 2;
+pub const PT_TONE_LUMA: u32 = 1;
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct PtMeterParams {
+    pub flags: u32,
+    pub x0: u32,
+    pub y0: u32,
+    pub x1: u32,
+    pub y1: u32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct PtMeterStats {
+    pub pixels: u64,
+    pub dark: u64,
+    pub histogram: [u32; 256],
+    pub max_luminance: f32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct PtMeterExposureParams {
+    pub key: f32,
+    pub low_fraction: f32,
+    pub high_fraction: f32,
+    pub min_exposure: f32,
+    pub max_exposure: f32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct PtTonemapParams {
+    pub curve: u32,
+    pub flags: u32,
+    pub exposure: f32,
+    pub white: f32,
+}
+
 // pt_ctx_present's parameters; all zero = the frame's own size, exposure 1, RGBA8, display order
 #[repr(C)]
 #[derive(Clone, Copy, Default, Debug)]
@@ -860,6 +906,40 @@ extern "C" {
         look: *const PtSolidLook,
         rgb_out: *mut f32,
     ) -> i32;
+}
+
+// include/ptrace_tone.h: the tone stage has a header of its own as well, and so a block of its own here
+extern "C" {
+    // the frame pt_ctx_accumulate holds, resolved without the clamp to [0, 1]; hip_stream as for pt_ctx_render
+    pub fn pt_ctx_accum_hdr(ctx: *mut PtCtx, cfg: *const PtConfig, d_out_rgb: *mut f32, hip_stream: *mut c_void) -> i32;
+    // a luminance histogram of a float frame on the device, and the host's way from it to an exposure
+    pub fn pt_ctx_meter(
+        ctx: *mut PtCtx,
+        width: u32,
+        height: u32,
+        params: *const PtMeterParams,
+        d_rgb: *const f32,
+        d_object_id: *const i32,
+        out: *mut PtMeterStats,
+        hip_stream: *mut c_void,
+    ) -> i32;
+    pub fn pt_meter_bin_host(luminance: f32, bin: *mut i32) -> i32;
+    pub fn pt_meter_exposure_defaults(out: *mut PtMeterExposureParams) -> i32;
+    pub fn pt_meter_exposure(stats: *const PtMeterStats, params: *const PtMeterExposureParams, exposure: *mut f32) -> i32;
+    pub fn pt_meter_exposure_weights(stats: *const PtMeterStats, params: *const PtMeterExposureParams, kept: *mut f64) -> i32;
+    pub fn pt_meter_adapt(current: f32, target: f32, dt: f32, tau: f32, next: *mut f32) -> i32;
+    // exposure and a curve: a float frame to a display-linear float frame in [0, 1]; d_out may be d_rgb
+    pub fn pt_tonemap_defaults(out: *mut PtTonemapParams) -> i32;
+    pub fn pt_ctx_tonemap(
+        ctx: *mut PtCtx,
+        width: u32,
+        height: u32,
+        params: *const PtTonemapParams,
+        d_rgb: *const f32,
+        d_out: *mut f32,
+        hip_stream: *mut c_void,
+    ) -> i32;
+    pub fn pt_tonemap_pixel_host(params: *const PtTonemapParams, rgb: *const f32, out: *mut f32) -> i32;
 }
 
 fn v3(v: Vec3) -> [f32; 3] {

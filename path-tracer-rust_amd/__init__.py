@@ -20,6 +20,8 @@ from .abi import (PT_AOV_MAX_CHAIN, PT_AOV_THROUGH_DELTA, PT_CANCELLED, PT_DENOI
 from .overlay_abi import PT_OVERLAY_GRID, PT_OVERLAY_SKY, pt_overlay_params  # noqa: F401  (include/ptrace_overlay.h)
 from .solid_abi import (PT_SOLID_HEADLIGHT, PT_SOLID_MAX_SHININESS_LOG2, PT_SOLID_REFLECT_SKY, pt_solid_look,  # noqa: F401
                         pt_solid_params)  # (include/ptrace_solid.h)
+from .tone_abi import (PT_METER_BINS, PT_METER_SKIP_MISSES, PT_TONE_ACES, PT_TONE_CLAMP, PT_TONE_LUMA, PT_TONE_REINHARD,  # noqa: F401
+                       pt_meter_exposure_params, pt_meter_params, pt_meter_stats, pt_tonemap_params)  # (include/ptrace_tone.h)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PT_LIB") or os.path.join(_HERE, "libptrace_hip.so")  # PT_LIB: A/B builds when tuning
@@ -251,6 +253,32 @@ class Context:
         _check(lib().pt_ctx_solid(self._h, width, height, C.byref(params) if params is not None else None, _camera(cam), ptr(albedo),
                                   ptr(normal), ptr(depth), ptr(object_id), looks, len(looks) if looks is not None else 0, ptr(out),
                                   C.c_void_p(stream or 0)))
+
+    def accum_hdr(self, out_ptr, width, height, seed=1, band=None, chunks=None, stream=None):
+        """The frame accumulate() holds for these arguments, resolved WITHOUT the clamp to [0, 1] (pt_ctx_accum_hdr): into device
+        memory at out_ptr, laid out as accumulate() lays its output out.  Raises if the context holds another frame or none."""
+        cfg = self._config(width, height, 1, seed, band=band, chunks=chunks)
+        _check(lib().pt_ctx_accum_hdr(self._h, C.byref(cfg), C.c_void_p(out_ptr), C.c_void_p(stream or 0)))
+
+    def meter(self, width, height, rgb, object_id=None, rect=None, skip_misses=False, stream=None):
+        """The luminance histogram of a whole width x height float frame in device memory (pt_ctx_meter): a pt_meter_stats -
+        256 bins, eight per octave from 2^-20, the dark pixels apart, and the largest luminance.  `rgb`: device pointer to
+        pixels * 3 float32; rect=(x0, y0, x1, y1) meters that half-open rectangle only; skip_misses=True leaves out the pixels
+        whose `object_id` (device pointer, pixels int32) is below 0.  meter_exposure() turns the result into an exposure."""
+        x0, y0, x1, y1 = rect if rect else (0, 0, 0, 0)
+        p = pt_meter_params(PT_METER_SKIP_MISSES if skip_misses else 0, x0, y0, x1, y1)
+        out = pt_meter_stats()
+        ptr = lambda q: C.c_void_p(q) if q else None  # noqa: E731
+        _check(lib().pt_ctx_meter(self._h, width, height, C.byref(p), ptr(rgb), ptr(object_id), C.byref(out), C.c_void_p(stream or 0)))
+        return out
+
+    def tonemap(self, width, height, rgb, out, params=None, stream=None):
+        """Exposure and a tone curve on a whole width x height float frame in device memory (pt_ctx_tonemap): `rgb` and `out` are
+        device pointers to pixels * 3 float32 (out may be rgb); the result is display-linear in [0, 1], what overlay() and
+        present() take.  `params`: a pt_tonemap_params (tonemap_defaults() gives one; None = the defaults)."""
+        ptr = lambda q: C.c_void_p(q) if q else None  # noqa: E731
+        _check(lib().pt_ctx_tonemap(self._h, width, height, C.byref(params) if params is not None else None, ptr(rgb), ptr(out),
+                                    C.c_void_p(stream or 0)))
 
     def _reproject(self, entry, params, width, height, cam, frame, history, outs, motion=None, stream=None):
         """The one call of the five reproject methods.  `params`: the entry point's struct, filled - pt_reproject_var_params
@@ -558,6 +586,48 @@ def solid_looks(objects):
     for i, o in enumerate(objects):
         _check(lib().pt_solid_look_of(C.byref(o), C.byref(arr[i])))
     return arr
+
+
+def tonemap_defaults():
+    """pt_ctx_tonemap's defaults written out (pt_tonemap_defaults): the ACES fit, no flags, exposure 1, white 4."""
+    p = pt_tonemap_params()
+    _check(lib().pt_tonemap_defaults(C.byref(p)))
+    return p
+
+
+def tonemap_pixel(rgb, params=None):
+    """pt_ctx_tonemap's arithmetic for one pixel on the host (pt_tonemap_pixel_host): (r, g, b) -> (r, g, b)."""
+    v, o = (C.c_float * 3)(*rgb), (C.c_float * 3)()
+    _check(lib().pt_tonemap_pixel_host(C.byref(params) if params is not None else None, v, o))
+    return tuple(o)
+
+
+def meter_bin(luminance):
+    """pt_ctx_meter's bin of one luminance (pt_meter_bin_host): 0..255, or -1 for a dark pixel."""
+    b = C.c_int32()
+    _check(lib().pt_meter_bin_host(luminance, C.byref(b)))
+    return b.value
+
+
+def meter_exposure_defaults():
+    """pt_meter_exposure's defaults written out: key 0.18, the darkest 5 % and the brightest 2 % dropped, range [2^-8, 2^8]."""
+    p = pt_meter_exposure_params()
+    _check(lib().pt_meter_exposure_defaults(C.byref(p)))
+    return p
+
+
+def meter_exposure(stats, params=None):
+    """The exposure that maps the log-average luminance of a pt_meter_stats (Context.meter) to the key (pt_meter_exposure)."""
+    e = C.c_float()
+    _check(lib().pt_meter_exposure(C.byref(stats), C.byref(params) if params is not None else None, C.byref(e)))
+    return e.value
+
+
+def meter_adapt(current, target, dt, tau):
+    """One step of eye adaptation in log2 exposure from `current` towards `target` over dt with time constant tau (pt_meter_adapt)."""
+    e = C.c_float()
+    _check(lib().pt_meter_adapt(current, target, dt, tau, C.byref(e)))
+    return e.value
 
 
 def present_thresholds():

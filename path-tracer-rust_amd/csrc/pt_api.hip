@@ -25,6 +25,7 @@
 #include "pt_refit.h"
 #include "pt_reproject.h"
 #include "pt_solid.h"
+#include "pt_tone.h"
 #include "pt_upsample.h"
 #include "pt_tile.h"
 
@@ -396,6 +397,9 @@ struct pt_ctx {
     DevBuf<pt_object_motion> rm_table;
     // pt_ctx_solid's scratch, its own too: the call's looks table, 16 B per record, grown on demand
     DevBuf<pt_solid_look> solid_looks;
+    // the tone stage's scratch, its own too: pt_ctx_meter's counters (kMeterWords), pt_ctx_accum_hdr's count per part
+    DevBuf<uint32_t> meter_cnt;
+    DevBuf<uint32_t> hdr_counts;
     // The adaptive calls: the frame kept between calls (pt_ctx_set_scene drops it), and their scratch, kept too and grown on
     // demand: the compact accumulator of a step's tiles, the step's open-tile list, the counters (u64 [0]: the sum of E at the
     // end; u32 [2], [3]: the tiles a step left open / closed; u32 [4]: the list's length; u32 [5..7]: k_tile_select's counts),
@@ -2863,6 +2867,67 @@ int pt_ctx_solid(pt_ctx *c, uint32_t width, uint32_t height, const pt_solid_para
             f.looks = c->solid_looks.p;
         }
         launch_solid(st, f);
+        return PT_OK;
+    });
+}
+
+// ---- the tone stage (ptrace_tone.h)
+int pt_ctx_accum_hdr(pt_ctx *c, const pt_config *cfg, float *d_out_rgb, void *hip_stream) {
+    if (!c || !cfg || !d_out_rgb) return refuse("NULL argument");
+    uint32_t ib = 0, ie = 0;
+    const int rc = check_cfg(cfg, &ib, &ie);
+    if (rc) return rc;
+    if (!c->held.holds(host::accum_key(cfg, ib, ie))) return refuse("cfg does not name the frame this context holds");
+    const HeldFrame &h = c->held;
+    HdrFrame f{h.sums.p, d_out_rgb, h.total, h.part_px, h.cnt[0], nullptr};
+    return run_image_pass(c, hip_stream, [&](hipStream_t st) {
+        if (h.n_parts() > 1u) {
+            // (the counts are the context's own: they outlive the copy, which the call waits for)
+            const int rt = c->hdr_counts.ensure(h.n_parts());
+            if (rt) return rt;
+            const hipError_t e = hipMemcpyAsync(c->hdr_counts.p, h.cnt.data(), (size_t)h.n_parts() * sizeof(uint32_t), hipMemcpyHostToDevice, st);
+            if (e != hipSuccess) {
+                set_error(std::string("uploading the parts' counts: ") + hipGetErrorString(e));
+                return PT_ERR_HIP;
+            }
+            f.counts = c->hdr_counts.p;
+        }
+        launch_hdr(st, f);
+        return PT_OK;
+    });
+}
+
+int pt_ctx_meter(pt_ctx *c, uint32_t width, uint32_t height, const pt_meter_params *params, const float *d_rgb, const int32_t *d_object_id,
+                 pt_meter_stats *out, void *hip_stream) {
+    MeterFrame f;
+    const int rc = host::check_meter(c, width, height, params, d_rgb, d_object_id, out, f);
+    if (rc) return rc;
+    uint32_t counters[kMeterWords];
+    const int rr = run_image_pass(c, hip_stream, [&](hipStream_t st) {
+        const int rt = c->meter_cnt.ensure(kMeterWords);
+        if (rt) return rt;
+        f.counters = c->meter_cnt.p;
+        HIP_TRY(hipMemsetAsync(f.counters, 0, sizeof counters, st));
+        launch_meter(st, f);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(counters, f.counters, sizeof counters, hipMemcpyDeviceToHost, st));
+        return PT_OK;
+    });
+    if (rr) return rr;
+    host::meter_stats_of(counters, out);
+    return PT_OK;
+}
+
+int pt_meter_exposure_defaults(pt_meter_exposure_params *out) { return give_defaults(out, kMeterExposureDefaults); }
+int pt_tonemap_defaults(pt_tonemap_params *out) { return give_defaults(out, kTonemapDefaults); }
+
+int pt_ctx_tonemap(pt_ctx *c, uint32_t width, uint32_t height, const pt_tonemap_params *params, const float *d_rgb, float *d_out,
+                   void *hip_stream) {
+    ToneFrame f;
+    const int rc = host::check_tonemap(c, width, height, params, d_rgb, d_out, f);
+    if (rc) return rc;
+    return run_image_pass(c, hip_stream, [&](hipStream_t st) {
+        launch_tonemap(st, f);
         return PT_OK;
     });
 }

@@ -11,6 +11,7 @@
 #include "pt_refit.h"
 #include "pt_reproject.h"
 #include "pt_solid.h"
+#include "pt_tone.h"
 #include "pt_upsample.h"
 
 #include <algorithm>
@@ -1854,6 +1855,128 @@ int check_solid(const void *ctx, uint32_t width, uint32_t height, const pt_solid
 bool solid_wide(const SolidFrame &f) {
     const uintptr_t all = (uintptr_t)f.albedo | (uintptr_t)f.normal | (uintptr_t)f.depth | (uintptr_t)f.object_id | (uintptr_t)f.out;
     return (all & 15u) == 0u && (uint64_t)f.width * f.height >= kSolidLanePixels;
+}
+
+// ---- the tone stage (ptrace_tone.h, pt_tone.h)
+static bool finite_pos(float v) { return v > 0.0f && v < __builtin_inff(); }
+
+int check_tonemap_params(const pt_tonemap_params *params, ToneFrame &f) {
+    const pt_tonemap_params P = params ? *params : kTonemapDefaults;
+    if (P.curve > PT_TONE_ACES) return refuse("pt_tonemap_params.curve: unknown curve");
+    if (P.flags & ~PT_TONE_LUMA) return refuse("pt_tonemap_params.flags: unknown bits");
+    if (!finite_pos(P.exposure)) return refuse("pt_tonemap_params.exposure is not finite and above 0");
+    if (P.curve == PT_TONE_REINHARD && !finite_pos(P.white)) return refuse("pt_tonemap_params.white is not finite and above 0");
+    f.curve = P.curve;
+    f.luma = (P.flags & PT_TONE_LUMA) != 0u;
+    f.exposure = P.exposure;
+    f.iw2 = P.curve == PT_TONE_REINHARD ? 1.0f / (P.white * P.white) : 0.0f;
+    return PT_OK;
+}
+
+int check_tonemap(const void *ctx, uint32_t width, uint32_t height, const pt_tonemap_params *params, const float *d_rgb, float *d_out,
+                  ToneFrame &f) {
+    f = ToneFrame{};
+    const int rc = check_tonemap_params(params, f);
+    if (rc) return rc;
+    if (!width || !height) return refuse("width and height must be positive");
+    if ((uint64_t)width * height > (1ull << 28)) return refuse("width*height exceeds 2^28");
+    if (!d_rgb) return refuse("d_rgb is NULL");
+    if (!d_out) return refuse("d_out is NULL");
+    if (!ctx) return refuse("ctx is NULL");
+    f.width = width;
+    f.height = height;
+    f.rgb = d_rgb;
+    f.out = d_out;
+    return PT_OK;
+}
+
+int check_meter(const void *ctx, uint32_t width, uint32_t height, const pt_meter_params *params, const float *d_rgb,
+                const int32_t *d_object_id, const pt_meter_stats *out, MeterFrame &f) {
+    pt_meter_params P{};
+    if (params) P = *params;
+    if (P.flags & ~PT_METER_SKIP_MISSES) return refuse("pt_meter_params.flags: unknown bits");
+    if (!width || !height) return refuse("width and height must be positive");
+    if ((uint64_t)width * height > (1ull << 28)) return refuse("width*height exceeds 2^28");
+    if (P.x0 | P.y0 | P.x1 | P.y1) {
+        if (P.x0 >= P.x1 || P.y0 >= P.y1) return refuse("pt_meter_params: the rectangle is empty");
+        if (P.x1 > width || P.y1 > height) return refuse("pt_meter_params: the rectangle leaves the frame");
+    } else {
+        P.x1 = width, P.y1 = height;
+    }
+    if (!d_rgb) return refuse("d_rgb is NULL");
+    if ((P.flags & PT_METER_SKIP_MISSES) && !d_object_id) return refuse("PT_METER_SKIP_MISSES without d_object_id");
+    if (!out) return refuse("out is NULL");
+    if (!ctx) return refuse("ctx is NULL");
+    f = MeterFrame{};
+    f.rgb = d_rgb;
+    f.object_id = (P.flags & PT_METER_SKIP_MISSES) ? d_object_id : nullptr;
+    f.npix = width * height;
+    f.pitch = width;
+    if (P.x0 == 0u && P.x1 == width) {  // whole rows: one run
+        f.first = P.y0 * width;
+        f.span = (P.y1 - P.y0) * width;
+        f.rows = 1u;
+    } else {
+        f.first = P.y0 * width + P.x0;
+        f.span = P.x1 - P.x0;
+        f.rows = P.y1 - P.y0;
+    }
+    f.row_groups = (f.span + 3u) / 4u + 1u;
+    return PT_OK;
+}
+
+int check_meter_exposure(const pt_meter_exposure_params *params, pt_meter_exposure_params &P) {
+    P = params ? *params : kMeterExposureDefaults;
+    if (!finite_pos(P.key)) return refuse("pt_meter_exposure_params.key is not finite and above 0");
+    for (float v : {P.low_fraction, P.high_fraction})
+        if (!(v >= 0.0f && v < 1.0f)) return refuse("pt_meter_exposure_params: a fraction is outside [0, 1)");
+    if (!((double)P.low_fraction + (double)P.high_fraction < 1.0)) return refuse("pt_meter_exposure_params: the fractions leave nothing");
+    if (!finite_pos(P.min_exposure)) return refuse("pt_meter_exposure_params.min_exposure is not finite and above 0");
+    if (!(P.max_exposure >= P.min_exposure && P.max_exposure < __builtin_inff()))
+        return refuse("pt_meter_exposure_params.max_exposure is not finite or below min_exposure");
+    return PT_OK;
+}
+
+void meter_weights(const pt_meter_stats &s, const pt_meter_exposure_params &P, double kept[PT_METER_BINS], double *sum_w, double *sum_wl) {
+    uint64_t N = 0;
+    for (uint32_t b = 0; b < PT_METER_BINS; ++b) N += s.histogram[b];
+    const double n = (double)N, lo = (double)P.low_fraction * n, hi = n - (double)P.high_fraction * n;
+    double sw = 0.0, swl = 0.0;
+    uint64_t c = 0;
+    for (uint32_t b = 0; b < PT_METER_BINS; ++b) {
+        const double below = (double)c, upto = (double)(c + s.histogram[b]);
+        const double w = (upto < hi ? upto : hi) - (below > lo ? below : lo);
+        kept[b] = w > 0.0 ? w : 0.0;
+        sw += kept[b];
+        swl += kept[b] * (-20.0 + ((double)b + 0.5) / 8.0);
+        c += s.histogram[b];
+    }
+    *sum_w = sw;
+    *sum_wl = swl;
+}
+
+bool tone_wide(const ToneFrame &f) {
+    return (((uintptr_t)f.rgb | (uintptr_t)f.out) & 15u) == 0u && (uint64_t)f.width * f.height >= kToneLanePixels;
+}
+
+bool meter_wide(const MeterFrame &f) { return (((uintptr_t)f.rgb | (uintptr_t)f.object_id) & 15u) == 0u; }
+
+bool hdr_wide(const HdrFrame &f) {
+    // the three planes are `total` u64 apart: all 16-byte aligned when the first is and total is even; a lane's four pixels
+    // share one count: there is one part, or no part boundary inside a group of four
+    return (((uintptr_t)f.sums | (uintptr_t)f.out) & 15u) == 0u && (f.total & 1u) == 0u && f.total >= kToneLanePixels &&
+           (!f.counts || f.part_px % kToneLanePixels == 0u);
+}
+
+void meter_stats_of(const uint32_t counters[kMeterWords], pt_meter_stats *out) {
+    memset(out, 0, sizeof *out);
+    out->dark = counters[kMeterDark];
+    out->pixels = out->dark;
+    for (uint32_t b = 0; b < PT_METER_BINS; ++b) {
+        out->histogram[b] = counters[b];
+        out->pixels += counters[b];
+    }
+    memcpy(&out->max_luminance, &counters[kMeterMax], 4);
 }
 
 // ---- pt_ctx_reproject (ptrace.h, pt_reproject.h)

@@ -20,6 +20,7 @@
 #include "../../include/ptrace.h"
 #include "../../include/ptrace_overlay.h"
 #include "../../include/ptrace_solid.h"
+#include "../../include/ptrace_tone.h"
 
 // --aov-chain [K]: the guides every pass of this program reads come from pt_ctx_render_aov_ex with PT_AOV_THROUGH_DELTA
 static bool g_aov_chain = false;
@@ -78,6 +79,74 @@ static int draw_solid(pt_ctx *ctx, const pt_config *frame, const pt_camera *cam,
     return pt_ctx_solid(ctx, frame->width, frame->height, &sp, cam, d_albedo, d_normal, d_depth, d_id, looks.data(), n_objs, d_out, nullptr);
 }
 
+// --hdr / --tonemap / --auto-exposure: the tone stage (ptrace_tone.h) between the frame and the cues of a --preview.  Any of them
+// turns the frame's render into pt_ctx_accumulate + pt_ctx_accum_hdr: the frame that follows is the radiance, not clamped.
+struct ToneOptions {
+    std::string hdr;                 // --hdr FILE.pfm: the unclamped frame
+    bool curve_on = false;           // --tonemap was given
+    uint32_t curve = PT_TONE_ACES;
+    bool luma = false;               // --tone-luma
+    float white = 4.0f;              // --white W
+    bool auto_on = false;            // --auto-exposure [KEY]
+    float key = 0.0f;                // 0: pt_meter_exposure_defaults'
+    bool any() const { return !hdr.empty() || curve_on || auto_on; }
+};
+static ToneOptions g_tone;
+// --orbit adapts the metered exposure over a fixed frame interval (the files do not depend on the machine's speed)
+static const float kOrbitFrameSeconds = 1.0f / 30.0f, kAdaptSeconds = 0.5f;
+
+// The frame cfg names, rendered through the held sums and resolved without the clamp into d_out (fresh: the held frame is dropped first)
+static int render_hdr(pt_ctx *ctx, const pt_config *cfg, float *d_out, bool fresh, pt_progress_fn cb, pt_stats *st) {
+    int rc = fresh ? pt_ctx_accum_reset(ctx) : PT_OK;
+    if (!rc) rc = pt_ctx_accumulate(ctx, cfg, d_out, nullptr, nullptr, cb, nullptr, st);
+    if (!rc) rc = pt_ctx_accum_hdr(ctx, cfg, d_out, nullptr);
+    return rc;
+}
+
+// meter -> pt_meter_exposure (-> pt_meter_adapt from *adapted, which it updates; NULL or 0: no adaptation) -> pt_ctx_tonemap in
+// place.  d_id: the ids of the frame when misses are to be skipped, else NULL.  `exposure`: --exposure's (0: none given); what
+// pt_ctx_present still has to apply comes back in *present_exposure (0 once a curve has applied it).
+static int tone_frame(pt_ctx *ctx, uint32_t w, uint32_t h, float *d_rgb, const int32_t *d_id, float exposure, float *adapted,
+                      float *present_exposure) {
+    float e = exposure > 0.0f ? exposure : 1.0f;
+    int rc = PT_OK;
+    if (g_tone.auto_on) {
+        pt_meter_params mp;
+        memset(&mp, 0, sizeof mp);
+        mp.flags = d_id ? PT_METER_SKIP_MISSES : 0u;
+        pt_meter_stats ms;
+        pt_meter_exposure_params ep;
+        rc = pt_ctx_meter(ctx, w, h, &mp, d_rgb, d_id, &ms, nullptr);
+        if (!rc) rc = pt_meter_exposure_defaults(&ep);
+        if (!rc && g_tone.key > 0.0f) ep.key = g_tone.key;
+        if (!rc) rc = pt_meter_exposure(&ms, &ep, &e);
+        if (!rc && adapted) {
+            if (*adapted > 0.0f) rc = pt_meter_adapt(*adapted, e, kOrbitFrameSeconds, kAdaptSeconds, &e);
+            *adapted = e;
+        }
+        if (rc) return rc;
+    }
+    *present_exposure = g_tone.auto_on ? e : exposure;
+    if (g_tone.curve_on) {
+        const pt_tonemap_params tp = {g_tone.curve, g_tone.luma ? PT_TONE_LUMA : 0u, e, g_tone.white};
+        rc = pt_ctx_tonemap(ctx, w, h, &tp, d_rgb, d_rgb, nullptr);
+        *present_exposure = 0.0f;
+    }
+    return rc;
+}
+
+// --hdr: the device frame as it stands, through pt_write_pfm
+static int write_hdr(int dev, const float *d_rgb, uint32_t w, uint32_t h, const std::string &path) {
+    std::vector<float> img((size_t)w * h * 3);
+    int rc = pt_device_download(dev, img.data(), d_rgb, img.size() * sizeof(float));
+    if (!rc) rc = pt_write_pfm(path.c_str(), img.data(), w, h, 3);
+    if (rc)
+        fprintf(stderr, "cannot write %s (%d): %s\n", path.c_str(), rc, pt_last_error());
+    else
+        printf("wrote %s\n", path.c_str());
+    return rc;
+}
+
 static void usage() {
     fprintf(stderr,
             "usage: ptrace <samplesPerPixel> <y-resolution> <scene id|index> [--width W] [--backend wavefront|megakernel]\n"
@@ -87,6 +156,7 @@ static void usage() {
             "              [--adaptive X [--tile N] [--spp-map FILE.pfm] [--error-map FILE.pfm] [--adaptive-checkpoint FILE]]\n"
             "              [--denoise-var [N]] [--preview FILE.ppm [--preview-size WxH] [--exposure E]]\n"
             "              [--select I[,J...]] [--outline-radius R] [--sky] [--grid] [--solid [N]]\n"
+            "              [--hdr FILE.pfm] [--tonemap clamp|reinhard|aces [--tone-luma] [--white W]] [--auto-exposure [KEY]]\n"
             "              [--trace-scale K [--retrace]]\n"
             "              [--orbit N [--orbit-step DEG] [--move I:DX,DY,DZ [--move-history [F]]] [--boost K]]\n"
             "  --checkpoint FILE: continue from the samples FILE holds (if it exists), render up to <samplesPerPixel> in all and\n"
@@ -126,6 +196,15 @@ static void usage() {
             "           frame pixels (1..8, default 2) around the objects listed (at most 16 indices), a sky gradient where the first\n"
             "           hit missed, the ground grid in y = 0 where no object hides it - pt_overlay_defaults for the frame's camera\n"
             "           otherwise; the single frame takes a 1-sample pt_ctx_render_aov for the object ids and depths\n"
+            "  --hdr FILE.pfm, --tonemap CURVE, --auto-exposure [KEY]: with --preview (the single frame or every frame of --orbit): the\n"
+            "           tone stage.  Any of them renders the frame through pt_ctx_accumulate + pt_ctx_accum_hdr: radiance, not clamped\n"
+            "           to [0, 1].  --hdr writes that frame (under --orbit FILE-000.pfm, ...: the frame shown, before the curve).\n"
+            "           --tonemap applies pt_ctx_tonemap's curve before the cues and pt_ctx_present (--tone-luma: on the luminance;\n"
+            "           --white W: Reinhard's white point, default 4); --exposure E then scales the radiance before the curve.\n"
+            "           --auto-exposure meters the frame (pt_ctx_meter, pt_meter_exposure, KEY default 0.18) in place of --exposure;\n"
+            "           under --orbit the exposure follows through pt_meter_adapt at 30 frames per second, half a second's time\n"
+            "           constant; with --sky or --solid the pixels that missed are not metered.  Not with --trace-scale, --adaptive\n"
+            "           or --boost.\n"
             "  --solid [N]: with --preview (the single frame or every frame of --orbit): the frame shown is not the traced one but the\n"
             "           objects lit and solid (pt_ctx_solid: ambient, diffuse and a highlight from a light at the lens, times the\n"
             "           albedo, plus the objects' emission; mirrors show the sky) from an N-sample pt_ctx_render_aov (default 1), the\n"
@@ -376,10 +455,12 @@ static int render_on_context(const pt_config *cfg, pt_scene *sc, const std::stri
             if (!noise->map.empty() && write_noise_map(dev, ctx, cfg, noise->map)) rc = kCliExit;
         }
     } else if (!rc) {
-        rc = file.empty() ? pt_ctx_render(ctx, cfg, d_out, nullptr, nullptr, progress, nullptr, st)
-                          : pt_ctx_accumulate(ctx, cfg, d_out, nullptr, nullptr, progress, nullptr, st);
+        rc = file.empty() && !g_tone.any() ? pt_ctx_render(ctx, cfg, d_out, nullptr, nullptr, progress, nullptr, st)
+                                           : pt_ctx_accumulate(ctx, cfg, d_out, nullptr, nullptr, progress, nullptr, st);
     }
     if (!rc) rc = pt_device_download(dev, img.data(), d_out, bytes);
+    // the tone stage takes the radiance: the frame kept on the device is the held sums without the clamp (img keeps the clamped one)
+    if (!rc && keep && g_tone.any()) rc = pt_ctx_accum_hdr(ctx, cfg, (float *)d_out, nullptr);
     if (!rc && !file.empty()) {
         rc = pt_ctx_accum_save(ctx, file.c_str());
         if (rc) fprintf(stderr, "cannot save checkpoint %s: %s\n", file.c_str(), pt_last_error());
@@ -522,6 +603,9 @@ static int write_preview(const pt_config *frame, const DeviceFrame &df, const st
         float *d_albedo = (float *)d_guides, *d_normal = d_albedo + npix * 3, *d_depth = d_normal + npix * 3;
         int32_t *d_id = (int32_t *)(d_depth + npix);
         if (!rc) rc = draw_solid(df.ctx, frame, cam, objs, n_objs, d_albedo, d_normal, d_depth, d_id, (float *)df.d_out);
+        // (the meter leaves the background out: misses are skipped)
+        if (!rc && (g_tone.curve_on || g_tone.auto_on))
+            rc = tone_frame(df.ctx, frame->width, frame->height, (float *)df.d_out, d_id, exposure, nullptr, &pp.exposure);
         if (!rc && g_overlay.on) rc = draw_overlay(df.ctx, frame->width, frame->height, cam, (float *)df.d_out, d_id, d_depth);
     } else if (!rc && g_overlay.on) {
         // nothing has produced ids and depths for this frame: one sample of first-hit guides, then the cues in place
@@ -532,7 +616,13 @@ static int write_preview(const pt_config *frame, const DeviceFrame &df, const st
         float *d_depth = (float *)d_guides;
         int32_t *d_id = (int32_t *)(d_depth + npix);
         if (!rc) rc = pt_ctx_render_aov(df.ctx, &one, nullptr, nullptr, d_depth, d_id, nullptr);
+        // the curve before the cues; with --sky the meter leaves out the pixels the sky will fill
+        if (!rc && (g_tone.curve_on || g_tone.auto_on))
+            rc = tone_frame(df.ctx, frame->width, frame->height, (float *)df.d_out, (g_overlay.flags & PT_OVERLAY_SKY) ? d_id : nullptr, exposure,
+                            nullptr, &pp.exposure);
         if (!rc) rc = draw_overlay(df.ctx, frame->width, frame->height, cam, (float *)df.d_out, d_id, d_depth);
+    } else if (!rc && (g_tone.curve_on || g_tone.auto_on)) {
+        rc = tone_frame(df.ctx, frame->width, frame->height, (float *)df.d_out, nullptr, exposure, nullptr, &pp.exposure);
     }
     if (d_guides) pt_device_free(df.dev, d_guides);
     if (!rc) rc = pt_ctx_present(df.ctx, frame->width, frame->height, &pp, (const float *)df.d_out, (uint8_t *)d_px, nullptr);
@@ -682,6 +772,8 @@ static int render_orbit(const pt_config *cfg, pt_scene *sc, uint32_t frames, dou
     }
     OrbitSide *cur = &side[0], *hist = &side[1];
     pt_camera hist_cam = cam0;
+    float adapted = 0.0f;  // --auto-exposure: the exposure of the frame before (0: none yet)
+    const bool tone = g_tone.curve_on || g_tone.auto_on;
     for (uint32_t k = 0; k < frames && !rc; ++k) {
         const pt_camera cam = orbit_camera(cam0, (double)k * step);
         // a frame in which an object moved passes no history on: the reprojection follows the camera, not the objects - unless
@@ -703,6 +795,7 @@ static int render_orbit(const pt_config *cfg, pt_scene *sc, uint32_t frames, dou
         if (g_solid) {
             // --solid: the guides, the lit solid view of them, the cues, the display pixels - no path is traced
             if (!rc) rc = draw_solid(ctx, cfg, &cam, objs, n_objs, d_albedo, cur->normal, cur->depth, cur->id, d_shown);
+            if (!rc && tone) rc = tone_frame(ctx, w, h, d_shown, cur->id, exposure, &adapted, &pp.exposure);
             if (!rc && g_overlay.on) rc = draw_overlay(ctx, w, h, &cam, d_shown, cur->id, cur->depth);
             if (!rc) rc = pt_ctx_present(ctx, w, h, &pp, d_shown, (uint8_t *)d_px, nullptr);
             if (!rc) rc = pt_device_download(dev, px.data(), d_px, px.size());
@@ -718,7 +811,10 @@ static int render_orbit(const pt_config *cfg, pt_scene *sc, uint32_t frames, dou
             printf("wrote %s\n", path.c_str());
             continue;
         }
-        if (!rc) rc = pt_ctx_render(ctx, cfg, cur->color, nullptr, nullptr, nullptr, nullptr, &st);
+        // with a tone option the frame is the radiance: the camera moved, so the held sums start over
+        if (!rc)
+            rc = g_tone.any() ? render_hdr(ctx, cfg, cur->color, true, nullptr, &st)
+                              : pt_ctx_render(ctx, cfg, cur->color, nullptr, nullptr, nullptr, nullptr, &st);
         if (!rc) rc = render_guides(ctx, cfg, d_albedo, cur->normal, cur->depth, cur->id);
         pt_reproject_var_params rp;
         memset(&rp, 0, sizeof rp);
@@ -769,6 +865,14 @@ static int render_orbit(const pt_config *cfg, pt_scene *sc, uint32_t frames, dou
         memset(&dp, 0, sizeof dp);
         dp.sigma_var = 2.0f;
         if (!rc) rc = pt_ctx_denoise_var(ctx, w, h, &dp, cur->color, d_error, d_albedo, cur->normal, cur->depth, d_shown, nullptr);
+        if (!rc && !g_tone.hdr.empty()) {
+            char hname[32];
+            snprintf(hname, sizeof hname, "-%03u.pfm", k);
+            const std::string &hp = g_tone.hdr;
+            if (write_hdr(dev, d_shown, w, h, (hp.size() > 4 && hp.substr(hp.size() - 4) == ".pfm" ? hp.substr(0, hp.size() - 4) : hp) + hname)) rc = PT_ERR_IO;
+        }
+        if (!rc && tone)
+            rc = tone_frame(ctx, w, h, d_shown, (g_overlay.flags & PT_OVERLAY_SKY) ? cur->id : nullptr, exposure, &adapted, &pp.exposure);
         if (!rc && g_overlay.on) rc = draw_overlay(ctx, w, h, &cam, d_shown, cur->id, cur->depth);
         if (!rc) rc = pt_ctx_present(ctx, w, h, &pp, d_shown, (uint8_t *)d_px, nullptr);
         if (!rc) rc = pt_device_download(dev, px.data(), d_px, px.size());
@@ -913,6 +1017,41 @@ int main(int argc, char **argv) {
             if (e == v || *e || !(exposure > 0.0f) || !(exposure < INFINITY)) {
                 fprintf(stderr, "--exposure needs a positive finite number\n");
                 return 1;
+            }
+        }
+        else if (a == "--hdr") {
+            g_tone.hdr = next();
+            if (g_tone.hdr.empty()) {
+                fprintf(stderr, "--hdr needs FILE.pfm\n");
+                return 1;
+            }
+        } else if (a == "--tonemap") {
+            const std::string c = next();
+            if (c != "clamp" && c != "reinhard" && c != "aces") {
+                fprintf(stderr, "--tonemap takes clamp, reinhard or aces\n");
+                return 1;
+            }
+            g_tone.curve_on = true;
+            g_tone.curve = c == "clamp" ? PT_TONE_CLAMP : c == "reinhard" ? PT_TONE_REINHARD : PT_TONE_ACES;
+        } else if (a == "--tone-luma") {
+            g_tone.luma = true;
+        } else if (a == "--white") {
+            const char *v = next();
+            char *e = nullptr;
+            g_tone.white = strtof(v, &e);
+            if (e == v || *e || !(g_tone.white > 0.0f) || !(g_tone.white < INFINITY)) {
+                fprintf(stderr, "--white needs a positive finite number\n");
+                return 1;
+            }
+        } else if (a == "--auto-exposure") {
+            g_tone.auto_on = true;
+            if (i + 1 < argc && argv[i + 1][0] != '-') {
+                char *e = nullptr;
+                g_tone.key = strtof(argv[++i], &e);
+                if (*e || !(g_tone.key > 0.0f) || !(g_tone.key < INFINITY)) {
+                    fprintf(stderr, "--auto-exposure takes a positive finite KEY (or none: 0.18)\n");
+                    return 1;
+                }
             }
         }
         else if (a == "--aov") {
@@ -1149,6 +1288,23 @@ int main(int argc, char **argv) {
         fprintf(stderr, "--solid goes with --preview FILE.ppm\n");
         return 1;
     }
+    if ((g_tone.any() || g_tone.luma) && preview.empty()) {
+        fprintf(stderr, "--hdr, --tonemap, --tone-luma and --auto-exposure go with --preview FILE.ppm\n");
+        return 1;
+    }
+    if (g_tone.luma && !g_tone.curve_on) {
+        fprintf(stderr, "--tone-luma goes with --tonemap\n");
+        return 1;
+    }
+    if (g_tone.any() && (trace_scale || is_adaptive || boost)) {
+        fprintf(stderr, "--hdr, --tonemap and --auto-exposure cannot be combined with %s: the frame is not the one pt_ctx_accumulate holds\n",
+                trace_scale ? "--trace-scale" : boost ? "--boost" : "--adaptive");
+        return 1;
+    }
+    if (!g_tone.hdr.empty() && g_solid && orbit_frames) {
+        fprintf(stderr, "--hdr cannot be combined with --solid under --orbit: no path is traced\n");
+        return 1;
+    }
     if (g_solid && g_aov_chain) {
         fprintf(stderr, "--solid cannot be combined with --aov-chain: the chain's ids and depths are the reflected object's\n");
         return 1;
@@ -1286,6 +1442,10 @@ int main(int argc, char **argv) {
         if (symlink(path.c_str(), "latest.ppm") != 0)
             printf("Could not create symlink to latest image. You can find it at %s\n", path.c_str());
         printf("wrote %s\n", path.c_str());
+    }
+    if (!g_tone.hdr.empty() && write_hdr(df.dev, (const float *)df.d_out, width, res_y, g_tone.hdr)) {
+        release();
+        return 3;
     }
     if (aov_spp && write_aovs(&cfg, aov_spp, sc, img, stem)) {
         release();

@@ -26,6 +26,7 @@
 #include "../csrc/pt_present.h"
 #include "../csrc/pt_reproject.h"
 #include "../csrc/pt_solid.h"
+#include "../csrc/pt_tone.h"
 #include "../csrc/pt_upsample.h"
 
 namespace {
@@ -1337,6 +1338,87 @@ int pt_solid_pixel_host(const pt_camera *cam, uint32_t width, uint32_t height, c
     float v[3];
     pt::solid_pixel(f, idx, object_id, depth, albedo ? albedo : clay, normal, look ? *look : none, v);
     memcpy(rgb_out, v, sizeof v);
+    return PT_OK;
+}
+
+// ---- the tone stage's host side (include/ptrace_tone.h)
+int pt_meter_bin_host(float Y, int32_t *bin) {
+    if (!bin) {
+        pt::set_error("bin is NULL");
+        return PT_ERR_INVALID;
+    }
+    const uint32_t s = pt::meter_slot(Y);
+    *bin = s == pt::kMeterDark ? -1 : (int32_t)s;
+    return PT_OK;
+}
+
+int pt_meter_exposure_weights(const pt_meter_stats *stats, const pt_meter_exposure_params *params, double kept[PT_METER_BINS]) {
+    if (!stats || !kept) {
+        pt::set_error("NULL argument");
+        return PT_ERR_INVALID;
+    }
+    pt_meter_exposure_params P;
+    const int rc = pt::host::check_meter_exposure(params, P);
+    if (rc) return rc;
+    double sw, swl;
+    pt::host::meter_weights(*stats, P, kept, &sw, &swl);
+    return PT_OK;
+}
+
+int pt_meter_exposure(const pt_meter_stats *stats, const pt_meter_exposure_params *params, float *exposure) {
+    if (!stats || !exposure) {
+        pt::set_error("NULL argument");
+        return PT_ERR_INVALID;
+    }
+    pt_meter_exposure_params P;
+    const int rc = pt::host::check_meter_exposure(params, P);
+    if (rc) return rc;
+    double kept[PT_METER_BINS], sw, swl;
+    pt::host::meter_weights(*stats, P, kept, &sw, &swl);
+    if (!(sw > 0.0)) {
+        *exposure = 1.0f;
+        return PT_OK;
+    }
+    double e = (double)P.key / exp2(swl / sw);
+    e = e < (double)P.min_exposure ? (double)P.min_exposure : e;
+    e = e > (double)P.max_exposure ? (double)P.max_exposure : e;
+    *exposure = (float)e;
+    return PT_OK;
+}
+
+int pt_meter_adapt(float current, float target, float dt, float tau, float *next) {
+    if (!next) {
+        pt::set_error("next is NULL");
+        return PT_ERR_INVALID;
+    }
+    if (!(current > 0.0f && current < INFINITY && target > 0.0f && target < INFINITY)) {
+        pt::set_error("current and target must be finite and above 0");
+        return PT_ERR_INVALID;
+    }
+    if (!(dt >= 0.0f && dt < INFINITY && tau >= 0.0f && tau < INFINITY)) {
+        pt::set_error("dt and tau must be finite and not negative");
+        return PT_ERR_INVALID;
+    }
+    if (tau == 0.0f) {
+        *next = target;
+        return PT_OK;
+    }
+    const double step = (log2((double)target) - log2((double)current)) * (1.0 - exp(-(double)dt / (double)tau));
+    *next = (float)((double)current * exp2(step));
+    return PT_OK;
+}
+
+int pt_tonemap_pixel_host(const pt_tonemap_params *params, const float rgb[3], float out[3]) {
+    pt::ToneFrame f = {};
+    const int rc = pt::host::check_tonemap_params(params, f);
+    if (rc) return rc;
+    if (!rgb || !out) {
+        pt::set_error("NULL argument");
+        return PT_ERR_INVALID;
+    }
+    float v[3];
+    pt::tone_pixel(f, rgb, v);
+    memcpy(out, v, sizeof v);
     return PT_OK;
 }
 
