@@ -185,6 +185,27 @@ pub struct PtTonemapParams {
     pub white: f32,
 }
 
+// the firefly stage (include/ptrace_despike.h): pt_ctx_despike's parameters, every field taken as it stands
+// (pt_despike_defaults writes the defaults out), and what it counts
+pub const PT_DESPIKE_SAME_OBJECT: u32 = 1;
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct PtDespikeParams {
+    pub radius: u32,
+    pub rank: u32,
+    pub flags: u32,
+    pub threshold: f32,
+    pub floor: f32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct PtDespikeStats {
+    pub pixels: u64,
+    pub spikes: u64,
+    pub nonfinite: u64,
+}
+
 // pt_ctx_present's parameters; all zero = the frame's own size, exposure 1, RGBA8, display order
 #[repr(C)]
 #[derive(Clone, Copy, Default, Debug)]
@@ -940,6 +961,34 @@ extern "C" {
         hip_stream: *mut c_void,
     ) -> i32;
     pub fn pt_tonemap_pixel_host(params: *const PtTonemapParams, rgb: *const f32, out: *mut f32) -> i32;
+}
+
+// include/ptrace_despike.h: the firefly stage has a header of its own as well, and so a block of its own here
+extern "C" {
+    pub fn pt_despike_defaults(out: *mut PtDespikeParams) -> i32;
+    // fireflies of a float frame clipped in front of the denoiser; d_out may not be d_rgb; hip_stream as for pt_ctx_render
+    pub fn pt_ctx_despike(
+        ctx: *mut PtCtx,
+        width: u32,
+        height: u32,
+        params: *const PtDespikeParams,
+        d_rgb: *const f32,
+        d_object_id: *const i32,
+        d_out: *mut f32,
+        d_mask: *mut u8,
+        out: *mut PtDespikeStats,
+        hip_stream: *mut c_void,
+    ) -> i32;
+    pub fn pt_despike_frame_host(
+        width: u32,
+        height: u32,
+        params: *const PtDespikeParams,
+        rgb: *const f32,
+        object_id: *const i32,
+        out_rgb: *mut f32,
+        mask: *mut u8,
+        out: *mut PtDespikeStats,
+    ) -> i32;
 }
 
 fn v3(v: Vec3) -> [f32; 3] {

@@ -22,6 +22,7 @@ from .solid_abi import (PT_SOLID_HEADLIGHT, PT_SOLID_MAX_SHININESS_LOG2, PT_SOLI
                         pt_solid_params)  # (include/ptrace_solid.h)
 from .tone_abi import (PT_METER_BINS, PT_METER_SKIP_MISSES, PT_TONE_ACES, PT_TONE_CLAMP, PT_TONE_LUMA, PT_TONE_REINHARD,  # noqa: F401
                        pt_meter_exposure_params, pt_meter_params, pt_meter_stats, pt_tonemap_params)  # (include/ptrace_tone.h)
+from .despike_abi import PT_DESPIKE_SAME_OBJECT, pt_despike_params, pt_despike_stats  # noqa: F401  (include/ptrace_despike.h)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PT_LIB") or os.path.join(_HERE, "libptrace_hip.so")  # PT_LIB: A/B builds when tuning
@@ -279,6 +280,20 @@ class Context:
         ptr = lambda q: C.c_void_p(q) if q else None  # noqa: E731
         _check(lib().pt_ctx_tonemap(self._h, width, height, C.byref(params) if params is not None else None, ptr(rgb), ptr(out),
                                     C.c_void_p(stream or 0)))
+
+    def despike(self, width, height, rgb, out, params=None, object_id=None, mask=None, stats=True, stream=None):
+        """Fireflies of a whole width x height float frame in device memory clipped (pt_ctx_despike), in front of denoise(): a
+        pixel brighter than threshold * (the rank-th largest luminance of its neighbours) + floor is scaled down to that limit,
+        a non-finite one written as 0.  `rgb` and `out` are device pointers to pixels * 3 float32 and may not be the same;
+        `params`: a pt_despike_params (despike_defaults() gives one; None = the defaults); `object_id` (device pointer, pixels
+        int32) is read with PT_DESPIKE_SAME_OBJECT in params.flags; `mask` (device pointer, pixels bytes) receives 0 / 1 (spike) /
+        2 (non-finite), the plane render_masked() reads.  Returns a pt_despike_stats, or None with stats=False (nothing is then
+        counted or downloaded)."""
+        st = pt_despike_stats() if stats else None
+        ptr = lambda q: C.c_void_p(q) if q else None  # noqa: E731
+        _check(lib().pt_ctx_despike(self._h, width, height, C.byref(params) if params is not None else None, ptr(rgb), ptr(object_id),
+                                    ptr(out), ptr(mask), C.byref(st) if stats else None, C.c_void_p(stream or 0)))
+        return st
 
     def _reproject(self, entry, params, width, height, cam, frame, history, outs, motion=None, stream=None):
         """The one call of the five reproject methods.  `params`: the entry point's struct, filled - pt_reproject_var_params
@@ -586,6 +601,26 @@ def solid_looks(objects):
     for i, o in enumerate(objects):
         _check(lib().pt_solid_look_of(C.byref(o), C.byref(arr[i])))
     return arr
+
+
+def despike_defaults():
+    """pt_ctx_despike's defaults written out (pt_despike_defaults): radius 1, rank 3, no flags, threshold 2, floor 0.25."""
+    p = pt_despike_params()
+    _check(lib().pt_despike_defaults(C.byref(p)))
+    return p
+
+
+def despike_frame(rgb, width, height, params=None, object_id=None):
+    """pt_ctx_despike's arithmetic for a whole frame on the host (pt_despike_frame_host): `rgb` a float32 array of pixels * 3
+    values, `object_id` an int32 array of pixels.  Returns (out, mask, pt_despike_stats) with out and mask numpy arrays."""
+    import numpy as np
+    src = np.ascontiguousarray(rgb, dtype=np.float32).reshape(-1)
+    ids = np.ascontiguousarray(object_id, dtype=np.int32).reshape(-1) if object_id is not None else None
+    out, mask, st = np.zeros_like(src), np.zeros(width * height, dtype=np.uint8), pt_despike_stats()
+    _check(lib().pt_despike_frame_host(width, height, C.byref(params) if params is not None else None, src.ctypes.data_as(C.c_void_p),
+                                       ids.ctypes.data_as(C.c_void_p) if ids is not None else None, out.ctypes.data_as(C.c_void_p),
+                                       mask.ctypes.data_as(C.c_void_p), C.byref(st)))
+    return out.reshape(-1, 3), mask, st
 
 
 def tonemap_defaults():

@@ -301,9 +301,10 @@ def declare(cdll, partial=False):
     from . import overlay_abi  # include/ptrace_overlay.h: a header of its own has a table of its own (imported here: it imports this module)
     from . import solid_abi  # include/ptrace_solid.h: likewise
     from . import tone_abi  # include/ptrace_tone.h: likewise
+    from . import despike_abi  # include/ptrace_despike.h: likewise
 
     missing = []
-    for table in (SIGNATURES, overlay_abi.SIGNATURES, solid_abi.SIGNATURES, tone_abi.SIGNATURES, DEBUG_SIGNATURES):
+    for table in (SIGNATURES, overlay_abi.SIGNATURES, solid_abi.SIGNATURES, tone_abi.SIGNATURES, despike_abi.SIGNATURES, DEBUG_SIGNATURES):
         for name, (restype, argtypes) in table.items():
             try:
                 fn = getattr(cdll, name)

@@ -15,6 +15,7 @@
 #include "pt_accum.h"
 #include "pt_aov.h"
 #include "pt_denoise.h"
+#include "pt_despike.h"
 #include "pt_host.h"
 #include "pt_kernels.h"
 #include "pt_masked.h"
@@ -400,6 +401,8 @@ struct pt_ctx {
     // the tone stage's scratch, its own too: pt_ctx_meter's counters (kMeterWords), pt_ctx_accum_hdr's count per part
     DevBuf<uint32_t> meter_cnt;
     DevBuf<uint32_t> hdr_counts;
+    // pt_ctx_despike's scratch, its own too: the call's two counters, 16 B
+    DevBuf<unsigned long long> despike_cnt;
     // The adaptive calls: the frame kept between calls (pt_ctx_set_scene drops it), and their scratch, kept too and grown on
     // demand: the compact accumulator of a step's tiles, the step's open-tile list, the counters (u64 [0]: the sum of E at the
     // end; u32 [2], [3]: the tiles a step left open / closed; u32 [4]: the list's length; u32 [5..7]: k_tile_select's counts),
@@ -2930,6 +2933,32 @@ int pt_ctx_tonemap(pt_ctx *c, uint32_t width, uint32_t height, const pt_tonemap_
         launch_tonemap(st, f);
         return PT_OK;
     });
+}
+
+// ---- the firefly stage (ptrace_despike.h)
+int pt_despike_defaults(pt_despike_params *out) { return give_defaults(out, kDespikeDefaults); }
+
+int pt_ctx_despike(pt_ctx *c, uint32_t width, uint32_t height, const pt_despike_params *params, const float *d_rgb,
+                   const int32_t *d_object_id, float *d_out, uint8_t *d_mask, pt_despike_stats *out, void *hip_stream) {
+    DespikeFrame f;
+    const int rc = host::check_despike(c, width, height, params, d_rgb, d_object_id, d_out, d_mask, f);
+    if (rc) return rc;
+    unsigned long long counters[2] = {0ull, 0ull};
+    const int rr = run_image_pass(c, hip_stream, [&](hipStream_t st) {
+        if (out) {  // without it nothing is cleared, counted or downloaded
+            const int rt = c->despike_cnt.ensure(2);
+            if (rt) return rt;
+            f.counters = c->despike_cnt.p;
+            HIP_TRY(hipMemsetAsync(f.counters, 0, sizeof counters, st));
+        }
+        launch_despike(st, f);
+        HIP_TRY(hipGetLastError());
+        if (out) HIP_TRY(hipMemcpyAsync(counters, f.counters, sizeof counters, hipMemcpyDeviceToHost, st));
+        return PT_OK;
+    });
+    if (rr) return rr;
+    if (out) *out = pt_despike_stats{(uint64_t)width * height, counters[0], counters[1]};
+    return PT_OK;
 }
 
 int pt_reproject_defaults(pt_reproject_params *out) {

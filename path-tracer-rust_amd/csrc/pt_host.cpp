@@ -3,6 +3,7 @@
 // for the triangle edges — see pt_device.h).
 #include "pt_host.h"
 #include "pt_denoise.h"
+#include "pt_despike.h"
 #include "pt_layout.h"
 #include "pt_masked.h"
 #include "pt_overlay.h"
@@ -1977,6 +1978,77 @@ void meter_stats_of(const uint32_t counters[kMeterWords], pt_meter_stats *out) {
         out->pixels += counters[b];
     }
     memcpy(&out->max_luminance, &counters[kMeterMax], 4);
+}
+
+// ---- the firefly stage (ptrace_despike.h, pt_despike.h)
+int check_despike(const void *ctx, uint32_t width, uint32_t height, const pt_despike_params *params, const float *d_rgb,
+                  const int32_t *d_object_id, float *d_out, uint8_t *d_mask, DespikeFrame &f) {
+    const pt_despike_params P = params ? *params : kDespikeDefaults;
+    if (P.radius < 1u || P.radius > kDespikeMaxRadius) return refuse("pt_despike_params.radius is not 1 or 2");
+    if (P.rank < 1u || P.rank > kDespikeMaxRank || P.rank > (2u * P.radius + 1u) * (2u * P.radius + 1u) - 1u)
+        return refuse("pt_despike_params.rank is not in 1..4");
+    if (P.flags & ~PT_DESPIKE_SAME_OBJECT) return refuse("pt_despike_params.flags: unknown bits");
+    if (!(P.threshold >= 1.0f && P.threshold < __builtin_inff())) return refuse("pt_despike_params.threshold is not finite and at least 1");
+    if (!(P.floor >= 0.0f && P.floor < __builtin_inff())) return refuse("pt_despike_params.floor is not finite and at least 0");
+    if (!width || !height) return refuse("width and height must be positive");
+    if ((uint64_t)width * height > (1ull << 28)) return refuse("width*height exceeds 2^28");
+    if (!d_rgb) return refuse("d_rgb is NULL");
+    if (!d_out) return refuse("d_out is NULL");
+    if (d_out == d_rgb) return refuse("d_out is d_rgb: the pass gathers and cannot run in place");
+    if ((P.flags & PT_DESPIKE_SAME_OBJECT) && !d_object_id) return refuse("PT_DESPIKE_SAME_OBJECT without d_object_id");
+    if (!ctx) return refuse("ctx is NULL");
+    f = DespikeFrame{};
+    f.width = width;
+    f.height = height;
+    f.rgb = d_rgb;
+    f.object_id = (P.flags & PT_DESPIKE_SAME_OBJECT) ? d_object_id : nullptr;
+    f.out = d_out;
+    f.mask = d_mask;
+    f.radius = P.radius;
+    f.rank = P.rank;
+    f.threshold = P.threshold;
+    f.floor = P.floor;
+    return PT_OK;
+}
+
+template <int RANK>
+static void despike_frame_rank(const DespikeFrame &f, unsigned long long counts[2]) {
+    const int64_t W = f.width, H = f.height, R = f.radius;
+    for (int64_t r = 0; r < H; ++r) {
+        for (int64_t x = 0; x < W; ++x) {
+            const size_t idx = (size_t)(r * W + x);
+            const float *v = f.rgb + idx * 3u;
+            float o[3] = {0.0f, 0.0f, 0.0f};
+            uint32_t m = kDespikeNonfinite;
+            if (!despike_nonfinite(v[0], v[1], v[2])) {
+                float t[RANK];
+                for (int k = 0; k < RANK; ++k) t[k] = kDespikeNone;
+                for (int64_t qr = r - R; qr <= r + R; ++qr) {
+                    for (int64_t qx = x - R; qx <= x + R; ++qx) {
+                        if ((qr == r && qx == x) || qx < 0 || qx >= W || qr < 0 || qr >= H) continue;
+                        const size_t q = (size_t)(qr * W + qx);
+                        if (f.object_id && f.object_id[q] != f.object_id[idx]) continue;
+                        despike_push<RANK>(t, despike_y(f.rgb[q * 3u], f.rgb[q * 3u + 1u], f.rgb[q * 3u + 2u]));
+                    }
+                }
+                m = despike_verdict(f.threshold, f.floor, t[RANK - 1], v, o);
+            }
+            memcpy(f.out + idx * 3u, o, sizeof o);
+            if (f.mask) f.mask[idx] = (uint8_t)m;
+            if (m == kDespikeSpike) ++counts[0];
+            if (m == kDespikeNonfinite) ++counts[1];
+        }
+    }
+}
+
+void despike_frame(const DespikeFrame &f, unsigned long long counts[2]) {
+    counts[0] = counts[1] = 0ull;
+    switch (f.rank) {
+        case 1u: return despike_frame_rank<1>(f, counts);
+        case 2u: return despike_frame_rank<2>(f, counts);
+        case 3u: return despike_frame_rank<3>(f, counts);
+        default: return despike_frame_rank<4>(f, counts);
+    }
 }
 
 // ---- pt_ctx_reproject (ptrace.h, pt_reproject.h)

@@ -21,6 +21,7 @@
 #include "../../include/ptrace_overlay.h"
 #include "../../include/ptrace_solid.h"
 #include "../../include/ptrace_tone.h"
+#include "../../include/ptrace_despike.h"
 
 // --aov-chain [K]: the guides every pass of this program reads come from pt_ctx_render_aov_ex with PT_AOV_THROUGH_DELTA
 static bool g_aov_chain = false;
@@ -89,7 +90,9 @@ struct ToneOptions {
     float white = 4.0f;              // --white W
     bool auto_on = false;            // --auto-exposure [KEY]
     float key = 0.0f;                // 0: pt_meter_exposure_defaults'
-    bool any() const { return !hdr.empty() || curve_on || auto_on; }
+    bool despike_on = false;         // --despike [T]
+    float despike_t = 0.0f;          // 0: pt_despike_defaults'
+    bool any() const { return !hdr.empty() || curve_on || auto_on || despike_on; }
 };
 static ToneOptions g_tone;
 // --orbit adapts the metered exposure over a fixed frame interval (the files do not depend on the machine's speed)
@@ -100,6 +103,29 @@ static int render_hdr(pt_ctx *ctx, const pt_config *cfg, float *d_out, bool fres
     int rc = fresh ? pt_ctx_accum_reset(ctx) : PT_OK;
     if (!rc) rc = pt_ctx_accumulate(ctx, cfg, d_out, nullptr, nullptr, cb, nullptr, st);
     if (!rc) rc = pt_ctx_accum_hdr(ctx, cfg, d_out, nullptr);
+    return rc;
+}
+
+// --despike [T]: pt_ctx_despike at its defaults (T: the threshold) from the radiance in d_rgb into d_out, in front of every filter
+// and of the meter.  Without PT_DESPIKE_SAME_OBJECT, also under --orbit where the ids are at hand: the defaults are the study's
+// choice (profiles/despike_study.json), and with the flag that setting is the grid's worst.  The line on stderr
+// is printed at once, or with later == true by despike_report() - the single frame's, once the progress line has been closed.
+static pt_despike_stats g_despike_stats;
+static bool g_despike_pending = false;
+static void despike_report() {
+    fprintf(stderr, "despike: %llu spikes, %llu non-finite of %llu pixels\n", (unsigned long long)g_despike_stats.spikes,
+            (unsigned long long)g_despike_stats.nonfinite, (unsigned long long)g_despike_stats.pixels);
+    g_despike_pending = false;
+}
+static int despike_frame(pt_ctx *ctx, uint32_t w, uint32_t h, const float *d_rgb, float *d_out, bool later) {
+    pt_despike_params dp;
+    pt_despike_stats &ds = g_despike_stats;
+    int rc = pt_despike_defaults(&dp);
+    if (rc) return rc;
+    if (g_tone.despike_t > 0.0f) dp.threshold = g_tone.despike_t;
+    rc = pt_ctx_despike(ctx, w, h, &dp, d_rgb, nullptr, d_out, nullptr, &ds, nullptr);
+    g_despike_pending = !rc && later;
+    if (!rc && !later) despike_report();
     return rc;
 }
 
@@ -157,6 +183,7 @@ static void usage() {
             "              [--denoise-var [N]] [--preview FILE.ppm [--preview-size WxH] [--exposure E]]\n"
             "              [--select I[,J...]] [--outline-radius R] [--sky] [--grid] [--solid [N]]\n"
             "              [--hdr FILE.pfm] [--tonemap clamp|reinhard|aces [--tone-luma] [--white W]] [--auto-exposure [KEY]]\n"
+            "              [--despike [T]]\n"
             "              [--trace-scale K [--retrace]]\n"
             "              [--orbit N [--orbit-step DEG] [--move I:DX,DY,DZ [--move-history [F]]] [--boost K]]\n"
             "  --checkpoint FILE: continue from the samples FILE holds (if it exists), render up to <samplesPerPixel> in all and\n"
@@ -205,6 +232,11 @@ static void usage() {
             "           under --orbit the exposure follows through pt_meter_adapt at 30 frames per second, half a second's time\n"
             "           constant; with --sky or --solid the pixels that missed are not metered.  Not with --trace-scale, --adaptive\n"
             "           or --boost.\n"
+            "  --despike [T]: with --preview (the single frame or every frame of --orbit): the radiance frame (as for --hdr) goes through\n"
+            "           pt_ctx_despike at its defaults, T its threshold (default 2), before --hdr writes it and before --denoise,\n"
+            "           --denoise-var, --auto-exposure and --tonemap see it: a pixel brighter than T times its third brightest\n"
+            "           neighbour plus 0.25 is scaled down to that limit.  One line on stderr per frame:\n"
+            "           despike: S spikes, N non-finite of P pixels.\n"
             "  --solid [N]: with --preview (the single frame or every frame of --orbit): the frame shown is not the traced one but the\n"
             "           objects lit and solid (pt_ctx_solid: ambient, diffuse and a highlight from a light at the lens, times the\n"
             "           albedo, plus the objects' emission; mirrors show the sky) from an N-sample pt_ctx_render_aov (default 1), the\n"
@@ -460,7 +492,14 @@ static int render_on_context(const pt_config *cfg, pt_scene *sc, const std::stri
     }
     if (!rc) rc = pt_device_download(dev, img.data(), d_out, bytes);
     // the tone stage takes the radiance: the frame kept on the device is the held sums without the clamp (img keeps the clamped one)
-    if (!rc && keep && g_tone.any()) rc = pt_ctx_accum_hdr(ctx, cfg, (float *)d_out, nullptr);
+    if (!rc && keep && g_tone.any() && !g_tone.despike_on) rc = pt_ctx_accum_hdr(ctx, cfg, (float *)d_out, nullptr);
+    if (!rc && keep && g_tone.despike_on) {  // the pass gathers: the radiance goes to a frame of its own, the clipped one to d_out
+        void *d_hdr = nullptr;
+        rc = pt_device_malloc(dev, bytes, &d_hdr);
+        if (!rc) rc = pt_ctx_accum_hdr(ctx, cfg, (float *)d_hdr, nullptr);
+        if (!rc) rc = despike_frame(ctx, cfg->width, cfg->height, (const float *)d_hdr, (float *)d_out, true);
+        if (d_hdr) pt_device_free(dev, d_hdr);
+    }
     if (!rc && !file.empty()) {
         rc = pt_ctx_accum_save(ctx, file.c_str());
         if (rc) fprintf(stderr, "cannot save checkpoint %s: %s\n", file.c_str(), pt_last_error());
@@ -812,10 +851,12 @@ static int render_orbit(const pt_config *cfg, pt_scene *sc, uint32_t frames, dou
             continue;
         }
         // with a tone option the frame is the radiance: the camera moved, so the held sums start over
+        // (--despike: into d_shown, which nothing uses before the filter, and from there clipped into the frame)
         if (!rc)
-            rc = g_tone.any() ? render_hdr(ctx, cfg, cur->color, true, nullptr, &st)
+            rc = g_tone.any() ? render_hdr(ctx, cfg, g_tone.despike_on ? d_shown : cur->color, true, nullptr, &st)
                               : pt_ctx_render(ctx, cfg, cur->color, nullptr, nullptr, nullptr, nullptr, &st);
         if (!rc) rc = render_guides(ctx, cfg, d_albedo, cur->normal, cur->depth, cur->id);
+        if (!rc && g_tone.despike_on) rc = despike_frame(ctx, w, h, d_shown, cur->color, false);
         pt_reproject_var_params rp;
         memset(&rp, 0, sizeof rp);
         rp.weight = cfg->spp;
@@ -1050,6 +1091,17 @@ int main(int argc, char **argv) {
                 g_tone.key = strtof(argv[++i], &e);
                 if (*e || !(g_tone.key > 0.0f) || !(g_tone.key < INFINITY)) {
                     fprintf(stderr, "--auto-exposure takes a positive finite KEY (or none: 0.18)\n");
+                    return 1;
+                }
+            }
+        }
+        else if (a == "--despike") {
+            g_tone.despike_on = true;
+            if (i + 1 < argc && argv[i + 1][0] != '-') {
+                char *e = nullptr;
+                g_tone.despike_t = strtof(argv[++i], &e);
+                if (*e || !(g_tone.despike_t >= 1.0f) || !(g_tone.despike_t < INFINITY)) {
+                    fprintf(stderr, "--despike takes a finite threshold T >= 1 (or none: 2)\n");
                     return 1;
                 }
             }
@@ -1289,7 +1341,7 @@ int main(int argc, char **argv) {
         return 1;
     }
     if ((g_tone.any() || g_tone.luma) && preview.empty()) {
-        fprintf(stderr, "--hdr, --tonemap, --tone-luma and --auto-exposure go with --preview FILE.ppm\n");
+        fprintf(stderr, "--hdr, --tonemap, --tone-luma, --auto-exposure and --despike go with --preview FILE.ppm\n");
         return 1;
     }
     if (g_tone.luma && !g_tone.curve_on) {
@@ -1297,12 +1349,16 @@ int main(int argc, char **argv) {
         return 1;
     }
     if (g_tone.any() && (trace_scale || is_adaptive || boost)) {
-        fprintf(stderr, "--hdr, --tonemap and --auto-exposure cannot be combined with %s: the frame is not the one pt_ctx_accumulate holds\n",
+        fprintf(stderr, "--hdr, --tonemap, --auto-exposure and --despike cannot be combined with %s: the frame is not the one pt_ctx_accumulate holds\n",
                 trace_scale ? "--trace-scale" : boost ? "--boost" : "--adaptive");
         return 1;
     }
     if (!g_tone.hdr.empty() && g_solid && orbit_frames) {
         fprintf(stderr, "--hdr cannot be combined with --solid under --orbit: no path is traced\n");
+        return 1;
+    }
+    if (g_tone.despike_on && g_solid) {
+        fprintf(stderr, "--despike cannot be combined with --solid: the frame shown is not a traced one\n");
         return 1;
     }
     if (g_solid && g_aov_chain) {
@@ -1414,6 +1470,7 @@ int main(int argc, char **argv) {
         return 1;
     }
     fprintf(stderr, "\n");
+    if (g_despike_pending) despike_report();
     if (rc) {
         fprintf(stderr, "render failed (%d): %s\n", rc, pt_last_error());
         release();

@@ -23,6 +23,7 @@
 #include "../../include/ptrace.h"
 #include "../csrc/pt_host.h"
 #include "../csrc/pt_overlay.h"
+#include "../csrc/pt_despike.h"
 #include "../csrc/pt_present.h"
 #include "../csrc/pt_reproject.h"
 #include "../csrc/pt_solid.h"
@@ -1419,6 +1420,19 @@ int pt_tonemap_pixel_host(const pt_tonemap_params *params, const float rgb[3], f
     float v[3];
     pt::tone_pixel(f, rgb, v);
     memcpy(out, v, sizeof v);
+    return PT_OK;
+}
+
+// ---- the firefly stage's host side (include/ptrace_despike.h)
+int pt_despike_frame_host(uint32_t width, uint32_t height, const pt_despike_params *params, const float *rgb, const int32_t *object_id,
+                          float *out_rgb, uint8_t *mask, pt_despike_stats *out) {
+    pt::DespikeFrame f;
+    // (no context to refuse: the frame itself stands in for one)
+    const int rc = pt::host::check_despike(&f, width, height, params, rgb, object_id, out_rgb, mask, f);
+    if (rc) return rc;
+    unsigned long long counts[2];
+    pt::host::despike_frame(f, counts);
+    if (out) *out = pt_despike_stats{(uint64_t)width * height, counts[0], counts[1]};
     return PT_OK;
 }
 
